@@ -12,10 +12,15 @@ for N>1 the kept samples of each chunk are all-gathered over RCCL (sample collec
 (child processes, one per GPU; the parent never touches the GPU) and relays rank 0's line.
 Under `python -m torch.distributed.run ... bench.py --gpus N` it is one of the N ranks.
 
-Timing: W untimed warm-up steps, a clock warm-up, then the timed region -- EXACTLY K steps
-between barrier + synchronize on both sides, max over ranks -- is repeated (>= 5 times,
-about a second in total) and the MEDIAN repetition is reported, so a short region (the
-driver passes --steps 20: 3 ms) is not dominated by clock ramp and first-launch effects.
+Timing: W untimed warm-up steps, an untimed clock warm-up of about 0.3 s on a throwaway copy of
+the state (it leaves the timed path's state and RNG offsets alone), then ONE timed region of
+EXACTLY K steps between barrier + synchronize on both sides, max over ranks.  `ms_per_step` =
+that region / K.  The timed path therefore computes the same thing for the same arguments.
+
+--dump-outputs DIR: after the timed region, rank 0 writes what the last Engine.step call of
+that region returned -- the state (position, momentum, logdensity, logdensity_grad) and the kept
+samples of its chunk -- as DIR/<name>.npy (float32), at most 64 MB in all: over that, every
+[..., d] array keeps the same fixed, seeded sample of parameter columns.
 
 Prints ONE JSON line on rank 0.  `value` = particles x steps / wall seconds over all ranks.
 The default run adds BASELINE configs[2..4] (B3, B4, B5) as bounded secondary legs inside the same line.
@@ -68,6 +73,8 @@ WORKLOADS = {
 }
 # bounded secondary legs of the default run: (workload, steps per repetition, warm-up steps)
 SECONDARY = (('B3', 10, 3), ('B4', 2, 1), ('B5', 10, 2))
+DUMP_BUDGET_BYTES = 64 * 10**6 - 2**16     # 64 MB in all, .npy headers included
+DUMP_SEED = 0
 
 
 def grad_flops_per_particle(F, hs, N):
@@ -149,6 +156,31 @@ def cpu_baseline(spec_o, prob, oracle, seconds_target=15.0, logpost_and_grad=Non
                       f'{el:.1f} s' + note}
 
 
+def dump_outputs(out_dir, arrays, d, budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+    """Writes {name: ndarray} as out_dir/<name>.npy in float32.  Over `budget` bytes, every array whose last axis is the
+    parameter axis (length d) keeps the same fixed, seeded, sorted sample of parameter columns, as many as fit."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    wide = [k for k, v in arrays.items() if v.ndim >= 2 and v.shape[-1] == d]
+    cols = None
+    if sum(v.nbytes for v in arrays.values()) > budget:
+        rest = sum(v.nbytes for k, v in arrays.items() if k not in wide)
+        rows = sum(arrays[k].size // d for k in wide)
+        k_cols = max(1, min(d, (budget - rest) // (rows * 4)))
+        cols = np.sort(np.random.default_rng(seed).choice(d, size=k_cols, replace=False))
+    shapes = {}
+    for name, v in arrays.items():
+        if cols is not None and name in wide:
+            v = np.ascontiguousarray(v[..., cols])
+        np.save(out_dir / f'{name}.npy', v)
+        shapes[name] = list(v.shape)
+    return {'dir': str(out_dir), 'dtype': 'float32', 'shapes': shapes,
+            'param_columns': None if cols is None else
+            f'{len(cols)} of {d}: sorted numpy.random.default_rng({seed}).choice({d}, {len(cols)}, replace=False)'}
+
+
 # ----------------------------------------------------------------------------------------------
 # N > 1 without a launcher: the parent starts one child per GPU and never initialises the GPU itself
 # ----------------------------------------------------------------------------------------------
@@ -224,22 +256,26 @@ class Leg:
         self.L = torch.from_numpy(prob['L'][lo:hi]).to(dev)
         self.state = self.eng.init(torch.from_numpy(prob['theta0'][lo:hi]), seed=1234, particle_ids=self.ids)
         self.offset = 0
+        self.last_samples = None
 
     def run(self, n_steps, state=None, collect=True):
-        """n_steps steps in chunks of CHUNK; kept samples of every chunk are all-gathered (N > 1)."""
+        """n_steps steps in chunks of CHUNK; kept samples of every chunk are all-gathered (N > 1).  Only a run on the
+        leg's own state advances its RNG step offset and records the last chunk's samples."""
         torch, dist = self.torch, self.dist
         own = state is None
         state = self.state if own else state
-        pending, done = [], 0
+        pending, done, last = [], 0, None
         while done < n_steps:
             c = min(CHUNK, n_steps - done)
             state, _, samples = self.eng.step(state, self.eps, self.L, n_steps=c, seed=1234, step_offset=self.offset + done,
                                               n_thinning=N_THINNING, particle_ids=self.ids, want_info=False, inplace=True)
+            last = samples
             if collect and dist is not None and samples is not None:
                 if self.gather_cpu:                 # single-device rehearsal under gloo: stage through the host
                     loc = samples.cpu()
                     out = torch.empty((self.world * loc.shape[0],) + tuple(loc.shape[1:]), dtype=loc.dtype)
                     dist.all_gather_into_tensor(out, loc)
+                    last = out
                 else:
                     out = torch.empty((self.world * samples.shape[0],) + tuple(samples.shape[1:]), dtype=samples.dtype, device=self.dev)
                     # default: the gather is ordered on the compute stream (no RCCL kernel competes with a grad launch that
@@ -247,12 +283,13 @@ class Leg:
                     w = dist.all_gather_into_tensor(out, samples, async_op=self.async_gather)
                     if self.async_gather:
                         pending.append((w, out, samples))
+                    last = out
             done += c
         for w, _, _ in pending:
             w.wait()
-        self.offset += n_steps
         if own:
-            self.state = state
+            self.state, self.last_samples = state, last
+            self.offset += n_steps
         return state
 
     def barrier(self):
@@ -275,7 +312,30 @@ class Leg:
             el = float(t.item())
         return el
 
+    def clock_warmup(self, seconds=0.3, max_steps=20000):
+        """Untimed steps on a throwaway copy of the state until about `seconds` have passed (1, 2, 4, ... steps per call):
+        the clocks ramp up without touching the timed path's state or RNG offsets.  Returns the number of steps."""
+        from mile_amd.engine import IntegratorState
+        scratch = IntegratorState(*(t.clone() for t in self.state))
+        n, total, t0 = 1, 0, time.perf_counter()
+        while total < max_steps and time.perf_counter() - t0 < seconds:
+            self.run(n, scratch, collect=False)
+            self.torch.cuda.synchronize()
+            total += n
+            n = min(2 * n, CHUNK)
+        del scratch
+        return total
+
+    def measure_exact(self, steps, warmup):
+        """The headline protocol: `warmup` untimed steps, a clock warm-up off the timed path, then ONE timed region of
+        exactly `steps` steps (seconds, max over ranks)."""
+        self.run(warmup)
+        self.barrier()
+        n_clock = self.clock_warmup()
+        return self.timed(steps), n_clock
+
     def measure(self, steps, warmup, budget_s=1.0, min_reps=5, max_reps=200):
+        """The secondary legs' protocol: the K-step region repeated, median reported."""
         self.run(warmup)
         self.barrier()
         first = self.timed(steps)                                   # also the estimate that sizes the repetitions
@@ -391,9 +451,14 @@ def main():
     ap.add_argument('--force-dist', action='store_true', help='init the process group even for 1 rank (rehearsal)')
     ap.add_argument('--rehearse-one-gpu', action='store_true',
                     help='all ranks share cuda:0 and talk over gloo (rehearsal of the N-rank control flow on a 1-GPU box)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step of the timed path returned as DIR/<name>.npy '
+                         '(float32, at most 64 MB in all)')
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
 
     # ---- N > 1 and no launcher environment: become the launcher (before anything touches the GPU) ----
     if args.gpus > 1 and 'RANK' not in os.environ:
@@ -438,9 +503,14 @@ def main():
         print(f'bench.py: rank {rank}/{world} on {dev} ({dist.get_backend()})', file=sys.stderr)
 
     leg = Leg(args.workload, args, dist, rank, world, dev, gather_cpu=args.rehearse_one_gpu)
-    tm = leg.measure(args.steps, args.warmup)
-    el = tm['median']
+    el, n_clock = leg.measure_exact(args.steps, args.warmup)
     finite = bool(torch.isfinite(leg.state.position).all().item())
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        arrays = {name: t.detach().cpu().numpy() for name, t in leg.state._asdict().items()}
+        if leg.last_samples is not None:
+            arrays['samples'] = leg.last_samples.detach().cpu().numpy()
+        dumped = dump_outputs(args.dump_outputs, arrays, leg.state.position.shape[-1])
 
     roof = None
     if rank == 0 and not args.no_kernel_timing:
@@ -490,15 +560,15 @@ def main():
                                           + ('(async, overlapping the next chunk)' if args.async_gather else '(ordered on the compute stream)'))),
                        'collective_backend': None if dist is None else dist.get_backend(),
                        'finite': finite},
-            'timing': {'repetitions': tm['reps'], 'reported': 'median repetition of the K-step timed region',
-                       'ms_per_step_min': round(tm['min'] / args.steps * 1e3, 5),
-                       'ms_per_step_max': round(tm['max'] / args.steps * 1e3, 5),
-                       'ms_per_step_first': round(tm['first'] / args.steps * 1e3, 5)},
+            'timing': {'repetitions': 1, 'reported': 'one timed region of exactly K steps',
+                       'timed_steps': args.steps, 'seconds': round(el, 6), 'clock_warmup_steps_off_path': n_clock},
             'roofline': roof,
             'cpu_baseline': cpu,
         }
         if secondary is not None:
             out['secondary'] = secondary
+        if dumped is not None:
+            out['dump_outputs'] = dumped
         os.write(json_fd, (json.dumps(out) + '\n').encode())
     if dist is not None:
         dist.barrier()

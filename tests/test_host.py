@@ -127,10 +127,14 @@ def test_config_accepts_reference_schema_and_rejects_unknown_keys(tmp_path):
     del d['data']['path']
     with pytest.raises(ConfigError, match='missing required'):
         Config.from_dict(d)
-    ref = Path('/root/reference/experiments/replicate_uci/mclmc.yaml')
-    if ref.exists():                                    # the reference's own YAML parses unchanged
-        r = Config.from_file(ref)
-        assert r.n_chains == 12 and r.model.hidden_structure == [16, 16, 2]
+    # the reference's stock experiment, restated value for value in the repository (only saving_dir / experiment_name
+    # differ), parses unchanged
+    r = Config.from_file(ROOT / 'experiments' / 'mclmc_airfoil_stock.yaml')
+    assert r.n_chains == 12 and r.model.hidden_structure == [16, 16, 2]
+    rs = r.training.sampler
+    assert (rs.warmup_steps, rs.n_samples, rs.n_thinning, rs.desired_energy_var_start, rs.desired_energy_var_end) == \
+        (50000, 10000, 10, 0.5, 0.1)
+    assert r.training.warmstart.include and r.rng == 4
     from mile_amd.kernels import KERNELS, WARMUP_KERNELS
     assert s.kernel is KERNELS['mclmc'] and WARMUP_KERNELS == {}
 
@@ -482,6 +486,7 @@ def _trainer_worker(rank, ws, port, tmp):
     from mile_amd import distributed as md
     from mile_amd.config import Config
     from mile_amd.trainer import BDETrainer
+    md.init_process_group('gloo')            # host-side control flow: gloo even where a GPU is visible (the trainer reuses the group)
     cfg = Config.from_file(ROOT / 'experiments' / 'mclmc_airfoil_b1.yaml').replace(saving_dir=str(tmp), logging=False)
     names = []
     for _ in range(2):                       # the second construction finds the directory and renames the experiment
@@ -517,6 +522,7 @@ def _empty_rank_worker(rank, ws, port, tmp):
     from mile_amd import distributed as md
     from mile_amd import trainer as T
     from mile_amd.config import Config
+    md.init_process_group('gloo')            # host-side control flow: gloo even where a GPU is visible (the trainer reuses the group)
     cfg = Config.from_file(ROOT / 'experiments' / 'mclmc_airfoil_b1.yaml').replace(saving_dir=str(tmp), logging=False)
     smp = dataclasses.replace(cfg.training.sampler, n_chains=1)
     cfg = cfg.replace(training=dataclasses.replace(cfg.training, sampler=smp,
@@ -620,6 +626,36 @@ def test_bench_workloads_name_every_baseline_config():
     assert bench.grad_flops_per_particle(5, (64, 64, 64, 2), 1052) == 1052 * (6 * (5 * 64 + 64 * 64 * 2 + 64 * 2) - 2 * 5 * 64)
     m1, m2, md = 32 * 32 * 75 * 6, 12 * 12 * 150 * 16, 576 * 120 + 120 * 84 + 84 * 10
     assert bench.lenet_grad_flops_per_particle(3, 32, 32, 10, 4000) == 4000 * (6 * (m1 + m2 + md) - 2 * m1)
+
+
+def test_bench_dump_outputs_within_budget_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per returned array; under the budget every array is written whole, over it every
+    [..., d] array keeps the same seeded column sample (identical from run to run) and the files stay within the budget."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', ROOT / 'bench.py')
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    E, d = 8, 1000
+    arrays = {'position': rng.standard_normal((E, d)), 'logdensity': rng.standard_normal(E),
+              'samples': rng.standard_normal((2, E, d)).astype(np.float32)}
+    m = bench.dump_outputs(tmp_path / 'whole', arrays, d)
+    assert m['param_columns'] is None
+    for name, a in arrays.items():
+        got = np.load(tmp_path / 'whole' / f'{name}.npy')
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    budget = 40_000
+    for run in ('a', 'b'):
+        m = bench.dump_outputs(tmp_path / run, arrays, d, budget=budget)
+        assert m['param_columns'] is not None
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) <= budget + 3 * 128   # + .npy headers
+    k = np.load(tmp_path / 'a' / 'position.npy').shape[1]
+    assert 0 < k < d and np.load(tmp_path / 'a' / 'samples.npy').shape == (2, E, k)
+    assert np.array_equal(np.load(tmp_path / 'a' / 'logdensity.npy'), arrays['logdensity'].astype(np.float32))
+    cols = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(d, k, replace=False))
+    for name in ('position', 'samples'):
+        a, b = np.load(tmp_path / 'a' / f'{name}.npy'), np.load(tmp_path / 'b' / f'{name}.npy')
+        assert np.array_equal(a, b) and np.array_equal(a, arrays[name][..., cols].astype(np.float32))
 
 
 def test_airfoil_table_loads_with_reference_split():
