@@ -1,8 +1,8 @@
 /*
- * mile_hip.h -- C ABI of the MI355X-native MCLMC ensemble sampler (libmile_hip.so).
+ * mile_hip.h -- C ABI of the MI355X-native MCLMC / NUTS ensemble sampler (libmile_hip.so).
  *
- * This is the drop-in boundary for ONE path of zhiyuan-yang/MILE: the MCLMC
- * integrator step over an ensemble of BNN-parameter particles with the
+ * This is the drop-in boundary for ONE path of zhiyuan-yang/MILE: the MCLMC and
+ * NUTS integrator steps over an ensemble of BNN-parameter particles with the
  * per-particle full-batch grad-log-posterior of the FCN MLP.  Every entry point
  * names the reference interface it replaces (paths relative to the reference
  * repository root).  The reference binds that path through Python callables
@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MILE_ABI_VERSION 4
+#define MILE_ABI_VERSION 5
 #define MILE_MAX_LAYERS 16
 
 typedef enum mile_status {
@@ -179,6 +179,48 @@ typedef struct mile_optim_args {
   float *out_nll;                /* [E] batch-mean negative log-likelihood at the parameters BEFORE the update, or NULL */
 } mile_optim_args;
 
+/* Arguments of n_steps NUTS steps == blackjax.nuts(logdensity_fn, step_size, inverse_mass_matrix, max_num_doublings,
+ * divergence_threshold).step (blackjax 1.2.2 nuts.build_kernel with integrators.velocity_verlet and
+ * metrics.default_metric of a diagonal inverse mass matrix) run n_steps times (src/training/sampling.py:140-178 with
+ * sampler.name 'nuts').  All chains build their trees in lockstep: one grad launch per leapfrog round.
+ * Random draws of step i (global step index step_offset + i): momentum normals, Philox stage 3 (same quad layout as the
+ * MCLMC noise); uniforms, Philox stage 4, counter word 0 = slot with M = max_num_doublings:
+ *   slot j in [0, M): direction of doubling j (forward when u < 0.5); slot M + j: progressive_biased_sampling of doubling j;
+ *   slot 2M + n: progressive_uniform_sampling of the n-th leapfrog leaf of the step (n = 0, 1, ...; the first leaf of a
+ *   subtree draws none).  Explicit draws use the same slots. */
+typedef struct mile_nuts_args {
+  const float *step_size;            /* [E] (ignored by mile_nuts_warmup: the adaptation state's) */
+  const float *inverse_mass_matrix;  /* [E, d] diagonal (ignored by mile_nuts_warmup) */
+  int32_t max_num_doublings;         /* 1..12, <= the value given to mile_nuts_reserve; blackjax default 10 */
+  float divergence_threshold;        /* blackjax default 1000: a leaf with energy - initial energy above it diverges */
+  const float *momentum_noise;       /* [n_steps, E, d] N(0,1) draws (parity mode) or NULL */
+  const float *uniforms;             /* [n_steps, E, 2 M + 2^M] U(0,1) draws by slot (parity mode) or NULL */
+  uint64_t seed;                     /* counter RNG when the explicit draws are NULL */
+  const int32_t *particle_ids;       /* [E] GLOBAL chain ids keying the RNG streams, or NULL => 0..E-1 */
+  int64_t step_offset;               /* index of the first step: RNG counter and thinning predicate */
+  int32_t n_steps;
+  int32_t n_thinning;                /* keep position when (step_offset+i) % n_thinning == 0; <=0: keep none */
+  float *out_samples;                /* [n_kept, E, d] kept positions in step order, or NULL */
+  float *out_info;                   /* [n_steps, E, 6] NUTSInfo (num_integration_steps, acceptance_rate,
+                                        num_trajectory_expansions, is_divergent, energy, is_turning) or NULL */
+  int64_t *out_stats;                /* HOST [2] or NULL: leapfrog rounds launched and host syncs, ADDED to */
+} mile_nuts_args;
+
+/* Window adaptation state (blackjax 1.2.2 adaptation.window_adaptation.base with a diagonal mass matrix), one per chain,
+ * caller-owned device memory updated in place by mile_nuts_warmup.  Start: step_size = initial_step_size,
+ * inverse_mass_matrix = 1, da = (log eps0, 0, 1, 0, log(10 eps0)), welford = 0, welford_count = 0.  After the last
+ * warm-up step the tuned step size is exp(da[:, 1]) (window_adaptation final). */
+typedef struct mile_nuts_adapt_args {
+  float *step_size;                  /* [E] in/out: exp(log_step_size), the step size of the next step */
+  float *inverse_mass_matrix;        /* [E, d] in/out */
+  float *da;                         /* [E, 5] in/out: log_step_size, log_step_size_avg, step, avg_error, mu */
+  float *welford;                    /* [E, 2, d] in/out: mean, m2 of the positions in the current slow window */
+  float *welford_count;              /* [E] in/out */
+  const int32_t *schedule;           /* HOST [n_steps, 2]: (stage, is_middle_window_end) of build_schedule, from the
+                                        caller's schedule position of the first step; stage 1 = slow window */
+  float target_acceptance_rate;      /* 0.8 */
+} mile_nuts_adapt_args;
+
 typedef struct mile_sampler mile_sampler;
 
 const char *mile_last_error(void);
@@ -251,6 +293,20 @@ int32_t mile_tune(mile_sampler *s, mile_state *state, const mile_tune_args *args
  * pointers of a TEST set (independent of mile_set_data); out [S, N] = log p(y_n | x_n, theta_s). */
 int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, int32_t S, const float *X, const void *y,
                               int64_t N, float *out, void *stream);
+
+/* Size the NUTS trajectory buffers (ends, momentum sums, proposals, [E, max_num_doublings, d] U-turn checkpoints) for
+ * ensembles of up to E chains, and the grad workspace as mile_reserve.  Allocation happens here, never in a launch. */
+int32_t mile_nuts_reserve(mile_sampler *s, int32_t E, int32_t max_num_doublings);
+
+/* Replaces: the scan of sampler.step(rng_key, state) with sampler = blackjax.nuts(...) (src/training/sampling.py:140-178,
+ * 200-210).  state->position / logdensity / logdensity_grad (HMCState; momentum is not used) advance in place.
+ * Synchronises `stream` once per doubling ("how many chains go on"); never per leapfrog. */
+int32_t mile_nuts_step(mile_sampler *s, mile_state *state, const mile_nuts_args *a, void *stream);
+
+/* Replaces: the lax.scan of one_step in custom_window_adaptation.run (src/training/warmup.py:89-140): n_steps NUTS steps
+ * with the adaptation state's step size and inverse mass matrix, each followed by one on-device adaptation update. */
+int32_t mile_nuts_warmup(mile_sampler *s, mile_state *state, const mile_nuts_args *a, const mile_nuts_adapt_args *w,
+                         void *stream);
 
 /* Counter-RNG words/normals exactly as the step kernels draw them (test hook). out [E, d]. */
 int32_t mile_debug_noise(mile_sampler *s, uint64_t seed, const int32_t *particle_ids, int32_t E,

@@ -7,7 +7,7 @@ from pathlib import Path
 from mile_amd._build import LIB_PATH
 
 MILE_MAX_LAYERS = 16
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 ACTIVATION_IDS = {'relu': 0, 'tanh': 1, 'sigmoid': 2}
 TASK_IDS = {'regr': 0, 'regression': 0, 'classification': 1, 'class': 1}
@@ -85,6 +85,23 @@ class OptimArgsC(C.Structure):
 
 OPTIMIZER_IDS = {'sgd': 0, 'adam': 1, 'adamw': 2}
 
+
+class NutsArgsC(C.Structure):
+    _fields_ = [
+        ('step_size', C.c_void_p), ('inverse_mass_matrix', C.c_void_p), ('max_num_doublings', C.c_int32),
+        ('divergence_threshold', C.c_float), ('momentum_noise', C.c_void_p), ('uniforms', C.c_void_p),
+        ('seed', C.c_uint64), ('particle_ids', C.c_void_p), ('step_offset', C.c_int64), ('n_steps', C.c_int32),
+        ('n_thinning', C.c_int32), ('out_samples', C.c_void_p), ('out_info', C.c_void_p),
+        ('out_stats', C.POINTER(C.c_int64)),
+    ]
+
+
+class NutsAdaptArgsC(C.Structure):
+    _fields_ = [
+        ('step_size', C.c_void_p), ('inverse_mass_matrix', C.c_void_p), ('da', C.c_void_p), ('welford', C.c_void_p),
+        ('welford_count', C.c_void_p), ('schedule', C.POINTER(C.c_int32)), ('target_acceptance_rate', C.c_float),
+    ]
+
 # name -> (restype, argtypes): every symbol include/mile_hip.h declares
 SIGNATURES = {
     'mile_last_error': (C.c_char_p, []),
@@ -109,6 +126,10 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p]),
     'mile_grad_launch_info': (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p, C.c_int32]),
+    'mile_nuts_reserve': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
+    'mile_nuts_step': (C.c_int32, [C.c_void_p, C.POINTER(StateC), C.POINTER(NutsArgsC), C.c_void_p]),
+    'mile_nuts_warmup': (C.c_int32, [C.c_void_p, C.POINTER(StateC), C.POINTER(NutsArgsC), C.POINTER(NutsAdaptArgsC),
+                                     C.c_void_p]),
     'mile_grad_timing_begin': (C.c_int32, [C.c_void_p]),
     'mile_grad_timing_end': (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
 }

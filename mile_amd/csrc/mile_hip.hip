@@ -23,6 +23,7 @@
 #include "mile_lenet_mfma.h"
 #include "mile_predict.h"
 #include "mile_update.h"
+#include "mile_nuts.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -69,6 +70,10 @@ struct mile_sampler {
   float *wide_ws = nullptr; size_t wide_ws_floats = 0; int wide_R = 0, wide_E = 0;
   void *wide_wt = nullptr; size_t wide_wt_bytes = 0;
   float *wide_hb = nullptr; size_t wide_hb_floats = 0;   // k_wide_headblock's per-workgroup partial sums
+  // NUTS trajectory buffers (mile_nuts_reserve)
+  NutsBufs nb{};
+  int nuts_E = 0, nuts_M = 0;
+  int32_t *nuts_count_h = nullptr;      // pinned host copy of nb.count
   // timing of grad launches
   bool timing = false;
   std::vector<hipEvent_t> ev;
@@ -353,6 +358,17 @@ static void free_ws(mile_sampler *s) {
   s->E_cap = 0; s->ES_cap = 0;
 }
 
+static void free_nuts(mile_sampler *s) {
+  NutsBufs &b = s->nb;
+  float **fs[] = {&b.T, &b.Ph, &b.xe[0], &b.xe[1], &b.pe[0], &b.pe[1], &b.ge[0], &b.ge[1], &b.psT, &b.psS, &b.xs, &b.gs,
+                  &b.ck_r, &b.ck_rs};
+  for (float **f : fs) { if (*f) (void)hipFree(*f); *f = nullptr; }
+  if (b.chain) (void)hipFree(b.chain);
+  if (b.count) (void)hipFree(b.count);
+  b.chain = nullptr; b.count = nullptr;
+  s->nuts_E = s->nuts_M = 0;
+}
+
 int32_t mile_destroy(mile_sampler *s) {
   if (!s) return MILE_OK;
   if (s->ev_X) (void)hipFree(s->ev_X);
@@ -367,6 +383,8 @@ int32_t mile_destroy(mile_sampler *s) {
   if (s->wide_hb) (void)hipFree(s->wide_hb);
   if (s->dbg_buf) (void)hipFree(s->dbg_buf);
   if (s->tune_info) (void)hipFree(s->tune_info);
+  free_nuts(s);
+  if (s->nuts_count_h) (void)hipHostFree(s->nuts_count_h);
   if (s->blas && g_rb.destroy) (void)g_rb.destroy(s->blas);
   for (auto ev : s->ev) (void)hipEventDestroy(ev);
   delete s;
@@ -2046,6 +2064,113 @@ int32_t mile_debug_noise(mile_sampler *s, uint64_t seed, const int32_t *particle
   k_debug_noise<<<E, AUX_NT, 0, (hipStream_t)stream>>>(s->ds.d, seed, particle_ids, (uint32_t)step, (uint32_t)stage, out);
   HIP_TRY(hipGetLastError());
   return MILE_OK;
+}
+
+int32_t mile_nuts_reserve(mile_sampler *s, int32_t E, int32_t max_num_doublings) {
+  if (!s || E < 1 || max_num_doublings < 1 || max_num_doublings > NUTS_MAX_DOUBLINGS)
+    return fail(MILE_ERR_INVALID, "mile_nuts_reserve: E >= 1 and 1 <= max_num_doublings <= 12");
+  const int rc = mile_reserve(s, E);
+  if (rc) return rc;
+  if (E <= s->nuts_E && max_num_doublings <= s->nuts_M) return MILE_OK;
+  const int En = std::max(E, s->nuts_E), Mn = std::max(max_num_doublings, s->nuts_M);
+  free_nuts(s);
+  const size_t Ed = (size_t)En * s->ds.d * 4;
+  NutsBufs &b = s->nb;
+  float **fs[] = {&b.T, &b.Ph, &b.xe[0], &b.xe[1], &b.pe[0], &b.pe[1], &b.ge[0], &b.ge[1], &b.psT, &b.psS, &b.xs, &b.gs};
+  for (float **f : fs) HIP_TRY(hipMalloc(f, Ed));
+  HIP_TRY(hipMalloc(&b.ck_r, Ed * Mn));
+  HIP_TRY(hipMalloc(&b.ck_rs, Ed * Mn));
+  HIP_TRY(hipMalloc(&b.chain, (size_t)En * sizeof(NutsChain)));
+  HIP_TRY(hipMalloc(&b.count, 16));
+  HIP_TRY(hipMemset(b.T, 0, Ed));   // rows of chains outside a launch are never read uninitialised by the grad kernels
+  if (!s->nuts_count_h) HIP_TRY(hipHostMalloc((void **)&s->nuts_count_h, 16, hipHostMallocDefault));
+  s->nuts_E = En; s->nuts_M = Mn;
+  return MILE_OK;
+}
+
+// n_steps NUTS steps (and, with `w`, one window-adaptation update after each), all chains in lockstep.
+static int nuts_run(mile_sampler *s, mile_state *state, const mile_nuts_args *a, const mile_nuts_adapt_args *w, void *stream) {
+  const char *fn = w ? "mile_nuts_warmup" : "mile_nuts_step";
+  if (!s || !state || !a) return fail(MILE_ERR_INVALID, std::string(fn) + ": null argument");
+  if (!state->position || !state->logdensity || !state->logdensity_grad) return fail(MILE_ERR_INVALID, std::string(fn) + ": null state field");
+  const int E = state->n_particles, d = s->ds.d, M = a->max_num_doublings;
+  if (E < 1 || a->n_steps < 0) return fail(MILE_ERR_INVALID, std::string(fn) + ": n_particles >= 1 and n_steps >= 0");
+  if (M < 1 || M > NUTS_MAX_DOUBLINGS) return fail(MILE_ERR_INVALID, std::string(fn) + ": 1 <= max_num_doublings <= 12");
+  if (w) {
+    if (!w->step_size || !w->inverse_mass_matrix || !w->da || !w->welford || !w->welford_count || !w->schedule)
+      return fail(MILE_ERR_INVALID, "mile_nuts_warmup: null adaptation field");
+  } else if (!a->step_size || !a->inverse_mass_matrix) {
+    return fail(MILE_ERR_INVALID, "mile_nuts_step: step_size and inverse_mass_matrix are required");
+  }
+  if (!s->X) return fail(MILE_ERR_STATE, "no data: call mile_set_data first");
+  if (E > s->nuts_E || M > s->nuts_M) return fail(MILE_ERR_STATE, std::string(fn) + ": call mile_nuts_reserve(E, max_num_doublings) first");
+  if (a->n_steps == 0) return MILE_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->device));
+  const int kernel = resolved_kernel(s);
+  const int S = choose_S(s, E, kernel);
+  if (E > s->E_cap || (size_t)E * S > s->ES_cap) return fail(MILE_ERR_STATE, "workspace too small: call mile_reserve(E) first");
+  NutsParams p{};
+  p.d = d; p.dp = (d + 3) / 4 * 4; p.S = S; p.E = E; p.M = M; p.prior = s->ds.prior;
+  p.loc = s->ds.prior_loc; p.scale = s->ds.prior_scale; p.thr = a->divergence_threshold;
+  p.slabs = s->slabs; p.llpart = s->llpart;
+  p.x = state->position; p.g = state->logdensity_grad; p.logp = state->logdensity;
+  p.eps = w ? w->step_size : a->step_size;
+  p.m = w ? w->inverse_mass_matrix : a->inverse_mass_matrix;
+  p.NU = 2 * M + (1 << M);
+  p.seed = a->seed; p.pids = a->particle_ids; p.b = s->nb;
+  const size_t Ed = (size_t)E * d;
+  int64_t rounds = 0, syncs = 0;
+  int kept = 0;
+  for (int i = 0; i < a->n_steps; ++i) {
+    const int64_t gstep = a->step_offset + i;
+    p.gstep = (uint32_t)gstep;
+    p.z = a->momentum_noise ? a->momentum_noise + (size_t)i * Ed : nullptr;
+    p.unif = a->uniforms ? a->uniforms + (size_t)i * E * p.NU : nullptr;
+    p.out_info = a->out_info ? a->out_info + (size_t)i * E * NUTS_INFO : nullptr;
+    p.out_sample = nullptr;
+    if (a->out_samples && a->n_thinning > 0 && (gstep % a->n_thinning) == 0) p.out_sample = a->out_samples + (size_t)(kept++) * Ed;
+    k_nuts_begin<<<E, NUTS_NT, 0, st>>>(p);
+    HIP_TRY(hipGetLastError());
+    for (int j = 0; j < M; ++j) {
+      p.sub_len = 1 << j;
+      for (int k = 0; k < p.sub_len; ++k) {   // one round: every chain still in its subtree takes one leapfrog step
+        const int rc = launch_grad(s, s->nb.T, E, st);
+        if (rc) return rc;
+        p.leaf = k;
+        k_nuts_leaf<<<E, NUTS_NT, 0, st>>>(p);
+        HIP_TRY(hipGetLastError());
+        ++rounds;
+      }
+      HIP_TRY(hipMemsetAsync(s->nb.count, 0, 4, st));
+      k_nuts_merge<<<E, NUTS_NT, 0, st>>>(p);
+      HIP_TRY(hipGetLastError());
+      if (j == M - 1) break;   // every chain has stopped
+      HIP_TRY(hipMemcpyAsync(s->nuts_count_h, s->nb.count, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      ++syncs;
+      if (*s->nuts_count_h == 0) break;
+    }
+    if (w) {
+      NutsAdaptParams ap{};
+      ap.d = d; ap.stage = w->schedule[2 * i]; ap.window_end = w->schedule[2 * i + 1]; ap.target = w->target_acceptance_rate;
+      ap.x = state->position; ap.chain = s->nb.chain; ap.step_size = w->step_size; ap.imm = w->inverse_mass_matrix;
+      ap.da = w->da; ap.wf = w->welford; ap.wf_n = w->welford_count;
+      k_nuts_adapt<<<E, NUTS_NT, 0, st>>>(ap);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  if (a->out_stats) { a->out_stats[0] += rounds; a->out_stats[1] += syncs; }
+  return MILE_OK;
+}
+
+int32_t mile_nuts_step(mile_sampler *s, mile_state *state, const mile_nuts_args *a, void *stream) {
+  return nuts_run(s, state, a, nullptr, stream);
+}
+
+int32_t mile_nuts_warmup(mile_sampler *s, mile_state *state, const mile_nuts_args *a, const mile_nuts_adapt_args *w, void *stream) {
+  if (!w) return fail(MILE_ERR_INVALID, "mile_nuts_warmup: null adaptation state");
+  return nuts_run(s, state, a, w, stream);
 }
 
 }  // extern "C"

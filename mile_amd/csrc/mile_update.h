@@ -957,6 +957,26 @@ static inline int upd_kind(const UpdParams &u) {
 }
 
 #define AUX_NT 256
+// Element i of the log-posterior gradient from the grad kernel's partial-gradient slabs (sl = this particle's S slab rows)
+// plus the prior's gradient at theta_i; the prior's log-density term (without its constant) is added to pv.
+__device__ __forceinline__ float slab_grad_logprior(const float *sl, int S, int dp, int i, int prior, float loc, float scale,
+                                                    float theta_i, float &pv) {
+  float gi = 0.0f;
+  for (int s = 0; s < S; ++s) gi += sl[(size_t)s * dp + i];
+  const float t = (theta_i - loc) / scale;
+  if (prior == MILE_PRIOR_NORMAL) { gi -= t / scale; pv += -0.5f * t * t; }
+  else { gi -= (t > 0.0f ? 1.0f : (t < 0.0f ? -1.0f : 0.0f)) / scale; pv += -fabsf(t); }
+  return gi;
+}
+// log-posterior of particle e: its S partial log-likelihoods + the summed prior terms pv + the prior's constant (fp64)
+__device__ __forceinline__ double llpart_logprior(const float *llpart, int S, int e, int d, int prior, float scale, double pv) {
+  double t = pv;
+  for (int s = 0; s < S; ++s) t += (double)llpart[(size_t)e * S + s];
+  t += prior == MILE_PRIOR_NORMAL ? -(double)d * (log((double)scale) + 0.91893853320467274)
+                                  : -(double)d * log(2.0 * (double)scale);
+  return t;
+}
+
 // g = sum_s slab + grad log prior;  logp = sum_s llpart + log prior.   (mile_logpost_grad)
 static __global__ __launch_bounds__(AUX_NT) void k_finalize(int d, int dp, int S, int prior, float loc, float scale,
                                                      const float *theta, const float *slabs,
@@ -966,24 +986,14 @@ static __global__ __launch_bounds__(AUX_NT) void k_finalize(int d, int dp, int S
   const size_t base = (size_t)e * d;
   const float *sl = slabs + (size_t)e * S * dp;
   float pv = 0.0f;
-  for (int i = tid; i < d; i += AUX_NT) {
-    float gi = 0.0f;
-    for (int s = 0; s < S; ++s) gi += sl[(size_t)s * dp + i];
-    const float t = (theta[base + i] - loc) / scale;
-    if (prior == MILE_PRIOR_NORMAL) { gi -= t / scale; pv += -0.5f * t * t; }
-    else { gi -= (t > 0.0f ? 1.0f : (t < 0.0f ? -1.0f : 0.0f)) / scale; pv += -fabsf(t); }
-    grad[base + i] = gi;
-  }
+  for (int i = tid; i < d; i += AUX_NT) grad[base + i] = slab_grad_logprior(sl, S, dp, i, prior, loc, scale, theta[base + i], pv);
   pv = wave_sum(pv);
   if ((tid & 63) == 0) red[tid >> 6] = pv;
   __syncthreads();
   if (tid == 0) {
     double t = 0.0;
     for (int w = 0; w < AUX_NT / 64; ++w) t += (double)red[w];
-    for (int s = 0; s < S; ++s) t += (double)llpart[(size_t)e * S + s];
-    t += prior == MILE_PRIOR_NORMAL ? -(double)d * (log((double)scale) + 0.91893853320467274)
-                                    : -(double)d * log(2.0 * (double)scale);
-    logp[e] = (float)t;
+    logp[e] = (float)llpart_logprior(llpart, S, e, d, prior, scale, t);
   }
 }
 

@@ -6,6 +6,7 @@ call goes through the C ABI of include/mile_hip.h on raw device pointers.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import NamedTuple
 
 import torch
@@ -29,6 +30,25 @@ class MCLMCInfo(NamedTuple):
     logdensity: torch.Tensor
     kinetic_change: torch.Tensor
     energy_change: torch.Tensor
+
+
+class HMCState(NamedTuple):
+    """blackjax HMCState with a leading ensemble axis."""
+
+    position: torch.Tensor         # [E, d]
+    logdensity: torch.Tensor       # [E]
+    logdensity_grad: torch.Tensor  # [E, d]
+
+
+class NUTSInfo(NamedTuple):
+    """The NUTSInfo fields the reference keeps (src/training/sampling.py:200-210), [n_steps, E] each."""
+
+    num_integration_steps: torch.Tensor
+    acceptance_rate: torch.Tensor
+    num_trajectory_expansions: torch.Tensor
+    is_divergent: torch.Tensor
+    energy: torch.Tensor
+    is_turning: torch.Tensor
 
 
 def _ptr(t):
@@ -329,6 +349,124 @@ class Engine:
         with torch.cuda.device(dev):
             _lib.check(self.lib.mile_tune(self._h, C.byref(sc), C.byref(a), self._stream()), self.lib)
         return MCLMCInfo(info[..., 0], info[..., 1], info[..., 2]) if info is not None else None
+
+    # ------------------------------------------------------------------ NUTS
+    def nuts_reserve(self, E: int, max_num_doublings: int):
+        self.reserve(E)
+        _lib.check(self.lib.mile_nuts_reserve(self._h, int(E), int(max_num_doublings)), self.lib)
+
+    def nuts_init(self, position) -> HMCState:
+        """blackjax.nuts init: the log density and its gradient at ``position`` [E, d]."""
+        position = _f32(position, self.device, name='position').clone()
+        if position.ndim != 2 or position.shape[1] != self.d:
+            raise ValueError(f'position must be [E, {self.d}], got {tuple(position.shape)}')
+        logp, grad = self.logpost_grad(position)
+        return HMCState(position, logp, grad)
+
+    def _nuts_args(self, state: HMCState, n_steps, max_num_doublings, divergence_threshold, noise, uniforms, seed,
+                   step_offset, n_thinning, particle_ids, want_info, stats):
+        E, dev = state.position.shape[0], self.device
+        for t in state:
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError('state tensors must be contiguous fp32 on the engine device')
+        M = int(max_num_doublings)
+        self.nuts_reserve(E, M)
+        keep = {}
+        z = _f32(noise, dev, (n_steps, E, self.d), 'noise') if noise is not None else None
+        u = _f32(uniforms, dev, (n_steps, E, 2 * M + 2 ** M), 'uniforms') if uniforms is not None else None
+        ids = self._ids(particle_ids, E)
+        n_kept = sum(1 for i in range(n_steps) if (step_offset + i) % n_thinning == 0) if n_thinning > 0 else 0
+        samples = torch.empty((n_kept, E, self.d), dtype=torch.float32, device=dev) if n_kept else None
+        info = torch.empty((n_steps, E, 6), dtype=torch.float32, device=dev) if want_info else None
+        a = _lib.NutsArgsC()
+        a.max_num_doublings = M
+        a.divergence_threshold = float(divergence_threshold)
+        a.momentum_noise = z.data_ptr() if z is not None else None
+        a.uniforms = u.data_ptr() if u is not None else None
+        a.seed = seed
+        a.particle_ids = ids.data_ptr() if ids is not None else None
+        a.step_offset = step_offset
+        a.n_steps = n_steps
+        a.n_thinning = n_thinning
+        a.out_samples = samples.data_ptr() if samples is not None else None
+        a.out_info = info.data_ptr() if info is not None else None
+        if stats is not None:
+            a.out_stats = stats
+        keep.update(z=z, u=u, ids=ids)
+        return a, keep, samples, info
+
+    @staticmethod
+    def _nuts_info(info):
+        return NUTSInfo(*(info[..., k] for k in range(6))) if info is not None else None
+
+    def nuts_step(self, state: HMCState, step_size, inverse_mass_matrix, n_steps: int = 1, *, max_num_doublings: int = 10,
+                  divergence_threshold: float = 1000.0, noise=None, uniforms=None, seed: int = 0, step_offset: int = 0,
+                  n_thinning: int = 0, particle_ids=None, want_info: bool = True, inplace: bool = False, stats=None):
+        """n_steps NUTS steps of all chains in lockstep (mile_nuts_step).  ``noise`` [n_steps, E, d] and ``uniforms``
+        [n_steps, E, 2 M + 2^M]: explicit draws (slot layout of include/mile_hip.h), else the counter RNG.
+        Returns (state, NUTSInfo | None, samples [n_kept, E, d] | None).  ``stats``: a ctypes int64[2] that receives the
+        leapfrog rounds launched and host syncs (added to)."""
+        E, dev = state.position.shape[0], self.device
+        if not inplace:
+            state = HMCState(*(t.clone() for t in state))
+        eps = _f32(step_size, dev).expand(E).contiguous() if torch.as_tensor(step_size).ndim == 0 \
+            else _f32(step_size, dev, (E,), 'step_size')
+        imm = torch.as_tensor(inverse_mass_matrix)
+        imm = _f32(imm, dev).expand(E, self.d).contiguous() if imm.ndim < 2 else _f32(imm, dev, (E, self.d), 'inverse_mass_matrix')
+        a, keep, samples, info = self._nuts_args(state, n_steps, max_num_doublings, divergence_threshold, noise, uniforms,
+                                                 seed, step_offset, n_thinning, particle_ids, want_info, stats)
+        a.step_size = eps.data_ptr()
+        a.inverse_mass_matrix = imm.data_ptr()
+        sc = _lib.StateC()
+        sc.n_particles = E
+        sc.position, sc.logdensity, sc.logdensity_grad = (state.position.data_ptr(), state.logdensity.data_ptr(),
+                                                          state.logdensity_grad.data_ptr())
+        with torch.cuda.device(dev):
+            _lib.check(self.lib.mile_nuts_step(self._h, C.byref(sc), C.byref(a), self._stream()), self.lib)
+        return state, self._nuts_info(info), samples
+
+    def nuts_adaptation_init(self, E: int, initial_step_size: float = 1.0) -> dict:
+        """window_adaptation.base init per chain: the caller-owned state mile_nuts_warmup updates in place."""
+        dev = self.device
+        ad = {'step_size': torch.full((E,), float(initial_step_size), dtype=torch.float32, device=dev),
+              'inverse_mass_matrix': torch.ones((E, self.d), dtype=torch.float32, device=dev),
+              'da': torch.tensor([math.log(initial_step_size), 0.0, 1.0, 0.0, math.log(10 * initial_step_size)],
+                                 dtype=torch.float32, device=dev).repeat(E, 1).contiguous(),
+              'welford': torch.zeros((E, 2, self.d), dtype=torch.float32, device=dev),
+              'welford_count': torch.zeros(E, dtype=torch.float32, device=dev)}
+        return ad
+
+    def nuts_warmup(self, state: HMCState, adaptation: dict, schedule, *, max_num_doublings: int = 10,
+                    divergence_threshold: float = 1000.0, target_acceptance_rate: float = 0.8, noise=None, uniforms=None,
+                    seed: int = 0, step_offset: int = 0, n_thinning: int = 0, particle_ids=None, want_info: bool = False,
+                    stats=None):
+        """len(schedule) NUTS steps with the window adaptation on the device (mile_nuts_warmup).  ``state`` and the
+        ``adaptation`` tensors advance IN PLACE; ``schedule`` [n_steps, 2] (stage, is_middle_window_end) from
+        warmup.build_schedule.  Returns (NUTSInfo | None, kept positions | None)."""
+        sch = (C.c_int32 * (2 * len(schedule)))(*[int(v) for row in schedule for v in row])
+        n_steps = len(schedule)
+        E = state.position.shape[0]
+        for k, t in adaptation.items():
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device or t.shape[0] != E:
+                raise ValueError(f'adaptation[{k!r}] must be a contiguous fp32 tensor of {E} rows on the engine device')
+        a, keep, samples, info = self._nuts_args(state, n_steps, max_num_doublings, divergence_threshold, noise, uniforms,
+                                                 seed, step_offset, n_thinning, particle_ids, want_info, stats)
+        w = _lib.NutsAdaptArgsC()
+        w.step_size = adaptation['step_size'].data_ptr()
+        w.inverse_mass_matrix = adaptation['inverse_mass_matrix'].data_ptr()
+        w.da = adaptation['da'].data_ptr()
+        w.welford = adaptation['welford'].data_ptr()
+        w.welford_count = adaptation['welford_count'].data_ptr()
+        w.schedule = C.cast(sch, C.POINTER(C.c_int32))
+        w.target_acceptance_rate = float(target_acceptance_rate)
+        sc = _lib.StateC()
+        sc.n_particles = E
+        sc.position, sc.logdensity, sc.logdensity_grad = (state.position.data_ptr(), state.logdensity.data_ptr(),
+                                                          state.logdensity_grad.data_ptr())
+        if n_steps:
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.mile_nuts_warmup(self._h, C.byref(sc), C.byref(a), C.byref(w), self._stream()), self.lib)
+        return self._nuts_info(info), samples
 
     def pointwise_loglik(self, theta, X, y) -> torch.Tensor:
         """log p(y_n | x_n, theta_s) for every sample and test row: theta [..., d] -> [..., N]

@@ -4,7 +4,14 @@
     sampler = KERNELS['mclmc'](logdensity_fn, L=..., step_size=...)
     state = sampler.init(position, rng_key);  state, info = sampler.step(rng_key, state)
 with every array carrying a leading ensemble axis (one row per chain), backed by
-libmile_hip.so.  'mclmc_hip' is an alias.  nuts/hmc are outside the hot path.
+libmile_hip.so.  'mclmc_hip' is an alias.
+
+``KERNELS['nuts']`` has blackjax.nuts's factory shape:
+    sampler = KERNELS['nuts'](logdensity_fn, step_size, inverse_mass_matrix, max_num_doublings=10,
+                              divergence_threshold=1000)
+    state = sampler.init(position, rng_key);  state, info = sampler.step(rng_key, state)
+(HMCState / NUTSInfo with the ensemble axis), backed by mile_nuts_step.  'hmc' stays unregistered: the reference has
+no warm-up for it either.
 """
 from __future__ import annotations
 
@@ -12,11 +19,11 @@ from typing import Callable, NamedTuple
 
 import torch
 
-from mile_amd.engine import IntegratorState, MCLMCInfo
+from mile_amd.engine import HMCState, IntegratorState, MCLMCInfo, NUTSInfo
 from mile_amd.probabilistic import resolve_target
 from mile_amd.tree import as_key, ravel_tree
 
-__all__ = ['mclmc', 'KERNELS', 'WARMUP_KERNELS', 'SamplingAlgorithm']
+__all__ = ['mclmc', 'nuts', 'KERNELS', 'WARMUP_KERNELS', 'SamplingAlgorithm', 'HMCState', 'NUTSInfo']
 
 
 class SamplingAlgorithm(NamedTuple):
@@ -64,9 +71,35 @@ def mclmc(logdensity_fn, L, step_size, integrator: str = 'isokinetic_mclachlan',
     return SamplingAlgorithm(init, step)
 
 
+def nuts(logdensity_fn, step_size, inverse_mass_matrix, max_num_doublings: int = 10, divergence_threshold: float = 1000,
+         chain_ids=None) -> SamplingAlgorithm:
+    """blackjax.nuts(logdensity_fn, step_size, inverse_mass_matrix, max_num_doublings=10, divergence_threshold=1000) as
+    built by sampler.get_kernel for sampler.name 'nuts' with the window-adapted parameters (src/training/sampling.py).
+
+    step_size: scalar or [E]; inverse_mass_matrix: the diagonal, [d] or [E, d].  chain_ids: global chain numbers keying
+    the RNG streams.
+    """
+    model, x, y = resolve_target(logdensity_fn)
+    eng = model.engine(x, y)
+
+    def init(position, rng_key=None) -> HMCState:
+        return eng.nuts_init(_flat(model.spec, position, eng.device))
+
+    def step(rng_key, state: HMCState, step_index: int = 0):
+        """One NUTS step.  The draws are Philox(rng_key.seed; chain id, step_index)."""
+        key = as_key(rng_key)
+        new, info, _ = eng.nuts_step(state, step_size, inverse_mass_matrix, n_steps=1, max_num_doublings=max_num_doublings,
+                                     divergence_threshold=divergence_threshold, seed=key.seed, step_offset=step_index,
+                                     particle_ids=chain_ids)
+        return new, NUTSInfo(*(f[0] for f in info))
+
+    return SamplingAlgorithm(init, step)
+
+
 KERNELS: dict[str, Callable[..., SamplingAlgorithm]] = {
     'mclmc': mclmc,
     'mclmc_hip': mclmc,
+    'nuts': nuts,
 }
 
 WARMUP_KERNELS: dict[str, Callable[..., SamplingAlgorithm]] = {}

@@ -1,4 +1,4 @@
-"""Full-batch MCLMC sampling driver (mirror of src/training/sampling.py:32-292).
+"""Full-batch MCLMC / NUTS sampling driver (mirror of src/training/sampling.py:32-292).
 
 inference_loop: warm-up -> n_samples kernel steps with the thinning predicate -> one
 ``samples/<chain>/sample_<idx>.npz`` per kept step, ``warmup_params.txt`` and ``info.pkl``.
@@ -22,7 +22,7 @@ from mile_amd.sample_writer import WriterPool
 from mile_amd.kernels import KERNELS
 from mile_amd.probabilistic import resolve_target
 from mile_amd.tree import as_key, ravel_tree
-from mile_amd.warmup import custom_mclmc_warmup
+from mile_amd.warmup import custom_mclmc_warmup, custom_window_adaptation
 
 logger = logging.getLogger(__name__)
 
@@ -50,6 +50,34 @@ def warmup_mclmc(config, rng_key, init_params, unnorm_log_posterior, n_devices: 
     return warmup_state, {'step_size': parameters.step_size, 'L': parameters.L}
 
 
+NUTS_INFO_FIELDS = ('num_integration_steps', 'acceptance_rate', 'num_trajectory_expansions', 'is_divergent', 'energy',
+                    'is_turning')
+_NUTS_INFO_DTYPES = (np.int32, np.float32, np.int32, np.bool_, np.float32, np.bool_)
+
+
+def _nuts_info_fields(parts) -> dict:
+    """Per-rank [E_r, 6, n_samples] blocks (rank order == chain order) -> {field: [n_chains, n_samples]}."""
+    parts = [p for p in parts if p.shape[0]]
+    allc = np.concatenate(parts, axis=0) if parts else np.zeros((0, 6, 0), np.float32)
+    return {k: allc[:, j].astype(t) for j, (k, t) in enumerate(zip(NUTS_INFO_FIELDS, _NUTS_INFO_DTYPES))}
+
+
+def join_without_chains(config):
+    """A rank that holds no chain of the group joins the group's collectives: the gather of the tuned (step_size, L)
+    for warmup_params.txt (MCLMC) or of the NUTS info."""
+    if config.name == 'nuts':
+        mdist.gather_objects(np.zeros((0, 6, 0), np.float32))
+    else:
+        mdist.gather_objects((np.zeros(0, np.float32), np.zeros(0, np.float32)))
+
+
+def warmup_nuts(config, rng_key, init_params, unnorm_log_posterior, n_devices: int, chain_ids=None, saving_path=None):
+    """sampling.py:220-255: custom_window_adaptation(algorithm=nuts) run for config.warmup_steps steps."""
+    warmup_algo = custom_window_adaptation(algorithm=config.kernel, logdensity_fn=unnorm_log_posterior,
+                                           progress_bar=True, saving_path=saving_path, chain_ids=chain_ids)
+    return warmup_algo.run(rng_key, init_params, chain_ids, config.warmup_steps, n_devices)
+
+
 def inference_loop(unnorm_log_posterior, config, rng_key, init_params, step_ids, saving_path: Path,
                    saving_path_warmup: Path | None = None, chunk_steps: int = 500, io_workers: int | None = None,
                    return_samples: bool = False):
@@ -65,7 +93,8 @@ def inference_loop(unnorm_log_posterior, config, rng_key, init_params, step_ids,
     key = as_key(rng_key)
     rng_key, warmup_key, sample_key = key.split(3)
     assert config.warmup_steps > 0, 'Number of warmup steps must be greater than 0.'
-    if config.name not in ('mclmc', 'mclmc_hip'):
+    is_nuts = config.name == 'nuts'
+    if config.name not in ('mclmc', 'mclmc_hip', 'nuts'):
         raise NotImplementedError(f'{config.name} does not have a warmup implemented.')
     saving_path = Path(saving_path)
     model, x, y = resolve_target(unnorm_log_posterior)
@@ -79,19 +108,28 @@ def inference_loop(unnorm_log_posterior, config, rng_key, init_params, step_ids,
 
     logger.info('> Starting Warmup sampling...')
     t_w0 = time.time()
-    warmup_state, parameters = warmup_mclmc(config=config, rng_key=warmup_key, init_params=flat0,
-                                            unnorm_log_posterior=unnorm_log_posterior, n_devices=n_devices,
-                                            chain_ids=chain_ids)
-    saving_path.mkdir(parents=True, exist_ok=True)
-    eps_host = parameters['step_size'].detach().cpu().numpy().reshape(-1)
-    L_host = parameters['L'].detach().cpu().numpy().reshape(-1)
-    # one file for the whole chain group (sampling.py:92-97): ranks hold disjoint chains, rank 0 writes all of them
-    # in chain order (shard_chains is a contiguous rank-major partition)
-    parts = mdist.gather_objects((eps_host, L_host))
-    if mdist.world()[0] == 0:
-        with open(saving_path.parent / 'warmup_params.txt', 'w') as f:
-            f.write(','.join(str(v) for p in parts for v in p[0]) + '\n')
-            f.write(','.join(str(v) for p in parts for v in p[1]) + '\n')
+    if is_nuts:
+        # the reference saves warm-up positions only when keep_warmup is set (trainer.py:322-325) and writes no
+        # warmup_params.txt for NUTS (sampling.py:74-84)
+        warmup_state, parameters = warmup_nuts(config=config, rng_key=warmup_key, init_params=flat0,
+                                               unnorm_log_posterior=unnorm_log_posterior, n_devices=n_devices,
+                                               chain_ids=chain_ids,
+                                               saving_path=saving_path_warmup if config.keep_warmup else None)
+        saving_path.mkdir(parents=True, exist_ok=True)
+    else:
+        warmup_state, parameters = warmup_mclmc(config=config, rng_key=warmup_key, init_params=flat0,
+                                                unnorm_log_posterior=unnorm_log_posterior, n_devices=n_devices,
+                                                chain_ids=chain_ids)
+        saving_path.mkdir(parents=True, exist_ok=True)
+        eps_host = parameters['step_size'].detach().cpu().numpy().reshape(-1)
+        L_host = parameters['L'].detach().cpu().numpy().reshape(-1)
+        # one file for the whole chain group (sampling.py:92-97): ranks hold disjoint chains, rank 0 writes all of them
+        # in chain order (shard_chains is a contiguous rank-major partition)
+        parts = mdist.gather_objects((eps_host, L_host))
+        if mdist.world()[0] == 0:
+            with open(saving_path.parent / 'warmup_params.txt', 'w') as f:
+                f.write(','.join(str(v) for p in parts for v in p[0]) + '\n')
+                f.write(','.join(str(v) for p in parts for v in p[1]) + '\n')
     torch.cuda.synchronize(eng.device)
     logger.info(f'> Warmup sampling completed successfully. ({time.time() - t_w0:.2f} s)')
 
@@ -99,7 +137,11 @@ def inference_loop(unnorm_log_posterior, config, rng_key, init_params, step_ids,
     # preconditioner is NOT forwarded (sampling.py:291), sqrt_diag_cov stays 1.
     sampler = config.kernel(unnorm_log_posterior, chain_ids=chain_ids, **parameters)
     del sampler  # the factory validates the target; the scan itself runs inside mile_step
-    state = warmup_state if config.use_warmup_as_init else eng.init(flat0, seed=sample_key.seed, particle_ids=chain_ids)
+    if is_nuts:
+        state = warmup_state if config.use_warmup_as_init else eng.nuts_init(flat0)
+    else:
+        state = warmup_state if config.use_warmup_as_init else eng.init(flat0, seed=sample_key.seed, particle_ids=chain_ids)
+    nuts_info = []
     logger.info(f'> Starting {config.name} Sampling...')
     kept_all = []
     t_s0 = time.time()
@@ -133,9 +175,15 @@ def inference_loop(unnorm_log_posterior, config, rng_key, init_params, step_ids,
     slot = 0
     while done < config.n_samples:
         c = min(chunk_steps, config.n_samples - done)
-        state, _, samples = eng.step(state, parameters['step_size'], parameters['L'], n_steps=c,
-                                     seed=sample_key.seed, step_offset=done, n_thinning=n_thin,
-                                     particle_ids=chain_ids, want_info=False, inplace=True)
+        if is_nuts:
+            state, inf, samples = eng.nuts_step(state, parameters['step_size'], parameters['inverse_mass_matrix'],
+                                                n_steps=c, seed=sample_key.seed, step_offset=done, n_thinning=n_thin,
+                                                particle_ids=chain_ids, want_info=True, inplace=True)
+            nuts_info.append(torch.stack(tuple(inf), dim=-1))          # [c, E, 6], stays on the device
+        else:
+            state, _, samples = eng.step(state, parameters['step_size'], parameters['L'], n_steps=c,
+                                         seed=sample_key.seed, step_offset=done, n_thinning=n_thin,
+                                         particle_ids=chain_ids, want_info=False, inplace=True)
         if samples is not None:
             idxs = [done + i for i in range(c) if (done + i) % n_thin == 0]
             if pinned[slot] is None or pinned[slot].numel() < samples.numel():
@@ -162,6 +210,10 @@ def inference_loop(unnorm_log_posterior, config, rng_key, init_params, step_ids,
     logger.info(f'> stepping {t_s1 - t_s0:.2f} s, waiting for sample files {time.time() - t_s1:.2f} s '
                 f'({n_files} files, {io_workers} writer processes)')
     logger.info(f'> {config.name} Sampling completed successfully.')
+    if is_nuts:
+        # sampling.py:200-210: the six NUTSInfo fields, [n_chains, n_samples] in chain order on rank 0
+        mine = torch.cat(nuts_info, dim=0).permute(1, 2, 0).cpu().numpy()  # [E, 6, n_samples]
+        info.update(_nuts_info_fields(mdist.gather_objects(mine)))
     if mdist.world()[0] == 0:
         with open(saving_path / 'info.pkl', 'wb') as f:                   # sampling.py:212-216
             pickle.dump(info, f)

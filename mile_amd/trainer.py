@@ -22,7 +22,7 @@ from mile_amd.callbacks import load_params_batch, save_params, save_tree
 from mile_amd.config import Config
 from mile_amd.dataset import ImageLoader, TabularLoader
 from mile_amd.probabilistic import ProbabilisticModel
-from mile_amd.sampling import inference_loop
+from mile_amd.sampling import inference_loop, join_without_chains
 from mile_amd.spec import LeNetSpec, ModelSpec
 from mile_amd.tree import PRNGKey
 
@@ -187,8 +187,9 @@ class BDETrainer:
                 if len(mine) == 0:
                     # fewer chains in the group than ranks (4 chains on 8 GPUs): this rank has nothing to sample but still
                     # joins the group's one collective -- the gather of the tuned (step_size, L) for warmup_params.txt
+                    # (MCLMC) or of the NUTS info
                     logger.info('\t| No chain of this group on this rank')
-                    mdist.gather_objects((np.zeros(0, np.float32), np.zeros(0, np.float32)))
+                    join_without_chains(cfgs)
                     continue
                 logger.info(f'\t| Starting Sampling for chains {mine}')
                 if chains:

@@ -13,6 +13,7 @@ from __future__ import annotations
 import math
 from typing import Callable, NamedTuple
 
+import numpy as np
 import torch
 
 from mile_amd.diagnostics import effective_sample_size
@@ -242,5 +243,96 @@ def custom_mclmc_warmup(logdensity_fn, diagonal_preconditioning: bool = True, de
             trust_in_estimate=trust_in_estimate, num_effective_samples=num_effective_samples,
             diagonal_preconditioning=diagonal_preconditioning, chain_ids=chain_ids, refresh=refresh)
         return AdaptationResults(state, params)
+
+    return AdaptationAlgorithm(run)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# NUTS: window adaptation (src/training/warmup.py:27-150, blackjax 1.2.2 adaptation.window_adaptation)
+
+def build_schedule(num_steps: int, initial_buffer_size: int = 75, final_buffer_size: int = 50,
+                   first_window_size: int = 25) -> list[tuple[int, bool]]:
+    """window_adaptation.build_schedule: (stage, is_middle_window_end) per step; stage 0 = fast (step size only),
+    1 = slow (step size + Welford of the positions), windows doubling in size between the two fast buffers."""
+    num_steps = int(num_steps)
+    if num_steps < 20:                      # too short to adapt the mass matrix: step size only
+        return [(0, False)] * num_steps
+    if initial_buffer_size + first_window_size + final_buffer_size > num_steps:
+        initial_buffer_size = int(0.15 * num_steps)
+        final_buffer_size = int(0.1 * num_steps)
+        first_window_size = num_steps - (initial_buffer_size + final_buffer_size)
+    schedule = [(0, False)] * initial_buffer_size
+    final_window_start = num_steps - final_buffer_size
+    next_window_size, next_window_start = first_window_size, initial_buffer_size
+    while next_window_start < final_window_start:
+        current_start, current_size = next_window_start, next_window_size
+        if 3 * current_size <= final_window_start - current_start:
+            next_window_size = 2 * current_size
+        else:
+            current_size = final_window_start - current_start
+        next_window_start = current_start + current_size
+        schedule += [(1, False)] * (next_window_start - 1 - current_start)
+        schedule.append((1, True))
+    schedule += [(0, False)] * (num_steps - final_window_start)
+    return schedule
+
+
+class NUTSAdaptationResults(NamedTuple):
+    state: object                 # engine.HMCState
+    parameters: dict              # {'step_size': [E], 'inverse_mass_matrix': [E, d]}
+
+
+def custom_window_adaptation(algorithm=None, logdensity_fn=None, is_mass_matrix_diagonal: bool = True,
+                             initial_step_size: float = 1.0, target_acceptance_rate: float = 0.80,
+                             progress_bar: bool = False, saving_path=None, chain_ids=None, max_num_doublings: int = 10,
+                             divergence_threshold: float = 1000.0, chunk_steps: int = 500,
+                             **extra_parameters) -> AdaptationAlgorithm:
+    """warmup.py:27-150.  run(rng_key, position, device_id, num_steps, n_devices) -> (state, {'step_size',
+    'inverse_mass_matrix'}): NUTS steps of every chain in lockstep with the step-size / mass-matrix adaptation on the
+    device (mile_nuts_warmup); build_schedule runs here.  With ``saving_path`` the position BEFORE each step is written
+    to ``<saving_path>/<chain>/sample_<n>.npz`` (the reference's io_callback saves ``state.position`` of the carry)."""
+    if not is_mass_matrix_diagonal:
+        raise NotImplementedError('only the diagonal mass matrix is adapted')
+    if extra_parameters:
+        raise NotImplementedError(f'extra NUTS parameters {sorted(extra_parameters)}')
+    model, x, y = resolve_target(logdensity_fn)
+
+    def run(rng_key, position, device_id=None, num_steps: int = 1000, n_devices: int = 1) -> NUTSAdaptationResults:
+        eng = model.engine(x, y)
+        key = as_key(rng_key)
+        flat = position if torch.is_tensor(position) else ravel_tree(model.spec, position)
+        if flat.ndim == 1:
+            flat = flat[None]
+        state = eng.nuts_init(flat)
+        E = state.position.shape[0]
+        ad = eng.nuts_adaptation_init(E, initial_step_size)
+        schedule = build_schedule(num_steps)
+        writer = None
+        if saving_path is not None:
+            from mile_amd.sample_writer import WriterPool
+            writer = WriterPool(2)
+            leaves = [(n, o, tuple(sh)) for n, o, sh in model.spec.leaves()]
+            ids = [int(c) for c in (chain_ids if chain_ids is not None else range(E))]
+        done = 0
+        while done < num_steps:
+            c = min(chunk_steps, num_steps - done)
+            if writer is not None:        # positions before each step: one step at a time is the simplest exact form
+                for i in range(c):
+                    host = state.position.detach().cpu().numpy()
+                    for e, cid in enumerate(ids):
+                        writer.submit(leaves, np.array(host[e][None], copy=True), str(saving_path), cid, [done + i])
+                    eng.nuts_warmup(state, ad, schedule[done + i:done + i + 1], max_num_doublings=max_num_doublings,
+                                    divergence_threshold=divergence_threshold,
+                                    target_acceptance_rate=target_acceptance_rate, seed=key.seed, step_offset=done + i,
+                                    particle_ids=chain_ids)
+            else:
+                eng.nuts_warmup(state, ad, schedule[done:done + c], max_num_doublings=max_num_doublings,
+                                divergence_threshold=divergence_threshold, target_acceptance_rate=target_acceptance_rate,
+                                seed=key.seed, step_offset=done, particle_ids=chain_ids)
+            done += c
+        if writer is not None:
+            writer.close()
+        step_size = torch.exp(ad['da'][:, 1])                 # window_adaptation final: exp(log_step_size_avg)
+        return NUTSAdaptationResults(state, {'step_size': step_size, 'inverse_mass_matrix': ad['inverse_mass_matrix']})
 
     return AdaptationAlgorithm(run)
