@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MILE_ABI_VERSION 5
+#define MILE_ABI_VERSION 6
 #define MILE_MAX_LAYERS 16
 
 typedef enum mile_status {
@@ -78,12 +78,16 @@ typedef enum mile_grad_kernel {
                                      either head: fused forward + backward on v_mfma_f32_16x16x4_f32 (fp32 operands -- exact fp32
                                      products, fp32 accumulation); what AUTO picks for the reference's own 16- / 32-wide nets
                                      (experiments/replicate_uci/mclmc.yaml [16,16,2], tabluar_classif/covertype.yaml [32,7]) */
-  MILE_GRAD_LENET_BF16 = 9        /* MILE_MODEL_LENET, <= 4 image channels: the five convolution products as implicit GEMMs on
+  MILE_GRAD_LENET_BF16 = 9,       /* MILE_MODEL_LENET, <= 4 image channels: the five convolution products as implicit GEMMs on
                                      v_mfma_f32_16x16x32_bf16 with bf16-ROUNDED operands (BASELINE config 5 names bf16), the rest
                                      as LENET_F32; explicit only */
+  MILE_GRAD_LENETTI_F32 = 11      /* MILE_MODEL_LENETTI only (and its only kernel; AUTO resolves to it): one fused fp32 forward +
+                                     backward launch, k_grad_lenetti (mile_lenetti.h); <= 4 image channels, (H+2)(W+2) <= 2048,
+                                     out_dim <= 16 */
 } mile_grad_kernel;
-/* Which network: the FCN (src/models/tabular/fcn.py:16-28) or LeNet (src/models/images/cnns.py:10-66). */
-typedef enum mile_model { MILE_MODEL_FCN = 0, MILE_MODEL_LENET = 1 } mile_model;
+/* Which network: the FCN (src/models/tabular/fcn.py:16-28), LeNet (src/models/images/cnns.py:10-66) or LeNetti
+ * (src/models/images/cnns.py:69-121). */
+typedef enum mile_model { MILE_MODEL_FCN = 0, MILE_MODEL_LENET = 1, MILE_MODEL_LENETTI = 2 } mile_model;
 
 /* FCNConfig (src/config/models/fcn.py:7-30) + PriorConfig (src/config/sampler.py:60-95)
  * + Task: everything log_unnormalized_posterior (src/training/probabilistic.py:115-138)
@@ -100,8 +104,10 @@ typedef struct mile_model_spec {
   int32_t use_bias;                  /* FCNConfig.use_bias; only 1 is supported */
   int32_t model;                     /* mile_model.  LENET: X rows are NCHW images, in_features = C*H*W,
                                       * n_layers = 1 and widths[0] = out_dim; parameter order is ravel_pytree's
-                                      * (conv1, conv2, fc1, fc2, fc3; bias before kernel [kh,kw,in,out]) */
-  int32_t img_c;                     /* LENET image geometry (ignored for the FCN) */
+                                      * (conv1, conv2, fc1, fc2, fc3; bias before kernel [kh,kw,in,out]).
+                                      * LENETTI: the same conventions; parameters conv1 (3x3, 1 output channel), fc1
+                                      * ((H+2)(W+2) -> 8), fc2, fc3 (8 -> 8), fc4 (8 -> out_dim) */
+  int32_t img_c;                     /* LENET / LENETTI image geometry (ignored for the FCN) */
   int32_t img_h;
   int32_t img_w;
 } mile_model_spec;
@@ -235,7 +241,8 @@ int32_t mile_destroy(mile_sampler *s);
 /* pytree_size(position) (blackjax.util; src/training/warmup.py:203). */
 int64_t mile_param_count(const mile_sampler *s);
 
-/* Offsets of layer `layer`'s bias and kernel inside the raveled vector (ravel_pytree order). */
+/* Offsets of layer `layer`'s bias and kernel inside the raveled vector (ravel_pytree order).  LENET: layers 0..4 = conv1, conv2,
+ * fc1, fc2, fc3; LENETTI: layers 0..4 = conv1, fc1, fc2, fc3, fc4. */
 int32_t mile_param_offsets(const mile_sampler *s, int32_t layer, int64_t *bias_off, int64_t *kernel_off);
 
 /* Replaces: partial(log_unnormalized_posterior, x=train_x, y=train_y)
@@ -245,7 +252,7 @@ int32_t mile_set_data(mile_sampler *s, const float *X, const void *y, int64_t N,
 /* Restrict the likelihood to rows [begin, begin + count) of the training set for the following mile_logpost_grad calls
  * (count = 0: all rows again).  Replaces the minibatches of the warm-start stage: loader.iter(split='train', batch_size=...)
  * (src/dataset/tabular.py:170-212) feeding single_step_regr / single_step_class (src/training/trainer.py:706-760).
- * Supported by MILE_GRAD_GENERIC, the MFMA_NARROW, MFMA_W64, MFMA_WIDE and LENET kernels (mile_logpost_grad fails with MILE_ERR_STATE on
+ * Supported by MILE_GRAD_GENERIC, the MFMA_NARROW, MFMA_W64, MFMA_WIDE, LENET and LENETTI kernels (mile_logpost_grad fails with MILE_ERR_STATE on
  * MFMA_W128_BF16 / GEMM_F32 under a window); the MCLMC path itself is full-batch (n_batches = 1). */
 int32_t mile_set_row_window(mile_sampler *s, int64_t begin, int64_t count);
 

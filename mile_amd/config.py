@@ -112,14 +112,35 @@ class LeNetConfig:
         _check(isinstance(self.out_dim, int) and self.out_dim > 0, 'out_dim must be a positive int')
 
 
+@dataclass(frozen=True)
+class LeNettiConfig:
+    """src/config/models/cnns.py (LeNettiConfig)."""
+
+    model: str = 'LeNetti'
+    activation: str = 'sigmoid'
+    out_dim: int = 10
+    use_bias: bool = True
+
+    def __post_init__(self):
+        _check(self.model == 'LeNetti', f'Could not find model {self.model}.')
+        _check(self.activation in ('sigmoid', 'relu', 'gelu', 'tanh', 'softmax', 'leaky_relu'),
+               f'unknown activation {self.activation!r}')
+        # the reference's enum (config/models/base.py:25-39) has three more; the HIP kernels implement these
+        _check(self.activation in ('sigmoid', 'relu', 'tanh'),
+               f'activation {self.activation!r} is not implemented on the MI355X path (supported: relu, tanh, sigmoid)')
+        _check(isinstance(self.out_dim, int) and self.out_dim > 0, 'out_dim must be a positive int')
+
+
 def _model_config(data):
     """ModelConfig.from_dict dispatch on the `model` key (src/config/models/__init__.py)."""
     name = data.get('model', 'FCN') if isinstance(data, dict) else 'FCN'
     if name == 'LeNet':
         return LeNetConfig
+    if name == 'LeNetti':
+        return LeNettiConfig
     if name == 'FCN':
         return FCNConfig
-    raise ConfigError(f"Could not find model {name}. Available on the MI355X hot path: ['FCN', 'LeNet']")
+    raise ConfigError(f"Could not find model {name}. Available on the MI355X hot path: ['FCN', 'LeNet', 'LeNetti']")
 
 
 @dataclass(frozen=True)
@@ -164,7 +185,8 @@ class SamplerConfig:
     def __post_init__(self):
         _check(self.name in ('nuts', 'mclmc', 'hmc', 'mclmc_hip'), f'unknown sampler {self.name!r}')
         _check(self.grad_kernel in ('auto', 'generic', 'mfma_w64', 'mfma_w64_bf16x3', 'mfma_w128_bf16', 'gemm_f32', 'mfma_wide_bf16x3',
-                                    'mfma_wide_bf16', 'lenet_f32', 'lenet_bf16', 'mfma_narrow_f32'), f'unknown grad_kernel {self.grad_kernel!r}')
+                                    'mfma_wide_bf16', 'lenet_f32', 'lenet_bf16', 'mfma_narrow_f32', 'lenetti_f32'),
+               f'unknown grad_kernel {self.grad_kernel!r}')
 
     @property
     def prior(self) -> Prior:

@@ -21,6 +21,7 @@
 #include "mile_mm3.h"
 #include "mile_lenet.h"
 #include "mile_lenet_mfma.h"
+#include "mile_lenetti.h"
 #include "mile_predict.h"
 #include "mile_update.h"
 #include "mile_nuts.h"
@@ -57,6 +58,7 @@ struct mile_sampler {
   float *alt_x = nullptr, *alt_u = nullptr, *alt_g = nullptr, *alt_logp = nullptr;   // ping-pong state of mile_tune
   int grad_kernel = MILE_GRAD_AUTO;
   LeNetGeom lg{};                       // MILE_MODEL_LENET geometry and parameter offsets
+  LeNettiGeom ng{};                     // MILE_MODEL_LENETTI geometry and parameter offsets
   // layer-wise GEMM path (MILE_GRAD_GEMM_F32): rocBLAS handle and activation workspace
   void *blas = nullptr;
   long long *dbg_buf = nullptr;         // dev instrumentation (MILE_DEBUG=16)
@@ -169,6 +171,7 @@ static bool w128b_supported(const mile_model_spec &sp) {
 }
 
 static int resolved_kernel(const mile_sampler *s) {
+  if (s->spec.model == MILE_MODEL_LENETTI) return MILE_GRAD_LENETTI_F32;
   if (s->spec.model == MILE_MODEL_LENET) return s->grad_kernel == MILE_GRAD_LENET_BF16 ? MILE_GRAD_LENET_BF16 : MILE_GRAD_LENET_F32;
   if (s->grad_kernel == MILE_GRAD_AUTO) {
     if (w64x3_supported(s->spec)) return MILE_GRAD_MFMA_W64_BF16X3;   // fp32-faithful and never slower than MFMA_W64
@@ -206,8 +209,16 @@ static int narrow_waves(const mile_sampler *s, int S, int N) {
   return std::max(1, std::min(NRW_MAXW, (tiles + S - 1) / S));
 }
 
+// k_grad_lenetti: about two workgroups per CU over the grid, at most 64 row ranges (every range is one more slab the update
+// kernels sum) and at least 32 images per range
+static int lenetti_S(const mile_sampler *s, int E) {
+  const int want = (2 * s->n_cu + std::max(E, 1) - 1) / std::max(E, 1);
+  return std::max(1, std::min({64, want, std::max(1, s->N / 32)}));
+}
+
 static int choose_S(const mile_sampler *s, int E, int kernel) {
   if (kernel == MILE_GRAD_MFMA_NARROW_F32) return narrow_S(s, E);
+  if (kernel == MILE_GRAD_LENETTI_F32) return lenetti_S(s, E);
   if (is_w64(kernel)) {
     const int NB = s->Npad / 32;
     int S = std::max(1, s->n_cu / std::max(E, 1));
@@ -245,7 +256,18 @@ int32_t mile_create(const mile_model_spec *spec, int32_t device, mile_sampler **
     if (spec->widths[l] < 1) return fail(MILE_ERR_INVALID, "layer width must be >= 1");
   if (spec->task == MILE_TASK_REGRESSION && spec->widths[spec->n_layers - 1] != 2)
     return fail(MILE_ERR_INVALID, "regression needs an output layer of width 2 (mu, log sigma)");
-  if (spec->model != MILE_MODEL_FCN && spec->model != MILE_MODEL_LENET) return fail(MILE_ERR_INVALID, "unknown model");
+  if (spec->model != MILE_MODEL_FCN && spec->model != MILE_MODEL_LENET && spec->model != MILE_MODEL_LENETTI)
+    return fail(MILE_ERR_INVALID, "unknown model");
+  if (spec->model == MILE_MODEL_LENETTI) {
+    if (spec->n_layers != 1) return fail(MILE_ERR_INVALID, "LeNetti: n_layers must be 1 (widths[0] = out_dim)");
+    if (spec->img_c < 1 || spec->img_h < 1 || spec->img_w < 1 ||
+        (long long)spec->img_c * spec->img_h * spec->img_w != spec->in_features)
+      return fail(MILE_ERR_INVALID, "LeNetti: in_features must equal img_c * img_h * img_w");
+    if (spec->img_c > LENETTI_MAX_C) return fail(MILE_ERR_INVALID, "LeNetti: at most 4 image channels");
+    if ((long long)(spec->img_h + 2) * (spec->img_w + 2) > LENETTI_NT * LENETTI_MAX_PPT)
+      return fail(MILE_ERR_INVALID, "LeNetti: (H+2)*(W+2) must be <= 2048 conv-output pixels");
+    if (spec->widths[0] > LENETTI_MAX_K) return fail(MILE_ERR_INVALID, "LeNetti: out_dim must be <= 16");
+  }
   if (spec->model == MILE_MODEL_LENET) {
     if (spec->n_layers != 1) return fail(MILE_ERR_INVALID, "LeNet: n_layers must be 1 (widths[0] = out_dim)");
     if (spec->img_c < 1 || spec->img_h < 1 || spec->img_w < 1 ||
@@ -266,6 +288,29 @@ int32_t mile_create(const mile_model_spec *spec, int32_t device, mile_sampler **
   ds.prior = spec->prior;
   ds.prior_loc = spec->prior_loc;
   ds.prior_scale = spec->prior_scale;
+  if (spec->model == MILE_MODEL_LENETTI) {   // ravel_pytree order of {'core': {conv1, fc1, fc2, fc3, fc4}}: bias, kernel each
+    LeNettiGeom &g = s->ng;
+    g.C = spec->img_c; g.H = spec->img_h; g.W = spec->img_w; g.K = spec->widths[0];
+    g.Ho = g.H + 2; g.Wo = g.W + 2; g.P = g.Ho * g.Wo;
+    int o = 0;
+    g.b_c = o; o += 1;   g.k_c = o; o += 9 * g.C;
+    g.b_1 = o; o += 8;   g.k_1 = o; o += 8 * g.P;
+    g.b_2 = o; o += 8;   g.k_2 = o; o += 64;
+    g.b_3 = o; o += 8;   g.k_3 = o; o += 64;
+    g.b_4 = o; o += g.K; g.k_4 = o; o += 8 * g.K;
+    g.d = o;
+    ds.d = g.d;
+    ds.widths[0] = g.K;
+    ds.b_off[0] = g.b_c; ds.w_off[0] = g.k_c;
+    ds.max_width = 8; ds.act_stride = 0;
+    int cnt = 0;
+    if (hipGetDeviceCount(&cnt) == hipSuccess && device < cnt) {
+      hipDeviceProp_t prop;
+      if (hipGetDeviceProperties(&prop, device) == hipSuccess) s->n_cu = prop.multiProcessorCount;
+    }
+    *out = s;
+    return MILE_OK;
+  }
   if (spec->model == MILE_MODEL_LENET) {   // ravel_pytree order of {'core': {conv1, conv2, fc1, fc2, fc3}}: bias, kernel each
     LeNetGeom &g = s->lg;
     g.C = spec->img_c; g.H = spec->img_h; g.W = spec->img_w; g.K = spec->widths[0];
@@ -402,6 +447,14 @@ int32_t mile_param_offsets(const mile_sampler *s, int32_t layer, int64_t *bias_o
     if (kernel_off) *kernel_off = ko[layer];
     return MILE_OK;
   }
+  if (s && s->spec.model == MILE_MODEL_LENETTI) {   // layers 0..4 = conv1, fc1, fc2, fc3, fc4
+    const LeNettiGeom &g = s->ng;
+    const int bo[5] = {g.b_c, g.b_1, g.b_2, g.b_3, g.b_4}, ko[5] = {g.k_c, g.k_1, g.k_2, g.k_3, g.k_4};
+    if (layer < 0 || layer >= 5) return fail(MILE_ERR_INVALID, "mile_param_offsets: bad layer");
+    if (bias_off) *bias_off = bo[layer];
+    if (kernel_off) *kernel_off = ko[layer];
+    return MILE_OK;
+  }
   if (!s || layer < 0 || layer >= s->ds.n_layers) return fail(MILE_ERR_INVALID, "mile_param_offsets: bad layer");
   if (bias_off) *bias_off = s->ds.b_off[layer];
   if (kernel_off) *kernel_off = s->ds.w_off[layer];
@@ -485,6 +538,7 @@ int32_t mile_reserve(mile_sampler *s, int32_t E) {
   int S = std::max(choose_S(s, E, MILE_GRAD_GENERIC), w64_supported(s->spec) ? choose_S(s, E, MILE_GRAD_MFMA_W64) : 1);
   if (w128b_supported(s->spec)) S = std::max(S, choose_S(s, E, MILE_GRAD_MFMA_W128_BF16));
   if (narrow_supported(s->spec)) S = std::max(S, choose_S(s, E, MILE_GRAD_MFMA_NARROW_F32));
+  if (s->spec.model == MILE_MODEL_LENETTI) S = std::max(S, choose_S(s, E, MILE_GRAD_LENETTI_F32));
   // A smaller ensemble splits the rows of a particle over MORE workgroups (S grows as E shrinks): capacity is counted in
   // slab rows E * S, and a later call with fewer particles must neither fail nor shrink what a larger one reserved.
   if (E <= s->E_cap && (size_t)E * S <= s->ES_cap) return MILE_OK;
@@ -509,7 +563,9 @@ int32_t mile_reserve(mile_sampler *s, int32_t E) {
 
 int32_t mile_set_grad_kernel(mile_sampler *s, int32_t which) {
   if (!s) return fail(MILE_ERR_INVALID, "null handle");
-  if (which < MILE_GRAD_AUTO || which > MILE_GRAD_MFMA_NARROW_F32) return fail(MILE_ERR_INVALID, "unknown grad kernel");
+  if (which < MILE_GRAD_AUTO || which > MILE_GRAD_LENETTI_F32) return fail(MILE_ERR_INVALID, "unknown grad kernel");
+  if ((s->spec.model == MILE_MODEL_LENETTI) != (which == MILE_GRAD_LENETTI_F32) && which != MILE_GRAD_AUTO)
+    return fail(MILE_ERR_INVALID, "LENETTI_F32 is the kernel of MILE_MODEL_LENETTI, and its only one");
   if (which == MILE_GRAD_MFMA_NARROW_F32 && !narrow_supported(s->spec))
     return fail(MILE_ERR_INVALID, "MFMA_NARROW_F32 needs an FCN with 1-3 hidden layers of width <= 64 and F <= 64 (or 4-10 of width <= 16 and F <= 16) and <= 16 outputs");
   if ((which == MILE_GRAD_MFMA_WIDE_BF16X3 || which == MILE_GRAD_MFMA_WIDE_BF16) && s->spec.model != MILE_MODEL_FCN)
@@ -1376,6 +1432,17 @@ static int launch_grad_wide(mile_sampler *s, const GradParams &gp, int E, hipStr
   return MILE_OK;
 }
 
+// ---- LeNetti (mile_lenetti.h; the kernels are instantiated in mile_lenetti.hip).  Gradient (out_ll == nullptr): grid (S row
+// ranges, E chains) -> slabs / llpart; evaluation: grid (S row blocks, E samples) -> out_ll[e * N + row]
+static hipError_t launch_lenetti(mile_sampler *s, const float *theta, int E, const float *X, const void *y, int N, int S, int dp,
+                                 float *out_ll, hipStream_t st) {
+  LeNettiParams lp{};
+  lp.g = s->ng; lp.activation = s->ds.activation; lp.task = s->ds.task;
+  lp.theta = theta; lp.X = X; lp.y = y; lp.slabs = s->slabs; lp.llpart = s->llpart; lp.out = out_ll;
+  lp.N = N; lp.S = S; lp.dp = dp;
+  return mile_launch_lenetti(lp, E, out_ll == nullptr, st);
+}
+
 static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t st, const UpdParams *fused_update) {
   if (!s->X) return fail(MILE_ERR_STATE, "no data: call mile_set_data first");
   const int kernel = resolved_kernel(s);
@@ -1389,9 +1456,9 @@ static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t s
   gp.N = s->N; gp.Npad = s->Npad; gp.Npb = s->Npb; gp.Fp = s->Fp; gp.S = S; gp.R = generic_R(s->ds); gp.dp = (s->ds.d + 3) / 4 * 4;
   if (s->win_count) {   // minibatch: the same kernels on a shifted view of the rows
     const bool chunked = kernel == MILE_GRAD_MFMA_WIDE_BF16X3 || kernel == MILE_GRAD_MFMA_WIDE_BF16 || kernel == MILE_GRAD_LENET_F32 ||
-                         kernel == MILE_GRAD_LENET_BF16;   // these walk the rows in chunks anyway: a window is a shorter walk
+                         kernel == MILE_GRAD_LENET_BF16 || kernel == MILE_GRAD_LENETTI_F32;   // these walk the rows in chunks anyway: a window is a shorter walk
     if (kernel != MILE_GRAD_GENERIC && kernel != MILE_GRAD_MFMA_NARROW_F32 && !is_w64(kernel) && !chunked)
-      return fail(MILE_ERR_STATE, "a row window needs the generic, the MFMA_NARROW, an MFMA_W64, an MFMA_WIDE or a LENET grad kernel");
+      return fail(MILE_ERR_STATE, "a row window needs the generic, the MFMA_NARROW, an MFMA_W64, an MFMA_WIDE, a LENET or the LENETTI grad kernel");
     if (fused_update) return fail(MILE_ERR_STATE, "row windows are for mile_logpost_grad only");
     const int F = s->spec.in_features;
     gp.X = s->X + (size_t)s->win_begin * F;
@@ -1442,6 +1509,8 @@ static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t s
     HIP_TRY(e);
   } else if (kernel == MILE_GRAD_MFMA_NARROW_F32) {
     HIP_TRY(launch_narrow(s, gp, E, st));
+  } else if (kernel == MILE_GRAD_LENETTI_F32) {
+    HIP_TRY(launch_lenetti(s, theta, E, gp.X, gp.y, gp.N, S, gp.dp, nullptr, st));
   } else if (kernel == MILE_GRAD_LENET_F32 || kernel == MILE_GRAD_LENET_BF16) {
     const int rc = run_lenet(s, theta, E, gp.X, gp.y, gp.N, gp.slabs, gp.dp, gp.llpart, nullptr, 0, st, kernel == MILE_GRAD_LENET_BF16);
     if (rc) return rc;
@@ -1655,6 +1724,14 @@ extern "C" int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, in
   pp.spec = s->ds; pp.theta = theta; pp.X = s->ev_X; pp.Xp = s->ev_Xp; pp.y = s->ev_y; pp.out = out;
   pp.N = (int)N; pp.Npad = Npad; pp.Fp = Fp; pp.R = generic_R(s->ds);
   const int kernel = resolved_kernel(s);
+  if (kernel == MILE_GRAD_LENETTI_F32) {
+    const int SB = std::max(1, std::min({64, (2 * s->n_cu + S - 1) / S, std::max(1, (int)N / 32)}));
+    for (int s0 = 0; s0 < S; s0 += 65535) {
+      const int Sc = std::min(65535, S - s0);
+      HIP_TRY(launch_lenetti(s, theta + (size_t)s0 * s->ds.d, Sc, s->ev_X, s->ev_y, (int)N, SB, 0, out + (size_t)s0 * N, st));
+    }
+    return MILE_OK;
+  }
   if (kernel == MILE_GRAD_LENET_F32 || kernel == MILE_GRAD_LENET_BF16) {
     for (int s0 = 0; s0 < S; s0 += 256) {
       const int rc = run_lenet(s, theta + (size_t)s0 * s->ds.d, std::min(256, S - s0), s->ev_X, s->ev_y, (int)N, nullptr, 0, nullptr, out, s0, st,
@@ -1717,6 +1794,9 @@ int32_t mile_grad_launch_info(const mile_sampler *s, int32_t E, int32_t *grid_x,
     if (block) *block = 64 * (narrow_tiles_hidden(s->spec) >= 3 ? NRW_MAXW : narrow_waves(s, S, s->N));
     lds = narrow_tiles_hidden(s->spec) >= 3 ? NarrowLayout<3, 4, 4, true>::BYTES      // upper bounds over the instantiations
                                             : std::max(NarrowLayout<3, 2, 4>::BYTES, NarrowLayout<10, 1, 1>::BYTES);
+  } else if (kernel == MILE_GRAD_LENETTI_F32) {
+    nm = "k_grad_lenetti";
+    lds = (int)lenetti_lds_bytes(s->ng, lenetti_T(s->ng));
   } else if (kernel == MILE_GRAD_LENET_BF16) {
     nm = "k_conv5m_fwd/dx/dw (implicit-GEMM bf16 MFMA) + k_mm3 (Dense, fp32-faithful three-term products)";
     lds = (int)cm_lds_dw(CM_IN8, s->lg.hp1, s->lg.wp1, 0);

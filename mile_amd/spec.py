@@ -142,3 +142,93 @@ class LeNetSpec:
         for v in sh:
             n *= v
         return off + n
+
+
+# geometry the LeNetti kernel (mile_amd/csrc/mile_lenetti.h) supports
+LENETTI_MAX_CHANNELS = 4
+LENETTI_MAX_PIXELS = 2048      # conv-output pixels (H+2)(W+2)
+LENETTI_MAX_OUT = 16
+
+
+@dataclass(frozen=True)
+class LeNettiSpec:
+    """LeNetti (src/models/images/cnns.py:69-121, LeNettiConfig src/config/models/cnns.py) on [N, C, H, W] images:
+    Conv(1, 3x3, pad 2) - act - flatten ((H+2)(W+2) features) - Dense 8 - act - Dense 8 - act - Dense 8 - act - Dense out_dim.
+    Duck-types ModelSpec where the host code needs it, as LeNetSpec does."""
+
+    channels: int
+    height: int
+    width: int
+    out_dim: int
+    activation: str = 'sigmoid'
+    task: str = 'classification'
+    prior: str = 'StandardNormal'
+    prior_loc: float = 0.0
+    prior_scale: float = 1.0
+    use_bias: bool = True
+    root: str = 'core'   # name of the LeNettiCore submodule inside LeNetti (LeNetti.setup)
+
+    def __post_init__(self):
+        if self.activation not in ACTIVATIONS:
+            raise NotImplementedError(f'activation {self.activation!r} (supported: {ACTIVATIONS})')
+        if self.task not in TASKS:
+            raise NotImplementedError(f'Likelihood computation for {self.task} not implemented')
+        if self.prior not in PRIORS:
+            raise NotImplementedError(f'Prior Distribution for {self.prior} is not yet implemented.')
+        if self.prior == 'StandardNormal':
+            object.__setattr__(self, 'prior_loc', 0.0)
+            object.__setattr__(self, 'prior_scale', 1.0)
+        if not self.use_bias:
+            raise NotImplementedError('use_bias=False is not supported')
+        if self.task == 'regr' and self.out_dim != 2:
+            raise ValueError('regression needs out_dim == 2 (mu, log sigma)')
+        if min(self.channels, self.height, self.width, self.out_dim) < 1:
+            raise ValueError('LeNetti: channels, height, width and out_dim must be >= 1')
+        if self.channels > LENETTI_MAX_CHANNELS:
+            raise NotImplementedError(f'LeNetti: at most {LENETTI_MAX_CHANNELS} image channels on the HIP kernel')
+        if self.pixels > LENETTI_MAX_PIXELS:
+            raise NotImplementedError(f'LeNetti: (H+2)*(W+2) = {self.pixels} conv-output pixels, the HIP kernel takes at most '
+                                      f'{LENETTI_MAX_PIXELS}')
+        if self.out_dim > LENETTI_MAX_OUT:
+            raise NotImplementedError(f'LeNetti: out_dim <= {LENETTI_MAX_OUT} on the HIP kernel')
+
+    @property
+    def in_features(self) -> int:
+        return self.channels * self.height * self.width
+
+    @property
+    def pixels(self) -> int:
+        """P: features after the flatten, one per conv-output pixel (one output channel)."""
+        return (self.height + 2) * (self.width + 2)
+
+    @property
+    def hidden_structure(self):          # only its last entry (the output width) is meaningful for LeNetti
+        return (self.out_dim,)
+
+    def leaves(self):
+        """[(dotted name, offset, shape)] in ravel_pytree order: conv1, fc1, fc2, fc3, fc4; bias before kernel;
+        the conv kernel [kh, kw, in, out] as flax stores it."""
+        shapes = [('conv1.bias', (1,)), ('conv1.kernel', (3, 3, self.channels, 1)),
+                  ('fc1.bias', (8,)), ('fc1.kernel', (self.pixels, 8)),
+                  ('fc2.bias', (8,)), ('fc2.kernel', (8, 8)),
+                  ('fc3.bias', (8,)), ('fc3.kernel', (8, 8)),
+                  ('fc4.bias', (self.out_dim,)), ('fc4.kernel', (8, self.out_dim))]
+        out, off = [], 0
+        for name, sh in shapes:
+            out.append((f'{self.root}.{name}', off, sh))
+            n = 1
+            for v in sh:
+                n *= v
+            off += n
+        return out
+
+    @property
+    def n_params(self) -> int:
+        name, off, sh = self.leaves()[-1]
+        n = 1
+        for v in sh:
+            n *= v
+        return off + n
+
+
+IMAGE_SPECS = (LeNetSpec, LeNettiSpec)

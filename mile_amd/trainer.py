@@ -23,7 +23,7 @@ from mile_amd.config import Config
 from mile_amd.dataset import ImageLoader, TabularLoader
 from mile_amd.probabilistic import ProbabilisticModel
 from mile_amd.sampling import inference_loop, join_without_chains
-from mile_amd.spec import LeNetSpec, ModelSpec
+from mile_amd.spec import LeNetSpec, LeNettiSpec, ModelSpec
 from mile_amd.tree import PRNGKey
 
 logger = logging.getLogger(__name__)
@@ -82,16 +82,17 @@ class BDETrainer:
     def build_model(self, config: Config):
         """Data loader, model spec and probabilistic model of a config (also used by evaluate.py)."""
         task = 'regr' if config.data.task == 'regr' else 'classification'
-        if config.model.model == 'LeNet':
+        if config.model.model in ('LeNet', 'LeNetti'):
             if config.data.data_type != 'image':
-                raise ValueError('model LeNet needs data_type: image')
+                raise ValueError(f'model {config.model.model} needs data_type: image')
             self.loader = ImageLoader(config.data, rng=config.rng)
             _, C, H, W = self.loader.train_x.shape
-            self.spec_model = LeNetSpec(channels=C, height=H, width=W, out_dim=config.model.out_dim,
-                                        activation=config.model.activation, task=task)
+            cls = LeNetSpec if config.model.model == 'LeNet' else LeNettiSpec
+            self.spec_model = cls(channels=C, height=H, width=W, out_dim=config.model.out_dim,
+                                  activation=config.model.activation, task=task)
         else:
             if config.data.data_type != 'tabular':
-                raise NotImplementedError('the FCN runs on tabular data; image data goes with model LeNet')
+                raise NotImplementedError('the FCN runs on tabular data; image data goes with model LeNet or LeNetti')
             self.loader = TabularLoader(config.data, rng=config.rng, target_len=config.data.target_len)
             F = self.loader.train_x.shape[-1]
             self.spec_model = ModelSpec(in_features=F, hidden_structure=tuple(config.model.hidden_structure),
