@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MILE_ABI_VERSION 6
+#define MILE_ABI_VERSION 7
 #define MILE_MAX_LAYERS 16
 
 typedef enum mile_status {
@@ -318,6 +318,10 @@ int32_t mile_nuts_warmup(mile_sampler *s, mile_state *state, const mile_nuts_arg
 /* Counter-RNG words/normals exactly as the step kernels draw them (test hook). out [E, d]. */
 int32_t mile_debug_noise(mile_sampler *s, uint64_t seed, const int32_t *particle_ids, int32_t E,
                          int64_t step, int32_t stage, float *out, void *stream);
+
+/* Test hook: how many mid-step update launches of mile_step have drawn the following record launch's Philox noise
+ * (the noise prefill) since mile_create; -1 for a null handle. */
+int64_t mile_debug_prefill_count(const mile_sampler *s);
 
 /* Introspection for bench.py's roofline: name, workgroups and LDS bytes of the grad kernel
  * that the current configuration launches for E particles. */

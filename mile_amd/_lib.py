@@ -7,7 +7,7 @@ from pathlib import Path
 from mile_amd._build import LIB_PATH
 
 MILE_MAX_LAYERS = 16
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 ACTIVATION_IDS = {'relu': 0, 'tanh': 1, 'sigmoid': 2}
 TASK_IDS = {'regr': 0, 'regression': 0, 'classification': 1, 'class': 1}
@@ -125,6 +125,7 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p]),
     'mile_debug_noise': (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
                                      C.c_void_p, C.c_void_p]),
+    'mile_debug_prefill_count': (C.c_int64, [C.c_void_p]),
     'mile_grad_launch_info': (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p, C.c_int32]),
     'mile_nuts_reserve': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -54,6 +54,9 @@ struct mile_sampler {
   float *slabs = nullptr, *llpart = nullptr, *dK = nullptr, *lold = nullptr;
   float *upart = nullptr;               // segmented update (d beyond the one-workgroup forms): partial sums per segment
   int32_t *arrive = nullptr;            // [E_cap] arrival tickets of the fused integrator epilogue (k_grad_w64 SPLIT)
+  float *nzbuf = nullptr;               // [2][nz_E][d] O-step noise a mid-step update launch prefills for the record launch
+  int nz_E = 0;                         // particle rows nzbuf holds (allocated by the first mile_step that prefills)
+  int64_t nz_launches = 0;              // mid-step launches that prefilled noise (mile_debug_prefill_count)
   float *ev_X = nullptr, *ev_Xp = nullptr; void *ev_y = nullptr; int ev_cap = 0;   // evaluation (test) set staging
   float *alt_x = nullptr, *alt_u = nullptr, *alt_g = nullptr, *alt_logp = nullptr;   // ping-pong state of mile_tune
   int grad_kernel = MILE_GRAD_AUTO;
@@ -397,6 +400,9 @@ static void free_ws(mile_sampler *s) {
   s->tune_info = nullptr;
   if (s->arrive) (void)hipFree(s->arrive);
   s->arrive = nullptr;
+  if (s->nzbuf) (void)hipFree(s->nzbuf);
+  s->nzbuf = nullptr;
+  s->nz_E = 0;
   if (s->dbg_buf) (void)hipFree(s->dbg_buf);   // sized from the slab-row capacity
   s->dbg_buf = nullptr;
   s->slabs = s->llpart = s->dK = s->lold = nullptr;
@@ -530,6 +536,9 @@ int32_t mile_set_row_window(mile_sampler *s, int64_t begin, int64_t count) {
   return MILE_OK;
 }
 
+// floats of one of the two noise-prefill arrays in s->nzbuf (E rows of d, rounded up so the second array is 16-byte aligned)
+static size_t nz_stride(int E, int d) { return ((size_t)E * d + 3) / 4 * 4; }
+
 int32_t mile_reserve(mile_sampler *s, int32_t E) {
   if (!s || E < 1) return fail(MILE_ERR_INVALID, "mile_reserve: bad argument");
   if (!s->X) return fail(MILE_ERR_STATE, "mile_reserve: call mile_set_data first");
@@ -602,9 +611,10 @@ static void launch_update_al(const UpdParams &u, int E, int nk, hipStream_t st) 
   const int nqf = u.d >> 2;
   const int nt = std::min(UPD_NT, ((nqf + nk - 1) / nk + 63) / 64 * 64);
   const int kind = SDC ? -1 : upd_kind(u);
+  const int nwg_mid = (u.nz_A || u.nz_B) ? 2 * E : E;   // + E workgroups that prefill the next launch's noise
 #define MILE_UPD_CASE(NK_)                                                                       \
   if constexpr (!SDC) {                                                                          \
-    if (kind == UPD_KIND_MID) { k_update_fast<NK_, AL, SDC, UPD_KIND_MID><<<E, nt, 0, st>>>(u); break; } \
+    if (kind == UPD_KIND_MID) { k_update_fast<NK_, AL, SDC, UPD_KIND_MID><<<nwg_mid, nt, 0, st>>>(u); break; } \
     if (kind == UPD_KIND_REC) { k_update_fast<NK_, AL, SDC, UPD_KIND_REC><<<E, nt, 0, st>>>(u); break; } \
     if (kind == UPD_KIND_TUNE) {                                                                 \
       if (nt <= 768) k_update_fast<NK_, AL, SDC, UPD_KIND_TUNE, 768><<<E, nt, 0, st>>>(u);       \
@@ -670,9 +680,15 @@ static bool launch_update_big(const UpdParams &u, int E, hipStream_t st) {
   return al == 4 ? launch_update_big_al<4, false>(u, E, nk, st) : (al == 2 ? launch_update_big_al<2, false>(u, E, nk, st) : launch_update_big_al<1, false>(u, E, nk, st));
 }
 
+// Whether launch_update runs `u` as the k_update_fast mid-step kind, the one launch that can prefill the next launch's noise
+// (u.nz_A / u.nz_B); for any other launch those fields are ignored.
+static bool update_prefills(const UpdParams &u) {
+  return upd_fast_d(u.d) && !u.sdc && upd_kind(u) == UPD_KIND_MID;
+}
+
 static void launch_update(const UpdParams &u, int E, hipStream_t st) {
   const int nqf = u.d >> 2;
-  if (nqf < 1 || nqf > UPD_NT * UPD_QMAX) {
+  if (!upd_fast_d(u.d)) {
     if (nqf >= 1 && launch_update_big(u, E, st)) return;
     if ((u.d + 3) / 4 <= UPD_NT * UPD_QMAX) { k_update<true><<<E, UPD_NT, 0, st>>>(u); return; }
     if (u.upart && getenv("MILE_NO_UPD_SEG") == nullptr) {   // any d, all CUs: segments of UPD_SEG elements, sums -> chain + apply -> scalars
@@ -687,7 +703,7 @@ static void launch_update(const UpdParams &u, int E, hipStream_t st) {
   }
   // every row base is (pointer + e*d): vector width allowed by d and by the pointers
   int al = (u.d % 4 == 0) ? 4 : ((u.d % 2 == 0) ? 2 : 1);
-  const void *ptrs[] = {u.x, u.u, u.g, u.slabs, u.sdc, u.zA, u.zB, u.out_sample, u.x_in, u.u_in, u.g_in, u.t_avg, u.u_rec};
+  const void *ptrs[] = {u.x, u.u, u.g, u.slabs, u.sdc, u.zA, u.zB, u.out_sample, u.x_in, u.u_in, u.g_in, u.t_avg, u.u_rec, u.nz_A, u.nz_B};
   for (const void *q : ptrs)
     if (q) al = std::min(al, ptr_align(q));
   const int nk = (nqf + UPD_NT - 1) / UPD_NT;
@@ -1929,6 +1945,17 @@ int32_t mile_step(mile_sampler *s, mile_state *state, const mile_step_args *a, v
   probe.zA = a->noise; probe.zB = a->noise; probe.out_sample = a->out_samples;
   const bool fused = fuse_ok(s, kernel, probe);
   if (fused) HIP_TRY(hipMemsetAsync(s->arrive, 0, ((size_t)E * 4 + 15) / 16 * 16, st));   // tickets re-zeroed every call
+  // noise prefill of the record launches (MILE_DEBUG bit 128 turns it off: every launch draws its own noise, as before).
+  // Only Philox calls with the register-cached update can prefill; they allocate the workspace the first time.
+  const char *dv = getenv("MILE_DEBUG");
+  const bool prefill = !fused && !a->noise && upd_fast_d(d) && !(dv && (atoi(dv) & 128));
+  if (prefill && s->nz_E < E) {
+    if (s->nzbuf) HIP_TRY(hipFree(s->nzbuf));
+    s->nzbuf = nullptr;
+    s->nz_E = 0;
+    HIP_TRY(hipMalloc(&s->nzbuf, 2 * nz_stride(s->E_cap, d) * 4));
+    s->nz_E = s->E_cap;
+  }
   int kept = 0;
   for (int i = 0; i < a->n_steps; ++i) {
     const int64_t gstep = a->step_offset + i;
@@ -1939,30 +1966,46 @@ int32_t mile_step(mile_sampler *s, mile_state *state, const mile_step_args *a, v
       u.coef_b2 = b1; u.coef_a = 0.5f;
       launch_update(u, E, st);
     }
+    // grad . B(b1) . O(z2) . record  [ . O(z1') . B(b1) . A(1/2) of the next step ]
+    UpdParams ur = up;
+    {
+      const bool last = (i == a->n_steps - 1);
+      ur.flags = UPD_FROM_SLABS | UPD_B1 | UPD_OA | UPD_RECORD;
+      ur.coef_b1 = b1;
+      ur.zA = noise_at(i, 1); ur.stepA = (uint32_t)gstep; ur.stageA = 1; ur.hA = oso ? 0.5f : 1.0f;
+      if (!last) {
+        ur.flags |= UPD_B2 | UPD_A | (oso ? UPD_OB : 0) | UPD_NO_G;
+        ur.zB = noise_at(i + 1, 0); ur.stepB = (uint32_t)(gstep + 1); ur.stageB = 0; ur.hB = 0.5f;
+        ur.coef_b2 = b1; ur.coef_a = 0.5f;
+      }
+      if (a->out_info) ur.out_info = a->out_info + (size_t)i * E * 3;
+      if (a->out_samples && a->n_thinning > 0 && (gstep % a->n_thinning) == 0) {
+        ur.out_sample = a->out_samples + (size_t)kept * Ed;
+        ++kept;
+      }
+    }
     {  // grad . B(1 - 2 b1) . A(1/2)
       UpdParams u = up;
       u.flags = UPD_FROM_SLABS | UPD_B1 | UPD_A | UPD_NO_G;
       u.coef_b1 = b2; u.coef_a = 0.5f;
+      // Philox noise of the record launch: drawn by E extra workgroups of this launch (the update kernel of the record launch
+      // fills only E of the chip's CUs) and read back through the record launch's explicit-noise path -- the same numbers.
+      if (prefill && update_prefills(u)) {
+        ++s->nz_launches;
+        if (!ur.zA) {
+          u.nz_A = s->nzbuf; u.nz_stepA = ur.stepA; u.nz_stageA = ur.stageA;
+          ur.zA = u.nz_A;
+        }
+        if ((ur.flags & UPD_OB) && !ur.zB) {
+          u.nz_B = s->nzbuf + nz_stride(s->nz_E, d); u.nz_stepB = ur.stepB; u.nz_stageB = ur.stageB;
+          ur.zB = u.nz_B;
+        }
+      }
       const int rc = grad_then_update(s, state->position, E, u, fused, st);
       if (rc) return rc;
     }
-    {  // grad . B(b1) . O(z2) . record  [ . O(z1') . B(b1) . A(1/2) of the next step ]
-      UpdParams u = up;
-      const bool last = (i == a->n_steps - 1);
-      u.flags = UPD_FROM_SLABS | UPD_B1 | UPD_OA | UPD_RECORD;
-      u.coef_b1 = b1;
-      u.zA = noise_at(i, 1); u.stepA = (uint32_t)gstep; u.stageA = 1; u.hA = oso ? 0.5f : 1.0f;
-      if (!last) {
-        u.flags |= UPD_B2 | UPD_A | (oso ? UPD_OB : 0) | UPD_NO_G;
-        u.zB = noise_at(i + 1, 0); u.stepB = (uint32_t)(gstep + 1); u.stageB = 0; u.hB = 0.5f;
-        u.coef_b2 = b1; u.coef_a = 0.5f;
-      }
-      if (a->out_info) u.out_info = a->out_info + (size_t)i * E * 3;
-      if (a->out_samples && a->n_thinning > 0 && (gstep % a->n_thinning) == 0) {
-        u.out_sample = a->out_samples + (size_t)kept * Ed;
-        ++kept;
-      }
-      const int rc = grad_then_update(s, state->position, E, u, fused, st);
+    {
+      const int rc = grad_then_update(s, state->position, E, ur, fused, st);
       if (rc) return rc;
     }
   }
@@ -2145,6 +2188,8 @@ int32_t mile_debug_noise(mile_sampler *s, uint64_t seed, const int32_t *particle
   HIP_TRY(hipGetLastError());
   return MILE_OK;
 }
+
+int64_t mile_debug_prefill_count(const mile_sampler *s) { return s ? s->nz_launches : -1; }
 
 int32_t mile_nuts_reserve(mile_sampler *s, int32_t E, int32_t max_num_doublings) {
   if (!s || E < 1 || max_num_doublings < 1 || max_num_doublings > NUTS_MAX_DOUBLINGS)

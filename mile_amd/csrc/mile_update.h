@@ -65,6 +65,10 @@ struct UpdParams {
   float *u_rec;                  // [E, d] momentum at the record point (nan_to_num'd), or NULL: plain record launch
   float *x_acc;                  // [E, d] == x_in, writable: a rejected chain gets bk_x back here
   int32_t force_restart;         // test hook (MILE_TUNE_FORCE_RESTART): every chain takes the restart path of the merged launch
+  // ---- noise prefill (k_update_fast launched with 2E workgroups): workgroups E..2E-1 write the NEXT update launch's O-step
+  // normals, the same philox_normal4 counters that launch would use, so that it reads them through its explicit-noise path ----
+  float *nz_A, *nz_B;            // [E, d] each, or NULL: that noise is not prefilled
+  uint32_t nz_stepA, nz_stageA, nz_stepB, nz_stageB;
 };
 
 // B / O chain on the coefficients of {u, e, zA, zB}; norms and projections come from the
@@ -924,10 +928,47 @@ __device__ __forceinline__ void upd_tune_restart(const UpdParams &p, const int e
 // MAXT: the launch bound.  A launch never uses more threads than the quads need (d = 8834: 768), and a kernel promised
 // <= 768 threads may use 170 registers instead of 128: the warm-up record kind (two coefficient sets, the restart path) spilled
 // 19 VGPRs / 45 SGPRs under the 1024-thread bound.
+// Noise prefill of particle e (the workgroups E..2E-1 of a k_update_fast launch): element 4q + m of a row is lane m of
+// philox_normal4(q, ...), the tail elements included -- exactly what upd_fast_body draws for them.
+template <int NK, int AL>
+__device__ __forceinline__ void upd_noise_body(const UpdParams &p, const int e, const int tid, const int nt) {
+  const int d = p.d, nqf = d >> 2, ntail = d & 3;
+  const size_t base = (size_t)e * d;
+  const uint32_t pid = p.pids ? (uint32_t)p.pids[e] : (uint32_t)e;
+#pragma unroll
+  for (int k = 0; k < NK; ++k) {
+    const int q = tid + k * nt;
+    if (q < nqf) {
+      if (p.nz_A) st4<AL>(p.nz_A + base + 4 * (size_t)q, philox_normal4(q, pid, p.nz_stepA, p.nz_stageA, p.seed));
+      if (p.nz_B) st4<AL>(p.nz_B + base + 4 * (size_t)q, philox_normal4(q, pid, p.nz_stepB, p.nz_stageB, p.seed));
+    }
+  }
+  if (ntail && tid == 0) {
+    const size_t o = base + 4 * (size_t)nqf;
+    if (p.nz_A) {
+      const f32x4 z = philox_normal4(nqf, pid, p.nz_stepA, p.nz_stageA, p.seed);
+      for (int t = 0; t < ntail; ++t) p.nz_A[o + t] = z[t];
+    }
+    if (p.nz_B) {
+      const f32x4 z = philox_normal4(nqf, pid, p.nz_stepB, p.nz_stageB, p.seed);
+      for (int t = 0; t < ntail; ++t) p.nz_B[o + t] = z[t];
+    }
+  }
+}
+
 template <int NK, int AL, bool SDC, int CF = -1, int MAXT = UPD_NT>
 static __global__ __launch_bounds__(MAXT) void k_update_fast(const UpdParams p) {
   __shared__ float red[UPD_NW][UPD_NSUM + 1];
   __shared__ float bc[16];
+  // Launched with 2E workgroups when the next update's noise is prefilled (only the mid-step kind: the record launch that
+  // follows it would otherwise run 2 x d Philox normals per particle on the E CUs it occupies while the other half of the chip
+  // idles).  The two halves share nothing, so correctness does not depend on where they are placed.
+  if constexpr (CF == UPD_KIND_MID) {
+    if ((int)blockIdx.x >= p.E) {
+      upd_noise_body<NK, AL>(p, blockIdx.x - p.E, threadIdx.x, blockDim.x);
+      return;
+    }
+  }
   // launched with the fewest waves that still give NK quads per thread (nt = blockDim.x <= UPD_NT, a multiple of 64): the
   // kernel is VALU-bound on half the chip (E workgroups), so idle padded lanes cost real time (d = 8834: 768 threads, not 1024)
   const bool again = upd_fast_body<NK, AL, SDC, false, CF>(p, blockIdx.x, threadIdx.x, blockDim.x, red, bc);
@@ -955,6 +996,9 @@ static inline int upd_kind(const UpdParams &u) {
   if (u.flags == UPD_KIND_TUNE && u.u_rec) return UPD_KIND_TUNE;
   return -1;
 }
+
+// d whose update launches run the register-cached k_update_fast
+static inline bool upd_fast_d(int d) { return (d >> 2) >= 1 && (d >> 2) <= UPD_NT * UPD_QMAX; }
 
 #define AUX_NT 256
 // Element i of the log-posterior gradient from the grad kernel's partial-gradient slabs (sl = this particle's S slab rows)

@@ -495,6 +495,10 @@ class Engine:
     def supports_device_tuner(self) -> bool:
         return self.d >= 4
 
+    def debug_prefill_count(self) -> int:
+        """Mid-step update launches so far whose E extra workgroups drew the record launch's noise (test hook)."""
+        return int(self.lib.mile_debug_prefill_count(self._h))
+
     def debug_noise(self, seed: int, E: int, step: int, stage: int, particle_ids=None):
         ids = self._ids(particle_ids, E)
         out = torch.empty((E, self.d), dtype=torch.float32, device=self.device)
