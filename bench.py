@@ -23,7 +23,10 @@ samples of its chunk -- as DIR/<name>.npy (float32), at most 64 MB in all: over 
 [..., d] array keeps the same fixed, seeded sample of parameter columns.
 
 Prints ONE JSON line on rank 0.  `value` = particles x steps / wall seconds over all ranks.
-The default run adds BASELINE configs[2..4] (B3, B4, B5) as bounded secondary legs inside the same line.
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs.
+--full adds what else the benchmark measures, after the timed region: the `roofline` pass (HIP events around every grad
+launch), the host `cpu_baseline` and, for the default B2 run on one rank, BASELINE configs[2..4] (B3, B4, B5) as
+bounded secondary legs inside the same line; --no-kernel-timing, --no-cpu-baseline and --no-secondary drop parts of it.
 """
 from __future__ import annotations
 
@@ -71,7 +74,7 @@ WORKLOADS = {
                     'softmax head, StandardNormal prior, d=83126, 32 particles per GPU (of 256 over 8); convolution products as '
                     'implicit GEMMs on bf16 MFMA (bf16 operands, fp32 accumulation), Dense layers / integrator fp32'),
 }
-# bounded secondary legs of the default run: (workload, steps per repetition, warm-up steps)
+# bounded secondary legs of the --full run: (workload, steps per repetition, warm-up steps)
 SECONDARY = (('B3', 10, 3), ('B4', 2, 1), ('B5', 10, 2))
 DUMP_BUDGET_BYTES = 64 * 10**6 - 2**16     # 64 MB in all, .npy headers included
 DUMP_SEED = 0
@@ -422,7 +425,7 @@ class Leg:
 
 
 def secondary_leg(name, k2, w2, args, dev, torch):
-    """One bounded secondary leg of the default run: the same measurement protocol, a few steps per repetition."""
+    """One bounded secondary leg of the --full run: the same measurement protocol, a few steps per repetition."""
     leg2 = Leg(name, args, None, 0, 1, dev, gather_cpu=False)
     tm2 = leg2.measure(k2, w2, budget_s=0.5, min_reps=3, max_reps=5)
     return {
@@ -435,7 +438,7 @@ def secondary_leg(name, k2, w2, args, dev, torch):
         'cpu_baseline': None if args.no_cpu_baseline else leg2.cpu()}
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--workload', default=WORKLOAD, choices=sorted(WORKLOADS))
@@ -443,9 +446,12 @@ def main():
     ap.add_argument('--warmup', type=int, default=None)
     ap.add_argument('--ensemble', type=int, default=None, help='particles per GPU')
     ap.add_argument('--grad-kernel', default=None)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-timing', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the bounded B3 / B4 / B5 legs of the default run')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run the roofline pass, the CPU baseline and (B2 on one rank) the bounded '
+                         'B3 / B4 / B5 legs; a plain run does only what the headline figure needs')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='--full without the roofline pass')
+    ap.add_argument('--no-secondary', action='store_true', help='--full without the bounded B3 / B4 / B5 legs')
     ap.add_argument('--async-gather', action='store_true',
                     help='N > 1: overlap each chunk\'s RCCL all-gather with the next chunk (default: ordered on the compute stream)')
     ap.add_argument('--force-dist', action='store_true', help='init the process group even for 1 rank (rehearsal)')
@@ -454,7 +460,11 @@ def main():
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last step of the timed path returned as DIR/<name>.npy '
                          '(float32, at most 64 MB in all)')
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = arg_parser().parse_args()
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
     if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
@@ -513,7 +523,7 @@ def main():
         dumped = dump_outputs(args.dump_outputs, arrays, leg.state.position.shape[-1])
 
     roof = None
-    if rank == 0 and not args.no_kernel_timing:
+    if rank == 0 and args.full and not args.no_kernel_timing:
         # a second pass of the same workload with HIP events around every grad launch: ~100-200 steps where a step is
         # microseconds (B2), the timed step count where it is tens of milliseconds or more (B3, B4)
         roof = leg.roofline(min(max(args.steps, 100), 200) if el / args.steps < 2e-3 else args.steps, args)
@@ -521,7 +531,8 @@ def main():
         dist.barrier()
 
     secondary = None
-    if world == 1 and args.workload == 'B2' and not args.no_secondary and args.ensemble is None and args.grad_kernel is None:
+    if (args.full and world == 1 and args.workload == 'B2' and not args.no_secondary and args.ensemble is None
+            and args.grad_kernel is None):
         # BASELINE configs[2..4] (B3, B4 per GPU, B5 per GPU), bounded: a few steps per repetition, 1-16 particles on the CPU side
         secondary = {}
         for name, k2, w2 in SECONDARY:
@@ -532,7 +543,7 @@ def main():
             torch.cuda.empty_cache()
 
     if rank == 0:
-        cpu = None if args.no_cpu_baseline else leg.cpu()
+        cpu = leg.cpu() if args.full and not args.no_cpu_baseline else None
         E = leg.E
         value = E * world * args.steps / el
         out = {

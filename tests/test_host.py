@@ -606,7 +606,7 @@ def test_bench_gpus_n_starts_n_ranks_without_a_launcher():
 
 def test_bench_workloads_name_every_baseline_config():
     """bench.py's workloads against BASELINE.json's configs and the oracle's shapes: B2 the default, B3 / B4 / B5 bounded secondary
-    legs of the default run; the FLOP models the roofline fields are priced with against hand counts."""
+    legs of the --full run; the FLOP models the roofline fields are priced with against hand counts."""
     import importlib.util, json
     spec = importlib.util.spec_from_file_location('bench_mod', ROOT / 'bench.py')
     bench = importlib.util.module_from_spec(spec)
@@ -626,6 +626,20 @@ def test_bench_workloads_name_every_baseline_config():
     assert bench.grad_flops_per_particle(5, (64, 64, 64, 2), 1052) == 1052 * (6 * (5 * 64 + 64 * 64 * 2 + 64 * 2) - 2 * 5 * 64)
     m1, m2, md = 32 * 32 * 75 * 6, 12 * 12 * 150 * 16, 576 * 120 + 120 * 84 + 84 * 10
     assert bench.lenet_grad_flops_per_particle(3, 32, 32, 10, 4000) == 4000 * (6 * (m1 + m2 + md) - 2 * m1)
+
+
+def test_bench_extras_only_with_full():
+    """bench.py's --full (roofline pass, CPU baseline, secondary legs) is off by default and combines with the --no-* options
+    that drop parts of it; what each run prints is checked on the GPU in tests/test_gpu_bench.py."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', ROOT / 'bench.py')
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    ap = bench.arg_parser()
+    plain = ap.parse_args(['--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert not plain.full and (plain.steps, plain.warmup) == (20, 5)
+    full = ap.parse_args(['--full', '--no-secondary'])
+    assert full.full and full.no_secondary and not full.no_cpu_baseline and not full.no_kernel_timing
 
 
 def test_bench_dump_outputs_within_budget_and_fixed_sample(tmp_path):
