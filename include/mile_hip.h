@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MILE_ABI_VERSION 7
+#define MILE_ABI_VERSION 8
 #define MILE_MAX_LAYERS 16
 
 typedef enum mile_status {
@@ -81,13 +81,18 @@ typedef enum mile_grad_kernel {
   MILE_GRAD_LENET_BF16 = 9,       /* MILE_MODEL_LENET, <= 4 image channels: the five convolution products as implicit GEMMs on
                                      v_mfma_f32_16x16x32_bf16 with bf16-ROUNDED operands (BASELINE config 5 names bf16), the rest
                                      as LENET_F32; explicit only */
-  MILE_GRAD_LENETTI_F32 = 11      /* MILE_MODEL_LENETTI only (and its only kernel; AUTO resolves to it): one fused fp32 forward +
+  MILE_GRAD_LENETTI_F32 = 11,     /* MILE_MODEL_LENETTI only (and its only kernel; AUTO resolves to it): one fused fp32 forward +
                                      backward launch, k_grad_lenetti (mile_lenetti.h); <= 4 image channels, (H+2)(W+2) <= 2048,
                                      out_dim <= 16 */
+  MILE_GRAD_ATTN_F32 = 12         /* MILE_MODEL_ATTN only (and its only kernel; AUTO resolves to it): one fused fp32 forward +
+                                     backward launch, k_grad_attn (mile_attn.h), products on v_mfma_f32_16x16x4_f32; T <= 128,
+                                     C <= 64, D <= 64 with H | D, <= 2 projections of width <= 64, n_classes <= 16, and
+                                     <= 160 KB of LDS per workgroup (refused otherwise: H = 3, D in {57, 60, 63} with
+                                     T > 112) */
 } mile_grad_kernel;
-/* Which network: the FCN (src/models/tabular/fcn.py:16-28), LeNet (src/models/images/cnns.py:10-66) or LeNetti
- * (src/models/images/cnns.py:69-121). */
-typedef enum mile_model { MILE_MODEL_FCN = 0, MILE_MODEL_LENET = 1, MILE_MODEL_LENETTI = 2 } mile_model;
+/* Which network: the FCN (src/models/tabular/fcn.py:16-28), LeNet (src/models/images/cnns.py:10-66), LeNetti
+ * (src/models/images/cnns.py:69-121) or AttentionClassifier (src/models/text/attention_classifier.py). */
+typedef enum mile_model { MILE_MODEL_FCN = 0, MILE_MODEL_LENET = 1, MILE_MODEL_LENETTI = 2, MILE_MODEL_ATTN = 3 } mile_model;
 
 /* FCNConfig (src/config/models/fcn.py:7-30) + PriorConfig (src/config/sampler.py:60-95)
  * + Task: everything log_unnormalized_posterior (src/training/probabilistic.py:115-138)
@@ -101,15 +106,27 @@ typedef struct mile_model_spec {
   int32_t prior;                     /* mile_prior */
   float prior_loc;
   float prior_scale;
-  int32_t use_bias;                  /* FCNConfig.use_bias; only 1 is supported */
+  int32_t use_bias;                  /* FCNConfig.use_bias; only 1 is supported (ATTN: AttentionClassifierConfig.bias, 0 or 1) */
   int32_t model;                     /* mile_model.  LENET: X rows are NCHW images, in_features = C*H*W,
                                       * n_layers = 1 and widths[0] = out_dim; parameter order is ravel_pytree's
                                       * (conv1, conv2, fc1, fc2, fc3; bias before kernel [kh,kw,in,out]).
                                       * LENETTI: the same conventions; parameters conv1 (3x3, 1 output channel), fc1
-                                      * ((H+2)(W+2) -> 8), fc2, fc3 (8 -> 8), fc4 (8 -> out_dim) */
+                                      * ((H+2)(W+2) -> 8), fc2, fc3 (8 -> 8), fc4 (8 -> out_dim).
+                                      * ATTN: X rows are T token ids stored as fp32 (exact below 2^24; the host checks
+                                      * 0 <= id < vocab_size, 0 is the pad id), in_features = ctx_len = T, task
+                                      * classification, widths = projection_dim + [n_classes] (n_layers = 1..3).
+                                      * Parameters in ravel_pytree order (sorted keys, bias before kernel; biases only
+                                      * with use_bias): MDPA.key [C,H,hd], MDPA.out [H,hd,C], MDPA.query, MDPA.value,
+                                      * TokenEmbedding_0.Embedding.embedding [V,C], .PositionEmbedding.embedding [T,C],
+                                      * classifier [P_last,K], projection_0 [C,P_0], projection_1 [P_0,P_1] */
   int32_t img_c;                     /* LENET / LENETTI image geometry (ignored for the FCN) */
   int32_t img_h;
   int32_t img_w;
+  int32_t vocab_size;                /* ATTN geometry (ignored otherwise): V */
+  int32_t ctx_len;                   /* T (== in_features) */
+  int32_t emb_size;                  /* C */
+  int32_t n_heads;                   /* H */
+  int32_t qkv_dim;                   /* D; H divides D, head size hd = D / H */
 } mile_model_spec;
 
 /* blackjax IntegratorState(position, momentum, logdensity, logdensity_grad) for an
@@ -242,7 +259,9 @@ int32_t mile_destroy(mile_sampler *s);
 int64_t mile_param_count(const mile_sampler *s);
 
 /* Offsets of layer `layer`'s bias and kernel inside the raveled vector (ravel_pytree order).  LENET: layers 0..4 = conv1, conv2,
- * fc1, fc2, fc3; LENETTI: layers 0..4 = conv1, fc1, fc2, fc3, fc4. */
+ * fc1, fc2, fc3; LENETTI: layers 0..4 = conv1, fc1, fc2, fc3, fc4; ATTN: layers 0..3 = MDPA key, out, query, value,
+ * 4 = Embedding (kernel = the table, no bias), 5 = PositionEmbedding, 6 = classifier, 7.. = projection_0, projection_1.
+ * A missing bias (use_bias = 0) has offset -1. */
 int32_t mile_param_offsets(const mile_sampler *s, int32_t layer, int64_t *bias_off, int64_t *kernel_off);
 
 /* Replaces: partial(log_unnormalized_posterior, x=train_x, y=train_y)
@@ -252,7 +271,7 @@ int32_t mile_set_data(mile_sampler *s, const float *X, const void *y, int64_t N,
 /* Restrict the likelihood to rows [begin, begin + count) of the training set for the following mile_logpost_grad calls
  * (count = 0: all rows again).  Replaces the minibatches of the warm-start stage: loader.iter(split='train', batch_size=...)
  * (src/dataset/tabular.py:170-212) feeding single_step_regr / single_step_class (src/training/trainer.py:706-760).
- * Supported by MILE_GRAD_GENERIC, the MFMA_NARROW, MFMA_W64, MFMA_WIDE, LENET and LENETTI kernels (mile_logpost_grad fails with MILE_ERR_STATE on
+ * Supported by MILE_GRAD_GENERIC, the MFMA_NARROW, MFMA_W64, MFMA_WIDE, LENET, LENETTI and ATTN kernels (mile_logpost_grad fails with MILE_ERR_STATE on
  * MFMA_W128_BF16 / GEMM_F32 under a window); the MCLMC path itself is full-batch (n_batches = 1). */
 int32_t mile_set_row_window(mile_sampler *s, int64_t begin, int64_t count);
 

@@ -7,7 +7,7 @@ from pathlib import Path
 from mile_amd._build import LIB_PATH
 
 MILE_MAX_LAYERS = 16
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 ACTIVATION_IDS = {'relu': 0, 'tanh': 1, 'sigmoid': 2}
 TASK_IDS = {'regr': 0, 'regression': 0, 'classification': 1, 'class': 1}
@@ -15,7 +15,7 @@ PRIOR_IDS = {'Normal': 0, 'StandardNormal': 0, 'Laplace': 1}
 REFRESH_IDS = {'O-step-O': 0, 'step-O': 1}
 GRAD_KERNEL_IDS = {'auto': 0, 'generic': 1, 'mfma_w64': 2, 'mfma_w128_bf16': 3, 'gemm_f32': 4, 'lenet_f32': 5, 'mfma_w64_bf16x3': 6,
                    'mfma_wide_bf16x3': 7, 'mfma_wide_bf16': 8, 'lenet_bf16': 9, 'mfma_narrow_f32': 10,
-                   'lenetti_f32': 11}
+                   'lenetti_f32': 11, 'attn_f32': 12}
 
 
 class ModelSpecC(C.Structure):
@@ -33,6 +33,11 @@ class ModelSpecC(C.Structure):
         ('img_c', C.c_int32),
         ('img_h', C.c_int32),
         ('img_w', C.c_int32),
+        ('vocab_size', C.c_int32),
+        ('ctx_len', C.c_int32),
+        ('emb_size', C.c_int32),
+        ('n_heads', C.c_int32),
+        ('qkv_dim', C.c_int32),
     ]
 
 

@@ -131,6 +131,35 @@ class LeNettiConfig:
         _check(isinstance(self.out_dim, int) and self.out_dim > 0, 'out_dim must be a positive int')
 
 
+@dataclass(frozen=True)
+class AttentionClassifierConfig:
+    """src/config/models/gpt.py (GPTConfig + AttentionClassifierConfig): same fields, same defaults.  dropout and n_blocks
+    have no effect in this model (its dropout lines are commented out and it has one attention layer)."""
+
+    model: str = 'AttentionClassifier'
+    vocab_size: int = 1000
+    context_len: int = 8
+    emb_size: int = 256
+    n_blocks: int = 6
+    n_heads: int = 8
+    qkv_dim: int = 512
+    bias: bool = False
+    dropout: float = 0.1
+    dtype: str = 'float32'
+    n_classes: int = 2
+    projection_dim: list = field(default_factory=lambda: [32], hash=False)
+
+    def __post_init__(self):
+        _check(self.model == 'AttentionClassifier', f'Could not find model {self.model}.')
+        for k in ('vocab_size', 'context_len', 'emb_size', 'n_blocks', 'n_heads', 'qkv_dim', 'n_classes'):
+            _check(isinstance(getattr(self, k), int) and getattr(self, k) > 0, f'{k} must be a positive int')
+        _check(isinstance(self.projection_dim, (list, tuple)) and all(isinstance(p, int) and p > 0 for p in self.projection_dim),
+               'projection_dim must be a list of positive ints')
+        _check(self.qkv_dim % self.n_heads == 0, 'qkv_dim must be divisible by n_heads')
+        _check(self.dtype in ('float32', 'bfloat16'), f'unknown dtype {self.dtype!r}')
+        _check(self.dtype == 'float32', f'dtype {self.dtype!r} is not implemented on the MI355X path (supported: float32)')
+
+
 def _model_config(data):
     """ModelConfig.from_dict dispatch on the `model` key (src/config/models/__init__.py)."""
     name = data.get('model', 'FCN') if isinstance(data, dict) else 'FCN'
@@ -138,9 +167,12 @@ def _model_config(data):
         return LeNetConfig
     if name == 'LeNetti':
         return LeNettiConfig
+    if name == 'AttentionClassifier':
+        return AttentionClassifierConfig
     if name == 'FCN':
         return FCNConfig
-    raise ConfigError(f"Could not find model {name}. Available on the MI355X hot path: ['FCN', 'LeNet', 'LeNetti']")
+    raise ConfigError(f"Could not find model {name}. Available on the MI355X hot path: ['FCN', 'LeNet', 'LeNetti', "
+                      "'AttentionClassifier']")
 
 
 @dataclass(frozen=True)
@@ -185,7 +217,7 @@ class SamplerConfig:
     def __post_init__(self):
         _check(self.name in ('nuts', 'mclmc', 'hmc', 'mclmc_hip'), f'unknown sampler {self.name!r}')
         _check(self.grad_kernel in ('auto', 'generic', 'mfma_w64', 'mfma_w64_bf16x3', 'mfma_w128_bf16', 'gemm_f32', 'mfma_wide_bf16x3',
-                                    'mfma_wide_bf16', 'lenet_f32', 'lenet_bf16', 'mfma_narrow_f32', 'lenetti_f32'),
+                                    'mfma_wide_bf16', 'lenet_f32', 'lenet_bf16', 'mfma_narrow_f32', 'lenetti_f32', 'attn_f32'),
                f'unknown grad_kernel {self.grad_kernel!r}')
 
     @property

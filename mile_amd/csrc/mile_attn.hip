@@ -1,0 +1,58 @@
+// AttentionClassifier kernels (mile_attn.h) in a translation unit of their own.  The dK register tiles per key tile
+// (ceil(hd / 16): 1..4) and whether Wq|Wk|Wv fit in LDS next to the sequence are template arguments.
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+
+#include "mile_attn.h"
+
+#define ATTN_MAX_DEVICES 64
+
+// hipFuncSetAttribute is per device: one flag per (device, instantiation)
+template <int NHT, bool WL>
+static hipError_t attn_set_lds(size_t lds) {
+  static std::atomic<bool> done[ATTN_MAX_DEVICES];
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev >= 0 && dev < ATTN_MAX_DEVICES && done[dev].load(std::memory_order_acquire)) return hipSuccess;
+  (void)lds;
+  e = hipFuncSetAttribute((const void *)k_grad_attn<NHT, WL>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LDS_MAX);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_fwd_attn<NHT, WL>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LDS_MAX);
+  if (e != hipSuccess) return e;
+  if (dev >= 0 && dev < ATTN_MAX_DEVICES) done[dev].store(true, std::memory_order_release);
+  return hipSuccess;
+}
+
+template <int NHT, bool WL>
+static hipError_t launch_t(const AttnParams &p, int E, bool grad, hipStream_t st) {
+  const size_t lds = attn_lds_bytes(p.g, WL);
+  hipError_t e = attn_set_lds<NHT, WL>(lds);
+  if (e != hipSuccess) return e;
+  const dim3 grid(p.S, E);
+  if (grad) k_grad_attn<NHT, WL><<<grid, ATTN_NT, lds, st>>>(p);
+  else k_fwd_attn<NHT, WL><<<grid, ATTN_NT, lds, st>>>(p);
+  return hipGetLastError();
+}
+
+template <bool WL>
+static hipError_t launch_w(const AttnParams &p, int E, bool grad, hipStream_t st) {
+  switch ((p.g.hd + 15) / 16) {
+    case 1: return launch_t<1, WL>(p, E, grad, st);
+    case 2: return launch_t<2, WL>(p, E, grad, st);
+    case 3: return launch_t<3, WL>(p, E, grad, st);
+    case 4: return launch_t<4, WL>(p, E, grad, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t mile_launch_attn(const AttnParams &p, int E, bool grad, hipStream_t st) {
+  const AttnGeom &g = p.g;
+  if (g.T < 1 || g.T > ATTN_MAX_T || g.C < 1 || g.C > ATTN_MAX_C || g.D < 1 || g.D > ATTN_MAX_D || g.H < 1 || g.D % g.H ||
+      g.K < 1 || g.K > ATTN_MAX_K || g.NP < 0 || g.NP > ATTN_MAX_NP || g.Tp != (g.T + 15) / 16 * 16 || g.V < 1)
+    return hipErrorInvalidValue;
+  for (int l = 0; l < g.NP; ++l)
+    if (g.P[l] < 1 || g.P[l] > ATTN_MAX_P) return hipErrorInvalidValue;
+  if (attn_lds_bytes(g, false) > ATTN_LDS_MAX) return hipErrorInvalidValue;
+  return attn_weights_in_lds(g) ? launch_w<true>(p, E, grad, st) : launch_w<false>(p, E, grad, st);
+}

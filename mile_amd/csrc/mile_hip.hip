@@ -22,6 +22,7 @@
 #include "mile_lenet.h"
 #include "mile_lenet_mfma.h"
 #include "mile_lenetti.h"
+#include "mile_attn.h"
 #include "mile_predict.h"
 #include "mile_update.h"
 #include "mile_nuts.h"
@@ -62,6 +63,7 @@ struct mile_sampler {
   int grad_kernel = MILE_GRAD_AUTO;
   LeNetGeom lg{};                       // MILE_MODEL_LENET geometry and parameter offsets
   LeNettiGeom ng{};                     // MILE_MODEL_LENETTI geometry and parameter offsets
+  AttnGeom ag{};                        // MILE_MODEL_ATTN geometry and parameter offsets
   // layer-wise GEMM path (MILE_GRAD_GEMM_F32): rocBLAS handle and activation workspace
   void *blas = nullptr;
   long long *dbg_buf = nullptr;         // dev instrumentation (MILE_DEBUG=16)
@@ -175,6 +177,7 @@ static bool w128b_supported(const mile_model_spec &sp) {
 
 static int resolved_kernel(const mile_sampler *s) {
   if (s->spec.model == MILE_MODEL_LENETTI) return MILE_GRAD_LENETTI_F32;
+  if (s->spec.model == MILE_MODEL_ATTN) return MILE_GRAD_ATTN_F32;
   if (s->spec.model == MILE_MODEL_LENET) return s->grad_kernel == MILE_GRAD_LENET_BF16 ? MILE_GRAD_LENET_BF16 : MILE_GRAD_LENET_F32;
   if (s->grad_kernel == MILE_GRAD_AUTO) {
     if (w64x3_supported(s->spec)) return MILE_GRAD_MFMA_W64_BF16X3;   // fp32-faithful and never slower than MFMA_W64
@@ -219,8 +222,15 @@ static int lenetti_S(const mile_sampler *s, int E) {
   return std::max(1, std::min({64, want, std::max(1, s->N / 32)}));
 }
 
+// k_grad_attn: one workgroup per CU (its LDS), at most 64 row ranges and at least 16 sequences per range
+static int attn_S(const mile_sampler *s, int E) {
+  const int want = (s->n_cu + std::max(E, 1) - 1) / std::max(E, 1);
+  return std::max(1, std::min({64, want, std::max(1, s->N / 16)}));
+}
+
 static int choose_S(const mile_sampler *s, int E, int kernel) {
   if (kernel == MILE_GRAD_MFMA_NARROW_F32) return narrow_S(s, E);
+  if (kernel == MILE_GRAD_ATTN_F32) return attn_S(s, E);
   if (kernel == MILE_GRAD_LENETTI_F32) return lenetti_S(s, E);
   if (is_w64(kernel)) {
     const int NB = s->Npad / 32;
@@ -250,7 +260,7 @@ int32_t mile_create(const mile_model_spec *spec, int32_t device, mile_sampler **
   if (!spec || !out) return fail(MILE_ERR_INVALID, "mile_create: null argument");
   if (spec->n_layers < 1 || spec->n_layers > MILE_MAX_LAYERS) return fail(MILE_ERR_INVALID, "n_layers out of range");
   if (spec->in_features < 1) return fail(MILE_ERR_INVALID, "in_features must be >= 1");
-  if (!spec->use_bias) return fail(MILE_ERR_INVALID, "use_bias=false is not supported");
+  if (!spec->use_bias && spec->model != MILE_MODEL_ATTN) return fail(MILE_ERR_INVALID, "use_bias=false is not supported");
   if (spec->activation < 0 || spec->activation > MILE_ACT_SIGMOID) return fail(MILE_ERR_INVALID, "unknown activation");
   if (spec->task != MILE_TASK_REGRESSION && spec->task != MILE_TASK_CLASSIFICATION) return fail(MILE_ERR_INVALID, "unknown task");
   if (spec->prior != MILE_PRIOR_NORMAL && spec->prior != MILE_PRIOR_LAPLACE) return fail(MILE_ERR_INVALID, "unknown prior");
@@ -259,8 +269,23 @@ int32_t mile_create(const mile_model_spec *spec, int32_t device, mile_sampler **
     if (spec->widths[l] < 1) return fail(MILE_ERR_INVALID, "layer width must be >= 1");
   if (spec->task == MILE_TASK_REGRESSION && spec->widths[spec->n_layers - 1] != 2)
     return fail(MILE_ERR_INVALID, "regression needs an output layer of width 2 (mu, log sigma)");
-  if (spec->model != MILE_MODEL_FCN && spec->model != MILE_MODEL_LENET && spec->model != MILE_MODEL_LENETTI)
+  if (spec->model != MILE_MODEL_FCN && spec->model != MILE_MODEL_LENET && spec->model != MILE_MODEL_LENETTI &&
+      spec->model != MILE_MODEL_ATTN)
     return fail(MILE_ERR_INVALID, "unknown model");
+  if (spec->model == MILE_MODEL_ATTN) {
+    if (spec->task != MILE_TASK_CLASSIFICATION) return fail(MILE_ERR_INVALID, "AttentionClassifier: classification only");
+    if (spec->n_layers < 1 || spec->n_layers > ATTN_MAX_NP + 1)
+      return fail(MILE_ERR_INVALID, "AttentionClassifier: widths = projection_dim (at most 2) + [n_classes]");
+    if (spec->ctx_len < 1 || spec->ctx_len > ATTN_MAX_T || spec->in_features != spec->ctx_len)
+      return fail(MILE_ERR_INVALID, "AttentionClassifier: 1 <= ctx_len <= 128 and in_features == ctx_len");
+    if (spec->emb_size < 1 || spec->emb_size > ATTN_MAX_C) return fail(MILE_ERR_INVALID, "AttentionClassifier: emb_size <= 64");
+    if (spec->qkv_dim < 1 || spec->qkv_dim > ATTN_MAX_D || spec->n_heads < 1 || spec->qkv_dim % spec->n_heads)
+      return fail(MILE_ERR_INVALID, "AttentionClassifier: qkv_dim <= 64 and n_heads dividing it");
+    if (spec->vocab_size < 1 || spec->vocab_size > (1 << 24)) return fail(MILE_ERR_INVALID, "AttentionClassifier: 1 <= vocab_size <= 2^24");
+    for (int l = 0; l + 1 < spec->n_layers; ++l)
+      if (spec->widths[l] > ATTN_MAX_P) return fail(MILE_ERR_INVALID, "AttentionClassifier: projection widths <= 64");
+    if (spec->widths[spec->n_layers - 1] > ATTN_MAX_K) return fail(MILE_ERR_INVALID, "AttentionClassifier: n_classes <= 16");
+  }
   if (spec->model == MILE_MODEL_LENETTI) {
     if (spec->n_layers != 1) return fail(MILE_ERR_INVALID, "LeNetti: n_layers must be 1 (widths[0] = out_dim)");
     if (spec->img_c < 1 || spec->img_h < 1 || spec->img_w < 1 ||
@@ -291,6 +316,42 @@ int32_t mile_create(const mile_model_spec *spec, int32_t device, mile_sampler **
   ds.prior = spec->prior;
   ds.prior_loc = spec->prior_loc;
   ds.prior_scale = spec->prior_scale;
+  if (spec->model == MILE_MODEL_ATTN) {   // ravel_pytree order (sorted keys): MDPA.{key, out, query, value}, TokenEmbedding_0,
+                                          // classifier, projection_*; bias before kernel
+    AttnGeom &g = s->ag;
+    g.V = spec->vocab_size; g.T = spec->ctx_len; g.C = spec->emb_size; g.H = spec->n_heads; g.D = spec->qkv_dim;
+    g.hd = g.D / g.H; g.NP = spec->n_layers - 1; g.K = spec->widths[g.NP]; g.bias = spec->use_bias ? 1 : 0;
+    g.Tp = (g.T + 15) / 16 * 16;
+    for (int l = 0; l < ATTN_MAX_NP; ++l) { g.P[l] = l < g.NP ? spec->widths[l] : 0; g.b_p[l] = g.k_p[l] = -1; }
+    if (attn_lds_bytes(g, false) > ATTN_LDS_MAX) {
+      delete s;
+      return fail(MILE_ERR_INVALID, "AttentionClassifier: shape needs more than 160 KB of LDS");
+    }
+    long long o = 0;
+    auto put = [&](int &b, int &k, long long nb, long long nk) { b = g.bias && nb ? (int)o : -1; o += g.bias ? nb : 0; k = (int)o; o += nk; };
+    int dummy;
+    put(g.b_k, g.k_k, g.D, (long long)g.C * g.D);
+    put(g.b_o, g.k_o, g.C, (long long)g.D * g.C);
+    put(g.b_q, g.k_q, g.D, (long long)g.C * g.D);
+    put(g.b_v, g.k_v, g.D, (long long)g.C * g.D);
+    put(dummy, g.emb, 0, (long long)g.V * g.C);
+    put(dummy, g.pos, 0, (long long)g.T * g.C);
+    put(g.b_c, g.k_c, g.K, (long long)(g.NP ? g.P[g.NP - 1] : g.C) * g.K);
+    for (int l = 0; l < g.NP; ++l) put(g.b_p[l], g.k_p[l], g.P[l], (long long)(l ? g.P[l - 1] : g.C) * g.P[l]);
+    if (o > 0x7fffffffLL) { delete s; return fail(MILE_ERR_INVALID, "AttentionClassifier: too many parameters"); }
+    g.d = (int)o;
+    ds.d = g.d;
+    ds.widths[0] = g.K;
+    ds.b_off[0] = g.b_c; ds.w_off[0] = g.k_c;
+    ds.max_width = 64; ds.act_stride = 0;
+    int cnt = 0;
+    if (hipGetDeviceCount(&cnt) == hipSuccess && device < cnt) {
+      hipDeviceProp_t prop;
+      if (hipGetDeviceProperties(&prop, device) == hipSuccess) s->n_cu = prop.multiProcessorCount;
+    }
+    *out = s;
+    return MILE_OK;
+  }
   if (spec->model == MILE_MODEL_LENETTI) {   // ravel_pytree order of {'core': {conv1, fc1, fc2, fc3, fc4}}: bias, kernel each
     LeNettiGeom &g = s->ng;
     g.C = spec->img_c; g.H = spec->img_h; g.W = spec->img_w; g.K = spec->widths[0];
@@ -453,6 +514,14 @@ int32_t mile_param_offsets(const mile_sampler *s, int32_t layer, int64_t *bias_o
     if (kernel_off) *kernel_off = ko[layer];
     return MILE_OK;
   }
+  if (s && s->spec.model == MILE_MODEL_ATTN) {   // key, out, query, value, Embedding, PositionEmbedding, classifier, projection_*
+    const AttnGeom &g = s->ag;
+    const int bo[8] = {g.b_k, g.b_o, g.b_q, g.b_v, -1, -1, g.b_c, -1}, ko[6] = {g.k_k, g.k_o, g.k_q, g.k_v, g.emb, g.pos};
+    if (layer < 0 || layer >= 7 + g.NP) return fail(MILE_ERR_INVALID, "mile_param_offsets: bad layer");
+    if (bias_off) *bias_off = layer >= 7 ? g.b_p[layer - 7] : bo[layer];
+    if (kernel_off) *kernel_off = layer >= 7 ? g.k_p[layer - 7] : (layer == 6 ? g.k_c : ko[layer]);
+    return MILE_OK;
+  }
   if (s && s->spec.model == MILE_MODEL_LENETTI) {   // layers 0..4 = conv1, fc1, fc2, fc3, fc4
     const LeNettiGeom &g = s->ng;
     const int bo[5] = {g.b_c, g.b_1, g.b_2, g.b_3, g.b_4}, ko[5] = {g.k_c, g.k_1, g.k_2, g.k_3, g.k_4};
@@ -548,6 +617,7 @@ int32_t mile_reserve(mile_sampler *s, int32_t E) {
   if (w128b_supported(s->spec)) S = std::max(S, choose_S(s, E, MILE_GRAD_MFMA_W128_BF16));
   if (narrow_supported(s->spec)) S = std::max(S, choose_S(s, E, MILE_GRAD_MFMA_NARROW_F32));
   if (s->spec.model == MILE_MODEL_LENETTI) S = std::max(S, choose_S(s, E, MILE_GRAD_LENETTI_F32));
+  if (s->spec.model == MILE_MODEL_ATTN) S = std::max(S, choose_S(s, E, MILE_GRAD_ATTN_F32));
   // A smaller ensemble splits the rows of a particle over MORE workgroups (S grows as E shrinks): capacity is counted in
   // slab rows E * S, and a later call with fewer particles must neither fail nor shrink what a larger one reserved.
   if (E <= s->E_cap && (size_t)E * S <= s->ES_cap) return MILE_OK;
@@ -572,7 +642,9 @@ int32_t mile_reserve(mile_sampler *s, int32_t E) {
 
 int32_t mile_set_grad_kernel(mile_sampler *s, int32_t which) {
   if (!s) return fail(MILE_ERR_INVALID, "null handle");
-  if (which < MILE_GRAD_AUTO || which > MILE_GRAD_LENETTI_F32) return fail(MILE_ERR_INVALID, "unknown grad kernel");
+  if (which < MILE_GRAD_AUTO || which > MILE_GRAD_ATTN_F32) return fail(MILE_ERR_INVALID, "unknown grad kernel");
+  if ((s->spec.model == MILE_MODEL_ATTN) != (which == MILE_GRAD_ATTN_F32) && which != MILE_GRAD_AUTO)
+    return fail(MILE_ERR_INVALID, "ATTN_F32 is the kernel of MILE_MODEL_ATTN, and its only one");
   if ((s->spec.model == MILE_MODEL_LENETTI) != (which == MILE_GRAD_LENETTI_F32) && which != MILE_GRAD_AUTO)
     return fail(MILE_ERR_INVALID, "LENETTI_F32 is the kernel of MILE_MODEL_LENETTI, and its only one");
   if (which == MILE_GRAD_MFMA_NARROW_F32 && !narrow_supported(s->spec))
@@ -1459,6 +1531,17 @@ static hipError_t launch_lenetti(mile_sampler *s, const float *theta, int E, con
   return mile_launch_lenetti(lp, E, out_ll == nullptr, st);
 }
 
+// ---- AttentionClassifier (mile_attn.h; the kernels are instantiated in mile_attn.hip).  Gradient (out_ll == nullptr): grid
+// (S row ranges, E chains) -> slabs / llpart; evaluation: grid (S row blocks, E samples) -> out_ll[e * N + row]
+static hipError_t launch_attn(mile_sampler *s, const float *theta, int E, const float *X, const void *y, int N, int S, int dp,
+                              float *out_ll, hipStream_t st) {
+  AttnParams ap{};
+  ap.g = s->ag;
+  ap.theta = theta; ap.X = X; ap.y = y; ap.slabs = s->slabs; ap.llpart = s->llpart; ap.out = out_ll;
+  ap.N = N; ap.S = S; ap.dp = dp;
+  return mile_launch_attn(ap, E, out_ll == nullptr, st);
+}
+
 static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t st, const UpdParams *fused_update) {
   if (!s->X) return fail(MILE_ERR_STATE, "no data: call mile_set_data first");
   const int kernel = resolved_kernel(s);
@@ -1472,9 +1555,10 @@ static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t s
   gp.N = s->N; gp.Npad = s->Npad; gp.Npb = s->Npb; gp.Fp = s->Fp; gp.S = S; gp.R = generic_R(s->ds); gp.dp = (s->ds.d + 3) / 4 * 4;
   if (s->win_count) {   // minibatch: the same kernels on a shifted view of the rows
     const bool chunked = kernel == MILE_GRAD_MFMA_WIDE_BF16X3 || kernel == MILE_GRAD_MFMA_WIDE_BF16 || kernel == MILE_GRAD_LENET_F32 ||
-                         kernel == MILE_GRAD_LENET_BF16 || kernel == MILE_GRAD_LENETTI_F32;   // these walk the rows in chunks anyway: a window is a shorter walk
+                         kernel == MILE_GRAD_LENET_BF16 || kernel == MILE_GRAD_LENETTI_F32 ||
+                         kernel == MILE_GRAD_ATTN_F32;   // these walk the rows in chunks anyway: a window is a shorter walk
     if (kernel != MILE_GRAD_GENERIC && kernel != MILE_GRAD_MFMA_NARROW_F32 && !is_w64(kernel) && !chunked)
-      return fail(MILE_ERR_STATE, "a row window needs the generic, the MFMA_NARROW, an MFMA_W64, an MFMA_WIDE, a LENET or the LENETTI grad kernel");
+      return fail(MILE_ERR_STATE, "a row window needs the generic, the MFMA_NARROW, an MFMA_W64, an MFMA_WIDE, a LENET, the LENETTI or the ATTN grad kernel");
     if (fused_update) return fail(MILE_ERR_STATE, "row windows are for mile_logpost_grad only");
     const int F = s->spec.in_features;
     gp.X = s->X + (size_t)s->win_begin * F;
@@ -1525,6 +1609,8 @@ static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t s
     HIP_TRY(e);
   } else if (kernel == MILE_GRAD_MFMA_NARROW_F32) {
     HIP_TRY(launch_narrow(s, gp, E, st));
+  } else if (kernel == MILE_GRAD_ATTN_F32) {
+    HIP_TRY(launch_attn(s, theta, E, gp.X, gp.y, gp.N, S, gp.dp, nullptr, st));
   } else if (kernel == MILE_GRAD_LENETTI_F32) {
     HIP_TRY(launch_lenetti(s, theta, E, gp.X, gp.y, gp.N, S, gp.dp, nullptr, st));
   } else if (kernel == MILE_GRAD_LENET_F32 || kernel == MILE_GRAD_LENET_BF16) {
@@ -1740,6 +1826,14 @@ extern "C" int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, in
   pp.spec = s->ds; pp.theta = theta; pp.X = s->ev_X; pp.Xp = s->ev_Xp; pp.y = s->ev_y; pp.out = out;
   pp.N = (int)N; pp.Npad = Npad; pp.Fp = Fp; pp.R = generic_R(s->ds);
   const int kernel = resolved_kernel(s);
+  if (kernel == MILE_GRAD_ATTN_F32) {
+    const int SB = std::max(1, std::min({64, (s->n_cu + S - 1) / S, std::max(1, (int)N / 16)}));
+    for (int s0 = 0; s0 < S; s0 += 65535) {
+      const int Sc = std::min(65535, S - s0);
+      HIP_TRY(launch_attn(s, theta + (size_t)s0 * s->ds.d, Sc, s->ev_X, s->ev_y, (int)N, SB, 0, out + (size_t)s0 * N, st));
+    }
+    return MILE_OK;
+  }
   if (kernel == MILE_GRAD_LENETTI_F32) {
     const int SB = std::max(1, std::min({64, (2 * s->n_cu + S - 1) / S, std::max(1, (int)N / 32)}));
     for (int s0 = 0; s0 < S; s0 += 65535) {
@@ -1810,6 +1904,9 @@ int32_t mile_grad_launch_info(const mile_sampler *s, int32_t E, int32_t *grid_x,
     if (block) *block = 64 * (narrow_tiles_hidden(s->spec) >= 3 ? NRW_MAXW : narrow_waves(s, S, s->N));
     lds = narrow_tiles_hidden(s->spec) >= 3 ? NarrowLayout<3, 4, 4, true>::BYTES      // upper bounds over the instantiations
                                             : std::max(NarrowLayout<3, 2, 4>::BYTES, NarrowLayout<10, 1, 1>::BYTES);
+  } else if (kernel == MILE_GRAD_ATTN_F32) {
+    nm = "k_grad_attn";
+    lds = (int)attn_lds_bytes(s->ag, attn_weights_in_lds(s->ag));
   } else if (kernel == MILE_GRAD_LENETTI_F32) {
     nm = "k_grad_lenetti";
     lds = (int)lenetti_lds_bytes(s->ng, lenetti_T(s->ng));

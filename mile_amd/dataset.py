@@ -117,3 +117,69 @@ class ImageLoader:
 
     def __len__(self):
         return len(self.train_x) + len(self.valid_x) + len(self.test_x)
+
+
+class TextLoader:
+    """Token-id data for the AttentionClassifier target: [N, T] integer ids (pad id 0 after the last token) and integer
+    labels, split into train / valid / test.  ``source: synthetic`` (path = '<N>x<T>x<V>') or a local ``.npz`` with
+    ``x`` [N, T] and ``y`` [N].  The reference's imdb download and BPE tokenizer (``source: huggingface``) need the
+    network: tokenize elsewhere and pass the ids as a .npz."""
+
+    def __init__(self, config: DataConfig, rng: int, context_len: int, vocab_size: int, n_classes: int = 2,
+                 shuffle: bool = True):
+        assert config.data_type == 'text'
+        self.config = config
+        g = np.random.Generator(np.random.PCG64(rng))
+        if config.source == 'huggingface':
+            raise NotImplementedError('text data from huggingface needs the network and a tokenizer; tokenize offline and '
+                                      'pass source: local with a .npz holding x [N, T] token ids (0 = pad) and y [N]')
+        if config.source == 'synthetic':
+            N, T, V = (int(v) for v in config.path.lower().split('x'))
+            x, y = synthetic_text(g, N, T, V, n_classes)
+        elif str(config.path).endswith('.npz'):
+            z = np.load(config.path)
+            x, y = np.asarray(z['x']), np.asarray(z['y'])
+            if x.ndim != 2 or y.shape != (x.shape[0],):
+                raise ValueError('text .npz: x must be [N, T] and y [N]')
+            if not np.issubdtype(x.dtype, np.integer) and not np.array_equal(x, np.floor(x)):
+                raise ValueError('text .npz: x must hold integer token ids')
+            x = x.astype(np.int64)
+        else:
+            raise NotImplementedError('text data: only source "synthetic" or a local .npz with x [N, T], y [N]')
+        if x.shape[1] != context_len:
+            raise ValueError(f'text data has T = {x.shape[1]} tokens per row, the model context_len = {context_len}')
+        if x.size and (x.min() < 0 or x.max() >= vocab_size):
+            raise ValueError(f'token ids must lie in [0, vocab_size = {vocab_size})')
+        if shuffle:
+            perm = g.permutation(len(x))
+            x, y = x[perm], y[perm]
+        if config.datapoint_limit:
+            x, y = x[: config.datapoint_limit], y[: config.datapoint_limit]
+        x = x.astype(np.float32)            # ids travel as fp32 (exact below 2^24)
+        y = y.astype(np.int32)
+        n = len(x)
+        a, b = int(n * config.train_split), int(n * (config.train_split + config.valid_split))
+        self.train_x, self.valid_x, self.test_x = x[:a], x[a:b], x[b:]
+        self.train_y, self.valid_y, self.test_y = y[:a], y[a:b], y[b:]
+
+    def __len__(self):
+        return len(self.train_x) + len(self.valid_x) + len(self.test_x)
+
+
+def synthetic_text(g: np.random.Generator, N: int, T: int, V: int, n_classes: int = 2):
+    """Seeded synthetic token sequences: lengths uniform in [max(1, T/4), T] with pad id 0 after the last token, token ids
+    1..V-1 drawn with Zipf-like frequencies (p_k ~ 1/k), labels from a hidden per-token score (mean score per sequence,
+    plus Gumbel noise, argmax over the classes)."""
+    if V < 2:
+        raise ValueError('synthetic text needs vocab_size >= 2 (id 0 is the pad)')
+    ranks = np.arange(1, V, dtype=np.float64)
+    p = 1.0 / ranks
+    p /= p.sum()
+    lengths = g.integers(max(1, T // 4), T + 1, N)
+    ids = g.choice(np.arange(1, V), size=(N, T), p=p)
+    x = np.where(np.arange(T)[None, :] < lengths[:, None], ids, 0).astype(np.int64)
+    score = g.standard_normal((V, n_classes))
+    score[0] = 0.0
+    s = score[x].sum(axis=1) / lengths[:, None]
+    y = np.argmax(3.0 * s + g.gumbel(size=(N, n_classes)), axis=1).astype(np.int64)
+    return x, y

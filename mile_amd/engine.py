@@ -12,7 +12,7 @@ from typing import NamedTuple
 import torch
 
 from mile_amd import _lib
-from mile_amd.spec import IMAGE_SPECS, LeNetSpec, LeNettiSpec, ModelSpec
+from mile_amd.spec import IMAGE_SPECS, AttentionSpec, LeNetSpec, LeNettiSpec, ModelSpec
 
 
 class IntegratorState(NamedTuple):
@@ -65,6 +65,15 @@ def _f32(t, device, shape=None, name='tensor'):
     return t
 
 
+
+def _check_tokens(spec, X):
+    """AttentionClassifier rows are token ids stored as fp32: integers in [0, vocab_size)."""
+    if not isinstance(spec, AttentionSpec) or not X.numel():
+        return
+    if bool((X != torch.floor(X)).any()) or float(X.min()) < 0 or float(X.max()) >= spec.vocab_size:
+        raise ValueError(f'token ids must be integers in [0, {spec.vocab_size})')
+
+
 class Engine:
     """One handle == one device, one model spec, one training set."""
 
@@ -80,6 +89,10 @@ class Engine:
         if isinstance(spec, IMAGE_SPECS):
             cs.model = 2 if isinstance(spec, LeNettiSpec) else 1
             cs.img_c, cs.img_h, cs.img_w = spec.channels, spec.height, spec.width
+        if isinstance(spec, AttentionSpec):
+            cs.model = 3
+            cs.vocab_size, cs.ctx_len, cs.emb_size = spec.vocab_size, spec.context_len, spec.emb_size
+            cs.n_heads, cs.qkv_dim = spec.n_heads, spec.qkv_dim
         cs.n_layers = len(spec.hidden_structure)
         if cs.n_layers > _lib.MILE_MAX_LAYERS:
             raise ValueError(f'at most {_lib.MILE_MAX_LAYERS} layers')
@@ -119,6 +132,7 @@ class Engine:
             X = X.reshape(X.shape[0], -1)
         if X.ndim != 2 or X.shape[1] != self.spec.in_features:
             raise ValueError(f'X must be [N, {self.spec.in_features}], got {tuple(X.shape)}')
+        _check_tokens(self.spec, X)
         y = torch.as_tensor(y, device=self.device)
         if y.ndim == 2 and y.shape[1] == 1:
             y = y[:, 0]
@@ -482,6 +496,7 @@ class Engine:
             X = X.reshape(X.shape[0], -1).contiguous()
         if X.ndim != 2 or X.shape[1] != self.spec.in_features or y.shape != (X.shape[0],):
             raise ValueError('X must be [N, F] and y [N]')
+        _check_tokens(self.spec, X)
         if self.spec.task != 'regr' and y.numel():       # the kernels index the logits with the raw label
             if int(y.min()) < 0 or int(y.max()) >= self.spec.hidden_structure[-1]:
                 raise ValueError('class labels out of range')

@@ -13,7 +13,7 @@ from functools import partial
 import torch
 
 from mile_amd.priors import Prior
-from mile_amd.spec import IMAGE_SPECS, ModelSpec
+from mile_amd.spec import NATIVE_SPECS, ModelSpec
 
 TASK_ALIASES = {'regr': 'regr', 'regression': 'regr', 'class': 'classification', 'classification': 'classification'}
 
@@ -29,15 +29,15 @@ class ProbabilisticModel:
         task = TASK_ALIASES[str(task)]
         if n_batches != 1:
             raise NotImplementedError('Mini-Batch Sampling not yet implemented.')  # trainer.py:591-592
-        if isinstance(module, IMAGE_SPECS):
+        if isinstance(module, NATIVE_SPECS):
             self.spec = dataclasses.replace(module, task=task, prior=prior.name, prior_loc=prior.loc, prior_scale=prior.scale)
-        if isinstance(module, (ModelSpec,) + IMAGE_SPECS):
+        if isinstance(module, (ModelSpec,) + NATIVE_SPECS):
             base = module
         else:
             base = ModelSpec(in_features=module.in_features, hidden_structure=tuple(module.hidden_structure),
                              activation=str(getattr(module.activation, 'value', module.activation)),
                              use_bias=getattr(module, 'use_bias', True))
-        if not isinstance(module, IMAGE_SPECS):
+        if not isinstance(module, NATIVE_SPECS):
             self.spec = ModelSpec(in_features=base.in_features, hidden_structure=base.hidden_structure,
                                   activation=base.activation, task=task, prior=prior.name,
                                   prior_loc=prior.loc, prior_scale=prior.scale, use_bias=base.use_bias)

@@ -232,3 +232,146 @@ class LeNettiSpec:
 
 
 IMAGE_SPECS = (LeNetSpec, LeNettiSpec)
+
+
+# shapes the AttentionClassifier kernel (mile_amd/csrc/mile_attn.h) supports
+ATTN_MAX_T = 128
+ATTN_MAX_C = 64
+ATTN_MAX_D = 64
+ATTN_MAX_PROJ = 2
+ATTN_MAX_P = 64
+ATTN_MAX_K = 16
+ATTN_LDS_MAX = 160 * 1024
+
+
+def attn_lds_bytes(T: int, C: int, H: int, D: int, weights: bool) -> int:
+    """LDS of one k_grad_attn workgroup (attn_lds_bytes in mile_attn.h)."""
+    Tp, hd = (T + 15) // 16 * 16, D // H
+    per_wave = 16 * Tp + (Tp * ((hd + 15) // 16 * 16) if hd > 16 else 0)
+    scr = max(64 * Tp, min(H, 4) * per_wave)
+    return 4 * ((C * 3 * D if weights else 0) + Tp * 3 * D + scr + 5 * Tp + 10 * 64 + 16)
+
+
+@dataclass(frozen=True)
+class AttentionSpec:
+    """AttentionClassifier (src/models/text/attention_classifier.py, AttentionClassifierConfig src/config/models/gpt.py) on
+    [N, T] token ids (pad id 0): TokenEmbedding (token + position) - one MultiHeadDotProductAttention 'MDPA' (H heads, qkv_dim D,
+    out_features C) - mean over the T positions - (Dense P_i - gelu) per projection - Dense n_classes 'classifier'.
+    Duck-types ModelSpec where the host code needs it (in_features = T, hidden_structure = projection_dim + [n_classes])."""
+
+    vocab_size: int
+    context_len: int
+    emb_size: int
+    n_heads: int
+    qkv_dim: int
+    n_classes: int = 2
+    projection_dim: tuple = (32,)
+    use_bias: bool = False
+    activation: str = 'relu'          # unused: the projections use gelu; kept for the ModelSpec interface
+    task: str = 'classification'
+    prior: str = 'StandardNormal'
+    prior_loc: float = 0.0
+    prior_scale: float = 1.0
+    root: str = ''
+
+    def __post_init__(self):
+        object.__setattr__(self, 'projection_dim', tuple(int(p) for p in self.projection_dim))
+        if self.task != 'classification':
+            raise NotImplementedError('AttentionClassifier: classification only')
+        if self.prior not in PRIORS:
+            raise NotImplementedError(f'Prior Distribution for {self.prior} is not yet implemented.')
+        if self.prior == 'StandardNormal':
+            object.__setattr__(self, 'prior_loc', 0.0)
+            object.__setattr__(self, 'prior_scale', 1.0)
+        V, T, C, H, D, K = self.vocab_size, self.context_len, self.emb_size, self.n_heads, self.qkv_dim, self.n_classes
+        if min(V, T, C, H, D, K) < 1 or any(p < 1 for p in self.projection_dim):
+            raise ValueError('AttentionClassifier: all sizes must be >= 1')
+        if D % H:
+            raise ValueError(f'AttentionClassifier: n_heads ({H}) must divide qkv_dim ({D})')
+        if T > ATTN_MAX_T:
+            raise NotImplementedError(f'AttentionClassifier: context_len = {T}, the HIP kernel takes at most {ATTN_MAX_T}')
+        if C > ATTN_MAX_C:
+            raise NotImplementedError(f'AttentionClassifier: emb_size = {C}, the HIP kernel takes at most {ATTN_MAX_C} '
+                                      '(its weights must fit on chip)')
+        if D > ATTN_MAX_D:
+            raise NotImplementedError(f'AttentionClassifier: qkv_dim = {D}, the HIP kernel takes at most {ATTN_MAX_D}')
+        if len(self.projection_dim) > ATTN_MAX_PROJ:
+            raise NotImplementedError(f'AttentionClassifier: at most {ATTN_MAX_PROJ} projection layers on the HIP kernel')
+        if any(p > ATTN_MAX_P for p in self.projection_dim):
+            raise NotImplementedError(f'AttentionClassifier: projection widths <= {ATTN_MAX_P} on the HIP kernel')
+        if K > ATTN_MAX_K:
+            raise NotImplementedError(f'AttentionClassifier: n_classes <= {ATTN_MAX_K} on the HIP kernel')
+        if V >= 1 << 24:
+            raise NotImplementedError('AttentionClassifier: vocab_size < 2^24 (token ids travel as fp32)')
+        if attn_lds_bytes(T, C, H, D, False) > ATTN_LDS_MAX:
+            raise NotImplementedError(f'AttentionClassifier: this shape needs more than {ATTN_LDS_MAX // 1024} KB of LDS '
+                                      'per workgroup on the HIP kernel')
+
+    @property
+    def in_features(self) -> int:
+        return self.context_len
+
+    @property
+    def head_dim(self) -> int:
+        return self.qkv_dim // self.n_heads
+
+    @property
+    def hidden_structure(self):
+        return self.projection_dim + (self.n_classes,)
+
+    def leaves(self):
+        """[(dotted name, offset, shape)] in ravel_pytree order: sorted keys at every level (uppercase before lowercase),
+        bias before kernel; biases only with use_bias.  DenseGeneral kernels keep flax's [C, H, hd] / [H, hd, C] shapes."""
+        C, H, hd, D, K = self.emb_size, self.n_heads, self.head_dim, self.qkv_dim, self.n_classes
+        shapes = []
+
+        def dense(name, bias_shape, kernel_shape):
+            if self.use_bias:
+                shapes.append((f'{name}.bias', bias_shape))
+            shapes.append((f'{name}.kernel', kernel_shape))
+
+        dense('MDPA.key', (H, hd), (C, H, hd))
+        dense('MDPA.out', (C,), (H, hd, C))
+        dense('MDPA.query', (H, hd), (C, H, hd))
+        dense('MDPA.value', (H, hd), (C, H, hd))
+        shapes.append(('TokenEmbedding_0.Embedding.embedding', (self.vocab_size, C)))
+        shapes.append(('TokenEmbedding_0.PositionEmbedding.embedding', (self.context_len, C)))
+        dense('classifier', (K,), ((self.projection_dim[-1] if self.projection_dim else C), K))
+        fin = C
+        for i, p in enumerate(self.projection_dim):
+            dense(f'projection_{i}', (p,), (fin, p))
+            fin = p
+        out, off = [], 0
+        for name, sh in shapes:
+            out.append((f'{self.root}.{name}' if self.root else name, off, sh))
+            n = 1
+            for v in sh:
+                n *= v
+            off += n
+        return out
+
+    @property
+    def n_params(self) -> int:
+        name, off, sh = self.leaves()[-1]
+        n = 1
+        for v in sh:
+            n *= v
+        return off + n
+
+    @property
+    def lds_bytes(self) -> int:
+        """LDS of one k_grad_attn workgroup: with Wq|Wk|Wv staged when they fit, without them otherwise."""
+        args = (self.context_len, self.emb_size, self.n_heads, self.qkv_dim)
+        with_w = attn_lds_bytes(*args, True)
+        return with_w if with_w <= ATTN_LDS_MAX else attn_lds_bytes(*args, False)
+
+    @property
+    def flops_per_sequence(self) -> int:
+        """3 x forward: 2 T C 3D + 4 T^2 D + 2 T D C + sum 2 P_{i-1} P_i (projections and classifier)."""
+        T, C, D = self.context_len, self.emb_size, self.qkv_dim
+        dims = (C,) + self.hidden_structure
+        fwd = 2 * T * C * 3 * D + 4 * T * T * D + 2 * T * D * C + sum(2 * a * b for a, b in zip(dims[:-1], dims[1:]))
+        return 3 * fwd
+
+
+NATIVE_SPECS = IMAGE_SPECS + (AttentionSpec,)

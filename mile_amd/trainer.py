@@ -20,10 +20,10 @@ import torch
 from mile_amd import distributed as mdist
 from mile_amd.callbacks import load_params_batch, save_params, save_tree
 from mile_amd.config import Config
-from mile_amd.dataset import ImageLoader, TabularLoader
+from mile_amd.dataset import ImageLoader, TabularLoader, TextLoader
 from mile_amd.probabilistic import ProbabilisticModel
 from mile_amd.sampling import inference_loop, join_without_chains
-from mile_amd.spec import LeNetSpec, LeNettiSpec, ModelSpec
+from mile_amd.spec import AttentionSpec, LeNetSpec, LeNettiSpec, ModelSpec
 from mile_amd.tree import PRNGKey
 
 logger = logging.getLogger(__name__)
@@ -82,7 +82,20 @@ class BDETrainer:
     def build_model(self, config: Config):
         """Data loader, model spec and probabilistic model of a config (also used by evaluate.py)."""
         task = 'regr' if config.data.task == 'regr' else 'classification'
-        if config.model.model in ('LeNet', 'LeNetti'):
+        if config.model.model == 'AttentionClassifier':
+            if config.data.data_type != 'text':
+                raise ValueError('model AttentionClassifier needs data_type: text')
+            if task != 'classification':
+                raise NotImplementedError('AttentionClassifier: classification only')
+            if config.training.tokenizer is not None:
+                logger.warning('training.tokenizer is ignored: text data comes as token ids (synthetic or .npz)')
+            m = config.model
+            self.loader = TextLoader(config.data, rng=config.rng, context_len=m.context_len, vocab_size=m.vocab_size,
+                                     n_classes=m.n_classes)
+            self.spec_model = AttentionSpec(vocab_size=m.vocab_size, context_len=m.context_len, emb_size=m.emb_size,
+                                            n_heads=m.n_heads, qkv_dim=m.qkv_dim, n_classes=m.n_classes,
+                                            projection_dim=tuple(m.projection_dim), use_bias=m.bias, task=task)
+        elif config.model.model in ('LeNet', 'LeNetti'):
             if config.data.data_type != 'image':
                 raise ValueError(f'model {config.model.model} needs data_type: image')
             self.loader = ImageLoader(config.data, rng=config.rng)
@@ -92,7 +105,8 @@ class BDETrainer:
                                   activation=config.model.activation, task=task)
         else:
             if config.data.data_type != 'tabular':
-                raise NotImplementedError('the FCN runs on tabular data; image data goes with model LeNet or LeNetti')
+                raise NotImplementedError('the FCN runs on tabular data; image data goes with model LeNet or LeNetti, '
+                                          'text data with AttentionClassifier')
             self.loader = TabularLoader(config.data, rng=config.rng, target_len=config.data.target_len)
             F = self.loader.train_x.shape[-1]
             self.spec_model = ModelSpec(in_features=F, hidden_structure=tuple(config.model.hidden_structure),
@@ -109,18 +123,25 @@ class BDETrainer:
     def init_module_params(self, chain_ids) -> np.ndarray:
         """Random parameters as `module.init` gives them (trainer.py:206-228, 904-917): flax Dense defaults --
         kernel lecun_normal (truncated normal on [-2, 2] standard deviations, variance 1/fan_in), bias zeros --
-        one stream per GLOBAL chain id.  (JAX's PRNG is not reproducible here; the distribution is.)"""
+        one stream per GLOBAL chain id.  (JAX's PRNG is not reproducible here; the distribution is.)
+        AttentionClassifier: DenseGeneral kernels use the fan-in of their input axes only (C for query / key / value,
+        H * hd for out), nn.Embed tables are normal with std 1 / sqrt(C); the draws of the other leaves are unchanged."""
         spec = self.prob_model.spec
         rows = []
         for cid in chain_ids:
             g = torch.Generator().manual_seed((self.config.rng * 1000003 + int(cid)) & 0x7FFFFFFFFFFFFFFF)
             flat = torch.zeros(spec.n_params, dtype=torch.float32)
             for name, off, shape in spec.leaves():
-                if name.endswith('kernel'):
+                if name.endswith('embedding'):                   # nn.Embed: variance_scaling(1, 'fan_in', 'normal', out_axis=0)
+                    w = torch.empty(shape, dtype=torch.float32).normal_(0.0, 1.0 / math.sqrt(shape[-1]), generator=g)
+                    flat[off:off + w.numel()] = w.reshape(-1)
+                elif name.endswith('kernel'):
                     w = torch.empty(shape, dtype=torch.float32)
                     torch.nn.init.trunc_normal_(w, mean=0.0, std=1.0, a=-2.0, b=2.0, generator=g)
                     # variance_scaling(1.0, 'fan_in', 'truncated_normal'): std = sqrt(1/fan_in) / 0.87962566...
                     fan_in = int(np.prod(shape[:-1]))             # Dense: in; Conv: kh * kw * in
+                    if name.startswith('MDPA.') or '.MDPA.' in name:   # DenseGeneral: the input axes only
+                        fan_in = int(np.prod(shape[:1] if not name.endswith('out.kernel') else shape[:2]))
                     flat[off:off + w.numel()] = (w * (math.sqrt(1.0 / fan_in) / 0.87962566103423978)).reshape(-1)
             rows.append(flat.numpy())
         return np.stack(rows).astype(np.float32)
