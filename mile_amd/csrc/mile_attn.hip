@@ -2,32 +2,12 @@
 // (ceil(hd / 16): 1..4) and whether Wq|Wk|Wv fit in LDS next to the sequence are template arguments.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "mile_attn.h"
-
-#define ATTN_MAX_DEVICES 64
-
-// hipFuncSetAttribute is per device: one flag per (device, instantiation)
-template <int NHT, bool WL>
-static hipError_t attn_set_lds(size_t lds) {
-  static std::atomic<bool> done[ATTN_MAX_DEVICES];
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev >= 0 && dev < ATTN_MAX_DEVICES && done[dev].load(std::memory_order_acquire)) return hipSuccess;
-  (void)lds;
-  e = hipFuncSetAttribute((const void *)k_grad_attn<NHT, WL>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LDS_MAX);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_fwd_attn<NHT, WL>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LDS_MAX);
-  if (e != hipSuccess) return e;
-  if (dev >= 0 && dev < ATTN_MAX_DEVICES) done[dev].store(true, std::memory_order_release);
-  return hipSuccess;
-}
 
 template <int NHT, bool WL>
 static hipError_t launch_t(const AttnParams &p, int E, bool grad, hipStream_t st) {
   const size_t lds = attn_lds_bytes(p.g, WL);
-  hipError_t e = attn_set_lds<NHT, WL>(lds);
+  hipError_t e = grad ? mile_set_max_lds<k_grad_attn<NHT, WL>>(ATTN_LDS_MAX) : mile_set_max_lds<k_fwd_attn<NHT, WL>>(ATTN_LDS_MAX);
   if (e != hipSuccess) return e;
   const dim3 grid(p.S, E);
   if (grad) k_grad_attn<NHT, WL><<<grid, ATTN_NT, lds, st>>>(p);

@@ -3,11 +3,29 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "../../include/mile_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting: set it for kernel K once per device.  One flag
+// per (instantiation, device) and no lock: two threads that both set it the first time do no harm.
+#define MILE_MAX_DEVICES 64
+template <auto K>
+static hipError_t mile_set_max_lds(int bytes) {
+  static std::atomic<bool> done[MILE_MAX_DEVICES];
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  const bool keep = dev >= 0 && dev < MILE_MAX_DEVICES;
+  if (keep && done[dev].load(std::memory_order_acquire)) return hipSuccess;
+  e = hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess && keep) done[dev].store(true, std::memory_order_release);
+  return e;
+}
 
 // Flattened description of the FCN that kernels take by value.
 struct DevSpec {

@@ -64,6 +64,8 @@ struct mile_sampler {
   LeNetGeom lg{};                       // MILE_MODEL_LENET geometry and parameter offsets
   LeNettiGeom ng{};                     // MILE_MODEL_LENETTI geometry and parameter offsets
   AttnGeom ag{};                        // MILE_MODEL_ATTN geometry and parameter offsets
+  struct ParamLayer { int bias_off, kernel_off; };
+  std::vector<ParamLayer> layers;       // mile_param_offsets, in ABI order (bias -1: none)
   // layer-wise GEMM path (MILE_GRAD_GEMM_F32): rocBLAS handle and activation workspace
   void *blas = nullptr;
   long long *dbg_buf = nullptr;         // dev instrumentation (MILE_DEBUG=16)
@@ -87,19 +89,31 @@ struct mile_sampler {
   size_t ev_used = 0;
 };
 
-static bool w64_supported(const mile_model_spec &sp) {
+// ---- which specs each grad kernel runs: the `supports` of its row in kGrad ------------------------------------------------
+static bool is_fcn(const mile_sampler *s) { return s->spec.model == MILE_MODEL_FCN; }
+static bool is_lenet(const mile_sampler *s) { return s->spec.model == MILE_MODEL_LENET; }
+static bool is_lenetti(const mile_sampler *s) { return s->spec.model == MILE_MODEL_LENETTI; }
+static bool is_attn(const mile_sampler *s) { return s->spec.model == MILE_MODEL_ATTN; }
+static bool lenet_bf16_supported(const mile_sampler *s) { return is_lenet(s) && s->lg.C <= 4; }
+
+// k_grad_w64 / k_grad_w128b: ReLU regression, 1-3 hidden layers of the kernel's width, F <= 16
+static bool relu_regression_of_width(const mile_sampler *s, int width) {
+  const mile_model_spec &sp = s->spec;
   if (sp.model != MILE_MODEL_FCN) return false;
   if (sp.task != MILE_TASK_REGRESSION || sp.activation != MILE_ACT_RELU) return false;
   const int nh = sp.n_layers - 1;
   if (nh < 1 || nh > 3) return false;
   for (int l = 0; l < nh; ++l)
-    if (sp.widths[l] != 64) return false;
+    if (sp.widths[l] != width) return false;
   if (sp.widths[nh] != 2) return false;
   if (sp.in_features > 16) return false;
   return true;
 }
-
+static bool w64_supported(const mile_sampler *s) { return relu_regression_of_width(s, 64); }
+static bool w128b_supported(const mile_sampler *s) { return relu_regression_of_width(s, 128); }
 // the split-bf16 variant replaces the hidden->hidden products, so it needs at least one
+static bool w64x3_supported(const mile_sampler *s) { return w64_supported(s) && s->spec.n_layers - 1 >= 2; }
+
 // k_grad_narrow: 1-3 hidden layers of width <= 64 and F <= 64 (<= 32: weights in registers; 33..64: weights in LDS), or 4-10
 // hidden layers of width <= 16 and F <= 16 (the depth ablations of the reference: experiments/**: [16]*4 .. [16]*9 + [2],
 // [8]*6 + [2]); <= 16 outputs (regression: exactly mu, log sigma), any activation
@@ -108,7 +122,8 @@ static int narrow_tiles_hidden(const mile_model_spec &sp) {
   for (int l = 0; l + 1 < sp.n_layers; ++l) mw = std::max(mw, sp.widths[l]);
   return (mw + 15) / 16;
 }
-static bool narrow_supported(const mile_model_spec &sp) {
+static bool narrow_supported(const mile_sampler *s) {
+  const mile_model_spec &sp = s->spec;
   if (sp.model != MILE_MODEL_FCN || !sp.use_bias) return false;
   const int nh = sp.n_layers - 1;
   if (nh < 1 || nh > 10 || sp.in_features > 64) return false;
@@ -120,8 +135,6 @@ static bool narrow_supported(const mile_model_spec &sp) {
   if (sp.task == MILE_TASK_REGRESSION && K != 2) return false;
   return true;
 }
-static bool w64x3_supported(const mile_model_spec &sp) { return w64_supported(sp) && sp.n_layers - 1 >= 2; }
-static bool is_w64(int kernel) { return kernel == MILE_GRAD_MFMA_W64 || kernel == MILE_GRAD_MFMA_W64_BF16X3; }
 
 // ---- rocBLAS, resolved at first use: libmile_hip.so has no link-time dependency on it -----------
 typedef int (*rb_create_t)(void **);
@@ -156,41 +169,13 @@ static bool rocblas_load() {
 }
 
 // library GEMMs pay off once the hidden layers are wide; below that the single-launch generic kernel wins
-static bool gemm_preferred(const mile_model_spec &sp) {
-  if (sp.model != MILE_MODEL_FCN) return false;
+static bool gemm_preferred(const mile_sampler *s) {
   int mw = 0;
-  for (int l = 0; l + 1 < sp.n_layers; ++l) mw = std::max(mw, sp.widths[l]);
-  return sp.n_layers >= 2 && mw >= 96;
+  for (int l = 0; l + 1 < s->spec.n_layers; ++l) mw = std::max(mw, s->spec.widths[l]);
+  return is_fcn(s) && s->spec.n_layers >= 2 && mw >= 96;
 }
 
-static bool w128b_supported(const mile_model_spec &sp) {
-  if (sp.model != MILE_MODEL_FCN) return false;
-  if (sp.task != MILE_TASK_REGRESSION || sp.activation != MILE_ACT_RELU) return false;
-  const int nh = sp.n_layers - 1;
-  if (nh < 1 || nh > 3) return false;
-  for (int l = 0; l < nh; ++l)
-    if (sp.widths[l] != 128) return false;
-  if (sp.widths[nh] != 2) return false;
-  if (sp.in_features > 16) return false;
-  return true;
-}
-
-static int resolved_kernel(const mile_sampler *s) {
-  if (s->spec.model == MILE_MODEL_LENETTI) return MILE_GRAD_LENETTI_F32;
-  if (s->spec.model == MILE_MODEL_ATTN) return MILE_GRAD_ATTN_F32;
-  if (s->spec.model == MILE_MODEL_LENET) return s->grad_kernel == MILE_GRAD_LENET_BF16 ? MILE_GRAD_LENET_BF16 : MILE_GRAD_LENET_F32;
-  if (s->grad_kernel == MILE_GRAD_AUTO) {
-    if (w64x3_supported(s->spec)) return MILE_GRAD_MFMA_W64_BF16X3;   // fp32-faithful and never slower than MFMA_W64
-    if (w64_supported(s->spec)) return MILE_GRAD_MFMA_W64;
-    // wide nets: the hand-written layer-wise MFMA GEMMs (fp32-faithful); rocBLAS (GEMM_F32) is the cross-check, never AUTO
-    if (gemm_preferred(s->spec)) return MILE_GRAD_MFMA_WIDE_BF16X3;
-    // the reference's own nets (16 / 32 wide, any activation, either head): fused fp32-MFMA kernel
-    if (narrow_supported(s->spec) && getenv("MILE_NO_NARROW") == nullptr) return MILE_GRAD_MFMA_NARROW_F32;
-    return MILE_GRAD_GENERIC;
-  }
-  return s->grad_kernel;
-}
-
+// ---- row ranges (slabs) per particle: the `row_splits` of each row in kGrad ----------------------------------------------
 // rows per LDS tile of the generic kernel: fit the activation record in ~56 KiB
 static int generic_R(const DevSpec &ds) {
   const int per_row = ds.act_stride + 2 * ds.max_width;
@@ -198,6 +183,23 @@ static int generic_R(const DevSpec &ds) {
   R = std::max(1, std::min(R, 64));
   return R;
 }
+static int generic_S(const mile_sampler *s, int E) {
+  int S = std::max(1, (2 * s->n_cu) / std::max(E, 1));
+  S = std::min(S, std::max(1, s->N / 64));
+  return std::min(S, 64);
+}
+static int w64_S(const mile_sampler *s, int E) {
+  const int NB = s->Npad / 32;
+  int S = std::max(1, s->n_cu / std::max(E, 1));
+  S = std::min(S, std::max(1, NB / 4));  // keep >= 4 row blocks (one per wave) per workgroup
+  return S;
+}
+static int w128b_S(const mile_sampler *s, int E) {
+  const int NBS = s->Npb / 64;              // iterations of two 32-row tiles
+  int S = std::max(1, s->n_cu / std::max(E, 1));
+  return std::min(S, std::max(1, NBS / 4));  // amortise weight staging over >= 8 row tiles
+}
+static int one_S(const mile_sampler *, int) { return 1; }   // the layer-wise paths: every launch covers all rows
 
 // k_grad_narrow: 16-row tiles, workgroups of up to 4 waves.  About four waves per SIMD over the whole grid (16 x CUs waves) and
 // NO MORE row splits than that needs: every split is one more slab the update kernels sum -- with S = 64 splits of a d = 402
@@ -228,27 +230,170 @@ static int attn_S(const mile_sampler *s, int E) {
   return std::max(1, std::min({64, want, std::max(1, s->N / 16)}));
 }
 
-static int choose_S(const mile_sampler *s, int E, int kernel) {
-  if (kernel == MILE_GRAD_MFMA_NARROW_F32) return narrow_S(s, E);
-  if (kernel == MILE_GRAD_ATTN_F32) return attn_S(s, E);
-  if (kernel == MILE_GRAD_LENETTI_F32) return lenetti_S(s, E);
-  if (is_w64(kernel)) {
-    const int NB = s->Npad / 32;
-    int S = std::max(1, s->n_cu / std::max(E, 1));
-    S = std::min(S, std::max(1, NB / 4));  // keep >= 4 row blocks (one per wave) per workgroup
-    return S;
+// Everything the library knows about one grad kernel: one row per MILE_GRAD_* id in kGrad, defined below the launchers.
+struct LaunchShape { int block, lds; };
+struct GradKernel {
+  int id;                                             // MILE_GRAD_*
+  const char *name;                                   // what mile_grad_launch_info reports
+  bool (*supports)(const mile_sampler *);             // the specs it runs: loads, allocates and reads nothing else
+  const char *refusal;                                // mile_set_grad_kernel's message for any other spec
+  const char *needs_rocblas;                          // non-null: mile_set_grad_kernel loads rocBLAS, and this is why it failed
+  int (*row_splits)(const mile_sampler *, int E);     // S: row ranges (slabs) per particle
+  bool windowed;                                      // takes a row window (mile_set_row_window)
+  bool fuses;                                         // can run the update that follows as its epilogue (W64Fuse)
+  int (*grad)(mile_sampler *, const GradParams &, const W64Fuse &, int E, hipStream_t);
+  int (*loglik)(mile_sampler *, PredParams pp, int S, hipStream_t);   // mile_pointwise_loglik on the staged evaluation set
+  LaunchShape (*shape)(const mile_sampler *, int S);  // block and LDS bytes that mile_grad_launch_info reports
+};
+static const GradKernel &grad_kernel(int kernel);
+
+// MILE_GRAD_AUTO, as a priority list
+static int auto_kernel(const mile_sampler *s) {
+  if (w64x3_supported(s)) return MILE_GRAD_MFMA_W64_BF16X3;   // fp32-faithful and never slower than MFMA_W64
+  if (w64_supported(s)) return MILE_GRAD_MFMA_W64;
+  // wide nets: the hand-written layer-wise MFMA GEMMs (fp32-faithful); rocBLAS (GEMM_F32) is the cross-check, never AUTO
+  if (gemm_preferred(s)) return MILE_GRAD_MFMA_WIDE_BF16X3;
+  // the reference's own nets (16 / 32 wide, any activation, either head): fused fp32-MFMA kernel
+  if (narrow_supported(s) && getenv("MILE_NO_NARROW") == nullptr) return MILE_GRAD_MFMA_NARROW_F32;
+  if (is_lenet(s)) return MILE_GRAD_LENET_F32;                // the other models: their own kernel
+  if (is_lenetti(s)) return MILE_GRAD_LENETTI_F32;
+  if (is_attn(s)) return MILE_GRAD_ATTN_F32;
+  return MILE_GRAD_GENERIC;
+}
+static int resolved_kernel(const mile_sampler *s) { return s->grad_kernel == MILE_GRAD_AUTO ? auto_kernel(s) : s->grad_kernel; }
+static int choose_S(const mile_sampler *s, int E, int kernel) { return grad_kernel(kernel).row_splits(s, E); }
+
+// ---- one layout per model family: validates the spec, fills the geometry, ds and the ABI layers of mile_param_offsets -------
+static int layout_fcn(mile_sampler *s) {   // ravel_pytree order: layers sorted by NAME ("layer10" < "layer2"), bias before kernel
+  const mile_model_spec *spec = &s->spec;
+  DevSpec &ds = s->ds;
+  std::vector<int> order(spec->n_layers);
+  for (int i = 0; i < spec->n_layers; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [](int a, int b) {
+    return std::string("layer") + std::to_string(a) < std::string("layer") + std::to_string(b);
+  });
+  long long off = 0;
+  for (int li : order) {
+    const int fin = li == 0 ? spec->in_features : spec->widths[li - 1], fout = spec->widths[li];
+    ds.b_off[li] = (int)off; off += fout;
+    ds.w_off[li] = (int)off; off += (long long)fin * fout;
   }
-  if (kernel == MILE_GRAD_GEMM_F32 || kernel == MILE_GRAD_LENET_F32 || kernel == MILE_GRAD_LENET_BF16 || kernel == MILE_GRAD_MFMA_WIDE_BF16X3 ||
-      kernel == MILE_GRAD_MFMA_WIDE_BF16)
-    return 1;
-  if (kernel == MILE_GRAD_MFMA_W128_BF16) {
-    const int NBS = s->Npb / 64;              // iterations of two 32-row tiles
-    int S = std::max(1, s->n_cu / std::max(E, 1));
-    return std::min(S, std::max(1, NBS / 4));  // amortise weight staging over >= 8 row tiles
+  if (off > 0x7fffffffLL) return fail(MILE_ERR_INVALID, "parameter count exceeds int32");
+  if (off < 2) return fail(MILE_ERR_INVALID, "The target distribution must have more than 1 dimension for MCLMC.");
+  ds.d = (int)off;
+  ds.act_off[0] = 0;
+  int a = spec->in_features, mw = spec->in_features;
+  for (int l = 0; l < spec->n_layers; ++l) {
+    ds.widths[l] = spec->widths[l];
+    ds.act_off[l + 1] = a;
+    a += spec->widths[l];
+    mw = std::max(mw, spec->widths[l]);
+    s->layers.push_back({ds.b_off[l], ds.w_off[l]});
   }
-  int S = std::max(1, (2 * s->n_cu) / std::max(E, 1));
-  S = std::min(S, std::max(1, s->N / 64));
-  return std::min(S, 64);
+  ds.act_stride = a;
+  ds.max_width = mw;
+  if (generic_R(ds) < 1) return fail(MILE_ERR_INVALID, "network too wide for the generic kernel");
+  return MILE_OK;
+}
+
+static int layout_lenet(mile_sampler *s) {   // ravel_pytree order of {'core': {conv1, conv2, fc1, fc2, fc3}}: bias, kernel each
+  const mile_model_spec *spec = &s->spec;
+  if (spec->n_layers != 1) return fail(MILE_ERR_INVALID, "LeNet: n_layers must be 1 (widths[0] = out_dim)");
+  if (spec->img_c < 1 || spec->img_h < 1 || spec->img_w < 1 ||
+      (long long)spec->img_c * spec->img_h * spec->img_w != spec->in_features)
+    return fail(MILE_ERR_INVALID, "LeNet: in_features must equal img_c * img_h * img_w");
+  if ((spec->img_h / 2 - 4) / 2 < 1 || (spec->img_w / 2 - 4) / 2 < 1) return fail(MILE_ERR_INVALID, "LeNet: image too small");
+  if (!rocblas_load()) return fail(MILE_ERR_HIP, "LeNet needs librocblas.so, which could not be loaded");
+  LeNetGeom &g = s->lg;
+  g.C = spec->img_c; g.H = spec->img_h; g.W = spec->img_w; g.K = spec->widths[0];
+  g.hp1 = g.H / 2; g.wp1 = g.W / 2; g.h2 = g.hp1 - 4; g.w2 = g.wp1 - 4; g.hp2 = g.h2 / 2; g.wp2 = g.w2 / 2;
+  g.flat = g.hp2 * g.wp2 * 16;
+  long long o = 0;
+  g.b_c1 = (int)o; o += 6;   g.k_c1 = (int)o; o += 25LL * g.C * 6;
+  g.b_c2 = (int)o; o += 16;  g.k_c2 = (int)o; o += 150LL * 16;
+  g.b_f1 = (int)o; o += 120; g.k_f1 = (int)o; o += (long long)g.flat * 120;
+  g.b_f2 = (int)o; o += 84;  g.k_f2 = (int)o; o += 120LL * 84;
+  g.b_f3 = (int)o; o += g.K; g.k_f3 = (int)o; o += 84LL * g.K;
+  if (o > 0x7fffffffLL) return fail(MILE_ERR_INVALID, "parameter count exceeds int32");
+  g.d = (int)o;
+  s->ds.d = g.d;
+  s->ds.widths[0] = g.K;
+  s->ds.b_off[0] = g.b_c1; s->ds.w_off[0] = g.k_c1;
+  s->ds.max_width = 150; s->ds.act_stride = 0;
+  s->layers = {{g.b_c1, g.k_c1}, {g.b_c2, g.k_c2}, {g.b_f1, g.k_f1}, {g.b_f2, g.k_f2}, {g.b_f3, g.k_f3}};
+  return MILE_OK;
+}
+
+static int layout_lenetti(mile_sampler *s) {   // ravel_pytree order of {'core': {conv1, fc1, fc2, fc3, fc4}}: bias, kernel each
+  const mile_model_spec *spec = &s->spec;
+  if (spec->n_layers != 1) return fail(MILE_ERR_INVALID, "LeNetti: n_layers must be 1 (widths[0] = out_dim)");
+  if (spec->img_c < 1 || spec->img_h < 1 || spec->img_w < 1 ||
+      (long long)spec->img_c * spec->img_h * spec->img_w != spec->in_features)
+    return fail(MILE_ERR_INVALID, "LeNetti: in_features must equal img_c * img_h * img_w");
+  if (spec->img_c > LENETTI_MAX_C) return fail(MILE_ERR_INVALID, "LeNetti: at most 4 image channels");
+  if ((long long)(spec->img_h + 2) * (spec->img_w + 2) > LENETTI_NT * LENETTI_MAX_PPT)
+    return fail(MILE_ERR_INVALID, "LeNetti: (H+2)*(W+2) must be <= 2048 conv-output pixels");
+  if (spec->widths[0] > LENETTI_MAX_K) return fail(MILE_ERR_INVALID, "LeNetti: out_dim must be <= 16");
+  LeNettiGeom &g = s->ng;
+  g.C = spec->img_c; g.H = spec->img_h; g.W = spec->img_w; g.K = spec->widths[0];
+  g.Ho = g.H + 2; g.Wo = g.W + 2; g.P = g.Ho * g.Wo;
+  int o = 0;
+  g.b_c = o; o += 1;   g.k_c = o; o += 9 * g.C;
+  g.b_1 = o; o += 8;   g.k_1 = o; o += 8 * g.P;
+  g.b_2 = o; o += 8;   g.k_2 = o; o += 64;
+  g.b_3 = o; o += 8;   g.k_3 = o; o += 64;
+  g.b_4 = o; o += g.K; g.k_4 = o; o += 8 * g.K;
+  g.d = o;
+  s->ds.d = g.d;
+  s->ds.widths[0] = g.K;
+  s->ds.b_off[0] = g.b_c; s->ds.w_off[0] = g.k_c;
+  s->ds.max_width = 8; s->ds.act_stride = 0;
+  s->layers = {{g.b_c, g.k_c}, {g.b_1, g.k_1}, {g.b_2, g.k_2}, {g.b_3, g.k_3}, {g.b_4, g.k_4}};
+  return MILE_OK;
+}
+
+// ravel_pytree order (sorted keys): MDPA.{key, out, query, value}, TokenEmbedding_0, classifier, projection_*; bias before kernel.
+// ABI layers: key, out, query, value, Embedding, PositionEmbedding (no bias: -1), classifier, projection_*
+static int layout_attn(mile_sampler *s) {
+  const mile_model_spec *spec = &s->spec;
+  if (spec->task != MILE_TASK_CLASSIFICATION) return fail(MILE_ERR_INVALID, "AttentionClassifier: classification only");
+  if (spec->n_layers < 1 || spec->n_layers > ATTN_MAX_NP + 1)
+    return fail(MILE_ERR_INVALID, "AttentionClassifier: widths = projection_dim (at most 2) + [n_classes]");
+  if (spec->ctx_len < 1 || spec->ctx_len > ATTN_MAX_T || spec->in_features != spec->ctx_len)
+    return fail(MILE_ERR_INVALID, "AttentionClassifier: 1 <= ctx_len <= 128 and in_features == ctx_len");
+  if (spec->emb_size < 1 || spec->emb_size > ATTN_MAX_C) return fail(MILE_ERR_INVALID, "AttentionClassifier: emb_size <= 64");
+  if (spec->qkv_dim < 1 || spec->qkv_dim > ATTN_MAX_D || spec->n_heads < 1 || spec->qkv_dim % spec->n_heads)
+    return fail(MILE_ERR_INVALID, "AttentionClassifier: qkv_dim <= 64 and n_heads dividing it");
+  if (spec->vocab_size < 1 || spec->vocab_size > (1 << 24)) return fail(MILE_ERR_INVALID, "AttentionClassifier: 1 <= vocab_size <= 2^24");
+  for (int l = 0; l + 1 < spec->n_layers; ++l)
+    if (spec->widths[l] > ATTN_MAX_P) return fail(MILE_ERR_INVALID, "AttentionClassifier: projection widths <= 64");
+  if (spec->widths[spec->n_layers - 1] > ATTN_MAX_K) return fail(MILE_ERR_INVALID, "AttentionClassifier: n_classes <= 16");
+  AttnGeom &g = s->ag;
+  g.V = spec->vocab_size; g.T = spec->ctx_len; g.C = spec->emb_size; g.H = spec->n_heads; g.D = spec->qkv_dim;
+  g.hd = g.D / g.H; g.NP = spec->n_layers - 1; g.K = spec->widths[g.NP]; g.bias = spec->use_bias ? 1 : 0;
+  g.Tp = (g.T + 15) / 16 * 16;
+  for (int l = 0; l < ATTN_MAX_NP; ++l) { g.P[l] = l < g.NP ? spec->widths[l] : 0; g.b_p[l] = g.k_p[l] = -1; }
+  if (attn_lds_bytes(g, false) > ATTN_LDS_MAX) return fail(MILE_ERR_INVALID, "AttentionClassifier: shape needs more than 160 KB of LDS");
+  long long o = 0;
+  auto put = [&](int &b, int &k, long long nb, long long nk) { b = g.bias && nb ? (int)o : -1; o += g.bias ? nb : 0; k = (int)o; o += nk; };
+  int no_bias;
+  put(g.b_k, g.k_k, g.D, (long long)g.C * g.D);
+  put(g.b_o, g.k_o, g.C, (long long)g.D * g.C);
+  put(g.b_q, g.k_q, g.D, (long long)g.C * g.D);
+  put(g.b_v, g.k_v, g.D, (long long)g.C * g.D);
+  put(no_bias, g.emb, 0, (long long)g.V * g.C);
+  put(no_bias, g.pos, 0, (long long)g.T * g.C);
+  put(g.b_c, g.k_c, g.K, (long long)(g.NP ? g.P[g.NP - 1] : g.C) * g.K);
+  for (int l = 0; l < g.NP; ++l) put(g.b_p[l], g.k_p[l], g.P[l], (long long)(l ? g.P[l - 1] : g.C) * g.P[l]);
+  if (o > 0x7fffffffLL) return fail(MILE_ERR_INVALID, "AttentionClassifier: too many parameters");
+  g.d = (int)o;
+  s->ds.d = g.d;
+  s->ds.widths[0] = g.K;
+  s->ds.b_off[0] = g.b_c; s->ds.w_off[0] = g.k_c;
+  s->ds.max_width = 64; s->ds.act_stride = 0;
+  s->layers = {{g.b_k, g.k_k}, {g.b_o, g.k_o}, {g.b_q, g.k_q}, {g.b_v, g.k_v}, {-1, g.emb}, {-1, g.pos}, {g.b_c, g.k_c}};
+  for (int l = 0; l < g.NP; ++l) s->layers.push_back({g.b_p[l], g.k_p[l]});
+  return MILE_OK;
 }
 
 extern "C" {
@@ -269,41 +414,8 @@ int32_t mile_create(const mile_model_spec *spec, int32_t device, mile_sampler **
     if (spec->widths[l] < 1) return fail(MILE_ERR_INVALID, "layer width must be >= 1");
   if (spec->task == MILE_TASK_REGRESSION && spec->widths[spec->n_layers - 1] != 2)
     return fail(MILE_ERR_INVALID, "regression needs an output layer of width 2 (mu, log sigma)");
-  if (spec->model != MILE_MODEL_FCN && spec->model != MILE_MODEL_LENET && spec->model != MILE_MODEL_LENETTI &&
-      spec->model != MILE_MODEL_ATTN)
-    return fail(MILE_ERR_INVALID, "unknown model");
-  if (spec->model == MILE_MODEL_ATTN) {
-    if (spec->task != MILE_TASK_CLASSIFICATION) return fail(MILE_ERR_INVALID, "AttentionClassifier: classification only");
-    if (spec->n_layers < 1 || spec->n_layers > ATTN_MAX_NP + 1)
-      return fail(MILE_ERR_INVALID, "AttentionClassifier: widths = projection_dim (at most 2) + [n_classes]");
-    if (spec->ctx_len < 1 || spec->ctx_len > ATTN_MAX_T || spec->in_features != spec->ctx_len)
-      return fail(MILE_ERR_INVALID, "AttentionClassifier: 1 <= ctx_len <= 128 and in_features == ctx_len");
-    if (spec->emb_size < 1 || spec->emb_size > ATTN_MAX_C) return fail(MILE_ERR_INVALID, "AttentionClassifier: emb_size <= 64");
-    if (spec->qkv_dim < 1 || spec->qkv_dim > ATTN_MAX_D || spec->n_heads < 1 || spec->qkv_dim % spec->n_heads)
-      return fail(MILE_ERR_INVALID, "AttentionClassifier: qkv_dim <= 64 and n_heads dividing it");
-    if (spec->vocab_size < 1 || spec->vocab_size > (1 << 24)) return fail(MILE_ERR_INVALID, "AttentionClassifier: 1 <= vocab_size <= 2^24");
-    for (int l = 0; l + 1 < spec->n_layers; ++l)
-      if (spec->widths[l] > ATTN_MAX_P) return fail(MILE_ERR_INVALID, "AttentionClassifier: projection widths <= 64");
-    if (spec->widths[spec->n_layers - 1] > ATTN_MAX_K) return fail(MILE_ERR_INVALID, "AttentionClassifier: n_classes <= 16");
-  }
-  if (spec->model == MILE_MODEL_LENETTI) {
-    if (spec->n_layers != 1) return fail(MILE_ERR_INVALID, "LeNetti: n_layers must be 1 (widths[0] = out_dim)");
-    if (spec->img_c < 1 || spec->img_h < 1 || spec->img_w < 1 ||
-        (long long)spec->img_c * spec->img_h * spec->img_w != spec->in_features)
-      return fail(MILE_ERR_INVALID, "LeNetti: in_features must equal img_c * img_h * img_w");
-    if (spec->img_c > LENETTI_MAX_C) return fail(MILE_ERR_INVALID, "LeNetti: at most 4 image channels");
-    if ((long long)(spec->img_h + 2) * (spec->img_w + 2) > LENETTI_NT * LENETTI_MAX_PPT)
-      return fail(MILE_ERR_INVALID, "LeNetti: (H+2)*(W+2) must be <= 2048 conv-output pixels");
-    if (spec->widths[0] > LENETTI_MAX_K) return fail(MILE_ERR_INVALID, "LeNetti: out_dim must be <= 16");
-  }
-  if (spec->model == MILE_MODEL_LENET) {
-    if (spec->n_layers != 1) return fail(MILE_ERR_INVALID, "LeNet: n_layers must be 1 (widths[0] = out_dim)");
-    if (spec->img_c < 1 || spec->img_h < 1 || spec->img_w < 1 ||
-        (long long)spec->img_c * spec->img_h * spec->img_w != spec->in_features)
-      return fail(MILE_ERR_INVALID, "LeNet: in_features must equal img_c * img_h * img_w");
-    if ((spec->img_h / 2 - 4) / 2 < 1 || (spec->img_w / 2 - 4) / 2 < 1) return fail(MILE_ERR_INVALID, "LeNet: image too small");
-    if (!rocblas_load()) return fail(MILE_ERR_HIP, "LeNet needs librocblas.so, which could not be loaded");
-  }
+  static int (*const layout[])(mile_sampler *) = {layout_fcn, layout_lenet, layout_lenetti, layout_attn};   // by mile_model
+  if (spec->model < MILE_MODEL_FCN || spec->model > MILE_MODEL_ATTN) return fail(MILE_ERR_INVALID, "unknown model");
 
   auto *s = new mile_sampler();
   s->spec = *spec;
@@ -316,120 +428,12 @@ int32_t mile_create(const mile_model_spec *spec, int32_t device, mile_sampler **
   ds.prior = spec->prior;
   ds.prior_loc = spec->prior_loc;
   ds.prior_scale = spec->prior_scale;
-  if (spec->model == MILE_MODEL_ATTN) {   // ravel_pytree order (sorted keys): MDPA.{key, out, query, value}, TokenEmbedding_0,
-                                          // classifier, projection_*; bias before kernel
-    AttnGeom &g = s->ag;
-    g.V = spec->vocab_size; g.T = spec->ctx_len; g.C = spec->emb_size; g.H = spec->n_heads; g.D = spec->qkv_dim;
-    g.hd = g.D / g.H; g.NP = spec->n_layers - 1; g.K = spec->widths[g.NP]; g.bias = spec->use_bias ? 1 : 0;
-    g.Tp = (g.T + 15) / 16 * 16;
-    for (int l = 0; l < ATTN_MAX_NP; ++l) { g.P[l] = l < g.NP ? spec->widths[l] : 0; g.b_p[l] = g.k_p[l] = -1; }
-    if (attn_lds_bytes(g, false) > ATTN_LDS_MAX) {
-      delete s;
-      return fail(MILE_ERR_INVALID, "AttentionClassifier: shape needs more than 160 KB of LDS");
-    }
-    long long o = 0;
-    auto put = [&](int &b, int &k, long long nb, long long nk) { b = g.bias && nb ? (int)o : -1; o += g.bias ? nb : 0; k = (int)o; o += nk; };
-    int dummy;
-    put(g.b_k, g.k_k, g.D, (long long)g.C * g.D);
-    put(g.b_o, g.k_o, g.C, (long long)g.D * g.C);
-    put(g.b_q, g.k_q, g.D, (long long)g.C * g.D);
-    put(g.b_v, g.k_v, g.D, (long long)g.C * g.D);
-    put(dummy, g.emb, 0, (long long)g.V * g.C);
-    put(dummy, g.pos, 0, (long long)g.T * g.C);
-    put(g.b_c, g.k_c, g.K, (long long)(g.NP ? g.P[g.NP - 1] : g.C) * g.K);
-    for (int l = 0; l < g.NP; ++l) put(g.b_p[l], g.k_p[l], g.P[l], (long long)(l ? g.P[l - 1] : g.C) * g.P[l]);
-    if (o > 0x7fffffffLL) { delete s; return fail(MILE_ERR_INVALID, "AttentionClassifier: too many parameters"); }
-    g.d = (int)o;
-    ds.d = g.d;
-    ds.widths[0] = g.K;
-    ds.b_off[0] = g.b_c; ds.w_off[0] = g.k_c;
-    ds.max_width = 64; ds.act_stride = 0;
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) == hipSuccess && device < cnt) {
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, device) == hipSuccess) s->n_cu = prop.multiProcessorCount;
-    }
-    *out = s;
-    return MILE_OK;
+  if (const int rc = layout[spec->model](s)) {
+    delete s;
+    return rc;
   }
-  if (spec->model == MILE_MODEL_LENETTI) {   // ravel_pytree order of {'core': {conv1, fc1, fc2, fc3, fc4}}: bias, kernel each
-    LeNettiGeom &g = s->ng;
-    g.C = spec->img_c; g.H = spec->img_h; g.W = spec->img_w; g.K = spec->widths[0];
-    g.Ho = g.H + 2; g.Wo = g.W + 2; g.P = g.Ho * g.Wo;
-    int o = 0;
-    g.b_c = o; o += 1;   g.k_c = o; o += 9 * g.C;
-    g.b_1 = o; o += 8;   g.k_1 = o; o += 8 * g.P;
-    g.b_2 = o; o += 8;   g.k_2 = o; o += 64;
-    g.b_3 = o; o += 8;   g.k_3 = o; o += 64;
-    g.b_4 = o; o += g.K; g.k_4 = o; o += 8 * g.K;
-    g.d = o;
-    ds.d = g.d;
-    ds.widths[0] = g.K;
-    ds.b_off[0] = g.b_c; ds.w_off[0] = g.k_c;
-    ds.max_width = 8; ds.act_stride = 0;
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) == hipSuccess && device < cnt) {
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, device) == hipSuccess) s->n_cu = prop.multiProcessorCount;
-    }
-    *out = s;
-    return MILE_OK;
-  }
-  if (spec->model == MILE_MODEL_LENET) {   // ravel_pytree order of {'core': {conv1, conv2, fc1, fc2, fc3}}: bias, kernel each
-    LeNetGeom &g = s->lg;
-    g.C = spec->img_c; g.H = spec->img_h; g.W = spec->img_w; g.K = spec->widths[0];
-    g.hp1 = g.H / 2; g.wp1 = g.W / 2; g.h2 = g.hp1 - 4; g.w2 = g.wp1 - 4; g.hp2 = g.h2 / 2; g.wp2 = g.w2 / 2;
-    g.flat = g.hp2 * g.wp2 * 16;
-    long long o = 0;
-    g.b_c1 = (int)o; o += 6;   g.k_c1 = (int)o; o += 25LL * g.C * 6;
-    g.b_c2 = (int)o; o += 16;  g.k_c2 = (int)o; o += 150LL * 16;
-    g.b_f1 = (int)o; o += 120; g.k_f1 = (int)o; o += (long long)g.flat * 120;
-    g.b_f2 = (int)o; o += 84;  g.k_f2 = (int)o; o += 120LL * 84;
-    g.b_f3 = (int)o; o += g.K; g.k_f3 = (int)o; o += 84LL * g.K;
-    if (o > 0x7fffffffLL) { delete s; return fail(MILE_ERR_INVALID, "parameter count exceeds int32"); }
-    g.d = (int)o;
-    ds.d = g.d;
-    ds.widths[0] = g.K;
-    ds.b_off[0] = g.b_c1; ds.w_off[0] = g.k_c1;
-    ds.max_width = 150; ds.act_stride = 0;
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) == hipSuccess && device < cnt) {
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, device) == hipSuccess) s->n_cu = prop.multiProcessorCount;
-    }
-    *out = s;
-    return MILE_OK;
-  }
-  // ravel_pytree order: layers sorted by NAME ("layer10" < "layer2"), bias before kernel
-  std::vector<int> order(spec->n_layers);
-  for (int i = 0; i < spec->n_layers; ++i) order[i] = i;
-  std::sort(order.begin(), order.end(), [](int a, int b) {
-    return std::string("layer") + std::to_string(a) < std::string("layer") + std::to_string(b);
-  });
-  long long off = 0;
-  for (int li : order) {
-    const int fin = li == 0 ? spec->in_features : spec->widths[li - 1], fout = spec->widths[li];
-    ds.b_off[li] = (int)off; off += fout;
-    ds.w_off[li] = (int)off; off += (long long)fin * fout;
-  }
-  if (off > 0x7fffffffLL) { delete s; return fail(MILE_ERR_INVALID, "parameter count exceeds int32"); }
-  if (off < 2) { delete s; return fail(MILE_ERR_INVALID, "The target distribution must have more than 1 dimension for MCLMC."); }
-  ds.d = (int)off;
-  ds.act_off[0] = 0;
-  int a = spec->in_features, mw = spec->in_features;
-  for (int l = 0; l < spec->n_layers; ++l) {
-    ds.widths[l] = spec->widths[l];
-    ds.act_off[l + 1] = a;
-    a += spec->widths[l];
-    mw = std::max(mw, spec->widths[l]);
-  }
-  ds.act_stride = a;
-  ds.max_width = mw;
-  if (generic_R(ds) < 1) { delete s; return fail(MILE_ERR_INVALID, "network too wide for the generic kernel"); }
-
   int cnt = 0;
-  hipError_t e = hipGetDeviceCount(&cnt);
-  if (e == hipSuccess && device < cnt) {
+  if (hipGetDeviceCount(&cnt) == hipSuccess && device < cnt) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) s->n_cu = prop.multiProcessorCount;
   }
@@ -506,33 +510,9 @@ int32_t mile_destroy(mile_sampler *s) {
 int64_t mile_param_count(const mile_sampler *s) { return s ? s->ds.d : -1; }
 
 int32_t mile_param_offsets(const mile_sampler *s, int32_t layer, int64_t *bias_off, int64_t *kernel_off) {
-  if (s && s->spec.model == MILE_MODEL_LENET) {   // layers 0..4 = conv1, conv2, fc1, fc2, fc3
-    const LeNetGeom &g = s->lg;
-    const int bo[5] = {g.b_c1, g.b_c2, g.b_f1, g.b_f2, g.b_f3}, ko[5] = {g.k_c1, g.k_c2, g.k_f1, g.k_f2, g.k_f3};
-    if (layer < 0 || layer >= 5) return fail(MILE_ERR_INVALID, "mile_param_offsets: bad layer");
-    if (bias_off) *bias_off = bo[layer];
-    if (kernel_off) *kernel_off = ko[layer];
-    return MILE_OK;
-  }
-  if (s && s->spec.model == MILE_MODEL_ATTN) {   // key, out, query, value, Embedding, PositionEmbedding, classifier, projection_*
-    const AttnGeom &g = s->ag;
-    const int bo[8] = {g.b_k, g.b_o, g.b_q, g.b_v, -1, -1, g.b_c, -1}, ko[6] = {g.k_k, g.k_o, g.k_q, g.k_v, g.emb, g.pos};
-    if (layer < 0 || layer >= 7 + g.NP) return fail(MILE_ERR_INVALID, "mile_param_offsets: bad layer");
-    if (bias_off) *bias_off = layer >= 7 ? g.b_p[layer - 7] : bo[layer];
-    if (kernel_off) *kernel_off = layer >= 7 ? g.k_p[layer - 7] : (layer == 6 ? g.k_c : ko[layer]);
-    return MILE_OK;
-  }
-  if (s && s->spec.model == MILE_MODEL_LENETTI) {   // layers 0..4 = conv1, fc1, fc2, fc3, fc4
-    const LeNettiGeom &g = s->ng;
-    const int bo[5] = {g.b_c, g.b_1, g.b_2, g.b_3, g.b_4}, ko[5] = {g.k_c, g.k_1, g.k_2, g.k_3, g.k_4};
-    if (layer < 0 || layer >= 5) return fail(MILE_ERR_INVALID, "mile_param_offsets: bad layer");
-    if (bias_off) *bias_off = bo[layer];
-    if (kernel_off) *kernel_off = ko[layer];
-    return MILE_OK;
-  }
-  if (!s || layer < 0 || layer >= s->ds.n_layers) return fail(MILE_ERR_INVALID, "mile_param_offsets: bad layer");
-  if (bias_off) *bias_off = s->ds.b_off[layer];
-  if (kernel_off) *kernel_off = s->ds.w_off[layer];
+  if (!s || layer < 0 || layer >= (int)s->layers.size()) return fail(MILE_ERR_INVALID, "mile_param_offsets: bad layer");
+  if (bias_off) *bias_off = s->layers[layer].bias_off;
+  if (kernel_off) *kernel_off = s->layers[layer].kernel_off;
   return MILE_OK;
 }
 
@@ -561,7 +541,8 @@ int32_t mile_set_data(mile_sampler *s, const float *X, const void *y, int64_t N,
   // Same number of rows as before (the warm-start stage hands over a reshuffled copy of the training set every epoch,
   // src/dataset/tabular.py:170-212): every buffer and the workspace keep their sizes -- overwrite in place, no
   // free / malloc cycle of ~15 allocations per epoch.
-  const bool same_shape = s->X && s->N == (int)N;
+  const bool w128b = grad_kernel(MILE_GRAD_MFMA_W128_BF16).supports(s);   // + the bf16 copies of k_grad_w128b
+  const bool same_shape = s->N == (int)N && s->X && s->Xp && s->y && (!w128b || (s->Xb && s->Xt));
   if (!same_shape) {
     free_data(s);
     free_ws(s);
@@ -583,7 +564,7 @@ int32_t mile_set_data(mile_sampler *s, const float *X, const void *y, int64_t N,
   const long long tot = (long long)s->Npad * s->Fp;
   k_pad_x<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(s->X, s->Xp, s->N, s->Npad, F, s->Fp);
   HIP_TRY(hipGetLastError());
-  if (w128b_supported(s->spec)) {
+  if (w128b) {
     s->Npb = ((int)N + 63) / 64 * 64;
     if (!same_shape) {
       HIP_TRY(hipMalloc(&s->Xb, (size_t)s->Npb * 16 * 2));
@@ -613,11 +594,9 @@ int32_t mile_reserve(mile_sampler *s, int32_t E) {
   if (!s->X) return fail(MILE_ERR_STATE, "mile_reserve: call mile_set_data first");
   HIP_TRY(hipSetDevice(s->device));
   // capacity must cover whichever grad kernel is selected later
-  int S = std::max(choose_S(s, E, MILE_GRAD_GENERIC), w64_supported(s->spec) ? choose_S(s, E, MILE_GRAD_MFMA_W64) : 1);
-  if (w128b_supported(s->spec)) S = std::max(S, choose_S(s, E, MILE_GRAD_MFMA_W128_BF16));
-  if (narrow_supported(s->spec)) S = std::max(S, choose_S(s, E, MILE_GRAD_MFMA_NARROW_F32));
-  if (s->spec.model == MILE_MODEL_LENETTI) S = std::max(S, choose_S(s, E, MILE_GRAD_LENETTI_F32));
-  if (s->spec.model == MILE_MODEL_ATTN) S = std::max(S, choose_S(s, E, MILE_GRAD_ATTN_F32));
+  int S = choose_S(s, E, MILE_GRAD_GENERIC);
+  for (int k = MILE_GRAD_GENERIC; k <= MILE_GRAD_ATTN_F32; ++k)
+    if (grad_kernel(k).supports(s)) S = std::max(S, choose_S(s, E, k));
   // A smaller ensemble splits the rows of a particle over MORE workgroups (S grows as E shrinks): capacity is counted in
   // slab rows E * S, and a later call with fewer particles must neither fail nor shrink what a larger one reserved.
   if (E <= s->E_cap && (size_t)E * S <= s->ES_cap) return MILE_OK;
@@ -643,24 +622,11 @@ int32_t mile_reserve(mile_sampler *s, int32_t E) {
 int32_t mile_set_grad_kernel(mile_sampler *s, int32_t which) {
   if (!s) return fail(MILE_ERR_INVALID, "null handle");
   if (which < MILE_GRAD_AUTO || which > MILE_GRAD_ATTN_F32) return fail(MILE_ERR_INVALID, "unknown grad kernel");
-  if ((s->spec.model == MILE_MODEL_ATTN) != (which == MILE_GRAD_ATTN_F32) && which != MILE_GRAD_AUTO)
-    return fail(MILE_ERR_INVALID, "ATTN_F32 is the kernel of MILE_MODEL_ATTN, and its only one");
-  if ((s->spec.model == MILE_MODEL_LENETTI) != (which == MILE_GRAD_LENETTI_F32) && which != MILE_GRAD_AUTO)
-    return fail(MILE_ERR_INVALID, "LENETTI_F32 is the kernel of MILE_MODEL_LENETTI, and its only one");
-  if (which == MILE_GRAD_MFMA_NARROW_F32 && !narrow_supported(s->spec))
-    return fail(MILE_ERR_INVALID, "MFMA_NARROW_F32 needs an FCN with 1-3 hidden layers of width <= 64 and F <= 64 (or 4-10 of width <= 16 and F <= 16) and <= 16 outputs");
-  if ((which == MILE_GRAD_MFMA_WIDE_BF16X3 || which == MILE_GRAD_MFMA_WIDE_BF16) && s->spec.model != MILE_MODEL_FCN)
-    return fail(MILE_ERR_INVALID, "MFMA_WIDE_* are FCN kernels");
-  if ((s->spec.model == MILE_MODEL_LENET) != (which == MILE_GRAD_LENET_F32 || which == MILE_GRAD_LENET_BF16) && which != MILE_GRAD_AUTO)
-    return fail(MILE_ERR_INVALID, "LENET_F32 / LENET_BF16 are the kernels of MILE_MODEL_LENET, and its only ones");
-  if (which == MILE_GRAD_LENET_BF16 && s->lg.C > 4) return fail(MILE_ERR_INVALID, "LENET_BF16 needs <= 4 image channels");
-  if (which == MILE_GRAD_GEMM_F32 && !rocblas_load()) return fail(MILE_ERR_HIP, "GEMM_F32 needs librocblas.so, which could not be loaded");
-  if (which == MILE_GRAD_MFMA_W128_BF16 && !w128b_supported(s->spec))
-    return fail(MILE_ERR_INVALID, "MFMA_W128_BF16 needs ReLU regression with 1-3 hidden layers of width 128 and F <= 16");
-  if (which == MILE_GRAD_MFMA_W64 && !w64_supported(s->spec))
-    return fail(MILE_ERR_INVALID, "MFMA_W64 needs ReLU regression with 1-3 hidden layers of width 64 and F <= 16");
-  if (which == MILE_GRAD_MFMA_W64_BF16X3 && !w64x3_supported(s->spec))
-    return fail(MILE_ERR_INVALID, "MFMA_W64_BF16X3 needs ReLU regression with 2-3 hidden layers of width 64 and F <= 16");
+  if (which != MILE_GRAD_AUTO) {
+    const GradKernel &k = grad_kernel(which);
+    if (!k.supports(s)) return fail(MILE_ERR_INVALID, k.refusal);
+    if (k.needs_rocblas && !rocblas_load()) return fail(MILE_ERR_HIP, k.needs_rocblas);
+  }
   s->grad_kernel = which;
   return MILE_OK;
 }
@@ -707,6 +673,12 @@ static void launch_update_al(const UpdParams &u, int E, int nk, hipStream_t st) 
 }
 
 // d beyond the register cache, up to 4 * UPD_NT * UPD_QMAX_BIG: k_update_big (x, u in registers, g in LDS)
+template <int NK, int AL, bool SDC>
+static bool launch_update_big_nk(const UpdParams &u, int E, int nt, size_t lds, hipStream_t st) {
+  if (mile_set_max_lds<k_update_big<NK, AL, SDC, -1>>(UPD_NT * NK * 16) != hipSuccess) return false;
+  k_update_big<NK, AL, SDC, -1><<<E, nt, lds, st>>>(u);
+  return true;
+}
 template <int AL, bool SDC>
 static bool launch_update_big_al(const UpdParams &u, int E, int nk, hipStream_t st) {
   const int nqf = u.d >> 2;
@@ -714,29 +686,13 @@ static bool launch_update_big_al(const UpdParams &u, int E, int nk, hipStream_t 
   const size_t lds = (size_t)nk * nt * 16;
   // no compile-time launch kinds here: with the flag tests folded the unrolled quads become one basic block, the compiler
   // interleaves them and spills 109 registers (NK = 9, record kind) against 7 with the run-time flags
-#define MILE_UPD_BIG(NK_, CF_)                                                                                     \
-  {                                                                                                                \
-    static bool attr = false;                                                                                      \
-    if (!attr) {                                                                                                   \
-      if (hipFuncSetAttribute((const void *)k_update_big<NK_, AL, SDC, CF_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              UPD_NT * NK_ * 16) != hipSuccess) return false;                                      \
-      attr = true;                                                                                                 \
-    }                                                                                                              \
-    k_update_big<NK_, AL, SDC, CF_><<<E, nt, lds, st>>>(u);                                                        \
-    return true;                                                                                                   \
-  }
-#define MILE_UPD_BIG_CASE(NK_) \
-  case NK_:                    \
-    MILE_UPD_BIG(NK_, -1)
   switch (nk) {
-    MILE_UPD_BIG_CASE(5)
-    MILE_UPD_BIG_CASE(6)
-    MILE_UPD_BIG_CASE(7)
-    MILE_UPD_BIG_CASE(8)
-    MILE_UPD_BIG_CASE(9)
+    case 5: return launch_update_big_nk<5, AL, SDC>(u, E, nt, lds, st);
+    case 6: return launch_update_big_nk<6, AL, SDC>(u, E, nt, lds, st);
+    case 7: return launch_update_big_nk<7, AL, SDC>(u, E, nt, lds, st);
+    case 8: return launch_update_big_nk<8, AL, SDC>(u, E, nt, lds, st);
+    case 9: return launch_update_big_nk<9, AL, SDC>(u, E, nt, lds, st);
   }
-#undef MILE_UPD_BIG_CASE
-#undef MILE_UPD_BIG
   return false;
 }
 
@@ -797,12 +753,8 @@ hipError_t mile_launch_w64_split_fq2(int nh, const GradParams &gp, int E, hipStr
 template <int NH, int FQ, bool SPLIT = false>
 static hipError_t launch_w64(const GradParams &gp, const W64Fuse &fz, int E, hipStream_t st) {
   using LY = W64Layout<NH, FQ, SPLIT>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_grad_w64<NH, FQ, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, LY::BYTES);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  hipError_t e = mile_set_max_lds<k_grad_w64<NH, FQ, SPLIT>>(LY::BYTES);
+  if (e != hipSuccess) return e;
   if constexpr (W64FuseArg<FQ, SPLIT>::FUSABLE) {
     k_grad_w64<NH, FQ, SPLIT><<<dim3(gp.S, E), 256, LY::BYTES, st>>>(gp, fz);
   } else {
@@ -815,7 +767,7 @@ static hipError_t launch_w64(const GradParams &gp, const W64Fuse &fz, int E, hip
 // Can the update that follows this gradient run as the grad launch's epilogue (k_grad_w64 SPLIT, W64Fuse)?
 // 8-byte aligned rows everywhere (the epilogue is the AL = 2 form), no preconditioner, d within its register cache.
 static bool fuse_ok(const mile_sampler *s, int kernel, const UpdParams &u) {
-  if (!MILE_W64_EPILOGUE_ON || kernel != MILE_GRAD_MFMA_W64_BF16X3 || getenv("MILE_NO_FUSE")) return false;
+  if (!MILE_W64_EPILOGUE_ON || !grad_kernel(kernel).fuses || getenv("MILE_NO_FUSE")) return false;
   if (u.sdc || (u.d & 1) || u.u_rec) return false;   // (the merged warm-up launch exists as a stand-alone kernel only)
   const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
   if (fq != 1) return false;                       // the F > 8 kernels are built without the epilogue (mile_grad_w64.h)
@@ -832,12 +784,8 @@ static hipError_t launch_narrow_t(const GradParams &gp, int E, int nw, hipStream
   constexpr bool WL = TH >= 3;
   using LY = NarrowLayout<NH, TH, TF, WL>;
   if constexpr (WL) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void *)k_grad_narrow<NH, TH, TF, WL>, hipFuncAttributeMaxDynamicSharedMemorySize, LY::BYTES);
-      if (e != hipSuccess) return e;
-      attr_set = true;
-    }
+    hipError_t e = mile_set_max_lds<k_grad_narrow<NH, TH, TF, WL>>(LY::BYTES);
+    if (e != hipSuccess) return e;
   }
   k_grad_narrow<NH, TH, TF, WL><<<dim3(gp.S, E), 64 * nw, LY::BYTES, st>>>(gp);
   return hipGetLastError();
@@ -861,19 +809,11 @@ static hipError_t launch_narrow(const mile_sampler *s, const GradParams &gp, int
 template <int NH>
 static hipError_t launch_w128b(const GradParams &gp, int E, hipStream_t st) {
   using LY = W128Layout<NH, 2>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_grad_w128b<NH, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LY::BYTES);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  hipError_t e = mile_set_max_lds<k_grad_w128b<NH, 2>>(LY::BYTES);
+  if (e != hipSuccess) return e;
   if (gp.dbg & 16) {   // dev: per-phase cycle counts from workgroup 0 (MILE_DEBUG=16)
-    static bool attr_t = false;
-    if (!attr_t) {
-      hipError_t e = hipFuncSetAttribute((const void *)k_grad_w128b<NH, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LY::BYTES);
-      if (e != hipSuccess) return e;
-      attr_t = true;
-    }
+    e = mile_set_max_lds<k_grad_w128b<NH, 2, true>>(LY::BYTES);
+    if (e != hipSuccess) return e;
     k_grad_w128b<NH, 2, true><<<dim3(gp.S, E), 256, LY::BYTES, st>>>(gp);
     long long hb[8];
     if (gp.dbg_buf && hipMemcpy(hb, gp.dbg_buf, 64, hipMemcpyDeviceToHost) == hipSuccess)
@@ -884,9 +824,6 @@ static hipError_t launch_w128b(const GradParams &gp, int E, hipStream_t st) {
   k_grad_w128b<NH, 2><<<dim3(gp.S, E), 256, LY::BYTES, st>>>(gp);
   return hipGetLastError();
 }
-
-template <int NH, int FQ, bool SPLIT = false>
-static int w64_lds_bytes() { return W64Layout<NH, FQ, SPLIT>::BYTES; }
 
 __global__ void k_fill(float *p, float v, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -977,23 +914,19 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
   if (grad) { df2 = take(ER * w_f2); df1 = take(ER * 120); dp2 = take(ER * n_p2); dz2 = take(direct ? 0 : ER * n_a2); dp1 = take(ER * n_p1); dz1 = take(direct ? 0 : ER * n_a1); }
   float *part1 = take(n_part1), *part2 = take(n_part2);
   if (direct) {
-    static bool attr_done = false;
-    if (!attr_done) {
-      HIP_TRY(hipFuncSetAttribute((const void *)k_conv5_fwd<6, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void *)k_conv5_fwd<16, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void *)k_conv5_dw<6, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void *)k_conv5_dw<16, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void *)k_conv5_dx<6, 16, 1, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void *)k_conv5m_fwd<CM_IN4, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void *)k_conv5m_fwd<CM_IN8, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void *)k_conv5m_dw<CM_IN4, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void *)k_conv5m_dw<CM_IN8, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void *)k_conv5m_dx<6, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void *)k_conv5m_fwd2x<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void *)k_conv5m_dx2x<6, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void *)k_conv5m_dw2x<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      attr_done = true;
-    }
+    HIP_TRY((mile_set_max_lds<k_conv5_fwd<6, 0>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5_fwd<16, 0>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5_dw<6, 0>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5_dw<16, 0>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5_dx<6, 16, 1, 0, 0>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5m_fwd<CM_IN4, 6>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5m_fwd<CM_IN8, 16>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5m_dw<CM_IN4, 6>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5m_dw<CM_IN8, 16>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5m_dx<6, 16>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5m_fwd2x<6>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5m_dx2x<6, 16>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5m_dw2x<6>>(150 * 1024)));
   }
   const int cm_dbg = getenv("MILE_CM_SKIP") ? atoi(getenv("MILE_CM_SKIP")) : 0;   // dev: timing knobs of k_conv5m_fwd
   const float one = 1.0f, zero = 0.0f;
@@ -1231,13 +1164,8 @@ static hipError_t launch_mm3_k(const MMParams &p, int batch, hipStream_t st) {
     if (!dbg && !no_full && p.M % 128 == 0 && p.N % 128 == 0)
       return launch_mm3_k<ALAY, BSRC, EPI, TERMS, ACT, ACCUM, COLSUM, true>(p, batch, st);
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_mm3<ALAY, BSRC, EPI, TERMS, KC, ACT, ACCUM, COLSUM, FULL>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, LY::BYTES);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  hipError_t e = mile_set_max_lds<k_mm3<ALAY, BSRC, EPI, TERMS, KC, ACT, ACCUM, COLSUM, FULL>>(LY::BYTES);
+  if (e != hipSuccess) return e;
   MMParams q = p;
   const int mtiles = (p.M + 127) / 128;
   const dim3 grid((p.N + 127) / 128, mtiles, batch);
@@ -1542,10 +1470,92 @@ static hipError_t launch_attn(mile_sampler *s, const float *theta, int E, const 
   return mile_launch_attn(ap, E, out_ll == nullptr, st);
 }
 
+// ---- the gradient of each grad kernel: the `grad` of its row in kGrad.  gp holds the row window and S; fz the update that runs
+// as the launch's epilogue (fuses) ----------------------------------------------------------------------------------------------
+// dev: phase timestamps of the w64 kernels (MILE_DEBUG=32; 100 MHz wall clock -> us)
+static int w64_report_phases(mile_sampler *s, const GradParams &gp, int E, hipStream_t st) {
+  if (!(gp.dbg & 32)) return MILE_OK;
+  const int S = gp.S;
+  std::vector<long long> hb((size_t)E * S * 16);
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy(hb.data(), s->dbg_buf, hb.size() * 8, hipMemcpyDeviceToHost));
+  long long t00 = hb[0], tend = 0;
+  for (int w = 0; w < E * S; ++w) { t00 = std::min(t00, hb[w * 16]); tend = std::max({tend, hb[w * 16 + 2], hb[w * 16 + 4]}); }
+  double a[4] = {0, 0, 0, 0}, mx[4] = {0, 0, 0, 0}, ep[4] = {0, 0, 0, 0}, sub[4] = {0, 0, 0, 0}; int nl = 0;
+  for (int w = 0; w < E * S; ++w) {
+    const long long *q = &hb[w * 16];
+    const double v0 = (q[1] - q[0]) * 0.01, v1 = (q[2] - q[1]) * 0.01;
+    a[0] += v0; a[1] += v1; mx[0] = std::max(mx[0], v0); mx[1] = std::max(mx[1], v1);
+    if (q[4]) { const double v2 = (q[3] - q[2]) * 0.01, v3 = (q[4] - q[3]) * 0.01; a[2] += v2; a[3] += v3; mx[2] = std::max(mx[2], v2); mx[3] = std::max(mx[3], v3); ++nl;
+      ep[0] += (q[5] - q[3]) * 0.01; ep[1] += (q[6] - q[5]) * 0.01; ep[2] += (q[7] - q[6]) * 0.01; ep[3] += (q[4] - q[7]) * 0.01;
+      sub[0] += (q[8] - q[5]) * 0.01; sub[1] += (q[9] - q[8]) * 0.01; sub[2] += (q[10] - q[9]) * 0.01; sub[3] += (q[6] - q[10]) * 0.01; }
+  }
+  fprintf(stderr, "w64 phases (us, mean/max over %d WGs): main %.1f/%.1f reduce+store %.1f/%.1f | last arrivers (%d): drain+ticket %.1f/%.1f epilogue %.1f/%.1f | first start -> last end %.1f\n",
+          E * S, a[0] / (E * S), mx[0], a[1] / (E * S), mx[1], nl, nl ? a[2] / nl : 0.0, mx[2], nl ? a[3] / nl : 0.0, mx[3], (tend - t00) * 0.01);
+  if (nl) fprintf(stderr, "    epilogue: loads %.1f  noise+sums+reduce %.1f  chain %.1f  pass2+stores %.1f   [sums: quads %.1f tail %.1f wave_sum %.1f lds+barrier %.1f]\n", ep[0] / nl, ep[1] / nl, ep[2] / nl, ep[3] / nl, sub[0] / nl, sub[1] / nl, sub[2] / nl, sub[3] / nl);
+  return MILE_OK;
+}
+static int grad_w64(mile_sampler *s, const GradParams &gp, const W64Fuse &fz, int E, hipStream_t st) {
+  const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
+  hipError_t e = hipErrorInvalidValue;
+  if (nh == 1 && fq == 1) e = launch_w64<1, 1>(gp, fz, E, st);
+  else if (nh == 2 && fq == 1) e = launch_w64<2, 1>(gp, fz, E, st);
+  else if (nh == 3 && fq == 1) e = launch_w64<3, 1>(gp, fz, E, st);
+  else if (nh == 1 && fq == 2) e = launch_w64<1, 2>(gp, fz, E, st);
+  else if (nh == 2 && fq == 2) e = launch_w64<2, 2>(gp, fz, E, st);
+  else if (nh == 3 && fq == 2) e = launch_w64<3, 2>(gp, fz, E, st);
+  HIP_TRY(e);
+  return w64_report_phases(s, gp, E, st);
+}
+static int grad_w64x3(mile_sampler *s, const GradParams &gp, const W64Fuse &fz, int E, hipStream_t st) {
+  const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
+  hipError_t e = hipErrorInvalidValue;
+  if (nh == 2 && fq == 1) e = launch_w64<2, 1, true>(gp, fz, E, st);
+  else if (nh == 3 && fq == 1) e = launch_w64<3, 1, true>(gp, fz, E, st);
+  else if (fq == 2 && !fz.enabled) e = mile_launch_w64_split_fq2(nh, gp, E, st);   // mile_w64_fq2.hip
+  HIP_TRY(e);
+  return w64_report_phases(s, gp, E, st);
+}
+static int grad_narrow(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
+  HIP_TRY(launch_narrow(s, gp, E, st));
+  return MILE_OK;
+}
+static int grad_attn(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
+  HIP_TRY(launch_attn(s, gp.theta, E, gp.X, gp.y, gp.N, gp.S, gp.dp, nullptr, st));
+  return MILE_OK;
+}
+static int grad_lenetti(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
+  HIP_TRY(launch_lenetti(s, gp.theta, E, gp.X, gp.y, gp.N, gp.S, gp.dp, nullptr, st));
+  return MILE_OK;
+}
+template <bool MFMA>
+static int grad_lenet(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
+  return run_lenet(s, gp.theta, E, gp.X, gp.y, gp.N, gp.slabs, gp.dp, gp.llpart, nullptr, 0, st, MFMA);
+}
+static int grad_gemm(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) { return launch_grad_gemm(s, gp, E, st); }
+static int grad_wide3(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) { return launch_grad_wide<3>(s, gp, E, st); }
+static int grad_wide1(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) { return launch_grad_wide<1>(s, gp, E, st); }
+static int grad_w128b(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
+  if (!s->Xb) return fail(MILE_ERR_STATE, "bf16 data copies missing: call mile_set_data");
+  const int nh = s->spec.n_layers - 1;
+  hipError_t e = hipErrorInvalidValue;
+  if (nh == 1) e = launch_w128b<1>(gp, E, st);
+  else if (nh == 2) e = launch_w128b<2>(gp, E, st);
+  else if (nh == 3) e = launch_w128b<3>(gp, E, st);
+  HIP_TRY(e);
+  return MILE_OK;
+}
+static size_t generic_lds(const DevSpec &ds) { return ((size_t)generic_R(ds) * (ds.act_stride + 2 * ds.max_width) + 16) * 4; }
+static int grad_generic(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
+  k_grad_generic<<<dim3(gp.S, E), 256, generic_lds(s->ds), st>>>(gp);
+  HIP_TRY(hipGetLastError());
+  return MILE_OK;
+}
+
 static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t st, const UpdParams *fused_update) {
   if (!s->X) return fail(MILE_ERR_STATE, "no data: call mile_set_data first");
-  const int kernel = resolved_kernel(s);
-  const int S = choose_S(s, E, kernel);
+  const GradKernel &k = grad_kernel(resolved_kernel(s));
+  const int S = k.row_splits(s, E);
   if (E > s->E_cap || (size_t)E * S > s->ES_cap) return fail(MILE_ERR_STATE, "workspace too small: call mile_reserve(E) first");
   GradParams gp;
   gp.spec = s->ds;
@@ -1554,10 +1564,7 @@ static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t s
   gp.slabs = s->slabs; gp.llpart = s->llpart;
   gp.N = s->N; gp.Npad = s->Npad; gp.Npb = s->Npb; gp.Fp = s->Fp; gp.S = S; gp.R = generic_R(s->ds); gp.dp = (s->ds.d + 3) / 4 * 4;
   if (s->win_count) {   // minibatch: the same kernels on a shifted view of the rows
-    const bool chunked = kernel == MILE_GRAD_MFMA_WIDE_BF16X3 || kernel == MILE_GRAD_MFMA_WIDE_BF16 || kernel == MILE_GRAD_LENET_F32 ||
-                         kernel == MILE_GRAD_LENET_BF16 || kernel == MILE_GRAD_LENETTI_F32 ||
-                         kernel == MILE_GRAD_ATTN_F32;   // these walk the rows in chunks anyway: a window is a shorter walk
-    if (kernel != MILE_GRAD_GENERIC && kernel != MILE_GRAD_MFMA_NARROW_F32 && !is_w64(kernel) && !chunked)
+    if (!k.windowed)
       return fail(MILE_ERR_STATE, "a row window needs the generic, the MFMA_NARROW, an MFMA_W64, an MFMA_WIDE, a LENET, the LENETTI or the ATTN grad kernel");
     if (fused_update) return fail(MILE_ERR_STATE, "row windows are for mile_logpost_grad only");
     const int F = s->spec.in_features;
@@ -1587,74 +1594,11 @@ static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t s
   }
   W64Fuse fz{};
   if (fused_update) {
-    if (kernel != MILE_GRAD_MFMA_W64_BF16X3) return fail(MILE_ERR_STATE, "fused update needs the mfma_w64_bf16x3 grad kernel");
+    if (!k.fuses) return fail(MILE_ERR_STATE, "fused update needs the mfma_w64_bf16x3 grad kernel");
     fz.upd = *fused_update; fz.arrive = s->arrive; fz.enabled = 1; fz.kind = upd_kind(*fused_update);
   }
-  if (kernel == MILE_GRAD_MFMA_W64) {
-    const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
-    hipError_t e = hipErrorInvalidValue;
-    if (nh == 1 && fq == 1) e = launch_w64<1, 1>(gp, fz, E, st);
-    else if (nh == 2 && fq == 1) e = launch_w64<2, 1>(gp, fz, E, st);
-    else if (nh == 3 && fq == 1) e = launch_w64<3, 1>(gp, fz, E, st);
-    else if (nh == 1 && fq == 2) e = launch_w64<1, 2>(gp, fz, E, st);
-    else if (nh == 2 && fq == 2) e = launch_w64<2, 2>(gp, fz, E, st);
-    else if (nh == 3 && fq == 2) e = launch_w64<3, 2>(gp, fz, E, st);
-    HIP_TRY(e);
-  } else if (kernel == MILE_GRAD_MFMA_W64_BF16X3) {
-    const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
-    hipError_t e = hipErrorInvalidValue;
-    if (nh == 2 && fq == 1) e = launch_w64<2, 1, true>(gp, fz, E, st);
-    else if (nh == 3 && fq == 1) e = launch_w64<3, 1, true>(gp, fz, E, st);
-    else if (fq == 2 && !fz.enabled) e = mile_launch_w64_split_fq2(nh, gp, E, st);   // mile_w64_fq2.hip
-    HIP_TRY(e);
-  } else if (kernel == MILE_GRAD_MFMA_NARROW_F32) {
-    HIP_TRY(launch_narrow(s, gp, E, st));
-  } else if (kernel == MILE_GRAD_ATTN_F32) {
-    HIP_TRY(launch_attn(s, theta, E, gp.X, gp.y, gp.N, S, gp.dp, nullptr, st));
-  } else if (kernel == MILE_GRAD_LENETTI_F32) {
-    HIP_TRY(launch_lenetti(s, theta, E, gp.X, gp.y, gp.N, S, gp.dp, nullptr, st));
-  } else if (kernel == MILE_GRAD_LENET_F32 || kernel == MILE_GRAD_LENET_BF16) {
-    const int rc = run_lenet(s, theta, E, gp.X, gp.y, gp.N, gp.slabs, gp.dp, gp.llpart, nullptr, 0, st, kernel == MILE_GRAD_LENET_BF16);
-    if (rc) return rc;
-  } else if (kernel == MILE_GRAD_GEMM_F32) {
-    const int rc = launch_grad_gemm(s, gp, E, st);
-    if (rc) return rc;
-  } else if (kernel == MILE_GRAD_MFMA_WIDE_BF16X3 || kernel == MILE_GRAD_MFMA_WIDE_BF16) {
-    const int rc = kernel == MILE_GRAD_MFMA_WIDE_BF16X3 ? launch_grad_wide<3>(s, gp, E, st) : launch_grad_wide<1>(s, gp, E, st);
-    if (rc) return rc;
-  } else if (kernel == MILE_GRAD_MFMA_W128_BF16) {
-    if (!s->Xb) return fail(MILE_ERR_STATE, "bf16 data copies missing: call mile_set_data");
-    const int nh = s->spec.n_layers - 1;
-    hipError_t e = hipErrorInvalidValue;
-    if (nh == 1) e = launch_w128b<1>(gp, E, st);
-    else if (nh == 2) e = launch_w128b<2>(gp, E, st);
-    else if (nh == 3) e = launch_w128b<3>(gp, E, st);
-    HIP_TRY(e);
-  } else {
-    const size_t lds = ((size_t)gp.R * (s->ds.act_stride + 2 * s->ds.max_width) + 16) * 4;
-    k_grad_generic<<<dim3(S, E), 256, lds, st>>>(gp);
-    HIP_TRY(hipGetLastError());
-  }
+  if (const int rc = k.grad(s, gp, fz, E, st)) return rc;
   if (s->timing) HIP_TRY(hipEventRecord(e1, st));
-  if ((gp.dbg & 32) && is_w64(kernel)) {   // dev: phase timestamps of the w64 kernels (100 MHz wall clock -> us)
-    std::vector<long long> hb((size_t)E * S * 16);
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(hb.data(), s->dbg_buf, hb.size() * 8, hipMemcpyDeviceToHost));
-    long long t00 = hb[0], tend = 0;
-    for (int w = 0; w < E * S; ++w) { t00 = std::min(t00, hb[w * 16]); tend = std::max({tend, hb[w * 16 + 2], hb[w * 16 + 4]}); }
-    double a[4] = {0, 0, 0, 0}, mx[4] = {0, 0, 0, 0}, ep[4] = {0, 0, 0, 0}, sub[4] = {0, 0, 0, 0}; int nl = 0;
-    for (int w = 0; w < E * S; ++w) {
-      const long long *q = &hb[w * 16];
-      const double v0 = (q[1] - q[0]) * 0.01, v1 = (q[2] - q[1]) * 0.01;
-      a[0] += v0; a[1] += v1; mx[0] = std::max(mx[0], v0); mx[1] = std::max(mx[1], v1);
-      if (q[4]) { const double v2 = (q[3] - q[2]) * 0.01, v3 = (q[4] - q[3]) * 0.01; a[2] += v2; a[3] += v3; mx[2] = std::max(mx[2], v2); mx[3] = std::max(mx[3], v3); ++nl;
-        ep[0] += (q[5] - q[3]) * 0.01; ep[1] += (q[6] - q[5]) * 0.01; ep[2] += (q[7] - q[6]) * 0.01; ep[3] += (q[4] - q[7]) * 0.01;
-        sub[0] += (q[8] - q[5]) * 0.01; sub[1] += (q[9] - q[8]) * 0.01; sub[2] += (q[10] - q[9]) * 0.01; sub[3] += (q[6] - q[10]) * 0.01; }
-    }
-    fprintf(stderr, "w64 phases (us, mean/max over %d WGs): main %.1f/%.1f reduce+store %.1f/%.1f | last arrivers (%d): drain+ticket %.1f/%.1f epilogue %.1f/%.1f | first start -> last end %.1f\n",
-            E * S, a[0] / (E * S), mx[0], a[1] / (E * S), mx[1], nl, nl ? a[2] / nl : 0.0, mx[2], nl ? a[3] / nl : 0.0, mx[3], (tend - t00) * 0.01);
-    if (nl) fprintf(stderr, "    epilogue: loads %.1f  noise+sums+reduce %.1f  chain %.1f  pass2+stores %.1f   [sums: quads %.1f tail %.1f wave_sum %.1f lds+barrier %.1f]\n", ep[0] / nl, ep[1] / nl, ep[2] / nl, ep[3] / nl, sub[0] / nl, sub[1] / nl, sub[2] / nl, sub[3] / nl);
-  }
   return MILE_OK;
 }
 
@@ -1670,12 +1614,8 @@ static int grad_then_update(mile_sampler *s, const float *theta, int E, const Up
 template <int NH, int FQ>
 static hipError_t launch_fwd_w64(const PredParams &pp, int S, hipStream_t st) {
   using LY = W64Layout<NH, FQ>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_fwd_w64<NH, FQ>, hipFuncAttributeMaxDynamicSharedMemorySize, LY::BYTES);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  hipError_t e = mile_set_max_lds<k_fwd_w64<NH, FQ>>(LY::BYTES);
+  if (e != hipSuccess) return e;
   k_fwd_w64<NH, FQ><<<dim3(pp.SB, S), 256, LY::BYTES, st>>>(pp);
   return hipGetLastError();
 }
@@ -1800,6 +1740,132 @@ static int launch_fwd_wide(mile_sampler *s, const float *theta, int S, const flo
   return MILE_OK;
 }
 
+// ---- evaluation of each grad kernel's model: the `loglik` of its row in kGrad.  pp holds the staged evaluation set ------------
+static int loglik_attn(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
+  const int SB = std::max(1, std::min({64, (s->n_cu + S - 1) / S, std::max(1, pp.N / 16)}));
+  for (int s0 = 0; s0 < S; s0 += 65535) {
+    const int Sc = std::min(65535, S - s0);
+    HIP_TRY(launch_attn(s, pp.theta + (size_t)s0 * s->ds.d, Sc, pp.X, pp.y, pp.N, SB, 0, pp.out + (size_t)s0 * pp.N, st));
+  }
+  return MILE_OK;
+}
+static int loglik_lenetti(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
+  const int SB = std::max(1, std::min({64, (2 * s->n_cu + S - 1) / S, std::max(1, pp.N / 32)}));
+  for (int s0 = 0; s0 < S; s0 += 65535) {
+    const int Sc = std::min(65535, S - s0);
+    HIP_TRY(launch_lenetti(s, pp.theta + (size_t)s0 * s->ds.d, Sc, pp.X, pp.y, pp.N, SB, 0, pp.out + (size_t)s0 * pp.N, st));
+  }
+  return MILE_OK;
+}
+template <bool MFMA>
+static int loglik_lenet(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
+  for (int s0 = 0; s0 < S; s0 += 256) {
+    const int rc = run_lenet(s, pp.theta + (size_t)s0 * s->ds.d, std::min(256, S - s0), pp.X, pp.y, pp.N, nullptr, 0, nullptr, pp.out, s0, st, MFMA);
+    if (rc) return rc;
+  }
+  return MILE_OK;
+}
+static int loglik_gemm(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
+  return launch_fwd_gemm(s, pp.theta, S, pp.X, pp.y, pp.N, pp.out, st);
+}
+// wide nets: evaluation stays fp32-faithful whatever the sampling kernel was
+static int loglik_wide(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
+  return launch_fwd_wide(s, pp.theta, S, pp.Xp, pp.Fp, pp.y, pp.N, pp.out, st);
+}
+static int loglik_w64(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
+  const int NB = pp.Npad / 32;
+  pp.SB = std::max(1, std::min(std::max(1, (2 * s->n_cu) / S), std::max(1, NB / 4)));
+  const int nh = s->spec.n_layers - 1, fq = pp.Fp / 8;
+  hipError_t e = hipErrorInvalidValue;
+  if (nh == 1 && fq == 1) e = launch_fwd_w64<1, 1>(pp, S, st);
+  else if (nh == 2 && fq == 1) e = launch_fwd_w64<2, 1>(pp, S, st);
+  else if (nh == 3 && fq == 1) e = launch_fwd_w64<3, 1>(pp, S, st);
+  else if (nh == 1 && fq == 2) e = launch_fwd_w64<1, 2>(pp, S, st);
+  else if (nh == 2 && fq == 2) e = launch_fwd_w64<2, 2>(pp, S, st);
+  else if (nh == 3 && fq == 2) e = launch_fwd_w64<3, 2>(pp, S, st);
+  HIP_TRY(e);
+  return MILE_OK;
+}
+static int loglik_generic(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
+  pp.SB = std::max(1, std::min(std::max(1, (4 * s->n_cu) / S), std::max(1, pp.N / 64)));
+  const size_t lds = ((size_t)pp.R * s->ds.act_stride + 16) * 4;
+  k_fwd_generic<<<dim3(pp.SB, S), 256, lds, st>>>(pp);
+  HIP_TRY(hipGetLastError());
+  return MILE_OK;
+}
+
+// ---- launch shape that mile_grad_launch_info reports: the `shape` of each row in kGrad --------------------------------------
+static LaunchShape shape_generic(const mile_sampler *s, int) { return {256, (int)generic_lds(s->ds)}; }
+static LaunchShape shape_w64(const mile_sampler *s, int) {
+  const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
+  return {256, nh == 1 ? (fq == 1 ? W64Layout<1, 1>::BYTES : W64Layout<1, 2>::BYTES)
+             : nh == 2 ? (fq == 1 ? W64Layout<2, 1>::BYTES : W64Layout<2, 2>::BYTES)
+                       : (fq == 1 ? W64Layout<3, 1>::BYTES : W64Layout<3, 2>::BYTES)};
+}
+static LaunchShape shape_w64x3(const mile_sampler *s, int) {
+  const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
+  return {256, nh == 2 ? (fq == 1 ? W64Layout<2, 1, true>::BYTES : W64Layout<2, 2, true>::BYTES)
+                       : (fq == 1 ? W64Layout<3, 1, true>::BYTES : W64Layout<3, 2, true>::BYTES)};
+}
+static LaunchShape shape_narrow(const mile_sampler *s, int S) {
+  const bool wl = narrow_tiles_hidden(s->spec) >= 3;
+  return {64 * (wl ? NRW_MAXW : narrow_waves(s, S, s->N)),
+          wl ? NarrowLayout<3, 4, 4, true>::BYTES                                         // upper bounds over the instantiations
+             : std::max(NarrowLayout<3, 2, 4>::BYTES, NarrowLayout<10, 1, 1>::BYTES)};
+}
+static LaunchShape shape_attn(const mile_sampler *s, int) { return {256, (int)attn_lds_bytes(s->ag, attn_weights_in_lds(s->ag))}; }
+static LaunchShape shape_lenetti(const mile_sampler *s, int) { return {256, (int)lenetti_lds_bytes(s->ng, lenetti_T(s->ng))}; }
+static LaunchShape shape_lenet_bf16(const mile_sampler *s, int) { return {256, (int)cm_lds_dw(CM_IN8, s->lg.hp1, s->lg.wp1, 0)}; }
+static LaunchShape shape_rocblas(const mile_sampler *, int) { return {256, 0}; }
+template <int TERMS>
+static LaunchShape shape_wide(const mile_sampler *, int) { return {256, MMLayout<MM_A_MK, MM_B_T3_NK, TERMS, MILE_MM_KC>::BYTES}; }
+static LaunchShape shape_w128b(const mile_sampler *s, int) {
+  const int nh = s->spec.n_layers - 1;
+  return {256, nh == 1 ? W128Layout<1, 2>::BYTES : nh == 2 ? W128Layout<2, 2>::BYTES : W128Layout<3, 2>::BYTES};
+}
+
+// ---- the grad kernels, one row per MILE_GRAD_* id (in id order) --------------------------------------------------------------
+static constexpr GradKernel kGrad[] = {
+    {MILE_GRAD_GENERIC, "k_grad_generic", is_fcn, "GENERIC is an FCN kernel", nullptr,
+     generic_S, true, false, grad_generic, loglik_generic, shape_generic},
+    {MILE_GRAD_MFMA_W64, "k_grad_w64", w64_supported,
+     "MFMA_W64 needs ReLU regression with 1-3 hidden layers of width 64 and F <= 16", nullptr,
+     w64_S, true, false, grad_w64, loglik_w64, shape_w64},
+    {MILE_GRAD_MFMA_W128_BF16, "k_grad_w128b", w128b_supported,
+     "MFMA_W128_BF16 needs ReLU regression with 1-3 hidden layers of width 128 and F <= 16", nullptr,
+     w128b_S, false, false, grad_w128b, loglik_wide, shape_w128b},
+    {MILE_GRAD_GEMM_F32, "rocblas_sgemm_strided_batched+k_gemm_*", is_fcn, "GEMM_F32 is an FCN kernel",
+     "GEMM_F32 needs librocblas.so, which could not be loaded",
+     one_S, false, false, grad_gemm, loglik_gemm, shape_rocblas},
+    {MILE_GRAD_LENET_F32, "rocblas_sgemm_strided_batched+k_im2col5/k_col2im5/k_avgpool2", is_lenet,
+     "LENET_F32 / LENET_BF16 are the kernels of MILE_MODEL_LENET, and its only ones", nullptr,
+     one_S, true, false, grad_lenet<false>, loglik_lenet<false>, shape_rocblas},
+    {MILE_GRAD_MFMA_W64_BF16X3, "k_grad_w64", w64x3_supported,
+     "MFMA_W64_BF16X3 needs ReLU regression with 2-3 hidden layers of width 64 and F <= 16", nullptr,
+     w64_S, true, true, grad_w64x3, loglik_w64, shape_w64x3},
+    {MILE_GRAD_MFMA_WIDE_BF16X3, "k_mm3 (layer-wise MFMA GEMMs)", is_fcn, "MFMA_WIDE_* are FCN kernels", nullptr,
+     one_S, true, false, grad_wide3, loglik_wide, shape_wide<3>},
+    {MILE_GRAD_MFMA_WIDE_BF16, "k_mm3 (layer-wise MFMA GEMMs)", is_fcn, "MFMA_WIDE_* are FCN kernels", nullptr,
+     one_S, true, false, grad_wide1, loglik_wide, shape_wide<1>},
+    {MILE_GRAD_LENET_BF16, "k_conv5m_fwd/dx/dw (implicit-GEMM bf16 MFMA) + k_mm3 (Dense, fp32-faithful three-term products)",
+     lenet_bf16_supported, "LENET_BF16 is a kernel of MILE_MODEL_LENET and needs <= 4 image channels", nullptr,
+     one_S, true, false, grad_lenet<true>, loglik_lenet<true>, shape_lenet_bf16},
+    {MILE_GRAD_MFMA_NARROW_F32, "k_grad_narrow", narrow_supported,
+     "MFMA_NARROW_F32 needs an FCN with 1-3 hidden layers of width <= 64 and F <= 64 (or 4-10 of width <= 16 and F <= 16) and <= 16 outputs",
+     nullptr, narrow_S, true, false, grad_narrow, loglik_generic, shape_narrow},
+    {MILE_GRAD_LENETTI_F32, "k_grad_lenetti", is_lenetti, "LENETTI_F32 is the kernel of MILE_MODEL_LENETTI, and its only one", nullptr,
+     lenetti_S, true, false, grad_lenetti, loglik_lenetti, shape_lenetti},
+    {MILE_GRAD_ATTN_F32, "k_grad_attn", is_attn, "ATTN_F32 is the kernel of MILE_MODEL_ATTN, and its only one", nullptr,
+     attn_S, true, false, grad_attn, loglik_attn, shape_attn},
+};
+static constexpr bool rows_in_id_order() {
+  for (int k = 0; k < (int)(sizeof(kGrad) / sizeof(kGrad[0])); ++k)
+    if (kGrad[k].id != k + 1) return false;
+  return sizeof(kGrad) / sizeof(kGrad[0]) == MILE_GRAD_ATTN_F32;
+}
+static_assert(rows_in_id_order(), "kGrad: one row per MILE_GRAD_* id, in id order");
+static const GradKernel &grad_kernel(int kernel) { return kGrad[kernel - 1]; }
+
 extern "C" int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, int32_t S, const float *X, const void *y,
                                          int64_t N, float *out, void *stream) {
   if (!s || !theta || !X || !y || !out || S < 1) return fail(MILE_ERR_INVALID, "mile_pointwise_loglik: bad argument");
@@ -1825,55 +1891,7 @@ extern "C" int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, in
   PredParams pp;
   pp.spec = s->ds; pp.theta = theta; pp.X = s->ev_X; pp.Xp = s->ev_Xp; pp.y = s->ev_y; pp.out = out;
   pp.N = (int)N; pp.Npad = Npad; pp.Fp = Fp; pp.R = generic_R(s->ds);
-  const int kernel = resolved_kernel(s);
-  if (kernel == MILE_GRAD_ATTN_F32) {
-    const int SB = std::max(1, std::min({64, (s->n_cu + S - 1) / S, std::max(1, (int)N / 16)}));
-    for (int s0 = 0; s0 < S; s0 += 65535) {
-      const int Sc = std::min(65535, S - s0);
-      HIP_TRY(launch_attn(s, theta + (size_t)s0 * s->ds.d, Sc, s->ev_X, s->ev_y, (int)N, SB, 0, out + (size_t)s0 * N, st));
-    }
-    return MILE_OK;
-  }
-  if (kernel == MILE_GRAD_LENETTI_F32) {
-    const int SB = std::max(1, std::min({64, (2 * s->n_cu + S - 1) / S, std::max(1, (int)N / 32)}));
-    for (int s0 = 0; s0 < S; s0 += 65535) {
-      const int Sc = std::min(65535, S - s0);
-      HIP_TRY(launch_lenetti(s, theta + (size_t)s0 * s->ds.d, Sc, s->ev_X, s->ev_y, (int)N, SB, 0, out + (size_t)s0 * N, st));
-    }
-    return MILE_OK;
-  }
-  if (kernel == MILE_GRAD_LENET_F32 || kernel == MILE_GRAD_LENET_BF16) {
-    for (int s0 = 0; s0 < S; s0 += 256) {
-      const int rc = run_lenet(s, theta + (size_t)s0 * s->ds.d, std::min(256, S - s0), s->ev_X, s->ev_y, (int)N, nullptr, 0, nullptr, out, s0, st,
-                               kernel == MILE_GRAD_LENET_BF16);
-      if (rc) return rc;
-    }
-    return MILE_OK;
-  }
-  if (kernel == MILE_GRAD_GEMM_F32) return launch_fwd_gemm(s, theta, S, s->ev_X, s->ev_y, (int)N, out, st);
-  if (kernel == MILE_GRAD_MFMA_WIDE_BF16X3 || kernel == MILE_GRAD_MFMA_WIDE_BF16 || kernel == MILE_GRAD_MFMA_W128_BF16) {
-    // wide nets: evaluation stays fp32-faithful whatever the sampling kernel was
-    return launch_fwd_wide(s, theta, S, s->ev_Xp, Fp, s->ev_y, (int)N, out, st);
-  }
-  if (is_w64(kernel)) {
-    const int NB = Npad / 32;
-    pp.SB = std::max(1, std::min(std::max(1, (2 * s->n_cu) / S), std::max(1, NB / 4)));
-    const int nh = s->spec.n_layers - 1, fq = Fp / 8;
-    hipError_t e = hipErrorInvalidValue;
-    if (nh == 1 && fq == 1) e = launch_fwd_w64<1, 1>(pp, S, st);
-    else if (nh == 2 && fq == 1) e = launch_fwd_w64<2, 1>(pp, S, st);
-    else if (nh == 3 && fq == 1) e = launch_fwd_w64<3, 1>(pp, S, st);
-    else if (nh == 1 && fq == 2) e = launch_fwd_w64<1, 2>(pp, S, st);
-    else if (nh == 2 && fq == 2) e = launch_fwd_w64<2, 2>(pp, S, st);
-    else if (nh == 3 && fq == 2) e = launch_fwd_w64<3, 2>(pp, S, st);
-    HIP_TRY(e);
-  } else {
-    pp.SB = std::max(1, std::min(std::max(1, (4 * s->n_cu) / S), std::max(1, (int)N / 64)));
-    const size_t lds = ((size_t)pp.R * s->ds.act_stride + 16) * 4;
-    k_fwd_generic<<<dim3(pp.SB, S), 256, lds, st>>>(pp);
-    HIP_TRY(hipGetLastError());
-  }
-  return MILE_OK;
+  return grad_kernel(resolved_kernel(s)).loglik(s, pp, S, st);
 }
 
 extern "C" {
@@ -1881,56 +1899,14 @@ extern "C" {
 int32_t mile_grad_launch_info(const mile_sampler *s, int32_t E, int32_t *grid_x, int32_t *grid_y,
                               int32_t *block, int32_t *lds_bytes, char *name, int32_t name_len) {
   if (!s || !s->X) return fail(MILE_ERR_STATE, "mile_grad_launch_info: no data set");
-  const int kernel = resolved_kernel(s);
-  const int S = choose_S(s, E, kernel);
+  const GradKernel &k = grad_kernel(resolved_kernel(s));
+  const int S = k.row_splits(s, E);
+  const LaunchShape sh = k.shape(s, S);
   if (grid_x) *grid_x = S;
   if (grid_y) *grid_y = E;
-  if (block) *block = 256;
-  int lds = 0;
-  const char *nm = "k_grad_generic";
-  if (kernel == MILE_GRAD_MFMA_W64) {
-    const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
-    nm = "k_grad_w64";
-    lds = nh == 1 ? (fq == 1 ? w64_lds_bytes<1, 1>() : w64_lds_bytes<1, 2>())
-        : nh == 2 ? (fq == 1 ? w64_lds_bytes<2, 1>() : w64_lds_bytes<2, 2>())
-                  : (fq == 1 ? w64_lds_bytes<3, 1>() : w64_lds_bytes<3, 2>());
-  } else if (kernel == MILE_GRAD_MFMA_W64_BF16X3) {
-    const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
-    nm = "k_grad_w64";
-    lds = nh == 2 ? (fq == 1 ? w64_lds_bytes<2, 1, true>() : w64_lds_bytes<2, 2, true>())
-                  : (fq == 1 ? w64_lds_bytes<3, 1, true>() : w64_lds_bytes<3, 2, true>());
-  } else if (kernel == MILE_GRAD_MFMA_NARROW_F32) {
-    nm = "k_grad_narrow";
-    if (block) *block = 64 * (narrow_tiles_hidden(s->spec) >= 3 ? NRW_MAXW : narrow_waves(s, S, s->N));
-    lds = narrow_tiles_hidden(s->spec) >= 3 ? NarrowLayout<3, 4, 4, true>::BYTES      // upper bounds over the instantiations
-                                            : std::max(NarrowLayout<3, 2, 4>::BYTES, NarrowLayout<10, 1, 1>::BYTES);
-  } else if (kernel == MILE_GRAD_ATTN_F32) {
-    nm = "k_grad_attn";
-    lds = (int)attn_lds_bytes(s->ag, attn_weights_in_lds(s->ag));
-  } else if (kernel == MILE_GRAD_LENETTI_F32) {
-    nm = "k_grad_lenetti";
-    lds = (int)lenetti_lds_bytes(s->ng, lenetti_T(s->ng));
-  } else if (kernel == MILE_GRAD_LENET_BF16) {
-    nm = "k_conv5m_fwd/dx/dw (implicit-GEMM bf16 MFMA) + k_mm3 (Dense, fp32-faithful three-term products)";
-    lds = (int)cm_lds_dw(CM_IN8, s->lg.hp1, s->lg.wp1, 0);
-  } else if (kernel == MILE_GRAD_LENET_F32) {
-    nm = "rocblas_sgemm_strided_batched+k_im2col5/k_col2im5/k_avgpool2";
-    lds = 0;
-  } else if (kernel == MILE_GRAD_MFMA_WIDE_BF16X3 || kernel == MILE_GRAD_MFMA_WIDE_BF16) {
-    nm = "k_mm3 (layer-wise MFMA GEMMs)";
-    lds = kernel == MILE_GRAD_MFMA_WIDE_BF16X3 ? MMLayout<MM_A_MK, MM_B_T3_NK, 3, MILE_MM_KC>::BYTES : MMLayout<MM_A_MK, MM_B_T3_NK, 1, MILE_MM_KC>::BYTES;
-  } else if (kernel == MILE_GRAD_GEMM_F32) {
-    nm = "rocblas_sgemm_strided_batched+k_gemm_*";
-    lds = 0;
-  } else if (kernel == MILE_GRAD_MFMA_W128_BF16) {
-    const int nh = s->spec.n_layers - 1;
-    nm = "k_grad_w128b";
-    lds = nh == 1 ? W128Layout<1, 2>::BYTES : nh == 2 ? W128Layout<2, 2>::BYTES : W128Layout<3, 2>::BYTES;
-  } else {
-    lds = (int)(((size_t)generic_R(s->ds) * (s->ds.act_stride + 2 * s->ds.max_width) + 16) * 4);
-  }
-  if (lds_bytes) *lds_bytes = lds;
-  if (name && name_len > 0) { std::strncpy(name, nm, name_len - 1); name[name_len - 1] = 0; }
+  if (block) *block = sh.block;
+  if (lds_bytes) *lds_bytes = sh.lds;
+  if (name && name_len > 0) { std::strncpy(name, k.name, name_len - 1); name[name_len - 1] = 0; }
   return MILE_OK;
 }
 

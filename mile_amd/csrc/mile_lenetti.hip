@@ -7,13 +7,8 @@
 template <int PPT, int T, int CM>
 static hipError_t launch_t(const LeNettiParams &lp, int E, bool grad, hipStream_t st) {
   const size_t lds = lenetti_lds_bytes(lp.g, T);
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_grad_lenetti<PPT, T, CM>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_fwd_lenetti<PPT, T, CM>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
+  hipError_t e = grad ? mile_set_max_lds<k_grad_lenetti<PPT, T, CM>>(150 * 1024) : mile_set_max_lds<k_fwd_lenetti<PPT, T, CM>>(150 * 1024);
+  if (e != hipSuccess) return e;
   const dim3 grid(lp.S, E);
   if (grad) k_grad_lenetti<PPT, T, CM><<<grid, LENETTI_NT, lds, st>>>(lp);
   else k_fwd_lenetti<PPT, T, CM><<<grid, LENETTI_NT, lds, st>>>(lp);

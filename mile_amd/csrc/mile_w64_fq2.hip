@@ -7,12 +7,8 @@
 template <int NH>
 static hipError_t launch(const GradParams &gp, int E, hipStream_t st) {
   using LY = W64Layout<NH, 2, true>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_grad_w64<NH, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LY::BYTES);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  hipError_t e = mile_set_max_lds<k_grad_w64<NH, 2, true>>(LY::BYTES);
+  if (e != hipSuccess) return e;
   k_grad_w64<NH, 2, true><<<dim3(gp.S, E), 256, LY::BYTES, st>>>(gp, W64NoFuse{0});
   return hipGetLastError();
 }

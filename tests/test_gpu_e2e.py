@@ -901,6 +901,7 @@ def test_bf16_kernel_lppd_within_one_percent_of_fp32(oracle):
     # wide nets evaluate through the strided-batched SGEMM forward (fp32 also when sampling ran on bf16 operands)
     (9, (128, 128, 128, 2), 'relu', 'regr', ('gemm_f32', 'mfma_w128_bf16', 'mfma_wide_bf16x3')),
     (54, (256, 256, 7), 'tanh', 'classification', ('gemm_f32', 'auto')),
+    (5, (16, 16, 2), 'relu', 'regr', ('mfma_narrow_f32',)),       # the narrow kernel's engines evaluate on k_fwd_generic
 ])
 def test_pointwise_loglik_kernel_matches_oracle(oracle, F, hs, act, task, kernels):
     from mile_amd.metrics import lppd

@@ -464,3 +464,87 @@ def test_row_window_on_the_chunked_kernels(oracle):
     be.set_row_window(0, 64)
     with pytest.raises(Exception, match='window'):
         be.logpost_grad(torch.from_numpy(bprob['theta0']))
+
+
+def _shape_engine(kernel, device='cuda:0'):
+    """One small problem per grad kernel: the engine and its ensemble size for the launch-shape check."""
+    from mile_amd import AttentionSpec, LeNetSpec, LeNettiSpec, ModelSpec
+    from mile_amd.engine import Engine
+    rng = np.random.default_rng(0)
+    fcn = {'generic': (5, (16, 16, 2), 'regr', 1052, 12), 'mfma_narrow_f32': (5, (48, 48, 2), 'regr', 1052, 12),
+           'mfma_w64': (5, (64, 64, 64, 2), 'regr', 1052, 16), 'mfma_w64_bf16x3': (12, (64, 64, 2), 'regr', 1052, 16),
+           'mfma_w128_bf16': (9, (128, 128, 2), 'regr', 600, 8), 'gemm_f32': (11, (32, 7), 'classification', 500, 6),
+           'mfma_wide_bf16x3': (54, (256, 256, 7), 'classification', 300, 4),
+           'mfma_wide_bf16': (54, (256, 256, 7), 'classification', 300, 4)}
+    if kernel in fcn:
+        F, hs, task, N, E = fcn[kernel]
+        spec, X = ModelSpec(F, hs, task=task), rng.standard_normal((N, F))
+    elif kernel in ('lenet_f32', 'lenet_bf16'):
+        spec, N, E = LeNetSpec(3, 16, 16, 4), 41, 2
+        X = rng.standard_normal((N, 3 * 16 * 16))
+    elif kernel == 'lenetti_f32':
+        spec, N, E = LeNettiSpec(1, 8, 8, 3), 100, 4
+        X = rng.standard_normal((N, 64))
+    else:
+        spec, N, E = AttentionSpec(50, 16, 16, 2, 16, n_classes=3), 64, 4
+        X = rng.integers(0, 50, (N, 16))
+    K = spec.hidden_structure[-1]
+    y = rng.standard_normal(N) if spec.task == 'regr' else rng.integers(0, K, N)
+    eng = Engine(spec, torch.tensor(X, dtype=torch.float32), torch.tensor(y), device=device, grad_kernel=kernel)
+    return eng, E
+
+
+# what mile_grad_launch_info reports for _shape_engine's problems on an MI355X (256 CUs); bench.py reads the names
+# k_grad_w64 and k_grad_w128b
+LAUNCH_SHAPES = {
+    'generic': ('k_grad_generic', (16, 12), 256, 18240),
+    'mfma_w64': ('k_grad_w64', (8, 16), 256, 139264),
+    'mfma_w128_bf16': ('k_grad_w128b', (2, 8), 256, 108560),
+    'gemm_f32': ('rocblas_sgemm_strided_batched+k_gemm_*', (1, 6), 256, 0),
+    'lenet_f32': ('rocblas_sgemm_strided_batched+k_im2col5/k_col2im5/k_avgpool2', (1, 2), 256, 0),
+    'mfma_w64_bf16x3': ('k_grad_w64', (8, 16), 256, 152848),
+    'mfma_wide_bf16x3': ('k_mm3 (layer-wise MFMA GEMMs)', (1, 4), 256, 65536),
+    'mfma_wide_bf16': ('k_mm3 (layer-wise MFMA GEMMs)', (1, 4), 256, 65536),
+    'lenet_bf16': ('k_conv5m_fwd/dx/dw (implicit-GEMM bf16 MFMA) + k_mm3 (Dense, fp', (1, 2), 256, 57344),
+    'mfma_narrow_f32': ('k_grad_narrow', (16, 12), 256, 101632),
+    'lenetti_f32': ('k_grad_lenetti', (3, 4), 256, 14544),
+    'attn_f32': ('k_grad_attn', (4, 4), 256, 13184),
+}
+
+
+@pytest.mark.parametrize('kernel', sorted(LAUNCH_SHAPES))
+def test_grad_launch_info_per_kernel(kernel):
+    eng, E = _shape_engine(kernel)
+    assert eng.grad_kernel == kernel
+    info = eng.grad_launch_info(E)
+    assert (info['kernel'], info['grid'], info['block'], info['lds_bytes']) == LAUNCH_SHAPES[kernel]
+
+
+@pytest.mark.parametrize('kernel', ['mfma_w128_bf16', 'gemm_f32'])
+def test_row_window_refused_by_unwindowed_kernels(kernel):
+    from mile_amd._lib import MileHipError
+    eng, E = _shape_engine(kernel)
+    theta = torch.zeros(E, eng.d)
+    eng.logpost_grad(theta)                     # no window: runs
+    eng.set_row_window(0, 64)
+    with pytest.raises(MileHipError, match='row window'):
+        eng.logpost_grad(theta)
+    eng.set_row_window(0, 0)
+    eng.logpost_grad(theta)
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason='needs two GPUs')
+def test_two_devices(oracle):
+    """The dynamic-LDS attribute is a per-device setting: kernels that need more than 64 KB of LDS run on a second device
+    too, after they ran on the first (the narrow kernel's LDS-weight form, k_grad_w64)."""
+    for hs, kernel in (((48, 48, 2), 'mfma_narrow_f32'), ((64, 64, 64, 2), 'mfma_w64_bf16x3')):
+        ospec = oracle.ModelSpec(5, hs)
+        prob = oracle.synthetic_problem(ospec, 257, 3, seed=21)
+        lp_ref, g_ref = oracle.logpost_and_grad(ospec, prob['theta0'].astype(np.float64), prob['X'], prob['y'])
+        for dev in ('cuda:0', 'cuda:1'):
+            from mile_amd import ModelSpec
+            from mile_amd.engine import Engine
+            eng = Engine(ModelSpec(5, hs), torch.from_numpy(prob['X']), torch.from_numpy(prob['y']), device=dev)
+            assert eng.grad_kernel == kernel
+            lp, g = eng.logpost_grad(torch.from_numpy(prob['theta0']))
+            assert _relerr(lp.cpu().numpy(), lp_ref) < 2e-5 and _relerr(g.cpu().numpy(), g_ref) < 2e-5, (kernel, dev)

@@ -64,6 +64,100 @@ def test_host_calls_that_need_no_gpu():
     assert lib.mile_create(C.byref(cs), 0, C.byref(h)) == -1
 
 
+def _fcn_cspec(F, widths, act=0, task=0):
+    from mile_amd import _lib
+    cs = _lib.ModelSpecC()
+    cs.in_features, cs.n_layers = F, len(widths)
+    for i, w in enumerate(widths):
+        cs.widths[i] = w
+    cs.activation, cs.task, cs.prior, cs.prior_loc, cs.prior_scale, cs.use_bias = act, task, 0, 0.0, 1.0, 1
+    return cs
+
+
+def _image_cspec(model, c, h, w, k):
+    cs = _fcn_cspec(c * h * w, (k,), task=1)
+    cs.model, cs.img_c, cs.img_h, cs.img_w = model, c, h, w
+    return cs
+
+
+def _attn_cspec():
+    cs = _fcn_cspec(16, (3,), task=1)
+    cs.model, cs.vocab_size, cs.ctx_len, cs.emb_size, cs.n_heads, cs.qkv_dim = 3, 50, 16, 16, 2, 16
+    return cs
+
+
+# spec -> (AUTO, AUTO under MILE_NO_NARROW, the ids mile_set_grad_kernel accepts).  Ids: 1 generic, 2 mfma_w64,
+# 3 mfma_w128_bf16, 4 gemm_f32, 5 lenet_f32, 6 mfma_w64_bf16x3, 7 mfma_wide_bf16x3, 8 mfma_wide_bf16, 9 lenet_bf16,
+# 10 mfma_narrow_f32, 11 lenetti_f32, 12 attn_f32
+KERNEL_CHOICE = {
+    'w64_3': (lambda: _fcn_cspec(5, (64, 64, 64, 2)), 6, 6, {1, 2, 4, 6, 7, 8, 10}),
+    'w64_1': (lambda: _fcn_cspec(5, (64, 2)), 2, 2, {1, 2, 4, 7, 8, 10}),
+    'w64_f17': (lambda: _fcn_cspec(17, (64, 64, 2)), 10, 1, {1, 4, 7, 8, 10}),          # refused by W64: F > 16
+    'w128': (lambda: _fcn_cspec(5, (128, 128, 2)), 7, 7, {1, 3, 4, 7, 8}),
+    'w128_cls': (lambda: _fcn_cspec(5, (128, 128, 3), task=1), 7, 7, {1, 4, 7, 8}),     # refused by W128: not regression
+    'narrow': (lambda: _fcn_cspec(5, (16, 16, 2), act=1), 10, 1, {1, 4, 7, 8, 10}),
+    'narrow_lds': (lambda: _fcn_cspec(5, (48, 48, 2)), 10, 1, {1, 4, 7, 8, 10}),
+    'deep32': (lambda: _fcn_cspec(5, (32,) * 4 + (2,)), 1, 1, {1, 4, 7, 8}),           # refused by NARROW: 4 layers > 16 wide
+    'wide': (lambda: _fcn_cspec(5, (256, 256, 2)), 7, 7, {1, 4, 7, 8}),
+    'generic': (lambda: _fcn_cspec(80, (32, 2)), 1, 1, {1, 4, 7, 8}),
+    'lenet_c1': (lambda: _image_cspec(1, 1, 28, 28, 10), 5, 5, {5, 9}),
+    'lenet_c5': (lambda: _image_cspec(1, 5, 16, 16, 10), 5, 5, {5}),
+    'lenetti': (lambda: _image_cspec(2, 1, 8, 8, 3), 11, 11, {11}),
+    'attn': (lambda: _attn_cspec(), 12, 12, {12}),
+}
+
+
+@pytest.mark.parametrize('name', sorted(KERNEL_CHOICE))
+def test_grad_kernel_choice_matrix(name, monkeypatch):
+    """mile_set_grad_kernel accepts exactly the kernels that run the spec (refusing the rest as invalid), and AUTO picks
+    by the documented priority, with or without MILE_NO_NARROW.  Host only: no GPU."""
+    import ctypes as C
+    from mile_amd import _lib
+    lib = _lib.load_library()
+    make, auto, auto_no_narrow, accepted = KERNEL_CHOICE[name]
+    h = C.c_void_p()
+    assert lib.mile_create(C.byref(make()), 0, C.byref(h)) == 0, lib.mile_last_error()
+    try:
+        assert lib.mile_get_grad_kernel(h) == auto
+        monkeypatch.setenv('MILE_NO_NARROW', '1')
+        assert lib.mile_get_grad_kernel(h) == auto_no_narrow
+        monkeypatch.delenv('MILE_NO_NARROW')
+        for k in range(1, 13):
+            rc = lib.mile_set_grad_kernel(h, k)
+            if k in accepted:
+                assert rc == 0, (k, lib.mile_last_error())
+                assert lib.mile_get_grad_kernel(h) == k
+            else:
+                assert rc == -1 and lib.mile_last_error(), k
+                assert lib.mile_get_grad_kernel(h) == auto     # a refusal leaves the choice as it was
+            assert lib.mile_set_grad_kernel(h, 0) == 0
+        assert lib.mile_set_grad_kernel(h, 13) == -1 and lib.mile_set_grad_kernel(h, -1) == -1
+    finally:
+        assert lib.mile_destroy(h) == 0
+
+
+@pytest.mark.parametrize('model', ['lenet', 'lenetti'])
+def test_image_model_param_offsets_follow_leaves(model):
+    """mile_param_offsets of the image models (layers conv1, then the Dense layers) against spec.leaves()."""
+    import ctypes as C
+    from mile_amd import _lib
+    from mile_amd.spec import LeNetSpec, LeNettiSpec
+    lib = _lib.load_library()
+    spec = LeNetSpec(3, 32, 32, 10) if model == 'lenet' else LeNettiSpec(2, 9, 7, 5)
+    layers = ['conv1', 'conv2', 'fc1', 'fc2', 'fc3'] if model == 'lenet' else ['conv1', 'fc1', 'fc2', 'fc3', 'fc4']
+    h = C.c_void_p()
+    cs = _image_cspec(1 if model == 'lenet' else 2, spec.channels, spec.height, spec.width, spec.out_dim)
+    assert lib.mile_create(C.byref(cs), 0, C.byref(h)) == 0, lib.mile_last_error()
+    assert lib.mile_param_count(h) == spec.n_params
+    L = {n: o for n, o, _ in spec.leaves()}
+    for li, nm in enumerate(layers):
+        b, k = C.c_int64(), C.c_int64()
+        assert lib.mile_param_offsets(h, li, C.byref(b), C.byref(k)) == 0
+        assert (b.value, k.value) == (L[f'core.{nm}.bias'], L[f'core.{nm}.kernel']), nm
+    assert lib.mile_param_offsets(h, len(layers), C.byref(b), C.byref(k)) == -1
+    assert lib.mile_destroy(h) == 0
+
+
 def test_product_path_fails_loudly_without_gpu_or_library(tmp_path):
     from mile_amd import ModelSpec, _lib
     with pytest.raises(_lib.MileHipError):
