@@ -22,8 +22,12 @@ struct GradParams {
   int32_t N, Npad, Fp, S, R;
   int32_t Npb;
   int32_t dp;           // slab row stride: d rounded up to a multiple of 4 floats (128-bit stores)
-  long long *dbg_buf;   // dev: 8 per-phase cycle counters (k_grad_w128b, MILE_DEBUG=16)
-  int32_t dbg;          // debug knobs (MILE_DEBUG env): bit0 skip row blocks, bit1 skip staging, bit2 skip reduction
+  // Lab harnesses only (tools/r03/lab); the library sets dbg_buf = nullptr and dbg = 0.  dbg_buf: phase counters of the
+  // -DMILE_LAB_* timing builds.  dbg: k_grad_w64 ablations, bit0 skip row blocks, bit1 skip staging, bit2 skip reduction
+  // (wrong results by design).  The three wave-uniform tests stay in the kernel: without them the allocator spills 224 bytes
+  // in k_grad_w64<3, 1, true>, 2.4 % slower on B2.
+  long long *dbg_buf;
+  int32_t dbg;
 };
 
 // Per-row log-likelihood and d/d(out).  NaN rows contribute nothing (jnp.nansum).

@@ -298,10 +298,6 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
   float *wv = lds + LY::WAVE0 + wave * LY::WAVE_SZ;
   float *img = wv + LY::IMG, *xt = wv + LY::XT, *dout_l = wv + LY::DOUT;
 
-  // dev (MILE_DEBUG=32): 100 MHz timestamps per workgroup: start, main loop done, slab stored, ticket drawn, epilogue done
-  const bool stamp = (p.dbg & 32) && p.dbg_buf && tid == 0;
-  long long *stamps = p.dbg_buf + ((size_t)e * p.S + s) * 16;
-  if (stamp) stamps[0] = wall_clock64();
   // ---- stage this particle's weights in LDS --------------------------------------
   char *BIMG = reinterpret_cast<char *>(WIMG);   // SPLIT: term t of image set s at BIMG + (3 s + t) * W64_TIMG
   if (!(p.dbg & 2))
@@ -475,7 +471,6 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
 #endif
   // ---- reduce the four waves' accumulators through LDS, write the slab -------------
   __syncthreads();  // weights and images are dead from here on; LDS is reused
-  if (stamp) stamps[1] = wall_clock64();
   float *RED = lds;
   if (p.dbg & 4) return;
   // one round for all hidden->hidden matrices: RED[l][wave][in][68]
@@ -559,7 +554,6 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
   }
 
   // ---- fused integrator epilogue: the particle's last-arriving workgroup runs the update -------------------
-  if (stamp) { stamps[2] = wall_clock64(); stamps[3] = 0; stamps[4] = 0; }
   if constexpr (FUSABLE) {
     if (fuse) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // EVERY storing wave drains its sc1 stores ...
@@ -572,7 +566,6 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
         *lflag = last;
       }
       __syncthreads();
-      if (stamp) stamps[3] = wall_clock64();
       if (*lflag) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // no instruction: keeps the compiler from hoisting loads
         // quads per thread at 256 threads for the largest d this (NH, FQ) can have
@@ -581,11 +574,9 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
         // through a generic pointer, each field was re-read with a flat load after every store: 24 us instead of 7.)
         float(*ured)[UPD_NSUM + 1] = reinterpret_cast<float(*)[UPD_NSUM + 1]>(lds + 16);
         float *ubc = lds + 16 + 4 * (UPD_NSUM + 1);
-        long long *ust = stamp ? stamps + 5 : nullptr;
-        if (fz.kind == UPD_KIND_MID) upd_fast_body<NKF, 2, false, true, UPD_KIND_MID>(fz.upd, e, tid, 256, ured, ubc, ust);
-        else if (fz.kind == UPD_KIND_REC) upd_fast_body<NKF, 2, false, true, UPD_KIND_REC>(fz.upd, e, tid, 256, ured, ubc, ust);
-        else upd_fast_body<NKF, 2, false, true>(fz.upd, e, tid, 256, ured, ubc, ust);
-        if (stamp) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamps[4] = wall_clock64(); }
+        if (fz.kind == UPD_KIND_MID) upd_fast_body<NKF, 2, false, true, UPD_KIND_MID>(fz.upd, e, tid, 256, ured, ubc);
+        else if (fz.kind == UPD_KIND_REC) upd_fast_body<NKF, 2, false, true, UPD_KIND_REC>(fz.upd, e, tid, 256, ured, ubc);
+        else upd_fast_body<NKF, 2, false, true>(fz.upd, e, tid, 256, ured, ubc);
       }
     }
   }

@@ -68,7 +68,6 @@ struct mile_sampler {
   std::vector<ParamLayer> layers;       // mile_param_offsets, in ABI order (bias -1: none)
   // layer-wise GEMM path (MILE_GRAD_GEMM_F32): rocBLAS handle and activation workspace
   void *blas = nullptr;
-  long long *dbg_buf = nullptr;         // dev instrumentation (MILE_DEBUG=16)
   float *tune_info = nullptr;           // [E_cap, 3] scratch MCLMCInfo of mile_tune's large-d path
   float *gemm_ws = nullptr, *gemm_ones = nullptr;
   int gemm_ones_n = 0;
@@ -468,8 +467,6 @@ static void free_ws(mile_sampler *s) {
   if (s->nzbuf) (void)hipFree(s->nzbuf);
   s->nzbuf = nullptr;
   s->nz_E = 0;
-  if (s->dbg_buf) (void)hipFree(s->dbg_buf);   // sized from the slab-row capacity
-  s->dbg_buf = nullptr;
   s->slabs = s->llpart = s->dK = s->lold = nullptr;
   s->E_cap = 0; s->ES_cap = 0;
 }
@@ -497,7 +494,6 @@ int32_t mile_destroy(mile_sampler *s) {
   if (s->wide_ws) (void)hipFree(s->wide_ws);
   if (s->wide_wt) (void)hipFree(s->wide_wt);
   if (s->wide_hb) (void)hipFree(s->wide_hb);
-  if (s->dbg_buf) (void)hipFree(s->dbg_buf);
   if (s->tune_info) (void)hipFree(s->tune_info);
   free_nuts(s);
   if (s->nuts_count_h) (void)hipHostFree(s->nuts_count_h);
@@ -767,7 +763,7 @@ static hipError_t launch_w64(const GradParams &gp, const W64Fuse &fz, int E, hip
 // Can the update that follows this gradient run as the grad launch's epilogue (k_grad_w64 SPLIT, W64Fuse)?
 // 8-byte aligned rows everywhere (the epilogue is the AL = 2 form), no preconditioner, d within its register cache.
 static bool fuse_ok(const mile_sampler *s, int kernel, const UpdParams &u) {
-  if (!MILE_W64_EPILOGUE_ON || !grad_kernel(kernel).fuses || getenv("MILE_NO_FUSE")) return false;
+  if (!MILE_W64_EPILOGUE_ON || !grad_kernel(kernel).fuses) return false;
   if (u.sdc || (u.d & 1) || u.u_rec) return false;   // (the merged warm-up launch exists as a stand-alone kernel only)
   const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
   if (fq != 1) return false;                       // the F > 8 kernels are built without the epilogue (mile_grad_w64.h)
@@ -811,16 +807,6 @@ static hipError_t launch_w128b(const GradParams &gp, int E, hipStream_t st) {
   using LY = W128Layout<NH, 2>;
   hipError_t e = mile_set_max_lds<k_grad_w128b<NH, 2>>(LY::BYTES);
   if (e != hipSuccess) return e;
-  if (gp.dbg & 16) {   // dev: per-phase cycle counts from workgroup 0 (MILE_DEBUG=16)
-    e = mile_set_max_lds<k_grad_w128b<NH, 2, true>>(LY::BYTES);
-    if (e != hipSuccess) return e;
-    k_grad_w128b<NH, 2, true><<<dim3(gp.S, E), 256, LY::BYTES, st>>>(gp);
-    long long hb[8];
-    if (gp.dbg_buf && hipMemcpy(hb, gp.dbg_buf, 64, hipMemcpyDeviceToHost) == hipSuccess)
-      fprintf(stderr, "w128b cycles per tile pair (%lld pairs): F1 %lld F2 %lld F3 %lld headbwd %lld L(1) %lld L(2) %lld first %lld\n", hb[7],
-              hb[0], hb[1], hb[2], hb[3], hb[4], hb[5], hb[6]);
-    return hipGetLastError();
-  }
   k_grad_w128b<NH, 2><<<dim3(gp.S, E), 256, LY::BYTES, st>>>(gp);
   return hipGetLastError();
 }
@@ -852,7 +838,7 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
   const size_t n_a1 = 6 * HW, n_p1 = 6 * P1, n_col2 = 150 * HW2, n_a2 = 16 * HW2, n_p2 = g.flat;
   // direct convolution kernels (LDS tiles per image) unless the image is too large for them or the im2col + SGEMM
   // form is asked for (MILE_LENET_GEMM=1: kept as the second implementation / fallback)
-  const int ipw = getenv("MILE_LENET_IPW") ? std::max(1, atoi(getenv("MILE_LENET_IPW"))) : (mfma ? 16 : 8);   // images per workgroup (measured: 53.0 / 54.7 ms at 16 / 8 on the MFMA forms)
+  const int ipw = mfma ? 16 : 8;   // images per workgroup (measured: 53.0 / 54.7 ms at 16 / 8 on the MFMA forms)
   const size_t lds_f1 = (size_t)(25 * g.C * 8 + 8 + g.C * (g.H + 4) * (g.W + 4)) * 4;
   const int KT1 = 25 * g.C;
   // k_conv5_dw: pixel groups are reduced 3 at a time through LDS (buffer aliases the tiles)
@@ -865,18 +851,18 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
   const bool direct = getenv("MILE_LENET_GEMM") == nullptr && g.C <= 16 && lds_max <= 150 * 1024;
   // MILE_GRAD_LENET_BF16: the five convolution launches on the bf16 matrix pipe (mile_lenet_mfma.h), everything else as below
   // small images: several per barrier pair (as many as keep the tiles under ~56 KB, at most 4)
-  const size_t per_img2 = (size_t)(g.hp1 * g.wp1 + 8) * 16 + (size_t)g.h2 * g.w2 * 32;   // input tile + dZ rows of one image
-  const int ni2 = getenv("MILE_CM_NI") ? std::max(1, std::min(8, atoi(getenv("MILE_CM_NI")))) : std::max(1, std::min(4, (int)(57344 / per_img2)));
-  const size_t ldm_f1 = cm_lds_fwd(CM_IN4, g.H, g.W, 2, g.C, 6), ldm_f2 = cm_lds_fwd(CM_IN8, g.hp1, g.wp1, 0, 6, 16, ni2), ldm_x2 = cm_lds_dx(g.h2, g.w2, 6, 16);
-  const size_t ldm_w1 = cm_lds_dw(CM_IN4, g.H, g.W, 2), ldm_w2 = cm_lds_dw(CM_IN8, g.hp1, g.wp1, 0, ni2);
-  // the 6-channel sides of the two convolutions in the PAIR forms (two pixels per MFMA row / column); MILE_CM_NO_PAIR: the pixel forms
-  const bool pair = mfma && getenv("MILE_CM_NO_PAIR") == nullptr;
-  // ReLU: the full-size conv activations are kept for the backward pass only as two-byte "was it positive" values
-  const int a16 = mfma && act == MILE_ACT_RELU && getenv("MILE_CM_A32") == nullptr;
-  const auto ni_for = [](size_t per_img) { return getenv("MILE_CM_NI") ? std::max(1, std::min(8, atoi(getenv("MILE_CM_NI")))) : std::max(1, std::min(4, (int)(57344 / per_img))); };
+  const auto ni_for = [](size_t per_img) { return std::max(1, std::min(4, (int)(57344 / per_img))); };
+  const int ni2 = ni_for((size_t)(g.hp1 * g.wp1 + 8) * 16 + (size_t)g.h2 * g.w2 * 32);   // input tile + dZ rows of one image
   const int ni_x2 = ni_for((size_t)((g.h2 + 8) * (g.w2 + 8) + 8) * 32), ni_f1 = ni_for((size_t)((g.H + 4) * (g.W + 4) + 8) * 8);
-  const size_t ldm_x2p = cm_lds_dx2x(g.h2, g.w2, 6, 16, ni_x2), ldm_w1p = cm_lds_dw2x(g.H, g.W, 2), ldm_f1p = cm_lds_fwd(CM_IN4, g.H, g.W, 2, g.C, 6, ni_f1);
-  if (mfma && (!direct || g.C > 4 || std::max({ldm_f1, ldm_f2, ldm_x2, ldm_w1, ldm_w2, ldm_x2p, ldm_w1p, ldm_f1p}) > 150 * 1024))
+  // the 6-channel sides of the two convolutions in the PAIR forms (two pixels per MFMA row / column)
+  const size_t ldm_f1p = cm_lds_fwd(CM_IN4, g.H, g.W, 2, g.C, 6, ni_f1), ldm_f2 = cm_lds_fwd(CM_IN8, g.hp1, g.wp1, 0, 6, 16, ni2);
+  const size_t ldm_x2p = cm_lds_dx2x(g.h2, g.w2, 6, 16, ni_x2), ldm_w1p = cm_lds_dw2x(g.H, g.W, 2), ldm_w2 = cm_lds_dw(CM_IN8, g.hp1, g.wp1, 0, ni2);
+  // ldm_w1 (conv1's kernel gradient in the pixel form, no longer built) exceeds ldm_w1p: kept in the check so that the same
+  // images are refused as when the pixel forms could be selected.  Their other two sizes never exceed ldm_f1p and ldm_x2p.
+  const size_t ldm_w1 = cm_lds_dw(CM_IN4, g.H, g.W, 2);
+  // ReLU: the full-size conv activations are kept for the backward pass only as two-byte "was it positive" values
+  const int a16 = mfma && act == MILE_ACT_RELU;
+  if (mfma && (!direct || g.C > 4 || std::max({ldm_f1p, ldm_f2, ldm_x2p, ldm_w1, ldm_w1p, ldm_w2}) > 150 * 1024))
     return fail(MILE_ERR_INVALID, "LENET_BF16 needs <= 4 image channels and an image that fits the LDS tiles");
   // Dense activations: exact widths on the rocBLAS path; k_mm3 wants rows of 8 k floats (zero padding columns)
   const size_t w_f2 = mfma ? 88 : 84, w_out = mfma ? (size_t)(g.K + 7) / 8 * 8 : (size_t)g.K;
@@ -919,16 +905,12 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
     HIP_TRY((mile_set_max_lds<k_conv5_dw<6, 0>>(150 * 1024)));
     HIP_TRY((mile_set_max_lds<k_conv5_dw<16, 0>>(150 * 1024)));
     HIP_TRY((mile_set_max_lds<k_conv5_dx<6, 16, 1, 0, 0>>(150 * 1024)));
-    HIP_TRY((mile_set_max_lds<k_conv5m_fwd<CM_IN4, 6>>(150 * 1024)));
     HIP_TRY((mile_set_max_lds<k_conv5m_fwd<CM_IN8, 16>>(150 * 1024)));
-    HIP_TRY((mile_set_max_lds<k_conv5m_dw<CM_IN4, 6>>(150 * 1024)));
     HIP_TRY((mile_set_max_lds<k_conv5m_dw<CM_IN8, 16>>(150 * 1024)));
-    HIP_TRY((mile_set_max_lds<k_conv5m_dx<6, 16>>(150 * 1024)));
     HIP_TRY((mile_set_max_lds<k_conv5m_fwd2x<6>>(150 * 1024)));
     HIP_TRY((mile_set_max_lds<k_conv5m_dx2x<6, 16>>(150 * 1024)));
     HIP_TRY((mile_set_max_lds<k_conv5m_dw2x<6>>(150 * 1024)));
   }
-  const int cm_dbg = getenv("MILE_CM_SKIP") ? atoi(getenv("MILE_CM_SKIP")) : 0;   // dev: timing knobs of k_conv5m_fwd
   const float one = 1.0f, zero = 0.0f;
   auto blocks = [](long long n) { return (unsigned)std::min<long long>((n + 255) / 256, 65535); };
   // row-major C[rows x fout] = A[rows x fin] W[fin x fout] per batch entry; W from theta (+ offset), batch stride d
@@ -955,11 +937,10 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
 #define LAUNCH_FWD1(GEO_) k_conv5_fwd<6, GEO_><<<dim3(nwg, E), 256, lds_f1, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, theta, g.k_c1, g.b_c1, d, a1, (int)Rc, ipw, act)
 #define LAUNCH_FWD2(GEO_) k_conv5_fwd<16, GEO_><<<dim3(nwg, E), 256, lds_f2, st>>>(p1, Rc * (long long)n_p1, (long long)n_p1, g.wp1 * 6, 6, 1, 6, g.hp1, g.wp1, 0, theta, g.k_c2, g.b_c2, d, a2, (int)Rc, ipw, act)
       // MFMA form: the pooled activations come out of the convolution's own epilogue; evaluation skips the full-size ones
-      if (pair) k_conv5m_fwd2x<6><<<dim3(nwg, E), 256, ldm_f1p, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, theta, g.k_c1, g.b_c1, d, grad ? a1 : nullptr, p1, (int)Rc, ipw, act, a16, ni_f1);
-      else if (mfma) k_conv5m_fwd<CM_IN4, 6><<<dim3(nwg, E), 256, ldm_f1, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, theta, g.k_c1, g.b_c1, d, grad ? a1 : nullptr, p1, (int)Rc, ipw, act, cm_dbg, a16);
+      if (mfma) k_conv5m_fwd2x<6><<<dim3(nwg, E), 256, ldm_f1p, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, theta, g.k_c1, g.b_c1, d, grad ? a1 : nullptr, p1, (int)Rc, ipw, act, a16, ni_f1);
       else if (geo == 1) LAUNCH_FWD1(1); else if (geo == 3) LAUNCH_FWD1(3); else LAUNCH_FWD1(0);
       if (!mfma) k_avgpool2<<<blocks(B * (long long)n_p1), 256, 0, st>>>(a1, p1, B, g.H, g.W, 6);
-      if (mfma) k_conv5m_fwd<CM_IN8, 16><<<dim3(nwg, E), 256, ldm_f2, st>>>(p1, Rc * (long long)n_p1, (long long)n_p1, g.wp1 * 6, 6, 1, 6, g.hp1, g.wp1, 0, theta, g.k_c2, g.b_c2, d, grad ? a2 : nullptr, p2, (int)Rc, ipw, act, cm_dbg, a16, ni2);
+      if (mfma) k_conv5m_fwd<CM_IN8, 16><<<dim3(nwg, E), 256, ldm_f2, st>>>(p1, Rc * (long long)n_p1, (long long)n_p1, g.wp1 * 6, 6, 1, 6, g.hp1, g.wp1, 0, theta, g.k_c2, g.b_c2, d, grad ? a2 : nullptr, p2, (int)Rc, ipw, act, a16, ni2);
       else if (geo == 1) LAUNCH_FWD2(2); else if (geo == 3) LAUNCH_FWD2(4); else LAUNCH_FWD2(0);
 #undef LAUNCH_FWD1
 #undef LAUNCH_FWD2
@@ -1028,11 +1009,9 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
       if (mfma) k_conv5m_dw<CM_IN8, 16><<<dim3(nwg, E), 256, ldm_w2, st>>>(p1, Rc * (long long)n_p1, (long long)n_p1, g.wp1 * 6, 6, 1, 6, g.hp1, g.wp1, 0, dp2, a2, act, part2, (int)Rc, ipw, a16, ni2);
       else if (geo == 1) LAUNCH_DW2(2); else if (geo == 3) LAUNCH_DW2(4); else LAUNCH_DW2(0);
       k_conv_reduce<<<dim3(10, E), 256, 0, st>>>(part2, (int)nwg, 2400, 16, slab, dp, g.k_c2, g.b_c2, acc);
-      if (pair) k_conv5m_dx2x<6, 16><<<dim3(nwg, E), 256, ldm_x2p, st>>>(dp2, a2, act, theta, g.k_c2, d, dp1, (int)Rc, g.h2, g.w2, ipw, a16, ni_x2);
-      else if (mfma) k_conv5m_dx<6, 16><<<dim3(nwg, E), 256, ldm_x2, st>>>(dp2, a2, act, theta, g.k_c2, d, dp1, (int)Rc, g.h2, g.w2, ipw, a16);
+      if (mfma) k_conv5m_dx2x<6, 16><<<dim3(nwg, E), 256, ldm_x2p, st>>>(dp2, a2, act, theta, g.k_c2, d, dp1, (int)Rc, g.h2, g.w2, ipw, a16, ni_x2);
       else if (geo == 1) LAUNCH_DX(12, 12); else if (geo == 3) LAUNCH_DX(10, 10); else LAUNCH_DX(0, 0);
-      if (pair) k_conv5m_dw2x<6><<<dim3(nwg, E), 256, ldm_w1p, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, dp1, a1, act, part1, (int)Rc, ipw, a16);
-      else if (mfma) k_conv5m_dw<CM_IN4, 6><<<dim3(nwg, E), 256, ldm_w1, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, dp1, a1, act, part1, (int)Rc, ipw, a16);
+      if (mfma) k_conv5m_dw2x<6><<<dim3(nwg, E), 256, ldm_w1p, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, dp1, a1, act, part1, (int)Rc, ipw, a16);
       else if (geo == 1) LAUNCH_DW1(1); else if (geo == 3) LAUNCH_DW1(3); else LAUNCH_DW1(0);
 #undef LAUNCH_DW2
 #undef LAUNCH_DX
@@ -1158,10 +1137,8 @@ template <int ALAY, int BSRC, int EPI, int TERMS, int ACT, bool ACCUM, bool COLS
 static hipError_t launch_mm3_k(const MMParams &p, int batch, hipStream_t st) {
   constexpr int KC = MILE_MM_KC;
   using LY = MMLayout<ALAY, BSRC, TERMS, KC>;
-  static const bool dbg = getenv("MILE_DEBUG") && (atoi(getenv("MILE_DEBUG")) & 64);
-  if constexpr (!FULL) {   // whole tiles everywhere: the predicate-free instantiation (timing stamps need the general one)
-    static const bool no_full = getenv("MILE_MM_NO_FULL") != nullptr;
-    if (!dbg && !no_full && p.M % 128 == 0 && p.N % 128 == 0)
+  if constexpr (!FULL) {   // whole tiles everywhere: the predicate-free instantiation
+    if (p.M % 128 == 0 && p.N % 128 == 0)
       return launch_mm3_k<ALAY, BSRC, EPI, TERMS, ACT, ACCUM, COLSUM, true>(p, batch, st);
   }
   hipError_t e = mile_set_max_lds<k_mm3<ALAY, BSRC, EPI, TERMS, KC, ACT, ACCUM, COLSUM, FULL>>(LY::BYTES);
@@ -1170,27 +1147,10 @@ static hipError_t launch_mm3_k(const MMParams &p, int batch, hipStream_t st) {
   const int mtiles = (p.M + 127) / 128;
   const dim3 grid((p.N + 127) / 128, mtiles, batch);
   q.c_vec = (p.ldc % 4 == 0) && (p.sC % 4 == 0) && (((uintptr_t)p.C & 15) == 0);
-  static const bool no_remap = getenv("MILE_MM_NO_XCD") != nullptr;
   q.xcd_remap = 0;
-  if (!no_remap) {
-    if (COLSUM && batch % 8 == 0) q.xcd_remap = 2;                     // dW: the few tiles of a particle share both operands
-    else if (!COLSUM && grid.x > 1 && grid.y >= 8) q.xcd_remap = 1;
-  }
-  static unsigned long long *dbuf = nullptr;
-  if (dbg) {   // dev: mean time per phase of wave 0 (100 MHz ticks -> us), per launch
-    if (!dbuf && hipMalloc(&dbuf, 64) != hipSuccess) return hipErrorOutOfMemory;
-    (void)hipMemsetAsync(dbuf, 0, 64, st);
-    q.dbg = dbuf;
-  }
+  if (COLSUM && batch % 8 == 0) q.xcd_remap = 2;                     // dW: the few tiles of a particle share both operands
+  else if (!COLSUM && grid.x > 1 && grid.y >= 8) q.xcd_remap = 1;
   k_mm3<ALAY, BSRC, EPI, TERMS, KC, ACT, ACCUM, COLSUM, FULL><<<grid, 256, LY::BYTES, st>>>(q);
-  if (dbg) {
-    unsigned long long h[8];
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpy(h, dbuf, 64, hipMemcpyDeviceToHost);
-    const double nc = (double)std::max<unsigned long long>(h[5], 1), nt = (double)std::max<unsigned long long>(h[6], 1);
-    fprintf(stderr, "k_mm3<A%d,B%d,E%d> M=%d N=%d K=%d grid %ux%ux%u: per chunk us: wait loads+barrier %.2f  split+store %.2f  barrier %.2f  loads issue+frags+MFMA %.2f | per tile: epilogue %.2f  (chunks/tile %.1f)\n",
-            ALAY, BSRC, EPI, p.M, p.N, p.K, grid.x, grid.y, grid.z, h[0] / nc * 0.01, h[1] / nc * 0.01, h[2] / nc * 0.01, h[3] / nc * 0.01, h[4] / nt * 0.01, nc / nt);
-  }
   return hipGetLastError();
 }
 // the three products of the layer-wise path, dispatched on the launch constants the kernel takes as template parameters
@@ -1373,8 +1333,7 @@ static int launch_grad_wide(mile_sampler *s, const GradParams &gp, int E, hipStr
   // The last layer (K <= 8 outputs on a hidden width <= 256) as one pass over the last hidden activations -- forward, head, dH and
   // dW of that layer in k_wide_headblock -- instead of four launches on 128-wide MFMA tiles (fp32-faithful form only: the
   // bf16-operand recipe rounds this product's operands)
-  const bool headblock = TERMS == 3 && L >= 2 && ds.widths[L - 2] <= 256 && ds.widths[L - 1] <= WH_KMAX &&
-                         getenv("MILE_WIDE_NO_HEADBLOCK") == nullptr;
+  const bool headblock = TERMS == 3 && L >= 2 && ds.widths[L - 2] <= 256 && ds.widths[L - 1] <= WH_KMAX;
   constexpr int HB_ROWS = 512;                      // rows per workgroup of k_wide_headblock
   if (headblock) {
     const size_t need = (size_t)E * ((R + HB_ROWS - 1) / HB_ROWS) * ((size_t)ds.widths[L - 2] * ds.widths[L - 1] + ds.widths[L - 1] + 1);
@@ -1472,29 +1431,6 @@ static hipError_t launch_attn(mile_sampler *s, const float *theta, int E, const 
 
 // ---- the gradient of each grad kernel: the `grad` of its row in kGrad.  gp holds the row window and S; fz the update that runs
 // as the launch's epilogue (fuses) ----------------------------------------------------------------------------------------------
-// dev: phase timestamps of the w64 kernels (MILE_DEBUG=32; 100 MHz wall clock -> us)
-static int w64_report_phases(mile_sampler *s, const GradParams &gp, int E, hipStream_t st) {
-  if (!(gp.dbg & 32)) return MILE_OK;
-  const int S = gp.S;
-  std::vector<long long> hb((size_t)E * S * 16);
-  HIP_TRY(hipStreamSynchronize(st));
-  HIP_TRY(hipMemcpy(hb.data(), s->dbg_buf, hb.size() * 8, hipMemcpyDeviceToHost));
-  long long t00 = hb[0], tend = 0;
-  for (int w = 0; w < E * S; ++w) { t00 = std::min(t00, hb[w * 16]); tend = std::max({tend, hb[w * 16 + 2], hb[w * 16 + 4]}); }
-  double a[4] = {0, 0, 0, 0}, mx[4] = {0, 0, 0, 0}, ep[4] = {0, 0, 0, 0}, sub[4] = {0, 0, 0, 0}; int nl = 0;
-  for (int w = 0; w < E * S; ++w) {
-    const long long *q = &hb[w * 16];
-    const double v0 = (q[1] - q[0]) * 0.01, v1 = (q[2] - q[1]) * 0.01;
-    a[0] += v0; a[1] += v1; mx[0] = std::max(mx[0], v0); mx[1] = std::max(mx[1], v1);
-    if (q[4]) { const double v2 = (q[3] - q[2]) * 0.01, v3 = (q[4] - q[3]) * 0.01; a[2] += v2; a[3] += v3; mx[2] = std::max(mx[2], v2); mx[3] = std::max(mx[3], v3); ++nl;
-      ep[0] += (q[5] - q[3]) * 0.01; ep[1] += (q[6] - q[5]) * 0.01; ep[2] += (q[7] - q[6]) * 0.01; ep[3] += (q[4] - q[7]) * 0.01;
-      sub[0] += (q[8] - q[5]) * 0.01; sub[1] += (q[9] - q[8]) * 0.01; sub[2] += (q[10] - q[9]) * 0.01; sub[3] += (q[6] - q[10]) * 0.01; }
-  }
-  fprintf(stderr, "w64 phases (us, mean/max over %d WGs): main %.1f/%.1f reduce+store %.1f/%.1f | last arrivers (%d): drain+ticket %.1f/%.1f epilogue %.1f/%.1f | first start -> last end %.1f\n",
-          E * S, a[0] / (E * S), mx[0], a[1] / (E * S), mx[1], nl, nl ? a[2] / nl : 0.0, mx[2], nl ? a[3] / nl : 0.0, mx[3], (tend - t00) * 0.01);
-  if (nl) fprintf(stderr, "    epilogue: loads %.1f  noise+sums+reduce %.1f  chain %.1f  pass2+stores %.1f   [sums: quads %.1f tail %.1f wave_sum %.1f lds+barrier %.1f]\n", ep[0] / nl, ep[1] / nl, ep[2] / nl, ep[3] / nl, sub[0] / nl, sub[1] / nl, sub[2] / nl, sub[3] / nl);
-  return MILE_OK;
-}
 static int grad_w64(mile_sampler *s, const GradParams &gp, const W64Fuse &fz, int E, hipStream_t st) {
   const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
   hipError_t e = hipErrorInvalidValue;
@@ -1505,7 +1441,7 @@ static int grad_w64(mile_sampler *s, const GradParams &gp, const W64Fuse &fz, in
   else if (nh == 2 && fq == 2) e = launch_w64<2, 2>(gp, fz, E, st);
   else if (nh == 3 && fq == 2) e = launch_w64<3, 2>(gp, fz, E, st);
   HIP_TRY(e);
-  return w64_report_phases(s, gp, E, st);
+  return MILE_OK;
 }
 static int grad_w64x3(mile_sampler *s, const GradParams &gp, const W64Fuse &fz, int E, hipStream_t st) {
   const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
@@ -1514,7 +1450,7 @@ static int grad_w64x3(mile_sampler *s, const GradParams &gp, const W64Fuse &fz, 
   else if (nh == 3 && fq == 1) e = launch_w64<3, 1, true>(gp, fz, E, st);
   else if (fq == 2 && !fz.enabled) e = mile_launch_w64_split_fq2(nh, gp, E, st);   // mile_w64_fq2.hip
   HIP_TRY(e);
-  return w64_report_phases(s, gp, E, st);
+  return MILE_OK;
 }
 static int grad_narrow(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
   HIP_TRY(launch_narrow(s, gp, E, st));
@@ -1574,11 +1510,7 @@ static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t s
     gp.N = s->win_count;
     gp.Npad = (s->win_count + 31) / 32 * 32;
   }
-  { const char *dv = getenv("MILE_DEBUG"); gp.dbg = dv ? atoi(dv) : 0; }
-  gp.dbg_buf = nullptr;
-  if ((gp.dbg & 16) && !s->dbg_buf) HIP_TRY(hipMalloc(&s->dbg_buf, 64));
-  if ((gp.dbg & 32) && !s->dbg_buf) HIP_TRY(hipMalloc(&s->dbg_buf, s->ES_cap * 128));
-  gp.dbg_buf = s->dbg_buf;
+  gp.dbg_buf = nullptr; gp.dbg = 0;   // lab-harness fields
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (s->timing) {
     if (s->ev_used + 2 > s->ev.size()) {

@@ -87,7 +87,7 @@ __device__ __forceinline__ int cm_div(int p, float inv) { return (int)(((float)p
 
 // Slot geometry.  PB = bytes per pixel of the tile; off(s, rowpix) = byte offset of slot s from the pixel base (rowpix =
 // pixels per tile row); tap(s) / c0(s) = kernel tap and first channel the slot stands for; NS slots in all.
-enum { CM_IN4 = 0, CM_IN8 = 1, CM_DZ16 = 2, CM_DZ16P = 3 };
+enum { CM_IN4 = 0, CM_IN8 = 1, CM_DZ16P = 2 };
 template <int MODE> struct CSlot;
 template <> struct CSlot<CM_IN4> {   // <= 4 input channels: slot = (kh, kw) with kw padded to 6 (kw = 5 is a zero tap)
   static constexpr int NS = 30, PB = 8;
@@ -103,14 +103,6 @@ template <> struct CSlot<CM_IN8> {   // <= 8 input channels: slot = (tap, half)
   __device__ static int tap(int s) { return s >> 1; }
   __device__ static int c0(int s) { return 4 * (s & 1); }
 };
-template <> struct CSlot<CM_DZ16> {  // the dZ tile of the input-gradient pass, <= 16 channels: slot = (tap, quarter), taps look BACK
-  static constexpr int NS = 100, PB = 32;
-  __device__ static int off(int s, int rowpix) { return -(((s >> 2) / 5) * rowpix + (s >> 2) % 5) * 32 + 8 * (s & 3); }
-  __device__ static bool valid(int s) { return s < NS; }
-  __device__ static int tap(int s) { return s >> 2; }
-  __device__ static int c0(int s) { return 4 * (s & 3); }
-};
-
 template <> struct CSlot<CM_DZ16P> { // dZ tile, pair form: slot = (kh, kw' = -1..4, quarter)
   static constexpr int NS = 120, PB = 32;
   __device__ static int off(int s, int rowpix) { return -((s / 24) * rowpix + ((s % 24) >> 2) - 1) * 32 + 8 * (s & 3); }
@@ -164,16 +156,16 @@ __device__ __forceinline__ void cm_stage_input(char *tile, const float *src, lon
 }
 
 // The particle's kernel as the A operand of the F form: ka[c] = rows m (lane & 15), k-blocks 4c + (lane >> 4) = slots 2 blk, 2 blk + 1.
-// DX = false: rows are output channels, K[(tap * CIN + ci) * COUT + m];  DX = true: rows are input channels, K[(tap * CIN + m) * COUT + co].
+// CK_FWD: rows are output channels, K[(tap * CIN + ci) * COUT + m].
 // K is read through an LDS copy (Ksh, 25 * CIN * COUT floats, aliasing the image tile): the gather below is 8 NMF scalar reads per
 // lane, which as global loads cost the workgroup more than the images it then processes.  Ends with a barrier-free state: the
 // caller's image loop starts with __syncthreads() before it overwrites the tile.
-// KIND: CK_FWD rows = output channels; CK_DX rows = input channels; CK_FWD2 / CK_DX2 the PAIR forms: row m = 2 * channel + dxo
+// CK_FWD2 / CK_DX2, the PAIR forms: row m = 2 * channel + dxo
 // stands for the output pixel x + dxo of a pixel PAIR (x even), i.e. the kernel shifted by dxo inside a 6-wide kw window:
 //   out[x + dxo][co]  = sum_{kw'} in[x + kw'] K[kw' - dxo][co]            (kw' = 0..5, the padded slots of CM_IN4)
 //   din[x + dxo][ci]  = sum_{kw'} dz[x - kw'] K[kw' + dxo][ci]            (kw' = -1..4, CM_DZ16P)
 // -- twice the useful MFMA rows (12 of 16 instead of 6) and half the tiles for the 6-channel sides of the two convolutions.
-enum { CK_FWD = 0, CK_DX = 1, CK_FWD2 = 2, CK_DX2 = 3 };
+enum { CK_FWD = 0, CK_FWD2 = 1, CK_DX2 = 2 };
 template <int MODE, int NMF, int KIND>
 __device__ __forceinline__ void cm_kernel_operand(const float *Kg, float *K, int CIN, int COUT, int tid, bf16x8 (&ka)[NMF]) {
   using G = CSlot<MODE>;
@@ -189,8 +181,7 @@ __device__ __forceinline__ void cm_kernel_operand(const float *Kg, float *K, int
       const int s = 2 * (4 * c + g) + (j >> 2), ch = G::c0(s) + (j & 3);
       bool ok;
       int idx;
-      if constexpr (KIND == CK_DX) { ok = G::valid(s) && m < CIN && ch < COUT; idx = (G::tap(s) * CIN + m) * COUT + ch; }
-      else if constexpr (KIND == CK_FWD) { ok = G::valid(s) && ch < CIN && m < COUT; idx = (G::tap(s) * CIN + ch) * COUT + m; }
+      if constexpr (KIND == CK_FWD) { ok = G::valid(s) && ch < CIN && m < COUT; idx = (G::tap(s) * CIN + ch) * COUT + m; }
       else if constexpr (KIND == CK_FWD2) {   // CM_IN4 slots: s = 6 kh + kw'
         const int kh = s / 6, kw = s % 6 - (m & 1), co = m >> 1;
         ok = s < G::NS && kw >= 0 && kw < 5 && ch < CIN && co < COUT;
@@ -279,10 +270,9 @@ __device__ __forceinline__ void cm_image_f(const char *tile, int ntiles, int wav
 template <int MODE, int COUT>
 __global__ __launch_bounds__(256) void k_conv5m_fwd(const float *in, long long sE, long long sB, long long sH, long long sW, long long sC,
                                                     int CIN, int H, int W, int pad, const float *theta, int k_off, int b_off, int d, float *out,
-                                                    float *pool, int R, int ipw, int activation, int dbg = 0, int a16 = 0, int ni = 1) {
+                                                    float *pool, int R, int ipw, int activation, int a16 = 0, int ni = 1) {
   // ni images are staged per barrier pair (small images: conv2's 144 output pixels are 12 tiles -- three tiles per wave in two pair
   // rounds; four images at once fill the rounds and quarter the barriers).
-  // dbg (MILE_CM_SKIP, timing experiments only -- results are wrong): 1 no full-size store, 2 no pooled store, 4 no MFMA loop, 8 no staging
   using G = CSlot<MODE>;
   constexpr int NMF = ((G::NS + 1) / 2 + 3) / 4;
   extern __shared__ __attribute__((aligned(16))) char cm_lds[];
@@ -310,13 +300,11 @@ __global__ __launch_bounds__(256) void k_conv5m_fwd(const float *in, long long s
   for (int b = b0; b < b1; b += ni) {
     const int nimg = min(ni, b1 - b);
     __syncthreads();
-    if (!(dbg & 8) || b == b0)
-      for (int im = 0; im < nimg; ++im)
-        cm_stage_input<MODE>(cm_lds + im * tile_bytes, in + (size_t)e * sE + (size_t)(b + im) * sB, sH, sW, sC, CIN, H, W, pad, tid);
+    for (int im = 0; im < nimg; ++im)
+      cm_stage_input<MODE>(cm_lds + im * tile_bytes, in + (size_t)e * sE + (size_t)(b + im) * sB, sH, sW, sC, CIN, H, W, pad, tid);
     __syncthreads();
-    float *dst = out && !(dbg & 1) ? (a16 ? (float *)((uint16_t *)out + ((size_t)e * R + b) * npix * COUT) : out + ((size_t)e * R + b) * npix * COUT) : nullptr;
+    float *dst = out ? (a16 ? (float *)((uint16_t *)out + ((size_t)e * R + b) * npix * COUT) : out + ((size_t)e * R + b) * npix * COUT) : nullptr;
     float *pdst = pool + ((size_t)e * R + b) * Hq * Wq * COUT;
-    if (dbg & 4) continue;
     cm_image_f<NMF>(cm_lds, nimg * ntiles, wave, so, ka,
       [&](const int tt) {
         const int im = cm_div(tt, inv_nt), t = tt - im * ntiles;
@@ -357,7 +345,7 @@ __global__ __launch_bounds__(256) void k_conv5m_fwd(const float *in, long long s
           const float h2 = v[i] + __shfl_xor(v[i], 1);
           s4[i] = 0.25f * (h2 + __shfl_xor(h2, 8));
         }
-        if (!(dbg & 2) && dy == 0 && (dx & 1) == 0 && y < 2 * Hq && x < 2 * Wq && 4 * g < COUT) {
+        if (dy == 0 && (dx & 1) == 0 && y < 2 * Hq && x < 2 * Wq && 4 * g < COUT) {
           float *o = pdst_i + (size_t)((y >> 1) * Wq + (x >> 1)) * COUT + 4 * g;
           if constexpr (COUT % 4 == 0) {
             *reinterpret_cast<cm_f32x4 *>(o) = cm_f32x4{s4[0], s4[1], s4[2], s4[3]};
@@ -497,54 +485,6 @@ __device__ __forceinline__ void cm_stage_dz(char *zt, const float *dp_img, const
       *reinterpret_cast<cm_u32x4 *>(zt + (size_t)px * 32) = cm_u32x4{pk[0], pk[1], pk[2], pk[3]};
       *reinterpret_cast<cm_u32x4 *>(zt + (size_t)px * 32 + 16) = cm_u32x4{pk[4], pk[5], pk[6], pk[7]};
     }
-  }
-}
-
-// VALID 5x5 conv, gradient w.r.t. the input (as k_conv5_dx): din[e][b][yi][xi][ci] = sum_{kh,kw,co} dz[yi-kh][xi-kw][co] K[kh][kw][ci][co]
-template <int CIN, int COUT>
-__global__ __launch_bounds__(256) void k_conv5m_dx(const float *dp, const float *a, int activation, const float *theta, int k_off, int d,
-                                                   float *din, int R, int Ho, int Wo, int ipw, int a16 = 0) {
-  using G = CSlot<CM_DZ16>;
-  constexpr int NMF = ((G::NS + 1) / 2 + 3) / 4;
-  static_assert(COUT <= 16 && CIN <= 16, "one slot quartet / one MFMA row block");
-  extern __shared__ __attribute__((aligned(16))) char cm_lds[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, e = blockIdx.y;
-  const int n16 = lane & 15, g = lane >> 4;
-  const int H = Ho + 4, W = Wo + 4, Ht = Ho + 8, Wt = Wo + 8, npix = H * W;
-  bf16x8 ka[NMF];
-  cm_kernel_operand<CM_DZ16, NMF, CK_DX>(theta + (size_t)e * d + k_off, reinterpret_cast<float *>(cm_lds), CIN, COUT, tid, ka);
-  int so[NMF][2];
-#pragma unroll
-  for (int c = 0; c < NMF; ++c)
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int s = 2 * (4 * c + g) + u;
-      so[c][u] = s < G::NS ? G::off(s, Wt) : 0;
-    }
-  const float inv_w = 1.0f / (float)W;
-  const int b0 = blockIdx.x * ipw, b1 = min(R, b0 + ipw);
-  for (int b = b0; b < b1; ++b) {
-    const size_t img = (size_t)e * R + b;
-    __syncthreads();
-    if (a16) cm_stage_dz<COUT, true>(cm_lds, dp + img * (Ho / 2) * (Wo / 2) * COUT, (const uint16_t *)a + img * Ho * Wo * COUT, Ho, Wo, 4, Ht * Wt, activation, tid);
-    else cm_stage_dz<COUT>(cm_lds, dp + img * (Ho / 2) * (Wo / 2) * COUT, a + img * Ho * Wo * COUT, Ho, Wo, 4, Ht * Wt, activation, tid);
-    __syncthreads();
-    float *dst = din + img * npix * CIN;
-    cm_image_f<NMF>(cm_lds, (npix + 15) / 16, wave, so, ka,
-      [&](const int t) {
-        const int pc = min(t * 16 + n16, npix - 1);
-        const int yi = cm_div(pc, inv_w), xi = pc - yi * W;
-        return ((yi + 4) * Wt + xi + 4) * 32;
-      },
-      [&](const int mt, const cm_f32x4 acc) {
-        const int p = mt * 16 + n16;
-        if (p < npix) {
-          float *o = dst + (size_t)p * CIN + 4 * g;
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            if (4 * g + i < CIN) o[i] = acc[i];
-        }
-      });
   }
 }
 
@@ -905,7 +845,6 @@ static inline size_t cm_lds_fwd(int mode, int H, int W, int pad, int CIN, int CO
   const int pb = mode == CM_IN4 ? 8 : 16;
   return std::max((size_t)ni * ((H + 2 * pad) * (W + 2 * pad) + 8) * pb, (size_t)25 * CIN * COUT * 4);
 }
-static inline size_t cm_lds_dx(int Ho, int Wo, int CIN, int COUT) { return std::max((size_t)(Ho + 8) * (Wo + 8) * 32, (size_t)25 * CIN * COUT * 4); }
 static inline size_t cm_lds_dx2x(int Ho, int Wo, int CIN, int COUT, int ni = 1) {
   return std::max((size_t)ni * ((Ho + 8) * (Wo + 8) + 8) * 32, (size_t)25 * CIN * COUT * 4);
 }

@@ -48,7 +48,6 @@ struct MMParams {
   float *colsum; long long sColsum;          // COLSUM: column sums of B over K -> colsum[bz * sColsum + n] (any alignment)
   int c_vec;                                 // C (and the accumulate reads of it) may use 16-byte accesses: ldc % 4 == 0, base aligned
   int xcd_remap;                             // 0 none; 1 N tiles of a row tile share an XCD; 2 all tiles of a batch entry do
-  unsigned long long *dbg;                   // dev (MILE_DEBUG=64): per-phase 100 MHz tick sums of wave 0 of every workgroup
 };
 
 typedef uint32_t mm_u32x2 __attribute__((ext_vector_type(2)));
@@ -134,7 +133,7 @@ struct MMLayout {
 // (as a per-element run-time switch the epilogue was most of the kernel's instructions; dispatched inside the kernel its
 // eight inlined copies spilled 150 registers).
 // FULL: M and N are multiples of 128 (the 256-wide layers of B4 at every chunk size the host picks; any K -- a ragged last chunk
-// costs two wave-uniform tests): no tile / row / column predicates and no timing stamps -- the MFMA groups of the K loop are one
+// costs two wave-uniform tests): no tile / row / column predicates -- the MFMA groups of the K loop are one
 // basic block the scheduler can order freely (the general form carries ~3 SALU instructions per MFMA and a branch around every
 // MFMA group).
 template <int ALAY, int BSRC, int EPI, int TERMS, int KC, int ACT, bool ACCUM, bool COLSUM = false, bool FULL = false>
@@ -498,16 +497,10 @@ __global__ __launch_bounds__(256, MILE_MM_OCC) void k_mm3(const MMParams p) {
   for (int j = 0; j < PF; ++j) {
     const int kc = g0 + j;
     if (kc >= nk) break;
-    long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0;
-    const bool stampw = !FULL && p.dbg != nullptr && tid == 0;
-    if (stampw) ts0 = wall_clock64();
     __syncthreads();          // every wave has read the previous chunk's images
-    if (stampw) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); ts1 = wall_clock64(); }
     store_a(j);
     store_b(j);
-    if (stampw) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); ts2 = wall_clock64(); }
     __syncthreads();
-    if (stampw) ts3 = wall_clock64();
     if (kc + PF < nk) {       // refill this stage
       load_a(j, KC * (kc + PF));
       load_b(j, KC * (kc + PF));
@@ -544,19 +537,12 @@ __global__ __launch_bounds__(256, MILE_MM_OCC) void k_mm3(const MMParams p) {
       if (ks < ksteps) kstep(ks);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (stampw) {
-      ts4 = wall_clock64();
-      atomicAdd(p.dbg + 0, (unsigned long long)(ts1 - ts0)); atomicAdd(p.dbg + 1, (unsigned long long)(ts2 - ts1));
-      atomicAdd(p.dbg + 2, (unsigned long long)(ts3 - ts2)); atomicAdd(p.dbg + 3, (unsigned long long)(ts4 - ts3));
-      atomicAdd(p.dbg + 5, 1ull);
-    }
     if (kc == nk - 1) {       // the C tile is complete
 #ifdef MILE_LAB_MM_NO_EPI   // dev experiment (tools/r03/lab/mm3_lab.hip): wrong results; what the C tile's epilogue costs
       if (acc[0][0][0] == 123.456f) epilogue(m0);
 #else
       epilogue(m0);
 #endif
-      if (stampw) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); atomicAdd(p.dbg + 4, (unsigned long long)(wall_clock64() - ts4)); atomicAdd(p.dbg + 6, 1ull); }
     }
   }
   if constexpr (COLSUM) {

@@ -559,8 +559,7 @@ __device__ __forceinline__ float ld1_shared(const float *q) {
 // rejected, or the accepted state needed nan_to_num -- and the caller has to run them from the stored state (upd_tune_restart).
 template <int NK, int AL, bool SDC, bool COH, int CF = -1, bool BIG = false>
 __device__ __forceinline__ bool upd_fast_body(const UpdParams &p, const int e, const int tid, const int nt,
-                                              float (*red)[UPD_NSUM + 1], float *bc, long long *stamps = nullptr,
-                                              f32x4 *gl = nullptr) {
+                                              float (*red)[UPD_NSUM + 1], float *bc, f32x4 *gl = nullptr) {
   const int d = p.d;
   const int flags = CF >= 0 ? CF : p.flags;
   const size_t base = (size_t)e * d;
@@ -634,7 +633,6 @@ __device__ __forceinline__ bool upd_fast_body(const UpdParams &p, const int e, c
     if (explA) ta = p.zA[tc];
     if (explB) tb = p.zB[tc];
   }
-  if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamps[0] = wall_clock64(); }   // dev: loads landed
   // ---- pass 1: noise + sums ------------------------------------------------------------
   float sm[UPD_NSUM];
 #pragma unroll
@@ -689,7 +687,6 @@ __device__ __forceinline__ bool upd_fast_body(const UpdParams &p, const int e, c
       __builtin_amdgcn_sched_barrier(0);   // one quad at a time: interleaved iterations spill (128 registers per thread)
     }
   }
-  if (stamps) stamps[3] = wall_clock64();
   if (ntail) {
     f32x4 za = {0, 0, 0, 0}, zb = {0, 0, 0, 0};
     if (useA && !p.zA) za = philox_normal4(nqf, pid, p.stepA, p.stageA, p.seed);
@@ -713,15 +710,12 @@ __device__ __forceinline__ bool upd_fast_body(const UpdParams &p, const int e, c
     sm[6] = fmaf(ui, tb, sm[6]); sm[7] = fmaf(gs, tb, sm[7]); sm[8] = fmaf(tb, tb, sm[8]);
     sm[9] = fmaf(ta, tb, sm[9]);
   }
-  if (stamps) stamps[4] = wall_clock64();
 #pragma unroll
   for (int k = 0; k < UPD_NSUM; ++k) sm[k] = wave_sum(sm[k]);
-  if (stamps) stamps[5] = wall_clock64();
   if ((tid & 63) == 0)
 #pragma unroll
     for (int k = 0; k < UPD_NSUM; ++k) red[tid >> 6][k] = sm[k];
   __syncthreads();
-  if (stamps) stamps[1] = wall_clock64();                                                          // dev: sums reduced
 
   // ---- scalar chain: wave 0 only, coefficients broadcast through LDS ------------------------
   if (tid < 64) {
@@ -814,7 +808,6 @@ __device__ __forceinline__ bool upd_fast_body(const UpdParams &p, const int e, c
   }
   }
   __syncthreads();
-  if (stamps) stamps[2] = wall_clock64();                                                          // dev: chain done
   // ---- pass 2 (from registers) ------------------------------------------------------------
   const bool any_op = flags & (UPD_B1 | UPD_OA | UPD_OB | UPD_B2);
   const bool doA = flags & UPD_A;
@@ -985,12 +978,12 @@ static __global__ __launch_bounds__(UPD_NT) void k_update_big(const UpdParams p)
   __shared__ float red[UPD_NW][UPD_NSUM + 1];
   __shared__ float bc[16];
   extern __shared__ __attribute__((aligned(16))) char upd_gl[];
-  upd_fast_body<NK, AL, SDC, false, CF, true>(p, blockIdx.x, threadIdx.x, blockDim.x, red, bc, nullptr, reinterpret_cast<f32x4 *>(upd_gl));
+  upd_fast_body<NK, AL, SDC, false, CF, true>(p, blockIdx.x, threadIdx.x, blockDim.x, red, bc, reinterpret_cast<f32x4 *>(upd_gl));
 }
 
 // which compile-time kind a launch is (else -1): steady-state flag words with a Normal prior, no tuner, no preconditioner
 static inline int upd_kind(const UpdParams &u) {
-  if (u.prior != MILE_PRIOR_NORMAL || u.sdc || getenv("MILE_NO_UPD_KIND")) return -1;
+  if (u.prior != MILE_PRIOR_NORMAL || u.sdc) return -1;
   if (u.flags == UPD_KIND_MID) return UPD_KIND_MID;
   if (u.flags == UPD_KIND_REC) return UPD_KIND_REC;
   if (u.flags == UPD_KIND_TUNE && u.u_rec) return UPD_KIND_TUNE;
