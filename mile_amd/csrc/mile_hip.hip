@@ -638,6 +638,26 @@ static int ptr_align(const void *q) {   // alignment in floats (4, 2 or 1) of a 
   return (a & 15) == 0 ? 4 : ((a & 7) == 0 ? 2 : 1);
 }
 
+// Every row base of an update launch is (pointer + e*d): the vector width (4, 2 or 1 floats) allowed by d and by the row
+// pointers the update kernels access in vectors.  (bk_* are read element by element; x_acc, when set, equals x_in.)
+static int row_align(const UpdParams &u) {
+  int al = (u.d % 4 == 0) ? 4 : ((u.d % 2 == 0) ? 2 : 1);
+  const void *ptrs[] = {u.x, u.u, u.g, u.slabs, u.sdc, u.zA, u.zB, u.out_sample, u.x_in, u.u_in, u.g_in, u.t_avg, u.u_rec, u.nz_A, u.nz_B};
+  for (const void *q : ptrs)
+    if (q) al = std::min(al, ptr_align(q));
+  return al;
+}
+
+// f(AL, SDC) with the launch's vector width and preconditioner as compile-time constants
+template <class F>
+static auto with_al_sdc(int al, bool sdc, F &&f) {
+  using A4 = std::integral_constant<int, 4>;
+  using A2 = std::integral_constant<int, 2>;
+  using A1 = std::integral_constant<int, 1>;
+  if (sdc) return al == 4 ? f(A4{}, std::true_type{}) : (al == 2 ? f(A2{}, std::true_type{}) : f(A1{}, std::true_type{}));
+  return al == 4 ? f(A4{}, std::false_type{}) : (al == 2 ? f(A2{}, std::false_type{}) : f(A1{}, std::false_type{}));
+}
+
 template <int AL, bool SDC>
 static void launch_update_al(const UpdParams &u, int E, int nk, hipStream_t st) {
   // fewest waves that still leave <= nk quads per thread: padded lanes are wasted VALU time in a kernel that only fills
@@ -696,12 +716,7 @@ static bool launch_update_big(const UpdParams &u, int E, hipStream_t st) {
   const int nqf = u.d >> 2;
   const int nk = (nqf + UPD_NT - 1) / UPD_NT;
   if (nk <= UPD_QMAX || nk > UPD_QMAX_BIG || (u.flags & UPD_TUNE) || u.zA || u.zB || getenv("MILE_NO_UPD_BIG")) return false;
-  int al = (u.d % 4 == 0) ? 4 : ((u.d % 2 == 0) ? 2 : 1);
-  const void *ptrs[] = {u.x, u.u, u.g, u.slabs, u.sdc, u.zA, u.zB, u.out_sample, u.x_in, u.u_in, u.g_in};
-  for (const void *q : ptrs)
-    if (q) al = std::min(al, ptr_align(q));
-  if (u.sdc) return al == 4 ? launch_update_big_al<4, true>(u, E, nk, st) : (al == 2 ? launch_update_big_al<2, true>(u, E, nk, st) : launch_update_big_al<1, true>(u, E, nk, st));
-  return al == 4 ? launch_update_big_al<4, false>(u, E, nk, st) : (al == 2 ? launch_update_big_al<2, false>(u, E, nk, st) : launch_update_big_al<1, false>(u, E, nk, st));
+  return with_al_sdc(row_align(u), u.sdc, [&](auto al, auto sdc) { return launch_update_big_al<al, sdc>(u, E, nk, st); });
 }
 
 // Whether launch_update runs `u` as the k_update_fast mid-step kind, the one launch that can prefill the next launch's noise
@@ -725,21 +740,8 @@ static void launch_update(const UpdParams &u, int E, hipStream_t st) {
     k_update<false><<<E, UPD_NT, 0, st>>>(u);
     return;
   }
-  // every row base is (pointer + e*d): vector width allowed by d and by the pointers
-  int al = (u.d % 4 == 0) ? 4 : ((u.d % 2 == 0) ? 2 : 1);
-  const void *ptrs[] = {u.x, u.u, u.g, u.slabs, u.sdc, u.zA, u.zB, u.out_sample, u.x_in, u.u_in, u.g_in, u.t_avg, u.u_rec, u.nz_A, u.nz_B};
-  for (const void *q : ptrs)
-    if (q) al = std::min(al, ptr_align(q));
   const int nk = (nqf + UPD_NT - 1) / UPD_NT;
-  if (u.sdc) {
-    if (al == 4) launch_update_al<4, true>(u, E, nk, st);
-    else if (al == 2) launch_update_al<2, true>(u, E, nk, st);
-    else launch_update_al<1, true>(u, E, nk, st);
-  } else {
-    if (al == 4) launch_update_al<4, false>(u, E, nk, st);
-    else if (al == 2) launch_update_al<2, false>(u, E, nk, st);
-    else launch_update_al<1, false>(u, E, nk, st);
-  }
+  with_al_sdc(row_align(u), u.sdc, [&](auto al, auto sdc) { launch_update_al<al, sdc>(u, E, nk, st); });
 }
 
 // The F > 8 split kernels live in their own translation unit, built WITHOUT -amdgpu-mfma-vgpr-form: with that option
@@ -764,15 +766,11 @@ static hipError_t launch_w64(const GradParams &gp, const W64Fuse &fz, int E, hip
 // 8-byte aligned rows everywhere (the epilogue is the AL = 2 form), no preconditioner, d within its register cache.
 static bool fuse_ok(const mile_sampler *s, int kernel, const UpdParams &u) {
   if (!MILE_W64_EPILOGUE_ON || !grad_kernel(kernel).fuses) return false;
-  if (u.sdc || (u.d & 1) || u.u_rec) return false;   // (the merged warm-up launch exists as a stand-alone kernel only)
+  if (u.sdc || u.u_rec) return false;   // (the merged warm-up launch exists as a stand-alone kernel only)
   const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
   if (fq != 1) return false;                       // the F > 8 kernels are built without the epilogue (mile_grad_w64.h)
   const int nk = nh == 2 ? w64_fuse_nk<2, 1>() : w64_fuse_nk<3, 1>();
-  if ((u.d >> 2) > 256 * nk) return false;
-  const void *ptrs[] = {u.x, u.u, u.g, u.zA, u.zB, u.out_sample, u.x_in, u.u_in, u.g_in, u.t_avg, u.bk_x, u.bk_u, u.bk_g};
-  for (const void *q : ptrs)
-    if (q && ptr_align(q) < 2) return false;
-  return true;
+  return (u.d >> 2) <= 256 * nk && row_align(u) >= 2;
 }
 
 template <int NH, int TH, int TF>
@@ -1543,6 +1541,114 @@ static int grad_then_update(mile_sampler *s, const float *theta, int E, const Up
   return MILE_OK;
 }
 
+// ---- MCLMC (mile_step, mile_tune) ------------------------------------------------------------------------------------
+// A step is three update launches around two gradients:
+//   start   O(z1) . B(b1) . A(1/2) from the cached gradient: the first step of a call, later chained onto a record launch
+//   mid     B(1 - 2 b1) . A(1/2)
+//   record  B(b1) . O(z2) . record [. the next step's start]
+// The steady-state words must be the kinds k_update_fast specialises (upd_kind); any other word runs the run-time-flag form.
+static constexpr int32_t UPD_STEP_START = UPD_B2 | UPD_A;                                   // + UPD_OB under O-step-O
+static constexpr int32_t UPD_STEP_RECORD = UPD_FROM_SLABS | UPD_B1 | UPD_OA | UPD_RECORD;
+static_assert((UPD_STEP_RECORD | UPD_STEP_START | UPD_OB | UPD_NO_G) == UPD_KIND_REC, "sampling steady state");
+static_assert((UPD_STEP_RECORD | UPD_TUNE | UPD_STEP_START | UPD_OB) == UPD_KIND_TUNE, "warm-up steady state");
+static const float MC_B1 = (float)MCLACHLAN_B1, MC_B2 = (float)(1.0 - 2.0 * MCLACHLAN_B1);
+
+struct Mclmc {             // one mile_step / mile_tune call
+  UpdParams up;            // what every update launch shares: sizes, prior, state, workspace, step size, L, preconditioner, RNG
+  int kernel;
+  bool oso;                // MILE_REFRESH_O_STEP_O
+  const float *noise;      // [n_steps, 2, E, d] or NULL: Philox
+  int64_t step_offset;
+  float *out_info;         // [n_steps, E, 3] or NULL
+  const float *noise_at(int i, int k) const { return noise ? noise + ((size_t)i * 2 + k) * ((size_t)up.E * up.d) : nullptr; }
+};
+
+// O(z1) . B(b1) . A(1/2) of step i, added to u (a start launch, or a record launch that chains the next step on)
+static void chain_start(UpdParams &u, const Mclmc &m, int i) {
+  u.flags |= UPD_STEP_START | (m.oso ? UPD_OB : 0);
+  u.zB = m.noise_at(i, 0); u.stepB = (uint32_t)(m.step_offset + i); u.stageB = 0; u.hB = 0.5f;
+  u.coef_b2 = MC_B1; u.coef_a = 0.5f;
+}
+static UpdParams upd_start(const Mclmc &m, int i) {
+  UpdParams u = m.up;
+  u.flags = UPD_START;
+  chain_start(u, m, i);
+  return u;
+}
+static UpdParams upd_mid(const Mclmc &m) {
+  UpdParams u = m.up;
+  u.flags = UPD_KIND_MID;
+  u.coef_b1 = MC_B2; u.coef_a = 0.5f;
+  return u;
+}
+static UpdParams upd_record(const Mclmc &m, int i) {
+  UpdParams u = m.up;
+  u.flags = UPD_STEP_RECORD;
+  u.coef_b1 = MC_B1;
+  u.zA = m.noise_at(i, 1); u.stepA = (uint32_t)(m.step_offset + i); u.stageA = 1; u.hA = m.oso ? 0.5f : 1.0f;
+  if (m.out_info) u.out_info = m.out_info + (size_t)i * m.up.E * 3;
+  return u;
+}
+
+// The warm-up tuner's inputs at schedule step sp (UpdParams under UPD_TUNE, TunePostParams)
+template <class P>
+static void set_tuner(P &p, const mile_tune_args *a, int sp) {
+  p.t_eps = a->step_size; p.t_eps_max = a->step_size_max; p.t_time = a->time; p.t_xavg = a->x_average;
+  p.t_W = a->stream_weight; p.t_avg = a->stream_average;
+  p.t_mask = sp < a->n_mask_steps ? 1.0f : 0.0f;
+  const double tot = (double)a->schedule_total, vs = a->desired_energy_var_start, ve = a->desired_energy_var_end;
+  if (vs > 2.0) {
+    const double tau = tot / 4.0, ex = std::exp(-(double)sp / tau);
+    p.t_var = (float)(vs * ex + ve * (1.0 - ex));
+  } else {
+    p.t_var = (float)(vs - (vs - ve) * std::min((double)sp / tot, 1.0));
+  }
+  p.t_trust = a->trust_in_estimate; p.t_decay = a->decay_rate;
+}
+
+static const char *args_refusal(const mile_sampler *, const mile_step_args *a) {
+  if (!a->step_size || !a->L) return "mile_step: step_size and L are required";
+  if (a->n_steps < 0) return "mile_step: n_steps < 0";
+  return nullptr;
+}
+static const char *args_refusal(const mile_sampler *s, const mile_tune_args *a) {
+  if (!a->step_size || !a->L || !a->step_size_max || !a->time || !a->x_average || !a->stream_weight || !a->stream_average)
+    return "mile_tune: null tuner array";
+  if (a->n_steps < 0 || a->schedule_total < 1) return "mile_tune: bad step counts";
+  if ((s->ds.d >> 2) < 1) return "mile_tune: d < 4";
+  return nullptr;
+}
+
+// The checks of mile_step / mile_tune (`fn`), then the call's Mclmc.  n_steps == 0 passes before the device is touched.
+template <class Args>
+static int mclmc_begin(mile_sampler *s, mile_state *state, const Args *a, const std::string &fn, Mclmc &m) {
+  if (!s || !state || !a) return fail(MILE_ERR_INVALID, fn + ": null argument");
+  if (!state->position || !state->momentum || !state->logdensity || !state->logdensity_grad)
+    return fail(MILE_ERR_INVALID, fn + ": null state field");
+  if (const char *r = args_refusal(s, a)) return fail(MILE_ERR_INVALID, r);
+  if (a->refresh != MILE_REFRESH_O_STEP_O && a->refresh != MILE_REFRESH_STEP_O)
+    return fail(MILE_ERR_INVALID, fn + ": unknown refresh mode");
+  const int E = state->n_particles, d = s->ds.d;
+  if (E < 1) return fail(MILE_ERR_INVALID, fn + ": n_particles must be >= 1");
+  if (a->n_steps == 0) return MILE_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  if (!s->X) return fail(MILE_ERR_STATE, "no data: call mile_set_data first");
+  m.kernel = resolved_kernel(s);
+  const int S = choose_S(s, E, m.kernel);
+  if (E > s->E_cap || (size_t)E * S > s->ES_cap) return fail(MILE_ERR_STATE, "workspace too small: call mile_reserve(E) first");
+  m.oso = a->refresh == MILE_REFRESH_O_STEP_O;
+  m.noise = a->noise; m.step_offset = a->step_offset; m.out_info = a->out_info;
+  UpdParams &up = m.up;
+  up.d = d; up.E = E; up.S = S; up.dp = (d + 3) / 4 * 4;
+  up.prior = s->ds.prior; up.prior_loc = s->ds.prior_loc; up.prior_scale = s->ds.prior_scale;
+  up.x = state->position; up.u = state->momentum; up.g = state->logdensity_grad; up.logp = state->logdensity;
+  up.slabs = s->slabs; up.llpart = s->llpart;
+  up.eps = a->step_size; up.L = a->L; up.sdc = a->sqrt_diag_cov;
+  up.seed = a->seed; up.pids = a->particle_ids;
+  up.dK = s->dK; up.lold = s->lold; up.upart = s->upart;
+  return MILE_OK;
+}
+
 template <int NH, int FQ>
 static hipError_t launch_fwd_w64(const PredParams &pp, int S, hipStream_t st) {
   using LY = W64Layout<NH, FQ>;
@@ -1915,45 +2021,21 @@ int32_t mile_init(mile_sampler *s, mile_state *state, const float *noise, uint64
 }
 
 int32_t mile_step(mile_sampler *s, mile_state *state, const mile_step_args *a, void *stream) {
-  if (!s || !state || !a) return fail(MILE_ERR_INVALID, "mile_step: null argument");
-  if (!state->position || !state->momentum || !state->logdensity || !state->logdensity_grad)
-    return fail(MILE_ERR_INVALID, "mile_step: null state field");
-  if (!a->step_size || !a->L) return fail(MILE_ERR_INVALID, "mile_step: step_size and L are required");
-  if (a->n_steps < 0) return fail(MILE_ERR_INVALID, "mile_step: n_steps < 0");
-  if (a->refresh != MILE_REFRESH_O_STEP_O && a->refresh != MILE_REFRESH_STEP_O)
-    return fail(MILE_ERR_INVALID, "mile_step: unknown refresh mode");
-  const int E = state->n_particles, d = s->ds.d;
-  if (E < 1) return fail(MILE_ERR_INVALID, "mile_step: n_particles must be >= 1");
-  if (a->n_steps == 0) return MILE_OK;
+  const char *dv = getenv("MILE_DEBUG");
+  const bool no_prefill = dv && (atoi(dv) & 128);   // test hook: every launch draws its own noise, as before the prefill
+  Mclmc m{};
+  if (const int rc = mclmc_begin(s, state, a, "mile_step", m); rc || a->n_steps == 0) return rc;
+  const int E = m.up.E, d = m.up.d;
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipSetDevice(s->device));
-  const int kernel = resolved_kernel(s);
-  const int S = choose_S(s, E, kernel);
-  if (!s->X) return fail(MILE_ERR_STATE, "no data: call mile_set_data first");
-  if (E > s->E_cap || (size_t)E * S > s->ES_cap) return fail(MILE_ERR_STATE, "workspace too small: call mile_reserve(E) first");
-
-  UpdParams up{};
-  up.d = d; up.E = E; up.S = S; up.dp = (d + 3) / 4 * 4;
-  up.prior = s->ds.prior; up.prior_loc = s->ds.prior_loc; up.prior_scale = s->ds.prior_scale;
-  up.x = state->position; up.u = state->momentum; up.g = state->logdensity_grad; up.logp = state->logdensity;
-  up.slabs = s->slabs; up.llpart = s->llpart;
-  up.eps = a->step_size; up.L = a->L; up.sdc = a->sqrt_diag_cov;
-  up.seed = a->seed; up.pids = a->particle_ids;
-  up.dK = s->dK; up.lold = s->lold; up.upart = s->upart;
-  const float b1 = (float)MCLACHLAN_B1, b2 = (float)(1.0 - 2.0 * MCLACHLAN_B1);
-  const bool oso = a->refresh == MILE_REFRESH_O_STEP_O;
-  const size_t Ed = (size_t)E * d;
-  auto noise_at = [&](int i, int k) -> const float * { return a->noise ? a->noise + ((size_t)i * 2 + k) * Ed : nullptr; };
 
   // two launches per step when the updates can run as the grad kernel's epilogue (k_grad_w64 SPLIT), else four
-  UpdParams probe = up;
+  UpdParams probe = m.up;
   probe.zA = a->noise; probe.zB = a->noise; probe.out_sample = a->out_samples;
-  const bool fused = fuse_ok(s, kernel, probe);
+  const bool fused = fuse_ok(s, m.kernel, probe);
   if (fused) HIP_TRY(hipMemsetAsync(s->arrive, 0, ((size_t)E * 4 + 15) / 16 * 16, st));   // tickets re-zeroed every call
-  // noise prefill of the record launches (MILE_DEBUG bit 128 turns it off: every launch draws its own noise, as before).
-  // Only Philox calls with the register-cached update can prefill; they allocate the workspace the first time.
-  const char *dv = getenv("MILE_DEBUG");
-  const bool prefill = !fused && !a->noise && upd_fast_d(d) && !(dv && (atoi(dv) & 128));
+  // noise prefill of the record launches: only Philox calls with the register-cached update can prefill; they allocate the
+  // workspace the first time
+  const bool prefill = !fused && !a->noise && upd_fast_d(d) && !no_prefill;
   if (prefill && s->nz_E < E) {
     if (s->nzbuf) HIP_TRY(hipFree(s->nzbuf));
     s->nzbuf = nullptr;
@@ -1963,217 +2045,113 @@ int32_t mile_step(mile_sampler *s, mile_state *state, const mile_step_args *a, v
   }
   int kept = 0;
   for (int i = 0; i < a->n_steps; ++i) {
+    if (i == 0) launch_update(upd_start(m, i), E, st);
+    UpdParams ur = upd_record(m, i);
+    if (i + 1 < a->n_steps) {
+      chain_start(ur, m, i + 1);
+      ur.flags |= UPD_NO_G;
+    }
     const int64_t gstep = a->step_offset + i;
-    if (i == 0) {  // O(z1) . B(b1) . A(1/2) from the cached gradient
-      UpdParams u = up;
-      u.flags = UPD_START | UPD_B2 | UPD_A | (oso ? UPD_OB : 0);
-      u.zB = noise_at(i, 0); u.stepB = (uint32_t)gstep; u.stageB = 0; u.hB = 0.5f;
-      u.coef_b2 = b1; u.coef_a = 0.5f;
-      launch_update(u, E, st);
-    }
-    // grad . B(b1) . O(z2) . record  [ . O(z1') . B(b1) . A(1/2) of the next step ]
-    UpdParams ur = up;
-    {
-      const bool last = (i == a->n_steps - 1);
-      ur.flags = UPD_FROM_SLABS | UPD_B1 | UPD_OA | UPD_RECORD;
-      ur.coef_b1 = b1;
-      ur.zA = noise_at(i, 1); ur.stepA = (uint32_t)gstep; ur.stageA = 1; ur.hA = oso ? 0.5f : 1.0f;
-      if (!last) {
-        ur.flags |= UPD_B2 | UPD_A | (oso ? UPD_OB : 0) | UPD_NO_G;
-        ur.zB = noise_at(i + 1, 0); ur.stepB = (uint32_t)(gstep + 1); ur.stageB = 0; ur.hB = 0.5f;
-        ur.coef_b2 = b1; ur.coef_a = 0.5f;
+    if (a->out_samples && a->n_thinning > 0 && (gstep % a->n_thinning) == 0) ur.out_sample = a->out_samples + (size_t)kept++ * E * d;
+    UpdParams u = upd_mid(m);
+    // Philox noise of the record launch: drawn by E extra workgroups of this launch (the update kernel of the record launch
+    // fills only E of the chip's CUs) and read back through the record launch's explicit-noise path -- the same numbers.
+    if (prefill && update_prefills(u)) {
+      ++s->nz_launches;
+      if (!ur.zA) {
+        u.nz_A = s->nzbuf; u.nz_stepA = ur.stepA; u.nz_stageA = ur.stageA;
+        ur.zA = u.nz_A;
       }
-      if (a->out_info) ur.out_info = a->out_info + (size_t)i * E * 3;
-      if (a->out_samples && a->n_thinning > 0 && (gstep % a->n_thinning) == 0) {
-        ur.out_sample = a->out_samples + (size_t)kept * Ed;
-        ++kept;
+      if ((ur.flags & UPD_OB) && !ur.zB) {
+        u.nz_B = s->nzbuf + nz_stride(s->nz_E, d); u.nz_stepB = ur.stepB; u.nz_stageB = ur.stageB;
+        ur.zB = u.nz_B;
       }
     }
-    {  // grad . B(1 - 2 b1) . A(1/2)
-      UpdParams u = up;
-      u.flags = UPD_FROM_SLABS | UPD_B1 | UPD_A | UPD_NO_G;
-      u.coef_b1 = b2; u.coef_a = 0.5f;
-      // Philox noise of the record launch: drawn by E extra workgroups of this launch (the update kernel of the record launch
-      // fills only E of the chip's CUs) and read back through the record launch's explicit-noise path -- the same numbers.
-      if (prefill && update_prefills(u)) {
-        ++s->nz_launches;
-        if (!ur.zA) {
-          u.nz_A = s->nzbuf; u.nz_stepA = ur.stepA; u.nz_stageA = ur.stageA;
-          ur.zA = u.nz_A;
-        }
-        if ((ur.flags & UPD_OB) && !ur.zB) {
-          u.nz_B = s->nzbuf + nz_stride(s->nz_E, d); u.nz_stepB = ur.stepB; u.nz_stageB = ur.stageB;
-          ur.zB = u.nz_B;
-        }
-      }
-      const int rc = grad_then_update(s, state->position, E, u, fused, st);
-      if (rc) return rc;
-    }
-    {
-      const int rc = grad_then_update(s, state->position, E, ur, fused, st);
-      if (rc) return rc;
-    }
+    if (const int rc = grad_then_update(s, state->position, E, u, fused, st)) return rc;
+    if (const int rc = grad_then_update(s, state->position, E, ur, fused, st)) return rc;
   }
   HIP_TRY(hipGetLastError());
   return MILE_OK;
 }
 
 int32_t mile_tune(mile_sampler *s, mile_state *state, const mile_tune_args *a, void *stream) {
-  if (!s || !state || !a) return fail(MILE_ERR_INVALID, "mile_tune: null argument");
-  if (!state->position || !state->momentum || !state->logdensity || !state->logdensity_grad)
-    return fail(MILE_ERR_INVALID, "mile_tune: null state field");
-  if (!a->step_size || !a->L || !a->step_size_max || !a->time || !a->x_average || !a->stream_weight || !a->stream_average)
-    return fail(MILE_ERR_INVALID, "mile_tune: null tuner array");
-  if (a->n_steps < 0 || a->schedule_total < 1) return fail(MILE_ERR_INVALID, "mile_tune: bad step counts");
-  if (a->refresh != MILE_REFRESH_O_STEP_O && a->refresh != MILE_REFRESH_STEP_O)
-    return fail(MILE_ERR_INVALID, "mile_tune: unknown refresh mode");
-  const int E = state->n_particles, d = s->ds.d;
-  if (E < 1) return fail(MILE_ERR_INVALID, "mile_tune: n_particles must be >= 1");
-  if ((d >> 2) < 1) return fail(MILE_ERR_INVALID, "mile_tune: d < 4");
-  const bool big = (d >> 2) > UPD_NT * UPD_QMAX || getenv("MILE_TUNE_POST") != nullptr;   // beyond k_update_fast's register cache
-  if (a->n_steps == 0) return MILE_OK;
+  // test hooks: the k_tune_post path at any d; the five-launch form of rounds 1-2; every chain through the merged launch's restart
+  const bool post = getenv("MILE_TUNE_POST") != nullptr, no_merge = getenv("MILE_TUNE_NO_MERGE") != nullptr;
+  const bool force_restart = getenv("MILE_TUNE_FORCE_RESTART") != nullptr;
+  Mclmc m{};
+  if (const int rc = mclmc_begin(s, state, a, "mile_tune", m); rc || a->n_steps == 0) return rc;
+  const int E = m.up.E, d = m.up.d;
+  const size_t Ed = (size_t)E * d;
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipSetDevice(s->device));
-  if (!s->X) return fail(MILE_ERR_STATE, "no data: call mile_set_data first");
-  const int S = choose_S(s, E, resolved_kernel(s));
-  if (E > s->E_cap || (size_t)E * S > s->ES_cap) return fail(MILE_ERR_STATE, "workspace too small: call mile_reserve(E) first");
 
   struct Buf { float *x, *u, *g, *logp; };
   const Buf A{state->position, state->momentum, state->logdensity_grad, state->logdensity};
   const Buf B{s->alt_x, s->alt_u, s->alt_g, s->alt_logp};
-  UpdParams up{};
-  up.d = d; up.E = E; up.S = S; up.dp = (d + 3) / 4 * 4;
-  up.prior = s->ds.prior; up.prior_loc = s->ds.prior_loc; up.prior_scale = s->ds.prior_scale;
-  up.slabs = s->slabs; up.llpart = s->llpart;
-  up.eps = a->step_size; up.L = a->L; up.sdc = a->sqrt_diag_cov;
-  up.seed = a->seed; up.pids = a->particle_ids;
-  up.dK = s->dK; up.lold = s->lold; up.upart = s->upart;
-  const float b1 = (float)MCLACHLAN_B1, b2 = (float)(1.0 - 2.0 * MCLACHLAN_B1);
-  const bool oso = a->refresh == MILE_REFRESH_O_STEP_O;
-  const size_t Ed = (size_t)E * d;
-  auto noise_at = [&](int i, int k) -> const float * { return a->noise ? a->noise + ((size_t)i * 2 + k) * Ed : nullptr; };
   auto set_state = [](UpdParams &u, const Buf &b) { u.x = b.x; u.u = b.u; u.g = b.g; u.logp = b.logp; };
-  auto target_var = [&](int sp) -> float {
-    const double tot = (double)a->schedule_total, vs = a->desired_energy_var_start, ve = a->desired_energy_var_end;
-    if (vs > 2.0) {
-      const double tau = tot / 4.0, ex = std::exp(-(double)sp / tau);
-      return (float)(vs * ex + ve * (1.0 - ex));
-    }
-    return (float)(vs - (vs - ve) * std::min((double)sp / tot, 1.0));
-  };
 
-  if (big) {
+  if ((d >> 2) > UPD_NT * UPD_QMAX || post) {   // beyond k_update_fast's register cache
     // Large d: an ordinary in-place kernel step (two-pass update kernels), the previous state copied aside first,
     // then k_tune_post applies the predictor, the rejection of non-finite steps and the streaming averages.
     if (!s->tune_info) HIP_TRY(hipMalloc(&s->tune_info, (size_t)s->E_cap * 3 * 4));
     for (int i = 0; i < a->n_steps; ++i) {
-      const int64_t gstep = a->step_offset + i;
       HIP_TRY(hipMemcpyAsync(B.x, A.x, Ed * 4, hipMemcpyDeviceToDevice, st));
       HIP_TRY(hipMemcpyAsync(B.u, A.u, Ed * 4, hipMemcpyDeviceToDevice, st));
       HIP_TRY(hipMemcpyAsync(B.g, A.g, Ed * 4, hipMemcpyDeviceToDevice, st));
       HIP_TRY(hipMemcpyAsync(B.logp, A.logp, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
       float *info_i = a->out_info ? a->out_info + (size_t)i * E * 3 : s->tune_info;
-      {
-        UpdParams u = up;
-        set_state(u, A);
-        u.flags = UPD_START | UPD_B2 | UPD_A | (oso ? UPD_OB : 0);
-        u.zB = noise_at(i, 0); u.stepB = (uint32_t)gstep; u.stageB = 0; u.hB = 0.5f;
-        u.coef_b2 = b1; u.coef_a = 0.5f;
-        launch_update(u, E, st);
-      }
-      int rc = launch_grad(s, A.x, E, st);
-      if (rc) return rc;
-      {
-        UpdParams u = up;
-        set_state(u, A);
-        u.flags = UPD_FROM_SLABS | UPD_B1 | UPD_A | UPD_NO_G;
-        u.coef_b1 = b2; u.coef_a = 0.5f;
-        launch_update(u, E, st);
-      }
-      rc = launch_grad(s, A.x, E, st);
-      if (rc) return rc;
-      {
-        UpdParams u = up;
-        set_state(u, A);
-        u.flags = UPD_FROM_SLABS | UPD_B1 | UPD_OA | UPD_RECORD;
-        u.coef_b1 = b1;
-        u.zA = noise_at(i, 1); u.stepA = (uint32_t)gstep; u.stageA = 1; u.hA = oso ? 0.5f : 1.0f;
-        u.out_info = info_i;
-        launch_update(u, E, st);
-      }
+      launch_update(upd_start(m, i), E, st);
+      if (const int rc = launch_grad(s, A.x, E, st)) return rc;
+      launch_update(upd_mid(m), E, st);
+      if (const int rc = launch_grad(s, A.x, E, st)) return rc;
+      UpdParams ur = upd_record(m, i);
+      ur.out_info = info_i;
+      launch_update(ur, E, st);
       TunePostParams tp{};
       tp.d = d; tp.x = A.x; tp.u = A.u; tp.g = A.g; tp.logp = A.logp;
       tp.bk_x = B.x; tp.bk_u = B.u; tp.bk_g = B.g; tp.bk_logp = B.logp;
       tp.info = info_i;
-      tp.t_eps = a->step_size; tp.t_eps_max = a->step_size_max; tp.t_time = a->time; tp.t_xavg = a->x_average;
-      tp.t_W = a->stream_weight; tp.t_avg = a->stream_average;
-      const int sp = a->schedule_step0 + i;
-      tp.t_mask = sp < a->n_mask_steps ? 1.0f : 0.0f;
-      tp.t_var = target_var(sp);
-      tp.t_trust = a->trust_in_estimate; tp.t_decay = a->decay_rate;
+      set_tuner(tp, a, a->schedule_step0 + i);
       k_tune_post<<<E, AUX_NT, 0, st>>>(tp);
     }
     HIP_TRY(hipGetLastError());
     return MILE_OK;
   }
 
-  UpdParams probe = up;
-  probe.x = A.x; probe.u = A.u; probe.g = A.g; probe.x_in = B.x; probe.u_in = B.u; probe.g_in = B.g;
+  UpdParams probe = m.up;
+  probe.x_in = B.x; probe.u_in = B.u; probe.g_in = B.g;
   probe.zA = a->noise; probe.t_avg = a->stream_average;
   if (a->n_steps > 1) probe.u_rec = A.u;
-  const bool fused = fuse_ok(s, resolved_kernel(s), probe);
+  const bool fused = fuse_ok(s, m.kernel, probe);
   if (fused) HIP_TRY(hipMemsetAsync(s->arrive, 0, ((size_t)E * 4 + 15) / 16 * 16, st));
   // Per step: grad . update(B, A) . grad . update(B, O, record + TUNE [. O, B, A of the next step with the NEW step size]) --
   // four launches, as a sampling step (mile_step).  Step i works in buffer W_i and leaves the accepted state there; its last
   // launch writes the next step's working position / momentum into the other buffer, which until then held the state before
   // step i (what handle_nans reverts to): W_{i+1} = K_i, K_{i+1} = W_i, no copies.
-  const bool no_merge = getenv("MILE_TUNE_NO_MERGE") != nullptr;      // dev / test: the five-launch form of rounds 1-2
   for (int i = 0; i < a->n_steps; ++i) {
     const Buf &cur = (i & 1) ? B : A, &nxt = (i & 1) ? A : B;
-    const int64_t gstep = a->step_offset + i;
-    if (i == 0 || no_merge) {  // O(z1) . B(b1) . A(1/2): reads the current state, writes the other buffer (free backup)
-      UpdParams u = up;
+    if (i == 0 || no_merge) {  // reads the current state, writes the other buffer (free backup)
+      UpdParams u = upd_start(m, i);
       set_state(u, nxt);
       u.x_in = cur.x; u.u_in = cur.u; u.g_in = cur.g; u.logp_in = cur.logp;
-      u.flags = UPD_START | UPD_B2 | UPD_A | (oso ? UPD_OB : 0);
-      u.zB = noise_at(i, 0); u.stepB = (uint32_t)gstep; u.stageB = 0; u.hB = 0.5f;
-      u.coef_b2 = b1; u.coef_a = 0.5f;
       launch_update(u, E, st);
     }
-    {
-      UpdParams u = up;
-      set_state(u, nxt);
-      u.flags = UPD_FROM_SLABS | UPD_B1 | UPD_A | UPD_NO_G;
-      u.coef_b1 = b2; u.coef_a = 0.5f;
-      const int rc = grad_then_update(s, nxt.x, E, u, fused, st);
-      if (rc) return rc;
+    UpdParams u = upd_mid(m);
+    set_state(u, nxt);
+    if (const int rc = grad_then_update(s, nxt.x, E, u, fused, st)) return rc;
+    // record + tuner (step-size predictor, handle_nans, streaming averages) [+ the next step's start]
+    UpdParams ur = upd_record(m, i);
+    set_state(ur, nxt);
+    ur.flags |= UPD_TUNE;
+    ur.bk_x = cur.x; ur.bk_u = cur.u; ur.bk_g = cur.g; ur.bk_logp = cur.logp;
+    set_tuner(ur, a, a->schedule_step0 + i);
+    if (i + 1 < a->n_steps && !no_merge) {
+      chain_start(ur, m, i + 1);
+      ur.x_in = nxt.x; ur.u_in = nxt.u;          // the step ran in nxt; its accepted state stays there ...
+      ur.x_acc = nxt.x; ur.u_rec = nxt.u;
+      ur.x = cur.x; ur.u = cur.u;                // ... and the next step's working state goes to the other buffer
+      ur.force_restart = force_restart;
     }
-    {  // B(b1) . O(z2) . record + tuner (step-size predictor, handle_nans, streaming averages) [+ the next step's O, B, A]
-      UpdParams u = up;
-      set_state(u, nxt);
-      u.flags = UPD_FROM_SLABS | UPD_B1 | UPD_OA | UPD_RECORD | UPD_TUNE;
-      u.coef_b1 = b1;
-      u.zA = noise_at(i, 1); u.stepA = (uint32_t)gstep; u.stageA = 1; u.hA = oso ? 0.5f : 1.0f;
-      u.bk_x = cur.x; u.bk_u = cur.u; u.bk_g = cur.g; u.bk_logp = cur.logp;
-      u.t_eps = a->step_size; u.t_eps_max = a->step_size_max; u.t_time = a->time; u.t_xavg = a->x_average;
-      u.t_W = a->stream_weight; u.t_avg = a->stream_average;
-      const int sp = a->schedule_step0 + i;
-      u.t_mask = sp < a->n_mask_steps ? 1.0f : 0.0f;
-      u.t_var = target_var(sp);
-      u.t_trust = a->trust_in_estimate; u.t_decay = a->decay_rate;
-      if (a->out_info) u.out_info = a->out_info + (size_t)i * E * 3;
-      if (i + 1 < a->n_steps && !no_merge) {
-        u.flags |= UPD_B2 | UPD_A | (oso ? UPD_OB : 0);
-        u.zB = noise_at(i + 1, 0); u.stepB = (uint32_t)(gstep + 1); u.stageB = 0; u.hB = 0.5f;
-        u.coef_b2 = b1; u.coef_a = 0.5f;
-        u.x_in = nxt.x; u.u_in = nxt.u;          // the step ran in nxt; its accepted state stays there ...
-        u.x_acc = nxt.x; u.u_rec = nxt.u;
-        u.x = cur.x; u.u = cur.u;                // ... and the next step's working state goes to the other buffer
-        u.force_restart = getenv("MILE_TUNE_FORCE_RESTART") != nullptr;
-      }
-      const int rc = grad_then_update(s, nxt.x, E, u, fused, st);
-      if (rc) return rc;
-    }
+    if (const int rc = grad_then_update(s, nxt.x, E, ur, fused, st)) return rc;
   }
   if (a->n_steps & 1) {   // the final state sits in the library's buffer
     HIP_TRY(hipMemcpyAsync(A.x, B.x, Ed * 4, hipMemcpyDeviceToDevice, st));

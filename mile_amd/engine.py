@@ -251,6 +251,40 @@ class Engine:
             raise ValueError(f'particle_ids must be [{E}]')
         return ids
 
+    def _mclmc_args(self, a, state, tuner, step_size, L, n_steps, noise, seed, step_offset, particle_ids, refresh,
+                    sqrt_diag_cov):
+        """Checks the state and fills what StepArgsC and TuneArgsC share.  ``tuner``: mile_tune's tensors (its step size
+        among them), or None for mile_step and its ``step_size``.  Returns the tensors ``a`` points into: they must outlive
+        the call."""
+        E, dev = state.position.shape[0], self.device
+        what, tensors = ('state', tuple(state)) if tuner is None else ('state / tuner', tuple(state) + tuple(tuner.values()))
+        for t in tensors:
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f'{what} tensors must be contiguous fp32 on the engine device')
+        if tuner is not None and tuner['stream_average'].shape != (E, 2, self.d):
+            raise ValueError('stream_average must be [E, 2, d]')
+        self.reserve(E)
+        if tuner is not None:
+            eps = tuner['step_size']
+        elif torch.as_tensor(step_size).ndim == 0:
+            eps = _f32(step_size, dev).expand(E).contiguous()
+        else:
+            eps = _f32(step_size, dev, (E,), 'step_size')
+        Lt = _f32(L, dev).expand(E).contiguous() if torch.as_tensor(L).ndim == 0 else _f32(L, dev, (E,), 'L')
+        z = _f32(noise, dev, (n_steps, 2, E, self.d), 'noise') if noise is not None else None
+        sdc = _f32(sqrt_diag_cov, dev, (E, self.d), 'sqrt_diag_cov') if sqrt_diag_cov is not None else None
+        ids = self._ids(particle_ids, E)
+        a.step_size = eps.data_ptr()
+        a.L = Lt.data_ptr()
+        a.sqrt_diag_cov = sdc.data_ptr() if sdc is not None else None
+        a.noise = z.data_ptr() if z is not None else None
+        a.seed = seed
+        a.particle_ids = ids.data_ptr() if ids is not None else None
+        a.step_offset = step_offset
+        a.n_steps = n_steps
+        a.refresh = _lib.REFRESH_IDS[refresh]
+        return eps, Lt, z, sdc, ids
+
     def init(self, position, noise=None, seed: int = 0, particle_ids=None) -> IntegratorState:
         """blackjax.mcmc.mclmc.init for an ensemble.  ``noise`` [E, d] (explicit N(0,1) draws)
         or the counter RNG keyed by (seed, particle id)."""
@@ -284,32 +318,15 @@ class Engine:
         dev = self.device
         if not inplace:
             state = IntegratorState(*(t.clone() for t in state))
-        for t in state:
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
-                raise ValueError('state tensors must be contiguous fp32 on the engine device')
-        self.reserve(E)
-        eps = _f32(step_size, dev).expand(E).contiguous() if torch.as_tensor(step_size).ndim == 0 \
-            else _f32(step_size, dev, (E,), 'step_size')
-        Lt = _f32(L, dev).expand(E).contiguous() if torch.as_tensor(L).ndim == 0 else _f32(L, dev, (E,), 'L')
-        z = _f32(noise, dev, (n_steps, 2, E, self.d), 'noise') if noise is not None else None
-        sdc = _f32(sqrt_diag_cov, dev, (E, self.d), 'sqrt_diag_cov') if sqrt_diag_cov is not None else None
-        ids = self._ids(particle_ids, E)
+        a = _lib.StepArgsC()
+        keep = self._mclmc_args(a, state, None, step_size, L, n_steps, noise, seed, step_offset, particle_ids, refresh,
+                                sqrt_diag_cov)
         n_kept = 0
         if n_thinning > 0:
             n_kept = sum(1 for i in range(n_steps) if (step_offset + i) % n_thinning == 0)
         samples = torch.empty((n_kept, E, self.d), dtype=torch.float32, device=dev) if n_kept else None
         info = torch.empty((n_steps, E, 3), dtype=torch.float32, device=dev) if want_info else None
-        a = _lib.StepArgsC()
-        a.step_size = eps.data_ptr()
-        a.L = Lt.data_ptr()
-        a.sqrt_diag_cov = sdc.data_ptr() if sdc is not None else None
-        a.noise = z.data_ptr() if z is not None else None
-        a.seed = seed
-        a.particle_ids = ids.data_ptr() if ids is not None else None
-        a.step_offset = step_offset
-        a.n_steps = n_steps
         a.n_thinning = n_thinning
-        a.refresh = _lib.REFRESH_IDS[refresh]
         a.out_samples = samples.data_ptr() if samples is not None else None
         a.out_info = info.data_ptr() if info is not None else None
         sc = self._state_c(state)
@@ -326,31 +343,15 @@ class Engine:
         ``tuner`` tensors (step_size, step_size_max, time, x_average, stream_weight [E];
         stream_average [E, 2, d]) are advanced IN PLACE.  Returns MCLMCInfo or None."""
         E, dev = state.position.shape[0], self.device
-        for t in tuple(state) + tuple(tuner.values()):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
-                raise ValueError('state / tuner tensors must be contiguous fp32 on the engine device')
-        if tuner['stream_average'].shape != (E, 2, self.d):
-            raise ValueError('stream_average must be [E, 2, d]')
-        self.reserve(E)
-        Lt = _f32(L, dev).expand(E).contiguous() if torch.as_tensor(L).ndim == 0 else _f32(L, dev, (E,), 'L')
-        z = _f32(noise, dev, (n_steps, 2, E, self.d), 'noise') if noise is not None else None
-        sdc = _f32(sqrt_diag_cov, dev, (E, self.d), 'sqrt_diag_cov') if sqrt_diag_cov is not None else None
-        ids = self._ids(particle_ids, E)
-        info = torch.empty((n_steps, E, 3), dtype=torch.float32, device=dev) if want_info else None
         a = _lib.TuneArgsC()
-        a.step_size = tuner['step_size'].data_ptr()
-        a.L = Lt.data_ptr()
-        a.sqrt_diag_cov = sdc.data_ptr() if sdc is not None else None
+        keep = self._mclmc_args(a, state, tuner, None, L, n_steps, noise, seed, step_offset, particle_ids, refresh,
+                                sqrt_diag_cov)
+        info = torch.empty((n_steps, E, 3), dtype=torch.float32, device=dev) if want_info else None
         a.step_size_max = tuner['step_size_max'].data_ptr()
         a.time = tuner['time'].data_ptr()
         a.x_average = tuner['x_average'].data_ptr()
         a.stream_weight = tuner['stream_weight'].data_ptr()
         a.stream_average = tuner['stream_average'].data_ptr()
-        a.noise = z.data_ptr() if z is not None else None
-        a.seed = seed
-        a.particle_ids = ids.data_ptr() if ids is not None else None
-        a.step_offset = step_offset
-        a.n_steps = n_steps
         a.schedule_step0 = schedule_step0
         a.n_mask_steps = n_mask_steps
         a.schedule_total = schedule_total
@@ -358,7 +359,6 @@ class Engine:
         a.desired_energy_var_end = desired_energy_var_end
         a.trust_in_estimate = trust_in_estimate
         a.decay_rate = decay_rate
-        a.refresh = _lib.REFRESH_IDS[refresh]
         a.out_info = info.data_ptr() if info is not None else None
         sc = self._state_c(state)
         with torch.cuda.device(dev):
