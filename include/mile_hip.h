@@ -16,7 +16,8 @@
  *   - All array pointers are DEVICE pointers into caller-owned memory (PyTorch-ROCm
  *     tensors), contiguous, row-major, fp32 unless stated.  The library never
  *     frees or retains caller memory beyond the call, except mile_set_data which
- *     COPIES X and y into its own padded layout.
+ *     COPIES X and y into its own padded layout, and mile_set_embedding, which COPIES
+ *     the frozen embedding tables.
  *   - [E, d] arrays: one row per particle (chain), d = mile_param_count(), in
  *     jax.flatten_util.ravel_pytree order of the FCN param tree: for each layer in
  *     sorted-name order ('layer0','layer1','layer10','layer11','layer2',...):
@@ -38,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MILE_ABI_VERSION 8
+#define MILE_ABI_VERSION 9
 #define MILE_MAX_LAYERS 16
 
 typedef enum mile_status {
@@ -84,15 +85,24 @@ typedef enum mile_grad_kernel {
   MILE_GRAD_LENETTI_F32 = 11,     /* MILE_MODEL_LENETTI only (and its only kernel; AUTO resolves to it): one fused fp32 forward +
                                      backward launch, k_grad_lenetti (mile_lenetti.h); <= 4 image channels, (H+2)(W+2) <= 2048,
                                      out_dim <= 16 */
-  MILE_GRAD_ATTN_F32 = 12         /* MILE_MODEL_ATTN only (and its only kernel; AUTO resolves to it): one fused fp32 forward +
+  MILE_GRAD_ATTN_F32 = 12,        /* MILE_MODEL_ATTN only (and its only kernel; AUTO resolves to it): one fused fp32 forward +
                                      backward launch, k_grad_attn (mile_attn.h), products on v_mfma_f32_16x16x4_f32; T <= 128,
                                      C <= 64, D <= 64 with H | D, <= 2 projections of width <= 64, n_classes <= 16, and
                                      <= 160 KB of LDS per workgroup (refused otherwise: H = 3, D in {57, 60, 63} with
                                      T > 112) */
+  MILE_GRAD_ATTN_PRE_F32 = 13     /* MILE_MODEL_ATTN_PRETRAINED only (and its only kernel; AUTO resolves to it): one fused fp32
+                                     forward + backward launch, k_grad_attn_pre (mile_attn_pre.h), products on
+                                     v_mfma_f32_16x16x4_f32, weights streamed from L2, gradients accumulated in the
+                                     workgroup's own slab row; T <= 128, C <= 192, D <= 128 with H | D, <= 2 projections of
+                                     width <= 128, n_classes <= 16, and <= 160 KB of LDS per workgroup (q|k|v [Tp][3D] + e
+                                     [Tp][C] + vectors: e.g. C = 192, D = 64 needs T <= 96) */
 } mile_grad_kernel;
 /* Which network: the FCN (src/models/tabular/fcn.py:16-28), LeNet (src/models/images/cnns.py:10-66), LeNetti
- * (src/models/images/cnns.py:69-121) or AttentionClassifier (src/models/text/attention_classifier.py). */
-typedef enum mile_model { MILE_MODEL_FCN = 0, MILE_MODEL_LENET = 1, MILE_MODEL_LENETTI = 2, MILE_MODEL_ATTN = 3 } mile_model;
+ * (src/models/images/cnns.py:69-121), AttentionClassifier (src/models/text/attention_classifier.py) or
+ * PretrainedAttentionClassifier (attention_classifier.py:74-132: frozen embedding tables, see mile_set_embedding). */
+typedef enum mile_model {
+  MILE_MODEL_FCN = 0, MILE_MODEL_LENET = 1, MILE_MODEL_LENETTI = 2, MILE_MODEL_ATTN = 3, MILE_MODEL_ATTN_PRETRAINED = 4
+} mile_model;
 
 /* FCNConfig (src/config/models/fcn.py:7-30) + PriorConfig (src/config/sampler.py:60-95)
  * + Task: everything log_unnormalized_posterior (src/training/probabilistic.py:115-138)
@@ -118,7 +128,10 @@ typedef struct mile_model_spec {
                                       * Parameters in ravel_pytree order (sorted keys, bias before kernel; biases only
                                       * with use_bias): MDPA.key [C,H,hd], MDPA.out [H,hd,C], MDPA.query, MDPA.value,
                                       * TokenEmbedding_0.Embedding.embedding [V,C], .PositionEmbedding.embedding [T,C],
-                                      * classifier [P_last,K], projection_0 [C,P_0], projection_1 [P_0,P_1] */
+                                      * classifier [P_last,K], projection_0 [C,P_0], projection_1 [P_0,P_1].
+                                      * ATTN_PRETRAINED: the same geometry fields and conventions; one more gelu before
+                                      * the classifier; no TokenEmbedding_0 leaves (the tables are not parameters: they
+                                      * come from mile_set_embedding) */
   int32_t img_c;                     /* LENET / LENETTI image geometry (ignored for the FCN) */
   int32_t img_h;
   int32_t img_w;
@@ -260,7 +273,8 @@ int64_t mile_param_count(const mile_sampler *s);
 
 /* Offsets of layer `layer`'s bias and kernel inside the raveled vector (ravel_pytree order).  LENET: layers 0..4 = conv1, conv2,
  * fc1, fc2, fc3; LENETTI: layers 0..4 = conv1, fc1, fc2, fc3, fc4; ATTN: layers 0..3 = MDPA key, out, query, value,
- * 4 = Embedding (kernel = the table, no bias), 5 = PositionEmbedding, 6 = classifier, 7.. = projection_0, projection_1.
+ * 4 = Embedding (kernel = the table, no bias), 5 = PositionEmbedding, 6 = classifier, 7.. = projection_0, projection_1;
+ * ATTN_PRETRAINED: layers 0..3 = MDPA key, out, query, value, 4 = classifier, 5.. = projection_0, projection_1.
  * A missing bias (use_bias = 0) has offset -1. */
 int32_t mile_param_offsets(const mile_sampler *s, int32_t layer, int64_t *bias_off, int64_t *kernel_off);
 
@@ -268,10 +282,17 @@ int32_t mile_param_offsets(const mile_sampler *s, int32_t layer, int64_t *bias_o
  * (src/training/trainer.py:576-580).  X [N, F] fp32; y [N] fp32 (regr) or int32 (classification). */
 int32_t mile_set_data(mile_sampler *s, const float *X, const void *y, int64_t N, void *stream);
 
+/* MILE_MODEL_ATTN_PRETRAINED only: PretrainedTokenEmbedding (src/flax_building_blocks/basic.py:117-143).  Copies the frozen
+ * token table emb [V, C] and the first T rows of the position table, pos [T, C], into buffers the sampler owns (shared by all
+ * chains; they are neither sampled nor in the prior).  Until it has been called, mile_logpost_grad, mile_warmstart_step,
+ * mile_init, mile_step, mile_tune, mile_nuts_step, mile_nuts_warmup and mile_pointwise_loglik fail with MILE_ERR_STATE.
+ * Calling it again replaces the tables. */
+int32_t mile_set_embedding(mile_sampler *s, const float *emb, const float *pos, void *stream);
+
 /* Restrict the likelihood to rows [begin, begin + count) of the training set for the following mile_logpost_grad calls
  * (count = 0: all rows again).  Replaces the minibatches of the warm-start stage: loader.iter(split='train', batch_size=...)
  * (src/dataset/tabular.py:170-212) feeding single_step_regr / single_step_class (src/training/trainer.py:706-760).
- * Supported by MILE_GRAD_GENERIC, the MFMA_NARROW, MFMA_W64, MFMA_WIDE, LENET, LENETTI and ATTN kernels (mile_logpost_grad fails with MILE_ERR_STATE on
+ * Supported by MILE_GRAD_GENERIC, the MFMA_NARROW, MFMA_W64, MFMA_WIDE, LENET, LENETTI, ATTN and ATTN_PRE kernels (mile_logpost_grad fails with MILE_ERR_STATE on
  * MFMA_W128_BF16 / GEMM_F32 under a window); the MCLMC path itself is full-batch (n_batches = 1). */
 int32_t mile_set_row_window(mile_sampler *s, int64_t begin, int64_t count);
 

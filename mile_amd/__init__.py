@@ -3,6 +3,6 @@
 Importing the package never touches the GPU; the HIP library is loaded on first use and
 there is no CPU fallback.
 """
-from mile_amd.spec import AttentionSpec, LeNetSpec, LeNettiSpec, ModelSpec  # noqa: F401
+from mile_amd.spec import AttentionSpec, LeNetSpec, LeNettiSpec, ModelSpec, PretrainedAttentionSpec  # noqa: F401
 
 __version__ = '0.1.0'

@@ -23,6 +23,7 @@
 #include "mile_lenet_mfma.h"
 #include "mile_lenetti.h"
 #include "mile_attn.h"
+#include "mile_attn_pre.h"
 #include "mile_predict.h"
 #include "mile_update.h"
 #include "mile_nuts.h"
@@ -63,7 +64,8 @@ struct mile_sampler {
   int grad_kernel = MILE_GRAD_AUTO;
   LeNetGeom lg{};                       // MILE_MODEL_LENET geometry and parameter offsets
   LeNettiGeom ng{};                     // MILE_MODEL_LENETTI geometry and parameter offsets
-  AttnGeom ag{};                        // MILE_MODEL_ATTN geometry and parameter offsets
+  AttnGeom ag{};                        // MILE_MODEL_ATTN / ATTN_PRETRAINED geometry and parameter offsets
+  float *emb_tab = nullptr, *pos_tab = nullptr;   // ATTN_PRETRAINED: frozen tables [V, C], [T, C] (mile_set_embedding)
   struct ParamLayer { int bias_off, kernel_off; };
   std::vector<ParamLayer> layers;       // mile_param_offsets, in ABI order (bias -1: none)
   // layer-wise GEMM path (MILE_GRAD_GEMM_F32): rocBLAS handle and activation workspace
@@ -93,6 +95,10 @@ static bool is_fcn(const mile_sampler *s) { return s->spec.model == MILE_MODEL_F
 static bool is_lenet(const mile_sampler *s) { return s->spec.model == MILE_MODEL_LENET; }
 static bool is_lenetti(const mile_sampler *s) { return s->spec.model == MILE_MODEL_LENETTI; }
 static bool is_attn(const mile_sampler *s) { return s->spec.model == MILE_MODEL_ATTN; }
+static bool is_attn_pre(const mile_sampler *s) { return s->spec.model == MILE_MODEL_ATTN_PRETRAINED; }
+// every call that evaluates the likelihood refuses a pretrained-attention sampler whose tables are not set
+static bool tables_missing(const mile_sampler *s) { return is_attn_pre(s) && !s->emb_tab; }
+static const char *const kNoTables = "PretrainedAttentionClassifier: call mile_set_embedding first";
 static bool lenet_bf16_supported(const mile_sampler *s) { return is_lenet(s) && s->lg.C <= 4; }
 
 // k_grad_w64 / k_grad_w128b: ReLU regression, 1-3 hidden layers of the kernel's width, F <= 16
@@ -223,7 +229,7 @@ static int lenetti_S(const mile_sampler *s, int E) {
   return std::max(1, std::min({64, want, std::max(1, s->N / 32)}));
 }
 
-// k_grad_attn: one workgroup per CU (its LDS), at most 64 row ranges and at least 16 sequences per range
+// k_grad_attn / k_grad_attn_pre: one workgroup per CU (its LDS), at most 64 row ranges and at least 16 sequences per range
 static int attn_S(const mile_sampler *s, int E) {
   const int want = (s->n_cu + std::max(E, 1) - 1) / std::max(E, 1);
   return std::max(1, std::min({64, want, std::max(1, s->N / 16)}));
@@ -257,6 +263,7 @@ static int auto_kernel(const mile_sampler *s) {
   if (is_lenet(s)) return MILE_GRAD_LENET_F32;                // the other models: their own kernel
   if (is_lenetti(s)) return MILE_GRAD_LENETTI_F32;
   if (is_attn(s)) return MILE_GRAD_ATTN_F32;
+  if (is_attn_pre(s)) return MILE_GRAD_ATTN_PRE_F32;
   return MILE_GRAD_GENERIC;
 }
 static int resolved_kernel(const mile_sampler *s) { return s->grad_kernel == MILE_GRAD_AUTO ? auto_kernel(s) : s->grad_kernel; }
@@ -395,6 +402,49 @@ static int layout_attn(mile_sampler *s) {
   return MILE_OK;
 }
 
+// PretrainedAttentionClassifier: ravel_pytree order MDPA.{key, out, query, value}, classifier, projection_*; bias before kernel.
+// No TokenEmbedding_0 leaves: the tables are frozen (mile_set_embedding).  ABI layers: key, out, query, value, classifier,
+// projection_*
+static int layout_attn_pre(mile_sampler *s) {
+  const mile_model_spec *spec = &s->spec;
+  if (spec->task != MILE_TASK_CLASSIFICATION) return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: classification only");
+  if (spec->n_layers < 1 || spec->n_layers > ATTN_MAX_NP + 1)
+    return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: widths = projection_dim (at most 2) + [n_classes]");
+  if (spec->ctx_len < 1 || spec->ctx_len > ATTN_MAX_T || spec->in_features != spec->ctx_len)
+    return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: 1 <= ctx_len <= 128 and in_features == ctx_len");
+  if (spec->emb_size < 1 || spec->emb_size > ATTNP_MAX_C) return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: emb_size <= 192");
+  if (spec->qkv_dim < 1 || spec->qkv_dim > ATTNP_MAX_D || spec->n_heads < 1 || spec->qkv_dim % spec->n_heads)
+    return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: qkv_dim <= 128 and n_heads dividing it");
+  if (spec->vocab_size < 1 || spec->vocab_size > (1 << 24))
+    return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: 1 <= vocab_size <= 2^24");
+  for (int l = 0; l + 1 < spec->n_layers; ++l)
+    if (spec->widths[l] > ATTNP_MAX_P) return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: projection widths <= 128");
+  if (spec->widths[spec->n_layers - 1] > ATTN_MAX_K) return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: n_classes <= 16");
+  AttnGeom &g = s->ag;
+  g.V = spec->vocab_size; g.T = spec->ctx_len; g.C = spec->emb_size; g.H = spec->n_heads; g.D = spec->qkv_dim;
+  g.hd = g.D / g.H; g.NP = spec->n_layers - 1; g.K = spec->widths[g.NP]; g.bias = spec->use_bias ? 1 : 0;
+  g.Tp = (g.T + 15) / 16 * 16;
+  for (int l = 0; l < ATTN_MAX_NP; ++l) { g.P[l] = l < g.NP ? spec->widths[l] : 0; g.b_p[l] = g.k_p[l] = -1; }
+  if (!attnp_supported(g)) return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: shape needs more than 160 KB of LDS");
+  long long o = 0;
+  auto put = [&](int &b, int &k, long long nb, long long nk) { b = g.bias && nb ? (int)o : -1; o += g.bias ? nb : 0; k = (int)o; o += nk; };
+  put(g.b_k, g.k_k, g.D, (long long)g.C * g.D);
+  put(g.b_o, g.k_o, g.C, (long long)g.D * g.C);
+  put(g.b_q, g.k_q, g.D, (long long)g.C * g.D);
+  put(g.b_v, g.k_v, g.D, (long long)g.C * g.D);
+  g.emb = g.pos = -1;
+  put(g.b_c, g.k_c, g.K, (long long)(g.NP ? g.P[g.NP - 1] : g.C) * g.K);
+  for (int l = 0; l < g.NP; ++l) put(g.b_p[l], g.k_p[l], g.P[l], (long long)(l ? g.P[l - 1] : g.C) * g.P[l]);
+  g.d = (int)o;
+  s->ds.d = g.d;
+  s->ds.widths[0] = g.K;
+  s->ds.b_off[0] = g.b_c; s->ds.w_off[0] = g.k_c;
+  s->ds.max_width = 64; s->ds.act_stride = 0;
+  s->layers = {{g.b_k, g.k_k}, {g.b_o, g.k_o}, {g.b_q, g.k_q}, {g.b_v, g.k_v}, {g.b_c, g.k_c}};
+  for (int l = 0; l < g.NP; ++l) s->layers.push_back({g.b_p[l], g.k_p[l]});
+  return MILE_OK;
+}
+
 extern "C" {
 
 const char *mile_last_error(void) { return g_err.c_str(); }
@@ -404,7 +454,7 @@ int32_t mile_create(const mile_model_spec *spec, int32_t device, mile_sampler **
   if (!spec || !out) return fail(MILE_ERR_INVALID, "mile_create: null argument");
   if (spec->n_layers < 1 || spec->n_layers > MILE_MAX_LAYERS) return fail(MILE_ERR_INVALID, "n_layers out of range");
   if (spec->in_features < 1) return fail(MILE_ERR_INVALID, "in_features must be >= 1");
-  if (!spec->use_bias && spec->model != MILE_MODEL_ATTN) return fail(MILE_ERR_INVALID, "use_bias=false is not supported");
+  if (!spec->use_bias && spec->model != MILE_MODEL_ATTN && spec->model != MILE_MODEL_ATTN_PRETRAINED) return fail(MILE_ERR_INVALID, "use_bias=false is not supported");
   if (spec->activation < 0 || spec->activation > MILE_ACT_SIGMOID) return fail(MILE_ERR_INVALID, "unknown activation");
   if (spec->task != MILE_TASK_REGRESSION && spec->task != MILE_TASK_CLASSIFICATION) return fail(MILE_ERR_INVALID, "unknown task");
   if (spec->prior != MILE_PRIOR_NORMAL && spec->prior != MILE_PRIOR_LAPLACE) return fail(MILE_ERR_INVALID, "unknown prior");
@@ -413,8 +463,8 @@ int32_t mile_create(const mile_model_spec *spec, int32_t device, mile_sampler **
     if (spec->widths[l] < 1) return fail(MILE_ERR_INVALID, "layer width must be >= 1");
   if (spec->task == MILE_TASK_REGRESSION && spec->widths[spec->n_layers - 1] != 2)
     return fail(MILE_ERR_INVALID, "regression needs an output layer of width 2 (mu, log sigma)");
-  static int (*const layout[])(mile_sampler *) = {layout_fcn, layout_lenet, layout_lenetti, layout_attn};   // by mile_model
-  if (spec->model < MILE_MODEL_FCN || spec->model > MILE_MODEL_ATTN) return fail(MILE_ERR_INVALID, "unknown model");
+  static int (*const layout[])(mile_sampler *) = {layout_fcn, layout_lenet, layout_lenetti, layout_attn, layout_attn_pre};   // by mile_model
+  if (spec->model < MILE_MODEL_FCN || spec->model > MILE_MODEL_ATTN_PRETRAINED) return fail(MILE_ERR_INVALID, "unknown model");
 
   auto *s = new mile_sampler();
   s->spec = *spec;
@@ -495,6 +545,8 @@ int32_t mile_destroy(mile_sampler *s) {
   if (s->wide_wt) (void)hipFree(s->wide_wt);
   if (s->wide_hb) (void)hipFree(s->wide_hb);
   if (s->tune_info) (void)hipFree(s->tune_info);
+  if (s->emb_tab) (void)hipFree(s->emb_tab);
+  if (s->pos_tab) (void)hipFree(s->pos_tab);
   free_nuts(s);
   if (s->nuts_count_h) (void)hipHostFree(s->nuts_count_h);
   if (s->blas && g_rb.destroy) (void)g_rb.destroy(s->blas);
@@ -573,6 +625,21 @@ int32_t mile_set_data(mile_sampler *s, const float *X, const void *y, int64_t N,
   return MILE_OK;
 }
 
+int32_t mile_set_embedding(mile_sampler *s, const float *emb, const float *pos, void *stream) {
+  if (!s || !emb || !pos) return fail(MILE_ERR_INVALID, "mile_set_embedding: null argument");
+  if (!is_attn_pre(s)) return fail(MILE_ERR_INVALID, "mile_set_embedding: only MILE_MODEL_ATTN_PRETRAINED has frozen tables");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->device));
+  const AttnGeom &g = s->ag;
+  if (!s->emb_tab) {
+    HIP_TRY(hipMalloc(&s->emb_tab, (size_t)g.V * g.C * 4));
+    HIP_TRY(hipMalloc(&s->pos_tab, (size_t)g.T * g.C * 4));
+  }
+  HIP_TRY(hipMemcpyAsync(s->emb_tab, emb, (size_t)g.V * g.C * 4, hipMemcpyDefault, st));
+  HIP_TRY(hipMemcpyAsync(s->pos_tab, pos, (size_t)g.T * g.C * 4, hipMemcpyDefault, st));
+  return MILE_OK;
+}
+
 int32_t mile_set_row_window(mile_sampler *s, int64_t begin, int64_t count) {
   if (!s) return fail(MILE_ERR_INVALID, "null handle");
   if (!s->X) return fail(MILE_ERR_STATE, "mile_set_row_window: call mile_set_data first");
@@ -591,7 +658,7 @@ int32_t mile_reserve(mile_sampler *s, int32_t E) {
   HIP_TRY(hipSetDevice(s->device));
   // capacity must cover whichever grad kernel is selected later
   int S = choose_S(s, E, MILE_GRAD_GENERIC);
-  for (int k = MILE_GRAD_GENERIC; k <= MILE_GRAD_ATTN_F32; ++k)
+  for (int k = MILE_GRAD_GENERIC; k <= MILE_GRAD_ATTN_PRE_F32; ++k)
     if (grad_kernel(k).supports(s)) S = std::max(S, choose_S(s, E, k));
   // A smaller ensemble splits the rows of a particle over MORE workgroups (S grows as E shrinks): capacity is counted in
   // slab rows E * S, and a later call with fewer particles must neither fail nor shrink what a larger one reserved.
@@ -617,7 +684,7 @@ int32_t mile_reserve(mile_sampler *s, int32_t E) {
 
 int32_t mile_set_grad_kernel(mile_sampler *s, int32_t which) {
   if (!s) return fail(MILE_ERR_INVALID, "null handle");
-  if (which < MILE_GRAD_AUTO || which > MILE_GRAD_ATTN_F32) return fail(MILE_ERR_INVALID, "unknown grad kernel");
+  if (which < MILE_GRAD_AUTO || which > MILE_GRAD_ATTN_PRE_F32) return fail(MILE_ERR_INVALID, "unknown grad kernel");
   if (which != MILE_GRAD_AUTO) {
     const GradKernel &k = grad_kernel(which);
     if (!k.supports(s)) return fail(MILE_ERR_INVALID, k.refusal);
@@ -1427,6 +1494,17 @@ static hipError_t launch_attn(mile_sampler *s, const float *theta, int E, const 
   return mile_launch_attn(ap, E, out_ll == nullptr, st);
 }
 
+// ---- PretrainedAttentionClassifier (mile_attn_pre.h; the kernels are instantiated in mile_attn_pre.hip), as launch_attn
+static hipError_t launch_attn_pre(mile_sampler *s, const float *theta, int E, const float *X, const void *y, int N, int S, int dp,
+                                  float *out_ll, hipStream_t st) {
+  AttnPreParams ap{};
+  ap.g = s->ag;
+  ap.theta = theta; ap.X = X; ap.y = y; ap.emb = s->emb_tab; ap.pos = s->pos_tab;
+  ap.slabs = s->slabs; ap.llpart = s->llpart; ap.out = out_ll;
+  ap.N = N; ap.S = S; ap.dp = dp;
+  return mile_launch_attn_pre(ap, E, out_ll == nullptr, st);
+}
+
 // ---- the gradient of each grad kernel: the `grad` of its row in kGrad.  gp holds the row window and S; fz the update that runs
 // as the launch's epilogue (fuses) ----------------------------------------------------------------------------------------------
 static int grad_w64(mile_sampler *s, const GradParams &gp, const W64Fuse &fz, int E, hipStream_t st) {
@@ -1456,6 +1534,10 @@ static int grad_narrow(mile_sampler *s, const GradParams &gp, const W64Fuse &, i
 }
 static int grad_attn(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
   HIP_TRY(launch_attn(s, gp.theta, E, gp.X, gp.y, gp.N, gp.S, gp.dp, nullptr, st));
+  return MILE_OK;
+}
+static int grad_attn_pre(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
+  HIP_TRY(launch_attn_pre(s, gp.theta, E, gp.X, gp.y, gp.N, gp.S, gp.dp, nullptr, st));
   return MILE_OK;
 }
 static int grad_lenetti(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
@@ -1488,6 +1570,7 @@ static int grad_generic(mile_sampler *s, const GradParams &gp, const W64Fuse &, 
 
 static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t st, const UpdParams *fused_update) {
   if (!s->X) return fail(MILE_ERR_STATE, "no data: call mile_set_data first");
+  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
   const GradKernel &k = grad_kernel(resolved_kernel(s));
   const int S = k.row_splits(s, E);
   if (E > s->E_cap || (size_t)E * S > s->ES_cap) return fail(MILE_ERR_STATE, "workspace too small: call mile_reserve(E) first");
@@ -1499,7 +1582,7 @@ static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t s
   gp.N = s->N; gp.Npad = s->Npad; gp.Npb = s->Npb; gp.Fp = s->Fp; gp.S = S; gp.R = generic_R(s->ds); gp.dp = (s->ds.d + 3) / 4 * 4;
   if (s->win_count) {   // minibatch: the same kernels on a shifted view of the rows
     if (!k.windowed)
-      return fail(MILE_ERR_STATE, "a row window needs the generic, the MFMA_NARROW, an MFMA_W64, an MFMA_WIDE, a LENET, the LENETTI or the ATTN grad kernel");
+      return fail(MILE_ERR_STATE, "a row window needs the generic, the MFMA_NARROW, an MFMA_W64, an MFMA_WIDE, a LENET, the LENETTI, the ATTN or the ATTN_PRE grad kernel");
     if (fused_update) return fail(MILE_ERR_STATE, "row windows are for mile_logpost_grad only");
     const int F = s->spec.in_features;
     gp.X = s->X + (size_t)s->win_begin * F;
@@ -1633,6 +1716,7 @@ static int mclmc_begin(mile_sampler *s, mile_state *state, const Args *a, const 
   if (a->n_steps == 0) return MILE_OK;
   HIP_TRY(hipSetDevice(s->device));
   if (!s->X) return fail(MILE_ERR_STATE, "no data: call mile_set_data first");
+  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
   m.kernel = resolved_kernel(s);
   const int S = choose_S(s, E, m.kernel);
   if (E > s->E_cap || (size_t)E * S > s->ES_cap) return fail(MILE_ERR_STATE, "workspace too small: call mile_reserve(E) first");
@@ -1787,6 +1871,14 @@ static int loglik_attn(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
   }
   return MILE_OK;
 }
+static int loglik_attn_pre(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
+  const int SB = std::max(1, std::min({64, (s->n_cu + S - 1) / S, std::max(1, pp.N / 16)}));
+  for (int s0 = 0; s0 < S; s0 += 65535) {
+    const int Sc = std::min(65535, S - s0);
+    HIP_TRY(launch_attn_pre(s, pp.theta + (size_t)s0 * s->ds.d, Sc, pp.X, pp.y, pp.N, SB, 0, pp.out + (size_t)s0 * pp.N, st));
+  }
+  return MILE_OK;
+}
 static int loglik_lenetti(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
   const int SB = std::max(1, std::min({64, (2 * s->n_cu + S - 1) / S, std::max(1, pp.N / 32)}));
   for (int s0 = 0; s0 < S; s0 += 65535) {
@@ -1852,6 +1944,7 @@ static LaunchShape shape_narrow(const mile_sampler *s, int S) {
              : std::max(NarrowLayout<3, 2, 4>::BYTES, NarrowLayout<10, 1, 1>::BYTES)};
 }
 static LaunchShape shape_attn(const mile_sampler *s, int) { return {256, (int)attn_lds_bytes(s->ag, attn_weights_in_lds(s->ag))}; }
+static LaunchShape shape_attn_pre(const mile_sampler *s, int) { return {256, (int)attnp_lds_bytes(s->ag)}; }
 static LaunchShape shape_lenetti(const mile_sampler *s, int) { return {256, (int)lenetti_lds_bytes(s->ng, lenetti_T(s->ng))}; }
 static LaunchShape shape_lenet_bf16(const mile_sampler *s, int) { return {256, (int)cm_lds_dw(CM_IN8, s->lg.hp1, s->lg.wp1, 0)}; }
 static LaunchShape shape_rocblas(const mile_sampler *, int) { return {256, 0}; }
@@ -1895,11 +1988,14 @@ static constexpr GradKernel kGrad[] = {
      lenetti_S, true, false, grad_lenetti, loglik_lenetti, shape_lenetti},
     {MILE_GRAD_ATTN_F32, "k_grad_attn", is_attn, "ATTN_F32 is the kernel of MILE_MODEL_ATTN, and its only one", nullptr,
      attn_S, true, false, grad_attn, loglik_attn, shape_attn},
+    {MILE_GRAD_ATTN_PRE_F32, "k_grad_attn_pre", is_attn_pre,
+     "ATTN_PRE_F32 is the kernel of MILE_MODEL_ATTN_PRETRAINED, and its only one", nullptr,
+     attn_S, true, false, grad_attn_pre, loglik_attn_pre, shape_attn_pre},
 };
 static constexpr bool rows_in_id_order() {
   for (int k = 0; k < (int)(sizeof(kGrad) / sizeof(kGrad[0])); ++k)
     if (kGrad[k].id != k + 1) return false;
-  return sizeof(kGrad) / sizeof(kGrad[0]) == MILE_GRAD_ATTN_F32;
+  return sizeof(kGrad) / sizeof(kGrad[0]) == MILE_GRAD_ATTN_PRE_F32;
 }
 static_assert(rows_in_id_order(), "kGrad: one row per MILE_GRAD_* id, in id order");
 static const GradKernel &grad_kernel(int kernel) { return kGrad[kernel - 1]; }
@@ -1908,6 +2004,7 @@ extern "C" int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, in
                                          int64_t N, float *out, void *stream) {
   if (!s || !theta || !X || !y || !out || S < 1) return fail(MILE_ERR_INVALID, "mile_pointwise_loglik: bad argument");
   if (N < 1 || N > 0x3fffffff) return fail(MILE_ERR_INVALID, "mile_pointwise_loglik: N out of range");
+  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->device));
   const int F = s->spec.in_features, Npad = ((int)N + 31) / 32 * 32, Fp = (F + 7) / 8 * 8;
@@ -2212,6 +2309,7 @@ static int nuts_run(mile_sampler *s, mile_state *state, const mile_nuts_args *a,
   }
   if (!s->X) return fail(MILE_ERR_STATE, "no data: call mile_set_data first");
   if (E > s->nuts_E || M > s->nuts_M) return fail(MILE_ERR_STATE, std::string(fn) + ": call mile_nuts_reserve(E, max_num_doublings) first");
+  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
   if (a->n_steps == 0) return MILE_OK;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->device));

@@ -12,7 +12,7 @@ from typing import NamedTuple
 import torch
 
 from mile_amd import _lib
-from mile_amd.spec import IMAGE_SPECS, AttentionSpec, LeNetSpec, LeNettiSpec, ModelSpec
+from mile_amd.spec import IMAGE_SPECS, AttentionSpec, LeNetSpec, LeNettiSpec, ModelSpec, PretrainedAttentionSpec
 
 
 class IntegratorState(NamedTuple):
@@ -68,7 +68,7 @@ def _f32(t, device, shape=None, name='tensor'):
 
 def _check_tokens(spec, X):
     """AttentionClassifier rows are token ids stored as fp32: integers in [0, vocab_size)."""
-    if not isinstance(spec, AttentionSpec) or not X.numel():
+    if not isinstance(spec, (AttentionSpec, PretrainedAttentionSpec)) or not X.numel():
         return
     if bool((X != torch.floor(X)).any()) or float(X.min()) < 0 or float(X.max()) >= spec.vocab_size:
         raise ValueError(f'token ids must be integers in [0, {spec.vocab_size})')
@@ -77,7 +77,8 @@ def _check_tokens(spec, X):
 class Engine:
     """One handle == one device, one model spec, one training set."""
 
-    def __init__(self, spec: ModelSpec, X, y, device=None, grad_kernel: str = 'auto'):
+    def __init__(self, spec: ModelSpec, X, y, device=None, grad_kernel: str = 'auto', tables=None):
+        """tables: (emb, pos) of a PretrainedAttentionSpec; None loads them from spec.emb_path (spec.load_tables)."""
         if not torch.cuda.is_available():
             raise _lib.MileHipError('mile_amd needs an MI355X (torch.cuda.is_available() is False); '
                                     'there is no CPU fallback.')
@@ -89,8 +90,8 @@ class Engine:
         if isinstance(spec, IMAGE_SPECS):
             cs.model = 2 if isinstance(spec, LeNettiSpec) else 1
             cs.img_c, cs.img_h, cs.img_w = spec.channels, spec.height, spec.width
-        if isinstance(spec, AttentionSpec):
-            cs.model = 3
+        if isinstance(spec, (AttentionSpec, PretrainedAttentionSpec)):
+            cs.model = _lib.MODEL_IDS['attn_pretrained' if isinstance(spec, PretrainedAttentionSpec) else 'attn']
             cs.vocab_size, cs.ctx_len, cs.emb_size = spec.vocab_size, spec.context_len, spec.emb_size
             cs.n_heads, cs.qkv_dim = spec.n_heads, spec.qkv_dim
         cs.n_layers = len(spec.hidden_structure)
@@ -110,6 +111,8 @@ class Engine:
         self.d = int(self.lib.mile_param_count(h))
         assert self.d == spec.n_params
         self._E_reserved = 0
+        if isinstance(spec, PretrainedAttentionSpec):
+            self.set_embedding(*(tables if tables is not None else spec.load_tables()))
         self.set_data(X, y)
         if grad_kernel != 'auto':
             self.set_grad_kernel(grad_kernel)
@@ -151,6 +154,16 @@ class Engine:
         if int(X.shape[0]) != getattr(self, 'N', None):
             self._E_reserved = 0            # (same N: the library keeps its buffers and workspace)
         self.N = int(X.shape[0])
+
+    def set_embedding(self, emb, pos):
+        """The frozen tables of a PretrainedAttentionSpec: emb [V, C] and pos [>= T, C] (its first T rows are used), validated
+        by spec.check_tables and copied into the library's own buffers."""
+        emb, pos = self.spec.check_tables(emb, pos)
+        emb = torch.from_numpy(emb).to(self.device)
+        pos = torch.from_numpy(pos).to(self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_set_embedding(self._h, _ptr(emb), _ptr(pos), self._stream()), self.lib)
+            torch.cuda.current_stream(self.device).synchronize()   # emb, pos are temporaries
 
     def set_row_window(self, begin: int = 0, count: int = 0):
         """Likelihood over rows [begin, begin + count) of the training set for the following logpost_grad calls

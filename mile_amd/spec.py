@@ -8,6 +8,8 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
+import numpy as np
+
 ACTIVATIONS = ('relu', 'tanh', 'sigmoid')
 TASKS = ('regr', 'classification')
 PRIORS = ('Normal', 'StandardNormal', 'Laplace')
@@ -374,4 +376,157 @@ class AttentionSpec:
         return 3 * fwd
 
 
-NATIVE_SPECS = IMAGE_SPECS + (AttentionSpec,)
+
+# shapes the PretrainedAttentionClassifier kernel (mile_amd/csrc/mile_attn_pre.h) supports
+ATTNP_MAX_C = 192
+ATTNP_MAX_D = 128
+ATTNP_MAX_P = 128
+
+
+def attn_pre_lds_bytes(T: int, C: int, H: int, D: int, projection_dim=()) -> int:
+    """LDS of one k_grad_attn_pre workgroup (attnp_lds_bytes in mile_attn_pre.h): q|k|v [Tp][3D], a scratch that holds
+    e [Tp][C] or the busy waves' dS | u | dK, and the tail vectors."""
+    Tp, hd = (T + 15) // 16 * 16, D // H
+    P = tuple(projection_dim)
+    per_wave = 17 * Tp + (Tp * ((hd + 15) // 16 * 16) if hd > 16 else 0)
+    scr = max(Tp * C, min(H, 4) * per_wave)
+    W = max((C,) + P)
+    vec = Tp + 2 * D + C + 2 * sum(P) + (P[-1] if P else C) + 2 * W + 16
+    return 4 * (Tp * 3 * D + scr + vec)
+
+
+def pretrained_table_paths(emb_path) -> tuple[str, str]:
+    """The token table's path and the position table's: PretrainedTokenEmbedding's plain str.replace('emb', 'pos_emb')
+    over the WHOLE path (src/flax_building_blocks/basic.py:129-135), so every 'emb' in it is rewritten, directories included:
+    'results/emb.npy' -> 'results/pos_emb.npy', 'emb_large.npy' -> 'pos_emb_large.npy'."""
+    emb_path = str(emb_path)
+    return emb_path, emb_path.replace('emb', 'pos_emb')
+
+
+@dataclass(frozen=True)
+class PretrainedAttentionSpec:
+    """PretrainedAttentionClassifier (src/models/text/attention_classifier.py:74-132, PretrainedAttentionClassifierConfig
+    src/config/models/gpt.py:55-61) on [N, T] token ids (pad id 0): e = emb[x] + pos[0..T) from frozen tables (`emb_path` and
+    its pos_emb twin, see pretrained_table_paths) - MultiHeadDotProductAttention 'MDPA' - mean over the T positions -
+    (Dense P_i - gelu) per projection - gelu - Dense n_classes 'classifier'.  The tables are not parameters: they are neither
+    sampled nor in the prior.  Duck-types ModelSpec as AttentionSpec does."""
+
+    vocab_size: int
+    context_len: int
+    emb_size: int
+    n_heads: int
+    qkv_dim: int
+    n_classes: int = 2
+    projection_dim: tuple = (32,)
+    use_bias: bool = False
+    emb_path: str | None = None
+    activation: str = 'relu'          # unused: the projections use gelu; kept for the ModelSpec interface
+    task: str = 'classification'
+    prior: str = 'StandardNormal'
+    prior_loc: float = 0.0
+    prior_scale: float = 1.0
+    root: str = ''
+
+    def __post_init__(self):
+        object.__setattr__(self, 'projection_dim', tuple(int(p) for p in self.projection_dim))
+        name = 'PretrainedAttentionClassifier'
+        if self.task != 'classification':
+            raise NotImplementedError(f'{name}: classification only')
+        if self.prior not in PRIORS:
+            raise NotImplementedError(f'Prior Distribution for {self.prior} is not yet implemented.')
+        if self.prior == 'StandardNormal':
+            object.__setattr__(self, 'prior_loc', 0.0)
+            object.__setattr__(self, 'prior_scale', 1.0)
+        V, T, C, H, D, K = self.vocab_size, self.context_len, self.emb_size, self.n_heads, self.qkv_dim, self.n_classes
+        if min(V, T, C, H, D, K) < 1 or any(p < 1 for p in self.projection_dim):
+            raise ValueError(f'{name}: all sizes must be >= 1')
+        if D % H:
+            raise ValueError(f'{name}: n_heads ({H}) must divide qkv_dim ({D})')
+        limits = ((T, ATTN_MAX_T, 'context_len'), (C, ATTNP_MAX_C, 'emb_size'), (D, ATTNP_MAX_D, 'qkv_dim'),
+                  (K, ATTN_MAX_K, 'n_classes'))
+        for v, top, what in limits:
+            if v > top:
+                raise NotImplementedError(f'{name}: {what} = {v}, the HIP kernel takes at most {top}')
+        if len(self.projection_dim) > ATTN_MAX_PROJ:
+            raise NotImplementedError(f'{name}: at most {ATTN_MAX_PROJ} projection layers on the HIP kernel')
+        if any(p > ATTNP_MAX_P for p in self.projection_dim):
+            raise NotImplementedError(f'{name}: projection widths <= {ATTNP_MAX_P} on the HIP kernel')
+        if V >= 1 << 24:
+            raise NotImplementedError(f'{name}: vocab_size < 2^24 (token ids travel as fp32)')
+        if self.lds_bytes > ATTN_LDS_MAX:
+            raise NotImplementedError(f'{name}: this shape needs {self.lds_bytes} bytes of LDS per workgroup, the HIP kernel '
+                                      f'has {ATTN_LDS_MAX} (q|k|v [T][3D] and e [T][C] share it)')
+
+    @property
+    def in_features(self) -> int:
+        return self.context_len
+
+    @property
+    def head_dim(self) -> int:
+        return self.qkv_dim // self.n_heads
+
+    @property
+    def hidden_structure(self):
+        return self.projection_dim + (self.n_classes,)
+
+    def leaves(self):
+        """[(dotted name, offset, shape)] in ravel_pytree order: AttentionSpec's without the TokenEmbedding_0 tables."""
+        full = AttentionSpec.leaves(self)
+        out, off = [], 0
+        for name, _, sh in full:
+            if 'TokenEmbedding_0.' in name:
+                continue
+            out.append((name, off, sh))
+            off += int(np.prod(sh))
+        return out
+
+    @property
+    def n_params(self) -> int:
+        name, off, sh = self.leaves()[-1]
+        return off + int(np.prod(sh))
+
+    @property
+    def lds_bytes(self) -> int:
+        return attn_pre_lds_bytes(self.context_len, self.emb_size, self.n_heads, self.qkv_dim, self.projection_dim)
+
+    @property
+    def flops_per_sequence(self) -> int:
+        """3 x AttentionSpec's forward, minus the 2 T C 3D input-gradient product a frozen table does not need."""
+        T, C, D = self.context_len, self.emb_size, self.qkv_dim
+        dims = (C,) + self.hidden_structure
+        fwd = 2 * T * C * 3 * D + 4 * T * T * D + 2 * T * D * C + sum(2 * a * b for a, b in zip(dims[:-1], dims[1:]))
+        return 3 * fwd - 2 * T * C * 3 * D
+
+    def table_paths(self) -> tuple[str, str]:
+        if not self.emb_path:
+            raise ValueError('PretrainedAttentionClassifier needs emb_path (the .npy token table; tools/make_embeddings.py '
+                             'writes one)')
+        return pretrained_table_paths(self.emb_path)
+
+    def check_tables(self, emb, pos) -> tuple[np.ndarray, np.ndarray]:
+        """emb [V, C] and the first T rows of pos [>= T, C], as contiguous fp32 arrays."""
+        V, T, C = self.vocab_size, self.context_len, self.emb_size
+        emb = np.ascontiguousarray(np.asarray(emb), dtype=np.float32)
+        pos = np.asarray(pos)
+        if emb.shape != (V, C):
+            raise ValueError(f'embedding table: expected [vocab_size, emb_size] = [{V}, {C}], got {list(emb.shape)}')
+        if pos.ndim != 2 or pos.shape[0] < T or pos.shape[1] != C:
+            raise ValueError(f'position table: expected at least {T} rows (context_len) of emb_size = {C}, got {list(pos.shape)}')
+        if not (np.isfinite(emb).all() and np.isfinite(pos[:T]).all()):
+            raise ValueError('embedding tables must be finite')
+        return emb, np.ascontiguousarray(pos[:T], dtype=np.float32)
+
+    def load_tables(self) -> tuple[np.ndarray, np.ndarray]:
+        """The one loader: np.load of both paths (pretrained_table_paths), validated and cast by check_tables."""
+        emb_path, pos_path = self.table_paths()
+        tables = []
+        for what, path in (('embedding', emb_path), ('position', pos_path)):
+            try:
+                tables.append(np.load(path))
+            except FileNotFoundError as exc:
+                raise FileNotFoundError(f'{what} table {path!r} not found (emb_path {self.emb_path!r}; tools/make_embeddings.py '
+                                        'writes both tables)') from exc
+        return self.check_tables(*tables)
+
+
+NATIVE_SPECS = IMAGE_SPECS + (AttentionSpec, PretrainedAttentionSpec)

@@ -23,7 +23,7 @@ from mile_amd.config import Config
 from mile_amd.dataset import ImageLoader, TabularLoader, TextLoader
 from mile_amd.probabilistic import ProbabilisticModel
 from mile_amd.sampling import inference_loop, join_without_chains
-from mile_amd.spec import AttentionSpec, LeNetSpec, LeNettiSpec, ModelSpec
+from mile_amd.spec import AttentionSpec, LeNetSpec, LeNettiSpec, ModelSpec, PretrainedAttentionSpec
 from mile_amd.tree import PRNGKey
 
 logger = logging.getLogger(__name__)
@@ -82,19 +82,24 @@ class BDETrainer:
     def build_model(self, config: Config):
         """Data loader, model spec and probabilistic model of a config (also used by evaluate.py)."""
         task = 'regr' if config.data.task == 'regr' else 'classification'
-        if config.model.model == 'AttentionClassifier':
+        if config.model.model in ('AttentionClassifier', 'PretrainedAttentionClassifier'):
             if config.data.data_type != 'text':
-                raise ValueError('model AttentionClassifier needs data_type: text')
+                raise ValueError(f'model {config.model.model} needs data_type: text')
             if task != 'classification':
-                raise NotImplementedError('AttentionClassifier: classification only')
+                raise NotImplementedError(f'{config.model.model}: classification only')
             if config.training.tokenizer is not None:
                 logger.warning('training.tokenizer is ignored: text data comes as token ids (synthetic or .npz)')
             m = config.model
             self.loader = TextLoader(config.data, rng=config.rng, context_len=m.context_len, vocab_size=m.vocab_size,
                                      n_classes=m.n_classes)
-            self.spec_model = AttentionSpec(vocab_size=m.vocab_size, context_len=m.context_len, emb_size=m.emb_size,
-                                            n_heads=m.n_heads, qkv_dim=m.qkv_dim, n_classes=m.n_classes,
-                                            projection_dim=tuple(m.projection_dim), use_bias=m.bias, task=task)
+            kw = dict(vocab_size=m.vocab_size, context_len=m.context_len, emb_size=m.emb_size, n_heads=m.n_heads,
+                      qkv_dim=m.qkv_dim, n_classes=m.n_classes, projection_dim=tuple(m.projection_dim), use_bias=m.bias,
+                      task=task)
+            if m.model == 'PretrainedAttentionClassifier':
+                self.spec_model = PretrainedAttentionSpec(emb_path=m.emb_path, **kw)
+                self.spec_model.load_tables()               # fail here, with the paths, rather than at the first engine
+            else:
+                self.spec_model = AttentionSpec(**kw)
         elif config.model.model in ('LeNet', 'LeNetti'):
             if config.data.data_type != 'image':
                 raise ValueError(f'model {config.model.model} needs data_type: image')
