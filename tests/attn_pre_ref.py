@@ -15,10 +15,10 @@ EMB = 'TokenEmbedding_0.Embedding.embedding'
 POS = 'TokenEmbedding_0.PositionEmbedding.embedding'
 
 
-def params(spec, theta, emb, pos):
-    P = A.unpack(spec, theta)
-    P[EMB] = np.asarray(emb, dtype=np.float64)
-    P[POS] = np.asarray(pos, dtype=np.float64)[:spec.context_len]
+def params(spec, theta, emb, pos, dtype=np.float64):
+    P = A.unpack(spec, theta, dtype)
+    P[EMB] = np.asarray(emb, dtype=dtype)
+    P[POS] = np.asarray(pos, dtype=dtype)[:spec.context_len]
     return P
 
 
@@ -41,11 +41,11 @@ def pointwise_loglik(spec, theta, emb, pos, x, y):
     return lsm[np.arange(len(lsm)), np.asarray(y, dtype=np.int64)]
 
 
-def loglik_and_grad(spec, theta, emb, pos, x, y):
-    """sum_n log p(y_n | x_n, theta) and its gradient (flat, spec.leaves() order)."""
+def loglik_and_grad(spec, theta, emb, pos, x, y, dtype=np.float64, mutant=None):
+    """sum_n log p(y_n | x_n, theta) and its gradient (flat, spec.leaves() order); `dtype` and `mutant` as in attn_ref."""
     x = np.asarray(x, dtype=np.int64)
     y = np.asarray(y, dtype=np.int64)
-    P = params(spec, theta, emb, pos)
+    P = params(spec, theta, emb, pos, dtype)
     f = forward(spec, P, x)
     N, T = x.shape
     C, H, D, hd = spec.emb_size, spec.n_heads, spec.qkv_dim, f['hd']
@@ -71,29 +71,32 @@ def loglik_and_grad(spec, theta, emb, pos, x, y):
     if b:
         G['MDPA.out.bias'] = dout.sum((0, 1))
     do = (dout @ f['Wo'].T).reshape(N, T, H, hd).transpose(0, 2, 1, 3)
-    p, vh, qh, kh = f['p'], f['v'], f['q'], f['k']
-    dv = p.transpose(0, 1, 3, 2) @ do
-    dp = do @ vh.transpose(0, 1, 3, 2)
-    ds = np.where(f['mask'], p * (dp - (dp * p).sum(-1, keepdims=True)), 0.0)
-    dq = (ds @ kh) / np.sqrt(hd)
-    dk = ds.transpose(0, 1, 3, 2) @ qh
-    merge = lambda t: t.transpose(0, 2, 1, 3).reshape(N, T, D)      # noqa: E731
-    for name, dX in (('query', merge(dq)), ('key', merge(dk)), ('value', merge(dv))):
+    dq, dk, dv = A.attention_backward(f, do, mutant)
+    for name, dX in (('query', dq), ('key', dk), ('value', dv)):
         G[f'MDPA.{name}.kernel'] = np.einsum('ntc,ntd->cd', f['e'], dX).reshape(C, H, hd)
         if b:
             G[f'MDPA.{name}.bias'] = dX.sum((0, 1)).reshape(H, hd)
+    if mutant == 'zero_qk_kernels':
+        G['MDPA.query.kernel'][:] = 0
+        G['MDPA.key.kernel'][:] = 0
     flat = np.concatenate([G[n].reshape(-1) for n, _, _ in spec.leaves()])
+    assert flat.dtype == np.dtype(dtype) and f['p'].dtype == flat.dtype and f['logits'].dtype == flat.dtype
     return ll, flat
 
 
-def logpost_and_grad(spec, theta, emb, pos, x, y):
+def loglik_grad(spec, theta, emb, pos, x, y, dtype=np.float64, mutant=None):
+    """The likelihood's gradient alone for an ensemble: theta [E, d] -> [E, d]."""
+    return np.stack([loglik_and_grad(spec, t, emb, pos, x, y, dtype, mutant)[1] for t in np.asarray(theta)])
+
+
+def logpost_and_grad(spec, theta, emb, pos, x, y, dtype=np.float64, mutant=None):
     """log_unnormalized_posterior and its gradient for an ensemble: theta [E, d] -> (logp [E], grad [E, d]).  The prior
     covers the sampled leaves only."""
     from oracle import mclmc_oracle as M
-    theta = np.asarray(theta, dtype=np.float64)
-    lls, gs = zip(*(loglik_and_grad(spec, t, emb, pos, x, y) for t in theta))
+    theta = np.asarray(theta, dtype=dtype)
+    lls, gs = zip(*(loglik_and_grad(spec, t, emb, pos, x, y, dtype, mutant) for t in theta))
     lp, gp = M.log_prior(spec, theta)
-    return np.asarray(lls) + lp, np.stack(gs) + gp
+    return np.asarray(lls, dtype=dtype) + lp, np.stack(gs) + gp
 
 
 def tables(spec, seed: int = 0, extra_pos_rows: int = 0):
@@ -108,5 +111,12 @@ def tables(spec, seed: int = 0, extra_pos_rows: int = 0):
 def synthetic_problem(spec, N: int, E: int, seed: int = 0) -> dict:
     """attn_ref.synthetic_problem's rows, labels and parameters (the sampled leaves), plus the tables."""
     prob = A.synthetic_problem(spec, N, E, seed)
+    prob['emb'], prob['pos'] = tables(spec, seed)
+    return prob
+
+
+def sharp_problem(spec, N: int, E: int, seed: int = 0, qk_scale: float | None = None) -> dict:
+    """attn_ref.sharp_problem (sharp attention, for a wide prior), plus the tables."""
+    prob = A.sharp_problem(spec, N, E, seed, qk_scale)
     prob['emb'], prob['pos'] = tables(spec, seed)
     return prob

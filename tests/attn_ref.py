@@ -11,16 +11,23 @@ recalled and pinned as choices):
 - out = DenseGeneral([H, hd] -> C); mean over all T positions (pads included).
 - per projection: Dense then gelu (tanh approximation); classifier Dense(n_classes); categorical log-likelihood.
 Parameters are the flat vector of AttentionSpec.leaves().
+
+The gradient functions take `dtype`: float64 is the reference; float32 evaluates the same formulas in float32 throughout (constants
+are Python floats, so nothing is promoted), which gives the rounding error a float32 implementation of these formulas has
+before any change of summation order (tests/leafcheck.py's bound for a leaf that does not meet its fixed tolerance).
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
-SQ2PI = np.sqrt(2.0 / np.pi)
+SQ2PI = math.sqrt(2.0 / math.pi)
+MUTANTS = ('zero_qk_kernels', 'dq_unscaled', 'ds_unmasked')     # wrong gradients for tests/test_leafcheck_host.py
 
 
-def unpack(spec, theta):
-    th = np.asarray(theta, dtype=np.float64)
+def unpack(spec, theta, dtype=np.float64):
+    th = np.asarray(theta, dtype=dtype)
     return {n: th[o:o + int(np.prod(s))].reshape(s) for n, o, s in spec.leaves()}
 
 
@@ -46,13 +53,14 @@ def _forward(spec, P, x):
     q = e @ Wq + (P['MDPA.query.bias'].reshape(D) if b else 0.0)
     k = e @ Wk + (P['MDPA.key.bias'].reshape(D) if b else 0.0)
     v = e @ Wv + (P['MDPA.value.bias'].reshape(D) if b else 0.0)
-    qh = (q / np.sqrt(hd)).reshape(N, T, H, hd).transpose(0, 2, 1, 3)
+    qh = (q / math.sqrt(hd)).reshape(N, T, H, hd).transpose(0, 2, 1, 3)
     kh = k.reshape(N, T, H, hd).transpose(0, 2, 1, 3)
     vh = v.reshape(N, T, H, hd).transpose(0, 2, 1, 3)
     s = qh @ kh.transpose(0, 1, 3, 2)                                # [N, H, T, T]
     tokm = x != 0
     mask = (tokm[:, :, None] & tokm[:, None, :])[:, None]
-    s = np.where(mask, s, np.finfo(np.float32).min)
+    s = np.where(mask, s, e.dtype.type(np.finfo(np.float32).min))
+    raw = s
     s = s - s.max(axis=-1, keepdims=True)
     p = np.exp(s)
     p /= p.sum(axis=-1, keepdims=True)
@@ -68,7 +76,7 @@ def _forward(spec, P, x):
         zs.append(z)
         gs.append(gp)
     logits = z @ P['classifier.kernel'] + (P['classifier.bias'] if b else 0.0)
-    return dict(e=e, q=qh, k=kh, v=vh, p=p, mask=mask, oc=oc, zs=zs, gs=gs, logits=logits, Wq=Wq, Wk=Wk, Wv=Wv, Wo=Wo,
+    return dict(e=e, s=raw, q=qh, k=kh, v=vh, p=p, mask=mask, oc=oc, zs=zs, gs=gs, logits=logits, Wq=Wq, Wk=Wk, Wv=Wv, Wo=Wo,
                 hd=hd, tokm=tokm)
 
 
@@ -82,11 +90,30 @@ def pointwise_loglik(spec, theta, x, y):
     return lg[np.arange(len(lg)), np.asarray(y, dtype=np.int64)] - lse
 
 
-def loglik_and_grad(spec, theta, x, y):
+def attention_backward(f, do, mutant=None):
+    """d(q, k, v) [N, T, D] (before the Dense layers) from d(o) [N, H, T, hd] and the forward's intermediates.  `mutant` builds
+    one of the wrong gradients of MUTANTS (the 1/sqrt(hd) of dq left out, the mask on ds left out)."""
+    assert mutant is None or mutant in MUTANTS, mutant
+    p, vh, qh, kh, hd = f['p'], f['v'], f['q'], f['k'], f['hd']
+    N, H, T, _ = p.shape
+    dv = p.transpose(0, 1, 3, 2) @ do
+    dp = do @ vh.transpose(0, 1, 3, 2)
+    ds = p * (dp - (dp * p).sum(-1, keepdims=True))
+    if mutant != 'ds_unmasked':
+        ds = np.where(f['mask'], ds, 0.0)                           # where() drops the masked entries' gradient
+    dq = ds @ kh
+    if mutant != 'dq_unscaled':
+        dq = dq / math.sqrt(hd)
+    dk = ds.transpose(0, 1, 3, 2) @ qh
+    merge = lambda t: t.transpose(0, 2, 1, 3).reshape(N, T, H * hd)      # noqa: E731
+    return merge(dq), merge(dk), merge(dv)
+
+
+def loglik_and_grad(spec, theta, x, y, dtype=np.float64, mutant=None):
     """sum_n log p(y_n | x_n, theta) and its gradient (flat, spec.leaves() order)."""
     x = np.asarray(x, dtype=np.int64)
     y = np.asarray(y, dtype=np.int64)
-    P = unpack(spec, theta)
+    P = unpack(spec, theta, dtype)
     f = _forward(spec, P, x)
     N, T = x.shape
     C, H, D, hd = spec.emb_size, spec.n_heads, spec.qkv_dim, f['hd']
@@ -115,16 +142,7 @@ def loglik_and_grad(spec, theta, x, y):
     if b:
         G['MDPA.out.bias'] = dout.sum((0, 1))
     doc = dout @ f['Wo'].T                                           # [N, T, D]
-    do = doc.reshape(N, T, H, hd).transpose(0, 2, 1, 3)
-    p, vh, qh, kh = f['p'], f['v'], f['q'], f['k']
-    dv = p.transpose(0, 1, 3, 2) @ do
-    dp = do @ vh.transpose(0, 1, 3, 2)
-    ds = p * (dp - (dp * p).sum(-1, keepdims=True))
-    ds = np.where(f['mask'], ds, 0.0)                               # where() drops the masked entries' gradient
-    dq = (ds @ kh) / np.sqrt(hd)
-    dk = ds.transpose(0, 1, 3, 2) @ qh
-    merge = lambda t: t.transpose(0, 2, 1, 3).reshape(N, T, D)      # noqa: E731
-    dq, dk, dv = merge(dq), merge(dk), merge(dv)
+    dq, dk, dv = attention_backward(f, doc.reshape(N, T, H, hd).transpose(0, 2, 1, 3), mutant)
     e = f['e']
     for name, dX, W in (('query', dq, f['Wq']), ('key', dk, f['Wk']), ('value', dv, f['Wv'])):
         G[f'MDPA.{name}.kernel'] = np.einsum('ntc,ntd->cd', e, dX).reshape(C, H, hd)
@@ -133,17 +151,38 @@ def loglik_and_grad(spec, theta, x, y):
     de = dq @ f['Wq'].T + dk @ f['Wk'].T + dv @ f['Wv'].T            # [N, T, C]
     np.add.at(G['TokenEmbedding_0.Embedding.embedding'], x.reshape(-1), de.reshape(-1, C))
     G['TokenEmbedding_0.PositionEmbedding.embedding'] = de.sum(0)
+    if mutant == 'zero_qk_kernels':
+        G['MDPA.query.kernel'][:] = 0
+        G['MDPA.key.kernel'][:] = 0
     flat = np.concatenate([G[n].reshape(-1) for n, _, _ in spec.leaves()])
+    assert flat.dtype == np.dtype(dtype) and f['p'].dtype == flat.dtype and lg.dtype == flat.dtype
     return ll, flat
 
 
-def logpost_and_grad(spec, theta, x, y):
+def loglik_grad(spec, theta, x, y, dtype=np.float64, mutant=None):
+    """The likelihood's gradient alone for an ensemble: theta [E, d] -> [E, d]."""
+    return np.stack([loglik_and_grad(spec, t, x, y, dtype, mutant)[1] for t in np.asarray(theta)])
+
+
+def logpost_and_grad(spec, theta, x, y, dtype=np.float64, mutant=None):
     """log_unnormalized_posterior and its gradient for an ensemble: theta [E, d] -> (logp [E], grad [E, d])."""
     from oracle import mclmc_oracle as M
-    theta = np.asarray(theta, dtype=np.float64)
-    lls, gs = zip(*(loglik_and_grad(spec, t, x, y) for t in theta))
+    theta = np.asarray(theta, dtype=dtype)
+    lls, gs = zip(*(loglik_and_grad(spec, t, x, y, dtype, mutant) for t in theta))
     lp, gp = M.log_prior(spec, theta)
-    return np.asarray(lls) + lp, np.stack(gs) + gp
+    return np.asarray(lls, dtype=dtype) + lp, np.stack(gs) + gp
+
+
+def attention_stats(spec, P, x):
+    """What makes a problem exercise the softmax, from the forward alone: the median over real query rows and heads of the largest
+    attention weight, the smallest weight of an unmasked entry relative to its row's largest, and the largest |logit|."""
+    f = _forward(spec, P, np.asarray(x, dtype=np.int64))
+    p, m = f['p'], f['mask']
+    real = np.broadcast_to(f['tokm'][:, None, :], p.shape[:3])
+    top = p.max(axis=-1)
+    rel = np.where(np.broadcast_to(m, p.shape), p / top[..., None], 1.0)
+    return {'median_top': float(np.median(top[real])), 'min_rel': float(rel.min()),
+            'max_logit': float(np.abs(np.where(np.broadcast_to(m, p.shape), f['s'], 0.0)).max())}
 
 
 def synthetic_problem(spec, N: int, E: int, seed: int = 0) -> dict:
@@ -177,3 +216,19 @@ def synthetic_problem(spec, N: int, E: int, seed: int = 0) -> dict:
     return {'X': x.astype(np.float32), 'x': x, 'y': y, 'theta0': theta, 'u0': rng.standard_normal((E, d)).astype(np.float32),
             'eps': (1e-3 * (1 + 0.05 * rng.uniform(-1, 1, E))).astype(np.float32),
             'L': (np.sqrt(d) * 1e-2 * (1 + 0.05 * rng.uniform(-1, 1, E))).astype(np.float32)}
+
+
+def sharp_problem(spec, N: int, E: int, seed: int = 0, qk_scale: float | None = None) -> dict:
+    """synthetic_problem's rows, labels and parameters with the query and key kernels scaled up so that attention is sharp: the
+    softmax's max-subtraction, the 1/sqrt(hd) scale and the softmax backward carry the gradient, which synthetic_problem's
+    near-uniform weights (scores of size 2 / C) do not ask of them.  With embeddings of variance 1 / C per entry (token + position:
+    |e|^2 = 2) and lecun-normal kernels, a score q.k / sqrt(hd) has standard deviation 2 a^2 / C under a scale a on both kernels,
+    whatever hd is; the default a = sqrt(2 C) puts it at 4.  Meant for a wide prior (`prior_scale` large), so that every leaf's
+    gradient is the likelihood's."""
+    prob = synthetic_problem(spec, N, E, seed)
+    a = math.sqrt(2.0 * spec.emb_size) if qk_scale is None else float(qk_scale)
+    for n, o, sh in spec.leaves():
+        if n.endswith(('MDPA.query.kernel', 'MDPA.key.kernel')):
+            prob['theta0'][:, o:o + int(np.prod(sh))] *= np.float32(a)
+    prob['qk_scale'] = a
+    return prob

@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+from tests import leafcheck as L
 from tests import lenetti_ref as R
 from tests import nuts_ref as NR
 
@@ -58,6 +59,7 @@ def test_logpost_grad_matches_restatement(C, H, W, K, act, task, prior, N, E):
     lp, g = eng.logpost_grad(torch.from_numpy(prob['theta0']))
     torch.cuda.synchronize()
     _check(lp, g, lp_ref, g_ref)
+    L.assert_leaves(g.cpu().numpy(), g_ref, L.spec_leaves(ospec), tag=(C, H, W, K, act))     # leaf by leaf: 5e-5 of the leaf's largest entry
 
 
 def test_row_splits_and_windows():

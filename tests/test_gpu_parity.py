@@ -4,6 +4,8 @@ import math
 import numpy as np
 import pytest
 
+from tests import leafcheck as L
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip('torch')
@@ -98,6 +100,7 @@ def test_logpost_grad_matches_oracle(oracle, F, hs, act, task, prior, N, E, kern
         if near.any() and near.sum() < N:
             prob = dict(prob, X=np.ascontiguousarray(prob['X'][~near]), y=np.ascontiguousarray(prob['y'][~near]))
     lp_ref, g_ref = oracle.logpost_and_grad(ospec, prob['theta0'].astype(np.float64), prob['X'], prob['y'])
+    leaves = L.fcn_leaves(ospec)
     for k in kernels:
         eng = _engine(oracle, ospec, prob, k)
         wide = max(hs[:-1], default=0) >= 96
@@ -107,6 +110,7 @@ def test_logpost_grad_matches_oracle(oracle, F, hs, act, task, prior, N, E, kern
         # fp32 accumulation over N rows vs fp64: tolerance 2e-5 relative to the largest entry
         assert _relerr(lp.cpu().numpy(), lp_ref) < 2e-5, k
         assert _relerr(g.cpu().numpy(), g_ref) < 2e-5, k
+        L.assert_leaves(g.cpu().numpy(), g_ref, leaves, tag=(k, F, hs, act, N, E))       # leaf by leaf: 5e-5 of the leaf's largest entry
 
 
 def test_narrow_kernel_on_random_specs(oracle):
