@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MILE_ABI_VERSION 9
+#define MILE_ABI_VERSION 10
 #define MILE_MAX_LAYERS 16
 
 typedef enum mile_status {
@@ -90,18 +90,26 @@ typedef enum mile_grad_kernel {
                                      C <= 64, D <= 64 with H | D, <= 2 projections of width <= 64, n_classes <= 16, and
                                      <= 160 KB of LDS per workgroup (refused otherwise: H = 3, D in {57, 60, 63} with
                                      T > 112) */
-  MILE_GRAD_ATTN_PRE_F32 = 13     /* MILE_MODEL_ATTN_PRETRAINED only (and its only kernel; AUTO resolves to it): one fused fp32
+  MILE_GRAD_ATTN_PRE_F32 = 13,    /* MILE_MODEL_ATTN_PRETRAINED only (and its only kernel; AUTO resolves to it): one fused fp32
                                      forward + backward launch, k_grad_attn_pre (mile_attn_pre.h), products on
                                      v_mfma_f32_16x16x4_f32, weights streamed from L2, gradients accumulated in the
                                      workgroup's own slab row; T <= 128, C <= 192, D <= 128 with H | D, <= 2 projections of
                                      width <= 128, n_classes <= 16, and <= 160 KB of LDS per workgroup (q|k|v [Tp][3D] + e
                                      [Tp][C] + vectors: e.g. C = 192, D = 64 needs T <= 96) */
+  MILE_GRAD_ATTN_WIDE_F32 = 14    /* MILE_MODEL_ATTN_WIDE only (and its only kernel; AUTO resolves to it): k_grad_attn_wide
+                                     (mile_attn_wide.h), the ATTN_PRE_F32 kernel with the tables read from the chain's own
+                                     parameters and their gradient added (dPos by owner threads, dEmb by fp32 vector atomics
+                                     into the slab row's own [V][C] block); the same envelope and LDS as ATTN_PRE_F32.  Its
+                                     row ranges are sized for that block (4 V C bytes per slab row), see mile_reserve */
 } mile_grad_kernel;
 /* Which network: the FCN (src/models/tabular/fcn.py:16-28), LeNet (src/models/images/cnns.py:10-66), LeNetti
  * (src/models/images/cnns.py:69-121), AttentionClassifier (src/models/text/attention_classifier.py) or
- * PretrainedAttentionClassifier (attention_classifier.py:74-132: frozen embedding tables, see mile_set_embedding). */
+ * PretrainedAttentionClassifier (attention_classifier.py:74-132: frozen embedding tables, see mile_set_embedding).
+ * ATTN_WIDE is the AttentionClassifier again, on the kernel that streams its weights (emb_size <= 192, qkv_dim <= 128,
+ * projections <= 128: the reference's pretraining shapes); ATTN keeps the on-chip kernel and its limits. */
 typedef enum mile_model {
-  MILE_MODEL_FCN = 0, MILE_MODEL_LENET = 1, MILE_MODEL_LENETTI = 2, MILE_MODEL_ATTN = 3, MILE_MODEL_ATTN_PRETRAINED = 4
+  MILE_MODEL_FCN = 0, MILE_MODEL_LENET = 1, MILE_MODEL_LENETTI = 2, MILE_MODEL_ATTN = 3, MILE_MODEL_ATTN_PRETRAINED = 4,
+  MILE_MODEL_ATTN_WIDE = 5
 } mile_model;
 
 /* FCNConfig (src/config/models/fcn.py:7-30) + PriorConfig (src/config/sampler.py:60-95)
@@ -131,7 +139,9 @@ typedef struct mile_model_spec {
                                       * classifier [P_last,K], projection_0 [C,P_0], projection_1 [P_0,P_1].
                                       * ATTN_PRETRAINED: the same geometry fields and conventions; one more gelu before
                                       * the classifier; no TokenEmbedding_0 leaves (the tables are not parameters: they
-                                      * come from mile_set_embedding) */
+                                      * come from mile_set_embedding).
+                                      * ATTN_WIDE: ATTN's model, parameters and conventions exactly; only the limits
+                                      * differ (those of ATTN_PRETRAINED) */
   int32_t img_c;                     /* LENET / LENETTI image geometry (ignored for the FCN) */
   int32_t img_h;
   int32_t img_w;
@@ -272,7 +282,7 @@ int32_t mile_destroy(mile_sampler *s);
 int64_t mile_param_count(const mile_sampler *s);
 
 /* Offsets of layer `layer`'s bias and kernel inside the raveled vector (ravel_pytree order).  LENET: layers 0..4 = conv1, conv2,
- * fc1, fc2, fc3; LENETTI: layers 0..4 = conv1, fc1, fc2, fc3, fc4; ATTN: layers 0..3 = MDPA key, out, query, value,
+ * fc1, fc2, fc3; LENETTI: layers 0..4 = conv1, fc1, fc2, fc3, fc4; ATTN and ATTN_WIDE: layers 0..3 = MDPA key, out, query, value,
  * 4 = Embedding (kernel = the table, no bias), 5 = PositionEmbedding, 6 = classifier, 7.. = projection_0, projection_1;
  * ATTN_PRETRAINED: layers 0..3 = MDPA key, out, query, value, 4 = classifier, 5.. = projection_0, projection_1.
  * A missing bias (use_bias = 0) has offset -1. */
@@ -292,7 +302,7 @@ int32_t mile_set_embedding(mile_sampler *s, const float *emb, const float *pos, 
 /* Restrict the likelihood to rows [begin, begin + count) of the training set for the following mile_logpost_grad calls
  * (count = 0: all rows again).  Replaces the minibatches of the warm-start stage: loader.iter(split='train', batch_size=...)
  * (src/dataset/tabular.py:170-212) feeding single_step_regr / single_step_class (src/training/trainer.py:706-760).
- * Supported by MILE_GRAD_GENERIC, the MFMA_NARROW, MFMA_W64, MFMA_WIDE, LENET, LENETTI, ATTN and ATTN_PRE kernels (mile_logpost_grad fails with MILE_ERR_STATE on
+ * Supported by MILE_GRAD_GENERIC, the MFMA_NARROW, MFMA_W64, MFMA_WIDE, LENET, LENETTI and ATTN* kernels (mile_logpost_grad fails with MILE_ERR_STATE on
  * MFMA_W128_BF16 / GEMM_F32 under a window); the MCLMC path itself is full-batch (n_batches = 1). */
 int32_t mile_set_row_window(mile_sampler *s, int64_t begin, int64_t count);
 
@@ -304,8 +314,14 @@ int32_t mile_set_row_window(mile_sampler *s, int64_t begin, int64_t count);
 int32_t mile_warmstart_step(mile_sampler *s, float *theta, int32_t E, const mile_optim_args *args, void *stream);
 
 /* Size the internal workspace (partial-gradient slabs etc.) for ensembles of up to E
- * particles.  Allocation happens here, never inside a launch call. */
+ * particles.  Allocation happens here, never inside a launch call.  The slabs are [E, S, d] floats, S the row ranges of
+ * the grad kernel.  ATTN_WIDE: a slab row holds the [V][C] table block, and S is min(CUs / E, rows / 8) with no cap at 64
+ * -- at V = 10 000, C = 192 (d = 1 989 218) one chain on N >= 2048 rows reserves 256 rows = 2.04 GB, eight chains 8 x 32
+ * rows = 2.04 GB as well (mile_slab_bytes reports it).  S is the largest row-range count among the kernels that run the model. */
 int32_t mile_reserve(mile_sampler *s, int32_t E);
+
+/* Bytes of the [E, S, d] partial-gradient slabs the workspace holds now (0 before the first mile_reserve). */
+int64_t mile_slab_bytes(const mile_sampler *s);
 
 /* Select the grad kernel (default AUTO). */
 int32_t mile_set_grad_kernel(mile_sampler *s, int32_t which);

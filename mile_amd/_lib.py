@@ -7,7 +7,7 @@ from pathlib import Path
 from mile_amd._build import LIB_PATH
 
 MILE_MAX_LAYERS = 16
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 ACTIVATION_IDS = {'relu': 0, 'tanh': 1, 'sigmoid': 2}
 TASK_IDS = {'regr': 0, 'regression': 0, 'classification': 1, 'class': 1}
@@ -15,8 +15,8 @@ PRIOR_IDS = {'Normal': 0, 'StandardNormal': 0, 'Laplace': 1}
 REFRESH_IDS = {'O-step-O': 0, 'step-O': 1}
 GRAD_KERNEL_IDS = {'auto': 0, 'generic': 1, 'mfma_w64': 2, 'mfma_w128_bf16': 3, 'gemm_f32': 4, 'lenet_f32': 5, 'mfma_w64_bf16x3': 6,
                    'mfma_wide_bf16x3': 7, 'mfma_wide_bf16': 8, 'lenet_bf16': 9, 'mfma_narrow_f32': 10,
-                   'lenetti_f32': 11, 'attn_f32': 12, 'attn_pre_f32': 13}
-MODEL_IDS = {'fcn': 0, 'lenet': 1, 'lenetti': 2, 'attn': 3, 'attn_pretrained': 4}
+                   'lenetti_f32': 11, 'attn_f32': 12, 'attn_pre_f32': 13, 'attn_wide_f32': 14}
+MODEL_IDS = {'fcn': 0, 'lenet': 1, 'lenetti': 2, 'attn': 3, 'attn_pretrained': 4, 'attn_wide': 5}
 
 
 class ModelSpecC(C.Structure):
@@ -121,6 +121,7 @@ SIGNATURES = {
     'mile_set_embedding': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'mile_set_row_window': (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64]),
     'mile_reserve': (C.c_int32, [C.c_void_p, C.c_int32]),
+    'mile_slab_bytes': (C.c_int64, [C.c_void_p]),
     'mile_warmstart_step': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(OptimArgsC), C.c_void_p]),
     'mile_set_grad_kernel': (C.c_int32, [C.c_void_p, C.c_int32]),
     'mile_get_grad_kernel': (C.c_int32, [C.c_void_p]),

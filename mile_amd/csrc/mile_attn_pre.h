@@ -18,6 +18,8 @@
 //     per sequence and workgroup against 19 / 30 MFLOP of MFMA work.  The first sequence of a range writes instead of adding;
 //     an empty range writes zeros.
 // k_fwd_attn_pre is the forward half: per-row log-likelihoods for mile_pointwise_loglik.
+// The same body with WIDE set is the AttentionClassifier at these widths (mile_attn_wide.h): tables inside theta, their
+// gradient, no extra gelu.
 #pragma once
 #include "mile_attn.h"
 
@@ -71,7 +73,9 @@ __host__ __device__ inline size_t attnp_lds_bytes(const AttnGeom &g) {
 }
 
 // NHT: ceil(hd / 16) (dq register tiles; dK in registers for NHT == 1, in the wave's scratch otherwise)
-template <int NHT, bool GRAD>
+// WIDE: the AttentionClassifier of mile_attn_wide.h -- the tables are the chain's own parameters (g.emb / g.pos offsets into
+// theta, p.emb / p.pos unused), they get a gradient, and the classifier reads the last projection without the extra gelu
+template <int NHT, bool GRAD, bool WIDE = false>
 __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
   constexpr int NJ = ATTN_MAX_T / 16;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -82,6 +86,7 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
   const int T = g.T, C = g.C, H = g.H, D = g.D, hd = g.hd, K = g.K, NP = g.NP, Tp = g.Tp, V = g.V;
   const int ld = 3 * D, nj = Tp / 16, CT = (C + 15) / 16, ND = (D + 15) / 16;
   const float *th = p.theta + (size_t)e * g.d;
+  const float *embt = WIDE ? th + g.emb : p.emb, *post = WIDE ? th + g.pos : p.pos;   // token table [V][C], position rows [T][C]
   float *QKV = lds;                                  // [Tp][3D]: q | k | v columns
   float *scr = QKV + Tp * ld;                        // e [Tp][C], or per wave dS | u | dK
   float *vb = scr + attnp_scr_floats(g);
@@ -102,6 +107,7 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
   const float scale = 1.0f / sqrtf((float)hd), invT = 1.0f / (float)T;
   const int PL = NP > 0 ? Pw(NP - 1) : C;            // classifier input width
   const float *zL = zv(NP);                          // input of the extra gelu
+  const float *zc = WIDE ? zL : zf;                  // classifier input
 
   float *slab = GRAD ? p.slabs + ((size_t)e * p.S + s) * p.dp : nullptr;
   float ll_acc = 0.0f;
@@ -112,7 +118,7 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
   auto stage_e = [&]() {
     for (int i = tid; i < Tp * C; i += ATTN_NT) {
       const int t = i / C, c = i - t * C;
-      scr[i] = t < T ? p.emb[(size_t)tok[t] * C + c] + p.pos[t * C + c] : 0.0f;
+      scr[i] = t < T ? embt[(size_t)tok[t] * C + c] + post[t * C + c] : 0.0f;
     }
   };
   // slab[off + r nb + c] (+)= a[r] b[c] over [na][nb]: thread-owned flat entries
@@ -126,6 +132,15 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
       if (c >= nb) { c -= nb; ++r; }
     }
   };
+
+  if (GRAD && WIDE) {   // the table block of this slab row is reached by atomics: zero it first (16-byte stores between the ends)
+    float *blk = slab + g.emb;
+    const int n = V * C, head = min(n, (4 - (g.emb & 3)) & 3), nq = (n - head) >> 2;
+    for (int i = tid; i < nq; i += ATTN_NT) *(f32x4 *)(blk + head + 4 * i) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    if (tid < head) blk[tid] = 0.0f;
+    if (tid < n - head - 4 * nq) blk[head + 4 * nq + tid] = 0.0f;
+    __threadfence();
+  }
 
   for (int row = r_begin; row < r_end; ++row) {
     const bool first = row == r_begin;
@@ -214,12 +229,14 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
       }
       __syncthreads();
     }
-    if (tid < PL) zf[tid] = attn_gelu(zL[tid]);
-    __syncthreads();
+    if (!WIDE) {
+      if (tid < PL) zf[tid] = attn_gelu(zL[tid]);
+      __syncthreads();
+    }
     if (tid < K) {
       float a = g.bias ? th[g.b_c + tid] : 0.0f;
       #pragma unroll 8
-      for (int i = 0; i < PL; ++i) a = fmaf(zf[i], th[g.k_c + i * K + tid], a);
+      for (int i = 0; i < PL; ++i) a = fmaf(zc[i], th[g.k_c + i * K + tid], a);
       lg[tid] = a;
     }
     __syncthreads();
@@ -243,13 +260,13 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
     if (!GRAD) continue;
     __syncthreads();
     // ---- backward through the tail; rank-1 weight gradients into the slab row
-    rank1(g.k_c, zf, PL, lg, K, first);
+    rank1(g.k_c, zc, PL, lg, K, first);
     if (g.bias && tid < K) slab[g.b_c + tid] = first ? lg[tid] : slab[g.b_c + tid] + lg[tid];
     float *dcur = dv0, *dnxt = dv1;
     if (tid < PL) {   // d(classifier input) -> through the extra gelu -> through the last projection's gelu
       float a = 0.0f;
       for (int k = 0; k < K; ++k) a = fmaf(th[g.k_c + tid * K + k], lg[k], a);
-      a *= attn_gelu_grad(zL[tid]);
+      if (!WIDE) a *= attn_gelu_grad(zL[tid]);
       dcur[tid] = NP > 0 ? a * attn_gelu_grad(av(NP - 1)[tid]) : a;
     }
     __syncthreads();
@@ -405,10 +422,51 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
           if (c < C) dst[c * D] = a[r];
         }
     }
+    // ---- (WIDE) de = d(qkv) [Wq|Wk|Wv]^T, [Tp][3D] x [3D][C]: a wave owns a 16-column block of C and all nj row tiles, each W operand
+    // it loads from L2 feeds nj MFMAs (the form of the q | k | v product).  The tiles leave the accumulators directly:
+    // dPos[t] (+)= de[t] is owned by the tile's thread for the whole launch; dEmb[x_t] += de[t] is a scatter (a token may repeat
+    // inside a sequence) by fp32 vector atomics into this workgroup's own table block
+    for (int ct = wave; WIDE && ct < CT; ct += 4) {
+      const int c = ct * 16 + col;
+      const bool cok = c < C;
+      const float *Wc = th + c * D;
+      f32x4 acc[NJ];
+#pragma unroll
+      for (int mt = 0; mt < NJ; ++mt) acc[mt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      for (int part = 0; part < 3; ++part) {
+        const float *W = Wc + woff(part);
+        const float *A = QKV + part * D;
+        float bnext = cok && kq < D ? W[kq] : 0.0f;
+        for (int k0 = 0; k0 < D; k0 += 4) {
+          const int k = k0 + kq;
+          const float b = bnext;
+          bnext = cok && k + 4 < D ? W[k + 4] : 0.0f;
+#pragma unroll
+          for (int mt = 0; mt < NJ; ++mt)
+            if (mt < nj) acc[mt] = attn_mfma(k < D ? A[(mt * 16 + col) * ld + k] : 0.0f, b, acc[mt]);
+        }
+      }
+      if (cok)
+#pragma unroll
+        for (int mt = 0; mt < NJ; ++mt)
+          if (mt < nj)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int t = mt * 16 + 4 * kq + r;
+              if (t < T) {
+                float *dp_ = slab + g.pos + t * C + c;
+                *dp_ = first ? acc[mt][r] : *dp_ + acc[mt][r];
+                unsafeAtomicAdd(slab + g.emb + (size_t)tok[t] * C + c, acc[mt][r]);
+              }
+            }
+    }
   }
   if (!GRAD) return;
-  if (r_begin >= r_end)   // no sequence in this range: its slab row is zero
-    for (int i = tid; i < g.d; i += ATTN_NT) slab[i] = 0.0f;
+  if (r_begin >= r_end) {   // no sequence in this range: its slab row is zero (WIDE: the table block already is)
+    const int lo = WIDE ? g.emb : g.d, hi = WIDE ? g.emb + V * C : g.d;
+    for (int i = tid; i < lo; i += ATTN_NT) slab[i] = 0.0f;
+    for (int i = hi + tid; i < g.d; i += ATTN_NT) slab[i] = 0.0f;
+  }
   if (tid < p.dp - g.d) slab[g.d + tid] = 0.0f;
   if (tid == 0) p.llpart[(size_t)e * p.S + s] = ll_acc;
 }

@@ -1,0 +1,23 @@
+// AttentionClassifier at the widths the on-chip k_grad_attn cannot hold (C <= 192, D <= 128, projections <= 128), fp32
+// (MILE_GRAD_ATTN_WIDE_F32).  The model is mile_attn.h's: token and position tables are parameters of every chain, no extra
+// gelu.  The kernel is mile_attn_pre.h's body with WIDE set: weights streamed from L2, accumulators in the workgroup's own slab
+// row, and on top of it
+//   - e gathered from the chain's own tables inside theta (AttnGeom emb / pos offsets);
+//   - de = d(qkv) [Wq|Wk|Wv]^T straight from the accumulators: dPos[t] (+)= de[t] by the tile's owner thread, dEmb[x_t] += de[t]
+//     by fp32 vector atomics into the slab row's own [V][C] block, which the workgroup zero-fills when it starts.
+// That block is 4 V C bytes per slab row (7.68 MB at V = 10 000, C = 192): see attn_wide_S in mile_hip.hip for what it means
+// for the number of row ranges.  LDS is the pretrained kernel's (attnp_lds_bytes); no [Tp][C] image of de is kept.
+#pragma once
+#include "mile_attn_pre.h"
+
+template <int NHT>
+static __global__ __launch_bounds__(ATTN_NT) void k_grad_attn_wide(const AttnPreParams p) { attnp_body<NHT, true, true>(p); }
+template <int NHT>
+static __global__ __launch_bounds__(ATTN_NT) void k_fwd_attn_wide(const AttnPreParams p) { attnp_body<NHT, false, true>(p); }
+
+__host__ __device__ inline size_t attn_wide_lds_bytes(const AttnGeom &g) { return attnp_lds_bytes(g); }
+// the envelope k_grad_attn_wide takes (mile_create refuses everything else; spec.py WideAttentionSpec mirrors it)
+__host__ inline bool attn_wide_supported(const AttnGeom &g) { return attnp_supported(g) && g.emb >= 0 && g.pos >= 0; }
+
+// gradient (out == nullptr): grid (S row ranges, E chains) -> slabs / llpart; evaluation: grid (S row blocks, E samples) -> out
+hipError_t mile_launch_attn_wide(const AttnPreParams &p, int E, bool grad, hipStream_t st);

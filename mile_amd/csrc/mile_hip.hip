@@ -24,6 +24,7 @@
 #include "mile_lenetti.h"
 #include "mile_attn.h"
 #include "mile_attn_pre.h"
+#include "mile_attn_wide.h"
 #include "mile_predict.h"
 #include "mile_update.h"
 #include "mile_nuts.h"
@@ -64,7 +65,7 @@ struct mile_sampler {
   int grad_kernel = MILE_GRAD_AUTO;
   LeNetGeom lg{};                       // MILE_MODEL_LENET geometry and parameter offsets
   LeNettiGeom ng{};                     // MILE_MODEL_LENETTI geometry and parameter offsets
-  AttnGeom ag{};                        // MILE_MODEL_ATTN / ATTN_PRETRAINED geometry and parameter offsets
+  AttnGeom ag{};                        // MILE_MODEL_ATTN / ATTN_PRETRAINED / ATTN_WIDE geometry and parameter offsets
   float *emb_tab = nullptr, *pos_tab = nullptr;   // ATTN_PRETRAINED: frozen tables [V, C], [T, C] (mile_set_embedding)
   struct ParamLayer { int bias_off, kernel_off; };
   std::vector<ParamLayer> layers;       // mile_param_offsets, in ABI order (bias -1: none)
@@ -96,6 +97,7 @@ static bool is_lenet(const mile_sampler *s) { return s->spec.model == MILE_MODEL
 static bool is_lenetti(const mile_sampler *s) { return s->spec.model == MILE_MODEL_LENETTI; }
 static bool is_attn(const mile_sampler *s) { return s->spec.model == MILE_MODEL_ATTN; }
 static bool is_attn_pre(const mile_sampler *s) { return s->spec.model == MILE_MODEL_ATTN_PRETRAINED; }
+static bool is_attn_wide(const mile_sampler *s) { return s->spec.model == MILE_MODEL_ATTN_WIDE; }
 // every call that evaluates the likelihood refuses a pretrained-attention sampler whose tables are not set
 static bool tables_missing(const mile_sampler *s) { return is_attn_pre(s) && !s->emb_tab; }
 static const char *const kNoTables = "PretrainedAttentionClassifier: call mile_set_embedding first";
@@ -235,6 +237,20 @@ static int attn_S(const mile_sampler *s, int E) {
   return std::max(1, std::min({64, want, std::max(1, s->N / 16)}));
 }
 
+// k_grad_attn_wide: every row range is one more slab row, and a slab row holds a [V][C] table block (7.68 MB at V = 10 000,
+// C = 192) that its workgroup zero-fills before the first sequence and the update sums afterwards.  One workgroup per CU is
+// still the aim -- a sequence costs ~0.5 ms of one CU, a table block ~2 us of HBM time each way at full width -- so there is
+// no cap at 64 ranges: one chain on N = 35 000 rows takes all 256 CUs (2.04 GB of slabs, ~1 ms of fill + sum against >= 60 ms
+// of gradient).  But a range must hold enough sequences to pay for a fill that ONE workgroup does alone (7.68 MB from one CU:
+// ~0.15 ms, a third of a sequence): at least ATTN_WIDE_MIN_ROWS, so a 256-row warm-start minibatch is cut into 32 ranges, not
+// 256.  The rows are the row window's when one is set; mile_reserve sizes for the whole data set, which is never fewer.
+#define ATTN_WIDE_MIN_ROWS 8
+static int attn_wide_S_rows(const mile_sampler *s, int E, int rows) {
+  const int want = (s->n_cu + std::max(E, 1) - 1) / std::max(E, 1);
+  return std::max(1, std::min(want, std::max(1, rows / ATTN_WIDE_MIN_ROWS)));
+}
+static int attn_wide_S(const mile_sampler *s, int E) { return attn_wide_S_rows(s, E, s->win_count ? s->win_count : s->N); }
+
 // Everything the library knows about one grad kernel: one row per MILE_GRAD_* id in kGrad, defined below the launchers.
 struct LaunchShape { int block, lds; };
 struct GradKernel {
@@ -264,6 +280,7 @@ static int auto_kernel(const mile_sampler *s) {
   if (is_lenetti(s)) return MILE_GRAD_LENETTI_F32;
   if (is_attn(s)) return MILE_GRAD_ATTN_F32;
   if (is_attn_pre(s)) return MILE_GRAD_ATTN_PRE_F32;
+  if (is_attn_wide(s)) return MILE_GRAD_ATTN_WIDE_F32;
   return MILE_GRAD_GENERIC;
 }
 static int resolved_kernel(const mile_sampler *s) { return s->grad_kernel == MILE_GRAD_AUTO ? auto_kernel(s) : s->grad_kernel; }
@@ -402,48 +419,61 @@ static int layout_attn(mile_sampler *s) {
   return MILE_OK;
 }
 
-// PretrainedAttentionClassifier: ravel_pytree order MDPA.{key, out, query, value}, classifier, projection_*; bias before kernel.
-// No TokenEmbedding_0 leaves: the tables are frozen (mile_set_embedding).  ABI layers: key, out, query, value, classifier,
-// projection_*
-static int layout_attn_pre(mile_sampler *s) {
+// The two models on the kernel that streams its weights (mile_attn_pre.h body): limits C <= 192, D <= 128, projections <= 128.
+//   tables == false, PretrainedAttentionClassifier: ravel_pytree order MDPA.{key, out, query, value}, classifier, projection_*;
+//     bias before kernel.  No TokenEmbedding_0 leaves: the tables are frozen (mile_set_embedding).  ABI layers: key, out, query,
+//     value, classifier, projection_*
+//   tables == true, AttentionClassifier on k_grad_attn_wide: layout_attn's parameters and ABI layers (the tables are leaves)
+static int layout_attn_streamed(mile_sampler *s, const std::string &name, bool tables) {
   const mile_model_spec *spec = &s->spec;
-  if (spec->task != MILE_TASK_CLASSIFICATION) return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: classification only");
+  if (spec->task != MILE_TASK_CLASSIFICATION) return fail(MILE_ERR_INVALID, name + ": classification only");
   if (spec->n_layers < 1 || spec->n_layers > ATTN_MAX_NP + 1)
-    return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: widths = projection_dim (at most 2) + [n_classes]");
+    return fail(MILE_ERR_INVALID, name + ": widths = projection_dim (at most 2) + [n_classes]");
   if (spec->ctx_len < 1 || spec->ctx_len > ATTN_MAX_T || spec->in_features != spec->ctx_len)
-    return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: 1 <= ctx_len <= 128 and in_features == ctx_len");
-  if (spec->emb_size < 1 || spec->emb_size > ATTNP_MAX_C) return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: emb_size <= 192");
+    return fail(MILE_ERR_INVALID, name + ": 1 <= ctx_len <= 128 and in_features == ctx_len");
+  if (spec->emb_size < 1 || spec->emb_size > ATTNP_MAX_C) return fail(MILE_ERR_INVALID, name + ": emb_size <= 192");
   if (spec->qkv_dim < 1 || spec->qkv_dim > ATTNP_MAX_D || spec->n_heads < 1 || spec->qkv_dim % spec->n_heads)
-    return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: qkv_dim <= 128 and n_heads dividing it");
-  if (spec->vocab_size < 1 || spec->vocab_size > (1 << 24))
-    return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: 1 <= vocab_size <= 2^24");
+    return fail(MILE_ERR_INVALID, name + ": qkv_dim <= 128 and n_heads dividing it");
+  // token ids travel as fp32: the new model takes what its spec takes (V < 2^24); the pretrained one keeps its bound
+  if (spec->vocab_size < 1 || spec->vocab_size > (1 << 24) - (tables ? 1 : 0))
+    return fail(MILE_ERR_INVALID, name + (tables ? ": 1 <= vocab_size < 2^24" : ": 1 <= vocab_size <= 2^24"));
   for (int l = 0; l + 1 < spec->n_layers; ++l)
-    if (spec->widths[l] > ATTNP_MAX_P) return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: projection widths <= 128");
-  if (spec->widths[spec->n_layers - 1] > ATTN_MAX_K) return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: n_classes <= 16");
+    if (spec->widths[l] > ATTNP_MAX_P) return fail(MILE_ERR_INVALID, name + ": projection widths <= 128");
+  if (spec->widths[spec->n_layers - 1] > ATTN_MAX_K) return fail(MILE_ERR_INVALID, name + ": n_classes <= 16");
   AttnGeom &g = s->ag;
   g.V = spec->vocab_size; g.T = spec->ctx_len; g.C = spec->emb_size; g.H = spec->n_heads; g.D = spec->qkv_dim;
   g.hd = g.D / g.H; g.NP = spec->n_layers - 1; g.K = spec->widths[g.NP]; g.bias = spec->use_bias ? 1 : 0;
   g.Tp = (g.T + 15) / 16 * 16;
   for (int l = 0; l < ATTN_MAX_NP; ++l) { g.P[l] = l < g.NP ? spec->widths[l] : 0; g.b_p[l] = g.k_p[l] = -1; }
-  if (!attnp_supported(g)) return fail(MILE_ERR_INVALID, "PretrainedAttentionClassifier: shape needs more than 160 KB of LDS");
+  if (!attnp_supported(g)) return fail(MILE_ERR_INVALID, name + ": shape needs more than 160 KB of LDS");   // (= attn_wide_lds_bytes)
   long long o = 0;
   auto put = [&](int &b, int &k, long long nb, long long nk) { b = g.bias && nb ? (int)o : -1; o += g.bias ? nb : 0; k = (int)o; o += nk; };
+  int no_bias;
   put(g.b_k, g.k_k, g.D, (long long)g.C * g.D);
   put(g.b_o, g.k_o, g.C, (long long)g.D * g.C);
   put(g.b_q, g.k_q, g.D, (long long)g.C * g.D);
   put(g.b_v, g.k_v, g.D, (long long)g.C * g.D);
   g.emb = g.pos = -1;
+  if (tables) {
+    put(no_bias, g.emb, 0, (long long)g.V * g.C);
+    put(no_bias, g.pos, 0, (long long)g.T * g.C);
+  }
   put(g.b_c, g.k_c, g.K, (long long)(g.NP ? g.P[g.NP - 1] : g.C) * g.K);
   for (int l = 0; l < g.NP; ++l) put(g.b_p[l], g.k_p[l], g.P[l], (long long)(l ? g.P[l - 1] : g.C) * g.P[l]);
+  if (o > 0x7fffffffLL) return fail(MILE_ERR_INVALID, name + ": too many parameters");
   g.d = (int)o;
   s->ds.d = g.d;
   s->ds.widths[0] = g.K;
   s->ds.b_off[0] = g.b_c; s->ds.w_off[0] = g.k_c;
   s->ds.max_width = 64; s->ds.act_stride = 0;
-  s->layers = {{g.b_k, g.k_k}, {g.b_o, g.k_o}, {g.b_q, g.k_q}, {g.b_v, g.k_v}, {g.b_c, g.k_c}};
+  s->layers = {{g.b_k, g.k_k}, {g.b_o, g.k_o}, {g.b_q, g.k_q}, {g.b_v, g.k_v}};
+  if (tables) { s->layers.push_back({-1, g.emb}); s->layers.push_back({-1, g.pos}); }
+  s->layers.push_back({g.b_c, g.k_c});
   for (int l = 0; l < g.NP; ++l) s->layers.push_back({g.b_p[l], g.k_p[l]});
   return MILE_OK;
 }
+static int layout_attn_pre(mile_sampler *s) { return layout_attn_streamed(s, "PretrainedAttentionClassifier", false); }
+static int layout_attn_wide(mile_sampler *s) { return layout_attn_streamed(s, "AttentionClassifier (wide)", true); }
 
 extern "C" {
 
@@ -454,7 +484,8 @@ int32_t mile_create(const mile_model_spec *spec, int32_t device, mile_sampler **
   if (!spec || !out) return fail(MILE_ERR_INVALID, "mile_create: null argument");
   if (spec->n_layers < 1 || spec->n_layers > MILE_MAX_LAYERS) return fail(MILE_ERR_INVALID, "n_layers out of range");
   if (spec->in_features < 1) return fail(MILE_ERR_INVALID, "in_features must be >= 1");
-  if (!spec->use_bias && spec->model != MILE_MODEL_ATTN && spec->model != MILE_MODEL_ATTN_PRETRAINED) return fail(MILE_ERR_INVALID, "use_bias=false is not supported");
+  const bool attn_family = spec->model == MILE_MODEL_ATTN || spec->model == MILE_MODEL_ATTN_PRETRAINED || spec->model == MILE_MODEL_ATTN_WIDE;
+  if (!spec->use_bias && !attn_family) return fail(MILE_ERR_INVALID, "use_bias=false is not supported");
   if (spec->activation < 0 || spec->activation > MILE_ACT_SIGMOID) return fail(MILE_ERR_INVALID, "unknown activation");
   if (spec->task != MILE_TASK_REGRESSION && spec->task != MILE_TASK_CLASSIFICATION) return fail(MILE_ERR_INVALID, "unknown task");
   if (spec->prior != MILE_PRIOR_NORMAL && spec->prior != MILE_PRIOR_LAPLACE) return fail(MILE_ERR_INVALID, "unknown prior");
@@ -463,8 +494,9 @@ int32_t mile_create(const mile_model_spec *spec, int32_t device, mile_sampler **
     if (spec->widths[l] < 1) return fail(MILE_ERR_INVALID, "layer width must be >= 1");
   if (spec->task == MILE_TASK_REGRESSION && spec->widths[spec->n_layers - 1] != 2)
     return fail(MILE_ERR_INVALID, "regression needs an output layer of width 2 (mu, log sigma)");
-  static int (*const layout[])(mile_sampler *) = {layout_fcn, layout_lenet, layout_lenetti, layout_attn, layout_attn_pre};   // by mile_model
-  if (spec->model < MILE_MODEL_FCN || spec->model > MILE_MODEL_ATTN_PRETRAINED) return fail(MILE_ERR_INVALID, "unknown model");
+  static int (*const layout[])(mile_sampler *) = {layout_fcn, layout_lenet, layout_lenetti, layout_attn, layout_attn_pre,
+                                                  layout_attn_wide};   // by mile_model
+  if (spec->model < MILE_MODEL_FCN || spec->model > MILE_MODEL_ATTN_WIDE) return fail(MILE_ERR_INVALID, "unknown model");
 
   auto *s = new mile_sampler();
   s->spec = *spec;
@@ -657,9 +689,10 @@ int32_t mile_reserve(mile_sampler *s, int32_t E) {
   if (!s->X) return fail(MILE_ERR_STATE, "mile_reserve: call mile_set_data first");
   HIP_TRY(hipSetDevice(s->device));
   // capacity must cover whichever grad kernel is selected later
-  int S = choose_S(s, E, MILE_GRAD_GENERIC);
-  for (int k = MILE_GRAD_GENERIC; k <= MILE_GRAD_ATTN_PRE_F32; ++k)
+  int S = 1;   // (only the kernels that run this model: GENERIC's 64 ranges would double the wide attention's 2 GB)
+  for (int k = MILE_GRAD_GENERIC; k <= MILE_GRAD_ATTN_WIDE_F32; ++k)
     if (grad_kernel(k).supports(s)) S = std::max(S, choose_S(s, E, k));
+  if (is_attn_wide(s)) S = std::max(S, attn_wide_S_rows(s, E, s->N));   // whatever row window is set now
   // A smaller ensemble splits the rows of a particle over MORE workgroups (S grows as E shrinks): capacity is counted in
   // slab rows E * S, and a later call with fewer particles must neither fail nor shrink what a larger one reserved.
   if (E <= s->E_cap && (size_t)E * S <= s->ES_cap) return MILE_OK;
@@ -684,7 +717,7 @@ int32_t mile_reserve(mile_sampler *s, int32_t E) {
 
 int32_t mile_set_grad_kernel(mile_sampler *s, int32_t which) {
   if (!s) return fail(MILE_ERR_INVALID, "null handle");
-  if (which < MILE_GRAD_AUTO || which > MILE_GRAD_ATTN_PRE_F32) return fail(MILE_ERR_INVALID, "unknown grad kernel");
+  if (which < MILE_GRAD_AUTO || which > MILE_GRAD_ATTN_WIDE_F32) return fail(MILE_ERR_INVALID, "unknown grad kernel");
   if (which != MILE_GRAD_AUTO) {
     const GradKernel &k = grad_kernel(which);
     if (!k.supports(s)) return fail(MILE_ERR_INVALID, k.refusal);
@@ -694,6 +727,7 @@ int32_t mile_set_grad_kernel(mile_sampler *s, int32_t which) {
   return MILE_OK;
 }
 int32_t mile_get_grad_kernel(const mile_sampler *s) { return s ? resolved_kernel(s) : MILE_ERR_INVALID; }
+int64_t mile_slab_bytes(const mile_sampler *s) { return s ? (int64_t)(s->ES_cap * ((size_t)(s->ds.d + 3) / 4 * 4) * 4) : -1; }
 
 }  // extern "C"
 
@@ -1505,6 +1539,17 @@ static hipError_t launch_attn_pre(mile_sampler *s, const float *theta, int E, co
   return mile_launch_attn_pre(ap, E, out_ll == nullptr, st);
 }
 
+// ---- wide AttentionClassifier (mile_attn_wide.h; the kernels are instantiated in mile_attn_wide.hip), as launch_attn
+static hipError_t launch_attn_wide(mile_sampler *s, const float *theta, int E, const float *X, const void *y, int N, int S, int dp,
+                                   float *out_ll, hipStream_t st) {
+  AttnPreParams ap{};
+  ap.g = s->ag;
+  ap.theta = theta; ap.X = X; ap.y = y;
+  ap.slabs = s->slabs; ap.llpart = s->llpart; ap.out = out_ll;
+  ap.N = N; ap.S = S; ap.dp = dp;
+  return mile_launch_attn_wide(ap, E, out_ll == nullptr, st);
+}
+
 // ---- the gradient of each grad kernel: the `grad` of its row in kGrad.  gp holds the row window and S; fz the update that runs
 // as the launch's epilogue (fuses) ----------------------------------------------------------------------------------------------
 static int grad_w64(mile_sampler *s, const GradParams &gp, const W64Fuse &fz, int E, hipStream_t st) {
@@ -1538,6 +1583,10 @@ static int grad_attn(mile_sampler *s, const GradParams &gp, const W64Fuse &, int
 }
 static int grad_attn_pre(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
   HIP_TRY(launch_attn_pre(s, gp.theta, E, gp.X, gp.y, gp.N, gp.S, gp.dp, nullptr, st));
+  return MILE_OK;
+}
+static int grad_attn_wide(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
+  HIP_TRY(launch_attn_wide(s, gp.theta, E, gp.X, gp.y, gp.N, gp.S, gp.dp, nullptr, st));
   return MILE_OK;
 }
 static int grad_lenetti(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
@@ -1582,7 +1631,7 @@ static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t s
   gp.N = s->N; gp.Npad = s->Npad; gp.Npb = s->Npb; gp.Fp = s->Fp; gp.S = S; gp.R = generic_R(s->ds); gp.dp = (s->ds.d + 3) / 4 * 4;
   if (s->win_count) {   // minibatch: the same kernels on a shifted view of the rows
     if (!k.windowed)
-      return fail(MILE_ERR_STATE, "a row window needs the generic, the MFMA_NARROW, an MFMA_W64, an MFMA_WIDE, a LENET, the LENETTI, the ATTN or the ATTN_PRE grad kernel");
+      return fail(MILE_ERR_STATE, "a row window needs the generic, the MFMA_NARROW, an MFMA_W64, an MFMA_WIDE, a LENET, the LENETTI or an ATTN grad kernel");
     if (fused_update) return fail(MILE_ERR_STATE, "row windows are for mile_logpost_grad only");
     const int F = s->spec.in_features;
     gp.X = s->X + (size_t)s->win_begin * F;
@@ -1863,19 +1912,12 @@ static int launch_fwd_wide(mile_sampler *s, const float *theta, int S, const flo
 }
 
 // ---- evaluation of each grad kernel's model: the `loglik` of its row in kGrad.  pp holds the staged evaluation set ------------
-static int loglik_attn(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
+template <hipError_t (*LAUNCH)(mile_sampler *, const float *, int, const float *, const void *, int, int, int, float *, hipStream_t)>
+static int loglik_attn_t(mile_sampler *s, PredParams pp, int S, hipStream_t st) {   // the three attention models: their launcher
   const int SB = std::max(1, std::min({64, (s->n_cu + S - 1) / S, std::max(1, pp.N / 16)}));
   for (int s0 = 0; s0 < S; s0 += 65535) {
     const int Sc = std::min(65535, S - s0);
-    HIP_TRY(launch_attn(s, pp.theta + (size_t)s0 * s->ds.d, Sc, pp.X, pp.y, pp.N, SB, 0, pp.out + (size_t)s0 * pp.N, st));
-  }
-  return MILE_OK;
-}
-static int loglik_attn_pre(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
-  const int SB = std::max(1, std::min({64, (s->n_cu + S - 1) / S, std::max(1, pp.N / 16)}));
-  for (int s0 = 0; s0 < S; s0 += 65535) {
-    const int Sc = std::min(65535, S - s0);
-    HIP_TRY(launch_attn_pre(s, pp.theta + (size_t)s0 * s->ds.d, Sc, pp.X, pp.y, pp.N, SB, 0, pp.out + (size_t)s0 * pp.N, st));
+    HIP_TRY(LAUNCH(s, pp.theta + (size_t)s0 * s->ds.d, Sc, pp.X, pp.y, pp.N, SB, 0, pp.out + (size_t)s0 * pp.N, st));
   }
   return MILE_OK;
 }
@@ -1945,6 +1987,7 @@ static LaunchShape shape_narrow(const mile_sampler *s, int S) {
 }
 static LaunchShape shape_attn(const mile_sampler *s, int) { return {256, (int)attn_lds_bytes(s->ag, attn_weights_in_lds(s->ag))}; }
 static LaunchShape shape_attn_pre(const mile_sampler *s, int) { return {256, (int)attnp_lds_bytes(s->ag)}; }
+static LaunchShape shape_attn_wide(const mile_sampler *s, int) { return {256, (int)attn_wide_lds_bytes(s->ag)}; }
 static LaunchShape shape_lenetti(const mile_sampler *s, int) { return {256, (int)lenetti_lds_bytes(s->ng, lenetti_T(s->ng))}; }
 static LaunchShape shape_lenet_bf16(const mile_sampler *s, int) { return {256, (int)cm_lds_dw(CM_IN8, s->lg.hp1, s->lg.wp1, 0)}; }
 static LaunchShape shape_rocblas(const mile_sampler *, int) { return {256, 0}; }
@@ -1987,15 +2030,18 @@ static constexpr GradKernel kGrad[] = {
     {MILE_GRAD_LENETTI_F32, "k_grad_lenetti", is_lenetti, "LENETTI_F32 is the kernel of MILE_MODEL_LENETTI, and its only one", nullptr,
      lenetti_S, true, false, grad_lenetti, loglik_lenetti, shape_lenetti},
     {MILE_GRAD_ATTN_F32, "k_grad_attn", is_attn, "ATTN_F32 is the kernel of MILE_MODEL_ATTN, and its only one", nullptr,
-     attn_S, true, false, grad_attn, loglik_attn, shape_attn},
+     attn_S, true, false, grad_attn, loglik_attn_t<launch_attn>, shape_attn},
     {MILE_GRAD_ATTN_PRE_F32, "k_grad_attn_pre", is_attn_pre,
      "ATTN_PRE_F32 is the kernel of MILE_MODEL_ATTN_PRETRAINED, and its only one", nullptr,
-     attn_S, true, false, grad_attn_pre, loglik_attn_pre, shape_attn_pre},
+     attn_S, true, false, grad_attn_pre, loglik_attn_t<launch_attn_pre>, shape_attn_pre},
+    {MILE_GRAD_ATTN_WIDE_F32, "k_grad_attn_wide", is_attn_wide,
+     "ATTN_WIDE_F32 is the kernel of MILE_MODEL_ATTN_WIDE, and its only one", nullptr,
+     attn_wide_S, true, false, grad_attn_wide, loglik_attn_t<launch_attn_wide>, shape_attn_wide},
 };
 static constexpr bool rows_in_id_order() {
   for (int k = 0; k < (int)(sizeof(kGrad) / sizeof(kGrad[0])); ++k)
     if (kGrad[k].id != k + 1) return false;
-  return sizeof(kGrad) / sizeof(kGrad[0]) == MILE_GRAD_ATTN_PRE_F32;
+  return sizeof(kGrad) / sizeof(kGrad[0]) == MILE_GRAD_ATTN_WIDE_F32;
 }
 static_assert(rows_in_id_order(), "kGrad: one row per MILE_GRAD_* id, in id order");
 static const GradKernel &grad_kernel(int kernel) { return kGrad[kernel - 1]; }

@@ -12,7 +12,8 @@ from typing import NamedTuple
 import torch
 
 from mile_amd import _lib
-from mile_amd.spec import IMAGE_SPECS, AttentionSpec, LeNetSpec, LeNettiSpec, ModelSpec, PretrainedAttentionSpec
+from mile_amd.spec import (IMAGE_SPECS, AttentionSpec, LeNetSpec, LeNettiSpec, ModelSpec, PretrainedAttentionSpec,
+                           WideAttentionSpec)
 
 
 class IntegratorState(NamedTuple):
@@ -91,7 +92,8 @@ class Engine:
             cs.model = 2 if isinstance(spec, LeNettiSpec) else 1
             cs.img_c, cs.img_h, cs.img_w = spec.channels, spec.height, spec.width
         if isinstance(spec, (AttentionSpec, PretrainedAttentionSpec)):
-            cs.model = _lib.MODEL_IDS['attn_pretrained' if isinstance(spec, PretrainedAttentionSpec) else 'attn']
+            cs.model = _lib.MODEL_IDS['attn_pretrained' if isinstance(spec, PretrainedAttentionSpec) else
+                                      ('attn_wide' if isinstance(spec, WideAttentionSpec) else 'attn')]
             cs.vocab_size, cs.ctx_len, cs.emb_size = spec.vocab_size, spec.context_len, spec.emb_size
             cs.n_heads, cs.qkv_dim = spec.n_heads, spec.qkv_dim
         cs.n_layers = len(spec.hidden_structure)
@@ -175,6 +177,11 @@ class Engine:
         # the larger one reserved (mile_reserve returns at once when the workspace already fits, and never shrinks it)
         _lib.check(self.lib.mile_reserve(self._h, int(E)), self.lib)
         self._E_reserved = max(self._E_reserved, int(E))
+
+    @property
+    def slab_bytes(self) -> int:
+        """Bytes of the gradient slabs the library holds now (mile_slab_bytes)."""
+        return int(self.lib.mile_slab_bytes(self._h))
 
     def set_grad_kernel(self, name: str):
         _lib.check(self.lib.mile_set_grad_kernel(self._h, _lib.GRAD_KERNEL_IDS[name]), self.lib)

@@ -403,6 +403,38 @@ def pretrained_table_paths(emb_path) -> tuple[str, str]:
     return emb_path, emb_path.replace('emb', 'pos_emb')
 
 
+def _check_streamed_attention(self, name: str):
+    """__post_init__ of the two specs on the kernel that streams its weights (mile_attn_pre.h's body): PretrainedAttentionSpec and
+    WideAttentionSpec share its limits and its LDS budget."""
+    object.__setattr__(self, 'projection_dim', tuple(int(p) for p in self.projection_dim))
+    if self.task != 'classification':
+        raise NotImplementedError(f'{name}: classification only')
+    if self.prior not in PRIORS:
+        raise NotImplementedError(f'Prior Distribution for {self.prior} is not yet implemented.')
+    if self.prior == 'StandardNormal':
+        object.__setattr__(self, 'prior_loc', 0.0)
+        object.__setattr__(self, 'prior_scale', 1.0)
+    V, T, C, H, D, K = self.vocab_size, self.context_len, self.emb_size, self.n_heads, self.qkv_dim, self.n_classes
+    if min(V, T, C, H, D, K) < 1 or any(p < 1 for p in self.projection_dim):
+        raise ValueError(f'{name}: all sizes must be >= 1')
+    if D % H:
+        raise ValueError(f'{name}: n_heads ({H}) must divide qkv_dim ({D})')
+    limits = ((T, ATTN_MAX_T, 'context_len'), (C, ATTNP_MAX_C, 'emb_size'), (D, ATTNP_MAX_D, 'qkv_dim'),
+              (K, ATTN_MAX_K, 'n_classes'))
+    for v, top, what in limits:
+        if v > top:
+            raise NotImplementedError(f'{name}: {what} = {v}, the HIP kernel takes at most {top}')
+    if len(self.projection_dim) > ATTN_MAX_PROJ:
+        raise NotImplementedError(f'{name}: at most {ATTN_MAX_PROJ} projection layers on the HIP kernel')
+    if any(p > ATTNP_MAX_P for p in self.projection_dim):
+        raise NotImplementedError(f'{name}: projection widths <= {ATTNP_MAX_P} on the HIP kernel')
+    if V >= 1 << 24:
+        raise NotImplementedError(f'{name}: vocab_size < 2^24 (token ids travel as fp32)')
+    if self.lds_bytes > ATTN_LDS_MAX:
+        raise NotImplementedError(f'{name}: this shape needs {self.lds_bytes} bytes of LDS per workgroup, the HIP kernel '
+                                  f'has {ATTN_LDS_MAX} (q|k|v [T][3D] and e [T][C] share it)')
+
+
 @dataclass(frozen=True)
 class PretrainedAttentionSpec:
     """PretrainedAttentionClassifier (src/models/text/attention_classifier.py:74-132, PretrainedAttentionClassifierConfig
@@ -428,34 +460,7 @@ class PretrainedAttentionSpec:
     root: str = ''
 
     def __post_init__(self):
-        object.__setattr__(self, 'projection_dim', tuple(int(p) for p in self.projection_dim))
-        name = 'PretrainedAttentionClassifier'
-        if self.task != 'classification':
-            raise NotImplementedError(f'{name}: classification only')
-        if self.prior not in PRIORS:
-            raise NotImplementedError(f'Prior Distribution for {self.prior} is not yet implemented.')
-        if self.prior == 'StandardNormal':
-            object.__setattr__(self, 'prior_loc', 0.0)
-            object.__setattr__(self, 'prior_scale', 1.0)
-        V, T, C, H, D, K = self.vocab_size, self.context_len, self.emb_size, self.n_heads, self.qkv_dim, self.n_classes
-        if min(V, T, C, H, D, K) < 1 or any(p < 1 for p in self.projection_dim):
-            raise ValueError(f'{name}: all sizes must be >= 1')
-        if D % H:
-            raise ValueError(f'{name}: n_heads ({H}) must divide qkv_dim ({D})')
-        limits = ((T, ATTN_MAX_T, 'context_len'), (C, ATTNP_MAX_C, 'emb_size'), (D, ATTNP_MAX_D, 'qkv_dim'),
-                  (K, ATTN_MAX_K, 'n_classes'))
-        for v, top, what in limits:
-            if v > top:
-                raise NotImplementedError(f'{name}: {what} = {v}, the HIP kernel takes at most {top}')
-        if len(self.projection_dim) > ATTN_MAX_PROJ:
-            raise NotImplementedError(f'{name}: at most {ATTN_MAX_PROJ} projection layers on the HIP kernel')
-        if any(p > ATTNP_MAX_P for p in self.projection_dim):
-            raise NotImplementedError(f'{name}: projection widths <= {ATTNP_MAX_P} on the HIP kernel')
-        if V >= 1 << 24:
-            raise NotImplementedError(f'{name}: vocab_size < 2^24 (token ids travel as fp32)')
-        if self.lds_bytes > ATTN_LDS_MAX:
-            raise NotImplementedError(f'{name}: this shape needs {self.lds_bytes} bytes of LDS per workgroup, the HIP kernel '
-                                      f'has {ATTN_LDS_MAX} (q|k|v [T][3D] and e [T][C] share it)')
+        _check_streamed_attention(self, 'PretrainedAttentionClassifier')
 
     @property
     def in_features(self) -> int:
@@ -529,4 +534,40 @@ class PretrainedAttentionSpec:
         return self.check_tables(*tables)
 
 
-NATIVE_SPECS = IMAGE_SPECS + (AttentionSpec, PretrainedAttentionSpec)
+@dataclass(frozen=True)
+class WideAttentionSpec(AttentionSpec):
+    """AttentionClassifier beyond the on-chip kernel's widths: the model, fields, leaves and FLOP model of AttentionSpec, the
+    limits and LDS of the kernel that streams its weights (k_grad_attn_wide, mile_amd/csrc/mile_attn_wide.h: emb_size <= 192,
+    qkv_dim <= 128, projections <= 128 -- the reference's emb_size-192 pretraining shapes).  The embedding tables are
+    parameters: 4 V C bytes of every slab row (see slab_bytes)."""
+
+    def __post_init__(self):
+        _check_streamed_attention(self, 'AttentionClassifier (wide kernel)')
+
+    @property
+    def lds_bytes(self) -> int:
+        """LDS of one k_grad_attn_wide workgroup (attn_wide_lds_bytes in mile_attn_wide.h): the pretrained kernel's."""
+        return attn_pre_lds_bytes(self.context_len, self.emb_size, self.n_heads, self.qkv_dim, self.projection_dim)
+
+    def row_splits(self, n_chains: int, n_rows: int, n_cu: int = 256) -> int:
+        """Row ranges (slab rows) per chain of k_grad_attn_wide (attn_wide_S in mile_hip.hip): one workgroup per CU, at least 8
+        sequences per range, no cap."""
+        want = (n_cu + max(n_chains, 1) - 1) // max(n_chains, 1)
+        return max(1, min(want, max(1, n_rows // 8)))
+
+    def slab_bytes(self, n_chains: int, n_rows: int, n_cu: int = 256) -> int:
+        """Bytes of the [E, S, d] gradient slabs mile_reserve allocates for n_chains on n_rows (Engine.slab_bytes is what the
+        library holds; tests/test_gpu_attn_wide.py holds the two equal)."""
+        return 4 * n_chains * self.row_splits(n_chains, n_rows, n_cu) * ((self.n_params + 3) // 4 * 4)
+
+
+def attention_spec(**kw):
+    """The spec of `model: AttentionClassifier`: AttentionSpec (the on-chip k_grad_attn) wherever it takes the shape, so no shape
+    that ran before changes kernel; WideAttentionSpec (k_grad_attn_wide) beyond it."""
+    try:
+        return AttentionSpec(**kw)
+    except NotImplementedError:
+        return WideAttentionSpec(**kw)
+
+
+NATIVE_SPECS = IMAGE_SPECS + (AttentionSpec, PretrainedAttentionSpec, WideAttentionSpec)

@@ -23,7 +23,7 @@ from mile_amd.config import Config
 from mile_amd.dataset import ImageLoader, TabularLoader, TextLoader
 from mile_amd.probabilistic import ProbabilisticModel
 from mile_amd.sampling import inference_loop, join_without_chains
-from mile_amd.spec import AttentionSpec, LeNetSpec, LeNettiSpec, ModelSpec, PretrainedAttentionSpec
+from mile_amd.spec import LeNetSpec, LeNettiSpec, ModelSpec, PretrainedAttentionSpec, attention_spec
 from mile_amd.tree import PRNGKey
 
 logger = logging.getLogger(__name__)
@@ -99,7 +99,7 @@ class BDETrainer:
                 self.spec_model = PretrainedAttentionSpec(emb_path=m.emb_path, **kw)
                 self.spec_model.load_tables()               # fail here, with the paths, rather than at the first engine
             else:
-                self.spec_model = AttentionSpec(**kw)
+                self.spec_model = attention_spec(**kw)        # the on-chip kernel where the shape fits it, the wide one beyond
         elif config.model.model in ('LeNet', 'LeNetti'):
             if config.data.data_type != 'image':
                 raise ValueError(f'model {config.model.model} needs data_type: image')

@@ -1,9 +1,10 @@
 """Write the frozen tables of a PretrainedAttentionClassifier: emb.npy [V, C] and its position twin [T, C].
 
-    python tools/make_embeddings.py --from results/.../params_0.npz --out results/pretrained_seq/emb.npy
+    python tools/make_embeddings.py --from <experiment dir>/warmstart/params_0.npz --out results/pretrained_seq/emb.npy
     python tools/make_embeddings.py --random 10000 70 192 --seed 0 --out results/pretrained_seq/emb.npy
 
---from reads an AttentionClassifier params_*.npz or sample_*.npz (the leaves TokenEmbedding_0.Embedding.embedding and
+--from reads an AttentionClassifier params_*.npz (the warm start writes one per chain under <experiment dir>/warmstart/; the run
+of experiments/mclmc_seqmod_pretraining*_synthetic.yaml is the one at the pretrained model's shape) or sample_*.npz (the leaves TokenEmbedding_0.Embedding.embedding and
 TokenEmbedding_0.PositionEmbedding.embedding; a stacked file with a leading sample axis takes --index).  --random draws both
 tables as normal with std 1 / sqrt(C), nn.Embed's initialiser, for synthetic runs.  The position table goes where the model
 will look for it: the --out path with every 'emb' replaced by 'pos_emb' (mile_amd.spec.pretrained_table_paths), so
