@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""LPPD of a finished experiment (the consumer of mile_pointwise_loglik; mirrors what the reference's
-report notebook does with src/inference/evaluation.py:409-544 + src/inference/metrics.py:247-312 for the
-log-score part):
+"""LPPD, ACC, RMSE, coverage and calibration error of a finished experiment (the consumer of mile_pointwise_loglik and
+mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
+src/inference/metrics.py:247-312):
 
     python evaluate.py -e results/mile_amd/<experiment> [--split test]
 
@@ -16,6 +16,67 @@ import numpy as np
 import torch
 
 
+def sample_chunk(N, O, budget=1 << 30):
+    """Samples per Engine.predict call: the raw block [chunk, N, O] fp32 stays under ``budget`` bytes."""
+    return max(1, (budget - 1) // (N * O * 4))
+
+
+def predictive_metrics(eng, samples, x, y, task, seed, coverages, with_rmse=True, budget=1 << 30):
+    """The part of evaluate_bde's report that needs the raw outputs (src/inference/evaluation.py:459-543): ACC for
+    classification; coverage, calibration error and (``with_rmse``) RMSE for regression.  samples [C, S, d] (host).
+
+    The samples are walked chain by chain in chunks of ``sample_chunk`` through Engine.predict, and each chunk's draws come
+    from ONE device generator seeded ``seed``, in that order.  Only the class counts [C, N, K], or the draws [C, S, N], are
+    kept -- never the raw outputs of the whole experiment."""
+    from mile_amd import metrics as M
+    dev = eng.device
+    gen = torch.Generator(device=dev).manual_seed(int(seed))
+    C_, S_, N = samples.shape[0], samples.shape[1], x.shape[0]
+    O = eng.spec.hidden_structure[-1]
+    xt = torch.from_numpy(x).to(dev)
+    step = sample_chunk(N, O, budget)
+    res = {}
+    if task != 'regr':
+        yt = torch.from_numpy(y).to(dev).reshape(-1)
+        counts = torch.zeros((C_, N, O), dtype=torch.int64, device=dev)
+        for c in range(C_):
+            for s0 in range(0, S_, step):
+                raw = eng.predict(torch.from_numpy(samples[c, s0:s0 + step]), xt)
+                counts[c] += M.class_counts(M.sample_from_predictions(raw, task, gen), O)
+        pc = M.accuracy_from_counts(counts, yt)
+        res['acc'] = float(M.accuracy_from_counts(counts.sum(dim=0), yt).item())
+        res['per_chain_acc'] = [float(v) for v in pc.cpu()]
+        res['per_chain_acc_median'] = float(pc.median().item())
+        return res
+    yt = torch.from_numpy(y).to(dev).to(torch.float32).reshape(-1)
+    draws = torch.empty((C_, S_, N), dtype=torch.float32, device=dev)
+    mu_sum = torch.zeros(N, dtype=torch.float64, device=dev)
+    mu_chain = torch.zeros((C_, N), dtype=torch.float64, device=dev)
+    n_ok = 0
+    for c in range(C_):
+        for s0 in range(0, S_, step):
+            raw = eng.predict(torch.from_numpy(samples[c, s0:s0 + step]), xt)
+            draws[c, s0:s0 + step] = M.sample_from_predictions(raw, task, gen)
+            mu = raw[..., 0]
+            fin_rows = torch.isfinite(mu).all(dim=1)                 # (the FCN rmse above: samples with a finite prediction)
+            mu_sum += mu[fin_rows].double().sum(dim=0)
+            n_ok += int(fin_rows.sum())
+            mu_chain[c] += torch.nan_to_num(mu.double(), nan=0.0, posinf=0.0, neginf=0.0).sum(dim=0)
+    if with_rmse and n_ok:
+        res['rmse'] = float(torch.sqrt(((yt.double() - mu_sum / n_ok) ** 2).mean()).item())
+        rc = torch.sqrt(((yt.double()[None] - mu_chain / S_) ** 2).mean(dim=1))
+        res['per_chain_rmse'] = [float(v) for v in rc.cpu()]
+        res['per_chain_rmse_median'] = float(rc.median().item())
+    # chains with a non-finite draw are left out, as the reference leaves out its NaN chains (evaluation.py:493-497,532)
+    ok = torch.isfinite(draws).all(dim=2).all(dim=1)
+    if bool(ok.any()):
+        cov = M.calculate_coverage(coverages, yt, draws[ok])
+        for c, v in zip(coverages, cov.cpu()):
+            res[f'coverage_{c}'] = float(v)
+        res['cal_error'] = float(M.calibration_error(coverages, cov).item())
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description='LPPD / NLL of the samples of an experiment directory')
     ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
@@ -24,6 +85,9 @@ def main():
     ap.add_argument('--ess-params', type=int, default=256, help='size of the random parameter subset ESS is evaluated on')
     ap.add_argument('--drop-nonfinite', action='store_true',
                     help='leave out chains with non-finite samples (the reference would report NaN; default: keep them)')
+    ap.add_argument('--seed', type=int, default=42, help='seed of the posterior-predictive draws behind ACC / coverage')
+    ap.add_argument('--coverages', type=float, nargs='+', default=[0.5, 0.75, 0.9, 0.95],
+                    help='nominal coverage levels of the central credible intervals (regression)')
     args = ap.parse_args()
     exp = Path(args.exp)
     from mile_amd.callbacks import load_samples_from_dir
@@ -91,6 +155,8 @@ def main():
             rc = torch.sqrt(((yt[None] - mu_chain / S_) ** 2).mean(dim=1))
             out['per_chain_rmse'] = [float(v) for v in rc.cpu()]
             out['per_chain_rmse_median'] = float(rc.median().item())
+    out.update(predictive_metrics(eng, samples, x, np.ascontiguousarray(y), cfg.data.task, args.seed, args.coverages,
+                                  with_rmse=not (cfg.data.task == 'regr' and cfg.model.model == 'FCN')))
     # dead chains: a tuned step size of 0 / NaN in warmup_params.txt (profiles/r03/01_dead_chains_mechanism.md)
     wp = exp / 'warmup_params.txt'
     if wp.exists():

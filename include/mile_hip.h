@@ -295,7 +295,8 @@ int32_t mile_set_data(mile_sampler *s, const float *X, const void *y, int64_t N,
 /* MILE_MODEL_ATTN_PRETRAINED only: PretrainedTokenEmbedding (src/flax_building_blocks/basic.py:117-143).  Copies the frozen
  * token table emb [V, C] and the first T rows of the position table, pos [T, C], into buffers the sampler owns (shared by all
  * chains; they are neither sampled nor in the prior).  Until it has been called, mile_logpost_grad, mile_warmstart_step,
- * mile_init, mile_step, mile_tune, mile_nuts_step, mile_nuts_warmup and mile_pointwise_loglik fail with MILE_ERR_STATE.
+ * mile_init, mile_step, mile_tune, mile_nuts_step, mile_nuts_warmup, mile_pointwise_loglik and mile_predict fail with
+ * MILE_ERR_STATE.
  * Calling it again replaces the tables. */
 int32_t mile_set_embedding(mile_sampler *s, const float *emb, const float *pos, void *stream);
 
@@ -356,6 +357,14 @@ int32_t mile_tune(mile_sampler *s, mile_state *state, const mile_tune_args *args
  * pointers of a TEST set (independent of mile_set_data); out [S, N] = log p(y_n | x_n, theta_s). */
 int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, int32_t S, const float *X, const void *y,
                               int64_t N, float *out, void *stream);
+
+/* Replaces: the per-sample module.apply of predict_from_samples / predict_bde (src/inference/evaluation.py:16-43,
+ * 334-406), the input of every metric but LPPD (ACC, RMSE, coverage, calibration error).
+ * theta [S, d] (any S >= 1) and X [N, F] as for mile_pointwise_loglik; no labels.  out [S, N, O] fp32 row-major, O the
+ * width of the last layer: the RAW outputs -- (mu, log sigma) unclipped, or the logits before any softmax; NaN / inf
+ * pass through.  Runs the forward kernels of mile_pointwise_loglik with the row's outputs stored instead of their
+ * log-probability.  (Added under ABI 10: a new symbol, no struct or existing entry changed.) */
+int32_t mile_predict(mile_sampler *s, const float *theta, int32_t S, const float *X, int64_t N, float *out, void *stream);
 
 /* Size the NUTS trajectory buffers (ends, momentum sums, proposals, [E, max_num_doublings, d] U-turn checkpoints) for
  * ensembles of up to E chains, and the grad workspace as mile_reserve.  Allocation happens here, never in a launch. */

@@ -131,6 +131,7 @@ SIGNATURES = {
     'mile_tune': (C.c_int32, [C.c_void_p, C.POINTER(StateC), C.POINTER(TuneArgsC), C.c_void_p]),
     'mile_pointwise_loglik': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_void_p, C.c_void_p]),
+    'mile_predict': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'mile_debug_noise': (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
                                      C.c_void_p, C.c_void_p]),
     'mile_debug_prefill_count': (C.c_int64, [C.c_void_p]),

@@ -45,7 +45,7 @@ struct AttnParams {
   const void *y;        // [N] int32 labels
   float *slabs;         // [E, S, dp] likelihood-gradient slabs (gradient)
   float *llpart;        // [E, S] (gradient)
-  float *out;           // [S, N] per-row log-likelihoods (evaluation)
+  float *out;           // [S, N] per-row log-likelihoods (evaluation); RAW: [S, N, K] logits, y unread
   int N, S, dp;
 };
 
@@ -142,7 +142,8 @@ __device__ __forceinline__ void attn_probs(const float *QKV, int ld, const int *
 }
 
 // NHT: ceil(hd / 16) (dK register tiles per key tile); WL: Wq|Wk|Wv staged in LDS
-template <int NHT, bool WL, bool GRAD>
+// RAW (evaluation only): the logits go to out[e][row][K] and the head is skipped, y unread (mile_predict)
+template <int NHT, bool WL, bool GRAD, bool RAW = false>
 __device__ __forceinline__ void attn_body(const AttnParams &p) {
   constexpr int NJ = ATTN_MAX_T / 16, NDW = 12, NDP = 8, NFW = ATTN_MAX_P / 4;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -279,7 +280,9 @@ __device__ __forceinline__ void attn_body(const AttnParams &p) {
       float a = g.bias ? th[g.b_c + tid] : 0.0f;
       for (int i = 0; i < PL; ++i) a = fmaf(zL[i], th[g.k_c + i * K + tid], a);
       lg[tid] = a;
+      if constexpr (RAW) p.out[((size_t)e * p.N + row) * K + tid] = a;   // K <= 16 lanes: one contiguous run of the row
     }
+    if constexpr (RAW) continue;
     __syncthreads();
     if (tid < 64) {   // wave 0: head (log softmax at the label, its gradient)
       float mx = -INFINITY;
@@ -538,6 +541,8 @@ template <int NHT, bool WL>
 static __global__ __launch_bounds__(ATTN_NT) void k_grad_attn(const AttnParams p) { attn_body<NHT, WL, true>(p); }
 template <int NHT, bool WL>
 static __global__ __launch_bounds__(ATTN_NT) void k_fwd_attn(const AttnParams p) { attn_body<NHT, WL, false>(p); }
+template <int NHT, bool WL>
+static __global__ __launch_bounds__(ATTN_NT) void k_out_attn(const AttnParams p) { attn_body<NHT, WL, false, true>(p); }
 
-// gradient (out == nullptr): grid (S row ranges, E chains) -> slabs / llpart; evaluation: grid (S row blocks, E samples) -> out
-hipError_t mile_launch_attn(const AttnParams &p, int E, bool grad, hipStream_t st);
+// MILE_RUN_GRAD: grid (S row ranges, E chains) -> slabs / llpart; _LOGLIK / _RAW: grid (S row blocks, E samples) -> out
+hipError_t mile_launch_attn(const AttnParams &p, int E, MileRun run, hipStream_t st);

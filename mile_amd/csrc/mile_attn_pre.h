@@ -75,7 +75,8 @@ __host__ __device__ inline size_t attnp_lds_bytes(const AttnGeom &g) {
 // NHT: ceil(hd / 16) (dq register tiles; dK in registers for NHT == 1, in the wave's scratch otherwise)
 // WIDE: the AttentionClassifier of mile_attn_wide.h -- the tables are the chain's own parameters (g.emb / g.pos offsets into
 // theta, p.emb / p.pos unused), they get a gradient, and the classifier reads the last projection without the extra gelu
-template <int NHT, bool GRAD, bool WIDE = false>
+// RAW (evaluation only): the logits go to out[e][row][K] and the head is skipped, y unread (mile_predict)
+template <int NHT, bool GRAD, bool WIDE = false, bool RAW = false>
 __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
   constexpr int NJ = ATTN_MAX_T / 16;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -238,7 +239,9 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
       #pragma unroll 8
       for (int i = 0; i < PL; ++i) a = fmaf(zc[i], th[g.k_c + i * K + tid], a);
       lg[tid] = a;
+      if constexpr (RAW) p.out[((size_t)e * p.N + row) * K + tid] = a;   // K <= 16 lanes: one contiguous run of the row
     }
+    if constexpr (RAW) continue;
     __syncthreads();
     if (tid < 64) {   // wave 0: head (log softmax at the label, its gradient)
       float mx = -INFINITY;
@@ -475,6 +478,8 @@ template <int NHT>
 static __global__ __launch_bounds__(ATTN_NT) void k_grad_attn_pre(const AttnPreParams p) { attnp_body<NHT, true>(p); }
 template <int NHT>
 static __global__ __launch_bounds__(ATTN_NT) void k_fwd_attn_pre(const AttnPreParams p) { attnp_body<NHT, false>(p); }
+template <int NHT>
+static __global__ __launch_bounds__(ATTN_NT) void k_out_attn_pre(const AttnPreParams p) { attnp_body<NHT, false, false, true>(p); }
 
 // the envelope k_grad_attn_pre takes (mile_create refuses everything else; spec.py PretrainedAttentionSpec mirrors it)
 __host__ inline bool attnp_supported(const AttnGeom &g) {
@@ -486,5 +491,5 @@ __host__ inline bool attnp_supported(const AttnGeom &g) {
   return attnp_lds_bytes(g) <= ATTN_LDS_MAX;
 }
 
-// gradient (out == nullptr): grid (S row ranges, E chains) -> slabs / llpart; evaluation: grid (S row blocks, E samples) -> out
-hipError_t mile_launch_attn_pre(const AttnPreParams &p, int E, bool grad, hipStream_t st);
+// MILE_RUN_GRAD: grid (S row ranges, E chains) -> slabs / llpart; _LOGLIK / _RAW: grid (S row blocks, E samples) -> out
+hipError_t mile_launch_attn_pre(const AttnPreParams &p, int E, MileRun run, hipStream_t st);

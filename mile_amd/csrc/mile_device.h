@@ -27,6 +27,10 @@ static hipError_t mile_set_max_lds(int bytes) {
   return e;
 }
 
+// What one launch of a model's fused kernel computes (mile_launch_lenetti / _attn / _attn_pre / _attn_wide): the gradient
+// slabs, the per-row log-likelihoods of mile_pointwise_loglik, or the per-row raw outputs of mile_predict.
+enum MileRun { MILE_RUN_LOGLIK = 0, MILE_RUN_GRAD = 1, MILE_RUN_RAW = 2 };
+
 // Flattened description of the FCN that kernels take by value.
 struct DevSpec {
   int32_t n_layers;

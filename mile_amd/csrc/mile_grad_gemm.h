@@ -71,10 +71,17 @@ __global__ __launch_bounds__(256) void k_gemm_head(float *out, const void *y, lo
 
 // Evaluation: per-row log-likelihood of the head outputs (no nansum zeroing: src/inference/metrics.py:247-294
 // uses the distributions' log_prob directly).  out_ll[(s0 + s) * N + r0 + r].
+// RAW (mile_predict): the head outputs themselves, out_ll[((s0 + s) * N + r0 + r) * K + c], one thread per float, y unread.
+template <bool RAW = false>
 __global__ __launch_bounds__(256) void k_gemm_rowll(const float *out, const void *y, long long r0, int R, int K, int task, float *out_ll,
                                                     long long N, long long s0) {
   const int s = blockIdx.y;
   const float *o = out + (size_t)s * R * K;
+  if constexpr (RAW) {
+    float *dst = out_ll + ((size_t)(s0 + s) * N + r0) * K;
+    for (long long i = blockIdx.x * 256 + threadIdx.x; i < (long long)R * K; i += gridDim.x * 256) dst[i] = o[i];
+    return;
+  }
   for (int r = blockIdx.x * 256 + threadIdx.x; r < R; r += gridDim.x * 256) {
     const float *z = o + (size_t)r * K;
     float v;

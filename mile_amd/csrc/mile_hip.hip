@@ -263,7 +263,8 @@ struct GradKernel {
   bool windowed;                                      // takes a row window (mile_set_row_window)
   bool fuses;                                         // can run the update that follows as its epilogue (W64Fuse)
   int (*grad)(mile_sampler *, const GradParams &, const W64Fuse &, int E, hipStream_t);
-  int (*loglik)(mile_sampler *, PredParams pp, int S, hipStream_t);   // mile_pointwise_loglik on the staged evaluation set
+  int (*loglik)(mile_sampler *, PredParams pp, int S, hipStream_t);   // mile_pointwise_loglik on the staged evaluation set;
+                                                                      // pp.y == nullptr: mile_predict, raw outputs [S, N, O]
   LaunchShape (*shape)(const mile_sampler *, int S);  // block and LDS bytes that mile_grad_launch_info reports
 };
 static const GradKernel &grad_kernel(int kernel);
@@ -1065,8 +1066,9 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
       bias_act(f2, g.b_f2, 84, Rc, 1);
       if (fwd(g.k_f3, 84, g.K, f2, Rc * 84, Rc, out)) return fail(MILE_ERR_HIP, "rocblas sgemm (fc3) failed");
       bias_act(out, g.b_f3, g.K, Rc, 0);
-      if (!grad) {
-        k_gemm_rowll<<<dim3((unsigned)((Rc + 255) / 256), E), 256, 0, st>>>(out, y, r0, (int)Rc, g.K, task, out_ll, N, s0);
+      if (!grad) {   // per-row log-likelihoods, or (y == nullptr: mile_predict) the raw outputs [.., N, K]
+        if (y) k_gemm_rowll<<<dim3((unsigned)((Rc + 255) / 256), E), 256, 0, st>>>(out, y, r0, (int)Rc, g.K, task, out_ll, N, s0);
+        else k_gemm_rowll<true><<<dim3(blocks(Rc * g.K), E), 256, 0, st>>>(out, y, r0, (int)Rc, g.K, task, out_ll, N, s0);
         continue;
       }
       k_gemm_head<<<E, 256, 0, st>>>(out, y, r0, (int)Rc, g.K, task, llacc, chunk == 0);
@@ -1322,8 +1324,9 @@ static int lenet_dense_chunk(mile_sampler *s, const float *theta, int E, int Rc,
     p.act = act; p.apply_act = l < 2;
     HIP_TRY(launch_mm3_fwd<3>(p, E, st));
   }
-  if (!slab) {   // evaluation: per-row log-likelihood
-    k_wide_rowll<<<dim3((unsigned)((Rc + 255) / 256), E), 256, 0, st>>>(b.out, (long long)Rc * ld[2], ld[2], y, r0, Rc, g.K, task, out_ll, Ntot, s0);
+  if (!slab) {   // evaluation: per-row log-likelihood, or (y == nullptr: mile_predict) the raw outputs [.., N, K]
+    if (y) k_wide_rowll<<<dim3((unsigned)((Rc + 255) / 256), E), 256, 0, st>>>(b.out, (long long)Rc * ld[2], ld[2], y, r0, Rc, g.K, task, out_ll, Ntot, s0);
+    else k_wide_rowll<true><<<dim3((unsigned)std::min<long long>(((long long)Rc * g.K + 255) / 256, 65535), E), 256, 0, st>>>(b.out, (long long)Rc * ld[2], ld[2], y, r0, Rc, g.K, task, out_ll, Ntot, s0);
     HIP_TRY(hipGetLastError());
     return MILE_OK;
   }
@@ -1506,26 +1509,31 @@ static int launch_grad_wide(mile_sampler *s, const GradParams &gp, int E, hipStr
   return MILE_OK;
 }
 
+// what the fused kernels' launchers below run: the gradient (out_ll == nullptr), the log-likelihoods, or (y == nullptr) raw outputs
+static MileRun run_of(const void *y, const float *out_ll) { return !out_ll ? MILE_RUN_GRAD : (y ? MILE_RUN_LOGLIK : MILE_RUN_RAW); }
+
 // ---- LeNetti (mile_lenetti.h; the kernels are instantiated in mile_lenetti.hip).  Gradient (out_ll == nullptr): grid (S row
-// ranges, E chains) -> slabs / llpart; evaluation: grid (S row blocks, E samples) -> out_ll[e * N + row]
+// ranges, E chains) -> slabs / llpart; evaluation: grid (S row blocks, E samples) -> out_ll[e * N + row], or (y == nullptr) the
+// raw outputs out_ll[(e * N + row) * K + c]
 static hipError_t launch_lenetti(mile_sampler *s, const float *theta, int E, const float *X, const void *y, int N, int S, int dp,
                                  float *out_ll, hipStream_t st) {
   LeNettiParams lp{};
   lp.g = s->ng; lp.activation = s->ds.activation; lp.task = s->ds.task;
   lp.theta = theta; lp.X = X; lp.y = y; lp.slabs = s->slabs; lp.llpart = s->llpart; lp.out = out_ll;
   lp.N = N; lp.S = S; lp.dp = dp;
-  return mile_launch_lenetti(lp, E, out_ll == nullptr, st);
+  return mile_launch_lenetti(lp, E, run_of(y, out_ll), st);
 }
 
 // ---- AttentionClassifier (mile_attn.h; the kernels are instantiated in mile_attn.hip).  Gradient (out_ll == nullptr): grid
-// (S row ranges, E chains) -> slabs / llpart; evaluation: grid (S row blocks, E samples) -> out_ll[e * N + row]
+// (S row ranges, E chains) -> slabs / llpart; evaluation: grid (S row blocks, E samples) -> out_ll[e * N + row], or
+// (y == nullptr) the logits out_ll[(e * N + row) * K + c]
 static hipError_t launch_attn(mile_sampler *s, const float *theta, int E, const float *X, const void *y, int N, int S, int dp,
                               float *out_ll, hipStream_t st) {
   AttnParams ap{};
   ap.g = s->ag;
   ap.theta = theta; ap.X = X; ap.y = y; ap.slabs = s->slabs; ap.llpart = s->llpart; ap.out = out_ll;
   ap.N = N; ap.S = S; ap.dp = dp;
-  return mile_launch_attn(ap, E, out_ll == nullptr, st);
+  return mile_launch_attn(ap, E, run_of(y, out_ll), st);
 }
 
 // ---- PretrainedAttentionClassifier (mile_attn_pre.h; the kernels are instantiated in mile_attn_pre.hip), as launch_attn
@@ -1536,7 +1544,7 @@ static hipError_t launch_attn_pre(mile_sampler *s, const float *theta, int E, co
   ap.theta = theta; ap.X = X; ap.y = y; ap.emb = s->emb_tab; ap.pos = s->pos_tab;
   ap.slabs = s->slabs; ap.llpart = s->llpart; ap.out = out_ll;
   ap.N = N; ap.S = S; ap.dp = dp;
-  return mile_launch_attn_pre(ap, E, out_ll == nullptr, st);
+  return mile_launch_attn_pre(ap, E, run_of(y, out_ll), st);
 }
 
 // ---- wide AttentionClassifier (mile_attn_wide.h; the kernels are instantiated in mile_attn_wide.hip), as launch_attn
@@ -1547,7 +1555,7 @@ static hipError_t launch_attn_wide(mile_sampler *s, const float *theta, int E, c
   ap.theta = theta; ap.X = X; ap.y = y;
   ap.slabs = s->slabs; ap.llpart = s->llpart; ap.out = out_ll;
   ap.N = N; ap.S = S; ap.dp = dp;
-  return mile_launch_attn_wide(ap, E, out_ll == nullptr, st);
+  return mile_launch_attn_wide(ap, E, run_of(y, out_ll), st);
 }
 
 // ---- the gradient of each grad kernel: the `grad` of its row in kGrad.  gp holds the row window and S; fz the update that runs
@@ -1782,16 +1790,30 @@ static int mclmc_begin(mile_sampler *s, mile_state *state, const Args *a, const 
   return MILE_OK;
 }
 
+// gridDim.y holds at most 65 535 samples: the raw-output (mile_predict) launches walk S in chunks of that many
+#define MILE_GRID_Y_MAX 65535
+
 template <int NH, int FQ>
 static hipError_t launch_fwd_w64(const PredParams &pp, int S, hipStream_t st) {
   using LY = W64Layout<NH, FQ>;
+  if (!pp.y) {   // mile_predict: (mu, log sigma) per row
+    hipError_t e = mile_set_max_lds<k_fwd_w64<NH, FQ, true>>(LY::BYTES);
+    for (int s0 = 0; s0 < S && e == hipSuccess; s0 += MILE_GRID_Y_MAX) {
+      PredParams q = pp;
+      q.theta += (size_t)s0 * pp.spec.d; q.out += (size_t)s0 * pp.N * 2;
+      k_fwd_w64<NH, FQ, true><<<dim3(pp.SB, std::min(MILE_GRID_Y_MAX, S - s0)), 256, LY::BYTES, st>>>(q);
+      e = hipGetLastError();
+    }
+    return e;
+  }
   hipError_t e = mile_set_max_lds<k_fwd_w64<NH, FQ>>(LY::BYTES);
   if (e != hipSuccess) return e;
   k_fwd_w64<NH, FQ><<<dim3(pp.SB, S), 256, LY::BYTES, st>>>(pp);
   return hipGetLastError();
 }
 
-// Evaluation forward for wide nets: the same strided-batched SGEMMs, samples as the batch.
+// Evaluation forward for wide nets: the same strided-batched SGEMMs, samples as the batch.  y == nullptr (mile_predict): out is
+// the raw outputs [S, N, O].
 static int launch_fwd_gemm(mile_sampler *s, const float *theta, int S, const float *X, const void *y, int N, float *out, hipStream_t st) {
   if (!rocblas_load()) return fail(MILE_ERR_HIP, "librocblas.so could not be loaded");
   const DevSpec &ds = s->ds;
@@ -1833,7 +1855,9 @@ static int launch_fwd_gemm(mile_sampler *s, const float *theta, int S, const flo
                                                                                                    ds.activation, l + 1 < L);
         pp ^= 1;
       }
-      k_gemm_rowll<<<dim3((Rc + 255) / 256, Sn), 256, 0, st>>>(buf[pp ^ 1], y, r0, Rc, ds.widths[L - 1], ds.task, out, N, s0);
+      const int O = ds.widths[L - 1];
+      if (y) k_gemm_rowll<<<dim3((Rc + 255) / 256, Sn), 256, 0, st>>>(buf[pp ^ 1], y, r0, Rc, O, ds.task, out, N, s0);
+      else k_gemm_rowll<true><<<dim3((unsigned)std::min<long long>(((long long)Rc * O + 255) / 256, 65535), Sn), 256, 0, st>>>(buf[pp ^ 1], y, r0, Rc, O, ds.task, out, N, s0);
     }
   }
   HIP_TRY(hipGetLastError());
@@ -1841,6 +1865,7 @@ static int launch_fwd_gemm(mile_sampler *s, const float *theta, int S, const flo
 }
 
 // Evaluation forward for wide nets on the MFMA GEMMs (fp32-faithful, whatever the sampling kernel was): samples as the batch.
+// y == nullptr (mile_predict): out is the raw outputs [S, N, O].
 static int launch_fwd_wide(mile_sampler *s, const float *theta, int S, const float *Xp, int Fp, const void *y, int N, float *out,
                            hipStream_t st) {
   const DevSpec &ds = s->ds;
@@ -1904,20 +1929,24 @@ static int launch_fwd_wide(mile_sampler *s, const float *theta, int S, const flo
         HIP_TRY(launch_mm3_fwd<3>(p, Sn, st));
         pp ^= 1;
       }
-      k_wide_rowll<<<dim3((Rc + 255) / 256, Sn), 256, 0, st>>>(buf[pp ^ 1], (long long)R * wp[L - 1], wp[L - 1], y, r0, Rc, ds.widths[L - 1], ds.task, out, N, s0);
+      const int O = ds.widths[L - 1];
+      if (y) k_wide_rowll<<<dim3((Rc + 255) / 256, Sn), 256, 0, st>>>(buf[pp ^ 1], (long long)R * wp[L - 1], wp[L - 1], y, r0, Rc, O, ds.task, out, N, s0);
+      else k_wide_rowll<true><<<dim3((unsigned)std::min<long long>(((long long)Rc * O + 255) / 256, 65535), Sn), 256, 0, st>>>(buf[pp ^ 1], (long long)R * wp[L - 1], wp[L - 1], y, r0, Rc, O, ds.task, out, N, s0);
     }
   }
   HIP_TRY(hipGetLastError());
   return MILE_OK;
 }
 
-// ---- evaluation of each grad kernel's model: the `loglik` of its row in kGrad.  pp holds the staged evaluation set ------------
+// ---- evaluation of each grad kernel's model: the `loglik` of its row in kGrad.  pp holds the staged evaluation set; without
+// labels (pp.y == nullptr, mile_predict) every row of the table writes the raw outputs, O floats per (sample, row) -----------------
+static size_t out_width(const mile_sampler *s, const PredParams &pp) { return pp.y ? 1 : (size_t)s->spec.widths[s->spec.n_layers - 1]; }
 template <hipError_t (*LAUNCH)(mile_sampler *, const float *, int, const float *, const void *, int, int, int, float *, hipStream_t)>
 static int loglik_attn_t(mile_sampler *s, PredParams pp, int S, hipStream_t st) {   // the three attention models: their launcher
   const int SB = std::max(1, std::min({64, (s->n_cu + S - 1) / S, std::max(1, pp.N / 16)}));
   for (int s0 = 0; s0 < S; s0 += 65535) {
     const int Sc = std::min(65535, S - s0);
-    HIP_TRY(LAUNCH(s, pp.theta + (size_t)s0 * s->ds.d, Sc, pp.X, pp.y, pp.N, SB, 0, pp.out + (size_t)s0 * pp.N, st));
+    HIP_TRY(LAUNCH(s, pp.theta + (size_t)s0 * s->ds.d, Sc, pp.X, pp.y, pp.N, SB, 0, pp.out + (size_t)s0 * pp.N * out_width(s, pp), st));
   }
   return MILE_OK;
 }
@@ -1925,7 +1954,7 @@ static int loglik_lenetti(mile_sampler *s, PredParams pp, int S, hipStream_t st)
   const int SB = std::max(1, std::min({64, (2 * s->n_cu + S - 1) / S, std::max(1, pp.N / 32)}));
   for (int s0 = 0; s0 < S; s0 += 65535) {
     const int Sc = std::min(65535, S - s0);
-    HIP_TRY(launch_lenetti(s, pp.theta + (size_t)s0 * s->ds.d, Sc, pp.X, pp.y, pp.N, SB, 0, pp.out + (size_t)s0 * pp.N, st));
+    HIP_TRY(launch_lenetti(s, pp.theta + (size_t)s0 * s->ds.d, Sc, pp.X, pp.y, pp.N, SB, 0, pp.out + (size_t)s0 * pp.N * out_width(s, pp), st));
   }
   return MILE_OK;
 }
@@ -1961,6 +1990,15 @@ static int loglik_w64(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
 static int loglik_generic(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
   pp.SB = std::max(1, std::min(std::max(1, (4 * s->n_cu) / S), std::max(1, pp.N / 64)));
   const size_t lds = ((size_t)pp.R * s->ds.act_stride + 16) * 4;
+  if (!pp.y) {   // mile_predict
+    for (int s0 = 0; s0 < S; s0 += MILE_GRID_Y_MAX) {
+      PredParams q = pp;
+      q.theta += (size_t)s0 * s->ds.d; q.out += (size_t)s0 * pp.N * out_width(s, pp);
+      k_fwd_generic<true><<<dim3(pp.SB, std::min(MILE_GRID_Y_MAX, S - s0)), 256, lds, st>>>(q);
+      HIP_TRY(hipGetLastError());
+    }
+    return MILE_OK;
+  }
   k_fwd_generic<<<dim3(pp.SB, S), 256, lds, st>>>(pp);
   HIP_TRY(hipGetLastError());
   return MILE_OK;
@@ -2046,11 +2084,8 @@ static constexpr bool rows_in_id_order() {
 static_assert(rows_in_id_order(), "kGrad: one row per MILE_GRAD_* id, in id order");
 static const GradKernel &grad_kernel(int kernel) { return kGrad[kernel - 1]; }
 
-extern "C" int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, int32_t S, const float *X, const void *y,
-                                         int64_t N, float *out, void *stream) {
-  if (!s || !theta || !X || !y || !out || S < 1) return fail(MILE_ERR_INVALID, "mile_pointwise_loglik: bad argument");
-  if (N < 1 || N > 0x3fffffff) return fail(MILE_ERR_INVALID, "mile_pointwise_loglik: N out of range");
-  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
+// mile_pointwise_loglik and (y == nullptr) mile_predict: stage the evaluation rows, then the resolved kernel's `loglik`
+static int evaluate_rows(mile_sampler *s, const float *theta, int32_t S, const float *X, const void *y, int64_t N, float *out, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->device));
   const int F = s->spec.in_features, Npad = ((int)N + 31) / 32 * 32, Fp = (F + 7) / 8 * 8;
@@ -2065,14 +2100,31 @@ extern "C" int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, in
     s->ev_cap = Npad;
   }
   HIP_TRY(hipMemcpyAsync(s->ev_X, X, (size_t)N * F * 4, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemsetAsync(s->ev_y, 0, (size_t)Npad * 4, st));
-  HIP_TRY(hipMemcpyAsync(s->ev_y, y, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+  if (y) {
+    HIP_TRY(hipMemsetAsync(s->ev_y, 0, (size_t)Npad * 4, st));
+    HIP_TRY(hipMemcpyAsync(s->ev_y, y, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+  }
   const long long tot = (long long)Npad * Fp;
   k_pad_x<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(s->ev_X, s->ev_Xp, (int)N, Npad, F, Fp);
   PredParams pp;
-  pp.spec = s->ds; pp.theta = theta; pp.X = s->ev_X; pp.Xp = s->ev_Xp; pp.y = s->ev_y; pp.out = out;
+  pp.spec = s->ds; pp.theta = theta; pp.X = s->ev_X; pp.Xp = s->ev_Xp; pp.y = y ? s->ev_y : nullptr; pp.out = out;
   pp.N = (int)N; pp.Npad = Npad; pp.Fp = Fp; pp.R = generic_R(s->ds);
   return grad_kernel(resolved_kernel(s)).loglik(s, pp, S, st);
+}
+
+extern "C" int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, int32_t S, const float *X, const void *y,
+                                         int64_t N, float *out, void *stream) {
+  if (!s || !theta || !X || !y || !out || S < 1) return fail(MILE_ERR_INVALID, "mile_pointwise_loglik: bad argument");
+  if (N < 1 || N > 0x3fffffff) return fail(MILE_ERR_INVALID, "mile_pointwise_loglik: N out of range");
+  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
+  return evaluate_rows(s, theta, S, X, y, N, out, stream);
+}
+
+extern "C" int32_t mile_predict(mile_sampler *s, const float *theta, int32_t S, const float *X, int64_t N, float *out, void *stream) {
+  if (!s || !theta || !X || !out || S < 1) return fail(MILE_ERR_INVALID, "mile_predict: bad argument");
+  if (N < 1 || N > 0x3fffffff) return fail(MILE_ERR_INVALID, "mile_predict: N out of range");
+  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
+  return evaluate_rows(s, theta, S, X, nullptr, N, out, stream);
 }
 
 extern "C" {

@@ -33,7 +33,7 @@ struct LeNettiParams {
   const void *y;        // [N] fp32 (regr) or int32 (classification)
   float *slabs;         // [E, S, dp] likelihood-gradient slabs (gradient)
   float *llpart;        // [E, S] (gradient)
-  float *out;           // [S, N] per-row log-likelihoods (evaluation)
+  float *out;           // [S, N] per-row log-likelihoods (evaluation); RAW: [S, N, K] raw outputs, y unread
   int N, S, dp;
 };
 
@@ -75,7 +75,7 @@ __device__ __forceinline__ void lenetti_reduce_scatter(float (&v)[NV], int lane)
 // tail gradient accumulators of wave 0, lane-private in LDS: entry q of lane l at tg[q * 64 + l]
 enum { TG_W2 = 0, TG_W3 = 8, TG_W4 = 16, TG_B1 = 16 + LENETTI_MAX_K, TG_B2, TG_B3, TG_B4, TG_N = TG_B4 + 2 };
 
-template <int PPT, int T, int CM, bool GRAD>
+template <int PPT, int T, int CM, bool GRAD, bool RAW = false>
 __device__ __forceinline__ void lenetti_body(const LeNettiParams &p) {
   static_assert(T == 4 || T == 2, "tile of 4 or 2 images");
   constexpr int NV = T * 8, SHIFT = T == 4 ? 1 : 2;
@@ -221,6 +221,14 @@ __device__ __forceinline__ void lenetti_body(const LeNettiParams &p) {
           if (c < K) z = fmaf(hk, W4[k * K + c], z);
         }
         o[m] = z;
+      }
+      if constexpr (RAW) {   // lane (ti, tj) holds outputs tj and tj + 8 of image ti: the tile's rows are one contiguous run of out
+        if (live) {
+          float *dst = p.out + ((size_t)e * p.N + t0 + ti) * K;
+          if (tj < K) dst[tj] = o[0];
+          if (tj + 8 < K) dst[tj + 8] = o[1];
+        }
+        continue;           // (the other waves leave the tile below; the barrier is the loop's first statement)
       }
       // head: regression (mu, log sigma) or softmax over K logits, as row_loss_regr / k_grad_generic
       float ll = 0.0f, dout[2] = {0.0f, 0.0f};
@@ -390,9 +398,11 @@ __global__ __launch_bounds__(LENETTI_NT) void k_grad_lenetti(const LeNettiParams
 
 template <int PPT, int T, int CM>
 __global__ __launch_bounds__(LENETTI_NT) void k_fwd_lenetti(const LeNettiParams p) { lenetti_body<PPT, T, CM, false>(p); }
+template <int PPT, int T, int CM>
+__global__ __launch_bounds__(LENETTI_NT) void k_out_lenetti(const LeNettiParams p) { lenetti_body<PPT, T, CM, false, true>(p); }
 
 // host: images per tile (registers hold a0 [T][PPT]) and the launch, in mile_lenetti.hip (its own translation unit)
 inline int lenetti_ppt(const LeNettiGeom &g) { return (g.P + LENETTI_NT - 1) / LENETTI_NT; }
 inline int lenetti_T(const LeNettiGeom &g) { return lenetti_ppt(g) <= 4 ? 4 : 2; }
-// gradient (out == nullptr): grid (S row ranges, E chains) -> slabs / llpart; evaluation: grid (S row blocks, E samples) -> out
-hipError_t mile_launch_lenetti(const LeNettiParams &lp, int E, bool grad, hipStream_t st);
+// MILE_RUN_GRAD: grid (S row ranges, E chains) -> slabs / llpart; _LOGLIK / _RAW: grid (S row blocks, E samples) -> out
+hipError_t mile_launch_lenetti(const LeNettiParams &lp, int E, MileRun run, hipStream_t st);

@@ -2,6 +2,9 @@
 // i.e. the per-sample module.apply + Normal / Categorical log_prob of the reference's evaluation
 // (src/inference/evaluation.py:16-43, src/inference/metrics.py:247-294).  out[s][n], NaNs are NOT zeroed
 // (metrics.py calls log_prob directly, there is no nansum there).
+// RAW instantiations (mile_predict): the same forward, but the row's raw outputs -- (mu, log sigma) unclipped or the logits, what
+// module.apply returns in predict_from_samples -- go to out[s][n][O] and y is never read.  A compile-time variant: the
+// log-likelihood instantiations are the code they were.
 #pragma once
 #include "mile_grad_w64.h"
 
@@ -10,8 +13,8 @@ struct PredParams {
   const float *theta;   // [S, d]
   const float *X;       // [N, F]
   const float *Xp;      // [Npad, Fp]
-  const void *y;        // [Npad]
-  float *out;           // [S, N]
+  const void *y;        // [Npad]; nullptr: mile_predict (the launchers pick the RAW kernels)
+  float *out;           // [S, N], RAW: [S, N, O]
   int32_t N, Npad, Fp, SB, R;
 };
 
@@ -23,7 +26,7 @@ __device__ __forceinline__ float row_logpdf_regr(float mu, float sr, float yv) {
 }
 
 // width-64 ReLU regression nets: the forward half of k_grad_w64 (same LDS images, same T layout)
-template <int NH, int FQ>
+template <int NH, int FQ, bool RAW = false>
 __global__ __launch_bounds__(256, 1) void k_fwd_w64(const PredParams p) {
   using LY = W64Layout<NH, FQ>;
   constexpr int FP = LY::FP;
@@ -114,12 +117,17 @@ __global__ __launch_bounds__(256, 1) void k_fwd_w64(const PredParams p) {
       }
     p0 += __shfl_xor(p0, 32);
     p1 += __shfl_xor(p1, 32);
-    if (h == 0 && row0 + j < p.N)
-      p.out[(size_t)e * p.N + row0 + j] = row_logpdf_regr(p0 + BO[0], p1 + BO[1], ((const float *)p.y)[row0 + j]);
+    if constexpr (RAW) {   // lane j of the low half holds row j's pair: 32 x 8 contiguous bytes per wave
+      if (h == 0 && row0 + j < p.N) *(float2 *)(p.out + ((size_t)e * p.N + row0 + j) * 2) = make_float2(p0 + BO[0], p1 + BO[1]);
+    } else {
+      if (h == 0 && row0 + j < p.N)
+        p.out[(size_t)e * p.N + row0 + j] = row_logpdf_regr(p0 + BO[0], p1 + BO[1], ((const float *)p.y)[row0 + j]);
+    }
   }
 }
 
 // any FCN: one thread per (row, unit), activations tiled through LDS (as k_grad_generic's forward)
+template <bool RAW = false>
 __global__ __launch_bounds__(256) void k_fwd_generic(const PredParams p) {
   extern __shared__ float lds[];
   const DevSpec &sp = p.spec;
@@ -151,6 +159,15 @@ __global__ __launch_bounds__(256) void k_fwd_generic(const PredParams p) {
       __syncthreads();
     }
     const int C = sp.widths[nl - 1];
+    if constexpr (RAW) {   // the tile's nr x C outputs are one contiguous run of out: consecutive threads, consecutive floats
+      float *o = p.out + ((size_t)e * p.N + t0) * C;
+      for (int idx = tid; idx < nr * C; idx += nt) {
+        const int r = idx / C, c = idx - r * C;
+        o[idx] = act[r * as + sp.act_off[nl] + c];
+      }
+      __syncthreads();
+      continue;
+    }
     for (int r = tid; r < nr; r += nt) {
       const float *out = act + r * as + sp.act_off[nl];
       float v;

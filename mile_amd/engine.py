@@ -526,6 +526,26 @@ class Engine:
                                                       _ptr(out), self._stream()), self.lib)
         return out.reshape(*lead, X.shape[0])
 
+    def predict(self, theta, X) -> torch.Tensor:
+        """Raw network outputs for every sample and test row: theta [..., d] -> [..., N, O], O the width of the last layer
+        (``module.apply`` in predict_from_samples, src/inference/evaluation.py:16-43): (mu, log sigma) unclipped or the
+        logits, NaN / inf untouched.  Computed by the HIP forward kernels of pointwise_loglik (mile_predict)."""
+        theta = _f32(theta, self.device, name='theta')
+        lead = theta.shape[:-1]
+        th = theta.reshape(-1, self.d).contiguous()
+        X = _f32(X, self.device, name='X')
+        if isinstance(self.spec, IMAGE_SPECS) and X.ndim == 4:
+            X = X.reshape(X.shape[0], -1).contiguous()
+        if X.ndim != 2 or X.shape[1] != self.spec.in_features:
+            raise ValueError('X must be [N, F]')
+        _check_tokens(self.spec, X)
+        O = self.spec.hidden_structure[-1]
+        out = torch.empty((th.shape[0], X.shape[0], O), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_predict(self._h, _ptr(th), th.shape[0], _ptr(X), X.shape[0], _ptr(out),
+                                             self._stream()), self.lib)
+        return out.reshape(*lead, X.shape[0], O)
+
     @property
     def supports_device_tuner(self) -> bool:
         return self.d >= 4
