@@ -3,7 +3,7 @@
 mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
 src/inference/metrics.py:247-312):
 
-    python evaluate.py -e results/mile_amd/<experiment> [--split test]
+    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]]
 
 Reloads config.yaml and the samples/<chain>/sample_<n>.npz files, rebuilds the data split with the same
 seed, evaluates all C x S samples on the split in one device pass and writes metrics.json next to them.
@@ -77,8 +77,38 @@ def predictive_metrics(eng, samples, x, y, task, seed, coverages, with_rmse=True
     return res
 
 
-def main():
+def diagnostic_metrics(samples, spec, n_splits, device):
+    """--diagnostics: ESS, split R-hat and within / between chain variance of EVERY parameter of the finite chains
+    (mile_amd.metrics.chain_diagnostics; the reference's experiments/diagnostics + plot_effective_sample_size /
+    plot_split_chain_r_hat, src/visualization/samples.py:158-212).  samples [C, S, d] (host).  Returns the metrics.json
+    keys and the full arrays for diagnostics.npz; ({}, None) without the flag (``n_splits`` None)."""
+    if n_splits is None:
+        return {}, None
+    from mile_amd.metrics import chain_diagnostics
+    fin = np.isfinite(samples).all(axis=(1, 2))
+    ok = np.ascontiguousarray(samples[fin])
+    if ok.shape[0] == 0:
+        raise SystemExit('--diagnostics: no chain with finite samples')
+    res = chain_diagnostics(torch.from_numpy(ok).to(device), n_splits)
+    arr = {k: v.detach().cpu().numpy() for k, v in res.items()}
+    out = {'diag_n_splits': int(n_splits),
+           'diag_ess_min': float(np.nanmin(arr['ess'])), 'diag_ess_median': float(np.nanmedian(arr['ess'])),
+           'diag_crhat_median': float(np.nanmedian(arr['crhat'])), 'diag_crhat_max': float(np.nanmax(arr['crhat'])),
+           'diag_rhat_median': float(np.nanmedian(arr['rhat'])), 'diag_rhat_max': float(np.nanmax(arr['rhat'])),
+           'diag_wcv_median': float(np.nanmedian(arr['wcv'])), 'diag_bcv_median': float(np.nanmedian(arr['bcv']))}
+    # per-layer means, keyed by leaf name as plot_effective_sample_size / plot_split_chain_r_hat return them
+    for key in ('ess', 'crhat'):
+        out[f'diag_{key}_layer_mean'] = {name: float(np.mean(arr[key][:, off:off + int(np.prod(shape))]))
+                                         for name, off, shape in spec.leaves()}
+    return out, arr
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description='LPPD / NLL of the samples of an experiment directory')
+    ap.add_argument('--diagnostics', type=int, nargs='?', const=2, default=None, metavar='N_SPLITS',
+                    help='per-parameter chain diagnostics of ALL parameters (ESS, split R-hat with N_SPLITS splits, default 2, '
+                         'within / between chain variance): diag_* keys in metrics.json and the arrays in diagnostics.npz; the HIP '
+                         'kernels take 4 <= n_samples <= 4096, other lengths run in plain torch')
     ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
     ap.add_argument('--split', default='test', choices=['train', 'valid', 'test'])
     ap.add_argument('--device', default='cuda:0')
@@ -88,7 +118,11 @@ def main():
     ap.add_argument('--seed', type=int, default=42, help='seed of the posterior-predictive draws behind ACC / coverage')
     ap.add_argument('--coverages', type=float, nargs='+', default=[0.5, 0.75, 0.9, 0.95],
                     help='nominal coverage levels of the central credible intervals (regression)')
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     exp = Path(args.exp)
     from mile_amd.callbacks import load_samples_from_dir
     from mile_amd.config import Config
@@ -181,8 +215,12 @@ def main():
                     'time_sampling_s': t_sampling,
                     'ess_per_s_min': float(np.nanmin(ess) / t_sampling) if t_sampling else None,
                     'ess_per_s_median': float(np.nanmedian(ess) / t_sampling) if t_sampling else None})
+    diag, diag_arrays = diagnostic_metrics(samples, spec, args.diagnostics, args.device)
+    out.update(diag)
+    if diag_arrays is not None:
+        np.savez(exp / 'diagnostics.npz', **diag_arrays)
     (exp / 'metrics.json').write_text(json.dumps(out, indent=1) + '\n')
-    print(json.dumps({k: v for k, v in out.items() if not isinstance(v, list)}))        # the per-chain arrays stay in metrics.json
+    print(json.dumps({k: v for k, v in out.items() if not isinstance(v, (list, dict))}))        # the per-chain arrays stay in metrics.json
 
 
 if __name__ == '__main__':

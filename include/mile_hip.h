@@ -366,6 +366,36 @@ int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, int32_t S, co
  * log-probability.  (Added under ABI 10: a new symbol, no struct or existing entry changed.) */
 int32_t mile_predict(mile_sampler *s, const float *theta, int32_t S, const float *X, int64_t N, float *out, void *stream);
 
+/* Which outputs mile_chain_diagnostics computes (`what`), and how it reads its input. */
+#define MILE_DIAG_WCV 1u
+#define MILE_DIAG_BCV 2u
+#define MILE_DIAG_ESS 4u
+#define MILE_DIAG_CRHAT 8u
+#define MILE_DIAG_RHAT 16u
+#define MILE_DIAG_POOLED_INPUT 32u /* samples already hold the pooled normal scores: ESS and RHAT only */
+#define MILE_DIAG_S_MIN 4
+#define MILE_DIAG_S_MAX 4096
+#define MILE_DIAG_POOL_MAX 16384   /* C * S up to which the pooled ranking runs in the library */
+
+/* Replaces: between_chain_var, within_chain_var, effective_sample_size, split_chain_r_hat and gelman_split_r_hat
+ * (src/inference/metrics.py:226-244, 354-405, 449-523), all rank-normalised as the reference's defaults, for every
+ * parameter at once.  Needs no model, so it takes no mile_sampler; it launches on the current device.
+ * samples [C][S][d] fp32, d contiguous (device).  Outputs (device, null where not asked for): wcv, bcv, rhat [d];
+ * ess, crhat [C][d].  ess[c][p] is the single-chain estimator of mile_amd/diagnostics.py on chain c of the scores ranked
+ * over all C*S draws of p; crhat[c][p] ranks chain c alone and splits it n_splits ways; rhat[p] uses all C*n_splits
+ * pieces of the pooled scores.  Ties get their average rank; a NaN draw makes every score ranked with it NaN.
+ * MILE_ERR_INVALID, with nothing launched: C outside [1, 65535], S outside [MILE_DIAG_S_MIN, MILE_DIAG_S_MAX], d < 1,
+ * n_splits < 1 or not a divisor of S, S / n_splits < 2, no or unknown bits in `what`, a null pointer for an output asked
+ * for, WCV / BCV / CRHAT together with MILE_DIAG_POOLED_INPUT, and ESS / RHAT on raw draws with C*S > MILE_DIAG_POOL_MAX
+ * (rank those outside and pass the scores with MILE_DIAG_POOLED_INPUT).  MILE_ERR_STATE, with nothing launched: a workspace
+ * below that of min(d, 32) parameters.  mile_chain_diagnostics_workspace returns the size that lets the call run in the
+ * fewest launches it will use (parameters are walked in chunks that fit the workspace given); -1 for a bad shape.
+ * (Added under ABI 10: two new symbols, no struct or existing entry changed.) */
+int32_t mile_chain_diagnostics(const float *samples, int32_t C, int32_t S, int64_t d, int32_t n_splits, uint32_t what,
+                               float *wcv, float *bcv, float *ess, float *crhat, float *rhat, void *workspace,
+                               int64_t workspace_bytes, void *stream);
+int64_t mile_chain_diagnostics_workspace(int32_t C, int32_t S, int64_t d, uint32_t what);
+
 /* Size the NUTS trajectory buffers (ends, momentum sums, proposals, [E, max_num_doublings, d] U-turn checkpoints) for
  * ensembles of up to E chains, and the grad workspace as mile_reserve.  Allocation happens here, never in a launch. */
 int32_t mile_nuts_reserve(mile_sampler *s, int32_t E, int32_t max_num_doublings);

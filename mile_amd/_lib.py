@@ -16,6 +16,8 @@ REFRESH_IDS = {'O-step-O': 0, 'step-O': 1}
 GRAD_KERNEL_IDS = {'auto': 0, 'generic': 1, 'mfma_w64': 2, 'mfma_w128_bf16': 3, 'gemm_f32': 4, 'lenet_f32': 5, 'mfma_w64_bf16x3': 6,
                    'mfma_wide_bf16x3': 7, 'mfma_wide_bf16': 8, 'lenet_bf16': 9, 'mfma_narrow_f32': 10,
                    'lenetti_f32': 11, 'attn_f32': 12, 'attn_pre_f32': 13, 'attn_wide_f32': 14}
+DIAG_BITS = {'wcv': 1, 'bcv': 2, 'ess': 4, 'crhat': 8, 'rhat': 16, 'pooled_input': 32}     # MILE_DIAG_*
+DIAG_S_MIN, DIAG_S_MAX, DIAG_POOL_MAX = 4, 4096, 16384
 MODEL_IDS = {'fcn': 0, 'lenet': 1, 'lenetti': 2, 'attn': 3, 'attn_pretrained': 4, 'attn_wide': 5}
 
 
@@ -132,6 +134,9 @@ SIGNATURES = {
     'mile_pointwise_loglik': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_void_p, C.c_void_p]),
     'mile_predict': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    'mile_chain_diagnostics': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'mile_chain_diagnostics_workspace': (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_uint32]),
     'mile_debug_noise': (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
                                      C.c_void_p, C.c_void_p]),
     'mile_debug_prefill_count': (C.c_int64, [C.c_void_p]),

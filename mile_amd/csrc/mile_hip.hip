@@ -28,6 +28,7 @@
 #include "mile_predict.h"
 #include "mile_update.h"
 #include "mile_nuts.h"
+#include "mile_diag.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -2125,6 +2126,57 @@ extern "C" int32_t mile_predict(mile_sampler *s, const float *theta, int32_t S, 
   if (N < 1 || N > 0x3fffffff) return fail(MILE_ERR_INVALID, "mile_predict: N out of range");
   if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
   return evaluate_rows(s, theta, S, X, nullptr, N, out, stream);
+}
+
+// mile_chain_diagnostics: every check before any launch; parameters in chunks that fit the workspace --------------------------
+static int diag_shape_ok(int32_t C, int32_t S, int64_t d) {
+  return C >= 1 && C <= DIAG_C_MAX && S >= DIAG_S_MIN && S <= DIAG_S_MAX && d >= 1 && d <= ((int64_t)1 << 40);
+}
+static const int64_t DIAG_WS_TARGET = (int64_t)256 << 20;   // workspace asked for: chunks of as many parameters as fit in it
+
+extern "C" int64_t mile_chain_diagnostics_workspace(int32_t C, int32_t S, int64_t d, uint32_t what) {
+  if (!diag_shape_ok(C, S, d)) return -1;
+  const int64_t per = diag_param_bytes(C, S, what);
+  const int64_t chunk = std::max<int64_t>(DIAG_TILE, DIAG_WS_TARGET / per / DIAG_TILE * DIAG_TILE);
+  return per * std::min<int64_t>(d, chunk);
+}
+
+extern "C" int32_t mile_chain_diagnostics(const float *samples, int32_t C, int32_t S, int64_t d, int32_t n_splits, uint32_t what,
+                                          float *wcv, float *bcv, float *ess, float *crhat, float *rhat, void *workspace,
+                                          int64_t workspace_bytes, void *stream) {
+  const uint32_t outs = MILE_DIAG_WCV | MILE_DIAG_BCV | MILE_DIAG_ESS | MILE_DIAG_CRHAT | MILE_DIAG_RHAT;
+  if (!samples) return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: null samples");
+  if (!diag_shape_ok(C, S, d)) return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: needs 1 <= C <= 65535, 4 <= S <= 4096, d >= 1");
+  if (n_splits < 1 || S % n_splits) return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: n_splits must divide S");
+  if (S / n_splits < 2) return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: fewer than 2 draws per split");
+  if (!(what & outs) || (what & ~(outs | MILE_DIAG_POOLED_INPUT))) return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: bad `what`");
+  if (((what & MILE_DIAG_WCV) && !wcv) || ((what & MILE_DIAG_BCV) && !bcv) || ((what & MILE_DIAG_ESS) && !ess) ||
+      ((what & MILE_DIAG_CRHAT) && !crhat) || ((what & MILE_DIAG_RHAT) && !rhat))
+    return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: null pointer for an output asked for");
+  const bool pooled_in = what & MILE_DIAG_POOLED_INPUT;
+  if (pooled_in && (what & (MILE_DIAG_WCV | MILE_DIAG_BCV | MILE_DIAG_CRHAT)))
+    return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: wcv, bcv and crhat need the raw draws");
+  if (!pooled_in && (what & (MILE_DIAG_ESS | MILE_DIAG_RHAT)) && (int64_t)C * S > DIAG_POOL_MAX)
+    return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: unsupported: C * S > 16384 pooled draws (pass pooled scores)");
+  const int64_t per = diag_param_bytes(C, S, what);
+  if (!workspace || workspace_bytes < per * std::min<int64_t>(d, DIAG_TILE))
+    return fail(MILE_ERR_STATE, "mile_chain_diagnostics: workspace too small");
+  int64_t chunk = std::min<int64_t>(d, workspace_bytes / per);
+  if (chunk < d) chunk = chunk / DIAG_TILE * DIAG_TILE;
+  chunk = std::min<int64_t>(chunk, 1 << 20);
+  DiagParams p{};
+  p.samples = samples; p.C = C; p.S = S; p.n_splits = n_splits; p.d = d; p.what = what;
+  p.wcv = wcv; p.bcv = bcv; p.ess = ess; p.crhat = crhat; p.rhat = rhat;
+  p.stat = (double *)workspace;                                      // [chunk][C][DIAG_NSTAT], then the fp32 planes
+  float *planes = (float *)((char *)workspace + chunk * C * DIAG_NSTAT * 8);
+  p.raw = pooled_in ? nullptr : planes;
+  p.z = pooled_in ? planes : planes + chunk * C * S;
+  for (int64_t p0 = 0; p0 < d; p0 += chunk) {
+    p.p0 = p0;
+    p.P = (int)std::min<int64_t>(chunk, d - p0);
+    HIP_TRY(mile_launch_diag(p, (hipStream_t)stream));
+  }
+  return MILE_OK;
 }
 
 extern "C" {

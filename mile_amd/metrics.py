@@ -102,6 +102,142 @@ def effective_sample_size(x: torch.Tensor, rank_normalize: bool = True) -> torch
     return out.reshape(C, *x.shape[2:])
 
 
+# ---- chain diagnostics (src/inference/metrics.py:354-383, 449-523): plain torch here, which is also what CPU tensors get;
+# chain_diagnostics sends CUDA fp32 draws through the library's fused kernels (mile_chain_diagnostics) instead.
+
+def between_chain_var(x: torch.Tensor) -> torch.Tensor:
+    """metrics.py:354-367: x [C, S, ...] -> ddof-1 variance of the C chain means (NaN for one chain, as NumPy's)."""
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        return x.mean(dim=1).var(dim=0, unbiased=True)
+
+
+def within_chain_var(x: torch.Tensor) -> torch.Tensor:
+    """metrics.py:370-383: x [C, S, ...] -> mean over chains of the ddof-1 variance over S."""
+    return x.var(dim=1, unbiased=True).mean(dim=0)
+
+
+def rank_normalize_columns(x2: torch.Tensor) -> torch.Tensor:
+    """x2 [n, m] -> float64 normal scores of every column ranked over its n entries, average rank for ties (what
+    rank_normalize_array gives column by column), from ONE batched sort.  A column with a NaN is NaN throughout."""
+    n = x2.shape[0]
+    sv, order = torch.sort(x2.to(torch.float64), dim=0, stable=True)
+    pos = torch.arange(n, device=x2.device, dtype=torch.int64)[:, None].expand_as(order)
+    first = torch.ones_like(order, dtype=torch.bool)
+    first[1:] = sv[1:] != sv[:-1]
+    last = torch.ones_like(first)
+    last[:-1] = first[1:]
+    lo = torch.cummax(torch.where(first, pos, torch.zeros_like(pos)), dim=0).values
+    hi = torch.flip(torch.cummin(torch.flip(torch.where(last, pos, torch.full_like(pos, n)), [0]), dim=0).values, [0])
+    ranks = torch.empty_like(sv).scatter_(0, order, (lo + hi).to(torch.float64) * 0.5 + 1.0)
+    z = torch.special.ndtri((ranks - 0.375) / (n + 0.25))
+    return torch.where(torch.isnan(sv[-1:]).expand_as(z), torch.full_like(z, float('nan')), z)
+
+
+def _pooled_scores(x: torch.Tensor) -> torch.Tensor:
+    """x [C, S, ...] -> float64 scores of every trailing column ranked over its pooled C*S draws."""
+    C, S = x.shape[:2]
+    return rank_normalize_columns(x.reshape(C * S, -1)).reshape(x.shape)
+
+
+def gelman_split_r_hat(samples: torch.Tensor, n_splits: int, rank_normalize: bool = True) -> torch.Tensor:
+    """metrics.py:449-494: split R-hat over all C * n_splits pieces, samples [C, S, ...] -> [...] (float64)."""
+    import warnings
+    C, S = samples.shape[:2]
+    if S % n_splits:
+        raise ValueError('Number of samples must be divisible by n_splits')
+    n = S // n_splits
+    if n < 50:
+        warnings.warn(message='Number of samples should be at least 50x the number of splits', category=UserWarning)
+    z = _pooled_scores(samples) if rank_normalize else samples.to(torch.float64)
+    splits = z.reshape(C * n_splits, n, *samples.shape[2:])
+    wcv, bcv = within_chain_var(splits), between_chain_var(splits)
+    return torch.sqrt(((n - 1) / n * wcv + bcv) / wcv)
+
+
+def split_chain_r_hat(samples: torch.Tensor, n_splits: int, rank_normalize: bool = True) -> torch.Tensor:
+    """metrics.py:497-523: gelman_split_r_hat of every chain on its own (ranked within the chain) -> [C, ...]."""
+    return torch.stack([gelman_split_r_hat(ch[None], n_splits, rank_normalize) for ch in samples])
+
+
+LAST_DIAG_PATH = None       # how the last chain_diagnostics call ran: 'torch', 'library' or 'library+torch_sort'
+
+
+def _library_diagnostics(x: torch.Tensor, n_splits: int) -> dict:
+    """x [C, S, d] contiguous CUDA fp32 -> the five statistics from mile_chain_diagnostics.  Past the library's pooled
+    bound (C*S > DIAG_POOL_MAX) only the pooled ranking is done here, one batched torch.sort per chunk of columns, and the
+    scores go back into the same ESS / R-hat kernels."""
+    global LAST_DIAG_PATH
+    import ctypes as Ct
+    from mile_amd import _lib
+    lib = _lib.load_library()
+    B = _lib.DIAG_BITS
+    C, S, d = x.shape
+    dev = x.device
+    new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+    out = {'ess': new(C, d), 'crhat': new(C, d), 'rhat': new(d), 'wcv': new(d), 'bcv': new(d)}
+    ptr = lambda t: Ct.c_void_p(t.data_ptr()) if t is not None else None
+
+    def call(src, what, **o):
+        dd = src.shape[2]
+        nbytes = lib.mile_chain_diagnostics_workspace(C, S, dd, what)
+        ws = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dev)
+        stream = Ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.mile_chain_diagnostics(ptr(src), C, S, dd, n_splits, what, ptr(o.get('wcv')), ptr(o.get('bcv')),
+                                              ptr(o.get('ess')), ptr(o.get('crhat')), ptr(o.get('rhat')), ptr(ws), ws.numel(),
+                                              stream), lib)
+
+    with torch.cuda.device(dev):
+        if C * S <= _lib.DIAG_POOL_MAX:
+            call(x, B['wcv'] | B['bcv'] | B['ess'] | B['crhat'] | B['rhat'], **out)
+            LAST_DIAG_PATH = 'library'
+        else:
+            call(x, B['wcv'] | B['bcv'] | B['crhat'], wcv=out['wcv'], bcv=out['bcv'], crhat=out['crhat'])
+            step = max(1, (1 << 28) // (C * S * 8))                 # columns per sort: the fp64 keys stay under 256 MB
+            for k0 in range(0, d, step):
+                z = _pooled_scores(x[:, :, k0:k0 + step]).to(torch.float32).contiguous()
+                ess, rhat = new(C, z.shape[2]), new(z.shape[2])
+                call(z, B['ess'] | B['rhat'] | B['pooled_input'], ess=ess, rhat=rhat)
+                out['ess'][:, k0:k0 + step] = ess
+                out['rhat'][k0:k0 + step] = rhat
+            LAST_DIAG_PATH = 'library+torch_sort'
+    return out
+
+
+def chain_diagnostics(samples: torch.Tensor, n_splits: int = 2) -> dict:
+    """samples [C, S, ...] -> {'ess' [C, ...], 'crhat' [C, ...], 'rhat' [...], 'wcv' [...], 'bcv' [...]}: the reference's
+    effective_sample_size, split_chain_r_hat and gelman_split_r_hat (rank-normalised) and within / between chain variance
+    of every parameter.  CUDA fp32 draws run in the library's fused kernels (fp32 results); anything else in the torch
+    functions above (float64 results) -- CPU tensors, other dtypes, and, with a UserWarning, chains shorter than 4 or
+    longer than 4096 draws, which the kernels do not take."""
+    global LAST_DIAG_PATH
+    import warnings
+    C, S = samples.shape[:2]
+    if S % n_splits:
+        raise ValueError('Number of samples must be divisible by n_splits')
+    if S // n_splits < 50:
+        warnings.warn(message='Number of samples should be at least 50x the number of splits', category=UserWarning)
+    trail = tuple(samples.shape[2:])
+    from mile_amd._lib import DIAG_S_MAX, DIAG_S_MIN
+    in_range = DIAG_S_MIN <= S <= DIAG_S_MAX
+    if samples.is_cuda and samples.dtype == torch.float32 and not in_range:
+        warnings.warn(f'chain_diagnostics: {S} draws per chain is outside the range of the HIP kernels '
+                      f'[{DIAG_S_MIN}, {DIAG_S_MAX}]; using the torch functions', category=UserWarning)
+    if samples.is_cuda and samples.dtype == torch.float32 and in_range:
+        res = _library_diagnostics(samples.reshape(C, S, -1).contiguous(), n_splits)
+        return {k: v.reshape(*((C,) if k in ('ess', 'crhat') else ()), *trail) for k, v in res.items()}
+    from mile_amd.diagnostics import effective_sample_size as ess1
+    x = samples.to(torch.float64)
+    z = _pooled_scores(x).reshape(C, S, -1)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', UserWarning)              # (already raised above, once)
+        crhat, rhat = split_chain_r_hat(x, n_splits), gelman_split_r_hat(x, n_splits)
+    LAST_DIAG_PATH = 'torch'
+    return {'ess': torch.stack([ess1(z[c][None]) for c in range(C)]).reshape(C, *trail), 'crhat': crhat, 'rhat': rhat,
+            'wcv': within_chain_var(x), 'bcv': between_chain_var(x)}
+
+
 # ---- the rest of evaluate_bde's report (src/inference/evaluation.py:46-137,409-544): draws from the raw outputs of
 # Engine.predict, then ACC, RMSE, coverage and calibration error.  Plain torch on the tensors' device, no loop over samples.
 
