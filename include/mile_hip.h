@@ -396,7 +396,32 @@ int32_t mile_chain_diagnostics(const float *samples, int32_t C, int32_t S, int64
                                int64_t workspace_bytes, void *stream);
 int64_t mile_chain_diagnostics_workspace(int32_t C, int32_t S, int64_t d, uint32_t what);
 
-/* Size the NUTS trajectory buffers (ends, momentum sums, proposals, [E, max_num_doublings, d] U-turn checkpoints) for
+/* Partition sampling (sampler.partition_sampling of the reference: src/training/partition_sampling.py:304-315 partition_params,
+ * src/training/trainer.py:593-659): only the FIRST and the LAST layer of an FCN are sampled; every other layer keeps, per chain,
+ * the values of `frozen`.  Target: log_prior(sampled coordinates only) + log_likelihood(full net on sampled U frozen).
+ * frozen [E, d] full-layout rows (d = mile_param_count), COPIED into rows the library owns; their sampled coordinates are
+ * overwritten by every gradient call.  Call it before mile_reserve (it drops the workspace); calling it again replaces the
+ * rows.  From then on mile_logpost_grad, mile_init, mile_step and mile_tune take and return COMPACT arrays: every [E, d]
+ * (theta, grad, the mile_state, noise, sqrt_diag_cov, out_samples; stream_average [E, 2, d]) is [E, d_s], d_s =
+ * mile_partition_dim, the sampled segments (mile_partition_segments) concatenated in full-row order, and d_s is the dimension
+ * in every formula of the integrator and the tuner.  Philox streams are keyed by the index inside the compact row.  E of those
+ * calls must equal the frozen rows' E.  mile_param_count / mile_param_offsets stay full-layout, and so do
+ * mile_pointwise_loglik, mile_predict and mile_warmstart_step (give them merged rows).
+ * AUTO keeps its choice; where that is MFMA_NARROW_F32 the partition form of k_grad_narrow reads both sources itself, skips the
+ * hidden layers' dW / db and writes slabs of width d_s; every other FCN kernel runs unchanged on the library's full rows between
+ * a scatter and a gather launch.  An FCN with <= 2 layers has no frozen layer: d_s = d and the ordinary path runs.
+ * MILE_ERR_INVALID: a model other than MILE_MODEL_FCN; E < 1; later, E different from the frozen rows', and mile_nuts_*
+ * on a handle in partition mode (not built).
+ * (Added under ABI 10: three new symbols, no struct or existing entry changed.) */
+int32_t mile_set_partition(mile_sampler *s, const float *frozen, int32_t E, void *stream);
+/* d_s in partition mode; mile_param_count otherwise. */
+int64_t mile_partition_dim(const mile_sampler *s);
+/* The sampled segments of the full row in full-row order: begin[i], length[i] for i < the return value (at most 4:
+ * layer0.bias|kernel are adjacent, so are the last layer's; lexicographic layer order decides whether the two pairs touch).
+ * Null pointers are allowed (count only).  0 segments outside partition mode; negative mile_status on error. */
+int32_t mile_partition_segments(const mile_sampler *s, int64_t *begin, int64_t *length, int32_t capacity);
+
+/* Size the NUTS trajectory buffers (ends,momentum sums, proposals, [E, max_num_doublings, d] U-turn checkpoints) for
  * ensembles of up to E chains, and the grad workspace as mile_reserve.  Allocation happens here, never in a launch. */
 int32_t mile_nuts_reserve(mile_sampler *s, int32_t E, int32_t max_num_doublings);
 

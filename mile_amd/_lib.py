@@ -122,6 +122,9 @@ SIGNATURES = {
     'mile_set_data': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'mile_set_embedding': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'mile_set_row_window': (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64]),
+    'mile_set_partition': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    'mile_partition_dim': (C.c_int64, [C.c_void_p]),
+    'mile_partition_segments': (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]),
     'mile_reserve': (C.c_int32, [C.c_void_p, C.c_int32]),
     'mile_slab_bytes': (C.c_int64, [C.c_void_p]),
     'mile_warmstart_step': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(OptimArgsC), C.c_void_p]),

@@ -242,6 +242,11 @@ class SamplerConfig:
                                     'mfma_wide_bf16', 'lenet_f32', 'lenet_bf16', 'mfma_narrow_f32', 'lenetti_f32', 'attn_f32',
                                     'attn_wide_f32'),
                f'unknown grad_kernel {self.grad_kernel!r}')
+        _check(isinstance(self.partition_sampling, bool), 'sampler.partition_sampling must be true or false')
+        _check(not (self.partition_sampling and self.name == 'nuts'),
+               'sampler.partition_sampling with sampler.name: nuts is not built yet (partition sampling runs with mclmc)')
+        _check(not (self.partition_sampling and self.name == 'hmc'),
+               'sampler.partition_sampling with sampler.name: hmc is not built (partition sampling runs with mclmc)')
 
     @property
     def prior(self) -> Prior:
@@ -283,6 +288,11 @@ class WarmStartConfig:
     patience: int | None = None
     partition_warmstart: bool = False
 
+    def __post_init__(self):
+        _check(not self.partition_warmstart,
+               'warmstart.partition_warmstart is not built: the warm-start stage trains every layer '
+               '(sampler.partition_sampling, the partition of the sampling stage, is)')
+
     @property
     def _dir_name(self):
         return 'warmstart'
@@ -306,6 +316,13 @@ class Config:
     saving_dir: str = 'results/'
     rng: int = 42
     logging: bool = True
+
+    def __post_init__(self):
+        sampler = getattr(self.training, 'sampler', None)
+        if getattr(sampler, 'partition_sampling', False):
+            _check(isinstance(self.model, FCNConfig),
+                   f'sampler.partition_sampling samples the first and the last Dense layer of an FCN; model '
+                   f"{getattr(self.model, 'model', type(self.model).__name__)} has no partition")
 
     @classmethod
     def from_dict(cls, d: dict) -> 'Config':

@@ -28,6 +28,11 @@ struct GradParams {
   // in k_grad_w64<3, 1, true>, 2.4 % slower on B2.
   long long *dbg_buf;
   int32_t dbg;
+  // Partition sampling, k_grad_narrow<.., PART = true> only (unset otherwise): theta is then the COMPACT [E, part_d] array (first
+  // and last layer), slabs are [E, S, dp] with dp = part_d rounded up, and the hidden layers come from part_frozen.
+  int32_t part_d = 0;
+  int32_t part_b0 = 0, part_w0 = 0, part_bl = 0, part_wl = 0;   // bias / kernel of the first and the last layer inside the compact row
+  const float *part_frozen = nullptr;                           // [E, d] full-layout rows of the chains
 };
 
 // Per-row log-likelihood and d/d(out).  NaN rows contribute nothing (jnp.nansum).

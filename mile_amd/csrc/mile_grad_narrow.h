@@ -71,7 +71,14 @@ __device__ __forceinline__ f32x4 nrw_transpose(float *img, int g, int c, const f
 __device__ __forceinline__ float nrw_xor16(float v) { return __shfl_xor(v, 16, 64); }
 __device__ __forceinline__ float nrw_xor32(float v) { return __shfl_xor(v, 32, 64); }
 
-template <int NH, int TH, int TF, bool WL = false>
+//
+// PART = true, partition sampling (mile_set_partition: only the first and the last layer are sampled).  p.theta is the compact
+// [E, part_d] array holding those two layers, the hidden layers are read from the chain's own row of p.part_frozen, and the slab
+// row has the compact layout too (p.dp = part_d rounded up).  The forward pass and the whole dH chain run as before -- layer0's
+// gradient needs the chain -- but no hidden layer's dW / db is formed: their MFMAs, the L2 -> L1 copies that feed them (every
+// hidden activation tile but the last, every hidden dZ tile but the first layer's), their accumulators, their share of the
+// cross-wave reduction and their stores are gone.
+template <int NH, int TH, int TF, bool WL = false, bool PART = false>
 static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const GradParams p) {
   extern __shared__ __attribute__((aligned(16))) float nrw_lds[];
   using LY = NarrowLayout<NH, TH, TF, WL>;
@@ -81,7 +88,10 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
   const int e = blockIdx.y, s = blockIdx.x;
   const int F = sp.in_features, K = sp.widths[NH], act = sp.activation;
   const bool regr = sp.task == MILE_TASK_REGRESSION;
-  const float *th = p.theta + (size_t)e * sp.d;
+  const float *th = p.theta + (size_t)e * (PART ? p.part_d : sp.d);           // first and last layer
+  const float *thh = PART ? p.part_frozen + (size_t)e * sp.d : th;            // hidden layers
+  const int ob0 = PART ? p.part_b0 : sp.b_off[0], ow0 = PART ? p.part_w0 : sp.w_off[0];
+  const int obl = PART ? p.part_bl : sp.b_off[NH], owl = PART ? p.part_wl : sp.w_off[NH];
   float *img = nrw_lds + wave * 16 * NRW_TS;
 
   // ---- weights -> registers, both operand arrangements (zero beyond the real widths) ---------------------------------
@@ -97,7 +107,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
     const int nt = blockDim.x;
     {  // first layer, forward image [in][out]
       const int o0 = sp.widths[0];
-      const float *W = th + sp.w_off[0];
+      const float *W = th + ow0;
       for (int i = tid; i < 16 * TF * LY::SH; i += nt) {
         const int in = i / LY::SH, out = i - in * LY::SH;
         wimg[LY::W0F + i] = (in < F && out < o0) ? W[in * o0 + out] : 0.0f;
@@ -106,7 +116,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
 #pragma unroll
     for (int l = 1; l < NH; ++l) {
       const int wi = sp.widths[l - 1], wo = sp.widths[l];
-      const float *W = th + sp.w_off[l];
+      const float *W = thh + sp.w_off[l];
       float *Wf = wimg + LY::WHF + (l - 1) * LY::HP * LY::SH, *Wb = wimg + LY::WHB + (l - 1) * LY::HP * LY::SH;
       for (int i = tid; i < LY::HP * LY::SH; i += nt) {
         const int r = i / LY::SH, q = i - r * LY::SH;
@@ -116,7 +126,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
     }
     {
       const int wi = sp.widths[NH - 1];
-      const float *W = th + sp.w_off[NH];
+      const float *W = th + owl;
       for (int i = tid; i < LY::HP * LY::SL; i += nt) {
         const int in = i / LY::SL, k = i - in * LY::SL;
         wimg[LY::WLF + i] = (in < wi && k < K) ? W[in * K + k] : 0.0f;
@@ -151,7 +161,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
   };
   {
     const int o0 = sp.widths[0];
-    const float *W = th + sp.w_off[0], *B = th + sp.b_off[0];
+    const float *W = th + ow0, *B = th + ob0;
     if constexpr (!WL) {
 #pragma unroll
     for (int ti = 0; ti < TF; ++ti)
@@ -171,7 +181,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
 #pragma unroll
   for (int l = 1; l < NH; ++l) {
     const int wi = sp.widths[l - 1], wo = sp.widths[l];
-    const float *W = th + sp.w_off[l], *B = th + sp.b_off[l];
+    const float *W = thh + sp.w_off[l], *B = thh + sp.b_off[l];
     if constexpr (!WL) {
 #pragma unroll
     for (int ti = 0; ti < TH; ++ti)
@@ -193,7 +203,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
   }
   {
     const int wi = sp.widths[NH - 1];
-    const float *W = th + sp.w_off[NH], *B = th + sp.b_off[NH];
+    const float *W = th + owl, *B = th + obl;
     if constexpr (!WL) {
 #pragma unroll
     for (int ti = 0; ti < TH; ++ti)
@@ -282,7 +292,8 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
 #pragma unroll
     for (int l = 0; l < NH; ++l)
 #pragma unroll
-      for (int t = 0; t < TH; ++t) h1[l][t] = nrw_transpose(img, g, c, h2[l][t]);
+      for (int t = 0; t < TH; ++t)
+        if (!PART || l == NH - 1) h1[l][t] = nrw_transpose(img, g, c, h2[l][t]);   // (PART: only dW_last reads an L1 activation)
 
     // ---- head: log-likelihood of row c and d(out), probabilistic.py:92-109, NaN rows contribute nothing (nansum) ----
     f32x4 dz2 = {0, 0, 0, 0};                          // dZ_last^T in L2
@@ -333,6 +344,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
     }
 #pragma unroll
     for (int l = NH - 1; l >= 1; --l) {
+      if constexpr (!PART) {
 #pragma unroll
       for (int t = 0; t < TH; ++t) {
         dzh1[t] = nrw_transpose(img, g, c, dzh2[t]);
@@ -344,6 +356,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
         for (int t = 0; t < TH; ++t)
 #pragma unroll
           for (int j = 0; j < 4; ++j) dwh[l - 1][ti][t] = nrw_mfma(h1[l - 1][ti][j], dzh1[t][j], dwh[l - 1][ti][t]);
+      }
       f32x4 nx[TH];
 #pragma unroll
       for (int ti = 0; ti < TH; ++ti) {
@@ -378,7 +391,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
 #pragma unroll
   for (int t = 0; t < TH; ++t) { db0[t] += nrw_xor16(db0[t]); db0[t] += nrw_xor32(db0[t]); }
 #pragma unroll
-  for (int l = 0; l < (NH > 1 ? NH - 1 : 1); ++l)
+  for (int l = 0; l < (PART ? 0 : (NH > 1 ? NH - 1 : 1)); ++l)
 #pragma unroll
     for (int t = 0; t < TH; ++t) { dbh[l][t] += nrw_xor16(dbh[l][t]); dbh[l][t] += nrw_xor32(dbh[l][t]); }
   dbl += nrw_xor16(dbl); dbl += nrw_xor32(dbl);
@@ -399,7 +412,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
 #pragma unroll
           for (int j = 0; j < 4; ++j) red[(k++) * 64 + lane] = dw0[ti][t][j];
 #pragma unroll
-      for (int l = 0; l < NH - 1; ++l)
+      for (int l = 0; l < (PART ? 0 : NH - 1); ++l)
 #pragma unroll
         for (int ti = 0; ti < TH; ++ti)
 #pragma unroll
@@ -413,7 +426,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
 #pragma unroll
       for (int t = 0; t < TH; ++t) red[(k++) * 64 + lane] = db0[t];
 #pragma unroll
-      for (int l = 0; l < NH - 1; ++l)
+      for (int l = 0; l < (PART ? 0 : NH - 1); ++l)
 #pragma unroll
         for (int t = 0; t < TH; ++t) red[(k++) * 64 + lane] = dbh[l][t];
       red[(k++) * 64 + lane] = dbl;
@@ -429,7 +442,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
 #pragma unroll
           for (int j = 0; j < 4; ++j) dw0[ti][t][j] += red[(k++) * 64 + lane];
 #pragma unroll
-      for (int l = 0; l < NH - 1; ++l)
+      for (int l = 0; l < (PART ? 0 : NH - 1); ++l)
 #pragma unroll
         for (int ti = 0; ti < TH; ++ti)
 #pragma unroll
@@ -443,7 +456,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
 #pragma unroll
       for (int t = 0; t < TH; ++t) db0[t] += red[(k++) * 64 + lane];
 #pragma unroll
-      for (int l = 0; l < NH - 1; ++l)
+      for (int l = 0; l < (PART ? 0 : NH - 1); ++l)
 #pragma unroll
         for (int t = 0; t < TH; ++t) dbh[l][t] += red[(k++) * 64 + lane];
       dbl += red[(k++) * 64 + lane];
@@ -454,7 +467,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
   // C layout of a dW tile: reg j of lane (g, c) = dW[in 16 ti + 4 g + j][out 16 t + c]
   {
     const int o0 = sp.widths[0];
-    float *G = slab + sp.w_off[0], *GB = slab + sp.b_off[0];
+    float *G = slab + ow0, *GB = slab + ob0;
 #pragma unroll
     for (int ti = 0; ti < TF; ++ti)
 #pragma unroll
@@ -469,7 +482,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
       if (g == 0 && 16 * t + c < o0) GB[16 * t + c] = db0[t];
   }
 #pragma unroll
-  for (int l = 1; l < NH; ++l) {
+  for (int l = 1; l < (PART ? 1 : NH); ++l) {
     const int wi = sp.widths[l - 1], wo = sp.widths[l];
     float *G = slab + sp.w_off[l], *GB = slab + sp.b_off[l];
 #pragma unroll
@@ -487,7 +500,7 @@ static __global__ __launch_bounds__(64 * NRW_MAXW) void k_grad_narrow(const Grad
   }
   {
     const int wi = sp.widths[NH - 1];
-    float *G = slab + sp.w_off[NH], *GB = slab + sp.b_off[NH];
+    float *G = slab + owl, *GB = slab + obl;
 #pragma unroll
     for (int ti = 0; ti < TH; ++ti)
 #pragma unroll

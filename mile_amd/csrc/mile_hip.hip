@@ -41,6 +41,8 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
 static const double MCLACHLAN_B1 = 0.1931833275037836;
 
+struct PartSegs { int n; int begin[4], len[4]; };   // sampled segments of the full row (mile_partition_segments)
+
 struct mile_sampler {
   mile_model_spec spec{};
   DevSpec ds{};
@@ -86,6 +88,13 @@ struct mile_sampler {
   NutsBufs nb{};
   int nuts_E = 0, nuts_M = 0;
   int32_t *nuts_count_h = nullptr;      // pinned host copy of nb.count
+  // partition sampling (mile_set_partition): the first and the last layer are sampled, the others stay at part_rows' values
+  bool part = false;
+  int part_E = 0, part_d = 0;           // chains of part_rows; d_s = sampled coordinates per chain
+  float *part_rows = nullptr;           // [part_E][d] full-layout rows: frozen layers, and what the general path scatters into
+  float *part_slabs = nullptr;          // [ES_cap][part_d rounded up] compact slabs: what the update kernels read
+  PartSegs part_seg{};                  // the sampled segments of the full row, in full-row order
+  int part_b0 = 0, part_w0 = 0, part_bl = 0, part_wl = 0;   // first / last layer's bias and kernel inside the compact row
   // timing of grad launches
   bool timing = false;
   std::vector<hipEvent_t> ev;
@@ -251,6 +260,33 @@ static int attn_wide_S_rows(const mile_sampler *s, int E, int rows) {
   return std::max(1, std::min(want, std::max(1, rows / ATTN_WIDE_MIN_ROWS)));
 }
 static int attn_wide_S(const mile_sampler *s, int E) { return attn_wide_S_rows(s, E, s->win_count ? s->win_count : s->N); }
+
+// ---- partition sampling -------------------------------------------------------------------------------------------------------
+// The dimension of everything the integrator and the tuner touch: d_s in partition mode, d otherwise.
+static int sample_dim(const mile_sampler *s) { return s->part ? s->part_d : s->ds.d; }
+static int sample_dp(const mile_sampler *s) { return (sample_dim(s) + 3) / 4 * 4; }
+static float *sample_slabs(const mile_sampler *s) { return s->part ? s->part_slabs : s->slabs; }
+
+// General path, before the grad launch: the compact rows' segments into the library's full-layout rows.
+__global__ void k_part_scatter(const float *compact, int ds, float *full, int d, PartSegs sg) {
+  const float *c = compact + (size_t)blockIdx.x * ds;
+  float *f = full + (size_t)blockIdx.x * d;
+  int o = 0;
+  for (int k = 0; k < sg.n; ++k) {
+    for (int i = threadIdx.x; i < sg.len[k]; i += blockDim.x) f[sg.begin[k] + i] = c[o + i];
+    o += sg.len[k];
+  }
+}
+// General path, after it: the sampled segments of every full-layout slab row (E * S of them) into the compact slab rows.
+__global__ void k_part_gather(const float *full, long long dp, float *compact, long long dps, PartSegs sg) {
+  const float *f = full + (size_t)blockIdx.x * dp;
+  float *c = compact + (size_t)blockIdx.x * dps;
+  int o = 0;
+  for (int k = 0; k < sg.n; ++k) {
+    for (int i = threadIdx.x; i < sg.len[k]; i += blockDim.x) c[o + i] = f[sg.begin[k] + i];
+    o += sg.len[k];
+  }
+}
 
 // Everything the library knows about one grad kernel: one row per MILE_GRAD_* id in kGrad, defined below the launchers.
 struct LaunchShape { int block, lds; };
@@ -551,6 +587,8 @@ static void free_ws(mile_sampler *s) {
   if (s->nzbuf) (void)hipFree(s->nzbuf);
   s->nzbuf = nullptr;
   s->nz_E = 0;
+  if (s->part_slabs) (void)hipFree(s->part_slabs);
+  s->part_slabs = nullptr;
   s->slabs = s->llpart = s->dK = s->lold = nullptr;
   s->E_cap = 0; s->ES_cap = 0;
 }
@@ -581,6 +619,7 @@ int32_t mile_destroy(mile_sampler *s) {
   if (s->tune_info) (void)hipFree(s->tune_info);
   if (s->emb_tab) (void)hipFree(s->emb_tab);
   if (s->pos_tab) (void)hipFree(s->pos_tab);
+  if (s->part_rows) (void)hipFree(s->part_rows);
   free_nuts(s);
   if (s->nuts_count_h) (void)hipHostFree(s->nuts_count_h);
   if (s->blas && g_rb.destroy) (void)g_rb.destroy(s->blas);
@@ -683,6 +722,49 @@ int32_t mile_set_row_window(mile_sampler *s, int64_t begin, int64_t count) {
   return MILE_OK;
 }
 
+int32_t mile_set_partition(mile_sampler *s, const float *frozen, int32_t E, void *stream) {
+  if (!s || !frozen || E < 1) return fail(MILE_ERR_INVALID, "mile_set_partition: bad argument");
+  if (!is_fcn(s)) return fail(MILE_ERR_INVALID, "mile_set_partition: partition sampling is built for the FCN only (first and last Dense layer)");
+  const int n = s->spec.n_layers;
+  if (n <= 2) return MILE_OK;   // no frozen layer: partition sampling of this net is ordinary sampling
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->device));
+  // the four sampled leaves in full-row order, adjacent ones merged into one segment
+  const DevSpec &ds = s->ds;
+  struct Leaf { int off, len, which; } lv[4] = {
+      {ds.b_off[0], ds.widths[0], 0}, {ds.w_off[0], ds.in_features * ds.widths[0], 1},
+      {ds.b_off[n - 1], ds.widths[n - 1], 2}, {ds.w_off[n - 1], ds.widths[n - 2] * ds.widths[n - 1], 3}};
+  std::sort(lv, lv + 4, [](const Leaf &a, const Leaf &b) { return a.off < b.off; });
+  PartSegs sg{};
+  int o = 0, coff[4];
+  for (const Leaf &l : lv) {
+    if (sg.n && sg.begin[sg.n - 1] + sg.len[sg.n - 1] == l.off) sg.len[sg.n - 1] += l.len;
+    else { sg.begin[sg.n] = l.off; sg.len[sg.n] = l.len; ++sg.n; }
+    coff[l.which] = o;
+    o += l.len;
+  }
+  if (s->part_rows && s->part_E != E) { (void)hipFree(s->part_rows); s->part_rows = nullptr; }
+  if (!s->part_rows) HIP_TRY(hipMalloc(&s->part_rows, (size_t)E * ds.d * 4));
+  HIP_TRY(hipMemcpyAsync(s->part_rows, frozen, (size_t)E * ds.d * 4, hipMemcpyDeviceToDevice, st));
+  if (!s->part) free_ws(s);   // the compact slabs are part of the workspace: the next mile_reserve allocates them
+  s->part = true; s->part_E = E; s->part_d = o; s->part_seg = sg;
+  s->part_b0 = coff[0]; s->part_w0 = coff[1]; s->part_bl = coff[2]; s->part_wl = coff[3];
+  return MILE_OK;
+}
+
+int64_t mile_partition_dim(const mile_sampler *s) { return s ? sample_dim(s) : -1; }
+
+int32_t mile_partition_segments(const mile_sampler *s, int64_t *begin, int64_t *length, int32_t capacity) {
+  if (!s) return fail(MILE_ERR_INVALID, "mile_partition_segments: null handle");
+  if (!s->part) return 0;
+  if ((begin || length) && capacity < s->part_seg.n) return fail(MILE_ERR_INVALID, "mile_partition_segments: capacity too small");
+  for (int k = 0; k < s->part_seg.n; ++k) {
+    if (begin) begin[k] = s->part_seg.begin[k];
+    if (length) length[k] = s->part_seg.len[k];
+  }
+  return s->part_seg.n;
+}
+
 // floats of one of the two noise-prefill arrays in s->nzbuf (E rows of d, rounded up so the second array is 16-byte aligned)
 static size_t nz_stride(int E, int d) { return ((size_t)E * d + 3) / 4 * 4; }
 
@@ -702,6 +784,7 @@ int32_t mile_reserve(mile_sampler *s, int32_t E) {
   const size_t ESn = std::max((size_t)E * S, s->ES_cap);
   free_ws(s);
   HIP_TRY(hipMalloc(&s->slabs, ESn * ((s->ds.d + 3) / 4 * 4) * 4));
+  if (s->part) HIP_TRY(hipMalloc(&s->part_slabs, ESn * sample_dp(s) * 4));
   HIP_TRY(hipMalloc(&s->llpart, ESn * 4));
   HIP_TRY(hipMalloc(&s->dK, (size_t)En * 4));
   HIP_TRY(hipMalloc(&s->lold, (size_t)En * 4));
@@ -850,6 +933,8 @@ static void launch_update(const UpdParams &u, int E, hipStream_t st) {
 // The F > 8 split kernels live in their own translation unit, built WITHOUT -amdgpu-mfma-vgpr-form: with that option
 // hipcc 7.2's 'AMDGPU Rewrite AGPR-Copy-MFMA' pass crashes on the heavily spilling k_grad_w64<3,2,true> (mile_amd/_build.py).
 hipError_t mile_launch_w64_split_fq2(int nh, const GradParams &gp, int E, hipStream_t st);
+// The partition forms of k_grad_narrow: mile_narrow_part.hip.
+hipError_t mile_launch_narrow_part(int nh, int th, int tf, int nw, const GradParams &gp, int E, hipStream_t st);
 
 template <int NH, int FQ, bool SPLIT = false>
 static hipError_t launch_w64(const GradParams &gp, const W64Fuse &fz, int E, hipStream_t st) {
@@ -868,7 +953,7 @@ static hipError_t launch_w64(const GradParams &gp, const W64Fuse &fz, int E, hip
 // Can the update that follows this gradient run as the grad launch's epilogue (k_grad_w64 SPLIT, W64Fuse)?
 // 8-byte aligned rows everywhere (the epilogue is the AL = 2 form), no preconditioner, d within its register cache.
 static bool fuse_ok(const mile_sampler *s, int kernel, const UpdParams &u) {
-  if (!MILE_W64_EPILOGUE_ON || !grad_kernel(kernel).fuses) return false;
+  if (!MILE_W64_EPILOGUE_ON || !grad_kernel(kernel).fuses || s->part) return false;   // (partition: a gather sits in between)
   if (u.sdc || u.u_rec) return false;   // (the merged warm-up launch exists as a stand-alone kernel only)
   const int nh = s->spec.n_layers - 1, fq = s->Fp / 8;
   if (fq != 1) return false;                       // the F > 8 kernels are built without the epilogue (mile_grad_w64.h)
@@ -891,6 +976,7 @@ static hipError_t launch_narrow(const mile_sampler *s, const GradParams &gp, int
   const int nh = s->spec.n_layers - 1;
   const int th = narrow_tiles_hidden(s->spec), tf = s->spec.in_features <= 16 ? 1 : 4;
   const int nw = th >= 3 ? NRW_MAXW : narrow_waves(s, gp.S, gp.N);
+  if (gp.part_frozen) return mile_launch_narrow_part(nh, th, tf, nw, gp, E, st);
 #define MILE_NRW(NH_, TH_, TF_) if (nh == NH_ && th == TH_ && tf == TF_) return launch_narrow_t<NH_, TH_, TF_>(gp, E, nw, st);
   MILE_NRW(1, 1, 1) MILE_NRW(1, 2, 1) MILE_NRW(1, 1, 4) MILE_NRW(1, 2, 4)
   MILE_NRW(2, 1, 1) MILE_NRW(2, 2, 1) MILE_NRW(2, 1, 4) MILE_NRW(2, 2, 4)
@@ -1225,7 +1311,8 @@ static int launch_grad_gemm(mile_sampler *s, const GradParams &gp, int E, hipStr
   return MILE_OK;
 }
 
-static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t st, const UpdParams *fused_update = nullptr);
+static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t st, const UpdParams *fused_update = nullptr,
+                       bool full_layout = false);
 
 // ------------------------------------------------------------------------------------
 // Layer-wise MFMA path (MILE_GRAD_MFMA_WIDE_BF16X3 / _BF16): mile_mm3.h.  Per row chunk: forward GEMM per layer with bias +
@@ -1626,8 +1713,14 @@ static int grad_generic(mile_sampler *s, const GradParams &gp, const W64Fuse &, 
   return MILE_OK;
 }
 
-static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t st, const UpdParams *fused_update) {
+// Partition mode: theta is the compact [E, d_s] array and the gradient lands in the compact slabs (sample_slabs) -- straight
+// from the partition form of k_grad_narrow, or, for every other kernel, from the unchanged kernel on the library's full rows
+// between k_part_scatter and k_part_gather.  full_layout (mile_warmstart_step): theta is [E, d] whatever the mode.
+static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t st, const UpdParams *fused_update, bool full_layout) {
   if (!s->X) return fail(MILE_ERR_STATE, "no data: call mile_set_data first");
+  const bool part = s->part && !full_layout;
+  if (part && E != s->part_E) return fail(MILE_ERR_INVALID, "partition mode: E differs from the frozen rows' (mile_set_partition)");
+  if (part && !s->part_slabs) return fail(MILE_ERR_STATE, "workspace too small: call mile_reserve(E) after mile_set_partition");
   if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
   const GradKernel &k = grad_kernel(resolved_kernel(s));
   const int S = k.row_splits(s, E);
@@ -1650,6 +1743,15 @@ static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t s
     gp.Npad = (s->win_count + 31) / 32 * 32;
   }
   gp.dbg_buf = nullptr; gp.dbg = 0;   // lab-harness fields
+  const bool part_fused = part && k.id == MILE_GRAD_MFMA_NARROW_F32;
+  if (part_fused) {
+    gp.part_frozen = s->part_rows; gp.part_d = s->part_d;
+    gp.part_b0 = s->part_b0; gp.part_w0 = s->part_w0; gp.part_bl = s->part_bl; gp.part_wl = s->part_wl;
+    gp.slabs = s->part_slabs; gp.dp = sample_dp(s);
+  } else if (part) {
+    if (fused_update) return fail(MILE_ERR_STATE, "partition mode: no update epilogue");
+    gp.theta = s->part_rows;
+  }
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (s->timing) {
     if (s->ev_used + 2 > s->ev.size()) {
@@ -1668,7 +1770,15 @@ static int launch_grad(mile_sampler *s, const float *theta, int E, hipStream_t s
     if (!k.fuses) return fail(MILE_ERR_STATE, "fused update needs the mfma_w64_bf16x3 grad kernel");
     fz.upd = *fused_update; fz.arrive = s->arrive; fz.enabled = 1; fz.kind = upd_kind(*fused_update);
   }
+  if (part && !part_fused) {
+    k_part_scatter<<<E, 256, 0, st>>>(theta, s->part_d, s->part_rows, s->ds.d, s->part_seg);
+    HIP_TRY(hipGetLastError());
+  }
   if (const int rc = k.grad(s, gp, fz, E, st)) return rc;
+  if (part && !part_fused) {
+    k_part_gather<<<E * S, 256, 0, st>>>(s->slabs, gp.dp, s->part_slabs, sample_dp(s), s->part_seg);
+    HIP_TRY(hipGetLastError());
+  }
   if (s->timing) HIP_TRY(hipEventRecord(e1, st));
   return MILE_OK;
 }
@@ -1756,7 +1866,7 @@ static const char *args_refusal(const mile_sampler *s, const mile_tune_args *a) 
   if (!a->step_size || !a->L || !a->step_size_max || !a->time || !a->x_average || !a->stream_weight || !a->stream_average)
     return "mile_tune: null tuner array";
   if (a->n_steps < 0 || a->schedule_total < 1) return "mile_tune: bad step counts";
-  if ((s->ds.d >> 2) < 1) return "mile_tune: d < 4";
+  if ((sample_dim(s) >> 2) < 1) return "mile_tune: d < 4";
   return nullptr;
 }
 
@@ -1769,8 +1879,9 @@ static int mclmc_begin(mile_sampler *s, mile_state *state, const Args *a, const 
   if (const char *r = args_refusal(s, a)) return fail(MILE_ERR_INVALID, r);
   if (a->refresh != MILE_REFRESH_O_STEP_O && a->refresh != MILE_REFRESH_STEP_O)
     return fail(MILE_ERR_INVALID, fn + ": unknown refresh mode");
-  const int E = state->n_particles, d = s->ds.d;
+  const int E = state->n_particles, d = sample_dim(s);
   if (E < 1) return fail(MILE_ERR_INVALID, fn + ": n_particles must be >= 1");
+  if (s->part && E != s->part_E) return fail(MILE_ERR_INVALID, fn + ": partition mode: E differs from the frozen rows' (mile_set_partition)");
   if (a->n_steps == 0) return MILE_OK;
   HIP_TRY(hipSetDevice(s->device));
   if (!s->X) return fail(MILE_ERR_STATE, "no data: call mile_set_data first");
@@ -1784,7 +1895,7 @@ static int mclmc_begin(mile_sampler *s, mile_state *state, const Args *a, const 
   up.d = d; up.E = E; up.S = S; up.dp = (d + 3) / 4 * 4;
   up.prior = s->ds.prior; up.prior_loc = s->ds.prior_loc; up.prior_scale = s->ds.prior_scale;
   up.x = state->position; up.u = state->momentum; up.g = state->logdensity_grad; up.logp = state->logdensity;
-  up.slabs = s->slabs; up.llpart = s->llpart;
+  up.slabs = sample_slabs(s); up.llpart = s->llpart;
   up.eps = a->step_size; up.L = a->L; up.sdc = a->sqrt_diag_cov;
   up.seed = a->seed; up.pids = a->particle_ids;
   up.dK = s->dK; up.lold = s->lold; up.upart = s->upart;
@@ -2191,7 +2302,8 @@ int32_t mile_grad_launch_info(const mile_sampler *s, int32_t E, int32_t *grid_x,
   if (grid_y) *grid_y = E;
   if (block) *block = sh.block;
   if (lds_bytes) *lds_bytes = sh.lds;
-  if (name && name_len > 0) { std::strncpy(name, k.name, name_len - 1); name[name_len - 1] = 0; }
+  const std::string nm = std::string(k.name) + (!s->part ? "" : k.id == MILE_GRAD_MFMA_NARROW_F32 ? "<partition>" : " between k_part_scatter / k_part_gather");
+  if (name && name_len > 0) { std::strncpy(name, nm.c_str(), name_len - 1); name[name_len - 1] = 0; }
   return MILE_OK;
 }
 
@@ -2226,8 +2338,8 @@ int32_t mile_logpost_grad(mile_sampler *s, const float *theta, int32_t E, float 
   int rc = launch_grad(s, theta, E, st);
   if (rc) return rc;
   const int S = choose_S(s, E, resolved_kernel(s));
-  k_finalize<<<E, AUX_NT, 0, st>>>(s->ds.d, (s->ds.d + 3) / 4 * 4, S, s->ds.prior, s->ds.prior_loc, s->ds.prior_scale, theta,
-                                   s->slabs, s->llpart, grad, logp);
+  k_finalize<<<E, AUX_NT, 0, st>>>(sample_dim(s), sample_dp(s), S, s->ds.prior, s->ds.prior_loc, s->ds.prior_scale, theta,
+                                   sample_slabs(s), s->llpart, grad, logp);
   HIP_TRY(hipGetLastError());
   return MILE_OK;
 }
@@ -2239,7 +2351,7 @@ int32_t mile_warmstart_step(mile_sampler *s, float *theta, int32_t E, const mile
   if (a->t < 1) return fail(MILE_ERR_INVALID, "mile_warmstart_step: t counts from 1");
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->device));
-  const int rc = launch_grad(s, theta, E, st);          // likelihood gradient of the row window -> slabs, llpart
+  const int rc = launch_grad(s, theta, E, st, nullptr, true);   // likelihood gradient of the row window -> slabs, llpart
   if (rc) return rc;
   OptimParams op{};
   op.d = s->ds.d; op.S = choose_S(s, E, resolved_kernel(s)); op.dp = (s->ds.d + 3) / 4 * 4; op.kind = a->kind;
@@ -2262,7 +2374,7 @@ int32_t mile_init(mile_sampler *s, mile_state *state, const float *noise, uint64
   hipStream_t st = (hipStream_t)stream;
   int rc = mile_logpost_grad(s, state->position, E, state->logdensity, state->logdensity_grad, stream);
   if (rc) return rc;
-  k_init_momentum<<<E, AUX_NT, 0, st>>>(s->ds.d, noise, seed, particle_ids, state->momentum);
+  k_init_momentum<<<E, AUX_NT, 0, st>>>(sample_dim(s), noise, seed, particle_ids, state->momentum);
   HIP_TRY(hipGetLastError());
   return MILE_OK;
 }
@@ -2414,7 +2526,7 @@ int32_t mile_debug_noise(mile_sampler *s, uint64_t seed, const int32_t *particle
                          int64_t step, int32_t stage, float *out, void *stream) {
   if (!s || !out || E < 1) return fail(MILE_ERR_INVALID, "mile_debug_noise: bad argument");
   HIP_TRY(hipSetDevice(s->device));
-  k_debug_noise<<<E, AUX_NT, 0, (hipStream_t)stream>>>(s->ds.d, seed, particle_ids, (uint32_t)step, (uint32_t)stage, out);
+  k_debug_noise<<<E, AUX_NT, 0, (hipStream_t)stream>>>(sample_dim(s), seed, particle_ids, (uint32_t)step, (uint32_t)stage, out);
   HIP_TRY(hipGetLastError());
   return MILE_OK;
 }
@@ -2424,6 +2536,7 @@ int64_t mile_debug_prefill_count(const mile_sampler *s) { return s ? s->nz_launc
 int32_t mile_nuts_reserve(mile_sampler *s, int32_t E, int32_t max_num_doublings) {
   if (!s || E < 1 || max_num_doublings < 1 || max_num_doublings > NUTS_MAX_DOUBLINGS)
     return fail(MILE_ERR_INVALID, "mile_nuts_reserve: E >= 1 and 1 <= max_num_doublings <= 12");
+  if (s->part) return fail(MILE_ERR_INVALID, "mile_nuts_reserve: partition sampling with NUTS is not built");
   const int rc = mile_reserve(s, E);
   if (rc) return rc;
   if (E <= s->nuts_E && max_num_doublings <= s->nuts_M) return MILE_OK;
@@ -2447,6 +2560,7 @@ int32_t mile_nuts_reserve(mile_sampler *s, int32_t E, int32_t max_num_doublings)
 static int nuts_run(mile_sampler *s, mile_state *state, const mile_nuts_args *a, const mile_nuts_adapt_args *w, void *stream) {
   const char *fn = w ? "mile_nuts_warmup" : "mile_nuts_step";
   if (!s || !state || !a) return fail(MILE_ERR_INVALID, std::string(fn) + ": null argument");
+  if (s->part) return fail(MILE_ERR_INVALID, std::string(fn) + ": partition sampling with NUTS is not built");
   if (!state->position || !state->logdensity || !state->logdensity_grad) return fail(MILE_ERR_INVALID, std::string(fn) + ": null state field");
   const int E = state->n_particles, d = s->ds.d, M = a->max_num_doublings;
   if (E < 1 || a->n_steps < 0) return fail(MILE_ERR_INVALID, std::string(fn) + ": n_particles >= 1 and n_steps >= 0");

@@ -112,6 +112,8 @@ class Engine:
         self._h = h
         self.d = int(self.lib.mile_param_count(h))
         assert self.d == spec.n_params
+        self.dim = self.d                   # what init / step / tune / logpost_grad work on: d_s after set_partition
+        self._frozen = None
         self._E_reserved = 0
         if isinstance(spec, PretrainedAttentionSpec):
             self.set_embedding(*(tables if tables is not None else spec.load_tables()))
@@ -167,6 +169,57 @@ class Engine:
             _lib.check(self.lib.mile_set_embedding(self._h, _ptr(emb), _ptr(pos), self._stream()), self.lib)
             torch.cuda.current_stream(self.device).synchronize()   # emb, pos are temporaries
 
+    # ------------------------------------------------------------------ partition sampling
+    def set_partition(self, frozen):
+        """Partition mode (mile_set_partition): only the first and the last FCN layer are sampled; every other layer keeps,
+        per chain, the values of ``frozen`` [E, d].  From here on ``init``, ``step``, ``tune`` and ``logpost_grad`` take and
+        return compact [E, dim] tensors, dim = d_s; ``partition`` / ``merge`` convert.  ``pointwise_loglik``, ``predict``
+        and ``warmstart_step`` stay full-layout.  A net with at most two layers has no frozen layer: dim stays d."""
+        from mile_amd import partition as mpart
+        frozen = _f32(frozen, self.device, name='frozen').clone()
+        if frozen.ndim != 2 or frozen.shape[1] != self.d:
+            raise ValueError(f'frozen must be [E, {self.d}], got {tuple(frozen.shape)}')
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_set_partition(self._h, _ptr(frozen), frozen.shape[0], self._stream()), self.lib)
+            torch.cuda.current_stream(self.device).synchronize()
+        self._E_reserved = 0
+        self._frozen = frozen
+        self.dim = int(self.lib.mile_partition_dim(self._h))
+        segs = self.partition_segments
+        if segs and segs != mpart.segments(self.spec):
+            raise _lib.MileHipError(f'partition segments differ: library {segs}, host {mpart.segments(self.spec)}')
+        self._part_idx = torch.as_tensor(mpart.sampled_index(self.spec), device=self.device)
+        assert self.dim == self._part_idx.numel()
+
+    @property
+    def partitioned(self) -> bool:
+        return self._frozen is not None
+
+    @property
+    def partition_segments(self) -> list:
+        """[(begin, length)] of the sampled coordinates inside the full row (mile_partition_segments); [] outside partition
+        mode (and for a net without a frozen layer)."""
+        b, n = (C.c_int64 * 4)(), (C.c_int64 * 4)()
+        k = self.lib.mile_partition_segments(self._h, b, n, 4)
+        _lib.check(min(k, 0), self.lib)
+        return [(int(b[i]), int(n[i])) for i in range(k)]
+
+    def partition(self, full):
+        """full [..., d] -> compact [..., dim]."""
+        if not self.partitioned:
+            raise ValueError('call set_partition first')
+        full = _f32(full, self.device, name='full')
+        if full.shape[-1] != self.d:
+            raise ValueError(f'expected [..., {self.d}], got {tuple(full.shape)}')
+        return full[..., self._part_idx].contiguous()
+
+    def merge(self, compact):
+        """compact [..., E, dim] -> full [..., E, d]: the frozen rows with the sampled coordinates replaced."""
+        if not self.partitioned:
+            raise ValueError('call set_partition first')
+        from mile_amd import partition as mpart
+        return mpart.merge(self.spec, _f32(compact, self.device, name='compact'), self._frozen)
+
     def set_row_window(self, begin: int = 0, count: int = 0):
         """Likelihood over rows [begin, begin + count) of the training set for the following logpost_grad calls
         (count = 0: all rows).  The minibatches of the warm-start stage."""
@@ -211,8 +264,8 @@ class Engine:
     def logpost_grad(self, theta):
         """jax.value_and_grad(logdensity_fn) for an ensemble: theta [E, d] -> (logp [E], grad [E, d])."""
         theta = _f32(theta, self.device, name='theta')
-        if theta.ndim != 2 or theta.shape[1] != self.d:
-            raise ValueError(f'theta must be [E, {self.d}], got {tuple(theta.shape)}')
+        if theta.ndim != 2 or theta.shape[1] != self.dim:
+            raise ValueError(f'theta must be [E, {self.dim}], got {tuple(theta.shape)}')
         E = theta.shape[0]
         self.reserve(E)
         logp = torch.empty(E, dtype=torch.float32, device=self.device)
@@ -281,7 +334,7 @@ class Engine:
         for t in tensors:
             if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
                 raise ValueError(f'{what} tensors must be contiguous fp32 on the engine device')
-        if tuner is not None and tuner['stream_average'].shape != (E, 2, self.d):
+        if tuner is not None and tuner['stream_average'].shape != (E, 2, self.dim):
             raise ValueError('stream_average must be [E, 2, d]')
         self.reserve(E)
         if tuner is not None:
@@ -291,8 +344,8 @@ class Engine:
         else:
             eps = _f32(step_size, dev, (E,), 'step_size')
         Lt = _f32(L, dev).expand(E).contiguous() if torch.as_tensor(L).ndim == 0 else _f32(L, dev, (E,), 'L')
-        z = _f32(noise, dev, (n_steps, 2, E, self.d), 'noise') if noise is not None else None
-        sdc = _f32(sqrt_diag_cov, dev, (E, self.d), 'sqrt_diag_cov') if sqrt_diag_cov is not None else None
+        z = _f32(noise, dev, (n_steps, 2, E, self.dim), 'noise') if noise is not None else None
+        sdc = _f32(sqrt_diag_cov, dev, (E, self.dim), 'sqrt_diag_cov') if sqrt_diag_cov is not None else None
         ids = self._ids(particle_ids, E)
         a.step_size = eps.data_ptr()
         a.L = Lt.data_ptr()
@@ -309,16 +362,16 @@ class Engine:
         """blackjax.mcmc.mclmc.init for an ensemble.  ``noise`` [E, d] (explicit N(0,1) draws)
         or the counter RNG keyed by (seed, particle id)."""
         position = _f32(position, self.device, name='position').clone()
-        if position.ndim != 2 or position.shape[1] != self.d:
-            raise ValueError(f'position must be [E, {self.d}], got {tuple(position.shape)}')
-        if self.d < 2:
+        if position.ndim != 2 or position.shape[1] != self.dim:
+            raise ValueError(f'position must be [E, {self.dim}], got {tuple(position.shape)}')
+        if self.dim < 2:
             raise ValueError('The target distribution must have more than 1 dimension for MCLMC.')
         E = position.shape[0]
         self.reserve(E)
         st = IntegratorState(position, torch.empty_like(position),
                              torch.empty(E, dtype=torch.float32, device=self.device),
                              torch.empty_like(position))
-        z = _f32(noise, self.device, (E, self.d), 'noise') if noise is not None else None
+        z = _f32(noise, self.device, (E, self.dim), 'noise') if noise is not None else None
         ids = self._ids(particle_ids, E)
         sc = self._state_c(st)
         with torch.cuda.device(self.device):
@@ -344,7 +397,7 @@ class Engine:
         n_kept = 0
         if n_thinning > 0:
             n_kept = sum(1 for i in range(n_steps) if (step_offset + i) % n_thinning == 0)
-        samples = torch.empty((n_kept, E, self.d), dtype=torch.float32, device=dev) if n_kept else None
+        samples = torch.empty((n_kept, E, self.dim), dtype=torch.float32, device=dev) if n_kept else None
         info = torch.empty((n_steps, E, 3), dtype=torch.float32, device=dev) if want_info else None
         a.n_thinning = n_thinning
         a.out_samples = samples.data_ptr() if samples is not None else None
@@ -548,7 +601,7 @@ class Engine:
 
     @property
     def supports_device_tuner(self) -> bool:
-        return self.d >= 4
+        return self.dim >= 4
 
     def debug_prefill_count(self) -> int:
         """Mid-step update launches so far whose E extra workgroups drew the record launch's noise (test hook)."""
@@ -556,7 +609,7 @@ class Engine:
 
     def debug_noise(self, seed: int, E: int, step: int, stage: int, particle_ids=None):
         ids = self._ids(particle_ids, E)
-        out = torch.empty((E, self.d), dtype=torch.float32, device=self.device)
+        out = torch.empty((E, self.dim), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.mile_debug_noise(self._h, C.c_uint64(seed), _ptr(ids), E, step, stage, _ptr(out),
                                                  self._stream()), self.lib)

@@ -20,7 +20,7 @@ from typing import Callable, NamedTuple
 import torch
 
 from mile_amd.engine import HMCState, IntegratorState, MCLMCInfo, NUTSInfo
-from mile_amd.probabilistic import resolve_target
+from mile_amd.probabilistic import is_partition_target, resolve_engine, resolve_target
 from mile_amd.tree import as_key, ravel_tree
 
 __all__ = ['mclmc', 'nuts', 'KERNELS', 'WARMUP_KERNELS', 'SamplingAlgorithm', 'HMCState', 'NUTSInfo']
@@ -33,11 +33,15 @@ class SamplingAlgorithm(NamedTuple):
     step: Callable
 
 
-def _flat(spec, position, device):
+def _flat(spec, position, device, eng=None):
+    """[E, d] rows of a position; a partition engine gets their compact [E, d_s] form (full rows are cut down)."""
     flat = position if torch.is_tensor(position) else ravel_tree(spec, position)
     if flat.ndim == 1:
         flat = flat[None]
-    return flat.to(device=device, dtype=torch.float32).contiguous()
+    flat = flat.to(device=device, dtype=torch.float32).contiguous()
+    if eng is not None and eng.partitioned and eng.dim != eng.d and flat.shape[1] == eng.d:
+        flat = eng.partition(flat)
+    return flat
 
 
 def mclmc(logdensity_fn, L, step_size, integrator: str = 'isokinetic_mclachlan', sqrt_diag_cov=1.0,
@@ -51,12 +55,12 @@ def mclmc(logdensity_fn, L, step_size, integrator: str = 'isokinetic_mclachlan',
     if integrator != 'isokinetic_mclachlan':
         raise NotImplementedError('only the isokinetic McLachlan integrator is implemented')
     model, x, y = resolve_target(logdensity_fn)
-    eng = model.engine(x, y)
+    eng = resolve_engine(logdensity_fn)    # a partition target (ProbabilisticModel.bind_partition): compact states throughout
     sdc = None if (not torch.is_tensor(sqrt_diag_cov) and float(sqrt_diag_cov) == 1.0) else sqrt_diag_cov
 
     def init(position, rng_key) -> IntegratorState:
         key = as_key(rng_key)
-        return eng.init(_flat(model.spec, position, eng.device), seed=key.seed, particle_ids=chain_ids)
+        return eng.init(_flat(model.spec, position, eng.device, eng), seed=key.seed, particle_ids=chain_ids)
 
     def step(rng_key, state: IntegratorState, step_index: int = 0):
         """One kernel step.  The noise stream is Philox(rng_key.seed; chain id, step_index)."""
@@ -80,6 +84,8 @@ def nuts(logdensity_fn, step_size, inverse_mass_matrix, max_num_doublings: int =
     the RNG streams.
     """
     model, x, y = resolve_target(logdensity_fn)
+    if is_partition_target(logdensity_fn):
+        raise NotImplementedError('partition sampling with NUTS is not built yet')
     eng = model.engine(x, y)
 
     def init(position, rng_key=None) -> HMCState:

@@ -67,6 +67,19 @@ class ProbabilisticModel:
             self._engines[key] = (Engine(self.spec, x, y, device=dev, grad_kernel=self.grad_kernel), x, y)   # keep x, y alive: id() stays unique
         return self._engines[key][0]
 
+    def partition_engine(self, x, y, frozen, device=None):
+        """The HIP engine of the partition target (Engine.set_partition): first and last layer sampled, the other layers at
+        the chains' ``frozen`` [E, d] rows.  One per data identity and device; a new ``frozen`` replaces it."""
+        from mile_amd.engine import Engine
+        dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        key = (id(x), id(y), str(dev), 'partition')
+        ent = self._engines.get(key)
+        if ent is None or ent[3] is not frozen:
+            eng = Engine(self.spec, x, y, device=dev, grad_kernel=self.grad_kernel)
+            eng.set_partition(frozen)
+            self._engines[key] = (eng, x, y, frozen)
+        return self._engines[key][0]
+
     def log_prior(self, params) -> torch.Tensor:
         from mile_amd.tree import ravel_tree
         flat = params if torch.is_tensor(params) else ravel_tree(self.spec, params)
@@ -81,12 +94,42 @@ class ProbabilisticModel:
         logp, _ = eng.logpost_grad(flat.reshape(-1, self.n_params))
         return logp[0] if squeeze else logp
 
+    def log_unnormalized_posterior_partition(self, position, x, y, frozen, **kwargs):
+        """trainer.py:651-659 of the reference: log_prior(first and last layer) + log_likelihood(full net with the other
+        layers at ``frozen``), on the GPU.  position: compact [E, d_s] (Engine.partition of a full row)."""
+        eng = self.partition_engine(x, y, frozen)
+        flat = torch.as_tensor(position)
+        squeeze = flat.ndim == 1
+        logp, _ = eng.logpost_grad(flat.reshape(-1, eng.dim))
+        return logp[0] if squeeze else logp
+
     def log_likelihood(self, params, x, y, **kwargs):
         return self.log_unnormalized_posterior(params, x, y) - self.log_prior(params).to(self.engine(x, y).device)
 
     def bind(self, x, y):
         """partial(self.log_unnormalized_posterior, x=x, y=y) as trainer.py:576-580 builds it."""
         return partial(self.log_unnormalized_posterior, x=x, y=y)
+
+    def bind_partition(self, x, y, frozen):
+        """partial(self.log_unnormalized_posterior_partition, x=x, y=y) with the hidden layers bound as
+        partition_inference_loop binds them: ``frozen`` [E, d], the chains' full warm-start rows."""
+        from mile_amd import partition as mpart
+        mpart.check_spec(self.spec)
+        frozen = torch.as_tensor(frozen, dtype=torch.float32)
+        if frozen.ndim != 2 or frozen.shape[1] != self.n_params:
+            raise ValueError(f'frozen must be [E, {self.n_params}], got {tuple(frozen.shape)}')
+        return partial(self.log_unnormalized_posterior_partition, x=x, y=y, frozen=frozen)
+
+
+def resolve_engine(logdensity_fn):
+    """The engine that evaluates a bound target: the partition engine when it was bound with ``bind_partition``."""
+    model, x, y = resolve_target(logdensity_fn)
+    frozen = (logdensity_fn.keywords or {}).get('frozen')
+    return model.partition_engine(x, y, frozen) if frozen is not None else model.engine(x, y)
+
+
+def is_partition_target(logdensity_fn) -> bool:
+    return isinstance(logdensity_fn, partial) and (logdensity_fn.keywords or {}).get('frozen') is not None
 
 
 def resolve_target(logdensity_fn):

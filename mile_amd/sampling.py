@@ -20,7 +20,7 @@ import torch
 from mile_amd import distributed as mdist
 from mile_amd.sample_writer import WriterPool
 from mile_amd.kernels import KERNELS
-from mile_amd.probabilistic import resolve_target
+from mile_amd.probabilistic import resolve_engine, resolve_target
 from mile_amd.tree import as_key, ravel_tree
 from mile_amd.warmup import custom_mclmc_warmup, custom_window_adaptation
 
@@ -86,6 +86,11 @@ def inference_loop(unnorm_log_posterior, config, rng_key, init_params, step_ids,
     init_params: param tree whose leaves have a leading ensemble axis (or an [E, d] tensor);
     step_ids: the chain ids of this group.  Returns None (files are the output) unless
     ``return_samples`` (then the kept positions [n_kept, E, d] as a CPU tensor).
+
+    A partition target (ProbabilisticModel.bind_partition; partition_inference_loop of the reference,
+    src/training/partition_sampling.py) samples the compact [E, d_s] vector of the first and the last layer: warm-up, init
+    and the steps run on it, and every kept position is merged with the chains' frozen rows on the device before it goes
+    to the sample writer, so ``sample_<idx>.npz`` has the keys, shapes and dtypes of a full run.
     """
     info = {}
     step_ids = np.asarray(step_ids).reshape(-1)
@@ -98,13 +103,18 @@ def inference_loop(unnorm_log_posterior, config, rng_key, init_params, step_ids,
         raise NotImplementedError(f'{config.name} does not have a warmup implemented.')
     saving_path = Path(saving_path)
     model, x, y = resolve_target(unnorm_log_posterior)
-    eng = model.engine(x, y)
+    eng = resolve_engine(unnorm_log_posterior)
+    partitioned = eng.partitioned and eng.dim != eng.d
+    if partitioned and is_nuts:
+        raise NotImplementedError('partition sampling with NUTS is not built yet')
     chain_ids = torch.as_tensor(step_ids, dtype=torch.int32)
     flat0 = init_params if torch.is_tensor(init_params) else ravel_tree(model.spec, init_params)
     if flat0.ndim == 1:
         flat0 = flat0[None]
     if flat0.shape[0] != n_devices:
         raise ValueError(f'init_params has {flat0.shape[0]} chains but step_ids has {n_devices}')
+    if partitioned and flat0.shape[1] == eng.d:
+        flat0 = eng.partition(flat0)
 
     logger.info('> Starting Warmup sampling...')
     t_w0 = time.time()
@@ -184,6 +194,8 @@ def inference_loop(unnorm_log_posterior, config, rng_key, init_params, step_ids,
             state, _, samples = eng.step(state, parameters['step_size'], parameters['L'], n_steps=c,
                                          seed=sample_key.seed, step_offset=done, n_thinning=n_thin,
                                          particle_ids=chain_ids, want_info=False, inplace=True)
+        if samples is not None and partitioned:
+            samples = eng.merge(samples)               # [n_kept, E, d]: the frozen layers are the warm-start member's, bit for bit
         if samples is not None:
             idxs = [done + i for i in range(c) if (done + i) % n_thin == 0]
             if pinned[slot] is None or pinned[slot].numel() < samples.numel():

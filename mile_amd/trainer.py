@@ -193,7 +193,8 @@ class BDETrainer:
             save_params(wdir, self.prob_model.spec, params[i], i)
 
     def start_sampling(self):
-        """trainer.py:543-607 (full-batch, non-partition branch)."""
+        """trainer.py:543-607 (full-batch).  sampler.partition_sampling: the chains of a group sample their first and last
+        layer only (the partition branch, :593-607); a net without a frozen layer takes the ordinary path."""
         with measure_time('time.sampling'):
             cfgs = self.config.training.sampler
             ws = self.config.training.warmstart
@@ -209,6 +210,7 @@ class BDETrainer:
                 x = torch.from_numpy(np.ascontiguousarray(self.loader.train_x).reshape(len(self.loader.train_x), -1))
                 y = torch.from_numpy(np.ascontiguousarray(self.loader.train_y))
             log_post = self.prob_model.bind(x, y)
+            partition = cfgs.partition_sampling and len(self.prob_model.spec.hidden_structure) > 2
             for step in self.train_plan:
                 mine = mdist.shard_chains(step, self.world_size, self.rank)
                 if len(mine) == 0:
@@ -224,6 +226,8 @@ class BDETrainer:
                 else:
                     logger.warning('\t| No warmstart path found, starting sampling from random params.')
                     params = self.init_module_params(mine)
+                if partition:   # the hidden layers are bound per chain: each keeps those of its own warm-start member
+                    log_post = self.prob_model.bind_partition(x, y, torch.from_numpy(params))
                 inference_loop(unnorm_log_posterior=log_post, config=cfgs, rng_key=self.key,
                                init_params=torch.from_numpy(params), step_ids=mine,
                                saving_path=self.exp_dir / cfgs._dir_name,

@@ -18,7 +18,7 @@ import torch
 
 from mile_amd.diagnostics import effective_sample_size
 from mile_amd.engine import IntegratorState
-from mile_amd.probabilistic import resolve_target
+from mile_amd.probabilistic import is_partition_target, resolve_engine, resolve_target
 from mile_amd.tree import as_key, ravel_tree
 
 
@@ -228,11 +228,15 @@ def custom_mclmc_warmup(logdensity_fn, diagonal_preconditioning: bool = True, de
     model, x, y = resolve_target(logdensity_fn)
 
     def run(rng_key, position, num_steps: int = 1000) -> AdaptationResults:
-        eng = model.engine(x, y)
+        # A partition target runs everything below on the compact vector: blackjax.mclmc.init and the three tuner phases
+        # see d = d_s (L0 = max(sqrt(d_s), 15), the predictor's xi / d_s, the phase-3 subsample of <= 2000 of d_s).
+        eng = resolve_engine(logdensity_fn)
         key = as_key(rng_key)
         flat = position if torch.is_tensor(position) else ravel_tree(model.spec, position)
         if flat.ndim == 1:
             flat = flat[None]
+        if eng.partitioned and eng.dim != eng.d and flat.shape[1] == eng.d:
+            flat = eng.partition(flat)
         state = eng.init(flat, seed=key.seed, particle_ids=chain_ids)     # same key reused, warmup.py:539-552
         phase_ratio = (0.8, 0.1, 0.1)
         state, params = mclmc_find_L_and_step_size(
@@ -296,6 +300,8 @@ def custom_window_adaptation(algorithm=None, logdensity_fn=None, is_mass_matrix_
     if extra_parameters:
         raise NotImplementedError(f'extra NUTS parameters {sorted(extra_parameters)}')
     model, x, y = resolve_target(logdensity_fn)
+    if is_partition_target(logdensity_fn):
+        raise NotImplementedError('partition sampling with NUTS is not built yet')
 
     def run(rng_key, position, device_id=None, num_steps: int = 1000, n_devices: int = 1) -> NUTSAdaptationResults:
         eng = model.engine(x, y)
