@@ -3,7 +3,7 @@
 mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
 src/inference/metrics.py:247-312):
 
-    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]]
+    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--moments]
 
 Reloads config.yaml and the samples/<chain>/sample_<n>.npz files, rebuilds the data split with the same
 seed, evaluates all C x S samples on the split in one device pass and writes metrics.json next to them.
@@ -103,12 +103,42 @@ def diagnostic_metrics(samples, spec, n_splits, device):
     return out, arr
 
 
+def moment_metrics(moments, dropped, y, task):
+    """--moments: the metrics.json keys and the moments.npz arrays of posterior-predictive moments [N, W]
+    (Engine.predict_moments, or metrics.predictive_moments of raw outputs), ``dropped`` [N] and the split's targets ``y``.
+    Keys: the mean over the rows of each column (rows without a finite draw left out), the draws dropped in all, and for
+    regression the RMSE of the mean prediction."""
+    from mile_amd import metrics as M
+    mom = moments.detach().double().cpu()
+    drop = dropped.detach().cpu().numpy().astype(np.int32)
+    col = [float(v) for v in torch.nanmean(mom, dim=0)]
+    if task == 'regr':
+        names = ['mean', 'epistemic_var', 'aleatoric_var']
+        arrays = {n: mom[:, i].numpy().astype(np.float32) for i, n in enumerate(names)}
+        out = {f'moments_{n}': col[i] for i, n in enumerate(names)}
+        fin = torch.isfinite(mom[:, 0])
+        yt = torch.as_tensor(np.ascontiguousarray(y), dtype=torch.float64).reshape(-1)
+        out['moments_rmse'] = float(M.rmse_from_moments(yt[fin], mom[fin])) if bool(fin.any()) else float('nan')
+    else:
+        K = mom.shape[1] - 2
+        arrays = {'probs': mom[:, :K].numpy().astype(np.float32), 'entropy': mom[:, K].numpy().astype(np.float32),
+                  'mutual_information': mom[:, K + 1].numpy().astype(np.float32)}
+        out = {'moments_probs': col[:K], 'moments_entropy': col[K], 'moments_mutual_information': col[K + 1]}
+    arrays['dropped'] = drop
+    out['moments_dropped'] = int(drop.sum())
+    return out, arrays
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description='LPPD / NLL of the samples of an experiment directory')
     ap.add_argument('--diagnostics', type=int, nargs='?', const=2, default=None, metavar='N_SPLITS',
                     help='per-parameter chain diagnostics of ALL parameters (ESS, split R-hat with N_SPLITS splits, default 2, '
                          'within / between chain variance): diag_* keys in metrics.json and the arrays in diagnostics.npz; the HIP '
                          'kernels take 4 <= n_samples <= 4096, other lengths run in plain torch')
+    ap.add_argument('--moments', action='store_true',
+                    help='posterior-predictive moments of all draws on the split, reduced on the device (mile_predict_moments): '
+                         'moments_* keys in metrics.json and the per-row arrays in moments.npz (regression: mean, epistemic_var, '
+                         'aleatoric_var; classification: probs, entropy, mutual_information; both: dropped)')
     ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
     ap.add_argument('--split', default='test', choices=['train', 'valid', 'test'])
     ap.add_argument('--device', default='cuda:0')
@@ -219,6 +249,11 @@ def main():
     out.update(diag)
     if diag_arrays is not None:
         np.savez(exp / 'diagnostics.npz', **diag_arrays)
+    if args.moments:
+        mom, dropped = eng.predict_moments(torch.from_numpy(samples), torch.from_numpy(x), return_dropped=True)
+        keys, arrays = moment_metrics(mom, dropped, np.ascontiguousarray(y), cfg.data.task)
+        out.update(keys)
+        np.savez(exp / 'moments.npz', **arrays)
     (exp / 'metrics.json').write_text(json.dumps(out, indent=1) + '\n')
     print(json.dumps({k: v for k, v in out.items() if not isinstance(v, (list, dict))}))        # the per-chain arrays stay in metrics.json
 

@@ -366,6 +366,27 @@ int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, int32_t S, co
  * log-probability.  (Added under ABI 10: a new symbol, no struct or existing entry changed.) */
 int32_t mile_predict(mile_sampler *s, const float *theta, int32_t S, const float *X, int64_t N, float *out, void *stream);
 
+/* Posterior-predictive moments: the Bayesian-model-average prediction of S draws on N rows, reduced over the draw axis on
+ * the device (the reference reduces predict_bde's [S, N, O] outputs on the host, src/inference/evaluation.py:459-543).
+ * theta [S, d] full-layout (partition mode included) and X [N, F] as for mile_predict.  out [N, W] fp32 row-major,
+ * W = mile_predict_moments_width:
+ *   regression, W = 3:          out[n] = (mean_s mu, Var_s mu with divisor S: epistemic, mean_s sigma^2: aleatoric),
+ *                               sigma = clip(exp(log sigma), 1e-6, 1e6) as in mile_pointwise_loglik; columns 1 + 2 are the
+ *                               variance of the equal-weight mixture of the S Normals
+ *   K classes, W = K + 2:       out[n, 0:K] = mean_s softmax, out[n, K] = its entropy (nats), out[n, K+1] = that entropy
+ *                               minus mean_s of each draw's entropy (mutual information, clamped at 0); p = 0 adds 0
+ * A draw with a non-finite raw output on row n is left out of row n's statistics (per draw and per row; the reference
+ * drops whole chains); dropped [N] int32 (device, may be null) receives how many were.  A row with every draw left out
+ * holds NaN.  The forward is mile_predict's, in passes of at most max_draws_per_pass draws (0: as many as fit 256 MiB of
+ * raw outputs) into a workspace the handle owns and grows here -- never [S, N, O] at once; accumulators are fp64
+ * (Welford + Chan for the variance), so the result does not depend on max_draws_per_pass beyond fp64 rounding.
+ * MILE_ERR_INVALID: a null handle / theta / X / out, S < 1 or > 2^31 - 1, N < 1 or > 2^30 - 1, max_draws_per_pass < 0;
+ * MILE_ERR_STATE: frozen tables not set; MILE_ERR_NOMEM: the workspace.  Nothing is launched on any of them.
+ * (Added under ABI 10: two new symbols, no struct or existing entry changed.) */
+int32_t mile_predict_moments(mile_sampler *s, const float *theta, int64_t S, const void *X, int64_t N, float *out,
+                             int32_t *dropped, int64_t max_draws_per_pass, void *stream);
+int32_t mile_predict_moments_width(const mile_sampler *s);
+
 /* Which outputs mile_chain_diagnostics computes (`what`), and how it reads its input. */
 #define MILE_DIAG_WCV 1u
 #define MILE_DIAG_BCV 2u

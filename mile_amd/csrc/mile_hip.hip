@@ -29,6 +29,7 @@
 #include "mile_update.h"
 #include "mile_nuts.h"
 #include "mile_diag.h"
+#include "mile_moments.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -64,6 +65,7 @@ struct mile_sampler {
   int nz_E = 0;                         // particle rows nzbuf holds (allocated by the first mile_step that prefills)
   int64_t nz_launches = 0;              // mid-step launches that prefilled noise (mile_debug_prefill_count)
   float *ev_X = nullptr, *ev_Xp = nullptr; void *ev_y = nullptr; int ev_cap = 0;   // evaluation (test) set staging
+  void *mom_ws = nullptr; size_t mom_ws_bytes = 0;   // mile_predict_moments: one pass of raw outputs, then the accumulators
   float *alt_x = nullptr, *alt_u = nullptr, *alt_g = nullptr, *alt_logp = nullptr;   // ping-pong state of mile_tune
   int grad_kernel = MILE_GRAD_AUTO;
   LeNetGeom lg{};                       // MILE_MODEL_LENET geometry and parameter offsets
@@ -609,6 +611,7 @@ int32_t mile_destroy(mile_sampler *s) {
   if (s->ev_X) (void)hipFree(s->ev_X);
   if (s->ev_Xp) (void)hipFree(s->ev_Xp);
   if (s->ev_y) (void)hipFree(s->ev_y);
+  if (s->mom_ws) (void)hipFree(s->mom_ws);
   free_data(s);
   free_ws(s);
   if (s->gemm_ws) (void)hipFree(s->gemm_ws);
@@ -2237,6 +2240,58 @@ extern "C" int32_t mile_predict(mile_sampler *s, const float *theta, int32_t S, 
   if (N < 1 || N > 0x3fffffff) return fail(MILE_ERR_INVALID, "mile_predict: N out of range");
   if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
   return evaluate_rows(s, theta, S, X, nullptr, N, out, stream);
+}
+
+// mile_predict_moments: mile_predict's forward in passes of `chunk` draws into the library's workspace, each folded into the
+// per-row accumulators by k_moments_accum; k_moments_finish writes out.  Every check before any launch.
+static const int64_t MOM_RAW_TARGET = (int64_t)256 << 20;   // bytes of raw outputs per pass when the caller leaves the choice
+
+extern "C" int32_t mile_predict_moments_width(const mile_sampler *s) {
+  if (!s) return fail(MILE_ERR_INVALID, "mile_predict_moments_width: null handle");
+  const int O = s->spec.widths[s->spec.n_layers - 1];
+  return s->spec.task == MILE_TASK_REGRESSION ? 3 : O + 2;
+}
+
+extern "C" int32_t mile_predict_moments(mile_sampler *s, const float *theta, int64_t S, const void *X, int64_t N, float *out,
+                                        int32_t *dropped, int64_t max_draws_per_pass, void *stream) {
+  if (!s || !theta || !X || !out || S < 1) return fail(MILE_ERR_INVALID, "mile_predict_moments: bad argument");
+  if (S > 0x7fffffff) return fail(MILE_ERR_INVALID, "mile_predict_moments: S out of range");
+  if (N < 1 || N > 0x3fffffff) return fail(MILE_ERR_INVALID, "mile_predict_moments: N out of range");
+  if (max_draws_per_pass < 0) return fail(MILE_ERR_INVALID, "mile_predict_moments: max_draws_per_pass < 0");
+  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
+  const int task = s->spec.task, O = s->spec.widths[s->spec.n_layers - 1];
+  if (task == MILE_TASK_REGRESSION && O != 2) return fail(MILE_ERR_INVALID, "mile_predict_moments: regression needs (mu, log sigma) outputs");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->device));
+  const int64_t per_draw = N * O * 4;
+  int64_t chunk = max_draws_per_pass ? max_draws_per_pass : std::max<int64_t>(1, MOM_RAW_TARGET / per_draw);
+  chunk = std::min<int64_t>(chunk, S);
+  // enough one-wave workgroups for about eight waves per CU, at most one slice per draw of a pass
+  const int slices = (int)std::min<int64_t>(std::min<int64_t>(MOM_MAX_SLICES, chunk), std::max<int64_t>(1, ((int64_t)s->n_cu * 8 * MOM_NT + N - 1) / N));
+  const size_t raw_bytes = ((size_t)chunk * per_draw + 255) / 256 * 256, acc_bytes = mom_acc_bytes(task, O, (int)N, slices);
+  if (raw_bytes + acc_bytes > s->mom_ws_bytes) {   // evaluation is off the stepping path: (re)allocate here
+    if (s->mom_ws) (void)hipFree(s->mom_ws);
+    s->mom_ws = nullptr; s->mom_ws_bytes = 0;
+    if (hipMalloc(&s->mom_ws, raw_bytes + acc_bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(MILE_ERR_NOMEM, "mile_predict_moments: workspace allocation failed (lower max_draws_per_pass)");
+    }
+    s->mom_ws_bytes = raw_bytes + acc_bytes;
+  }
+  MomParams p{};
+  p.raw = (const float *)s->mom_ws; p.N = (int)N; p.O = O; p.slices = slices; p.S = S;
+  p.acc = (double *)((char *)s->mom_ws + raw_bytes);
+  p.cnt = (int32_t *)(p.acc + (size_t)slices * mom_planes(task, O) * N);
+  p.out = out; p.dropped = dropped;
+  HIP_TRY(hipMemsetAsync(p.acc, 0, acc_bytes, st));
+  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+    p.Sc = (int)std::min<int64_t>(chunk, S - s0);
+    const int rc = evaluate_rows(s, theta + s0 * s->ds.d, p.Sc, (const float *)X, nullptr, N, (float *)s->mom_ws, stream);
+    if (rc != MILE_OK) return rc;
+    HIP_TRY(mile_launch_moments_accum(task, p, st));
+  }
+  HIP_TRY(mile_launch_moments_finish(task, p, st));
+  return MILE_OK;
 }
 
 // mile_chain_diagnostics: every check before any launch; parameters in chunks that fit the workspace --------------------------

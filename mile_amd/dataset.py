@@ -53,11 +53,15 @@ class TabularLoader:
         else:
             raise NotImplementedError('Only .npy and .csv files are supported at this time.')
         data = np.asarray(data, dtype=np.float32)      # jnp.array default dtype
+        self.norm = {}                                 # what normalisation_stats() hands to predict.py
         if normalize:
             if self.config.task == 'class':
+                self.norm = {'x_mean': data[:, :-1].mean(axis=0), 'x_std': data[:, :-1].std(axis=0)}
                 data = np.concatenate([(data[:, :-1] - data[:, :-1].mean(axis=0)) / data[:, :-1].std(axis=0),
                                        data[:, -1:]], axis=1)
             else:
+                mean, std, t = data.mean(axis=0), data.std(axis=0), self.target_len
+                self.norm = {'x_mean': mean[:-t], 'x_std': std[:-t], 'y_mean': mean[-t:], 'y_std': std[-t:]}
                 data = (data - data.mean(axis=0)) / data.std(axis=0)
         if shuffle:
             data = data[self._rng.permutation(len(data))]
@@ -102,7 +106,9 @@ class ImageLoader:
             x, y = np.asarray(z['x'], dtype=np.float32), np.asarray(z['y'])
         else:
             raise NotImplementedError('image data: only source "synthetic" or a local .npz with x [N,C,H,W], y [N]')
+        self.norm = {}
         if config.normalize:
+            self.norm = {'x_mean': np.asarray(x.mean(), dtype=np.float32), 'x_std': np.asarray(x.std(), dtype=np.float32)}
             x = (x - x.mean()) / x.std()
         if shuffle:
             perm = g.permutation(len(x))
@@ -183,3 +189,18 @@ def synthetic_text(g: np.random.Generator, N: int, T: int, V: int, n_classes: in
     s = score[x].sum(axis=1) / lengths[:, None]
     y = np.argmax(3.0 * s + g.gumbel(size=(N, n_classes)), axis=1).astype(np.int64)
     return x, y
+
+
+NORMALIZATION_FILE = 'normalization.npz'
+
+
+def normalization_stats(loader) -> dict:
+    """The statistics a loader normalised its data with, as float32 arrays: ``x_mean`` / ``x_std`` (per feature for tabular
+    data, one scalar for images) and, where the target was z-scored too (tabular regression), ``y_mean`` / ``y_std``.
+    Empty without normalisation (and for token ids)."""
+    return {k: np.asarray(v, dtype=np.float32) for k, v in getattr(loader, 'norm', {}).items()}
+
+
+def save_normalization(exp_dir, loader):
+    """Write the loader's statistics next to config.yaml (normalization.npz): what predict.py applies to new inputs."""
+    np.savez(os.path.join(str(exp_dir), NORMALIZATION_FILE), **normalization_stats(loader))

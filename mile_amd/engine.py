@@ -599,6 +599,29 @@ class Engine:
                                              self._stream()), self.lib)
         return out.reshape(*lead, X.shape[0], O)
 
+    def predict_moments(self, theta, X, *, max_draws_per_pass: int = 0, return_dropped: bool = False):
+        """Posterior-predictive moments of all draws theta [..., d] on X [N, F], reduced on the device (mile_predict_moments):
+        [N, 3] = (mean, epistemic variance, aleatoric variance) for regression, [N, K + 2] = (mean class probabilities,
+        predictive entropy, mutual information) for classification -- ``metrics.predictive_moments`` of ``predict``'s
+        outputs, without ever holding them.  ``max_draws_per_pass`` bounds the draws forwarded at a time (0: the library's
+        choice).  A draw with a non-finite output on a row is left out of that row; ``return_dropped`` also returns how many
+        were, int32 [N]."""
+        theta = _f32(theta, self.device, name='theta')
+        th = theta.reshape(-1, self.d).contiguous()
+        X = _f32(X, self.device, name='X')
+        if isinstance(self.spec, IMAGE_SPECS) and X.ndim == 4:
+            X = X.reshape(X.shape[0], -1).contiguous()
+        if X.ndim != 2 or X.shape[1] != self.spec.in_features:
+            raise ValueError('X must be [N, F]')
+        _check_tokens(self.spec, X)
+        W = int(self.lib.mile_predict_moments_width(self._h))
+        out = torch.empty((X.shape[0], W), dtype=torch.float32, device=self.device)
+        dropped = torch.empty(X.shape[0], dtype=torch.int32, device=self.device) if return_dropped else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_predict_moments(self._h, _ptr(th), th.shape[0], _ptr(X), X.shape[0], _ptr(out),
+                                                     _ptr(dropped), int(max_draws_per_pass), self._stream()), self.lib)
+        return (out, dropped) if return_dropped else out
+
     @property
     def supports_device_tuner(self) -> bool:
         return self.dim >= 4

@@ -332,3 +332,49 @@ def rmse(y: torch.Tensor, draws_or_means: torch.Tensor) -> torch.Tensor:
     (evaluation.py:509-512)."""
     m = draws_or_means.reshape(-1, draws_or_means.shape[-1]).mean(dim=0)
     return torch.sqrt(((y.to(m.device, m.dtype) - m) ** 2).mean())
+
+
+# ---- posterior-predictive moments: the torch restatement of mile_predict_moments (Engine.predict_moments), over raw
+# outputs that fit in memory.  The tests' yardstick in fp32, and the CPU fallback of the tools.
+
+def predictive_moments(outputs: torch.Tensor, task: str, return_dropped: bool = False):
+    """outputs [..., N, O] raw outputs of all draws (every leading axis is a draw axis) -> [N, W] in the outputs' dtype.
+    Regression (W = 3): mean of mu, its population variance over the draws (epistemic), mean of sigma^2 (aleatoric),
+    sigma = clip(exp(log sigma), 1e-6, 1e6); columns 1 + 2 are the variance of the equal-weight mixture of the draws'
+    Normals.  The variance is the shifted form mean(d^2) - mean(d)^2, d = mu - mean: draws that agree to many digits keep it.
+    Classification (W = K + 2): mean softmax probabilities, the entropy of that mean (nats) and the mutual information --
+    that entropy minus the mean entropy of the draws, clamped at 0; p = 0 adds 0.
+    A draw with a non-finite output on a row is left out of that row; ``return_dropped`` also returns how many, int32 [N].
+    A row without a finite draw holds NaN."""
+    N, O = outputs.shape[-2], outputs.shape[-1]
+    o = outputs.reshape(-1, N, O)
+    ok = torch.isfinite(o).all(dim=-1)                                  # [S, N]
+    cnt = ok.sum(dim=0)
+    w = ok.to(o.dtype)
+    n = cnt.to(o.dtype)                                                 # 0 -> 0 / 0 = NaN below
+    o = torch.where(ok[..., None], o, torch.zeros_like(o))
+    if task in ('regr', 'regression'):
+        mu = o[..., 0]
+        mean = (mu * w).sum(dim=0) / n
+        d = (mu - mean) * w
+        var = (d * d).sum(dim=0) / n - (d.sum(dim=0) / n) ** 2
+        sig = torch.exp(o[..., 1]).clamp(min=1e-6, max=1e6)
+        res = torch.stack([mean, var.clamp(min=0), (sig * sig * w).sum(dim=0) / n], dim=-1)
+    else:
+        p = torch.softmax(o, dim=-1)
+        pm = (p * w[..., None]).sum(dim=0) / n[:, None]
+        h_mean = -torch.special.xlogy(pm, pm).sum(dim=-1)
+        h_draw = -torch.special.xlogy(p, p).sum(dim=-1)
+        mi = (h_mean - (h_draw * w).sum(dim=0) / n).clamp(min=0)
+        mi = torch.where(cnt > 0, mi, torch.full_like(mi, float('nan')))     # (clamp keeps NaN; spelled out)
+        res = torch.cat([pm, h_mean[:, None], mi[:, None]], dim=-1)
+    if return_dropped:
+        return res, (o.shape[0] - cnt).to(torch.int32)
+    return res
+
+
+def rmse_from_moments(y: torch.Tensor, moments: torch.Tensor) -> torch.Tensor:
+    """sqrt(mean_n (y_n - mean_n)^2) of the predictive mean, column 0 of regression moments [N, 3] (``rmse`` of the draws'
+    predicted means, without the draws)."""
+    m = moments[:, 0]
+    return torch.sqrt(((y.to(m.device, m.dtype).reshape(-1) - m) ** 2).mean())

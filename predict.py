@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""Posterior-predictive moments of a finished experiment on NEW inputs (the consumer of mile_predict_moments):
+
+    python predict.py -e results/mile_amd/<experiment> -i <table or .npz> [-o predictions.npz] [--draws-per-pass K]
+
+Reloads config.yaml and the samples the way evaluate.py does, applies the training normalisation the loader recorded
+(normalization.npz, written by train.py) to the rows of the table, reduces all C x S draws on the device and writes, per row:
+
+    regression       mean, epistemic_var, aleatoric_var     (target units, see below)
+    classification   probs [N, K], entropy, mutual_information (nats)
+    both             dropped: draws left out of the row because an output was not finite
+
+The table holds one row per input and the model's features as columns (no target column): .npy, .csv (comma), .data / .txt
+(whitespace), or an .npz with an array ``x`` (images [N, C, H, W], token ids [N, T]).  Where the target was z-scored
+(tabular regression with ``normalize``), y = y_std * y' + y_mean: the mean is mapped back the same way and BOTH variances are
+multiplied by y_std^2.  ``--normalized`` takes rows that already are in the training normalisation and leaves the outputs in
+it.
+"""
+import argparse
+from pathlib import Path
+
+import numpy as np
+import torch
+
+
+def read_table(path) -> np.ndarray:
+    path = str(path)
+    if path.endswith('.npz'):
+        with np.load(path) as z:
+            if 'x' not in z:
+                raise SystemExit(f'{path}: an .npz input needs an array "x"')
+            return np.asarray(z['x'], dtype=np.float32)
+    if path.endswith('.npy'):
+        return np.asarray(np.load(path), dtype=np.float32)
+    if path.endswith('.csv'):
+        return np.atleast_2d(np.loadtxt(path, delimiter=',', dtype=np.float32))
+    if path.endswith('.data') or path.endswith('.txt'):
+        return np.atleast_2d(np.loadtxt(path, dtype=np.float32))
+    raise SystemExit(f'{path}: expected .npy, .csv, .data, .txt or .npz')
+
+
+def load_normalization(exp: Path, loader) -> dict:
+    """normalization.npz of the experiment; an experiment trained before that file existed falls back to the statistics of
+    the loader rebuilt from config.yaml (the same data and seed give the same numbers)."""
+    from mile_amd.dataset import NORMALIZATION_FILE, normalization_stats
+    f = exp / NORMALIZATION_FILE
+    if f.exists():
+        with np.load(f) as z:
+            return {k: np.asarray(z[k], dtype=np.float32) for k in z.files}
+    return normalization_stats(loader)
+
+
+def denormalize(arrays: dict, norm: dict) -> dict:
+    """Regression moments back in target units where the target was z-scored: mean * y_std + y_mean, variances * y_std^2."""
+    if 'y_std' not in norm or 'mean' not in arrays:
+        return arrays
+    ys, ym = float(norm['y_std'].reshape(-1)[0]), float(norm['y_mean'].reshape(-1)[0])
+    out = dict(arrays)
+    out['mean'] = (arrays['mean'] * ys + ym).astype(np.float32)
+    out['epistemic_var'] = (arrays['epistemic_var'] * ys * ys).astype(np.float32)
+    out['aleatoric_var'] = (arrays['aleatoric_var'] * ys * ys).astype(np.float32)
+    return out
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description='posterior-predictive moments of an experiment on a table of new inputs')
+    ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
+    ap.add_argument('--input', '-i', required=True, help='table of inputs: .npy, .csv, .data, .txt, or .npz with an array x')
+    ap.add_argument('--output', '-o', default=None, help='default: <experiment directory>/predictions.npz')
+    ap.add_argument('--draws-per-pass', type=int, default=0, help='draws forwarded at a time (0: the library chooses)')
+    ap.add_argument('--normalized', action='store_true',
+                    help='the rows already are in the training normalisation; the outputs stay in it')
+    ap.add_argument('--drop-nonfinite', action='store_true', help='leave out chains with non-finite samples, as evaluate.py does')
+    ap.add_argument('--device', default='cuda:0')
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
+    exp = Path(args.exp)
+    from evaluate import moment_metrics
+    from mile_amd.callbacks import load_samples_from_dir
+    from mile_amd.config import Config
+    from mile_amd.trainer import BDETrainer
+    cfg = Config.from_file(exp / 'config.yaml').replace(logging=False)
+    tr = BDETrainer.__new__(BDETrainer)            # data + model spec only: no new experiment directory
+    tr.build_model(cfg)
+    spec = tr.prob_model.spec
+    samples = load_samples_from_dir(exp / cfg.training.sampler._dir_name, spec)       # [C, S, d]
+    bad_chains = ~np.isfinite(samples).all(axis=(1, 2))
+    if args.drop_nonfinite and bad_chains.any() and not bad_chains.all():
+        samples = samples[~bad_chains]
+    x = read_table(args.input)
+    norm = {} if args.normalized else load_normalization(exp, tr.loader)
+    if 'x_mean' in norm:
+        if norm['x_mean'].ndim and x.shape[-1] != norm['x_mean'].shape[0]:
+            raise SystemExit(f'{args.input}: {x.shape[-1]} columns, the model was trained on {norm["x_mean"].shape[0]} features')
+        x = ((x - norm['x_mean']) / norm['x_std']).astype(np.float32)
+    x = np.ascontiguousarray(x).reshape(len(x), -1)
+    if x.shape[1] != spec.in_features:
+        raise SystemExit(f'{args.input}: rows of {x.shape[1]} values, the model takes {spec.in_features}')
+    eng = tr.prob_model.engine(torch.from_numpy(np.ascontiguousarray(tr.loader.train_x).reshape(len(tr.loader.train_x), -1)),
+                               torch.from_numpy(np.ascontiguousarray(tr.loader.train_y)), device=args.device)
+    mom, dropped = eng.predict_moments(torch.from_numpy(samples), torch.from_numpy(x), max_draws_per_pass=args.draws_per_pass,
+                                       return_dropped=True)
+    _, arrays = moment_metrics(mom, dropped, np.zeros(len(x), dtype=np.float32), cfg.data.task)
+    arrays = denormalize(arrays, norm)
+    out = Path(args.output) if args.output else exp / 'predictions.npz'
+    np.savez(out, **arrays)
+    print(f'{out}: {len(x)} rows, {samples.shape[0] * samples.shape[1]} draws, {int(arrays["dropped"].sum())} dropped; '
+          + ', '.join(f'{k} {tuple(v.shape)}' for k, v in arrays.items()))
+
+
+if __name__ == '__main__':
+    main()

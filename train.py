@@ -20,6 +20,9 @@ def train_bde(config, n_devices: int):
     from mile_amd.trainer import BDETrainer
     logger.info(f'> Running experiment: {config.experiment_name}')
     trainer = BDETrainer(config=config)
+    if trainer.rank == 0:                          # a side file of its own: the statistics predict.py normalises new inputs with
+        from mile_amd.dataset import save_normalization
+        save_normalization(trainer.exp_dir, trainer.loader)
     trainer.train_bde()
 
 
