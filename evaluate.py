@@ -3,7 +3,7 @@
 mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
 src/inference/metrics.py:247-312):
 
-    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--moments]
+    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]]
 
 Reloads config.yaml and the samples/<chain>/sample_<n>.npz files, rebuilds the data split with the same
 seed, evaluates all C x S samples on the split in one device pass and writes metrics.json next to them.
@@ -129,6 +129,20 @@ def moment_metrics(moments, dropped, y, task):
     return out, arrays
 
 
+def running_metrics(res):
+    """--running: the metrics.json keys and the running_lppd.npz arrays of Engine.lppd_stream's result ``res``.  Keys: the
+    ensemble LPPD and each chain's from the stream, the first and last value of both curves (``running_lppd``, the LPPD of all draws, is
+    also the last point of the ensemble curve), and the (draw, row) pairs dropped in all."""
+    arrays = {k: res[k].detach().cpu().numpy() for k in ('curve_points', 'run_chain', 'run_ens', 'chain_lppd', 'row_lppd', 'dropped')}
+    pc = [float(v) for v in arrays['chain_lppd']]
+    out = {'running_points': int(len(arrays['curve_points'])), 'running_lppd': float(res['lppd'].item()),
+           'running_per_chain_lppd': pc, 'running_per_chain_lppd_median': float(np.nanmedian(pc)),
+           'running_ens_first': float(arrays['run_ens'][0]), 'running_ens_last': float(arrays['run_ens'][-1]),
+           'running_chain_first': float(arrays['run_chain'][0]), 'running_chain_last': float(arrays['run_chain'][-1]),
+           'running_dropped': int(arrays['dropped'].sum())}
+    return out, arrays
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description='LPPD / NLL of the samples of an experiment directory')
     ap.add_argument('--diagnostics', type=int, nargs='?', const=2, default=None, metavar='N_SPLITS',
@@ -139,6 +153,11 @@ def build_parser():
                     help='posterior-predictive moments of all draws on the split, reduced on the device (mile_predict_moments): '
                          'moments_* keys in metrics.json and the per-row arrays in moments.npz (regression: mean, epistemic_var, '
                          'aleatoric_var; classification: probs, entropy, mutual_information; both: dropped)')
+    ap.add_argument('--running', type=int, nargs='?', const=64, default=None, metavar='N_POINTS',
+                    help='LPPD against the number of draws, streamed on the device (mile_lppd_stream) at N_POINTS draw counts spaced '
+                         'geometrically from 1 to n_samples (default 64): running_* keys in metrics.json -- the ensemble and per-chain '
+                         'LPPD from the stream, the ends of both curves -- and curve_points, run_chain, run_ens, chain_lppd, row_lppd, '
+                         'dropped in running_lppd.npz')
     ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
     ap.add_argument('--split', default='test', choices=['train', 'valid', 'test'])
     ap.add_argument('--device', default='cuda:0')
@@ -254,6 +273,13 @@ def main():
         keys, arrays = moment_metrics(mom, dropped, np.ascontiguousarray(y), cfg.data.task)
         out.update(keys)
         np.savez(exp / 'moments.npz', **arrays)
+    if args.running is not None:
+        from mile_amd.metrics import curve_points, streamed_lppd
+        res = streamed_lppd(eng, torch.from_numpy(samples), torch.from_numpy(x), torch.from_numpy(np.ascontiguousarray(y)),
+                            curve_points=curve_points(samples.shape[1], args.running))
+        keys, arrays = running_metrics(res)
+        out.update(keys)
+        np.savez(exp / 'running_lppd.npz', **arrays)
     (exp / 'metrics.json').write_text(json.dumps(out, indent=1) + '\n')
     print(json.dumps({k: v for k, v in out.items() if not isinstance(v, (list, dict))}))        # the per-chain arrays stay in metrics.json
 

@@ -387,6 +387,37 @@ int32_t mile_predict_moments(mile_sampler *s, const float *theta, int64_t S, con
                              int32_t *dropped, int64_t max_draws_per_pass, void *stream);
 int32_t mile_predict_moments_width(const mile_sampler *s);
 
+/* Streamed LPPD and its running curves (the reference's lppd and running_lppd, src/inference/metrics.py:297-312, 408-446, and
+ * the per-chain LPPD of src/inference/evaluation.py:520-529), reduced on the device without a [C, S, N] tensor.
+ * theta [C * S, d] full-layout (partition mode included, as for mile_pointwise_loglik): draw j of chain c is row c * S + j.
+ * X [N, F] and y [N] as for mile_pointwise_loglik.  curve_points [K] int32, 1 <= k_1 < ... < k_K <= S: the draw counts per
+ * chain at which the curves are taken (read back to the host for their check).  With l = log p(y_n | x_n, theta_{c,j}),
+ * A_k[c][n] = logsumexp over the first k draws of chain c, cnt_k(c, n) the draws of those that are not NaN:
+ *   run_chain [K]:   mean_c mean_n (A_k - log cnt_k) at k = k_i: running_lppd at k, without exp(l) underflowing
+ *   run_ens   [K]:   mean_n (logsumexp_c A_k - log sum_c cnt_k): lppd of the first k draws of all chains
+ *   chain_lppd [C], row_lppd [N], lppd [1]: after all S draws, mean_n (A_S - log cnt_S) of each chain, the ensemble term of
+ *                    each row, and its mean over the rows (= the last run_ens when k_K = S)
+ *   dropped [C] int64: (draw, row) pairs of chain c left out
+ * All fp64, all device pointers; an output not wanted is null (K = 0: no curve).
+ * A draw whose log-likelihood on row n is NaN is left out of (chain c, row n) and counted (per draw and per row, the rule of
+ * mile_predict_moments); +inf and -inf take part as values, -inf adding 0.  A (chain, row) with every draw left out makes
+ * that chain's figures NaN, run_chain with them; the ensemble figures skip that chain on that row.
+ * The forward is mile_pointwise_loglik's, the same window of at most max_draws_per_pass draws of every chain at a time
+ * (0: as many as fit 256 MiB of [C * J, N] floats; at most 65535) into a workspace the handle owns and grows here; a pass is
+ * split at each curve point.  The state is a streaming log-sum-exp (max, scaled sum) in fp64 per (chain, row), the row
+ * means are a per-wave sum followed by a one-workgroup sum, both in a fixed order and without atomics: the outputs are
+ * bitwise the same for every max_draws_per_pass.  mile_lppd_stream_workspace: bytes of the state and partial sums for
+ * (C, N), what the workspace holds beyond the pass's [C * J, N] floats; -1 for a null handle or a shape out of range.
+ * MILE_ERR_INVALID: a null handle / theta / X / y, C outside [1, 65535], S < 1, N < 1 or > 2^30 - 1, K < 0 or > S, K = 0
+ * with run_chain or run_ens, K > 0 with null curve_points or without a curve output, no output at all, curve points not
+ * strictly increasing or outside [1, S], max_draws_per_pass < 0; MILE_ERR_STATE: frozen tables not set; MILE_ERR_NOMEM: the
+ * workspace.  Nothing is launched on any of them.
+ * (Added under ABI 10: two new symbols, no struct or existing entry changed.) */
+int32_t mile_lppd_stream(mile_sampler *s, const float *theta, int32_t C, int32_t S, const void *X, const void *y, int64_t N,
+                         const int32_t *curve_points, int32_t K, double *run_chain, double *run_ens, double *chain_lppd,
+                         double *row_lppd, double *lppd, int64_t *dropped, int64_t max_draws_per_pass, void *stream);
+int64_t mile_lppd_stream_workspace(const mile_sampler *s, int32_t C, int64_t N);
+
 /* Which outputs mile_chain_diagnostics computes (`what`), and how it reads its input. */
 #define MILE_DIAG_WCV 1u
 #define MILE_DIAG_BCV 2u

@@ -30,6 +30,7 @@
 #include "mile_nuts.h"
 #include "mile_diag.h"
 #include "mile_moments.h"
+#include "mile_lppd.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -66,6 +67,7 @@ struct mile_sampler {
   int64_t nz_launches = 0;              // mid-step launches that prefilled noise (mile_debug_prefill_count)
   float *ev_X = nullptr, *ev_Xp = nullptr; void *ev_y = nullptr; int ev_cap = 0;   // evaluation (test) set staging
   void *mom_ws = nullptr; size_t mom_ws_bytes = 0;   // mile_predict_moments: one pass of raw outputs, then the accumulators
+  void *lppd_ws = nullptr; size_t lppd_ws_bytes = 0; // mile_lppd_stream: one pass of log-likelihoods, then the state and partial sums
   float *alt_x = nullptr, *alt_u = nullptr, *alt_g = nullptr, *alt_logp = nullptr;   // ping-pong state of mile_tune
   int grad_kernel = MILE_GRAD_AUTO;
   LeNetGeom lg{};                       // MILE_MODEL_LENET geometry and parameter offsets
@@ -612,6 +614,7 @@ int32_t mile_destroy(mile_sampler *s) {
   if (s->ev_Xp) (void)hipFree(s->ev_Xp);
   if (s->ev_y) (void)hipFree(s->ev_y);
   if (s->mom_ws) (void)hipFree(s->mom_ws);
+  if (s->lppd_ws) (void)hipFree(s->lppd_ws);
   free_data(s);
   free_ws(s);
   if (s->gemm_ws) (void)hipFree(s->gemm_ws);
@@ -2199,9 +2202,8 @@ static constexpr bool rows_in_id_order() {
 static_assert(rows_in_id_order(), "kGrad: one row per MILE_GRAD_* id, in id order");
 static const GradKernel &grad_kernel(int kernel) { return kGrad[kernel - 1]; }
 
-// mile_pointwise_loglik and (y == nullptr) mile_predict: stage the evaluation rows, then the resolved kernel's `loglik`
-static int evaluate_rows(mile_sampler *s, const float *theta, int32_t S, const float *X, const void *y, int64_t N, float *out, void *stream) {
-  hipStream_t st = (hipStream_t)stream;
+// stage the evaluation rows (and labels) in the handle and describe them in pp; theta and out are the caller's to fill in
+static int stage_rows(mile_sampler *s, const float *X, const void *y, int64_t N, PredParams &pp, hipStream_t st) {
   HIP_TRY(hipSetDevice(s->device));
   const int F = s->spec.in_features, Npad = ((int)N + 31) / 32 * 32, Fp = (F + 7) / 8 * 8;
   if (Npad > s->ev_cap) {   // evaluation is off the stepping path: (re)allocate its staging here
@@ -2221,9 +2223,18 @@ static int evaluate_rows(mile_sampler *s, const float *theta, int32_t S, const f
   }
   const long long tot = (long long)Npad * Fp;
   k_pad_x<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(s->ev_X, s->ev_Xp, (int)N, Npad, F, Fp);
-  PredParams pp;
-  pp.spec = s->ds; pp.theta = theta; pp.X = s->ev_X; pp.Xp = s->ev_Xp; pp.y = y ? s->ev_y : nullptr; pp.out = out;
+  pp.spec = s->ds; pp.theta = nullptr; pp.X = s->ev_X; pp.Xp = s->ev_Xp; pp.y = y ? s->ev_y : nullptr; pp.out = nullptr;
   pp.N = (int)N; pp.Npad = Npad; pp.Fp = Fp; pp.R = generic_R(s->ds);
+  return MILE_OK;
+}
+
+// mile_pointwise_loglik and (y == nullptr) mile_predict: stage the evaluation rows, then the resolved kernel's `loglik`
+static int evaluate_rows(mile_sampler *s, const float *theta, int32_t S, const float *X, const void *y, int64_t N, float *out, void *stream) {
+  hipStream_t st = (hipStream_t)stream;
+  PredParams pp;
+  const int rc = stage_rows(s, X, y, N, pp, st);
+  if (rc != MILE_OK) return rc;
+  pp.theta = theta; pp.out = out;
   return grad_kernel(resolved_kernel(s)).loglik(s, pp, S, st);
 }
 
@@ -2244,7 +2255,7 @@ extern "C" int32_t mile_predict(mile_sampler *s, const float *theta, int32_t S, 
 
 // mile_predict_moments: mile_predict's forward in passes of `chunk` draws into the library's workspace, each folded into the
 // per-row accumulators by k_moments_accum; k_moments_finish writes out.  Every check before any launch.
-static const int64_t MOM_RAW_TARGET = (int64_t)256 << 20;   // bytes of raw outputs per pass when the caller leaves the choice
+static const int64_t EVAL_PASS_TARGET = (int64_t)256 << 20;   // bytes of forward outputs per pass (moments, streamed LPPD) when the caller leaves the choice
 
 extern "C" int32_t mile_predict_moments_width(const mile_sampler *s) {
   if (!s) return fail(MILE_ERR_INVALID, "mile_predict_moments_width: null handle");
@@ -2264,7 +2275,7 @@ extern "C" int32_t mile_predict_moments(mile_sampler *s, const float *theta, int
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->device));
   const int64_t per_draw = N * O * 4;
-  int64_t chunk = max_draws_per_pass ? max_draws_per_pass : std::max<int64_t>(1, MOM_RAW_TARGET / per_draw);
+  int64_t chunk = max_draws_per_pass ? max_draws_per_pass : std::max<int64_t>(1, EVAL_PASS_TARGET / per_draw);
   chunk = std::min<int64_t>(chunk, S);
   // enough one-wave workgroups for about eight waves per CU, at most one slice per draw of a pass
   const int slices = (int)std::min<int64_t>(std::min<int64_t>(MOM_MAX_SLICES, chunk), std::max<int64_t>(1, ((int64_t)s->n_cu * 8 * MOM_NT + N - 1) / N));
@@ -2291,6 +2302,98 @@ extern "C" int32_t mile_predict_moments(mile_sampler *s, const float *theta, int
     HIP_TRY(mile_launch_moments_accum(task, p, st));
   }
   HIP_TRY(mile_launch_moments_finish(task, p, st));
+  return MILE_OK;
+}
+
+// mile_lppd_stream: mile_pointwise_loglik's forward on the same draw window of every chain, a pass at a time, into the library's
+// workspace; k_lppd_accum folds the pass into the (m, s) state up to the next curve point, k_lppd_emit reduces the state there.
+// Every check before any launch (the curve points come to the host for theirs: a copy, no kernel).
+static bool lppd_shape_ok(int32_t C, int64_t N) { return C >= 1 && C <= LPPD_C_MAX && N >= 1 && N <= 0x3fffffff; }
+
+extern "C" int64_t mile_lppd_stream_workspace(const mile_sampler *s, int32_t C, int64_t N) {
+  if (!s || !lppd_shape_ok(C, N)) return -1;
+  return (int64_t)lppd_state_bytes(C, N);
+}
+
+extern "C" int32_t mile_lppd_stream(mile_sampler *s, const float *theta, int32_t C, int32_t S, const void *X, const void *y, int64_t N,
+                                    const int32_t *curve_points, int32_t K, double *run_chain, double *run_ens, double *chain_lppd,
+                                    double *row_lppd, double *lppd, int64_t *dropped, int64_t max_draws_per_pass, void *stream) {
+  if (!s || !theta || !X || !y) return fail(MILE_ERR_INVALID, "mile_lppd_stream: null handle, theta, X or y");
+  if (!lppd_shape_ok(C, N)) return fail(MILE_ERR_INVALID, "mile_lppd_stream: C (1 .. 65535) or N (1 .. 2^30 - 1) out of range");
+  if (S < 1) return fail(MILE_ERR_INVALID, "mile_lppd_stream: S out of range");
+  if (K < 0 || K > S) return fail(MILE_ERR_INVALID, "mile_lppd_stream: K out of range (0 .. S)");
+  if (K == 0 && (run_chain || run_ens)) return fail(MILE_ERR_INVALID, "mile_lppd_stream: K = 0 with a curve output");
+  if (K > 0 && !curve_points) return fail(MILE_ERR_INVALID, "mile_lppd_stream: null curve_points");
+  if (K > 0 && !run_chain && !run_ens) return fail(MILE_ERR_INVALID, "mile_lppd_stream: curve points without a curve output");
+  if (K == 0 && !chain_lppd && !row_lppd && !lppd && !dropped) return fail(MILE_ERR_INVALID, "mile_lppd_stream: no output asked for");
+  if (max_draws_per_pass < 0) return fail(MILE_ERR_INVALID, "mile_lppd_stream: max_draws_per_pass < 0");
+  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->device));
+  std::vector<int32_t> pts((size_t)K);
+  if (K > 0) {
+    HIP_TRY(hipMemcpyAsync(pts.data(), curve_points, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < K; ++i) {
+      if (pts[i] < 1 || pts[i] > S) return fail(MILE_ERR_INVALID, "mile_lppd_stream: curve point outside [1, S]");
+      if (i > 0 && pts[i] <= pts[i - 1]) return fail(MILE_ERR_INVALID, "mile_lppd_stream: curve points not strictly increasing");
+    }
+  }
+  const int64_t per_draw = (int64_t)C * N * 4;   // one draw of every chain
+  int64_t J = max_draws_per_pass ? max_draws_per_pass : std::max<int64_t>(1, EVAL_PASS_TARGET / per_draw);
+  J = std::min<int64_t>(std::min<int64_t>(J, S), LPPD_J_MAX);
+  const size_t raw_bytes = ((size_t)J * per_draw + 255) / 256 * 256, st_bytes = lppd_state_bytes(C, N);
+  if (raw_bytes + st_bytes > s->lppd_ws_bytes) {   // evaluation is off the stepping path: (re)allocate here
+    if (s->lppd_ws) (void)hipFree(s->lppd_ws);
+    s->lppd_ws = nullptr; s->lppd_ws_bytes = 0;
+    if (hipMalloc(&s->lppd_ws, raw_bytes + st_bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(MILE_ERR_NOMEM, "mile_lppd_stream: workspace allocation failed (lower max_draws_per_pass)");
+    }
+    s->lppd_ws_bytes = raw_bytes + st_bytes;
+  }
+  const size_t cn = (size_t)C * (size_t)N;
+  LppdParams p{};
+  p.ll = (const float *)s->lppd_ws; p.C = C; p.N = (int)N; p.S = S; p.waves = lppd_waves(N);
+  p.state = (double2 *)((char *)s->lppd_ws + raw_bytes);
+  p.cnt = (int32_t *)(p.state + cn);
+  p.part_ens = (double *)((char *)p.cnt + (cn * 4 + 7) / 8 * 8);
+  p.part_chain = p.part_ens + p.waves;
+  p.part_cnt = (long long *)(p.part_chain + (size_t)p.waves * C);
+  p.run_chain = run_chain; p.run_ens = run_ens; p.chain_lppd = chain_lppd; p.row_lppd = row_lppd; p.lppd = lppd;
+  p.dropped = (long long *)dropped;
+  const bool want_final = chain_lppd || row_lppd || lppd || dropped;
+  PredParams pp;
+  const int rc0 = stage_rows(s, (const float *)X, y, N, pp, st);
+  if (rc0 != MILE_OK) return rc0;
+  const GradKernel &gk = grad_kernel(resolved_kernel(s));
+  p.fresh = 1;    // the first launch of k_lppd_accum starts every (chain, row) at (m, s) = (-inf, 0), cnt = 0
+  int next = 0;   // next curve point
+  for (int64_t j0 = 0; j0 < S; j0 += J) {
+    p.J = (int)std::min<int64_t>(J, S - j0);
+    for (int c = 0; c < C; ++c) {   // chain c's draws j0 .. j0 + J - 1 are rows c * S + j0 .. of theta
+      pp.theta = theta + ((size_t)c * S + (size_t)j0) * s->ds.d;
+      pp.out = (float *)s->lppd_ws + (size_t)c * p.J * N;
+      const int rc = gk.loglik(s, pp, p.J, st);
+      if (rc != MILE_OK) return rc;
+    }
+    int ja = 0;
+    while (ja < p.J) {   // split the pass at every curve point inside it
+      const int jb = next < K && pts[next] <= j0 + p.J ? (int)(pts[next] - j0) : p.J;
+      p.ja = ja; p.jb = jb;
+      HIP_TRY(mile_launch_lppd_accum(p, st));
+      p.fresh = 0;
+      if (next < K && pts[next] == j0 + jb) {
+        p.point = next++;
+        HIP_TRY(mile_launch_lppd_emit(p, want_final && j0 + jb == S, st));
+      }
+      ja = jb;
+    }
+  }
+  if (want_final && (K == 0 || pts[K - 1] != S)) {
+    p.point = -1;
+    HIP_TRY(mile_launch_lppd_emit(p, true, st));
+  }
   return MILE_OK;
 }
 

@@ -622,6 +622,51 @@ class Engine:
                                                      _ptr(dropped), int(max_draws_per_pass), self._stream()), self.lib)
         return (out, dropped) if return_dropped else out
 
+    def lppd_stream_workspace(self, C: int, N: int) -> int:
+        """Bytes of the (max, scaled sum) state and partial sums ``lppd_stream`` keeps for C chains on N rows, beyond the
+        pass's block of log-likelihoods (mile_lppd_stream_workspace)."""
+        return int(self.lib.mile_lppd_stream_workspace(self._h, int(C), int(N)))
+
+    def lppd_stream(self, samples, x, y, curve_points=None, max_draws_per_pass: int = 0) -> dict:
+        """LPPD of samples [C, S, d] on (x [N, F], y [N]) and its curves over the number of draws, reduced on the device
+        (mile_lppd_stream) -- ``metrics.lppd`` and ``metrics.running_lppd`` of ``pointwise_loglik``'s [C, S, N] tensor without
+        ever holding it, and without the underflow of exp(l).  ``curve_points``: increasing draw counts per chain in
+        [1, S] (None: ``metrics.curve_points(S)``; empty: no curves).  Returns fp64 tensors on the device:
+        ``curve_points`` [K] int32, ``run_chain`` [K] (the chain-averaged running LPPD), ``run_ens`` [K] (the LPPD of the
+        first k draws of all chains), ``chain_lppd`` [C], ``row_lppd`` [N], ``lppd`` [] and ``dropped`` [C] int64, the (draw,
+        row) pairs of each chain left out for a NaN log-likelihood.  ``max_draws_per_pass`` bounds the draws of each chain
+        forwarded at a time (0: the library's choice); the outputs do not depend on it, bit for bit.  A host ``samples`` is
+        uploaded whole: the library reads all chains' windows from one device array."""
+        from mile_amd.metrics import curve_points as default_points
+        theta = _f32(samples, self.device, name='samples')
+        if theta.ndim != 3 or theta.shape[2] != self.d:
+            raise ValueError(f'samples must be [C, S, {self.d}]')
+        C_, S_ = int(theta.shape[0]), int(theta.shape[1])
+        X = _f32(x, self.device, name='x')
+        y = torch.as_tensor(y, device=self.device)
+        y = (y.to(torch.float32) if self.spec.task == 'regr' else y.to(torch.int32)).contiguous()
+        if isinstance(self.spec, IMAGE_SPECS) and X.ndim == 4:
+            X = X.reshape(X.shape[0], -1).contiguous()
+        if X.ndim != 2 or X.shape[1] != self.spec.in_features or y.shape != (X.shape[0],):
+            raise ValueError('x must be [N, F] and y [N]')
+        _check_tokens(self.spec, X)
+        if self.spec.task != 'regr' and y.numel():       # the kernels index the logits with the raw label
+            if int(y.min()) < 0 or int(y.max()) >= self.spec.hidden_structure[-1]:
+                raise ValueError('class labels out of range')
+        pts = default_points(S_) if curve_points is None else curve_points
+        pts = torch.as_tensor(pts, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
+        K, N = int(pts.numel()), int(X.shape[0])
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)
+        out = {'curve_points': pts, 'run_chain': f64(K), 'run_ens': f64(K), 'chain_lppd': f64(C_), 'row_lppd': f64(N),
+               'lppd': f64(), 'dropped': torch.empty(C_, dtype=torch.int64, device=self.device)}
+        curve = lambda k: _ptr(out[k]) if K else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_lppd_stream(self._h, _ptr(theta), C_, S_, _ptr(X), _ptr(y), N, _ptr(pts) if K else None, K,
+                                                 curve('run_chain'), curve('run_ens'), _ptr(out['chain_lppd']),
+                                                 _ptr(out['row_lppd']), _ptr(out['lppd']), _ptr(out['dropped']),
+                                                 int(max_draws_per_pass), self._stream()), self.lib)
+        return out
+
     @property
     def supports_device_tuner(self) -> bool:
         return self.dim >= 4

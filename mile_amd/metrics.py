@@ -69,6 +69,34 @@ def running_lppd(lppd_pointwise: torch.Tensor) -> torch.Tensor:
     return torch.log(torch.cumsum(e, dim=1) / cnt).mean(dim=-1).mean(dim=0)
 
 
+def curve_points(S: int, n: int = 64) -> list:
+    """Default draw counts of the LPPD-versus-draws curves: all of 1..S when S <= n, otherwise n points spaced
+    geometrically from 1 to S (rounded, repeats moved up to the next free integer), 1 and S always among them."""
+    S, n = int(S), int(n)
+    if S < 1 or n < 1:
+        raise ValueError('curve_points: S >= 1 and n >= 1')
+    if S <= n:
+        return list(range(1, S + 1))
+    if n == 1:
+        return [S]
+    pts, prev = [], 0
+    for i in range(n):
+        k = max(prev + 1, int(round(S ** (i / (n - 1)))))
+        k = min(k, S - (n - 1 - i))                                    # room for the points still to come
+        pts.append(k)
+        prev = k
+    pts[-1] = S
+    return pts
+
+
+def streamed_lppd(engine, samples, x, y, curve_points=None, max_draws_per_pass: int = 0) -> dict:
+    """``lppd`` and ``running_lppd`` of samples [C, S, d] on (x, y), the LPPD of each chain and of each row, streamed on the
+    device in a stable log-sum-exp form (Engine.lppd_stream / mile_lppd_stream): no [C, S, N] tensor, no -inf from exp(l)
+    underflowing.  ``run_chain`` is ``running_lppd`` at the curve points, ``run_ens`` is ``lppd`` of the first k draws of
+    every chain, ``lppd`` the figure of all draws."""
+    return engine.lppd_stream(samples, x, y, curve_points=curve_points, max_draws_per_pass=max_draws_per_pass)
+
+
 def rank_normalize_array(samples: torch.Tensor) -> torch.Tensor:
     """metrics.py:226-244: overall ranks (average rank for ties) -> normal quantiles."""
     flat = samples.reshape(-1).to(torch.float64)
