@@ -121,8 +121,9 @@ def loglik_and_grad(spec, theta, x, y, dtype=np.float64, mutant=None):
     lg = f['logits']
     m = lg.max(axis=1, keepdims=True)
     sm = np.exp(lg - m)
-    sm /= sm.sum(axis=1, keepdims=True)
-    ll = float(np.sum(np.log(sm[np.arange(N), y])))
+    den = sm.sum(axis=1, keepdims=True)
+    ll = float(np.sum((lg - m - np.log(den))[np.arange(N), y]))     # log-softmax, not log(softmax): a label 104 below the row maximum is exp() = 0 in float32
+    sm /= den
     G = {n: np.zeros_like(v) for n, v in P.items()}
     dl = -sm
     dl[np.arange(N), y] += 1.0
