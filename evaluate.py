@@ -3,7 +3,7 @@
 mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
 src/inference/metrics.py:247-312):
 
-    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]]
+    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals]
 
 Reloads config.yaml and the samples/<chain>/sample_<n>.npz files, rebuilds the data split with the same
 seed, evaluates all C x S samples on the split in one device pass and writes metrics.json next to them.
@@ -143,6 +143,28 @@ def running_metrics(res):
     return out, arrays
 
 
+def interval_metrics(quant, pit, dropped, levels, coverages):
+    """--intervals: the metrics.json keys and the intervals.npz arrays of the ensemble's exact predictive quantiles [N, Q] at
+    ``levels`` (``metrics.interval_levels(coverages)``), the PIT [N] and ``dropped`` [N] (Engine.predict_quantiles, or
+    metrics.mixture_quantiles / mixture_pit of raw outputs).  Keys: the observed coverage of each central interval from the
+    PIT (no draws, no seed), the calibration error of those, the mean width of each interval, the draws dropped in all."""
+    from mile_amd import metrics as M
+    q = quant.detach().double().cpu()
+    lv = [float(v) for v in levels]
+    cov = M.coverage_from_pit(pit.detach().cpu(), coverages)
+    out = {}
+    for c, v in zip(coverages, cov):
+        lo, hi = (lv.index(float(a)) for a in M.get_quantiles(float(c)))
+        out[f'intervals_coverage_{c}'] = float(v)
+        out[f'intervals_width_{c}'] = float(torch.nanmean(q[:, hi] - q[:, lo]))
+    out['intervals_cal_error'] = float(M.calibration_error(coverages, cov).item())
+    drop = dropped.detach().cpu().numpy().astype(np.int32)
+    out['intervals_dropped'] = int(drop.sum())
+    arrays = {'levels': np.asarray(lv, dtype=np.float64), 'quantiles': q.numpy().astype(np.float32),
+              'pit': pit.detach().cpu().numpy().astype(np.float32), 'dropped': drop}
+    return out, arrays
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description='LPPD / NLL of the samples of an experiment directory')
     ap.add_argument('--diagnostics', type=int, nargs='?', const=2, default=None, metavar='N_SPLITS',
@@ -158,6 +180,11 @@ def build_parser():
                          'geometrically from 1 to n_samples (default 64): running_* keys in metrics.json -- the ensemble and per-chain '
                          'LPPD from the stream, the ends of both curves -- and curve_points, run_chain, run_ens, chain_lppd, row_lppd, '
                          'dropped in running_lppd.npz')
+    ap.add_argument('--intervals', action='store_true',
+                    help='regression: exact quantiles of the ensemble\'s predictive mixture at the levels of --coverages and the PIT, '
+                         'solved on the device (mile_predict_quantiles): intervals_coverage_<c>, intervals_width_<c>, '
+                         'intervals_cal_error and intervals_dropped in metrics.json -- no draws, so no seed and no Monte-Carlo noise -- '
+                         'and levels, quantiles, pit, dropped in intervals.npz')
     ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
     ap.add_argument('--split', default='test', choices=['train', 'valid', 'test'])
     ap.add_argument('--device', default='cuda:0')
@@ -179,6 +206,8 @@ def main():
     from mile_amd.trainer import BDETrainer
     cfg = Config.from_file(exp / 'config.yaml').replace(logging=False)
     tr = BDETrainer.__new__(BDETrainer)            # data + model spec only: no new experiment directory
+    if args.intervals and cfg.data.task != 'regr':
+        raise SystemExit('--intervals: predictive intervals are for regression experiments; this one is classification')
     tr.build_model(cfg)
     spec = tr.prob_model.spec
     samples = load_samples_from_dir(exp / cfg.training.sampler._dir_name, spec)       # [C, S, d]
@@ -280,6 +309,14 @@ def main():
         keys, arrays = running_metrics(res)
         out.update(keys)
         np.savez(exp / 'running_lppd.npz', **arrays)
+    if args.intervals:
+        from mile_amd.metrics import interval_levels
+        levels = interval_levels(args.coverages)
+        quant, pit, dropped = eng.predict_quantiles(torch.from_numpy(samples), torch.from_numpy(x), levels,
+                                                    y=torch.from_numpy(np.ascontiguousarray(y)), return_dropped=True)
+        keys, arrays = interval_metrics(quant, pit, dropped, levels, args.coverages)
+        out.update(keys)
+        np.savez(exp / 'intervals.npz', **arrays)
     (exp / 'metrics.json').write_text(json.dumps(out, indent=1) + '\n')
     print(json.dumps({k: v for k, v in out.items() if not isinstance(v, (list, dict))}))        # the per-chain arrays stay in metrics.json
 

@@ -387,6 +387,43 @@ int32_t mile_predict_moments(mile_sampler *s, const float *theta, int64_t S, con
                              int32_t *dropped, int64_t max_draws_per_pass, void *stream);
 int32_t mile_predict_moments_width(const mile_sampler *s);
 
+/* Exact predictive quantiles and probability integral transform of the ensemble.  On row n the predictive is the equal-weight
+ * mixture of the kept draws' Normals, F_n(t) = mean_s Phi((t - mu_sn) / sigma_sn), sigma = clip(exp(log sigma), 1e-6, 1e6) as in
+ * mile_pointwise_loglik; quant[n, i] is the root of F_n(t) = levels[i] and pit[n] = F_n(y_n).  y_n lies in the central
+ * interval of coverage c exactly when |pit[n] - 1/2| <= c / 2.
+ * raw [S, N, 2] fp32 (mu, log sigma) as mile_predict writes them; levels [Q] fp64 on the HOST, strictly inside (0, 1),
+ * strictly increasing, 1 <= Q <= 32; y [N] fp32 device or null; quant [N, Q] fp32 or null; pit [N] fp32 or null (needs y);
+ * dropped [N] int32 or null.
+ * A draw is left out of row n if either of its two raw outputs there is NaN or +-inf (per draw and per row, the rule of
+ * mile_predict_moments); dropped[n] counts them, and a row with nothing kept holds NaN in quant and pit.  Quantiles of
+ * increasing levels are non-decreasing.  The root is bracketed exactly by min_s and max_s of mu_s + Phi^-1(p) sigma_s and
+ * found by a bracketed Newton iteration on fp64 sums of Phi (through erfc) and of the density, all levels in one sweep over the
+ * row's components, until the bracket is below 2^-25 max(|mid|, sd_n), sd_n the mixture's standard deviation; sums in a
+ * fixed order, no atomics: a row's result depends on its S pairs alone, bit for bit.
+ * mile_mixture_quantiles needs no handle (outputs from anywhere, a deep ensemble's members for example); its workspace (the
+ * packed copy of a row tile, at most 256 MiB) is allocated and freed in the call, which returns after the kernels finish.
+ * mile_predict_quantiles is the same for draws theta [S, d] full-layout on X [N, F]: mile_predict's forward, never
+ * [S, N, 2] at once.  The rows go in tiles of Nt rows, [S][Nt][2] floats plus the packed copy within 256 MiB (Nt a multiple
+ * of 32 where it can be; max_rows_per_tile > 0 caps it, 0: the library's choice); inside a tile the forward runs in passes of
+ * at most max_draws_per_pass draws (0: all), each written at its draw offset, every (draw, row) forward exactly once.  The
+ * workspace is the handle's and grown in the call; mile_predict_quantiles_workspace gives its bytes for (S, N) with the
+ * library's tile, -1 for a null handle or a shape out of range.  The result is bitwise the same for every
+ * max_draws_per_pass and max_rows_per_tile, and equal to mile_mixture_quantiles of mile_predict's outputs.
+ * MILE_ERR_INVALID: a null raw / handle / theta / X / levels, S < 1 or > 2^31 - 1, N < 1 or > 2^30 - 1, Q outside [1, 32],
+ * levels not strictly increasing or not strictly inside (0, 1), pit without y, neither quant nor pit, a negative pass or tile
+ * size, a handle whose task is not regression; MILE_ERR_STATE: frozen tables not set; MILE_ERR_NOMEM: the workspace.
+ * Nothing is launched on any of them.
+ * (Added under ABI 10: three new symbols, no struct or existing entry changed.) */
+int32_t mile_mixture_quantiles(const float *raw, int64_t S, int64_t N, const double *levels, int32_t Q, const float *y,
+                               float *quant, float *pit, int32_t *dropped, void *stream);
+int32_t mile_predict_quantiles(mile_sampler *s, const float *theta, int64_t S, const void *X, int64_t N,
+                               const double *levels, int32_t Q, const float *y, float *quant, float *pit, int32_t *dropped,
+                               int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream);
+int64_t mile_predict_quantiles_workspace(const mile_sampler *s, int64_t S, int64_t N);   /* bytes; -1 out of range */
+/* Test and tool hook: over the rows of the handle's last mile_predict_quantiles that asked for quantiles, the row count, the
+ * sum of the solver's sweeps and the largest sweep count of a row (synchronises the device). */
+int32_t mile_debug_quantile_sweeps(mile_sampler *s, int64_t *rows, int64_t *total, int32_t *most);
+
 /* Streamed LPPD and its running curves (the reference's lppd and running_lppd, src/inference/metrics.py:297-312, 408-446, and
  * the per-chain LPPD of src/inference/evaluation.py:520-529), reduced on the device without a [C, S, N] tensor.
  * theta [C * S, d] full-layout (partition mode included, as for mile_pointwise_loglik): draw j of chain c is row c * S + j.

@@ -31,6 +31,7 @@
 #include "mile_diag.h"
 #include "mile_moments.h"
 #include "mile_lppd.h"
+#include "mile_quantiles.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -68,6 +69,8 @@ struct mile_sampler {
   float *ev_X = nullptr, *ev_Xp = nullptr; void *ev_y = nullptr; int ev_cap = 0;   // evaluation (test) set staging
   void *mom_ws = nullptr; size_t mom_ws_bytes = 0;   // mile_predict_moments: one pass of raw outputs, then the accumulators
   void *lppd_ws = nullptr; size_t lppd_ws_bytes = 0; // mile_lppd_stream: one pass of log-likelihoods, then the state and partial sums
+  void *qnt_ws = nullptr; size_t qnt_ws_bytes = 0;   // mile_predict_quantiles: a row tile's raw outputs, its packed copy, brackets, sweeps
+  const int32_t *qnt_sweeps = nullptr; int64_t qnt_rows = 0;   // sweeps per row of the last mile_predict_quantiles, in qnt_ws
   float *alt_x = nullptr, *alt_u = nullptr, *alt_g = nullptr, *alt_logp = nullptr;   // ping-pong state of mile_tune
   int grad_kernel = MILE_GRAD_AUTO;
   LeNetGeom lg{};                       // MILE_MODEL_LENET geometry and parameter offsets
@@ -614,6 +617,7 @@ int32_t mile_destroy(mile_sampler *s) {
   if (s->ev_Xp) (void)hipFree(s->ev_Xp);
   if (s->ev_y) (void)hipFree(s->ev_y);
   if (s->mom_ws) (void)hipFree(s->mom_ws);
+  if (s->qnt_ws) (void)hipFree(s->qnt_ws);
   if (s->lppd_ws) (void)hipFree(s->lppd_ws);
   free_data(s);
   free_ws(s);
@@ -2302,6 +2306,186 @@ extern "C" int32_t mile_predict_moments(mile_sampler *s, const float *theta, int
     HIP_TRY(mile_launch_moments_accum(task, p, st));
   }
   HIP_TRY(mile_launch_moments_finish(task, p, st));
+  return MILE_OK;
+}
+
+// mile_mixture_quantiles / mile_predict_quantiles: every check before any launch; rows in tiles whose raw block and packed
+// copy fit the evaluation budget, k_qnt_pack + k_qnt_solve per tile (mile_quantiles.h).
+static double host_Phi(double z) { return 0.5 * std::erfc(-z * 0.70710678118654752440); }
+// Phi^-1(p), 0 < p < 1, in fp64: bisection on the lower tail (where erfc keeps its relative accuracy), mirrored for p > 1/2
+static double host_ndtri(double p) {
+  if (p == 0.5) return 0.0;
+  const double pl = p < 0.5 ? p : 1.0 - p;
+  double lo = -40.0, hi = 0.0;
+  for (int i = 0; i < 200 && hi - lo > 0.0; ++i) {
+    const double mid = 0.5 * (lo + hi);
+    if (mid <= lo || mid >= hi) break;
+    if (host_Phi(mid) < pl) lo = mid; else hi = mid;
+  }
+  double z = 0.5 * (lo + hi);
+  for (int i = 0; i < 2; ++i) {   // Newton polish
+    const double f = std::exp(-0.5 * z * z) * 0.39894228040143267794;
+    if (f > 0.0) z -= (host_Phi(z) - pl) / f;
+  }
+  return p < 0.5 ? z : -z;
+}
+
+static const char *qnt_bad_args(const char *fn, int64_t S, int64_t N, const double *levels, int32_t Q, const float *y,
+                                const float *quant, const float *pit, std::string &msg) {
+  auto bad = [&](const char *m) { msg = std::string(fn) + ": " + m; return msg.c_str(); };
+  if (S < 1 || S > 0x7fffffff) return bad("S out of range (1 .. 2^31 - 1)");
+  if (N < 1 || N > 0x3fffffff) return bad("N out of range (1 .. 2^30 - 1)");
+  if (!levels) return bad("null levels");
+  if (Q < 1 || Q > QNT_MAX_Q) return bad("Q out of range (1 .. 32)");
+  for (int i = 0; i < Q; ++i) {
+    if (!(levels[i] > 0.0 && levels[i] < 1.0)) return bad("levels must lie strictly inside (0, 1)");
+    if (i > 0 && !(levels[i] > levels[i - 1])) return bad("levels must be strictly increasing");
+  }
+  if (!quant && !pit) return bad("neither quantiles nor PIT asked for");
+  if (pit && !y) return bad("PIT needs y");
+  return nullptr;
+}
+
+static int64_t qnt_tile_rows(int64_t S, int64_t N, int64_t max_rows) {
+  int64_t nt = std::max<int64_t>(1, EVAL_PASS_TARGET / (S * 16));   // [S][Nt][2] floats plus the packed copy
+  if (nt >= QNT_TILE) nt = nt / QNT_TILE * QNT_TILE;
+  if (max_rows > 0) nt = std::min(nt, max_rows);
+  return std::min(nt, N);
+}
+// bytes of the workspace behind the raw block for tiles of Nt rows: packed copy, slice partials, levels; then (handle only) sweeps
+static size_t qnt_tail_bytes(int64_t S, int64_t Nt, int slices) {
+  return qnt_pk_bytes(S, Nt) + qnt_part_bytes((int)Nt, QNT_MAX_Q, slices) + qnt_r256(2 * QNT_MAX_Q * 8);
+}
+
+// the tiles of one call: raw0 [S][ld][2] holds rows r0 .. of the tile at raw0 + 2 * (tile offset) when the caller's array is
+// walked (ld = N), or is refilled per tile by `fill` (ld = Nt)
+template <class Fill>
+static int qnt_run(const float *raw_all, char *tail, int64_t S, int64_t N, int64_t Nt, int slices_cu, const double *levels, int32_t Q,
+                   const float *y, float *quant, float *pit, int32_t *dropped, int32_t *sweeps, hipStream_t st, Fill fill) {
+  double lev[2 * QNT_MAX_Q];
+  for (int i = 0; i < Q; ++i) { lev[i] = levels[i]; lev[Q + i] = host_ndtri(levels[i]); }
+  QntParams p{};
+  p.S = (int)S; p.Q = Q;
+  p.pk = (float2 *)tail;
+  char *part = tail + qnt_pk_bytes(S, Nt);
+  const int max_slices = qnt_slices((int)S, (int)Nt, slices_cu);
+  double *lev_d = (double *)(part + qnt_part_bytes((int)Nt, QNT_MAX_Q, max_slices));
+  HIP_TRY(hipMemcpyAsync(lev_d, lev, (size_t)2 * Q * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));   // lev is on this stack
+  p.lev = lev_d;
+  for (int64_t r0 = 0; r0 < N; r0 += Nt) {
+    p.Nt = (int)std::min<int64_t>(Nt, N - r0);
+    p.slices = max_slices;   // of the full tile, for every tile: the partials of a ragged last tile fit behind it
+    p.part_brk = (double *)part;
+    p.part_cnt = (int32_t *)(part + qnt_r256((size_t)p.slices * p.Nt * Q * 16));
+    if (raw_all) { p.raw = raw_all + 2 * r0; p.ld = N; }
+    else {
+      const float *tile = nullptr;
+      const int rc = fill(r0, p.Nt, &tile);
+      if (rc != MILE_OK) return rc;
+      p.raw = tile; p.ld = p.Nt;
+    }
+    p.y = y ? y + r0 : nullptr;
+    p.quant = quant ? quant + r0 * Q : nullptr;
+    p.pit = pit ? pit + r0 : nullptr;
+    p.dropped = dropped ? dropped + r0 : nullptr;
+    p.sweeps = sweeps ? sweeps + r0 : nullptr;
+    HIP_TRY(mile_launch_quantiles(p, st));
+  }
+  return MILE_OK;
+}
+
+extern "C" int32_t mile_mixture_quantiles(const float *raw, int64_t S, int64_t N, const double *levels, int32_t Q, const float *y,
+                                          float *quant, float *pit, int32_t *dropped, void *stream) {
+  if (!raw) return fail(MILE_ERR_INVALID, "mile_mixture_quantiles: null raw");
+  std::string msg;
+  if (qnt_bad_args("mile_mixture_quantiles", S, N, levels, Q, y, quant, pit, msg)) return fail(MILE_ERR_INVALID, msg);
+  hipStream_t st = (hipStream_t)stream;
+  int dev = 0, n_cu = 256;
+  HIP_TRY(hipGetDevice(&dev));
+  (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+  const int64_t Nt = std::min<int64_t>(N, std::max<int64_t>(1, EVAL_PASS_TARGET / (S * 8)));   // the packed copy alone: raw is the caller's
+  void *ws = nullptr;
+  if (hipMalloc(&ws, qnt_tail_bytes(S, Nt, qnt_slices((int)S, (int)Nt, n_cu))) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MILE_ERR_NOMEM, "mile_mixture_quantiles: workspace allocation failed");
+  }
+  const int rc = qnt_run(raw, (char *)ws, S, N, Nt, n_cu, levels, Q, y, quant, pit, dropped, nullptr, st,
+                         [](int64_t, int, const float **) { return (int)MILE_OK; });
+  const hipError_t es = hipStreamSynchronize(st);   // the workspace is this call's: the kernels finish before it goes
+  (void)hipFree(ws);
+  if (rc != MILE_OK) return rc;
+  HIP_TRY(es);
+  return MILE_OK;
+}
+
+extern "C" int64_t mile_predict_quantiles_workspace(const mile_sampler *s, int64_t S, int64_t N) {
+  if (!s || S < 1 || S > 0x7fffffff || N < 1 || N > 0x3fffffff) return -1;
+  const int64_t Nt = qnt_tile_rows(S, N, 0);
+  return (int64_t)(qnt_r256((size_t)S * Nt * 8) + qnt_tail_bytes(S, Nt, qnt_slices((int)S, (int)Nt, s->n_cu)) + qnt_r256((size_t)N * 4));
+}
+
+extern "C" int32_t mile_predict_quantiles(mile_sampler *s, const float *theta, int64_t S, const void *X, int64_t N,
+                                          const double *levels, int32_t Q, const float *y, float *quant, float *pit, int32_t *dropped,
+                                          int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
+  if (!s || !theta || !X) return fail(MILE_ERR_INVALID, "mile_predict_quantiles: null handle, theta or X");
+  std::string msg;
+  if (qnt_bad_args("mile_predict_quantiles", S, N, levels, Q, y, quant, pit, msg)) return fail(MILE_ERR_INVALID, msg);
+  if (max_draws_per_pass < 0) return fail(MILE_ERR_INVALID, "mile_predict_quantiles: max_draws_per_pass < 0");
+  if (max_rows_per_tile < 0) return fail(MILE_ERR_INVALID, "mile_predict_quantiles: max_rows_per_tile < 0");
+  if (s->spec.task != MILE_TASK_REGRESSION || s->spec.widths[s->spec.n_layers - 1] != 2)
+    return fail(MILE_ERR_INVALID, "mile_predict_quantiles: needs a regression model with (mu, log sigma) outputs");
+  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->device));
+  const int64_t Nt = qnt_tile_rows(S, N, max_rows_per_tile);
+  const int64_t chunk = std::min<int64_t>(S, max_draws_per_pass ? max_draws_per_pass : S);
+  const size_t raw_bytes = qnt_r256((size_t)S * Nt * 8), tail_bytes = qnt_tail_bytes(S, Nt, qnt_slices((int)S, (int)Nt, s->n_cu));
+  const size_t need = raw_bytes + tail_bytes + qnt_r256((size_t)N * 4);
+  if (need > s->qnt_ws_bytes) {   // evaluation is off the stepping path: (re)allocate here
+    if (s->qnt_ws) (void)hipFree(s->qnt_ws);
+    s->qnt_ws = nullptr; s->qnt_ws_bytes = 0; s->qnt_rows = 0;
+    if (hipMalloc(&s->qnt_ws, need) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(MILE_ERR_NOMEM, "mile_predict_quantiles: workspace allocation failed (lower max_rows_per_tile)");
+    }
+    s->qnt_ws_bytes = need;
+  }
+  float *raw = (float *)s->qnt_ws;
+  char *tail = (char *)s->qnt_ws + raw_bytes;
+  int32_t *sweeps = (int32_t *)(tail + tail_bytes);
+  s->qnt_rows = 0; s->qnt_sweeps = sweeps;
+  const GradKernel &gk = grad_kernel(resolved_kernel(s));
+  const size_t row_floats = (size_t)s->spec.in_features;
+  auto fill = [&](int64_t r0, int nt, const float **tile) -> int {   // every (draw, row) forward once: passes at their draw offset
+    PredParams pp;
+    const int rc0 = stage_rows(s, (const float *)X + (size_t)r0 * row_floats, nullptr, nt, pp, st);
+    if (rc0 != MILE_OK) return rc0;
+    for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+      pp.theta = theta + (size_t)s0 * s->ds.d;
+      pp.out = raw + (size_t)s0 * nt * 2;
+      const int rc = gk.loglik(s, pp, (int)std::min<int64_t>(chunk, S - s0), st);
+      if (rc != MILE_OK) return rc;
+    }
+    *tile = raw;
+    return MILE_OK;
+  };
+  const int rc = qnt_run(nullptr, tail, S, N, Nt, s->n_cu, levels, Q, y, quant, pit, dropped, quant ? sweeps : nullptr, st, fill);
+  if (rc != MILE_OK) return rc;
+  s->qnt_rows = quant ? N : 0;
+  return MILE_OK;
+}
+
+/* test and tool hook: sweeps of k_qnt_solve over the rows of the handle's last mile_predict_quantiles that asked for quantiles */
+extern "C" int32_t mile_debug_quantile_sweeps(mile_sampler *s, int64_t *rows, int64_t *total, int32_t *most) {
+  if (!s || !rows || !total || !most) return fail(MILE_ERR_INVALID, "mile_debug_quantile_sweeps: null argument");
+  *rows = s->qnt_rows; *total = 0; *most = 0;
+  if (!s->qnt_rows) return MILE_OK;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<int32_t> h((size_t)s->qnt_rows);
+  HIP_TRY(hipMemcpy(h.data(), s->qnt_sweeps, h.size() * 4, hipMemcpyDeviceToHost));
+  for (int32_t v : h) { *total += v; *most = std::max(*most, v); }
   return MILE_OK;
 }
 

@@ -622,6 +622,86 @@ class Engine:
                                                      _ptr(dropped), int(max_draws_per_pass), self._stream()), self.lib)
         return (out, dropped) if return_dropped else out
 
+    @staticmethod
+    def _quantile_levels(levels):
+        lv = [float(v) for v in torch.as_tensor(levels, dtype=torch.float64).reshape(-1)]
+        if not 1 <= len(lv) <= 32:
+            raise ValueError('levels: between 1 and 32 of them')
+        if not all(0.0 < v < 1.0 for v in lv):
+            raise ValueError('levels must lie strictly inside (0, 1)')
+        if not all(a < b for a, b in zip(lv, lv[1:])):
+            raise ValueError('levels must be strictly increasing')
+        return (C.c_double * len(lv))(*lv), len(lv)
+
+    def _quantile_outputs(self, N, Q, y, return_dropped):
+        if y is not None:
+            y = torch.as_tensor(y, device=self.device).to(torch.float32).reshape(-1).contiguous()
+            if y.shape != (N,):
+                raise ValueError('y must be [N]')
+        quant = torch.empty((N, Q), dtype=torch.float32, device=self.device)
+        pit = torch.empty(N, dtype=torch.float32, device=self.device) if y is not None else None
+        dropped = torch.empty(N, dtype=torch.int32, device=self.device) if return_dropped else None
+        return y, quant, pit, dropped
+
+    @staticmethod
+    def _quantile_result(quant, pit, dropped):
+        res = (quant,) + ((pit,) if pit is not None else ()) + ((dropped,) if dropped is not None else ())
+        return res if len(res) > 1 else quant
+
+    def mixture_quantiles(self, raw, levels, y=None, return_dropped: bool = False):
+        """Exact quantiles of the equal-weight mixture of Normals that raw outputs [..., N, 2] (mu, log sigma; every leading
+        axis is a draw axis) describe on each row, at ``levels`` (strictly increasing, strictly inside (0, 1), at most 32),
+        by the library's bracketed solver (mile_mixture_quantiles): [N, Q] fp32, non-decreasing along Q.  With ``y`` [N] also
+        the probability integral transform F_n(y_n), [N] fp32; ``return_dropped`` appends the draws left out of each row for
+        a non-finite output, int32 [N].  The outputs may come from anywhere -- ``predict``, or a deep ensemble's members."""
+        lv, Q = self._quantile_levels(levels)
+        raw = _f32(raw, self.device, name='raw')
+        if raw.ndim < 2 or raw.shape[-1] != 2:
+            raise ValueError('raw must be [..., N, 2]')
+        N = int(raw.shape[-2])
+        r = raw.reshape(-1, N, 2).contiguous()
+        y, quant, pit, dropped = self._quantile_outputs(N, Q, y, return_dropped)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_mixture_quantiles(_ptr(r), r.shape[0], N, lv, Q, _ptr(y), _ptr(quant), _ptr(pit),
+                                                       _ptr(dropped), self._stream()), self.lib)
+        return self._quantile_result(quant, pit, dropped)
+
+    def predict_quantiles_workspace(self, S: int, N: int) -> int:
+        """Bytes of the workspace ``predict_quantiles`` keeps in the handle for S draws on N rows with the library's own
+        tile (mile_predict_quantiles_workspace)."""
+        return int(self.lib.mile_predict_quantiles_workspace(self._h, int(S), int(N)))
+
+    def predict_quantiles(self, theta, X, levels, y=None, *, max_draws_per_pass: int = 0, max_rows_per_tile: int = 0,
+                          return_dropped: bool = False):
+        """``mixture_quantiles`` of ``predict``'s outputs for draws theta [..., d] on X [N, F] without ever holding them
+        (mile_predict_quantiles): the rows go in tiles of at most ``max_rows_per_tile`` (0: the library's choice), the forward
+        inside a tile in passes of at most ``max_draws_per_pass`` draws (0: all).  Returns ``quant`` [N, Q] fp32, and ``pit``
+        [N] when ``y`` is given; ``return_dropped`` appends the draws left out of each row.  The result does not depend on the
+        two sizes, bit for bit.  Regression only."""
+        if self.spec.task != 'regr':
+            raise ValueError('predict_quantiles: a regression model is needed')
+        lv, Q = self._quantile_levels(levels)
+        theta = _f32(theta, self.device, name='theta')
+        th = theta.reshape(-1, self.d).contiguous()
+        X = _f32(X, self.device, name='X')
+        if isinstance(self.spec, IMAGE_SPECS) and X.ndim == 4:
+            X = X.reshape(X.shape[0], -1).contiguous()
+        if X.ndim != 2 or X.shape[1] != self.spec.in_features:
+            raise ValueError('X must be [N, F]')
+        N = int(X.shape[0])
+        y, quant, pit, dropped = self._quantile_outputs(N, Q, y, return_dropped)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_predict_quantiles(self._h, _ptr(th), th.shape[0], _ptr(X), N, lv, Q, _ptr(y), _ptr(quant),
+                                                       _ptr(pit), _ptr(dropped), int(max_draws_per_pass), int(max_rows_per_tile),
+                                                       self._stream()), self.lib)
+        return self._quantile_result(quant, pit, dropped)
+
+    def debug_quantile_sweeps(self):
+        """(rows, total sweeps, most sweeps of a row) of the solver in the last ``predict_quantiles`` (test and tool hook)."""
+        rows, total, most = C.c_int64(), C.c_int64(), C.c_int32()
+        _lib.check(self.lib.mile_debug_quantile_sweeps(self._h, C.byref(rows), C.byref(total), C.byref(most)), self.lib)
+        return int(rows.value), int(total.value), int(most.value)
+
     def lppd_stream_workspace(self, C: int, N: int) -> int:
         """Bytes of the (max, scaled sum) state and partial sums ``lppd_stream`` keeps for C chains on N rows, beyond the
         pass's block of log-likelihoods (mile_lppd_stream_workspace)."""

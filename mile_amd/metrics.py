@@ -406,3 +406,68 @@ def rmse_from_moments(y: torch.Tensor, moments: torch.Tensor) -> torch.Tensor:
     predicted means, without the draws)."""
     m = moments[:, 0]
     return torch.sqrt(((y.to(m.device, m.dtype).reshape(-1) - m) ** 2).mean())
+
+
+# ---- exact predictive quantiles and PIT of the ensemble: the torch restatement of mile_mixture_quantiles
+# (Engine.mixture_quantiles / predict_quantiles), over raw outputs that fit in memory.  The predictive of row n is the
+# equal-weight mixture of the kept draws' Normals, F_n(t) = mean_s Phi((t - mu_sn) / sigma_sn).
+
+def interval_levels(coverages) -> torch.Tensor:
+    """The sorted union of ``get_quantiles(c)`` over the nominal coverages, float64 [Q]."""
+    lv = torch.cat([get_quantiles(float(c)) for c in coverages])
+    return torch.unique(lv, sorted=True)
+
+
+def _mixture_components(outputs: torch.Tensor):
+    """outputs [..., N, 2] -> mu, sigma [S, N] float64 and the mask of kept draws (both outputs finite)."""
+    o = outputs.reshape(-1, outputs.shape[-2], 2)
+    ok = torch.isfinite(o).all(dim=-1)
+    o = torch.where(ok[..., None], o, torch.zeros_like(o)).to(torch.float64)
+    return o[..., 0], torch.exp(o[..., 1]).clamp(min=1e-6, max=1e6), ok
+
+
+def _mixture_cdf(mu, sig, ok, t):
+    """mean over the kept draws of Phi((t - mu) / sigma): t [N, Q] -> [N, Q] (0 / 0 = NaN where nothing is kept)."""
+    c = torch.special.ndtr((t[None] - mu[..., None]) / sig[..., None]) * ok[..., None]
+    return c.sum(dim=0) / ok.sum(dim=0)[:, None]
+
+
+def mixture_quantiles(outputs: torch.Tensor, levels, return_dropped: bool = False, steps: int = 200):
+    """outputs [..., N, 2] raw (mu, log sigma) of all draws (every leading axis is a draw axis), levels [Q] strictly inside
+    (0, 1) -> [N, Q] float64: the roots of F_n(t) = p by ``steps`` bisections of the exact bracket, min_s and max_s of
+    mu_s + Phi^-1(p) sigma_s.  A draw with a non-finite output on a row is left out of that row; ``return_dropped`` also
+    returns how many, int32 [N].  A row with nothing kept holds NaN."""
+    mu, sig, ok = _mixture_components(outputs)
+    p = torch.as_tensor(levels, dtype=torch.float64, device=mu.device).reshape(-1)
+    if p.numel() < 1 or not bool(((p > 0) & (p < 1)).all()):
+        raise ValueError('levels must lie strictly inside (0, 1)')
+    b = mu[..., None] + torch.special.ndtri(p) * sig[..., None]          # [S, N, Q]
+    inf = torch.full_like(b, float('inf'))
+    lo = torch.where(ok[..., None], b, inf).amin(dim=0)
+    hi = torch.where(ok[..., None], b, -inf).amax(dim=0)
+    for _ in range(steps):
+        mid = lo + 0.5 * (hi - lo)
+        below = _mixture_cdf(mu, sig, ok, mid) < p[None]
+        lo, hi = torch.where(below, mid, lo), torch.where(below, hi, mid)
+    out = lo + 0.5 * (hi - lo)
+    out = torch.where(ok.any(dim=0)[:, None], out, torch.full_like(out, float('nan')))
+    if return_dropped:
+        return out, (ok.shape[0] - ok.sum(dim=0)).to(torch.int32)
+    return out
+
+
+def mixture_pit(outputs: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """outputs [..., N, 2], y [N] -> the probability integral transform F_n(y_n), float64 [N], with mixture_quantiles'
+    leave-out rule."""
+    mu, sig, ok = _mixture_components(outputs)
+    t = torch.as_tensor(y, device=mu.device).to(torch.float64).reshape(-1, 1)
+    return _mixture_cdf(mu, sig, ok, t)[:, 0]
+
+
+def coverage_from_pit(pit: torch.Tensor, coverages) -> torch.Tensor:
+    """Observed coverage of the central intervals from the PIT: mean(|pit - 1/2| <= c / 2) over the rows with a finite PIT,
+    float64 [len(coverages)].  y_n lies in the central interval of coverage c exactly when the condition holds."""
+    v = pit.to(torch.float64).reshape(-1)
+    v = v[torch.isfinite(v)]
+    c = torch.as_tensor([float(c) for c in coverages], dtype=torch.float64, device=v.device)
+    return ((v[None] - 0.5).abs() <= c[:, None] / 2).to(torch.float64).mean(dim=1)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Posterior-predictive moments of a finished experiment on NEW inputs (the consumer of mile_predict_moments):
 
-    python predict.py -e results/mile_amd/<experiment> -i <table or .npz> [-o predictions.npz] [--draws-per-pass K]
+    python predict.py -e results/mile_amd/<experiment> -i <table or .npz> [-o predictions.npz] [--draws-per-pass K] [--intervals C [C ...]]
 
 Reloads config.yaml and the samples the way evaluate.py does, applies the training normalisation the loader recorded
 (normalization.npz, written by train.py) to the rows of the table, reduces all C x S draws on the device and writes, per row:
@@ -9,6 +9,8 @@ Reloads config.yaml and the samples the way evaluate.py does, applies the traini
     regression       mean, epistemic_var, aleatoric_var     (target units, see below)
     classification   probs [N, K], entropy, mutual_information (nats)
     both             dropped: draws left out of the row because an output was not finite
+    --intervals C..  regression: quantile_levels [Q] (the bounds of the central intervals of coverage C.. and the median) and
+                     quantiles [N, Q] of the ensemble's predictive mixture, solved exactly on the device (target units)
 
 The table holds one row per input and the model's features as columns (no target column): .npy, .csv (comma), .data / .txt
 (whitespace), or an .npz with an array ``x`` (images [N, C, H, W], token ids [N, T]).  Where the target was z-scored
@@ -68,6 +70,10 @@ def build_parser():
     ap.add_argument('--input', '-i', required=True, help='table of inputs: .npy, .csv, .data, .txt, or .npz with an array x')
     ap.add_argument('--output', '-o', default=None, help='default: <experiment directory>/predictions.npz')
     ap.add_argument('--draws-per-pass', type=int, default=0, help='draws forwarded at a time (0: the library chooses)')
+    ap.add_argument('--intervals', type=float, nargs='+', default=None, metavar='C',
+                    help='regression: also the exact quantiles of the predictive mixture at the bounds of the central intervals of '
+                         'these coverages and at the median (mile_predict_quantiles): quantile_levels [Q] and quantiles [N, Q], in '
+                         'target units where the target was z-scored')
     ap.add_argument('--normalized', action='store_true',
                     help='the rows already are in the training normalisation; the outputs stay in it')
     ap.add_argument('--drop-nonfinite', action='store_true', help='leave out chains with non-finite samples, as evaluate.py does')
@@ -84,6 +90,8 @@ def main():
     from mile_amd.trainer import BDETrainer
     cfg = Config.from_file(exp / 'config.yaml').replace(logging=False)
     tr = BDETrainer.__new__(BDETrainer)            # data + model spec only: no new experiment directory
+    if args.intervals and cfg.data.task != 'regr':
+        raise SystemExit('--intervals: predictive intervals are for regression experiments; this one is classification')
     tr.build_model(cfg)
     spec = tr.prob_model.spec
     samples = load_samples_from_dir(exp / cfg.training.sampler._dir_name, spec)       # [C, S, d]
@@ -105,6 +113,15 @@ def main():
                                        return_dropped=True)
     _, arrays = moment_metrics(mom, dropped, np.zeros(len(x), dtype=np.float32), cfg.data.task)
     arrays = denormalize(arrays, norm)
+    if args.intervals:
+        from mile_amd.metrics import interval_levels
+        levels = torch.unique(torch.cat([interval_levels(args.intervals), torch.tensor([0.5], dtype=torch.float64)]), sorted=True)
+        quant = eng.predict_quantiles(torch.from_numpy(samples), torch.from_numpy(x), levels, max_draws_per_pass=args.draws_per_pass)
+        q = quant.double().cpu().numpy()
+        if 'y_std' in norm:
+            q = q * float(norm['y_std'].reshape(-1)[0]) + float(norm['y_mean'].reshape(-1)[0])
+        arrays['quantile_levels'] = levels.numpy()
+        arrays['quantiles'] = q.astype(np.float32)
     out = Path(args.output) if args.output else exp / 'predictions.npz'
     np.savez(out, **arrays)
     print(f'{out}: {len(x)} rows, {samples.shape[0] * samples.shape[1]} draws, {int(arrays["dropped"].sum())} dropped; '
