@@ -382,6 +382,10 @@ int32_t mile_predict(mile_sampler *s, const float *theta, int32_t S, const float
  * (Welford + Chan for the variance), so the result does not depend on max_draws_per_pass beyond fp64 rounding.
  * MILE_ERR_INVALID: a null handle / theta / X / out, S < 1 or > 2^31 - 1, N < 1 or > 2^30 - 1, max_draws_per_pass < 0;
  * MILE_ERR_STATE: frozen tables not set; MILE_ERR_NOMEM: the workspace.  Nothing is launched on any of them.
+ * The workspace is ONE buffer of the handle that mile_predict_moments, mile_predict_quantiles and mile_lppd_stream share: it is
+ * as large as the largest of their calls so far asked for, each call lays its own blocks out in it, and -- like the staged
+ * evaluation rows, which every evaluation call of a handle has always shared -- it holds one call at a time: evaluation calls
+ * on one handle go on one stream, or are ordered by the caller.
  * (Added under ABI 10: two new symbols, no struct or existing entry changed.) */
 int32_t mile_predict_moments(mile_sampler *s, const float *theta, int64_t S, const void *X, int64_t N, float *out,
                              int32_t *dropped, int64_t max_draws_per_pass, void *stream);
@@ -421,7 +425,9 @@ int32_t mile_predict_quantiles(mile_sampler *s, const float *theta, int64_t S, c
                                int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream);
 int64_t mile_predict_quantiles_workspace(const mile_sampler *s, int64_t S, int64_t N);   /* bytes; -1 out of range */
 /* Test and tool hook: over the rows of the handle's last mile_predict_quantiles that asked for quantiles, the row count, the
- * sum of the solver's sweeps and the largest sweep count of a row (synchronises the device). */
+ * sum of the solver's sweeps and the largest sweep count of a row (synchronises the device).  The sweep counts lie in the
+ * shared evaluation workspace: once a later mile_predict_moments, mile_lppd_stream or mile_predict_quantiles has reserved
+ * it they are gone, and this reports 0 rows (never stale counts) until a mile_predict_quantiles has finished again. */
 int32_t mile_debug_quantile_sweeps(mile_sampler *s, int64_t *rows, int64_t *total, int32_t *most);
 
 /* Streamed LPPD and its running curves (the reference's lppd and running_lppd, src/inference/metrics.py:297-312, 408-446, and

@@ -42,6 +42,19 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
       return fail(MILE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));           \
   } while (0)
 
+// Grow the device buffer p of `cap` elements to `need` of `unit` bytes each (contents are not kept).  On failure p is null, cap
+// is 0 and the sticky HIP error is cleared.
+template <class P, class N>
+static hipError_t grow(P *&p, N &cap, size_t need, size_t unit) {
+  if (need <= (size_t)cap) return hipSuccess;
+  if (p) (void)hipFree(p);
+  p = nullptr; cap = 0;
+  const hipError_t e = hipMalloc(&p, need * unit);
+  if (e != hipSuccess) { p = nullptr; (void)hipGetLastError(); return e; }
+  cap = (N)need;
+  return hipSuccess;
+}
+
 static const double MCLACHLAN_B1 = 0.1931833275037836;
 
 struct PartSegs { int n; int begin[4], len[4]; };   // sampled segments of the full row (mile_partition_segments)
@@ -66,11 +79,11 @@ struct mile_sampler {
   float *nzbuf = nullptr;               // [2][nz_E][d] O-step noise a mid-step update launch prefills for the record launch
   int nz_E = 0;                         // particle rows nzbuf holds (allocated by the first mile_step that prefills)
   int64_t nz_launches = 0;              // mid-step launches that prefilled noise (mile_debug_prefill_count)
-  float *ev_X = nullptr, *ev_Xp = nullptr; void *ev_y = nullptr; int ev_cap = 0;   // evaluation (test) set staging
-  void *mom_ws = nullptr; size_t mom_ws_bytes = 0;   // mile_predict_moments: one pass of raw outputs, then the accumulators
-  void *lppd_ws = nullptr; size_t lppd_ws_bytes = 0; // mile_lppd_stream: one pass of log-likelihoods, then the state and partial sums
-  void *qnt_ws = nullptr; size_t qnt_ws_bytes = 0;   // mile_predict_quantiles: a row tile's raw outputs, its packed copy, brackets, sweeps
-  const int32_t *qnt_sweeps = nullptr; int64_t qnt_rows = 0;   // sweeps per row of the last mile_predict_quantiles, in qnt_ws
+  void *ev_rows = nullptr; size_t ev_rows_bytes = 0;   // evaluation (test) set staging: X, its padded copy and y (stage_rows)
+  // the streamed evaluation calls' one workspace (reserve_eval_ws): a pass of forward outputs, then the call's own state --
+  // moments: the accumulators; LPPD: the (m, s) state and partial sums; quantiles: the packed copy, brackets and sweeps
+  void *eval_ws = nullptr; size_t eval_ws_bytes = 0;
+  const int32_t *qnt_sweeps = nullptr; int64_t qnt_rows = 0;   // sweeps per row of the last mile_predict_quantiles, in eval_ws
   float *alt_x = nullptr, *alt_u = nullptr, *alt_g = nullptr, *alt_logp = nullptr;   // ping-pong state of mile_tune
   int grad_kernel = MILE_GRAD_AUTO;
   LeNetGeom lg{};                       // MILE_MODEL_LENET geometry and parameter offsets
@@ -613,12 +626,8 @@ static void free_nuts(mile_sampler *s) {
 
 int32_t mile_destroy(mile_sampler *s) {
   if (!s) return MILE_OK;
-  if (s->ev_X) (void)hipFree(s->ev_X);
-  if (s->ev_Xp) (void)hipFree(s->ev_Xp);
-  if (s->ev_y) (void)hipFree(s->ev_y);
-  if (s->mom_ws) (void)hipFree(s->mom_ws);
-  if (s->qnt_ws) (void)hipFree(s->qnt_ws);
-  if (s->lppd_ws) (void)hipFree(s->lppd_ws);
+  if (s->ev_rows) (void)hipFree(s->ev_rows);
+  if (s->eval_ws) (void)hipFree(s->eval_ws);
   free_data(s);
   free_ws(s);
   if (s->gemm_ws) (void)hipFree(s->gemm_ws);
@@ -1073,20 +1082,12 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
   const size_t n_part1 = direct && grad ? (size_t)E * nwg_max * (25 * g.C * 6 + 6) : 0;
   const size_t n_part2 = direct && grad ? (size_t)E * nwg_max * (2400 + 16) : 0;
   const size_t need = R * ((size_t)E * per + shared) + n_part1 + n_part2 + 128;   // + the arrays' alignment padding
-  if (need > s->gemm_ws_floats) {
-    if (s->gemm_ws) (void)hipFree(s->gemm_ws);
-    s->gemm_ws = nullptr; s->gemm_ws_floats = 0;
-    HIP_TRY(hipMalloc(&s->gemm_ws, need * 4));
-    s->gemm_ws_floats = need;
-  }
+  HIP_TRY(grow(s->gemm_ws, s->gemm_ws_floats, need, 4));
   s->gemm_E = 0;
   const size_t n_ones = R * HW;
   if ((size_t)s->gemm_ones_n < n_ones) {
-    if (s->gemm_ones) (void)hipFree(s->gemm_ones);
-    s->gemm_ones = nullptr; s->gemm_ones_n = 0;
-    HIP_TRY(hipMalloc(&s->gemm_ones, n_ones * 4));
+    HIP_TRY(grow(s->gemm_ones, s->gemm_ones_n, n_ones, 4));
     k_fill<<<(unsigned)((n_ones + 255) / 256), 256, 0, st>>>(s->gemm_ones, 1.0f, (int)n_ones);
-    s->gemm_ones_n = (int)n_ones;
   }
   const size_t ER = (size_t)E * R;
   float *q = s->gemm_ws;
@@ -1164,8 +1165,8 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
       if (fwd(g.k_f3, 84, g.K, f2, Rc * 84, Rc, out)) return fail(MILE_ERR_HIP, "rocblas sgemm (fc3) failed");
       bias_act(out, g.b_f3, g.K, Rc, 0);
       if (!grad) {   // per-row log-likelihoods, or (y == nullptr: mile_predict) the raw outputs [.., N, K]
-        if (y) k_gemm_rowll<<<dim3((unsigned)((Rc + 255) / 256), E), 256, 0, st>>>(out, y, r0, (int)Rc, g.K, task, out_ll, N, s0);
-        else k_gemm_rowll<true><<<dim3(blocks(Rc * g.K), E), 256, 0, st>>>(out, y, r0, (int)Rc, g.K, task, out_ll, N, s0);
+        if (y) k_rowll<<<dim3((unsigned)((Rc + 255) / 256), E), 256, 0, st>>>(out, Rc * g.K, g.K, y, r0, (int)Rc, g.K, task, out_ll, N, s0);
+        else k_rowll<true><<<dim3(blocks(Rc * g.K), E), 256, 0, st>>>(out, Rc * g.K, g.K, y, r0, (int)Rc, g.K, task, out_ll, N, s0);
         continue;
       }
       k_gemm_head<<<E, 256, 0, st>>>(out, y, r0, (int)Rc, g.K, task, llacc, chunk == 0);
@@ -1248,21 +1249,13 @@ static int launch_grad_gemm(mile_sampler *s, const GradParams &gp, int E, hipStr
     R = std::min<size_t>(R, (size_t)N);
     if (const char *rv = getenv("MILE_GEMM_ROWS")) R = std::max<size_t>(1, std::min<size_t>((size_t)atoll(rv), (size_t)N));   // test hook
     const size_t need = (size_t)E * R * per_row;
-    if (need > s->gemm_ws_floats) {
-      if (s->gemm_ws) (void)hipFree(s->gemm_ws);
-      s->gemm_ws = nullptr; s->gemm_ws_floats = 0;
-      HIP_TRY(hipMalloc(&s->gemm_ws, need * 4));
-      s->gemm_ws_floats = need;
-    }
+    HIP_TRY(grow(s->gemm_ws, s->gemm_ws_floats, need, 4));
     s->gemm_R = (int)R; s->gemm_E = E;
   }
   const int R = s->gemm_R;
   if (s->gemm_ones_n < R) {   // ones[R]: bias gradients are dZ^T 1 (a skinny GEMM, memory bound like the sum it replaces)
-    if (s->gemm_ones) (void)hipFree(s->gemm_ones);
-    s->gemm_ones = nullptr; s->gemm_ones_n = 0;
-    HIP_TRY(hipMalloc(&s->gemm_ones, (size_t)R * 4));
+    HIP_TRY(grow(s->gemm_ones, s->gemm_ones_n, (size_t)R, 4));
     k_fill<<<(R + 255) / 256, 256, 0, st>>>(s->gemm_ones, 1.0f, R);
-    s->gemm_ones_n = R;
   }
   float *H[MILE_MAX_LAYERS], *tmp[2];
   {
@@ -1388,12 +1381,7 @@ static int lenet_dense_prep(mile_sampler *s, const float *theta, int E, hipStrea
   int fin[3], fout[3], ld[3], woff[3], boff[3]; size_t pl[3], elems;
   lenet_dense_dims(s->lg, fin, fout, ld, woff, boff, pl, elems);
   const size_t bytes = (size_t)E * elems * 2;
-  if (bytes > s->wide_wt_bytes) {
-    if (s->wide_wt) (void)hipFree(s->wide_wt);
-    s->wide_wt = nullptr; s->wide_wt_bytes = 0;
-    HIP_TRY(hipMalloc(&s->wide_wt, bytes));
-    s->wide_wt_bytes = bytes;
-  }
+  HIP_TRY(grow(s->wide_wt, s->wide_wt_bytes, bytes, 1));
   for (int l = 0; l < 3; ++l) {
     const long long plane = (long long)fin[l] * ld[l];
     k_wide_prep_weights<3><<<dim3((unsigned)std::min<long long>((plane + 255) / 256, 1024), E), 256, 0, st>>>(
@@ -1423,8 +1411,8 @@ static int lenet_dense_chunk(mile_sampler *s, const float *theta, int E, int Rc,
     HIP_TRY(launch_mm3_fwd<3>(p, E, st));
   }
   if (!slab) {   // evaluation: per-row log-likelihood, or (y == nullptr: mile_predict) the raw outputs [.., N, K]
-    if (y) k_wide_rowll<<<dim3((unsigned)((Rc + 255) / 256), E), 256, 0, st>>>(b.out, (long long)Rc * ld[2], ld[2], y, r0, Rc, g.K, task, out_ll, Ntot, s0);
-    else k_wide_rowll<true><<<dim3((unsigned)std::min<long long>(((long long)Rc * g.K + 255) / 256, 65535), E), 256, 0, st>>>(b.out, (long long)Rc * ld[2], ld[2], y, r0, Rc, g.K, task, out_ll, Ntot, s0);
+    if (y) k_rowll<<<dim3((unsigned)((Rc + 255) / 256), E), 256, 0, st>>>(b.out, (long long)Rc * ld[2], ld[2], y, r0, Rc, g.K, task, out_ll, Ntot, s0);
+    else k_rowll<true><<<dim3((unsigned)std::min<long long>(((long long)Rc * g.K + 255) / 256, 65535), E), 256, 0, st>>>(b.out, (long long)Rc * ld[2], ld[2], y, r0, Rc, g.K, task, out_ll, Ntot, s0);
     HIP_TRY(hipGetLastError());
     return MILE_OK;
   }
@@ -1487,22 +1475,12 @@ static int launch_grad_wide(mile_sampler *s, const GradParams &gp, int E, hipStr
     if (R < Nall) R = std::max<size_t>(128, R / 128 * 128);
     if (const char *rv = getenv("MILE_GEMM_ROWS")) R = std::max<size_t>(1, std::min<size_t>((size_t)atoll(rv), Nall));   // test hook
     const size_t need = (size_t)E * R * per_row;
-    if (need > s->wide_ws_floats) {
-      if (s->wide_ws) (void)hipFree(s->wide_ws);
-      s->wide_ws = nullptr; s->wide_ws_floats = 0;
-      HIP_TRY(hipMalloc(&s->wide_ws, need * 4));
-      s->wide_ws_floats = need;
-    }
+    HIP_TRY(grow(s->wide_ws, s->wide_ws_floats, need, 4));
     HIP_TRY(hipMemsetAsync(s->wide_ws, 0, s->wide_ws_floats * 4, st));   // padding columns are read as operands: zero, once per layout
     s->wide_R = (int)R; s->wide_E = E;
   }
   const size_t wt_bytes = (size_t)E * wt_elems * 2;
-  if (wt_bytes > s->wide_wt_bytes) {
-    if (s->wide_wt) (void)hipFree(s->wide_wt);
-    s->wide_wt = nullptr; s->wide_wt_bytes = 0;
-    HIP_TRY(hipMalloc(&s->wide_wt, wt_bytes));
-    s->wide_wt_bytes = wt_bytes;
-  }
+  HIP_TRY(grow(s->wide_wt, s->wide_wt_bytes, wt_bytes, 1));
   const int R = s->wide_R;
   float *H[MILE_MAX_LAYERS], *tmp[2];
   {
@@ -1537,12 +1515,7 @@ static int launch_grad_wide(mile_sampler *s, const GradParams &gp, int E, hipStr
   constexpr int HB_ROWS = 512;                      // rows per workgroup of k_wide_headblock
   if (headblock) {
     const size_t need = (size_t)E * ((R + HB_ROWS - 1) / HB_ROWS) * ((size_t)ds.widths[L - 2] * ds.widths[L - 1] + ds.widths[L - 1] + 1);
-    if (need > s->wide_hb_floats) {
-      if (s->wide_hb) (void)hipFree(s->wide_hb);
-      s->wide_hb = nullptr; s->wide_hb_floats = 0;
-      HIP_TRY(hipMalloc(&s->wide_hb, need * 4));
-      s->wide_hb_floats = need;
-    }
+    HIP_TRY(grow(s->wide_hb, s->wide_hb_floats, need, 4));
   }
   for (int r0 = 0, chunk = 0; r0 < N; r0 += R, ++chunk) {
     const int Rc = std::min(R, N - r0);
@@ -1912,25 +1885,17 @@ static int mclmc_begin(mile_sampler *s, mile_state *state, const Args *a, const 
   return MILE_OK;
 }
 
-// gridDim.y holds at most 65 535 samples: the raw-output (mile_predict) launches walk S in chunks of that many
+// gridDim.y holds at most 65 535 samples: eval_forward walks S in chunks of that many, so every `loglik` below sees S <= this
 #define MILE_GRID_Y_MAX 65535
 
 template <int NH, int FQ>
 static hipError_t launch_fwd_w64(const PredParams &pp, int S, hipStream_t st) {
   using LY = W64Layout<NH, FQ>;
-  if (!pp.y) {   // mile_predict: (mu, log sigma) per row
-    hipError_t e = mile_set_max_lds<k_fwd_w64<NH, FQ, true>>(LY::BYTES);
-    for (int s0 = 0; s0 < S && e == hipSuccess; s0 += MILE_GRID_Y_MAX) {
-      PredParams q = pp;
-      q.theta += (size_t)s0 * pp.spec.d; q.out += (size_t)s0 * pp.N * 2;
-      k_fwd_w64<NH, FQ, true><<<dim3(pp.SB, std::min(MILE_GRID_Y_MAX, S - s0)), 256, LY::BYTES, st>>>(q);
-      e = hipGetLastError();
-    }
-    return e;
-  }
-  hipError_t e = mile_set_max_lds<k_fwd_w64<NH, FQ>>(LY::BYTES);
+  const bool raw = !pp.y;   // mile_predict: (mu, log sigma) per row
+  const hipError_t e = raw ? mile_set_max_lds<k_fwd_w64<NH, FQ, true>>(LY::BYTES) : mile_set_max_lds<k_fwd_w64<NH, FQ>>(LY::BYTES);
   if (e != hipSuccess) return e;
-  k_fwd_w64<NH, FQ><<<dim3(pp.SB, S), 256, LY::BYTES, st>>>(pp);
+  if (raw) k_fwd_w64<NH, FQ, true><<<dim3(pp.SB, S), 256, LY::BYTES, st>>>(pp);
+  else k_fwd_w64<NH, FQ><<<dim3(pp.SB, S), 256, LY::BYTES, st>>>(pp);
   return hipGetLastError();
 }
 
@@ -1950,12 +1915,7 @@ static int launch_fwd_gemm(mile_sampler *s, const float *theta, int S, const flo
   if (const char *rv = getenv("MILE_GEMM_ROWS")) Rr = std::max<size_t>(1, std::min<size_t>((size_t)atoll(rv), (size_t)N));
   const int R = (int)Rr;
   const size_t need = 2 * (size_t)Sc * R * ds.max_width;
-  if (need > s->gemm_ws_floats) {
-    if (s->gemm_ws) (void)hipFree(s->gemm_ws);
-    s->gemm_ws = nullptr; s->gemm_ws_floats = 0; s->gemm_E = 0;
-    HIP_TRY(hipMalloc(&s->gemm_ws, need * 4));
-    s->gemm_ws_floats = need;
-  }
+  HIP_TRY(grow(s->gemm_ws, s->gemm_ws_floats, need, 4));
   s->gemm_E = 0;   // the gradient path re-derives its layout on its next call
   float *buf[2] = {s->gemm_ws, s->gemm_ws + (size_t)Sc * R * ds.max_width};
   const float one = 1.0f, zero = 0.0f;
@@ -1978,8 +1938,8 @@ static int launch_fwd_gemm(mile_sampler *s, const float *theta, int S, const flo
         pp ^= 1;
       }
       const int O = ds.widths[L - 1];
-      if (y) k_gemm_rowll<<<dim3((Rc + 255) / 256, Sn), 256, 0, st>>>(buf[pp ^ 1], y, r0, Rc, O, ds.task, out, N, s0);
-      else k_gemm_rowll<true><<<dim3((unsigned)std::min<long long>(((long long)Rc * O + 255) / 256, 65535), Sn), 256, 0, st>>>(buf[pp ^ 1], y, r0, Rc, O, ds.task, out, N, s0);
+      if (y) k_rowll<<<dim3((Rc + 255) / 256, Sn), 256, 0, st>>>(buf[pp ^ 1], (long long)Rc * O, O, y, r0, Rc, O, ds.task, out, N, s0);
+      else k_rowll<true><<<dim3((unsigned)std::min<long long>(((long long)Rc * O + 255) / 256, 65535), Sn), 256, 0, st>>>(buf[pp ^ 1], (long long)Rc * O, O, y, r0, Rc, O, ds.task, out, N, s0);
     }
   }
   HIP_TRY(hipGetLastError());
@@ -2009,20 +1969,10 @@ static int launch_fwd_wide(mile_sampler *s, const float *theta, int S, const flo
   if (const char *rv = getenv("MILE_GEMM_ROWS")) Rr = std::max<size_t>(1, std::min<size_t>((size_t)atoll(rv), (size_t)N));
   const int R = (int)Rr;
   const size_t need = 2 * (size_t)Sc * R * maxwp;
-  if (need > s->wide_ws_floats) {
-    if (s->wide_ws) (void)hipFree(s->wide_ws);
-    s->wide_ws = nullptr; s->wide_ws_floats = 0;
-    HIP_TRY(hipMalloc(&s->wide_ws, need * 4));
-    s->wide_ws_floats = need;
-  }
+  HIP_TRY(grow(s->wide_ws, s->wide_ws_floats, need, 4));
   s->wide_E = 0;   // the gradient path re-derives (and re-zeroes) its layout on its next call
   const size_t wt_bytes = (size_t)Sc * wt_elems * 2;
-  if (wt_bytes > s->wide_wt_bytes) {
-    if (s->wide_wt) (void)hipFree(s->wide_wt);
-    s->wide_wt = nullptr; s->wide_wt_bytes = 0;
-    HIP_TRY(hipMalloc(&s->wide_wt, wt_bytes));
-    s->wide_wt_bytes = wt_bytes;
-  }
+  HIP_TRY(grow(s->wide_wt, s->wide_wt_bytes, wt_bytes, 1));
   float *buf[2] = {s->wide_ws, s->wide_ws + (size_t)Sc * R * maxwp};
   bf16 *Wt = (bf16 *)s->wide_wt;
   for (int s0 = 0; s0 < S; s0 += Sc) {
@@ -2052,8 +2002,8 @@ static int launch_fwd_wide(mile_sampler *s, const float *theta, int S, const flo
         pp ^= 1;
       }
       const int O = ds.widths[L - 1];
-      if (y) k_wide_rowll<<<dim3((Rc + 255) / 256, Sn), 256, 0, st>>>(buf[pp ^ 1], (long long)R * wp[L - 1], wp[L - 1], y, r0, Rc, O, ds.task, out, N, s0);
-      else k_wide_rowll<true><<<dim3((unsigned)std::min<long long>(((long long)Rc * O + 255) / 256, 65535), Sn), 256, 0, st>>>(buf[pp ^ 1], (long long)R * wp[L - 1], wp[L - 1], y, r0, Rc, O, ds.task, out, N, s0);
+      if (y) k_rowll<<<dim3((Rc + 255) / 256, Sn), 256, 0, st>>>(buf[pp ^ 1], (long long)R * wp[L - 1], wp[L - 1], y, r0, Rc, O, ds.task, out, N, s0);
+      else k_rowll<true><<<dim3((unsigned)std::min<long long>(((long long)Rc * O + 255) / 256, 65535), Sn), 256, 0, st>>>(buf[pp ^ 1], (long long)R * wp[L - 1], wp[L - 1], y, r0, Rc, O, ds.task, out, N, s0);
     }
   }
   HIP_TRY(hipGetLastError());
@@ -2062,22 +2012,15 @@ static int launch_fwd_wide(mile_sampler *s, const float *theta, int S, const flo
 
 // ---- evaluation of each grad kernel's model: the `loglik` of its row in kGrad.  pp holds the staged evaluation set; without
 // labels (pp.y == nullptr, mile_predict) every row of the table writes the raw outputs, O floats per (sample, row) -----------------
-static size_t out_width(const mile_sampler *s, const PredParams &pp) { return pp.y ? 1 : (size_t)s->spec.widths[s->spec.n_layers - 1]; }
 template <hipError_t (*LAUNCH)(mile_sampler *, const float *, int, const float *, const void *, int, int, int, float *, hipStream_t)>
 static int loglik_attn_t(mile_sampler *s, PredParams pp, int S, hipStream_t st) {   // the three attention models: their launcher
   const int SB = std::max(1, std::min({64, (s->n_cu + S - 1) / S, std::max(1, pp.N / 16)}));
-  for (int s0 = 0; s0 < S; s0 += 65535) {
-    const int Sc = std::min(65535, S - s0);
-    HIP_TRY(LAUNCH(s, pp.theta + (size_t)s0 * s->ds.d, Sc, pp.X, pp.y, pp.N, SB, 0, pp.out + (size_t)s0 * pp.N * out_width(s, pp), st));
-  }
+  HIP_TRY(LAUNCH(s, pp.theta, S, pp.X, pp.y, pp.N, SB, 0, pp.out, st));
   return MILE_OK;
 }
 static int loglik_lenetti(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
   const int SB = std::max(1, std::min({64, (2 * s->n_cu + S - 1) / S, std::max(1, pp.N / 32)}));
-  for (int s0 = 0; s0 < S; s0 += 65535) {
-    const int Sc = std::min(65535, S - s0);
-    HIP_TRY(launch_lenetti(s, pp.theta + (size_t)s0 * s->ds.d, Sc, pp.X, pp.y, pp.N, SB, 0, pp.out + (size_t)s0 * pp.N * out_width(s, pp), st));
-  }
+  HIP_TRY(launch_lenetti(s, pp.theta, S, pp.X, pp.y, pp.N, SB, 0, pp.out, st));
   return MILE_OK;
 }
 template <bool MFMA>
@@ -2112,16 +2055,8 @@ static int loglik_w64(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
 static int loglik_generic(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
   pp.SB = std::max(1, std::min(std::max(1, (4 * s->n_cu) / S), std::max(1, pp.N / 64)));
   const size_t lds = ((size_t)pp.R * s->ds.act_stride + 16) * 4;
-  if (!pp.y) {   // mile_predict
-    for (int s0 = 0; s0 < S; s0 += MILE_GRID_Y_MAX) {
-      PredParams q = pp;
-      q.theta += (size_t)s0 * s->ds.d; q.out += (size_t)s0 * pp.N * out_width(s, pp);
-      k_fwd_generic<true><<<dim3(pp.SB, std::min(MILE_GRID_Y_MAX, S - s0)), 256, lds, st>>>(q);
-      HIP_TRY(hipGetLastError());
-    }
-    return MILE_OK;
-  }
-  k_fwd_generic<<<dim3(pp.SB, S), 256, lds, st>>>(pp);
+  if (pp.y) k_fwd_generic<<<dim3(pp.SB, S), 256, lds, st>>>(pp);
+  else k_fwd_generic<true><<<dim3(pp.SB, S), 256, lds, st>>>(pp);   // mile_predict
   HIP_TRY(hipGetLastError());
   return MILE_OK;
 }
@@ -2206,55 +2141,77 @@ static constexpr bool rows_in_id_order() {
 static_assert(rows_in_id_order(), "kGrad: one row per MILE_GRAD_* id, in id order");
 static const GradKernel &grad_kernel(int kernel) { return kGrad[kernel - 1]; }
 
-// stage the evaluation rows (and labels) in the handle and describe them in pp; theta and out are the caller's to fill in
+// stage the evaluation rows (and labels) in the handle and describe them in pp; theta and out are eval_forward's to fill in
 static int stage_rows(mile_sampler *s, const float *X, const void *y, int64_t N, PredParams &pp, hipStream_t st) {
   HIP_TRY(hipSetDevice(s->device));
   const int F = s->spec.in_features, Npad = ((int)N + 31) / 32 * 32, Fp = (F + 7) / 8 * 8;
-  if (Npad > s->ev_cap) {   // evaluation is off the stepping path: (re)allocate its staging here
-    if (s->ev_X) (void)hipFree(s->ev_X);
-    if (s->ev_Xp) (void)hipFree(s->ev_Xp);
-    if (s->ev_y) (void)hipFree(s->ev_y);
-    s->ev_X = s->ev_Xp = nullptr; s->ev_y = nullptr; s->ev_cap = 0;
-    HIP_TRY(hipMalloc(&s->ev_X, (size_t)Npad * F * 4));
-    HIP_TRY(hipMalloc(&s->ev_Xp, (size_t)Npad * Fp * 4));
-    HIP_TRY(hipMalloc(&s->ev_y, (size_t)Npad * 4));
-    s->ev_cap = Npad;
-  }
-  HIP_TRY(hipMemcpyAsync(s->ev_X, X, (size_t)N * F * 4, hipMemcpyDeviceToDevice, st));
+  auto r256 = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t x_bytes = r256((size_t)Npad * F * 4), xp_bytes = r256((size_t)Npad * Fp * 4);
+  HIP_TRY(grow(s->ev_rows, s->ev_rows_bytes, x_bytes + xp_bytes + (size_t)Npad * 4, 1));   // evaluation is off the stepping path
+  float *ev_X = (float *)s->ev_rows, *ev_Xp = (float *)((char *)s->ev_rows + x_bytes);
+  void *ev_y = (char *)s->ev_rows + x_bytes + xp_bytes;
+  HIP_TRY(hipMemcpyAsync(ev_X, X, (size_t)N * F * 4, hipMemcpyDeviceToDevice, st));
   if (y) {
-    HIP_TRY(hipMemsetAsync(s->ev_y, 0, (size_t)Npad * 4, st));
-    HIP_TRY(hipMemcpyAsync(s->ev_y, y, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetAsync(ev_y, 0, (size_t)Npad * 4, st));
+    HIP_TRY(hipMemcpyAsync(ev_y, y, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
   }
   const long long tot = (long long)Npad * Fp;
-  k_pad_x<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(s->ev_X, s->ev_Xp, (int)N, Npad, F, Fp);
-  pp.spec = s->ds; pp.theta = nullptr; pp.X = s->ev_X; pp.Xp = s->ev_Xp; pp.y = y ? s->ev_y : nullptr; pp.out = nullptr;
+  k_pad_x<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(ev_X, ev_Xp, (int)N, Npad, F, Fp);
+  pp.spec = s->ds; pp.theta = nullptr; pp.X = ev_X; pp.Xp = ev_Xp; pp.y = y ? ev_y : nullptr; pp.out = nullptr;
   pp.N = (int)N; pp.Npad = Npad; pp.Fp = Fp; pp.R = generic_R(s->ds);
   return MILE_OK;
 }
 
-// mile_pointwise_loglik and (y == nullptr) mile_predict: stage the evaluation rows, then the resolved kernel's `loglik`
+// The one forward of evaluation: the resolved kernel's `loglik` of S samples (rows of theta) on the staged rows pp, into
+// out [S, N] -- or, staged without labels, the raw outputs [S, N, O] -- in launches of at most MILE_GRID_Y_MAX samples.
+static int eval_forward(mile_sampler *s, PredParams pp, const float *theta, int64_t S, float *out, hipStream_t st) {
+  const GradKernel &gk = grad_kernel(resolved_kernel(s));
+  const size_t per_sample = (size_t)pp.N * (pp.y ? 1 : (size_t)s->spec.widths[s->spec.n_layers - 1]);   // floats of out
+  for (int64_t s0 = 0; s0 < S; s0 += MILE_GRID_Y_MAX) {
+    pp.theta = theta + (size_t)s0 * s->ds.d; pp.out = out + (size_t)s0 * per_sample;
+    const int rc = gk.loglik(s, pp, (int)std::min<int64_t>(MILE_GRID_Y_MAX, S - s0), st);
+    if (rc != MILE_OK) return rc;
+  }
+  return MILE_OK;
+}
+
+// mile_pointwise_loglik and (y == nullptr) mile_predict: stage the evaluation rows, then the forward
 static int evaluate_rows(mile_sampler *s, const float *theta, int32_t S, const float *X, const void *y, int64_t N, float *out, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   PredParams pp;
   const int rc = stage_rows(s, X, y, N, pp, st);
-  if (rc != MILE_OK) return rc;
-  pp.theta = theta; pp.out = out;
-  return grad_kernel(resolved_kernel(s)).loglik(s, pp, S, st);
+  return rc != MILE_OK ? rc : eval_forward(s, pp, theta, S, out, st);
+}
+
+// What every evaluation entry point `fn` on a handle checks before anything else, in this order: null arguments, S, N, the call's
+// own checks (`more`: a message or null; it may read *s), then the frozen tables.  MILE_OK, or the failure with its message set.
+template <class More>
+static int eval_args(const char *fn, const mile_sampler *s, bool null_arg, int64_t S, int64_t N, More more) {
+  auto bad = [&](const char *m) { return fail(MILE_ERR_INVALID, std::string(fn) + ": " + m); };
+  if (!s || null_arg) return bad("null argument");
+  if (S < 1 || S > 0x7fffffff) return bad("S out of range (1 .. 2^31 - 1)");
+  if (N < 1 || N > 0x3fffffff) return bad("N out of range (1 .. 2^30 - 1)");
+  if (const char *m = more()) return bad(m);
+  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
+  return MILE_OK;
+}
+static const char *no_more_checks() { return nullptr; }
+
+// The streamed calls' workspace.  The sweeps of the last mile_predict_quantiles lie in it: whoever reserves it forgets them.
+static hipError_t reserve_eval_ws(mile_sampler *s, size_t bytes) {
+  s->qnt_rows = 0;
+  return grow(s->eval_ws, s->eval_ws_bytes, bytes, 1);
 }
 
 extern "C" int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, int32_t S, const float *X, const void *y,
                                          int64_t N, float *out, void *stream) {
-  if (!s || !theta || !X || !y || !out || S < 1) return fail(MILE_ERR_INVALID, "mile_pointwise_loglik: bad argument");
-  if (N < 1 || N > 0x3fffffff) return fail(MILE_ERR_INVALID, "mile_pointwise_loglik: N out of range");
-  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
-  return evaluate_rows(s, theta, S, X, y, N, out, stream);
+  const int rc = eval_args("mile_pointwise_loglik", s, !theta || !X || !y || !out, S, N, no_more_checks);
+  return rc != MILE_OK ? rc : evaluate_rows(s, theta, S, X, y, N, out, stream);
 }
 
 extern "C" int32_t mile_predict(mile_sampler *s, const float *theta, int32_t S, const float *X, int64_t N, float *out, void *stream) {
-  if (!s || !theta || !X || !out || S < 1) return fail(MILE_ERR_INVALID, "mile_predict: bad argument");
-  if (N < 1 || N > 0x3fffffff) return fail(MILE_ERR_INVALID, "mile_predict: N out of range");
-  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
-  return evaluate_rows(s, theta, S, X, nullptr, N, out, stream);
+  const int rc = eval_args("mile_predict", s, !theta || !X || !out, S, N, no_more_checks);
+  return rc != MILE_OK ? rc : evaluate_rows(s, theta, S, X, nullptr, N, out, stream);
 }
 
 // mile_predict_moments: mile_predict's forward in passes of `chunk` draws into the library's workspace, each folded into the
@@ -2269,11 +2226,9 @@ extern "C" int32_t mile_predict_moments_width(const mile_sampler *s) {
 
 extern "C" int32_t mile_predict_moments(mile_sampler *s, const float *theta, int64_t S, const void *X, int64_t N, float *out,
                                         int32_t *dropped, int64_t max_draws_per_pass, void *stream) {
-  if (!s || !theta || !X || !out || S < 1) return fail(MILE_ERR_INVALID, "mile_predict_moments: bad argument");
-  if (S > 0x7fffffff) return fail(MILE_ERR_INVALID, "mile_predict_moments: S out of range");
-  if (N < 1 || N > 0x3fffffff) return fail(MILE_ERR_INVALID, "mile_predict_moments: N out of range");
-  if (max_draws_per_pass < 0) return fail(MILE_ERR_INVALID, "mile_predict_moments: max_draws_per_pass < 0");
-  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
+  const int rc0 = eval_args("mile_predict_moments", s, !theta || !X || !out, S, N,
+                            [&] { return max_draws_per_pass < 0 ? "max_draws_per_pass < 0" : nullptr; });
+  if (rc0 != MILE_OK) return rc0;
   const int task = s->spec.task, O = s->spec.widths[s->spec.n_layers - 1];
   if (task == MILE_TASK_REGRESSION && O != 2) return fail(MILE_ERR_INVALID, "mile_predict_moments: regression needs (mu, log sigma) outputs");
   hipStream_t st = (hipStream_t)stream;
@@ -2284,24 +2239,20 @@ extern "C" int32_t mile_predict_moments(mile_sampler *s, const float *theta, int
   // enough one-wave workgroups for about eight waves per CU, at most one slice per draw of a pass
   const int slices = (int)std::min<int64_t>(std::min<int64_t>(MOM_MAX_SLICES, chunk), std::max<int64_t>(1, ((int64_t)s->n_cu * 8 * MOM_NT + N - 1) / N));
   const size_t raw_bytes = ((size_t)chunk * per_draw + 255) / 256 * 256, acc_bytes = mom_acc_bytes(task, O, (int)N, slices);
-  if (raw_bytes + acc_bytes > s->mom_ws_bytes) {   // evaluation is off the stepping path: (re)allocate here
-    if (s->mom_ws) (void)hipFree(s->mom_ws);
-    s->mom_ws = nullptr; s->mom_ws_bytes = 0;
-    if (hipMalloc(&s->mom_ws, raw_bytes + acc_bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(MILE_ERR_NOMEM, "mile_predict_moments: workspace allocation failed (lower max_draws_per_pass)");
-    }
-    s->mom_ws_bytes = raw_bytes + acc_bytes;
-  }
+  if (reserve_eval_ws(s, raw_bytes + acc_bytes) != hipSuccess)
+    return fail(MILE_ERR_NOMEM, "mile_predict_moments: workspace allocation failed (lower max_draws_per_pass)");
   MomParams p{};
-  p.raw = (const float *)s->mom_ws; p.N = (int)N; p.O = O; p.slices = slices; p.S = S;
-  p.acc = (double *)((char *)s->mom_ws + raw_bytes);
+  p.raw = (const float *)s->eval_ws; p.N = (int)N; p.O = O; p.slices = slices; p.S = S;
+  p.acc = (double *)((char *)s->eval_ws + raw_bytes);
   p.cnt = (int32_t *)(p.acc + (size_t)slices * mom_planes(task, O) * N);
   p.out = out; p.dropped = dropped;
   HIP_TRY(hipMemsetAsync(p.acc, 0, acc_bytes, st));
+  PredParams pp;
+  const int rc1 = stage_rows(s, (const float *)X, nullptr, N, pp, st);
+  if (rc1 != MILE_OK) return rc1;
   for (int64_t s0 = 0; s0 < S; s0 += chunk) {
     p.Sc = (int)std::min<int64_t>(chunk, S - s0);
-    const int rc = evaluate_rows(s, theta + s0 * s->ds.d, p.Sc, (const float *)X, nullptr, N, (float *)s->mom_ws, stream);
+    const int rc = eval_forward(s, pp, theta + s0 * s->ds.d, p.Sc, (float *)s->eval_ws, st);
     if (rc != MILE_OK) return rc;
     HIP_TRY(mile_launch_moments_accum(task, p, st));
   }
@@ -2330,19 +2281,16 @@ static double host_ndtri(double p) {
   return p < 0.5 ? z : -z;
 }
 
-static const char *qnt_bad_args(const char *fn, int64_t S, int64_t N, const double *levels, int32_t Q, const float *y,
-                                const float *quant, const float *pit, std::string &msg) {
-  auto bad = [&](const char *m) { msg = std::string(fn) + ": " + m; return msg.c_str(); };
-  if (S < 1 || S > 0x7fffffff) return bad("S out of range (1 .. 2^31 - 1)");
-  if (N < 1 || N > 0x3fffffff) return bad("N out of range (1 .. 2^30 - 1)");
-  if (!levels) return bad("null levels");
-  if (Q < 1 || Q > QNT_MAX_Q) return bad("Q out of range (1 .. 32)");
+// what is wrong with the levels or the outputs asked for, or null
+static const char *qnt_bad_args(const double *levels, int32_t Q, const float *y, const float *quant, const float *pit) {
+  if (!levels) return "null levels";
+  if (Q < 1 || Q > QNT_MAX_Q) return "Q out of range (1 .. 32)";
   for (int i = 0; i < Q; ++i) {
-    if (!(levels[i] > 0.0 && levels[i] < 1.0)) return bad("levels must lie strictly inside (0, 1)");
-    if (i > 0 && !(levels[i] > levels[i - 1])) return bad("levels must be strictly increasing");
+    if (!(levels[i] > 0.0 && levels[i] < 1.0)) return "levels must lie strictly inside (0, 1)";
+    if (i > 0 && !(levels[i] > levels[i - 1])) return "levels must be strictly increasing";
   }
-  if (!quant && !pit) return bad("neither quantiles nor PIT asked for");
-  if (pit && !y) return bad("PIT needs y");
+  if (!quant && !pit) return "neither quantiles nor PIT asked for";
+  if (pit && !y) return "PIT needs y";
   return nullptr;
 }
 
@@ -2398,8 +2346,9 @@ static int qnt_run(const float *raw_all, char *tail, int64_t S, int64_t N, int64
 extern "C" int32_t mile_mixture_quantiles(const float *raw, int64_t S, int64_t N, const double *levels, int32_t Q, const float *y,
                                           float *quant, float *pit, int32_t *dropped, void *stream) {
   if (!raw) return fail(MILE_ERR_INVALID, "mile_mixture_quantiles: null raw");
-  std::string msg;
-  if (qnt_bad_args("mile_mixture_quantiles", S, N, levels, Q, y, quant, pit, msg)) return fail(MILE_ERR_INVALID, msg);
+  if (S < 1 || S > 0x7fffffff) return fail(MILE_ERR_INVALID, "mile_mixture_quantiles: S out of range (1 .. 2^31 - 1)");
+  if (N < 1 || N > 0x3fffffff) return fail(MILE_ERR_INVALID, "mile_mixture_quantiles: N out of range (1 .. 2^30 - 1)");
+  if (const char *m = qnt_bad_args(levels, Q, y, quant, pit)) return fail(MILE_ERR_INVALID, std::string("mile_mixture_quantiles: ") + m);
   hipStream_t st = (hipStream_t)stream;
   int dev = 0, n_cu = 256;
   HIP_TRY(hipGetDevice(&dev));
@@ -2428,43 +2377,34 @@ extern "C" int64_t mile_predict_quantiles_workspace(const mile_sampler *s, int64
 extern "C" int32_t mile_predict_quantiles(mile_sampler *s, const float *theta, int64_t S, const void *X, int64_t N,
                                           const double *levels, int32_t Q, const float *y, float *quant, float *pit, int32_t *dropped,
                                           int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
-  if (!s || !theta || !X) return fail(MILE_ERR_INVALID, "mile_predict_quantiles: null handle, theta or X");
-  std::string msg;
-  if (qnt_bad_args("mile_predict_quantiles", S, N, levels, Q, y, quant, pit, msg)) return fail(MILE_ERR_INVALID, msg);
-  if (max_draws_per_pass < 0) return fail(MILE_ERR_INVALID, "mile_predict_quantiles: max_draws_per_pass < 0");
-  if (max_rows_per_tile < 0) return fail(MILE_ERR_INVALID, "mile_predict_quantiles: max_rows_per_tile < 0");
-  if (s->spec.task != MILE_TASK_REGRESSION || s->spec.widths[s->spec.n_layers - 1] != 2)
-    return fail(MILE_ERR_INVALID, "mile_predict_quantiles: needs a regression model with (mu, log sigma) outputs");
-  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
+  const int rc0 = eval_args("mile_predict_quantiles", s, !theta || !X, S, N, [&]() -> const char * {
+    if (const char *m = qnt_bad_args(levels, Q, y, quant, pit)) return m;
+    if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
+    if (max_rows_per_tile < 0) return "max_rows_per_tile < 0";
+    if (s->spec.task != MILE_TASK_REGRESSION || s->spec.widths[s->spec.n_layers - 1] != 2)
+      return "needs a regression model with (mu, log sigma) outputs";
+    return nullptr;
+  });
+  if (rc0 != MILE_OK) return rc0;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->device));
   const int64_t Nt = qnt_tile_rows(S, N, max_rows_per_tile);
   const int64_t chunk = std::min<int64_t>(S, max_draws_per_pass ? max_draws_per_pass : S);
   const size_t raw_bytes = qnt_r256((size_t)S * Nt * 8), tail_bytes = qnt_tail_bytes(S, Nt, qnt_slices((int)S, (int)Nt, s->n_cu));
   const size_t need = raw_bytes + tail_bytes + qnt_r256((size_t)N * 4);
-  if (need > s->qnt_ws_bytes) {   // evaluation is off the stepping path: (re)allocate here
-    if (s->qnt_ws) (void)hipFree(s->qnt_ws);
-    s->qnt_ws = nullptr; s->qnt_ws_bytes = 0; s->qnt_rows = 0;
-    if (hipMalloc(&s->qnt_ws, need) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(MILE_ERR_NOMEM, "mile_predict_quantiles: workspace allocation failed (lower max_rows_per_tile)");
-    }
-    s->qnt_ws_bytes = need;
-  }
-  float *raw = (float *)s->qnt_ws;
-  char *tail = (char *)s->qnt_ws + raw_bytes;
+  if (reserve_eval_ws(s, need) != hipSuccess)
+    return fail(MILE_ERR_NOMEM, "mile_predict_quantiles: workspace allocation failed (lower max_rows_per_tile)");
+  float *raw = (float *)s->eval_ws;
+  char *tail = (char *)s->eval_ws + raw_bytes;
   int32_t *sweeps = (int32_t *)(tail + tail_bytes);
-  s->qnt_rows = 0; s->qnt_sweeps = sweeps;
-  const GradKernel &gk = grad_kernel(resolved_kernel(s));
+  s->qnt_sweeps = sweeps;
   const size_t row_floats = (size_t)s->spec.in_features;
   auto fill = [&](int64_t r0, int nt, const float **tile) -> int {   // every (draw, row) forward once: passes at their draw offset
     PredParams pp;
     const int rc0 = stage_rows(s, (const float *)X + (size_t)r0 * row_floats, nullptr, nt, pp, st);
     if (rc0 != MILE_OK) return rc0;
     for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-      pp.theta = theta + (size_t)s0 * s->ds.d;
-      pp.out = raw + (size_t)s0 * nt * 2;
-      const int rc = gk.loglik(s, pp, (int)std::min<int64_t>(chunk, S - s0), st);
+      const int rc = eval_forward(s, pp, theta + (size_t)s0 * s->ds.d, std::min<int64_t>(chunk, S - s0), raw + (size_t)s0 * nt * 2, st);
       if (rc != MILE_OK) return rc;
     }
     *tile = raw;
@@ -2502,16 +2442,17 @@ extern "C" int64_t mile_lppd_stream_workspace(const mile_sampler *s, int32_t C, 
 extern "C" int32_t mile_lppd_stream(mile_sampler *s, const float *theta, int32_t C, int32_t S, const void *X, const void *y, int64_t N,
                                     const int32_t *curve_points, int32_t K, double *run_chain, double *run_ens, double *chain_lppd,
                                     double *row_lppd, double *lppd, int64_t *dropped, int64_t max_draws_per_pass, void *stream) {
-  if (!s || !theta || !X || !y) return fail(MILE_ERR_INVALID, "mile_lppd_stream: null handle, theta, X or y");
-  if (!lppd_shape_ok(C, N)) return fail(MILE_ERR_INVALID, "mile_lppd_stream: C (1 .. 65535) or N (1 .. 2^30 - 1) out of range");
-  if (S < 1) return fail(MILE_ERR_INVALID, "mile_lppd_stream: S out of range");
-  if (K < 0 || K > S) return fail(MILE_ERR_INVALID, "mile_lppd_stream: K out of range (0 .. S)");
-  if (K == 0 && (run_chain || run_ens)) return fail(MILE_ERR_INVALID, "mile_lppd_stream: K = 0 with a curve output");
-  if (K > 0 && !curve_points) return fail(MILE_ERR_INVALID, "mile_lppd_stream: null curve_points");
-  if (K > 0 && !run_chain && !run_ens) return fail(MILE_ERR_INVALID, "mile_lppd_stream: curve points without a curve output");
-  if (K == 0 && !chain_lppd && !row_lppd && !lppd && !dropped) return fail(MILE_ERR_INVALID, "mile_lppd_stream: no output asked for");
-  if (max_draws_per_pass < 0) return fail(MILE_ERR_INVALID, "mile_lppd_stream: max_draws_per_pass < 0");
-  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
+  const int rc1 = eval_args("mile_lppd_stream", s, !theta || !X || !y, S, N, [&]() -> const char * {
+    if (!lppd_shape_ok(C, N)) return "C out of range (1 .. 65535)";
+    if (K < 0 || K > S) return "K out of range (0 .. S)";
+    if (K == 0 && (run_chain || run_ens)) return "K = 0 with a curve output";
+    if (K > 0 && !curve_points) return "null curve_points";
+    if (K > 0 && !run_chain && !run_ens) return "curve points without a curve output";
+    if (K == 0 && !chain_lppd && !row_lppd && !lppd && !dropped) return "no output asked for";
+    if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
+    return nullptr;
+  });
+  if (rc1 != MILE_OK) return rc1;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->device));
   std::vector<int32_t> pts((size_t)K);
@@ -2527,19 +2468,12 @@ extern "C" int32_t mile_lppd_stream(mile_sampler *s, const float *theta, int32_t
   int64_t J = max_draws_per_pass ? max_draws_per_pass : std::max<int64_t>(1, EVAL_PASS_TARGET / per_draw);
   J = std::min<int64_t>(std::min<int64_t>(J, S), LPPD_J_MAX);
   const size_t raw_bytes = ((size_t)J * per_draw + 255) / 256 * 256, st_bytes = lppd_state_bytes(C, N);
-  if (raw_bytes + st_bytes > s->lppd_ws_bytes) {   // evaluation is off the stepping path: (re)allocate here
-    if (s->lppd_ws) (void)hipFree(s->lppd_ws);
-    s->lppd_ws = nullptr; s->lppd_ws_bytes = 0;
-    if (hipMalloc(&s->lppd_ws, raw_bytes + st_bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(MILE_ERR_NOMEM, "mile_lppd_stream: workspace allocation failed (lower max_draws_per_pass)");
-    }
-    s->lppd_ws_bytes = raw_bytes + st_bytes;
-  }
+  if (reserve_eval_ws(s, raw_bytes + st_bytes) != hipSuccess)
+    return fail(MILE_ERR_NOMEM, "mile_lppd_stream: workspace allocation failed (lower max_draws_per_pass)");
   const size_t cn = (size_t)C * (size_t)N;
   LppdParams p{};
-  p.ll = (const float *)s->lppd_ws; p.C = C; p.N = (int)N; p.S = S; p.waves = lppd_waves(N);
-  p.state = (double2 *)((char *)s->lppd_ws + raw_bytes);
+  p.ll = (const float *)s->eval_ws; p.C = C; p.N = (int)N; p.S = S; p.waves = lppd_waves(N);
+  p.state = (double2 *)((char *)s->eval_ws + raw_bytes);
   p.cnt = (int32_t *)(p.state + cn);
   p.part_ens = (double *)((char *)p.cnt + (cn * 4 + 7) / 8 * 8);
   p.part_chain = p.part_ens + p.waves;
@@ -2550,15 +2484,12 @@ extern "C" int32_t mile_lppd_stream(mile_sampler *s, const float *theta, int32_t
   PredParams pp;
   const int rc0 = stage_rows(s, (const float *)X, y, N, pp, st);
   if (rc0 != MILE_OK) return rc0;
-  const GradKernel &gk = grad_kernel(resolved_kernel(s));
   p.fresh = 1;    // the first launch of k_lppd_accum starts every (chain, row) at (m, s) = (-inf, 0), cnt = 0
   int next = 0;   // next curve point
   for (int64_t j0 = 0; j0 < S; j0 += J) {
     p.J = (int)std::min<int64_t>(J, S - j0);
     for (int c = 0; c < C; ++c) {   // chain c's draws j0 .. j0 + J - 1 are rows c * S + j0 .. of theta
-      pp.theta = theta + ((size_t)c * S + (size_t)j0) * s->ds.d;
-      pp.out = (float *)s->lppd_ws + (size_t)c * p.J * N;
-      const int rc = gk.loglik(s, pp, p.J, st);
+      const int rc = eval_forward(s, pp, theta + ((size_t)c * S + (size_t)j0) * s->ds.d, p.J, (float *)s->eval_ws + (size_t)c * p.J * N, st);
       if (rc != MILE_OK) return rc;
     }
     int ja = 0;

@@ -758,40 +758,3 @@ __global__ __launch_bounds__(256) void k_wide_headblock_reduce(const float *part
     *o = accumulate ? *o + s : s;
   }
 }
-
-// ---- evaluation: per-row log-likelihood of the head outputs out [S][R][ld] -> out_ll[(s0 + s) * N + r0 + r] ------------
-// (no nansum zeroing: src/inference/metrics.py:247-294 uses the distributions' log_prob directly)
-// RAW (mile_predict): the head outputs without their padding columns, out_ll[((s0 + s) * N + r0 + r) * K + c], one thread per
-// float, y unread
-template <bool RAW = false>
-__global__ __launch_bounds__(256) void k_wide_rowll(const float *out, long long sOut, int ld, const void *y, long long r0, int R, int K, int task,
-                                                    float *out_ll, long long N, long long s0) {
-  const int s = blockIdx.y;
-  const float *o = out + (size_t)s * sOut;
-  if constexpr (RAW) {
-    float *dst = out_ll + ((size_t)(s0 + s) * N + r0) * K;
-    for (long long i = blockIdx.x * 256 + threadIdx.x; i < (long long)R * K; i += gridDim.x * 256) {
-      const long long rr = i / K;
-      dst[i] = o[rr * ld + (i - rr * K)];
-    }
-    return;
-  }
-  for (int rr = blockIdx.x * 256 + threadIdx.x; rr < R; rr += gridDim.x * 256) {
-    const float *z = o + (size_t)rr * ld;
-    float v;
-    if (task == MILE_TASK_REGRESSION) {
-      const float es = expf(z[1]);
-      const float sig = isnan(es) ? es : fminf(fmaxf(es, 1e-6f), 1e6f);
-      const float q = (((const float *)y)[r0 + rr] - z[0]) / sig;
-      v = -0.5f * q * q - logf(sig) - 0.91893853320467274f;
-    } else {
-      const int yi = ((const int32_t *)y)[r0 + rr];
-      float m = z[0];
-      for (int c = 1; c < K; ++c) m = fmaxf(m, z[c]);
-      float se = 0.0f;
-      for (int c = 0; c < K; ++c) se += expf(z[c] - m);
-      v = z[yi] - (m + logf(se));
-    }
-    out_ll[(size_t)(s0 + s) * N + r0 + rr] = v;
-  }
-}

@@ -18,11 +18,42 @@ struct PredParams {
   int32_t N, Npad, Fp, SB, R;
 };
 
-__device__ __forceinline__ float row_logpdf_regr(float mu, float sr, float yv) {
-  const float es = expf(sr);
-  const float sig = isnan(es) ? es : fminf(fmaxf(es, 1e-6f), 1e6f);
-  const float r = (yv - mu) / sig;
-  return -0.5f * r * r - logf(sig) - 0.91893853320467274f;
+// The likelihood head of every evaluation kernel that does not share it with a backward pass: log p(y[row] | z) for the K head
+// outputs z of one row -- Normal(mu, sigma clipped to [1e-6, 1e6]) of z = (mu, log sigma), or log-softmax(z) at the label.
+__device__ __forceinline__ float row_loglik(const float *z, int K, int task, const void *y, long long row) {
+  if (task == MILE_TASK_REGRESSION) {
+    const float es = expf(z[1]);
+    const float sig = isnan(es) ? es : fminf(fmaxf(es, 1e-6f), 1e6f);
+    const float r = (((const float *)y)[row] - z[0]) / sig;
+    return -0.5f * r * r - logf(sig) - 0.91893853320467274f;
+  }
+  const int yi = ((const int32_t *)y)[row];
+  float m = z[0];
+  for (int c = 1; c < K; ++c) m = fmaxf(m, z[c]);
+  float se = 0.0f;
+  for (int c = 0; c < K; ++c) se += expf(z[c] - m);
+  return z[yi] - (m + logf(se));
+}
+
+// The layer-wise paths (rocBLAS, k_mm3, both LeNet forms) leave the head outputs in a buffer out [S][R][ld] (sample stride sOut):
+// per-row log-likelihood -> out_ll[(s0 + s) * N + r0 + r] (no nansum zeroing: src/inference/metrics.py:247-294 uses the
+// distributions' log_prob directly).  RAW (mile_predict): the head outputs without their padding columns,
+// out_ll[((s0 + s) * N + r0 + r) * K + c], one thread per float, y unread.
+template <bool RAW = false>
+__global__ __launch_bounds__(256) void k_rowll(const float *out, long long sOut, int ld, const void *y, long long r0, int R, int K, int task,
+                                               float *out_ll, long long N, long long s0) {
+  const int s = blockIdx.y;
+  const float *o = out + (size_t)s * sOut;
+  if constexpr (RAW) {
+    float *dst = out_ll + ((size_t)(s0 + s) * N + r0) * K;
+    for (long long i = blockIdx.x * 256 + threadIdx.x; i < (long long)R * K; i += gridDim.x * 256) {
+      const long long rr = i / K;
+      dst[i] = o[rr * ld + (i - rr * K)];
+    }
+    return;
+  }
+  for (int rr = blockIdx.x * 256 + threadIdx.x; rr < R; rr += gridDim.x * 256)
+    out_ll[(size_t)(s0 + s) * N + r0 + rr] = row_loglik(o + (size_t)rr * ld, K, task, y, r0 + rr);
 }
 
 // width-64 ReLU regression nets: the forward half of k_grad_w64 (same LDS images, same T layout)
@@ -120,8 +151,10 @@ __global__ __launch_bounds__(256, 1) void k_fwd_w64(const PredParams p) {
     if constexpr (RAW) {   // lane j of the low half holds row j's pair: 32 x 8 contiguous bytes per wave
       if (h == 0 && row0 + j < p.N) *(float2 *)(p.out + ((size_t)e * p.N + row0 + j) * 2) = make_float2(p0 + BO[0], p1 + BO[1]);
     } else {
-      if (h == 0 && row0 + j < p.N)
-        p.out[(size_t)e * p.N + row0 + j] = row_logpdf_regr(p0 + BO[0], p1 + BO[1], ((const float *)p.y)[row0 + j]);
+      if (h == 0 && row0 + j < p.N) {
+        const float z[2] = {p0 + BO[0], p1 + BO[1]};
+        p.out[(size_t)e * p.N + row0 + j] = row_loglik(z, 2, MILE_TASK_REGRESSION, p.y, row0 + j);
+      }
     }
   }
 }
@@ -168,21 +201,8 @@ __global__ __launch_bounds__(256) void k_fwd_generic(const PredParams p) {
       __syncthreads();
       continue;
     }
-    for (int r = tid; r < nr; r += nt) {
-      const float *out = act + r * as + sp.act_off[nl];
-      float v;
-      if (sp.task == MILE_TASK_REGRESSION) {
-        v = row_logpdf_regr(out[0], out[1], ((const float *)p.y)[t0 + r]);
-      } else {
-        const int yi = ((const int32_t *)p.y)[t0 + r];
-        float m = out[0];
-        for (int c = 1; c < C; ++c) m = fmaxf(m, out[c]);
-        float se = 0.0f;
-        for (int c = 0; c < C; ++c) se += expf(out[c] - m);
-        v = out[yi] - (m + logf(se));
-      }
-      p.out[(size_t)e * p.N + t0 + r] = v;
-    }
+    for (int r = tid; r < nr; r += nt)
+      p.out[(size_t)e * p.N + t0 + r] = row_loglik(act + r * as + sp.act_off[nl], C, sp.task, p.y, t0 + r);
     __syncthreads();
   }
 }

@@ -556,23 +556,33 @@ class Engine:
                 _lib.check(self.lib.mile_nuts_warmup(self._h, C.byref(sc), C.byref(a), C.byref(w), self._stream()), self.lib)
         return self._nuts_info(info), samples
 
+    def _eval_inputs(self, theta, X, y=None, *, name_x: str = 'X'):
+        """The inputs every evaluation method shares, checked and on the device: (leading shape of theta, theta [*, d] fp32,
+        X [N, F] fp32 with images flattened, y [N] fp32 / int32 by task or None)."""
+        theta = _f32(theta, self.device, name='theta')
+        th = theta.reshape(-1, self.d).contiguous()
+        X = _f32(X, self.device, name=name_x)
+        if isinstance(self.spec, IMAGE_SPECS) and X.ndim == 4:
+            X = X.reshape(X.shape[0], -1).contiguous()
+        ok = X.ndim == 2 and X.shape[1] == self.spec.in_features
+        if y is None:
+            if not ok:
+                raise ValueError(f'{name_x} must be [N, F]')
+        else:
+            y = torch.as_tensor(y, device=self.device)
+            y = (y.to(torch.float32) if self.spec.task == 'regr' else y.to(torch.int32)).contiguous()
+            if not ok or y.shape != (X.shape[0],):
+                raise ValueError(f'{name_x} must be [N, F] and y [N]')
+        _check_tokens(self.spec, X)
+        if y is not None and self.spec.task != 'regr' and y.numel():       # the kernels index the logits with the raw label
+            if int(y.min()) < 0 or int(y.max()) >= self.spec.hidden_structure[-1]:
+                raise ValueError('class labels out of range')
+        return theta.shape[:-1], th, X, y
+
     def pointwise_loglik(self, theta, X, y) -> torch.Tensor:
         """log p(y_n | x_n, theta_s) for every sample and test row: theta [..., d] -> [..., N]
         (pointwise_lppd's input, src/inference/metrics.py:247-294), computed by the HIP forward kernels."""
-        theta = _f32(theta, self.device, name='theta')
-        lead = theta.shape[:-1]
-        th = theta.reshape(-1, self.d).contiguous()
-        X = _f32(X, self.device, name='X')
-        y = torch.as_tensor(y, device=self.device)
-        y = (y.to(torch.float32) if self.spec.task == 'regr' else y.to(torch.int32)).contiguous()
-        if isinstance(self.spec, IMAGE_SPECS) and X.ndim == 4:
-            X = X.reshape(X.shape[0], -1).contiguous()
-        if X.ndim != 2 or X.shape[1] != self.spec.in_features or y.shape != (X.shape[0],):
-            raise ValueError('X must be [N, F] and y [N]')
-        _check_tokens(self.spec, X)
-        if self.spec.task != 'regr' and y.numel():       # the kernels index the logits with the raw label
-            if int(y.min()) < 0 or int(y.max()) >= self.spec.hidden_structure[-1]:
-                raise ValueError('class labels out of range')
+        lead, th, X, y = self._eval_inputs(theta, X, y)
         out = torch.empty((th.shape[0], X.shape[0]), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.mile_pointwise_loglik(self._h, _ptr(th), th.shape[0], _ptr(X), _ptr(y), X.shape[0],
@@ -583,15 +593,7 @@ class Engine:
         """Raw network outputs for every sample and test row: theta [..., d] -> [..., N, O], O the width of the last layer
         (``module.apply`` in predict_from_samples, src/inference/evaluation.py:16-43): (mu, log sigma) unclipped or the
         logits, NaN / inf untouched.  Computed by the HIP forward kernels of pointwise_loglik (mile_predict)."""
-        theta = _f32(theta, self.device, name='theta')
-        lead = theta.shape[:-1]
-        th = theta.reshape(-1, self.d).contiguous()
-        X = _f32(X, self.device, name='X')
-        if isinstance(self.spec, IMAGE_SPECS) and X.ndim == 4:
-            X = X.reshape(X.shape[0], -1).contiguous()
-        if X.ndim != 2 or X.shape[1] != self.spec.in_features:
-            raise ValueError('X must be [N, F]')
-        _check_tokens(self.spec, X)
+        lead, th, X, _ = self._eval_inputs(theta, X)
         O = self.spec.hidden_structure[-1]
         out = torch.empty((th.shape[0], X.shape[0], O), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
@@ -606,14 +608,7 @@ class Engine:
         outputs, without ever holding them.  ``max_draws_per_pass`` bounds the draws forwarded at a time (0: the library's
         choice).  A draw with a non-finite output on a row is left out of that row; ``return_dropped`` also returns how many
         were, int32 [N]."""
-        theta = _f32(theta, self.device, name='theta')
-        th = theta.reshape(-1, self.d).contiguous()
-        X = _f32(X, self.device, name='X')
-        if isinstance(self.spec, IMAGE_SPECS) and X.ndim == 4:
-            X = X.reshape(X.shape[0], -1).contiguous()
-        if X.ndim != 2 or X.shape[1] != self.spec.in_features:
-            raise ValueError('X must be [N, F]')
-        _check_tokens(self.spec, X)
+        _, th, X, _ = self._eval_inputs(theta, X)
         W = int(self.lib.mile_predict_moments_width(self._h))
         out = torch.empty((X.shape[0], W), dtype=torch.float32, device=self.device)
         dropped = torch.empty(X.shape[0], dtype=torch.int32, device=self.device) if return_dropped else None
@@ -681,13 +676,7 @@ class Engine:
         if self.spec.task != 'regr':
             raise ValueError('predict_quantiles: a regression model is needed')
         lv, Q = self._quantile_levels(levels)
-        theta = _f32(theta, self.device, name='theta')
-        th = theta.reshape(-1, self.d).contiguous()
-        X = _f32(X, self.device, name='X')
-        if isinstance(self.spec, IMAGE_SPECS) and X.ndim == 4:
-            X = X.reshape(X.shape[0], -1).contiguous()
-        if X.ndim != 2 or X.shape[1] != self.spec.in_features:
-            raise ValueError('X must be [N, F]')
+        _, th, X, _ = self._eval_inputs(theta, X)
         N = int(X.shape[0])
         y, quant, pit, dropped = self._quantile_outputs(N, Q, y, return_dropped)
         with torch.cuda.device(self.device):
@@ -718,21 +707,10 @@ class Engine:
         forwarded at a time (0: the library's choice); the outputs do not depend on it, bit for bit.  A host ``samples`` is
         uploaded whole: the library reads all chains' windows from one device array."""
         from mile_amd.metrics import curve_points as default_points
-        theta = _f32(samples, self.device, name='samples')
-        if theta.ndim != 3 or theta.shape[2] != self.d:
+        samples = _f32(samples, self.device, name='samples')
+        if samples.ndim != 3 or samples.shape[2] != self.d:
             raise ValueError(f'samples must be [C, S, {self.d}]')
-        C_, S_ = int(theta.shape[0]), int(theta.shape[1])
-        X = _f32(x, self.device, name='x')
-        y = torch.as_tensor(y, device=self.device)
-        y = (y.to(torch.float32) if self.spec.task == 'regr' else y.to(torch.int32)).contiguous()
-        if isinstance(self.spec, IMAGE_SPECS) and X.ndim == 4:
-            X = X.reshape(X.shape[0], -1).contiguous()
-        if X.ndim != 2 or X.shape[1] != self.spec.in_features or y.shape != (X.shape[0],):
-            raise ValueError('x must be [N, F] and y [N]')
-        _check_tokens(self.spec, X)
-        if self.spec.task != 'regr' and y.numel():       # the kernels index the logits with the raw label
-            if int(y.min()) < 0 or int(y.max()) >= self.spec.hidden_structure[-1]:
-                raise ValueError('class labels out of range')
+        (C_, S_), theta, X, y = self._eval_inputs(samples, x, y, name_x='x')
         pts = default_points(S_) if curve_points is None else curve_points
         pts = torch.as_tensor(pts, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
         K, N = int(pts.numel()), int(X.shape[0])

@@ -37,7 +37,7 @@ control chain; 1.5e-06 in a clipped chain) against 1e-4.  Aleatoric variance: 4.
 No head needed more than its project bound, so the 4 x float32 term decided nothing.
 
 With the `unclipped` test of row_loss_regr forced to true, all eleven test_regression_head_gradient_in_the_clip cases fail; with
-the clip constants of row_logpdf_regr swapped, test_pointwise_loglik_on_the_steered_chains[regr-narrow_relu-generic] and
+the clip constants of row_loglik swapped, test_pointwise_loglik_on_the_steered_chains[regr-narrow_relu-generic] and
 [regr-w64-mfma_w64] fail; with the `- m` of k_grad_generic's softmax taken out,
 test_softmax_head_gradient_when_saturated[cls-covertype_like-generic] fails; each time everything else in this file passes.
 """

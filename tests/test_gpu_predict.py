@@ -185,6 +185,35 @@ def test_more_samples_than_one_grid_holds_w64():
     _assert_close('S=70000 mfma_w64', out, O.mlp_forward(ospec, theta.astype(np.float64), X.astype(np.float64)))
 
 
+def _loglik_beyond_one_grid(kernel, hs, seed):
+    """pointwise_loglik for S = 70 000 > 65 535 (gridDim.y): the library's forward driver walks S in chunks for the
+    log-likelihood launches as for the raw outputs; the samples on either side of the seam are checked on their own."""
+    ospec = O.ModelSpec(5, hs)
+    S, N = 70000, 7
+    prob = O.synthetic_problem(ospec, 32, 1, seed=8)
+    rng = np.random.default_rng(seed)
+    theta = (0.1 * rng.standard_normal((S, ospec.n_params))).astype(np.float32)
+    X = rng.standard_normal((N, 5)).astype(np.float32)
+    y = rng.standard_normal(N).astype(np.float32)
+    eng = _fcn_engine(ospec, prob, kernel)
+    out = eng.pointwise_loglik(torch.from_numpy(theta), torch.from_numpy(X), torch.from_numpy(y))
+    torch.cuda.synchronize()
+    assert out.shape == (S, N)
+    ref = O.pointwise_loglik_raw(ospec, O.mlp_forward(ospec, theta.astype(np.float64), X.astype(np.float64)), y.astype(np.float64))[0]
+    assert np.isfinite(ref).all()
+    _assert_close(f'loglik S=70000 {kernel}', out, ref)
+    for row in (65534, 65535, 65536):
+        _assert_close(f'loglik S=70000 {kernel} sample {row}', out[row], ref[row])
+
+
+def test_more_samples_than_one_grid_holds_loglik():
+    _loglik_beyond_one_grid('mfma_narrow_f32', (16, 16, 2), 0)
+
+
+def test_more_samples_than_one_grid_holds_loglik_w64():
+    _loglik_beyond_one_grid('mfma_w64', (64, 2), 1)
+
+
 @pytest.mark.parametrize('kernel,hs', [('mfma_narrow_f32', (16, 16, 2)), ('mfma_w64_bf16x3', (64, 64, 2)), ('gemm_f32', (128, 96, 2))])
 def test_nan_passes_through(kernel, hs):
     ospec = O.ModelSpec(5, hs)

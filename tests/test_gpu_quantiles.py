@@ -234,6 +234,25 @@ def test_every_tiling_gives_the_same_bits(kernel, hs):
     assert from_pit == counted
 
 
+def test_streamed_calls_share_one_workspace():
+    """predict_quantiles, predict_moments and lppd_stream lay their blocks out in the same buffer of the handle: a quantile
+    call gives the same bits after the others have used it, and the sweeps of a quantile call are forgotten, not read
+    back stale, once another streamed call has reused the buffer."""
+    eng = _engine()
+    ospec, prob, X = _fcn_problem(5, (16, 16, 2), 'relu', 'regr', 70, 12)
+    th, Xt, levels = torch.from_numpy(prob['theta0']), torch.from_numpy(X), _levels()
+    y = torch.from_numpy(np.random.default_rng(13).standard_normal(70).astype(np.float32))
+    first = eng.predict_quantiles(th, Xt, levels, y=y, return_dropped=True)
+    assert eng.debug_quantile_sweeps()[0] == 70
+    moments = eng.predict_moments(th, Xt)
+    assert eng.debug_quantile_sweeps()[0] == 0
+    lppd = eng.lppd_stream(th.reshape(3, 4, -1), Xt, y)
+    again = eng.predict_quantiles(th, Xt, levels, y=y, return_dropped=True)
+    assert eng.debug_quantile_sweeps()[0] == 70
+    assert all(torch.equal(a, b) for a, b in zip(again, first))
+    assert torch.isfinite(moments).all() and torch.isfinite(lppd['lppd'])
+
+
 def test_refusals_leave_the_handle_usable():
     ospec, prob, X = _fcn_problem(5, (16, 16, 2), 'relu', 'regr', 70, 3)
     eng = _fcn_engine(ospec, prob, 'mfma_narrow_f32')
