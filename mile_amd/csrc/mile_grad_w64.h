@@ -429,8 +429,13 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
   // STASH: a wave of a pair must not start exchanging tiles through the buffer its partner still keeps activations in
   // SPLIT: a shared block's pair images PA / PB are the two waves' private images of the main loop
   if constexpr (LY::STASH || SPLIT) __syncthreads();
+  // <3, 2, fp32> is the one fp32 form that spills (120 VGPRs).  Behind a branch on the VGPR-derived wave index -- divergent as
+  // far as the compiler knows -- the three-block round below returned wrong gradients in that form (a leaf off by up to 85 %, logp
+  // right; tests/test_gpu_w64_schedule.py, every cell with rem == 3).  The wave index is uniform: said so, the round is an
+  // ordinary scalar branch.  The other forms keep the code they were measured with.
+  const int wave_t = (NH == 3 && FQ == 2 && !SPLIT) ? __builtin_amdgcn_readfirstlane(wave) : wave;
   if (rem == 3) {               // three leftovers: one more independent round
-    if (wave < 3) {
+    if (wave_t < 3) {
       const int row0 = (b0 + 4 * nfull + wave) * 32;
 #define W64_COOP 0
 #define W64_W 0
