@@ -3,7 +3,7 @@
 mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
 src/inference/metrics.py:247-312):
 
-    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals]
+    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo]
 
 Reloads config.yaml and the samples/<chain>/sample_<n>.npz files, rebuilds the data split with the same
 seed, evaluates all C x S samples on the split in one device pass and writes metrics.json next to them.
@@ -165,6 +165,18 @@ def interval_metrics(quant, pit, dropped, levels, coverages):
     return out, arrays
 
 
+def loo_metrics(rows):
+    """--loo: the metrics.json keys and the loo.npz arrays of the per-row PSIS-LOO / WAIC result ``rows`` (Engine.loo_stream, or
+    metrics.psis_loo of a pointwise tensor) on the train split.  Keys: ``loo_`` + every total of ``metrics.loo_summary``, the
+    rows evaluated and the draws dropped in all."""
+    from mile_amd.metrics import loo_summary
+    arrays = {k: rows[k].detach().cpu().numpy() for k in ('lppd', 'p_waic', 'elpd_loo', 'khat', 'dropped')}
+    out = {f'loo_{k}': v for k, v in loo_summary(arrays).items()}
+    out['loo_n_points'] = int(arrays['lppd'].shape[0])
+    out['loo_dropped'] = int(arrays['dropped'].sum())
+    return out, arrays
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description='LPPD / NLL of the samples of an experiment directory')
     ap.add_argument('--diagnostics', type=int, nargs='?', const=2, default=None, metavar='N_SPLITS',
@@ -185,6 +197,14 @@ def build_parser():
                          'solved on the device (mile_predict_quantiles): intervals_coverage_<c>, intervals_width_<c>, '
                          'intervals_cal_error and intervals_dropped in metrics.json -- no draws, so no seed and no Monte-Carlo noise -- '
                          'and levels, quantiles, pit, dropped in intervals.npz')
+    ap.add_argument('--loo', action='store_true',
+                    help='PSIS-LOO and WAIC of the ensemble, streamed on the device (mile_loo_stream).  Always on the TRAIN split, '
+                         'whatever --split says: leave-one-out estimates out-of-sample fit from the rows the sampler conditioned on, '
+                         'and means nothing on held-out rows.  loo_* keys in metrics.json (elpd_loo, p_loo, elpd_waic, p_waic with '
+                         'standard errors, lppd_sum, the counts of rows with khat > 0.7, without a tail fit and with p_waic > 0.4) and '
+                         'lppd, p_waic, elpd_loo, khat, dropped per row in loo.npz')
+    ap.add_argument('--loo-r-eff', type=float, default=1.0, metavar='R_EFF',
+                    help='relative efficiency of the draws behind the PSIS tail length (default 1: independent draws)')
     ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
     ap.add_argument('--split', default='test', choices=['train', 'valid', 'test'])
     ap.add_argument('--device', default='cuda:0')
@@ -317,6 +337,13 @@ def main():
         keys, arrays = interval_metrics(quant, pit, dropped, levels, args.coverages)
         out.update(keys)
         np.savez(exp / 'intervals.npz', **arrays)
+    if args.loo:
+        train_x = np.ascontiguousarray(tr.loader.train_x).reshape(len(tr.loader.train_x), -1)
+        rows = eng.loo_stream(torch.from_numpy(samples), torch.from_numpy(train_x), torch.from_numpy(np.ascontiguousarray(tr.loader.train_y)),
+                              r_eff=args.loo_r_eff)
+        keys, arrays = loo_metrics(rows)
+        out.update(keys)
+        np.savez(exp / 'loo.npz', **arrays)
     (exp / 'metrics.json').write_text(json.dumps(out, indent=1) + '\n')
     print(json.dumps({k: v for k, v in out.items() if not isinstance(v, (list, dict))}))        # the per-chain arrays stay in metrics.json
 

@@ -382,7 +382,8 @@ int32_t mile_predict(mile_sampler *s, const float *theta, int32_t S, const float
  * (Welford + Chan for the variance), so the result does not depend on max_draws_per_pass beyond fp64 rounding.
  * MILE_ERR_INVALID: a null handle / theta / X / out, S < 1 or > 2^31 - 1, N < 1 or > 2^30 - 1, max_draws_per_pass < 0;
  * MILE_ERR_STATE: frozen tables not set; MILE_ERR_NOMEM: the workspace.  Nothing is launched on any of them.
- * The workspace is ONE buffer of the handle that mile_predict_moments, mile_predict_quantiles and mile_lppd_stream share: it is
+ * The workspace is ONE buffer of the handle that mile_predict_moments, mile_predict_quantiles, mile_lppd_stream and
+ * mile_loo_stream share: it is
  * as large as the largest of their calls so far asked for, each call lays its own blocks out in it, and -- like the staged
  * evaluation rows, which every evaluation call of a handle has always shared -- it holds one call at a time: evaluation calls
  * on one handle go on one stream, or are ordered by the caller.
@@ -426,9 +427,51 @@ int32_t mile_predict_quantiles(mile_sampler *s, const float *theta, int64_t S, c
 int64_t mile_predict_quantiles_workspace(const mile_sampler *s, int64_t S, int64_t N);   /* bytes; -1 out of range */
 /* Test and tool hook: over the rows of the handle's last mile_predict_quantiles that asked for quantiles, the row count, the
  * sum of the solver's sweeps and the largest sweep count of a row (synchronises the device).  The sweep counts lie in the
- * shared evaluation workspace: once a later mile_predict_moments, mile_lppd_stream or mile_predict_quantiles has reserved
- * it they are gone, and this reports 0 rows (never stale counts) until a mile_predict_quantiles has finished again. */
+ * shared evaluation workspace: once a later mile_predict_moments, mile_lppd_stream, mile_loo_stream or mile_predict_quantiles
+ * has reserved it they are gone, and this reports 0 rows (never stale counts) until a mile_predict_quantiles has finished again. */
 int32_t mile_debug_quantile_sweeps(mile_sampler *s, int64_t *rows, int64_t *total, int32_t *most);
+
+/* PSIS-LOO and WAIC of the ensemble on the rows the sampler conditioned on: Pareto-smoothed importance-sampling leave-one-out
+ * cross-validation (Vehtari, Gelman & Gabry 2017; Vehtari et al. 2024; the generalised-Pareto fit of Zhang & Stephens 2009),
+ * per row, on the device.  The reference has no counterpart.  For row n let l_s = log p(y_n | x_n, theta_s) over all S draws
+ * pooled over chains (fp32 as mile_pointwise_loglik writes them; all arithmetic below is fp64).
+ *   A draw whose l_s is NaN or +-inf is left out of row n (per draw and per row, the rule of mile_predict_moments);
+ *   dropped[n] counts them, S_n are kept, and a row with S_n < 2 holds NaN in every other output.
+ *   lppd[n]   = logsumexp_s l_s - log S_n
+ *   p_waic[n] = sum_s (l_s - mean l)^2 / (S_n - 1)  (Welford per thread, Chan's merge in a fixed order); elpd_waic = lppd - p_waic
+ *   r_s = -l_s - max_s(-l_s); M = ceil(fmin(S_n / 5.0, 3.0 * sqrt(S_n / r_eff))); the tail is the M largest r_s (ties at the
+ *   boundary broken in any way: every output is a sum that cannot see the choice); cut = max((M+1)-th largest r, log DBL_MIN),
+ *   ec = exp(cut), x_i = exp(r_(i)) - ec for the tail in ascending order, i = 1 .. M.
+ *   The fit runs if M >= 5 and x_q > 0, q = floor(M / 4 + 0.5): m = 30 + floor(sqrt(M)); for j = 1 .. m
+ *   b_j = (1 - sqrt(m / (j - 0.5))) / (3 x_q) + 1 / x_M, k_j = mean_i log1p(-b_j x_i), L_j = M (log(-b_j / k_j) - k_j - 1),
+ *   w_j = 1 / sum_i exp(L_i - L_j) (a sum that overflows gives weight 0); b = sum_j b_j w_j, k = mean_i log1p(-b x_i),
+ *   sigma = -k / b, khat = (M k + 5) / (M + 10).  Without a fit, or with a non-finite khat or sigma, khat[n] = NaN and
+ *   nothing is smoothed.  With one, tail rank i takes lw = log(sigma expm1(-khat log1p(-p_i)) / khat + ec),
+ *   p_i = (i - 0.5) / M (at khat == 0: -sigma log1p(-p_i) in place of the quotient); every other draw keeps lw = r_s; then
+ *   lw = min(lw, 0), lw -= logsumexp_s lw, and elpd_loo[n] = logsumexp_s(lw_s + l_s).
+ * lppd, p_waic, elpd_loo, khat [N] fp64 and dropped [N] int32 are device pointers; each may be null, but not all five.
+ * r_eff, the relative efficiency of the draws, is a finite positive host scalar (1: independent draws).
+ * mile_psis_loo needs no handle: loglik [S, N] from anywhere; its workspace (the packed copy of a row tile, at most 256 MiB)
+ * is allocated and freed in the call, which returns after the kernels finish.
+ * mile_loo_stream is the same for draws theta [S, d] full-layout on (X [N, F], y [N]) as for mile_pointwise_loglik, whose
+ * forward it runs, never [S, N] at once.  The rows go in tiles of Nt rows, [S][Nt] floats plus the packed [Nt][S] copy within
+ * 256 MiB (Nt a multiple of 32 where it can be; max_rows_per_tile > 0 caps it, 0: the library's choice); inside a tile the
+ * forward runs in passes of at most max_draws_per_pass draws (0: all), each written at its draw offset, every (draw, row)
+ * forward exactly once.  The workspace is the handle's shared one, grown in the call; mile_loo_stream_workspace gives its
+ * bytes for (S, N) with the library's tile, -1 for a null handle or a shape out of range.
+ * Sums run in a fixed order without floating-point atomics and a row's result depends on its S values alone: the outputs
+ * are bitwise the same for every max_draws_per_pass and max_rows_per_tile, and equal to mile_psis_loo of
+ * mile_pointwise_loglik's tensor.
+ * MILE_ERR_INVALID: a null loglik / handle / theta / X / y, no output asked for, S < 2 or > 2^20, N < 1 or > 2^30 - 1,
+ * r_eff not finite or <= 0, a tail of more than 4096 draws (M at S_n = S; M <= 3072 whenever r_eff >= 1), a negative pass or
+ * tile size; MILE_ERR_STATE: frozen tables not set; MILE_ERR_NOMEM: the workspace.  Nothing is launched on any of them.
+ * (Added under ABI 10: three new symbols, no struct or existing entry changed.) */
+int32_t mile_psis_loo(const float *loglik, int64_t S, int64_t N, double r_eff, double *lppd, double *p_waic, double *elpd_loo,
+                      double *khat, int32_t *dropped, void *stream);
+int32_t mile_loo_stream(mile_sampler *s, const float *theta, int64_t S, const void *X, const void *y, int64_t N, double r_eff,
+                        double *lppd, double *p_waic, double *elpd_loo, double *khat, int32_t *dropped, int64_t max_draws_per_pass,
+                        int64_t max_rows_per_tile, void *stream);
+int64_t mile_loo_stream_workspace(const mile_sampler *s, int64_t S, int64_t N);   /* bytes; -1 out of range */
 
 /* Streamed LPPD and its running curves (the reference's lppd and running_lppd, src/inference/metrics.py:297-312, 408-446, and
  * the per-chain LPPD of src/inference/evaluation.py:520-529), reduced on the device without a [C, S, N] tensor.

@@ -32,6 +32,7 @@
 #include "mile_moments.h"
 #include "mile_lppd.h"
 #include "mile_quantiles.h"
+#include "mile_loo.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -81,7 +82,8 @@ struct mile_sampler {
   int64_t nz_launches = 0;              // mid-step launches that prefilled noise (mile_debug_prefill_count)
   void *ev_rows = nullptr; size_t ev_rows_bytes = 0;   // evaluation (test) set staging: X, its padded copy and y (stage_rows)
   // the streamed evaluation calls' one workspace (reserve_eval_ws): a pass of forward outputs, then the call's own state --
-  // moments: the accumulators; LPPD: the (m, s) state and partial sums; quantiles: the packed copy, brackets and sweeps
+  // moments: the accumulators; LPPD: the (m, s) state and partial sums; quantiles: the packed copy, brackets and sweeps;
+  // LOO: the packed copy
   void *eval_ws = nullptr; size_t eval_ws_bytes = 0;
   const int32_t *qnt_sweeps = nullptr; int64_t qnt_rows = 0;   // sweeps per row of the last mile_predict_quantiles, in eval_ws
   float *alt_x = nullptr, *alt_u = nullptr, *alt_g = nullptr, *alt_logp = nullptr;   // ping-pong state of mile_tune
@@ -2427,6 +2429,118 @@ extern "C" int32_t mile_debug_quantile_sweeps(mile_sampler *s, int64_t *rows, in
   HIP_TRY(hipMemcpy(h.data(), s->qnt_sweeps, h.size() * 4, hipMemcpyDeviceToHost));
   for (int32_t v : h) { *total += v; *most = std::max(*most, v); }
   return MILE_OK;
+}
+
+// mile_psis_loo / mile_loo_stream: every check before any launch; rows in tiles whose [S][Nt] block of log-likelihoods and
+// packed copy fit the evaluation budget, k_loo_pack + k_loo_row per tile (mile_loo.h).
+static const char *loo_bad_S(int64_t S) { return S < 2 || S > LOO_MAX_S ? "S out of range (2 .. 2^20)" : nullptr; }
+// what is wrong with r_eff or the outputs asked for (S in range), or null
+static const char *loo_bad_args(int64_t S, double r_eff, bool any_output) {
+  if (!any_output) return "no output asked for";
+  if (!std::isfinite(r_eff) || !(r_eff > 0.0)) return "r_eff must be finite and positive";
+  if (loo_tail_host(S, r_eff) > LOO_MAX_TAIL) return "the tail is longer than 4096 draws (S / r_eff too large)";
+  return nullptr;
+}
+
+static int64_t loo_tile_rows(int64_t S, int64_t N, int64_t max_rows) {
+  int64_t nt = std::max<int64_t>(1, EVAL_PASS_TARGET / (S * 8));   // [S][Nt] floats plus the packed copy
+  if (nt >= LOO_TILE) nt = nt / LOO_TILE * LOO_TILE;
+  if (max_rows > 0) nt = std::min(nt, max_rows);
+  return std::min(nt, N);
+}
+
+// the tiles of one call: ll_all [S][N] is the caller's tensor, walked in place (ld = N), or null and `fill` writes each
+// tile's [S][Nt] block (ld = Nt)
+template <class Fill>
+static int loo_run(const float *ll_all, float *pk, int64_t S, int64_t N, int64_t Nt, int n_cu, double r_eff, double *lppd, double *p_waic,
+                   double *elpd_loo, double *khat, int32_t *dropped, hipStream_t st, Fill fill) {
+  LooParams p{};
+  p.S = (int)S; p.pk = pk; p.r_eff = r_eff; p.M_full = loo_tail_host(S, r_eff);
+  for (int64_t r0 = 0; r0 < N; r0 += Nt) {
+    p.Nt = (int)std::min<int64_t>(Nt, N - r0);
+    p.slices = loo_slices((int)S, p.Nt, n_cu);
+    if (ll_all) { p.ll = ll_all + r0; p.ld = N; }
+    else {
+      const float *tile = nullptr;
+      const int rc = fill(r0, p.Nt, &tile);
+      if (rc != MILE_OK) return rc;
+      p.ll = tile; p.ld = p.Nt;
+    }
+    p.lppd = lppd ? lppd + r0 : nullptr;
+    p.p_waic = p_waic ? p_waic + r0 : nullptr;
+    p.elpd_loo = elpd_loo ? elpd_loo + r0 : nullptr;
+    p.khat = khat ? khat + r0 : nullptr;
+    p.dropped = dropped ? dropped + r0 : nullptr;
+    HIP_TRY(mile_launch_loo(p, st));
+  }
+  return MILE_OK;
+}
+
+extern "C" int32_t mile_psis_loo(const float *loglik, int64_t S, int64_t N, double r_eff, double *lppd, double *p_waic, double *elpd_loo,
+                                 double *khat, int32_t *dropped, void *stream) {
+  auto bad = [](const char *m) { return fail(MILE_ERR_INVALID, std::string("mile_psis_loo: ") + m); };
+  if (!loglik) return bad("null loglik");
+  if (const char *m = loo_bad_S(S)) return bad(m);
+  if (N < 1 || N > 0x3fffffff) return bad("N out of range (1 .. 2^30 - 1)");
+  if (const char *m = loo_bad_args(S, r_eff, lppd || p_waic || elpd_loo || khat || dropped)) return bad(m);
+  hipStream_t st = (hipStream_t)stream;
+  int dev = 0, n_cu = 256;
+  HIP_TRY(hipGetDevice(&dev));
+  (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+  const int64_t Nt = std::min<int64_t>(N, std::max<int64_t>(1, EVAL_PASS_TARGET / (S * 4)));   // the packed copy alone: loglik is the caller's
+  void *ws = nullptr;
+  if (hipMalloc(&ws, loo_pk_bytes(S, Nt)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MILE_ERR_NOMEM, "mile_psis_loo: workspace allocation failed");
+  }
+  const int rc = loo_run(loglik, (float *)ws, S, N, Nt, n_cu, r_eff, lppd, p_waic, elpd_loo, khat, dropped, st,
+                         [](int64_t, int, const float **) { return (int)MILE_OK; });
+  const hipError_t es = hipStreamSynchronize(st);   // the workspace is this call's: the kernels finish before it goes
+  (void)hipFree(ws);
+  if (rc != MILE_OK) return rc;
+  HIP_TRY(es);
+  return MILE_OK;
+}
+
+extern "C" int64_t mile_loo_stream_workspace(const mile_sampler *s, int64_t S, int64_t N) {
+  if (!s || loo_bad_S(S) || N < 1 || N > 0x3fffffff) return -1;
+  const int64_t Nt = loo_tile_rows(S, N, 0);
+  return (int64_t)(loo_r256((size_t)S * Nt * 4) + loo_pk_bytes(S, Nt));
+}
+
+extern "C" int32_t mile_loo_stream(mile_sampler *s, const float *theta, int64_t S, const void *X, const void *y, int64_t N, double r_eff,
+                                   double *lppd, double *p_waic, double *elpd_loo, double *khat, int32_t *dropped,
+                                   int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
+  if (s && theta && X && y)
+    if (const char *m = loo_bad_S(S)) return fail(MILE_ERR_INVALID, std::string("mile_loo_stream: ") + m);
+  const int rc0 = eval_args("mile_loo_stream", s, !theta || !X || !y, S, N, [&]() -> const char * {
+    if (const char *m = loo_bad_args(S, r_eff, lppd || p_waic || elpd_loo || khat || dropped)) return m;
+    if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
+    if (max_rows_per_tile < 0) return "max_rows_per_tile < 0";
+    return nullptr;
+  });
+  if (rc0 != MILE_OK) return rc0;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->device));
+  const int64_t Nt = loo_tile_rows(S, N, max_rows_per_tile);
+  const int64_t chunk = std::min<int64_t>(S, max_draws_per_pass ? max_draws_per_pass : S);
+  const size_t raw_bytes = loo_r256((size_t)S * Nt * 4);
+  if (reserve_eval_ws(s, raw_bytes + loo_pk_bytes(S, Nt)) != hipSuccess)
+    return fail(MILE_ERR_NOMEM, "mile_loo_stream: workspace allocation failed (lower max_rows_per_tile)");
+  float *raw = (float *)s->eval_ws;
+  const size_t row_floats = (size_t)s->spec.in_features;
+  auto fill = [&](int64_t r0, int nt, const float **tile) -> int {   // every (draw, row) forward once: passes at their draw offset
+    PredParams pp;
+    const int rc1 = stage_rows(s, (const float *)X + (size_t)r0 * row_floats, (const char *)y + (size_t)r0 * 4, nt, pp, st);
+    if (rc1 != MILE_OK) return rc1;
+    for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+      const int rc = eval_forward(s, pp, theta + (size_t)s0 * s->ds.d, std::min<int64_t>(chunk, S - s0), raw + (size_t)s0 * nt, st);
+      if (rc != MILE_OK) return rc;
+    }
+    *tile = raw;
+    return MILE_OK;
+  };
+  return loo_run(nullptr, (float *)((char *)s->eval_ws + raw_bytes), S, N, Nt, s->n_cu, r_eff, lppd, p_waic, elpd_loo, khat, dropped, st, fill);
 }
 
 // mile_lppd_stream: mile_pointwise_loglik's forward on the same draw window of every chain, a pass at a time, into the library's

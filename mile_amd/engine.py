@@ -725,6 +725,47 @@ class Engine:
                                                  int(max_draws_per_pass), self._stream()), self.lib)
         return out
 
+    def _loo_outputs(self, N, r_eff):
+        r_eff = float(r_eff)                                               # (the library refuses one that is not finite and positive)
+        out = {k: torch.empty(N, dtype=torch.float64, device=self.device) for k in ('lppd', 'p_waic', 'elpd_loo', 'khat')}
+        out['dropped'] = torch.empty(N, dtype=torch.int32, device=self.device)
+        return r_eff, out
+
+    def psis_loo(self, loglik, r_eff: float = 1.0) -> dict:
+        """PSIS-LOO and WAIC per row from pointwise log-likelihoods loglik [..., N] (every leading axis is a draw axis; from
+        ``pointwise_loglik`` or anywhere else), by the library's kernels (mile_psis_loo): fp64 device tensors ``lppd``,
+        ``p_waic``, ``elpd_loo``, ``khat`` [N] and ``dropped`` [N] int32 -- ``metrics.psis_loo`` of the same tensor.
+        ``r_eff``: relative efficiency of the draws (1: independent).  ``metrics.loo_summary`` gives the totals."""
+        ll = _f32(loglik, self.device, name='loglik')
+        if ll.ndim < 2:
+            raise ValueError('loglik must be [..., N]')
+        N = int(ll.shape[-1])
+        ll = ll.reshape(-1, N).contiguous()
+        r_eff, out = self._loo_outputs(N, r_eff)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_psis_loo(_ptr(ll), ll.shape[0], N, r_eff, _ptr(out['lppd']), _ptr(out['p_waic']),
+                                              _ptr(out['elpd_loo']), _ptr(out['khat']), _ptr(out['dropped']), self._stream()), self.lib)
+        return out
+
+    def loo_stream_workspace(self, S: int, N: int) -> int:
+        """Bytes of the workspace ``loo_stream`` keeps in the handle for S draws on N rows with the library's own tile
+        (mile_loo_stream_workspace)."""
+        return int(self.lib.mile_loo_stream_workspace(self._h, int(S), int(N)))
+
+    def loo_stream(self, theta, X, y, r_eff: float = 1.0, max_draws_per_pass: int = 0, max_rows_per_tile: int = 0) -> dict:
+        """``psis_loo`` of ``pointwise_loglik``'s tensor for draws theta [..., d] on (X [N, F], y [N]) -- the rows the sampler
+        conditioned on -- without ever holding it (mile_loo_stream): the rows go in tiles of at most ``max_rows_per_tile``
+        (0: the library's choice), the forward inside a tile in passes of at most ``max_draws_per_pass`` draws (0: all).  The
+        result does not depend on the two sizes, bit for bit."""
+        _, th, X, y = self._eval_inputs(theta, X, y)
+        N = int(X.shape[0])
+        r_eff, out = self._loo_outputs(N, r_eff)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_loo_stream(self._h, _ptr(th), th.shape[0], _ptr(X), _ptr(y), N, r_eff, _ptr(out['lppd']),
+                                                _ptr(out['p_waic']), _ptr(out['elpd_loo']), _ptr(out['khat']), _ptr(out['dropped']),
+                                                int(max_draws_per_pass), int(max_rows_per_tile), self._stream()), self.lib)
+        return out
+
     @property
     def supports_device_tuner(self) -> bool:
         return self.dim >= 4

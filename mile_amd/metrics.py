@@ -471,3 +471,101 @@ def coverage_from_pit(pit: torch.Tensor, coverages) -> torch.Tensor:
     v = v[torch.isfinite(v)]
     c = torch.as_tensor([float(c) for c in coverages], dtype=torch.float64, device=v.device)
     return ((v[None] - 0.5).abs() <= c[:, None] / 2).to(torch.float64).mean(dim=1)
+
+
+# ---- PSIS-LOO and WAIC of the ensemble: the torch restatement of mile_psis_loo (Engine.psis_loo / loo_stream), over a
+# pointwise tensor that fits in memory.  The timing tool's yardstick, and what a CPU tensor gets.  All fp64.
+
+_LOG_DBL_MIN = math.log(2.2250738585072014e-308)
+
+
+def _gpdfit(x: torch.Tensor, budget: int = 1 << 24):
+    """Zhang & Stephens' (2009) generalised-Pareto fit of the ascending exceedances x [G, M] -> (khat, sigma, ran) [G]: ``ran``
+    is False where the fit does not run (M < 5, x_q <= 0) or gives a non-finite khat or sigma."""
+    G, M = x.shape
+    nan = torch.full((G,), float('nan'), dtype=x.dtype, device=x.device)
+    if M < 5:
+        return nan, nan, torch.zeros(G, dtype=torch.bool, device=x.device)
+    q = int(math.floor(M / 4 + 0.5))
+    m = 30 + int(math.floor(math.sqrt(M)))
+    xq, xM = x[:, q - 1], x[:, M - 1]
+    j = torch.arange(1, m + 1, dtype=x.dtype, device=x.device)
+    b = (1.0 - torch.sqrt(m / (j - 0.5)))[None] / (3.0 * xq)[:, None] + (1.0 / xM)[:, None]        # [G, m]
+    k = torch.empty_like(b)
+    step = max(1, budget // (m * M))
+    for g0 in range(0, G, step):                                        # [g, m, M] at a time
+        k[g0:g0 + step] = torch.log1p(-b[g0:g0 + step, :, None] * x[g0:g0 + step, None, :]).mean(dim=-1)
+    L = M * (torch.log(-b / k) - k - 1.0)
+    w = 1.0 / torch.exp(L[:, :, None] - L[:, None, :]).sum(dim=1)       # w_j = 1 / sum_i exp(L_i - L_j); inf -> 0
+    bb = (b * w).sum(dim=1)
+    kk = torch.log1p(-bb[:, None] * x).mean(dim=1)
+    sigma = -kk / bb
+    khat = (M * kk + 5.0) / (M + 10.0)
+    ran = (xq > 0) & torch.isfinite(khat) & torch.isfinite(sigma)
+    return torch.where(ran, khat, nan), torch.where(ran, sigma, nan), ran
+
+
+def psis_loo(loglik: torch.Tensor, r_eff: float = 1.0) -> dict:
+    """loglik [..., N] = log p(y_n | x_n, theta_s) (every leading axis is a draw axis) -> per-row fp64 tensors ``lppd``,
+    ``p_waic``, ``elpd_loo``, ``khat`` [N] and ``dropped`` [N] int32: Pareto-smoothed importance-sampling leave-one-out
+    (Vehtari, Gelman & Gabry 2017; Vehtari et al. 2024) and WAIC.  A draw whose value on a row is NaN or +-inf is left out of
+    that row and counted; with S_n kept, lppd = logsumexp l - log S_n, p_waic the ddof-1 variance of l, and the
+    M = ceil(min(S_n / 5, 3 sqrt(S_n / r_eff))) largest ratios r = -l - max(-l) are replaced by the quantiles of the
+    generalised Pareto fitted to them (no fit and khat = NaN when M < 5 or the tail is degenerate), capped at 0 and
+    normalised; elpd_loo = logsumexp(lw + l).  A row with fewer than two kept draws holds NaN."""
+    if not (math.isfinite(r_eff) and r_eff > 0):
+        raise ValueError('r_eff must be finite and positive')
+    N = loglik.shape[-1]
+    l = loglik.reshape(-1, N).t().to(torch.float64)                     # [N, S]
+    S, dev = l.shape[1], l.device
+    ok = torch.isfinite(l)
+    Sn = ok.sum(dim=1)
+    out = {k: torch.full((N,), float('nan'), dtype=torch.float64, device=dev) for k in ('lppd', 'p_waic', 'elpd_loo', 'khat')}
+    out['dropped'] = (S - Sn).to(torch.int32)
+    neg = torch.where(ok, -l, torch.full_like(l, -float('inf')))
+    rs, idx = torch.sort(neg, dim=1)                                    # ascending; the dropped draws come first
+    ls = torch.gather(l, 1, idx)
+    del neg, idx, l, ok
+    for sn in torch.unique(Sn).tolist():
+        if sn < 2:
+            continue
+        rows = torch.nonzero(Sn == sn).reshape(-1)
+        lg = ls[rows, S - sn:]                                          # the kept draws, l descending
+        rg = rs[rows, S - sn:]
+        rg = rg - rg[:, -1:]                                            # r = -l - max(-l), ascending
+        out['lppd'][rows] = torch.logsumexp(lg, dim=1) - math.log(sn)
+        out['p_waic'][rows] = ((lg - lg.mean(dim=1, keepdim=True)) ** 2).sum(dim=1) / (sn - 1)
+        M = int(math.ceil(min(sn / 5.0, 3.0 * math.sqrt(sn / r_eff))))
+        cut = rg[:, sn - M - 1].clamp(min=_LOG_DBL_MIN)
+        ec = torch.exp(cut)
+        tail = rg[:, sn - M:]
+        khat, sigma, ran = _gpdfit(torch.exp(tail) - ec[:, None])
+        p = (torch.arange(1, M + 1, dtype=torch.float64, device=dev) - 0.5) / M
+        lp = torch.log1p(-p)[None]
+        qv = torch.where((khat == 0)[:, None], -sigma[:, None] * lp, sigma[:, None] * torch.expm1(-khat[:, None] * lp) / khat[:, None])
+        lw = torch.cat([rg[:, :sn - M], torch.where(ran[:, None], torch.log(qv + ec[:, None]), tail)], dim=1).clamp(max=0.0)
+        lw = lw - torch.logsumexp(lw, dim=1, keepdim=True)
+        out['elpd_loo'][rows] = torch.logsumexp(lw + lg, dim=1)
+        out['khat'][rows] = khat
+    return out
+
+
+def loo_summary(rows: dict) -> dict:
+    """The totals of per-row PSIS-LOO / WAIC arrays (``psis_loo``, Engine.psis_loo or Engine.loo_stream), on the host in fp64:
+    ``elpd_loo`` = sum_n elpd_loo_n with ``se_elpd_loo`` = sqrt(N var_n) (var with divisor N - 1, as the loo package) and
+    ``p_loo`` = sum_n (lppd_n - elpd_loo_n); ``elpd_waic`` = sum_n (lppd_n - p_waic_n) with ``se_elpd_waic`` and ``p_waic``;
+    ``lppd_sum``; and the diagnostics ``n_khat_above_0.7`` (finite khat only), ``n_khat_nofit`` (NaN khat) and
+    ``n_p_waic_above_0.4``.  A NaN row (fewer than two kept draws) makes the sums NaN."""
+    import numpy as np
+    a = {k: (rows[k].detach().cpu().numpy() if isinstance(rows[k], torch.Tensor) else np.asarray(rows[k])).astype(np.float64).reshape(-1)
+         for k in ('lppd', 'p_waic', 'elpd_loo', 'khat')}
+    N = a['lppd'].shape[0]
+    se = lambda v: float(np.sqrt(N * np.var(v, ddof=1))) if N > 1 else float('nan')
+    waic = a['lppd'] - a['p_waic']
+    khat = a['khat']
+    with np.errstate(invalid='ignore'):
+        return {'elpd_loo': float(a['elpd_loo'].sum()), 'se_elpd_loo': se(a['elpd_loo']), 'p_loo': float((a['lppd'] - a['elpd_loo']).sum()),
+                'elpd_waic': float(waic.sum()), 'se_elpd_waic': se(waic), 'p_waic': float(a['p_waic'].sum()),
+                'lppd_sum': float(a['lppd'].sum()),
+                'n_khat_above_0.7': int((khat[np.isfinite(khat)] > 0.7).sum()), 'n_khat_nofit': int(np.isnan(khat).sum()),
+                'n_p_waic_above_0.4': int((a['p_waic'] > 0.4).sum())}
