@@ -177,6 +177,24 @@ def loo_metrics(rows):
     return out, arrays
 
 
+def calibration_metrics(res, n_bins):
+    """--calibration: the metrics.json keys and the calibration.npz arrays of a calibration result ``res``
+    (Engine.calibration_stream, or metrics.classification_calibration of logits).  Keys: ``calibration_`` + every entry of the
+    ensemble's ``metrics.calibration_summary``, the per-chain ACC, Brier score, NLL and ECE with their medians, the bins used
+    and the (draw, row) pairs dropped in all."""
+    from mile_amd.metrics import calibration_summary
+    arrays = {k: res[k].detach().cpu().numpy() for k in ('coverages', 'order', 'set_size', 'rank', 'kept', 'bins', 'totals')}
+    arrays['probs'] = res['probs'][-1].detach().cpu().numpy().astype(np.float32)
+    summary = calibration_summary(arrays)
+    out = {f'calibration_{k}': v for k, v in summary[-1].items()}
+    for k in ('acc', 'brier', 'nll', 'ece'):
+        pc = [s[k] for s in summary[:-1]]
+        out[f'calibration_per_chain_{k}'] = pc
+        out[f'calibration_per_chain_{k}_median'] = float(np.nanmedian(pc))
+    out['calibration_n_bins'] = int(n_bins)
+    return out, arrays
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description='LPPD / NLL of the samples of an experiment directory')
     ap.add_argument('--diagnostics', type=int, nargs='?', const=2, default=None, metavar='N_SPLITS',
@@ -203,6 +221,13 @@ def build_parser():
                          'and means nothing on held-out rows.  loo_* keys in metrics.json (elpd_loo, p_loo, elpd_waic, p_waic with '
                          'standard errors, lppd_sum, the counts of rows with khat > 0.7, without a tail fit and with p_waic > 0.4) and '
                          'lppd, p_waic, elpd_loo, khat, dropped per row in loo.npz')
+    ap.add_argument('--calibration', type=int, nargs='?', const=15, default=None, metavar='N_BINS',
+                    help='classification: prediction sets and calibration of every chain and of the ensemble, streamed on the device '
+                         '(mile_calibration_stream) -- highest-probability sets at the levels of --coverages, the rank of the label, Brier '
+                         'score, NLL, accuracy and N_BINS equal-width reliability bins (default 15): calibration_* keys in metrics.json '
+                         '(acc, brier, nll, ece, mce, coverage_<c>, set_size_<c>, cal_error of the ensemble, per-chain lists and medians, '
+                         'calibration_dropped) and coverages, probs, order, set_size, rank, kept, bins, totals in calibration.npz -- no '
+                         'draws, so no seed')
     ap.add_argument('--loo-r-eff', type=float, default=1.0, metavar='R_EFF',
                     help='relative efficiency of the draws behind the PSIS tail length (default 1: independent draws)')
     ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
@@ -228,6 +253,9 @@ def main():
     tr = BDETrainer.__new__(BDETrainer)            # data + model spec only: no new experiment directory
     if args.intervals and cfg.data.task != 'regr':
         raise SystemExit('--intervals: predictive intervals are for regression experiments; this one is classification')
+    if args.calibration is not None and cfg.data.task == 'regr':
+        raise SystemExit('--calibration: prediction sets and reliability bins are for classification experiments; this one is '
+                         'regression (--intervals is its counterpart)')
     tr.build_model(cfg)
     spec = tr.prob_model.spec
     samples = load_samples_from_dir(exp / cfg.training.sampler._dir_name, spec)       # [C, S, d]
@@ -344,6 +372,17 @@ def main():
         keys, arrays = loo_metrics(rows)
         out.update(keys)
         np.savez(exp / 'loo.npz', **arrays)
+    if args.calibration is not None:
+        xt, yt = torch.from_numpy(x), torch.from_numpy(np.ascontiguousarray(y))
+        if spec.hidden_structure[-1] <= 64:
+            res = eng.calibration_stream(torch.from_numpy(samples), xt, yt, coverages=args.coverages, n_bins=args.calibration)
+        else:                                                              # more classes than the kernels take: the torch form
+            from mile_amd.metrics import classification_calibration
+            res = classification_calibration(eng.predict(torch.from_numpy(samples), xt), yt.to(args.device), args.coverages, args.calibration)
+        keys, arrays = calibration_metrics(res, args.calibration)
+        keys['calibration_dropped'] = int(samples.shape[0] * samples.shape[1] * x.shape[0] - int(arrays['kept'][-1].sum()))
+        out.update(keys)
+        np.savez(exp / 'calibration.npz', **arrays)
     (exp / 'metrics.json').write_text(json.dumps(out, indent=1) + '\n')
     print(json.dumps({k: v for k, v in out.items() if not isinstance(v, (list, dict))}))        # the per-chain arrays stay in metrics.json
 

@@ -382,8 +382,8 @@ int32_t mile_predict(mile_sampler *s, const float *theta, int32_t S, const float
  * (Welford + Chan for the variance), so the result does not depend on max_draws_per_pass beyond fp64 rounding.
  * MILE_ERR_INVALID: a null handle / theta / X / out, S < 1 or > 2^31 - 1, N < 1 or > 2^30 - 1, max_draws_per_pass < 0;
  * MILE_ERR_STATE: frozen tables not set; MILE_ERR_NOMEM: the workspace.  Nothing is launched on any of them.
- * The workspace is ONE buffer of the handle that mile_predict_moments, mile_predict_quantiles, mile_lppd_stream and
- * mile_loo_stream share: it is
+ * The workspace is ONE buffer of the handle that mile_predict_moments, mile_predict_quantiles, mile_lppd_stream,
+ * mile_loo_stream and mile_calibration_stream share: it is
  * as large as the largest of their calls so far asked for, each call lays its own blocks out in it, and -- like the staged
  * evaluation rows, which every evaluation call of a handle has always shared -- it holds one call at a time: evaluation calls
  * on one handle go on one stream, or are ordered by the caller.
@@ -427,8 +427,8 @@ int32_t mile_predict_quantiles(mile_sampler *s, const float *theta, int64_t S, c
 int64_t mile_predict_quantiles_workspace(const mile_sampler *s, int64_t S, int64_t N);   /* bytes; -1 out of range */
 /* Test and tool hook: over the rows of the handle's last mile_predict_quantiles that asked for quantiles, the row count, the
  * sum of the solver's sweeps and the largest sweep count of a row (synchronises the device).  The sweep counts lie in the
- * shared evaluation workspace: once a later mile_predict_moments, mile_lppd_stream, mile_loo_stream or mile_predict_quantiles
- * has reserved it they are gone, and this reports 0 rows (never stale counts) until a mile_predict_quantiles has finished again. */
+ * shared evaluation workspace: once a later mile_predict_moments, mile_lppd_stream, mile_loo_stream, mile_calibration_stream or
+ * mile_predict_quantiles has reserved it they are gone, and this reports 0 rows (never stale counts) until a mile_predict_quantiles has finished again. */
 int32_t mile_debug_quantile_sweeps(mile_sampler *s, int64_t *rows, int64_t *total, int32_t *most);
 
 /* PSIS-LOO and WAIC of the ensemble on the rows the sampler conditioned on: Pareto-smoothed importance-sampling leave-one-out
@@ -472,6 +472,52 @@ int32_t mile_loo_stream(mile_sampler *s, const float *theta, int64_t S, const vo
                         double *lppd, double *p_waic, double *elpd_loo, double *khat, int32_t *dropped, int64_t max_draws_per_pass,
                         int64_t max_rows_per_tile, void *stream);
 int64_t mile_loo_stream_workspace(const mile_sampler *s, int64_t S, int64_t N);   /* bytes; -1 out of range */
+
+/* Prediction sets and calibration of the classification ensemble, per chain and for the ensemble of all chains, on the device.
+ * The reference stops before this (src/inference/evaluation.py:463-464).  raw [C * S, N, K] fp32 logits as mile_predict
+ * writes them: draw j of chain c is row c * S + j, as in mile_lppd_stream (a deep ensemble's members are valid input).
+ * y [N] int32 device labels, or null.  coverages [Q] fp64 on the HOST, strictly inside (0, 1), strictly increasing.
+ * The groups are g = 0 .. C - 1 (each chain) and g = C (the ensemble), G = C + 1.  All arithmetic below is fp64.
+ *   A draw is kept on row n iff all K logits there are finite (per draw and per row, the rule of mile_predict_moments).
+ *   Per kept draw e_k = exp((double)z_k - (double)max_k z), p_k = e_k / sum_k e_k, the sum in class order.
+ *   P[c][n][k] = (sum of p_k over chain c's kept draws in draw order) / kept[c][n]; P[C][n][k] = (sum of the chains' sums in
+ *   chain order) / (sum of the chains' counts).  A (g, n) with nothing kept holds NaN in probs, has kept 0, is left out of
+ *   group g's totals and bins, and its ensemble outputs are order = 0 .. K - 1, set_size = 0, rank = 0.
+ *   Per (g, n) the classes are ordered by P descending, ties to the lower class index.  cum_i is the sequential sum of P in
+ *   that order; size_q is the smallest m with cum_m >= coverages[q], or K if none reaches it.
+ *   rank is the 1-based position of y_n in the order; covered_q = rank <= size_q; conf = P_(1); correct = (rank == 1);
+ *   bin = min(n_bins - 1, (int)floor(conf * n_bins)); brier = sum_k (P_k - [k == y_n])^2 in class order; nll = -log P_y.
+ *   A label outside [0, K) leaves the row out of the totals and bins, gives rank 0, and is counted in `bad labels`.
+ * Outputs, device pointers, each may be null but not all: probs [G, N, K] fp64; kept [G, N] int32; order [N, K], set_size
+ * [N, Q] and rank [N] int32, of the ensemble; totals [G, 5 + 2 Q] fp64 = (rows counted, rows correct, sum brier, sum nll,
+ * bad labels, covered_q .., sum size_q ..); bins [G, n_bins, 3] fp64 = (count, sum conf, sum correct).  rank, totals and bins
+ * need y.
+ * Sums over rows take a fixed two-stage order: blocks of B rows (B a function of N, G, Q and n_bins alone) summed in row
+ * order, then the blocks in block order; no floating-point atomics; counts are exact.
+ * mile_calibration needs no handle: logits from anywhere; its workspace (a row tile's sums and records and the blocks'
+ * partial sums, at most 256 MiB) is allocated and freed in the call, which returns after the kernels finish.
+ * mile_calibration_stream is the same for draws theta [C * S, d] full-layout (partition mode included) on X [N, F]:
+ * mile_predict's forward, never [C, S, N, K] at once.  The rows go in tiles of Nt rows (a multiple of 64 where it can be;
+ * max_rows_per_tile > 0 caps it, 0: the library's choice), inside a tile the forward runs in passes of at most
+ * max_draws_per_pass draws of every chain (0: as many as fit 128 MiB of logits), every (draw, row) forward exactly once.  The
+ * workspace is the handle's shared one, grown in the call; mile_calibration_stream_workspace gives an upper bound of its
+ * bytes for (C, S, N) with the library's tile and pass (over Q and n_bins), -1 for a null handle, a shape out of range or a
+ * handle that the call would refuse.  The outputs are bitwise the same for every max_draws_per_pass and max_rows_per_tile,
+ * and equal to mile_calibration of mile_predict's tensor.
+ * MILE_ERR_INVALID: a null raw / handle / theta / X / coverages, no output asked for, C outside [1, 65535], S < 1 (or
+ * C * S > 2^31 - 1), N < 1 or > 2^30 - 1, K outside [2, 64], Q outside [1, 16], coverages not strictly increasing or not
+ * strictly inside (0, 1), n_bins outside [1, 64], rank / totals / bins without y, a negative pass or tile size, a handle
+ * whose task is not classification or whose output width is not K (the stream takes K from the handle);
+ * MILE_ERR_STATE: frozen tables not set; MILE_ERR_NOMEM: the workspace.  Nothing is launched on any of them.
+ * (Added under ABI 10: three new symbols, no struct or existing entry changed.) */
+int32_t mile_calibration(const float *raw, int32_t C, int64_t S, int64_t N, int32_t K, const void *y, const double *coverages,
+                         int32_t Q, int32_t n_bins, double *probs, int32_t *kept, int32_t *order, int32_t *set_size, int32_t *rank,
+                         double *totals, double *bins, void *stream);
+int32_t mile_calibration_stream(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, const void *y, int64_t N,
+                                const double *coverages, int32_t Q, int32_t n_bins, double *probs, int32_t *kept, int32_t *order,
+                                int32_t *set_size, int32_t *rank, double *totals, double *bins, int64_t max_draws_per_pass,
+                                int64_t max_rows_per_tile, void *stream);
+int64_t mile_calibration_stream_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N);   /* bytes; -1 out of range */
 
 /* Streamed LPPD and its running curves (the reference's lppd and running_lppd, src/inference/metrics.py:297-312, 408-446, and
  * the per-chain LPPD of src/inference/evaluation.py:520-529), reduced on the device without a [C, S, N] tensor.

@@ -30,6 +30,7 @@
 #include "mile_nuts.h"
 #include "mile_diag.h"
 #include "mile_moments.h"
+#include "mile_calib.h"
 #include "mile_lppd.h"
 #include "mile_quantiles.h"
 #include "mile_loo.h"
@@ -83,6 +84,7 @@ struct mile_sampler {
   void *ev_rows = nullptr; size_t ev_rows_bytes = 0;   // evaluation (test) set staging: X, its padded copy and y (stage_rows)
   // the streamed evaluation calls' one workspace (reserve_eval_ws): a pass of forward outputs, then the call's own state --
   // moments: the accumulators; LPPD: the (m, s) state and partial sums; quantiles: the packed copy, brackets and sweeps;
+  // calibration: the chains' sums, the groups' records and the blocks' partial sums;
   // LOO: the packed copy
   void *eval_ws = nullptr; size_t eval_ws_bytes = 0;
   const int32_t *qnt_sweeps = nullptr; int64_t qnt_rows = 0;   // sweeps per row of the last mile_predict_quantiles, in eval_ws
@@ -2541,6 +2543,148 @@ extern "C" int32_t mile_loo_stream(mile_sampler *s, const float *theta, int64_t 
     return MILE_OK;
   };
   return loo_run(nullptr, (float *)((char *)s->eval_ws + raw_bytes), S, N, Nt, s->n_cu, r_eff, lppd, p_waic, elpd_loo, khat, dropped, st, fill);
+}
+
+// mile_calibration / mile_calibration_stream: every check before any launch; rows in tiles whose per-chain sums and per-group
+// records fit half the evaluation budget, k_cal_accum per pass of draws, k_cal_rows + k_cal_part per tile, k_cal_final at the
+// end (mile_calib.h).
+struct CalOut { double *probs; int32_t *kept, *order, *set_size, *rank; double *totals, *bins; };
+// what is wrong with the shape, the levels or the outputs asked for, or null (pointers other than y and the outputs checked before)
+static const char *cal_bad_args(int32_t C, int64_t S, int64_t N, int32_t K, const double *coverages, int32_t Q, int32_t n_bins, const void *y,
+                                const CalOut &o) {
+  if (!o.probs && !o.kept && !o.order && !o.set_size && !o.rank && !o.totals && !o.bins) return "no output asked for";
+  if (C < 1 || C > 65535) return "C out of range (1 .. 65535)";
+  if (S < 1 || S > 0x7fffffff) return "S out of range (1 .. 2^31 - 1)";
+  if (N < 1 || N > 0x3fffffff) return "N out of range (1 .. 2^30 - 1)";
+  if (K < 2 || K > CAL_K_MAX) return "K out of range (2 .. 64)";
+  if (Q < 1 || Q > CAL_Q_MAX) return "Q out of range (1 .. 16)";
+  for (int i = 0; i < Q; ++i) {
+    if (!(coverages[i] > 0.0 && coverages[i] < 1.0)) return "coverages must lie strictly inside (0, 1)";
+    if (i > 0 && !(coverages[i] > coverages[i - 1])) return "coverages must be strictly increasing";
+  }
+  if (n_bins < 1 || n_bins > CAL_BINS_MAX) return "n_bins out of range (1 .. 64)";
+  if (!y && (o.rank || o.totals || o.bins)) return "rank, totals and bins need y";
+  if ((int64_t)C * S > 0x7fffffff) return "C * S above 2^31 - 1";
+  return nullptr;
+}
+
+static const int64_t CAL_STATE_TARGET = (int64_t)128 << 20;   // bytes of a tile's sums, counts and records; the pass's logits take as much
+static int64_t cal_tile_rows(int C, int K, int64_t N, int64_t max_rows) {
+  int64_t nt = std::max<int64_t>(1, CAL_STATE_TARGET / (int64_t)cal_row_bytes(C, K));
+  if (nt >= CAL_NT) nt = nt / CAL_NT * CAL_NT;
+  if (max_rows > 0) nt = std::min(nt, max_rows);
+  return std::min(nt, N);
+}
+static int64_t cal_pass_draws(int C, int K, int64_t S, int64_t Nt, int64_t max_draws) {
+  const int64_t J = max_draws ? max_draws : std::max<int64_t>(1, CAL_STATE_TARGET / ((int64_t)C * Nt * K * 4));
+  return std::min(J, S);
+}
+// bytes behind the pass's logits for tiles of Nt rows: sums, counts, records, the blocks' partial sums
+static size_t cal_state_bytes(int C, int K, int64_t N, int64_t Nt, int Q, int n_bins) {
+  return cal_sum_bytes(C, K, Nt) + cal_cnt_bytes(C, Nt) + cal_rec_bytes(C, Nt) + cal_part_bytes(N, C + 1, cal_cols(Q, n_bins));
+}
+
+// the tiles of one call: `accum` folds all draws of the tile p describes (r0, Nt) into p.sum / p.cnt, zeroed here
+template <class Accum>
+static int cal_run(char *state, int C, int64_t N, int K, int64_t Nt, const void *y, const double *coverages, int Q, int n_bins, const CalOut &o,
+                   hipStream_t st, Accum accum) {
+  const int W = cal_cols(Q, n_bins);
+  CalParams p{};
+  p.C = C; p.K = K; p.Q = Q; p.n_bins = n_bins; p.N = N; p.y = (const int32_t *)y;
+  for (int i = 0; i < Q; ++i) p.cov[i] = coverages[i];
+  p.sum = (double *)state;
+  p.cnt = (int32_t *)(state + cal_sum_bytes(C, K, Nt));
+  char *rec = (char *)p.cnt + cal_cnt_bytes(C, Nt);
+  const bool reduce = y && (o.totals || o.bins);
+  p.rec = reduce ? (CalRec *)rec : nullptr;
+  p.part = (double *)(rec + cal_rec_bytes(C, Nt));
+  p.B = cal_block_rows(N, C + 1, W); p.nblk = (N + p.B - 1) / p.B;
+  p.probs = o.probs; p.kept = o.kept; p.order = o.order; p.set_size = o.set_size; p.rank = o.rank; p.totals = o.totals; p.bins = o.bins;
+  if (reduce) HIP_TRY(hipMemsetAsync(p.part, 0, (size_t)(C + 1) * p.nblk * W * 8, st));
+  for (int64_t r0 = 0; r0 < N; r0 += Nt) {
+    p.r0 = r0; p.Nt = (int)std::min<int64_t>(Nt, N - r0);
+    HIP_TRY(hipMemsetAsync(p.sum, 0, (size_t)C * p.Nt * K * 8, st));
+    HIP_TRY(hipMemsetAsync(p.cnt, 0, (size_t)C * p.Nt * 4, st));
+    const int rc = accum(p);
+    if (rc != MILE_OK) return rc;
+    HIP_TRY(mile_launch_cal_rows(p, st));
+  }
+  if (reduce) HIP_TRY(mile_launch_cal_final(p, st));
+  return MILE_OK;
+}
+
+extern "C" int32_t mile_calibration(const float *raw, int32_t C, int64_t S, int64_t N, int32_t K, const void *y, const double *coverages,
+                                    int32_t Q, int32_t n_bins, double *probs, int32_t *kept, int32_t *order, int32_t *set_size, int32_t *rank,
+                                    double *totals, double *bins, void *stream) {
+  auto bad = [](const char *m) { return fail(MILE_ERR_INVALID, std::string("mile_calibration: ") + m); };
+  const CalOut o{probs, kept, order, set_size, rank, totals, bins};
+  if (!raw || !coverages) return bad("null argument");
+  if (const char *m = cal_bad_args(C, S, N, K, coverages, Q, n_bins, y, o)) return bad(m);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t Nt = cal_tile_rows(C, K, N, 0);
+  void *ws = nullptr;
+  if (hipMalloc(&ws, cal_state_bytes(C, K, N, Nt, Q, n_bins)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MILE_ERR_NOMEM, "mile_calibration: workspace allocation failed");
+  }
+  const int rc = cal_run((char *)ws, C, N, K, Nt, y, coverages, Q, n_bins, o, st, [&](CalParams &p) -> int {
+    p.raw = raw + (size_t)p.r0 * K; p.cs = S; p.ld = N; p.J = (int)S;   // the caller's tensor, walked in place
+    HIP_TRY(mile_launch_cal_accum(p, st));
+    return MILE_OK;
+  });
+  const hipError_t es = hipStreamSynchronize(st);   // the workspace is this call's: the kernels finish before it goes
+  (void)hipFree(ws);
+  if (rc != MILE_OK) return rc;
+  HIP_TRY(es);
+  return MILE_OK;
+}
+
+extern "C" int64_t mile_calibration_stream_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N) {
+  if (!s || C < 1 || C > 65535 || S < 1 || S > 0x7fffffff || N < 1 || N > 0x3fffffff) return -1;
+  const int K = s->spec.widths[s->spec.n_layers - 1];
+  if (s->spec.task != MILE_TASK_CLASSIFICATION || K < 2 || K > CAL_K_MAX) return -1;
+  const int64_t Nt = cal_tile_rows(C, K, N, 0), J = cal_pass_draws(C, K, S, Nt, 0);
+  return (int64_t)(cal_r256((size_t)C * J * Nt * K * 4) + cal_state_bytes(C, K, N, Nt, CAL_Q_MAX, CAL_BINS_MAX));
+}
+
+extern "C" int32_t mile_calibration_stream(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, const void *y, int64_t N,
+                                           const double *coverages, int32_t Q, int32_t n_bins, double *probs, int32_t *kept, int32_t *order,
+                                           int32_t *set_size, int32_t *rank, double *totals, double *bins, int64_t max_draws_per_pass,
+                                           int64_t max_rows_per_tile, void *stream) {
+  const CalOut o{probs, kept, order, set_size, rank, totals, bins};
+  int K = 0;
+  const int rc0 = eval_args("mile_calibration_stream", s, !theta || !X || !coverages, S, N, [&]() -> const char * {
+    if (s->spec.task != MILE_TASK_CLASSIFICATION) return "needs a classification model";
+    K = s->spec.widths[s->spec.n_layers - 1];
+    if (const char *m = cal_bad_args(C, S, N, K, coverages, Q, n_bins, y, o)) return m;
+    if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
+    if (max_rows_per_tile < 0) return "max_rows_per_tile < 0";
+    return nullptr;
+  });
+  if (rc0 != MILE_OK) return rc0;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->device));
+  const int64_t Nt = cal_tile_rows(C, K, N, max_rows_per_tile), J = cal_pass_draws(C, K, S, Nt, max_draws_per_pass);
+  const size_t raw_bytes = cal_r256((size_t)C * J * Nt * K * 4);
+  if (reserve_eval_ws(s, raw_bytes + cal_state_bytes(C, K, N, Nt, Q, n_bins)) != hipSuccess)
+    return fail(MILE_ERR_NOMEM, "mile_calibration_stream: workspace allocation failed (lower max_draws_per_pass or max_rows_per_tile)");
+  float *raw = (float *)s->eval_ws;
+  const size_t row_floats = (size_t)s->spec.in_features;
+  return cal_run((char *)s->eval_ws + raw_bytes, C, N, K, Nt, y, coverages, Q, n_bins, o, st, [&](CalParams &p) -> int {
+    PredParams pp;
+    const int rc1 = stage_rows(s, (const float *)X + (size_t)p.r0 * row_floats, nullptr, p.Nt, pp, st);
+    if (rc1 != MILE_OK) return rc1;
+    p.raw = raw; p.ld = p.Nt;
+    for (int64_t j0 = 0; j0 < S; j0 += J) {   // every (draw, row) forward once: chain c's draws j0 .. are rows c * S + j0 .. of theta
+      p.J = (int)std::min<int64_t>(J, S - j0); p.cs = p.J;
+      for (int c = 0; c < C; ++c) {
+        const int rc = eval_forward(s, pp, theta + ((size_t)c * S + (size_t)j0) * s->ds.d, p.J, raw + (size_t)c * p.J * p.Nt * K, st);
+        if (rc != MILE_OK) return rc;
+      }
+      HIP_TRY(mile_launch_cal_accum(p, st));
+    }
+    return MILE_OK;
+  });
 }
 
 // mile_lppd_stream: mile_pointwise_loglik's forward on the same draw window of every chain, a pass at a time, into the library's

@@ -766,6 +766,79 @@ class Engine:
                                                 int(max_draws_per_pass), int(max_rows_per_tile), self._stream()), self.lib)
         return out
 
+    @staticmethod
+    def _calibration_levels(coverages):
+        lv = [float(v) for v in torch.as_tensor(coverages, dtype=torch.float64).reshape(-1)]
+        if not 1 <= len(lv) <= 16:
+            raise ValueError('coverages: between 1 and 16 of them')
+        return (C.c_double * len(lv))(*lv), lv                          # (the library checks their range and order)
+
+    def _calibration_outputs(self, G, N, K, lv, n_bins, y):
+        dev, Q = self.device, len(lv)
+        if y is not None:
+            y = torch.as_tensor(y, device=dev).to(torch.int32).reshape(-1).contiguous()
+            if y.shape != (N,):
+                raise ValueError('y must be [N]')
+        out = {'coverages': torch.tensor(lv, dtype=torch.float64, device=dev),
+               'probs': torch.empty((G, N, K), dtype=torch.float64, device=dev),
+               'kept': torch.empty((G, N), dtype=torch.int32, device=dev),
+               'order': torch.empty((N, K), dtype=torch.int32, device=dev),
+               'set_size': torch.empty((N, Q), dtype=torch.int32, device=dev)}
+        if y is not None:
+            out['rank'] = torch.empty(N, dtype=torch.int32, device=dev)
+            out['totals'] = torch.empty((G, 5 + 2 * Q), dtype=torch.float64, device=dev)
+            out['bins'] = torch.empty((G, max(int(n_bins), 0), 3), dtype=torch.float64, device=dev)
+        ptrs = [_ptr(out.get(k)) for k in ('probs', 'kept', 'order', 'set_size', 'rank', 'totals', 'bins')]
+        return y, out, ptrs
+
+    def calibration(self, raw, y=None, coverages=(0.5, 0.75, 0.9, 0.95), n_bins: int = 15) -> dict:
+        """Prediction sets and calibration of a classification ensemble from logits raw [C, S, N, K] (from ``predict``, or a deep
+        ensemble's members with S = 1), by the library's kernels (mile_calibration), for every chain (groups 0 .. C - 1) and the
+        ensemble of all chains (group C): device tensors ``probs`` [C + 1, N, K] fp64 (mean softmax of the draws whose logits
+        are all finite on the row), ``kept`` [C + 1, N] int32, and of the ensemble ``order`` [N, K] (classes by descending
+        probability, ties to the lower index) and ``set_size`` [N, Q] (the smallest highest-probability set whose sequential
+        sum reaches each of ``coverages``) int32.  With labels ``y`` [N] also ``rank`` [N] (1-based position of the label in
+        the order; 0 for a label outside [0, K)), ``totals`` [C + 1, 5 + 2 Q] (rows counted, rows correct, sum Brier, sum
+        NLL, bad labels, rows covered per level, sum of set sizes per level) and ``bins`` [C + 1, n_bins, 3] (count, sum of
+        confidence, sum of correct per equal-width confidence bin) fp64 -- ``metrics.classification_calibration`` of the same
+        tensor; ``metrics.calibration_summary`` turns them into ACC, Brier, NLL, ECE, MCE, coverage and mean set size.
+        K <= 64."""
+        lvc, lv = self._calibration_levels(coverages)
+        raw = _f32(raw, self.device, name='raw')
+        if raw.ndim != 4:
+            raise ValueError('raw must be [C, S, N, K]')
+        C_, S_, N, K = (int(v) for v in raw.shape)
+        r = raw.contiguous()
+        y, out, ptrs = self._calibration_outputs(C_ + 1, N, K, lv, n_bins, y)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_calibration(_ptr(r), C_, S_, N, K, _ptr(y), lvc, len(lv), int(n_bins), *ptrs, self._stream()),
+                       self.lib)
+        return out
+
+    def calibration_stream_workspace(self, C: int, S: int, N: int) -> int:
+        """Upper bound of the bytes of the workspace ``calibration_stream`` keeps in the handle for C chains of S draws on N rows
+        with the library's own tile and pass (mile_calibration_stream_workspace)."""
+        return int(self.lib.mile_calibration_stream_workspace(self._h, int(C), int(S), int(N)))
+
+    def calibration_stream(self, samples, x, y=None, coverages=(0.5, 0.75, 0.9, 0.95), n_bins: int = 15,
+                           max_draws_per_pass: int = 0, max_rows_per_tile: int = 0) -> dict:
+        """``calibration`` of ``predict``'s logits for samples [C, S, d] on x [N, F] without ever holding them
+        (mile_calibration_stream): the rows go in tiles of at most ``max_rows_per_tile`` (0: the library's choice), the forward
+        inside a tile in passes of at most ``max_draws_per_pass`` draws of every chain (0: the library's choice).  The result
+        does not depend on the two sizes, bit for bit.  Classification only."""
+        lvc, lv = self._calibration_levels(coverages)                   # (the library refuses a regression handle)
+        samples = _f32(samples, self.device, name='samples')
+        if samples.ndim != 3 or samples.shape[2] != self.d:
+            raise ValueError(f'samples must be [C, S, {self.d}]')
+        (C_, S_), theta, X, _ = self._eval_inputs(samples, x, name_x='x')
+        N, K = int(X.shape[0]), int(self.spec.hidden_structure[-1])
+        y, out, ptrs = self._calibration_outputs(C_ + 1, N, K, lv, n_bins, y)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_calibration_stream(self._h, _ptr(theta), C_, S_, _ptr(X), _ptr(y), N, lvc, len(lv), int(n_bins),
+                                                        *ptrs, int(max_draws_per_pass), int(max_rows_per_tile), self._stream()),
+                       self.lib)
+        return out
+
     @property
     def supports_device_tuner(self) -> bool:
         return self.dim >= 4

@@ -569,3 +569,115 @@ def loo_summary(rows: dict) -> dict:
                 'lppd_sum': float(a['lppd'].sum()),
                 'n_khat_above_0.7': int((khat[np.isfinite(khat)] > 0.7).sum()), 'n_khat_nofit': int(np.isnan(khat).sum()),
                 'n_p_waic_above_0.4': int((a['p_waic'] > 0.4).sum())}
+
+
+# ---- prediction sets and calibration of the classification ensemble: the torch restatement of mile_calibration
+# (Engine.calibration / calibration_stream) over logits that fit in memory.  The fallback for K > 64 and the tools' yardstick.
+
+def calibration_decide(probs: torch.Tensor, kept: torch.Tensor, y, coverages, n_bins: int = 15) -> dict:
+    """Group probabilities probs [G, N, K] fp64 (the last group is the ensemble) and kept [G, N] -> every discrete and summed
+    output of mile_calibration: ``order`` [N, K], ``set_size`` [N, Q] int32 of the ensemble, and with labels ``y`` [N] ``rank``
+    [N] int32, ``totals`` [G, 5 + 2 Q] and ``bins`` [G, n_bins, 3] fp64 (include/mile_hip.h states the definition).  The
+    cumulative sum that sizes a set is sequential, as in the library."""
+    G, N, K = probs.shape
+    dev = probs.device
+    cov = torch.as_tensor(coverages, dtype=torch.float64, device=dev).reshape(-1)
+    Q = int(cov.numel())
+    empty = kept.to(dev) == 0                                            # [G, N]
+    P = torch.where(empty[..., None], torch.zeros_like(probs), probs)
+    order = torch.argsort(-P, dim=-1, stable=True)                       # ties to the lower class index
+    order = torch.where(empty[..., None], torch.arange(K, device=dev).expand(G, N, K), order)
+    Ps = torch.gather(P, -1, order)
+    size = torch.zeros((G, N, Q), dtype=torch.int32, device=dev)
+    cum = torch.zeros((G, N), dtype=torch.float64, device=dev)
+    for i in range(K):
+        cum = cum + Ps[..., i]
+        hit = (cum[..., None] >= cov) & (size == 0)
+        size = torch.where(hit, torch.full_like(size, i + 1), size)
+    size = torch.where(size == 0, torch.full_like(size, K), size)
+    size = torch.where(empty[..., None], torch.zeros_like(size), size)
+    out = {'order': order[-1].to(torch.int32), 'set_size': size[-1]}
+    if y is None:
+        return out
+    yl = torch.as_tensor(y, device=dev).to(torch.int64).reshape(-1)
+    bad = (yl < 0) | (yl >= K)
+    ys = torch.where(bad, torch.zeros_like(yl), yl)
+    rank = (order == ys[None, :, None]).to(torch.int32).argmax(dim=-1).to(torch.int32) + 1
+    rank = torch.where(bad[None] | empty, torch.zeros_like(rank), rank)
+    valid = ~empty & ~bad[None]
+    onehot = torch.nn.functional.one_hot(ys, K).to(torch.float64)
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    brier = torch.where(valid, ((P - onehot[None]) ** 2).sum(dim=-1), zero)
+    nll = torch.where(valid, -torch.log(torch.gather(P, -1, ys[None, :, None].expand(G, N, 1))[..., 0]), zero)
+    conf = Ps[..., 0]
+    correct = (rank == 1) & valid
+    f = lambda t: t.to(torch.float64)
+    covered = (rank[..., None] <= size) & valid[..., None]
+    totals = torch.cat([torch.stack([f(valid).sum(1), f(correct).sum(1), brier.sum(1), nll.sum(1), f(bad[None] & ~empty).sum(1)], dim=1),
+                        f(covered).sum(1), (f(size) * f(valid)[..., None]).sum(1)], dim=1)
+    b = torch.clamp(torch.floor(conf * n_bins).to(torch.int64), max=n_bins - 1)
+    b = torch.where(valid, b, torch.zeros_like(b))
+    bins = torch.zeros((G, n_bins, 3), dtype=torch.float64, device=dev)
+    for j, v in enumerate((f(valid), torch.where(valid, conf, zero), f(correct))):
+        bins[..., j].scatter_add_(1, b, v)
+    out.update(rank=rank[-1], totals=totals, bins=bins)
+    return out
+
+
+def classification_calibration(raw: torch.Tensor, y=None, coverages=(0.5, 0.75, 0.9, 0.95), n_bins: int = 15,
+                               budget: int = 1 << 28) -> dict:
+    """The plain-torch form of Engine.calibration: logits raw [C, S, N, K] (any float dtype; the arithmetic is fp64) -> the same
+    dict -- ``coverages``, ``probs`` [C + 1, N, K] fp64, ``kept`` [C + 1, N] int32, ``order``, ``set_size``, and with ``y``
+    ``rank``, ``totals``, ``bins``.  A draw is kept on a row iff all its logits there are finite; a group's probabilities are
+    the mean softmax of its kept draws (the ensemble: all chains' draws), NaN with nothing kept.  No bound on K.  The draws
+    go through in slices of about ``budget`` bytes."""
+    C_, S_, N, K = raw.shape
+    dev = raw.device
+    sums = torch.zeros((C_, N, K), dtype=torch.float64, device=dev)
+    cnt = torch.zeros((C_, N), dtype=torch.int64, device=dev)
+    step = max(1, budget // max(1, C_ * N * K * 8 * 4))
+    for s0 in range(0, S_, step):
+        z = raw[:, s0:s0 + step]
+        ok = torch.isfinite(z).all(dim=-1)                               # [C, s, N]
+        z = torch.where(ok[..., None], z, torch.zeros_like(z)).to(torch.float64)
+        e = torch.exp(z - z.max(dim=-1, keepdim=True).values)
+        p = e / e.sum(dim=-1, keepdim=True)
+        sums += (p * ok[..., None]).sum(dim=1)
+        cnt += ok.sum(dim=1)
+    kept = torch.cat([cnt, cnt.sum(dim=0, keepdim=True)])
+    tot = torch.cat([sums, sums.sum(dim=0, keepdim=True)])
+    probs = torch.where(kept[..., None] > 0, tot / kept[..., None].to(torch.float64), torch.full_like(tot, float('nan')))
+    out = {'coverages': torch.as_tensor(coverages, dtype=torch.float64, device=dev).reshape(-1), 'probs': probs,
+           'kept': kept.to(torch.int32)}
+    out.update(calibration_decide(probs, kept, y, out['coverages'], n_bins))
+    return out
+
+
+def calibration_summary(result: dict) -> list:
+    """Per group (each chain, then the ensemble) of a calibration result's ``totals``, ``bins`` and ``coverages``: ``rows``,
+    ``acc``, ``brier``, ``nll`` (means over the rows counted), ``ece`` = sum_b |sum correct_b - sum conf_b| / rows, ``mce`` =
+    the largest |mean correct_b - mean conf_b| of a non-empty bin, ``coverage_<c>`` and ``set_size_<c>`` (share of rows whose
+    label is in the set, mean set size) and ``cal_error`` = ``calibration_error`` of the coverages.  Highest-probability sets
+    reach their level by construction, so that error is one-sided.  A group without rows holds NaN."""
+    tot = torch.as_tensor(result['totals']).detach().double().cpu()
+    bins = torch.as_tensor(result['bins']).detach().double().cpu()
+    cov = [float(v) for v in torch.as_tensor(result['coverages'], dtype=torch.float64).reshape(-1)]
+    Q = len(cov)
+    res = []
+    for g in range(tot.shape[0]):
+        rows = float(tot[g, 0])
+        nan = float('nan')
+        d = {'rows': int(rows), 'bad_labels': int(tot[g, 4])}
+        for i, k in enumerate(('acc', 'brier', 'nll')):
+            d[k] = float(tot[g, 1 + i]) / rows if rows else nan
+        gap = (bins[g, :, 2] - bins[g, :, 1]).abs()
+        full = bins[g, :, 0] > 0
+        d['ece'] = float(gap.sum()) / rows if rows else nan
+        d['mce'] = float((gap[full] / bins[g, full, 0]).max()) if bool(full.any()) else nan
+        obs = [float(tot[g, 5 + q]) / rows if rows else nan for q in range(Q)]
+        for q, c in enumerate(cov):
+            d[f'coverage_{c}'] = obs[q]
+            d[f'set_size_{c}'] = float(tot[g, 5 + Q + q]) / rows if rows else nan
+        d['cal_error'] = float(calibration_error(cov, obs).item())
+        res.append(d)
+    return res

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Posterior-predictive moments of a finished experiment on NEW inputs (the consumer of mile_predict_moments):
 
-    python predict.py -e results/mile_amd/<experiment> -i <table or .npz> [-o predictions.npz] [--draws-per-pass K] [--intervals C [C ...]]
+    python predict.py -e results/mile_amd/<experiment> -i <table or .npz> [-o predictions.npz] [--draws-per-pass K] [--intervals C [C ...]] [--sets C [C ...]]
 
 Reloads config.yaml and the samples the way evaluate.py does, applies the training normalisation the loader recorded
 (normalization.npz, written by train.py) to the rows of the table, reduces all C x S draws on the device and writes, per row:
@@ -11,6 +11,8 @@ Reloads config.yaml and the samples the way evaluate.py does, applies the traini
     both             dropped: draws left out of the row because an output was not finite
     --intervals C..  regression: quantile_levels [Q] (the bounds of the central intervals of coverage C.. and the median) and
                      quantiles [N, Q] of the ensemble's predictive mixture, solved exactly on the device (target units)
+    --sets C..       classification: set_levels [Q], class_order [N, K] (the classes by descending ensemble probability) and
+                     set_size [N, Q]: the highest-probability set of level C is the first set_size entries of class_order
 
 The table holds one row per input and the model's features as columns (no target column): .npy, .csv (comma), .data / .txt
 (whitespace), or an .npz with an array ``x`` (images [N, C, H, W], token ids [N, T]).  Where the target was z-scored
@@ -74,6 +76,10 @@ def build_parser():
                     help='regression: also the exact quantiles of the predictive mixture at the bounds of the central intervals of '
                          'these coverages and at the median (mile_predict_quantiles): quantile_levels [Q] and quantiles [N, Q], in '
                          'target units where the target was z-scored')
+    ap.add_argument('--sets', type=float, nargs='+', default=None, metavar='C',
+                    help='classification: also the highest-probability prediction sets of the ensemble at these coverage levels '
+                         '(mile_calibration_stream): set_levels [Q], class_order [N, K] and set_size [N, Q]; the set of a level is the '
+                         'first set_size entries of class_order')
     ap.add_argument('--normalized', action='store_true',
                     help='the rows already are in the training normalisation; the outputs stay in it')
     ap.add_argument('--drop-nonfinite', action='store_true', help='leave out chains with non-finite samples, as evaluate.py does')
@@ -92,6 +98,8 @@ def main():
     tr = BDETrainer.__new__(BDETrainer)            # data + model spec only: no new experiment directory
     if args.intervals and cfg.data.task != 'regr':
         raise SystemExit('--intervals: predictive intervals are for regression experiments; this one is classification')
+    if args.sets and cfg.data.task == 'regr':
+        raise SystemExit('--sets: prediction sets are for classification experiments; this one is regression (--intervals is its counterpart)')
     tr.build_model(cfg)
     spec = tr.prob_model.spec
     samples = load_samples_from_dir(exp / cfg.training.sampler._dir_name, spec)       # [C, S, d]
@@ -122,6 +130,16 @@ def main():
             q = q * float(norm['y_std'].reshape(-1)[0]) + float(norm['y_mean'].reshape(-1)[0])
         arrays['quantile_levels'] = levels.numpy()
         arrays['quantiles'] = q.astype(np.float32)
+    if args.sets:
+        levels = sorted(float(c) for c in args.sets)
+        if spec.hidden_structure[-1] <= 64:
+            res = eng.calibration_stream(torch.from_numpy(samples), torch.from_numpy(x), coverages=levels, max_draws_per_pass=args.draws_per_pass)
+        else:                                                              # more classes than the kernels take: the torch form
+            from mile_amd.metrics import classification_calibration
+            res = classification_calibration(eng.predict(torch.from_numpy(samples), torch.from_numpy(x)), None, levels)
+        arrays['set_levels'] = np.asarray(levels, dtype=np.float64)
+        arrays['class_order'] = res['order'].cpu().numpy()
+        arrays['set_size'] = res['set_size'].cpu().numpy()
     out = Path(args.output) if args.output else exp / 'predictions.npz'
     np.savez(out, **arrays)
     print(f'{out}: {len(x)} rows, {samples.shape[0] * samples.shape[1]} draws, {int(arrays["dropped"].sum())} dropped; '
