@@ -3,7 +3,7 @@
 mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
 src/inference/metrics.py:247-312):
 
-    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo]
+    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo] [--stacking]
 
 Reloads config.yaml and the samples/<chain>/sample_<n>.npz files, rebuilds the data split with the same
 seed, evaluates all C x S samples on the split in one device pass and writes metrics.json next to them.
@@ -177,6 +177,39 @@ def loo_metrics(rows):
     return out, arrays
 
 
+def stacking_refusal(n_chains, n_draws):
+    """Why --stacking cannot run on ``n_chains`` chains of ``n_draws`` draws, or None."""
+    if n_draws < 2:
+        return f'--stacking: PSIS-LOO of a chain needs at least 2 draws per chain; this experiment kept {n_draws}'
+    if n_chains > 1024:
+        return f'--stacking: at most 1024 chains (mile_chain_loo_stream, mile_stack_eval); this experiment has {n_chains}'
+    return None
+
+
+def stacking_metrics(train_rows, lpd_eval, eval=None):
+    """--stacking: the metrics.json keys and the stacking.npz arrays from the per-chain PSIS-LOO of the train split
+    ``train_rows`` (Engine.chain_loo_stream: ``elpd_loo`` and ``khat`` [C, N_train]) and the per-chain log predictive density of
+    the evaluated split ``lpd_eval`` [C, N].  The weights maximise the leave-one-out log score of the weighted mixture of the
+    chains (``metrics.stacking_weights``; ``eval``: Engine.stack_eval, None for the torch form); ``stacking_lppd`` is the
+    weighted LPPD of the evaluated split, ``stacking_lppd_equal`` the same at 1 / C -- the ensemble's LPPD -- and
+    ``stacking_gain`` their difference."""
+    from mile_amd import metrics as M
+    sol = M.stacking_weights(train_rows['elpd_loo'], eval=eval)
+    w = sol['w']
+    summary = M.stacking_summary(train_rows)
+    C_ = int(w.shape[0])
+    weighted = M.weighted_lppd(lpd_eval, w, eval=eval)
+    equal = M.weighted_lppd(lpd_eval, np.full(C_, 1.0 / C_), eval=eval)
+    out = {'stacking_lppd': weighted, 'stacking_lppd_equal': equal, 'stacking_gain': weighted - equal,
+           'stacking_gap': float(sol['gap']), 'stacking_iterations': int(sol['iterations']),
+           'stacking_converged': bool(sol['converged']), 'stacking_effective_chains': float(1.0 / np.sum(w * w)),
+           'stacking_khat_bad': int(sum(summary['chain_khat_bad'])), 'stacking_weights': [float(v) for v in w]}
+    arrays = {'weights': np.asarray(w, dtype=np.float64), 'chain_elpd_loo': np.asarray(summary['chain_elpd_loo'], dtype=np.float64),
+              'chain_khat_bad': np.asarray(summary['chain_khat_bad'], dtype=np.int64), 'gap': np.float64(sol['gap']),
+              'n_train': np.int64(summary['n_rows']), 'n_train_used': np.int64(sol['used']), 'n_eval': np.int64(lpd_eval.shape[1])}
+    return out, arrays
+
+
 def calibration_metrics(res, n_bins):
     """--calibration: the metrics.json keys and the calibration.npz arrays of a calibration result ``res``
     (Engine.calibration_stream, or metrics.classification_calibration of logits).  Keys: ``calibration_`` + every entry of the
@@ -228,8 +261,17 @@ def build_parser():
                          '(acc, brier, nll, ece, mce, coverage_<c>, set_size_<c>, cal_error of the ensemble, per-chain lists and medians, '
                          'calibration_dropped) and coverages, probs, order, set_size, rank, kept, bins, totals in calibration.npz -- no '
                          'draws, so no seed')
-    ap.add_argument('--loo-r-eff', type=float, default=1.0, metavar='R_EFF',
-                    help='relative efficiency of the draws behind the PSIS tail length (default 1: independent draws)')
+    ap.add_argument('--stacking', action='store_true',
+                    help='stacking weights of the chains (Yao et al. 2018), for chains that do not mix: PSIS-LOO of every chain on '
+                         'its own on the TRAIN split (mile_chain_loo_stream), the simplex weights that maximise the leave-one-out log '
+                         'score of the weighted mixture (mile_stack_eval behind a Newton / active-set solver), and what they buy on '
+                         '--split: stacking_lppd (weighted), stacking_lppd_equal (1 / C: the lppd above), stacking_gain, stacking_gap '
+                         '(a certified bound on the score left on the table), stacking_iterations, stacking_converged, '
+                         'stacking_effective_chains (1 / sum w^2), stacking_khat_bad (chain rows with khat > 0.7) and stacking_weights in '
+                         'metrics.json; weights, chain_elpd_loo, chain_khat_bad, gap, n_train, n_train_used, n_eval in stacking.npz.  '
+                         'Needs at least 2 draws per chain; --loo-r-eff applies')
+    ap.add_argument('--loo-r-eff', '--r-eff', type=float, default=1.0, metavar='R_EFF',
+                    help='relative efficiency of the draws behind the PSIS tail length of --loo and --stacking (default 1: independent draws)')
     ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
     ap.add_argument('--split', default='test', choices=['train', 'valid', 'test'])
     ap.add_argument('--device', default='cuda:0')
@@ -259,6 +301,8 @@ def main():
     tr.build_model(cfg)
     spec = tr.prob_model.spec
     samples = load_samples_from_dir(exp / cfg.training.sampler._dir_name, spec)       # [C, S, d]
+    if args.stacking and stacking_refusal(samples.shape[0], samples.shape[1]):
+        raise SystemExit(stacking_refusal(samples.shape[0], samples.shape[1]))
     bad_chains = ~np.isfinite(samples).all(axis=(1, 2))
     if args.drop_nonfinite and bad_chains.any() and not bad_chains.all():
         samples = samples[~bad_chains]
@@ -372,6 +416,15 @@ def main():
         keys, arrays = loo_metrics(rows)
         out.update(keys)
         np.savez(exp / 'loo.npz', **arrays)
+    if args.stacking:
+        st = torch.from_numpy(samples)
+        train_x = np.ascontiguousarray(tr.loader.train_x).reshape(len(tr.loader.train_x), -1)
+        train_rows = eng.chain_loo_stream(st, torch.from_numpy(train_x), torch.from_numpy(np.ascontiguousarray(tr.loader.train_y)),
+                                          r_eff=args.loo_r_eff, outputs=('elpd_loo', 'khat'))
+        lpd_eval = eng.chain_loo_stream(st, torch.from_numpy(x), torch.from_numpy(np.ascontiguousarray(y)), outputs=('lppd',))['lppd']
+        keys, arrays = stacking_metrics(train_rows, lpd_eval, eval=eng.stack_eval)
+        out.update(keys)
+        np.savez(exp / 'stacking.npz', **arrays)
     if args.calibration is not None:
         xt, yt = torch.from_numpy(x), torch.from_numpy(np.ascontiguousarray(y))
         if spec.hidden_structure[-1] <= 64:

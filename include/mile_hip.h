@@ -473,6 +473,46 @@ int32_t mile_loo_stream(mile_sampler *s, const float *theta, int64_t S, const vo
                         int64_t max_rows_per_tile, void *stream);
 int64_t mile_loo_stream_workspace(const mile_sampler *s, int64_t S, int64_t N);   /* bytes; -1 out of range */
 
+/* PSIS-LOO and WAIC of every chain on its own: mile_loo_stream for theta [C * S, d] full-layout, draw j of chain c at row
+ * c * S + j as for mile_lppd_stream.  lppd, p_waic, elpd_loo, khat [C, N] fp64 and dropped [C, N] int32 are device pointers;
+ * each may be null, but not all five.  A row tile is staged once for all chains; each chain's S draws then go through the tile
+ * and pass scheme and the two kernels of mile_loo_stream, every (draw, row) forward exactly once, so row c of every output is
+ * bitwise what mile_loo_stream gives for theta + c * S * d alone, for every max_draws_per_pass and max_rows_per_tile.  A call
+ * that asks for lppd alone ends each row after its first pass: the [C, N] matrix of a held-out split.  The workspace is the
+ * handle's shared one and that of one chain (mile_chain_loo_stream_workspace).
+ * Limits and refusals are mile_loo_stream's, S being the draws of one chain, plus MILE_ERR_INVALID for C < 1 or > 1024.
+ * (Added under ABI 10: two new symbols, no struct or existing entry changed.) */
+int32_t mile_chain_loo_stream(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, const void *y, int64_t N,
+                              double r_eff, double *lppd, double *p_waic, double *elpd_loo, double *khat, int32_t *dropped,
+                              int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream);
+int64_t mile_chain_loo_stream_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N);   /* bytes; -1 out of range */
+
+/* Stacking of chains that do not mix (Yao, Vehtari, Simpson & Gelman 2018; Yao, Vehtari & Gelman 2022): one evaluation of the
+ * log score of the weighted mixture of the chains' pointwise predictive densities, with its gradient in the weights and the
+ * Gram matrix of the responsibilities (the negative Hessian), on the device.  The reference has no counterpart.  No handle.
+ * lpd [C, N] fp64 (say the elpd_loo of mile_chain_loo_stream) and w [C] fp64 with entries >= 0 are device pointers.  All
+ * arithmetic is fp64.
+ *   Row n is used iff no lpd[c][n] is NaN or +inf and m_n = max_c lpd[c][n] > -inf; any other row is left out, holds NaN in
+ *   row_score and enters no sum; used[0] counts the rest.
+ *   e_cn = exp(lpd[c][n] - m_n); mix_n = sum_c w_c e_cn in chain order (one fma per chain); row_score[n] = m_n + log mix_n;
+ *   R_cn = e_cn / mix_n.
+ *   score[0] = (sum_n row_score[n]) / used;  grad[c] = (sum_n R_cn) / used;  hess[a][b] = (sum_n R_an R_bn) / used.
+ *   A used row with mix_n == 0 makes score -inf; grad and hess are then unspecified.  used == 0 makes all three NaN.
+ *   hess is exactly symmetric: the lower triangle is computed and mirrored.
+ * Sums over rows take a fixed two-stage order: blocks of B rows, each entry one chain of fma over the block's rows in row
+ * order, then the blocks in block order; B depends on C and N alone (the blocks' partial sums within 64 MiB, at most 1024
+ * blocks, B a multiple of 32).  No floating-point atomics.  The rows go in tiles whose responsibilities [C + 2][Nt] fp64 stay
+ * within 256 MiB (max_rows_per_tile > 0 caps Nt, 0: the library's choice); a block that a tile cuts is carried from its
+ * partial sum, so the outputs are bitwise the same for every max_rows_per_tile.
+ * score [1], row_score [N], grad [C], hess [C, C] fp64 and used [1] int64 are device pointers; each may be null, but not all
+ * five.  A call without hess computes only what score, grad and used need; one for row_score alone sums nothing.
+ * The workspace is allocated and freed in the call, which returns after the kernels finish.
+ * MILE_ERR_INVALID: a null lpd or w, C < 1 or > 1024, N < 1 or > 2^30 - 1, a negative tile size, no output asked for;
+ * MILE_ERR_NOMEM: the workspace.  Nothing is launched on any of them.
+ * (Added under ABI 10: a new symbol, no struct or existing entry changed.) */
+int32_t mile_stack_eval(const double *lpd, const double *w, int32_t C, int64_t N, double *score, double *row_score, double *grad,
+                        double *hess, int64_t *used, int64_t max_rows_per_tile, void *stream);
+
 /* Prediction sets and calibration of the classification ensemble, per chain and for the ensemble of all chains, on the device.
  * The reference stops before this (src/inference/evaluation.py:463-464).  raw [C * S, N, K] fp32 logits as mile_predict
  * writes them: draw j of chain c is row c * S + j, as in mile_lppd_stream (a deep ensemble's members are valid input).

@@ -34,6 +34,7 @@
 #include "mile_lppd.h"
 #include "mile_quantiles.h"
 #include "mile_loo.h"
+#include "mile_stack.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -2510,6 +2511,46 @@ extern "C" int64_t mile_loo_stream_workspace(const mile_sampler *s, int64_t S, i
   return (int64_t)(loo_r256((size_t)S * Nt * 4) + loo_pk_bytes(S, Nt));
 }
 
+// mile_loo_stream and mile_chain_loo_stream after their checks: theta [C * S, d], chain c's S draws at row c * S, outputs
+// [C, N].  The row tiles go outermost, so a tile's rows are staged once for all chains; each chain's block [S][Nt] is forwarded
+// and goes through k_loo_pack + k_loo_row on its own, as a call on that chain alone would send it.
+static int loo_stream_chains(mile_sampler *s, const float *theta, int64_t C, int64_t S, const void *X, const void *y, int64_t N, double r_eff,
+                             double *lppd, double *p_waic, double *elpd_loo, double *khat, int32_t *dropped,
+                             int64_t max_draws_per_pass, int64_t max_rows_per_tile, const char *fn, hipStream_t st) {
+  HIP_TRY(hipSetDevice(s->device));
+  const int64_t Nt = loo_tile_rows(S, N, max_rows_per_tile);
+  const int64_t chunk = std::min<int64_t>(S, max_draws_per_pass ? max_draws_per_pass : S);
+  const size_t raw_bytes = loo_r256((size_t)S * Nt * 4);
+  if (reserve_eval_ws(s, raw_bytes + loo_pk_bytes(S, Nt)) != hipSuccess)
+    return fail(MILE_ERR_NOMEM, std::string(fn) + ": workspace allocation failed (lower max_rows_per_tile)");
+  float *raw = (float *)s->eval_ws;
+  const size_t row_floats = (size_t)s->spec.in_features;
+  LooParams p{};
+  p.S = (int)S; p.pk = (float *)((char *)s->eval_ws + raw_bytes); p.r_eff = r_eff; p.M_full = loo_tail_host(S, r_eff);
+  for (int64_t r0 = 0; r0 < N; r0 += Nt) {
+    const int nt = (int)std::min<int64_t>(Nt, N - r0);
+    PredParams pp;
+    const int rc1 = stage_rows(s, (const float *)X + (size_t)r0 * row_floats, (const char *)y + (size_t)r0 * 4, nt, pp, st);
+    if (rc1 != MILE_OK) return rc1;
+    p.Nt = nt; p.slices = loo_slices((int)S, nt, s->n_cu); p.ll = raw; p.ld = nt;
+    for (int64_t c = 0; c < C; ++c) {
+      const float *th = theta + (size_t)c * S * s->ds.d;
+      for (int64_t s0 = 0; s0 < S; s0 += chunk) {   // every (draw, row) forward once: passes at their draw offset
+        const int rc = eval_forward(s, pp, th + (size_t)s0 * s->ds.d, std::min<int64_t>(chunk, S - s0), raw + (size_t)s0 * nt, st);
+        if (rc != MILE_OK) return rc;
+      }
+      const size_t at = (size_t)c * N + r0;
+      p.lppd = lppd ? lppd + at : nullptr;
+      p.p_waic = p_waic ? p_waic + at : nullptr;
+      p.elpd_loo = elpd_loo ? elpd_loo + at : nullptr;
+      p.khat = khat ? khat + at : nullptr;
+      p.dropped = dropped ? dropped + at : nullptr;
+      HIP_TRY(mile_launch_loo(p, st));
+    }
+  }
+  return MILE_OK;
+}
+
 extern "C" int32_t mile_loo_stream(mile_sampler *s, const float *theta, int64_t S, const void *X, const void *y, int64_t N, double r_eff,
                                    double *lppd, double *p_waic, double *elpd_loo, double *khat, int32_t *dropped,
                                    int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
@@ -2522,27 +2563,68 @@ extern "C" int32_t mile_loo_stream(mile_sampler *s, const float *theta, int64_t 
     return nullptr;
   });
   if (rc0 != MILE_OK) return rc0;
+  return loo_stream_chains(s, theta, 1, S, X, y, N, r_eff, lppd, p_waic, elpd_loo, khat, dropped, max_draws_per_pass, max_rows_per_tile,
+                           "mile_loo_stream", (hipStream_t)stream);
+}
+
+// mile_chain_loo_stream: mile_loo_stream's checks, plus C
+extern "C" int64_t mile_chain_loo_stream_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N) {
+  if (C < 1 || C > 1024) return -1;
+  return mile_loo_stream_workspace(s, S, N);   // a chain at a time: the workspace of one
+}
+
+extern "C" int32_t mile_chain_loo_stream(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, const void *y, int64_t N,
+                                         double r_eff, double *lppd, double *p_waic, double *elpd_loo, double *khat, int32_t *dropped,
+                                         int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
+  if (s && theta && X && y)
+    if (const char *m = loo_bad_S(S)) return fail(MILE_ERR_INVALID, std::string("mile_chain_loo_stream: ") + m);
+  const int rc0 = eval_args("mile_chain_loo_stream", s, !theta || !X || !y, S, N, [&]() -> const char * {
+    if (C < 1 || C > 1024) return "C out of range (1 .. 1024)";
+    if (const char *m = loo_bad_args(S, r_eff, lppd || p_waic || elpd_loo || khat || dropped)) return m;
+    if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
+    if (max_rows_per_tile < 0) return "max_rows_per_tile < 0";
+    return nullptr;
+  });
+  if (rc0 != MILE_OK) return rc0;
+  return loo_stream_chains(s, theta, C, S, X, y, N, r_eff, lppd, p_waic, elpd_loo, khat, dropped, max_draws_per_pass, max_rows_per_tile,
+                           "mile_chain_loo_stream", (hipStream_t)stream);
+}
+
+// mile_stack_eval: every check before any launch; rows in tiles whose responsibilities fit 256 MiB, k_stk_rows + k_stk_gram per
+// tile, k_stk_final at the end (mile_stack.h).  The workspace is this call's.
+extern "C" int32_t mile_stack_eval(const double *lpd, const double *w, int32_t C, int64_t N, double *score, double *row_score, double *grad,
+                                   double *hess, int64_t *used, int64_t max_rows_per_tile, void *stream) {
+  auto bad = [](const char *m) { return fail(MILE_ERR_INVALID, std::string("mile_stack_eval: ") + m); };
+  if (!lpd || !w) return bad("null lpd or w");
+  if (const char *m = stk_bad_args(C, N, max_rows_per_tile, score || row_score || grad || hess || used)) return bad(m);
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipSetDevice(s->device));
-  const int64_t Nt = loo_tile_rows(S, N, max_rows_per_tile);
-  const int64_t chunk = std::min<int64_t>(S, max_draws_per_pass ? max_draws_per_pass : S);
-  const size_t raw_bytes = loo_r256((size_t)S * Nt * 4);
-  if (reserve_eval_ws(s, raw_bytes + loo_pk_bytes(S, Nt)) != hipSuccess)
-    return fail(MILE_ERR_NOMEM, "mile_loo_stream: workspace allocation failed (lower max_rows_per_tile)");
-  float *raw = (float *)s->eval_ws;
-  const size_t row_floats = (size_t)s->spec.in_features;
-  auto fill = [&](int64_t r0, int nt, const float **tile) -> int {   // every (draw, row) forward once: passes at their draw offset
-    PredParams pp;
-    const int rc1 = stage_rows(s, (const float *)X + (size_t)r0 * row_floats, (const char *)y + (size_t)r0 * 4, nt, pp, st);
-    if (rc1 != MILE_OK) return rc1;
-    for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-      const int rc = eval_forward(s, pp, theta + (size_t)s0 * s->ds.d, std::min<int64_t>(chunk, S - s0), raw + (size_t)s0 * nt, st);
-      if (rc != MILE_OK) return rc;
+  StkParams p{};
+  p.lpd = lpd; p.w = w; p.C = C; p.Cx = C + 2; p.N = N;
+  p.B = stk_block_rows(C, N); p.nb = (int)stk_blocks(C, N);
+  p.want_grad = grad != nullptr; p.want_hess = hess != nullptr; p.want_sums = score || grad || hess || used;
+  p.score = score; p.row_score = row_score; p.grad = grad; p.hess = hess; p.used = (long long *)used;
+  const int64_t Nt = stk_tile_rows(C, N, max_rows_per_tile);
+  p.ldR = Nt;
+  void *ws = nullptr;
+  if (p.want_sums) {
+    const size_t rx_bytes = stk_rx_bytes(C, Nt);
+    if (hipMalloc(&ws, rx_bytes + stk_part_bytes(C, N)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(MILE_ERR_NOMEM, "mile_stack_eval: workspace allocation failed (lower max_rows_per_tile)");
     }
-    *tile = raw;
-    return MILE_OK;
-  };
-  return loo_run(nullptr, (float *)((char *)s->eval_ws + raw_bytes), S, N, Nt, s->n_cu, r_eff, lppd, p_waic, elpd_loo, khat, dropped, st, fill);
+    p.Rx = (double *)ws; p.part = (double *)((char *)ws + rx_bytes);
+  }
+  hipError_t e = hipSuccess;
+  for (int64_t r0 = 0; r0 < N && e == hipSuccess; r0 += Nt) {
+    p.r0 = r0; p.Nt = (int)std::min<int64_t>(Nt, N - r0);
+    e = mile_launch_stack_tile(p, st);
+  }
+  if (e == hipSuccess && p.want_sums) e = mile_launch_stack_final(p, st);
+  const hipError_t es = hipStreamSynchronize(st);   // the workspace is this call's: the kernels finish before it goes
+  if (ws) (void)hipFree(ws);
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return MILE_OK;
 }
 
 // mile_calibration / mile_calibration_stream: every check before any launch; rows in tiles whose per-chain sums and per-group

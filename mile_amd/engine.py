@@ -766,6 +766,58 @@ class Engine:
                                                 int(max_draws_per_pass), int(max_rows_per_tile), self._stream()), self.lib)
         return out
 
+    def chain_loo_stream_workspace(self, C_: int, S: int, N: int) -> int:
+        """Bytes of the workspace ``chain_loo_stream`` keeps in the handle for C chains of S draws on N rows with the library's
+        own tile (mile_chain_loo_stream_workspace): that of one chain."""
+        return int(self.lib.mile_chain_loo_stream_workspace(self._h, int(C_), int(S), int(N)))
+
+    def chain_loo_stream(self, samples, X, y, r_eff: float = 1.0, outputs=('lppd', 'p_waic', 'elpd_loo', 'khat', 'dropped'),
+                         max_draws_per_pass: int = 0, max_rows_per_tile: int = 0) -> dict:
+        """``loo_stream`` of every chain of samples [C, S, d] on its own (mile_chain_loo_stream): the ``outputs`` asked for, each
+        [C, N] (fp64; ``dropped`` int32), row c bitwise what ``loo_stream(samples[c], ...)`` gives.  ``outputs=('lppd',)`` is the
+        per-chain log predictive density of a held-out split, and ends each row after its first pass.  The result does not
+        depend on the two sizes, bit for bit."""
+        names = ('lppd', 'p_waic', 'elpd_loo', 'khat', 'dropped')
+        outputs = tuple(outputs)
+        if not outputs or any(k not in names for k in outputs):
+            raise ValueError(f'outputs: a non-empty choice of {names}')
+        samples = _f32(samples, self.device, name='samples')
+        if samples.ndim != 3 or samples.shape[2] != self.d:
+            raise ValueError(f'samples must be [C, S, {self.d}]')
+        (C_, S_), th, X, y = self._eval_inputs(samples, X, y)
+        N = int(X.shape[0])
+        out = {k: torch.empty((C_, N), dtype=torch.int32 if k == 'dropped' else torch.float64, device=self.device) for k in outputs}
+        ptr = lambda k: _ptr(out[k]) if k in out else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_chain_loo_stream(self._h, _ptr(th), C_, S_, _ptr(X), _ptr(y), N, float(r_eff), ptr('lppd'),
+                                                      ptr('p_waic'), ptr('elpd_loo'), ptr('khat'), ptr('dropped'),
+                                                      int(max_draws_per_pass), int(max_rows_per_tile), self._stream()), self.lib)
+        return out
+
+    def stack_eval(self, lpd, w, outputs=('score', 'grad', 'hess', 'used'), max_rows_per_tile: int = 0) -> dict:
+        """One evaluation of the stacking objective on the device (mile_stack_eval): lpd [C, N] and w [C] (fp64, entries >= 0)
+        -> the ``outputs`` asked for among ``score`` [], ``row_score`` [N], ``grad`` [C], ``hess`` [C, C] (fp64) and ``used`` []
+        int64, device tensors -- ``metrics.stack_eval_dense`` of the same inputs.  The result does not depend on
+        ``max_rows_per_tile``, bit for bit.  A call without ``hess`` computes only what the rest needs."""
+        names = ('score', 'row_score', 'grad', 'hess', 'used')
+        outputs = tuple(outputs)
+        if not outputs or any(k not in names for k in outputs):
+            raise ValueError(f'outputs: a non-empty choice of {names}')
+        lpd = torch.as_tensor(lpd).to(device=self.device, dtype=torch.float64).contiguous()
+        if lpd.ndim != 2:
+            raise ValueError('lpd must be [C, N]')
+        C_, N = int(lpd.shape[0]), int(lpd.shape[1])
+        w = torch.as_tensor(w).to(device=self.device, dtype=torch.float64).reshape(-1).contiguous()
+        if w.shape != (C_,):
+            raise ValueError('w must be [C]')
+        shapes = {'score': (), 'row_score': (N,), 'grad': (C_,), 'hess': (C_, C_), 'used': ()}
+        out = {k: torch.empty(shapes[k], dtype=torch.int64 if k == 'used' else torch.float64, device=self.device) for k in outputs}
+        ptr = lambda k: _ptr(out[k]) if k in out else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_stack_eval(_ptr(lpd), _ptr(w), C_, N, ptr('score'), ptr('row_score'), ptr('grad'), ptr('hess'),
+                                                ptr('used'), int(max_rows_per_tile), self._stream()), self.lib)
+        return out
+
     @staticmethod
     def _calibration_levels(coverages):
         lv = [float(v) for v in torch.as_tensor(coverages, dtype=torch.float64).reshape(-1)]

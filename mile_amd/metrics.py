@@ -681,3 +681,155 @@ def calibration_summary(result: dict) -> list:
         d['cal_error'] = float(calibration_error(cov, obs).item())
         res.append(d)
     return res
+
+
+# ---- stacking of chains that do not mix (Yao, Vehtari, Simpson & Gelman 2018; Yao, Vehtari & Gelman 2022): the torch restatement
+# of mile_stack_eval (Engine.stack_eval), the solver for the weights on either of them, and what evaluate.py --stacking reports.
+
+_STACK_OUTPUTS = ('score', 'row_score', 'grad', 'hess', 'used')
+
+
+def stack_eval_dense(lpd: torch.Tensor, w, outputs=('score', 'grad', 'hess', 'used'), max_rows_per_tile: int = 0) -> dict:
+    """lpd [C, N] and w [C] (entries >= 0) -> the ``outputs`` asked for among ``score`` [], ``row_score`` [N], ``grad`` [C],
+    ``hess`` [C, C] (fp64) and ``used`` [] int64, on lpd's device: the log score of the w-weighted mixture of the chains'
+    pointwise predictive densities, its gradient in w and the Gram matrix of the responsibilities (the negative Hessian).  A row
+    with a NaN or +inf entry, or with no entry above -inf, is left out (NaN in ``row_score``) and ``used`` counts the rest; with
+    m_n = max_c lpd_cn, e = exp(lpd - m), mix_n = sum_c w_c e_cn and R = e / mix: row_score = m + log mix, score its mean,
+    grad_c the mean of R_cn, hess_ab the mean of R_an R_bn over the used rows.  A used row with mix_n = 0 makes the score -inf.
+    The any-device form of Engine.stack_eval, with its signature (``max_rows_per_tile`` means nothing here)."""
+    outputs = tuple(outputs)
+    if not outputs or any(k not in _STACK_OUTPUTS for k in outputs):
+        raise ValueError(f'outputs: a non-empty choice of {_STACK_OUTPUTS}')
+    l = torch.as_tensor(lpd).to(torch.float64)
+    if l.ndim != 2:
+        raise ValueError('lpd must be [C, N]')
+    w = torch.as_tensor(w).to(device=l.device, dtype=torch.float64).reshape(-1)
+    if w.shape != (l.shape[0],):
+        raise ValueError('w must be [C]')
+    m = torch.where(torch.isnan(l), torch.full_like(l, -float('inf')), l).max(dim=0).values
+    ok = ~(torch.isnan(l) | (l == float('inf'))).any(dim=0) & (m > -float('inf'))
+    lu, mu = l[:, ok], m[ok]
+    used = int(lu.shape[1])
+    e = torch.exp(lu - mu[None])
+    mix = (w[:, None] * e).sum(dim=0)
+    res = {}
+    if 'row_score' in outputs:
+        res['row_score'] = torch.full((l.shape[1],), float('nan'), dtype=torch.float64, device=l.device)
+        res['row_score'][ok] = mu + torch.log(mix)
+    if 'used' in outputs:
+        res['used'] = torch.tensor(used, dtype=torch.int64, device=l.device)
+    if 'score' in outputs:
+        res['score'] = (mu + torch.log(mix)).sum() / used if used else torch.tensor(float('nan'), dtype=torch.float64, device=l.device)
+    if 'grad' in outputs or 'hess' in outputs:
+        R = e / mix[None]
+        if 'grad' in outputs:
+            res['grad'] = R.sum(dim=1) / used if used else torch.full_like(w, float('nan'))
+        if 'hess' in outputs:
+            h = (R @ R.t()) / used if used else torch.full((l.shape[0],) * 2, float('nan'), dtype=torch.float64, device=l.device)
+            res['hess'] = torch.tril(h) + torch.tril(h, -1).t()
+    return res
+
+
+def _stack_qp(H, g, w):
+    """min over y >= 0 of 1/2 y'Hy + (1 - g - Hw)'y by an active-set method from y = w (fp64 NumPy): the free set starts as the
+    positive entries, a ridge 1e-12 I steadies the free block, a negative component of the free block's solution moves y to
+    the boundary and binds the blocking entry, and at a feasible solution the bound entry with the most negative multiplier
+    is released.  (Kim, Carbonetto, Stephens & Anitescu 2020, the subproblem of mix-SQP.)"""
+    import numpy as np
+    C = w.shape[0]
+    q = 1.0 - g - H @ w
+    y = w.copy()
+    free = y > 0
+    for _ in range(4 * C + 16):
+        F = np.flatnonzero(free)
+        z = np.zeros(C)
+        if F.size:
+            z[F] = np.linalg.solve(H[np.ix_(F, F)] + 1e-12 * np.eye(F.size), -q[F])
+        if F.size and (z[F] < 0).any():
+            d = z - y
+            neg = F[z[F] < 0]
+            ratio = y[neg] / np.maximum(y[neg] - z[neg], 1e-300)
+            k = int(np.argmin(ratio))
+            y = np.maximum(y + float(ratio[k]) * d, 0.0)
+            y[neg[k]] = 0.0
+            free[neg[k]] = False
+            y[~free] = 0.0
+            continue
+        y = z
+        lam = H @ y + q
+        lam[free] = 0.0
+        k = int(np.argmin(lam))
+        if lam[k] >= -1e-12:
+            break
+        free[k] = True
+    return y
+
+
+def stacking_weights(lpd, tol: float = 1e-8, max_iter: int = 50, eval=None, w0=None) -> dict:
+    """The stacking weights of chains with pointwise leave-one-out log densities lpd [C, N] (Engine.chain_loo_stream's
+    ``elpd_loo``): the w on the simplex that maximise the mean log score of the weighted mixture, by Newton steps on
+    phi(w) = -score(w) + sum(w) over w >= 0 (whose minimiser sums to 1), each from the active-set QP of ``_stack_qp`` on the
+    gradient and Hessian that ``eval`` returns -- Engine.stack_eval for the kernels, None for ``stack_eval_dense`` -- followed
+    by a backtracking line search (t halved from 1, score-only evaluations of w + t p clipped at 0, Armijo constant 1e-4 on phi,
+    a non-finite score rejects the step) and a renormalisation to sum 1.  From w0 (None: 1 / C).
+    Stops when gap = max_c grad_c - 1 <= tol: by concavity score(w*) - score(w) <= gap, so ``gap`` certifies the value returned.
+    Returns ``w`` [C] (fp64 NumPy), ``score``, ``gap``, ``iterations`` (Newton steps), ``score_evals`` (line-search
+    evaluations), ``converged`` and ``used``; reaching ``max_iter``, or a step the line search cannot place, returns
+    ``converged`` False with the gap of the last evaluation, never an exception."""
+    import numpy as np
+    ev = stack_eval_dense if eval is None else eval
+    if not isinstance(lpd, torch.Tensor):
+        lpd = torch.as_tensor(np.asarray(lpd, dtype=np.float64))
+    C = int(lpd.shape[0])
+    w = np.full(C, 1.0 / C) if w0 is None else np.asarray(w0, dtype=np.float64).reshape(-1).copy()
+    host = lambda t: t.detach().cpu().numpy().astype(np.float64)
+    iters = score_evals = 0
+    while True:
+        r = ev(lpd, torch.from_numpy(w), outputs=('score', 'grad', 'hess', 'used'))
+        score, used = float(r['score']), int(r['used'])
+        if not math.isfinite(score):
+            return {'w': w, 'score': score, 'gap': float('inf'), 'iterations': iters, 'score_evals': score_evals, 'converged': False,
+                    'used': used}
+        g, H = host(r['grad']), host(r['hess'])
+        gap = float(g.max() - 1.0)
+        if gap <= tol or iters >= max_iter:
+            return {'w': w, 'score': score, 'gap': gap, 'iterations': iters, 'score_evals': score_evals, 'converged': gap <= tol,
+                    'used': used}
+        p = _stack_qp(H, g, w) - w
+        slope = float((1.0 - g) @ p)
+        phi0 = -score + w.sum()
+        t, placed = 1.0, False
+        for _ in range(60):
+            wt = np.maximum(w + t * p, 0.0)
+            st = float(ev(lpd, torch.from_numpy(wt), outputs=('score',))['score'])
+            score_evals += 1
+            if math.isfinite(st) and -st + wt.sum() <= phi0 + 1e-4 * t * slope:
+                placed = True
+                break
+            t *= 0.5
+        if not placed or not (wt.sum() > 0) or np.array_equal(wt / wt.sum(), w):
+            return {'w': w, 'score': score, 'gap': gap, 'iterations': iters, 'score_evals': score_evals, 'converged': False,
+                    'used': used}
+        w = wt / wt.sum()
+        iters += 1
+
+
+def weighted_lppd(lpd_test, w, eval=None) -> float:
+    """The mean over the used rows of log sum_c w_c exp(lpd_test[c, n]): the score of ``stack_eval_dense`` (``eval`` as for
+    ``stacking_weights``) at fixed w.  With w = 1 / C and per-chain LPPD rows it is the ensemble's LPPD."""
+    ev = stack_eval_dense if eval is None else eval
+    return float(ev(lpd_test, torch.as_tensor(w, dtype=torch.float64), outputs=('score',))['score'])
+
+
+def stacking_summary(rows: dict) -> dict:
+    """Per chain, from per-chain PSIS-LOO arrays [C, N] (Engine.chain_loo_stream), on the host in fp64: ``chain_elpd_loo`` the
+    sum over the rows of elpd_loo (NaN rows left out, ``chain_rows_nan`` counting them) and ``chain_khat_bad`` the rows with a
+    finite khat > 0.7; ``n_rows``."""
+    import numpy as np
+    a = {k: (rows[k].detach().cpu().numpy() if isinstance(rows[k], torch.Tensor) else np.asarray(rows[k])).astype(np.float64)
+         for k in ('elpd_loo', 'khat')}
+    with np.errstate(invalid='ignore'):
+        return {'chain_elpd_loo': [float(v) for v in np.nansum(a['elpd_loo'], axis=1)],
+                'chain_rows_nan': [int(v) for v in np.isnan(a['elpd_loo']).sum(axis=1)],
+                'chain_khat_bad': [int(v) for v in (np.isfinite(a['khat']) & (a['khat'] > 0.7)).sum(axis=1)],
+                'n_rows': int(a['elpd_loo'].shape[1])}
