@@ -11,9 +11,9 @@
 //   dW        dW_l (+)= H_{l-1}^T dZ_l                      A = H_{l-1} read transposed,  B = dZ_l [rows][out]; K = data rows
 // (src/flax_building_blocks/basic.py:42-61; the likelihood head and its skinny products are k_wide_head.)
 //
-// Arithmetic: every fp32 operand is the exact sum of three bf16 terms (top / middle / bottom 8 significand bits); a product
+// Arithmetic: every fp32 operand is the exact sum of three bf16 terms (x rounded, the residual rounded, the exact rest); a product
 // a.b is accumulated in fp32 from the six bf16 MFMA products a3b1 a1b3 a2b2 a2b1 a1b2 a1b1 (the three dropped ones are
-// below 2^-23 of a1b1) -- the scheme of k_grad_w64<.., SPLIT>, 3/8 of the fp32-MFMA time at fp32 accuracy.
+// below 2^-25 of a1b1, of either sign) -- the scheme of k_grad_w64<.., SPLIT>, 3/8 of the fp32-MFMA time at fp32 accuracy.
 // Here the split is paid once per operand element per workgroup tile and reused by 128 output columns / rows, and the
 // weights arrive pre-split (k_wide_prep_weights), so it is a few % of the MFMA time instead of half of it.
 // TERMS = 1 gives the bf16-operand form (one product, operands rounded to nearest-even) for callers that ask for it.
@@ -56,7 +56,8 @@ typedef uint32_t mm_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint32_t mm_hi16_pair(float x1, float x0) {   // {bf16 bits of x1 : bf16 bits of x0}, truncating
   return __builtin_amdgcn_perm(__float_as_uint(x1), __float_as_uint(x0), 0x07060302u);
 }
-__device__ __forceinline__ float mm_trunc(float x) { return __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
+__device__ __forceinline__ float mm_lo16(uint32_t pk) { return __uint_as_float(pk << 16); }          // low bf16 of a pair, as fp32
+__device__ __forceinline__ float mm_hi16(uint32_t pk) { return __uint_as_float(pk & 0xffff0000u); }  // high bf16 of a pair
 #ifndef MILE_SPLIT_DOT2
 #define MILE_SPLIT_DOT2 0
 #endif
@@ -83,15 +84,19 @@ __device__ __forceinline__ void mm_split4(const f32x4 x, mm_u32x2 (&pk)[TERMS]) 
     pk[2] = pk[0];
     return;
 #endif
-    pk[0] = mm_u32x2{mm_hi16_pair(x[1], x[0]), mm_hi16_pair(x[3], x[2])};
+    // The first two terms are ROUNDED to nearest even (v_cvt_pk_bf16_f32), the residuals are exact, and the third term holds what
+    // is left (<= 8 bits: exact).  With truncated terms every residual carries the sign of x, so the dropped products a2 b3,
+    // a3 b2, a3 b3 all carry the sign of a b and add up over a sum of same-signed products instead of averaging out
+    // (tests/test_gpu_wide_schedule.py, kzoo-32); rounded terms halve each residual and leave its sign free.
+    pk[0] = __builtin_bit_cast(mm_u32x2, __builtin_convertvector(x, bf16x4));
 #if MILE_SPLIT_DOT2   // residuals from the packed term, one v_dot2c_f32_bf16 per element (mile_grad_w64.h, split3_pk)
     const f32x4 r = {mm_sub_lo(pk[0][0], x[0]), mm_sub_hi(pk[0][0], x[1]), mm_sub_lo(pk[0][1], x[2]), mm_sub_hi(pk[0][1], x[3])};
-    pk[1] = mm_u32x2{mm_hi16_pair(r[1], r[0]), mm_hi16_pair(r[3], r[2])};
+    pk[1] = __builtin_bit_cast(mm_u32x2, __builtin_convertvector(r, bf16x4));
     const f32x4 q = {mm_sub_lo(pk[1][0], r[0]), mm_sub_hi(pk[1][0], r[1]), mm_sub_lo(pk[1][1], r[2]), mm_sub_hi(pk[1][1], r[3])};
 #else
-    const f32x4 r = {x[0] - mm_trunc(x[0]), x[1] - mm_trunc(x[1]), x[2] - mm_trunc(x[2]), x[3] - mm_trunc(x[3])};
-    pk[1] = mm_u32x2{mm_hi16_pair(r[1], r[0]), mm_hi16_pair(r[3], r[2])};
-    const f32x4 q = {r[0] - mm_trunc(r[0]), r[1] - mm_trunc(r[1]), r[2] - mm_trunc(r[2]), r[3] - mm_trunc(r[3])};
+    const f32x4 r = {x[0] - mm_lo16(pk[0][0]), x[1] - mm_hi16(pk[0][0]), x[2] - mm_lo16(pk[0][1]), x[3] - mm_hi16(pk[0][1])};
+    pk[1] = __builtin_bit_cast(mm_u32x2, __builtin_convertvector(r, bf16x4));
+    const f32x4 q = {r[0] - mm_lo16(pk[1][0]), r[1] - mm_hi16(pk[1][0]), r[2] - mm_lo16(pk[1][1]), r[3] - mm_hi16(pk[1][1])};
 #endif
     pk[2] = mm_u32x2{mm_hi16_pair(q[1], q[0]), mm_hi16_pair(q[3], q[2])};
   }
@@ -578,10 +583,12 @@ __global__ __launch_bounds__(256) void k_wide_prep_weights(const float *theta, l
     if constexpr (TERMS == 1) {
       o[idx] = (bf16)x;
     } else {
-      const float x1 = mm_trunc(x), r1 = x - x1, x2 = mm_trunc(r1), x3 = r1 - x2;
-      o[idx] = __builtin_bit_cast(bf16, (uint16_t)(__float_as_uint(x1) >> 16));
-      o[plane + idx] = __builtin_bit_cast(bf16, (uint16_t)(__float_as_uint(x2) >> 16));
-      o[2 * plane + idx] = __builtin_bit_cast(bf16, (uint16_t)(__float_as_uint(x3) >> 16));
+      const bf16 b1 = (bf16)x;                              // as mm_split4: two rounded terms, the exact rest
+      const float r1 = x - (float)b1;
+      const bf16 b2 = (bf16)r1;
+      o[idx] = b1;
+      o[plane + idx] = b2;
+      o[2 * plane + idx] = (bf16)(r1 - (float)b2);
     }
   }
 }
