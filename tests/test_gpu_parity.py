@@ -355,8 +355,10 @@ def test_steps_match_oracle_explicit_noise(oracle, kernel, refresh):
 
 @pytest.mark.parametrize('per_call', [1, 3])
 def test_steps_match_oracle_beyond_the_register_cached_update(oracle, per_call):
-    """d > 16384 floats takes the two-pass update kernel (k_update) instead of k_update_fast; one-step calls
-    are what the host-driven tuner issues for such nets."""
+    """d > 16384 floats is beyond k_update_fast.  With explicit noise the start and record launches of d = 17922 run k_update_seg
+    (the two-pass k_update<false> under MILE_NO_UPD_SEG): launch_update_big refuses a launch that carries explicit noise.  The
+    mid-step launch has no O-step, carries none and runs k_update_big.  One-step calls are what the host-driven tuner issues for
+    such nets.  (tests/test_gpu_update_schedule.py holds each of these kernels to the oracle per schedule cell.)"""
     ospec = oracle.ModelSpec(9, (128, 128, 2))
     assert ospec.n_params > 16384
     N, E, T = 80, 3, 6
