@@ -96,11 +96,16 @@ typedef enum mile_grad_kernel {
                                      workgroup's own slab row; T <= 128, C <= 192, D <= 128 with H | D, <= 2 projections of
                                      width <= 128, n_classes <= 16, and <= 160 KB of LDS per workgroup (q|k|v [Tp][3D] + e
                                      [Tp][C] + vectors: e.g. C = 192, D = 64 needs T <= 96) */
-  MILE_GRAD_ATTN_WIDE_F32 = 14    /* MILE_MODEL_ATTN_WIDE only (and its only kernel; AUTO resolves to it): k_grad_attn_wide
+  MILE_GRAD_ATTN_WIDE_F32 = 14,   /* MILE_MODEL_ATTN_WIDE only (and its only kernel; AUTO resolves to it): k_grad_attn_wide
                                      (mile_attn_wide.h), the ATTN_PRE_F32 kernel with the tables read from the chain's own
                                      parameters and their gradient added (dPos by owner threads, dEmb by fp32 vector atomics
                                      into the slab row's own [V][C] block); the same envelope and LDS as ATTN_PRE_F32.  Its
                                      row ranges are sized for that block (4 V C bytes per slab row), see mile_reserve */
+  MILE_GRAD_LENET_BF16X3 = 15     /* MILE_MODEL_LENET, <= 4 image channels: LENET_BF16 with its five convolution products made
+                                     fp32-faithful -- input, dZ and kernel operands as exact three-term bf16 splits (three term
+                                     planes per LDS tile), six v_mfma_f32_16x16x32_bf16 products per accumulator, smallest first;
+                                     the error against fp64 of the fp32 kernels and no library kernel.  Images whose three
+                                     planes do not fit 150 KB of LDS are refused at the first gradient; explicit only */
 } mile_grad_kernel;
 /* Which network: the FCN (src/models/tabular/fcn.py:16-28), LeNet (src/models/images/cnns.py:10-66), LeNetti
  * (src/models/images/cnns.py:69-121), AttentionClassifier (src/models/text/attention_classifier.py) or

@@ -15,7 +15,7 @@ PRIOR_IDS = {'Normal': 0, 'StandardNormal': 0, 'Laplace': 1}
 REFRESH_IDS = {'O-step-O': 0, 'step-O': 1}
 GRAD_KERNEL_IDS = {'auto': 0, 'generic': 1, 'mfma_w64': 2, 'mfma_w128_bf16': 3, 'gemm_f32': 4, 'lenet_f32': 5, 'mfma_w64_bf16x3': 6,
                    'mfma_wide_bf16x3': 7, 'mfma_wide_bf16': 8, 'lenet_bf16': 9, 'mfma_narrow_f32': 10,
-                   'lenetti_f32': 11, 'attn_f32': 12, 'attn_pre_f32': 13, 'attn_wide_f32': 14}
+                   'lenetti_f32': 11, 'attn_f32': 12, 'attn_pre_f32': 13, 'attn_wide_f32': 14, 'lenet_bf16x3': 15}
 DIAG_BITS = {'wcv': 1, 'bcv': 2, 'ess': 4, 'crhat': 8, 'rhat': 16, 'pooled_input': 32}     # MILE_DIAG_*
 DIAG_S_MIN, DIAG_S_MAX, DIAG_POOL_MAX = 4, 4096, 16384
 MODEL_IDS = {'fcn': 0, 'lenet': 1, 'lenetti': 2, 'attn': 3, 'attn_pretrained': 4, 'attn_wide': 5}

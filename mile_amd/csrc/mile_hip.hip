@@ -136,7 +136,7 @@ static bool is_attn_wide(const mile_sampler *s) { return s->spec.model == MILE_M
 // every call that evaluates the likelihood refuses a pretrained-attention sampler whose tables are not set
 static bool tables_missing(const mile_sampler *s) { return is_attn_pre(s) && !s->emb_tab; }
 static const char *const kNoTables = "PretrainedAttentionClassifier: call mile_set_embedding first";
-static bool lenet_bf16_supported(const mile_sampler *s) { return is_lenet(s) && s->lg.C <= 4; }
+static bool lenet_bf16_supported(const mile_sampler *s) { return is_lenet(s) && s->lg.C <= 4; }   // LENET_BF16 and LENET_BF16X3
 
 // k_grad_w64 / k_grad_w128b: ReLU regression, 1-3 hidden layers of the kernel's width, F <= 16
 static bool relu_regression_of_width(const mile_sampler *s, int width) {
@@ -798,7 +798,7 @@ int32_t mile_reserve(mile_sampler *s, int32_t E) {
   HIP_TRY(hipSetDevice(s->device));
   // capacity must cover whichever grad kernel is selected later
   int S = 1;   // (only the kernels that run this model: GENERIC's 64 ranges would double the wide attention's 2 GB)
-  for (int k = MILE_GRAD_GENERIC; k <= MILE_GRAD_ATTN_WIDE_F32; ++k)
+  for (int k = MILE_GRAD_GENERIC; k <= MILE_GRAD_LENET_BF16X3; ++k)
     if (grad_kernel(k).supports(s)) S = std::max(S, choose_S(s, E, k));
   if (is_attn_wide(s)) S = std::max(S, attn_wide_S_rows(s, E, s->N));   // whatever row window is set now
   // A smaller ensemble splits the rows of a particle over MORE workgroups (S grows as E shrinks): capacity is counted in
@@ -826,7 +826,7 @@ int32_t mile_reserve(mile_sampler *s, int32_t E) {
 
 int32_t mile_set_grad_kernel(mile_sampler *s, int32_t which) {
   if (!s) return fail(MILE_ERR_INVALID, "null handle");
-  if (which < MILE_GRAD_AUTO || which > MILE_GRAD_ATTN_WIDE_F32) return fail(MILE_ERR_INVALID, "unknown grad kernel");
+  if (which < MILE_GRAD_AUTO || which > MILE_GRAD_LENET_BF16X3) return fail(MILE_ERR_INVALID, "unknown grad kernel");
   if (which != MILE_GRAD_AUTO) {
     const GradKernel &k = grad_kernel(which);
     if (!k.supports(s)) return fail(MILE_ERR_INVALID, k.refusal);
@@ -1031,14 +1031,20 @@ __global__ void k_fill(float *p, float v, int n) {
 // out_ll != nullptr: evaluation, per-row log-likelihoods out_ll[(s0 + e) * N + r]; otherwise the gradient goes
 // to slab[e * dp + offset] and the log-likelihood sums to llacc[e].
 // Dense half of LeNet on the hand-written MFMA GEMMs (k_mm3 with fp32-faithful three-term products; defined below the k_mm3
-// launchers): LENET_BF16 uses no library kernel.  lenet_dense_prep once per gradient, lenet_dense_chunk per image chunk.
+// launchers): LENET_BF16 / LENET_BF16X3 use no library kernel.  lenet_dense_prep once per gradient, lenet_dense_chunk per image chunk.
 struct LeNetDenseBufs { const float *p2; float *f1, *f2, *out, *df2, *df1, *dp2; };
 static int lenet_dense_prep(mile_sampler *s, const float *theta, int E, hipStream_t st);
 static int lenet_dense_chunk(mile_sampler *s, const float *theta, int E, int Rc, int r0, int chunk, const LeNetDenseBufs &b, const void *y,
                              float *slab, long long dp, float *llacc, float *out_ll, long long Ntot, long long s0, hipStream_t st);
 
+// the convolution products: fp32 VALU kernels (mile_lenet.h) / bf16-rounded operands on the matrix pipe / exact three-term
+// bf16 splits of both operands and six MFMA products (fp32-faithful), mile_lenet_mfma.h
+enum { LENET_CONV_F32 = 0, LENET_CONV_BF16 = 1, LENET_CONV_BF16X3 = 2 };
+// images per barrier pair of the MFMA convolution kernels: as many as keep the tiles (all term planes) under ~56 KB, at most 4
+static int lenet_ni_for(size_t per_img, int terms) { return std::max(1, std::min(4, (int)(57344 / (terms * per_img)))); }
 static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X, const void *y, int N, float *slab, long long dp,
-                     float *llacc, float *out_ll, long long s0, hipStream_t st, bool mfma = false) {
+                     float *llacc, float *out_ll, long long s0, hipStream_t st, int mode = LENET_CONV_F32) {
+  const bool mfma = mode != LENET_CONV_F32, x3 = mode == LENET_CONV_BF16X3;
   if (!rocblas_load()) return fail(MILE_ERR_HIP, "librocblas.so could not be loaded");
   const LeNetGeom &g = s->lg;
   const int d = g.d, act = s->ds.activation, task = s->ds.task;
@@ -1062,19 +1068,22 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
   const bool direct = getenv("MILE_LENET_GEMM") == nullptr && g.C <= 16 && lds_max <= 150 * 1024;
   // MILE_GRAD_LENET_BF16: the five convolution launches on the bf16 matrix pipe (mile_lenet_mfma.h), everything else as below
   // small images: several per barrier pair (as many as keep the tiles under ~56 KB, at most 4)
-  const auto ni_for = [](size_t per_img) { return std::max(1, std::min(4, (int)(57344 / per_img))); };
+  const int terms = x3 ? 3 : 1;   // LENET_BF16X3: every tile once per term plane, so fewer images per barrier pair
+  const auto ni_for = [terms](size_t per_img) { return lenet_ni_for(per_img, terms); };
   const int ni2 = ni_for((size_t)(g.hp1 * g.wp1 + 8) * 16 + (size_t)g.h2 * g.w2 * 32);   // input tile + dZ rows of one image
   const int ni_x2 = ni_for((size_t)((g.h2 + 8) * (g.w2 + 8) + 8) * 32), ni_f1 = ni_for((size_t)((g.H + 4) * (g.W + 4) + 8) * 8);
   // the 6-channel sides of the two convolutions in the PAIR forms (two pixels per MFMA row / column)
-  const size_t ldm_f1p = cm_lds_fwd(CM_IN4, g.H, g.W, 2, g.C, 6, ni_f1), ldm_f2 = cm_lds_fwd(CM_IN8, g.hp1, g.wp1, 0, 6, 16, ni2);
-  const size_t ldm_x2p = cm_lds_dx2x(g.h2, g.w2, 6, 16, ni_x2), ldm_w1p = cm_lds_dw2x(g.H, g.W, 2), ldm_w2 = cm_lds_dw(CM_IN8, g.hp1, g.wp1, 0, ni2);
+  const size_t ldm_f1p = cm_lds_fwd(CM_IN4, g.H, g.W, 2, g.C, 6, ni_f1, terms), ldm_f2 = cm_lds_fwd(CM_IN8, g.hp1, g.wp1, 0, 6, 16, ni2, terms);
+  const size_t ldm_x2p = cm_lds_dx2x(g.h2, g.w2, 6, 16, ni_x2, terms), ldm_w1p = cm_lds_dw2x(g.H, g.W, 2, terms);
+  const size_t ldm_w2 = cm_lds_dw(CM_IN8, g.hp1, g.wp1, 0, ni2, terms);
   // ldm_w1 (conv1's kernel gradient in the pixel form, no longer built) exceeds ldm_w1p: kept in the check so that the same
   // images are refused as when the pixel forms could be selected.  Their other two sizes never exceed ldm_f1p and ldm_x2p.
   const size_t ldm_w1 = cm_lds_dw(CM_IN4, g.H, g.W, 2);
   // ReLU: the full-size conv activations are kept for the backward pass only as two-byte "was it positive" values
   const int a16 = mfma && act == MILE_ACT_RELU;
   if (mfma && (!direct || g.C > 4 || std::max({ldm_f1p, ldm_f2, ldm_x2p, ldm_w1, ldm_w1p, ldm_w2}) > 150 * 1024))
-    return fail(MILE_ERR_INVALID, "LENET_BF16 needs <= 4 image channels and an image that fits the LDS tiles");
+    return fail(MILE_ERR_INVALID, x3 ? "LENET_BF16X3 needs <= 4 image channels and an image whose three term planes fit the LDS tiles"
+                                     : "LENET_BF16 needs <= 4 image channels and an image that fits the LDS tiles");
   // Dense activations: exact widths on the rocBLAS path; k_mm3 wants rows of 8 k floats (zero padding columns)
   const size_t w_f2 = mfma ? 88 : 84, w_out = mfma ? (size_t)(g.K + 7) / 8 * 8 : (size_t)g.K;
   size_t per = n_a1 + n_p1 + (direct ? 0 : n_col2) + n_a2 + n_p2 + 120 + w_f2 + w_out;
@@ -1113,6 +1122,11 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
     HIP_TRY((mile_set_max_lds<k_conv5m_fwd2x<6>>(150 * 1024)));
     HIP_TRY((mile_set_max_lds<k_conv5m_dx2x<6, 16>>(150 * 1024)));
     HIP_TRY((mile_set_max_lds<k_conv5m_dw2x<6>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5m_fwd<CM_IN8, 16, 3>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5m_dw<CM_IN8, 16, 3>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5m_fwd2x<6, 3>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5m_dx2x<6, 16, 3>>(150 * 1024)));
+    HIP_TRY((mile_set_max_lds<k_conv5m_dw2x<6, 3>>(150 * 1024)));
   }
   const float one = 1.0f, zero = 0.0f;
   auto blocks = [](long long n) { return (unsigned)std::min<long long>((n + 255) / 256, 65535); };
@@ -1140,10 +1154,12 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
 #define LAUNCH_FWD1(GEO_) k_conv5_fwd<6, GEO_><<<dim3(nwg, E), 256, lds_f1, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, theta, g.k_c1, g.b_c1, d, a1, (int)Rc, ipw, act)
 #define LAUNCH_FWD2(GEO_) k_conv5_fwd<16, GEO_><<<dim3(nwg, E), 256, lds_f2, st>>>(p1, Rc * (long long)n_p1, (long long)n_p1, g.wp1 * 6, 6, 1, 6, g.hp1, g.wp1, 0, theta, g.k_c2, g.b_c2, d, a2, (int)Rc, ipw, act)
       // MFMA form: the pooled activations come out of the convolution's own epilogue; evaluation skips the full-size ones
-      if (mfma) k_conv5m_fwd2x<6><<<dim3(nwg, E), 256, ldm_f1p, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, theta, g.k_c1, g.b_c1, d, grad ? a1 : nullptr, p1, (int)Rc, ipw, act, a16, ni_f1);
+      if (x3) k_conv5m_fwd2x<6, 3><<<dim3(nwg, E), 256, ldm_f1p, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, theta, g.k_c1, g.b_c1, d, grad ? a1 : nullptr, p1, (int)Rc, ipw, act, a16, ni_f1);
+      else if (mfma) k_conv5m_fwd2x<6><<<dim3(nwg, E), 256, ldm_f1p, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, theta, g.k_c1, g.b_c1, d, grad ? a1 : nullptr, p1, (int)Rc, ipw, act, a16, ni_f1);
       else if (geo == 1) LAUNCH_FWD1(1); else if (geo == 3) LAUNCH_FWD1(3); else LAUNCH_FWD1(0);
       if (!mfma) k_avgpool2<<<blocks(B * (long long)n_p1), 256, 0, st>>>(a1, p1, B, g.H, g.W, 6);
-      if (mfma) k_conv5m_fwd<CM_IN8, 16><<<dim3(nwg, E), 256, ldm_f2, st>>>(p1, Rc * (long long)n_p1, (long long)n_p1, g.wp1 * 6, 6, 1, 6, g.hp1, g.wp1, 0, theta, g.k_c2, g.b_c2, d, grad ? a2 : nullptr, p2, (int)Rc, ipw, act, a16, ni2);
+      if (x3) k_conv5m_fwd<CM_IN8, 16, 3><<<dim3(nwg, E), 256, ldm_f2, st>>>(p1, Rc * (long long)n_p1, (long long)n_p1, g.wp1 * 6, 6, 1, 6, g.hp1, g.wp1, 0, theta, g.k_c2, g.b_c2, d, grad ? a2 : nullptr, p2, (int)Rc, ipw, act, a16, ni2);
+      else if (mfma) k_conv5m_fwd<CM_IN8, 16><<<dim3(nwg, E), 256, ldm_f2, st>>>(p1, Rc * (long long)n_p1, (long long)n_p1, g.wp1 * 6, 6, 1, 6, g.hp1, g.wp1, 0, theta, g.k_c2, g.b_c2, d, grad ? a2 : nullptr, p2, (int)Rc, ipw, act, a16, ni2);
       else if (geo == 1) LAUNCH_FWD2(2); else if (geo == 3) LAUNCH_FWD2(4); else LAUNCH_FWD2(0);
 #undef LAUNCH_FWD1
 #undef LAUNCH_FWD2
@@ -1210,12 +1226,15 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
 #define LAUNCH_DW2(GEO_) k_conv5_dw<16, GEO_><<<dim3(nwg, E), 256, lds_w2, st>>>(p1, Rc * (long long)n_p1, (long long)n_p1, g.wp1 * 6, 6, 1, 6, g.hp1, g.wp1, 0, dp2, a2, act, part2, (int)Rc, ipw)
 #define LAUNCH_DX(HO_, WO_) k_conv5_dx<6, 16, 1, HO_, WO_><<<dim3(nwg, E), 256, lds_x2, st>>>(dp2, a2, act, theta, g.k_c2, d, dp1, (int)Rc, g.h2, g.w2, ipw)
 #define LAUNCH_DW1(GEO_) k_conv5_dw<6, GEO_><<<dim3(nwg, E), 256, lds_w1, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, dp1, a1, act, part1, (int)Rc, ipw)
-      if (mfma) k_conv5m_dw<CM_IN8, 16><<<dim3(nwg, E), 256, ldm_w2, st>>>(p1, Rc * (long long)n_p1, (long long)n_p1, g.wp1 * 6, 6, 1, 6, g.hp1, g.wp1, 0, dp2, a2, act, part2, (int)Rc, ipw, a16, ni2);
+      if (x3) k_conv5m_dw<CM_IN8, 16, 3><<<dim3(nwg, E), 256, ldm_w2, st>>>(p1, Rc * (long long)n_p1, (long long)n_p1, g.wp1 * 6, 6, 1, 6, g.hp1, g.wp1, 0, dp2, a2, act, part2, (int)Rc, ipw, a16, ni2);
+      else if (mfma) k_conv5m_dw<CM_IN8, 16><<<dim3(nwg, E), 256, ldm_w2, st>>>(p1, Rc * (long long)n_p1, (long long)n_p1, g.wp1 * 6, 6, 1, 6, g.hp1, g.wp1, 0, dp2, a2, act, part2, (int)Rc, ipw, a16, ni2);
       else if (geo == 1) LAUNCH_DW2(2); else if (geo == 3) LAUNCH_DW2(4); else LAUNCH_DW2(0);
       k_conv_reduce<<<dim3(10, E), 256, 0, st>>>(part2, (int)nwg, 2400, 16, slab, dp, g.k_c2, g.b_c2, acc);
-      if (mfma) k_conv5m_dx2x<6, 16><<<dim3(nwg, E), 256, ldm_x2p, st>>>(dp2, a2, act, theta, g.k_c2, d, dp1, (int)Rc, g.h2, g.w2, ipw, a16, ni_x2);
+      if (x3) k_conv5m_dx2x<6, 16, 3><<<dim3(nwg, E), 256, ldm_x2p, st>>>(dp2, a2, act, theta, g.k_c2, d, dp1, (int)Rc, g.h2, g.w2, ipw, a16, ni_x2);
+      else if (mfma) k_conv5m_dx2x<6, 16><<<dim3(nwg, E), 256, ldm_x2p, st>>>(dp2, a2, act, theta, g.k_c2, d, dp1, (int)Rc, g.h2, g.w2, ipw, a16, ni_x2);
       else if (geo == 1) LAUNCH_DX(12, 12); else if (geo == 3) LAUNCH_DX(10, 10); else LAUNCH_DX(0, 0);
-      if (mfma) k_conv5m_dw2x<6><<<dim3(nwg, E), 256, ldm_w1p, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, dp1, a1, act, part1, (int)Rc, ipw, a16);
+      if (x3) k_conv5m_dw2x<6, 3><<<dim3(nwg, E), 256, ldm_w1p, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, dp1, a1, act, part1, (int)Rc, ipw, a16);
+      else if (mfma) k_conv5m_dw2x<6><<<dim3(nwg, E), 256, ldm_w1p, st>>>(Xc, 0, (long long)g.C * HW, g.W, 1, (long long)HW, g.C, g.H, g.W, 2, dp1, a1, act, part1, (int)Rc, ipw, a16);
       else if (geo == 1) LAUNCH_DW1(1); else if (geo == 3) LAUNCH_DW1(3); else LAUNCH_DW1(0);
 #undef LAUNCH_DW2
 #undef LAUNCH_DX
@@ -1677,9 +1696,9 @@ static int grad_lenetti(mile_sampler *s, const GradParams &gp, const W64Fuse &, 
   HIP_TRY(launch_lenetti(s, gp.theta, E, gp.X, gp.y, gp.N, gp.S, gp.dp, nullptr, st));
   return MILE_OK;
 }
-template <bool MFMA>
+template <int MODE>
 static int grad_lenet(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
-  return run_lenet(s, gp.theta, E, gp.X, gp.y, gp.N, gp.slabs, gp.dp, gp.llpart, nullptr, 0, st, MFMA);
+  return run_lenet(s, gp.theta, E, gp.X, gp.y, gp.N, gp.slabs, gp.dp, gp.llpart, nullptr, 0, st, MODE);
 }
 static int grad_gemm(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) { return launch_grad_gemm(s, gp, E, st); }
 static int grad_wide3(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) { return launch_grad_wide<3>(s, gp, E, st); }
@@ -2028,10 +2047,10 @@ static int loglik_lenetti(mile_sampler *s, PredParams pp, int S, hipStream_t st)
   HIP_TRY(launch_lenetti(s, pp.theta, S, pp.X, pp.y, pp.N, SB, 0, pp.out, st));
   return MILE_OK;
 }
-template <bool MFMA>
+template <int MODE>
 static int loglik_lenet(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
   for (int s0 = 0; s0 < S; s0 += 256) {
-    const int rc = run_lenet(s, pp.theta + (size_t)s0 * s->ds.d, std::min(256, S - s0), pp.X, pp.y, pp.N, nullptr, 0, nullptr, pp.out, s0, st, MFMA);
+    const int rc = run_lenet(s, pp.theta + (size_t)s0 * s->ds.d, std::min(256, S - s0), pp.X, pp.y, pp.N, nullptr, 0, nullptr, pp.out, s0, st, MODE);
     if (rc) return rc;
   }
   return MILE_OK;
@@ -2090,6 +2109,12 @@ static LaunchShape shape_attn_pre(const mile_sampler *s, int) { return {256, (in
 static LaunchShape shape_attn_wide(const mile_sampler *s, int) { return {256, (int)attn_wide_lds_bytes(s->ag)}; }
 static LaunchShape shape_lenetti(const mile_sampler *s, int) { return {256, (int)lenetti_lds_bytes(s->ng, lenetti_T(s->ng))}; }
 static LaunchShape shape_lenet_bf16(const mile_sampler *s, int) { return {256, (int)cm_lds_dw(CM_IN8, s->lg.hp1, s->lg.wp1, 0)}; }
+// the largest of the five launches at three term planes: conv2's kernel gradient, or (large images) conv1's
+static LaunchShape shape_lenet_bf16x3(const mile_sampler *s, int) {
+  const LeNetGeom &g = s->lg;
+  const int ni2 = lenet_ni_for((size_t)(g.hp1 * g.wp1 + 8) * 16 + (size_t)g.h2 * g.w2 * 32, 3);
+  return {256, (int)std::max(cm_lds_dw(CM_IN8, g.hp1, g.wp1, 0, ni2, 3), cm_lds_dw2x(g.H, g.W, 2, 3))};
+}
 static LaunchShape shape_rocblas(const mile_sampler *, int) { return {256, 0}; }
 template <int TERMS>
 static LaunchShape shape_wide(const mile_sampler *, int) { return {256, MMLayout<MM_A_MK, MM_B_T3_NK, TERMS, MILE_MM_KC>::BYTES}; }
@@ -2112,8 +2137,8 @@ static constexpr GradKernel kGrad[] = {
      "GEMM_F32 needs librocblas.so, which could not be loaded",
      one_S, false, false, grad_gemm, loglik_gemm, shape_rocblas},
     {MILE_GRAD_LENET_F32, "rocblas_sgemm_strided_batched+k_im2col5/k_col2im5/k_avgpool2", is_lenet,
-     "LENET_F32 / LENET_BF16 are the kernels of MILE_MODEL_LENET, and its only ones", nullptr,
-     one_S, true, false, grad_lenet<false>, loglik_lenet<false>, shape_rocblas},
+     "LENET_F32 / LENET_BF16 / LENET_BF16X3 are the kernels of MILE_MODEL_LENET, and its only ones", nullptr,
+     one_S, true, false, grad_lenet<LENET_CONV_F32>, loglik_lenet<LENET_CONV_F32>, shape_rocblas},
     {MILE_GRAD_MFMA_W64_BF16X3, "k_grad_w64", w64x3_supported,
      "MFMA_W64_BF16X3 needs ReLU regression with 2-3 hidden layers of width 64 and F <= 16", nullptr,
      w64_S, true, true, grad_w64x3, loglik_w64, shape_w64x3},
@@ -2123,7 +2148,7 @@ static constexpr GradKernel kGrad[] = {
      one_S, true, false, grad_wide1, loglik_wide, shape_wide<1>},
     {MILE_GRAD_LENET_BF16, "k_conv5m_fwd/dx/dw (implicit-GEMM bf16 MFMA) + k_mm3 (Dense, fp32-faithful three-term products)",
      lenet_bf16_supported, "LENET_BF16 is a kernel of MILE_MODEL_LENET and needs <= 4 image channels", nullptr,
-     one_S, true, false, grad_lenet<true>, loglik_lenet<true>, shape_lenet_bf16},
+     one_S, true, false, grad_lenet<LENET_CONV_BF16>, loglik_lenet<LENET_CONV_BF16>, shape_lenet_bf16},
     {MILE_GRAD_MFMA_NARROW_F32, "k_grad_narrow", narrow_supported,
      "MFMA_NARROW_F32 needs an FCN with 1-3 hidden layers of width <= 64 and F <= 64 (or 4-10 of width <= 16 and F <= 16) and <= 16 outputs",
      nullptr, narrow_S, true, false, grad_narrow, loglik_generic, shape_narrow},
@@ -2137,11 +2162,14 @@ static constexpr GradKernel kGrad[] = {
     {MILE_GRAD_ATTN_WIDE_F32, "k_grad_attn_wide", is_attn_wide,
      "ATTN_WIDE_F32 is the kernel of MILE_MODEL_ATTN_WIDE, and its only one", nullptr,
      attn_wide_S, true, false, grad_attn_wide, loglik_attn_t<launch_attn_wide>, shape_attn_wide},
+    {MILE_GRAD_LENET_BF16X3, "k_conv5m_fwd/dx/dw<.., 3> (implicit-GEMM bf16x3 MFMA: six products of three-term splits) + k_mm3 (Dense, the same)",
+     lenet_bf16_supported, "LENET_BF16X3 is a kernel of MILE_MODEL_LENET and needs <= 4 image channels", nullptr,
+     one_S, true, false, grad_lenet<LENET_CONV_BF16X3>, loglik_lenet<LENET_CONV_BF16X3>, shape_lenet_bf16x3},
 };
 static constexpr bool rows_in_id_order() {
   for (int k = 0; k < (int)(sizeof(kGrad) / sizeof(kGrad[0])); ++k)
     if (kGrad[k].id != k + 1) return false;
-  return sizeof(kGrad) / sizeof(kGrad[0]) == MILE_GRAD_ATTN_WIDE_F32;
+  return sizeof(kGrad) / sizeof(kGrad[0]) == MILE_GRAD_LENET_BF16X3;
 }
 static_assert(rows_in_id_order(), "kGrad: one row per MILE_GRAD_* id, in id order");
 static const GradKernel &grad_kernel(int kernel) { return kGrad[kernel - 1]; }

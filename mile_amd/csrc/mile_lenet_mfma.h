@@ -18,12 +18,18 @@
 // B[k = 8 (l >> 4) + j][col l & 15], D[row 4 (l >> 4) + reg][col l & 15].
 // Everything that is not a convolution product (bias, activation and its derivative, pooling, the Dense layers, the
 // likelihood) is the fp32 code of mile_lenet.h; dZ = unpool(dP) * act'(A) is formed while staging, as there.
+//
+// MILE_GRAD_LENET_BF16X3: the same kernels with TERMS = 3 -- every operand is the exact three-term bf16 split of its fp32 value
+// (mm_split4 of mile_mm3.h, taken where TERMS = 1 rounds), a tile is kept once per term ("term planes", the same slot layout, plane t
+// at + t * plane bytes) and every accumulator takes the six products a0 b2, a1 b1, a2 b0, a0 b1, a1 b0, a0 b0, smallest first:
+// fp32-faithful products on the bf16 pipe.  TERMS = 1 compiles to the code it was before the parameter.
 #pragma once
 #include <algorithm>
 #include <type_traits>
 
 #include "mile_bf16_frag.h"
 #include "mile_lenet.h"
+#include "mile_mm3.h"
 
 typedef float cm_f32x4 __attribute__((ext_vector_type(4)));
 typedef float cm_f32x2 __attribute__((ext_vector_type(2)));
@@ -114,9 +120,10 @@ template <> struct CSlot<CM_DZ16P> { // dZ tile, pair form: slot = (kh, kw' = -1
 // zero-padded bf16 input tile [Hp][Wp][PB / 2 channels] (+ 8 pixels of zero slack: the padded taps read past the last row).
 // U pixels per thread and pass with all their global loads issued before the first conversion: as a plain loop every
 // iteration waited out its own loads' latency (16 serial HBM round trips per image were most of the kernels' time).
-template <int MODE>
+// TERMS = 3: term plane t of the tile lies `plane` bytes behind plane t - 1 (same slot layout in every plane).
+template <int MODE, int TERMS = 1>
 __device__ __forceinline__ void cm_stage_input(char *tile, const float *src, long long sH, long long sW, long long sC, int CIN, int H, int W,
-                                               int pad, int tid) {
+                                               int pad, int tid, int plane = 0) {
   constexpr int CPX = CSlot<MODE>::PB / 2, U = 3;
   const int Hp = H + 2 * pad, Wp = W + 2 * pad, n = Hp * Wp + 8;
   const float inv_wp = 1.0f / (float)Wp;
@@ -145,7 +152,16 @@ __device__ __forceinline__ void cm_stage_input(char *tile, const float *src, lon
     for (int u = 0; u < U; ++u) {
       const int i = i0 + 256 * u;
       if (i >= n) continue;
-      if constexpr (CPX == 4) {
+      if constexpr (TERMS != 1) {
+        cm_u32x2 pa[TERMS], pb[TERMS];
+        mm_split4<TERMS>(cm_f32x4{v[u][0], v[u][1], v[u][2], v[u][3]}, pa);
+        if constexpr (CPX == 8) mm_split4<TERMS>(cm_f32x4{v[u][4], v[u][5], v[u][6], v[u][7]}, pb);
+#pragma unroll
+        for (int t = 0; t < TERMS; ++t) {
+          if constexpr (CPX == 4) *reinterpret_cast<cm_u32x2 *>(tile + t * plane + (size_t)i * 8) = pa[t];
+          else *reinterpret_cast<cm_u32x4 *>(tile + t * plane + (size_t)i * 16) = cm_u32x4{pa[t][0], pa[t][1], pb[t][0], pb[t][1]};
+        }
+      } else if constexpr (CPX == 4) {
         *reinterpret_cast<cm_u32x2 *>(tile + (size_t)i * 8) = cm_u32x2{cm_pack2(v[u][0], v[u][1]), cm_pack2(v[u][2], v[u][3])};
       } else {
         *reinterpret_cast<cm_u32x4 *>(tile + (size_t)i * 16) =
@@ -166,8 +182,9 @@ __device__ __forceinline__ void cm_stage_input(char *tile, const float *src, lon
 //   din[x + dxo][ci]  = sum_{kw'} dz[x - kw'] K[kw' + dxo][ci]            (kw' = -1..4, CM_DZ16P)
 // -- twice the useful MFMA rows (12 of 16 instead of 6) and half the tiles for the 6-channel sides of the two convolutions.
 enum { CK_FWD = 0, CK_FWD2 = 1, CK_DX2 = 2 };
-template <int MODE, int NMF, int KIND>
-__device__ __forceinline__ void cm_kernel_operand(const float *Kg, float *K, int CIN, int COUT, int tid, bf16x8 (&ka)[NMF]) {
+// TERMS = 3: ka[t] = term t of the exact three-term bf16 split of the gathered fp32 values (mm_split4).
+template <int MODE, int NMF, int KIND, int TERMS = 1>
+__device__ __forceinline__ void cm_kernel_operand(const float *Kg, float *K, int CIN, int COUT, int tid, bf16x8 (&ka)[TERMS][NMF]) {
   using G = CSlot<MODE>;
   for (int i = tid; i < 25 * CIN * COUT; i += 256) K[i] = Kg[i];
   __syncthreads();
@@ -193,8 +210,16 @@ __device__ __forceinline__ void cm_kernel_operand(const float *Kg, float *K, int
       }
       v[j] = ok ? K[idx] : 0.0f;
     }
-    const cm_u32x4 pk = {cm_pack2(v[0], v[1]), cm_pack2(v[2], v[3]), cm_pack2(v[4], v[5]), cm_pack2(v[6], v[7])};
-    ka[c] = __builtin_bit_cast(bf16x8, pk);
+    if constexpr (TERMS != 1) {
+      cm_u32x2 pa[TERMS], pb[TERMS];
+      mm_split4<TERMS>(cm_f32x4{v[0], v[1], v[2], v[3]}, pa);
+      mm_split4<TERMS>(cm_f32x4{v[4], v[5], v[6], v[7]}, pb);
+#pragma unroll
+      for (int t = 0; t < TERMS; ++t) ka[t][c] = __builtin_bit_cast(bf16x8, cm_u32x4{pa[t][0], pa[t][1], pb[t][0], pb[t][1]});
+    } else {
+      const cm_u32x4 pk = {cm_pack2(v[0], v[1]), cm_pack2(v[2], v[3]), cm_pack2(v[4], v[5]), cm_pack2(v[6], v[7])};
+      ka[0][c] = __builtin_bit_cast(bf16x8, pk);
+    }
   }
 }
 
@@ -203,20 +228,27 @@ __device__ __forceinline__ void cm_kernel_operand(const float *Kg, float *K, int
 // current group's MFMAs run (register double buffer, parities resolved at compile time).  Left to the compiler the loop was
 // read -> s_waitcnt lgkmcnt(0) -> MFMA per k-block through ONE fragment register set: an LDS round trip per MFMA.
 // base_of(t) = byte offset of this lane's pixel of tile t in the LDS image; epi(t, acc) stores one tile (all lanes call it).
-template <int NMF, class BaseFn, class EpiFn>
-__device__ __forceinline__ void cm_image_f(const char *tile, int ntiles, int wave, const int (&so)[NMF][2], const bf16x8 (&ka)[NMF],
-                                           BaseFn base_of, EpiFn epi) {
-  constexpr int NG = (NMF + 3) / 4;
-  cm_u32x2 lo[2][2][4], hi[2][2][4];                    // [buffer][tile of the pair][k-block of the group]
-  auto load = [&](const int bA, const int bB, const int grp, cm_u32x2 (&l)[2][4], cm_u32x2 (&h)[2][4]) {
+// TERMS = 3 (fp32-faithful): both operands are exact three-term bf16 splits, the tile's term plane t lies at tile + t * plane, and a
+// k-block is the six products a0 b2, a1 b1, a2 b0, a0 b1, a1 b0, a0 b0 into the same accumulator, smallest first (as k_mm3; the three
+// dropped products are below 2^-25 of a0 b0).  Groups are two k-blocks then: the double buffer holds three planes of each.
+template <int NMF, int TERMS = 1, class BaseFn, class EpiFn>
+__device__ __forceinline__ void cm_image_f(const char *tile, int ntiles, int wave, const int (&so)[NMF][2], const bf16x8 (&ka)[TERMS][NMF],
+                                           BaseFn base_of, EpiFn epi, int plane = 0) {
+  constexpr int GU = TERMS == 1 ? 4 : 2, NG = (NMF + GU - 1) / GU;
+  cm_u32x2 lo[2][TERMS][2][GU], hi[2][TERMS][2][GU];    // [buffer][term plane][tile of the pair][k-block of the group]
+  auto load = [&](const int bA, const int bB, const int grp, cm_u32x2 (&l)[TERMS][2][GU], cm_u32x2 (&h)[TERMS][2][GU]) {
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = 4 * grp + u;
+    for (int u = 0; u < GU; ++u) {
+      const int c = GU * grp + u;
       if (c < NMF) {
-        l[0][u] = *reinterpret_cast<const cm_u32x2 *>(tile + bA + so[c][0]);
-        h[0][u] = *reinterpret_cast<const cm_u32x2 *>(tile + bA + so[c][1]);
-        l[1][u] = *reinterpret_cast<const cm_u32x2 *>(tile + bB + so[c][0]);
-        h[1][u] = *reinterpret_cast<const cm_u32x2 *>(tile + bB + so[c][1]);
+#pragma unroll
+        for (int t = 0; t < TERMS; ++t) {
+          const char *tp = tile + t * plane;
+          l[t][0][u] = *reinterpret_cast<const cm_u32x2 *>(tp + bA + so[c][0]);
+          h[t][0][u] = *reinterpret_cast<const cm_u32x2 *>(tp + bA + so[c][1]);
+          l[t][1][u] = *reinterpret_cast<const cm_u32x2 *>(tp + bB + so[c][0]);
+          h[t][1][u] = *reinterpret_cast<const cm_u32x2 *>(tp + bB + so[c][1]);
+        }
       }
     }
   };
@@ -239,13 +271,22 @@ __device__ __forceinline__ void cm_image_f(const char *tile, int ntiles, int wav
       else if (more) load(nA, nB, 0, lo[nxt], hi[nxt]);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int c = 4 * grp + u;
+      for (int u = 0; u < GU; ++u) {
+        const int c = GU * grp + u;
         if (c < NMF) {
-          const cm_u32x4 f0 = {lo[cur][0][u][0], lo[cur][0][u][1], hi[cur][0][u][0], hi[cur][0][u][1]};
-          const cm_u32x4 f1 = {lo[cur][1][u][0], lo[cur][1][u][1], hi[cur][1][u][0], hi[cur][1][u][1]};
-          acc0 = cm_mfma(ka[c], __builtin_bit_cast(bf16x8, f0), acc0);
-          acc1 = cm_mfma(ka[c], __builtin_bit_cast(bf16x8, f1), acc1);
+          bf16x8 f0[TERMS], f1[TERMS];
+#pragma unroll
+          for (int t = 0; t < TERMS; ++t) {
+            f0[t] = __builtin_bit_cast(bf16x8, cm_u32x4{lo[cur][t][0][u][0], lo[cur][t][0][u][1], hi[cur][t][0][u][0], hi[cur][t][0][u][1]});
+            f1[t] = __builtin_bit_cast(bf16x8, cm_u32x4{lo[cur][t][1][u][0], lo[cur][t][1][u][1], hi[cur][t][1][u][0], hi[cur][t][1][u][1]});
+          }
+#pragma unroll
+          for (int o = TERMS - 1; o >= 0; --o)                // order o = ta + tb of the product, smallest terms first
+#pragma unroll
+            for (int ta = 0; ta <= o; ++ta) {
+              acc0 = cm_mfma(ka[ta][c], f0[o - ta], acc0);
+              acc1 = cm_mfma(ka[ta][c], f1[o - ta], acc1);
+            }
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -267,7 +308,7 @@ __device__ __forceinline__ void cm_image_f(const char *tile, int ntiles, int wav
 // pool[e][b][y/2][x/2][co] = its 2 x 2 average (avg_pool VALID, k_avgpool2) from the same registers: an MFMA tile is a 2 x 8 block
 // of output pixels (lane n: row n >> 3, column n & 7), so a pooling window is lanes {n, n^1, n^8, n^9} of one 16-lane group.
 // out may be null (evaluation needs the pooled activations only).
-template <int MODE, int COUT>
+template <int MODE, int COUT, int TERMS = 1>
 __global__ __launch_bounds__(256) void k_conv5m_fwd(const float *in, long long sE, long long sB, long long sH, long long sW, long long sC,
                                                     int CIN, int H, int W, int pad, const float *theta, int k_off, int b_off, int d, float *out,
                                                     float *pool, int R, int ipw, int activation, int a16 = 0, int ni = 1) {
@@ -280,8 +321,8 @@ __global__ __launch_bounds__(256) void k_conv5m_fwd(const float *in, long long s
   const int n16 = lane & 15, g = lane >> 4;
   const int Ho = H + 2 * pad - 4, Wo = W + 2 * pad - 4, Wp = W + 2 * pad, npix = Ho * Wo;
   const int Hq = Ho / 2, Wq = Wo / 2, TX = (Wo + 7) / 8, ntiles = ((Ho + 1) / 2) * TX;
-  bf16x8 ka[NMF];
-  cm_kernel_operand<MODE, NMF, CK_FWD>(theta + (size_t)e * d + k_off, reinterpret_cast<float *>(cm_lds), CIN, COUT, tid, ka);
+  bf16x8 ka[TERMS][NMF];
+  cm_kernel_operand<MODE, NMF, CK_FWD, TERMS>(theta + (size_t)e * d + k_off, reinterpret_cast<float *>(cm_lds), CIN, COUT, tid, ka);
   int so[NMF][2];
 #pragma unroll
   for (int c = 0; c < NMF; ++c)
@@ -296,16 +337,17 @@ __global__ __launch_bounds__(256) void k_conv5m_fwd(const float *in, long long s
   const float inv_tx = 1.0f / (float)TX, inv_nt = 1.0f / (float)ntiles;
   const int dy = n16 >> 3, dx = n16 & 7;
   const int tile_bytes = ((H + 2 * pad) * Wp + 8) * G::PB;              // one image's tile (a multiple of 16 bytes)
+  const int plane = ni * tile_bytes;                                    // TERMS = 3: the ni tiles once per term
   const int b0 = blockIdx.x * ipw, b1 = min(R, b0 + ipw);
   for (int b = b0; b < b1; b += ni) {
     const int nimg = min(ni, b1 - b);
     __syncthreads();
     for (int im = 0; im < nimg; ++im)
-      cm_stage_input<MODE>(cm_lds + im * tile_bytes, in + (size_t)e * sE + (size_t)(b + im) * sB, sH, sW, sC, CIN, H, W, pad, tid);
+      cm_stage_input<MODE, TERMS>(cm_lds + im * tile_bytes, in + (size_t)e * sE + (size_t)(b + im) * sB, sH, sW, sC, CIN, H, W, pad, tid, plane);
     __syncthreads();
     float *dst = out ? (a16 ? (float *)((uint16_t *)out + ((size_t)e * R + b) * npix * COUT) : out + ((size_t)e * R + b) * npix * COUT) : nullptr;
     float *pdst = pool + ((size_t)e * R + b) * Hq * Wq * COUT;
-    cm_image_f<NMF>(cm_lds, nimg * ntiles, wave, so, ka,
+    cm_image_f<NMF, TERMS>(cm_lds, nimg * ntiles, wave, so, ka,
       [&](const int tt) {
         const int im = cm_div(tt, inv_nt), t = tt - im * ntiles;
         const int ty = cm_div(t, inv_tx), tx = t - ty * TX;
@@ -355,14 +397,14 @@ __global__ __launch_bounds__(256) void k_conv5m_fwd(const float *in, long long s
               if (4 * g + i < COUT) o[i] = s4[i];
           }
         }
-      });
+      }, plane);
   }
 }
 
 // The forward convolution in the PAIR form (CK_FWD2; <= 4 input channels, 2 COUT <= 16): an MFMA column is the pixel pair
 // (y, x), (y, x + 1) with x even, rows are (output channel, which pixel of the pair).  A tile = 2 rows x 8 pairs = 2 x 16 pixels:
 // the horizontal half of a pooling window sits in ONE lane (registers i, i + 1), the vertical half in lane n ^ 8.
-template <int COUT>
+template <int COUT, int TERMS = 1>
 __global__ __launch_bounds__(256) void k_conv5m_fwd2x(const float *in, long long sE, long long sB, long long sH, long long sW, long long sC,
                                                       int CIN, int H, int W, int pad, const float *theta, int k_off, int b_off, int d, float *out,
                                                       float *pool, int R, int ipw, int activation, int a16 = 0, int ni = 1) {
@@ -374,8 +416,8 @@ __global__ __launch_bounds__(256) void k_conv5m_fwd2x(const float *in, long long
   const int n16 = lane & 15, g = lane >> 4;
   const int Ho = H + 2 * pad - 4, Wo = W + 2 * pad - 4, Wp = W + 2 * pad, npix = Ho * Wo;
   const int Hq = Ho / 2, Wq = Wo / 2, TX = (Wo + 15) / 16, ntiles = ((Ho + 1) / 2) * TX;
-  bf16x8 ka[NMF];
-  cm_kernel_operand<CM_IN4, NMF, CK_FWD2>(theta + (size_t)e * d + k_off, reinterpret_cast<float *>(cm_lds), CIN, COUT, tid, ka);
+  bf16x8 ka[TERMS][NMF];
+  cm_kernel_operand<CM_IN4, NMF, CK_FWD2, TERMS>(theta + (size_t)e * d + k_off, reinterpret_cast<float *>(cm_lds), CIN, COUT, tid, ka);
   int so[NMF][2];
 #pragma unroll
   for (int c = 0; c < NMF; ++c)
@@ -389,16 +431,17 @@ __global__ __launch_bounds__(256) void k_conv5m_fwd2x(const float *in, long long
   const float inv_tx = 1.0f / (float)TX, inv_nt = 1.0f / (float)ntiles;
   const int dy = n16 >> 3, px = n16 & 7;
   const int tile_bytes = ((H + 2 * pad) * Wp + 8) * G::PB;               // per image (ni images per barrier pair)
+  const int plane = ni * tile_bytes;                                     // TERMS = 3: the ni tiles once per term
   const int b0 = blockIdx.x * ipw, b1 = min(R, b0 + ipw);
   for (int b = b0; b < b1; b += ni) {
     const int nimg = min(ni, b1 - b);
     __syncthreads();
     for (int im = 0; im < nimg; ++im)
-      cm_stage_input<CM_IN4>(cm_lds + im * tile_bytes, in + (size_t)e * sE + (size_t)(b + im) * sB, sH, sW, sC, CIN, H, W, pad, tid);
+      cm_stage_input<CM_IN4, TERMS>(cm_lds + im * tile_bytes, in + (size_t)e * sE + (size_t)(b + im) * sB, sH, sW, sC, CIN, H, W, pad, tid, plane);
     __syncthreads();
     float *dst0 = out ? (a16 ? (float *)((uint16_t *)out + ((size_t)e * R + b) * npix * COUT) : out + ((size_t)e * R + b) * npix * COUT) : nullptr;
     float *pdst0 = pool + ((size_t)e * R + b) * Hq * Wq * COUT;
-    cm_image_f<NMF>(cm_lds, nimg * ntiles, wave, so, ka,
+    cm_image_f<NMF, TERMS>(cm_lds, nimg * ntiles, wave, so, ka,
       [&](const int tt) {
         const int im = cm_div(tt, inv_nt), t = tt - im * ntiles;
         const int ty = cm_div(t, inv_tx), tx = t - ty * TX;
@@ -429,7 +472,7 @@ __global__ __launch_bounds__(256) void k_conv5m_fwd2x(const float *in, long long
         const float s0 = 0.25f * (h0 + __shfl_xor(h0, 8)), s1 = 0.25f * (h1 + __shfl_xor(h1, 8));
         if (rows_on && dy == 0 && y < 2 * Hq && x < 2 * Wq)
           *reinterpret_cast<cm_f32x2 *>(pdst + (size_t)((y >> 1) * Wq + (x >> 1)) * COUT + 2 * g) = cm_f32x2{s0, s1};
-      });
+      }, plane);
   }
 }
 
@@ -437,9 +480,10 @@ __global__ __launch_bounds__(256) void k_conv5m_fwd2x(const float *in, long long
 // dz = unpool(dp) * act'(a): dz[y][x][c] = (avg-pool backward: dp[y/2][x/2][c] / 4, zero on the cropped border) * act'(a[y][x][c])
 // (mile_lenet.h dz_from_pool).  npix_alloc pixels are written (zeros outside the image).  One pixel per thread and pass, its
 // channels as 8- / 16-byte loads, U pixels' loads in flight (see cm_stage_input); a / dp rows are 8-byte aligned (COUT even).
-template <int COUT, bool A16 = false>
+// TERMS = 3: the exact three-term split of every dz, term plane t at zt + t * plane.
+template <int COUT, bool A16 = false, int TERMS = 1>
 __device__ __forceinline__ void cm_stage_dz(char *zt, const float *dp_img, const void *a_img, int Ho, int Wo, int halo, int npix_alloc,
-                                            int activation, int tid) {
+                                            int activation, int tid, int plane = 0) {
   static_assert(COUT % 2 == 0 && COUT <= 16, "channel pairs");
   constexpr int U = COUT > 8 ? 2 : 4, VW = COUT % 4 == 0 ? 4 : 2;   // 2 x 16 channels x (a, dp) = 64 registers in flight
   const int Wt = Wo + 2 * halo, Ht = Ho + 2 * halo, Hq = Ho / 2, Wq = Wo / 2;
@@ -472,6 +516,24 @@ __device__ __forceinline__ void cm_stage_dz(char *zt, const float *dp_img, const
     for (int u = 0; u < U; ++u) {
       const int px = i0 + 256 * u;
       if (px >= npix_alloc) continue;
+      if constexpr (TERMS != 1) {
+#pragma unroll
+        for (int c = 0; c < 16; c += 8) {
+          cm_u32x2 pa[TERMS], pb[TERMS];
+          cm_f32x4 z0 = {0.0f, 0.0f, 0.0f, 0.0f}, z1 = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            if (c + k < COUT) z0[k] = in[u] ? 0.25f * gv[u][c + k] * act_bwd(activation, av[u][c + k]) : 0.0f;
+            if (c + 4 + k < COUT) z1[k] = in[u] ? 0.25f * gv[u][c + 4 + k] * act_bwd(activation, av[u][c + 4 + k]) : 0.0f;
+          }
+          mm_split4<TERMS>(z0, pa);
+          mm_split4<TERMS>(z1, pb);
+#pragma unroll
+          for (int t = 0; t < TERMS; ++t)
+            *reinterpret_cast<cm_u32x4 *>(zt + t * plane + (size_t)px * 32 + 2 * c) = cm_u32x4{pa[t][0], pa[t][1], pb[t][0], pb[t][1]};
+        }
+        continue;
+      }
       uint32_t pk[8];
 #pragma unroll
       for (int c = 0; c < 16; c += 2) {
@@ -490,7 +552,7 @@ __device__ __forceinline__ void cm_stage_dz(char *zt, const float *dp_img, const
 
 // The input gradient in the PAIR form (CK_DX2, CM_DZ16P): an MFMA column is the input pixel pair (yi, xi), (yi, xi + 1), rows are
 // (input channel, which pixel): 12 of 16 rows useful for conv2's 6 input channels and 15 MFMAs per 32 pixels instead of 26.
-template <int CIN, int COUT>
+template <int CIN, int COUT, int TERMS = 1>
 __global__ __launch_bounds__(256) void k_conv5m_dx2x(const float *dp, const float *a, int activation, const float *theta, int k_off, int d,
                                                      float *din, int R, int Ho, int Wo, int ipw, int a16 = 0, int ni = 1) {
   using G = CSlot<CM_DZ16P>;
@@ -500,8 +562,8 @@ __global__ __launch_bounds__(256) void k_conv5m_dx2x(const float *dp, const floa
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, e = blockIdx.y;
   const int n16 = lane & 15, g = lane >> 4;
   const int H = Ho + 4, W = Wo + 4, Ht = Ho + 8, Wt = Wo + 8, npix = H * W, W2 = (W + 1) / 2, npairs = H * W2;
-  bf16x8 ka[NMF];
-  cm_kernel_operand<CM_DZ16P, NMF, CK_DX2>(theta + (size_t)e * d + k_off, reinterpret_cast<float *>(cm_lds), CIN, COUT, tid, ka);
+  bf16x8 ka[TERMS][NMF];
+  cm_kernel_operand<CM_DZ16P, NMF, CK_DX2, TERMS>(theta + (size_t)e * d + k_off, reinterpret_cast<float *>(cm_lds), CIN, COUT, tid, ka);
   int so[NMF][2];
 #pragma unroll
   for (int c = 0; c < NMF; ++c)
@@ -513,6 +575,7 @@ __global__ __launch_bounds__(256) void k_conv5m_dx2x(const float *dp, const floa
   const float inv_w2 = 1.0f / (float)W2;
   const int ntiles = (npairs + 15) / 16, tile_bytes = (Ht * Wt + 8) * 32;     // per image (ni images per barrier pair)
   const float inv_nt = 1.0f / (float)ntiles;
+  const int plane = ni * tile_bytes;                                          // TERMS = 3: the ni dZ tiles once per term
   const int b0 = blockIdx.x * ipw, b1 = min(R, b0 + ipw);
   for (int b = b0; b < b1; b += ni) {
     const int nimg = min(ni, b1 - b);
@@ -520,12 +583,12 @@ __global__ __launch_bounds__(256) void k_conv5m_dx2x(const float *dp, const floa
     for (int im = 0; im < nimg; ++im) {
       const size_t img = (size_t)e * R + b + im;
       // + 8 pixels of zero slack: the kw' = -1 slot of an odd-width image's last pair reads one pixel past the tile
-      if (a16) cm_stage_dz<COUT, true>(cm_lds + im * tile_bytes, dp + img * (Ho / 2) * (Wo / 2) * COUT, (const uint16_t *)a + img * Ho * Wo * COUT, Ho, Wo, 4, Ht * Wt + 8, activation, tid);
-      else cm_stage_dz<COUT>(cm_lds + im * tile_bytes, dp + img * (Ho / 2) * (Wo / 2) * COUT, a + img * Ho * Wo * COUT, Ho, Wo, 4, Ht * Wt + 8, activation, tid);
+      if (a16) cm_stage_dz<COUT, true, TERMS>(cm_lds + im * tile_bytes, dp + img * (Ho / 2) * (Wo / 2) * COUT, (const uint16_t *)a + img * Ho * Wo * COUT, Ho, Wo, 4, Ht * Wt + 8, activation, tid, plane);
+      else cm_stage_dz<COUT, false, TERMS>(cm_lds + im * tile_bytes, dp + img * (Ho / 2) * (Wo / 2) * COUT, a + img * Ho * Wo * COUT, Ho, Wo, 4, Ht * Wt + 8, activation, tid, plane);
     }
     __syncthreads();
     float *dst0 = din + ((size_t)e * R + b) * npix * CIN;
-    cm_image_f<NMF>(cm_lds, nimg * ntiles, wave, so, ka,
+    cm_image_f<NMF, TERMS>(cm_lds, nimg * ntiles, wave, so, ka,
       [&](const int tt) {
         const int im = cm_div(tt, inv_nt), t = tt - im * ntiles;
         const int pc = min(t * 16 + n16, npairs - 1);
@@ -542,13 +605,13 @@ __global__ __launch_bounds__(256) void k_conv5m_dx2x(const float *dp, const floa
           *reinterpret_cast<cm_f32x2 *>(o) = cm_f32x2{acc[0], acc[2]};
           if (xi + 1 < W) *reinterpret_cast<cm_f32x2 *>(o + CIN) = cm_f32x2{acc[1], acc[3]};
         }
-      });
+      }, plane);
   }
 }
 
 // Kernel / bias gradient of one image range (as k_conv5_dw): part[(e * nwg + wg) * (25*CIN*COUT + COUT) + ...]
 //   dK[kh][kw][ci][co] = sum_{b,y,x} in[b][y+kh-pad][x+kw-pad][ci] dz[b][y][x][co],  db[co] = sum dz
-template <int MODE, int COUT>
+template <int MODE, int COUT, int TERMS = 1>
 __global__ __launch_bounds__(256) void k_conv5m_dw(const float *in, long long sE, long long sB, long long sH, long long sW, long long sC, int CIN,
                                                    int H, int W, int pad, const float *dp, const float *a, int activation, float *part, int R,
                                                    int ipw, int a16 = 0, int ni = 1) {
@@ -564,6 +627,7 @@ __global__ __launch_bounds__(256) void k_conv5m_dw(const float *in, long long sE
   const int tile_bytes = ((Hp * Wp + 8) * G::PB + 15) / 16 * 16;   // one image's input tile
   char *tile = cm_lds;                                              // ni tiles
   char *zt = cm_lds + (size_t)ni * tile_bytes;                      // [roundup32(ni * npix)][16] bf16, zero beyond the last image
+  const int plane = ni * tile_bytes + (ni * npix + 31) / 32 * 32 * 32;   // TERMS = 3: tiles and dZ rows once per term
   int so[NMT];
 #pragma unroll
   for (int mt = 0; mt < NMT; ++mt) so[mt] = 4 * mt + p4 < G::NS ? G::off(4 * mt + p4, Wp) : 0;
@@ -581,16 +645,16 @@ __global__ __launch_bounds__(256) void k_conv5m_dw(const float *in, long long sE
     for (int im = 0; im < nimg; ++im) {
       const size_t img = (size_t)e * R + b + im;
       const int rows = im + 1 < nimg ? npix : npix + ntot32 - ntot;        // the last image also zeroes the rows up to the chunk boundary
-      cm_stage_input<MODE>(tile + im * tile_bytes, in + (size_t)e * sE + (size_t)(b + im) * sB, sH, sW, sC, CIN, H, W, pad, tid);
-      if (a16) cm_stage_dz<COUT, true>(zt + (size_t)im * npix * 32, dp + img * (Ho / 2) * (Wo / 2) * COUT, (const uint16_t *)a + img * npix * COUT, Ho, Wo, 0, rows, activation, tid);
-      else cm_stage_dz<COUT>(zt + (size_t)im * npix * 32, dp + img * (Ho / 2) * (Wo / 2) * COUT, a + img * npix * COUT, Ho, Wo, 0, rows, activation, tid);
+      cm_stage_input<MODE, TERMS>(tile + im * tile_bytes, in + (size_t)e * sE + (size_t)(b + im) * sB, sH, sW, sC, CIN, H, W, pad, tid, plane);
+      if (a16) cm_stage_dz<COUT, true, TERMS>(zt + (size_t)im * npix * 32, dp + img * (Ho / 2) * (Wo / 2) * COUT, (const uint16_t *)a + img * npix * COUT, Ho, Wo, 0, rows, activation, tid, plane);
+      else cm_stage_dz<COUT, false, TERMS>(zt + (size_t)im * npix * 32, dp + img * (Ho / 2) * (Wo / 2) * COUT, a + img * npix * COUT, Ho, Wo, 0, rows, activation, tid, plane);
     }
     __syncthreads();
     // chunks of 32 pixels: ch = wave, wave + 4, ...  The fragments of the next group of four accumulator tiles -- or of the next
     // chunk's first group and its dZ fragment -- are in flight while the current group's MFMAs run (see cm_image_f).
     constexpr int NG = (NMT + 3) / 4;
     static_assert(NG % 2 == 0, "the register double buffer returns to buffer 0 at every chunk");
-    bf16x4 a0[2][4], a1[2][4];
+    bf16x4 a0[2][TERMS][4], a1[2][TERMS][4];             // [buffer][term plane][accumulator tile of the group]
     auto addr = [&](const int ch, int &bs0, int &bs1, int &zo0, int &zo1) {
       // this lane's two rows of the transposed reads: pixels P0 = 32 ch + 8 g + q and P0 + 4 (dZ rows beyond the image are zero)
       const int P0 = 32 * ch + 8 * g + q, P1 = P0 + 4;
@@ -600,18 +664,24 @@ __global__ __launch_bounds__(256) void k_conv5m_dw(const float *in, long long sE
       bs0 = i0 * tile_bytes + (y0 * Wp + x0) * G::PB; bs1 = i1 * tile_bytes + (y1 * Wp + x1) * G::PB;
       zo0 = P0 * 32 + 8 * p4; zo1 = P1 * 32 + 8 * p4;
     };
-    auto load_z = [&](const int zo0, const int zo1) {
-      const bf16x4 z0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, zt + zo0));
-      const bf16x4 z1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, zt + zo1));
-      return __builtin_shufflevector(z0, z1, 0, 1, 2, 3, 4, 5, 6, 7);
+    auto load_z = [&](const int zo0, const int zo1, bf16x8 (&z)[TERMS]) {
+#pragma unroll
+      for (int t = 0; t < TERMS; ++t) {
+        const bf16x4 z0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, zt + t * plane + zo0));
+        const bf16x4 z1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, zt + t * plane + zo1));
+        z[t] = __builtin_shufflevector(z0, z1, 0, 1, 2, 3, 4, 5, 6, 7);
+      }
     };
-    auto load_a = [&](const int bs0, const int bs1, const int grp, bf16x4 (&f0)[4], bf16x4 (&f1)[4]) {
+    auto load_a = [&](const int bs0, const int bs1, const int grp, bf16x4 (&f0)[TERMS][4], bf16x4 (&f1)[TERMS][4]) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int mt = 4 * grp + u;
         if (mt < NMT) {
-          f0[u] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, tile + bs0 + so[mt]));
-          f1[u] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, tile + bs1 + so[mt]));
+#pragma unroll
+          for (int t = 0; t < TERMS; ++t) {
+            f0[t][u] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, tile + t * plane + bs0 + so[mt]));
+            f1[t][u] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, tile + t * plane + bs1 + so[mt]));
+          }
         }
       }
     };
@@ -619,29 +689,42 @@ __global__ __launch_bounds__(256) void k_conv5m_dw(const float *in, long long sE
     if (ch * 32 < ntot) {
       int bs0, bs1, zo0, zo1;
       addr(ch, bs0, bs1, zo0, zo1);
-      bf16x8 bz = load_z(zo0, zo1);
+      bf16x8 bz[TERMS], bzn[TERMS];
+      load_z(zo0, zo1, bz);
       load_a(bs0, bs1, 0, a0[0], a1[0]);
       for (bool more = true; more;) {
         const int nch = ch + 4;
         more = nch * 32 < ntot;
         int nb0 = 0, nb1 = 0, nz0 = 0, nz1 = 0;
         if (more) addr(nch, nb0, nb1, nz0, nz1);
-        bf16x8 bzn = bz;
+#pragma unroll
+        for (int t = 0; t < TERMS; ++t) bzn[t] = bz[t];
 #pragma unroll
         for (int grp = 0; grp < NG; ++grp) {
           const int cur = grp & 1, nxt = cur ^ 1;
           if (grp + 1 < NG) load_a(bs0, bs1, grp + 1, a0[nxt], a1[nxt]);
-          else if (more) { bzn = load_z(nz0, nz1); load_a(nb0, nb1, 0, a0[nxt], a1[nxt]); }
+          else if (more) { load_z(nz0, nz1, bzn); load_a(nb0, nb1, 0, a0[nxt], a1[nxt]); }
           __builtin_amdgcn_sched_barrier(0);
-          if (grp == 0) accb = cm_mfma(ones, bz, accb);
+          if (grp == 0) {                                       // 1.0 is exact: the ones row meets every dZ term, smallest first
+#pragma unroll
+            for (int t = TERMS - 1; t >= 0; --t) accb = cm_mfma(ones, bz[t], accb);
+          }
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             const int mt = 4 * grp + u;
-            if (mt < NMT) acc[mt] = cm_mfma(__builtin_shufflevector(a0[cur][u], a1[cur][u], 0, 1, 2, 3, 4, 5, 6, 7), bz, acc[mt]);
+            if (mt < NMT) {
+#pragma unroll
+              for (int o = TERMS - 1; o >= 0; --o)              // six products for TERMS = 3, smallest first (see cm_image_f)
+#pragma unroll
+                for (int ta = 0; ta <= o; ++ta)
+                  acc[mt] = cm_mfma(__builtin_shufflevector(a0[cur][ta][u], a1[cur][ta][u], 0, 1, 2, 3, 4, 5, 6, 7), bz[o - ta], acc[mt]);
+            }
           }
           __builtin_amdgcn_sched_barrier(0);
         }
-        bz = bzn; bs0 = nb0; bs1 = nb1; ch = nch;
+#pragma unroll
+        for (int t = 0; t < TERMS; ++t) bz[t] = bzn[t];
+        bs0 = nb0; bs1 = nb1; ch = nch;
       }
     }
   }
@@ -673,9 +756,9 @@ __global__ __launch_bounds__(256) void k_conv5m_dw(const float *in, long long sE
 
 // dZ of one image as PAIR rows for the kernel-gradient pass: zt[pair (y, x / 2)][column 2 co + dxo] = dz[y][x + dxo][co], bf16,
 // npairs_alloc rows written (zeros outside the image).  One pair per thread and pass, U pairs' loads in flight.
-template <int COUT, bool A16 = false>
+template <int COUT, bool A16 = false, int TERMS = 1>
 __device__ __forceinline__ void cm_stage_dz_pairs(char *zt, const float *dp_img, const void *a_img, int Ho, int Wo, int npairs_alloc,
-                                                  int activation, int tid) {
+                                                  int activation, int tid, int plane = 0) {
   static_assert(COUT % 2 == 0 && 2 * COUT <= 16, "channel pairs, 16 columns");
   constexpr int U = 2;
   const int W2 = (Wo + 1) / 2, Hq = Ho / 2, Wq = Wo / 2;
@@ -704,6 +787,25 @@ __device__ __forceinline__ void cm_stage_dz_pairs(char *zt, const float *dp_img,
     for (int u = 0; u < U; ++u) {
       const int pi = i0 + 256 * u;
       if (pi >= npairs_alloc) continue;
+      if constexpr (TERMS != 1) {
+#pragma unroll
+        for (int c = 0; c < 8; c += 4) {       // four packed words = channels c .. c + 3 at x and x + 1
+          cm_u32x2 pa[TERMS], pb[TERMS];
+          cm_f32x4 z0 = {0.0f, 0.0f, 0.0f, 0.0f}, z1 = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const int ch = c + (k >> 1), dxo = k & 1;
+            if (ch < COUT) z0[k] = in[u][dxo] ? 0.25f * gv[u][dxo][ch] * act_bwd(activation, av[u][dxo][ch]) : 0.0f;
+            if (ch + 2 < COUT) z1[k] = in[u][dxo] ? 0.25f * gv[u][dxo][ch + 2] * act_bwd(activation, av[u][dxo][ch + 2]) : 0.0f;
+          }
+          mm_split4<TERMS>(z0, pa);
+          mm_split4<TERMS>(z1, pb);
+#pragma unroll
+          for (int t = 0; t < TERMS; ++t)
+            *reinterpret_cast<cm_u32x4 *>(zt + t * plane + (size_t)pi * 32 + 4 * c) = cm_u32x4{pa[t][0], pa[t][1], pb[t][0], pb[t][1]};
+        }
+        continue;
+      }
       uint32_t pk[8];
 #pragma unroll
       for (int c = 0; c < 8; ++c) {          // packed word c = columns 2c, 2c + 1 = channel c at x and x + 1
@@ -724,7 +826,7 @@ __device__ __forceinline__ void cm_stage_dz_pairs(char *zt, const float *dp_img,
 // are (output channel, which pixel of the pair):  D[(kh, kw', ci)][(co, dxo)] = sum_pairs in[y + kh][x + kw'][ci] dz[y][x + dxo][co]
 // is a contribution to dK[kh][kw' - dxo][ci][co], so dK[kh][kw] = D[kw][dxo = 0] + D[kw + 1][dxo = 1] -- half the MFMAs and
 // transposed reads of the pixel form, 12 of 16 columns useful instead of 6.  The two halves meet in the final LDS reduction.
-template <int COUT>
+template <int COUT, int TERMS = 1>
 __global__ __launch_bounds__(256) void k_conv5m_dw2x(const float *in, long long sE, long long sB, long long sH, long long sW, long long sC,
                                                      int CIN, int H, int W, int pad, const float *dp, const float *a, int activation, float *part,
                                                      int R, int ipw, int a16 = 0) {
@@ -738,6 +840,7 @@ __global__ __launch_bounds__(256) void k_conv5m_dw2x(const float *in, long long 
   const int W2 = (Wo + 1) / 2, npairs = Ho * W2, npairs32 = (npairs + 31) / 32 * 32;
   char *tile = cm_lds;                                                  // (Hp * Wp + 8) pixels of 8 bytes
   char *zt = cm_lds + ((size_t)(Hp * Wp + 8) * G::PB + 15) / 16 * 16;   // [npairs32][16] bf16
+  const int plane = ((Hp * Wp + 8) * G::PB + 15) / 16 * 16 + npairs32 * 32;   // TERMS = 3: tile and dZ rows once per term
   int so[NMT];
 #pragma unroll
   for (int mt = 0; mt < NMT; ++mt) so[mt] = 4 * mt + p4 < G::NS ? G::off(4 * mt + p4, Wp) : 0;
@@ -751,13 +854,13 @@ __global__ __launch_bounds__(256) void k_conv5m_dw2x(const float *in, long long 
   for (int b = b0; b < b1; ++b) {
     const size_t img = (size_t)e * R + b;
     __syncthreads();
-    cm_stage_input<CM_IN4>(tile, in + (size_t)e * sE + (size_t)b * sB, sH, sW, sC, CIN, H, W, pad, tid);
-    if (a16) cm_stage_dz_pairs<COUT, true>(zt, dp + img * (Ho / 2) * (Wo / 2) * COUT, (const uint16_t *)a + img * npix * COUT, Ho, Wo, npairs32, activation, tid);
-    else cm_stage_dz_pairs<COUT>(zt, dp + img * (Ho / 2) * (Wo / 2) * COUT, a + img * npix * COUT, Ho, Wo, npairs32, activation, tid);
+    cm_stage_input<CM_IN4, TERMS>(tile, in + (size_t)e * sE + (size_t)b * sB, sH, sW, sC, CIN, H, W, pad, tid, plane);
+    if (a16) cm_stage_dz_pairs<COUT, true, TERMS>(zt, dp + img * (Ho / 2) * (Wo / 2) * COUT, (const uint16_t *)a + img * npix * COUT, Ho, Wo, npairs32, activation, tid, plane);
+    else cm_stage_dz_pairs<COUT, false, TERMS>(zt, dp + img * (Ho / 2) * (Wo / 2) * COUT, a + img * npix * COUT, Ho, Wo, npairs32, activation, tid, plane);
     __syncthreads();
     constexpr int NG = (NMT + 3) / 4;
     static_assert(NG % 2 == 0, "the register double buffer returns to buffer 0 at every chunk");
-    bf16x4 a0[2][4], a1[2][4];
+    bf16x4 a0[2][TERMS][4], a1[2][TERMS][4];             // [buffer][term plane][accumulator tile of the group]
     auto addr = [&](const int ch, int &bs0, int &bs1, int &zo0, int &zo1) {
       const int P0 = 32 * ch + 8 * g + q, P1 = P0 + 4;            // this lane's two pair rows of the transposed reads
       const int c0 = min(P0, npairs - 1), c1 = min(P1, npairs - 1);
@@ -765,18 +868,24 @@ __global__ __launch_bounds__(256) void k_conv5m_dw2x(const float *in, long long 
       bs0 = (y0 * Wp + x0) * G::PB; bs1 = (y1 * Wp + x1) * G::PB;
       zo0 = P0 * 32 + 8 * p4; zo1 = P1 * 32 + 8 * p4;
     };
-    auto load_z = [&](const int zo0, const int zo1) {
-      const bf16x4 z0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, zt + zo0));
-      const bf16x4 z1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, zt + zo1));
-      return __builtin_shufflevector(z0, z1, 0, 1, 2, 3, 4, 5, 6, 7);
+    auto load_z = [&](const int zo0, const int zo1, bf16x8 (&z)[TERMS]) {
+#pragma unroll
+      for (int t = 0; t < TERMS; ++t) {
+        const bf16x4 z0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, zt + t * plane + zo0));
+        const bf16x4 z1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, zt + t * plane + zo1));
+        z[t] = __builtin_shufflevector(z0, z1, 0, 1, 2, 3, 4, 5, 6, 7);
+      }
     };
-    auto load_a = [&](const int bs0, const int bs1, const int grp, bf16x4 (&f0)[4], bf16x4 (&f1)[4]) {
+    auto load_a = [&](const int bs0, const int bs1, const int grp, bf16x4 (&f0)[TERMS][4], bf16x4 (&f1)[TERMS][4]) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int mt = 4 * grp + u;
         if (mt < NMT) {
-          f0[u] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, tile + bs0 + so[mt]));
-          f1[u] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, tile + bs1 + so[mt]));
+#pragma unroll
+          for (int t = 0; t < TERMS; ++t) {
+            f0[t][u] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, tile + t * plane + bs0 + so[mt]));
+            f1[t][u] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MILE_LDS_PTR(bf16x4, tile + t * plane + bs1 + so[mt]));
+          }
         }
       }
     };
@@ -784,29 +893,42 @@ __global__ __launch_bounds__(256) void k_conv5m_dw2x(const float *in, long long 
     if (ch * 32 < npairs) {
       int bs0, bs1, zo0, zo1;
       addr(ch, bs0, bs1, zo0, zo1);
-      bf16x8 bz = load_z(zo0, zo1);
+      bf16x8 bz[TERMS], bzn[TERMS];
+      load_z(zo0, zo1, bz);
       load_a(bs0, bs1, 0, a0[0], a1[0]);
       for (bool more = true; more;) {
         const int nch = ch + 4;
         more = nch * 32 < npairs;
         int nb0 = 0, nb1 = 0, nz0 = 0, nz1 = 0;
         if (more) addr(nch, nb0, nb1, nz0, nz1);
-        bf16x8 bzn = bz;
+#pragma unroll
+        for (int t = 0; t < TERMS; ++t) bzn[t] = bz[t];
 #pragma unroll
         for (int grp = 0; grp < NG; ++grp) {
           const int cur = grp & 1, nxt = cur ^ 1;
           if (grp + 1 < NG) load_a(bs0, bs1, grp + 1, a0[nxt], a1[nxt]);
-          else if (more) { bzn = load_z(nz0, nz1); load_a(nb0, nb1, 0, a0[nxt], a1[nxt]); }
+          else if (more) { load_z(nz0, nz1, bzn); load_a(nb0, nb1, 0, a0[nxt], a1[nxt]); }
           __builtin_amdgcn_sched_barrier(0);
-          if (grp == 0) accb = cm_mfma(ones, bz, accb);
+          if (grp == 0) {                                       // 1.0 is exact: the ones row meets every dZ term, smallest first
+#pragma unroll
+            for (int t = TERMS - 1; t >= 0; --t) accb = cm_mfma(ones, bz[t], accb);
+          }
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             const int mt = 4 * grp + u;
-            if (mt < NMT) acc[mt] = cm_mfma(__builtin_shufflevector(a0[cur][u], a1[cur][u], 0, 1, 2, 3, 4, 5, 6, 7), bz, acc[mt]);
+            if (mt < NMT) {
+#pragma unroll
+              for (int o = TERMS - 1; o >= 0; --o)              // six products for TERMS = 3, smallest first (see cm_image_f)
+#pragma unroll
+                for (int ta = 0; ta <= o; ++ta)
+                  acc[mt] = cm_mfma(__builtin_shufflevector(a0[cur][ta][u], a1[cur][ta][u], 0, 1, 2, 3, 4, 5, 6, 7), bz[o - ta], acc[mt]);
+            }
           }
           __builtin_amdgcn_sched_barrier(0);
         }
-        bz = bzn; bs0 = nb0; bs1 = nb1; ch = nch;
+#pragma unroll
+        for (int t = 0; t < TERMS; ++t) bz[t] = bzn[t];
+        bs0 = nb0; bs1 = nb1; ch = nch;
       }
     }
   }
@@ -840,24 +962,24 @@ __global__ __launch_bounds__(256) void k_conv5m_dw2x(const float *in, long long 
   }
 }
 
-// LDS bytes of the three kernels for a geometry (host side)
-static inline size_t cm_lds_fwd(int mode, int H, int W, int pad, int CIN, int COUT, int ni = 1) {
+// LDS bytes of the three kernels for a geometry (host side); terms = 3: one plane of the tiles (the kernels' `plane`) per term
+static inline size_t cm_lds_fwd(int mode, int H, int W, int pad, int CIN, int COUT, int ni = 1, int terms = 1) {
   const int pb = mode == CM_IN4 ? 8 : 16;
-  return std::max((size_t)ni * ((H + 2 * pad) * (W + 2 * pad) + 8) * pb, (size_t)25 * CIN * COUT * 4);
+  return std::max((size_t)terms * ni * ((H + 2 * pad) * (W + 2 * pad) + 8) * pb, (size_t)25 * CIN * COUT * 4);
 }
-static inline size_t cm_lds_dx2x(int Ho, int Wo, int CIN, int COUT, int ni = 1) {
-  return std::max((size_t)ni * ((Ho + 8) * (Wo + 8) + 8) * 32, (size_t)25 * CIN * COUT * 4);
+static inline size_t cm_lds_dx2x(int Ho, int Wo, int CIN, int COUT, int ni = 1, int terms = 1) {
+  return std::max((size_t)terms * ni * ((Ho + 8) * (Wo + 8) + 8) * 32, (size_t)25 * CIN * COUT * 4);
 }
-static inline size_t cm_lds_dw2x(int H, int W, int pad) {
+static inline size_t cm_lds_dw2x(int H, int W, int pad, int terms = 1) {
   const int Ho = H + 2 * pad - 4, Wo = W + 2 * pad - 4, npairs = Ho * ((Wo + 1) / 2);
-  const size_t tiles = ((size_t)((H + 2 * pad) * (W + 2 * pad) + 8) * 8 + 15) / 16 * 16 + (size_t)((npairs + 31) / 32 * 32) * 32;
+  const size_t tiles = terms * (((size_t)((H + 2 * pad) * (W + 2 * pad) + 8) * 8 + 15) / 16 * 16 + (size_t)((npairs + 31) / 32 * 32) * 32);
   const size_t red = (size_t)4 * (8 + 1) * 64 * 16;
   return tiles > red ? tiles : red;
 }
-static inline size_t cm_lds_dw(int mode, int H, int W, int pad, int ni = 1) {
+static inline size_t cm_lds_dw(int mode, int H, int W, int pad, int ni = 1, int terms = 1) {
   const int pb = mode == CM_IN4 ? 8 : 16, ns = mode == CM_IN4 ? 30 : 50;
   const int Ho = H + 2 * pad - 4, Wo = W + 2 * pad - 4;
-  const size_t tiles = (size_t)ni * (((size_t)((H + 2 * pad) * (W + 2 * pad) + 8) * pb + 15) / 16 * 16) + (size_t)((ni * Ho * Wo + 31) / 32 * 32) * 32;
+  const size_t tiles = terms * ((size_t)ni * (((size_t)((H + 2 * pad) * (W + 2 * pad) + 8) * pb + 15) / 16 * 16) + (size_t)((ni * Ho * Wo + 31) / 32 * 32) * 32);
   const size_t red = (size_t)4 * ((ns + 3) / 4 + 1) * 64 * 16;
   return tiles > red ? tiles : red;
 }

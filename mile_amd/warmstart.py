@@ -20,6 +20,10 @@ import torch
 
 logger = logging.getLogger(__name__)
 
+# the grad kernels that take a row window (mile_set_row_window): minibatches run on the sampler's own kernel
+WINDOWED = ('generic', 'mfma_narrow_f32', 'mfma_w64', 'mfma_w64_bf16x3', 'mfma_wide_bf16x3', 'mfma_wide_bf16', 'lenet_f32', 'lenet_bf16',
+            'lenet_bf16x3', 'lenetti_f32', 'attn_f32', 'attn_pre_f32', 'attn_wide_f32')
+
 
 def earlystop(losses: torch.Tensor, patience: int) -> torch.Tensor:
     """trainer.py:920-939: stop a member when none of its last `patience` validation losses is below the one before
@@ -89,8 +93,6 @@ def train_deep_ensemble(eng, prior, theta0: torch.Tensor, n_train: int, valid_x,
     opt = _Optimizer(optimizer, optimizer_parameters or {}, theta)
     ostate = {'name': opt.name, 'learning_rate': opt.lr, 'b1': opt.b1, 'b2': opt.b2, 'eps': opt.eps, 'weight_decay': opt.wd,
               't': 0, 'm': opt.m, 'v': opt.v}
-    WINDOWED = ('generic', 'mfma_narrow_f32', 'mfma_w64', 'mfma_w64_bf16x3', 'mfma_wide_bf16x3', 'mfma_wide_bf16', 'lenet_f32', 'lenet_bf16',
-                'lenetti_f32', 'attn_f32', 'attn_pre_f32', 'attn_wide_f32')
     want_minibatch = bool(batch_size) and batch_size < n_train and train_x is not None and train_y is not None
     sampler_kernel = eng.grad_kernel
     if want_minibatch and sampler_kernel not in WINDOWED:

@@ -1,5 +1,5 @@
 """dev: time one ensemble gradient of LeNet at BASELINE config 5's shape (3 x 32 x 32, 10 classes) on a grad kernel.
-usage: lenet_time.py [kernel=lenet_f32|lenet_bf16] [N=4000] [E=256]"""
+usage: lenet_time.py [kernel=lenet_f32|lenet_bf16|lenet_bf16x3] [N=4000] [E=256]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -22,6 +22,13 @@ for _ in range(n):
     lp, g = eng.logpost_grad(th)
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / n
+each = []                                  # the spread: the same call timed one at a time
+for _ in range(5):
+    t1 = time.perf_counter()
+    lp, g = eng.logpost_grad(th)
+    torch.cuda.synchronize()
+    each.append((time.perf_counter() - t1) * 1e3)
+print(f'{eng.grad_kernel}: single calls min/median/max {min(each):.1f} / {sorted(each)[2]:.1f} / {max(each):.1f} ms')
 flop = 3 * 2 * (1024 * 75 * 6 + 144 * 150 * 16 + 576 * 120 + 120 * 84 + 84 * 10) * N * E
 print(f'{eng.grad_kernel}: N={N} E={E} d={spec.n_params}  {dt * 1e3:.1f} ms per ensemble gradient  {flop / dt / 1e12:.1f} TFLOP/s (algorithmic)  '
       f'finite={bool(torch.isfinite(g).all())}  |g|={g.norm().item():.6g} lp0={lp[0].item():.6g}')
