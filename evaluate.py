@@ -210,6 +210,52 @@ def stacking_metrics(train_rows, lpd_eval, eval=None):
     return out, arrays
 
 
+CRPS_GRAM_BYTES = 256 << 20             # --crps asks for the Gram matrices [N, C, C] fp64 only while they fit
+
+
+def crps_refusal(task, n_chains):
+    """Why --crps cannot run on this experiment, or None."""
+    if task != 'regr':
+        return ('--crps: the CRPS scores a predictive density on the real line, so it is for regression experiments; this one is '
+                'classification (--calibration is its counterpart)')
+    if n_chains > 1024:
+        return f'--crps: at most 1024 chains (mile_crps_stream); this experiment has {n_chains}'
+    return None
+
+
+def crps_outputs(n_rows, n_chains):
+    """The outputs --crps asks Engine.crps_stream for: ``gram`` only while N * C^2 * 8 B <= 256 MiB."""
+    base = ('crps_chain', 'spread_chain', 'crps_mix', 'spread_mix', 'dropped')
+    return base + (('gram',) if n_rows * n_chains * n_chains * 8 <= CRPS_GRAM_BYTES else ())
+
+
+def crps_metrics(rows, stride, stacked=None):
+    """--crps: the metrics.json keys and the crps.npz arrays of Engine.crps_stream's result ``rows`` (or
+    metrics.mixture_crps_dense's).  The call's weight vectors are 1 / C and, with ``stacked`` [C] (the weights of --stacking),
+    those: ``crps`` / ``crps_spread`` (the pooled ensemble of all kept draws), ``crps_uniform``, ``crps_stacked`` with their
+    standard errors over rows, what pooling gains over the chains one by one, each chain's own CRPS and spread with the
+    median, the largest row-mean energy distance between two chains (with ``gram``), the thinning stride and the draws dropped."""
+    from mile_amd.metrics import crps_summary
+    C_ = int(rows['crps_chain'].shape[0])
+    W = [np.full(C_, 1.0 / C_)] + ([np.asarray(stacked, dtype=np.float64)] if stacked is not None else [])
+    arrays = {k: v.detach().cpu().numpy() for k, v in rows.items()}
+    s = crps_summary(arrays, weights=np.stack(W))
+    out = {'crps': s['crps'], 'crps_se': s['crps_se'], 'crps_spread': s['spread'], 'crps_spread_se': s['spread_se'],
+           'crps_uniform': s['mix_crps'][0], 'crps_uniform_se': s['mix_crps_se'][0], 'crps_uniform_pooling_gain': s['mix_pooling_gain'][0],
+           'crps_per_chain': s['chain_crps'], 'crps_per_chain_median': float(np.nanmedian(s['chain_crps'])),
+           'crps_per_chain_spread': s['chain_spread'], 'crps_rows_nan': s['rows_nan'], 'crps_thin_stride': int(stride),
+           'crps_dropped': int(arrays['dropped'].sum())}
+    if stacked is not None:
+        out.update({'crps_stacked': s['mix_crps'][1], 'crps_stacked_se': s['mix_crps_se'][1],
+                    'crps_stacked_pooling_gain': s['mix_pooling_gain'][1]})
+    if 'energy_distance' in s:
+        out['crps_energy_distance_max'] = float(np.max(s['energy_distance']))
+        arrays['energy_distance'] = np.asarray(s['energy_distance'], dtype=np.float64)
+    arrays['weights'] = np.stack(W)
+    arrays['thin_stride'] = np.int64(stride)
+    return out, arrays
+
+
 def calibration_metrics(res, n_bins):
     """--calibration: the metrics.json keys and the calibration.npz arrays of a calibration result ``res``
     (Engine.calibration_stream, or metrics.classification_calibration of logits).  Keys: ``calibration_`` + every entry of the
@@ -270,6 +316,17 @@ def build_parser():
                          'stacking_effective_chains (1 / sum w^2), stacking_khat_bad (chain rows with khat > 0.7) and stacking_weights in '
                          'metrics.json; weights, chain_elpd_loo, chain_khat_bad, gap, n_train, n_train_used, n_eval in stacking.npz.  '
                          'Needs at least 2 draws per chain; --loo-r-eff applies')
+    ap.add_argument('--crps', action='store_true',
+                    help='regression: the exact CRPS of the predictive mixture on --split, from all pairs of draws on the device '
+                         '(mile_crps_stream; closed form, so no draws and no seed): crps (the pooled ensemble), crps_spread, '
+                         'crps_uniform (chains weighted 1 / C), each with _se over rows, crps_uniform_pooling_gain, crps_per_chain, '
+                         'crps_per_chain_median, crps_per_chain_spread, crps_energy_distance_max, crps_rows_nan, crps_thin_stride and '
+                         'crps_dropped in metrics.json; the per-row arrays crps_chain, spread_chain, crps_mix, spread_mix, dropped, '
+                         'weights, thin_stride (and gram, energy_distance while N C^2 8 B <= 256 MiB) in crps.npz.  With --stacking in '
+                         'the same call the stacked weights are scored too: crps_stacked, crps_stacked_se, crps_stacked_pooling_gain')
+    ap.add_argument('--crps-max-draws', type=int, default=131072, metavar='M',
+                    help='--crps thins every chain to its draws j = 0 mod k, k = ceil(n_chains * n_samples / M), so that about M '
+                         'draws enter the pair sums (default 131072; k is recorded as crps_thin_stride)')
     ap.add_argument('--loo-r-eff', '--r-eff', type=float, default=1.0, metavar='R_EFF',
                     help='relative efficiency of the draws behind the PSIS tail length of --loo and --stacking (default 1: independent draws)')
     ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
@@ -298,9 +355,15 @@ def main():
     if args.calibration is not None and cfg.data.task == 'regr':
         raise SystemExit('--calibration: prediction sets and reliability bins are for classification experiments; this one is '
                          'regression (--intervals is its counterpart)')
+    if args.crps and crps_refusal(cfg.data.task, 1):
+        raise SystemExit(crps_refusal(cfg.data.task, 1))
+    if args.crps and args.crps_max_draws < 1:
+        raise SystemExit('--crps-max-draws: at least 1')
     tr.build_model(cfg)
     spec = tr.prob_model.spec
     samples = load_samples_from_dir(exp / cfg.training.sampler._dir_name, spec)       # [C, S, d]
+    if args.crps and crps_refusal(cfg.data.task, samples.shape[0]):
+        raise SystemExit(crps_refusal(cfg.data.task, samples.shape[0]))
     if args.stacking and stacking_refusal(samples.shape[0], samples.shape[1]):
         raise SystemExit(stacking_refusal(samples.shape[0], samples.shape[1]))
     bad_chains = ~np.isfinite(samples).all(axis=(1, 2))
@@ -425,6 +488,19 @@ def main():
         keys, arrays = stacking_metrics(train_rows, lpd_eval, eval=eng.stack_eval)
         out.update(keys)
         np.savez(exp / 'stacking.npz', **arrays)
+    if args.crps:
+        from mile_amd.metrics import crps_thin_stride
+        k = crps_thin_stride(samples.shape[0], samples.shape[1], args.crps_max_draws)
+        thin = np.ascontiguousarray(samples[:, ::k])
+        stacked = np.clip(arrays['weights'], 0.0, None) if args.stacking else None      # (stacking.npz's, just solved)
+        C_ = thin.shape[0]
+        W = np.stack([np.full(C_, 1.0 / C_)] + ([stacked / stacked.sum()] if stacked is not None else []))
+        print(f'--crps: {C_} chains x {thin.shape[1]} draws (every {k}th of {samples.shape[1]}) on {x.shape[0]} rows')
+        rows = eng.crps_stream(torch.from_numpy(thin), torch.from_numpy(x), torch.from_numpy(np.ascontiguousarray(y)), weights=W,
+                               outputs=crps_outputs(x.shape[0], C_))
+        keys, arrays = crps_metrics(rows, k, stacked=W[1] if stacked is not None else None)
+        out.update(keys)
+        np.savez(exp / 'crps.npz', **arrays)
     if args.calibration is not None:
         xt, yt = torch.from_numpy(x), torch.from_numpy(np.ascontiguousarray(y))
         if spec.hidden_structure[-1] <= 64:

@@ -518,6 +518,50 @@ int64_t mile_chain_loo_stream_workspace(const mile_sampler *s, int32_t C, int64_
 int32_t mile_stack_eval(const double *lpd, const double *w, int32_t C, int64_t N, double *score, double *row_score, double *grad,
                         double *hess, int64_t *used, int64_t max_rows_per_tile, void *stream);
 
+/* Exact CRPS (continuous ranked probability score) of the predictive mixture, per chain and for chain-weighted mixtures, on the
+ * device.  Regression only; the reference has no counterpart.  raw [C * S, N, 2] fp32 (mu, log sigma) as mile_predict writes
+ * them, draw j of chain c at row c * S + j as in mile_lppd_stream; y [N] fp32 device; weights [n_w, C] fp64 on the HOST,
+ * 0 <= n_w <= 8, every vector >= 0, finite and summing to 1 within 1e-9.  mile_mixture_crps needs no handle.
+ *   sigma = clip(expf(log sigma), 1e-6, 1e6) as in mile_pointwise_loglik.  A draw with a non-finite mu or log sigma on row n is
+ *   left out of row n (per draw and per row, the rule of mile_predict_moments); K_c counts chain c's kept draws on the row and
+ *   dropped[c][n] = S - K_c.
+ *   A(d, v) = E|N(d, v)| = d erf(d / sqrt(2v)) + sqrt(2v / pi) exp(-d^2 / (2v)) >= 0.
+ *   a_c = (1 / K_c) sum_{i in c} A(y - mu_i, sigma_i^2), fp64.
+ *   G_cc' = (1 / (K_c K_c')) sum_{i in c} sum_{j in c'} A(mu_i - mu_j, sigma_i^2 + sigma_j^2), i = j included: pair terms in
+ *   fp32, summed in fp32 over fixed runs of at most 32 terms and in fp64 beyond, in a fixed order; pairs i < j of one chain
+ *   are computed once and counted twice, chain blocks c > c' are mirrored from c < c'.
+ *   crps_chain[c][n] = a_c - G_cc / 2, spread_chain[c][n] = G_cc / 2: chain c alone.
+ *   crps_mix[m][n] = sum_c w_c a_c - w'Gw / 2, spread_mix[m][n] = w'Gw / 2.  Row m = 0 is always the pooled ensemble,
+ *   w_c = K_c / sum K (the equal-weight mixture of all kept draws, the predictive of mile_mixture_quantiles); rows 1 .. n_w are
+ *   the caller's weight vectors in order.  A chain of weight 0 enters no sum.
+ *   gram[n][c][c'] = G_cc', exactly symmetric.  2 G_cc' - G_cc - G_c'c' >= 0 is the energy distance between two chains'
+ *   predictives on the row.
+ *   A chain with K_c = 0 has NaN in its own outputs and in its row and column of gram, is skipped by the pooled weights and
+ *   makes a caller's mixture with w_c > 0 NaN on that row; a row with nothing kept holds NaN everywhere.
+ * No floating-point atomics; how the pairs are split over workgroups depends on (C, S, N) alone, so a row's outputs depend on
+ * its draws alone, bit for bit.  The rows go in tiles (max_rows_per_tile > 0 caps them, 0: the library's choice) that keep a
+ * launch of the pair kernel within 2^37 pairs -- a single row at the least -- and the workspace within the evaluation budget.
+ * crps_chain, spread_chain [C, N], crps_mix, spread_mix [1 + n_w, N], gram [N, C, C] fp64 and dropped [C, N] int32 are device
+ * pointers; each may be null, but not all six.  A call for dropped alone launches no pair kernel.
+ * mile_mixture_crps allocates and frees its workspace in the call and returns after the kernels finish.
+ * mile_crps_stream is the same for draws theta [C * S, d] full-layout on X [N, F]: mile_predict's forward runs in row tiles and
+ * passes of at most max_draws_per_pass draws (0: all) into the handle's shared evaluation workspace, every (draw, row) forward
+ * exactly once, [C * S, N, 2] never held at once.  Its outputs are bitwise the same for every pass and tile size and equal to
+ * mile_mixture_crps of mile_predict's outputs.  mile_crps_stream_workspace: the bytes for the library's own tile.
+ * MILE_ERR_INVALID: a null raw / handle / theta / X / y, no output asked for, C < 1 or > 1024, S < 1, C * S > 2^20, N < 1 or
+ * > 2^30 - 1, n_w outside [0, 8] or n_w > 0 without weights, a weight negative or non-finite, |sum_c w_c - 1| > 1e-9, a negative
+ * pass or tile size, a handle whose task is not regression; MILE_ERR_STATE: frozen tables not set; MILE_ERR_NOMEM: the
+ * workspace.  Nothing is launched on any of them.
+ * (Added under ABI 10: three new symbols, no struct or existing entry changed.) */
+int32_t mile_mixture_crps(const float *raw, int32_t C, int64_t S, int64_t N, const float *y, const double *weights, int32_t n_w,
+                          double *crps_chain, double *spread_chain, double *crps_mix, double *spread_mix, double *gram,
+                          int32_t *dropped, int64_t max_rows_per_tile, void *stream);
+int32_t mile_crps_stream(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, const float *y, int64_t N,
+                         const double *weights, int32_t n_w, double *crps_chain, double *spread_chain, double *crps_mix,
+                         double *spread_mix, double *gram, int32_t *dropped, int64_t max_draws_per_pass, int64_t max_rows_per_tile,
+                         void *stream);
+int64_t mile_crps_stream_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N);   /* bytes; -1 out of range */
+
 /* Prediction sets and calibration of the classification ensemble, per chain and for the ensemble of all chains, on the device.
  * The reference stops before this (src/inference/evaluation.py:463-464).  raw [C * S, N, K] fp32 logits as mile_predict
  * writes them: draw j of chain c is row c * S + j, as in mile_lppd_stream (a deep ensemble's members are valid input).

@@ -35,6 +35,7 @@
 #include "mile_quantiles.h"
 #include "mile_loo.h"
 #include "mile_stack.h"
+#include "mile_crps.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -2616,6 +2617,155 @@ extern "C" int32_t mile_chain_loo_stream(mile_sampler *s, const float *theta, in
   if (rc0 != MILE_OK) return rc0;
   return loo_stream_chains(s, theta, C, S, X, y, N, r_eff, lppd, p_waic, elpd_loo, khat, dropped, max_draws_per_pass, max_rows_per_tile,
                            "mile_chain_loo_stream", (hipStream_t)stream);
+}
+
+// mile_mixture_crps / mile_crps_stream: every check before any launch; rows in tiles that respect the evaluation budget, the
+// pairs of one launch (CRPS_MAX_PAIRS_PER_LAUNCH) and the slots' bytes; k_crps_pack + k_crps_pairs + k_crps_finish per tile
+// (mile_crps.h).
+struct CrpsOut {
+  double *crps_chain, *spread_chain, *crps_mix, *spread_mix, *gram;
+  int32_t *dropped;
+  bool any() const { return crps_chain || spread_chain || crps_mix || spread_mix || gram || dropped; }
+  bool pairs() const { return crps_chain || spread_chain || crps_mix || spread_mix || gram; }
+};
+// what is wrong with the shape, the weights or the outputs asked for, or null
+static const char *crps_bad_args(int32_t C, int64_t S, int64_t N, const double *weights, int32_t n_w, const CrpsOut &o, int64_t max_rows) {
+  if (C < 1 || C > CRPS_MAX_C) return "C out of range (1 .. 1024)";
+  if (S < 1) return "S < 1";
+  if (S > CRPS_MAX_DRAWS || (int64_t)C * S > CRPS_MAX_DRAWS) return "C * S out of range (1 .. 2^20)";
+  if (N < 1 || N > 0x3fffffff) return "N out of range (1 .. 2^30 - 1)";
+  if (!o.any()) return "no output asked for";
+  if (n_w < 0 || n_w > CRPS_MAX_W) return "n_w out of range (0 .. 8)";
+  if (n_w > 0 && !weights) return "n_w > 0 without weights";
+  for (int m = 0; m < n_w; ++m) {
+    double sum = 0.0;
+    for (int c = 0; c < C; ++c) {
+      const double w = weights[(size_t)m * C + c];
+      if (!std::isfinite(w) || w < 0.0) return "weights must be finite and >= 0";
+      sum += w;
+    }
+    if (!(std::fabs(sum - 1.0) <= 1e-9)) return "every weight vector must sum to 1 (within 1e-9)";
+  }
+  if (max_rows < 0) return "max_rows_per_tile < 0";
+  return nullptr;
+}
+
+// rows of a tile; per_pair_bytes: 16 with the forward's raw block beside the packed copy, 8 with the caller's raw walked in place
+static int64_t crps_tile_rows(int64_t C, int64_t S, int64_t N, const CrpsPlan &pl, int64_t max_rows, int per_pair_bytes) {
+  const int64_t D = C * S;
+  int64_t nt = std::max<int64_t>(1, EVAL_PASS_TARGET / (D * per_pair_bytes));
+  nt = std::min(nt, std::max<int64_t>(1, CRPS_MAX_PAIRS_PER_LAUNCH / (D * (D + 1) / 2)));
+  nt = std::min(nt, std::max<int64_t>(1, CRPS_MAX_SLOT_BYTES / (pl.units * 8)));
+  nt = std::min(nt, std::max<int64_t>(1, CRPS_MAX_GRID / pl.units));
+  if (max_rows > 0) nt = std::min(nt, max_rows);
+  return std::min(nt, N);
+}
+
+// the tiles of one call: raw_all [C * S][N][2] is the caller's array, walked in place (ld = N), or null and `fill` writes each
+// tile's [C * S][Nt][2] block (ld = Nt).  tail: crps_tail_bytes of Nt rows.
+template <class Fill>
+static int crps_run(const float *raw_all, char *tail, int32_t C, int64_t S, int64_t N, int64_t Nt, const CrpsPlan &pl, const float *y,
+                    const double *weights, int32_t n_w, const CrpsOut &o, hipStream_t st, Fill fill) {
+  CrpsParams p{};
+  p.C = C; p.S = (int)S; p.pl = pl; p.N = N; p.n_w = n_w;
+  p.pk = (float2 *)tail;
+  char *at = tail + crps_r256((size_t)C * S * Nt * 8);
+  p.cnt = (int32_t *)at; at += crps_r256((size_t)Nt * C * 4);
+  p.part = (double *)at; at += crps_r256((size_t)Nt * pl.units * 8);
+  if (n_w > 0) {
+    HIP_TRY(hipMemcpyAsync(at, weights, (size_t)n_w * C * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));   // weights is the caller's host memory
+    p.w = (const double *)at;
+  }
+  p.crps_chain = o.crps_chain; p.spread_chain = o.spread_chain; p.crps_mix = o.crps_mix; p.spread_mix = o.spread_mix;
+  p.gram = o.gram; p.dropped = o.dropped;
+  for (int64_t r0 = 0; r0 < N; r0 += Nt) {
+    p.Nt = (int)std::min<int64_t>(Nt, N - r0);
+    p.r0 = r0;
+    if (raw_all) { p.raw = raw_all + 2 * r0; p.ld = N; }
+    else {
+      const float *tile = nullptr;
+      const int rc = fill(r0, p.Nt, &tile);
+      if (rc != MILE_OK) return rc;
+      p.raw = tile; p.ld = p.Nt;
+    }
+    p.y = y + r0;
+    HIP_TRY(mile_launch_crps_pack(p, st));
+    if (!o.pairs()) continue;
+    HIP_TRY(mile_launch_crps_pairs(p, st));
+    HIP_TRY(mile_launch_crps_finish(p, st));
+  }
+  return MILE_OK;
+}
+
+extern "C" int32_t mile_mixture_crps(const float *raw, int32_t C, int64_t S, int64_t N, const float *y, const double *weights, int32_t n_w,
+                                     double *crps_chain, double *spread_chain, double *crps_mix, double *spread_mix, double *gram,
+                                     int32_t *dropped, int64_t max_rows_per_tile, void *stream) {
+  auto bad = [](const char *m) { return fail(MILE_ERR_INVALID, std::string("mile_mixture_crps: ") + m); };
+  if (!raw || !y) return bad("null raw or y");
+  const CrpsOut o{crps_chain, spread_chain, crps_mix, spread_mix, gram, dropped};
+  if (const char *m = crps_bad_args(C, S, N, weights, n_w, o, max_rows_per_tile)) return bad(m);
+  hipStream_t st = (hipStream_t)stream;
+  const CrpsPlan pl = crps_plan(C, S, N);
+  const int64_t Nt = crps_tile_rows(C, S, N, pl, max_rows_per_tile, 8);   // the packed copy alone: raw is the caller's
+  void *ws = nullptr;
+  if (hipMalloc(&ws, crps_tail_bytes(C, S, Nt, pl)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MILE_ERR_NOMEM, "mile_mixture_crps: workspace allocation failed (lower max_rows_per_tile)");
+  }
+  const int rc = crps_run(raw, (char *)ws, C, S, N, Nt, pl, y, weights, n_w, o, st,
+                          [](int64_t, int, const float **) { return (int)MILE_OK; });
+  const hipError_t es = hipStreamSynchronize(st);   // the workspace is this call's: the kernels finish before it goes
+  (void)hipFree(ws);
+  if (rc != MILE_OK) return rc;
+  HIP_TRY(es);
+  return MILE_OK;
+}
+
+extern "C" int64_t mile_crps_stream_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N) {
+  if (!s || C < 1 || C > CRPS_MAX_C || S < 1 || S > CRPS_MAX_DRAWS || (int64_t)C * S > CRPS_MAX_DRAWS || N < 1 || N > 0x3fffffff) return -1;
+  const CrpsPlan pl = crps_plan(C, S, N);
+  const int64_t Nt = crps_tile_rows(C, S, N, pl, 0, 16);
+  return (int64_t)(crps_r256((size_t)C * S * Nt * 8) + crps_tail_bytes(C, S, Nt, pl));
+}
+
+extern "C" int32_t mile_crps_stream(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, const float *y, int64_t N,
+                                    const double *weights, int32_t n_w, double *crps_chain, double *spread_chain, double *crps_mix,
+                                    double *spread_mix, double *gram, int32_t *dropped, int64_t max_draws_per_pass,
+                                    int64_t max_rows_per_tile, void *stream) {
+  const CrpsOut o{crps_chain, spread_chain, crps_mix, spread_mix, gram, dropped};
+  if (s && theta && X && y)
+    if (const char *m = crps_bad_args(C, S, N, weights, n_w, o, max_rows_per_tile)) return fail(MILE_ERR_INVALID, std::string("mile_crps_stream: ") + m);
+  const int rc0 = eval_args("mile_crps_stream", s, !theta || !X || !y, 1, 1, [&]() -> const char * {
+    if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
+    if (s->spec.task != MILE_TASK_REGRESSION || s->spec.widths[s->spec.n_layers - 1] != 2)
+      return "needs a regression model with (mu, log sigma) outputs";
+    return nullptr;
+  });
+  if (rc0 != MILE_OK) return rc0;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->device));
+  const int64_t D = (int64_t)C * S;
+  const CrpsPlan pl = crps_plan(C, S, N);
+  const int64_t Nt = crps_tile_rows(C, S, N, pl, max_rows_per_tile, 16);
+  const int64_t chunk = std::min<int64_t>(D, max_draws_per_pass ? max_draws_per_pass : D);
+  const size_t raw_bytes = crps_r256((size_t)D * Nt * 8);
+  if (reserve_eval_ws(s, raw_bytes + crps_tail_bytes(C, S, Nt, pl)) != hipSuccess)
+    return fail(MILE_ERR_NOMEM, "mile_crps_stream: workspace allocation failed (lower max_rows_per_tile)");
+  float *raw = (float *)s->eval_ws;
+  const size_t row_floats = (size_t)s->spec.in_features;
+  auto fill = [&](int64_t r0, int nt, const float **tile) -> int {   // every (draw, row) forward once: passes at their draw offset
+    PredParams pp;
+    const int rc1 = stage_rows(s, (const float *)X + (size_t)r0 * row_floats, nullptr, nt, pp, st);
+    if (rc1 != MILE_OK) return rc1;
+    for (int64_t s0 = 0; s0 < D; s0 += chunk) {
+      const int rc = eval_forward(s, pp, theta + (size_t)s0 * s->ds.d, std::min<int64_t>(chunk, D - s0), raw + (size_t)s0 * nt * 2, st);
+      if (rc != MILE_OK) return rc;
+    }
+    *tile = raw;
+    return MILE_OK;
+  };
+  return crps_run(nullptr, (char *)s->eval_ws + raw_bytes, C, S, N, Nt, pl, y, weights, n_w, o, st, fill);
 }
 
 // mile_stack_eval: every check before any launch; rows in tiles whose responsibilities fit 256 MiB, k_stk_rows + k_stk_gram per

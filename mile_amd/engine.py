@@ -818,6 +818,70 @@ class Engine:
                                                 ptr('used'), int(max_rows_per_tile), self._stream()), self.lib)
         return out
 
+    def _crps_call(self, C_, N, y, weights, outputs):
+        """What both CRPS methods share: y [N] fp32 on the device, the checked host weights and their pointer, the output
+        tensors and a pointer getter."""
+        from mile_amd.metrics import CRPS_OUTPUTS, crps_weights
+        outputs = tuple(outputs)
+        if not outputs or any(k not in CRPS_OUTPUTS for k in outputs):
+            raise ValueError(f'outputs: a non-empty choice of {CRPS_OUTPUTS}')
+        y = torch.as_tensor(y, device=self.device).to(torch.float32).reshape(-1).contiguous()
+        if y.shape != (N,):
+            raise ValueError('y must be [N]')
+        W = crps_weights(weights, C_)
+        n_w = int(W.shape[0])
+        w_c = (C.c_double * max(1, n_w * C_))(*W.reshape(-1).tolist())
+        shapes = {'crps_chain': (C_, N), 'spread_chain': (C_, N), 'crps_mix': (1 + n_w, N), 'spread_mix': (1 + n_w, N),
+                  'gram': (N, C_, C_), 'dropped': (C_, N)}
+        out = {k: torch.empty(shapes[k], dtype=torch.int32 if k == 'dropped' else torch.float64, device=self.device) for k in outputs}
+        return y, (w_c if n_w else None), n_w, out, (lambda k: _ptr(out[k]) if k in out else None)
+
+    def mixture_crps(self, raw, y, weights=None, outputs=('crps_chain', 'spread_chain', 'crps_mix', 'spread_mix', 'dropped'),
+                     max_rows_per_tile: int = 0) -> dict:
+        """The exact CRPS of the mixture of Normals that raw outputs [C, S, N, 2] (mu, log sigma) describe on each row, against
+        y [N], by the library's pair kernel (mile_mixture_crps): the ``outputs`` asked for among ``crps_chain``,
+        ``spread_chain`` [C, N] (every chain alone: its CRPS and half the expected distance of two of its draws), ``crps_mix``,
+        ``spread_mix`` [1 + n_w, N] (row 0 the pooled ensemble of all kept draws, then the chain-weighted mixtures of
+        ``weights`` [n_w, C] or [C], at most 8 vectors on the simplex), ``gram`` [N, C, C] (the mean pair term between chains,
+        exactly symmetric) and ``dropped`` [C, N] int32 -- fp64 device tensors, ``metrics.mixture_crps_dense`` of the same
+        inputs.  The raw outputs may come from anywhere -- ``predict``, or a deep ensemble's members as chains of one draw."""
+        raw = _f32(raw, self.device, name='raw')
+        if raw.ndim != 4 or raw.shape[-1] != 2:
+            raise ValueError('raw must be [C, S, N, 2]')
+        C_, S_, N = (int(v) for v in raw.shape[:3])
+        r = raw.contiguous()
+        y, w_c, n_w, out, ptr = self._crps_call(C_, N, y, weights, outputs)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_mixture_crps(_ptr(r), C_, S_, N, _ptr(y), w_c, n_w, ptr('crps_chain'), ptr('spread_chain'),
+                                                  ptr('crps_mix'), ptr('spread_mix'), ptr('gram'), ptr('dropped'),
+                                                  int(max_rows_per_tile), self._stream()), self.lib)
+        return out
+
+    def crps_stream_workspace(self, C_: int, S: int, N: int) -> int:
+        """Bytes of the workspace ``crps_stream`` keeps in the handle for C chains of S draws on N rows with the library's own
+        tile (mile_crps_stream_workspace)."""
+        return int(self.lib.mile_crps_stream_workspace(self._h, int(C_), int(S), int(N)))
+
+    def crps_stream(self, samples, X, y, weights=None, outputs=('crps_chain', 'spread_chain', 'crps_mix', 'spread_mix', 'dropped'),
+                    max_draws_per_pass: int = 0, max_rows_per_tile: int = 0) -> dict:
+        """``mixture_crps`` of ``predict``'s outputs for samples [C, S, d] on (X [N, F], y [N]) without ever holding them
+        (mile_crps_stream): the rows go in tiles of at most ``max_rows_per_tile`` (0: the library's choice), the forward inside
+        a tile in passes of at most ``max_draws_per_pass`` draws (0: all).  The result does not depend on the two sizes, bit
+        for bit.  Regression only."""
+        if self.spec.task != 'regr':
+            raise ValueError('crps_stream: a regression model is needed')
+        samples = _f32(samples, self.device, name='samples')
+        if samples.ndim != 3 or samples.shape[2] != self.d:
+            raise ValueError(f'samples must be [C, S, {self.d}]')
+        (C_, S_), th, X, _ = self._eval_inputs(samples, X)
+        N = int(X.shape[0])
+        y, w_c, n_w, out, ptr = self._crps_call(C_, N, y, weights, outputs)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_crps_stream(self._h, _ptr(th), C_, S_, _ptr(X), _ptr(y), N, w_c, n_w, ptr('crps_chain'),
+                                                 ptr('spread_chain'), ptr('crps_mix'), ptr('spread_mix'), ptr('gram'), ptr('dropped'),
+                                                 int(max_draws_per_pass), int(max_rows_per_tile), self._stream()), self.lib)
+        return out
+
     @staticmethod
     def _calibration_levels(coverages):
         lv = [float(v) for v in torch.as_tensor(coverages, dtype=torch.float64).reshape(-1)]

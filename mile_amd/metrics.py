@@ -833,3 +833,139 @@ def stacking_summary(rows: dict) -> dict:
                 'chain_rows_nan': [int(v) for v in np.isnan(a['elpd_loo']).sum(axis=1)],
                 'chain_khat_bad': [int(v) for v in (np.isfinite(a['khat']) & (a['khat'] > 0.7)).sum(axis=1)],
                 'n_rows': int(a['elpd_loo'].shape[1])}
+
+
+CRPS_OUTPUTS = ('crps_chain', 'spread_chain', 'crps_mix', 'spread_mix', 'gram', 'dropped')
+CRPS_MAX_WEIGHTS = 8
+
+
+def crps_weights(weights, C: int) -> torch.Tensor:
+    """Chain weight vectors for the CRPS of a weighted mixture, checked as the library checks them: None -> [0, C]; [C] or
+    [n_w, C] with n_w <= 8, every entry finite and >= 0, every vector summing to 1 within 1e-9 -> float64 [n_w, C] on the host."""
+    if weights is None:
+        return torch.zeros((0, C), dtype=torch.float64)
+    w = torch.as_tensor(weights, dtype=torch.float64).detach().cpu()        # (a list goes straight to fp64, not through fp32)
+    if w.ndim == 1:
+        w = w[None]
+    if w.ndim != 2 or w.shape[1] != C:
+        raise ValueError(f'weights must be [{C}] or [n_w, {C}]')
+    if w.shape[0] > CRPS_MAX_WEIGHTS:
+        raise ValueError(f'weights: at most {CRPS_MAX_WEIGHTS} vectors')
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError('weights must be finite and >= 0')
+    if bool(((w.sum(dim=1) - 1.0).abs() > 1e-9).any()):
+        raise ValueError('every weight vector must sum to 1 (within 1e-9)')
+    return w.contiguous()
+
+
+def crps_thin_stride(C: int, S: int, max_draws: int) -> int:
+    """k = ceil(C * S / max_draws), at least 1: every chain keeps its draws j = 0 mod k (``samples[:, ::k]``), so at most
+    about ``max_draws`` draws enter the CRPS's pair sums."""
+    if max_draws < 1:
+        raise ValueError('max_draws must be >= 1')
+    return max(1, -(-(int(C) * int(S)) // int(max_draws)))
+
+
+def _abs_normal_mean(d: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """A(d, v) = E|N(d, v)| = d erf(d / sqrt(2 v)) + sqrt(2 v / pi) exp(-d^2 / (2 v))."""
+    return d * torch.erf(d / torch.sqrt(2.0 * v)) + torch.sqrt(2.0 * v / math.pi) * torch.exp(-d * d / (2.0 * v))
+
+
+def mixture_crps_dense(raw: torch.Tensor, y, weights=None, outputs=CRPS_OUTPUTS, budget: int = 1 << 24) -> dict:
+    """The exact CRPS of the predictive mixture in torch float64, on raw's device: raw [C, S, N, 2] (mu, log sigma), y [N],
+    weights as ``crps_weights`` takes them -> the ``outputs`` asked for among ``crps_chain``, ``spread_chain`` [C, N],
+    ``crps_mix``, ``spread_mix`` [1 + n_w, N] (row 0 the pooled ensemble, w_c = K_c / sum K), ``gram`` [N, C, C] and
+    ``dropped`` [C, N] int32 -- what ``Engine.mixture_crps`` computes, with every pair term in fp64.  The pairs go in chunks of
+    at most ``budget`` terms.  A draw with a non-finite output on a row is left out of that row; a chain with nothing kept has
+    NaN in its own outputs, is skipped by the pooled weights and makes a weighted mixture that uses it NaN."""
+    outputs = tuple(outputs)
+    if not outputs or any(k not in CRPS_OUTPUTS for k in outputs):
+        raise ValueError(f'outputs: a non-empty choice of {CRPS_OUTPUTS}')
+    if raw.ndim != 4 or raw.shape[-1] != 2:
+        raise ValueError('raw must be [C, S, N, 2]')
+    C, S, N = (int(v) for v in raw.shape[:3])
+    W = crps_weights(weights, C).to(raw.device)
+    ok = torch.isfinite(raw).all(dim=-1)                                   # [C, S, N]
+    o = torch.where(ok[..., None], raw, torch.zeros_like(raw)).to(torch.float64)
+    mu, var = o[..., 0], torch.exp(o[..., 1]).clamp(min=1e-6, max=1e6) ** 2
+    okf = ok.to(torch.float64)
+    K = okf.sum(dim=1)                                                     # [C, N]
+    yv = torch.as_tensor(y, device=raw.device).to(torch.float64).reshape(-1)
+    if yv.shape != (N,):
+        raise ValueError('y must be [N]')
+    a = (_abs_normal_mean(yv[None, None] - mu, var) * okf).sum(dim=1) / K  # [C, N]
+    G = torch.empty((N, C, C), dtype=torch.float64, device=raw.device)
+    step = max(1, budget // max(1, S * N))
+    for c in range(C):
+        for c2 in range(c, C):
+            tot = torch.zeros(N, dtype=torch.float64, device=raw.device)
+            for i0 in range(0, S, step):
+                d = mu[c, i0:i0 + step, None] - mu[c2, None]              # [i, S, N]
+                v = var[c, i0:i0 + step, None] + var[c2, None]
+                tot += (_abs_normal_mean(d, v) * okf[c, i0:i0 + step, None] * okf[c2, None]).sum(dim=(0, 1))
+            G[:, c, c2] = G[:, c2, c] = tot / (K[c] * K[c2])
+    diag = torch.diagonal(G, dim1=1, dim2=2).T                            # [C, N]
+    Ktot = K.sum(dim=0)
+    pooled = torch.where(Ktot > 0, K / Ktot, torch.full_like(K, float('nan'))).T      # [N, C]
+    t1, t2 = [], []
+    for m in range(1 + W.shape[0]):
+        w = pooled if m == 0 else W[m - 1][None].expand(N, C)
+        ww = w[:, :, None] * w[:, None, :]
+        t1.append(torch.where(w == 0, torch.zeros_like(w), w * a.T).sum(dim=1))
+        t2.append(torch.where(ww == 0, torch.zeros_like(ww), ww * G).sum(dim=(1, 2)))
+    t1, t2 = torch.stack(t1), torch.stack(t2)
+    res = {'crps_chain': a - 0.5 * diag, 'spread_chain': 0.5 * diag, 'crps_mix': t1 - 0.5 * t2, 'spread_mix': 0.5 * t2,
+           'gram': G, 'dropped': (S - ok.sum(dim=1)).to(torch.int32)}
+    return {k: res[k] for k in outputs}
+
+
+def crps_summary(rows: dict, weights=None) -> dict:
+    """Totals of the per-row CRPS arrays (``Engine.crps_stream`` / ``mixture_crps_dense``), on the host in fp64.  Means run over
+    the rows with a finite value, standard errors are sd / sqrt(rows).  ``crps``, ``crps_se``, ``spread``, ``spread_se``: the
+    pooled ensemble (row 0 of the mix arrays); ``mix_crps`` ... ``mix_spread_se``: lists over the caller's weight vectors;
+    ``chain_crps`` ... ``chain_spread_se``: lists over the chains.  With ``weights`` [n_w, C] (those of the call) also
+    ``mix_pooling_gain``, the mean over rows of sum_c w_c crps_chain[c] - crps_mix: what pooling the chains gains over scoring
+    them one by one, >= 0 up to rounding.  With ``gram`` also ``energy_distance`` [C][C], the row mean of
+    2 G_cc' - G_cc - G_c'c'.  Keys whose arrays are absent are left out."""
+    import numpy as np
+    a = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float64)
+         for k, v in rows.items() if k in CRPS_OUTPUTS and k != 'dropped'}
+
+    def mean_se(x):
+        out = []
+        for r in np.atleast_2d(x):
+            f = r[np.isfinite(r)]
+            m = float(f.mean()) if f.size else float('nan')
+            se = float(f.std(ddof=1) / math.sqrt(f.size)) if f.size > 1 else float('nan')
+            out.append((m, se))
+        return out
+
+    res = {}
+    for key, name in (('crps_mix', 'crps'), ('spread_mix', 'spread')):
+        if key in a:
+            ms = mean_se(a[key])
+            res[name], res[name + '_se'] = ms[0]
+            res['mix_' + name], res['mix_' + name + '_se'] = [m for m, _ in ms[1:]], [s for _, s in ms[1:]]
+            res['n_rows'] = int(a[key].shape[1])
+            res['rows_nan'] = int((~np.isfinite(a[key][0])).sum())
+    for key, name in (('crps_chain', 'chain_crps'), ('spread_chain', 'chain_spread')):
+        if key in a:
+            ms = mean_se(a[key])
+            res[name], res[name + '_se'] = [m for m, _ in ms], [s for _, s in ms]
+    if weights is not None and 'crps_chain' in a and 'crps_mix' in a:
+        W = crps_weights(weights, a['crps_chain'].shape[0]).numpy()
+        gains = []
+        for m in range(W.shape[0]):
+            use = W[m] != 0
+            g = (W[m][use, None] * a['crps_chain'][use]).sum(axis=0) - a['crps_mix'][1 + m]
+            gains.append(mean_se(g)[0][0])
+        res['mix_pooling_gain'] = gains
+    if 'gram' in a:
+        G = a['gram']
+        d = np.diagonal(G, axis1=1, axis2=2)
+        with np.errstate(invalid='ignore'):
+            D2 = 2.0 * G - d[:, :, None] - d[:, None, :]
+            fin = np.isfinite(D2)
+            cnt = fin.sum(axis=0)
+            res['energy_distance'] = (np.where(fin, D2, 0.0).sum(axis=0) / np.where(cnt > 0, cnt, 1)).tolist()
+    return res
