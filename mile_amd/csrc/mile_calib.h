@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "../../include/mile_hip.h"
+#include "mile_eval_plan.h"
 
 #define CAL_NT 64          // k_cal_accum workgroup: one wave
 #define CAL_KC 16          // classes whose sums a thread of k_cal_accum holds in registers at a time
@@ -66,7 +67,6 @@ struct CalParams {
 };
 
 __host__ __device__ static inline int cal_cols(int Q, int n_bins) { return 5 + 2 * Q + 3 * n_bins; }
-static inline size_t cal_r256(size_t b) { return (b + 255) / 256 * 256; }
 // rows per reduction block: a function of the call's shape alone, never of its tiling
 static inline int64_t cal_block_rows(int64_t N, int G, int W) {
   int64_t B = CAL_BLOCK;
@@ -75,13 +75,13 @@ static inline int64_t cal_block_rows(int64_t N, int G, int W) {
 }
 static inline size_t cal_part_bytes(int64_t N, int G, int W) {
   const int64_t B = cal_block_rows(N, G, W);
-  return cal_r256((size_t)G * (size_t)((N + B - 1) / B) * W * 8);
+  return r256((size_t)G * (size_t)((N + B - 1) / B) * W * 8);
 }
 // per tile row: the chains' sums and counts, and the groups' records
 static inline size_t cal_row_bytes(int C, int K) { return (size_t)C * ((size_t)K * 8 + 4) + (size_t)(C + 1) * sizeof(CalRec); }
-static inline size_t cal_sum_bytes(int C, int K, int64_t Nt) { return cal_r256((size_t)C * Nt * K * 8); }
-static inline size_t cal_cnt_bytes(int C, int64_t Nt) { return cal_r256((size_t)C * Nt * 4); }
-static inline size_t cal_rec_bytes(int C, int64_t Nt) { return cal_r256((size_t)(C + 1) * Nt * sizeof(CalRec)); }
+static inline size_t cal_sum_bytes(int C, int K, int64_t Nt) { return r256((size_t)C * Nt * K * 8); }
+static inline size_t cal_cnt_bytes(int C, int64_t Nt) { return r256((size_t)C * Nt * 4); }
+static inline size_t cal_rec_bytes(int C, int64_t Nt) { return r256((size_t)(C + 1) * Nt * sizeof(CalRec)); }
 
 hipError_t mile_launch_cal_accum(const CalParams &p, hipStream_t st);
 hipError_t mile_launch_cal_rows(const CalParams &p, hipStream_t st);    // k_cal_rows, then (with y) k_cal_part

@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "../../include/mile_hip.h"
+#include "mile_eval_plan.h"
 
 #define CRPS_NT 256                       // workgroup of every kernel: four waves
 #define CRPS_R 4                          // i-draws a thread of k_crps_pairs keeps
@@ -82,13 +83,6 @@ struct CrpsParams {
   double *gram;                        // [N, C, C], or null
   int32_t *dropped;                    // [C, N], or null
 };
-
-static inline size_t crps_r256(size_t b) { return (b + 255) / 256 * 256; }
-// bytes behind the raw block for tiles of Nt rows: the packed copy, the counts, the slots, the weights
-static inline size_t crps_tail_bytes(int64_t C, int64_t S, int64_t Nt, const CrpsPlan &pl) {
-  return crps_r256((size_t)C * S * Nt * 8) + crps_r256((size_t)Nt * C * 4) + crps_r256((size_t)Nt * pl.units * 8) +
-         crps_r256((size_t)CRPS_MAX_W * C * 8);
-}
 
 hipError_t mile_launch_crps_pack(const CrpsParams &p, hipStream_t st);
 hipError_t mile_launch_crps_pairs(const CrpsParams &p, hipStream_t st);

@@ -29,6 +29,7 @@
 #include "mile_update.h"
 #include "mile_nuts.h"
 #include "mile_diag.h"
+#include "mile_eval_plan.h"
 #include "mile_moments.h"
 #include "mile_calib.h"
 #include "mile_lppd.h"
@@ -84,10 +85,8 @@ struct mile_sampler {
   int nz_E = 0;                         // particle rows nzbuf holds (allocated by the first mile_step that prefills)
   int64_t nz_launches = 0;              // mid-step launches that prefilled noise (mile_debug_prefill_count)
   void *ev_rows = nullptr; size_t ev_rows_bytes = 0;   // evaluation (test) set staging: X, its padded copy and y (stage_rows)
-  // the streamed evaluation calls' one workspace (reserve_eval_ws): a pass of forward outputs, then the call's own state --
-  // moments: the accumulators; LPPD: the (m, s) state and partial sums; quantiles: the packed copy, brackets and sweeps;
-  // calibration: the chains' sums, the groups' records and the blocks' partial sums;
-  // LOO: the packed copy
+  // the streamed evaluation calls' one workspace (reserve_eval_ws): a pass's or a tile's forward outputs first, then the call's
+  // own state at the offsets of its plan (qnt_ / loo_ / crps_ / cal_tile_plan; moments and LPPD lay theirs out in place)
   void *eval_ws = nullptr; size_t eval_ws_bytes = 0;
   const int32_t *qnt_sweeps = nullptr; int64_t qnt_rows = 0;   // sweeps per row of the last mile_predict_quantiles, in eval_ws
   float *alt_x = nullptr, *alt_u = nullptr, *alt_g = nullptr, *alt_logp = nullptr;   // ping-pong state of mile_tune
@@ -2179,7 +2178,6 @@ static const GradKernel &grad_kernel(int kernel) { return kGrad[kernel - 1]; }
 static int stage_rows(mile_sampler *s, const float *X, const void *y, int64_t N, PredParams &pp, hipStream_t st) {
   HIP_TRY(hipSetDevice(s->device));
   const int F = s->spec.in_features, Npad = ((int)N + 31) / 32 * 32, Fp = (F + 7) / 8 * 8;
-  auto r256 = [](size_t b) { return (b + 255) / 256 * 256; };
   const size_t x_bytes = r256((size_t)Npad * F * 4), xp_bytes = r256((size_t)Npad * Fp * 4);
   HIP_TRY(grow(s->ev_rows, s->ev_rows_bytes, x_bytes + xp_bytes + (size_t)Npad * 4, 1));   // evaluation is off the stepping path
   float *ev_X = (float *)s->ev_rows, *ev_Xp = (float *)((char *)s->ev_rows + x_bytes);
@@ -2198,12 +2196,31 @@ static int stage_rows(mile_sampler *s, const float *X, const void *y, int64_t N,
 
 // The one forward of evaluation: the resolved kernel's `loglik` of S samples (rows of theta) on the staged rows pp, into
 // out [S, N] -- or, staged without labels, the raw outputs [S, N, O] -- in launches of at most MILE_GRID_Y_MAX samples.
+static size_t eval_per_sample(const mile_sampler *s, const PredParams &pp) {   // floats of out per sample
+  return (size_t)pp.N * (pp.y ? 1 : (size_t)s->spec.widths[s->spec.n_layers - 1]);
+}
 static int eval_forward(mile_sampler *s, PredParams pp, const float *theta, int64_t S, float *out, hipStream_t st) {
   const GradKernel &gk = grad_kernel(resolved_kernel(s));
-  const size_t per_sample = (size_t)pp.N * (pp.y ? 1 : (size_t)s->spec.widths[s->spec.n_layers - 1]);   // floats of out
+  const size_t per_sample = eval_per_sample(s, pp);
   for (int64_t s0 = 0; s0 < S; s0 += MILE_GRID_Y_MAX) {
     pp.theta = theta + (size_t)s0 * s->ds.d; pp.out = out + (size_t)s0 * per_sample;
     const int rc = gk.loglik(s, pp, (int)std::min<int64_t>(MILE_GRID_Y_MAX, S - s0), st);
+    if (rc != MILE_OK) return rc;
+  }
+  return MILE_OK;
+}
+// D consecutive draws in passes of `chunk`, each pass at its draw offset of out [D][per sample]: every (draw, row) forward once
+static int forward_draws(mile_sampler *s, const PredParams &pp, const float *theta, int64_t D, int64_t chunk, float *out, hipStream_t st) {
+  for (int64_t s0 = 0; s0 < D; s0 += chunk) {
+    const int rc = eval_forward(s, pp, theta + (size_t)s0 * s->ds.d, std::min<int64_t>(chunk, D - s0), out + (size_t)s0 * eval_per_sample(s, pp), st);
+    if (rc != MILE_OK) return rc;
+  }
+  return MILE_OK;
+}
+// draws j0 .. j0 + J of each of C chains of S draws (chain c's are rows c * S + j0 .. of theta) into out [C][J][per sample]
+static int forward_chains(mile_sampler *s, const PredParams &pp, const float *theta, int C, int64_t S, int64_t j0, int J, float *out, hipStream_t st) {
+  for (int c = 0; c < C; ++c) {
+    const int rc = eval_forward(s, pp, theta + ((size_t)c * S + (size_t)j0) * s->ds.d, J, out + (size_t)c * J * eval_per_sample(s, pp), st);
     if (rc != MILE_OK) return rc;
   }
   return MILE_OK;
@@ -2217,14 +2234,26 @@ static int evaluate_rows(mile_sampler *s, const float *theta, int32_t S, const f
   return rc != MILE_OK ? rc : eval_forward(s, pp, theta, S, out, st);
 }
 
-// What every evaluation entry point `fn` on a handle checks before anything else, in this order: null arguments, S, N, the call's
-// own checks (`more`: a message or null; it may read *s), then the frozen tables.  MILE_OK, or the failure with its message set.
+// The checks that the evaluation calls share, each a message or null: the range of N, the generic shape of a call (S, then
+// N), the signs of the caller's pass and tile caps, the model of the statistics of a Gaussian predictive.
+static const char *bad_N(int64_t N) { return N < 1 || N > 0x3fffffff ? "N out of range (1 .. 2^30 - 1)" : nullptr; }
+static const char *bad_SN(int64_t S, int64_t N) { return S < 1 || S > 0x7fffffff ? "S out of range (1 .. 2^31 - 1)" : bad_N(N); }
+static const char *bad_caps(int64_t max_draws_per_pass, int64_t max_rows_per_tile) {
+  if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
+  return max_rows_per_tile < 0 ? "max_rows_per_tile < 0" : nullptr;
+}
+static const char *not_mu_log_sigma(const mile_sampler *s) {
+  return s->spec.task != MILE_TASK_REGRESSION || s->spec.widths[s->spec.n_layers - 1] != 2 ? "needs a regression model with (mu, log sigma) outputs" : nullptr;
+}
+
+// What every evaluation entry point `fn` on a handle checks before anything else, in this order: null arguments, the shape
+// (`shape`: the statistic's own message or null, bad_SN for most), the call's other checks (`more`: a message or null; it may
+// read *s), then the frozen tables.  MILE_OK, or the failure with its message set.
 template <class More>
-static int eval_args(const char *fn, const mile_sampler *s, bool null_arg, int64_t S, int64_t N, More more) {
+static int eval_args(const char *fn, const mile_sampler *s, bool null_arg, const char *shape, More more) {
   auto bad = [&](const char *m) { return fail(MILE_ERR_INVALID, std::string(fn) + ": " + m); };
   if (!s || null_arg) return bad("null argument");
-  if (S < 1 || S > 0x7fffffff) return bad("S out of range (1 .. 2^31 - 1)");
-  if (N < 1 || N > 0x3fffffff) return bad("N out of range (1 .. 2^30 - 1)");
+  if (shape) return bad(shape);
   if (const char *m = more()) return bad(m);
   if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
   return MILE_OK;
@@ -2237,21 +2266,58 @@ static hipError_t reserve_eval_ws(mile_sampler *s, size_t bytes) {
   return grow(s->eval_ws, s->eval_ws_bytes, bytes, 1);
 }
 
+// The tensor-input calls' workspace of `bytes` (0: none), this call's own: `run` gets it, and the stream is drained before it is
+// freed, whatever run returned.  run's code goes before the synchronise's; no memory is MILE_ERR_NOMEM with `nomem`.
+template <class Run>
+static int with_call_ws(size_t bytes, const char *nomem, hipStream_t st, Run run) {
+  void *ws = nullptr;
+  if (bytes && hipMalloc(&ws, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MILE_ERR_NOMEM, nomem);
+  }
+  const int rc = run((char *)ws);
+  const hipError_t es = hipStreamSynchronize(st);   // the kernels finish before their workspace goes
+  if (ws) (void)hipFree(ws);
+  if (rc != MILE_OK) return rc;
+  HIP_TRY(es);
+  return MILE_OK;
+}
+// the compute units of the current device, for the tensor-input calls that size a grid by them
+static int current_cus(int *n_cu) {
+  int dev = 0;
+  *n_cu = 256;
+  HIP_TRY(hipGetDevice(&dev));
+  (void)hipDeviceGetAttribute(n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+  return MILE_OK;
+}
+
+// Where a tile's block of forward outputs lies and how many rows each draw has in it.  A statistic's tile loop asks its source
+// for the tile of rows r0 .. r0 + nt: a tensor-input call answers with the caller's array at the tile's first row (ld = N), a
+// streamed call stages the rows, forwards every draw into the workspace and answers with that (ld = nt).
+struct Tile { const float *at; int64_t ld; };
+// the streamed source of the statistics that read raw outputs: the block [D][nt][O] at the start of eval_ws
+static auto stream_tiles(mile_sampler *s, const float *theta, int64_t D, int64_t chunk, const void *X, hipStream_t st) {
+  return [=](int64_t r0, int nt, Tile &t) -> int {
+    PredParams pp;
+    const int rc = stage_rows(s, (const float *)X + (size_t)r0 * s->spec.in_features, nullptr, nt, pp, st);
+    t = {(const float *)s->eval_ws, nt};
+    return rc != MILE_OK ? rc : forward_draws(s, pp, theta, D, chunk, (float *)s->eval_ws, st);
+  };
+}
+
 extern "C" int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, int32_t S, const float *X, const void *y,
                                          int64_t N, float *out, void *stream) {
-  const int rc = eval_args("mile_pointwise_loglik", s, !theta || !X || !y || !out, S, N, no_more_checks);
+  const int rc = eval_args("mile_pointwise_loglik", s, !theta || !X || !y || !out, bad_SN(S, N), no_more_checks);
   return rc != MILE_OK ? rc : evaluate_rows(s, theta, S, X, y, N, out, stream);
 }
 
 extern "C" int32_t mile_predict(mile_sampler *s, const float *theta, int32_t S, const float *X, int64_t N, float *out, void *stream) {
-  const int rc = eval_args("mile_predict", s, !theta || !X || !out, S, N, no_more_checks);
+  const int rc = eval_args("mile_predict", s, !theta || !X || !out, bad_SN(S, N), no_more_checks);
   return rc != MILE_OK ? rc : evaluate_rows(s, theta, S, X, nullptr, N, out, stream);
 }
 
 // mile_predict_moments: mile_predict's forward in passes of `chunk` draws into the library's workspace, each folded into the
 // per-row accumulators by k_moments_accum; k_moments_finish writes out.  Every check before any launch.
-static const int64_t EVAL_PASS_TARGET = (int64_t)256 << 20;   // bytes of forward outputs per pass (moments, streamed LPPD) when the caller leaves the choice
-
 extern "C" int32_t mile_predict_moments_width(const mile_sampler *s) {
   if (!s) return fail(MILE_ERR_INVALID, "mile_predict_moments_width: null handle");
   const int O = s->spec.widths[s->spec.n_layers - 1];
@@ -2260,19 +2326,17 @@ extern "C" int32_t mile_predict_moments_width(const mile_sampler *s) {
 
 extern "C" int32_t mile_predict_moments(mile_sampler *s, const float *theta, int64_t S, const void *X, int64_t N, float *out,
                                         int32_t *dropped, int64_t max_draws_per_pass, void *stream) {
-  const int rc0 = eval_args("mile_predict_moments", s, !theta || !X || !out, S, N,
-                            [&] { return max_draws_per_pass < 0 ? "max_draws_per_pass < 0" : nullptr; });
+  const int rc0 = eval_args("mile_predict_moments", s, !theta || !X || !out, bad_SN(S, N), [&] { return bad_caps(max_draws_per_pass, 0); });
   if (rc0 != MILE_OK) return rc0;
   const int task = s->spec.task, O = s->spec.widths[s->spec.n_layers - 1];
   if (task == MILE_TASK_REGRESSION && O != 2) return fail(MILE_ERR_INVALID, "mile_predict_moments: regression needs (mu, log sigma) outputs");
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->device));
   const int64_t per_draw = N * O * 4;
-  int64_t chunk = max_draws_per_pass ? max_draws_per_pass : std::max<int64_t>(1, EVAL_PASS_TARGET / per_draw);
-  chunk = std::min<int64_t>(chunk, S);
+  const int64_t chunk = pass_draws(EVAL_PASS_TARGET, per_draw, max_draws_per_pass, S);
   // enough one-wave workgroups for about eight waves per CU, at most one slice per draw of a pass
   const int slices = (int)std::min<int64_t>(std::min<int64_t>(MOM_MAX_SLICES, chunk), std::max<int64_t>(1, ((int64_t)s->n_cu * 8 * MOM_NT + N - 1) / N));
-  const size_t raw_bytes = ((size_t)chunk * per_draw + 255) / 256 * 256, acc_bytes = mom_acc_bytes(task, O, (int)N, slices);
+  const size_t raw_bytes = r256((size_t)chunk * per_draw), acc_bytes = mom_acc_bytes(task, O, (int)N, slices);
   if (reserve_eval_ws(s, raw_bytes + acc_bytes) != hipSuccess)
     return fail(MILE_ERR_NOMEM, "mile_predict_moments: workspace allocation failed (lower max_draws_per_pass)");
   MomParams p{};
@@ -2328,50 +2392,46 @@ static const char *qnt_bad_args(const double *levels, int32_t Q, const float *y,
   return nullptr;
 }
 
-static int64_t qnt_tile_rows(int64_t S, int64_t N, int64_t max_rows) {
-  int64_t nt = std::max<int64_t>(1, EVAL_PASS_TARGET / (S * 16));   // [S][Nt][2] floats plus the packed copy
-  if (nt >= QNT_TILE) nt = nt / QNT_TILE * QNT_TILE;
-  if (max_rows > 0) nt = std::min(nt, max_rows);
-  return std::min(nt, N);
-}
-// bytes of the workspace behind the raw block for tiles of Nt rows: packed copy, slice partials, levels; then (handle only) sweeps
-static size_t qnt_tail_bytes(int64_t S, int64_t Nt, int slices) {
-  return qnt_pk_bytes(S, Nt) + qnt_part_bytes((int)Nt, QNT_MAX_Q, slices) + qnt_r256(2 * QNT_MAX_Q * 8);
+// The plan of one call: rows per tile, draws per pass and the byte offset of every block of its workspace.  own_raw: the
+// streamed call, whose workspace begins with the forward's raw block [S][Nt][2] (16 bytes per (draw, row) with the packed copy,
+// tiles of whole transpose tiles) and ends with the sweeps [N]; else raw is the caller's and the packed copy comes first.
+struct QntTilePlan { int64_t Nt, chunk; int slices; size_t pk, part, lev, sweeps, total; };
+static QntTilePlan qnt_tile_plan(int64_t S, int64_t N, int n_cu, bool own_raw, int64_t max_rows, int64_t max_draws) {
+  QntTilePlan t;
+  t.Nt = tile_rows(EVAL_PASS_TARGET, S * (own_raw ? 16 : 8), own_raw ? QNT_TILE : 1, max_rows, N);
+  t.chunk = pass_draws(EVAL_NO_BUDGET, 1, max_draws, S);
+  t.slices = qnt_slices((int)S, (int)t.Nt, n_cu);   // of the full tile, for every tile: the partials of a ragged last tile fit behind it
+  t.pk = own_raw ? r256((size_t)S * t.Nt * 8) : 0;
+  t.part = t.pk + qnt_pk_bytes(S, t.Nt);
+  t.lev = t.part + qnt_part_bytes((int)t.Nt, QNT_MAX_Q, t.slices);
+  t.sweeps = t.lev + r256(2 * QNT_MAX_Q * 8);
+  t.total = t.sweeps + (own_raw ? r256((size_t)N * 4) : 0);
+  return t;
 }
 
-// the tiles of one call: raw0 [S][ld][2] holds rows r0 .. of the tile at raw0 + 2 * (tile offset) when the caller's array is
-// walked (ld = N), or is refilled per tile by `fill` (ld = Nt)
-template <class Fill>
-static int qnt_run(const float *raw_all, char *tail, int64_t S, int64_t N, int64_t Nt, int slices_cu, const double *levels, int32_t Q,
-                   const float *y, float *quant, float *pit, int32_t *dropped, int32_t *sweeps, hipStream_t st, Fill fill) {
+// the tiles of one call, each from `source`; sweeps: record them in the workspace
+template <class Source>
+static int qnt_run(char *ws, const QntTilePlan &t, int64_t S, int64_t N, const double *levels, int32_t Q, const float *y, float *quant,
+                   float *pit, int32_t *dropped, bool sweeps, hipStream_t st, Source source) {
   double lev[2 * QNT_MAX_Q];
   for (int i = 0; i < Q; ++i) { lev[i] = levels[i]; lev[Q + i] = host_ndtri(levels[i]); }
   QntParams p{};
-  p.S = (int)S; p.Q = Q;
-  p.pk = (float2 *)tail;
-  char *part = tail + qnt_pk_bytes(S, Nt);
-  const int max_slices = qnt_slices((int)S, (int)Nt, slices_cu);
-  double *lev_d = (double *)(part + qnt_part_bytes((int)Nt, QNT_MAX_Q, max_slices));
-  HIP_TRY(hipMemcpyAsync(lev_d, lev, (size_t)2 * Q * 8, hipMemcpyHostToDevice, st));
+  p.S = (int)S; p.Q = Q; p.slices = t.slices;
+  p.pk = (float2 *)(ws + t.pk); p.part_brk = (double *)(ws + t.part); p.lev = (const double *)(ws + t.lev);
+  HIP_TRY(hipMemcpyAsync(ws + t.lev, lev, (size_t)2 * Q * 8, hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));   // lev is on this stack
-  p.lev = lev_d;
-  for (int64_t r0 = 0; r0 < N; r0 += Nt) {
-    p.Nt = (int)std::min<int64_t>(Nt, N - r0);
-    p.slices = max_slices;   // of the full tile, for every tile: the partials of a ragged last tile fit behind it
-    p.part_brk = (double *)part;
-    p.part_cnt = (int32_t *)(part + qnt_r256((size_t)p.slices * p.Nt * Q * 16));
-    if (raw_all) { p.raw = raw_all + 2 * r0; p.ld = N; }
-    else {
-      const float *tile = nullptr;
-      const int rc = fill(r0, p.Nt, &tile);
-      if (rc != MILE_OK) return rc;
-      p.raw = tile; p.ld = p.Nt;
-    }
+  for (int64_t r0 = 0; r0 < N; r0 += t.Nt) {
+    p.Nt = (int)std::min<int64_t>(t.Nt, N - r0);
+    p.part_cnt = (int32_t *)(ws + t.part + r256((size_t)p.slices * p.Nt * Q * 16));
+    Tile tile;
+    const int rc = source(r0, p.Nt, tile);
+    if (rc != MILE_OK) return rc;
+    p.raw = tile.at; p.ld = tile.ld;
     p.y = y ? y + r0 : nullptr;
     p.quant = quant ? quant + r0 * Q : nullptr;
     p.pit = pit ? pit + r0 : nullptr;
     p.dropped = dropped ? dropped + r0 : nullptr;
-    p.sweeps = sweeps ? sweeps + r0 : nullptr;
+    p.sweeps = sweeps ? (int32_t *)(ws + t.sweeps) + r0 : nullptr;
     HIP_TRY(mile_launch_quantiles(p, st));
   }
   return MILE_OK;
@@ -2379,72 +2439,42 @@ static int qnt_run(const float *raw_all, char *tail, int64_t S, int64_t N, int64
 
 extern "C" int32_t mile_mixture_quantiles(const float *raw, int64_t S, int64_t N, const double *levels, int32_t Q, const float *y,
                                           float *quant, float *pit, int32_t *dropped, void *stream) {
-  if (!raw) return fail(MILE_ERR_INVALID, "mile_mixture_quantiles: null raw");
-  if (S < 1 || S > 0x7fffffff) return fail(MILE_ERR_INVALID, "mile_mixture_quantiles: S out of range (1 .. 2^31 - 1)");
-  if (N < 1 || N > 0x3fffffff) return fail(MILE_ERR_INVALID, "mile_mixture_quantiles: N out of range (1 .. 2^30 - 1)");
-  if (const char *m = qnt_bad_args(levels, Q, y, quant, pit)) return fail(MILE_ERR_INVALID, std::string("mile_mixture_quantiles: ") + m);
+  auto bad = [](const char *m) { return fail(MILE_ERR_INVALID, std::string("mile_mixture_quantiles: ") + m); };
+  if (!raw) return bad("null raw");
+  if (const char *m = bad_SN(S, N)) return bad(m);
+  if (const char *m = qnt_bad_args(levels, Q, y, quant, pit)) return bad(m);
   hipStream_t st = (hipStream_t)stream;
-  int dev = 0, n_cu = 256;
-  HIP_TRY(hipGetDevice(&dev));
-  (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-  const int64_t Nt = std::min<int64_t>(N, std::max<int64_t>(1, EVAL_PASS_TARGET / (S * 8)));   // the packed copy alone: raw is the caller's
-  void *ws = nullptr;
-  if (hipMalloc(&ws, qnt_tail_bytes(S, Nt, qnt_slices((int)S, (int)Nt, n_cu))) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(MILE_ERR_NOMEM, "mile_mixture_quantiles: workspace allocation failed");
-  }
-  const int rc = qnt_run(raw, (char *)ws, S, N, Nt, n_cu, levels, Q, y, quant, pit, dropped, nullptr, st,
-                         [](int64_t, int, const float **) { return (int)MILE_OK; });
-  const hipError_t es = hipStreamSynchronize(st);   // the workspace is this call's: the kernels finish before it goes
-  (void)hipFree(ws);
-  if (rc != MILE_OK) return rc;
-  HIP_TRY(es);
-  return MILE_OK;
+  int n_cu;
+  const int rc0 = current_cus(&n_cu);
+  if (rc0 != MILE_OK) return rc0;
+  const QntTilePlan t = qnt_tile_plan(S, N, n_cu, false, 0, 0);
+  return with_call_ws(t.total, "mile_mixture_quantiles: workspace allocation failed", st, [&](char *ws) {
+    return qnt_run(ws, t, S, N, levels, Q, y, quant, pit, dropped, false, st,
+                   [&](int64_t r0, int, Tile &tile) { tile = {raw + 2 * r0, N}; return (int)MILE_OK; });
+  });
 }
 
 extern "C" int64_t mile_predict_quantiles_workspace(const mile_sampler *s, int64_t S, int64_t N) {
-  if (!s || S < 1 || S > 0x7fffffff || N < 1 || N > 0x3fffffff) return -1;
-  const int64_t Nt = qnt_tile_rows(S, N, 0);
-  return (int64_t)(qnt_r256((size_t)S * Nt * 8) + qnt_tail_bytes(S, Nt, qnt_slices((int)S, (int)Nt, s->n_cu)) + qnt_r256((size_t)N * 4));
+  return !s || bad_SN(S, N) ? -1 : (int64_t)qnt_tile_plan(S, N, s->n_cu, true, 0, 0).total;
 }
 
 extern "C" int32_t mile_predict_quantiles(mile_sampler *s, const float *theta, int64_t S, const void *X, int64_t N,
                                           const double *levels, int32_t Q, const float *y, float *quant, float *pit, int32_t *dropped,
                                           int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
-  const int rc0 = eval_args("mile_predict_quantiles", s, !theta || !X, S, N, [&]() -> const char * {
+  const int rc0 = eval_args("mile_predict_quantiles", s, !theta || !X, bad_SN(S, N), [&]() -> const char * {
     if (const char *m = qnt_bad_args(levels, Q, y, quant, pit)) return m;
-    if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
-    if (max_rows_per_tile < 0) return "max_rows_per_tile < 0";
-    if (s->spec.task != MILE_TASK_REGRESSION || s->spec.widths[s->spec.n_layers - 1] != 2)
-      return "needs a regression model with (mu, log sigma) outputs";
-    return nullptr;
+    if (const char *m = bad_caps(max_draws_per_pass, max_rows_per_tile)) return m;
+    return not_mu_log_sigma(s);
   });
   if (rc0 != MILE_OK) return rc0;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->device));
-  const int64_t Nt = qnt_tile_rows(S, N, max_rows_per_tile);
-  const int64_t chunk = std::min<int64_t>(S, max_draws_per_pass ? max_draws_per_pass : S);
-  const size_t raw_bytes = qnt_r256((size_t)S * Nt * 8), tail_bytes = qnt_tail_bytes(S, Nt, qnt_slices((int)S, (int)Nt, s->n_cu));
-  const size_t need = raw_bytes + tail_bytes + qnt_r256((size_t)N * 4);
-  if (reserve_eval_ws(s, need) != hipSuccess)
+  const QntTilePlan t = qnt_tile_plan(S, N, s->n_cu, true, max_rows_per_tile, max_draws_per_pass);
+  if (reserve_eval_ws(s, t.total) != hipSuccess)
     return fail(MILE_ERR_NOMEM, "mile_predict_quantiles: workspace allocation failed (lower max_rows_per_tile)");
-  float *raw = (float *)s->eval_ws;
-  char *tail = (char *)s->eval_ws + raw_bytes;
-  int32_t *sweeps = (int32_t *)(tail + tail_bytes);
-  s->qnt_sweeps = sweeps;
-  const size_t row_floats = (size_t)s->spec.in_features;
-  auto fill = [&](int64_t r0, int nt, const float **tile) -> int {   // every (draw, row) forward once: passes at their draw offset
-    PredParams pp;
-    const int rc0 = stage_rows(s, (const float *)X + (size_t)r0 * row_floats, nullptr, nt, pp, st);
-    if (rc0 != MILE_OK) return rc0;
-    for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-      const int rc = eval_forward(s, pp, theta + (size_t)s0 * s->ds.d, std::min<int64_t>(chunk, S - s0), raw + (size_t)s0 * nt * 2, st);
-      if (rc != MILE_OK) return rc;
-    }
-    *tile = raw;
-    return MILE_OK;
-  };
-  const int rc = qnt_run(nullptr, tail, S, N, Nt, s->n_cu, levels, Q, y, quant, pit, dropped, quant ? sweeps : nullptr, st, fill);
+  s->qnt_sweeps = (const int32_t *)((char *)s->eval_ws + t.sweeps);
+  const int rc = qnt_run((char *)s->eval_ws, t, S, N, levels, Q, y, quant, pit, dropped, quant != nullptr, st,
+                         stream_tiles(s, theta, S, t.chunk, X, st));
   if (rc != MILE_OK) return rc;
   s->qnt_rows = quant ? N : 0;
   return MILE_OK;
@@ -2465,7 +2495,7 @@ extern "C" int32_t mile_debug_quantile_sweeps(mile_sampler *s, int64_t *rows, in
 
 // mile_psis_loo / mile_loo_stream: every check before any launch; rows in tiles whose [S][Nt] block of log-likelihoods and
 // packed copy fit the evaluation budget, k_loo_pack + k_loo_row per tile (mile_loo.h).
-static const char *loo_bad_S(int64_t S) { return S < 2 || S > LOO_MAX_S ? "S out of range (2 .. 2^20)" : nullptr; }
+static const char *loo_bad_SN(int64_t S, int64_t N) { return S < 2 || S > LOO_MAX_S ? "S out of range (2 .. 2^20)" : bad_N(N); }
 // what is wrong with r_eff or the outputs asked for (S in range), or null
 static const char *loo_bad_args(int64_t S, double r_eff, bool any_output) {
   if (!any_output) return "no output asked for";
@@ -2474,36 +2504,47 @@ static const char *loo_bad_args(int64_t S, double r_eff, bool any_output) {
   return nullptr;
 }
 
-static int64_t loo_tile_rows(int64_t S, int64_t N, int64_t max_rows) {
-  int64_t nt = std::max<int64_t>(1, EVAL_PASS_TARGET / (S * 8));   // [S][Nt] floats plus the packed copy
-  if (nt >= LOO_TILE) nt = nt / LOO_TILE * LOO_TILE;
-  if (max_rows > 0) nt = std::min(nt, max_rows);
-  return std::min(nt, N);
+struct LooOut {   // [C, N] each, any may be null
+  double *lppd, *p_waic, *elpd_loo, *khat;
+  int32_t *dropped;
+  bool any() const { return lppd || p_waic || elpd_loo || khat || dropped; }
+};
+
+// The plan of one call: rows per tile, draws per pass and the byte offset of the packed copy in its workspace.  own_raw: the
+// streamed call, whose workspace begins with the forward's block [S][Nt] (8 bytes per (draw, row) with the packed copy, tiles of
+// whole transpose tiles); else loglik is the caller's and the packed copy is all there is.
+struct LooTilePlan { int64_t Nt, chunk; size_t pk, total; };
+static LooTilePlan loo_tile_plan(int64_t S, int64_t N, bool own_raw, int64_t max_rows, int64_t max_draws) {
+  LooTilePlan t;
+  t.Nt = tile_rows(EVAL_PASS_TARGET, S * (own_raw ? 8 : 4), own_raw ? LOO_TILE : 1, max_rows, N);
+  t.chunk = pass_draws(EVAL_NO_BUDGET, 1, max_draws, S);
+  t.pk = own_raw ? loo_pk_bytes(S, t.Nt) : 0;   // the forward's block is as large as its packed copy
+  t.total = t.pk + loo_pk_bytes(S, t.Nt);
+  return t;
 }
 
-// the tiles of one call: ll_all [S][N] is the caller's tensor, walked in place (ld = N), or null and `fill` writes each
-// tile's [S][Nt] block (ld = Nt)
-template <class Fill>
-static int loo_run(const float *ll_all, float *pk, int64_t S, int64_t N, int64_t Nt, int n_cu, double r_eff, double *lppd, double *p_waic,
-                   double *elpd_loo, double *khat, int32_t *dropped, hipStream_t st, Fill fill) {
+// the tiles of one call, the C chains inside each: chain c's block [S][..] of the tile from `source`, its outputs at row c
+template <class Source>
+static int loo_run(char *ws, const LooTilePlan &t, int64_t C, int64_t S, int64_t N, int n_cu, double r_eff, const LooOut &o, hipStream_t st,
+                   Source source) {
   LooParams p{};
-  p.S = (int)S; p.pk = pk; p.r_eff = r_eff; p.M_full = loo_tail_host(S, r_eff);
-  for (int64_t r0 = 0; r0 < N; r0 += Nt) {
-    p.Nt = (int)std::min<int64_t>(Nt, N - r0);
+  p.S = (int)S; p.pk = (float *)(ws + t.pk); p.r_eff = r_eff; p.M_full = loo_tail_host(S, r_eff);
+  for (int64_t r0 = 0; r0 < N; r0 += t.Nt) {
+    p.Nt = (int)std::min<int64_t>(t.Nt, N - r0);
     p.slices = loo_slices((int)S, p.Nt, n_cu);
-    if (ll_all) { p.ll = ll_all + r0; p.ld = N; }
-    else {
-      const float *tile = nullptr;
-      const int rc = fill(r0, p.Nt, &tile);
+    for (int64_t c = 0; c < C; ++c) {
+      Tile tile;
+      const int rc = source(r0, p.Nt, c, tile);
       if (rc != MILE_OK) return rc;
-      p.ll = tile; p.ld = p.Nt;
+      p.ll = tile.at; p.ld = tile.ld;
+      const size_t at = (size_t)c * N + r0;
+      p.lppd = o.lppd ? o.lppd + at : nullptr;
+      p.p_waic = o.p_waic ? o.p_waic + at : nullptr;
+      p.elpd_loo = o.elpd_loo ? o.elpd_loo + at : nullptr;
+      p.khat = o.khat ? o.khat + at : nullptr;
+      p.dropped = o.dropped ? o.dropped + at : nullptr;
+      HIP_TRY(mile_launch_loo(p, st));
     }
-    p.lppd = lppd ? lppd + r0 : nullptr;
-    p.p_waic = p_waic ? p_waic + r0 : nullptr;
-    p.elpd_loo = elpd_loo ? elpd_loo + r0 : nullptr;
-    p.khat = khat ? khat + r0 : nullptr;
-    p.dropped = dropped ? dropped + r0 : nullptr;
-    HIP_TRY(mile_launch_loo(p, st));
   }
   return MILE_OK;
 }
@@ -2511,92 +2552,58 @@ static int loo_run(const float *ll_all, float *pk, int64_t S, int64_t N, int64_t
 extern "C" int32_t mile_psis_loo(const float *loglik, int64_t S, int64_t N, double r_eff, double *lppd, double *p_waic, double *elpd_loo,
                                  double *khat, int32_t *dropped, void *stream) {
   auto bad = [](const char *m) { return fail(MILE_ERR_INVALID, std::string("mile_psis_loo: ") + m); };
+  const LooOut o{lppd, p_waic, elpd_loo, khat, dropped};
   if (!loglik) return bad("null loglik");
-  if (const char *m = loo_bad_S(S)) return bad(m);
-  if (N < 1 || N > 0x3fffffff) return bad("N out of range (1 .. 2^30 - 1)");
-  if (const char *m = loo_bad_args(S, r_eff, lppd || p_waic || elpd_loo || khat || dropped)) return bad(m);
+  if (const char *m = loo_bad_SN(S, N)) return bad(m);
+  if (const char *m = loo_bad_args(S, r_eff, o.any())) return bad(m);
   hipStream_t st = (hipStream_t)stream;
-  int dev = 0, n_cu = 256;
-  HIP_TRY(hipGetDevice(&dev));
-  (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-  const int64_t Nt = std::min<int64_t>(N, std::max<int64_t>(1, EVAL_PASS_TARGET / (S * 4)));   // the packed copy alone: loglik is the caller's
-  void *ws = nullptr;
-  if (hipMalloc(&ws, loo_pk_bytes(S, Nt)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(MILE_ERR_NOMEM, "mile_psis_loo: workspace allocation failed");
-  }
-  const int rc = loo_run(loglik, (float *)ws, S, N, Nt, n_cu, r_eff, lppd, p_waic, elpd_loo, khat, dropped, st,
-                         [](int64_t, int, const float **) { return (int)MILE_OK; });
-  const hipError_t es = hipStreamSynchronize(st);   // the workspace is this call's: the kernels finish before it goes
-  (void)hipFree(ws);
-  if (rc != MILE_OK) return rc;
-  HIP_TRY(es);
-  return MILE_OK;
+  int n_cu;
+  const int rc0 = current_cus(&n_cu);
+  if (rc0 != MILE_OK) return rc0;
+  const LooTilePlan t = loo_tile_plan(S, N, false, 0, 0);
+  return with_call_ws(t.total, "mile_psis_loo: workspace allocation failed", st, [&](char *ws) {
+    return loo_run(ws, t, 1, S, N, n_cu, r_eff, o, st, [&](int64_t r0, int, int64_t, Tile &tile) { tile = {loglik + r0, N}; return (int)MILE_OK; });
+  });
 }
 
 extern "C" int64_t mile_loo_stream_workspace(const mile_sampler *s, int64_t S, int64_t N) {
-  if (!s || loo_bad_S(S) || N < 1 || N > 0x3fffffff) return -1;
-  const int64_t Nt = loo_tile_rows(S, N, 0);
-  return (int64_t)(loo_r256((size_t)S * Nt * 4) + loo_pk_bytes(S, Nt));
+  return !s || loo_bad_SN(S, N) ? -1 : (int64_t)loo_tile_plan(S, N, true, 0, 0).total;
 }
 
-// mile_loo_stream and mile_chain_loo_stream after their checks: theta [C * S, d], chain c's S draws at row c * S, outputs
-// [C, N].  The row tiles go outermost, so a tile's rows are staged once for all chains; each chain's block [S][Nt] is forwarded
-// and goes through k_loo_pack + k_loo_row on its own, as a call on that chain alone would send it.
-static int loo_stream_chains(mile_sampler *s, const float *theta, int64_t C, int64_t S, const void *X, const void *y, int64_t N, double r_eff,
-                             double *lppd, double *p_waic, double *elpd_loo, double *khat, int32_t *dropped,
-                             int64_t max_draws_per_pass, int64_t max_rows_per_tile, const char *fn, hipStream_t st) {
+// mile_loo_stream (C = 1) and mile_chain_loo_stream: theta [C * S, d], chain c's S draws at row c * S, outputs [C, N].  A tile's
+// rows are staged once for all chains; each chain's block [S][Nt] is forwarded and goes through k_loo_pack + k_loo_row on its
+// own, as a call on that chain alone would send it.
+static int loo_stream_chains(const char *fn, mile_sampler *s, const float *theta, int64_t C, int64_t S, const void *X, const void *y, int64_t N,
+                             double r_eff, const LooOut &o, int64_t max_draws_per_pass, int64_t max_rows_per_tile, hipStream_t st) {
+  const int rc0 = eval_args(fn, s, !theta || !X || !y, loo_bad_SN(S, N), [&]() -> const char * {
+    if (C < 1 || C > 1024) return "C out of range (1 .. 1024)";
+    if (const char *m = loo_bad_args(S, r_eff, o.any())) return m;
+    return bad_caps(max_draws_per_pass, max_rows_per_tile);
+  });
+  if (rc0 != MILE_OK) return rc0;
   HIP_TRY(hipSetDevice(s->device));
-  const int64_t Nt = loo_tile_rows(S, N, max_rows_per_tile);
-  const int64_t chunk = std::min<int64_t>(S, max_draws_per_pass ? max_draws_per_pass : S);
-  const size_t raw_bytes = loo_r256((size_t)S * Nt * 4);
-  if (reserve_eval_ws(s, raw_bytes + loo_pk_bytes(S, Nt)) != hipSuccess)
+  const LooTilePlan t = loo_tile_plan(S, N, true, max_rows_per_tile, max_draws_per_pass);
+  if (reserve_eval_ws(s, t.total) != hipSuccess)
     return fail(MILE_ERR_NOMEM, std::string(fn) + ": workspace allocation failed (lower max_rows_per_tile)");
   float *raw = (float *)s->eval_ws;
-  const size_t row_floats = (size_t)s->spec.in_features;
-  LooParams p{};
-  p.S = (int)S; p.pk = (float *)((char *)s->eval_ws + raw_bytes); p.r_eff = r_eff; p.M_full = loo_tail_host(S, r_eff);
-  for (int64_t r0 = 0; r0 < N; r0 += Nt) {
-    const int nt = (int)std::min<int64_t>(Nt, N - r0);
-    PredParams pp;
-    const int rc1 = stage_rows(s, (const float *)X + (size_t)r0 * row_floats, (const char *)y + (size_t)r0 * 4, nt, pp, st);
-    if (rc1 != MILE_OK) return rc1;
-    p.Nt = nt; p.slices = loo_slices((int)S, nt, s->n_cu); p.ll = raw; p.ld = nt;
-    for (int64_t c = 0; c < C; ++c) {
-      const float *th = theta + (size_t)c * S * s->ds.d;
-      for (int64_t s0 = 0; s0 < S; s0 += chunk) {   // every (draw, row) forward once: passes at their draw offset
-        const int rc = eval_forward(s, pp, th + (size_t)s0 * s->ds.d, std::min<int64_t>(chunk, S - s0), raw + (size_t)s0 * nt, st);
-        if (rc != MILE_OK) return rc;
-      }
-      const size_t at = (size_t)c * N + r0;
-      p.lppd = lppd ? lppd + at : nullptr;
-      p.p_waic = p_waic ? p_waic + at : nullptr;
-      p.elpd_loo = elpd_loo ? elpd_loo + at : nullptr;
-      p.khat = khat ? khat + at : nullptr;
-      p.dropped = dropped ? dropped + at : nullptr;
-      HIP_TRY(mile_launch_loo(p, st));
+  PredParams pp;   // the tile's rows and labels, staged when its first chain is asked for
+  return loo_run((char *)s->eval_ws, t, C, S, N, s->n_cu, r_eff, o, st, [&](int64_t r0, int nt, int64_t c, Tile &tile) -> int {
+    if (c == 0) {
+      const int rc = stage_rows(s, (const float *)X + (size_t)r0 * s->spec.in_features, (const char *)y + (size_t)r0 * 4, nt, pp, st);
+      if (rc != MILE_OK) return rc;
     }
-  }
-  return MILE_OK;
+    tile = {raw, nt};
+    return forward_draws(s, pp, theta + (size_t)c * S * s->ds.d, S, t.chunk, raw, st);
+  });
 }
 
 extern "C" int32_t mile_loo_stream(mile_sampler *s, const float *theta, int64_t S, const void *X, const void *y, int64_t N, double r_eff,
                                    double *lppd, double *p_waic, double *elpd_loo, double *khat, int32_t *dropped,
                                    int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
-  if (s && theta && X && y)
-    if (const char *m = loo_bad_S(S)) return fail(MILE_ERR_INVALID, std::string("mile_loo_stream: ") + m);
-  const int rc0 = eval_args("mile_loo_stream", s, !theta || !X || !y, S, N, [&]() -> const char * {
-    if (const char *m = loo_bad_args(S, r_eff, lppd || p_waic || elpd_loo || khat || dropped)) return m;
-    if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
-    if (max_rows_per_tile < 0) return "max_rows_per_tile < 0";
-    return nullptr;
-  });
-  if (rc0 != MILE_OK) return rc0;
-  return loo_stream_chains(s, theta, 1, S, X, y, N, r_eff, lppd, p_waic, elpd_loo, khat, dropped, max_draws_per_pass, max_rows_per_tile,
-                           "mile_loo_stream", (hipStream_t)stream);
+  return loo_stream_chains("mile_loo_stream", s, theta, 1, S, X, y, N, r_eff, {lppd, p_waic, elpd_loo, khat, dropped}, max_draws_per_pass,
+                           max_rows_per_tile, (hipStream_t)stream);
 }
 
-// mile_chain_loo_stream: mile_loo_stream's checks, plus C
 extern "C" int64_t mile_chain_loo_stream_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N) {
   if (C < 1 || C > 1024) return -1;
   return mile_loo_stream_workspace(s, S, N);   // a chain at a time: the workspace of one
@@ -2605,18 +2612,8 @@ extern "C" int64_t mile_chain_loo_stream_workspace(const mile_sampler *s, int32_
 extern "C" int32_t mile_chain_loo_stream(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, const void *y, int64_t N,
                                          double r_eff, double *lppd, double *p_waic, double *elpd_loo, double *khat, int32_t *dropped,
                                          int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
-  if (s && theta && X && y)
-    if (const char *m = loo_bad_S(S)) return fail(MILE_ERR_INVALID, std::string("mile_chain_loo_stream: ") + m);
-  const int rc0 = eval_args("mile_chain_loo_stream", s, !theta || !X || !y, S, N, [&]() -> const char * {
-    if (C < 1 || C > 1024) return "C out of range (1 .. 1024)";
-    if (const char *m = loo_bad_args(S, r_eff, lppd || p_waic || elpd_loo || khat || dropped)) return m;
-    if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
-    if (max_rows_per_tile < 0) return "max_rows_per_tile < 0";
-    return nullptr;
-  });
-  if (rc0 != MILE_OK) return rc0;
-  return loo_stream_chains(s, theta, C, S, X, y, N, r_eff, lppd, p_waic, elpd_loo, khat, dropped, max_draws_per_pass, max_rows_per_tile,
-                           "mile_chain_loo_stream", (hipStream_t)stream);
+  return loo_stream_chains("mile_chain_loo_stream", s, theta, C, S, X, y, N, r_eff, {lppd, p_waic, elpd_loo, khat, dropped}, max_draws_per_pass,
+                           max_rows_per_tile, (hipStream_t)stream);
 }
 
 // mile_mixture_crps / mile_crps_stream: every check before any launch; rows in tiles that respect the evaluation budget, the
@@ -2628,12 +2625,14 @@ struct CrpsOut {
   bool any() const { return crps_chain || spread_chain || crps_mix || spread_mix || gram || dropped; }
   bool pairs() const { return crps_chain || spread_chain || crps_mix || spread_mix || gram; }
 };
-// what is wrong with the shape, the weights or the outputs asked for, or null
-static const char *crps_bad_args(int32_t C, int64_t S, int64_t N, const double *weights, int32_t n_w, const CrpsOut &o, int64_t max_rows) {
+// what is wrong with the shape, or null; then (the shape in range) with the weights, the outputs asked for or the tile cap
+static const char *crps_bad_shape(int32_t C, int64_t S, int64_t N) {
   if (C < 1 || C > CRPS_MAX_C) return "C out of range (1 .. 1024)";
   if (S < 1) return "S < 1";
   if (S > CRPS_MAX_DRAWS || (int64_t)C * S > CRPS_MAX_DRAWS) return "C * S out of range (1 .. 2^20)";
-  if (N < 1 || N > 0x3fffffff) return "N out of range (1 .. 2^30 - 1)";
+  return bad_N(N);
+}
+static const char *crps_bad_args(int32_t C, const double *weights, int32_t n_w, const CrpsOut &o, int64_t max_rows) {
   if (!o.any()) return "no output asked for";
   if (n_w < 0 || n_w > CRPS_MAX_W) return "n_w out of range (0 .. 8)";
   if (n_w > 0 && !weights) return "n_w > 0 without weights";
@@ -2646,49 +2645,51 @@ static const char *crps_bad_args(int32_t C, int64_t S, int64_t N, const double *
     }
     if (!(std::fabs(sum - 1.0) <= 1e-9)) return "every weight vector must sum to 1 (within 1e-9)";
   }
-  if (max_rows < 0) return "max_rows_per_tile < 0";
-  return nullptr;
+  return bad_caps(0, max_rows);
 }
 
-// rows of a tile; per_pair_bytes: 16 with the forward's raw block beside the packed copy, 8 with the caller's raw walked in place
-static int64_t crps_tile_rows(int64_t C, int64_t S, int64_t N, const CrpsPlan &pl, int64_t max_rows, int per_pair_bytes) {
+// The plan of one call: the pairs' units, rows per tile (the budget's, then the caps of one k_crps_pairs launch), draws per pass
+// and the byte offset of every block of its workspace.  own_raw: the streamed call, whose workspace begins with the forward's raw
+// block [C * S][Nt][2] (16 bytes per (draw, row) with the packed copy); else raw is the caller's and the packed copy comes first.
+struct CrpsTilePlan { CrpsPlan pl; int64_t Nt, chunk; size_t pk, cnt, part, w, total; };
+static CrpsTilePlan crps_tile_plan(int64_t C, int64_t S, int64_t N, bool own_raw, int64_t max_rows, int64_t max_draws) {
+  CrpsTilePlan t;
   const int64_t D = C * S;
-  int64_t nt = std::max<int64_t>(1, EVAL_PASS_TARGET / (D * per_pair_bytes));
-  nt = std::min(nt, std::max<int64_t>(1, CRPS_MAX_PAIRS_PER_LAUNCH / (D * (D + 1) / 2)));
-  nt = std::min(nt, std::max<int64_t>(1, CRPS_MAX_SLOT_BYTES / (pl.units * 8)));
-  nt = std::min(nt, std::max<int64_t>(1, CRPS_MAX_GRID / pl.units));
-  if (max_rows > 0) nt = std::min(nt, max_rows);
-  return std::min(nt, N);
+  t.pl = crps_plan(C, S, N);
+  t.Nt = tile_rows(EVAL_PASS_TARGET, D * (own_raw ? 16 : 8), 1, max_rows, N);
+  t.Nt = std::min(t.Nt, std::max<int64_t>(1, CRPS_MAX_PAIRS_PER_LAUNCH / (D * (D + 1) / 2)));
+  t.Nt = std::min(t.Nt, std::max<int64_t>(1, CRPS_MAX_SLOT_BYTES / (t.pl.units * 8)));
+  t.Nt = std::min(t.Nt, std::max<int64_t>(1, CRPS_MAX_GRID / t.pl.units));
+  t.chunk = pass_draws(EVAL_NO_BUDGET, 1, max_draws, D);
+  t.pk = own_raw ? r256((size_t)D * t.Nt * 8) : 0;
+  t.cnt = t.pk + r256((size_t)D * t.Nt * 8);
+  t.part = t.cnt + r256((size_t)t.Nt * C * 4);
+  t.w = t.part + r256((size_t)t.Nt * t.pl.units * 8);
+  t.total = t.w + r256((size_t)CRPS_MAX_W * C * 8);
+  return t;
 }
 
-// the tiles of one call: raw_all [C * S][N][2] is the caller's array, walked in place (ld = N), or null and `fill` writes each
-// tile's [C * S][Nt][2] block (ld = Nt).  tail: crps_tail_bytes of Nt rows.
-template <class Fill>
-static int crps_run(const float *raw_all, char *tail, int32_t C, int64_t S, int64_t N, int64_t Nt, const CrpsPlan &pl, const float *y,
-                    const double *weights, int32_t n_w, const CrpsOut &o, hipStream_t st, Fill fill) {
+// the tiles of one call, each from `source`
+template <class Source>
+static int crps_run(char *ws, const CrpsTilePlan &t, int32_t C, int64_t S, int64_t N, const float *y, const double *weights, int32_t n_w,
+                    const CrpsOut &o, hipStream_t st, Source source) {
   CrpsParams p{};
-  p.C = C; p.S = (int)S; p.pl = pl; p.N = N; p.n_w = n_w;
-  p.pk = (float2 *)tail;
-  char *at = tail + crps_r256((size_t)C * S * Nt * 8);
-  p.cnt = (int32_t *)at; at += crps_r256((size_t)Nt * C * 4);
-  p.part = (double *)at; at += crps_r256((size_t)Nt * pl.units * 8);
+  p.C = C; p.S = (int)S; p.pl = t.pl; p.N = N; p.n_w = n_w;
+  p.pk = (float2 *)(ws + t.pk); p.cnt = (int32_t *)(ws + t.cnt); p.part = (double *)(ws + t.part);
   if (n_w > 0) {
-    HIP_TRY(hipMemcpyAsync(at, weights, (size_t)n_w * C * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ws + t.w, weights, (size_t)n_w * C * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));   // weights is the caller's host memory
-    p.w = (const double *)at;
+    p.w = (const double *)(ws + t.w);
   }
   p.crps_chain = o.crps_chain; p.spread_chain = o.spread_chain; p.crps_mix = o.crps_mix; p.spread_mix = o.spread_mix;
   p.gram = o.gram; p.dropped = o.dropped;
-  for (int64_t r0 = 0; r0 < N; r0 += Nt) {
-    p.Nt = (int)std::min<int64_t>(Nt, N - r0);
+  for (int64_t r0 = 0; r0 < N; r0 += t.Nt) {
+    p.Nt = (int)std::min<int64_t>(t.Nt, N - r0);
     p.r0 = r0;
-    if (raw_all) { p.raw = raw_all + 2 * r0; p.ld = N; }
-    else {
-      const float *tile = nullptr;
-      const int rc = fill(r0, p.Nt, &tile);
-      if (rc != MILE_OK) return rc;
-      p.raw = tile; p.ld = p.Nt;
-    }
+    Tile tile;
+    const int rc = source(r0, p.Nt, tile);
+    if (rc != MILE_OK) return rc;
+    p.raw = tile.at; p.ld = tile.ld;
     p.y = y + r0;
     HIP_TRY(mile_launch_crps_pack(p, st));
     if (!o.pairs()) continue;
@@ -2704,29 +2705,17 @@ extern "C" int32_t mile_mixture_crps(const float *raw, int32_t C, int64_t S, int
   auto bad = [](const char *m) { return fail(MILE_ERR_INVALID, std::string("mile_mixture_crps: ") + m); };
   if (!raw || !y) return bad("null raw or y");
   const CrpsOut o{crps_chain, spread_chain, crps_mix, spread_mix, gram, dropped};
-  if (const char *m = crps_bad_args(C, S, N, weights, n_w, o, max_rows_per_tile)) return bad(m);
+  if (const char *m = crps_bad_shape(C, S, N)) return bad(m);
+  if (const char *m = crps_bad_args(C, weights, n_w, o, max_rows_per_tile)) return bad(m);
   hipStream_t st = (hipStream_t)stream;
-  const CrpsPlan pl = crps_plan(C, S, N);
-  const int64_t Nt = crps_tile_rows(C, S, N, pl, max_rows_per_tile, 8);   // the packed copy alone: raw is the caller's
-  void *ws = nullptr;
-  if (hipMalloc(&ws, crps_tail_bytes(C, S, Nt, pl)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(MILE_ERR_NOMEM, "mile_mixture_crps: workspace allocation failed (lower max_rows_per_tile)");
-  }
-  const int rc = crps_run(raw, (char *)ws, C, S, N, Nt, pl, y, weights, n_w, o, st,
-                          [](int64_t, int, const float **) { return (int)MILE_OK; });
-  const hipError_t es = hipStreamSynchronize(st);   // the workspace is this call's: the kernels finish before it goes
-  (void)hipFree(ws);
-  if (rc != MILE_OK) return rc;
-  HIP_TRY(es);
-  return MILE_OK;
+  const CrpsTilePlan t = crps_tile_plan(C, S, N, false, max_rows_per_tile, 0);
+  return with_call_ws(t.total, "mile_mixture_crps: workspace allocation failed (lower max_rows_per_tile)", st, [&](char *ws) {
+    return crps_run(ws, t, C, S, N, y, weights, n_w, o, st, [&](int64_t r0, int, Tile &tile) { tile = {raw + 2 * r0, N}; return (int)MILE_OK; });
+  });
 }
 
 extern "C" int64_t mile_crps_stream_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N) {
-  if (!s || C < 1 || C > CRPS_MAX_C || S < 1 || S > CRPS_MAX_DRAWS || (int64_t)C * S > CRPS_MAX_DRAWS || N < 1 || N > 0x3fffffff) return -1;
-  const CrpsPlan pl = crps_plan(C, S, N);
-  const int64_t Nt = crps_tile_rows(C, S, N, pl, 0, 16);
-  return (int64_t)(crps_r256((size_t)C * S * Nt * 8) + crps_tail_bytes(C, S, Nt, pl));
+  return !s || crps_bad_shape(C, S, N) ? -1 : (int64_t)crps_tile_plan(C, S, N, true, 0, 0).total;
 }
 
 extern "C" int32_t mile_crps_stream(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, const float *y, int64_t N,
@@ -2734,38 +2723,18 @@ extern "C" int32_t mile_crps_stream(mile_sampler *s, const float *theta, int32_t
                                     double *spread_mix, double *gram, int32_t *dropped, int64_t max_draws_per_pass,
                                     int64_t max_rows_per_tile, void *stream) {
   const CrpsOut o{crps_chain, spread_chain, crps_mix, spread_mix, gram, dropped};
-  if (s && theta && X && y)
-    if (const char *m = crps_bad_args(C, S, N, weights, n_w, o, max_rows_per_tile)) return fail(MILE_ERR_INVALID, std::string("mile_crps_stream: ") + m);
-  const int rc0 = eval_args("mile_crps_stream", s, !theta || !X || !y, 1, 1, [&]() -> const char * {
-    if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
-    if (s->spec.task != MILE_TASK_REGRESSION || s->spec.widths[s->spec.n_layers - 1] != 2)
-      return "needs a regression model with (mu, log sigma) outputs";
-    return nullptr;
+  const int rc0 = eval_args("mile_crps_stream", s, !theta || !X || !y, crps_bad_shape(C, S, N), [&]() -> const char * {
+    if (const char *m = crps_bad_args(C, weights, n_w, o, max_rows_per_tile)) return m;
+    if (const char *m = bad_caps(max_draws_per_pass, 0)) return m;
+    return not_mu_log_sigma(s);
   });
   if (rc0 != MILE_OK) return rc0;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->device));
-  const int64_t D = (int64_t)C * S;
-  const CrpsPlan pl = crps_plan(C, S, N);
-  const int64_t Nt = crps_tile_rows(C, S, N, pl, max_rows_per_tile, 16);
-  const int64_t chunk = std::min<int64_t>(D, max_draws_per_pass ? max_draws_per_pass : D);
-  const size_t raw_bytes = crps_r256((size_t)D * Nt * 8);
-  if (reserve_eval_ws(s, raw_bytes + crps_tail_bytes(C, S, Nt, pl)) != hipSuccess)
+  const CrpsTilePlan t = crps_tile_plan(C, S, N, true, max_rows_per_tile, max_draws_per_pass);
+  if (reserve_eval_ws(s, t.total) != hipSuccess)
     return fail(MILE_ERR_NOMEM, "mile_crps_stream: workspace allocation failed (lower max_rows_per_tile)");
-  float *raw = (float *)s->eval_ws;
-  const size_t row_floats = (size_t)s->spec.in_features;
-  auto fill = [&](int64_t r0, int nt, const float **tile) -> int {   // every (draw, row) forward once: passes at their draw offset
-    PredParams pp;
-    const int rc1 = stage_rows(s, (const float *)X + (size_t)r0 * row_floats, nullptr, nt, pp, st);
-    if (rc1 != MILE_OK) return rc1;
-    for (int64_t s0 = 0; s0 < D; s0 += chunk) {
-      const int rc = eval_forward(s, pp, theta + (size_t)s0 * s->ds.d, std::min<int64_t>(chunk, D - s0), raw + (size_t)s0 * nt * 2, st);
-      if (rc != MILE_OK) return rc;
-    }
-    *tile = raw;
-    return MILE_OK;
-  };
-  return crps_run(nullptr, (char *)s->eval_ws + raw_bytes, C, S, N, Nt, pl, y, weights, n_w, o, st, fill);
+  return crps_run((char *)s->eval_ws, t, C, S, N, y, weights, n_w, o, st, stream_tiles(s, theta, (int64_t)C * S, t.chunk, X, st));
 }
 
 // mile_stack_eval: every check before any launch; rows in tiles whose responsibilities fit 256 MiB, k_stk_rows + k_stk_gram per
@@ -2783,26 +2752,17 @@ extern "C" int32_t mile_stack_eval(const double *lpd, const double *w, int32_t C
   p.score = score; p.row_score = row_score; p.grad = grad; p.hess = hess; p.used = (long long *)used;
   const int64_t Nt = stk_tile_rows(C, N, max_rows_per_tile);
   p.ldR = Nt;
-  void *ws = nullptr;
-  if (p.want_sums) {
-    const size_t rx_bytes = stk_rx_bytes(C, Nt);
-    if (hipMalloc(&ws, rx_bytes + stk_part_bytes(C, N)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(MILE_ERR_NOMEM, "mile_stack_eval: workspace allocation failed (lower max_rows_per_tile)");
+  const size_t rx_bytes = stk_rx_bytes(C, Nt);
+  return with_call_ws(p.want_sums ? rx_bytes + stk_part_bytes(C, N) : 0, "mile_stack_eval: workspace allocation failed (lower max_rows_per_tile)",
+                      st, [&](char *ws) -> int {
+    if (ws) { p.Rx = (double *)ws; p.part = (double *)(ws + rx_bytes); }
+    for (int64_t r0 = 0; r0 < N; r0 += Nt) {
+      p.r0 = r0; p.Nt = (int)std::min<int64_t>(Nt, N - r0);
+      HIP_TRY(mile_launch_stack_tile(p, st));
     }
-    p.Rx = (double *)ws; p.part = (double *)((char *)ws + rx_bytes);
-  }
-  hipError_t e = hipSuccess;
-  for (int64_t r0 = 0; r0 < N && e == hipSuccess; r0 += Nt) {
-    p.r0 = r0; p.Nt = (int)std::min<int64_t>(Nt, N - r0);
-    e = mile_launch_stack_tile(p, st);
-  }
-  if (e == hipSuccess && p.want_sums) e = mile_launch_stack_final(p, st);
-  const hipError_t es = hipStreamSynchronize(st);   // the workspace is this call's: the kernels finish before it goes
-  if (ws) (void)hipFree(ws);
-  HIP_TRY(e);
-  HIP_TRY(es);
-  return MILE_OK;
+    if (p.want_sums) HIP_TRY(mile_launch_stack_final(p, st));
+    return MILE_OK;
+  });
 }
 
 // mile_calibration / mile_calibration_stream: every check before any launch; rows in tiles whose per-chain sums and per-group
@@ -2814,8 +2774,7 @@ static const char *cal_bad_args(int32_t C, int64_t S, int64_t N, int32_t K, cons
                                 const CalOut &o) {
   if (!o.probs && !o.kept && !o.order && !o.set_size && !o.rank && !o.totals && !o.bins) return "no output asked for";
   if (C < 1 || C > 65535) return "C out of range (1 .. 65535)";
-  if (S < 1 || S > 0x7fffffff) return "S out of range (1 .. 2^31 - 1)";
-  if (N < 1 || N > 0x3fffffff) return "N out of range (1 .. 2^30 - 1)";
+  if (const char *m = bad_SN(S, N)) return m;
   if (K < 2 || K > CAL_K_MAX) return "K out of range (2 .. 64)";
   if (Q < 1 || Q > CAL_Q_MAX) return "Q out of range (1 .. 16)";
   for (int i = 0; i < Q; ++i) {
@@ -2829,35 +2788,33 @@ static const char *cal_bad_args(int32_t C, int64_t S, int64_t N, int32_t K, cons
 }
 
 static const int64_t CAL_STATE_TARGET = (int64_t)128 << 20;   // bytes of a tile's sums, counts and records; the pass's logits take as much
-static int64_t cal_tile_rows(int C, int K, int64_t N, int64_t max_rows) {
-  int64_t nt = std::max<int64_t>(1, CAL_STATE_TARGET / (int64_t)cal_row_bytes(C, K));
-  if (nt >= CAL_NT) nt = nt / CAL_NT * CAL_NT;
-  if (max_rows > 0) nt = std::min(nt, max_rows);
-  return std::min(nt, N);
-}
-static int64_t cal_pass_draws(int C, int K, int64_t S, int64_t Nt, int64_t max_draws) {
-  const int64_t J = max_draws ? max_draws : std::max<int64_t>(1, CAL_STATE_TARGET / ((int64_t)C * Nt * K * 4));
-  return std::min(J, S);
-}
-// bytes behind the pass's logits for tiles of Nt rows: sums, counts, records, the blocks' partial sums
-static size_t cal_state_bytes(int C, int K, int64_t N, int64_t Nt, int Q, int n_bins) {
-  return cal_sum_bytes(C, K, Nt) + cal_cnt_bytes(C, Nt) + cal_rec_bytes(C, Nt) + cal_part_bytes(N, C + 1, cal_cols(Q, n_bins));
+// The plan of one call: rows per tile (whole k_cal_accum workgroups), draws per pass and the byte offset of every block of its
+// workspace: sums, counts, records, the blocks' partial sums.  own_raw: the streamed call, whose workspace begins with a pass's
+// logits [C][J][Nt][K], as many bytes as the tile's state; else raw is the caller's and its S draws are one pass.
+struct CalTilePlan { int64_t Nt, J; size_t sum, cnt, rec, part, total; };
+static CalTilePlan cal_tile_plan(int C, int K, int64_t S, int64_t N, int Q, int n_bins, bool own_raw, int64_t max_rows, int64_t max_draws) {
+  CalTilePlan t;
+  t.Nt = tile_rows(CAL_STATE_TARGET, (int64_t)cal_row_bytes(C, K), CAL_NT, max_rows, N);
+  t.J = own_raw ? pass_draws(CAL_STATE_TARGET, (int64_t)C * t.Nt * K * 4, max_draws, S) : S;
+  t.sum = own_raw ? r256((size_t)C * t.J * t.Nt * K * 4) : 0;
+  t.cnt = t.sum + cal_sum_bytes(C, K, t.Nt);
+  t.rec = t.cnt + cal_cnt_bytes(C, t.Nt);
+  t.part = t.rec + cal_rec_bytes(C, t.Nt);
+  t.total = t.part + cal_part_bytes(N, C + 1, cal_cols(Q, n_bins));
+  return t;
 }
 
 // the tiles of one call: `accum` folds all draws of the tile p describes (r0, Nt) into p.sum / p.cnt, zeroed here
 template <class Accum>
-static int cal_run(char *state, int C, int64_t N, int K, int64_t Nt, const void *y, const double *coverages, int Q, int n_bins, const CalOut &o,
-                   hipStream_t st, Accum accum) {
+static int cal_run(char *ws, const CalTilePlan &t, int C, int64_t N, int K, const void *y, const double *coverages, int Q, int n_bins,
+                   const CalOut &o, hipStream_t st, Accum accum) {
   const int W = cal_cols(Q, n_bins);
+  const int64_t Nt = t.Nt;
   CalParams p{};
   p.C = C; p.K = K; p.Q = Q; p.n_bins = n_bins; p.N = N; p.y = (const int32_t *)y;
   for (int i = 0; i < Q; ++i) p.cov[i] = coverages[i];
-  p.sum = (double *)state;
-  p.cnt = (int32_t *)(state + cal_sum_bytes(C, K, Nt));
-  char *rec = (char *)p.cnt + cal_cnt_bytes(C, Nt);
   const bool reduce = y && (o.totals || o.bins);
-  p.rec = reduce ? (CalRec *)rec : nullptr;
-  p.part = (double *)(rec + cal_rec_bytes(C, Nt));
+  p.sum = (double *)(ws + t.sum); p.cnt = (int32_t *)(ws + t.cnt); p.rec = reduce ? (CalRec *)(ws + t.rec) : nullptr; p.part = (double *)(ws + t.part);
   p.B = cal_block_rows(N, C + 1, W); p.nblk = (N + p.B - 1) / p.B;
   p.probs = o.probs; p.kept = o.kept; p.order = o.order; p.set_size = o.set_size; p.rank = o.rank; p.totals = o.totals; p.bins = o.bins;
   if (reduce) HIP_TRY(hipMemsetAsync(p.part, 0, (size_t)(C + 1) * p.nblk * W * 8, st));
@@ -2881,30 +2838,21 @@ extern "C" int32_t mile_calibration(const float *raw, int32_t C, int64_t S, int6
   if (!raw || !coverages) return bad("null argument");
   if (const char *m = cal_bad_args(C, S, N, K, coverages, Q, n_bins, y, o)) return bad(m);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t Nt = cal_tile_rows(C, K, N, 0);
-  void *ws = nullptr;
-  if (hipMalloc(&ws, cal_state_bytes(C, K, N, Nt, Q, n_bins)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(MILE_ERR_NOMEM, "mile_calibration: workspace allocation failed");
-  }
-  const int rc = cal_run((char *)ws, C, N, K, Nt, y, coverages, Q, n_bins, o, st, [&](CalParams &p) -> int {
-    p.raw = raw + (size_t)p.r0 * K; p.cs = S; p.ld = N; p.J = (int)S;   // the caller's tensor, walked in place
-    HIP_TRY(mile_launch_cal_accum(p, st));
-    return MILE_OK;
+  const CalTilePlan t = cal_tile_plan(C, K, S, N, Q, n_bins, false, 0, 0);
+  return with_call_ws(t.total, "mile_calibration: workspace allocation failed", st, [&](char *ws) {
+    return cal_run(ws, t, C, N, K, y, coverages, Q, n_bins, o, st, [&](CalParams &p) -> int {
+      p.raw = raw + (size_t)p.r0 * K; p.cs = S; p.ld = N; p.J = (int)S;   // the caller's tensor, walked in place
+      HIP_TRY(mile_launch_cal_accum(p, st));
+      return MILE_OK;
+    });
   });
-  const hipError_t es = hipStreamSynchronize(st);   // the workspace is this call's: the kernels finish before it goes
-  (void)hipFree(ws);
-  if (rc != MILE_OK) return rc;
-  HIP_TRY(es);
-  return MILE_OK;
 }
 
 extern "C" int64_t mile_calibration_stream_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N) {
-  if (!s || C < 1 || C > 65535 || S < 1 || S > 0x7fffffff || N < 1 || N > 0x3fffffff) return -1;
+  if (!s || C < 1 || C > 65535 || bad_SN(S, N)) return -1;
   const int K = s->spec.widths[s->spec.n_layers - 1];
   if (s->spec.task != MILE_TASK_CLASSIFICATION || K < 2 || K > CAL_K_MAX) return -1;
-  const int64_t Nt = cal_tile_rows(C, K, N, 0), J = cal_pass_draws(C, K, S, Nt, 0);
-  return (int64_t)(cal_r256((size_t)C * J * Nt * K * 4) + cal_state_bytes(C, K, N, Nt, CAL_Q_MAX, CAL_BINS_MAX));
+  return (int64_t)cal_tile_plan(C, K, S, N, CAL_Q_MAX, CAL_BINS_MAX, true, 0, 0).total;
 }
 
 extern "C" int32_t mile_calibration_stream(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, const void *y, int64_t N,
@@ -2913,34 +2861,28 @@ extern "C" int32_t mile_calibration_stream(mile_sampler *s, const float *theta, 
                                            int64_t max_rows_per_tile, void *stream) {
   const CalOut o{probs, kept, order, set_size, rank, totals, bins};
   int K = 0;
-  const int rc0 = eval_args("mile_calibration_stream", s, !theta || !X || !coverages, S, N, [&]() -> const char * {
+  const int rc0 = eval_args("mile_calibration_stream", s, !theta || !X || !coverages, bad_SN(S, N), [&]() -> const char * {
     if (s->spec.task != MILE_TASK_CLASSIFICATION) return "needs a classification model";
     K = s->spec.widths[s->spec.n_layers - 1];
     if (const char *m = cal_bad_args(C, S, N, K, coverages, Q, n_bins, y, o)) return m;
-    if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
-    if (max_rows_per_tile < 0) return "max_rows_per_tile < 0";
-    return nullptr;
+    return bad_caps(max_draws_per_pass, max_rows_per_tile);
   });
   if (rc0 != MILE_OK) return rc0;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->device));
-  const int64_t Nt = cal_tile_rows(C, K, N, max_rows_per_tile), J = cal_pass_draws(C, K, S, Nt, max_draws_per_pass);
-  const size_t raw_bytes = cal_r256((size_t)C * J * Nt * K * 4);
-  if (reserve_eval_ws(s, raw_bytes + cal_state_bytes(C, K, N, Nt, Q, n_bins)) != hipSuccess)
+  const CalTilePlan t = cal_tile_plan(C, K, S, N, Q, n_bins, true, max_rows_per_tile, max_draws_per_pass);
+  if (reserve_eval_ws(s, t.total) != hipSuccess)
     return fail(MILE_ERR_NOMEM, "mile_calibration_stream: workspace allocation failed (lower max_draws_per_pass or max_rows_per_tile)");
   float *raw = (float *)s->eval_ws;
-  const size_t row_floats = (size_t)s->spec.in_features;
-  return cal_run((char *)s->eval_ws + raw_bytes, C, N, K, Nt, y, coverages, Q, n_bins, o, st, [&](CalParams &p) -> int {
+  return cal_run((char *)s->eval_ws, t, C, N, K, y, coverages, Q, n_bins, o, st, [&](CalParams &p) -> int {
     PredParams pp;
-    const int rc1 = stage_rows(s, (const float *)X + (size_t)p.r0 * row_floats, nullptr, p.Nt, pp, st);
+    const int rc1 = stage_rows(s, (const float *)X + (size_t)p.r0 * s->spec.in_features, nullptr, p.Nt, pp, st);
     if (rc1 != MILE_OK) return rc1;
     p.raw = raw; p.ld = p.Nt;
-    for (int64_t j0 = 0; j0 < S; j0 += J) {   // every (draw, row) forward once: chain c's draws j0 .. are rows c * S + j0 .. of theta
-      p.J = (int)std::min<int64_t>(J, S - j0); p.cs = p.J;
-      for (int c = 0; c < C; ++c) {
-        const int rc = eval_forward(s, pp, theta + ((size_t)c * S + (size_t)j0) * s->ds.d, p.J, raw + (size_t)c * p.J * p.Nt * K, st);
-        if (rc != MILE_OK) return rc;
-      }
+    for (int64_t j0 = 0; j0 < S; j0 += t.J) {   // every (draw, row) forward once
+      p.J = (int)std::min<int64_t>(t.J, S - j0); p.cs = p.J;
+      const int rc = forward_chains(s, pp, theta, C, S, j0, p.J, raw, st);
+      if (rc != MILE_OK) return rc;
       HIP_TRY(mile_launch_cal_accum(p, st));
     }
     return MILE_OK;
@@ -2950,7 +2892,7 @@ extern "C" int32_t mile_calibration_stream(mile_sampler *s, const float *theta, 
 // mile_lppd_stream: mile_pointwise_loglik's forward on the same draw window of every chain, a pass at a time, into the library's
 // workspace; k_lppd_accum folds the pass into the (m, s) state up to the next curve point, k_lppd_emit reduces the state there.
 // Every check before any launch (the curve points come to the host for theirs: a copy, no kernel).
-static bool lppd_shape_ok(int32_t C, int64_t N) { return C >= 1 && C <= LPPD_C_MAX && N >= 1 && N <= 0x3fffffff; }
+static bool lppd_shape_ok(int32_t C, int64_t N) { return C >= 1 && C <= LPPD_C_MAX && !bad_N(N); }
 
 extern "C" int64_t mile_lppd_stream_workspace(const mile_sampler *s, int32_t C, int64_t N) {
   if (!s || !lppd_shape_ok(C, N)) return -1;
@@ -2960,15 +2902,14 @@ extern "C" int64_t mile_lppd_stream_workspace(const mile_sampler *s, int32_t C, 
 extern "C" int32_t mile_lppd_stream(mile_sampler *s, const float *theta, int32_t C, int32_t S, const void *X, const void *y, int64_t N,
                                     const int32_t *curve_points, int32_t K, double *run_chain, double *run_ens, double *chain_lppd,
                                     double *row_lppd, double *lppd, int64_t *dropped, int64_t max_draws_per_pass, void *stream) {
-  const int rc1 = eval_args("mile_lppd_stream", s, !theta || !X || !y, S, N, [&]() -> const char * {
+  const int rc1 = eval_args("mile_lppd_stream", s, !theta || !X || !y, bad_SN(S, N), [&]() -> const char * {
     if (!lppd_shape_ok(C, N)) return "C out of range (1 .. 65535)";
     if (K < 0 || K > S) return "K out of range (0 .. S)";
     if (K == 0 && (run_chain || run_ens)) return "K = 0 with a curve output";
     if (K > 0 && !curve_points) return "null curve_points";
     if (K > 0 && !run_chain && !run_ens) return "curve points without a curve output";
     if (K == 0 && !chain_lppd && !row_lppd && !lppd && !dropped) return "no output asked for";
-    if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
-    return nullptr;
+    return bad_caps(max_draws_per_pass, 0);
   });
   if (rc1 != MILE_OK) return rc1;
   hipStream_t st = (hipStream_t)stream;
@@ -2983,9 +2924,8 @@ extern "C" int32_t mile_lppd_stream(mile_sampler *s, const float *theta, int32_t
     }
   }
   const int64_t per_draw = (int64_t)C * N * 4;   // one draw of every chain
-  int64_t J = max_draws_per_pass ? max_draws_per_pass : std::max<int64_t>(1, EVAL_PASS_TARGET / per_draw);
-  J = std::min<int64_t>(std::min<int64_t>(J, S), LPPD_J_MAX);
-  const size_t raw_bytes = ((size_t)J * per_draw + 255) / 256 * 256, st_bytes = lppd_state_bytes(C, N);
+  const int64_t J = pass_draws(EVAL_PASS_TARGET, per_draw, max_draws_per_pass, std::min<int64_t>(S, LPPD_J_MAX));
+  const size_t raw_bytes = r256((size_t)J * per_draw), st_bytes = lppd_state_bytes(C, N);
   if (reserve_eval_ws(s, raw_bytes + st_bytes) != hipSuccess)
     return fail(MILE_ERR_NOMEM, "mile_lppd_stream: workspace allocation failed (lower max_draws_per_pass)");
   const size_t cn = (size_t)C * (size_t)N;
@@ -3006,10 +2946,8 @@ extern "C" int32_t mile_lppd_stream(mile_sampler *s, const float *theta, int32_t
   int next = 0;   // next curve point
   for (int64_t j0 = 0; j0 < S; j0 += J) {
     p.J = (int)std::min<int64_t>(J, S - j0);
-    for (int c = 0; c < C; ++c) {   // chain c's draws j0 .. j0 + J - 1 are rows c * S + j0 .. of theta
-      const int rc = eval_forward(s, pp, theta + ((size_t)c * S + (size_t)j0) * s->ds.d, p.J, (float *)s->eval_ws + (size_t)c * p.J * N, st);
-      if (rc != MILE_OK) return rc;
-    }
+    const int rc = forward_chains(s, pp, theta, C, S, j0, p.J, (float *)s->eval_ws, st);
+    if (rc != MILE_OK) return rc;
     int ja = 0;
     while (ja < p.J) {   // split the pass at every curve point inside it
       const int jb = next < K && pts[next] <= j0 + p.J ? (int)(pts[next] - j0) : p.J;

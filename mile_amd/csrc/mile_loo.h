@@ -37,6 +37,7 @@
 #include <stdint.h>
 
 #include "../../include/mile_hip.h"
+#include "mile_eval_plan.h"
 
 #define LOO_NT 256                // k_loo_row workgroup: four waves
 #define LOO_NW (LOO_NT / 64)
@@ -68,7 +69,6 @@ static inline int loo_slices(int S, int Nt, int n_cu) {   // about two workgroup
   if (sl > s_tiles) sl = s_tiles;
   return sl < 1 ? 1 : sl;
 }
-static inline size_t loo_r256(size_t b) { return (b + 255) / 256 * 256; }
-static inline size_t loo_pk_bytes(int64_t S, int64_t Nt) { return loo_r256((size_t)S * (size_t)Nt * 4); }
+static inline size_t loo_pk_bytes(int64_t S, int64_t Nt) { return r256((size_t)S * (size_t)Nt * 4); }
 
 hipError_t mile_launch_loo(const LooParams &p, hipStream_t st);

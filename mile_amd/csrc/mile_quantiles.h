@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "../../include/mile_hip.h"
+#include "mile_eval_plan.h"
 
 #define QNT_MAX_Q 32
 #define QNT_NT 256                // solve workgroup: four waves
@@ -59,10 +60,9 @@ static inline int qnt_slices(int S, int Nt, int n_cu) {   // about two workgroup
   return sl < 1 ? 1 : sl;
 }
 // bytes behind the raw block: the packed copy, the slices' brackets and counts (each rounded up to 256)
-static inline size_t qnt_r256(size_t b) { return (b + 255) / 256 * 256; }
-static inline size_t qnt_pk_bytes(int64_t S, int64_t Nt) { return qnt_r256((size_t)S * (size_t)Nt * 8); }
+static inline size_t qnt_pk_bytes(int64_t S, int64_t Nt) { return r256((size_t)S * (size_t)Nt * 8); }
 static inline size_t qnt_part_bytes(int Nt, int Q, int slices) {
-  return qnt_r256((size_t)slices * Nt * Q * 16) + qnt_r256((size_t)slices * Nt * 4);
+  return r256((size_t)slices * Nt * Q * 16) + r256((size_t)slices * Nt * 4);
 }
 
 hipError_t mile_launch_quantiles(const QntParams &p, hipStream_t st);

@@ -22,6 +22,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mile_eval_plan.h"
+
 #define STK_NT 256               // every kernel's workgroup
 #define STK_TILE 64              // chains of an output tile's side
 #define STK_K 16                 // rows of a step through LDS
@@ -66,9 +68,8 @@ static inline int64_t stk_tile_rows(int64_t C, int64_t N, int64_t max_rows) {
   if (max_rows > 0 && nt > max_rows) nt = max_rows;
   return nt < N ? nt : N;
 }
-static inline size_t stk_r256(size_t b) { return (b + 255) / 256 * 256; }
-static inline size_t stk_rx_bytes(int64_t C, int64_t Nt) { return stk_r256((size_t)(C + 2) * (size_t)Nt * 8); }
-static inline size_t stk_part_bytes(int64_t C, int64_t N) { return stk_r256((size_t)stk_blocks(C, N) * (size_t)(C + 2) * (size_t)(C + 2) * 8); }
+static inline size_t stk_rx_bytes(int64_t C, int64_t Nt) { return r256((size_t)(C + 2) * (size_t)Nt * 8); }
+static inline size_t stk_part_bytes(int64_t C, int64_t N) { return r256((size_t)stk_blocks(C, N) * (size_t)(C + 2) * (size_t)(C + 2) * 8); }
 // what is wrong with the shape or the outputs asked for, or null
 static inline const char *stk_bad_args(int64_t C, int64_t N, int64_t max_rows, bool any_output) {
   if (C < 1 || C > STK_MAX_C) return "C out of range (1 .. 1024)";

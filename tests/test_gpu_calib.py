@@ -163,6 +163,31 @@ def test_nonfinite_draws_are_left_out_per_draw_and_row():
     assert got['rank'][5] == 0 and (got['set_size'][5] == 0).all() and (got['order'][5] == np.arange(K)).all()
 
 
+def test_logits_beyond_the_budget_are_walked_in_tiles_of_their_own_rows():
+    """C = 1024 members, K = 64: a row's sums, counts and records take 577 584 bytes, so the 128 MiB of a tile hold 232 rows,
+    192 in whole workgroups of 64.  N = 193 is that tile and one row more: mile_calibration walks the caller's logits
+    (ld = N) in two tiles.  A row's outputs depend on its own logits only, so they are, bit for bit, those of the call on each
+    tile's rows alone; the counts among totals and bins are exact sums of 0 / 1 and add up over the tiles."""
+    C_, S_, K, Q = 1024, 1, 64, len(COV)
+    tile = (128 << 20) // (C_ * (K * 8 + 4) + (C_ + 1) * 48) // 64 * 64
+    N = tile + 1
+    assert tile == 192
+    gen = torch.Generator(device=DEV).manual_seed(13)
+    raw = torch.randn(C_, S_, N, K, device=DEV, generator=gen)
+    y = torch.randint(0, K, (N,), device=DEV, generator=gen, dtype=torch.int32)
+    eng = _engine()
+    whole = _np(eng.calibration(raw, y, COV, NB))
+    parts = [_np(eng.calibration(raw[:, :, r0:r0 + tile].contiguous(), y[r0:r0 + tile], COV, NB)) for r0 in range(0, N, tile)]
+    assert (whole['kept'] == S_ * np.array([1] * C_ + [C_])[:, None]).all() and np.isfinite(whole['probs']).all()
+    for k, axis in (('probs', 1), ('kept', 1), ('order', 0), ('set_size', 0), ('rank', 0)):
+        both = np.concatenate([p[k] for p in parts], axis=axis)
+        assert whole[k].dtype == both.dtype and whole[k].tobytes() == both.tobytes(), k
+    counts = [0, 1, 4] + list(range(5, 5 + 2 * Q))                         # rows counted, correct, bad labels, covered, set sizes
+    assert (whole['totals'][:, counts] == sum(p['totals'][:, counts] for p in parts)).all()
+    assert (whole['bins'][:, :, [0, 2]] == sum(p['bins'][:, :, [0, 2]] for p in parts)).all()
+    assert whole['totals'][:, 0].tolist() == [N] * (C_ + 1)
+
+
 # ---- 3. the streamed call ---------------------------------------------------------------------------------------------------
 C_ST, S_ST, N_ST = 2, 3, 130
 FCN = {'tanh-3': (7, (40, 40, 3), 'tanh'), 'sigmoid-7': (11, (32, 7), 'sigmoid')}

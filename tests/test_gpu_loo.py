@@ -121,6 +121,20 @@ def test_the_sort_s_padding_boundary_and_the_longest_tail(S):
     _check_given(f'S={S}', _tensor(S, ('light', 'heavy1.5'), S % 1000))
 
 
+def test_a_tensor_beyond_the_budget_is_walked_in_tiles_of_its_own_rows():
+    """S = 2^20, N = 66: the packed copy of 64 rows fills the budget, so mile_psis_loo walks the caller's tensor (ld = N) in a
+    tile of 64 rows and one of 2.  A row's result depends on its own draws only: the call on all rows is, bit for bit, the
+    call on each tile's columns alone."""
+    S, N, tile = 1 << 20, 66, 64
+    assert (256 << 20) // (S * 4) == tile < N
+    ll = -torch.rand(S, N, device=DEV, generator=torch.Generator(device=DEV).manual_seed(11)).square_() - 0.5
+    eng = _engine()
+    whole = _np(eng.psis_loo(ll))
+    assert np.isfinite(whole['elpd_loo']).all() and not whole['dropped'].any()
+    parts = [_np(eng.psis_loo(ll[:, r0:r0 + tile].contiguous())) for r0 in range(0, N, tile)]
+    _same_bits('two tiles', whole, {k: np.concatenate([p[k] for p in parts]) for k in KEYS + ('dropped',)})
+
+
 def test_r_eff_moves_the_tail_length():
     ll = _tensor(1000, SEVEN, 9)
     assert LR.tail_length(1000, 0.2) == 200 and LR.tail_length(1000, 4.0) == 48 and LR.tail_length(1000) == 95

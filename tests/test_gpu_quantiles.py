@@ -156,6 +156,25 @@ def test_nonfinite_draws_are_left_out_per_row():
     assert (np.abs(q1 - q2) <= 2.0 ** -22 * np.maximum(np.abs(q2), QR.mixture_sd(raw)[1])).all()
 
 
+def test_outputs_beyond_the_budget_are_walked_in_tiles_of_their_own_rows():
+    """S = 2^20, N = 33: the packed copy of 32 rows fills the budget, so mile_mixture_quantiles walks the caller's array
+    (ld = N) in a tile of 32 rows and one of 1.  A row's result depends on its own pairs only: the call on all rows is, bit
+    for bit, the call on each tile's rows alone."""
+    S, N, tile, levels = 1 << 20, 33, 32, [0.05, 0.5, 0.95]
+    assert (256 << 20) // (S * 8) == tile < N
+    gen = torch.Generator(device=DEV).manual_seed(12)
+    raw = torch.randn(S, N, 2, device=DEV, generator=gen)
+    raw[..., 0] += torch.linspace(-3.0, 3.0, N, device=DEV)
+    raw[..., 1] *= 0.5
+    y = torch.linspace(-4.0, 4.0, N, device=DEV)
+    eng = _engine()
+    whole = eng.mixture_quantiles(raw, levels, y=y, return_dropped=True)
+    assert torch.isfinite(whole[0]).all() and not whole[2].any()
+    parts = [eng.mixture_quantiles(raw[:, r0:r0 + tile].contiguous(), levels, y=y[r0:r0 + tile], return_dropped=True) for r0 in range(0, N, tile)]
+    for k, name in enumerate(('quant', 'pit', 'dropped')):
+        assert torch.equal(whole[k], torch.cat([p[k] for p in parts])), name
+
+
 # ---- end to end ------------------------------------------------------------------------------------------------------------
 def _end_to_end(tag, eng, theta, X, out64, out32):
     levels = _levels()
