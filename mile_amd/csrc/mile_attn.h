@@ -43,6 +43,8 @@ struct AttnParams {
   const float *theta;   // [E, d] (gradient) or [S, d] (evaluation)
   const float *X;       // [N, T] token ids as fp32
   const void *y;        // [N] int32 labels
+  const float *emb;     // [V, C] frozen token table (mile_attn_pre.h); null where the tables are inside theta (g.emb / g.pos)
+  const float *pos;     // [T, C] frozen position rows, likewise
   float *slabs;         // [E, S, dp] likelihood-gradient slabs (gradient)
   float *llpart;        // [E, S] (gradient)
   float *out;           // [S, N] per-row log-likelihoods (evaluation); RAW: [S, N, K] logits, y unread
@@ -141,6 +143,186 @@ __device__ __forceinline__ void attn_probs(const float *QKV, int ld, const int *
   }
 }
 
+// ---- The blocks that attn_body (below) and attnp_body (mile_attn_pre.h) share: each exists once, here.  The workgroup barriers
+// between them stay in the bodies; the in-wave LDS ordering (attn_wave_sync) is inside.  What stays per kernel, because it is
+// not the same code: the Dense tail forward and backward (vectors at stride 64 against packed, `#pragma unroll 8`, accumulators
+// in registers against the slab row), the q | k | v product (LDS operands through attn_tile against the software-pipelined L2
+// form), and dW_qkv, de and the slab write-out.
+
+// tok[t] = the sequence's token ids clamped to [0, V), -1 for t in [T, Tp)
+__device__ __forceinline__ void attn_stage_tokens(int *tok, const float *X, int row, int T, int Tp, int V) {
+  for (int t = threadIdx.x; t < Tp; t += ATTN_NT) {
+    int v = -1;
+    if (t < T) v = min(max((int)X[(size_t)row * T + t], 0), V - 1);
+    tok[t] = v;
+  }
+}
+
+// e [Tp][C] = embt[tok] + post (token table [V][C], position rows [T][C]), rows past T zero.  V C < 2^32 (V <= 2^24, C <= 192)
+__device__ __forceinline__ void attn_stage_e(float *e, const int *tok, const float *embt, const float *post, int T, int Tp, int C) {
+  for (int i = threadIdx.x; i < Tp * C; i += ATTN_NT) {
+    const int t = i / C, c = i - t * C;
+    e[i] = t < T ? embt[(size_t)tok[t] * C + c] + post[t * C + c] : 0.0f;
+  }
+}
+
+// Attention forward of head h, by one wave: obar[h hd ..) = invT sum_j colsum_j(P) v_j, invT = 1 / T.  Its scalars are arguments
+// and attn_bwd_head reads its own from the geometry: other forms spill in k_grad_attn<1, *> or cost k_out_attn a wave per SIMD
+// (profiles/r08/01_attn_shared_blocks.md).  attnp_body<WIDE> keeps this text in place of the call, for speed.
+template <int NJ>
+__device__ __forceinline__ void attn_fwd_head(const float *QKV, int ld, const int *tok, int T, int D, int hd, int h, int nj, float invT,
+                                              float *obar) {
+  const int lane = threadIdx.x & 63, col = lane & 15, kq = lane >> 4;
+  float cs[NJ];
+#pragma unroll
+  for (int jt = 0; jt < NJ; ++jt) cs[jt] = 0.0f;
+  for (int it = 0; it < nj; ++it) {
+    f32x4 pr[NJ];
+    attn_probs<NJ>(QKV, ld, tok, T, D, hd, it, h, pr, nj);
+#pragma unroll
+    for (int jt = 0; jt < NJ; ++jt) cs[jt] += (pr[jt][0] + pr[jt][1]) + (pr[jt][2] + pr[jt][3]);
+  }
+#pragma unroll
+  for (int jt = 0; jt < NJ; ++jt) { cs[jt] += __shfl_xor(cs[jt], 16); cs[jt] += __shfl_xor(cs[jt], 32); }
+  for (int d0 = 0; d0 < hd; d0 += 4) {
+    const int dd = d0 + kq;
+    float a = 0.0f;
+#pragma unroll
+    for (int jt = 0; jt < NJ; ++jt)
+      if (jt < nj && dd < hd) a = fmaf(cs[jt], QKV[(jt * 16 + col) * ld + 2 * D + h * hd + dd], a);
+    a += __shfl_xor(a, 1); a += __shfl_xor(a, 2); a += __shfl_xor(a, 4); a += __shfl_xor(a, 8);
+    if (col == 0 && dd < hd) obar[h * hd + dd] = a * invT;
+  }
+}
+
+// The head, by wave 0 (tid < 64): log softmax of the logits lg [K] at the label.  !GRAD: the row's log-likelihood goes to
+// *out_ll.  GRAD: lg becomes d(ll) / d(logits), zero for a row whose ll is NaN (`bad`; the caller leaves it out of its sum).
+struct AttnHead { float ll; bool bad; };
+template <bool GRAD>
+__device__ __forceinline__ AttnHead attn_head(float *lg, int K, int yi, float *out_ll) {
+  const int tid = threadIdx.x;
+  float mx = -INFINITY;
+  for (int k = 0; k < K; ++k) mx = fmaxf(mx, lg[k]);
+  float se = 0.0f;
+  for (int k = 0; k < K; ++k) se += expf(lg[k] - mx);
+  const float lse = mx + logf(se);
+  const float ll = lg[min(max(yi, 0), K - 1)] - lse;
+  const bool bad = isnan(ll);
+  const float dl = (bad || tid >= K) ? 0.0f : ((tid == yi ? 1.0f : 0.0f) - expf(lg[min(tid, K - 1)] - lse));
+  if (!GRAD && tid == 0) *out_ll = ll;
+  if (GRAD) {
+    __builtin_amdgcn_wave_barrier();
+    if (tid < K) lg[tid] = dl;
+  }
+  return {ll, bad};
+}
+
+// Attention backward of head h, by one wave.  In: q' | k | v of the head in QKV [Tp][3D], dobar [D].
+// Out: dq (pre-scale) | dK | dV over them.  The wave's scratch, carved out by the caller: dS [16][Tp], u [Tp], and for NHT > 1
+// (dK too large for registers) dKl [Tp][16 NHT].
+template <int NJ, int NHT>
+__device__ __forceinline__ void attn_bwd_head(const AttnGeom &g, float *QKV, const int *tok, int h, const float *dobar, float *dS, float *u,
+                                              float *dKl) {
+  constexpr bool DKL = NHT > 1;                      // dK in the wave's scratch, not in registers
+  const int lane = threadIdx.x & 63, col = lane & 15, kq = lane >> 4;
+  const int T = g.T, Tp = g.Tp, D = g.D, hd = g.hd, ld = 3 * D, nj = Tp / 16;
+  const float scale = 1.0f / sqrtf((float)hd), invT = 1.0f / (float)T;
+  if (DKL) {
+    for (int i = lane; i < Tp * 16 * NHT; i += 64) dKl[i] = 0.0f;
+  }
+  for (int j = lane; j < Tp; j += 64) {
+    float a = 0.0f;
+    for (int dd = 0; dd < hd; ++dd) a = fmaf(dobar[h * hd + dd], QKV[j * ld + 2 * D + h * hd + dd], a);
+    u[j] = a * invT;
+  }
+  attn_wave_sync();
+  float cs[NJ];
+  f32x4 dk[NJ];
+#pragma unroll
+  for (int jt = 0; jt < NJ; ++jt) { cs[jt] = 0.0f; dk[jt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
+  for (int it = 0; it < nj; ++it) {
+    f32x4 pr[NJ];
+    attn_probs<NJ>(QKV, ld, tok, T, D, hd, it, h, pr, nj);
+    float uj[NJ];
+#pragma unroll
+    for (int jt = 0; jt < NJ; ++jt) uj[jt] = jt < nj ? u[jt * 16 + col] : 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = it * 16 + 4 * kq + r;
+      const bool real = i < T && tok[i] > 0;
+      float rs = 0.0f;
+#pragma unroll
+      for (int jt = 0; jt < NJ; ++jt) rs = fmaf(pr[jt][r], uj[jt], rs);
+      rs += __shfl_xor(rs, 1); rs += __shfl_xor(rs, 2); rs += __shfl_xor(rs, 4); rs += __shfl_xor(rs, 8);
+#pragma unroll
+      for (int jt = 0; jt < NJ; ++jt) {
+        cs[jt] += pr[jt][r];
+        if (jt < nj) dS[(4 * kq + r) * Tp + jt * 16 + col] = real ? pr[jt][r] * (uj[jt] - rs) : 0.0f;
+      }
+    }
+    attn_wave_sync();
+    const float *Qh = QKV + h * hd, *Kh = QKV + D + h * hd;
+    // dK[j] += sum_i dS[i][j] q'[i] over this tile's rows
+    if (!DKL) {
+#pragma unroll
+      for (int jt = 0; jt < NJ; ++jt)
+        if (jt < nj)
+          dk[jt] = attn_tile(16, [&](int m, int k) { return dS[k * Tp + jt * 16 + m]; },
+                             [&](int k, int n) { return n < hd ? Qh[(it * 16 + k) * ld + n] : 0.0f; }, dk[jt]);
+    } else {
+      for (int jt = 0; jt < nj; ++jt)
+#pragma unroll
+        for (int q = 0; q < NHT; ++q) {
+          f32x4 a;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) a[r] = dKl[(jt * 16 + 4 * kq + r) * 16 * NHT + q * 16 + col];
+          a = attn_tile(16, [&](int m, int k) { return dS[k * Tp + jt * 16 + m]; },
+                        [&](int k, int n) { return q * 16 + n < hd ? Qh[(it * 16 + k) * ld + q * 16 + n] : 0.0f; }, a);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) dKl[(jt * 16 + 4 * kq + r) * 16 * NHT + q * 16 + col] = a[r];
+        }
+    }
+    // dq (pre-scale) = dS K / sqrt(hd) for this tile's rows, written over q'
+    f32x4 dq[NHT];
+#pragma unroll
+    for (int q = 0; q < NHT; ++q)
+      dq[q] = attn_tile(Tp, [&](int m, int k) { return dS[m * Tp + k]; },
+                        [&](int k, int n) { return q * 16 + n < hd ? Kh[k * ld + q * 16 + n] : 0.0f; }, f32x4{0.0f, 0.0f, 0.0f, 0.0f});
+    attn_wave_sync();
+#pragma unroll
+    for (int q = 0; q < NHT; ++q)
+      if (q * 16 + col < hd)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) QKV[(it * 16 + 4 * kq + r) * ld + h * hd + q * 16 + col] = dq[q][r] * scale;
+    attn_wave_sync();
+  }
+#pragma unroll
+  for (int jt = 0; jt < NJ; ++jt) { cs[jt] += __shfl_xor(cs[jt], 16); cs[jt] += __shfl_xor(cs[jt], 32); }
+  // dV[j] = (dobar_h / T) colsum_j; dK written over k
+  for (int d0 = 0; d0 < hd; d0 += 4) {
+    const int dd = d0 + kq;
+    if (dd < hd) {
+      const float gdd = dobar[h * hd + dd] * invT;
+#pragma unroll
+      for (int jt = 0; jt < NJ; ++jt)
+        if (jt < nj) QKV[(jt * 16 + col) * ld + 2 * D + h * hd + dd] = gdd * cs[jt];
+    }
+  }
+  if (!DKL) {
+#pragma unroll
+    for (int jt = 0; jt < NJ; ++jt)
+      if (jt < nj && col < hd)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) QKV[(jt * 16 + 4 * kq + r) * ld + D + h * hd + col] = dk[jt][r];
+  } else {
+    attn_wave_sync();
+    for (int i = lane; i < Tp * hd; i += 64) {
+      const int j = i / hd, dd = i - j * hd;
+      QKV[j * ld + D + h * hd + dd] = dKl[j * 16 * NHT + dd];
+    }
+  }
+}
+
 // NHT: ceil(hd / 16) (dK register tiles per key tile); WL: Wq|Wk|Wv staged in LDS
 // RAW (evaluation only): the logits go to out[e][row][K] and the head is skipped, y unread (mile_predict)
 template <int NHT, bool WL, bool GRAD, bool RAW = false>
@@ -204,16 +386,9 @@ __device__ __forceinline__ void attn_body(const AttnParams &p) {
 
   for (int row = r_begin; row < r_end; ++row) {
     __syncthreads();                                 // previous sequence's readers are done
-    for (int t = tid; t < Tp; t += ATTN_NT) {
-      int v = -1;
-      if (t < T) v = min(max((int)p.X[(size_t)row * T + t], 0), V - 1);
-      tok[t] = v;
-    }
+    attn_stage_tokens(tok, p.X, row, T, Tp, V);
     __syncthreads();
-    for (int i = tid; i < Tp * C; i += ATTN_NT) {
-      const int t = i / C, c = i - t * C;
-      scr[i] = t < T ? th[g.emb + tok[t] * C + c] + th[g.pos + t * C + c] : 0.0f;
-    }
+    attn_stage_e(scr, tok, th + g.emb, th + g.pos, T, Tp, C);
     __syncthreads();
     // ---- q | k | v = e W (+ b); q scaled by 1/sqrt(hd)
     for (int f = wave; f < nj * 3 * ND; f += 4) {
@@ -233,30 +408,9 @@ __device__ __forceinline__ void attn_body(const AttnParams &p) {
     }
     __syncthreads();
     // ---- attention forward: column sums of P per head -> obar
-    for (int h = wave; h < H; h += 4) {
-      float cs[NJ];
-#pragma unroll
-      for (int jt = 0; jt < NJ; ++jt) cs[jt] = 0.0f;
-      for (int it = 0; it < nj; ++it) {
-        f32x4 pr[NJ];
-        attn_probs<NJ>(QKV, ld, tok, T, D, hd, it, h, pr, nj);
-#pragma unroll
-        for (int jt = 0; jt < NJ; ++jt) cs[jt] += (pr[jt][0] + pr[jt][1]) + (pr[jt][2] + pr[jt][3]);
-      }
-#pragma unroll
-      for (int jt = 0; jt < NJ; ++jt) { cs[jt] += __shfl_xor(cs[jt], 16); cs[jt] += __shfl_xor(cs[jt], 32); }
-      for (int d0 = 0; d0 < hd; d0 += 4) {
-        const int dd = d0 + kq;
-        float a = 0.0f;
-#pragma unroll
-        for (int jt = 0; jt < NJ; ++jt)
-          if (jt < nj && dd < hd) a = fmaf(cs[jt], QKV[(jt * 16 + col) * ld + 2 * D + h * hd + dd], a);
-        a += __shfl_xor(a, 1); a += __shfl_xor(a, 2); a += __shfl_xor(a, 4); a += __shfl_xor(a, 8);
-        if (col == 0 && dd < hd) obar[h * hd + dd] = a * invT;
-      }
-    }
+    for (int h = wave; h < H; h += 4) attn_fwd_head<NJ>(QKV, ld, tok, T, D, hd, h, nj, invT, obar);
     __syncthreads();
-    // ---- tail: pooled = obar Wo (+ bo), projections with gelu, classifier
+    // ---- tail: pooled = obar Wo (+ bo), projections with gelu, classifier (this kernel's own: vectors at stride 64)
     if (tid < C) {
       float a = g.bias ? th[g.b_o + tid] : 0.0f;
       for (int d = 0; d < D; ++d) a = fmaf(obar[d], th[g.k_o + d * C + tid], a);
@@ -285,25 +439,12 @@ __device__ __forceinline__ void attn_body(const AttnParams &p) {
     if constexpr (RAW) continue;
     __syncthreads();
     if (tid < 64) {   // wave 0: head (log softmax at the label, its gradient)
-      float mx = -INFINITY;
-      for (int k = 0; k < K; ++k) mx = fmaxf(mx, lg[k]);
-      float se = 0.0f;
-      for (int k = 0; k < K; ++k) se += expf(lg[k] - mx);
-      const float lse = mx + logf(se);
-      const int yi = ((const int32_t *)p.y)[row];
-      float ll = lg[min(max(yi, 0), K - 1)] - lse;
-      const bool bad = isnan(ll);
-      const float dl = (bad || tid >= K) ? 0.0f : ((tid == yi ? 1.0f : 0.0f) - expf(lg[min(tid, K - 1)] - lse));
-      if (!GRAD && tid == 0) p.out[(size_t)e * p.N + row] = ll;
-      if (GRAD) {
-        if (tid == 0) ll_acc += bad ? 0.0f : ll;
-        __builtin_amdgcn_wave_barrier();
-        if (tid < K) lg[tid] = dl;
-      }
+      const AttnHead hh = attn_head<GRAD>(lg, K, ((const int32_t *)p.y)[row], GRAD ? nullptr : p.out + (size_t)e * p.N + row);
+      if (GRAD && tid == 0) ll_acc += hh.bad ? 0.0f : hh.ll;
     }
     if (!GRAD) continue;
     __syncthreads();
-    // ---- backward through the tail
+    // ---- backward through the tail (this kernel's own: weight gradients in registers)
 #pragma unroll
     for (int m = 0; m < NFW; ++m)
       if (q4 + 4 * m < PL && lane < K) gwc[m] = fmaf(zL[q4 + 4 * m], lg[lane], gwc[m]);
@@ -345,114 +486,12 @@ __device__ __forceinline__ void attn_body(const AttnParams &p) {
     __syncthreads();
     // ---- attention backward, head by head (wave-owned columns of q | k | v)
     for (int h = wave; h < H; h += 4) {
-      constexpr bool DKL = NHT > 1;                  // dK in the wave's scratch, not in registers
-      constexpr int NHR = DKL ? 1 : NHT;
-      float *u = uw + wave * Tp, *dS = scr + wave * attn_scr_wave(g), *dKl = dS + 16 * Tp;   // dKl [Tp][16 NHT]
-      if (DKL) {
-        for (int i = lane; i < Tp * 16 * NHT; i += 64) dKl[i] = 0.0f;
-      }
-      for (int j = lane; j < Tp; j += 64) {
-        float a = 0.0f;
-        for (int dd = 0; dd < hd; ++dd) a = fmaf(dobar[h * hd + dd], QKV[j * ld + 2 * D + h * hd + dd], a);
-        u[j] = a * invT;
-      }
-      attn_wave_sync();
-      float cs[NJ];
-      f32x4 dk[NJ][NHR];
-#pragma unroll
-      for (int jt = 0; jt < NJ; ++jt) {
-        cs[jt] = 0.0f;
-#pragma unroll
-        for (int q = 0; q < NHR; ++q) dk[jt][q] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      }
-      for (int it = 0; it < nj; ++it) {
-        f32x4 pr[NJ];
-        attn_probs<NJ>(QKV, ld, tok, T, D, hd, it, h, pr, nj);
-        float uj[NJ];
-#pragma unroll
-        for (int jt = 0; jt < NJ; ++jt) uj[jt] = jt < nj ? u[jt * 16 + col] : 0.0f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = it * 16 + 4 * kq + r;
-          const bool real = i < T && tok[i] > 0;
-          float rs = 0.0f;
-#pragma unroll
-          for (int jt = 0; jt < NJ; ++jt) rs = fmaf(pr[jt][r], uj[jt], rs);
-          rs += __shfl_xor(rs, 1); rs += __shfl_xor(rs, 2); rs += __shfl_xor(rs, 4); rs += __shfl_xor(rs, 8);
-#pragma unroll
-          for (int jt = 0; jt < NJ; ++jt) {
-            cs[jt] += pr[jt][r];
-            if (jt < nj) dS[(4 * kq + r) * Tp + jt * 16 + col] = real ? pr[jt][r] * (uj[jt] - rs) : 0.0f;
-          }
-        }
-        attn_wave_sync();
-        const float *Qh = QKV + h * hd, *Kh = QKV + D + h * hd;
-        // dK[j] += sum_i dS[i][j] q'[i] over this tile's rows
-        if (!DKL) {
-#pragma unroll
-          for (int jt = 0; jt < NJ; ++jt)
-            if (jt < nj)
-              dk[jt][0] = attn_tile(16, [&](int m, int k) { return dS[k * Tp + jt * 16 + m]; },
-                                    [&](int k, int n) { return n < hd ? Qh[(it * 16 + k) * ld + n] : 0.0f; }, dk[jt][0]);
-        } else {
-          for (int jt = 0; jt < nj; ++jt)
-#pragma unroll
-            for (int q = 0; q < NHT; ++q) {
-              f32x4 a;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) a[r] = dKl[(jt * 16 + 4 * kq + r) * 16 * NHT + q * 16 + col];
-              a = attn_tile(16, [&](int m, int k) { return dS[k * Tp + jt * 16 + m]; },
-                            [&](int k, int n) { return q * 16 + n < hd ? Qh[(it * 16 + k) * ld + q * 16 + n] : 0.0f; }, a);
-#pragma unroll
-              for (int r = 0; r < 4; ++r) dKl[(jt * 16 + 4 * kq + r) * 16 * NHT + q * 16 + col] = a[r];
-            }
-        }
-        // dq (pre-scale) = dS K / sqrt(hd) for this tile's rows, written over q'
-        f32x4 dq[NHT];
-#pragma unroll
-        for (int q = 0; q < NHT; ++q)
-          dq[q] = attn_tile(Tp, [&](int m, int k) { return dS[m * Tp + k]; },
-                            [&](int k, int n) { return q * 16 + n < hd ? Kh[k * ld + q * 16 + n] : 0.0f; }, f32x4{0.0f, 0.0f, 0.0f, 0.0f});
-        attn_wave_sync();
-#pragma unroll
-        for (int q = 0; q < NHT; ++q)
-          if (q * 16 + col < hd)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) QKV[(it * 16 + 4 * kq + r) * ld + h * hd + q * 16 + col] = dq[q][r] * scale;
-        attn_wave_sync();
-      }
-#pragma unroll
-      for (int jt = 0; jt < NJ; ++jt) { cs[jt] += __shfl_xor(cs[jt], 16); cs[jt] += __shfl_xor(cs[jt], 32); }
-      // dV[j] = (dobar_h / T) colsum_j; dK written over k
-      for (int d0 = 0; d0 < hd; d0 += 4) {
-        const int dd = d0 + kq;
-        if (dd < hd) {
-          const float gdd = dobar[h * hd + dd] * invT;
-#pragma unroll
-          for (int jt = 0; jt < NJ; ++jt)
-            if (jt < nj) QKV[(jt * 16 + col) * ld + 2 * D + h * hd + dd] = gdd * cs[jt];
-        }
-      }
-      if (!DKL) {
-#pragma unroll
-        for (int jt = 0; jt < NJ; ++jt)
-          if (jt < nj && col < hd)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) QKV[(jt * 16 + 4 * kq + r) * ld + D + h * hd + col] = dk[jt][0][r];
-      } else {
-        attn_wave_sync();
-        for (int i = lane; i < Tp * hd; i += 64) {
-          const int j = i / hd, dd = i - j * hd;
-          QKV[j * ld + D + h * hd + dd] = dKl[j * 16 * NHT + dd];
-        }
-      }
+      float *dS = scr + wave * attn_scr_wave(g);
+      attn_bwd_head<NJ, NHT>(g, QKV, tok, h, dobar, dS, uw + wave * Tp, dS + 16 * Tp);
     }
     __syncthreads();
     // ---- e again (the scratch held dS), then dW_qkv += e^T d(qkv), de = d(qkv) W^T
-    for (int i = tid; i < Tp * C; i += ATTN_NT) {
-      const int t = i / C, c = i - t * C;
-      scr[i] = t < T ? th[g.emb + tok[t] * C + c] + th[g.pos + t * C + c] : 0.0f;
-    }
+    attn_stage_e(scr, tok, th + g.emb, th + g.pos, T, Tp, C);
     if (g.bias && tid < ld) {
       float a = 0.0f;
       for (int t = 0; t < T; ++t) a += QKV[t * ld + tid];
@@ -543,6 +582,38 @@ template <int NHT, bool WL>
 static __global__ __launch_bounds__(ATTN_NT) void k_fwd_attn(const AttnParams p) { attn_body<NHT, WL, false>(p); }
 template <int NHT, bool WL>
 static __global__ __launch_bounds__(ATTN_NT) void k_out_attn(const AttnParams p) { attn_body<NHT, WL, false, true>(p); }
+
+// the envelope k_grad_attn takes (mile_create refuses everything else; spec.py AttentionSpec mirrors it)
+__host__ inline bool attn_supported(const AttnGeom &g) {
+  if (g.T < 1 || g.T > ATTN_MAX_T || g.C < 1 || g.C > ATTN_MAX_C || g.D < 1 || g.D > ATTN_MAX_D || g.H < 1 || g.D % g.H ||
+      g.K < 1 || g.K > ATTN_MAX_K || g.NP < 0 || g.NP > ATTN_MAX_NP || g.Tp != (g.T + 15) / 16 * 16 || g.V < 1)
+    return false;
+  for (int l = 0; l < g.NP; ++l)
+    if (g.P[l] < 1 || g.P[l] > ATTN_MAX_P) return false;
+  return attn_lds_bytes(g, false) <= ATTN_LDS_MAX;
+}
+
+// The launch of all three attention translation units.  KS names a kernel family by its members grad<NHT>, fwd<NHT>,
+// out<NHT>; the instantiation is picked by ceil(hd / 16) in 1..MAX, the kernel by `run`, and it runs on grid (p.S, E) with
+// `lds` bytes of dynamic LDS.
+template <auto K>
+static hipError_t attn_launch_kernel(const AttnParams &p, int E, size_t lds, hipStream_t st) {
+  const hipError_t e = mile_set_max_lds<K>(ATTN_LDS_MAX);
+  if (e != hipSuccess) return e;
+  K<<<dim3(p.S, E), ATTN_NT, lds, st>>>(p);
+  return hipGetLastError();
+}
+template <class KS, int MAX, int NHT = 1>
+static hipError_t attn_launch(const AttnParams &p, int E, MileRun run, size_t lds, hipStream_t st) {
+  if constexpr (NHT > MAX) {
+    return hipErrorInvalidValue;
+  } else {
+    if ((p.g.hd + 15) / 16 != NHT) return attn_launch<KS, MAX, NHT + 1>(p, E, run, lds, st);
+    return run == MILE_RUN_GRAD  ? attn_launch_kernel<KS::template grad<NHT>>(p, E, lds, st)
+           : run == MILE_RUN_RAW ? attn_launch_kernel<KS::template out<NHT>>(p, E, lds, st)
+                                 : attn_launch_kernel<KS::template fwd<NHT>>(p, E, lds, st);
+  }
+}
 
 // MILE_RUN_GRAD: grid (S row ranges, E chains) -> slabs / llpart; _LOGLIK / _RAW: grid (S row blocks, E samples) -> out
 hipError_t mile_launch_attn(const AttnParams &p, int E, MileRun run, hipStream_t st);

@@ -2,7 +2,8 @@
 //   x [T] token ids -> e = emb[x] + pos[0..T) (frozen tables loaded from .npy, not parameters) -> MDPA as in mile_attn.h ->
 //   mean over all T positions -> (Dense P_i -> gelu) per projection -> gelu -> Dense K 'classifier'
 // One fused forward + backward launch per gradient: k_grad_attn_pre, grid (S row ranges, E chains), 256 threads (4 waves), one
-// sequence at a time.  The products, the masking and the attention backward are those of k_grad_attn (attn_tile, attn_probs).
+// sequence at a time.  The products and the masking are those of k_grad_attn (attn_tile, attn_probs), and so are the blocks of
+// mile_attn.h that attnp_body calls: token and e staging, the attention forward and backward of one head, the head.
 // What differs:
 //   - C <= 192 and D <= 128: Wq|Wk|Wv (up to 288 KB) never fit in LDS next to the sequence, so every weight streams from L2.
 //     LDS holds q|k|v [Tp][3D], a scratch that is e [Tp][C] while the projections and dW_qkv run and per-wave dS tiles, u and
@@ -26,19 +27,6 @@
 #define ATTNP_MAX_C 192
 #define ATTNP_MAX_D 128        // hd = D / H <= 128: ceil(hd / 16) <= 8 dq register tiles
 #define ATTNP_MAX_P 128
-
-struct AttnPreParams {
-  AttnGeom g;            // emb / pos offsets are -1: the tables are not parameters
-  const float *theta;    // [E, d] (gradient) or [S, d] (evaluation)
-  const float *X;        // [N, T] token ids as fp32
-  const void *y;         // [N] int32 labels
-  const float *emb;      // [V, C] frozen token table
-  const float *pos;      // [T, C] frozen position rows
-  float *slabs;          // [E, S, dp] likelihood-gradient slabs (gradient)
-  float *llpart;         // [E, S] (gradient)
-  float *out;            // [S, N] per-row log-likelihoods (evaluation)
-  int N, S, dp;
-};
 
 // tail vectors (float offsets): tok [Tp] | obar [D] | dobar [D] | z0 [C] z1 [P0] z2 [P1] (layer inputs) | a0 [P0] a1 [P1]
 // (pre-activations) | zf [PL] (after the extra gelu) | dv0, dv1 [W] | lg [16]
@@ -77,7 +65,7 @@ __host__ __device__ inline size_t attnp_lds_bytes(const AttnGeom &g) {
 // theta, p.emb / p.pos unused), they get a gradient, and the classifier reads the last projection without the extra gelu
 // RAW (evaluation only): the logits go to out[e][row][K] and the head is skipped, y unread (mile_predict)
 template <int NHT, bool GRAD, bool WIDE = false, bool RAW = false>
-__device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
+__device__ __forceinline__ void attnp_body(const AttnParams &p) {
   constexpr int NJ = ATTN_MAX_T / 16;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const AttnGeom &g = p.g;
@@ -116,12 +104,6 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
   const int rows_per = (p.N + nsplit - 1) / nsplit;
   const int r_begin = min(p.N, s * rows_per), r_end = min(p.N, r_begin + rows_per);
 
-  auto stage_e = [&]() {
-    for (int i = tid; i < Tp * C; i += ATTN_NT) {
-      const int t = i / C, c = i - t * C;
-      scr[i] = t < T ? embt[(size_t)tok[t] * C + c] + post[t * C + c] : 0.0f;
-    }
-  };
   // slab[off + r nb + c] (+)= a[r] b[c] over [na][nb]: thread-owned flat entries
   auto rank1 = [&](int off, const float *a, int na, const float *b, int nb, bool first) {
     const int dr = ATTN_NT / nb, dc = ATTN_NT - dr * nb;
@@ -146,13 +128,9 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
   for (int row = r_begin; row < r_end; ++row) {
     const bool first = row == r_begin;
     __syncthreads();                                 // previous sequence's readers are done
-    for (int t = tid; t < Tp; t += ATTN_NT) {
-      int v = -1;
-      if (t < T) v = min(max((int)p.X[(size_t)row * T + t], 0), V - 1);
-      tok[t] = v;
-    }
+    attn_stage_tokens(tok, p.X, row, T, Tp, V);
     __syncthreads();
-    stage_e();
+    attn_stage_e(scr, tok, embt, post, T, Tp, C);
     __syncthreads();
     // ---- q | k | v = e W (+ b), W from global; q scaled by 1/sqrt(hd).  A wave owns a 16-column block of [Wq|Wk|Wv] and all
     // nj row tiles: each W operand it loads from L2 feeds nj MFMAs, and the next k step's operand is loaded before this one's
@@ -187,6 +165,7 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
     }
     __syncthreads();
     // ---- attention forward: column sums of P per head -> obar
+    if constexpr (WIDE) {   // attn_fwd_head's text in place: called as a function, k_grad_attn_wide was 1.2 % slower (profiles/r08)
     for (int h = wave; h < H; h += 4) {
       float cs[NJ];
 #pragma unroll
@@ -209,8 +188,11 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
         if (col == 0 && dd < hd) obar[h * hd + dd] = a * invT;
       }
     }
+    } else {
+    for (int h = wave; h < H; h += 4) attn_fwd_head<NJ>(QKV, ld, tok, T, D, hd, h, nj, invT, obar);
+    }
     __syncthreads();
-    // ---- tail: pooled = obar Wo (+ bo), projections with gelu, the extra gelu, classifier
+    // ---- tail: pooled = obar Wo (+ bo), projections with gelu, the extra gelu, classifier (this kernel's own: packed vectors)
     if (tid < C) {
       float a = g.bias ? th[g.b_o + tid] : 0.0f;
       #pragma unroll 8
@@ -244,25 +226,12 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
     if constexpr (RAW) continue;
     __syncthreads();
     if (tid < 64) {   // wave 0: head (log softmax at the label, its gradient)
-      float mx = -INFINITY;
-      for (int k = 0; k < K; ++k) mx = fmaxf(mx, lg[k]);
-      float se = 0.0f;
-      for (int k = 0; k < K; ++k) se += expf(lg[k] - mx);
-      const float lse = mx + logf(se);
-      const int yi = ((const int32_t *)p.y)[row];
-      float ll = lg[min(max(yi, 0), K - 1)] - lse;
-      const bool bad = isnan(ll);
-      const float dl = (bad || tid >= K) ? 0.0f : ((tid == yi ? 1.0f : 0.0f) - expf(lg[min(tid, K - 1)] - lse));
-      if (!GRAD && tid == 0) p.out[(size_t)e * p.N + row] = ll;
-      if (GRAD) {
-        if (tid == 0) ll_acc += bad ? 0.0f : ll;
-        __builtin_amdgcn_wave_barrier();
-        if (tid < K) lg[tid] = dl;
-      }
+      const AttnHead hh = attn_head<GRAD>(lg, K, ((const int32_t *)p.y)[row], GRAD ? nullptr : p.out + (size_t)e * p.N + row);
+      if (GRAD && tid == 0) ll_acc += hh.bad ? 0.0f : hh.ll;
     }
     if (!GRAD) continue;
     __syncthreads();
-    // ---- backward through the tail; rank-1 weight gradients into the slab row
+    // ---- backward through the tail (this kernel's own); rank-1 weight gradients into the slab row
     rank1(g.k_c, zc, PL, lg, K, first);
     if (g.bias && tid < K) slab[g.b_c + tid] = first ? lg[tid] : slab[g.b_c + tid] + lg[tid];
     float *dcur = dv0, *dnxt = dv1;
@@ -296,108 +265,14 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
       dobar[tid] = a;
     }
     __syncthreads();
-    // ---- attention backward, head by head (wave-owned columns of q | k | v), as in k_grad_attn
+    // ---- attention backward, head by head (wave-owned columns of q | k | v)
     for (int h = wave; h < H; h += 4) {
-      constexpr bool DKL = NHT > 1;                  // dK in the wave's scratch, not in registers
-      float *dS = scr + wave * attnp_scr_wave(g), *u = dS + 16 * Tp, *dKl = u + Tp;   // dKl [Tp][16 NHT]
-      if (DKL) {
-        for (int i = lane; i < Tp * 16 * NHT; i += 64) dKl[i] = 0.0f;
-      }
-      for (int j = lane; j < Tp; j += 64) {
-        float a = 0.0f;
-        for (int dd = 0; dd < hd; ++dd) a = fmaf(dobar[h * hd + dd], QKV[j * ld + 2 * D + h * hd + dd], a);
-        u[j] = a * invT;
-      }
-      attn_wave_sync();
-      float cs[NJ];
-      f32x4 dk[NJ];
-#pragma unroll
-      for (int jt = 0; jt < NJ; ++jt) { cs[jt] = 0.0f; dk[jt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
-      for (int it = 0; it < nj; ++it) {
-        f32x4 pr[NJ];
-        attn_probs<NJ>(QKV, ld, tok, T, D, hd, it, h, pr, nj);
-        float uj[NJ];
-#pragma unroll
-        for (int jt = 0; jt < NJ; ++jt) uj[jt] = jt < nj ? u[jt * 16 + col] : 0.0f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = it * 16 + 4 * kq + r;
-          const bool real = i < T && tok[i] > 0;
-          float rs = 0.0f;
-#pragma unroll
-          for (int jt = 0; jt < NJ; ++jt) rs = fmaf(pr[jt][r], uj[jt], rs);
-          rs += __shfl_xor(rs, 1); rs += __shfl_xor(rs, 2); rs += __shfl_xor(rs, 4); rs += __shfl_xor(rs, 8);
-#pragma unroll
-          for (int jt = 0; jt < NJ; ++jt) {
-            cs[jt] += pr[jt][r];
-            if (jt < nj) dS[(4 * kq + r) * Tp + jt * 16 + col] = real ? pr[jt][r] * (uj[jt] - rs) : 0.0f;
-          }
-        }
-        attn_wave_sync();
-        const float *Qh = QKV + h * hd, *Kh = QKV + D + h * hd;
-        // dK[j] += sum_i dS[i][j] q'[i] over this tile's rows
-        if (!DKL) {
-#pragma unroll
-          for (int jt = 0; jt < NJ; ++jt)
-            if (jt < nj)
-              dk[jt] = attn_tile(16, [&](int m, int k) { return dS[k * Tp + jt * 16 + m]; },
-                                 [&](int k, int n) { return n < hd ? Qh[(it * 16 + k) * ld + n] : 0.0f; }, dk[jt]);
-        } else {
-          for (int jt = 0; jt < nj; ++jt)
-#pragma unroll
-            for (int q = 0; q < NHT; ++q) {
-              f32x4 a;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) a[r] = dKl[(jt * 16 + 4 * kq + r) * 16 * NHT + q * 16 + col];
-              a = attn_tile(16, [&](int m, int k) { return dS[k * Tp + jt * 16 + m]; },
-                            [&](int k, int n) { return q * 16 + n < hd ? Qh[(it * 16 + k) * ld + q * 16 + n] : 0.0f; }, a);
-#pragma unroll
-              for (int r = 0; r < 4; ++r) dKl[(jt * 16 + 4 * kq + r) * 16 * NHT + q * 16 + col] = a[r];
-            }
-        }
-        // dq (pre-scale) = dS K / sqrt(hd) for this tile's rows, written over q'
-        f32x4 dq[NHT];
-#pragma unroll
-        for (int q = 0; q < NHT; ++q)
-          dq[q] = attn_tile(Tp, [&](int m, int k) { return dS[m * Tp + k]; },
-                            [&](int k, int n) { return q * 16 + n < hd ? Kh[k * ld + q * 16 + n] : 0.0f; }, f32x4{0.0f, 0.0f, 0.0f, 0.0f});
-        attn_wave_sync();
-#pragma unroll
-        for (int q = 0; q < NHT; ++q)
-          if (q * 16 + col < hd)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) QKV[(it * 16 + 4 * kq + r) * ld + h * hd + q * 16 + col] = dq[q][r] * scale;
-        attn_wave_sync();
-      }
-#pragma unroll
-      for (int jt = 0; jt < NJ; ++jt) { cs[jt] += __shfl_xor(cs[jt], 16); cs[jt] += __shfl_xor(cs[jt], 32); }
-      // dV[j] = (dobar_h / T) colsum_j; dK written over k
-      for (int d0 = 0; d0 < hd; d0 += 4) {
-        const int dd = d0 + kq;
-        if (dd < hd) {
-          const float gdd = dobar[h * hd + dd] * invT;
-#pragma unroll
-          for (int jt = 0; jt < NJ; ++jt)
-            if (jt < nj) QKV[(jt * 16 + col) * ld + 2 * D + h * hd + dd] = gdd * cs[jt];
-        }
-      }
-      if (!DKL) {
-#pragma unroll
-        for (int jt = 0; jt < NJ; ++jt)
-          if (jt < nj && col < hd)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) QKV[(jt * 16 + 4 * kq + r) * ld + D + h * hd + col] = dk[jt][r];
-      } else {
-        attn_wave_sync();
-        for (int i = lane; i < Tp * hd; i += 64) {
-          const int j = i / hd, dd = i - j * hd;
-          QKV[j * ld + D + h * hd + dd] = dKl[j * 16 * NHT + dd];
-        }
-      }
+      float *dS = scr + wave * attnp_scr_wave(g), *u = dS + 16 * Tp;
+      attn_bwd_head<NJ, NHT>(g, QKV, tok, h, dobar, dS, u, u + Tp);
     }
     __syncthreads();
     // ---- e again (the scratch held dS), then dW_qkv (+)= e^T d(qkv) into the slab, one 16x16 tile per wave at a time
-    stage_e();
+    attn_stage_e(scr, tok, embt, post, T, Tp, C);
     if (g.bias)
       for (int n = tid; n < ld; n += ATTN_NT) {
         float a = 0.0f;
@@ -475,11 +350,11 @@ __device__ __forceinline__ void attnp_body(const AttnPreParams &p) {
 }
 
 template <int NHT>
-static __global__ __launch_bounds__(ATTN_NT) void k_grad_attn_pre(const AttnPreParams p) { attnp_body<NHT, true>(p); }
+static __global__ __launch_bounds__(ATTN_NT) void k_grad_attn_pre(const AttnParams p) { attnp_body<NHT, true>(p); }
 template <int NHT>
-static __global__ __launch_bounds__(ATTN_NT) void k_fwd_attn_pre(const AttnPreParams p) { attnp_body<NHT, false>(p); }
+static __global__ __launch_bounds__(ATTN_NT) void k_fwd_attn_pre(const AttnParams p) { attnp_body<NHT, false>(p); }
 template <int NHT>
-static __global__ __launch_bounds__(ATTN_NT) void k_out_attn_pre(const AttnPreParams p) { attnp_body<NHT, false, false, true>(p); }
+static __global__ __launch_bounds__(ATTN_NT) void k_out_attn_pre(const AttnParams p) { attnp_body<NHT, false, false, true>(p); }
 
 // the envelope k_grad_attn_pre takes (mile_create refuses everything else; spec.py PretrainedAttentionSpec mirrors it)
 __host__ inline bool attnp_supported(const AttnGeom &g) {
@@ -492,4 +367,4 @@ __host__ inline bool attnp_supported(const AttnGeom &g) {
 }
 
 // MILE_RUN_GRAD: grid (S row ranges, E chains) -> slabs / llpart; _LOGLIK / _RAW: grid (S row blocks, E samples) -> out
-hipError_t mile_launch_attn_pre(const AttnPreParams &p, int E, MileRun run, hipStream_t st);
+hipError_t mile_launch_attn_pre(const AttnParams &p, int E, MileRun run, hipStream_t st);

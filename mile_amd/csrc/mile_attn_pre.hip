@@ -4,31 +4,13 @@
 
 #include "mile_attn_pre.h"
 
-template <int NHT>
-static hipError_t launch_t(const AttnPreParams &p, int E, MileRun run, hipStream_t st) {
-  const size_t lds = attnp_lds_bytes(p.g);
-  hipError_t e = run == MILE_RUN_GRAD  ? mile_set_max_lds<k_grad_attn_pre<NHT>>(ATTN_LDS_MAX)
-                 : run == MILE_RUN_RAW ? mile_set_max_lds<k_out_attn_pre<NHT>>(ATTN_LDS_MAX)
-                                       : mile_set_max_lds<k_fwd_attn_pre<NHT>>(ATTN_LDS_MAX);
-  if (e != hipSuccess) return e;
-  const dim3 grid(p.S, E);
-  if (run == MILE_RUN_GRAD) k_grad_attn_pre<NHT><<<grid, ATTN_NT, lds, st>>>(p);
-  else if (run == MILE_RUN_RAW) k_out_attn_pre<NHT><<<grid, ATTN_NT, lds, st>>>(p);
-  else k_fwd_attn_pre<NHT><<<grid, ATTN_NT, lds, st>>>(p);
-  return hipGetLastError();
-}
+struct AttnPreKernels {
+  template <int NHT> static constexpr auto grad = k_grad_attn_pre<NHT>;
+  template <int NHT> static constexpr auto fwd = k_fwd_attn_pre<NHT>;
+  template <int NHT> static constexpr auto out = k_out_attn_pre<NHT>;
+};
 
-hipError_t mile_launch_attn_pre(const AttnPreParams &p, int E, MileRun run, hipStream_t st) {
+hipError_t mile_launch_attn_pre(const AttnParams &p, int E, MileRun run, hipStream_t st) {
   if (!attnp_supported(p.g) || !p.emb || !p.pos) return hipErrorInvalidValue;
-  switch ((p.g.hd + 15) / 16) {
-    case 1: return launch_t<1>(p, E, run, st);
-    case 2: return launch_t<2>(p, E, run, st);
-    case 3: return launch_t<3>(p, E, run, st);
-    case 4: return launch_t<4>(p, E, run, st);
-    case 5: return launch_t<5>(p, E, run, st);
-    case 6: return launch_t<6>(p, E, run, st);
-    case 7: return launch_t<7>(p, E, run, st);
-    case 8: return launch_t<8>(p, E, run, st);
-  }
-  return hipErrorInvalidValue;
+  return attn_launch<AttnPreKernels, 8>(p, E, run, attnp_lds_bytes(p.g), st);
 }

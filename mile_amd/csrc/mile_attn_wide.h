@@ -11,15 +11,14 @@
 #include "mile_attn_pre.h"
 
 template <int NHT>
-static __global__ __launch_bounds__(ATTN_NT) void k_grad_attn_wide(const AttnPreParams p) { attnp_body<NHT, true, true>(p); }
+static __global__ __launch_bounds__(ATTN_NT) void k_grad_attn_wide(const AttnParams p) { attnp_body<NHT, true, true>(p); }
 template <int NHT>
-static __global__ __launch_bounds__(ATTN_NT) void k_fwd_attn_wide(const AttnPreParams p) { attnp_body<NHT, false, true>(p); }
+static __global__ __launch_bounds__(ATTN_NT) void k_fwd_attn_wide(const AttnParams p) { attnp_body<NHT, false, true>(p); }
 template <int NHT>
-static __global__ __launch_bounds__(ATTN_NT) void k_out_attn_wide(const AttnPreParams p) { attnp_body<NHT, false, true, true>(p); }
+static __global__ __launch_bounds__(ATTN_NT) void k_out_attn_wide(const AttnParams p) { attnp_body<NHT, false, true, true>(p); }
 
-__host__ __device__ inline size_t attn_wide_lds_bytes(const AttnGeom &g) { return attnp_lds_bytes(g); }
 // the envelope k_grad_attn_wide takes (mile_create refuses everything else; spec.py WideAttentionSpec mirrors it)
 __host__ inline bool attn_wide_supported(const AttnGeom &g) { return attnp_supported(g) && g.emb >= 0 && g.pos >= 0; }
 
 // MILE_RUN_GRAD: grid (S row ranges, E chains) -> slabs / llpart; _LOGLIK / _RAW: grid (S row blocks, E samples) -> out
-hipError_t mile_launch_attn_wide(const AttnPreParams &p, int E, MileRun run, hipStream_t st);
+hipError_t mile_launch_attn_wide(const AttnParams &p, int E, MileRun run, hipStream_t st);

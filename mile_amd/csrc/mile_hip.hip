@@ -266,11 +266,13 @@ static int lenetti_S(const mile_sampler *s, int E) {
   return std::max(1, std::min({64, want, std::max(1, s->N / 32)}));
 }
 
-// k_grad_attn / k_grad_attn_pre: one workgroup per CU (its LDS), at most 64 row ranges and at least 16 sequences per range
-static int attn_S(const mile_sampler *s, int E) {
-  const int want = (s->n_cu + std::max(E, 1) - 1) / std::max(E, 1);
-  return std::max(1, std::min({64, want, std::max(1, s->N / 16)}));
+// k_grad_attn / k_grad_attn_pre, and the evaluation of all three attention models: one workgroup per CU (its LDS), at most 64
+// row ranges and at least 16 sequences per range
+static int attn_ranges(int n_cu, int E, int rows) {
+  const int want = (n_cu + std::max(E, 1) - 1) / std::max(E, 1);
+  return std::max(1, std::min({64, want, std::max(1, rows / 16)}));
 }
+static int attn_S(const mile_sampler *s, int E) { return attn_ranges(s->n_cu, E, s->N); }
 
 // k_grad_attn_wide: every row range is one more slab row, and a slab row holds a [V][C] table block (7.68 MB at V = 10 000,
 // C = 192) that its workgroup zero-fills before the first sequence and the update sums afterwards.  One workgroup per CU is
@@ -438,77 +440,35 @@ static int layout_lenetti(mile_sampler *s) {   // ravel_pytree order of {'core':
   return MILE_OK;
 }
 
-// ravel_pytree order (sorted keys): MDPA.{key, out, query, value}, TokenEmbedding_0, classifier, projection_*; bias before kernel.
-// ABI layers: key, out, query, value, Embedding, PositionEmbedding (no bias: -1), classifier, projection_*
-static int layout_attn(mile_sampler *s) {
-  const mile_model_spec *spec = &s->spec;
-  if (spec->task != MILE_TASK_CLASSIFICATION) return fail(MILE_ERR_INVALID, "AttentionClassifier: classification only");
-  if (spec->n_layers < 1 || spec->n_layers > ATTN_MAX_NP + 1)
-    return fail(MILE_ERR_INVALID, "AttentionClassifier: widths = projection_dim (at most 2) + [n_classes]");
-  if (spec->ctx_len < 1 || spec->ctx_len > ATTN_MAX_T || spec->in_features != spec->ctx_len)
-    return fail(MILE_ERR_INVALID, "AttentionClassifier: 1 <= ctx_len <= 128 and in_features == ctx_len");
-  if (spec->emb_size < 1 || spec->emb_size > ATTN_MAX_C) return fail(MILE_ERR_INVALID, "AttentionClassifier: emb_size <= 64");
-  if (spec->qkv_dim < 1 || spec->qkv_dim > ATTN_MAX_D || spec->n_heads < 1 || spec->qkv_dim % spec->n_heads)
-    return fail(MILE_ERR_INVALID, "AttentionClassifier: qkv_dim <= 64 and n_heads dividing it");
-  if (spec->vocab_size < 1 || spec->vocab_size > (1 << 24)) return fail(MILE_ERR_INVALID, "AttentionClassifier: 1 <= vocab_size <= 2^24");
-  for (int l = 0; l + 1 < spec->n_layers; ++l)
-    if (spec->widths[l] > ATTN_MAX_P) return fail(MILE_ERR_INVALID, "AttentionClassifier: projection widths <= 64");
-  if (spec->widths[spec->n_layers - 1] > ATTN_MAX_K) return fail(MILE_ERR_INVALID, "AttentionClassifier: n_classes <= 16");
-  AttnGeom &g = s->ag;
-  g.V = spec->vocab_size; g.T = spec->ctx_len; g.C = spec->emb_size; g.H = spec->n_heads; g.D = spec->qkv_dim;
-  g.hd = g.D / g.H; g.NP = spec->n_layers - 1; g.K = spec->widths[g.NP]; g.bias = spec->use_bias ? 1 : 0;
-  g.Tp = (g.T + 15) / 16 * 16;
-  for (int l = 0; l < ATTN_MAX_NP; ++l) { g.P[l] = l < g.NP ? spec->widths[l] : 0; g.b_p[l] = g.k_p[l] = -1; }
-  if (attn_lds_bytes(g, false) > ATTN_LDS_MAX) return fail(MILE_ERR_INVALID, "AttentionClassifier: shape needs more than 160 KB of LDS");
-  long long o = 0;
-  auto put = [&](int &b, int &k, long long nb, long long nk) { b = g.bias && nb ? (int)o : -1; o += g.bias ? nb : 0; k = (int)o; o += nk; };
-  int no_bias;
-  put(g.b_k, g.k_k, g.D, (long long)g.C * g.D);
-  put(g.b_o, g.k_o, g.C, (long long)g.D * g.C);
-  put(g.b_q, g.k_q, g.D, (long long)g.C * g.D);
-  put(g.b_v, g.k_v, g.D, (long long)g.C * g.D);
-  put(no_bias, g.emb, 0, (long long)g.V * g.C);
-  put(no_bias, g.pos, 0, (long long)g.T * g.C);
-  put(g.b_c, g.k_c, g.K, (long long)(g.NP ? g.P[g.NP - 1] : g.C) * g.K);
-  for (int l = 0; l < g.NP; ++l) put(g.b_p[l], g.k_p[l], g.P[l], (long long)(l ? g.P[l - 1] : g.C) * g.P[l]);
-  if (o > 0x7fffffffLL) return fail(MILE_ERR_INVALID, "AttentionClassifier: too many parameters");
-  g.d = (int)o;
-  s->ds.d = g.d;
-  s->ds.widths[0] = g.K;
-  s->ds.b_off[0] = g.b_c; s->ds.w_off[0] = g.k_c;
-  s->ds.max_width = 64; s->ds.act_stride = 0;
-  s->layers = {{g.b_k, g.k_k}, {g.b_o, g.k_o}, {g.b_q, g.k_q}, {g.b_v, g.k_v}, {-1, g.emb}, {-1, g.pos}, {g.b_c, g.k_c}};
-  for (int l = 0; l < g.NP; ++l) s->layers.push_back({g.b_p[l], g.k_p[l]});
-  return MILE_OK;
-}
-
-// The two models on the kernel that streams its weights (mile_attn_pre.h body): limits C <= 192, D <= 128, projections <= 128.
-//   tables == false, PretrainedAttentionClassifier: ravel_pytree order MDPA.{key, out, query, value}, classifier, projection_*;
-//     bias before kernel.  No TokenEmbedding_0 leaves: the tables are frozen (mile_set_embedding).  ABI layers: key, out, query,
-//     value, classifier, projection_*
-//   tables == true, AttentionClassifier on k_grad_attn_wide: layout_attn's parameters and ABI layers (the tables are leaves)
-static int layout_attn_streamed(mile_sampler *s, const std::string &name, bool tables) {
+// The three attention models.  tables == true (the two AttentionClassifiers): ravel_pytree order (sorted keys) MDPA.{key, out,
+// query, value}, TokenEmbedding_0, classifier, projection_*; bias before kernel.  ABI layers: key, out, query, value, Embedding,
+// PositionEmbedding (no bias: -1), classifier, projection_*.  tables == false (PretrainedAttentionClassifier): the same without
+// the TokenEmbedding_0 leaves and their two ABI layers -- the tables are frozen (mile_set_embedding).
+// max_c / max_d / max_p: the kernel's limits on emb_size, qkv_dim and the projection widths; supported: its envelope, LDS
+// included; max_v: token ids travel as fp32, so the vocabulary ends at 2^24 (the wide model takes what its spec takes, V < 2^24)
+static int layout_attn_model(mile_sampler *s, const std::string &name, int max_c, int max_d, int max_p, bool tables,
+                             bool (*supported)(const AttnGeom &), int max_v) {
   const mile_model_spec *spec = &s->spec;
   if (spec->task != MILE_TASK_CLASSIFICATION) return fail(MILE_ERR_INVALID, name + ": classification only");
   if (spec->n_layers < 1 || spec->n_layers > ATTN_MAX_NP + 1)
     return fail(MILE_ERR_INVALID, name + ": widths = projection_dim (at most 2) + [n_classes]");
   if (spec->ctx_len < 1 || spec->ctx_len > ATTN_MAX_T || spec->in_features != spec->ctx_len)
     return fail(MILE_ERR_INVALID, name + ": 1 <= ctx_len <= 128 and in_features == ctx_len");
-  if (spec->emb_size < 1 || spec->emb_size > ATTNP_MAX_C) return fail(MILE_ERR_INVALID, name + ": emb_size <= 192");
-  if (spec->qkv_dim < 1 || spec->qkv_dim > ATTNP_MAX_D || spec->n_heads < 1 || spec->qkv_dim % spec->n_heads)
-    return fail(MILE_ERR_INVALID, name + ": qkv_dim <= 128 and n_heads dividing it");
-  // token ids travel as fp32: the new model takes what its spec takes (V < 2^24); the pretrained one keeps its bound
-  if (spec->vocab_size < 1 || spec->vocab_size > (1 << 24) - (tables ? 1 : 0))
-    return fail(MILE_ERR_INVALID, name + (tables ? ": 1 <= vocab_size < 2^24" : ": 1 <= vocab_size <= 2^24"));
+  if (spec->emb_size < 1 || spec->emb_size > max_c) return fail(MILE_ERR_INVALID, name + ": emb_size <= " + std::to_string(max_c));
+  if (spec->qkv_dim < 1 || spec->qkv_dim > max_d || spec->n_heads < 1 || spec->qkv_dim % spec->n_heads)
+    return fail(MILE_ERR_INVALID, name + ": qkv_dim <= " + std::to_string(max_d) + " and n_heads dividing it");
+  if (spec->vocab_size < 1 || spec->vocab_size > max_v)
+    return fail(MILE_ERR_INVALID, name + (max_v < (1 << 24) ? ": 1 <= vocab_size < 2^24" : ": 1 <= vocab_size <= 2^24"));
   for (int l = 0; l + 1 < spec->n_layers; ++l)
-    if (spec->widths[l] > ATTNP_MAX_P) return fail(MILE_ERR_INVALID, name + ": projection widths <= 128");
+    if (spec->widths[l] > max_p) return fail(MILE_ERR_INVALID, name + ": projection widths <= " + std::to_string(max_p));
   if (spec->widths[spec->n_layers - 1] > ATTN_MAX_K) return fail(MILE_ERR_INVALID, name + ": n_classes <= 16");
   AttnGeom &g = s->ag;
   g.V = spec->vocab_size; g.T = spec->ctx_len; g.C = spec->emb_size; g.H = spec->n_heads; g.D = spec->qkv_dim;
   g.hd = g.D / g.H; g.NP = spec->n_layers - 1; g.K = spec->widths[g.NP]; g.bias = spec->use_bias ? 1 : 0;
   g.Tp = (g.T + 15) / 16 * 16;
   for (int l = 0; l < ATTN_MAX_NP; ++l) { g.P[l] = l < g.NP ? spec->widths[l] : 0; g.b_p[l] = g.k_p[l] = -1; }
-  if (!attnp_supported(g)) return fail(MILE_ERR_INVALID, name + ": shape needs more than 160 KB of LDS");   // (= attn_wide_lds_bytes)
+  g.emb = g.pos = tables ? 0 : -1;                   // (the wide envelope asks for tables; their offsets follow)
+  if (!supported(g)) return fail(MILE_ERR_INVALID, name + ": shape needs more than 160 KB of LDS");
   long long o = 0;
   auto put = [&](int &b, int &k, long long nb, long long nk) { b = g.bias && nb ? (int)o : -1; o += g.bias ? nb : 0; k = (int)o; o += nk; };
   int no_bias;
@@ -516,7 +476,6 @@ static int layout_attn_streamed(mile_sampler *s, const std::string &name, bool t
   put(g.b_o, g.k_o, g.C, (long long)g.D * g.C);
   put(g.b_q, g.k_q, g.D, (long long)g.C * g.D);
   put(g.b_v, g.k_v, g.D, (long long)g.C * g.D);
-  g.emb = g.pos = -1;
   if (tables) {
     put(no_bias, g.emb, 0, (long long)g.V * g.C);
     put(no_bias, g.pos, 0, (long long)g.T * g.C);
@@ -535,8 +494,15 @@ static int layout_attn_streamed(mile_sampler *s, const std::string &name, bool t
   for (int l = 0; l < g.NP; ++l) s->layers.push_back({g.b_p[l], g.k_p[l]});
   return MILE_OK;
 }
-static int layout_attn_pre(mile_sampler *s) { return layout_attn_streamed(s, "PretrainedAttentionClassifier", false); }
-static int layout_attn_wide(mile_sampler *s) { return layout_attn_streamed(s, "AttentionClassifier (wide)", true); }
+static int layout_attn(mile_sampler *s) {
+  return layout_attn_model(s, "AttentionClassifier", ATTN_MAX_C, ATTN_MAX_D, ATTN_MAX_P, true, attn_supported, 1 << 24);
+}
+static int layout_attn_pre(mile_sampler *s) {
+  return layout_attn_model(s, "PretrainedAttentionClassifier", ATTNP_MAX_C, ATTNP_MAX_D, ATTNP_MAX_P, false, attnp_supported, 1 << 24);
+}
+static int layout_attn_wide(mile_sampler *s) {
+  return layout_attn_model(s, "AttentionClassifier (wide)", ATTNP_MAX_C, ATTNP_MAX_D, ATTNP_MAX_P, true, attn_wide_supported, (1 << 24) - 1);
+}
 
 extern "C" {
 
@@ -1619,38 +1585,20 @@ static hipError_t launch_lenetti(mile_sampler *s, const float *theta, int E, con
   return mile_launch_lenetti(lp, E, run_of(y, out_ll), st);
 }
 
-// ---- AttentionClassifier (mile_attn.h; the kernels are instantiated in mile_attn.hip).  Gradient (out_ll == nullptr): grid
-// (S row ranges, E chains) -> slabs / llpart; evaluation: grid (S row blocks, E samples) -> out_ll[e * N + row], or
-// (y == nullptr) the logits out_ll[(e * N + row) * K + c]
+// ---- the three attention models (mile_attn.h, mile_attn_pre.h, mile_attn_wide.h; the kernels are instantiated in the .hip file
+// of the same name).  Gradient (out_ll == nullptr): grid (S row ranges, E chains) -> slabs / llpart; evaluation: grid (S row
+// blocks, E samples) -> out_ll[e * N + row], or (y == nullptr) the logits out_ll[(e * N + row) * K + c]
 static hipError_t launch_attn(mile_sampler *s, const float *theta, int E, const float *X, const void *y, int N, int S, int dp,
                               float *out_ll, hipStream_t st) {
   AttnParams ap{};
   ap.g = s->ag;
-  ap.theta = theta; ap.X = X; ap.y = y; ap.slabs = s->slabs; ap.llpart = s->llpart; ap.out = out_ll;
-  ap.N = N; ap.S = S; ap.dp = dp;
-  return mile_launch_attn(ap, E, run_of(y, out_ll), st);
-}
-
-// ---- PretrainedAttentionClassifier (mile_attn_pre.h; the kernels are instantiated in mile_attn_pre.hip), as launch_attn
-static hipError_t launch_attn_pre(mile_sampler *s, const float *theta, int E, const float *X, const void *y, int N, int S, int dp,
-                                  float *out_ll, hipStream_t st) {
-  AttnPreParams ap{};
-  ap.g = s->ag;
-  ap.theta = theta; ap.X = X; ap.y = y; ap.emb = s->emb_tab; ap.pos = s->pos_tab;
+  ap.theta = theta; ap.X = X; ap.y = y; ap.emb = s->emb_tab; ap.pos = s->pos_tab;   // the tables: null but for the pretrained model
   ap.slabs = s->slabs; ap.llpart = s->llpart; ap.out = out_ll;
   ap.N = N; ap.S = S; ap.dp = dp;
-  return mile_launch_attn_pre(ap, E, run_of(y, out_ll), st);
-}
-
-// ---- wide AttentionClassifier (mile_attn_wide.h; the kernels are instantiated in mile_attn_wide.hip), as launch_attn
-static hipError_t launch_attn_wide(mile_sampler *s, const float *theta, int E, const float *X, const void *y, int N, int S, int dp,
-                                   float *out_ll, hipStream_t st) {
-  AttnPreParams ap{};
-  ap.g = s->ag;
-  ap.theta = theta; ap.X = X; ap.y = y;
-  ap.slabs = s->slabs; ap.llpart = s->llpart; ap.out = out_ll;
-  ap.N = N; ap.S = S; ap.dp = dp;
-  return mile_launch_attn_wide(ap, E, run_of(y, out_ll), st);
+  const MileRun run = run_of(y, out_ll);
+  return is_attn(s) ? mile_launch_attn(ap, E, run, st)
+         : is_attn_pre(s) ? mile_launch_attn_pre(ap, E, run, st)
+                          : mile_launch_attn_wide(ap, E, run, st);
 }
 
 // ---- the gradient of each grad kernel: the `grad` of its row in kGrad.  gp holds the row window and S; fz the update that runs
@@ -1682,14 +1630,6 @@ static int grad_narrow(mile_sampler *s, const GradParams &gp, const W64Fuse &, i
 }
 static int grad_attn(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
   HIP_TRY(launch_attn(s, gp.theta, E, gp.X, gp.y, gp.N, gp.S, gp.dp, nullptr, st));
-  return MILE_OK;
-}
-static int grad_attn_pre(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
-  HIP_TRY(launch_attn_pre(s, gp.theta, E, gp.X, gp.y, gp.N, gp.S, gp.dp, nullptr, st));
-  return MILE_OK;
-}
-static int grad_attn_wide(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
-  HIP_TRY(launch_attn_wide(s, gp.theta, E, gp.X, gp.y, gp.N, gp.S, gp.dp, nullptr, st));
   return MILE_OK;
 }
 static int grad_lenetti(mile_sampler *s, const GradParams &gp, const W64Fuse &, int E, hipStream_t st) {
@@ -2036,10 +1976,8 @@ static int launch_fwd_wide(mile_sampler *s, const float *theta, int S, const flo
 
 // ---- evaluation of each grad kernel's model: the `loglik` of its row in kGrad.  pp holds the staged evaluation set; without
 // labels (pp.y == nullptr, mile_predict) every row of the table writes the raw outputs, O floats per (sample, row) -----------------
-template <hipError_t (*LAUNCH)(mile_sampler *, const float *, int, const float *, const void *, int, int, int, float *, hipStream_t)>
-static int loglik_attn_t(mile_sampler *s, PredParams pp, int S, hipStream_t st) {   // the three attention models: their launcher
-  const int SB = std::max(1, std::min({64, (s->n_cu + S - 1) / S, std::max(1, pp.N / 16)}));
-  HIP_TRY(LAUNCH(s, pp.theta, S, pp.X, pp.y, pp.N, SB, 0, pp.out, st));
+static int loglik_attn_t(mile_sampler *s, PredParams pp, int S, hipStream_t st) {   // the three attention models
+  HIP_TRY(launch_attn(s, pp.theta, S, pp.X, pp.y, pp.N, attn_ranges(s->n_cu, S, pp.N), 0, pp.out, st));
   return MILE_OK;
 }
 static int loglik_lenetti(mile_sampler *s, PredParams pp, int S, hipStream_t st) {
@@ -2105,8 +2043,7 @@ static LaunchShape shape_narrow(const mile_sampler *s, int S) {
              : std::max(NarrowLayout<3, 2, 4>::BYTES, NarrowLayout<10, 1, 1>::BYTES)};
 }
 static LaunchShape shape_attn(const mile_sampler *s, int) { return {256, (int)attn_lds_bytes(s->ag, attn_weights_in_lds(s->ag))}; }
-static LaunchShape shape_attn_pre(const mile_sampler *s, int) { return {256, (int)attnp_lds_bytes(s->ag)}; }
-static LaunchShape shape_attn_wide(const mile_sampler *s, int) { return {256, (int)attn_wide_lds_bytes(s->ag)}; }
+static LaunchShape shape_attn_streamed(const mile_sampler *s, int) { return {256, (int)attnp_lds_bytes(s->ag)}; }   // _pre and _wide
 static LaunchShape shape_lenetti(const mile_sampler *s, int) { return {256, (int)lenetti_lds_bytes(s->ng, lenetti_T(s->ng))}; }
 static LaunchShape shape_lenet_bf16(const mile_sampler *s, int) { return {256, (int)cm_lds_dw(CM_IN8, s->lg.hp1, s->lg.wp1, 0)}; }
 // the largest of the five launches at three term planes: conv2's kernel gradient, or (large images) conv1's
@@ -2155,13 +2092,13 @@ static constexpr GradKernel kGrad[] = {
     {MILE_GRAD_LENETTI_F32, "k_grad_lenetti", is_lenetti, "LENETTI_F32 is the kernel of MILE_MODEL_LENETTI, and its only one", nullptr,
      lenetti_S, true, false, grad_lenetti, loglik_lenetti, shape_lenetti},
     {MILE_GRAD_ATTN_F32, "k_grad_attn", is_attn, "ATTN_F32 is the kernel of MILE_MODEL_ATTN, and its only one", nullptr,
-     attn_S, true, false, grad_attn, loglik_attn_t<launch_attn>, shape_attn},
+     attn_S, true, false, grad_attn, loglik_attn_t, shape_attn},
     {MILE_GRAD_ATTN_PRE_F32, "k_grad_attn_pre", is_attn_pre,
      "ATTN_PRE_F32 is the kernel of MILE_MODEL_ATTN_PRETRAINED, and its only one", nullptr,
-     attn_S, true, false, grad_attn_pre, loglik_attn_t<launch_attn_pre>, shape_attn_pre},
+     attn_S, true, false, grad_attn, loglik_attn_t, shape_attn_streamed},
     {MILE_GRAD_ATTN_WIDE_F32, "k_grad_attn_wide", is_attn_wide,
      "ATTN_WIDE_F32 is the kernel of MILE_MODEL_ATTN_WIDE, and its only one", nullptr,
-     attn_wide_S, true, false, grad_attn_wide, loglik_attn_t<launch_attn_wide>, shape_attn_wide},
+     attn_wide_S, true, false, grad_attn, loglik_attn_t, shape_attn_streamed},
     {MILE_GRAD_LENET_BF16X3, "k_conv5m_fwd/dx/dw<.., 3> (implicit-GEMM bf16x3 MFMA: six products of three-term splits) + k_mm3 (Dense, the same)",
      lenet_bf16_supported, "LENET_BF16X3 is a kernel of MILE_MODEL_LENET and needs <= 4 image channels", nullptr,
      one_S, true, false, grad_lenet<LENET_CONV_BF16X3>, loglik_lenet<LENET_CONV_BF16X3>, shape_lenet_bf16x3},

@@ -546,7 +546,7 @@ class WideAttentionSpec(AttentionSpec):
 
     @property
     def lds_bytes(self) -> int:
-        """LDS of one k_grad_attn_wide workgroup (attn_wide_lds_bytes in mile_attn_wide.h): the pretrained kernel's."""
+        """LDS of one k_grad_attn_wide workgroup (attnp_lds_bytes in mile_attn_pre.h): the pretrained kernel's."""
         return attn_pre_lds_bytes(self.context_len, self.emb_size, self.n_heads, self.qkv_dim, self.projection_dim)
 
     def row_splits(self, n_chains: int, n_rows: int, n_cu: int = 256) -> int:

@@ -46,9 +46,14 @@ CASES = [
     (200, 128, 64, 8, 64, 16, (64, 64), True, 5, 2),     # widest supported
     (60, 128, 64, 2, 64, 2, (16,), False, 6, 2),         # hd = 32 at T = 128: dK in LDS, two 16-column tiles per key tile
 ]
+# the ceil(hd / 16) instantiations of the shared attention backward that CASES does not reach.  A list of its own: tests/leaf_cases.py
+# builds its sharp problems from CASES, and their ids count its entries
+NHT_CASES = [
+    (30, 16, 16, 1, 48, 2, (8,), True, 5, 2),            # hd = 48: three 16-column dK / dq tiles
+]
 
 
-@pytest.mark.parametrize('V,T,C,H,D,K,proj,bias,N,E', CASES)
+@pytest.mark.parametrize('V,T,C,H,D,K,proj,bias,N,E', CASES + NHT_CASES)
 def test_logpost_grad_matches_restatement(V, T, C, H, D, K, proj, bias, N, E):
     spec = _spec(V, T, C, H, D, K, proj, bias)
     prob = R.synthetic_problem(spec, N, E, seed=3)

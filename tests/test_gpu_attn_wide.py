@@ -53,9 +53,18 @@ CASES = [
     (80, 128, 64, 4, 64, 16, (16,), True, 4, 2),             # T = 128, K = 16
     (1000, 70, 48, 8, 64, 2, (32,), True, 24, 2),            # inside k_grad_attn's envelope, forced onto the wide kernel
 ]
+# the ceil(hd / 16) instantiations of the shared attention backward that CASES does not reach.  A list of its own: tests/leaf_cases.py
+# builds its sharp problems from CASES, and their ids count its entries
+NHT_CASES = [
+    (40, 20, 24, 2, 96, 2, (8,), True, 5, 2),                # hd = 48: three dq tiles
+    (40, 20, 24, 1, 64, 2, (8,), True, 5, 2),                # hd = 64: four
+    (40, 20, 24, 1, 80, 2, (8,), True, 5, 2),                # hd = 80: five
+    (40, 20, 24, 1, 96, 2, (8,), True, 5, 2),                # hd = 96: six
+    (40, 20, 24, 1, 128, 2, (8,), True, 5, 2),               # hd = 128: eight, the most
+]
 
 
-@pytest.mark.parametrize('V,T,C,H,D,K,proj,bias,N,E', CASES)
+@pytest.mark.parametrize('V,T,C,H,D,K,proj,bias,N,E', CASES + NHT_CASES)
 def test_logpost_grad_matches_restatement(V, T, C, H, D, K, proj, bias, N, E):
     spec = wide_spec(V, T, C, H, D, K, proj, bias)
     prob = R.synthetic_problem(spec, N, E, seed=3)
