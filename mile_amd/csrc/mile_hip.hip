@@ -30,6 +30,7 @@
 #include "mile_nuts.h"
 #include "mile_diag.h"
 #include "mile_eval_plan.h"
+#include "mile_layer_plan.h"
 #include "mile_moments.h"
 #include "mile_calib.h"
 #include "mile_lppd.h"
@@ -208,6 +209,18 @@ static bool rocblas_load() {
   g_rb.sgemm_sb = (rb_sgemm_sb_t)dlsym(g_rb.lib, "rocblas_sgemm_strided_batched");
   if (!g_rb.create || !g_rb.destroy || !g_rb.set_stream || !g_rb.sgemm_sb) { g_rb.sgemm_sb = nullptr; return false; }
   return true;
+}
+// what a launcher needs before its first SGEMM: the library, the sampler's handle, the handle on the launcher's stream
+static int rocblas_ready(mile_sampler *s, hipStream_t st) {
+  if (!rocblas_load()) return fail(MILE_ERR_HIP, "librocblas.so could not be loaded");
+  if (!s->blas && g_rb.create(&s->blas) != 0) { s->blas = nullptr; return fail(MILE_ERR_HIP, "rocblas_create_handle failed"); }
+  if (g_rb.set_stream(s->blas, st) != 0) return fail(MILE_ERR_HIP, "rocblas_set_stream failed");
+  return MILE_OK;
+}
+// MILE_GEMM_ROWS (test hook): the rows per chunk of the layer-wise and LeNet paths, 1 .. N, in place of the R their own rule gave
+static size_t gemm_rows_hook(size_t R, size_t N) {
+  if (const char *rv = getenv("MILE_GEMM_ROWS")) R = std::max<size_t>(1, std::min<size_t>((size_t)atoll(rv), N));
+  return R;
 }
 
 // library GEMMs pay off once the hidden layers are wide; below that the single-launch generic kernel wins
@@ -993,6 +1006,16 @@ __global__ void k_fill(float *p, float v, int n) {
   if (i < n) p[i] = v;
 }
 
+// An operand of the layer-wise paths: (pointer, batch stride, leading dimension), in floats
+struct MMIn { const float *p; long long s; int ld; };
+struct MMOut { float *p; long long s; int ld; operator MMIn() const { return {p, s, ld}; } };
+// The row head of the layer-wise evaluations, on the outputs Z [batch][rows][ld] (O per row) of data rows r0 .. of N and samples
+// s0 ..: the per-row log-likelihoods against y into out [.., N], or (y == nullptr: mile_predict) the raw outputs into out [.., N, O]
+static void launch_rowll(MMIn Z, const void *y, int r0, int rows, int O, int task, float *out, long long N, long long s0, int batch, hipStream_t st) {
+  if (y) k_rowll<<<dim3((unsigned)((rows + 255) / 256), batch), 256, 0, st>>>(Z.p, Z.s, Z.ld, y, r0, rows, O, task, out, N, s0);
+  else k_rowll<true><<<dim3((unsigned)std::min<long long>(((long long)rows * O + 255) / 256, 65535), batch), 256, 0, st>>>(Z.p, Z.s, Z.ld, y, r0, rows, O, task, out, N, s0);
+}
+
 // LeNet: forward (+ backward when slab != nullptr) over image chunks; batch = particles (or samples).
 // out_ll != nullptr: evaluation, per-row log-likelihoods out_ll[(s0 + e) * N + r]; otherwise the gradient goes
 // to slab[e * dp + offset] and the log-likelihood sums to llacc[e].
@@ -1011,12 +1034,10 @@ static int lenet_ni_for(size_t per_img, int terms) { return std::max(1, std::min
 static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X, const void *y, int N, float *slab, long long dp,
                      float *llacc, float *out_ll, long long s0, hipStream_t st, int mode = LENET_CONV_F32) {
   const bool mfma = mode != LENET_CONV_F32, x3 = mode == LENET_CONV_BF16X3;
-  if (!rocblas_load()) return fail(MILE_ERR_HIP, "librocblas.so could not be loaded");
+  if (const int rc = rocblas_ready(s, st)) return rc;
   const LeNetGeom &g = s->lg;
   const int d = g.d, act = s->ds.activation, task = s->ds.task;
   const bool grad = slab != nullptr;
-  if (!s->blas && g_rb.create(&s->blas) != 0) { s->blas = nullptr; return fail(MILE_ERR_HIP, "rocblas_create_handle failed"); }
-  if (g_rb.set_stream(s->blas, st) != 0) return fail(MILE_ERR_HIP, "rocblas_set_stream failed");
   const size_t HW = (size_t)g.H * g.W, P1 = (size_t)g.hp1 * g.wp1, HW2 = (size_t)g.h2 * g.w2;
   const size_t n_a1 = 6 * HW, n_p1 = 6 * P1, n_col2 = 150 * HW2, n_a2 = 16 * HW2, n_p2 = g.flat;
   // direct convolution kernels (LDS tiles per image) unless the image is too large for them or the im2col + SGEMM
@@ -1057,7 +1078,7 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
   const size_t shared = direct ? 0 : 25 * (size_t)g.C * HW;
   size_t R = ((size_t)1 << 30) / ((size_t)E * per + shared);
   R = std::max<size_t>(1, std::min<size_t>(R, (size_t)N));
-  if (const char *rv = getenv("MILE_GEMM_ROWS")) R = std::max<size_t>(1, std::min<size_t>((size_t)atoll(rv), (size_t)N));
+  R = gemm_rows_hook(R, (size_t)N);
   const size_t nwg_max = (R + ipw - 1) / ipw;
   const size_t n_part1 = direct && grad ? (size_t)E * nwg_max * (25 * g.C * 6 + 6) : 0;
   const size_t n_part2 = direct && grad ? (size_t)E * nwg_max * (2400 + 16) : 0;
@@ -1152,8 +1173,7 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
       if (fwd(g.k_f3, 84, g.K, f2, Rc * 84, Rc, out)) return fail(MILE_ERR_HIP, "rocblas sgemm (fc3) failed");
       bias_act(out, g.b_f3, g.K, Rc, 0);
       if (!grad) {   // per-row log-likelihoods, or (y == nullptr: mile_predict) the raw outputs [.., N, K]
-        if (y) k_rowll<<<dim3((unsigned)((Rc + 255) / 256), E), 256, 0, st>>>(out, Rc * g.K, g.K, y, r0, (int)Rc, g.K, task, out_ll, N, s0);
-        else k_rowll<true><<<dim3(blocks(Rc * g.K), E), 256, 0, st>>>(out, Rc * g.K, g.K, y, r0, (int)Rc, g.K, task, out_ll, N, s0);
+        launch_rowll({out, Rc * g.K, g.K}, y, r0, (int)Rc, g.K, task, out_ll, N, s0, E, st);
         continue;
       }
       k_gemm_head<<<E, 256, 0, st>>>(out, y, r0, (int)Rc, g.K, task, llacc, chunk == 0);
@@ -1222,13 +1242,9 @@ static int run_lenet(mile_sampler *s, const float *theta, int E, const float *X,
 // dW (accumulated in place in the slab), bias column sums, dH GEMM + activation derivative.
 // Row-major products through rocBLAS's column-major interface: C = A B  <=>  C^T = B^T A^T.
 static int launch_grad_gemm(mile_sampler *s, const GradParams &gp, int E, hipStream_t st) {
-  if (!rocblas_load()) return fail(MILE_ERR_HIP, "librocblas.so could not be loaded");
+  if (const int rc = rocblas_ready(s, st)) return rc;
   const DevSpec &ds = s->ds;
   const int L = ds.n_layers, F = ds.in_features, d = ds.d, N = s->N;
-  if (!s->blas) {
-    if (g_rb.create(&s->blas) != 0) { s->blas = nullptr; return fail(MILE_ERR_HIP, "rocblas_create_handle failed"); }
-  }
-  if (g_rb.set_stream(s->blas, st) != 0) return fail(MILE_ERR_HIP, "rocblas_set_stream failed");
   size_t per_row = 2 * (size_t)ds.max_width;
   for (int l = 0; l < L; ++l) per_row += ds.widths[l];
   if (E != s->gemm_E || !s->gemm_ws) {   // (re)size the activation workspace: <= ~4 GiB, whole data set if it fits
@@ -1237,7 +1253,7 @@ static int launch_grad_gemm(mile_sampler *s, const GradParams &gp, int E, hipStr
     R = std::min<size_t>(R, (size_t)N);
     if (R < (size_t)N) R = std::max<size_t>(256, R / 256 * 256);
     R = std::min<size_t>(R, (size_t)N);
-    if (const char *rv = getenv("MILE_GEMM_ROWS")) R = std::max<size_t>(1, std::min<size_t>((size_t)atoll(rv), (size_t)N));   // test hook
+    R = gemm_rows_hook(R, (size_t)N);
     const size_t need = (size_t)E * R * per_row;
     HIP_TRY(grow(s->gemm_ws, s->gemm_ws_floats, need, 4));
     s->gemm_R = (int)R; s->gemm_E = E;
@@ -1356,82 +1372,89 @@ static hipError_t launch_mm3_dw(const MMParams &p, int batch, hipStream_t st) {
                       : launch_mm3_k<MM_A_KM, MM_B_F32_KN, MM_EPI_STORE, TERMS, -1, false, true>(p, batch, st);
 }
 
-// ---- Dense half of LeNet (flat -> 120 -> 84 -> K) on k_mm3, TERMS = 3: the weights as zero-padded bf16 term planes in
-// s->wide_wt [E][layer][term][in][outp], activations [E][Rc][ld] with ld = 120 / 88 / up8(K)
-static void lenet_dense_dims(const LeNetGeom &g, int (&fin)[3], int (&fout)[3], int (&ld)[3], int (&woff)[3], int (&boff)[3], size_t (&pl)[3],
-                             size_t &elems) {
-  fin[0] = g.flat; fin[1] = 120; fin[2] = 84;
-  fout[0] = 120; fout[1] = 84; fout[2] = g.K;
-  woff[0] = g.k_f1; woff[1] = g.k_f2; woff[2] = g.k_f3;
-  boff[0] = g.b_f1; boff[1] = g.b_f2; boff[2] = g.b_f3;
-  elems = 0;
-  for (int l = 0; l < 3; ++l) { ld[l] = (fout[l] + 7) / 8 * 8; pl[l] = elems; elems += (size_t)3 * fin[l] * ld[l]; }
+// ---- the MMParams of the three products of layer l of a LayerPlan (mile_layer_plan.h).  The plan owns the weights' term-plane
+// format; the callers own their activations, each operand an MMIn / MMOut
+struct LayerGemm {                 // what the products of one call share
+  const LayerPlan &pl;
+  const bf16 *Wt;                  // the batch's term planes, from wide_prep_weights
+  const float *theta; int d;       // the batch's parameter rows (the biases) and their stride
+  int act;
+};
+// the kernels of n parameter rows at stride d as zero-padded bf16 term planes Wt [n][layer][term][in][outp]
+template <int TERMS>
+static void wide_prep_weights(const LayerPlan &pl, const float *theta, int d, int n, bf16 *Wt, hipStream_t st) {
+  for (int l = 0; l < pl.L; ++l)
+    k_wide_prep_weights<TERMS><<<dim3((unsigned)std::min<long long>(((long long)pl.plane(l) + 255) / 256, 1024), n), 256, 0, st>>>(
+        theta, d, pl.w_off[l], pl.fin[l], pl.fout[l], pl.wp[l], Wt + pl.wt_off[l], (long long)pl.wt_elems);
 }
+static void mm3_weights(const LayerGemm &g, int l, MMParams &p) {   // B = layer l's term planes, [in][outp] each
+  p.B = g.Wt + g.pl.wt_off[l]; p.sB = (long long)g.pl.wt_elems; p.ldb = g.pl.wp[l]; p.tB = (long long)g.pl.plane(l);
+}
+// forward (launch_mm3_fwd): C [rows][fout] = act(A [rows][fin] W_l + b_l), no activation on the last layer
+static MMParams layer_fwd(const LayerGemm &g, int l, MMIn A, MMOut C, int rows) {
+  MMParams p{};
+  p.A = A.p; p.sA = A.s; p.lda = A.ld; p.K = g.pl.fin[l];
+  mm3_weights(g, l, p);
+  p.C = C.p; p.sC = C.s; p.ldc = C.ld;
+  p.M = rows; p.N = g.pl.fout[l];
+  p.bias = g.theta + g.pl.b_off[l]; p.sBias = g.d;
+  p.act = g.act; p.apply_act = l + 1 < g.pl.L;
+  return p;
+}
+// dW (launch_mm3_dw): dW_l [fin][fout] (+)= A^T dZ over the rows, straight into the slab rows at the kernel's offset (leading
+// dimension: the real width); the bias gradient dZ^T 1 from the B tiles of M tile 0
+static MMParams layer_dw(const LayerGemm &g, int l, MMIn A, MMIn dZ, int rows, float *slab, long long dp, bool accumulate) {
+  MMParams p{};
+  p.A = A.p; p.sA = A.s; p.lda = A.ld;
+  p.B = dZ.p; p.sB = dZ.s; p.ldb = dZ.ld;
+  p.C = slab + g.pl.w_off[l]; p.sC = dp; p.ldc = g.pl.fout[l];
+  p.M = g.pl.fin[l]; p.N = g.pl.fout[l]; p.K = rows;
+  p.accumulate = accumulate;
+  p.colsum = slab + g.pl.b_off[l]; p.sColsum = dp;
+  return p;
+}
+// dH (launch_mm3_dh): C [rows][fin] = (dZ [rows][fout] W_l^T) * act'(Hprev), the forward's planes read as [in][out] rows.  No
+// Hprev (the layer's input is no activation's output): the product alone, for the plain store form
+static MMParams layer_dh(const LayerGemm &g, int l, MMIn dZ, MMIn Hprev, MMOut C, int rows) {
+  MMParams p{};
+  p.A = dZ.p; p.sA = dZ.s; p.lda = dZ.ld; p.K = g.pl.fout[l];
+  mm3_weights(g, l, p);
+  p.C = C.p; p.sC = C.s; p.ldc = C.ld;
+  p.M = rows; p.N = g.pl.fin[l];
+  if (Hprev.p) { p.Hprev = Hprev.p; p.sH = Hprev.s; p.ldh = Hprev.ld; p.act = g.act; }
+  return p;
+}
+
+// ---- Dense half of LeNet (flat -> 120 -> 84 -> K) on k_mm3, TERMS = 3: the weights as term planes in s->wide_wt, activations
+// [E][Rc][ld] with ld = 120 / 88 / up8(K)
 static int lenet_dense_prep(mile_sampler *s, const float *theta, int E, hipStream_t st) {
-  int fin[3], fout[3], ld[3], woff[3], boff[3]; size_t pl[3], elems;
-  lenet_dense_dims(s->lg, fin, fout, ld, woff, boff, pl, elems);
-  const size_t bytes = (size_t)E * elems * 2;
-  HIP_TRY(grow(s->wide_wt, s->wide_wt_bytes, bytes, 1));
-  for (int l = 0; l < 3; ++l) {
-    const long long plane = (long long)fin[l] * ld[l];
-    k_wide_prep_weights<3><<<dim3((unsigned)std::min<long long>((plane + 255) / 256, 1024), E), 256, 0, st>>>(
-        theta, s->lg.d, woff[l], fin[l], fout[l], ld[l], (bf16 *)s->wide_wt + pl[l], (long long)elems);
-  }
+  const LayerPlan pl = layer_plan_lenet(s->lg);
+  HIP_TRY(grow(s->wide_wt, s->wide_wt_bytes, (size_t)E * pl.wt_elems * 2, 1));
+  wide_prep_weights<3>(pl, theta, s->lg.d, E, (bf16 *)s->wide_wt, st);
   HIP_TRY(hipGetLastError());
   return MILE_OK;
 }
 static int lenet_dense_chunk(mile_sampler *s, const float *theta, int E, int Rc, int r0, int chunk, const LeNetDenseBufs &b, const void *y,
                              float *slab, long long dp, float *llacc, float *out_ll, long long Ntot, long long s0, hipStream_t st) {
   const LeNetGeom &g = s->lg;
-  int fin[3], fout[3], ld[3], woff[3], boff[3]; size_t pl[3], elems;
-  lenet_dense_dims(g, fin, fout, ld, woff, boff, pl, elems);
-  const bf16 *Wt = (const bf16 *)s->wide_wt;
-  const int act = s->ds.activation, task = s->ds.task, d = g.d;
-  const float *in[3] = {b.p2, b.f1, b.f2};
-  const int ldin[3] = {g.flat, ld[0], ld[1]};
-  float *H[3] = {b.f1, b.f2, b.out};
-  for (int l = 0; l < 3; ++l) {   // forward: H_l = act(in W_l + b_l), no activation on the head
-    MMParams p{};
-    p.A = in[l]; p.sA = (long long)Rc * ldin[l]; p.lda = ldin[l]; p.K = fin[l];
-    p.B = Wt + pl[l]; p.sB = (long long)elems; p.ldb = ld[l]; p.tB = (long long)fin[l] * ld[l];
-    p.C = H[l]; p.sC = (long long)Rc * ld[l]; p.ldc = ld[l];
-    p.M = Rc; p.N = fout[l];
-    p.bias = theta + boff[l]; p.sBias = d;
-    p.act = act; p.apply_act = l < 2;
-    HIP_TRY(launch_mm3_fwd<3>(p, E, st));
-  }
-  if (!slab) {   // evaluation: per-row log-likelihood, or (y == nullptr: mile_predict) the raw outputs [.., N, K]
-    if (y) k_rowll<<<dim3((unsigned)((Rc + 255) / 256), E), 256, 0, st>>>(b.out, (long long)Rc * ld[2], ld[2], y, r0, Rc, g.K, task, out_ll, Ntot, s0);
-    else k_rowll<true><<<dim3((unsigned)std::min<long long>(((long long)Rc * g.K + 255) / 256, 65535), E), 256, 0, st>>>(b.out, (long long)Rc * ld[2], ld[2], y, r0, Rc, g.K, task, out_ll, Ntot, s0);
+  const LayerPlan pl = layer_plan_lenet(g);
+  const LayerGemm lg{pl, (const bf16 *)s->wide_wt, theta, g.d, s->ds.activation};
+  auto of = [&](float *p, int l) { return MMOut{p, (long long)Rc * pl.wp[l], pl.wp[l]}; };   // layer l's outputs, or their dZ
+  const MMOut H[3] = {of(b.f1, 0), of(b.f2, 1), of(b.out, 2)};
+  const MMOut dz[3] = {of(b.df1, 0), of(b.df2, 1), H[2]};        // the head's d(out) is in place
+  const MMIn in[3] = {{b.p2, (long long)Rc * g.flat, g.flat}, H[0], H[1]};
+  for (int l = 0; l < 3; ++l) HIP_TRY(launch_mm3_fwd<3>(layer_fwd(lg, l, in[l], H[l], Rc), E, st));
+  if (!slab) {   // evaluation
+    launch_rowll(H[2], y, r0, Rc, g.K, s->ds.task, out_ll, Ntot, s0, E, st);
     HIP_TRY(hipGetLastError());
     return MILE_OK;
   }
-  k_wide_head<<<E, 256, 0, st>>>(b.out, (long long)Rc * ld[2], ld[2], y, r0, Rc, g.K, task, llacc, chunk == 0);
-  float *dz[3] = {b.df1, b.df2, b.out};      // dZ of layer l (the head's d(out) is in place)
+  k_wide_head<<<E, 256, 0, st>>>(H[2].p, H[2].s, H[2].ld, y, r0, Rc, g.K, s->ds.task, llacc, chunk == 0);
   for (int l = 2; l >= 0; --l) {
-    {  // dW_l (+)= in^T dZ_l into the slab, bias gradient from the same B tiles
-      MMParams p{};
-      p.A = in[l]; p.sA = (long long)Rc * ldin[l]; p.lda = ldin[l];
-      p.B = dz[l]; p.sB = (long long)Rc * ld[l]; p.ldb = ld[l];
-      p.C = slab + woff[l]; p.sC = dp; p.ldc = fout[l];
-      p.M = fin[l]; p.N = fout[l]; p.K = Rc;
-      p.accumulate = chunk != 0;
-      p.colsum = slab + boff[l]; p.sColsum = dp;
-      HIP_TRY(launch_mm3_dw<3>(p, E, st));
-    }
-    MMParams p{};   // d(in) = dZ_l W_l^T, times act'(in) for the Dense inputs; the pooled conv output takes it as is
-    p.A = dz[l]; p.sA = (long long)Rc * ld[l]; p.lda = ld[l]; p.K = fout[l];
-    p.B = Wt + pl[l]; p.sB = (long long)elems; p.ldb = ld[l]; p.tB = (long long)fin[l] * ld[l];
-    p.M = Rc; p.N = fin[l];
-    if (l > 0) {
-      p.C = dz[l - 1]; p.sC = (long long)Rc * ldin[l]; p.ldc = ldin[l];
-      p.Hprev = in[l]; p.sH = (long long)Rc * ldin[l]; p.ldh = ldin[l];
-      p.act = act;
-      HIP_TRY(launch_mm3_dh<3>(p, E, st));
-    } else {
-      p.C = b.dp2; p.sC = (long long)Rc * g.flat; p.ldc = g.flat;
-      HIP_TRY((launch_mm3_k<MM_A_MK, MM_B_T3_NK, MM_EPI_STORE, 3, -1, false, false>(p, E, st)));
-    }
+    HIP_TRY(launch_mm3_dw<3>(layer_dw(lg, l, in[l], dz[l], Rc, slab, dp, chunk != 0), E, st));
+    if (l > 0) HIP_TRY(launch_mm3_dh<3>(layer_dh(lg, l, dz[l], in[l], dz[l - 1], Rc), E, st));
+    else   // the pooled conv output [E][Rc][flat] takes d(in) as it is
+      HIP_TRY((launch_mm3_k<MM_A_MK, MM_B_T3_NK, MM_EPI_STORE, 3, -1, false, false>(layer_dh(lg, 0, dz[0], {}, {b.dp2, in[0].s, in[0].ld}, Rc), E, st)));
   }
   HIP_TRY(hipGetLastError());
   return MILE_OK;
@@ -1441,44 +1464,31 @@ template <int TERMS>
 static int launch_grad_wide(mile_sampler *s, const GradParams &gp, int E, hipStream_t st) {
   const DevSpec &ds = s->ds;
   const int L = ds.n_layers, d = ds.d, N = gp.N, Fp = s->Fp;   // gp.N < s->N under a row window (workspace sized for the whole set)
-  auto up8 = [](int v) { return (v + 7) / 8 * 8; };
-  int wp[MILE_MAX_LAYERS], fin[MILE_MAX_LAYERS], finp[MILE_MAX_LAYERS];
-  size_t per_row = 0, wt_elems = 0, wt_off[MILE_MAX_LAYERS];
-  int maxwp = 0;
-  for (int l = 0; l < L; ++l) {
-    wp[l] = up8(ds.widths[l]);
-    fin[l] = l == 0 ? ds.in_features : ds.widths[l - 1];
-    finp[l] = l == 0 ? Fp : wp[l - 1];
-    per_row += wp[l];
-    maxwp = std::max(maxwp, wp[l]);
-    wt_off[l] = wt_elems;
-    wt_elems += (size_t)TERMS * fin[l] * wp[l];
-  }
-  per_row += 2 * (size_t)maxwp;
+  const LayerPlan pl = layer_plan_fcn(ds, Fp, TERMS);
   if (E != s->wide_E || !s->wide_ws) {   // activation workspace: MILE_WIDE_WS_GB (default 16 GiB of the 288), whole data set if it fits
     double gb = 16.0;
     if (const char *ev = getenv("MILE_WIDE_WS_GB")) gb = std::max(0.001, atof(ev));
     const size_t budget = (size_t)(gb * (double)(1ull << 30) / 4.0);
     const size_t Nall = (size_t)s->N;   // sized for the whole data set, also when the first call comes under a row window
-    size_t R = budget / ((size_t)E * per_row);
+    size_t R = budget / ((size_t)E * pl.per_row());
     R = std::min<size_t>(std::max<size_t>(R, 128), Nall);
     if (R < Nall) R = std::max<size_t>(128, R / 128 * 128);
-    if (const char *rv = getenv("MILE_GEMM_ROWS")) R = std::max<size_t>(1, std::min<size_t>((size_t)atoll(rv), Nall));   // test hook
-    const size_t need = (size_t)E * R * per_row;
+    R = gemm_rows_hook(R, Nall);
+    const size_t need = (size_t)E * R * pl.per_row();
     HIP_TRY(grow(s->wide_ws, s->wide_ws_floats, need, 4));
     HIP_TRY(hipMemsetAsync(s->wide_ws, 0, s->wide_ws_floats * 4, st));   // padding columns are read as operands: zero, once per layout
     s->wide_R = (int)R; s->wide_E = E;
   }
-  const size_t wt_bytes = (size_t)E * wt_elems * 2;
-  HIP_TRY(grow(s->wide_wt, s->wide_wt_bytes, wt_bytes, 1));
+  HIP_TRY(grow(s->wide_wt, s->wide_wt_bytes, (size_t)E * pl.wt_elems * 2, 1));
   const int R = s->wide_R;
   float *H[MILE_MAX_LAYERS], *tmp[2];
   {
     float *q = s->wide_ws;
-    for (int l = 0; l < L; ++l) { H[l] = q; q += (size_t)E * R * wp[l]; }
-    tmp[0] = q; q += (size_t)E * R * maxwp;
+    for (int l = 0; l < L; ++l) { H[l] = q; q += (size_t)E * R * pl.wp[l]; }
+    tmp[0] = q; q += (size_t)E * R * pl.maxwp;
     tmp[1] = q;
   }
+  auto of = [&](float *p, int l) { return MMOut{p, (long long)R * pl.wp[l], pl.wp[l]}; };   // layer l's outputs, or their dZ: [E][R][wp]
   // The two dZ buffers are shared by layers of different padded widths: a layer's padding columns (real width .. wp) are not
   // written by the dH epilogue and would otherwise show what an earlier use with another leading dimension -- possibly an
   // earlier CALL with a diverged, non-finite theta -- left there; k_mm3 reads operands in 4- / 8-element granules, and
@@ -1486,16 +1496,11 @@ static int launch_grad_wide(mile_sampler *s, const GradParams &gp, int E, hipStr
   // widths -- B4 -- keep one layout per buffer, whose padding stays zero from the workspace's own memset).
   {
     bool mixed = false;                                    // dZ of layers 0 .. L-2 lives in tmp with leading dimension wp[l]
-    for (int l = 1; l + 1 < L; ++l) mixed = mixed || wp[l] != wp[0];
-    if (mixed) HIP_TRY(hipMemsetAsync(tmp[0], 0, (size_t)E * R * maxwp * 2 * 4, st));
+    for (int l = 1; l + 1 < L; ++l) mixed = mixed || pl.wp[l] != pl.wp[0];
+    if (mixed) HIP_TRY(hipMemsetAsync(tmp[0], 0, (size_t)E * R * pl.maxwp * 2 * 4, st));
   }
-  bf16 *Wt = (bf16 *)s->wide_wt;
-  // ---- this gradient's weights as zero-padded bf16 term planes [E][layer][term][in][outp]
-  for (int l = 0; l < L; ++l) {
-    const long long plane = (long long)fin[l] * wp[l];
-    k_wide_prep_weights<TERMS><<<dim3((unsigned)std::min<long long>((plane + 255) / 256, 1024), E), 256, 0, st>>>(
-        gp.theta, d, ds.w_off[l], fin[l], ds.widths[l], wp[l], Wt + wt_off[l], (long long)wt_elems);
-  }
+  const LayerGemm g{pl, (const bf16 *)s->wide_wt, gp.theta, d, ds.activation};
+  wide_prep_weights<TERMS>(pl, gp.theta, d, E, (bf16 *)s->wide_wt, st);   // this gradient's weights
   float *slab = gp.slabs;        // S = 1: [E][dp]
   const long long dp = gp.dp;
   // The last layer (K <= 8 outputs on a hidden width <= 256) as one pass over the last hidden activations -- forward, head, dH and
@@ -1509,26 +1514,16 @@ static int launch_grad_wide(mile_sampler *s, const GradParams &gp, int E, hipStr
   }
   for (int r0 = 0, chunk = 0; r0 < N; r0 += R, ++chunk) {
     const int Rc = std::min(R, N - r0);
+    auto in = [&](int l) { return l ? MMIn(of(H[l - 1], l - 1)) : MMIn{gp.Xp + (size_t)r0 * Fp, 0, Fp}; };   // X zero-padded to Fp columns, one copy for the batch
     // ---- forward
-    for (int l = 0; l < L - (headblock ? 1 : 0); ++l) {
-      MMParams p{};
-      if (l == 0) { p.A = gp.Xp + (size_t)r0 * Fp; p.sA = 0; p.lda = Fp; }   // X zero-padded to Fp columns
-      else { p.A = H[l - 1]; p.sA = (long long)R * wp[l - 1]; p.lda = wp[l - 1]; }
-      p.K = fin[l];
-      p.B = Wt + wt_off[l]; p.sB = (long long)wt_elems; p.ldb = wp[l]; p.tB = (long long)fin[l] * wp[l];
-      p.C = H[l]; p.sC = (long long)R * wp[l]; p.ldc = wp[l];
-      p.M = Rc; p.N = ds.widths[l];
-      p.bias = gp.theta + ds.b_off[l]; p.sBias = d;
-      p.act = ds.activation; p.apply_act = l + 1 < L;
-      HIP_TRY(launch_mm3_fwd<TERMS>(p, E, st));
-    }
+    for (int l = 0; l < L - (headblock ? 1 : 0); ++l) HIP_TRY(launch_mm3_fwd<TERMS>(layer_fwd(g, l, in(l), of(H[l], l), Rc), E, st));
     // ---- head: log-likelihood and d(out), in place
     float *dz = H[L - 1];
     int pp = 0, ltop = L - 1;
     if (headblock) {
       const int Wl = ds.widths[L - 2], K = ds.widths[L - 1], nblk = (Rc + HB_ROWS - 1) / HB_ROWS;
-#define MILE_HB(K_, WF_) k_wide_headblock<K_, WF_><<<dim3(nblk, E), 256, 0, st>>>(H[L - 2], (long long)R * wp[L - 2], wp[L - 2], Wl, gp.theta, d, \
-      ds.w_off[L - 1], ds.b_off[L - 1], gp.y, r0, Rc, ds.task, ds.activation, tmp[0], (long long)R * wp[L - 2], wp[L - 2], s->wide_hb, HB_ROWS)
+#define MILE_HB(K_, WF_) k_wide_headblock<K_, WF_><<<dim3(nblk, E), 256, 0, st>>>(H[L - 2], (long long)R * pl.wp[L - 2], pl.wp[L - 2], Wl, gp.theta, d, \
+      ds.w_off[L - 1], ds.b_off[L - 1], gp.y, r0, Rc, ds.task, ds.activation, tmp[0], (long long)R * pl.wp[L - 2], pl.wp[L - 2], s->wide_hb, HB_ROWS)
 #define MILE_HB_K(K_) case K_: if (Wl == 256) MILE_HB(K_, true); else MILE_HB(K_, false); break;
       switch (K) { MILE_HB_K(1) MILE_HB_K(2) MILE_HB_K(3) MILE_HB_K(4) MILE_HB_K(5) MILE_HB_K(6) MILE_HB_K(7) MILE_HB_K(8) }
 #undef MILE_HB_K
@@ -1537,30 +1532,13 @@ static int launch_grad_wide(mile_sampler *s, const GradParams &gp, int E, hipStr
                                                           chunk != 0);
       dz = tmp[0]; pp = 1; ltop = L - 2;
     } else {
-      k_wide_head<<<E, 256, 0, st>>>(H[L - 1], (long long)R * wp[L - 1], wp[L - 1], gp.y, r0, Rc, ds.widths[L - 1], ds.task, gp.llpart, chunk == 0);
+      k_wide_head<<<E, 256, 0, st>>>(H[L - 1], (long long)R * pl.wp[L - 1], pl.wp[L - 1], gp.y, r0, Rc, ds.widths[L - 1], ds.task, gp.llpart, chunk == 0);
     }
     // ---- backward
     for (int l = ltop; l >= 0; --l) {
-      {  // dW_l[in][out] (+)= in^T dz, straight into the slab at the kernel's offset
-        MMParams p{};
-        if (l == 0) { p.A = gp.Xp + (size_t)r0 * Fp; p.sA = 0; p.lda = Fp; }
-        else { p.A = H[l - 1]; p.sA = (long long)R * wp[l - 1]; p.lda = wp[l - 1]; }
-        p.B = dz; p.sB = (long long)R * wp[l]; p.ldb = wp[l];
-        p.C = slab + ds.w_off[l]; p.sC = dp; p.ldc = ds.widths[l];
-        p.M = fin[l]; p.N = ds.widths[l]; p.K = Rc;
-        p.accumulate = chunk != 0;
-        p.colsum = slab + ds.b_off[l]; p.sColsum = dp;      // bias gradient dz^T 1 from the B tiles of M tile 0
-        HIP_TRY(launch_mm3_dw<TERMS>(p, E, st));
-      }
+      HIP_TRY(launch_mm3_dw<TERMS>(layer_dw(g, l, in(l), of(dz, l), Rc, slab, dp, chunk != 0), E, st));
       if (l > 0) {   // dZ_{l-1} = (dz W_l^T) * act'(H_{l-1})
-        MMParams p{};
-        p.A = dz; p.sA = (long long)R * wp[l]; p.lda = wp[l]; p.K = ds.widths[l];
-        p.B = Wt + wt_off[l]; p.sB = (long long)wt_elems; p.ldb = wp[l]; p.tB = (long long)fin[l] * wp[l];
-        p.C = tmp[pp]; p.sC = (long long)R * wp[l - 1]; p.ldc = wp[l - 1];
-        p.M = Rc; p.N = fin[l];
-        p.Hprev = H[l - 1]; p.sH = (long long)R * wp[l - 1]; p.ldh = wp[l - 1];
-        p.act = ds.activation;
-        HIP_TRY(launch_mm3_dh<TERMS>(p, E, st));
+        HIP_TRY(launch_mm3_dh<TERMS>(layer_dh(g, l, of(dz, l), in(l), of(tmp[pp], l - 1), Rc), E, st));
         dz = tmp[pp];
         pp ^= 1;
       }
@@ -1866,17 +1844,15 @@ static hipError_t launch_fwd_w64(const PredParams &pp, int S, hipStream_t st) {
 // Evaluation forward for wide nets: the same strided-batched SGEMMs, samples as the batch.  y == nullptr (mile_predict): out is
 // the raw outputs [S, N, O].
 static int launch_fwd_gemm(mile_sampler *s, const float *theta, int S, const float *X, const void *y, int N, float *out, hipStream_t st) {
-  if (!rocblas_load()) return fail(MILE_ERR_HIP, "librocblas.so could not be loaded");
+  if (const int rc = rocblas_ready(s, st)) return rc;
   const DevSpec &ds = s->ds;
   const int L = ds.n_layers, F = ds.in_features, d = ds.d;
-  if (!s->blas && g_rb.create(&s->blas) != 0) { s->blas = nullptr; return fail(MILE_ERR_HIP, "rocblas_create_handle failed"); }
-  if (g_rb.set_stream(s->blas, st) != 0) return fail(MILE_ERR_HIP, "rocblas_set_stream failed");
   // two ping-pong activation buffers of [Sc][Rc][max_width]; <= 1 GiB of floats
   const size_t budget = (size_t)1 << 28;
   const int Sc = std::min(S, 1024);
   size_t Rr = budget / (2 * (size_t)Sc * ds.max_width);
   Rr = std::max<size_t>(1, std::min<size_t>(Rr, (size_t)N));
-  if (const char *rv = getenv("MILE_GEMM_ROWS")) Rr = std::max<size_t>(1, std::min<size_t>((size_t)atoll(rv), (size_t)N));
+  Rr = gemm_rows_hook(Rr, (size_t)N);
   const int R = (int)Rr;
   const size_t need = 2 * (size_t)Sc * R * ds.max_width;
   HIP_TRY(grow(s->gemm_ws, s->gemm_ws_floats, need, 4));
@@ -1902,8 +1878,7 @@ static int launch_fwd_gemm(mile_sampler *s, const float *theta, int S, const flo
         pp ^= 1;
       }
       const int O = ds.widths[L - 1];
-      if (y) k_rowll<<<dim3((Rc + 255) / 256, Sn), 256, 0, st>>>(buf[pp ^ 1], (long long)Rc * O, O, y, r0, Rc, O, ds.task, out, N, s0);
-      else k_rowll<true><<<dim3((unsigned)std::min<long long>(((long long)Rc * O + 255) / 256, 65535), Sn), 256, 0, st>>>(buf[pp ^ 1], (long long)Rc * O, O, y, r0, Rc, O, ds.task, out, N, s0);
+      launch_rowll({buf[pp ^ 1], (long long)Rc * O, O}, y, r0, Rc, O, ds.task, out, N, s0, Sn, st);
     }
   }
   HIP_TRY(hipGetLastError());
@@ -1916,58 +1891,33 @@ static int launch_fwd_wide(mile_sampler *s, const float *theta, int S, const flo
                            hipStream_t st) {
   const DevSpec &ds = s->ds;
   const int L = ds.n_layers, d = ds.d;
-  auto up8 = [](int v) { return (v + 7) / 8 * 8; };
-  int wp[MILE_MAX_LAYERS], fin[MILE_MAX_LAYERS];
-  size_t wt_elems = 0, wt_off[MILE_MAX_LAYERS];
-  int maxwp = 0;
-  for (int l = 0; l < L; ++l) {
-    wp[l] = up8(ds.widths[l]);
-    fin[l] = l == 0 ? ds.in_features : ds.widths[l - 1];
-    maxwp = std::max(maxwp, wp[l]);
-    wt_off[l] = wt_elems;
-    wt_elems += (size_t)3 * fin[l] * wp[l];
-  }
+  const LayerPlan pl = layer_plan_fcn(ds, Fp, 3);
   const int Sc = std::min(S, 512);
-  size_t Rr = ((size_t)1 << 28) / (2 * (size_t)Sc * maxwp);           // two ping-pong buffers, <= 1 GiB of floats
+  size_t Rr = ((size_t)1 << 28) / (2 * (size_t)Sc * pl.maxwp);        // two ping-pong buffers, <= 1 GiB of floats
   Rr = std::max<size_t>(1, std::min<size_t>(Rr, (size_t)N));
-  if (const char *rv = getenv("MILE_GEMM_ROWS")) Rr = std::max<size_t>(1, std::min<size_t>((size_t)atoll(rv), (size_t)N));
+  Rr = gemm_rows_hook(Rr, (size_t)N);
   const int R = (int)Rr;
-  const size_t need = 2 * (size_t)Sc * R * maxwp;
+  const size_t need = 2 * (size_t)Sc * R * pl.maxwp;
   HIP_TRY(grow(s->wide_ws, s->wide_ws_floats, need, 4));
   s->wide_E = 0;   // the gradient path re-derives (and re-zeroes) its layout on its next call
-  const size_t wt_bytes = (size_t)Sc * wt_elems * 2;
-  HIP_TRY(grow(s->wide_wt, s->wide_wt_bytes, wt_bytes, 1));
-  float *buf[2] = {s->wide_ws, s->wide_ws + (size_t)Sc * R * maxwp};
-  bf16 *Wt = (bf16 *)s->wide_wt;
+  HIP_TRY(grow(s->wide_wt, s->wide_wt_bytes, (size_t)Sc * pl.wt_elems * 2, 1));
+  float *buf[2] = {s->wide_ws, s->wide_ws + (size_t)Sc * R * pl.maxwp};
   for (int s0 = 0; s0 < S; s0 += Sc) {
     const int Sn = std::min(Sc, S - s0);
     const float *th = theta + (size_t)s0 * d;
-    for (int l = 0; l < L; ++l) {
-      const long long plane = (long long)fin[l] * wp[l];
-      k_wide_prep_weights<3><<<dim3((unsigned)std::min<long long>((plane + 255) / 256, 1024), Sn), 256, 0, st>>>(
-          th, d, ds.w_off[l], fin[l], ds.widths[l], wp[l], Wt + wt_off[l], (long long)wt_elems);
-    }
+    const LayerGemm g{pl, (const bf16 *)s->wide_wt, th, d, ds.activation};
+    wide_prep_weights<3>(pl, th, d, Sn, (bf16 *)s->wide_wt, st);
     for (int r0 = 0; r0 < N; r0 += R) {
       const int Rc = std::min(R, N - r0);
       // layers of different widths share the two buffers: padding columns an operand read may touch must be zero
       HIP_TRY(hipMemsetAsync(s->wide_ws, 0, need * 4, st));
-      int pp = 0;
+      MMIn in{Xp + (size_t)r0 * Fp, 0, Fp};
       for (int l = 0; l < L; ++l) {
-        MMParams p{};
-        if (l == 0) { p.A = Xp + (size_t)r0 * Fp; p.sA = 0; p.lda = Fp; }
-        else { p.A = buf[pp ^ 1]; p.sA = (long long)R * wp[l - 1]; p.lda = wp[l - 1]; }
-        p.K = fin[l];
-        p.B = Wt + wt_off[l]; p.sB = (long long)wt_elems; p.ldb = wp[l]; p.tB = (long long)fin[l] * wp[l];
-        p.C = buf[pp]; p.sC = (long long)R * wp[l]; p.ldc = wp[l];
-        p.M = Rc; p.N = ds.widths[l];
-        p.bias = th + ds.b_off[l]; p.sBias = d;
-        p.act = ds.activation; p.apply_act = l + 1 < L;
-        HIP_TRY(launch_mm3_fwd<3>(p, Sn, st));
-        pp ^= 1;
+        const MMOut Hl{buf[l & 1], (long long)R * pl.wp[l], pl.wp[l]};
+        HIP_TRY(launch_mm3_fwd<3>(layer_fwd(g, l, in, Hl, Rc), Sn, st));
+        in = Hl;
       }
-      const int O = ds.widths[L - 1];
-      if (y) k_rowll<<<dim3((Rc + 255) / 256, Sn), 256, 0, st>>>(buf[pp ^ 1], (long long)R * wp[L - 1], wp[L - 1], y, r0, Rc, O, ds.task, out, N, s0);
-      else k_rowll<true><<<dim3((unsigned)std::min<long long>(((long long)Rc * O + 255) / 256, 65535), Sn), 256, 0, st>>>(buf[pp ^ 1], (long long)R * wp[L - 1], wp[L - 1], y, r0, Rc, O, ds.task, out, N, s0);
+      launch_rowll(in, y, r0, Rc, ds.widths[L - 1], ds.task, out, N, s0, Sn, st);
     }
   }
   HIP_TRY(hipGetLastError());

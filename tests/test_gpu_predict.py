@@ -71,6 +71,30 @@ def test_fcn_outputs_match_fp64(kernel, F, hs, act, task):
     _assert_close(kernel, out, ref)
 
 
+@pytest.mark.parametrize('K,act,task', [(2, 'relu', 'regr'), (3, 'tanh', 'classification')])
+@pytest.mark.parametrize('kernel,S,Sc', [('mfma_wide_bf16x3', 515, 512), ('gemm_f32', 1027, 1024)])
+def test_fcn_evaluation_walks_row_and_sample_chunks(monkeypatch, kernel, S, Sc, K, act, task):
+    """launch_fwd_wide and launch_fwd_gemm beyond one row chunk and one sample chunk: 37 rows in chunks of 16, 16 and 5, S samples
+    in one chunk of Sc (512 / 1024) and a second of 3.  [9 -> 24 -> 17 -> K] pads to 24, 24, 8 columns, so the two ping-pong
+    buffers change their leading dimension between layers.  The first and last sample of each sample chunk on their own."""
+    monkeypatch.setenv('MILE_GEMM_ROWS', '16')                   # read by the library in every evaluation call
+    ospec = O.ModelSpec(9, (24, 17, K), activation=act, task=task)
+    prob = O.synthetic_problem(ospec, 64, S, seed=3, theta_scale=0.3)
+    test = O.synthetic_problem(ospec, 37, 1, seed=4)
+    eng = _fcn_engine(ospec, prob, kernel)
+    theta, X, y = torch.from_numpy(prob['theta0']), torch.from_numpy(test['X']), torch.from_numpy(test['y'])
+    out = eng.predict(theta, X)
+    pw = eng.pointwise_loglik(theta, X, y)
+    ref = O.mlp_forward(ospec, prob['theta0'].astype(np.float64), test['X'].astype(np.float64))
+    ref_ll = O.pointwise_loglik_raw(ospec, ref, test['y'].astype(np.float64))[0]
+    assert out.shape == (S, 37, K) and pw.shape == (S, 37) and np.isfinite(ref_ll).all()
+    _assert_close(f'{kernel} predict', out, ref)
+    _assert_close(f'{kernel} loglik', pw, ref_ll)
+    for smp in (0, Sc - 1, Sc, S - 1):
+        _assert_close(f'{kernel} predict sample {smp}', out[smp], ref[smp])
+        _assert_close(f'{kernel} loglik sample {smp}', pw[smp], ref_ll[smp])
+
+
 @pytest.mark.parametrize('kernel,bound', [('lenet_f32', 1e-4), ('lenet_bf16', 2e-3)])
 @pytest.mark.parametrize('C,H,W,K,act,task', [(1, 28, 28, 10, 'relu', 'classification'), (2, 13, 17, 2, 'tanh', 'regr')])
 def test_lenet_outputs_match_fp64(kernel, bound, C, H, W, K, act, task):

@@ -57,6 +57,10 @@ def test_constants_are_the_sources():
     assert float(_one(r'double gb = ([\d.]+);\s*if \(const char \*ev = getenv\("MILE_WIDE_WS_GB"\)\)', hip)) == W.WS_GB
     assert 'R = std::min<size_t>(std::max<size_t>(R, 128), Nall);' in hip and 'if (R < Nall) R = std::max<size_t>(128, R / 128 * 128);' in hip
     assert 'if (E != s->wide_E || !s->wide_ws) {' in hip
+    # the padded widths and the floats per row, in the one LayerPlan (tests/test_wide_plan_host.py checks its integers)
+    plan = _src('mile_layer_plan.h')
+    assert _one(r'wp\[l\] = \(fout_ \+ (\d+)\) / (\d+) \* (\d+);', plan) == ('7', '8', '8') and W.up8(17) == 24
+    assert 'size_t per_row() const { return sum_wp + 2 * (size_t)maxwp; }' in plan and 'size_t R = budget / ((size_t)E * pl.per_row());' in hip
     # the parameter layout: bias, then kernel
     assert re.search(r'ds\.b_off\[li\] = \(int\)off; off \+= fout;\s*ds\.w_off\[li\] = \(int\)off; off \+= \(long long\)fin \* fout;', hip)
 

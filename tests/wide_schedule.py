@@ -1,13 +1,14 @@
 """What launch_grad_wide<TERMS> and launch_mm3_k decide, restated, and the cases that put a launch into every cell of that
 schedule (no torch, no GPU; tests/test_wide_schedule_host.py proves the table on the CPU, tests/test_gpu_wide_schedule.py runs it).
 
-The path (mile_amd/csrc/mile_hip.hip, launch_grad_wide, lines 1455-1586; mile_amd/csrc/mile_mm3.h): the rows -- the data set's, or
-a row window's -- are walked in chunks of R rows, R fixed when the activation workspace is laid out (1473-1486).  Per chunk: one
-forward k_mm3 per layer (1528-1539), the head -- k_wide_headblock<K, WFULL> + k_wide_headblock_reduce where the three-term form
-has at least two layers, a last hidden width <= 256 and <= WH_KMAX outputs (1519, 1543-1553), else k_wide_head on the outputs of a
-K-wide forward GEMM (1555) -- and per layer, top down, a dW k_mm3 with the bias column sums (1559-1569) and a dH k_mm3 (1570-1581).
-launch_mm3_k (1333-1352) picks the predicate-free FULL instantiation, 16-byte or scalar C access and the XCD placement; k_mm3
-itself walks K in chunks of 32 (mile_mm3.h:484) of one or two 16-wide k-steps (508).
+The path (mile_amd/csrc/mile_hip.hip: launch_grad_wide and, for each product, layer_fwd / layer_dw / layer_dh over the LayerPlan of
+mile_amd/csrc/mile_layer_plan.h; mile_amd/csrc/mile_mm3.h): the rows -- the data set's, or a row window's -- are walked in chunks
+of R rows, R fixed when launch_grad_wide lays out the activation workspace.  Per chunk: one forward k_mm3 per layer (layer_fwd),
+the head -- k_wide_headblock<K, WFULL> + k_wide_headblock_reduce where the three-term form has at least two layers, a last hidden
+width <= 256 and <= WH_KMAX outputs (`headblock` in launch_grad_wide), else k_wide_head on the outputs of a K-wide forward GEMM --
+and per layer, top down, a dW k_mm3 with the bias column sums (layer_dw) and a dH k_mm3 (layer_dh).  launch_mm3_k picks the
+predicate-free FULL instantiation, 16-byte or scalar C access and the XCD placement; k_mm3 itself walks K in chunks of 32
+(mile_mm3.h:484) of one or two 16-wide k-steps (508).
 
 CELLS are projections of a launch, not the Cartesian product of its properties.  The pruning rule: a property is crossed with
 another one only where one piece of code reads both.  The row predicates (M), the column predicates (N) and the K walk of k_mm3 are
@@ -31,10 +32,10 @@ import numpy as np
 TILE = 128                      # C tile of k_mm3, both ways (launch_mm3_k: p.M % 128, (p.N + 127) / 128)
 KC = 32                         # MILE_MM_KC
 KSTEP = 16                      # k-step of the bf16 MFMA (mile_mm3.h:508)
-HB_ROWS = 512                   # rows per workgroup of k_wide_headblock (mile_hip.hip:1520)
+HB_ROWS = 512                   # rows per workgroup of k_wide_headblock (launch_grad_wide)
 HB_WAVES = 4                    # a wave takes every fourth row of its block (mile_mm3.h:670)
 WH_KMAX = 8
-WS_GB = 16.0                    # MILE_WIDE_WS_GB default (mile_hip.hip:1474)
+WS_GB = 16.0                    # MILE_WIDE_WS_GB default (launch_grad_wide)
 X3, X1, GEMM = 'mfma_wide_bf16x3', 'mfma_wide_bf16', 'gemm_f32'
 
 Case = namedtuple('Case', 'name F hidden act task prior N E chunk_rows window kernel')
@@ -51,7 +52,7 @@ def up8(v):
 # ---- the schedule ------------------------------------------------------------------------------------------------------------------
 
 def offsets(case):
-    """(b_off, w_off, d, dp): bias then kernel per layer (mile_hip.hip:364-365), slab rows padded to 4 floats (1721)."""
+    """(b_off, w_off, d, dp): bias then kernel per layer (layout_fcn), slab rows padded to 4 floats (launch_grad)."""
     off, b_off, w_off, fin = 0, [], [], case.F
     for w in case.hidden:
         b_off.append(off)
@@ -63,8 +64,9 @@ def offsets(case):
 
 
 def layout_rows(hidden, E, N_full, chunk_rows=None):
-    """R of the workspace layout (mile_hip.hip:1472-1481): what 16 GiB hold, at least 128, whole 128s when below the data set,
-    MILE_GEMM_ROWS over it all.  N_full is the data set's row count when the layout is made, whatever the window."""
+    """R of the workspace layout (launch_grad_wide, on LayerPlan::per_row floats per row): what 16 GiB hold, at least 128, whole
+    128s when below the data set, MILE_GEMM_ROWS over it all.  N_full is the data set's row count when the layout is made,
+    whatever the window."""
     wp = [up8(w) for w in hidden]
     per_row = sum(wp) + 2 * max(wp)
     budget = int(WS_GB * float(1 << 30) / 4.0)
@@ -78,10 +80,10 @@ def layout_rows(hidden, E, N_full, chunk_rows=None):
 
 
 def mm3(form, act, M, N, K, ldc, sC, c_off, accumulate, colsum, E, terms, chunk, layer):
-    """launch_mm3_k (mile_hip.hip:1333-1352) on one product; c_off is C's offset in floats from a 256-byte aligned allocation."""
+    """launch_mm3_k (mile_hip.hip) on one product; c_off is C's offset in floats from a 256-byte aligned allocation."""
     nx, ny = (N + TILE - 1) // TILE, (M + TILE - 1) // TILE
-    c_vec = ldc % 4 == 0 and sC % 4 == 0 and (4 * c_off) % 16 == 0                         # 1346
-    xcd = 2 if (colsum and E % 8 == 0) else (1 if (not colsum and nx > 1 and ny >= 8) else 0)   # 1348-1349
+    c_vec = ldc % 4 == 0 and sC % 4 == 0 and (4 * c_off) % 16 == 0                         # q.c_vec
+    xcd = 2 if (colsum and E % 8 == 0) else (1 if (not colsum and nx > 1 and ny >= 8) else 0)   # q.xcd_remap
     nk = (K + KC - 1) // KC                                                               # mile_mm3.h:484
     last = K - KC * (nk - 1)
     return dict(kind='mm3', form=form, act=act, M=M, N=N, K=K, FULL=M % TILE == 0 and N % TILE == 0, ldc=ldc, sC=sC, c_off=c_off,
@@ -93,11 +95,11 @@ def mm3(form, act, M, N, K, ldc, sC, c_off, accumulate, colsum, E, terms, chunk,
 
 def headblock_of(case, terms):
     hs = case.hidden
-    return terms == 3 and len(hs) >= 2 and hs[-2] <= 256 and hs[-1] <= WH_KMAX             # mile_hip.hip:1519
+    return terms == 3 and len(hs) >= 2 and hs[-2] <= 256 and hs[-1] <= WH_KMAX             # launch_grad_wide: headblock
 
 
 def fallback_reason(case, terms):
-    """The first condition of line 1519 that fails."""
+    """The first condition of launch_grad_wide's `headblock` that fails."""
     hs = case.hidden
     if terms != 3:
         return 'terms == 1'
@@ -110,7 +112,7 @@ def fallback_reason(case, terms):
 
 
 def chunks_of(rows, R):
-    return [min(R, rows - r0) for r0 in range(0, rows, R)]                                 # 1525-1526
+    return [min(R, rows - r0) for r0 in range(0, rows, R)]                                 # launch_grad_wide: the chunk walk
 
 
 def launches(case, R=None):
@@ -121,22 +123,22 @@ def launches(case, R=None):
     assert case.kernel in (X3, X1)
     if R is None:
         R = layout_rows(hs, E, case.N, case.chunk_rows)
-    rows = case.window[1] if case.window else case.N                                       # gp.N under a window (1458, 1730)
+    rows = case.window[1] if case.window else case.N                                       # gp.N under a window (launch_grad_wide, launch_grad)
     wp = [up8(w) for w in hs]
     fin = [case.F] + list(hs[:-1])
     maxwp = max(wp)
     b_off, w_off, d, dp = offsets(case)
-    H = [E * R * sum(wp[:l]) for l in range(L)]                                            # 1492-1495
+    H = [E * R * sum(wp[:l]) for l in range(L)]                                            # launch_grad_wide: H, tmp
     tmp = [E * R * sum(wp), E * R * sum(wp) + E * R * maxwp]
     hb = headblock_of(case, terms)
     act = case.act
     out = []
     for chunk, Rc in enumerate(chunks_of(rows, R)):
-        for l in range(L - (1 if hb else 0)):                                              # 1528-1539
+        for l in range(L - (1 if hb else 0)):                                              # layer_fwd
             last = l + 1 == L
             out.append(mm3('fwd-noact' if last else 'fwd', 'none' if last else act, Rc, hs[l], fin[l], wp[l], R * wp[l], H[l],
                            False, False, E, terms, chunk, l))
-        if hb:                                                                             # 1543-1553
+        if hb:                                                                             # MILE_HB, k_wide_headblock_reduce
             nblk = (Rc + HB_ROWS - 1) // HB_ROWS
             out.append(dict(kind='headblock', K=hs[-1], WFULL=hs[-2] == 256, nblk=nblk, last_rows=Rc - HB_ROWS * (nblk - 1),
                             grid=(nblk, E), accumulate=chunk != 0, chunk=chunk, rows=Rc))
@@ -146,7 +148,7 @@ def launches(case, R=None):
             out.append(dict(kind='head', reason=fallback_reason(case, terms), task=case.task, first_chunk=chunk == 0, chunk=chunk,
                             rows=Rc))
             pp, ltop = 0, L - 1
-        for l in range(ltop, -1, -1):                                                      # 1558-1582
+        for l in range(ltop, -1, -1):                                                      # layer_dw, layer_dh
             out.append(mm3('dw', 'none', fin[l], hs[l], Rc, hs[l], dp, w_off[l], chunk != 0, True, E, terms, chunk, l))
             if l > 0:
                 out.append(mm3('dh', act, Rc, fin[l], hs[l], wp[l - 1], R * wp[l - 1], tmp[pp], False, False, E, terms, chunk, l))
@@ -155,7 +157,7 @@ def launches(case, R=None):
 
 
 def mixed(case):
-    """The per-call memset of the two dZ buffers (mile_hip.hip:1503-1505)."""
+    """The per-call memset of the two dZ buffers (launch_grad_wide: `mixed`)."""
     wp = [up8(w) for w in case.hidden]
     return any(wp[l] != wp[0] for l in range(1, len(wp) - 1))
 
