@@ -71,6 +71,9 @@ struct W64FuseArg {
 };
 
 #define W64_RS 68  // row stride (floats) of every padded LDS image
+// MILE_LAB_W64_EDGES stamps: 0 kernel entry, 1 behind the staging barrier, 2 last row block done, 3.. one behind each step of the
+// reduction (see the W64_EDGE marks), W64_NEDGE - 1 = every store of the wave acknowledged
+#define W64_NEDGE 12
 #ifndef W64_OVERLAP
 #define W64_OVERLAP 1   // SPLIT main loop: form the next backward layer's dZ (mask + split) inside the dW MFMA groups
 #endif
@@ -268,20 +271,34 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
   const int j = lane & 31, h = lane >> 5;
   const int e = blockIdx.y, s = blockIdx.x;
   const int d = sp.d, F = sp.in_features;
+#ifdef MILE_LAB_W64_EDGES   // dev (tools/r10/lab): s_memtime at the launch's edges, wave 0 of workgroups (0..1, 0), into p.dbg_buf[16 + 16 s + k]
+  unsigned long long w64_edge[W64_NEDGE] = {};
+#define W64_EDGE(k) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w64_edge[k])::"memory");
+#define W64_EDGE_RT(v) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v)::"memory");   // 100 MHz: gives the stamps' clock
+  unsigned long long w64_rt0, w64_rt1;
+  W64_EDGE_RT(w64_rt0)
+  W64_EDGE(0)
+#else
+#define W64_EDGE(k)
+#endif
   const float *th = p.theta + (size_t)e * d;
   float *slab = p.slabs + ((size_t)e * p.S + s) * p.dp;
-  // slab / llpart stores: plain, or sc1 (write-through) when the update runs as this launch's epilogue
+  // The 128-bit slab stores (the dW tiles: 32 KB of a workgroup's 35) are write-through (sc1): a workgroup's lines leave the
+  // L2 while the others still compute instead of waiting dirty for the end of the kernel -- 1.2 us per launch on B2
+  // (profiles/r10/02_bench_ab.md).  The fused epilogue's hand-off needs the same form.  The scalar stores of the small leaves
+  // and of llpart stay plain (a scalar sc1 store is one fabric write each), sc1 only under the fused epilogue.
+  // MILE_LAB_W64_STORE (dev, tools/r10/lab): 0 plain stores, 2 non-temporal ones.
   constexpr bool FUSABLE = W64FuseArg<FQ, SPLIT>::FUSABLE;
   const bool fuse = FUSABLE && fz.enabled;
   auto st_quad = [&](int off, const f32x4 v) {
-    if constexpr (FUSABLE) {
-      if (fuse) {
-        const __amdgpu_buffer_rsrc_t slab_rs = __builtin_amdgcn_make_buffer_rsrc(slab, 0, p.dp * 4, 0x00020000);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(upd_u32x4, v), slab_rs, off * 4, 0, 16);   // aux 16 = sc1
-        return;
-      }
-    }
+#if defined(MILE_LAB_W64_STORE) && MILE_LAB_W64_STORE == 0
     *(f32x4 *)(slab + off) = v;
+#elif defined(MILE_LAB_W64_STORE) && MILE_LAB_W64_STORE == 2
+    __builtin_nontemporal_store(v, (f32x4 *)(slab + off));
+#else
+    const __amdgpu_buffer_rsrc_t slab_rs = __builtin_amdgcn_make_buffer_rsrc(slab, 0, p.dp * 4, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(upd_u32x4, v), slab_rs, off * 4, 0, 16);   // aux 16 = sc1
+#endif
   };
   auto st_one = [&](float *q, const float v) {
     if constexpr (FUSABLE) {
@@ -300,24 +317,49 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
 
   // ---- stage this particle's weights in LDS --------------------------------------
   char *BIMG = reinterpret_cast<char *>(WIMG);   // SPLIT: term t of image set s at BIMG + (3 s + t) * W64_TIMG
-  if (!(p.dbg & 2))
-  for (int l = 1; l < NH; ++l) {
+  // F <= 8, SPLIT: the next task's loads are in flight while this one is split -- one round trip to memory in front of the first
+  // row block, not one per task.  (F > 8 keeps the task-by-task loop: its three-layer form spills, and more with a second task
+  // in registers.)
+  constexpr bool PIPE = SPLIT && FQ == 1;
+  // SPLIT thread task (layer l, out o, 8 consecutive in 8 ic ..): 8 coalesced loads (lanes along out), one 16-byte store per term
+  auto load8 = [&](float (&v)[8], const int l, const int t) {
     const float *W = th + sp.w_off[l];
-    if constexpr (SPLIT) {
-      // thread task (out, 8 consecutive in): 8 coalesced loads (lanes along out), one 16-byte store per term
-      for (int t = tid; t < 512; t += 256) {
-        const int o = t & 63, ic = t >> 6;
-        float x[8];
+    const int o = t & 63, ic = t >> 6;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) x[i] = W[(8 * ic + i) * 64 + o];
-        bf16x8 tv[3];
-        split3_vec(x, tv);
+    for (int i = 0; i < 8; ++i) v[i] = W[(8 * ic + i) * 64 + o];
+  };
+  auto split_store8 = [&](const float (&v)[8], const int l, const int t) {
+    const int o = t & 63, ic = t >> 6;
+    bf16x8 tv[3];
+    split3_vec(v, tv);
 #pragma unroll
-        for (int tt = 0; tt < 3; ++tt)
-          *reinterpret_cast<bf16x8 *>(BIMG + (3 * ((l - 1) >> 1) + tt) * W64_TIMG + pim_off(o, 8 * ((l - 1) & 1) + ic)) = tv[tt];
+    for (int tt = 0; tt < 3; ++tt)
+      *reinterpret_cast<bf16x8 *>(BIMG + (3 * ((l - 1) >> 1) + tt) * W64_TIMG + pim_off(o, 8 * ((l - 1) & 1) + ic)) = tv[tt];
+  };
+  if (!(p.dbg & 2)) {
+    if constexpr (PIPE) {
+      constexpr int NT = 2 * (NH - 1);   // task it: layer 1 + it / 2, t = tid + 256 (it & 1)
+      float x[8], xn[8];
+      load8(x, 1, tid);
+      for (int it = 0; it < NT; ++it) {
+        if (it + 1 < NT) load8(xn, 1 + ((it + 1) >> 1), tid + 256 * ((it + 1) & 1));
+        split_store8(x, 1 + (it >> 1), tid + 256 * (it & 1));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[i] = xn[i];
       }
     } else {
-      for (int idx = tid; idx < 4096; idx += 256) WIMG[(l - 1) * 64 * W64_RS + (idx >> 6) * W64_RS + (idx & 63)] = W[idx];
+      for (int l = 1; l < NH; ++l) {
+        if constexpr (SPLIT) {
+          for (int t = tid; t < 512; t += 256) {
+            float x[8];
+            load8(x, l, t);
+            split_store8(x, l, t);
+          }
+        } else {
+          const float *W = th + sp.w_off[l];
+          for (int idx = tid; idx < 4096; idx += 256) WIMG[(l - 1) * 64 * W64_RS + (idx >> 6) * W64_RS + (idx & 63)] = W[idx];
+        }
+      }
     }
   }
   {
@@ -332,6 +374,7 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
     if (tid < 2) BO[tid] = th[sp.b_off[NH] + tid];
   }
   __syncthreads();
+  W64_EDGE(1)
 
   // ---- per-wave accumulators ------------------------------------------------------
   f32x16 dWacc[LY::NW][2][2];   // [hidden->hidden layer][ob][ib]: dW^T[out 32ob+row][in 32ib+col]
@@ -475,7 +518,9 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
   }
 #endif
   // ---- reduce the four waves' accumulators through LDS, write the slab -------------
+  W64_EDGE(2)
   __syncthreads();  // weights and images are dead from here on; LDS is reused
+  W64_EDGE(3)
   float *RED = lds;
   if (p.dbg & 4) return;
   // one round for all hidden->hidden matrices: RED[l][wave][in][68]
@@ -492,7 +537,9 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
           f32x4 v = {D[4 * g], D[4 * g + 1], D[4 * g + 2], D[4 * g + 3]};
           *(f32x4 *)(RED + (l * 4 + wave) * 64 * W64_RS + (32 * ib + j) * W64_RS + 32 * ob + 8 * g + 4 * h) = v;
         }
+  W64_EDGE(4)
   __syncthreads();
+  W64_EDGE(5)
 #pragma unroll
   for (int l = 0; l < NH - 1; ++l) {
     float *out = slab + sp.w_off[l + 1];
@@ -514,7 +561,9 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
       }
     }
   }
+  W64_EDGE(6)
   __syncthreads();
+  W64_EDGE(7)
   // small accumulators: SM[wave][k]
   constexpr int SM_B = 0;                 // biases of hidden layers [NH][64]
   constexpr int SM_W1 = SM_B + NH * 64;   // [FP][64]
@@ -548,7 +597,9 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
     const float v0 = wave_sum(boacc[0]), v1 = wave_sum(boacc[1]), vl = wave_sum(llacc);
     if (lane == 0) { SM[SM_BO] = v0; SM[SM_BO + 1] = v1; SM[SM_LL] = vl; }
   }
+  W64_EDGE(8)
   __syncthreads();
+  W64_EDGE(9)
   for (int k = tid; k < SM_LL + 1; k += 256) {
     const float v = (RED[k] + RED[SM_SZ + k]) + (RED[2 * SM_SZ + k] + RED[3 * SM_SZ + k]);
     if (k < SM_W1) st_one(slab + sp.b_off[k >> 6] + (k & 63), v);
@@ -557,6 +608,18 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
     else if (k < SM_LL) st_one(slab + sp.b_off[NH] + (k - SM_BO), v);
     else st_one(p.llpart + (size_t)e * p.S + s, v);
   }
+#ifdef MILE_LAB_W64_EDGES
+  W64_EDGE(10)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  W64_EDGE(W64_NEDGE - 1)
+  W64_EDGE_RT(w64_rt1)
+  if (blockIdx.x < 2 && blockIdx.y == 0 && tid == 0 && p.dbg_buf) {
+#pragma unroll
+    for (int k = 1; k < W64_NEDGE; ++k) p.dbg_buf[16 + 16 * blockIdx.x + k] += (long long)(w64_edge[k] - w64_edge[0]);   // summed over launches
+    p.dbg_buf[16 + 16 * blockIdx.x] += 1;
+    p.dbg_buf[16 + 16 * blockIdx.x + W64_NEDGE] += (long long)(w64_rt1 - w64_rt0);
+  }
+#endif
 
   // ---- fused integrator epilogue: the particle's last-arriving workgroup runs the update -------------------
   if constexpr (FUSABLE) {

@@ -69,7 +69,19 @@ struct UpdParams {
   // normals, the same philox_normal4 counters that launch would use, so that it reads them through its explicit-noise path ----
   float *nz_A, *nz_B;            // [E, d] each, or NULL: that noise is not prefilled
   uint32_t nz_stepA, nz_stageA, nz_stepB, nz_stageB;
+#ifdef MILE_LAB_UPD_EDGES        // dev (tools/r10/lab): s_memtime stamps of thread 0 of particle 0 (and of its noise workgroup)
+  long long *dbg_buf;
+#endif
 };
+// MILE_LAB_UPD_EDGES stamps of upd_fast_body: 0 entry, 1 loads issued, 2 loads landed, 3 sums formed, 4 wave sums in LDS, 5 behind
+// the barrier, 6 scalar chain done, 7 behind the broadcast barrier, 8 apply stores issued, 9 stores acknowledged
+#ifdef MILE_LAB_UPD_EDGES
+#define UPD_EDGE(k) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(upd_edge[k])::"memory");
+#define UPD_EDGE_WAIT asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#else
+#define UPD_EDGE(k)
+#define UPD_EDGE_WAIT
+#endif
 
 // B / O chain on the coefficients of {u, e, zA, zB}; norms and projections come from the
 // Gram matrix M.  fp32 with expm1f/log1pf: the inputs (dot products) are fp32 sums anyway
@@ -543,6 +555,24 @@ __device__ __forceinline__ float ld1_shared(const float *q) {
   else return *q;
 }
 
+// Which of the UPD_NSUM sums the scalar chain of launch kind CF reads (CF < 0, the run-time-flag form: all of them).  Without
+// O(zA) / O(zB) the noise vector is identically zero and its Gram entries with it; the log-prior sum belongs to a launch that
+// forms g from the slabs, the non-finite count to the tuner.  The mid-step kind needs {0, 1, 2, 10}.
+template <int CF>
+__host__ __device__ constexpr bool upd_needs(int k) {
+  if (CF < 0) return true;
+  const bool a = (CF & UPD_OA) != 0, b = (CF & UPD_OB) != 0;
+  return k < 3 ? true : k < 6 ? a : k < 9 ? b : k == 9 ? (a && b) : k == 10 ? (CF & UPD_FROM_SLABS) != 0 : (CF & UPD_TUNE) != 0;
+}
+// One element's contribution to the ten dot products of {u, g~, zA, zB}
+template <int CF>
+__device__ __forceinline__ void upd_add_sums(float (&sm)[UPD_NSUM], float ui, float gs, float a, float b) {
+  sm[0] = fmaf(ui, ui, sm[0]); sm[1] = fmaf(ui, gs, sm[1]); sm[2] = fmaf(gs, gs, sm[2]);
+  if constexpr (upd_needs<CF>(3)) { sm[3] = fmaf(ui, a, sm[3]); sm[4] = fmaf(gs, a, sm[4]); sm[5] = fmaf(a, a, sm[5]); }
+  if constexpr (upd_needs<CF>(6)) { sm[6] = fmaf(ui, b, sm[6]); sm[7] = fmaf(gs, b, sm[7]); sm[8] = fmaf(b, b, sm[8]); }
+  if constexpr (upd_needs<CF>(9)) sm[9] = fmaf(a, b, sm[9]);
+}
+
 // The body of k_update_fast for particle e, run by `nt` threads (a multiple of 64, nt * NK >= d / 4) with thread index tid;
 // red / bc: LDS scratch of the caller ([nt / 64][UPD_NSUM + 1] and [8] floats).
 // CF >= 0: the launch kind is known at compile time -- the flag word is the constant CF and the prior is Normal -- so every
@@ -562,6 +592,11 @@ __device__ __forceinline__ bool upd_fast_body(const UpdParams &p, const int e, c
                                               float (*red)[UPD_NSUM + 1], float *bc, f32x4 *gl = nullptr) {
   const int d = p.d;
   const int flags = CF >= 0 ? CF : p.flags;
+#ifdef MILE_LAB_UPD_EDGES
+  unsigned long long upd_edge[10] = {}, upd_rt0, upd_rt1;
+  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(upd_rt0)::"memory");   // 100 MHz: gives the stamps' clock
+#endif
+  UPD_EDGE(0)
   const size_t base = (size_t)e * d;
   const int nqf = d >> 2;            // full quads
   const int ntail = d & 3;           // leftover elements, handled by threads 0..ntail-1
@@ -633,6 +668,9 @@ __device__ __forceinline__ bool upd_fast_body(const UpdParams &p, const int e, c
     if (explA) ta = p.zA[tc];
     if (explB) tb = p.zB[tc];
   }
+  UPD_EDGE(1)
+  UPD_EDGE_WAIT
+  UPD_EDGE(2)
   // ---- pass 1: noise + sums ------------------------------------------------------------
   float sm[UPD_NSUM];
 #pragma unroll
@@ -665,10 +703,7 @@ __device__ __forceinline__ bool upd_fast_body(const UpdParams &p, const int e, c
       const float gs = (SDC ? gi * csd[kq][m] : gi) * mk;
       const float ui = cu[kq][m] * mk, a = ca[k][m] * mk, b = cb[k][m] * mk;
       ca[k][m] = a; cb[k][m] = b;
-      sm[0] = fmaf(ui, ui, sm[0]); sm[1] = fmaf(ui, gs, sm[1]); sm[2] = fmaf(gs, gs, sm[2]);
-      sm[3] = fmaf(ui, a, sm[3]); sm[4] = fmaf(gs, a, sm[4]); sm[5] = fmaf(a, a, sm[5]);
-      sm[6] = fmaf(ui, b, sm[6]); sm[7] = fmaf(gs, b, sm[7]); sm[8] = fmaf(b, b, sm[8]);
-      sm[9] = fmaf(a, b, sm[9]);
+      upd_add_sums<CF>(sm, ui, gs, a, b);
     }
     if (store_g && q < nqf) {
       f32x4 gst = cg[k];
@@ -705,17 +740,20 @@ __device__ __forceinline__ bool upd_fast_body(const UpdParams &p, const int e, c
     tg *= tsd;
     const float gs = tg * mk, ui = tu * mk;
     ta *= mk; tb *= mk;
-    sm[0] = fmaf(ui, ui, sm[0]); sm[1] = fmaf(ui, gs, sm[1]); sm[2] = fmaf(gs, gs, sm[2]);
-    sm[3] = fmaf(ui, ta, sm[3]); sm[4] = fmaf(gs, ta, sm[4]); sm[5] = fmaf(ta, ta, sm[5]);
-    sm[6] = fmaf(ui, tb, sm[6]); sm[7] = fmaf(gs, tb, sm[7]); sm[8] = fmaf(tb, tb, sm[8]);
-    sm[9] = fmaf(ta, tb, sm[9]);
+    upd_add_sums<CF>(sm, ui, gs, ta, tb);
   }
+  UPD_EDGE(3)
+  // only the sums this launch kind's chain reads are reduced and exchanged
 #pragma unroll
-  for (int k = 0; k < UPD_NSUM; ++k) sm[k] = wave_sum(sm[k]);
+  for (int k = 0; k < UPD_NSUM; ++k)
+    if (upd_needs<CF>(k)) sm[k] = wave_sum(sm[k]);
   if ((tid & 63) == 0)
 #pragma unroll
-    for (int k = 0; k < UPD_NSUM; ++k) red[tid >> 6][k] = sm[k];
+    for (int k = 0; k < UPD_NSUM; ++k)
+      if (upd_needs<CF>(k)) red[tid >> 6][k] = sm[k];
+  UPD_EDGE(4)
   __syncthreads();
+  UPD_EDGE(5)
 
   // ---- scalar chain: wave 0 only, coefficients broadcast through LDS ------------------------
   if (tid < 64) {
@@ -726,7 +764,8 @@ __device__ __forceinline__ bool upd_fast_body(const UpdParams &p, const int e, c
 #pragma unroll
     for (int w = 0; w < (nt >> 6); ++w) t += red[w][kk];
 #pragma unroll
-    for (int k = 0; k < UPD_NSUM; ++k) S[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, t), k));
+    for (int k = 0; k < UPD_NSUM; ++k)   // a sum that was not formed is the +0 it would have been (its column of red is unwritten)
+      S[k] = upd_needs<CF>(k) ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, t), k)) : 0.0f;
   }
   const float eps = eps_in, L = L_in;
   float logp_now;
@@ -807,7 +846,9 @@ __device__ __forceinline__ bool upd_fast_body(const UpdParams &p, const int e, c
     if (merged) { bc[8] = r0; bc[9] = r1; bc[10] = r2; bc[11] = r3; bc[12] = t_simple ? 1.0f : 0.0f; }
   }
   }
+  UPD_EDGE(6)
   __syncthreads();
+  UPD_EDGE(7)
   // ---- pass 2 (from registers) ------------------------------------------------------------
   const bool any_op = flags & (UPD_B1 | UPD_OA | UPD_OB | UPD_B2);
   const bool doA = flags & UPD_A;
@@ -900,6 +941,18 @@ __device__ __forceinline__ bool upd_fast_body(const UpdParams &p, const int e, c
       if (doA) p.x[to] = fmaf(ea * tsd, v, tx);
     }
   }
+#ifdef MILE_LAB_UPD_EDGES
+  UPD_EDGE(8)
+  UPD_EDGE_WAIT
+  UPD_EDGE(9)
+  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(upd_rt1)::"memory");
+  if (e == 0 && tid == 0 && p.dbg_buf) {
+#pragma unroll
+    for (int k = 1; k < 10; ++k) p.dbg_buf[k] += (long long)(upd_edge[k] - upd_edge[0]);   // summed over launches
+    p.dbg_buf[0] += 1;
+    p.dbg_buf[10] += (long long)(upd_rt1 - upd_rt0);
+  }
+#endif
   return merged && !simple;
 }
 
@@ -958,7 +1011,16 @@ static __global__ __launch_bounds__(MAXT) void k_update_fast(const UpdParams p) 
   // idles).  The two halves share nothing, so correctness does not depend on where they are placed.
   if constexpr (CF == UPD_KIND_MID) {
     if ((int)blockIdx.x >= p.E) {
+#ifdef MILE_LAB_UPD_EDGES
+      unsigned long long upd_edge[2];
+      UPD_EDGE(0)
+#endif
       upd_noise_body<NK, AL>(p, blockIdx.x - p.E, threadIdx.x, blockDim.x);
+#ifdef MILE_LAB_UPD_EDGES
+      UPD_EDGE_WAIT
+      UPD_EDGE(1)
+      if ((int)blockIdx.x == p.E && threadIdx.x == 0 && p.dbg_buf) p.dbg_buf[16] += (long long)(upd_edge[1] - upd_edge[0]);
+#endif
       return;
     }
   }
