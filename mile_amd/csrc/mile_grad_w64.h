@@ -564,35 +564,29 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
   W64_EDGE(6)
   __syncthreads();
   W64_EDGE(7)
-  // small accumulators: SM[wave][k]
+  // small accumulators: SM[wave][lane half][k].  Every lane stores its own partial sums (a register store per word, as in the dW
+  // phase: no cross-half shuffle on the way), and the read pass adds the halves first, lo + hi as the fold of the halves would,
+  // then the waves.  SM_SZ = 32 mod 64 words: the two halves of a wave store to disjoint LDS banks.
   constexpr int SM_B = 0;                 // biases of hidden layers [NH][64]
   constexpr int SM_W1 = SM_B + NH * 64;   // [FP][64]
   constexpr int SM_WO = SM_W1 + FP * 64;  // [64][2]
-  constexpr int SM_BO = SM_WO + 128;      // [2]
+  constexpr int SM_BO = SM_WO + 128;      // [2]   (whole-wave sums: half 0's copy only)
   constexpr int SM_LL = SM_BO + 2;
-  constexpr int SM_SZ = SM_LL + 2;
-  float *SM = RED + wave * SM_SZ;
+  constexpr int SM_SZ = ((SM_LL + 2 + 31) / 64) * 64 + 32;
+  static_assert(8 * SM_SZ <= LY::RED, "the small accumulators live in the dead dW reduction area");
+  float *SM = RED + (2 * wave + h) * SM_SZ;
 #pragma unroll
   for (int l = 0; l < NH; ++l)
 #pragma unroll
-    for (int ob = 0; ob < 2; ++ob) {
-      const float v = bacc[l][ob] + __shfl_xor(bacc[l][ob], 32);
-      if (h == 0) SM[SM_B + l * 64 + 32 * ob + j] = v;
-    }
+    for (int ob = 0; ob < 2; ++ob) SM[SM_B + l * 64 + 32 * ob + j] = bacc[l][ob];
 #pragma unroll
   for (int ob = 0; ob < 2; ++ob)
 #pragma unroll
-    for (int c = 0; c < FP; ++c) {
-      const float v = w1acc[ob][c] + __shfl_xor(w1acc[ob][c], 32);
-      if (h == 0) SM[SM_W1 + c * 64 + 32 * ob + j] = v;
-    }
+    for (int c = 0; c < FP; ++c) SM[SM_W1 + c * 64 + 32 * ob + j] = w1acc[ob][c];
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const float v = woacc[kb][c] + __shfl_xor(woacc[kb][c], 32);
-      if (h == 0) SM[SM_WO + (32 * kb + j) * 2 + c] = v;
-    }
+    for (int c = 0; c < 2; ++c) SM[SM_WO + (32 * kb + j) * 2 + c] = woacc[kb][c];
   {
     const float v0 = wave_sum(boacc[0]), v1 = wave_sum(boacc[1]), vl = wave_sum(llacc);
     if (lane == 0) { SM[SM_BO] = v0; SM[SM_BO + 1] = v1; SM[SM_LL] = vl; }
@@ -600,8 +594,11 @@ __global__ __launch_bounds__(256, 1) void k_grad_w64(const GradParams p, const t
   W64_EDGE(8)
   __syncthreads();
   W64_EDGE(9)
+  // (one loop with the leaf branch chain: walking the leaf ranges one after the other made <3, 1, true> spill in the row-block loop)
   for (int k = tid; k < SM_LL + 1; k += 256) {
-    const float v = (RED[k] + RED[SM_SZ + k]) + (RED[2 * SM_SZ + k] + RED[3 * SM_SZ + k]);
+    const float *R = RED + k;
+    const float v = k < SM_BO ? ((R[0] + R[SM_SZ]) + (R[2 * SM_SZ] + R[3 * SM_SZ])) + ((R[4 * SM_SZ] + R[5 * SM_SZ]) + (R[6 * SM_SZ] + R[7 * SM_SZ]))
+                              : (R[0] + R[2 * SM_SZ]) + (R[4 * SM_SZ] + R[6 * SM_SZ]);
     if (k < SM_W1) st_one(slab + sp.b_off[k >> 6] + (k & 63), v);
     else if (k < SM_WO) { if ((k - SM_W1) < F * 64) st_one(slab + sp.w_off[0] + (k - SM_W1), v); }
     else if (k < SM_BO) st_one(slab + sp.w_off[NH] + (k - SM_WO), v);
