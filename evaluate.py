@@ -3,7 +3,7 @@
 mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
 src/inference/metrics.py:247-312):
 
-    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo] [--stacking]
+    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--function-diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo] [--stacking]
 
 Reloads config.yaml and the samples/<chain>/sample_<n>.npz files, rebuilds the data split with the same
 seed, evaluates all C x S samples on the split in one device pass and writes metrics.json next to them.
@@ -101,6 +101,23 @@ def diagnostic_metrics(samples, spec, n_splits, device):
         out[f'diag_{key}_layer_mean'] = {name: float(np.mean(arr[key][:, off:off + int(np.prod(shape))]))
                                          for name, off, shape in spec.leaves()}
     return out, arr
+
+
+def function_diagnostic_metrics(eng, samples, x, y, task, n_splits):
+    """--function-diagnostics: ESS, split R-hat and within / between chain variance of what the finite chains PREDICT on the
+    split's rows (mile_amd.metrics.function_diagnostics: mile_function_diagnostics on the device).  samples [C, S, d] (host).
+    Returns the fdiag_* keys of metrics.json and the arrays of function_diagnostics.npz."""
+    from mile_amd import metrics as M
+    fin = np.isfinite(samples).all(axis=(1, 2))
+    ok = np.ascontiguousarray(samples[fin])
+    if ok.shape[0] == 0:
+        raise SystemExit('--function-diagnostics: no chain with finite samples')
+    res = M.function_diagnostics(eng, torch.from_numpy(ok), torch.from_numpy(x), torch.from_numpy(y), n_splits=n_splits)
+    out = {'fdiag_n_splits': int(n_splits), 'fdiag_chain_ids': [int(c) for c in np.nonzero(fin)[0]]}
+    out.update(M.function_diagnostics_summary(res, int(x.shape[0]), int(res['Q']), task))
+    arrays = {k: res[k].detach().cpu().numpy() for k in ('wcv', 'bcv', 'rhat', 'ess', 'crhat', 'loglik_sum', 'chain_summary')}
+    arrays['Q'] = np.int64(res['Q'])
+    return out, arrays
 
 
 def moment_metrics(moments, dropped, y, task):
@@ -280,6 +297,16 @@ def build_parser():
                     help='per-parameter chain diagnostics of ALL parameters (ESS, split R-hat with N_SPLITS splits, default 2, '
                          'within / between chain variance): diag_* keys in metrics.json and the arrays in diagnostics.npz; the HIP '
                          'kernels take 4 <= n_samples <= 4096, other lengths run in plain torch')
+    ap.add_argument('--function-diagnostics', type=int, nargs='?', const=2, default=None, metavar='N_SPLITS',
+                    help='chain diagnostics in FUNCTION space, streamed on the device (mile_function_diagnostics): ESS, split R-hat '
+                         'with N_SPLITS splits (default 2) and within / between chain variance of every prediction on the rows of '
+                         '--split (regression: mu, log sigma and the log-likelihood of each row; classification: the class '
+                         'probabilities and the log-likelihood) and of the summed log-likelihood of each draw, over the finite '
+                         'chains.  Chains in permuted copies of one mode agree here although their parameters do not.  The kernels '
+                         'take 4 <= n_samples <= 4096 with N_SPLITS dividing n_samples into pieces of at least 2 draws; other '
+                         'lengths are refused with the library\'s message (no torch fall-back, unlike --diagnostics).  fdiag_* keys '
+                         'in metrics.json (fdiag_rhat_max, fdiag_ess_min, fdiag_r_eff_mean, per-quantity and per-chain figures) and '
+                         'wcv, bcv, rhat, ess, crhat, loglik_sum, chain_summary, Q in function_diagnostics.npz')
     ap.add_argument('--moments', action='store_true',
                     help='posterior-predictive moments of all draws on the split, reduced on the device (mile_predict_moments): '
                          'moments_* keys in metrics.json and the per-row arrays in moments.npz (regression: mean, epistemic_var, '
@@ -452,6 +479,10 @@ def main():
     out.update(diag)
     if diag_arrays is not None:
         np.savez(exp / 'diagnostics.npz', **diag_arrays)
+    if args.function_diagnostics is not None:
+        keys, arrays = function_diagnostic_metrics(eng, samples, x, np.ascontiguousarray(y), cfg.data.task, args.function_diagnostics)
+        out.update(keys)
+        np.savez(exp / 'function_diagnostics.npz', **arrays)
     if args.moments:
         mom, dropped = eng.predict_moments(torch.from_numpy(samples), torch.from_numpy(x), return_dropped=True)
         keys, arrays = moment_metrics(mom, dropped, np.ascontiguousarray(y), cfg.data.task)

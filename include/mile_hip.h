@@ -669,6 +669,38 @@ int32_t mile_chain_diagnostics(const float *samples, int32_t C, int32_t S, int64
                                int64_t workspace_bytes, void *stream);
 int64_t mile_chain_diagnostics_workspace(int32_t C, int32_t S, int64_t d, uint32_t what);
 
+/* Function-space chain diagnostics: the statistics of mile_chain_diagnostics of what the draws PREDICT, streamed -- the
+ * [C][S][N][O] outputs are never held.  Hidden-unit permutations and other symmetries of the parameters leave these series
+ * untouched, so their R-hat answers whether the chains agree in their predictions, and their ESS how many effective draws
+ * stand behind each.  theta [C*S][d] full layout, draw j of chain c at row c*S + j, as for mile_lppd_stream; X, y as for
+ * mile_pointwise_loglik; y may be null.
+ * Columns: O the width of the last layer, Q = O + (y ? 1 : 0); column m = n*Q + q is quantity q of row n.  Regression: q = 0
+ * mu, q = 1 log sigma, the floats mile_predict writes; q = 2 the row's log-likelihood.  Classification (O <= 64): q = k the fp32
+ * softmax probability expf(z_k - (m + logf(se))) with the maximum m and the sum se of the likelihood head; q = O the row's
+ * log-likelihood.  With y one last column m = N*Q holds L, the draw's log-likelihood summed in fp64 over the rows in row
+ * order (so it does not depend on the tiles) and rounded to fp32 for the statistics.  M = N*Q + (y ? 1 : 0).
+ * Outputs (device, null where not asked for): wcv, bcv, rhat [M]; ess, crhat [C][M], by the bits of `what` exactly as in
+ * mile_chain_diagnostics with d := M, with its NaN and tie rules; columns [M][C][S] fp32, the series themselves; loglik_sum
+ * [C][S] fp64, L before rounding; summary [16] fp64 over the N*Q per-row columns (L's own statistics are at index M - 1 of
+ * the arrays), in this order: max rhat, mean rhat, column of the max, columns with rhat above 1.01, 1.05, 1.1, non-finite
+ * rhat cells skipped; max crhat, its chain, its column, cells skipped; min ess, mean ess, chain and column of the min, cells
+ * skipped (of equal extremes the lower chain, then the lower column; -1 and NaN where no cell is finite); chain_summary
+ * [C][2] fp64: each chain's min ess and max crhat.  summary and chain_summary need ESS, CRHAT and RHAT in `what`.
+ * Rows go in tiles of at most max_rows_per_tile (0: the library's choice), the forward of a tile in passes of at most
+ * max_draws_per_pass draws (0: the library's choice); no output depends on either, bit for bit.
+ * MILE_ERR_INVALID, with nothing launched: a null s, theta or X; C outside [1, 65535], S outside [MILE_DIAG_S_MIN,
+ * MILE_DIAG_S_MAX], N outside [1, 2^30 - 1]; more than 64 head outputs; n_splits as in mile_chain_diagnostics; unknown bits
+ * or MILE_DIAG_POOLED_INPUT in `what`; nothing asked for; a null pointer for a statistic in `what`, a pointer for one that
+ * is not; loglik_sum without y; negative caps; ESS / RHAT with C*S > MILE_DIAG_POOL_MAX ("unsupported": WCV, BCV, CRHAT,
+ * columns and loglik_sum run at any C*S -- rank the columns outside and pass the scores to mile_chain_diagnostics).
+ * mile_function_diagnostics_workspace: the bytes of the workspace kept in the handle for the library's own tile; -1 out of
+ * range.  (Added under ABI 10: two new symbols, no struct or existing entry changed.) */
+int32_t mile_function_diagnostics(mile_sampler *s, const float *theta, int32_t C, int32_t S, const void *X, const void *y, int64_t N,
+                                  int32_t n_splits, uint32_t what, float *wcv, float *bcv, float *ess, float *crhat, float *rhat,
+                                  float *columns, double *loglik_sum, double *summary, double *chain_summary,
+                                  int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream);
+int64_t mile_function_diagnostics_workspace(const mile_sampler *s, int32_t C, int32_t S, int64_t N, int32_t with_y);
+
 /* Partition sampling (sampler.partition_sampling of the reference: src/training/partition_sampling.py:304-315 partition_params,
  * src/training/trainer.py:593-659): only the FIRST and the LAST layer of an FCN are sampled; every other layer keeps, per chain,
  * the values of `frozen`.  Target: log_prior(sampled coordinates only) + log_likelihood(full net on sampled U frozen).

@@ -18,6 +18,11 @@ GRAD_KERNEL_IDS = {'auto': 0, 'generic': 1, 'mfma_w64': 2, 'mfma_w128_bf16': 3, 
                    'lenetti_f32': 11, 'attn_f32': 12, 'attn_pre_f32': 13, 'attn_wide_f32': 14, 'lenet_bf16x3': 15}
 DIAG_BITS = {'wcv': 1, 'bcv': 2, 'ess': 4, 'crhat': 8, 'rhat': 16, 'pooled_input': 32}     # MILE_DIAG_*
 DIAG_S_MIN, DIAG_S_MAX, DIAG_POOL_MAX = 4, 4096, 16384
+# layout of mile_function_diagnostics' summary (the FDIAG_* enum of csrc/mile_fdiag.h)
+FDIAG_SUMMARY = ('rhat_max', 'rhat_mean', 'rhat_column', 'rhat_gt_1_01', 'rhat_gt_1_05', 'rhat_gt_1_1', 'rhat_skipped',
+                 'crhat_max', 'crhat_chain', 'crhat_column', 'crhat_skipped',
+                 'ess_min', 'ess_mean', 'ess_chain', 'ess_column', 'ess_skipped')
+FDIAG_O_MAX = 64
 MODEL_IDS = {'fcn': 0, 'lenet': 1, 'lenetti': 2, 'attn': 3, 'attn_pretrained': 4, 'attn_wide': 5}
 
 
@@ -176,6 +181,10 @@ SIGNATURES = {
     'mile_chain_diagnostics': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'mile_chain_diagnostics_workspace': (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_uint32]),
+    'mile_function_diagnostics': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                              C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'mile_function_diagnostics_workspace': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
     'mile_debug_noise': (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
                                      C.c_void_p, C.c_void_p]),
     'mile_debug_prefill_count': (C.c_int64, [C.c_void_p]),

@@ -27,7 +27,7 @@
 #define DIAG_POOL_NT 1024
 
 struct DiagParams {
-  const float *samples;   // [C][S][d]
+  const float *samples;   // [C][S][d]; null: raw (z with MILE_DIAG_POOLED_INPUT) already holds the chunk, no k_diag_transpose
   int C, S, n_splits;
   long long d;
   long long p0;           // first parameter of this chunk

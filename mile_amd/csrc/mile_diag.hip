@@ -305,7 +305,7 @@ __global__ __launch_bounds__(64) void k_diag_final(DiagParams p) {
 hipError_t mile_launch_diag(const DiagParams &p, hipStream_t st) {
   const bool pooled_in = p.what & MILE_DIAG_POOLED_INPUT, need_z = p.what & (MILE_DIAG_ESS | MILE_DIAG_RHAT);
   const dim3 tg((p.P + DIAG_TILE - 1) / DIAG_TILE, (p.S + DIAG_TILE - 1) / DIAG_TILE, p.C);
-  k_diag_transpose<<<tg, dim3(DIAG_TILE, 8), 0, st>>>(p);
+  if (p.samples) k_diag_transpose<<<tg, dim3(DIAG_TILE, 8), 0, st>>>(p);   // null: the caller has filled the plane itself
   if (need_z && !pooled_in) {
     hipError_t e = mile_set_max_lds<k_diag_pool_rank>((int)diag_pool_lds(DIAG_POOL_MAX));
     if (e != hipSuccess) return e;

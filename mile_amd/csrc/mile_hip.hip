@@ -29,6 +29,7 @@
 #include "mile_update.h"
 #include "mile_nuts.h"
 #include "mile_diag.h"
+#include "mile_fdiag.h"
 #include "mile_eval_plan.h"
 #include "mile_layer_plan.h"
 #include "mile_moments.h"
@@ -2902,6 +2903,112 @@ extern "C" int32_t mile_chain_diagnostics(const float *samples, int32_t C, int32
     p.p0 = p0;
     p.P = (int)std::min<int64_t>(chunk, d - p0);
     HIP_TRY(mile_launch_diag(p, (hipStream_t)stream));
+  }
+  return MILE_OK;
+}
+
+// mile_function_diagnostics: every check before any launch; rows in tiles whose raw block, two [P][C][S] planes and stat block fit
+// the evaluation budget; per tile the forward, k_fdiag_pack, k_fdiag_lp and mile_chain_diagnostics' launches on the tile's columns
+// (mile_fdiag.h).  The plan of one call: the head's width, rows per tile, draws per pass and the byte offset of every block.
+struct FdiagPlan { int O, Q; int64_t D, NQ, M, nt, chunk; size_t plane, z, stat, acc, part, total; };
+static FdiagPlan fdiag_plan(const mile_sampler *s, int C, int S, int64_t N, bool with_y, int64_t max_rows, int64_t max_draws) {
+  FdiagPlan t;
+  t.O = s->spec.widths[s->spec.n_layers - 1]; t.Q = t.O + (with_y ? 1 : 0);
+  t.D = (int64_t)C * S; t.NQ = N * t.Q; t.M = t.NQ + (with_y ? 1 : 0);
+  const int64_t per_row = t.D * t.O * 4 + t.Q * diag_param_bytes(C, S, 0);
+  int64_t cap = FDIAG_P_MAX / t.Q;
+  if (max_rows > 0 && max_rows < cap) cap = max_rows;
+  t.nt = tile_rows(EVAL_PASS_TARGET, per_row, 1, cap, N);
+  t.chunk = pass_draws(EVAL_PASS_TARGET, t.nt * t.O * 4, max_draws, t.D);
+  const size_t plane = r256((size_t)t.nt * t.Q * t.D * 4);
+  t.plane = r256((size_t)t.D * t.nt * t.O * 4);
+  t.z = t.plane + plane;
+  t.stat = t.z + plane;
+  t.acc = t.stat + r256((size_t)t.nt * t.Q * C * DIAG_NSTAT * 8);
+  t.part = t.acc + r256((size_t)t.D * 8);
+  t.total = t.part + r256(fdiag_part_bytes(C, t.NQ));
+  return t;
+}
+static const char *fdiag_bad_shape(int32_t C, int32_t S, int64_t N) {
+  return !diag_shape_ok(C, S, 1) ? "needs 1 <= C <= 65535 and 4 <= S <= 4096" : bad_N(N);
+}
+
+extern "C" int64_t mile_function_diagnostics_workspace(const mile_sampler *s, int32_t C, int32_t S, int64_t N, int32_t with_y) {
+  if (!s || fdiag_bad_shape(C, S, N) || s->spec.widths[s->spec.n_layers - 1] > FDIAG_O_MAX) return -1;
+  return (int64_t)fdiag_plan(s, C, S, N, with_y != 0, 0, 0).total;
+}
+
+extern "C" int32_t mile_function_diagnostics(mile_sampler *s, const float *theta, int32_t C, int32_t S, const void *X, const void *y, int64_t N,
+                                             int32_t n_splits, uint32_t what, float *wcv, float *bcv, float *ess, float *crhat, float *rhat,
+                                             float *columns, double *loglik_sum, double *summary, double *chain_summary,
+                                             int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
+  const uint32_t outs = MILE_DIAG_WCV | MILE_DIAG_BCV | MILE_DIAG_ESS | MILE_DIAG_CRHAT | MILE_DIAG_RHAT;
+  const uint32_t summed = MILE_DIAG_ESS | MILE_DIAG_CRHAT | MILE_DIAG_RHAT;
+  const int rc0 = eval_args("mile_function_diagnostics", s, !theta || !X, fdiag_bad_shape(C, S, N), [&]() -> const char * {
+    if (s->spec.widths[s->spec.n_layers - 1] > FDIAG_O_MAX) return "more than 64 head outputs";
+    if (n_splits < 1 || S % n_splits) return "n_splits must divide S";
+    if (S / n_splits < 2) return "fewer than 2 draws per split";
+    if (what & MILE_DIAG_POOLED_INPUT) return "MILE_DIAG_POOLED_INPUT: the columns are formed here, there is no input that could hold scores";
+    if (what & ~outs) return "bad `what`";
+    if (!what && !columns && !loglik_sum) return "no output asked for";
+    if (((what & MILE_DIAG_WCV) && !wcv) || ((what & MILE_DIAG_BCV) && !bcv) || ((what & MILE_DIAG_ESS) && !ess) ||
+        ((what & MILE_DIAG_CRHAT) && !crhat) || ((what & MILE_DIAG_RHAT) && !rhat))
+      return "null pointer for an output asked for";
+    if ((!(what & MILE_DIAG_WCV) && wcv) || (!(what & MILE_DIAG_BCV) && bcv) || (!(what & MILE_DIAG_ESS) && ess) ||
+        (!(what & MILE_DIAG_CRHAT) && crhat) || (!(what & MILE_DIAG_RHAT) && rhat))
+      return "an output whose statistic is not in `what`";
+    if ((summary || chain_summary) && (what & summed) != summed) return "summary and chain_summary need ESS, CRHAT and RHAT in `what`";
+    if (loglik_sum && !y) return "loglik_sum needs y";
+    if ((what & (MILE_DIAG_ESS | MILE_DIAG_RHAT)) && (int64_t)C * S > DIAG_POOL_MAX)
+      return "unsupported: C * S > 16384 pooled draws (take WCV, BCV, CRHAT and `columns`, and rank those outside)";
+    return bad_caps(max_draws_per_pass, max_rows_per_tile);
+  });
+  if (rc0 != MILE_OK) return rc0;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->device));
+  const FdiagPlan t = fdiag_plan(s, C, S, N, y != nullptr, max_rows_per_tile, max_draws_per_pass);
+  if (reserve_eval_ws(s, t.total) != hipSuccess)
+    return fail(MILE_ERR_NOMEM, "mile_function_diagnostics: workspace allocation failed (lower max_rows_per_tile)");
+  char *ws = (char *)s->eval_ws;
+  FdiagParams f{};
+  f.out = (const float *)ws; f.D = (int)t.D; f.O = t.O; f.Q = t.Q; f.task = s->spec.task;
+  f.raw = (float *)(ws + t.plane); f.acc = (double *)(ws + t.acc);
+  DiagParams p{};
+  p.C = C; p.S = S; p.n_splits = n_splits; p.d = t.M; p.what = what;   // samples stays null: k_fdiag_pack fills the raw plane
+  p.raw = f.raw; p.z = (float *)(ws + t.z); p.stat = (double *)(ws + t.stat);
+  p.wcv = wcv; p.bcv = bcv; p.ess = ess; p.crhat = crhat; p.rhat = rhat;
+  if (y) HIP_TRY(hipMemsetAsync(f.acc, 0, (size_t)t.D * 8, st));
+  auto source = stream_tiles(s, theta, t.D, t.chunk, X, st);             // the raw block [D][nt][O] at the start of the workspace
+  for (int64_t r0 = 0; r0 < N; r0 += t.nt) {
+    const int nt = (int)std::min<int64_t>(t.nt, N - r0);
+    Tile tile;
+    const int rc1 = source(r0, nt, tile);
+    if (rc1 != MILE_OK) return rc1;
+    f.out = tile.at; f.nt = nt; f.y = y ? (const char *)y + (size_t)r0 * 4 : nullptr; f.lcol = nullptr;
+    HIP_TRY(mile_launch_fdiag_pack(f, st));
+    if (y) HIP_TRY(mile_launch_fdiag_lp(f, st));
+    const size_t m0 = (size_t)r0 * t.Q;
+    if (columns) HIP_TRY(hipMemcpyAsync(columns + m0 * t.D, f.raw, (size_t)nt * t.Q * t.D * 4, hipMemcpyDeviceToDevice, st));
+    if (what) {
+      p.p0 = (long long)m0; p.P = nt * t.Q;
+      HIP_TRY(mile_launch_diag(p, st));
+    }
+  }
+  if (y) {                                                              // the L column: one chunk of its own
+    f.nt = 0; f.lcol = f.raw;
+    HIP_TRY(mile_launch_fdiag_lp(f, st));
+    if (columns) HIP_TRY(hipMemcpyAsync(columns + (size_t)t.NQ * t.D, f.raw, (size_t)t.D * 4, hipMemcpyDeviceToDevice, st));
+    if (loglik_sum) HIP_TRY(hipMemcpyAsync(loglik_sum, f.acc, (size_t)t.D * 8, hipMemcpyDeviceToDevice, st));
+    if (what) {
+      p.p0 = t.NQ; p.P = 1;
+      HIP_TRY(mile_launch_diag(p, st));
+    }
+  }
+  if (summary || chain_summary) {
+    FdiagSumParams q{};
+    q.rhat = rhat; q.crhat = crhat; q.ess = ess; q.M = t.M; q.NQ = t.NQ; q.C = C; q.B = fdiag_sum_blocks(C, t.NQ);
+    q.part = (FdiagPart *)(ws + t.part); q.summary = summary; q.chain_summary = chain_summary;
+    HIP_TRY(mile_launch_fdiag_summary(q, st));
   }
   return MILE_OK;
 }

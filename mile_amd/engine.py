@@ -955,6 +955,54 @@ class Engine:
                        self.lib)
         return out
 
+    def function_diagnostics_workspace(self, C_: int, S: int, N: int, with_y: bool = True) -> int:
+        """Bytes of the workspace ``function_diagnostics`` keeps in the handle for C chains of S draws on N rows with the
+        library's own tile (mile_function_diagnostics_workspace); -1 out of range."""
+        return int(self.lib.mile_function_diagnostics_workspace(self._h, int(C_), int(S), int(N), int(bool(with_y))))
+
+    def function_diagnostics(self, samples, x, y=None, n_splits: int = 2, what=('wcv', 'bcv', 'ess', 'crhat', 'rhat'),
+                             return_columns: bool = False, max_draws_per_pass: int = 0, max_rows_per_tile: int = 0) -> dict:
+        """Chain diagnostics in function space (mile_function_diagnostics): ``metrics.chain_diagnostics`` of what samples
+        [C, S, d] predict on x [N, F], without ever holding ``predict``'s tensor.  With O the head's width and Q = O + 1 (Q = O
+        without ``y``), column n * Q + q is quantity q of row n -- regression: mu, log sigma, the row's log-likelihood;
+        classification: the K softmax probabilities, the row's log-likelihood -- and with ``y`` the last column, M - 1 = N * Q,
+        is the draw's summed log-likelihood.  ``what``: the statistics wanted.  Returns fp32 tensors on the device, None for
+        what was not asked: ``wcv``, ``bcv``, ``rhat`` [M]; ``ess``, ``crhat`` [C, M]; ``columns`` [M, C, S] with
+        ``return_columns``; ``loglik_sum`` [C, S] fp64 with ``y``; and, when ess, crhat and rhat are all in ``what``,
+        ``summary`` (a dict keyed by ``_lib.FDIAG_SUMMARY`` over the N * Q per-row columns) and ``chain_summary`` [C, 2] fp64
+        (each chain's min ess and max crhat); ``Q`` and ``M``.  No output depends on ``max_draws_per_pass`` or
+        ``max_rows_per_tile`` (0: the library's choice), bit for bit.  ess / rhat need C * S <= 16384
+        (``metrics.function_diagnostics`` goes on past that)."""
+        samples = _f32(samples, self.device, name='samples')
+        if samples.ndim != 3 or samples.shape[2] != self.d:
+            raise ValueError(f'samples must be [C, S, {self.d}]')
+        (C_, S_), theta, X, y = self._eval_inputs(samples, x, y, name_x='x')
+        names = tuple(what)
+        if any(k not in ('wcv', 'bcv', 'ess', 'crhat', 'rhat') for k in names):
+            raise ValueError(f'what: names among wcv, bcv, ess, crhat, rhat, not {names}')
+        bits = 0
+        for k in names:
+            bits |= _lib.DIAG_BITS[k]
+        N, O = int(X.shape[0]), int(self.spec.hidden_structure[-1])
+        Q = O + (1 if y is not None else 0)
+        M = N * Q + (1 if y is not None else 0)
+        new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=self.device)
+        out = {k: (new(C_, M) if k in ('ess', 'crhat') else new(M)) if k in names else None for k in ('wcv', 'bcv', 'rhat', 'ess', 'crhat')}
+        out['columns'] = new(M, C_, S_) if return_columns else None
+        out['loglik_sum'] = new(C_, S_, dtype=torch.float64) if y is not None else None
+        summed = all(k in names for k in ('ess', 'crhat', 'rhat'))
+        summary = new(len(_lib.FDIAG_SUMMARY), dtype=torch.float64) if summed else None
+        out['chain_summary'] = new(C_, 2, dtype=torch.float64) if summed else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_function_diagnostics(self._h, _ptr(theta), C_, S_, _ptr(X), _ptr(y), N, int(n_splits), bits,
+                                                          _ptr(out['wcv']), _ptr(out['bcv']), _ptr(out['ess']), _ptr(out['crhat']),
+                                                          _ptr(out['rhat']), _ptr(out['columns']), _ptr(out['loglik_sum']),
+                                                          _ptr(summary), _ptr(out['chain_summary']), int(max_draws_per_pass),
+                                                          int(max_rows_per_tile), self._stream()), self.lib)
+        out['summary'] = dict(zip(_lib.FDIAG_SUMMARY, summary.cpu().tolist())) if summed else None
+        out['Q'], out['M'] = Q, M
+        return out
+
     @property
     def supports_device_tuner(self) -> bool:
         return self.dim >= 4

@@ -197,40 +197,53 @@ def _library_diagnostics(x: torch.Tensor, n_splits: int) -> dict:
     bound (C*S > DIAG_POOL_MAX) only the pooled ranking is done here, one batched torch.sort per chunk of columns, and the
     scores go back into the same ESS / R-hat kernels."""
     global LAST_DIAG_PATH
+    from mile_amd import _lib
+    B = _lib.DIAG_BITS
+    C, S, d = x.shape
+    new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=x.device)
+    out = {'ess': new(C, d), 'crhat': new(C, d), 'rhat': new(d), 'wcv': new(d), 'bcv': new(d)}
+    if C * S <= _lib.DIAG_POOL_MAX:
+        _diag_call(x, n_splits, B['wcv'] | B['bcv'] | B['ess'] | B['crhat'] | B['rhat'], **out)
+        LAST_DIAG_PATH = 'library'
+    else:
+        _diag_call(x, n_splits, B['wcv'] | B['bcv'] | B['crhat'], wcv=out['wcv'], bcv=out['bcv'], crhat=out['crhat'])
+        out['ess'], out['rhat'] = _pooled_ess_rhat(x, n_splits)
+        LAST_DIAG_PATH = 'library+torch_sort'
+    return out
+
+
+def _diag_call(src: torch.Tensor, n_splits: int, what: int, **o):
+    """mile_chain_diagnostics on src [C, S, m] contiguous CUDA fp32 with a workspace of the size it asks for; o: the output
+    tensors of the bits in `what`, by name."""
     import ctypes as Ct
     from mile_amd import _lib
     lib = _lib.load_library()
-    B = _lib.DIAG_BITS
-    C, S, d = x.shape
-    dev = x.device
-    new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
-    out = {'ess': new(C, d), 'crhat': new(C, d), 'rhat': new(d), 'wcv': new(d), 'bcv': new(d)}
+    C, S, m = src.shape
     ptr = lambda t: Ct.c_void_p(t.data_ptr()) if t is not None else None
-
-    def call(src, what, **o):
-        dd = src.shape[2]
-        nbytes = lib.mile_chain_diagnostics_workspace(C, S, dd, what)
-        ws = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dev)
-        stream = Ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.mile_chain_diagnostics(ptr(src), C, S, dd, n_splits, what, ptr(o.get('wcv')), ptr(o.get('bcv')),
+    with torch.cuda.device(src.device):
+        ws = torch.empty(max(int(lib.mile_chain_diagnostics_workspace(C, S, m, what)), 8), dtype=torch.uint8, device=src.device)
+        stream = Ct.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+        _lib.check(lib.mile_chain_diagnostics(ptr(src), C, S, m, n_splits, what, ptr(o.get('wcv')), ptr(o.get('bcv')),
                                               ptr(o.get('ess')), ptr(o.get('crhat')), ptr(o.get('rhat')), ptr(ws), ws.numel(),
                                               stream), lib)
 
-    with torch.cuda.device(dev):
-        if C * S <= _lib.DIAG_POOL_MAX:
-            call(x, B['wcv'] | B['bcv'] | B['ess'] | B['crhat'] | B['rhat'], **out)
-            LAST_DIAG_PATH = 'library'
-        else:
-            call(x, B['wcv'] | B['bcv'] | B['crhat'], wcv=out['wcv'], bcv=out['bcv'], crhat=out['crhat'])
-            step = max(1, (1 << 28) // (C * S * 8))                 # columns per sort: the fp64 keys stay under 256 MB
-            for k0 in range(0, d, step):
-                z = _pooled_scores(x[:, :, k0:k0 + step]).to(torch.float32).contiguous()
-                ess, rhat = new(C, z.shape[2]), new(z.shape[2])
-                call(z, B['ess'] | B['rhat'] | B['pooled_input'], ess=ess, rhat=rhat)
-                out['ess'][:, k0:k0 + step] = ess
-                out['rhat'][k0:k0 + step] = rhat
-            LAST_DIAG_PATH = 'library+torch_sort'
-    return out
+
+def _pooled_ess_rhat(x: torch.Tensor, n_splits: int):
+    """x [C, S, m] CUDA fp32 with C * S past the library's pooled bound -> (ess [C, m], rhat [m]): the pooled ranking by one
+    batched torch.sort per chunk of columns, the scores through the library's ESS / R-hat kernels (MILE_DIAG_POOLED_INPUT).
+    The one torch-sort path: the parameters (_library_diagnostics) and the function-space columns both come here."""
+    from mile_amd._lib import DIAG_BITS as B
+    C, S, m = x.shape
+    new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=x.device)
+    ess, rhat = new(C, m), new(m)
+    step = max(1, (1 << 28) // (C * S * 8))                         # columns per sort: the fp64 keys stay under 256 MB
+    for k0 in range(0, m, step):
+        z = _pooled_scores(x[:, :, k0:k0 + step]).to(torch.float32).contiguous()
+        e, r = new(C, z.shape[2]), new(z.shape[2])
+        _diag_call(z, n_splits, B['ess'] | B['rhat'] | B['pooled_input'], ess=e, rhat=r)
+        ess[:, k0:k0 + step] = e
+        rhat[k0:k0 + step] = r
+    return ess, rhat
 
 
 def chain_diagnostics(samples: torch.Tensor, n_splits: int = 2) -> dict:
@@ -264,6 +277,194 @@ def chain_diagnostics(samples: torch.Tensor, n_splits: int = 2) -> dict:
     LAST_DIAG_PATH = 'torch'
     return {'ess': torch.stack([ess1(z[c][None]) for c in range(C)]).reshape(C, *trail), 'crhat': crhat, 'rhat': rhat,
             'wcv': within_chain_var(x), 'bcv': between_chain_var(x)}
+
+
+# ---- chain diagnostics in function space: the statistics above, of what every draw predicts on every row.  The library
+# streams them (Engine.function_diagnostics, mile_function_diagnostics); the dense forms here are the yardstick and the path
+# for CPU tensors.
+
+def function_columns_dense(outputs: torch.Tensor, y, task: str) -> torch.Tensor:
+    """outputs [C, S, N, O] (``predict``'s tensor) -> the series [C, S, M] in outputs' dtype.  With Q = O + 1 (Q = O when ``y``
+    is None) column n * Q + q is quantity q of row n: regression (mu, log sigma, l), classification (the O softmax
+    probabilities exp(z_k - (m + log(se))), l), l = log p(y_n | x_n, theta) with sigma clipped to [1e-6, 1e6] as in
+    ``pointwise_loglik``.  With ``y`` the last column is L = sum_n l_n, summed in float64 in row order."""
+    z = outputs
+    C_, S_, N, O = z.shape
+    if task == 'regr':
+        parts = [z]
+        if y is not None:
+            yt = torch.as_tensor(y, device=z.device).to(z.dtype).reshape(N)
+            es = torch.exp(z[..., 1])
+            sig = torch.where(torch.isnan(es), es, es.clamp(1e-6, 1e6))
+            r = (yt - z[..., 0]) / sig
+            ll = -0.5 * r * r - torch.log(sig) - 0.91893853320467274
+    else:
+        m = z.max(dim=-1, keepdim=True).values
+        lse = m + torch.log(torch.exp(z - m).sum(dim=-1, keepdim=True))
+        parts = [torch.exp(z - lse)]
+        if y is not None:
+            yi = torch.as_tensor(y, device=z.device).to(torch.int64).reshape(1, 1, N, 1).expand(C_, S_, N, 1)
+            ll = (torch.gather(z, 3, yi) - lse)[..., 0]
+    if y is None:
+        return parts[0].reshape(C_, S_, N * O)
+    cols = torch.cat([parts[0], ll[..., None]], dim=-1).reshape(C_, S_, N * (O + 1))
+    L = torch.cumsum(ll.to(torch.float64), dim=-1)[..., -1:]              # row after row, as the library adds them
+    return torch.cat([cols, L.to(z.dtype)], dim=-1)
+
+
+def _function_summaries(rhat, crhat, ess, NQ: int):
+    """(summary dict keyed by _lib.FDIAG_SUMMARY, chain_summary [C, 2] float64) of statistic arrays rhat [M], crhat, ess [C, M]
+    over their first NQ columns: what k_fdiag_summary reduces on the device, for the paths that do not run it.  Non-finite
+    cells are skipped and counted; of equal extremes the lower chain, then the lower column wins."""
+    import numpy as np
+    r = rhat.detach().cpu().numpy().astype(np.float64)[:NQ]
+    c = crhat.detach().cpu().numpy().astype(np.float64)[:, :NQ]
+    e = ess.detach().cpu().numpy().astype(np.float64)[:, :NQ]
+    nan = float('nan')
+
+    def extreme(a, fin, largest):
+        if not fin.any():
+            return nan, -1
+        b = np.where(fin, a, -np.inf if largest else np.inf).reshape(-1)
+        i = int(np.argmax(b) if largest else np.argmin(b))               # the first of equal extremes in C order
+        return float(b[i]), i
+    fr, fc, fe = np.isfinite(r), np.isfinite(c), np.isfinite(e)
+    rmax, ri = extreme(r, fr, True)
+    cmax, ci = extreme(c, fc, True)
+    emin, ei = extreme(e, fe, False)
+    s = {'rhat_max': rmax, 'rhat_mean': float(r[fr].sum() / fr.sum()) if fr.any() else nan, 'rhat_column': float(ri),
+         'rhat_gt_1_01': float((r[fr] > 1.01).sum()), 'rhat_gt_1_05': float((r[fr] > 1.05).sum()),
+         'rhat_gt_1_1': float((r[fr] > 1.1).sum()), 'rhat_skipped': float((~fr).sum()),
+         'crhat_max': cmax, 'crhat_chain': float(ci // NQ if ci >= 0 else -1), 'crhat_column': float(ci % NQ if ci >= 0 else -1),
+         'crhat_skipped': float((~fc).sum()),
+         'ess_min': emin, 'ess_mean': float(e[fe].sum() / fe.sum()) if fe.any() else nan,
+         'ess_chain': float(ei // NQ if ei >= 0 else -1), 'ess_column': float(ei % NQ if ei >= 0 else -1),
+         'ess_skipped': float((~fe).sum())}
+    chain = np.stack([np.where(fe.any(axis=1), np.where(fe, e, np.inf).min(axis=1), nan),
+                      np.where(fc.any(axis=1), np.where(fc, c, -np.inf).max(axis=1), nan)], axis=1)
+    return s, torch.from_numpy(chain)
+
+
+def function_diagnostics_dense(outputs: torch.Tensor, y, task: str, n_splits: int = 2) -> dict:
+    """``chain_diagnostics`` of ``function_columns_dense(outputs, y, task)``, as the dict ``Engine.function_diagnostics``
+    returns (``columns`` [M, C, S] always there): the composition that holds every tensor at once, which the library call is
+    measured against, and the path for CPU tensors (float64 statistics then)."""
+    cols = function_columns_dense(outputs, y, task)
+    C_, S_, N, O = outputs.shape
+    Q = O + (1 if y is not None else 0)
+    res = dict(chain_diagnostics(cols, n_splits))
+    res['columns'] = cols.permute(2, 0, 1).contiguous()
+    res['loglik_sum'] = None
+    if y is not None:
+        ll = cols[:, :, :N * Q].reshape(C_, S_, N, Q)[..., O]
+        res['loglik_sum'] = torch.cumsum(ll.to(torch.float64), dim=-1)[..., -1]
+    res['summary'], res['chain_summary'] = _function_summaries(res['rhat'], res['crhat'], res['ess'], N * Q)
+    res['Q'], res['M'] = Q, int(cols.shape[2])
+    return res
+
+
+LAST_FDIAG_PATH = None      # how the last function_diagnostics call ran: 'library' or 'library+torch_sort'
+
+
+def function_diagnostics(eng, samples, x, y=None, n_splits: int = 2, return_columns: bool = False, max_draws_per_pass: int = 0,
+                         max_rows_per_tile: int = 0, block_rows: int = 0) -> dict:
+    """All five statistics of ``Engine.function_diagnostics`` for samples [C, S, d] at any C * S.  Up to the library's pooled
+    bound (C * S <= 16384) this is one library call.  Past it the rows go in blocks of ``block_rows`` (0: as many as keep a
+    block's columns under 256 MB): the library gives wcv, bcv, crhat, the columns and the block's summed log-likelihood, the
+    columns are ranked by the torch sort that ``chain_diagnostics`` uses there and go back into the library's ESS / R-hat
+    kernels; the blocks' log-likelihood sums are added in block order, and that column gets its statistics last.  Inside a
+    block the library adds the rows in row order; across blocks the fp64 sums associate by block, so ``loglik_sum`` (and the
+    last column's statistics) equal the one-call, row-order sum bit for bit only while every block after the first holds one
+    row, and to fp64 rounding otherwise: unlike the library's tiles, ``block_rows`` can move the last bits of that column."""
+    global LAST_FDIAG_PATH
+    from mile_amd._lib import DIAG_POOL_MAX
+    samples = torch.as_tensor(samples)
+    C_, S_ = int(samples.shape[0]), int(samples.shape[1])
+    caps = dict(max_draws_per_pass=max_draws_per_pass, max_rows_per_tile=max_rows_per_tile)
+    if C_ * S_ <= DIAG_POOL_MAX:
+        LAST_FDIAG_PATH = 'library'
+        return eng.function_diagnostics(samples, x, y, n_splits=n_splits, return_columns=return_columns, **caps)
+    x = torch.as_tensor(x)
+    N = int(x.shape[0])
+    O = int(eng.spec.hidden_structure[-1])
+    Q = O + (1 if y is not None else 0)
+    M = N * Q + (1 if y is not None else 0)
+    nb = int(block_rows) if block_rows else max(1, (1 << 28) // (C_ * S_ * 4 * Q))
+    dev = eng.device
+    samples = samples.to(dev)
+    y = None if y is None else torch.as_tensor(y)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = {'wcv': new(M), 'bcv': new(M), 'rhat': new(M), 'ess': new(C_, M), 'crhat': new(C_, M),
+           'columns': new(M, C_, S_) if return_columns else None, 'loglik_sum': None}
+    total = torch.zeros((C_, S_), dtype=torch.float64, device=dev) if y is not None else None
+    for r0 in range(0, N, nb):
+        r1 = min(N, r0 + nb)
+        blk = eng.function_diagnostics(samples, x[r0:r1], None if y is None else y[r0:r1], n_splits=n_splits,
+                                       what=('wcv', 'bcv', 'crhat'), return_columns=True, **caps)
+        m0, m1 = r0 * Q, r1 * Q                                          # (the block's own last column, its L, is left out)
+        for k in ('wcv', 'bcv'):
+            out[k][m0:m1] = blk[k][:m1 - m0]
+        out['crhat'][:, m0:m1] = blk['crhat'][:, :m1 - m0]
+        cols = blk['columns'][:m1 - m0]
+        out['ess'][:, m0:m1], out['rhat'][m0:m1] = _pooled_ess_rhat(cols.permute(1, 2, 0).contiguous(), n_splits)
+        if return_columns:
+            out['columns'][m0:m1] = cols
+        if y is not None:
+            total += blk['loglik_sum']
+    if y is not None:
+        L = total.to(torch.float32)[:, :, None].contiguous()
+        last = _library_diagnostics(L, n_splits)
+        for k in ('wcv', 'bcv', 'rhat'):
+            out[k][M - 1] = last[k][0]
+        for k in ('ess', 'crhat'):
+            out[k][:, M - 1] = last[k][:, 0]
+        if return_columns:
+            out['columns'][M - 1] = L[:, :, 0]
+        out['loglik_sum'] = total
+    out['summary'], cs = _function_summaries(out['rhat'], out['crhat'], out['ess'], N * Q)
+    out['chain_summary'] = cs.to(dev)
+    out['Q'], out['M'] = Q, M
+    LAST_FDIAG_PATH = 'library+torch_sort'
+    return out
+
+
+def function_quantity_names(task: str, O: int, with_y: bool) -> list:
+    """The names of the Q quantities of a row, in column order."""
+    names = ['mu', 'log_sigma'] if task == 'regr' else [f'p{k}' for k in range(O)]
+    return names + (['loglik'] if with_y else [])
+
+
+def function_diagnostics_summary(res: dict, N: int, Q: int, task: str = 'regr') -> dict:
+    """The ``fdiag_*`` scalars of a ``function_diagnostics`` result on N rows with Q quantities each: the library's summary
+    (max / mean R-hat and its column, the columns above 1.01 / 1.05 / 1.1, max per-chain R-hat, min / mean ESS, the cells
+    skipped), per quantity the max / mean R-hat and min ESS, the summed log-likelihood's own R-hat and ESS, the mean share of
+    the between-chain variance bcv / (bcv + wcv), and ``fdiag_r_eff_mean``: the mean over the rows of sum_c ess[c, l_n] /
+    (C * S), the relative efficiency PSIS-LOO asks for when the rows are the training rows."""
+    import numpy as np
+    arr = {k: res[k].detach().cpu().numpy().astype(np.float64) for k in ('wcv', 'bcv', 'rhat', 'ess', 'crhat')}
+    NQ, M = N * Q, int(res['M'])
+    with_y = M > NQ
+    C_ = arr['ess'].shape[0]
+    out = {f'fdiag_{k}': (int(v) if k.endswith(('_column', '_chain', '_skipped')) or '_gt_' in k else float(v))
+           for k, v in res['summary'].items()}
+    out['fdiag_n_columns'] = M
+    with np.errstate(all='ignore'):
+        for q, name in enumerate(function_quantity_names(task, Q - (1 if with_y else 0), with_y)):
+            r, e = arr['rhat'][q:NQ:Q], arr['ess'][:, q:NQ:Q]
+            out[f'fdiag_rhat_max_{name}'] = float(np.nanmax(r)) if np.isfinite(r).any() else float('nan')
+            out[f'fdiag_rhat_mean_{name}'] = float(np.nanmean(r)) if np.isfinite(r).any() else float('nan')
+            out[f'fdiag_ess_min_{name}'] = float(np.nanmin(e)) if np.isfinite(e).any() else float('nan')
+        share = arr['bcv'][:NQ] / (arr['bcv'][:NQ] + arr['wcv'][:NQ])
+        out['fdiag_between_share'] = float(np.nanmean(share)) if np.isfinite(share).any() else float('nan')
+    if with_y:
+        out['fdiag_loglik_sum_rhat'] = float(arr['rhat'][M - 1])
+        out['fdiag_loglik_sum_ess'] = float(arr['ess'][:, M - 1].sum())
+        if res.get('loglik_sum') is not None:
+            S_ = int(res['loglik_sum'].shape[1])
+            out['fdiag_r_eff_mean'] = float(np.mean(arr['ess'][:, Q - 1:NQ:Q].sum(axis=0) / (C_ * S_)))
+    out['fdiag_chain_ess_min'] = [float(v) for v in res['chain_summary'][:, 0].cpu()]
+    out['fdiag_chain_crhat_max'] = [float(v) for v in res['chain_summary'][:, 1].cpu()]
+    return out
 
 
 # ---- the rest of evaluate_bde's report (src/inference/evaluation.py:46-137,409-544): draws from the raw outputs of
