@@ -3,7 +3,7 @@
 // classes in descending order of probability, the highest-probability set at each coverage level, the rank of the true
 // label, the Brier score, the NLL, the accuracy and the reliability bins.  include/mile_hip.h states the definition.  Kernels
 // in mile_calib.hip; the entry points (argument checks, the row tiles and the passes over the draws through mile_predict's
-// forward) in mile_hip.hip.
+// forward) in mile_eval.hip.
 //
 // One tile of Nt rows goes through these launches:
 //   k_cal_accum   grid (ceil(Nt / 64), C), once per pass of J draws: a thread per (chain, row) along the contiguous row axis

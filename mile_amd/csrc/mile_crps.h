@@ -2,7 +2,7 @@
 // draws i of chain c are Normals (mu_i, sigma_i^2); with A(d, v) = E|N(d, v)| = d erf(d / sqrt(2v)) + sqrt(2v / pi) exp(-d^2 / 2v)
 //   a_c   = mean_i A(y - mu_i, sigma_i^2)                               G_cc' = mean_{i in c, j in c'} A(mu_i - mu_j, sigma_i^2 + sigma_j^2)
 //   crps_chain[c] = a_c - G_cc / 2                                       crps_mix(w) = sum_c w_c a_c - w'Gw / 2
-// Kernels in mile_crps.hip; the entry points (argument checks, row tiles, the forward passes) in mile_hip.hip.
+// Kernels in mile_crps.hip; the entry points (argument checks, row tiles, the forward passes) in mile_eval.hip.
 //
 // One tile of Nt rows goes through three launches:
 //   k_crps_pack    grid (ceil(Nt / 32), C): raw [C * S][ld][2] -> pk [Nt][C][S] pairs (mu, sigma^2), a chain's kept draws of a row

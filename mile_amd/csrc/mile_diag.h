@@ -1,6 +1,6 @@
 // Chain diagnostics (mile_chain_diagnostics): within / between chain variance, rank-normalised per-chain ESS, per-chain
 // split R-hat and the pooled split R-hat of draws [C][S][d].  Kernels in mile_diag.hip; the entry point (argument checks,
-// parameter chunks) in mile_hip.hip.
+// parameter chunks) in mile_eval.hip.
 //
 // One chunk of P parameters goes through four launches:
 //   k_diag_transpose  [C][S][d] -> [p][c][s] through a 32 x 32 LDS tile (both sides coalesced)

@@ -1,0 +1,936 @@
+// libmile_hip.so -- the evaluation layer of the C ABI declared in include/mile_hip.h: the host drivers of the likelihood and
+// prediction calls and of every statistic of the ensemble (argument checks, tile plans, tile loops).  The statistics' kernels
+// are in their own translation units behind the launchers of their headers; the forward is the sampler's, reached through
+// mile_eval_handle.h and nothing else of the handle.  No kernel is defined or launched from this file.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/mile_hip.h"
+#include "mile_eval_handle.h"
+#include "mile_eval_plan.h"
+#include "mile_moments.h"
+#include "mile_lppd.h"
+#include "mile_quantiles.h"
+#include "mile_loo.h"
+#include "mile_stack.h"
+#include "mile_calib.h"
+#include "mile_crps.h"
+#include "mile_diag.h"
+#include "mile_fdiag.h"
+
+// D consecutive draws in passes of `chunk`, each pass at its draw offset of out [D][per sample]: every (draw, row) forward once
+static int forward_draws(mile_sampler *s, const float *theta, int64_t D, int64_t chunk, float *out, hipStream_t st) {
+  const size_t d = eval_view(s).d;
+  for (int64_t s0 = 0; s0 < D; s0 += chunk) {
+    const int rc = eval_forward(s, theta + (size_t)s0 * d, std::min<int64_t>(chunk, D - s0), out + (size_t)s0 * eval_per_sample(s), st);
+    if (rc != MILE_OK) return rc;
+  }
+  return MILE_OK;
+}
+// draws j0 .. j0 + J of each of C chains of S draws (chain c's are rows c * S + j0 .. of theta) into out [C][J][per sample]
+static int forward_chains(mile_sampler *s, const float *theta, int C, int64_t S, int64_t j0, int J, float *out, hipStream_t st) {
+  const size_t d = eval_view(s).d;
+  for (int c = 0; c < C; ++c) {
+    const int rc = eval_forward(s, theta + ((size_t)c * S + (size_t)j0) * d, J, out + (size_t)c * J * eval_per_sample(s), st);
+    if (rc != MILE_OK) return rc;
+  }
+  return MILE_OK;
+}
+
+// mile_pointwise_loglik and (y == nullptr) mile_predict: stage the evaluation rows, then the forward
+static int evaluate_rows(mile_sampler *s, const float *theta, int32_t S, const float *X, const void *y, int64_t N, float *out, void *stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = stage_rows(s, X, y, N, st);
+  return rc != MILE_OK ? rc : eval_forward(s, theta, S, out, st);
+}
+
+// The checks that the evaluation calls share, each a message or null: the range of N, the generic shape of a call (S, then
+// N), the signs of the caller's pass and tile caps, the model of the statistics of a Gaussian predictive.
+static const char *bad_N(int64_t N) { return N < 1 || N > 0x3fffffff ? "N out of range (1 .. 2^30 - 1)" : nullptr; }
+static const char *bad_SN(int64_t S, int64_t N) { return S < 1 || S > 0x7fffffff ? "S out of range (1 .. 2^31 - 1)" : bad_N(N); }
+static const char *bad_caps(int64_t max_draws_per_pass, int64_t max_rows_per_tile) {
+  if (max_draws_per_pass < 0) return "max_draws_per_pass < 0";
+  return max_rows_per_tile < 0 ? "max_rows_per_tile < 0" : nullptr;
+}
+static const char *not_mu_log_sigma(const mile_sampler *s) {
+  return eval_view(s).task != MILE_TASK_REGRESSION || eval_view(s).O != 2 ? "needs a regression model with (mu, log sigma) outputs" : nullptr;
+}
+// the refusal of an argument of `fn`: MILE_ERR_INVALID with "fn: m"
+static int bad(const char *fn, const char *m) { return fail(MILE_ERR_INVALID, std::string(fn) + ": " + m); }
+
+// What every evaluation entry point `fn` on a handle checks before anything else, in this order: null arguments, the shape
+// (`shape`: the statistic's own message or null, bad_SN for most), the call's other checks (`more`: a message or null; it may
+// read the handle), then the frozen tables.  MILE_OK, or the failure with its message set.
+template <class More>
+static int eval_args(const char *fn, const mile_sampler *s, bool null_arg, const char *shape, More more) {
+  if (!s || null_arg) return bad(fn, "null argument");
+  if (shape) return bad(fn, shape);
+  if (const char *m = more()) return bad(fn, m);
+  if (tables_missing(s)) return fail(MILE_ERR_STATE, kNoTables);
+  return MILE_OK;
+}
+static const char *no_more_checks() { return nullptr; }
+
+// What every streamed call `fn` does once its checks have passed and its plan stands: the handle's device, then the handle's
+// workspace of the plan's `bytes` in ws.  No memory is MILE_ERR_NOMEM with "fn: workspace allocation failed (hint)".
+static int stream_ws(const char *fn, mile_sampler *s, size_t bytes, const char *hint, char *&ws) {
+  HIP_TRY(hipSetDevice(eval_view(s).device));
+  ws = (char *)reserve_eval_ws(s, bytes);
+  return ws ? MILE_OK : fail(MILE_ERR_NOMEM, std::string(fn) + ": workspace allocation failed (" + hint + ")");
+}
+
+// The tensor-input calls' workspace of `bytes` (0: none), this call's own: `run` gets it, and the stream is drained before it is
+// freed, whatever run returned.  run's code goes before the synchronise's; no memory is MILE_ERR_NOMEM with `nomem`.
+template <class Run>
+static int with_call_ws(size_t bytes, const char *nomem, hipStream_t st, Run run) {
+  void *ws = nullptr;
+  if (bytes && hipMalloc(&ws, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MILE_ERR_NOMEM, nomem);
+  }
+  const int rc = run((char *)ws);
+  const hipError_t es = hipStreamSynchronize(st);   // the kernels finish before their workspace goes
+  if (ws) (void)hipFree(ws);
+  if (rc != MILE_OK) return rc;
+  HIP_TRY(es);
+  return MILE_OK;
+}
+// the compute units of the current device, for the tensor-input calls that size a grid by them
+static int current_cus(int *n_cu) {
+  int dev = 0;
+  *n_cu = 256;
+  HIP_TRY(hipGetDevice(&dev));
+  (void)hipDeviceGetAttribute(n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+  return MILE_OK;
+}
+
+// Where a tile's block of forward outputs lies and how many rows each draw has in it.  A statistic's tile loop asks its source
+// for the tile of rows r0 .. r0 + nt: a tensor-input call answers with the caller's array at the tile's first row (ld = N), a
+// streamed call stages the rows, forwards every draw into the workspace and answers with that (ld = nt).
+struct Tile { const float *at; int64_t ld; };
+// the streamed source of the statistics that read raw outputs: the block [D][nt][O] at the start of the workspace ws
+static auto stream_tiles(mile_sampler *s, const float *theta, int64_t D, int64_t chunk, const void *X, char *ws, hipStream_t st) {
+  return [=](int64_t r0, int nt, Tile &t) -> int {
+    const int rc = stage_rows(s, (const float *)X + (size_t)r0 * eval_view(s).in_features, nullptr, nt, st);
+    t = {(const float *)ws, nt};
+    return rc != MILE_OK ? rc : forward_draws(s, theta, D, chunk, (float *)ws, st);
+  };
+}
+
+extern "C" int32_t mile_pointwise_loglik(mile_sampler *s, const float *theta, int32_t S, const float *X, const void *y,
+                                         int64_t N, float *out, void *stream) {
+  const int rc = eval_args("mile_pointwise_loglik", s, !theta || !X || !y || !out, bad_SN(S, N), no_more_checks);
+  return rc != MILE_OK ? rc : evaluate_rows(s, theta, S, X, y, N, out, stream);
+}
+
+extern "C" int32_t mile_predict(mile_sampler *s, const float *theta, int32_t S, const float *X, int64_t N, float *out, void *stream) {
+  const int rc = eval_args("mile_predict", s, !theta || !X || !out, bad_SN(S, N), no_more_checks);
+  return rc != MILE_OK ? rc : evaluate_rows(s, theta, S, X, nullptr, N, out, stream);
+}
+
+// mile_predict_moments: mile_predict's forward in passes of `chunk` draws into the library's workspace, each folded into the
+// per-row accumulators by k_moments_accum; k_moments_finish writes out.  Every check before any launch.
+extern "C" int32_t mile_predict_moments_width(const mile_sampler *s) {
+  if (!s) return fail(MILE_ERR_INVALID, "mile_predict_moments_width: null handle");
+  return eval_view(s).task == MILE_TASK_REGRESSION ? 3 : eval_view(s).O + 2;
+}
+
+extern "C" int32_t mile_predict_moments(mile_sampler *s, const float *theta, int64_t S, const void *X, int64_t N, float *out,
+                                        int32_t *dropped, int64_t max_draws_per_pass, void *stream) {
+  const int rc0 = eval_args("mile_predict_moments", s, !theta || !X || !out, bad_SN(S, N), [&] { return bad_caps(max_draws_per_pass, 0); });
+  if (rc0 != MILE_OK) return rc0;
+  const EvalView v = eval_view(s);
+  const int task = v.task, O = v.O;
+  if (task == MILE_TASK_REGRESSION && O != 2) return fail(MILE_ERR_INVALID, "mile_predict_moments: regression needs (mu, log sigma) outputs");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t per_draw = N * O * 4;
+  const int64_t chunk = pass_draws(EVAL_PASS_TARGET, per_draw, max_draws_per_pass, S);
+  // enough one-wave workgroups for about eight waves per CU, at most one slice per draw of a pass
+  const int slices = (int)std::min<int64_t>(std::min<int64_t>(MOM_MAX_SLICES, chunk), std::max<int64_t>(1, ((int64_t)v.n_cu * 8 * MOM_NT + N - 1) / N));
+  const size_t raw_bytes = r256((size_t)chunk * per_draw), acc_bytes = mom_acc_bytes(task, O, (int)N, slices);
+  char *ws;
+  const int rc2 = stream_ws("mile_predict_moments", s, raw_bytes + acc_bytes, "lower max_draws_per_pass", ws);
+  if (rc2 != MILE_OK) return rc2;
+  MomParams p{};
+  p.raw = (const float *)ws; p.N = (int)N; p.O = O; p.slices = slices; p.S = S;
+  p.acc = (double *)(ws + raw_bytes);
+  p.cnt = (int32_t *)(p.acc + (size_t)slices * mom_planes(task, O) * N);
+  p.out = out; p.dropped = dropped;
+  HIP_TRY(hipMemsetAsync(p.acc, 0, acc_bytes, st));
+  const int rc1 = stage_rows(s, (const float *)X, nullptr, N, st);
+  if (rc1 != MILE_OK) return rc1;
+  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+    p.Sc = (int)std::min<int64_t>(chunk, S - s0);
+    const int rc = eval_forward(s, theta + s0 * v.d, p.Sc, (float *)ws, st);
+    if (rc != MILE_OK) return rc;
+    HIP_TRY(mile_launch_moments_accum(task, p, st));
+  }
+  HIP_TRY(mile_launch_moments_finish(task, p, st));
+  return MILE_OK;
+}
+
+// mile_mixture_quantiles / mile_predict_quantiles: every check before any launch; rows in tiles whose raw block and packed
+// copy fit the evaluation budget, k_qnt_pack + k_qnt_solve per tile (mile_quantiles.h).
+static double host_Phi(double z) { return 0.5 * std::erfc(-z * 0.70710678118654752440); }
+// Phi^-1(p), 0 < p < 1, in fp64: bisection on the lower tail (where erfc keeps its relative accuracy), mirrored for p > 1/2
+static double host_ndtri(double p) {
+  if (p == 0.5) return 0.0;
+  const double pl = p < 0.5 ? p : 1.0 - p;
+  double lo = -40.0, hi = 0.0;
+  for (int i = 0; i < 200 && hi - lo > 0.0; ++i) {
+    const double mid = 0.5 * (lo + hi);
+    if (mid <= lo || mid >= hi) break;
+    if (host_Phi(mid) < pl) lo = mid; else hi = mid;
+  }
+  double z = 0.5 * (lo + hi);
+  for (int i = 0; i < 2; ++i) {   // Newton polish
+    const double f = std::exp(-0.5 * z * z) * 0.39894228040143267794;
+    if (f > 0.0) z -= (host_Phi(z) - pl) / f;
+  }
+  return p < 0.5 ? z : -z;
+}
+
+// what is wrong with the levels or the outputs asked for, or null
+static const char *qnt_bad_args(const double *levels, int32_t Q, const float *y, const float *quant, const float *pit) {
+  if (!levels) return "null levels";
+  if (Q < 1 || Q > QNT_MAX_Q) return "Q out of range (1 .. 32)";
+  for (int i = 0; i < Q; ++i) {
+    if (!(levels[i] > 0.0 && levels[i] < 1.0)) return "levels must lie strictly inside (0, 1)";
+    if (i > 0 && !(levels[i] > levels[i - 1])) return "levels must be strictly increasing";
+  }
+  if (!quant && !pit) return "neither quantiles nor PIT asked for";
+  if (pit && !y) return "PIT needs y";
+  return nullptr;
+}
+
+// The plan of one call: rows per tile, draws per pass and the byte offset of every block of its workspace.  own_raw: the
+// streamed call, whose workspace begins with the forward's raw block [S][Nt][2] (16 bytes per (draw, row) with the packed copy,
+// tiles of whole transpose tiles) and ends with the sweeps [N]; else raw is the caller's and the packed copy comes first.
+struct QntTilePlan { int64_t Nt, chunk; int slices; size_t pk, part, lev, sweeps, total; };
+static QntTilePlan qnt_tile_plan(int64_t S, int64_t N, int n_cu, bool own_raw, int64_t max_rows, int64_t max_draws) {
+  QntTilePlan t;
+  t.Nt = tile_rows(EVAL_PASS_TARGET, S * (own_raw ? 16 : 8), own_raw ? QNT_TILE : 1, max_rows, N);
+  t.chunk = pass_draws(EVAL_NO_BUDGET, 1, max_draws, S);
+  t.slices = qnt_slices((int)S, (int)t.Nt, n_cu);   // of the full tile, for every tile: the partials of a ragged last tile fit behind it
+  t.pk = own_raw ? r256((size_t)S * t.Nt * 8) : 0;
+  t.part = t.pk + qnt_pk_bytes(S, t.Nt);
+  t.lev = t.part + qnt_part_bytes((int)t.Nt, QNT_MAX_Q, t.slices);
+  t.sweeps = t.lev + r256(2 * QNT_MAX_Q * 8);
+  t.total = t.sweeps + (own_raw ? r256((size_t)N * 4) : 0);
+  return t;
+}
+
+// the tiles of one call, each from `source`; sweeps: record them in the workspace
+template <class Source>
+static int qnt_run(char *ws, const QntTilePlan &t, int64_t S, int64_t N, const double *levels, int32_t Q, const float *y, float *quant,
+                   float *pit, int32_t *dropped, bool sweeps, hipStream_t st, Source source) {
+  double lev[2 * QNT_MAX_Q];
+  for (int i = 0; i < Q; ++i) { lev[i] = levels[i]; lev[Q + i] = host_ndtri(levels[i]); }
+  QntParams p{};
+  p.S = (int)S; p.Q = Q; p.slices = t.slices;
+  p.pk = (float2 *)(ws + t.pk); p.part_brk = (double *)(ws + t.part); p.lev = (const double *)(ws + t.lev);
+  HIP_TRY(hipMemcpyAsync(ws + t.lev, lev, (size_t)2 * Q * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));   // lev is on this stack
+  for (int64_t r0 = 0; r0 < N; r0 += t.Nt) {
+    p.Nt = (int)std::min<int64_t>(t.Nt, N - r0);
+    p.part_cnt = (int32_t *)(ws + t.part + r256((size_t)p.slices * p.Nt * Q * 16));
+    Tile tile;
+    const int rc = source(r0, p.Nt, tile);
+    if (rc != MILE_OK) return rc;
+    p.raw = tile.at; p.ld = tile.ld;
+    p.y = y ? y + r0 : nullptr;
+    p.quant = quant ? quant + r0 * Q : nullptr;
+    p.pit = pit ? pit + r0 : nullptr;
+    p.dropped = dropped ? dropped + r0 : nullptr;
+    p.sweeps = sweeps ? (int32_t *)(ws + t.sweeps) + r0 : nullptr;
+    HIP_TRY(mile_launch_quantiles(p, st));
+  }
+  return MILE_OK;
+}
+
+extern "C" int32_t mile_mixture_quantiles(const float *raw, int64_t S, int64_t N, const double *levels, int32_t Q, const float *y,
+                                          float *quant, float *pit, int32_t *dropped, void *stream) {
+  if (!raw) return bad("mile_mixture_quantiles", "null raw");
+  if (const char *m = bad_SN(S, N)) return bad("mile_mixture_quantiles", m);
+  if (const char *m = qnt_bad_args(levels, Q, y, quant, pit)) return bad("mile_mixture_quantiles", m);
+  hipStream_t st = (hipStream_t)stream;
+  int n_cu;
+  const int rc0 = current_cus(&n_cu);
+  if (rc0 != MILE_OK) return rc0;
+  const QntTilePlan t = qnt_tile_plan(S, N, n_cu, false, 0, 0);
+  return with_call_ws(t.total, "mile_mixture_quantiles: workspace allocation failed", st, [&](char *ws) {
+    return qnt_run(ws, t, S, N, levels, Q, y, quant, pit, dropped, false, st,
+                   [&](int64_t r0, int, Tile &tile) { tile = {raw + 2 * r0, N}; return (int)MILE_OK; });
+  });
+}
+
+extern "C" int64_t mile_predict_quantiles_workspace(const mile_sampler *s, int64_t S, int64_t N) {
+  return !s || bad_SN(S, N) ? -1 : (int64_t)qnt_tile_plan(S, N, eval_view(s).n_cu, true, 0, 0).total;
+}
+
+extern "C" int32_t mile_predict_quantiles(mile_sampler *s, const float *theta, int64_t S, const void *X, int64_t N,
+                                          const double *levels, int32_t Q, const float *y, float *quant, float *pit, int32_t *dropped,
+                                          int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
+  const int rc0 = eval_args("mile_predict_quantiles", s, !theta || !X, bad_SN(S, N), [&]() -> const char * {
+    if (const char *m = qnt_bad_args(levels, Q, y, quant, pit)) return m;
+    if (const char *m = bad_caps(max_draws_per_pass, max_rows_per_tile)) return m;
+    return not_mu_log_sigma(s);
+  });
+  if (rc0 != MILE_OK) return rc0;
+  hipStream_t st = (hipStream_t)stream;
+  const QntTilePlan t = qnt_tile_plan(S, N, eval_view(s).n_cu, true, max_rows_per_tile, max_draws_per_pass);
+  char *ws;
+  const int rc1 = stream_ws("mile_predict_quantiles", s, t.total, "lower max_rows_per_tile", ws);
+  if (rc1 != MILE_OK) return rc1;
+  const int rc = qnt_run(ws, t, S, N, levels, Q, y, quant, pit, dropped, quant != nullptr, st, stream_tiles(s, theta, S, t.chunk, X, ws, st));
+  if (rc != MILE_OK) return rc;
+  record_quantile_sweeps(s, (const int32_t *)(ws + t.sweeps), quant ? N : 0);
+  return MILE_OK;
+}
+
+/* test and tool hook: sweeps of k_qnt_solve over the rows of the handle's last mile_predict_quantiles that asked for quantiles */
+extern "C" int32_t mile_debug_quantile_sweeps(mile_sampler *s, int64_t *rows, int64_t *total, int32_t *most) {
+  if (!s || !rows || !total || !most) return fail(MILE_ERR_INVALID, "mile_debug_quantile_sweeps: null argument");
+  const int32_t *sweeps;
+  *rows = recorded_quantile_sweeps(s, &sweeps); *total = 0; *most = 0;
+  if (!*rows) return MILE_OK;
+  HIP_TRY(hipSetDevice(eval_view(s).device));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<int32_t> h((size_t)*rows);
+  HIP_TRY(hipMemcpy(h.data(), sweeps, h.size() * 4, hipMemcpyDeviceToHost));
+  for (int32_t v : h) { *total += v; *most = std::max(*most, v); }
+  return MILE_OK;
+}
+
+// mile_psis_loo / mile_loo_stream: every check before any launch; rows in tiles whose [S][Nt] block of log-likelihoods and
+// packed copy fit the evaluation budget, k_loo_pack + k_loo_row per tile (mile_loo.h).
+static const char *loo_bad_SN(int64_t S, int64_t N) { return S < 2 || S > LOO_MAX_S ? "S out of range (2 .. 2^20)" : bad_N(N); }
+// what is wrong with r_eff or the outputs asked for (S in range), or null
+static const char *loo_bad_args(int64_t S, double r_eff, bool any_output) {
+  if (!any_output) return "no output asked for";
+  if (!std::isfinite(r_eff) || !(r_eff > 0.0)) return "r_eff must be finite and positive";
+  if (loo_tail_host(S, r_eff) > LOO_MAX_TAIL) return "the tail is longer than 4096 draws (S / r_eff too large)";
+  return nullptr;
+}
+
+struct LooOut {   // [C, N] each, any may be null
+  double *lppd, *p_waic, *elpd_loo, *khat;
+  int32_t *dropped;
+  bool any() const { return lppd || p_waic || elpd_loo || khat || dropped; }
+};
+
+// The plan of one call: rows per tile, draws per pass and the byte offset of the packed copy in its workspace.  own_raw: the
+// streamed call, whose workspace begins with the forward's block [S][Nt] (8 bytes per (draw, row) with the packed copy, tiles of
+// whole transpose tiles); else loglik is the caller's and the packed copy is all there is.
+struct LooTilePlan { int64_t Nt, chunk; size_t pk, total; };
+static LooTilePlan loo_tile_plan(int64_t S, int64_t N, bool own_raw, int64_t max_rows, int64_t max_draws) {
+  LooTilePlan t;
+  t.Nt = tile_rows(EVAL_PASS_TARGET, S * (own_raw ? 8 : 4), own_raw ? LOO_TILE : 1, max_rows, N);
+  t.chunk = pass_draws(EVAL_NO_BUDGET, 1, max_draws, S);
+  t.pk = own_raw ? loo_pk_bytes(S, t.Nt) : 0;   // the forward's block is as large as its packed copy
+  t.total = t.pk + loo_pk_bytes(S, t.Nt);
+  return t;
+}
+
+// the tiles of one call, the C chains inside each: chain c's block [S][..] of the tile from `source`, its outputs at row c
+template <class Source>
+static int loo_run(char *ws, const LooTilePlan &t, int64_t C, int64_t S, int64_t N, int n_cu, double r_eff, const LooOut &o, hipStream_t st,
+                   Source source) {
+  LooParams p{};
+  p.S = (int)S; p.pk = (float *)(ws + t.pk); p.r_eff = r_eff; p.M_full = loo_tail_host(S, r_eff);
+  for (int64_t r0 = 0; r0 < N; r0 += t.Nt) {
+    p.Nt = (int)std::min<int64_t>(t.Nt, N - r0);
+    p.slices = loo_slices((int)S, p.Nt, n_cu);
+    for (int64_t c = 0; c < C; ++c) {
+      Tile tile;
+      const int rc = source(r0, p.Nt, c, tile);
+      if (rc != MILE_OK) return rc;
+      p.ll = tile.at; p.ld = tile.ld;
+      const size_t at = (size_t)c * N + r0;
+      p.lppd = o.lppd ? o.lppd + at : nullptr;
+      p.p_waic = o.p_waic ? o.p_waic + at : nullptr;
+      p.elpd_loo = o.elpd_loo ? o.elpd_loo + at : nullptr;
+      p.khat = o.khat ? o.khat + at : nullptr;
+      p.dropped = o.dropped ? o.dropped + at : nullptr;
+      HIP_TRY(mile_launch_loo(p, st));
+    }
+  }
+  return MILE_OK;
+}
+
+extern "C" int32_t mile_psis_loo(const float *loglik, int64_t S, int64_t N, double r_eff, double *lppd, double *p_waic, double *elpd_loo,
+                                 double *khat, int32_t *dropped, void *stream) {
+  const LooOut o{lppd, p_waic, elpd_loo, khat, dropped};
+  if (!loglik) return bad("mile_psis_loo", "null loglik");
+  if (const char *m = loo_bad_SN(S, N)) return bad("mile_psis_loo", m);
+  if (const char *m = loo_bad_args(S, r_eff, o.any())) return bad("mile_psis_loo", m);
+  hipStream_t st = (hipStream_t)stream;
+  int n_cu;
+  const int rc0 = current_cus(&n_cu);
+  if (rc0 != MILE_OK) return rc0;
+  const LooTilePlan t = loo_tile_plan(S, N, false, 0, 0);
+  return with_call_ws(t.total, "mile_psis_loo: workspace allocation failed", st, [&](char *ws) {
+    return loo_run(ws, t, 1, S, N, n_cu, r_eff, o, st, [&](int64_t r0, int, int64_t, Tile &tile) { tile = {loglik + r0, N}; return (int)MILE_OK; });
+  });
+}
+
+extern "C" int64_t mile_loo_stream_workspace(const mile_sampler *s, int64_t S, int64_t N) {
+  return !s || loo_bad_SN(S, N) ? -1 : (int64_t)loo_tile_plan(S, N, true, 0, 0).total;
+}
+
+// mile_loo_stream (C = 1) and mile_chain_loo_stream: theta [C * S, d], chain c's S draws at row c * S, outputs [C, N].  A tile's
+// rows are staged once for all chains; each chain's block [S][Nt] is forwarded and goes through k_loo_pack + k_loo_row on its
+// own, as a call on that chain alone would send it.
+static int loo_stream_chains(const char *fn, mile_sampler *s, const float *theta, int64_t C, int64_t S, const void *X, const void *y, int64_t N,
+                             double r_eff, const LooOut &o, int64_t max_draws_per_pass, int64_t max_rows_per_tile, hipStream_t st) {
+  const int rc0 = eval_args(fn, s, !theta || !X || !y, loo_bad_SN(S, N), [&]() -> const char * {
+    if (C < 1 || C > 1024) return "C out of range (1 .. 1024)";
+    if (const char *m = loo_bad_args(S, r_eff, o.any())) return m;
+    return bad_caps(max_draws_per_pass, max_rows_per_tile);
+  });
+  if (rc0 != MILE_OK) return rc0;
+  const LooTilePlan t = loo_tile_plan(S, N, true, max_rows_per_tile, max_draws_per_pass);
+  char *ws;
+  const int rc1 = stream_ws(fn, s, t.total, "lower max_rows_per_tile", ws);
+  if (rc1 != MILE_OK) return rc1;
+  const EvalView v = eval_view(s);
+  float *raw = (float *)ws;
+  return loo_run(ws, t, C, S, N, v.n_cu, r_eff, o, st, [&](int64_t r0, int nt, int64_t c, Tile &tile) -> int {
+    if (c == 0) {   // the tile's rows and labels, staged when its first chain is asked for
+      const int rc = stage_rows(s, (const float *)X + (size_t)r0 * v.in_features, (const char *)y + (size_t)r0 * 4, nt, st);
+      if (rc != MILE_OK) return rc;
+    }
+    tile = {raw, nt};
+    return forward_draws(s, theta + (size_t)c * S * v.d, S, t.chunk, raw, st);
+  });
+}
+
+extern "C" int32_t mile_loo_stream(mile_sampler *s, const float *theta, int64_t S, const void *X, const void *y, int64_t N, double r_eff,
+                                   double *lppd, double *p_waic, double *elpd_loo, double *khat, int32_t *dropped,
+                                   int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
+  return loo_stream_chains("mile_loo_stream", s, theta, 1, S, X, y, N, r_eff, {lppd, p_waic, elpd_loo, khat, dropped}, max_draws_per_pass,
+                           max_rows_per_tile, (hipStream_t)stream);
+}
+
+extern "C" int64_t mile_chain_loo_stream_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N) {
+  if (C < 1 || C > 1024) return -1;
+  return mile_loo_stream_workspace(s, S, N);   // a chain at a time: the workspace of one
+}
+
+extern "C" int32_t mile_chain_loo_stream(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, const void *y, int64_t N,
+                                         double r_eff, double *lppd, double *p_waic, double *elpd_loo, double *khat, int32_t *dropped,
+                                         int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
+  return loo_stream_chains("mile_chain_loo_stream", s, theta, C, S, X, y, N, r_eff, {lppd, p_waic, elpd_loo, khat, dropped}, max_draws_per_pass,
+                           max_rows_per_tile, (hipStream_t)stream);
+}
+
+// mile_mixture_crps / mile_crps_stream: every check before any launch; rows in tiles that respect the evaluation budget, the
+// pairs of one launch (CRPS_MAX_PAIRS_PER_LAUNCH) and the slots' bytes; k_crps_pack + k_crps_pairs + k_crps_finish per tile
+// (mile_crps.h).
+struct CrpsOut {
+  double *crps_chain, *spread_chain, *crps_mix, *spread_mix, *gram;
+  int32_t *dropped;
+  bool any() const { return crps_chain || spread_chain || crps_mix || spread_mix || gram || dropped; }
+  bool pairs() const { return crps_chain || spread_chain || crps_mix || spread_mix || gram; }
+};
+// what is wrong with the shape, or null; then (the shape in range) with the weights, the outputs asked for or the tile cap
+static const char *crps_bad_shape(int32_t C, int64_t S, int64_t N) {
+  if (C < 1 || C > CRPS_MAX_C) return "C out of range (1 .. 1024)";
+  if (S < 1) return "S < 1";
+  if (S > CRPS_MAX_DRAWS || (int64_t)C * S > CRPS_MAX_DRAWS) return "C * S out of range (1 .. 2^20)";
+  return bad_N(N);
+}
+static const char *crps_bad_args(int32_t C, const double *weights, int32_t n_w, const CrpsOut &o, int64_t max_rows) {
+  if (!o.any()) return "no output asked for";
+  if (n_w < 0 || n_w > CRPS_MAX_W) return "n_w out of range (0 .. 8)";
+  if (n_w > 0 && !weights) return "n_w > 0 without weights";
+  for (int m = 0; m < n_w; ++m) {
+    double sum = 0.0;
+    for (int c = 0; c < C; ++c) {
+      const double w = weights[(size_t)m * C + c];
+      if (!std::isfinite(w) || w < 0.0) return "weights must be finite and >= 0";
+      sum += w;
+    }
+    if (!(std::fabs(sum - 1.0) <= 1e-9)) return "every weight vector must sum to 1 (within 1e-9)";
+  }
+  return bad_caps(0, max_rows);
+}
+
+// The plan of one call: the pairs' units, rows per tile (the budget's, then the caps of one k_crps_pairs launch), draws per pass
+// and the byte offset of every block of its workspace.  own_raw: the streamed call, whose workspace begins with the forward's raw
+// block [C * S][Nt][2] (16 bytes per (draw, row) with the packed copy); else raw is the caller's and the packed copy comes first.
+struct CrpsTilePlan { CrpsPlan pl; int64_t Nt, chunk; size_t pk, cnt, part, w, total; };
+static CrpsTilePlan crps_tile_plan(int64_t C, int64_t S, int64_t N, bool own_raw, int64_t max_rows, int64_t max_draws) {
+  CrpsTilePlan t;
+  const int64_t D = C * S;
+  t.pl = crps_plan(C, S, N);
+  t.Nt = tile_rows(EVAL_PASS_TARGET, D * (own_raw ? 16 : 8), 1, max_rows, N);
+  t.Nt = std::min(t.Nt, std::max<int64_t>(1, CRPS_MAX_PAIRS_PER_LAUNCH / (D * (D + 1) / 2)));
+  t.Nt = std::min(t.Nt, std::max<int64_t>(1, CRPS_MAX_SLOT_BYTES / (t.pl.units * 8)));
+  t.Nt = std::min(t.Nt, std::max<int64_t>(1, CRPS_MAX_GRID / t.pl.units));
+  t.chunk = pass_draws(EVAL_NO_BUDGET, 1, max_draws, D);
+  t.pk = own_raw ? r256((size_t)D * t.Nt * 8) : 0;
+  t.cnt = t.pk + r256((size_t)D * t.Nt * 8);
+  t.part = t.cnt + r256((size_t)t.Nt * C * 4);
+  t.w = t.part + r256((size_t)t.Nt * t.pl.units * 8);
+  t.total = t.w + r256((size_t)CRPS_MAX_W * C * 8);
+  return t;
+}
+
+// the tiles of one call, each from `source`
+template <class Source>
+static int crps_run(char *ws, const CrpsTilePlan &t, int32_t C, int64_t S, int64_t N, const float *y, const double *weights, int32_t n_w,
+                    const CrpsOut &o, hipStream_t st, Source source) {
+  CrpsParams p{};
+  p.C = C; p.S = (int)S; p.pl = t.pl; p.N = N; p.n_w = n_w;
+  p.pk = (float2 *)(ws + t.pk); p.cnt = (int32_t *)(ws + t.cnt); p.part = (double *)(ws + t.part);
+  if (n_w > 0) {
+    HIP_TRY(hipMemcpyAsync(ws + t.w, weights, (size_t)n_w * C * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));   // weights is the caller's host memory
+    p.w = (const double *)(ws + t.w);
+  }
+  p.crps_chain = o.crps_chain; p.spread_chain = o.spread_chain; p.crps_mix = o.crps_mix; p.spread_mix = o.spread_mix;
+  p.gram = o.gram; p.dropped = o.dropped;
+  for (int64_t r0 = 0; r0 < N; r0 += t.Nt) {
+    p.Nt = (int)std::min<int64_t>(t.Nt, N - r0);
+    p.r0 = r0;
+    Tile tile;
+    const int rc = source(r0, p.Nt, tile);
+    if (rc != MILE_OK) return rc;
+    p.raw = tile.at; p.ld = tile.ld;
+    p.y = y + r0;
+    HIP_TRY(mile_launch_crps_pack(p, st));
+    if (!o.pairs()) continue;
+    HIP_TRY(mile_launch_crps_pairs(p, st));
+    HIP_TRY(mile_launch_crps_finish(p, st));
+  }
+  return MILE_OK;
+}
+
+extern "C" int32_t mile_mixture_crps(const float *raw, int32_t C, int64_t S, int64_t N, const float *y, const double *weights, int32_t n_w,
+                                     double *crps_chain, double *spread_chain, double *crps_mix, double *spread_mix, double *gram,
+                                     int32_t *dropped, int64_t max_rows_per_tile, void *stream) {
+  if (!raw || !y) return bad("mile_mixture_crps", "null raw or y");
+  const CrpsOut o{crps_chain, spread_chain, crps_mix, spread_mix, gram, dropped};
+  if (const char *m = crps_bad_shape(C, S, N)) return bad("mile_mixture_crps", m);
+  if (const char *m = crps_bad_args(C, weights, n_w, o, max_rows_per_tile)) return bad("mile_mixture_crps", m);
+  hipStream_t st = (hipStream_t)stream;
+  const CrpsTilePlan t = crps_tile_plan(C, S, N, false, max_rows_per_tile, 0);
+  return with_call_ws(t.total, "mile_mixture_crps: workspace allocation failed (lower max_rows_per_tile)", st, [&](char *ws) {
+    return crps_run(ws, t, C, S, N, y, weights, n_w, o, st, [&](int64_t r0, int, Tile &tile) { tile = {raw + 2 * r0, N}; return (int)MILE_OK; });
+  });
+}
+
+extern "C" int64_t mile_crps_stream_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N) {
+  return !s || crps_bad_shape(C, S, N) ? -1 : (int64_t)crps_tile_plan(C, S, N, true, 0, 0).total;
+}
+
+extern "C" int32_t mile_crps_stream(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, const float *y, int64_t N,
+                                    const double *weights, int32_t n_w, double *crps_chain, double *spread_chain, double *crps_mix,
+                                    double *spread_mix, double *gram, int32_t *dropped, int64_t max_draws_per_pass,
+                                    int64_t max_rows_per_tile, void *stream) {
+  const CrpsOut o{crps_chain, spread_chain, crps_mix, spread_mix, gram, dropped};
+  const int rc0 = eval_args("mile_crps_stream", s, !theta || !X || !y, crps_bad_shape(C, S, N), [&]() -> const char * {
+    if (const char *m = crps_bad_args(C, weights, n_w, o, max_rows_per_tile)) return m;
+    if (const char *m = bad_caps(max_draws_per_pass, 0)) return m;
+    return not_mu_log_sigma(s);
+  });
+  if (rc0 != MILE_OK) return rc0;
+  hipStream_t st = (hipStream_t)stream;
+  const CrpsTilePlan t = crps_tile_plan(C, S, N, true, max_rows_per_tile, max_draws_per_pass);
+  char *ws;
+  const int rc1 = stream_ws("mile_crps_stream", s, t.total, "lower max_rows_per_tile", ws);
+  if (rc1 != MILE_OK) return rc1;
+  return crps_run(ws, t, C, S, N, y, weights, n_w, o, st, stream_tiles(s, theta, (int64_t)C * S, t.chunk, X, ws, st));
+}
+
+// mile_stack_eval: every check before any launch; rows in tiles whose responsibilities fit 256 MiB, k_stk_rows + k_stk_gram per
+// tile, k_stk_final at the end (mile_stack.h).  The workspace is this call's.
+extern "C" int32_t mile_stack_eval(const double *lpd, const double *w, int32_t C, int64_t N, double *score, double *row_score, double *grad,
+                                   double *hess, int64_t *used, int64_t max_rows_per_tile, void *stream) {
+  if (!lpd || !w) return bad("mile_stack_eval", "null lpd or w");
+  if (const char *m = stk_bad_args(C, N, max_rows_per_tile, score || row_score || grad || hess || used)) return bad("mile_stack_eval", m);
+  hipStream_t st = (hipStream_t)stream;
+  StkParams p{};
+  p.lpd = lpd; p.w = w; p.C = C; p.Cx = C + 2; p.N = N;
+  p.B = stk_block_rows(C, N); p.nb = (int)stk_blocks(C, N);
+  p.want_grad = grad != nullptr; p.want_hess = hess != nullptr; p.want_sums = score || grad || hess || used;
+  p.score = score; p.row_score = row_score; p.grad = grad; p.hess = hess; p.used = (long long *)used;
+  const int64_t Nt = stk_tile_rows(C, N, max_rows_per_tile);
+  p.ldR = Nt;
+  const size_t rx_bytes = stk_rx_bytes(C, Nt);
+  return with_call_ws(p.want_sums ? rx_bytes + stk_part_bytes(C, N) : 0, "mile_stack_eval: workspace allocation failed (lower max_rows_per_tile)",
+                      st, [&](char *ws) -> int {
+    if (ws) { p.Rx = (double *)ws; p.part = (double *)(ws + rx_bytes); }
+    for (int64_t r0 = 0; r0 < N; r0 += Nt) {
+      p.r0 = r0; p.Nt = (int)std::min<int64_t>(Nt, N - r0);
+      HIP_TRY(mile_launch_stack_tile(p, st));
+    }
+    if (p.want_sums) HIP_TRY(mile_launch_stack_final(p, st));
+    return MILE_OK;
+  });
+}
+
+// mile_calibration / mile_calibration_stream: every check before any launch; rows in tiles whose per-chain sums and per-group
+// records fit half the evaluation budget, k_cal_accum per pass of draws, k_cal_rows + k_cal_part per tile, k_cal_final at the
+// end (mile_calib.h).
+struct CalOut { double *probs; int32_t *kept, *order, *set_size, *rank; double *totals, *bins; };
+// what is wrong with the shape, the levels or the outputs asked for, or null (pointers other than y and the outputs checked before)
+static const char *cal_bad_args(int32_t C, int64_t S, int64_t N, int32_t K, const double *coverages, int32_t Q, int32_t n_bins, const void *y,
+                                const CalOut &o) {
+  if (!o.probs && !o.kept && !o.order && !o.set_size && !o.rank && !o.totals && !o.bins) return "no output asked for";
+  if (C < 1 || C > 65535) return "C out of range (1 .. 65535)";
+  if (const char *m = bad_SN(S, N)) return m;
+  if (K < 2 || K > CAL_K_MAX) return "K out of range (2 .. 64)";
+  if (Q < 1 || Q > CAL_Q_MAX) return "Q out of range (1 .. 16)";
+  for (int i = 0; i < Q; ++i) {
+    if (!(coverages[i] > 0.0 && coverages[i] < 1.0)) return "coverages must lie strictly inside (0, 1)";
+    if (i > 0 && !(coverages[i] > coverages[i - 1])) return "coverages must be strictly increasing";
+  }
+  if (n_bins < 1 || n_bins > CAL_BINS_MAX) return "n_bins out of range (1 .. 64)";
+  if (!y && (o.rank || o.totals || o.bins)) return "rank, totals and bins need y";
+  if ((int64_t)C * S > 0x7fffffff) return "C * S above 2^31 - 1";
+  return nullptr;
+}
+
+static const int64_t CAL_STATE_TARGET = (int64_t)128 << 20;   // bytes of a tile's sums, counts and records; the pass's logits take as much
+// The plan of one call: rows per tile (whole k_cal_accum workgroups), draws per pass and the byte offset of every block of its
+// workspace: sums, counts, records, the blocks' partial sums.  own_raw: the streamed call, whose workspace begins with a pass's
+// logits [C][J][Nt][K], as many bytes as the tile's state; else raw is the caller's and its S draws are one pass.
+struct CalTilePlan { int64_t Nt, J; size_t sum, cnt, rec, part, total; };
+static CalTilePlan cal_tile_plan(int C, int K, int64_t S, int64_t N, int Q, int n_bins, bool own_raw, int64_t max_rows, int64_t max_draws) {
+  CalTilePlan t;
+  t.Nt = tile_rows(CAL_STATE_TARGET, (int64_t)cal_row_bytes(C, K), CAL_NT, max_rows, N);
+  t.J = own_raw ? pass_draws(CAL_STATE_TARGET, (int64_t)C * t.Nt * K * 4, max_draws, S) : S;
+  t.sum = own_raw ? r256((size_t)C * t.J * t.Nt * K * 4) : 0;
+  t.cnt = t.sum + cal_sum_bytes(C, K, t.Nt);
+  t.rec = t.cnt + cal_cnt_bytes(C, t.Nt);
+  t.part = t.rec + cal_rec_bytes(C, t.Nt);
+  t.total = t.part + cal_part_bytes(N, C + 1, cal_cols(Q, n_bins));
+  return t;
+}
+
+// the tiles of one call: `accum` folds all draws of the tile p describes (r0, Nt) into p.sum / p.cnt, zeroed here
+template <class Accum>
+static int cal_run(char *ws, const CalTilePlan &t, int C, int64_t N, int K, const void *y, const double *coverages, int Q, int n_bins,
+                   const CalOut &o, hipStream_t st, Accum accum) {
+  const int W = cal_cols(Q, n_bins);
+  const int64_t Nt = t.Nt;
+  CalParams p{};
+  p.C = C; p.K = K; p.Q = Q; p.n_bins = n_bins; p.N = N; p.y = (const int32_t *)y;
+  for (int i = 0; i < Q; ++i) p.cov[i] = coverages[i];
+  const bool reduce = y && (o.totals || o.bins);
+  p.sum = (double *)(ws + t.sum); p.cnt = (int32_t *)(ws + t.cnt); p.rec = reduce ? (CalRec *)(ws + t.rec) : nullptr; p.part = (double *)(ws + t.part);
+  p.B = cal_block_rows(N, C + 1, W); p.nblk = (N + p.B - 1) / p.B;
+  p.probs = o.probs; p.kept = o.kept; p.order = o.order; p.set_size = o.set_size; p.rank = o.rank; p.totals = o.totals; p.bins = o.bins;
+  if (reduce) HIP_TRY(hipMemsetAsync(p.part, 0, (size_t)(C + 1) * p.nblk * W * 8, st));
+  for (int64_t r0 = 0; r0 < N; r0 += Nt) {
+    p.r0 = r0; p.Nt = (int)std::min<int64_t>(Nt, N - r0);
+    HIP_TRY(hipMemsetAsync(p.sum, 0, (size_t)C * p.Nt * K * 8, st));
+    HIP_TRY(hipMemsetAsync(p.cnt, 0, (size_t)C * p.Nt * 4, st));
+    const int rc = accum(p);
+    if (rc != MILE_OK) return rc;
+    HIP_TRY(mile_launch_cal_rows(p, st));
+  }
+  if (reduce) HIP_TRY(mile_launch_cal_final(p, st));
+  return MILE_OK;
+}
+
+extern "C" int32_t mile_calibration(const float *raw, int32_t C, int64_t S, int64_t N, int32_t K, const void *y, const double *coverages,
+                                    int32_t Q, int32_t n_bins, double *probs, int32_t *kept, int32_t *order, int32_t *set_size, int32_t *rank,
+                                    double *totals, double *bins, void *stream) {
+  const CalOut o{probs, kept, order, set_size, rank, totals, bins};
+  if (!raw || !coverages) return bad("mile_calibration", "null argument");
+  if (const char *m = cal_bad_args(C, S, N, K, coverages, Q, n_bins, y, o)) return bad("mile_calibration", m);
+  hipStream_t st = (hipStream_t)stream;
+  const CalTilePlan t = cal_tile_plan(C, K, S, N, Q, n_bins, false, 0, 0);
+  return with_call_ws(t.total, "mile_calibration: workspace allocation failed", st, [&](char *ws) {
+    return cal_run(ws, t, C, N, K, y, coverages, Q, n_bins, o, st, [&](CalParams &p) -> int {
+      p.raw = raw + (size_t)p.r0 * K; p.cs = S; p.ld = N; p.J = (int)S;   // the caller's tensor, walked in place
+      HIP_TRY(mile_launch_cal_accum(p, st));
+      return MILE_OK;
+    });
+  });
+}
+
+extern "C" int64_t mile_calibration_stream_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N) {
+  if (!s || C < 1 || C > 65535 || bad_SN(S, N)) return -1;
+  const int K = eval_view(s).O;
+  if (eval_view(s).task != MILE_TASK_CLASSIFICATION || K < 2 || K > CAL_K_MAX) return -1;
+  return (int64_t)cal_tile_plan(C, K, S, N, CAL_Q_MAX, CAL_BINS_MAX, true, 0, 0).total;
+}
+
+extern "C" int32_t mile_calibration_stream(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, const void *y, int64_t N,
+                                           const double *coverages, int32_t Q, int32_t n_bins, double *probs, int32_t *kept, int32_t *order,
+                                           int32_t *set_size, int32_t *rank, double *totals, double *bins, int64_t max_draws_per_pass,
+                                           int64_t max_rows_per_tile, void *stream) {
+  const CalOut o{probs, kept, order, set_size, rank, totals, bins};
+  int K = 0;
+  const int rc0 = eval_args("mile_calibration_stream", s, !theta || !X || !coverages, bad_SN(S, N), [&]() -> const char * {
+    if (eval_view(s).task != MILE_TASK_CLASSIFICATION) return "needs a classification model";
+    K = eval_view(s).O;
+    if (const char *m = cal_bad_args(C, S, N, K, coverages, Q, n_bins, y, o)) return m;
+    return bad_caps(max_draws_per_pass, max_rows_per_tile);
+  });
+  if (rc0 != MILE_OK) return rc0;
+  hipStream_t st = (hipStream_t)stream;
+  const CalTilePlan t = cal_tile_plan(C, K, S, N, Q, n_bins, true, max_rows_per_tile, max_draws_per_pass);
+  char *ws;
+  const int rc2 = stream_ws("mile_calibration_stream", s, t.total, "lower max_draws_per_pass or max_rows_per_tile", ws);
+  if (rc2 != MILE_OK) return rc2;
+  float *raw = (float *)ws;
+  return cal_run(ws, t, C, N, K, y, coverages, Q, n_bins, o, st, [&](CalParams &p) -> int {
+    const int rc1 = stage_rows(s, (const float *)X + (size_t)p.r0 * eval_view(s).in_features, nullptr, p.Nt, st);
+    if (rc1 != MILE_OK) return rc1;
+    p.raw = raw; p.ld = p.Nt;
+    for (int64_t j0 = 0; j0 < S; j0 += t.J) {   // every (draw, row) forward once
+      p.J = (int)std::min<int64_t>(t.J, S - j0); p.cs = p.J;
+      const int rc = forward_chains(s, theta, C, S, j0, p.J, raw, st);
+      if (rc != MILE_OK) return rc;
+      HIP_TRY(mile_launch_cal_accum(p, st));
+    }
+    return MILE_OK;
+  });
+}
+
+// mile_lppd_stream: mile_pointwise_loglik's forward on the same draw window of every chain, a pass at a time, into the library's
+// workspace; k_lppd_accum folds the pass into the (m, s) state up to the next curve point, k_lppd_emit reduces the state there.
+// Every check before any launch (the curve points come to the host for theirs: a copy, no kernel).
+static bool lppd_shape_ok(int32_t C, int64_t N) { return C >= 1 && C <= LPPD_C_MAX && !bad_N(N); }
+
+extern "C" int64_t mile_lppd_stream_workspace(const mile_sampler *s, int32_t C, int64_t N) {
+  if (!s || !lppd_shape_ok(C, N)) return -1;
+  return (int64_t)lppd_state_bytes(C, N);
+}
+
+extern "C" int32_t mile_lppd_stream(mile_sampler *s, const float *theta, int32_t C, int32_t S, const void *X, const void *y, int64_t N,
+                                    const int32_t *curve_points, int32_t K, double *run_chain, double *run_ens, double *chain_lppd,
+                                    double *row_lppd, double *lppd, int64_t *dropped, int64_t max_draws_per_pass, void *stream) {
+  const int rc1 = eval_args("mile_lppd_stream", s, !theta || !X || !y, bad_SN(S, N), [&]() -> const char * {
+    if (!lppd_shape_ok(C, N)) return "C out of range (1 .. 65535)";
+    if (K < 0 || K > S) return "K out of range (0 .. S)";
+    if (K == 0 && (run_chain || run_ens)) return "K = 0 with a curve output";
+    if (K > 0 && !curve_points) return "null curve_points";
+    if (K > 0 && !run_chain && !run_ens) return "curve points without a curve output";
+    if (K == 0 && !chain_lppd && !row_lppd && !lppd && !dropped) return "no output asked for";
+    return bad_caps(max_draws_per_pass, 0);
+  });
+  if (rc1 != MILE_OK) return rc1;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(eval_view(s).device));   // the curve points' copy comes before the preamble the other streamed calls share
+  std::vector<int32_t> pts((size_t)K);
+  if (K > 0) {
+    HIP_TRY(hipMemcpyAsync(pts.data(), curve_points, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < K; ++i) {
+      if (pts[i] < 1 || pts[i] > S) return fail(MILE_ERR_INVALID, "mile_lppd_stream: curve point outside [1, S]");
+      if (i > 0 && pts[i] <= pts[i - 1]) return fail(MILE_ERR_INVALID, "mile_lppd_stream: curve points not strictly increasing");
+    }
+  }
+  const int64_t per_draw = (int64_t)C * N * 4;   // one draw of every chain
+  const int64_t J = pass_draws(EVAL_PASS_TARGET, per_draw, max_draws_per_pass, std::min<int64_t>(S, LPPD_J_MAX));
+  const size_t raw_bytes = r256((size_t)J * per_draw), st_bytes = lppd_state_bytes(C, N);
+  char *ws;
+  const int rc2 = stream_ws("mile_lppd_stream", s, raw_bytes + st_bytes, "lower max_draws_per_pass", ws);
+  if (rc2 != MILE_OK) return rc2;
+  const size_t cn = (size_t)C * (size_t)N;
+  LppdParams p{};
+  p.ll = (const float *)ws; p.C = C; p.N = (int)N; p.S = S; p.waves = lppd_waves(N);
+  p.state = (double2 *)(ws + raw_bytes);
+  p.cnt = (int32_t *)(p.state + cn);
+  p.part_ens = (double *)((char *)p.cnt + (cn * 4 + 7) / 8 * 8);
+  p.part_chain = p.part_ens + p.waves;
+  p.part_cnt = (long long *)(p.part_chain + (size_t)p.waves * C);
+  p.run_chain = run_chain; p.run_ens = run_ens; p.chain_lppd = chain_lppd; p.row_lppd = row_lppd; p.lppd = lppd;
+  p.dropped = (long long *)dropped;
+  const bool want_final = chain_lppd || row_lppd || lppd || dropped;
+  const int rc0 = stage_rows(s, (const float *)X, y, N, st);
+  if (rc0 != MILE_OK) return rc0;
+  p.fresh = 1;    // the first launch of k_lppd_accum starts every (chain, row) at (m, s) = (-inf, 0), cnt = 0
+  int next = 0;   // next curve point
+  for (int64_t j0 = 0; j0 < S; j0 += J) {
+    p.J = (int)std::min<int64_t>(J, S - j0);
+    const int rc = forward_chains(s, theta, C, S, j0, p.J, (float *)ws, st);
+    if (rc != MILE_OK) return rc;
+    int ja = 0;
+    while (ja < p.J) {   // split the pass at every curve point inside it
+      const int jb = next < K && pts[next] <= j0 + p.J ? (int)(pts[next] - j0) : p.J;
+      p.ja = ja; p.jb = jb;
+      HIP_TRY(mile_launch_lppd_accum(p, st));
+      p.fresh = 0;
+      if (next < K && pts[next] == j0 + jb) {
+        p.point = next++;
+        HIP_TRY(mile_launch_lppd_emit(p, want_final && j0 + jb == S, st));
+      }
+      ja = jb;
+    }
+  }
+  if (want_final && (K == 0 || pts[K - 1] != S)) {
+    p.point = -1;
+    HIP_TRY(mile_launch_lppd_emit(p, true, st));
+  }
+  return MILE_OK;
+}
+
+// mile_chain_diagnostics: every check before any launch; parameters in chunks that fit the workspace --------------------------
+static int diag_shape_ok(int32_t C, int32_t S, int64_t d) {
+  return C >= 1 && C <= DIAG_C_MAX && S >= DIAG_S_MIN && S <= DIAG_S_MAX && d >= 1 && d <= ((int64_t)1 << 40);
+}
+static const int64_t DIAG_WS_TARGET = (int64_t)256 << 20;   // workspace asked for: chunks of as many parameters as fit in it
+// an output of `what` whose pointer is null: the message, or null
+static const char *diag_null_output(uint32_t what, const float *wcv, const float *bcv, const float *ess, const float *crhat, const float *rhat) {
+  if (((what & MILE_DIAG_WCV) && !wcv) || ((what & MILE_DIAG_BCV) && !bcv) || ((what & MILE_DIAG_ESS) && !ess) ||
+      ((what & MILE_DIAG_CRHAT) && !crhat) || ((what & MILE_DIAG_RHAT) && !rhat))
+    return "null pointer for an output asked for";
+  return nullptr;
+}
+
+extern "C" int64_t mile_chain_diagnostics_workspace(int32_t C, int32_t S, int64_t d, uint32_t what) {
+  if (!diag_shape_ok(C, S, d)) return -1;
+  const int64_t per = diag_param_bytes(C, S, what);
+  const int64_t chunk = std::max<int64_t>(DIAG_TILE, DIAG_WS_TARGET / per / DIAG_TILE * DIAG_TILE);
+  return per * std::min<int64_t>(d, chunk);
+}
+
+extern "C" int32_t mile_chain_diagnostics(const float *samples, int32_t C, int32_t S, int64_t d, int32_t n_splits, uint32_t what,
+                                          float *wcv, float *bcv, float *ess, float *crhat, float *rhat, void *workspace,
+                                          int64_t workspace_bytes, void *stream) {
+  const uint32_t outs = MILE_DIAG_WCV | MILE_DIAG_BCV | MILE_DIAG_ESS | MILE_DIAG_CRHAT | MILE_DIAG_RHAT;
+  if (!samples) return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: null samples");
+  if (!diag_shape_ok(C, S, d)) return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: needs 1 <= C <= 65535, 4 <= S <= 4096, d >= 1");
+  if (n_splits < 1 || S % n_splits) return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: n_splits must divide S");
+  if (S / n_splits < 2) return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: fewer than 2 draws per split");
+  if (!(what & outs) || (what & ~(outs | MILE_DIAG_POOLED_INPUT))) return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: bad `what`");
+  if (const char *m = diag_null_output(what, wcv, bcv, ess, crhat, rhat)) return bad("mile_chain_diagnostics", m);
+  const bool pooled_in = what & MILE_DIAG_POOLED_INPUT;
+  if (pooled_in && (what & (MILE_DIAG_WCV | MILE_DIAG_BCV | MILE_DIAG_CRHAT)))
+    return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: wcv, bcv and crhat need the raw draws");
+  if (!pooled_in && (what & (MILE_DIAG_ESS | MILE_DIAG_RHAT)) && (int64_t)C * S > DIAG_POOL_MAX)
+    return fail(MILE_ERR_INVALID, "mile_chain_diagnostics: unsupported: C * S > 16384 pooled draws (pass pooled scores)");
+  const int64_t per = diag_param_bytes(C, S, what);
+  if (!workspace || workspace_bytes < per * std::min<int64_t>(d, DIAG_TILE))
+    return fail(MILE_ERR_STATE, "mile_chain_diagnostics: workspace too small");
+  int64_t chunk = std::min<int64_t>(d, workspace_bytes / per);
+  if (chunk < d) chunk = chunk / DIAG_TILE * DIAG_TILE;
+  chunk = std::min<int64_t>(chunk, 1 << 20);
+  DiagParams p{};
+  p.samples = samples; p.C = C; p.S = S; p.n_splits = n_splits; p.d = d; p.what = what;
+  p.wcv = wcv; p.bcv = bcv; p.ess = ess; p.crhat = crhat; p.rhat = rhat;
+  p.stat = (double *)workspace;                                      // [chunk][C][DIAG_NSTAT], then the fp32 planes
+  float *planes = (float *)((char *)workspace + chunk * C * DIAG_NSTAT * 8);
+  p.raw = pooled_in ? nullptr : planes;
+  p.z = pooled_in ? planes : planes + chunk * C * S;
+  for (int64_t p0 = 0; p0 < d; p0 += chunk) {
+    p.p0 = p0;
+    p.P = (int)std::min<int64_t>(chunk, d - p0);
+    HIP_TRY(mile_launch_diag(p, (hipStream_t)stream));
+  }
+  return MILE_OK;
+}
+
+// mile_function_diagnostics: every check before any launch; rows in tiles whose raw block, two [P][C][S] planes and stat block fit
+// the evaluation budget; per tile the forward, k_fdiag_pack, k_fdiag_lp and mile_chain_diagnostics' launches on the tile's columns
+// (mile_fdiag.h).  The plan of one call: the head's width, rows per tile, draws per pass and the byte offset of every block.
+struct FdiagPlan { int O, Q; int64_t D, NQ, M, nt, chunk; size_t plane, z, stat, acc, part, total; };
+static FdiagPlan fdiag_plan(int O, int C, int S, int64_t N, bool with_y, int64_t max_rows, int64_t max_draws) {
+  FdiagPlan t;
+  t.O = O; t.Q = t.O + (with_y ? 1 : 0);
+  t.D = (int64_t)C * S; t.NQ = N * t.Q; t.M = t.NQ + (with_y ? 1 : 0);
+  const int64_t per_row = t.D * t.O * 4 + t.Q * diag_param_bytes(C, S, 0);
+  int64_t cap = FDIAG_P_MAX / t.Q;
+  if (max_rows > 0 && max_rows < cap) cap = max_rows;
+  t.nt = tile_rows(EVAL_PASS_TARGET, per_row, 1, cap, N);
+  t.chunk = pass_draws(EVAL_PASS_TARGET, t.nt * t.O * 4, max_draws, t.D);
+  const size_t plane = r256((size_t)t.nt * t.Q * t.D * 4);
+  t.plane = r256((size_t)t.D * t.nt * t.O * 4);
+  t.z = t.plane + plane;
+  t.stat = t.z + plane;
+  t.acc = t.stat + r256((size_t)t.nt * t.Q * C * DIAG_NSTAT * 8);
+  t.part = t.acc + r256((size_t)t.D * 8);
+  t.total = t.part + r256(fdiag_part_bytes(C, t.NQ));
+  return t;
+}
+static const char *fdiag_bad_shape(int32_t C, int32_t S, int64_t N) {
+  return !diag_shape_ok(C, S, 1) ? "needs 1 <= C <= 65535 and 4 <= S <= 4096" : bad_N(N);
+}
+
+extern "C" int64_t mile_function_diagnostics_workspace(const mile_sampler *s, int32_t C, int32_t S, int64_t N, int32_t with_y) {
+  if (!s || fdiag_bad_shape(C, S, N) || eval_view(s).O > FDIAG_O_MAX) return -1;
+  return (int64_t)fdiag_plan(eval_view(s).O, C, S, N, with_y != 0, 0, 0).total;
+}
+
+extern "C" int32_t mile_function_diagnostics(mile_sampler *s, const float *theta, int32_t C, int32_t S, const void *X, const void *y, int64_t N,
+                                             int32_t n_splits, uint32_t what, float *wcv, float *bcv, float *ess, float *crhat, float *rhat,
+                                             float *columns, double *loglik_sum, double *summary, double *chain_summary,
+                                             int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
+  const uint32_t outs = MILE_DIAG_WCV | MILE_DIAG_BCV | MILE_DIAG_ESS | MILE_DIAG_CRHAT | MILE_DIAG_RHAT;
+  const uint32_t summed = MILE_DIAG_ESS | MILE_DIAG_CRHAT | MILE_DIAG_RHAT;
+  const int rc0 = eval_args("mile_function_diagnostics", s, !theta || !X, fdiag_bad_shape(C, S, N), [&]() -> const char * {
+    if (eval_view(s).O > FDIAG_O_MAX) return "more than 64 head outputs";
+    if (n_splits < 1 || S % n_splits) return "n_splits must divide S";
+    if (S / n_splits < 2) return "fewer than 2 draws per split";
+    if (what & MILE_DIAG_POOLED_INPUT) return "MILE_DIAG_POOLED_INPUT: the columns are formed here, there is no input that could hold scores";
+    if (what & ~outs) return "bad `what`";
+    if (!what && !columns && !loglik_sum) return "no output asked for";
+    if (const char *m = diag_null_output(what, wcv, bcv, ess, crhat, rhat)) return m;
+    if ((!(what & MILE_DIAG_WCV) && wcv) || (!(what & MILE_DIAG_BCV) && bcv) || (!(what & MILE_DIAG_ESS) && ess) ||
+        (!(what & MILE_DIAG_CRHAT) && crhat) || (!(what & MILE_DIAG_RHAT) && rhat))
+      return "an output whose statistic is not in `what`";
+    if ((summary || chain_summary) && (what & summed) != summed) return "summary and chain_summary need ESS, CRHAT and RHAT in `what`";
+    if (loglik_sum && !y) return "loglik_sum needs y";
+    if ((what & (MILE_DIAG_ESS | MILE_DIAG_RHAT)) && (int64_t)C * S > DIAG_POOL_MAX)
+      return "unsupported: C * S > 16384 pooled draws (take WCV, BCV, CRHAT and `columns`, and rank those outside)";
+    return bad_caps(max_draws_per_pass, max_rows_per_tile);
+  });
+  if (rc0 != MILE_OK) return rc0;
+  hipStream_t st = (hipStream_t)stream;
+  const FdiagPlan t = fdiag_plan(eval_view(s).O, C, S, N, y != nullptr, max_rows_per_tile, max_draws_per_pass);
+  char *ws;
+  const int rc2 = stream_ws("mile_function_diagnostics", s, t.total, "lower max_rows_per_tile", ws);
+  if (rc2 != MILE_OK) return rc2;
+  FdiagParams f{};
+  f.out = (const float *)ws; f.D = (int)t.D; f.O = t.O; f.Q = t.Q; f.task = eval_view(s).task;
+  f.raw = (float *)(ws + t.plane); f.acc = (double *)(ws + t.acc);
+  DiagParams p{};
+  p.C = C; p.S = S; p.n_splits = n_splits; p.d = t.M; p.what = what;   // samples stays null: k_fdiag_pack fills the raw plane
+  p.raw = f.raw; p.z = (float *)(ws + t.z); p.stat = (double *)(ws + t.stat);
+  p.wcv = wcv; p.bcv = bcv; p.ess = ess; p.crhat = crhat; p.rhat = rhat;
+  if (y) HIP_TRY(hipMemsetAsync(f.acc, 0, (size_t)t.D * 8, st));
+  auto source = stream_tiles(s, theta, t.D, t.chunk, X, ws, st);         // the raw block [D][nt][O] at the start of the workspace
+  for (int64_t r0 = 0; r0 < N; r0 += t.nt) {
+    const int nt = (int)std::min<int64_t>(t.nt, N - r0);
+    Tile tile;
+    const int rc1 = source(r0, nt, tile);
+    if (rc1 != MILE_OK) return rc1;
+    f.out = tile.at; f.nt = nt; f.y = y ? (const char *)y + (size_t)r0 * 4 : nullptr; f.lcol = nullptr;
+    HIP_TRY(mile_launch_fdiag_pack(f, st));
+    if (y) HIP_TRY(mile_launch_fdiag_lp(f, st));
+    const size_t m0 = (size_t)r0 * t.Q;
+    if (columns) HIP_TRY(hipMemcpyAsync(columns + m0 * t.D, f.raw, (size_t)nt * t.Q * t.D * 4, hipMemcpyDeviceToDevice, st));
+    if (what) {
+      p.p0 = (long long)m0; p.P = nt * t.Q;
+      HIP_TRY(mile_launch_diag(p, st));
+    }
+  }
+  if (y) {                                                              // the L column: one chunk of its own
+    f.nt = 0; f.lcol = f.raw;
+    HIP_TRY(mile_launch_fdiag_lp(f, st));
+    if (columns) HIP_TRY(hipMemcpyAsync(columns + (size_t)t.NQ * t.D, f.raw, (size_t)t.D * 4, hipMemcpyDeviceToDevice, st));
+    if (loglik_sum) HIP_TRY(hipMemcpyAsync(loglik_sum, f.acc, (size_t)t.D * 8, hipMemcpyDeviceToDevice, st));
+    if (what) {
+      p.p0 = t.NQ; p.P = 1;
+      HIP_TRY(mile_launch_diag(p, st));
+    }
+  }
+  if (summary || chain_summary) {
+    FdiagSumParams q{};
+    q.rhat = rhat; q.crhat = crhat; q.ess = ess; q.M = t.M; q.NQ = t.NQ; q.C = C; q.B = fdiag_sum_blocks(C, t.NQ);
+    q.part = (FdiagPart *)(ws + t.part); q.summary = summary; q.chain_summary = chain_summary;
+    HIP_TRY(mile_launch_fdiag_summary(q, st));
+  }
+  return MILE_OK;
+}

@@ -1,7 +1,7 @@
 // Function-space chain diagnostics (mile_function_diagnostics): the statistics of mile_chain_diagnostics, not of the
 // parameters but of what each draw PREDICTS on every row -- the head outputs (mu, log sigma, or the softmax probabilities),
 // the row's log-likelihood, and the draw's summed log-likelihood L.  Kernels in mile_fdiag.hip; the entry point (argument
-// checks, row tiles) in mile_hip.hip.
+// checks, row tiles) in mile_eval.hip.
 //
 // Columns: with O the width of the last layer and Q = O + (y ? 1 : 0), column m = n * Q + q is quantity q of row n; with y
 // there is one last column m = N * Q, the draw's L.  One tile of nt rows goes through

@@ -3,7 +3,7 @@
 // the Pareto-smoothed importance-sampling leave-one-out density and the Pareto shape khat of its weights (Vehtari, Gelman &
 // Gabry 2017; Vehtari et al. 2024; the fit of Zhang & Stephens 2009).  include/mile_hip.h states the definition.  Kernels in
 // mile_loo.hip; the entry points (argument checks, the row tiles and the passes over the draws through
-// mile_pointwise_loglik's forward) in mile_hip.hip.
+// mile_pointwise_loglik's forward) in mile_eval.hip.
 //
 // One tile of Nt rows goes through two launches:
 //   k_loo_pack  grid (ceil(Nt / 32), slices): ll [S][ld] -> pk [Nt][S], contiguous per row, through a 32 x 32 LDS tile (both

@@ -1,7 +1,7 @@
 // Streamed LPPD (mile_lppd_stream): the log posterior predictive density of C chains x S draws on N rows, of each chain, of
 // each row, and both as curves over the number of draws, reduced on the device without a [C, S, N] tensor.  Kernels in
 // mile_lppd.hip; the entry point (argument checks, the passes over the draws through mile_pointwise_loglik's forward) in
-// mile_hip.hip.
+// mile_eval.hip.
 //
 // State per (chain, row): a streaming log-sum-exp (m, s) -- the running maximum m and s = sum exp(l - m) over the draws
 // folded so far -- both fp64, [C][N] pairs of 16 bytes, plus cnt[C][N], the draws folded.  Every figure is written in terms

@@ -1,6 +1,6 @@
 // Posterior-predictive moments (mile_predict_moments): the Bayesian-model-average prediction of S draws on N rows, reduced
 // over the draw axis on the device.  Kernels in mile_moments.hip; the entry point (argument checks, the passes over the
-// draws through mile_predict's forward) in mile_hip.hip.
+// draws through mile_predict's forward) in mile_eval.hip.
 //
 // The forward writes one pass of raw outputs [Sc][N][O] into the library's workspace; then
 //   k_moments_accum<TASK>   grid (ceil(N / 64), slices): a thread per row n (the contiguous axis of [Sc][N][O], so a wave reads

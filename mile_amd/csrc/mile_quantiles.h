@@ -1,7 +1,7 @@
 // Exact predictive quantiles and PIT of the ensemble (mile_mixture_quantiles, mile_predict_quantiles): the equal-weight
 // mixture of the S draws' Normals on every row, F_n(t) = mean_s Phi((t - mu_sn) / sigma_sn), inverted at Q levels and
 // evaluated at y_n.  Kernels in mile_quantiles.hip; the entry points (argument checks, the row tiles and the passes over the
-// draws through mile_predict's forward) in mile_hip.hip.
+// draws through mile_predict's forward) in mile_eval.hip.
 //
 // One tile of Nt rows goes through two launches:
 //   k_qnt_pack   grid (ceil(Nt / 32), slices): raw [S][ld][2] -> pk [Nt][S] pairs, contiguous per row, through a 32 x 32 LDS

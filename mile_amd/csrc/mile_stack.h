@@ -1,7 +1,7 @@
 // Stacking of non-mixing chains (mile_stack_eval): the score of the weighted mixture of the chains' pointwise predictive
 // densities, its gradient in the weights and the Gram matrix of the responsibilities (the negative Hessian), from
 // lpd [C, N] fp64 and w [C] fp64 (Yao, Vehtari, Simpson & Gelman 2018).  include/mile_hip.h states the definition.  Kernels in
-// mile_stack.hip; the entry point (argument checks, the row tiles) in mile_hip.hip.
+// mile_stack.hip; the entry point (argument checks, the row tiles) in mile_eval.hip.
 //
 // The responsibilities of a tile of Nt rows are written as Rx [Cx][Nt] fp64, Cx = C + 2: rows 0 .. C-1 hold R_cn, row C holds
 // 1 for a used row and row C + 1 its row_score; a row left out holds 0 in all of them.  Every sum over the rows is then an

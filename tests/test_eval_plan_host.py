@@ -1,9 +1,11 @@
 """mile_eval_plan.h on the host: the one tile_rows and the one pass_draws against the formulas they replaced, restated here
-literally as the oracle, in a program of its own built with the address and undefined-behaviour sanitizers.
+literally as the oracle, in a program of its own built with the address and undefined-behaviour sanitizers.  Below that, the
+boundary between mile_hip.hip and the evaluation layer (mile_eval.hip behind mile_eval_handle.h), read from the source.
 
 The formulas are integer arithmetic, so the bound is equality, at every point of the grid: S in {1, 2, 31, 32, 33, 12000, 2^20,
 2^20 + 1, 2^31 - 1}, N in {1, 31, 32, 33, 301, 1052, 10^5, 2^30 - 1}, C in {1, 3, 128, 1024, 65535} and the caller's cap in {0, 1,
 31, 32, 33, 10^9}."""
+import re
 import shutil
 import subprocess
 from pathlib import Path
@@ -108,3 +110,46 @@ def test_tile_rows_and_pass_draws_are_the_formulas_they_replaced_under_sanitizer
                     '-I', str(ROOT / 'mile_amd' / 'csrc'), str(tmp_path / 'main.cpp'), '-o', str(exe)], check=True)
     res = subprocess.run([str(exe)], capture_output=True, text=True)
     assert res.returncode == 0 and 'evaluation sizing ok' in res.stdout and 'runtime error' not in res.stderr, (res.stdout[-2000:], res.stderr[-2000:])
+
+
+# ---- the boundary between the sampler's translation unit and the evaluation layer, read from the source --------------------
+CSRC = ROOT / 'mile_amd' / 'csrc'
+MOVED = ['mile_pointwise_loglik', 'mile_predict', 'mile_predict_moments_width', 'mile_predict_moments', 'mile_mixture_quantiles',
+         'mile_predict_quantiles_workspace', 'mile_predict_quantiles', 'mile_debug_quantile_sweeps', 'mile_psis_loo',
+         'mile_loo_stream_workspace', 'mile_loo_stream', 'mile_chain_loo_stream_workspace', 'mile_chain_loo_stream', 'mile_mixture_crps',
+         'mile_crps_stream_workspace', 'mile_crps_stream', 'mile_stack_eval', 'mile_calibration', 'mile_calibration_stream_workspace',
+         'mile_calibration_stream', 'mile_lppd_stream_workspace', 'mile_lppd_stream', 'mile_chain_diagnostics_workspace',
+         'mile_chain_diagnostics', 'mile_function_diagnostics_workspace', 'mile_function_diagnostics']
+
+
+def _code(name):
+    """The file without its // comments (none of these files has a string with // in it)."""
+    return re.sub(r'//[^\n]*', '', (CSRC / name).read_text())
+
+
+def test_only_the_samplers_unit_defines_the_handle():
+    owners = [p.name for p in sorted(CSRC.iterdir()) if p.suffix in ('.hip', '.h', '.inc') and 'struct mile_sampler {' in p.read_text()]
+    assert owners == ['mile_hip.hip']
+
+
+def test_the_evaluation_layer_includes_no_kernel_header_and_launches_nothing():
+    for name in ('mile_eval.hip', 'mile_eval_handle.h'):
+        included = re.findall(r'#include\s+"([^"]+)"', (CSRC / name).read_text())
+        assert included, name
+        banned = [h for h in included if re.search(r'mile_grad_|mile_predict\.h|mile_device\.h|mile_update\.h|mile_nuts\.h', h)]
+        assert not banned, (name, banned)
+    ev = _code('mile_eval.hip')
+    assert '__global__' not in ev and '<<<' not in ev
+    assert '"mile_eval_handle.h"' in ev and 's->' not in ev   # the handle is an incomplete type there: nothing of it is read
+
+
+def test_every_evaluation_entry_point_moved_out_of_the_samplers_unit():
+    hip, ev = _code('mile_hip.hip'), _code('mile_eval.hip')
+    for fn in MOVED:
+        definition = re.compile(r'\b(?:int32_t|int64_t)\s+' + fn + r'\s*\(')
+        assert not definition.search(hip), fn
+        assert len(definition.findall(ev)) == 1, fn
+    for helper in ('forward_draws', 'forward_chains', 'evaluate_rows', 'eval_args', 'with_call_ws'):
+        assert not re.search(r'\b' + helper + r'\s*\(', hip), helper
+    for stays in ('stage_rows', 'eval_forward', 'reserve_eval_ws', 'k_pad_x<<<'):
+        assert stays in hip, stays

@@ -2,11 +2,11 @@
 schedule, and the fp64 reference of one call (no torch, no GPU; tests/test_update_schedule_host.py proves the table on the CPU,
 tests/test_gpu_update_schedule.py runs it).
 
-The path (mile_amd/csrc/mile_hip.hip): mile_step (2995-3047) and mile_tune (3049-3136) build each launch's UpdParams with
-upd_start / upd_mid / upd_record / chain_start (1806-1830) and hand it to launch_update (938-955) behind a gradient, or to the
-gradient launch itself where fuse_ok (979-986) lets k_grad_w64 run it as its epilogue.  launch_update picks k_update_fast
-(launch_update_al, 871-899: NK, nt, the compile-time kind of upd_kind, MAXT), k_update_big (launch_update_big, 901-930),
-k_update_seg + k_update_seg_scalars or the two-pass k_update<false>; row_align (853-859) picks the vector width AL.  All of them
+The path (mile_amd/csrc/mile_hip.hip): mile_step and mile_tune build each launch's UpdParams with
+upd_start / upd_mid / upd_record / chain_start and hand it to launch_update behind a gradient, or to the
+gradient launch itself where fuse_ok lets k_grad_w64 run it as its epilogue.  launch_update picks k_update_fast
+(launch_update_al: NK, nt, the compile-time kind of upd_kind, MAXT), k_update_big (launch_update_big),
+k_update_seg + k_update_seg_scalars or the two-pass k_update<false>; row_align picks the vector width AL.  All of them
 but the two-pass and the segment kernels run upd_fast_body (mile_update.h:560-904).  The epilogue form of that body is compiled
 only under -DMILE_W64_EPILOGUE, which the build does not pass: its cells are listed as unreachable and its schedule is restated
 for a library that has it (launches(case, epilogue=True)).  k_update<true> needs (d + 3) / 4 <= 4096
@@ -87,12 +87,12 @@ def dim(case):
 # ---- the schedule ------------------------------------------------------------------------------------------------------------------
 
 def ptr_align(off):
-    """Alignment in floats of a pointer `off` floats behind a 16-byte aligned address (mile_hip.hip:846-849)."""
+    """Alignment in floats of a pointer `off` floats behind a 16-byte aligned address (ptr_align in mile_hip.hip)."""
     return 4 if off % 4 == 0 else (2 if off % 2 == 0 else 1)
 
 
 def row_align(d, ptrs):
-    """(AL, why) of row_align (853-859): the width d allows, lowered by any non-null row pointer; ptrs: name -> offset."""
+    """(AL, why) of row_align: the width d allows, lowered by any non-null row pointer; ptrs: name -> offset."""
     al, why = (4, 'd % 4 == 0') if d % 4 == 0 else ((2, 'd % 2 == 0') if d % 2 == 0 else (1, 'd odd'))
     for off in ptrs.values():
         if ptr_align(off) < al:
@@ -125,7 +125,7 @@ def fuse_nk(nh):
 
 
 def fuse_ok(case, u, epilogue=None):
-    """fuse_ok (979-986) on the probe `u`; `epilogue`: MILE_W64_EPILOGUE_ON, the build's unless given."""
+    """fuse_ok on the probe `u`; `epilogue`: MILE_W64_EPILOGUE_ON, the build's unless given."""
     if not (EPILOGUE_ON if epilogue is None else epilogue):
         return False
     if case.kernel != W64X3 or u['sdc'] or 'u_rec' in u['ptrs']:
@@ -163,7 +163,7 @@ def _reasons(u, kernel):
 
 
 def classify(case, u, fused):
-    """The launch dict of UpdParams `u`: launch_update (938-955) or the epilogue of the gradient launch."""
+    """The launch dict of UpdParams `u`: launch_update or the epilogue of the gradient launch."""
     d, E = u['d'], case.E
     nqf, ntail = d >> 2, d & 3
     env = set(case.env)
@@ -255,7 +255,7 @@ def _upd_record(base, case, i):
 
 
 def launches(case, epilogue=None):
-    """Every update launch of the call, in order (mile_step 2995-3047, mile_tune 3049-3136).  The pointer offsets: the caller's
+    """Every update launch of the call, in order (mile_step, mile_tune).  The pointer offsets: the caller's
     state `case.off` floats behind a 16-byte boundary, everything the library or the engine allocates on one.  `epilogue`: what
     the schedule would be in a library built with -DMILE_W64_EPILOGUE (the default build: EPILOGUE_ON)."""
     d, n, env = dim(case), case.n_steps, set(case.env)
@@ -370,10 +370,10 @@ def _enumerate_cells():
 CELLS = _enumerate_cells()
 
 # cell -> the line that makes it unreachable
-_NOT_REC = 'mile_hip.hip:1807: chain_start adds UPD_OB only under O-step-O, so the chained word is not the kind\'s (1791-1792)'
+_NOT_REC = 'mile_hip.hip, chain_start: it adds UPD_OB only under O-step-O, so the chained word is not the kind\'s (static_asserts on UPD_KIND_REC / UPD_KIND_TUNE)'
 _NOT_LAPLACE = 'mile_update.h:986: upd_kind returns -1 unless the prior is Normal'
 _NO_EPILOGUE = ('mile_grad_w64.h:62-66 with mile_amd/_build.py: the library is built without -DMILE_W64_EPILOGUE, so MILE_W64_EPILOGUE_ON '
-                'is 0 and fuse_ok (mile_hip.hip:980) refuses every launch; the body is not in the library')
+                'is 0 and fuse_ok (mile_hip.hip) refuses every launch; the body is not in the library')
 UNREACHABLE = {('kind', 'REC', 'Normal', 'step-O'): _NOT_REC, ('kind', 'TUNE', 'Normal', 'step-O'): _NOT_REC}
 UNREACHABLE.update({('kind', k, 'Laplace', r): _NOT_LAPLACE for k in ('MID', 'REC', 'TUNE') for r in REFRESH})
 UNREACHABLE.update({c: _NO_EPILOGUE for c in CELLS if c[0] == 'epilogue' or c[:2] in (('kernel', 'epilogue'), ('one step', 'epilogue'))})
