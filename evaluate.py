@@ -3,7 +3,7 @@
 mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
 src/inference/metrics.py:247-312):
 
-    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--function-diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo] [--stacking]
+    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--function-diagnostics [N_SPLITS]] [--canonical-diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo] [--stacking]
 
 Reloads config.yaml and the samples/<chain>/sample_<n>.npz files, rebuilds the data split with the same
 seed, evaluates all C x S samples on the split in one device pass and writes metrics.json next to them.
@@ -91,15 +91,51 @@ def diagnostic_metrics(samples, spec, n_splits, device):
         raise SystemExit('--diagnostics: no chain with finite samples')
     res = chain_diagnostics(torch.from_numpy(ok).to(device), n_splits)
     arr = {k: v.detach().cpu().numpy() for k, v in res.items()}
-    out = {'diag_n_splits': int(n_splits),
-           'diag_ess_min': float(np.nanmin(arr['ess'])), 'diag_ess_median': float(np.nanmedian(arr['ess'])),
-           'diag_crhat_median': float(np.nanmedian(arr['crhat'])), 'diag_crhat_max': float(np.nanmax(arr['crhat'])),
-           'diag_rhat_median': float(np.nanmedian(arr['rhat'])), 'diag_rhat_max': float(np.nanmax(arr['rhat'])),
-           'diag_wcv_median': float(np.nanmedian(arr['wcv'])), 'diag_bcv_median': float(np.nanmedian(arr['bcv']))}
+    return diagnostic_keys('diag', arr, spec, n_splits), arr
+
+
+def diagnostic_keys(prefix, arr, spec, n_splits):
+    """The metrics.json keys of the five per-parameter arrays ``arr`` under ``prefix`` (diag: the draws as sampled; cdiag: their
+    canonical ordering)."""
+    out = {f'{prefix}_n_splits': int(n_splits),
+           f'{prefix}_ess_min': float(np.nanmin(arr['ess'])), f'{prefix}_ess_median': float(np.nanmedian(arr['ess'])),
+           f'{prefix}_crhat_median': float(np.nanmedian(arr['crhat'])), f'{prefix}_crhat_max': float(np.nanmax(arr['crhat'])),
+           f'{prefix}_rhat_median': float(np.nanmedian(arr['rhat'])), f'{prefix}_rhat_max': float(np.nanmax(arr['rhat'])),
+           f'{prefix}_wcv_median': float(np.nanmedian(arr['wcv'])), f'{prefix}_bcv_median': float(np.nanmedian(arr['bcv']))}
     # per-layer means, keyed by leaf name as plot_effective_sample_size / plot_split_chain_r_hat return them
     for key in ('ess', 'crhat'):
-        out[f'diag_{key}_layer_mean'] = {name: float(np.mean(arr[key][:, off:off + int(np.prod(shape))]))
-                                         for name, off, shape in spec.leaves()}
+        out[f'{prefix}_{key}_layer_mean'] = {name: float(np.mean(arr[key][:, off:off + int(np.prod(shape))]))
+                                             for name, off, shape in spec.leaves()}
+    return out
+
+
+def canonical_refusal(model, activation, sign):
+    """Why --canonical-diagnostics cannot run on an experiment of ``model`` with ``activation``, or None."""
+    if model != 'FCN':
+        return (f'--canonical-diagnostics: the canonical hidden-unit ordering is defined for FCN experiments only; this one is '
+                f'{model} (--function-diagnostics compares chains of any model)')
+    if sign and activation != 'tanh':
+        return (f'--canonical-sign: fixing the signs of the hidden units needs an odd activation (tanh); this net uses '
+                f'{activation}, whose units have no sign symmetry to remove')
+    return None
+
+
+def canonical_diagnostic_metrics(samples, spec, n_splits, key, sign, device):
+    """--canonical-diagnostics: the statistics of --diagnostics on the canonical hidden-unit ordering of the finite chains
+    (mile_amd.metrics.canonical_diagnostics: mile_canonicalize_fcn, then mile_chain_diagnostics, on the device), and how often the
+    order of each hidden layer changes from one draw to the next.  samples [C, S, d] (host).  Returns the cdiag_* keys of
+    metrics.json and the arrays of canonical_diagnostics.npz."""
+    from mile_amd.metrics import canonical_diagnostics
+    fin = np.isfinite(samples).all(axis=(1, 2))
+    ok = np.ascontiguousarray(samples[fin])
+    if ok.shape[0] == 0:
+        raise SystemExit('--canonical-diagnostics: no chain with finite samples')
+    res = canonical_diagnostics(spec, torch.from_numpy(ok).to(device), n_splits, key=key, sign=sign)
+    arr = {k: v.detach().cpu().numpy() for k, v in res.items()}
+    out = diagnostic_keys('cdiag', arr, spec, n_splits)
+    out['cdiag_key'], out['cdiag_sign'] = key, bool(sign)
+    for l in range(arr['switches'].shape[1]):
+        out[f'cdiag_switch_rate_layer{l}'] = float(np.mean(arr['switches'][:, l] / max(ok.shape[1] - 1, 1)))
     return out, arr
 
 
@@ -307,6 +343,22 @@ def build_parser():
                          'lengths are refused with the library\'s message (no torch fall-back, unlike --diagnostics).  fdiag_* keys '
                          'in metrics.json (fdiag_rhat_max, fdiag_ess_min, fdiag_r_eff_mean, per-quantity and per-chain figures) and '
                          'wcv, bcv, rhat, ess, crhat, loglik_sum, chain_summary, Q in function_diagnostics.npz')
+    ap.add_argument('--canonical-diagnostics', type=int, nargs='?', const=2, default=None, metavar='N_SPLITS',
+                    help='FCN experiments: the statistics of --diagnostics on the CANONICAL hidden-unit ordering of every draw of '
+                         'the finite chains (mile_canonicalize_fcn, then mile_chain_diagnostics, on the device): the units of each '
+                         'hidden layer sorted by --canonical-key, which removes the permutation symmetry that makes chains in '
+                         'permuted copies of one mode fail every per-parameter check.  cdiag_* keys in metrics.json mirror the '
+                         'diag_* keys, plus cdiag_key, cdiag_sign and cdiag_switch_rate_layer<l> (the share of draws whose order of '
+                         'hidden layer l differs from the draw before: ordering by a key gives order statistics, not an alignment to '
+                         'a reference mode, and a high rate says the key does not separate the units of this posterior); wcv, bcv, '
+                         'rhat, ess, crhat, switches in canonical_diagnostics.npz.  No ReLU rescaling, no sigmoid reflection; hidden '
+                         'widths above 1024 run in plain torch')
+    ap.add_argument('--canonical-key', choices=['bias', 'norm'], default='bias',
+                    help='--canonical-diagnostics orders the hidden units by their bias (default) or by the squared norm of their '
+                         'bias and incoming weights')
+    ap.add_argument('--canonical-sign', action='store_true',
+                    help='--canonical-diagnostics on a tanh net: flip every hidden unit whose bias is negative first (the sign '
+                         'symmetry of an odd activation)')
     ap.add_argument('--moments', action='store_true',
                     help='posterior-predictive moments of all draws on the split, reduced on the device (mile_predict_moments): '
                          'moments_* keys in metrics.json and the per-row arrays in moments.npz (regression: mean, epistemic_var, '
@@ -386,6 +438,9 @@ def main():
         raise SystemExit(crps_refusal(cfg.data.task, 1))
     if args.crps and args.crps_max_draws < 1:
         raise SystemExit('--crps-max-draws: at least 1')
+    why = canonical_refusal(cfg.model.model, getattr(cfg.model, 'activation', None), args.canonical_sign)
+    if args.canonical_diagnostics is not None and why:
+        raise SystemExit(why)
     tr.build_model(cfg)
     spec = tr.prob_model.spec
     samples = load_samples_from_dir(exp / cfg.training.sampler._dir_name, spec)       # [C, S, d]
@@ -483,6 +538,11 @@ def main():
         keys, arrays = function_diagnostic_metrics(eng, samples, x, np.ascontiguousarray(y), cfg.data.task, args.function_diagnostics)
         out.update(keys)
         np.savez(exp / 'function_diagnostics.npz', **arrays)
+    if args.canonical_diagnostics is not None:
+        keys, arrays = canonical_diagnostic_metrics(samples, spec, args.canonical_diagnostics, args.canonical_key, args.canonical_sign,
+                                                    args.device)
+        out.update(keys)
+        np.savez(exp / 'canonical_diagnostics.npz', **arrays)
     if args.moments:
         mom, dropped = eng.predict_moments(torch.from_numpy(samples), torch.from_numpy(x), return_dropped=True)
         keys, arrays = moment_metrics(mom, dropped, np.ascontiguousarray(y), cfg.data.task)

@@ -669,6 +669,48 @@ int32_t mile_chain_diagnostics(const float *samples, int32_t C, int32_t S, int64
                                int64_t workspace_bytes, void *stream);
 int64_t mile_chain_diagnostics_workspace(int32_t C, int32_t S, int64_t d, uint32_t what);
 
+/* How mile_canonicalize_fcn orders the hidden units (`how`): one key, and optionally the sign fix. */
+#define MILE_CANON_KEY_BIAS 0u
+#define MILE_CANON_KEY_NORM 1u
+#define MILE_CANON_SIGN     2u
+#define MILE_CANON_WIDTH_MAX 1024
+
+/* Canonical hidden-unit ordering of FCN draws: every draw is replaced by one representative of its orbit under the
+ * permutations of the hidden units of each layer (and, with MILE_CANON_SIGN on a tanh net, their sign flips), so that
+ * per-parameter statistics (mile_chain_diagnostics, trace and histogram plots, posterior summaries) of chains that sit in
+ * permuted copies of one mode agree.  Needs no mile_sampler; launches on the current device.
+ * theta [M][d] fp32 (device) holds draws of the MILE_MODEL_FCN `spec` in the library's full layout (mile_param_offsets).
+ * Hidden layers are l = 0 .. n_layers - 2 with widths W_l; the output layer and the inputs never move.  H = sum_l W_l
+ * (mile_canonical_hidden); hidden layer l owns [o_l, o_l + W_l) of the H axis.
+ *   sign  (MILE_CANON_SIGN, MILE_ACT_TANH only) s_l[j] = -1 iff bias_l[j] < 0, else +1: -0.0, +0.0 and NaN are not flipped.
+ *   key   MILE_CANON_KEY_BIAS: s_l[j] * bias_l[j], compared as fp32.  MILE_CANON_KEY_NORM: bias^2 + sum_i kernel_l[i][j]^2 in
+ *         fp64, the terms added one after another, bias first, then i ascending (squares of fp32 values are exact in fp64, so
+ *         the key is reproducible bit for bit).
+ *   order ascending key; equal keys (-0.0 == +0.0, duplicated units) keep their index order; NaN keys come after every
+ *         number, among themselves in index order; +-inf sort as numbers.  p_l[j'] is the original index of the unit that
+ *         lands at position j'.
+ *   out [M][d] (device, required, not overlapping theta):
+ *         bias_l'[j'] = s_l[p_l[j']] * bias_l[p_l[j']]
+ *         kernel_l'[i'][j'] = s_{l-1}[p_{l-1}[i']] * s_l[p_l[j']] * kernel_l[p_{l-1}[i']][p_l[j']]
+ *         (row factors: identity for l = 0; column factors: identity for the output layer).  Every output float is an input
+ *         float moved, possibly negated: nothing is recomputed.  A draw is handled on its own (a NaN in one draw touches no
+ *         other), and a draw gives the same bits whatever M is.  With n_layers == 1, H = 0 and out is a copy.
+ *   perm [M][H] int32 (device, or null): perm[m][o_l + j'] = p_l[j'].  sign [M][H] int8 (or null): s_l[p_l[j']].
+ * Out of scope: the positive rescaling symmetry of ReLU, sigmoid's reflection (it needs a bias correction downstream),
+ * alignment to a reference draw by assignment, and every model other than the FCN.
+ * MILE_ERR_INVALID, with nothing launched and no device touched: a null spec, theta or out; M < 1 (or > 2^31 - 1); a model
+ * other than MILE_MODEL_FCN, use_bias != 1, or a spec mile_create would refuse; unknown bits in `how`; MILE_CANON_SIGN with an
+ * activation other than tanh; a hidden width above MILE_CANON_WIDTH_MAX; out overlapping theta.  MILE_ERR_STATE: a workspace
+ * below mile_canonicalize_fcn_workspace's figure -- 0 while a draw with its keys fits the LDS of a compute unit (one launch),
+ * 4 * M * H bytes for the row-tiled form of larger draws (two launches); -1 for a bad shape.  mile_canonical_hidden: H, -1 for
+ * a bad spec.  Every refusal leaves its message in mile_last_error.
+ * (Added under ABI 10: three new symbols, no struct or existing entry changed.) */
+int32_t mile_canonicalize_fcn(const mile_model_spec *spec, const float *theta, int64_t M, uint32_t how,
+                              float *out, int32_t *perm, int8_t *sign,
+                              void *workspace, int64_t workspace_bytes, void *stream);
+int64_t mile_canonicalize_fcn_workspace(const mile_model_spec *spec, int64_t M, uint32_t how);
+int64_t mile_canonical_hidden(const mile_model_spec *spec);
+
 /* Function-space chain diagnostics: the statistics of mile_chain_diagnostics of what the draws PREDICT, streamed -- the
  * [C][S][N][O] outputs are never held.  Hidden-unit permutations and other symmetries of the parameters leave these series
  * untouched, so their R-hat answers whether the chains agree in their predictions, and their ESS how many effective draws

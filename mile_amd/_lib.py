@@ -23,6 +23,8 @@ FDIAG_SUMMARY = ('rhat_max', 'rhat_mean', 'rhat_column', 'rhat_gt_1_01', 'rhat_g
                  'crhat_max', 'crhat_chain', 'crhat_column', 'crhat_skipped',
                  'ess_min', 'ess_mean', 'ess_chain', 'ess_column', 'ess_skipped')
 FDIAG_O_MAX = 64
+CANON_BITS = {'bias': 0, 'norm': 1, 'sign': 2}                                                # MILE_CANON_*
+CANON_WIDTH_MAX = 1024
 MODEL_IDS = {'fcn': 0, 'lenet': 1, 'lenetti': 2, 'attn': 3, 'attn_pretrained': 4, 'attn_wide': 5}
 
 
@@ -47,6 +49,25 @@ class ModelSpecC(C.Structure):
         ('n_heads', C.c_int32),
         ('qkv_dim', C.c_int32),
     ]
+
+
+def fcn_spec_c(spec) -> ModelSpecC:
+    """The mile_model_spec of an FCN ``mile_amd.spec.ModelSpec``, for the calls that take a spec and no handle."""
+    if len(spec.hidden_structure) > MILE_MAX_LAYERS:
+        raise ValueError(f'at most {MILE_MAX_LAYERS} layers')
+    cs = ModelSpecC()
+    cs.in_features = spec.in_features
+    cs.n_layers = len(spec.hidden_structure)
+    for i, w in enumerate(spec.hidden_structure):
+        cs.widths[i] = w
+    cs.activation = ACTIVATION_IDS[spec.activation]
+    cs.task = TASK_IDS[spec.task]
+    cs.prior = PRIOR_IDS[spec.prior]
+    cs.prior_loc = spec.prior_loc
+    cs.prior_scale = spec.prior_scale
+    cs.use_bias = int(spec.use_bias)
+    cs.model = MODEL_IDS['fcn']
+    return cs
 
 
 class StateC(C.Structure):
@@ -185,6 +206,10 @@ SIGNATURES = {
                                               C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     'mile_function_diagnostics_workspace': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    'mile_canonicalize_fcn': (C.c_int32, [C.POINTER(ModelSpecC), C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_void_p]),
+    'mile_canonicalize_fcn_workspace': (C.c_int64, [C.POINTER(ModelSpecC), C.c_int64, C.c_uint32]),
+    'mile_canonical_hidden': (C.c_int64, [C.POINTER(ModelSpecC)]),
     'mile_debug_noise': (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
                                      C.c_void_p, C.c_void_p]),
     'mile_debug_prefill_count': (C.c_int64, [C.c_void_p]),

@@ -21,6 +21,11 @@ MILE_LOCAL int fail(int code, const std::string &msg);
       return fail(MILE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));           \
   } while (0)
 
+// The FCN's parameter row without a handle: bias and kernel offset of each of spec->n_layers layers (in_features >= 1, widths
+// >= 1 and 1 <= n_layers <= MILE_MAX_LAYERS are the caller's to check), d back.  The table behind mile_param_offsets.
+struct FcnOffsets { int32_t *b_off, *w_off; };       // [n_layers] each, the caller's
+MILE_LOCAL long long fcn_param_layout(const mile_model_spec *spec, FcnOffsets ds);
+
 // what the statistics read of a handle: its device and compute units, the task, the row width F, the head width O, d
 struct EvalView { int device, n_cu, task, in_features, O, d; };
 MILE_LOCAL EvalView eval_view(const mile_sampler *s);

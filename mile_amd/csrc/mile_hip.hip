@@ -353,9 +353,9 @@ static int resolved_kernel(const mile_sampler *s) { return s->grad_kernel == MIL
 static int choose_S(const mile_sampler *s, int E, int kernel) { return grad_kernel(kernel).row_splits(s, E); }
 
 // ---- one layout per model family: validates the spec, fills the geometry, ds and the ABI layers of mile_param_offsets -------
-static int layout_fcn(mile_sampler *s) {   // ravel_pytree order: layers sorted by NAME ("layer10" < "layer2"), bias before kernel
-  const mile_model_spec *spec = &s->spec;
-  DevSpec &ds = s->ds;
+// The FCN's parameter row, the one table every user of the layout reads (mile_eval_handle.h): ravel_pytree order, layers sorted
+// by NAME ("layer10" < "layer2"), bias before kernel.  Returns d.
+long long fcn_param_layout(const mile_model_spec *spec, FcnOffsets ds) {
   std::vector<int> order(spec->n_layers);
   for (int i = 0; i < spec->n_layers; ++i) order[i] = i;
   std::sort(order.begin(), order.end(), [](int a, int b) {
@@ -367,6 +367,13 @@ static int layout_fcn(mile_sampler *s) {   // ravel_pytree order: layers sorted 
     ds.b_off[li] = (int)off; off += fout;
     ds.w_off[li] = (int)off; off += (long long)fin * fout;
   }
+  return off;
+}
+
+static int layout_fcn(mile_sampler *s) {
+  const mile_model_spec *spec = &s->spec;
+  DevSpec &ds = s->ds;
+  const long long off = fcn_param_layout(spec, FcnOffsets{ds.b_off, ds.w_off});
   if (off > 0x7fffffffLL) return fail(MILE_ERR_INVALID, "parameter count exceeds int32");
   if (off < 2) return fail(MILE_ERR_INVALID, "The target distribution must have more than 1 dimension for MCLMC.");
   ds.d = (int)off;

@@ -1003,6 +1003,12 @@ class Engine:
         out['Q'], out['M'] = Q, M
         return out
 
+    def canonicalize(self, theta, key: str = 'bias', sign: bool = False, return_perm: bool = False):
+        """theta [C, S, d] or [M, d] -> the canonical hidden-unit ordering of every draw on this engine's device
+        (mile_amd.metrics.canonicalize with the engine's spec: mile_canonicalize_fcn)."""
+        from mile_amd.metrics import canonicalize
+        return canonicalize(self.spec, torch.as_tensor(theta).to(self.device, torch.float32), key, sign, return_perm)
+
     @property
     def supports_device_tuner(self) -> bool:
         return self.dim >= 4

@@ -279,6 +279,157 @@ def chain_diagnostics(samples: torch.Tensor, n_splits: int = 2) -> dict:
             'wcv': within_chain_var(x), 'bcv': between_chain_var(x)}
 
 
+# ---- canonical hidden-unit ordering of FCN draws: one representative of every draw's orbit under the permutations (and, for
+# tanh, the sign flips) of its hidden units, so that the per-parameter statistics above mean something for chains that sit in
+# permuted copies of one mode.  The rule is stated once, in include/mile_hip.h (mile_canonicalize_fcn); the library runs it on
+# device tensors, the dense form here is the CPU statement, the timing yardstick and the path for very wide layers.
+
+CANON_KEYS = ('bias', 'norm')
+LAST_CANON_PATH = None      # how the last canonicalize call ran: 'library' or 'torch'
+
+
+def _canon_check(spec, key: str, sign: bool):
+    if not isinstance(spec, ModelSpec):
+        raise ValueError(f'canonical ordering is defined for the FCN only, not for {type(spec).__name__}')
+    if not spec.use_bias:
+        raise ValueError('canonical ordering needs use_bias=True')
+    if key not in CANON_KEYS:
+        raise ValueError(f'key {key!r} (supported: {CANON_KEYS})')
+    if sign and spec.activation != 'tanh':
+        raise ValueError(f'sign fixing needs an odd activation: tanh only, not {spec.activation}')
+
+
+def canonical_hidden(spec) -> int:
+    """H: the hidden units of all hidden layers of the FCN ``spec`` (the last axis of ``perm`` and ``sign``)."""
+    return int(sum(spec.hidden_structure[:-1]))
+
+
+def canonicalize_dense(spec, theta: torch.Tensor, key: str = 'bias', sign: bool = False):
+    """The rule of mile_canonicalize_fcn in torch, on whatever device ``theta`` [M, d] is on: a stable ``torch.sort`` of each
+    hidden layer's keys (NaNs last), then ``take_along_dim`` of the bias, the columns and the next layer's rows.  Returns
+    ``out`` [M, d] (theta's dtype), ``perm`` [M, H] int32, ``sign`` [M, H] int8."""
+    _canon_check(spec, key, sign)
+    M = theta.shape[0]
+    leaves = {n.split('.', 1)[1]: (o, sh) for n, o, sh in spec.leaves()}
+    nl = len(spec.hidden_structure)
+
+    def layer(li):
+        (ob, (fout,)), (ok, (fin, _)) = leaves[f'layer{li}.bias'], leaves[f'layer{li}.kernel']
+        return ob, ok, fin, fout
+
+    perms, signs = [], []
+    for li in range(nl - 1):
+        ob, ok, fin, fout = layer(li)
+        b = theta[:, ob:ob + fout]
+        s = torch.where(b < 0, -torch.ones_like(b), torch.ones_like(b)) if sign else torch.ones_like(b)
+        if key == 'bias':
+            k = s * b
+        else:                                                   # fp64, the terms one after another: bias, then i ascending
+            K = theta[:, ok:ok + fin * fout].reshape(M, fin, fout)
+            k = b.double() * b.double()
+            for i in range(fin):
+                x = K[:, i, :].double()
+                k = k + x * x
+        p = torch.sort(k, dim=1, stable=True).indices
+        perms.append(p)
+        signs.append(torch.take_along_dim(s, p, dim=1))
+    out = torch.empty_like(theta)
+    for li in range(nl):
+        ob, ok, fin, fout = layer(li)
+        B = theta[:, ob:ob + fout]
+        K = theta[:, ok:ok + fin * fout].reshape(M, fin, fout)
+        if li < nl - 1:
+            B = torch.take_along_dim(B, perms[li], dim=1) * signs[li]
+            K = torch.take_along_dim(K, perms[li][:, None, :], dim=2) * signs[li][:, None, :]
+        if li > 0:
+            K = torch.take_along_dim(K, perms[li - 1][:, :, None], dim=1) * signs[li - 1][:, :, None]
+        out[:, ob:ob + fout] = B
+        out[:, ok:ok + fin * fout] = K.reshape(M, fin * fout)
+    cat = lambda ts, dt: (torch.cat(ts, dim=1) if ts else torch.empty((M, 0), device=theta.device)).to(dt)
+    return out, cat(perms, torch.int32), cat(signs, torch.int8)
+
+
+def _library_canonicalize(spec, theta: torch.Tensor, key: str, sign: bool, want_index: bool):
+    """theta [M, d] contiguous CUDA fp32 -> (out, perm, sign) from mile_canonicalize_fcn (perm, sign None unless wanted)."""
+    import ctypes as Ct
+    from mile_amd import _lib
+    lib = _lib.load_library()
+    cs = _lib.fcn_spec_c(spec)
+    M, H = theta.shape[0], canonical_hidden(spec)
+    how = _lib.CANON_BITS[key] | (_lib.CANON_BITS['sign'] if sign else 0)
+    ptr = lambda t: Ct.c_void_p(t.data_ptr()) if t is not None else None
+    with torch.cuda.device(theta.device):
+        out = torch.empty_like(theta)
+        perm = torch.empty((M, H), dtype=torch.int32, device=theta.device) if want_index else None
+        sgn = torch.empty((M, H), dtype=torch.int8, device=theta.device) if want_index else None
+        nws = int(lib.mile_canonicalize_fcn_workspace(Ct.byref(cs), M, how))
+        if nws < 0:
+            _lib.check(-1, lib)
+        ws = torch.empty(nws, dtype=torch.uint8, device=theta.device) if nws else None
+        stream = Ct.c_void_p(torch.cuda.current_stream(theta.device).cuda_stream)
+        _lib.check(lib.mile_canonicalize_fcn(Ct.byref(cs), ptr(theta), M, how, ptr(out), ptr(perm), ptr(sgn), ptr(ws), nws, stream), lib)
+    return out, perm, sgn
+
+
+def canonicalize(spec, theta: torch.Tensor, key: str = 'bias', sign: bool = False, return_perm: bool = False):
+    """theta [C, S, d] or [M, d] draws of the FCN ``spec`` -> the canonical draws in the same shape: hidden units of every
+    layer in ascending order of ``key`` ('bias': the unit's bias; 'norm': the squared norm of its bias and incoming weights),
+    with ``sign`` (tanh only) every unit's bias made non-negative first.  With ``return_perm`` also ``perm`` [..., H] int32 (the
+    original index of the unit at each position) and ``sign`` [..., H] int8.  CUDA fp32 draws run in the library
+    (mile_canonicalize_fcn), anything else -- and, with a UserWarning, nets with a hidden layer wider than 1024 -- in
+    ``canonicalize_dense``.  Ordering by a key gives order statistics, not an alignment to a reference mode: where two units'
+    keys cross inside a chain the labels switch (see ``permutation_switches``)."""
+    global LAST_CANON_PATH
+    import warnings
+    from mile_amd._lib import CANON_WIDTH_MAX
+    _canon_check(spec, key, sign)
+    if theta.dim() not in (2, 3) or theta.shape[-1] != spec.n_params:
+        raise ValueError(f'theta must be [C, S, {spec.n_params}] or [M, {spec.n_params}], got {tuple(theta.shape)}')
+    flat = theta.reshape(-1, theta.shape[-1])
+    wide = max(spec.hidden_structure[:-1], default=0) > CANON_WIDTH_MAX
+    on_device = theta.is_cuda and theta.dtype == torch.float32
+    if on_device and wide:
+        warnings.warn(f'canonicalize: a hidden layer wider than {CANON_WIDTH_MAX} is outside the range of the HIP kernels; '
+                      'using the torch form', category=UserWarning)
+    if on_device and not wide:
+        out, perm, sgn = _library_canonicalize(spec, flat.contiguous(), key, sign, return_perm)
+        LAST_CANON_PATH = 'library'
+    else:
+        out, perm, sgn = canonicalize_dense(spec, flat, key, sign)
+        LAST_CANON_PATH = 'torch'
+    out = out.reshape(theta.shape)
+    if not return_perm:
+        return out
+    lead = tuple(theta.shape[:-1])
+    return out, perm.reshape(*lead, -1), sgn.reshape(*lead, -1)
+
+
+def permutation_switches(perm: torch.Tensor, spec) -> torch.Tensor:
+    """perm [C, S, H] -> int64 [C, n_hidden]: for each chain and hidden layer the draws j >= 1 whose order differs from that of
+    draw j - 1.  The label-switching count: near 0 the key separates the units of this posterior and the canonical parameters
+    are the same units throughout; a large share means the per-parameter statistics are those of order statistics."""
+    perm = torch.as_tensor(perm)
+    widths = list(spec.hidden_structure[:-1])
+    if perm.dim() != 3 or perm.shape[2] != sum(widths):
+        raise ValueError(f'perm must be [C, S, {sum(widths)}], got {tuple(perm.shape)}')
+    out = torch.zeros((perm.shape[0], len(widths)), dtype=torch.int64, device=perm.device)
+    o = 0
+    for l, w in enumerate(widths):
+        span = perm[:, :, o:o + w]
+        out[:, l] = (span[:, 1:] != span[:, :-1]).any(dim=2).sum(dim=1)
+        o += w
+    return out
+
+
+def canonical_diagnostics(spec, samples: torch.Tensor, n_splits: int = 2, key: str = 'bias', sign: bool = False) -> dict:
+    """samples [C, S, d] -> ``chain_diagnostics`` of the canonical draws (``canonicalize``), plus 'switches' [C, n_hidden]
+    (``permutation_switches``)."""
+    out, perm, _ = canonicalize(spec, samples, key, sign, return_perm=True)
+    res = chain_diagnostics(out, n_splits)
+    res['switches'] = permutation_switches(perm, spec)
+    return res
+
+
 # ---- chain diagnostics in function space: the statistics above, of what every draw predicts on every row.  The library
 # streams them (Engine.function_diagnostics, mile_function_diagnostics); the dense forms here are the yardstick and the path
 # for CPU tensors.
