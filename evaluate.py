@@ -266,6 +266,31 @@ def stacking_metrics(train_rows, lpd_eval, eval=None):
 CRPS_GRAM_BYTES = 256 << 20             # --crps asks for the Gram matrices [N, C, C] fp64 only while they fit
 
 
+def stacked_weights(w):
+    """The solved stacking weights as the weighted entry points take them: clipped at 0 and renormalised, float64 [C]."""
+    w = np.clip(np.asarray(w, dtype=np.float64), 0.0, None)
+    return w / w.sum()
+
+
+def stacked_interval_metrics(quant, pit, levels, coverages):
+    """--stacking with --intervals: ``interval_metrics`` of the stacking-weighted mixture (Engine.predict_quantiles_weighted),
+    the keys as ``intervals_stacked_*`` and the arrays as ``quantiles_stacked``, ``pit_stacked``."""
+    keys, arrays = interval_metrics(quant, pit, torch.zeros(1, dtype=torch.int32), levels, coverages)
+    out = {k.replace('intervals_', 'intervals_stacked_', 1): v for k, v in keys.items() if k != 'intervals_dropped'}
+    return out, {'quantiles_stacked': arrays['quantiles'], 'pit_stacked': arrays['pit']}
+
+
+def stacked_calibration_metrics(res, w, y, n_bins):
+    """--stacking with --calibration: NLL, Brier score, ECE and accuracy of P = sum_c w_c P_c, from the calibration result's
+    per-chain probabilities through ``metrics.weighted_class_probs`` and ``metrics.calibration_decide``."""
+    from mile_amd import metrics as M
+    P, kept = M.weighted_class_probs(res['probs'][:-1].double(), res['kept'][:-1], w)
+    dec = M.calibration_decide(P[None], kept[None], torch.as_tensor(y), res['coverages'], n_bins)
+    s = M.calibration_summary({'totals': dec['totals'], 'bins': dec['bins'], 'coverages': res['coverages']})[0]
+    return {'calibration_stacked_nll': s['nll'], 'calibration_stacked_brier': s['brier'], 'calibration_stacked_ece': s['ece'],
+            'calibration_stacked_accuracy': s['acc']}
+
+
 def crps_refusal(task, n_chains):
     """Why --crps cannot run on this experiment, or None."""
     if task != 'regr':
@@ -394,7 +419,10 @@ def build_parser():
                          '(a certified bound on the score left on the table), stacking_iterations, stacking_converged, '
                          'stacking_effective_chains (1 / sum w^2), stacking_khat_bad (chain rows with khat > 0.7) and stacking_weights in '
                          'metrics.json; weights, chain_elpd_loo, chain_khat_bad, gap, n_train, n_train_used, n_eval in stacking.npz.  '
-                         'Needs at least 2 draws per chain; --loo-r-eff applies')
+                         'Needs at least 2 draws per chain; --loo-r-eff applies.  Next to --intervals, --moments or --calibration the '
+                         'stacked mixture is reported beside the ensemble: intervals_stacked_coverage_<c>, intervals_stacked_width_<c>, '
+                         'intervals_stacked_cal_error (quantiles_stacked and pit_stacked in intervals.npz; mile_predict_quantiles_weighted), '
+                         'moments_stacked_rmse, calibration_stacked_nll, _brier, _ece and _accuracy')
     ap.add_argument('--crps', action='store_true',
                     help='regression: the exact CRPS of the predictive mixture on --split, from all pairs of draws on the device '
                          '(mile_crps_stream; closed form, so no draws and no seed): crps (the pooled ensemble), crps_spread, '
@@ -579,6 +607,20 @@ def main():
         keys, arrays = stacking_metrics(train_rows, lpd_eval, eval=eng.stack_eval)
         out.update(keys)
         np.savez(exp / 'stacking.npz', **arrays)
+        w_stacked = stacked_weights(arrays['weights'])
+        if args.intervals:      # the stacked counterparts, next to the ensemble's keys and arrays above
+            quant, pit = eng.predict_quantiles_weighted(st, torch.from_numpy(x), w_stacked, levels,
+                                                        y=torch.from_numpy(np.ascontiguousarray(y)))
+            keys, more = stacked_interval_metrics(quant, pit, levels, args.coverages)
+            out.update(keys)
+            with np.load(exp / 'intervals.npz') as z:
+                np.savez(exp / 'intervals.npz', **{k: z[k] for k in z.files}, **more)
+        if args.moments and cfg.data.task == 'regr':
+            from mile_amd.metrics import rmse_from_moments, weighted_moments
+            mom = weighted_moments(*eng.predict_moments_by_chain(st, torch.from_numpy(x)), w_stacked, cfg.data.task).cpu()
+            fin = torch.isfinite(mom[:, 0])
+            yt = torch.as_tensor(np.ascontiguousarray(y), dtype=torch.float64).reshape(-1)
+            out['moments_stacked_rmse'] = float(rmse_from_moments(yt[fin], mom[fin])) if bool(fin.any()) else float('nan')
     if args.crps:
         from mile_amd.metrics import crps_thin_stride
         k = crps_thin_stride(samples.shape[0], samples.shape[1], args.crps_max_draws)
@@ -601,6 +643,8 @@ def main():
             res = classification_calibration(eng.predict(torch.from_numpy(samples), xt), yt.to(args.device), args.coverages, args.calibration)
         keys, arrays = calibration_metrics(res, args.calibration)
         keys['calibration_dropped'] = int(samples.shape[0] * samples.shape[1] * x.shape[0] - int(arrays['kept'][-1].sum()))
+        if args.stacking:
+            keys.update(stacked_calibration_metrics(res, w_stacked, yt, args.calibration))
         out.update(keys)
         np.savez(exp / 'calibration.npz', **arrays)
     (exp / 'metrics.json').write_text(json.dumps(out, indent=1) + '\n')

@@ -430,6 +430,35 @@ int32_t mile_predict_quantiles(mile_sampler *s, const float *theta, int64_t S, c
                                const double *levels, int32_t Q, const float *y, float *quant, float *pit, int32_t *dropped,
                                int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream);
 int64_t mile_predict_quantiles_workspace(const mile_sampler *s, int64_t S, int64_t N);   /* bytes; -1 out of range */
+/* The same for the chain-weighted mixture, the predictive that stacking weights describe; the conventions are those of
+ * mile_mixture_crps.  raw [C * S, N, 2] fp32 (mu, log sigma), draw j of chain c at row c * S + j; weights [C] fp64 on the HOST,
+ * every entry finite and >= 0, |sum_c w_c - 1| <= 1e-9.  On row n a draw with a non-finite mu or log sigma is left out of that
+ * row, K_c counts chain c's kept draws and dropped[c][n] = S - K_c (dropped [C, N] int32 or null); sigma = clip(exp(log sigma),
+ * 1e-6, 1e6), formed in fp64 where it is used.  The weighted CDF is
+ *   F_n(t) = sum_c (w_c / K_c) sum_{i in c, kept} Phi((t - mu_i) / sigma_i),
+ * quant[n, q] is the root of F_n(t) = levels[q] and pit[n] = F_n(y_n).  A chain with w_c = 0 enters no sum, so its non-finite
+ * draws cannot poison a row; a chain with w_c > 0 and K_c = 0 makes the row NaN in quant and pit.  Quantiles of increasing
+ * levels are non-decreasing.  The bracket of the unweighted solver stays exact for any convex combination: min and max of
+ * mu_i + Phi^-1(p) sigma_i over the components that carry weight; the iteration is the unweighted one, with w_c / K_c
+ * multiplied into Phi and the density, and stops at a bracket below 2^-25 max(|mid|, sd_n), sd_n the weighted mixture's
+ * standard deviation.  fp64 sums in a fixed order, no floating-point atomics: a row's result depends on its C * S pairs and
+ * the weights alone, bit for bit.  With w_c = 1 / C and nothing dropped it is the predictive of mile_mixture_quantiles (equal
+ * within the solver's tolerance, not bitwise: the sums differ in their last bits).
+ * mile_predict_quantiles_weighted is the same for draws theta [C * S, d] on X [N, F], with the tiles, passes and shared
+ * workspace of mile_predict_quantiles (mile_predict_quantiles_weighted_workspace: its bytes); the result is bitwise the same
+ * for every max_draws_per_pass and max_rows_per_tile, and equal to mile_mixture_quantiles_weighted of mile_predict's outputs.
+ * It records no sweeps for mile_debug_quantile_sweeps.
+ * MILE_ERR_INVALID, nothing launched: the refusals of the unweighted pair (with C * S for S), C < 1 or > 1024,
+ * C * S > 2^31 - 1, null weights, a negative or non-finite weight, a weight sum off by more than 1e-9.
+ * (Added under ABI 10: three new symbols, no struct or existing entry changed.) */
+int32_t mile_mixture_quantiles_weighted(const float *raw, int32_t C, int64_t S, int64_t N, const double *weights,
+                                        const double *levels, int32_t Q, const float *y, float *quant, float *pit,
+                                        int32_t *dropped /* [C, N] */, void *stream);
+int32_t mile_predict_quantiles_weighted(mile_sampler *s, const float *theta /* [C*S, d] */, int32_t C, int64_t S, const void *X,
+                                        int64_t N, const double *weights, const double *levels, int32_t Q, const float *y,
+                                        float *quant, float *pit, int32_t *dropped, int64_t max_draws_per_pass,
+                                        int64_t max_rows_per_tile, void *stream);
+int64_t mile_predict_quantiles_weighted_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N);   /* bytes; -1 out of range */
 /* Test and tool hook: over the rows of the handle's last mile_predict_quantiles that asked for quantiles, the row count, the
  * sum of the solver's sweeps and the largest sweep count of a row (synchronises the device).  The sweep counts lie in the
  * shared evaluation workspace: once a later mile_predict_moments, mile_lppd_stream, mile_loo_stream, mile_calibration_stream or

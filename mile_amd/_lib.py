@@ -175,6 +175,12 @@ SIGNATURES = {
     'mile_predict_quantiles': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     'mile_predict_quantiles_workspace': (C.c_int64, [C.c_void_p, C.c_int64, C.c_int64]),
+    'mile_mixture_quantiles_weighted': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mile_predict_quantiles_weighted': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                    C.c_int64, C.c_void_p]),
+    'mile_predict_quantiles_weighted_workspace': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64]),
     'mile_debug_quantile_sweeps': (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     'mile_psis_loo': (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),

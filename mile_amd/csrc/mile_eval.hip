@@ -210,8 +210,9 @@ static const char *qnt_bad_args(const double *levels, int32_t Q, const float *y,
 // The plan of one call: rows per tile, draws per pass and the byte offset of every block of its workspace.  own_raw: the
 // streamed call, whose workspace begins with the forward's raw block [S][Nt][2] (16 bytes per (draw, row) with the packed copy,
 // tiles of whole transpose tiles) and ends with the sweeps [N]; else raw is the caller's and the packed copy comes first.
-struct QntTilePlan { int64_t Nt, chunk; int slices; size_t pk, part, lev, sweeps, total; };
-static QntTilePlan qnt_tile_plan(int64_t S, int64_t N, int n_cu, bool own_raw, int64_t max_rows, int64_t max_draws) {
+// C > 0: the chain-weighted form, whose weights [C] come last.
+struct QntTilePlan { int64_t Nt, chunk; int slices; size_t pk, part, lev, sweeps, w, total; };
+static QntTilePlan qnt_tile_plan(int64_t S, int64_t N, int n_cu, bool own_raw, int64_t max_rows, int64_t max_draws, int32_t C = 0) {
   QntTilePlan t;
   t.Nt = tile_rows(EVAL_PASS_TARGET, S * (own_raw ? 16 : 8), own_raw ? QNT_TILE : 1, max_rows, N);
   t.chunk = pass_draws(EVAL_NO_BUDGET, 1, max_draws, S);
@@ -220,21 +221,44 @@ static QntTilePlan qnt_tile_plan(int64_t S, int64_t N, int n_cu, bool own_raw, i
   t.part = t.pk + qnt_pk_bytes(S, t.Nt);
   t.lev = t.part + qnt_part_bytes((int)t.Nt, QNT_MAX_Q, t.slices);
   t.sweeps = t.lev + r256(2 * QNT_MAX_Q * 8);
-  t.total = t.sweeps + (own_raw ? r256((size_t)N * 4) : 0);
+  t.w = t.sweeps + (own_raw ? r256((size_t)N * 4) : 0);
+  t.total = t.w + (C > 0 ? r256((size_t)C * 8) : 0);
   return t;
 }
 
-// the tiles of one call, each from `source`; sweeps: record them in the workspace
+// the chains of a weighted call: S = C * Sc draws, weights [C] on the host
+struct QntChains { int32_t C; int64_t Sc; const double *weights; };
+// what is wrong with them, or null
+static const char *qnt_bad_chains(const QntChains &ch) {
+  if (ch.C < 1 || ch.C > QNT_MAX_C) return "C out of range (1 .. 1024)";
+  if (ch.Sc < 1 || ch.Sc > 0x7fffffff / ch.C) return "C * S out of range (1 .. 2^31 - 1)";
+  return nullptr;
+}
+static const char *qnt_bad_weights(const QntChains &ch) {
+  if (!ch.weights) return "null weights";
+  double sum = 0.0;
+  for (int c = 0; c < ch.C; ++c) {
+    if (!std::isfinite(ch.weights[c]) || ch.weights[c] < 0.0) return "weights must be finite and >= 0";
+    sum += ch.weights[c];
+  }
+  return std::fabs(sum - 1.0) <= 1e-9 ? nullptr : "the weights must sum to 1 (within 1e-9)";
+}
+
+// the tiles of one call, each from `source`; sweeps: record them in the workspace; ch: the chain-weighted form, dropped [C][N]
 template <class Source>
 static int qnt_run(char *ws, const QntTilePlan &t, int64_t S, int64_t N, const double *levels, int32_t Q, const float *y, float *quant,
-                   float *pit, int32_t *dropped, bool sweeps, hipStream_t st, Source source) {
+                   float *pit, int32_t *dropped, bool sweeps, hipStream_t st, Source source, const QntChains *ch = nullptr) {
   double lev[2 * QNT_MAX_Q];
   for (int i = 0; i < Q; ++i) { lev[i] = levels[i]; lev[Q + i] = host_ndtri(levels[i]); }
-  QntParams p{};
+  QntWParams p{};
   p.S = (int)S; p.Q = Q; p.slices = t.slices;
   p.pk = (float2 *)(ws + t.pk); p.part_brk = (double *)(ws + t.part); p.lev = (const double *)(ws + t.lev);
   HIP_TRY(hipMemcpyAsync(ws + t.lev, lev, (size_t)2 * Q * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));   // lev is on this stack
+  if (ch) {
+    p.C = ch->C; p.Sc = (int)ch->Sc; p.N = N; p.w = (const double *)(ws + t.w);
+    HIP_TRY(hipMemcpyAsync(ws + t.w, ch->weights, (size_t)ch->C * 8, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));   // lev is on this stack, the weights are the caller's host memory
   for (int64_t r0 = 0; r0 < N; r0 += t.Nt) {
     p.Nt = (int)std::min<int64_t>(t.Nt, N - r0);
     p.part_cnt = (int32_t *)(ws + t.part + r256((size_t)p.slices * p.Nt * Q * 16));
@@ -245,9 +269,9 @@ static int qnt_run(char *ws, const QntTilePlan &t, int64_t S, int64_t N, const d
     p.y = y ? y + r0 : nullptr;
     p.quant = quant ? quant + r0 * Q : nullptr;
     p.pit = pit ? pit + r0 : nullptr;
-    p.dropped = dropped ? dropped + r0 : nullptr;
+    (ch ? p.dropped_c : p.dropped) = dropped ? dropped + r0 : nullptr;
     p.sweeps = sweeps ? (int32_t *)(ws + t.sweeps) + r0 : nullptr;
-    HIP_TRY(mile_launch_quantiles(p, st));
+    HIP_TRY(ch ? mile_launch_quantiles_weighted(p, st) : mile_launch_quantiles(p, st));
   }
   return MILE_OK;
 }
@@ -290,6 +314,57 @@ extern "C" int32_t mile_predict_quantiles(mile_sampler *s, const float *theta, i
   if (rc != MILE_OK) return rc;
   record_quantile_sweeps(s, (const int32_t *)(ws + t.sweeps), quant ? N : 0);
   return MILE_OK;
+}
+
+// The chain-weighted pair: the same plan, passes and workspace with the draws' C * S for S, and the weights behind them.
+extern "C" int32_t mile_mixture_quantiles_weighted(const float *raw, int32_t C, int64_t S, int64_t N, const double *weights,
+                                                   const double *levels, int32_t Q, const float *y, float *quant, float *pit,
+                                                   int32_t *dropped, void *stream) {
+  const char *fn = "mile_mixture_quantiles_weighted";
+  const QntChains ch{C, S, weights};
+  if (!raw) return bad(fn, "null raw");
+  if (const char *m = qnt_bad_chains(ch)) return bad(fn, m);
+  if (const char *m = bad_N(N)) return bad(fn, m);
+  if (const char *m = qnt_bad_weights(ch)) return bad(fn, m);
+  if (const char *m = qnt_bad_args(levels, Q, y, quant, pit)) return bad(fn, m);
+  hipStream_t st = (hipStream_t)stream;
+  int n_cu;
+  const int rc0 = current_cus(&n_cu);
+  if (rc0 != MILE_OK) return rc0;
+  const int64_t D = (int64_t)C * S;
+  const QntTilePlan t = qnt_tile_plan(D, N, n_cu, false, 0, 0, C);
+  return with_call_ws(t.total, "mile_mixture_quantiles_weighted: workspace allocation failed", st, [&](char *ws) {
+    return qnt_run(ws, t, D, N, levels, Q, y, quant, pit, dropped, false, st,
+                   [&](int64_t r0, int, Tile &tile) { tile = {raw + 2 * r0, N}; return (int)MILE_OK; }, &ch);
+  });
+}
+
+extern "C" int64_t mile_predict_quantiles_weighted_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N) {
+  if (!s || qnt_bad_chains({C, S, nullptr}) || bad_N(N)) return -1;
+  return (int64_t)qnt_tile_plan((int64_t)C * S, N, eval_view(s).n_cu, true, 0, 0, C).total;
+}
+
+extern "C" int32_t mile_predict_quantiles_weighted(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, int64_t N,
+                                                   const double *weights, const double *levels, int32_t Q, const float *y, float *quant,
+                                                   float *pit, int32_t *dropped, int64_t max_draws_per_pass, int64_t max_rows_per_tile,
+                                                   void *stream) {
+  const char *fn = "mile_predict_quantiles_weighted";
+  const QntChains ch{C, S, weights};
+  const char *shape = qnt_bad_chains(ch);
+  const int rc0 = eval_args(fn, s, !theta || !X, shape ? shape : bad_N(N), [&]() -> const char * {
+    if (const char *m = qnt_bad_weights(ch)) return m;
+    if (const char *m = qnt_bad_args(levels, Q, y, quant, pit)) return m;
+    if (const char *m = bad_caps(max_draws_per_pass, max_rows_per_tile)) return m;
+    return not_mu_log_sigma(s);
+  });
+  if (rc0 != MILE_OK) return rc0;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t D = (int64_t)C * S;
+  const QntTilePlan t = qnt_tile_plan(D, N, eval_view(s).n_cu, true, max_rows_per_tile, max_draws_per_pass, C);
+  char *ws;
+  const int rc1 = stream_ws(fn, s, t.total, "lower max_rows_per_tile", ws);
+  if (rc1 != MILE_OK) return rc1;
+  return qnt_run(ws, t, D, N, levels, Q, y, quant, pit, dropped, false, st, stream_tiles(s, theta, D, t.chunk, X, ws, st), &ch);
 }
 
 /* test and tool hook: sweeps of k_qnt_solve over the rows of the handle's last mile_predict_quantiles that asked for quantiles */

@@ -22,6 +22,16 @@
 //                <true>: the row's S pairs are loaded into LDS once (S <= QNT_LDS_MAX_S); <false>: every sweep streams them
 //                from global memory.
 // fp64 sums, fixed order, no atomics: a row's result depends on its S pairs alone, bit for bit.
+//
+// The chain-weighted form (mile_mixture_quantiles_weighted, mile_predict_quantiles_weighted; QntWParams and
+// mile_launch_quantiles_weighted): the S = C * Sc pairs of a row are C chains of Sc draws, chain c with weight w_c, and
+// F_n(t) = sum_c (w_c / K_c) sum_{i in c, kept} Phi((t - mu_i) / sigma_i).  k_qnt_pack runs as above with no level (its counts and
+// brackets are not read).  k_qnt_solve<., QntWParams> first counts K_c per chain (whole waves by ballot, integer adds in LDS),
+// writes dropped [C][N] and a table omega_c = w_c / K_c in LDS (0 for w_c = 0: such a chain enters no sum, the bracket
+// included; w_c > 0 with K_c = 0: the row is NaN), takes the bracket min_i and max_i of mu_i + z_p sigma_i over the components
+// with omega > 0 in the sweep's own lane layout, and multiplies omega[chain(i)] into Phi and the density of every sweep, into
+// the mean and sd_n of the first iterate and into the PIT sum.  Same summation orders as above; a row's result depends on its
+// pairs and the weights alone, bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,6 +62,15 @@ struct QntParams {
   int32_t *sweeps;         // [Nt], or null
 };
 
+// the chain-weighted form: S = C * Sc, chain c's draws at pairs c * Sc .. of a row
+#define QNT_MAX_C 1024
+struct QntWParams : QntParams {
+  const double *w;         // device: [C] weights, >= 0, summing to 1
+  int C, Sc;
+  int32_t *dropped_c;      // [C][N] at the tile's first row, or null
+  long long N;             // rows per chain in dropped_c
+};
+
 static inline int qnt_slices(int S, int Nt, int n_cu) {   // about two workgroups per CU, whole transpose tiles per slice
   const int row_groups = (Nt + QNT_TILE - 1) / QNT_TILE, s_tiles = (S + QNT_TILE - 1) / QNT_TILE;
   int sl = (2 * n_cu + row_groups - 1) / row_groups;
@@ -66,3 +85,4 @@ static inline size_t qnt_part_bytes(int Nt, int Q, int slices) {
 }
 
 hipError_t mile_launch_quantiles(const QntParams &p, hipStream_t st);
+hipError_t mile_launch_quantiles_weighted(const QntWParams &p, hipStream_t st);

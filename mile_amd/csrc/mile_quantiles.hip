@@ -4,6 +4,8 @@
 
 #include <math.h>
 
+#include <type_traits>
+
 #include "mile_device.h"
 #include "mile_quantiles.h"
 
@@ -93,25 +95,40 @@ __device__ __forceinline__ double qnt_block_sum(double v, double *red) {
   return t;
 }
 
-template <bool LDS>
-__global__ __launch_bounds__(QNT_NT) void k_qnt_solve(const QntParams p) {
+// omega of component i's chain, for a walk of increasing i: the division only where the walk enters another chain
+struct QntChainWalk {
+  int c = 0, end = 0;
+  __device__ __forceinline__ double at(int i, int Sc, const double *om) {
+    if (i >= end) { c = i / Sc; end = (c + 1) * Sc; }
+    return om[c];
+  }
+};
+
+// P = QntParams: the equal-weight mixture; P = QntWParams: the chain-weighted one (W below)
+template <bool LDS, class P = QntParams>
+__global__ __launch_bounds__(QNT_NT) void k_qnt_solve(const P p) {
+  constexpr bool W = std::is_same<P, QntWParams>::value;
   extern __shared__ float2 qnt_comp[];
   __shared__ double red[QNT_NW][QNT_MAX_Q][2];
   __shared__ double redb[QNT_NW];
   __shared__ double res[QNT_MAX_Q];
+  __shared__ double om[W ? QNT_MAX_C : 1];     // omega_c = w_c / K_c
+  __shared__ int kc[W ? QNT_MAX_C : 1];        // K_c
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int S = p.S, Nt = p.Nt, Q = p.Q;
   const float2 *g = p.pk + (size_t)n * S;
   const float qnan = __int_as_float(0x7fc00000);
 
   int kept = 0;
-  for (int sl = 0; sl < p.slices; ++sl) kept += p.part_cnt[(size_t)sl * Nt + n];
-  if (tid == 0 && p.dropped) p.dropped[n] = (int32_t)(S - kept);
-  if (kept == 0) {     // (the same in every thread)
-    if (p.quant && tid < Q) p.quant[(size_t)n * Q + tid] = qnan;
-    if (p.pit && tid == 0) p.pit[n] = qnan;
-    if (p.sweeps && tid == 0) p.sweeps[n] = 0;
-    return;
+  if constexpr (!W) {
+    for (int sl = 0; sl < p.slices; ++sl) kept += p.part_cnt[(size_t)sl * Nt + n];
+    if (tid == 0 && p.dropped) p.dropped[n] = (int32_t)(S - kept);
+    if (kept == 0) {     // (the same in every thread)
+      if (p.quant && tid < Q) p.quant[(size_t)n * Q + tid] = qnan;
+      if (p.pit && tid == 0) p.pit[n] = qnan;
+      if (p.sweeps && tid == 0) p.sweeps[n] = 0;
+      return;
+    }
   }
   if constexpr (LDS) {
     for (int i = tid; i < S; i += QNT_NT) qnt_comp[i] = g[i];
@@ -121,35 +138,114 @@ __global__ __launch_bounds__(QNT_NT) void k_qnt_solve(const QntParams p) {
     if constexpr (LDS) return qnt_comp[i];
     else return g[i];
   };
+  int Sc = 1;
+  if constexpr (W) {
+    Sc = p.Sc;
+    const int C = p.C;
+    for (int c = tid; c < C; c += QNT_NT) kc[c] = 0;
+    __syncthreads();
+    // K_c: 64 consecutive components per wave step; a step inside one chain adds its ballot's count once
+    for (int b = wv * 64; b < S; b += QNT_NT) {
+      const int i = b + lane;
+      bool k = false;
+      if (lane <= S - 1 - b) { const float mu = comp(i).x; k = mu == mu; }
+      const int c0 = b / Sc, c1 = (S - 1 - b < 63 ? S - 1 : b + 63) / Sc;
+      if (c0 == c1) {
+        const int cnt = __popcll(__ballot(k));
+        if (lane == 0 && cnt) atomicAdd(&kc[c0], cnt);
+      } else if (k) {
+        atomicAdd(&kc[i / Sc], 1);
+      }
+    }
+    __syncthreads();
+    int bad = 0;
+    for (int c = tid; c < C; c += QNT_NT) {
+      const double wc = p.w[c];
+      const int K = kc[c];
+      if (p.dropped_c) p.dropped_c[(size_t)c * (size_t)p.N + n] = (int32_t)(Sc - K);
+      if (wc > 0.0 && K == 0) bad = 1;
+      om[c] = wc > 0.0 && K > 0 ? wc / (double)K : 0.0;
+    }
+    if (__syncthreads_or(bad)) {     // a weighted chain with nothing kept (the same in every thread)
+      if (p.quant && tid < Q) p.quant[(size_t)n * Q + tid] = qnan;
+      if (p.pit && tid == 0) p.pit[n] = qnan;
+      if (p.sweeps && tid == 0) p.sweeps[n] = 0;
+      return;
+    }
+  }
   const double fk = (double)kept;
   int sweeps = 0;
 
   if (p.quant) {
     // sd_n of the mixture, two passes: the stopping width's scale and, with the mean, the first iterate
     double sm = 0.0, sv = 0.0;
-    for (int i = tid; i < S; i += QNT_NT) {
-      const float2 v = comp(i);
-      if (v.x == v.x) { const double sg = qnt_sigma(v.y); sm += (double)v.x; sv += sg * sg; }
+    if constexpr (W) {
+      QntChainWalk cw;
+      for (int i = tid; i < S; i += QNT_NT) {
+        const float2 v = comp(i);
+        const double o = cw.at(i, Sc, om);
+        if (o > 0.0 && v.x == v.x) { const double sg = qnt_sigma(v.y); sm = fma(o, (double)v.x, sm); sv = fma(o, sg * sg, sv); }
+      }
+    } else {
+      for (int i = tid; i < S; i += QNT_NT) {
+        const float2 v = comp(i);
+        if (v.x == v.x) { const double sg = qnt_sigma(v.y); sm += (double)v.x; sv += sg * sg; }
+      }
     }
     sm = qnt_block_sum(sm, redb);
     sv = qnt_block_sum(sv, redb);
-    const double mean = sm / fk;
+    const double mean = W ? sm : sm / fk;
     double sd2 = 0.0;
-    for (int i = tid; i < S; i += QNT_NT) {
-      const float2 v = comp(i);
-      if (v.x == v.x) { const double d = (double)v.x - mean; sd2 += d * d; }
+    if constexpr (W) {
+      QntChainWalk cw;
+      for (int i = tid; i < S; i += QNT_NT) {
+        const float2 v = comp(i);
+        const double o = cw.at(i, Sc, om);
+        if (o > 0.0 && v.x == v.x) { const double d = (double)v.x - mean; sd2 = fma(o, d * d, sd2); }
+      }
+    } else {
+      for (int i = tid; i < S; i += QNT_NT) {
+        const float2 v = comp(i);
+        if (v.x == v.x) { const double d = (double)v.x - mean; sd2 += d * d; }
+      }
     }
     sd2 = qnt_block_sum(sd2, redb);
-    const double sd = sqrt((sd2 + sv) / fk);
+    const double sd = W ? sqrt(sd2 + sv) : sqrt((sd2 + sv) / fk);
 
     const int nc = 64 / Q, q = lane % Q, cl = lane / Q;     // components a wave takes at a time; this lane's level and slot
     const bool act = lane < nc * Q;
     const double plev = p.lev[q];
     double lo = INFINITY, hi = -INFINITY;
-    for (int sl = 0; sl < p.slices; ++sl) {
-      const double *b = p.part_brk + (((size_t)sl * Nt + n) * Q + q) * 2;
-      lo = fmin(lo, b[0]);
-      hi = fmax(hi, b[1]);
+    if constexpr (W) {     // the bracket over the components that carry weight, in the sweep's layout
+      if (act) {
+        const double zp = p.lev[Q + q];
+        QntChainWalk cw;
+        for (int i = wv * nc + cl; i < S; i += QNT_NW * nc) {
+          const float2 v = comp(i);
+          if (cw.at(i, Sc, om) > 0.0 && v.x == v.x) {
+            const double b = fma(zp, qnt_sigma(v.y), (double)v.x);
+            lo = fmin(lo, b);
+            hi = fmax(hi, b);
+          }
+        }
+      }
+      double a = INFINITY, b = -INFINITY;
+      for (int c = 0; c < nc; ++c) {
+        a = fmin(a, __shfl(lo, q + Q * c));
+        b = fmax(b, __shfl(hi, q + Q * c));
+      }
+      if (lane < Q) { red[wv][lane][0] = a; red[wv][lane][1] = b; }
+      __syncthreads();
+      lo = INFINITY; hi = -INFINITY;
+#pragma unroll
+      for (int w = 0; w < QNT_NW; ++w) { lo = fmin(lo, red[w][q][0]); hi = fmax(hi, red[w][q][1]); }
+      __syncthreads();
+    } else {
+      for (int sl = 0; sl < p.slices; ++sl) {
+        const double *b = p.part_brk + (((size_t)sl * Nt + n) * Q + q) * 2;
+        lo = fmin(lo, b[0]);
+        hi = fmax(hi, b[1]);
+      }
     }
     auto width = [&]() { return 0x1p-25 * fmax(fabs(0.5 * (lo + hi)), sd); };
     double t = fma(p.lev[Q + q], sd, mean);
@@ -160,12 +256,25 @@ __global__ __launch_bounds__(QNT_NT) void k_qnt_solve(const QntParams p) {
       ++sweeps;
       double F = 0.0, f = 0.0;
       if (act && !done) {
-        for (int i = wv * nc + cl; i < S; i += QNT_NW * nc) {
-          const float2 v = comp(i);
-          if (v.x == v.x) {
-            const double rs = qnt_rsigma(v.y), z = (t - (double)v.x) * rs;
-            F += qnt_Phi(z);
-            f += exp(-0.5 * z * z) * rs;
+        if constexpr (W) {
+          QntChainWalk cw;
+          for (int i = wv * nc + cl; i < S; i += QNT_NW * nc) {
+            const float2 v = comp(i);
+            const double o = cw.at(i, Sc, om);
+            if (o > 0.0 && v.x == v.x) {
+              const double rs = qnt_rsigma(v.y), z = (t - (double)v.x) * rs;
+              F = fma(o, qnt_Phi(z), F);
+              f = fma(o, exp(-0.5 * z * z) * rs, f);
+            }
+          }
+        } else {
+          for (int i = wv * nc + cl; i < S; i += QNT_NW * nc) {
+            const float2 v = comp(i);
+            if (v.x == v.x) {
+              const double rs = qnt_rsigma(v.y), z = (t - (double)v.x) * rs;
+              F += qnt_Phi(z);
+              f += exp(-0.5 * z * z) * rs;
+            }
           }
         }
       }
@@ -181,8 +290,8 @@ __global__ __launch_bounds__(QNT_NT) void k_qnt_solve(const QntParams p) {
       for (int w = 0; w < QNT_NW; ++w) { Ft += red[w][q][0]; ft += red[w][q][1]; }
       __syncthreads();
       if (!done) {
-        const double e = Ft / fk - plev;
-        ft *= 0.39894228040143267794 / fk;
+        const double e = W ? Ft - plev : Ft / fk - plev;
+        ft *= W ? 0.39894228040143267794 : 0.39894228040143267794 / fk;
         if (e < 0.0) lo = t; else hi = t;
         if (e == 0.0) lo = t;     // a root, to the last bit (a flat stretch of F at k / S): the bracket closes on it
         const double wd = hi - lo, tl = width();
@@ -208,12 +317,21 @@ __global__ __launch_bounds__(QNT_NT) void k_qnt_solve(const QntParams p) {
   if (p.pit) {
     const double yv = (double)p.y[n];
     double F = 0.0;
-    for (int i = tid; i < S; i += QNT_NT) {
-      const float2 v = comp(i);
-      if (v.x == v.x) F += qnt_Phi((yv - (double)v.x) * qnt_rsigma(v.y));
+    if constexpr (W) {
+      QntChainWalk cw;
+      for (int i = tid; i < S; i += QNT_NT) {
+        const float2 v = comp(i);
+        const double o = cw.at(i, Sc, om);
+        if (o > 0.0 && v.x == v.x) F = fma(o, qnt_Phi((yv - (double)v.x) * qnt_rsigma(v.y)), F);
+      }
+    } else {
+      for (int i = tid; i < S; i += QNT_NT) {
+        const float2 v = comp(i);
+        if (v.x == v.x) F += qnt_Phi((yv - (double)v.x) * qnt_rsigma(v.y));
+      }
     }
     F = qnt_block_sum(F, redb);
-    if (tid == 0) p.pit[n] = (float)(F / fk);
+    if (tid == 0) p.pit[n] = (float)(W ? F : F / fk);
   }
   if (p.sweeps && tid == 0) p.sweeps[n] = sweeps;
 }
@@ -228,6 +346,22 @@ hipError_t mile_launch_quantiles(const QntParams &p, hipStream_t st) {
     k_qnt_solve<true><<<p.Nt, QNT_NT, (size_t)p.S * 8, st>>>(p);
   } else {
     k_qnt_solve<false><<<p.Nt, QNT_NT, 0, st>>>(p);
+  }
+  return hipGetLastError();
+}
+
+hipError_t mile_launch_quantiles_weighted(const QntWParams &p, hipStream_t st) {
+  QntParams pack = p;     // the transpose alone: with no level k_qnt_pack forms no bracket, and its counts are not read
+  pack.Q = 0;
+  k_qnt_pack<<<dim3((p.Nt + QNT_TILE - 1) / QNT_TILE, p.slices), 256, 0, st>>>(pack);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (p.S <= QNT_LDS_MAX_S) {
+    e = mile_set_max_lds<k_qnt_solve<true, QntWParams>>(QNT_LDS_MAX_S * 8);
+    if (e != hipSuccess) return e;
+    k_qnt_solve<true, QntWParams><<<p.Nt, QNT_NT, (size_t)p.S * 8, st>>>(p);
+  } else {
+    k_qnt_solve<false, QntWParams><<<p.Nt, QNT_NT, 0, st>>>(p);
   }
   return hipGetLastError();
 }

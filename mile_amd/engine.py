@@ -685,6 +685,68 @@ class Engine:
                                                        self._stream()), self.lib)
         return self._quantile_result(quant, pit, dropped)
 
+    @staticmethod
+    def _chain_weights(weights, n_chains):
+        from .metrics import chain_weights
+        return (C.c_double * n_chains)(*[float(v) for v in chain_weights(weights, n_chains)])
+
+    def mixture_quantiles_weighted(self, raw, weights, levels, y=None, return_dropped: bool = False):
+        """``mixture_quantiles`` for the chain-weighted mixture (mile_mixture_quantiles_weighted): raw [C, S, N, 2], chain c
+        with weight ``weights[c]`` (>= 0, summing to 1; stacking weights), F_n(t) = sum_c (w_c / K_c) sum_kept Phi(.).  A chain
+        with weight 0 enters no sum; a row on which a weighted chain has no finite draw is NaN.  ``return_dropped`` appends the
+        draws left out per chain and row, int32 [C, N]."""
+        lv, Q = self._quantile_levels(levels)
+        raw = _f32(raw, self.device, name='raw')
+        if raw.ndim != 4 or raw.shape[-1] != 2:
+            raise ValueError('raw must be [C, S, N, 2]')
+        n_chains, S, N = (int(v) for v in raw.shape[:3])
+        w = self._chain_weights(weights, n_chains)
+        r = raw.contiguous()
+        y, quant, pit, _ = self._quantile_outputs(N, Q, y, False)
+        dropped = torch.empty((n_chains, N), dtype=torch.int32, device=self.device) if return_dropped else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_mixture_quantiles_weighted(_ptr(r), n_chains, S, N, w, lv, Q, _ptr(y), _ptr(quant), _ptr(pit),
+                                                                _ptr(dropped), self._stream()), self.lib)
+        return self._quantile_result(quant, pit, dropped)
+
+    def predict_quantiles_weighted_workspace(self, C: int, S: int, N: int) -> int:
+        """Bytes of the workspace ``predict_quantiles_weighted`` keeps in the handle for C chains of S draws on N rows with the
+        library's own tile (mile_predict_quantiles_weighted_workspace)."""
+        return int(self.lib.mile_predict_quantiles_weighted_workspace(self._h, int(C), int(S), int(N)))
+
+    def predict_quantiles_weighted(self, theta, X, weights, levels, y=None, *, max_draws_per_pass: int = 0,
+                                   max_rows_per_tile: int = 0, return_dropped: bool = False):
+        """``mixture_quantiles_weighted`` of ``predict``'s outputs for draws theta [C, S, d] on X [N, F] without ever holding
+        them (mile_predict_quantiles_weighted), with ``predict_quantiles``' tiles and passes; the result does not depend on the
+        two sizes, bit for bit.  Regression only."""
+        if self.spec.task != 'regr':
+            raise ValueError('predict_quantiles_weighted: a regression model is needed')
+        lv, Q = self._quantile_levels(levels)
+        lead, th, X, _ = self._eval_inputs(theta, X)
+        if len(lead) != 2:
+            raise ValueError('theta must be [C, S, d]')
+        n_chains, S = int(lead[0]), int(lead[1])
+        w = self._chain_weights(weights, n_chains)
+        N = int(X.shape[0])
+        y, quant, pit, _ = self._quantile_outputs(N, Q, y, False)
+        dropped = torch.empty((n_chains, N), dtype=torch.int32, device=self.device) if return_dropped else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_predict_quantiles_weighted(self._h, _ptr(th), n_chains, S, _ptr(X), N, w, lv, Q, _ptr(y),
+                                                                _ptr(quant), _ptr(pit), _ptr(dropped), int(max_draws_per_pass),
+                                                                int(max_rows_per_tile), self._stream()), self.lib)
+        return self._quantile_result(quant, pit, dropped)
+
+    def predict_moments_by_chain(self, theta, X, *, max_draws_per_pass: int = 0):
+        """``predict_moments`` of each chain's draws: theta [C, S, d] -> (moments [C, N, W] fp32, kept [C, N] int32, the
+        chain's draws with finite outputs on the row) -- what ``metrics.weighted_moments`` and ``weighted_class_probs``
+        combine.  The same forwards in all as one ``predict_moments`` of every draw."""
+        theta = _f32(theta, self.device, name='theta')
+        if theta.ndim != 3:
+            raise ValueError('theta must be [C, S, d]')
+        res = [self.predict_moments(theta[c], X, max_draws_per_pass=max_draws_per_pass, return_dropped=True)
+               for c in range(theta.shape[0])]
+        return torch.stack([m for m, _ in res]), torch.stack([int(theta.shape[1]) - d for _, d in res])
+
     def debug_quantile_sweeps(self):
         """(rows, total sweeps, most sweeps of a row) of the solver in the last ``predict_quantiles`` (test and tool hook)."""
         rows, total, most = C.c_int64(), C.c_int64(), C.c_int32()

@@ -825,6 +825,114 @@ def coverage_from_pit(pit: torch.Tensor, coverages) -> torch.Tensor:
     return ((v[None] - 0.5).abs() <= c[:, None] / 2).to(torch.float64).mean(dim=1)
 
 
+# ---- the chain-weighted mixture (stacking weights): the torch restatement of mile_mixture_quantiles_weighted
+# (Engine.mixture_quantiles_weighted / predict_quantiles_weighted), and the exact composition of per-chain moments and class
+# probabilities.  F_n(t) = sum_c (w_c / K_c) sum_{i in c, kept} Phi((t - mu_i) / sigma_i); a chain with w_c = 0 enters no sum,
+# a chain with w_c > 0 and nothing kept on a row makes that row NaN.
+
+def chain_weights(weights, C: int) -> torch.Tensor:
+    """One chain weight vector, checked as the library checks it (``crps_weights`` for a single vector): [C], every entry finite
+    and >= 0, summing to 1 within 1e-9 -> float64 [C] on the host."""
+    w = torch.as_tensor(weights, dtype=torch.float64).detach().cpu()
+    if w.ndim != 1 or w.shape[0] != C:
+        raise ValueError(f'weights must be [{C}], one per chain')
+    return crps_weights(w, C)[0]
+
+
+def _weighted_components(raw: torch.Tensor, weights):
+    """raw [C, S, N, 2] -> mu, sigma [C, S, N] float64, omega [C, S, N] = w_c / K_c on the kept draws of the chains that carry
+    weight and 0 elsewhere, the kept mask [C, S, N] and the rows [N] on which a weighted chain has nothing kept."""
+    if raw.ndim != 4 or raw.shape[-1] != 2:
+        raise ValueError('raw must be [C, S, N, 2]')
+    w = chain_weights(weights, int(raw.shape[0])).to(raw.device)
+    ok = torch.isfinite(raw).all(dim=-1)
+    o = torch.where(ok[..., None], raw, torch.zeros_like(raw)).to(torch.float64)
+    K = ok.sum(dim=1)                                                       # [C, N]
+    use = (w > 0)[:, None] & (K > 0)
+    om = torch.where(use, w[:, None] / K.clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=raw.device))
+    bad = ((w > 0)[:, None] & (K == 0)).any(dim=0)
+    return o[..., 0], torch.exp(o[..., 1]).clamp(min=1e-6, max=1e6), om[:, None, :] * ok, ok, bad
+
+
+def weighted_mixture_quantiles(raw: torch.Tensor, weights, levels, return_dropped: bool = False, steps: int = 200):
+    """raw [C, S, N, 2] (mu, log sigma), weights [C], levels [Q] strictly inside (0, 1) -> [N, Q] float64: the roots of the
+    chain-weighted F_n(t) = p by ``steps`` bisections of the exact bracket, min and max of mu_i + Phi^-1(p) sigma_i over the
+    components that carry weight.  ``return_dropped`` also returns the draws left out per chain and row, int32 [C, N]."""
+    mu, sig, om, ok, bad = _weighted_components(raw, weights)
+    p = torch.as_tensor(levels, dtype=torch.float64, device=mu.device).reshape(-1)
+    if p.numel() < 1 or not bool(((p > 0) & (p < 1)).all()):
+        raise ValueError('levels must lie strictly inside (0, 1)')
+    N = mu.shape[-1]
+    mu, sig, om = mu.reshape(-1, N), sig.reshape(-1, N), om.reshape(-1, N)
+    on = (om > 0)[..., None]
+    b = mu[..., None] + torch.special.ndtri(p) * sig[..., None]             # [C * S, N, Q]
+    inf = torch.full_like(b, float('inf'))
+    lo = torch.where(on, b, inf).amin(dim=0)
+    hi = torch.where(on, b, -inf).amax(dim=0)
+    for _ in range(steps):
+        mid = lo + 0.5 * (hi - lo)
+        F = (torch.special.ndtr((mid[None] - mu[..., None]) / sig[..., None]) * om[..., None]).sum(dim=0)
+        below = F < p[None]
+        lo, hi = torch.where(below, mid, lo), torch.where(below, hi, mid)
+    out = lo + 0.5 * (hi - lo)
+    out = torch.where(bad[:, None], torch.full_like(out, float('nan')), out)
+    if return_dropped:
+        return out, (ok.shape[1] - ok.sum(dim=1)).to(torch.int32)
+    return out
+
+
+def weighted_mixture_pit(raw: torch.Tensor, weights, y) -> torch.Tensor:
+    """raw [C, S, N, 2], weights [C], y [N] -> the chain-weighted F_n(y_n), float64 [N], NaN where a weighted chain has
+    nothing kept."""
+    mu, sig, om, _, bad = _weighted_components(raw, weights)
+    t = torch.as_tensor(y, device=mu.device).to(torch.float64).reshape(-1)
+    F = (torch.special.ndtr((t - mu) / sig) * om).sum(dim=(0, 1))
+    return torch.where(bad, torch.full_like(F, float('nan')), F)
+
+
+def weighted_moments(per_chain: torch.Tensor, kept: torch.Tensor, weights, task: str) -> torch.Tensor:
+    """The chain-weighted mixture's moments from the chains' own: per_chain [C, N, W] (``predictive_moments`` /
+    Engine.predict_moments of each chain's draws), kept [C, N] (the chain's kept draws on the row), weights [C] -> [N, W]
+    float64.  Regression, by the law of total variance with (m_c, e_c, a_c) = per_chain[c]: mean = sum w_c m_c, epistemic =
+    sum w_c (e_c + (m_c - mean)^2), aleatoric = sum w_c a_c.  Classification: P = sum w_c P_c, the entropy of P and the mutual
+    information H(P) - sum w_c mean-entropy_c (clamped at 0), the chain's mean entropy being H(P_c) - MI_c.  A chain with w_c = 0
+    enters no sum; a row on which a chain with w_c > 0 has nothing kept is NaN."""
+    C = int(per_chain.shape[0])
+    w = chain_weights(weights, C).to(per_chain.device)
+    m = per_chain.to(torch.float64)
+    on = (w > 0)[:, None] & (kept.to(per_chain.device) > 0)                 # [C, N]
+    bad = ((w > 0)[:, None] & ~on).any(dim=0)
+    m = torch.where(on[..., None], m, torch.zeros_like(m))
+    wc = (w[:, None] * on)[..., None]                                       # [C, N, 1]
+    if task in ('regr', 'regression'):
+        mean = (wc * m[..., 0:1]).sum(dim=0)                                # [N, 1]
+        epi = (wc * (m[..., 1:2] + (m[..., 0:1] - mean) ** 2)).sum(dim=0)
+        res = torch.cat([mean, epi, (wc * m[..., 2:3]).sum(dim=0)], dim=-1)
+    else:
+        K = m.shape[-1] - 2
+        P = (wc * m[..., :K]).sum(dim=0)
+        h = -torch.special.xlogy(P, P).sum(dim=-1)
+        h_c = -torch.special.xlogy(m[..., :K], m[..., :K]).sum(dim=-1) - m[..., K + 1]      # the chain's mean draw entropy
+        mi = (h - (wc[..., 0] * h_c).sum(dim=0)).clamp(min=0)
+        res = torch.cat([P, h[:, None], mi[:, None]], dim=-1)
+    return torch.where(bad[:, None], torch.full_like(res, float('nan')), res)
+
+
+def weighted_class_probs(probs: torch.Tensor, kept: torch.Tensor, weights):
+    """P = sum_c w_c P_c of per-chain mean softmax probabilities probs [C, N, K] with kept [C, N] -> (P [N, K] float64,
+    kept [N] int32): kept is 0, and P NaN, on a row where a chain with w_c > 0 has nothing kept, else the kept draws of the
+    chains that carry weight -- the pair ``calibration_decide`` takes as one group."""
+    C = int(probs.shape[0])
+    w = chain_weights(weights, C).to(probs.device)
+    kept = kept.to(probs.device)
+    on = (w > 0)[:, None] & (kept > 0)
+    bad = ((w > 0)[:, None] & ~on).any(dim=0)
+    p = torch.where(on[..., None], probs.to(torch.float64), torch.zeros((), dtype=torch.float64, device=probs.device))
+    P = ((w[:, None] * on)[..., None] * p).sum(dim=0)
+    k = torch.where(bad, torch.zeros_like(kept[0]), (kept * on).sum(dim=0)).to(torch.int32)
+    return torch.where(bad[:, None], torch.full_like(P, float('nan')), P), k
+
+
 # ---- PSIS-LOO and WAIC of the ensemble: the torch restatement of mile_psis_loo (Engine.psis_loo / loo_stream), over a
 # pointwise tensor that fits in memory.  The timing tool's yardstick, and what a CPU tensor gets.  All fp64.
 

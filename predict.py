@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Posterior-predictive moments of a finished experiment on NEW inputs (the consumer of mile_predict_moments):
 
-    python predict.py -e results/mile_amd/<experiment> -i <table or .npz> [-o predictions.npz] [--draws-per-pass K] [--intervals C [C ...]] [--sets C [C ...]]
+    python predict.py -e results/mile_amd/<experiment> -i <table or .npz> [-o predictions.npz] [--draws-per-pass K] [--intervals C [C ...]] [--sets C [C ...]] [--weights PATH|stacking]
 
 Reloads config.yaml and the samples the way evaluate.py does, applies the training normalisation the loader recorded
 (normalization.npz, written by train.py) to the rows of the table, reduces all C x S draws on the device and writes, per row:
@@ -13,6 +13,12 @@ Reloads config.yaml and the samples the way evaluate.py does, applies the traini
                      quantiles [N, Q] of the ensemble's predictive mixture, solved exactly on the device (target units)
     --sets C..       classification: set_levels [Q], class_order [N, K] (the classes by descending ensemble probability) and
                      set_size [N, Q]: the highest-probability set of level C is the first set_size entries of class_order
+    --weights PATH   predict with the chain-weighted mixture sum_c w_c p_c instead of the equal-weight one: every output above is
+                     that mixture's (the moments composed exactly from the chains' own, the quantiles by
+                     mile_predict_quantiles_weighted, the sets from P = sum_c w_c P_c), ``dropped`` becomes [C, N] and
+                     ``chain_weights`` [C] is added.  PATH: an .npz with ``weights``, a .npy or a text vector; ``stacking``:
+                     <experiment>/stacking.npz, as evaluate.py --stacking wrote it.  One weight per chain LOADED: a vector of
+                     another length is refused (evaluate and predict with the same --drop-nonfinite)
 
 The table holds one row per input and the model's features as columns (no target column): .npy, .csv (comma), .data / .txt
 (whitespace), or an .npz with an array ``x`` (images [N, C, H, W], token ids [N, T]).  Where the target was z-scored
@@ -41,6 +47,47 @@ def read_table(path) -> np.ndarray:
     if path.endswith('.data') or path.endswith('.txt'):
         return np.atleast_2d(np.loadtxt(path, dtype=np.float32))
     raise SystemExit(f'{path}: expected .npy, .csv, .data, .txt or .npz')
+
+
+def read_weights(path, exp: Path, n_chains: int) -> np.ndarray:
+    """--weights: the vector of ``path`` (``stacking``: <exp>/stacking.npz), one weight per loaded chain, float64 [C] >= 0
+    summing to 1.  A solver's round-off is taken out first: entries in (-1e-9, 0) become 0 and a sum within 1e-6 of 1 is
+    renormalised; anything further off is refused."""
+    from mile_amd.metrics import chain_weights
+    f = str(exp / 'stacking.npz') if path == 'stacking' else str(path)
+    if not Path(f).exists():
+        raise SystemExit(f'--weights: {f} does not exist' + (' (run evaluate.py --stacking first)' if path == 'stacking' else ''))
+    if f.endswith('.npz'):
+        with np.load(f) as z:
+            if 'weights' not in z:
+                raise SystemExit(f'--weights: {f} has no array "weights"')
+            w = np.asarray(z['weights'], dtype=np.float64)
+    elif f.endswith('.npy'):
+        w = np.asarray(np.load(f), dtype=np.float64)
+    else:
+        w = np.atleast_1d(np.loadtxt(f, dtype=np.float64, delimiter=',' if f.endswith('.csv') else None))
+    w = w.reshape(-1)
+    if w.shape[0] != n_chains:
+        raise SystemExit(f'--weights: {f} holds {w.shape[0]} weights, {n_chains} chains are loaded: one weight per chain, in the '
+                         'order of the chains loaded (the same --drop-nonfinite as the run that solved them)')
+    w = np.where((w < 0) & (w > -1e-9), 0.0, w)
+    if abs(w.sum() - 1.0) <= 1e-6:
+        w = w / w.sum()
+    try:
+        return chain_weights(w, n_chains).numpy()
+    except ValueError as e:
+        raise SystemExit(f'--weights: {f}: {e}')
+
+
+def weighted_predictions(eng, samples, x, w, task, draws_per_pass):
+    """The moment arrays of the chain-weighted mixture: per-chain moments on the device, composed on the host."""
+    from evaluate import moment_metrics
+    from mile_amd.metrics import weighted_moments
+    mom, kept = eng.predict_moments_by_chain(samples, x, max_draws_per_pass=draws_per_pass)
+    _, arrays = moment_metrics(weighted_moments(mom, kept, w, task), torch.zeros(1), np.zeros(len(x), dtype=np.float32), task)
+    arrays['dropped'] = (samples.shape[1] - kept).cpu().numpy().astype(np.int32)
+    arrays['chain_weights'] = np.asarray(w, dtype=np.float64)
+    return arrays, mom, kept
 
 
 def load_normalization(exp: Path, loader) -> dict:
@@ -80,6 +127,9 @@ def build_parser():
                     help='classification: also the highest-probability prediction sets of the ensemble at these coverage levels '
                          '(mile_calibration_stream): set_levels [Q], class_order [N, K] and set_size [N, Q]; the set of a level is the '
                          'first set_size entries of class_order')
+    ap.add_argument('--weights', default=None, metavar='PATH',
+                    help='chain weights (stacking): every output is the weighted mixture\'s.  An .npz with an array weights, a .npy '
+                         'or a text vector with one weight per loaded chain; "stacking": <experiment>/stacking.npz')
     ap.add_argument('--normalized', action='store_true',
                     help='the rows already are in the training normalisation; the outputs stay in it')
     ap.add_argument('--drop-nonfinite', action='store_true', help='leave out chains with non-finite samples, as evaluate.py does')
@@ -106,6 +156,7 @@ def main():
     bad_chains = ~np.isfinite(samples).all(axis=(1, 2))
     if args.drop_nonfinite and bad_chains.any() and not bad_chains.all():
         samples = samples[~bad_chains]
+    weights = read_weights(args.weights, exp, samples.shape[0]) if args.weights else None
     x = read_table(args.input)
     norm = {} if args.normalized else load_normalization(exp, tr.loader)
     if 'x_mean' in norm:
@@ -117,14 +168,22 @@ def main():
         raise SystemExit(f'{args.input}: rows of {x.shape[1]} values, the model takes {spec.in_features}')
     eng = tr.prob_model.engine(torch.from_numpy(np.ascontiguousarray(tr.loader.train_x).reshape(len(tr.loader.train_x), -1)),
                                torch.from_numpy(np.ascontiguousarray(tr.loader.train_y)), device=args.device)
-    mom, dropped = eng.predict_moments(torch.from_numpy(samples), torch.from_numpy(x), max_draws_per_pass=args.draws_per_pass,
-                                       return_dropped=True)
-    _, arrays = moment_metrics(mom, dropped, np.zeros(len(x), dtype=np.float32), cfg.data.task)
+    if weights is None:
+        mom, dropped = eng.predict_moments(torch.from_numpy(samples), torch.from_numpy(x), max_draws_per_pass=args.draws_per_pass,
+                                           return_dropped=True)
+        _, arrays = moment_metrics(mom, dropped, np.zeros(len(x), dtype=np.float32), cfg.data.task)
+    else:
+        arrays, mom_c, kept_c = weighted_predictions(eng, torch.from_numpy(samples), torch.from_numpy(x), weights, cfg.data.task,
+                                                     args.draws_per_pass)
     arrays = denormalize(arrays, norm)
     if args.intervals:
         from mile_amd.metrics import interval_levels
         levels = torch.unique(torch.cat([interval_levels(args.intervals), torch.tensor([0.5], dtype=torch.float64)]), sorted=True)
-        quant = eng.predict_quantiles(torch.from_numpy(samples), torch.from_numpy(x), levels, max_draws_per_pass=args.draws_per_pass)
+        if weights is None:
+            quant = eng.predict_quantiles(torch.from_numpy(samples), torch.from_numpy(x), levels, max_draws_per_pass=args.draws_per_pass)
+        else:
+            quant = eng.predict_quantiles_weighted(torch.from_numpy(samples), torch.from_numpy(x), weights, levels,
+                                                   max_draws_per_pass=args.draws_per_pass)
         q = quant.double().cpu().numpy()
         if 'y_std' in norm:
             q = q * float(norm['y_std'].reshape(-1)[0]) + float(norm['y_mean'].reshape(-1)[0])
@@ -132,7 +191,11 @@ def main():
         arrays['quantiles'] = q.astype(np.float32)
     if args.sets:
         levels = sorted(float(c) for c in args.sets)
-        if spec.hidden_structure[-1] <= 64:
+        if weights is not None:                                            # P = sum_c w_c P_c of the per-chain moments above
+            from mile_amd.metrics import calibration_decide, weighted_class_probs
+            P, kept = weighted_class_probs(mom_c[..., :-2].double(), kept_c, weights)
+            res = calibration_decide(P[None], kept[None], None, levels)
+        elif spec.hidden_structure[-1] <= 64:
             res = eng.calibration_stream(torch.from_numpy(samples), torch.from_numpy(x), coverages=levels, max_draws_per_pass=args.draws_per_pass)
         else:                                                              # more classes than the kernels take: the torch form
             from mile_amd.metrics import classification_calibration
