@@ -3,7 +3,7 @@
 mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
 src/inference/metrics.py:247-312):
 
-    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--function-diagnostics [N_SPLITS]] [--canonical-diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo] [--stacking]
+    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--function-diagnostics [N_SPLITS]] [--canonical-diagnostics [N_SPLITS]] [--tail-diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo] [--stacking]
 
 Reloads config.yaml and the samples/<chain>/sample_<n>.npz files, rebuilds the data split with the same
 seed, evaluates all C x S samples on the split in one device pass and writes metrics.json next to them.
@@ -109,6 +109,32 @@ def diagnostic_keys(prefix, arr, spec, n_splits):
     return out
 
 
+def tail_diagnostic_metrics(samples, n_splits, device):
+    """--tail-diagnostics: the pooled bulk / tail / mean ESS, the MCSE of the mean and the folded split R-hat of EVERY parameter of
+    the finite chains (mile_amd.metrics.tail_diagnostics: mile_chain_diagnostics_tail on the device).  samples [C, S, d] (host).
+    Returns the dtail_* keys of metrics.json and the arrays of tail_diagnostics.npz."""
+    from mile_amd import metrics as M
+    fin = np.isfinite(samples).all(axis=(1, 2))
+    ok = np.ascontiguousarray(samples[fin])
+    if ok.shape[0] == 0:
+        raise SystemExit('--tail-diagnostics: no chain with finite samples')
+    xt = torch.from_numpy(ok).to(device)
+    res = M.tail_diagnostics(xt, n_splits)
+    rhat = M.chain_diagnostics(xt, n_splits)['rhat']
+    return tail_keys('dtail', res, ok.shape[0] * ok.shape[1], n_splits, rhat)
+
+
+def tail_keys(prefix, res, n_draws, n_splits, rhat):
+    """The metrics.json keys of a tail_diagnostics result under ``prefix`` (dtail: the parameters as sampled; fdiag_tail: the
+    function-space columns; cdiag_tail: the canonical ordering) with ``rhat``, the rank R-hat of the same columns, and the arrays
+    for tail_diagnostics.npz under the same prefix (none for dtail)."""
+    from mile_amd import metrics as M
+    keys = M.tail_diagnostics_summary(res, n_draws, n_splits, rhat=rhat, prefix=prefix)
+    stem = '' if prefix == 'dtail' else prefix[:-len('tail')]
+    arrays = {stem + k: res[k].detach().cpu().numpy() for k in M.TAIL_OUTPUTS + ('quantiles',)}
+    return keys, arrays
+
+
 def canonical_refusal(model, activation, sign):
     """Why --canonical-diagnostics cannot run on an experiment of ``model`` with ``activation``, or None."""
     if model != 'FCN':
@@ -120,7 +146,7 @@ def canonical_refusal(model, activation, sign):
     return None
 
 
-def canonical_diagnostic_metrics(samples, spec, n_splits, key, sign, device):
+def canonical_diagnostic_metrics(samples, spec, n_splits, key, sign, device, tail_splits=None):
     """--canonical-diagnostics: the statistics of --diagnostics on the canonical hidden-unit ordering of the finite chains
     (mile_amd.metrics.canonical_diagnostics: mile_canonicalize_fcn, then mile_chain_diagnostics, on the device), and how often the
     order of each hidden layer changes from one draw to the next.  samples [C, S, d] (host).  Returns the cdiag_* keys of
@@ -136,10 +162,14 @@ def canonical_diagnostic_metrics(samples, spec, n_splits, key, sign, device):
     out['cdiag_key'], out['cdiag_sign'] = key, bool(sign)
     for l in range(arr['switches'].shape[1]):
         out[f'cdiag_switch_rate_layer{l}'] = float(np.mean(arr['switches'][:, l] / max(ok.shape[1] - 1, 1)))
-    return out, arr
+    if tail_splits is None:
+        return out, arr
+    from mile_amd import metrics as M
+    canon = M.canonicalize(spec, torch.from_numpy(ok).to(device), key, sign, return_perm=True)[0]
+    return out, arr, tail_keys('cdiag_tail', M.tail_diagnostics(canon, tail_splits), ok.shape[0] * ok.shape[1], tail_splits, res['rhat'])
 
 
-def function_diagnostic_metrics(eng, samples, x, y, task, n_splits):
+def function_diagnostic_metrics(eng, samples, x, y, task, n_splits, tail_splits=None):
     """--function-diagnostics: ESS, split R-hat and within / between chain variance of what the finite chains PREDICT on the
     split's rows (mile_amd.metrics.function_diagnostics: mile_function_diagnostics on the device).  samples [C, S, d] (host).
     Returns the fdiag_* keys of metrics.json and the arrays of function_diagnostics.npz."""
@@ -148,12 +178,16 @@ def function_diagnostic_metrics(eng, samples, x, y, task, n_splits):
     ok = np.ascontiguousarray(samples[fin])
     if ok.shape[0] == 0:
         raise SystemExit('--function-diagnostics: no chain with finite samples')
-    res = M.function_diagnostics(eng, torch.from_numpy(ok), torch.from_numpy(x), torch.from_numpy(y), n_splits=n_splits)
+    res = M.function_diagnostics(eng, torch.from_numpy(ok), torch.from_numpy(x), torch.from_numpy(y), n_splits=n_splits,
+                                 return_columns=tail_splits is not None)
     out = {'fdiag_n_splits': int(n_splits), 'fdiag_chain_ids': [int(c) for c in np.nonzero(fin)[0]]}
     out.update(M.function_diagnostics_summary(res, int(x.shape[0]), int(res['Q']), task))
     arrays = {k: res[k].detach().cpu().numpy() for k in ('wcv', 'bcv', 'rhat', 'ess', 'crhat', 'loglik_sum', 'chain_summary')}
     arrays['Q'] = np.int64(res['Q'])
-    return out, arrays
+    if tail_splits is None:
+        return out, arrays
+    tail = M.tail_diagnostics(res['columns'], tail_splits, plane=True)                # every column, the summed log-likelihood's too
+    return out, arrays, tail_keys('fdiag_tail', tail, ok.shape[0] * ok.shape[1], tail_splits, res['rhat'])
 
 
 def moment_metrics(moments, dropped, y, task):
@@ -378,6 +412,15 @@ def build_parser():
                          'a reference mode, and a high rate says the key does not separate the units of this posterior); wcv, bcv, '
                          'rhat, ess, crhat, switches in canonical_diagnostics.npz.  No ReLU rescaling, no sigmoid reflection; hidden '
                          'widths above 1024 run in plain torch')
+    ap.add_argument('--tail-diagnostics', type=int, nargs='?', const=2, default=None, metavar='N_SPLITS',
+                    help='tail diagnostics of ALL parameters of the finite chains on the device (mile_chain_diagnostics_tail): the '
+                         'POOLED multi-chain ESS of the rank-normalised draws (bulk), of the 5 %% / 95 %% tails and of the mean, the '
+                         'Monte Carlo standard error of the posterior mean, and the split R-hat of the draws folded about their median, '
+                         'which sees chains that agree in location and differ in scale.  dtail_* keys in metrics.json (ess_bulk and '
+                         'ess_tail min / median, rhat_folded median / max, rhat_rank_max = max over the parameters of max(rhat, '
+                         'rhat_folded), mcse_mean_over_sd_max, ess_bulk_share) and ess_bulk, ess_tail, ess_mean, mcse_mean, '
+                         'rhat_folded, quantiles in tail_diagnostics.npz.  With --function-diagnostics also fdiag_tail_* (every '
+                         'function-space column, fdiag_* arrays in the npz), with --canonical-diagnostics also cdiag_tail_*')
     ap.add_argument('--canonical-key', choices=['bias', 'norm'], default='bias',
                     help='--canonical-diagnostics orders the hidden units by their bias (default) or by the squared norm of their '
                          'bias and incoming weights')
@@ -562,15 +605,28 @@ def main():
     out.update(diag)
     if diag_arrays is not None:
         np.savez(exp / 'diagnostics.npz', **diag_arrays)
+    tail_arrays = {}
+    if args.tail_diagnostics is not None:
+        keys, tail_arrays = tail_diagnostic_metrics(samples, args.tail_diagnostics, args.device)
+        out.update(keys)
     if args.function_diagnostics is not None:
-        keys, arrays = function_diagnostic_metrics(eng, samples, x, np.ascontiguousarray(y), cfg.data.task, args.function_diagnostics)
+        keys, arrays, *tail = function_diagnostic_metrics(eng, samples, x, np.ascontiguousarray(y), cfg.data.task,
+                                                          args.function_diagnostics, args.tail_diagnostics)
         out.update(keys)
         np.savez(exp / 'function_diagnostics.npz', **arrays)
+        for tk, ta in tail:
+            out.update(tk)
+            tail_arrays.update(ta)
     if args.canonical_diagnostics is not None:
-        keys, arrays = canonical_diagnostic_metrics(samples, spec, args.canonical_diagnostics, args.canonical_key, args.canonical_sign,
-                                                    args.device)
+        keys, arrays, *tail = canonical_diagnostic_metrics(samples, spec, args.canonical_diagnostics, args.canonical_key,
+                                                           args.canonical_sign, args.device, args.tail_diagnostics)
         out.update(keys)
         np.savez(exp / 'canonical_diagnostics.npz', **arrays)
+        for tk, ta in tail:
+            out.update(tk)
+            tail_arrays.update(ta)
+    if tail_arrays:
+        np.savez(exp / 'tail_diagnostics.npz', **tail_arrays)
     if args.moments:
         mom, dropped = eng.predict_moments(torch.from_numpy(samples), torch.from_numpy(x), return_dropped=True)
         keys, arrays = moment_metrics(mom, dropped, np.ascontiguousarray(y), cfg.data.task)

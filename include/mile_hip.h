@@ -772,6 +772,62 @@ int32_t mile_function_diagnostics(mile_sampler *s, const float *theta, int32_t C
                                   int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream);
 int64_t mile_function_diagnostics_workspace(const mile_sampler *s, int32_t C, int32_t S, int64_t N, int32_t with_y);
 
+/* Which outputs mile_chain_diagnostics_tail computes (`what`), and how it reads its input. */
+#define MILE_DTAIL_ESS_BULK 1u
+#define MILE_DTAIL_ESS_TAIL 2u
+#define MILE_DTAIL_ESS_MEAN 4u      /* ess_mean and mcse_mean */
+#define MILE_DTAIL_RHAT_FOLDED 8u
+#define MILE_DTAIL_PLANE_INPUT 16u  /* samples are [d][C][S] (the `columns` of mile_function_diagnostics): no transpose */
+
+/* Tail diagnostics of the ensemble (Vehtari, Gelman, Simpson, Carpenter & Buerkner 2021): the POOLED effective sample size
+ * of the bulk, of the 5 % / 95 % tails and of the mean, the Monte Carlo standard error of the posterior mean, and the split
+ * R-hat of the draws folded about their median, which sees chains that agree in location and differ in scale.  Needs no
+ * model; launches on the current device.  This comment is the one statement of the definitions.
+ * One column has draws x[c][s] (fp32), n = C*S, len = S / n_splits and M = C * n_splits pieces x.reshape(M, len).
+ *   order statistics, of the pooled sorted fp32 draws xs[0..n), integer indices only:
+ *         q_lo = xs[(n + 19) / 20 - 1]            (index ceil(n / 20) - 1)
+ *         q_hi = xs[(19 * n + 19) / 20 - 1]       (index ceil(19 n / 20) - 1)
+ *         m32  = fl32((double(xs[(n - 1) / 2]) + double(xs[n / 2])) / 2)
+ *         quantiles [3][d] holds q_lo, q_hi, m32 in this order: the draws themselves, bit for bit.
+ *   series z: the pooled normal scores of x, ranked as for mile_chain_diagnostics (ties get their average rank);
+ *         I_lo = (x <= q_lo), I_hi = (x <= q_hi) as 0 / 1;  x itself;
+ *         zf: the pooled normal scores of the folded draws f = |x - m32|, the subtraction in fp32.
+ *   ESS_mc(v), the multi-chain estimator of Stan and blackjax on the M pieces, all in fp64:
+ *         mean_acov[k]  the mean over the pieces of the biased autocovariance at lag k about the piece's own mean
+ *         mean_var0     mean_acov[0] * len / (len - 1)
+ *         weighted_var  mean_acov[0] + the ddof-1 variance of the M piece means (that term only when M > 1)
+ *         rho_k         1 - (mean_var0 - mean_acov[k]) / weighted_var, rho_0 = 1
+ *         Geyer's initial positive and initial monotone sequences on the pairs rho_2t + rho_2t+1, t < floor(len / 2), as in
+ *         the single-chain estimator of mile_chain_diagnostics; tau floored at 1 / log10(n); ESS_mc = n / tau.
+ *         A weighted_var that is not a positive finite number (a series constant over all pooled draws, a non-finite draw)
+ *         gives NaN.
+ *   outputs (device, fp32 [d], null where not asked for):
+ *         ess_bulk = ESS_mc(z);  ess_tail = min(ESS_mc(I_lo), ESS_mc(I_hi)), NaN if either is;  ess_mean = ESS_mc(x);
+ *         mcse_mean = sd / sqrt(ess_mean), sd the ddof-1 standard deviation of the n draws in fp64;
+ *         rhat_folded: the pooled split R-hat of mile_chain_diagnostics (its kernels, no other arithmetic) on zf.
+ *         A NaN draw makes every output of its column NaN, and its quantiles.  quantiles may be null.
+ * Every sum is added in a fixed order, without atomics: the outputs are bitwise reproducible and do not depend on how the
+ * parameters were walked in chunks of the workspace.
+ * MILE_ERR_INVALID, with nothing launched: null samples; C outside [1, 65535], S outside [MILE_DIAG_S_MIN, MILE_DIAG_S_MAX],
+ * d < 1; n_splits < 1 or not a divisor of S, S / n_splits < 2; no statistic or unknown bits in `what`; a null pointer for an
+ * output asked for (MILE_DTAIL_ESS_MEAN needs ess_mean and mcse_mean); and, "unsupported", C*S > MILE_DIAG_POOL_MAX with
+ * anything that needs the pooled sort: ESS_BULK, ESS_TAIL, RHAT_FOLDED or quantiles (sort those outside and pass the series
+ * to mile_multichain_ess, zf to mile_chain_diagnostics with MILE_DIAG_RHAT | MILE_DIAG_POOLED_INPUT).  MILE_ERR_STATE, with
+ * nothing launched: a workspace below that of min(d, 32) parameters.  mile_chain_diagnostics_tail_workspace: the size that
+ * lets the call run in the fewest launches it will use; -1 for a bad shape.
+ *
+ * mile_multichain_ess: ESS_mc of m given series, no ranking, at any C*S in the shape range above.  series [C][S][m] fp32, or
+ * [m][C][S] with plane_input != 0 (then no workspace is needed and its size is 0); ess [m] fp32.  The same errors: null
+ * series or ess, the shape (m for d), n_splits, a workspace below min(m, 32) series.
+ * (Added under ABI 10: four new symbols, no struct or existing entry changed.) */
+int32_t mile_chain_diagnostics_tail(const float *samples, int32_t C, int32_t S, int64_t d, int32_t n_splits, uint32_t what,
+                                    float *ess_bulk, float *ess_tail, float *ess_mean, float *mcse_mean, float *rhat_folded,
+                                    float *quantiles, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t mile_chain_diagnostics_tail_workspace(int32_t C, int32_t S, int64_t d, uint32_t what);
+int32_t mile_multichain_ess(const float *series, int32_t C, int32_t S, int64_t m, int32_t n_splits, int32_t plane_input,
+                            float *ess, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t mile_multichain_ess_workspace(int32_t C, int32_t S, int64_t m, int32_t plane_input);
+
 /* Partition sampling (sampler.partition_sampling of the reference: src/training/partition_sampling.py:304-315 partition_params,
  * src/training/trainer.py:593-659): only the FIRST and the LAST layer of an FCN are sampled; every other layer keeps, per chain,
  * the values of `frozen`.  Target: log_prior(sampled coordinates only) + log_likelihood(full net on sampled U frozen).

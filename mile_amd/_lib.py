@@ -18,6 +18,7 @@ GRAD_KERNEL_IDS = {'auto': 0, 'generic': 1, 'mfma_w64': 2, 'mfma_w128_bf16': 3, 
                    'lenetti_f32': 11, 'attn_f32': 12, 'attn_pre_f32': 13, 'attn_wide_f32': 14, 'lenet_bf16x3': 15}
 DIAG_BITS = {'wcv': 1, 'bcv': 2, 'ess': 4, 'crhat': 8, 'rhat': 16, 'pooled_input': 32}     # MILE_DIAG_*
 DIAG_S_MIN, DIAG_S_MAX, DIAG_POOL_MAX = 4, 4096, 16384
+DTAIL_BITS = {'ess_bulk': 1, 'ess_tail': 2, 'ess_mean': 4, 'rhat_folded': 8, 'plane_input': 16}   # MILE_DTAIL_*
 # layout of mile_function_diagnostics' summary (the FDIAG_* enum of csrc/mile_fdiag.h)
 FDIAG_SUMMARY = ('rhat_max', 'rhat_mean', 'rhat_column', 'rhat_gt_1_01', 'rhat_gt_1_05', 'rhat_gt_1_1', 'rhat_skipped',
                  'crhat_max', 'crhat_chain', 'crhat_column', 'crhat_skipped',
@@ -212,6 +213,13 @@ SIGNATURES = {
                                               C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     'mile_function_diagnostics_workspace': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    'mile_chain_diagnostics_tail': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                C.c_void_p]),
+    'mile_chain_diagnostics_tail_workspace': (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_uint32]),
+    'mile_multichain_ess': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_int64, C.c_void_p]),
+    'mile_multichain_ess_workspace': (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
     'mile_canonicalize_fcn': (C.c_int32, [C.POINTER(ModelSpecC), C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int64, C.c_void_p]),
     'mile_canonicalize_fcn_workspace': (C.c_int64, [C.POINTER(ModelSpecC), C.c_int64, C.c_uint32]),

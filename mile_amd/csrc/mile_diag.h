@@ -49,3 +49,5 @@ static inline size_t diag_chain_lds(int S) { return (size_t)((S * 4 + 15) / 16 *
 static inline size_t diag_pool_lds(int n) { return (size_t)diag_pow2(n) * 8; }
 
 hipError_t mile_launch_diag(const DiagParams &p, hipStream_t st);
+// k_diag_transpose alone: the chunk's [C][S][d] columns into p.raw (p.z with MILE_DIAG_POOLED_INPUT), for mile_dtail.h
+hipError_t mile_launch_diag_transpose(const DiagParams &p, hipStream_t st);

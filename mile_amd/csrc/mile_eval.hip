@@ -21,6 +21,7 @@
 #include "mile_crps.h"
 #include "mile_diag.h"
 #include "mile_fdiag.h"
+#include "mile_dtail.h"
 
 // D consecutive draws in passes of `chunk`, each pass at its draw offset of out [D][per sample]: every (draw, row) forward once
 static int forward_draws(mile_sampler *s, const float *theta, int64_t D, int64_t chunk, float *out, hipStream_t st) {
@@ -1006,6 +1007,128 @@ extern "C" int32_t mile_function_diagnostics(mile_sampler *s, const float *theta
     q.rhat = rhat; q.crhat = crhat; q.ess = ess; q.M = t.M; q.NQ = t.NQ; q.C = C; q.B = fdiag_sum_blocks(C, t.NQ);
     q.part = (FdiagPart *)(ws + t.part); q.summary = summary; q.chain_summary = chain_summary;
     HIP_TRY(mile_launch_fdiag_summary(q, st));
+  }
+  return MILE_OK;
+}
+
+// mile_chain_diagnostics_tail: every check before any launch; parameters in chunks that fit the workspace, each through
+// mile_dtail.h's launches and, for rhat_folded, mile_chain_diagnostics' own on the folded score plane ------------------------------
+static const char *diag_bad_splits(int32_t S, int32_t n_splits) {
+  if (n_splits < 1 || S % n_splits) return "n_splits must divide S";
+  return S / n_splits < 2 ? "fewer than 2 draws per split" : nullptr;
+}
+// workspace bytes of one parameter: the x plane (unless the input is one), z and zf, k_diag_chain's moments, the four ESS and
+// the sd, the two thresholds
+static int64_t dtail_param_bytes(int C, int S, uint32_t what) {
+  const int64_t cs = (int64_t)C * S * 4;
+  return ((what & MILE_DTAIL_PLANE_INPUT) ? 2 : 3) * cs + (int64_t)C * DIAG_NSTAT * 8 + DTAIL_NRES * 8 + 2 * 4;
+}
+static int64_t diag_ws_chunk(int64_t per) { return std::max<int64_t>(DIAG_TILE, DIAG_WS_TARGET / per / DIAG_TILE * DIAG_TILE); }
+// the parameters per chunk of a workspace of `bytes`: all of them, or a multiple of the transpose tile
+static int64_t diag_chunk_of(int64_t bytes, int64_t per, int64_t d) {
+  int64_t chunk = std::min<int64_t>(d, bytes / per);
+  if (chunk < d) chunk = chunk / DIAG_TILE * DIAG_TILE;
+  return std::min<int64_t>(chunk, 1 << 20);
+}
+
+extern "C" int64_t mile_chain_diagnostics_tail_workspace(int32_t C, int32_t S, int64_t d, uint32_t what) {
+  if (!diag_shape_ok(C, S, d)) return -1;
+  const int64_t per = dtail_param_bytes(C, S, what);
+  return per * std::min<int64_t>(d, diag_ws_chunk(per));
+}
+
+extern "C" int32_t mile_chain_diagnostics_tail(const float *samples, int32_t C, int32_t S, int64_t d, int32_t n_splits, uint32_t what,
+                                               float *ess_bulk, float *ess_tail, float *ess_mean, float *mcse_mean, float *rhat_folded,
+                                               float *quantiles, void *workspace, int64_t workspace_bytes, void *stream) {
+  const char *fn = "mile_chain_diagnostics_tail";
+  const uint32_t outs = MILE_DTAIL_ESS_BULK | MILE_DTAIL_ESS_TAIL | MILE_DTAIL_ESS_MEAN | MILE_DTAIL_RHAT_FOLDED;
+  const uint32_t sorted = MILE_DTAIL_ESS_BULK | MILE_DTAIL_ESS_TAIL | MILE_DTAIL_RHAT_FOLDED;
+  if (!samples) return bad(fn, "null samples");
+  if (!diag_shape_ok(C, S, d)) return bad(fn, "needs 1 <= C <= 65535, 4 <= S <= 4096, d >= 1");
+  if (const char *m = diag_bad_splits(S, n_splits)) return bad(fn, m);
+  if (!(what & outs) || (what & ~(outs | MILE_DTAIL_PLANE_INPUT))) return bad(fn, "bad `what`");
+  if (((what & MILE_DTAIL_ESS_BULK) && !ess_bulk) || ((what & MILE_DTAIL_ESS_TAIL) && !ess_tail) ||
+      ((what & MILE_DTAIL_ESS_MEAN) && (!ess_mean || !mcse_mean)) || ((what & MILE_DTAIL_RHAT_FOLDED) && !rhat_folded))
+    return bad(fn, "null pointer for an output asked for");
+  const bool sort = (what & sorted) || quantiles;
+  if (sort && (int64_t)C * S > DIAG_POOL_MAX)
+    return bad(fn, "unsupported: C * S > 16384 pooled draws (sort outside, pass the series to mile_multichain_ess)");
+  const int64_t per = dtail_param_bytes(C, S, what);
+  if (!workspace || workspace_bytes < per * std::min<int64_t>(d, DIAG_TILE)) return fail(MILE_ERR_STATE, std::string(fn) + ": workspace too small");
+  const bool plane_in = what & MILE_DTAIL_PLANE_INPUT;
+  const int64_t chunk = diag_chunk_of(workspace_bytes, per, d), cs = (int64_t)C * S;
+  hipStream_t st = (hipStream_t)stream;
+  DiagParams g{};                                   // the transpose, and R-hat of the folded scores
+  g.C = C; g.S = S; g.n_splits = n_splits; g.d = d; g.rhat = rhat_folded;
+  g.stat = (double *)workspace;                                       // [chunk][C][DIAG_NSTAT], [chunk][DTAIL_NRES], then the fp32 blocks
+  DtailParams t{};
+  t.C = C; t.S = S; t.n_splits = n_splits; t.d = d; t.quantiles = quantiles;
+  t.res = g.stat + chunk * C * DIAG_NSTAT;
+  t.z = (float *)(t.res + chunk * DTAIL_NRES);
+  t.zf = t.z + chunk * cs;
+  float *xplane = plane_in ? nullptr : t.zf + chunk * cs;
+  t.thr = t.zf + chunk * cs * (plane_in ? 1 : 2);
+  t.want_zf = (what & MILE_DTAIL_RHAT_FOLDED) != 0;
+  t.series = ((what & MILE_DTAIL_ESS_BULK) ? 1u : 0u) | ((what & MILE_DTAIL_ESS_TAIL) ? 6u : 0u) | ((what & MILE_DTAIL_ESS_MEAN) ? 8u : 0u);
+  if (what & MILE_DTAIL_ESS_BULK) t.ess_bulk = ess_bulk;
+  if (what & MILE_DTAIL_ESS_TAIL) t.ess_tail = ess_tail;
+  if (what & MILE_DTAIL_ESS_MEAN) { t.ess_mean = ess_mean; t.mcse_mean = mcse_mean; }
+  for (int64_t p0 = 0; p0 < d; p0 += chunk) {
+    const int P = (int)std::min<int64_t>(chunk, d - p0);
+    t.p0 = p0; t.P = P;
+    if (plane_in) {
+      t.x = samples + p0 * cs;
+    } else {
+      g.samples = samples; g.what = 0; g.raw = xplane; g.p0 = p0; g.P = P;
+      HIP_TRY(mile_launch_diag_transpose(g, st));
+      t.x = xplane;
+    }
+    if (sort) HIP_TRY(mile_launch_dtail_derive(t, st));
+    if (t.series) {
+      HIP_TRY(mile_launch_dtail_ess(t, st));
+      HIP_TRY(mile_launch_dtail_final(t, st));
+    }
+    if (what & MILE_DTAIL_RHAT_FOLDED) {
+      g.samples = nullptr; g.what = MILE_DIAG_RHAT | MILE_DIAG_POOLED_INPUT; g.raw = nullptr; g.z = t.zf; g.p0 = p0; g.P = P;
+      HIP_TRY(mile_launch_diag(g, st));
+    }
+  }
+  return MILE_OK;
+}
+
+extern "C" int64_t mile_multichain_ess_workspace(int32_t C, int32_t S, int64_t m, int32_t plane_input) {
+  if (!diag_shape_ok(C, S, m)) return -1;
+  if (plane_input) return 0;
+  const int64_t per = (int64_t)C * S * 4;
+  return per * std::min<int64_t>(m, diag_ws_chunk(per));
+}
+
+extern "C" int32_t mile_multichain_ess(const float *series, int32_t C, int32_t S, int64_t m, int32_t n_splits, int32_t plane_input,
+                                       float *ess, void *workspace, int64_t workspace_bytes, void *stream) {
+  const char *fn = "mile_multichain_ess";
+  if (!series || !ess) return bad(fn, "null series or ess");
+  if (!diag_shape_ok(C, S, m)) return bad(fn, "needs 1 <= C <= 65535, 4 <= S <= 4096, m >= 1");
+  if (const char *e = diag_bad_splits(S, n_splits)) return bad(fn, e);
+  const int64_t cs = (int64_t)C * S, per = cs * 4;
+  if (!plane_input && (!workspace || workspace_bytes < per * std::min<int64_t>(m, DIAG_TILE)))
+    return fail(MILE_ERR_STATE, std::string(fn) + ": workspace too small");
+  const int64_t chunk = plane_input ? std::min<int64_t>(m, 1 << 20) : diag_chunk_of(workspace_bytes, per, m);
+  hipStream_t st = (hipStream_t)stream;
+  DiagParams g{};
+  g.samples = series; g.C = C; g.S = S; g.n_splits = n_splits; g.d = m; g.raw = (float *)workspace;
+  DtailParams t{};
+  t.C = C; t.S = S; t.n_splits = n_splits; t.d = m; t.series = 8u; t.ess_plain = ess;
+  for (int64_t p0 = 0; p0 < m; p0 += chunk) {
+    const int P = (int)std::min<int64_t>(chunk, m - p0);
+    t.p0 = p0; t.P = P;
+    if (plane_input) {
+      t.x = series + p0 * cs;
+    } else {
+      g.p0 = p0; g.P = P;
+      HIP_TRY(mile_launch_diag_transpose(g, st));
+      t.x = g.raw;
+    }
+    HIP_TRY(mile_launch_dtail_ess(t, st));
   }
   return MILE_OK;
 }

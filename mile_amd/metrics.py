@@ -149,18 +149,29 @@ def within_chain_var(x: torch.Tensor) -> torch.Tensor:
 def rank_normalize_columns(x2: torch.Tensor) -> torch.Tensor:
     """x2 [n, m] -> float64 normal scores of every column ranked over its n entries, average rank for ties (what
     rank_normalize_array gives column by column), from ONE batched sort.  A column with a NaN is NaN throughout."""
-    n = x2.shape[0]
-    sv, order = torch.sort(x2.to(torch.float64), dim=0, stable=True)
-    pos = torch.arange(n, device=x2.device, dtype=torch.int64)[:, None].expand_as(order)
+    return _scores_of_sorted(*torch.sort(x2.to(torch.float64), dim=0, stable=True))
+
+
+def _scores_of_sorted(sv: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
+    """rank_normalize_columns' scores from the stable sort (values, indices) of the columns [n, m], in any float dtype."""
+    return _scores_of_sorted_rows(sv.t().contiguous(), order.t().contiguous()).t()
+
+
+def _scores_of_sorted_rows(sv: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
+    """The scores of m series laid out as rows [m, n], from their stable sort along dim 1.  The tie groups come from two scans
+    along the contiguous axis: a scan down the rows of [n, m] is an order of magnitude slower on the device (59 ms against the
+    sort's 4 ms at [128 000, 262]); the integers, and so the scores, are the same either way."""
+    n = sv.shape[1]
+    pos = torch.arange(n, device=sv.device, dtype=torch.int64)[None, :].expand_as(order)
     first = torch.ones_like(order, dtype=torch.bool)
-    first[1:] = sv[1:] != sv[:-1]
+    first[:, 1:] = sv[:, 1:] != sv[:, :-1]
     last = torch.ones_like(first)
-    last[:-1] = first[1:]
-    lo = torch.cummax(torch.where(first, pos, torch.zeros_like(pos)), dim=0).values
-    hi = torch.flip(torch.cummin(torch.flip(torch.where(last, pos, torch.full_like(pos, n)), [0]), dim=0).values, [0])
-    ranks = torch.empty_like(sv).scatter_(0, order, (lo + hi).to(torch.float64) * 0.5 + 1.0)
+    last[:, :-1] = first[:, 1:]
+    lo = torch.cummax(torch.where(first, pos, torch.zeros_like(pos)), dim=1).values
+    hi = torch.flip(torch.cummin(torch.flip(torch.where(last, pos, torch.full_like(pos, n)), [1]), dim=1).values, [1])
+    ranks = torch.empty_like(sv, dtype=torch.float64).scatter_(1, order, (lo + hi).to(torch.float64) * 0.5 + 1.0)
     z = torch.special.ndtri((ranks - 0.375) / (n + 0.25))
-    return torch.where(torch.isnan(sv[-1:]).expand_as(z), torch.full_like(z, float('nan')), z)
+    return torch.where(torch.isnan(sv[:, -1:]).expand_as(z), torch.full_like(z, float('nan')), z)
 
 
 def _pooled_scores(x: torch.Tensor) -> torch.Tensor:
@@ -277,6 +288,219 @@ def chain_diagnostics(samples: torch.Tensor, n_splits: int = 2) -> dict:
     LAST_DIAG_PATH = 'torch'
     return {'ess': torch.stack([ess1(z[c][None]) for c in range(C)]).reshape(C, *trail), 'crhat': crhat, 'rhat': rhat,
             'wcv': within_chain_var(x), 'bcv': between_chain_var(x)}
+
+
+# ---- tail diagnostics (Vehtari, Gelman, Simpson, Carpenter & Buerkner 2021): the pooled ESS of the bulk, the tails and the mean,
+# the MCSE of the mean and the folded split R-hat.  The definitions are stated once, in include/mile_hip.h
+# (mile_chain_diagnostics_tail); the library runs them on CUDA fp32 draws, the dense forms here are the CPU statement and, for
+# the series, the path past the library's pooled bound.
+
+LAST_DTAIL_PATH = None      # how the last tail_diagnostics call ran: 'torch', 'library' or 'library+torch_sort'
+TAIL_OUTPUTS = ('ess_bulk', 'ess_tail', 'ess_mean', 'mcse_mean', 'rhat_folded')
+
+
+def tail_quantile_indices(n: int) -> tuple:
+    """The integer positions in the n pooled sorted draws: (q_lo, q_hi, lower middle, upper middle)."""
+    return (n + 19) // 20 - 1, (19 * n + 19) // 20 - 1, (n - 1) // 2, n // 2
+
+
+def tail_series_plane(xp: torch.Tensor) -> dict:
+    """xp [m, n], every row the n pooled draws of one column -> the derived series as rows [m, n]: 'z', 'zf' (float64 pooled
+    normal scores of the draws and of the draws folded about the pooled median), 'i_lo', 'i_hi' (the 0 / 1 of x <= q_lo,
+    x <= q_hi, in xp's dtype), and 'quantiles' [3, m] (q_lo, q_hi, the median) in xp's dtype.  Order statistics, the median's
+    rounding and the fold are evaluated in xp's dtype, so fp32 draws give the library's fp32 series; a column with a NaN has NaN
+    quantiles and scores.  One stable sort of the draws serves the order statistics and the ranks, one more the folded ranks."""
+    n = xp.shape[1]
+    xs, order = torch.sort(xp, dim=1, stable=True)
+    lo, hi, a, b = tail_quantile_indices(n)
+    med = ((xs[:, a].to(torch.float64) + xs[:, b].to(torch.float64)) / 2).to(xp.dtype)
+    quant = torch.stack([xs[:, lo], xs[:, hi], med])
+    quant = torch.where(torch.isnan(xs[:, -1])[None].expand_as(quant), torch.full_like(quant, float('nan')), quant)
+    z = _scores_of_sorted_rows(xs, order)
+    del xs, order
+    f = (xp - quant[2][:, None]).abs()
+    zf = _scores_of_sorted_rows(*torch.sort(f, dim=1, stable=True))
+    return {'z': z, 'zf': zf, 'i_lo': (xp <= quant[0][:, None]).to(xp.dtype), 'i_hi': (xp <= quant[1][:, None]).to(xp.dtype),
+            'quantiles': quant}
+
+
+def tail_series_dense(x: torch.Tensor) -> dict:
+    """x [C, S, m] -> ``tail_series_plane`` of its columns, every series back in x's layout [C, S, m]."""
+    C, S, m = x.shape
+    ser = tail_series_plane(x.reshape(C * S, m).t().contiguous())
+    return {k: (v if k == 'quantiles' else v.t().reshape(C, S, m)) for k, v in ser.items()}
+
+
+def multichain_ess_dense(v: torch.Tensor, n_splits: int) -> torch.Tensor:
+    """v [C, S, m] -> ESS_mc [m]: mile_amd.diagnostics.effective_sample_size on the C * n_splits pieces, NaN where the weighted
+    variance is not a positive finite number (a series constant over all pooled draws, a non-finite draw)."""
+    import warnings
+    from mile_amd.diagnostics import effective_sample_size as ess_mc
+    C, S, m = v.shape
+    pieces = v.reshape(C * n_splits, S // n_splits, m)
+    ess = ess_mc(pieces)
+    pc = pieces.to(ess.dtype)
+    wv = pc.var(dim=1, unbiased=False).mean(dim=0)
+    if pc.shape[0] > 1:
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            wv = wv + pc.mean(dim=1).var(dim=0, unbiased=True)
+    return torch.where((wv > 0) & torch.isfinite(wv), ess, torch.full_like(ess, float('nan')))
+
+
+def _split_r_hat_of_scores(z: torch.Tensor, n_splits: int) -> torch.Tensor:
+    """gelman_split_r_hat's formula on scores z [C, S, m] that are ranked already."""
+    C, S, m = z.shape
+    n = S // n_splits
+    splits = z.reshape(C * n_splits, n, m)
+    wcv = within_chain_var(splits)
+    return torch.sqrt(((n - 1) / n * wcv + between_chain_var(splits)) / wcv)
+
+
+def tail_diagnostics_dense(x: torch.Tensor, n_splits: int) -> dict:
+    """x [C, S, m] -> the six outputs of ``tail_diagnostics`` in float64 (quantiles in x's dtype), all in torch."""
+    ser = tail_series_dense(x)
+    x64 = x.to(torch.float64)
+    out = {'ess_bulk': multichain_ess_dense(ser['z'], n_splits), 'ess_mean': multichain_ess_dense(x64, n_splits)}
+    lo, hi = multichain_ess_dense(ser['i_lo'].to(torch.float64), n_splits), multichain_ess_dense(ser['i_hi'].to(torch.float64), n_splits)
+    out['ess_tail'] = torch.where(torch.isnan(lo) | torch.isnan(hi), torch.full_like(lo, float('nan')), torch.minimum(lo, hi))
+    out['mcse_mean'] = x64.reshape(-1, x.shape[2]).std(dim=0, unbiased=True) / torch.sqrt(out['ess_mean'])
+    out['rhat_folded'] = _split_r_hat_of_scores(ser['zf'], n_splits)
+    out['quantiles'] = ser['quantiles']
+    return out
+
+
+def _tail_call(src: torch.Tensor, C: int, S: int, m: int, n_splits: int, what: int, **o):
+    """mile_chain_diagnostics_tail on contiguous CUDA fp32 ``src`` ([C, S, m], or [m, C, S] with the plane bit in ``what``) with a
+    workspace of the size it asks for; o: the output tensors, by name."""
+    import ctypes as Ct
+    from mile_amd import _lib
+    lib = _lib.load_library()
+    ptr = lambda t: Ct.c_void_p(t.data_ptr()) if t is not None else None
+    with torch.cuda.device(src.device):
+        ws = torch.empty(max(int(lib.mile_chain_diagnostics_tail_workspace(C, S, m, what)), 8), dtype=torch.uint8, device=src.device)
+        stream = Ct.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+        _lib.check(lib.mile_chain_diagnostics_tail(ptr(src), C, S, m, n_splits, what, ptr(o.get('ess_bulk')), ptr(o.get('ess_tail')),
+                                                   ptr(o.get('ess_mean')), ptr(o.get('mcse_mean')), ptr(o.get('rhat_folded')),
+                                                   ptr(o.get('quantiles')), ptr(ws), ws.numel(), stream), lib)
+
+
+def multichain_ess(series: torch.Tensor, n_splits: int = 2, plane: bool = False) -> torch.Tensor:
+    """ESS_mc of given series, no ranking: series [C, S, m] (or [m, C, S] with ``plane``) -> [m].  CUDA fp32 runs in the
+    library (mile_multichain_ess, at any C * S); anything else in ``multichain_ess_dense`` (float64)."""
+    import ctypes as Ct
+    from mile_amd import _lib
+    m, C, S = (series.shape if plane else (series.shape[2], *series.shape[:2]))
+    if not (series.is_cuda and series.dtype == torch.float32 and _lib.DIAG_S_MIN <= S <= _lib.DIAG_S_MAX):
+        return multichain_ess_dense(series.permute(1, 2, 0) if plane else series, n_splits)
+    lib = _lib.load_library()
+    src = series.contiguous()
+    ess = torch.empty(m, dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        ws = torch.empty(max(int(lib.mile_multichain_ess_workspace(C, S, m, int(plane))), 8), dtype=torch.uint8, device=src.device)
+        stream = Ct.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+        _lib.check(lib.mile_multichain_ess(Ct.c_void_p(src.data_ptr()), C, S, m, n_splits, int(plane), Ct.c_void_p(ess.data_ptr()),
+                                           Ct.c_void_p(ws.data_ptr()), ws.numel(), stream), lib)
+    return ess
+
+
+def _tail_torch_sort(src: torch.Tensor, C: int, S: int, m: int, n_splits: int, plane: bool) -> dict:
+    """The path past the library's pooled bound: per chunk of columns the series by torch sorts (``tail_series_dense`` on the
+    fp32 draws), their ESS from mile_multichain_ess, R-hat of the folded scores from mile_chain_diagnostics' kernels."""
+    from mile_amd._lib import DIAG_BITS as B
+    new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=src.device)
+    out = {k: new(m) for k in TAIL_OUTPUTS}
+    out['quantiles'] = new(3, m)
+    step = max(1, (1 << 28) // (C * S * 8))                         # columns per sort: the int64 indices stay under 256 MB
+    for k0 in range(0, m, step):
+        xp = (src[k0:k0 + step].reshape(-1, C * S) if plane else src[:, :, k0:k0 + step].reshape(C * S, -1).t()).contiguous()
+        k = xp.shape[0]
+        ser = tail_series_plane(xp)                                  # rows [k, C * S]: the library's plane layout
+        ess = multichain_ess(torch.cat([ser['z'].to(torch.float32), ser['i_lo'], ser['i_hi'], xp]).reshape(4 * k, C, S), n_splits,
+                             plane=True)
+        lo, hi = ess[k:2 * k], ess[2 * k:3 * k]
+        sl = slice(k0, k0 + k)
+        out['ess_bulk'][sl], out['ess_mean'][sl] = ess[:k], ess[3 * k:]
+        out['ess_tail'][sl] = torch.where(torch.isnan(lo) | torch.isnan(hi), torch.full_like(lo, float('nan')), torch.minimum(lo, hi))
+        sd = xp.to(torch.float64).std(dim=1, unbiased=True)
+        out['mcse_mean'][sl] = (sd / torch.sqrt(ess[3 * k:].to(torch.float64))).to(torch.float32)
+        r = new(k)
+        _diag_call(ser['zf'].to(torch.float32).t().reshape(C, S, k).contiguous(), n_splits, B['rhat'] | B['pooled_input'], rhat=r)
+        out['rhat_folded'][sl] = r
+        out['quantiles'][:, sl] = ser['quantiles']
+    return out
+
+
+def tail_diagnostics(samples: torch.Tensor, n_splits: int = 2, plane: bool = False, torch_sort: bool = False) -> dict:
+    """samples [C, S, ...] (with ``plane``: [m, C, S], the ``columns`` of ``function_diagnostics``) -> {'ess_bulk', 'ess_tail',
+    'ess_mean', 'mcse_mean', 'rhat_folded' [...], 'quantiles' [3, ...] (q_lo, q_hi, median)}: the pooled multi-chain ESS of the
+    rank-normalised draws, of the 5 % / 95 % tail indicators and of the draws, the Monte Carlo standard error of the mean, and the
+    split R-hat of the draws folded about their median (include/mile_hip.h states each).  CUDA fp32 draws run in the library
+    (mile_chain_diagnostics_tail; fp32 results), with torch sorts for the ranking past its pooled bound C * S > 16384 or when
+    ``torch_sort`` asks for that path; anything else in torch (float64 results) -- CPU tensors, other dtypes, and, with a
+    UserWarning, chains shorter than 4 or longer than 4096 draws."""
+    global LAST_DTAIL_PATH
+    import warnings
+    from mile_amd._lib import DIAG_POOL_MAX, DIAG_S_MAX, DIAG_S_MIN, DTAIL_BITS
+    if plane:
+        m, C, S = samples.shape
+        trail = (m,)
+    else:
+        C, S = samples.shape[:2]
+        trail = tuple(samples.shape[2:])
+    if S % n_splits:
+        raise ValueError('Number of samples must be divisible by n_splits')
+    if S // n_splits < 50:
+        warnings.warn(message='Number of samples should be at least 50x the number of splits', category=UserWarning)
+    in_range = DIAG_S_MIN <= S <= DIAG_S_MAX
+    on_device = samples.is_cuda and samples.dtype == torch.float32
+    if on_device and not in_range:
+        warnings.warn(f'tail_diagnostics: {S} draws per chain is outside the range of the HIP kernels '
+                      f'[{DIAG_S_MIN}, {DIAG_S_MAX}]; using the torch functions', category=UserWarning)
+    if on_device and in_range:
+        src = (samples if plane else samples.reshape(C, S, -1)).contiguous()
+        m = src.shape[0] if plane else src.shape[2]
+        if C * S <= DIAG_POOL_MAX and not torch_sort:
+            out = {k: torch.empty(m, dtype=torch.float32, device=src.device) for k in TAIL_OUTPUTS}
+            out['quantiles'] = torch.empty((3, m), dtype=torch.float32, device=src.device)
+            what = sum(DTAIL_BITS[k] for k in ('ess_bulk', 'ess_tail', 'ess_mean', 'rhat_folded')) | (DTAIL_BITS['plane_input'] if plane else 0)
+            _tail_call(src, C, S, m, n_splits, what, **out)
+            LAST_DTAIL_PATH = 'library'
+        else:
+            out = _tail_torch_sort(src, C, S, m, n_splits, plane)
+            LAST_DTAIL_PATH = 'library+torch_sort'
+    else:
+        x = (samples.permute(1, 2, 0) if plane else samples.reshape(C, S, -1)).contiguous()
+        if not x.dtype.is_floating_point:
+            x = x.to(torch.float64)
+        out = tail_diagnostics_dense(x, n_splits)
+        LAST_DTAIL_PATH = 'torch'
+    return {k: v.reshape(*((3,) if k == 'quantiles' else ()), *trail) for k, v in out.items()}
+
+
+def tail_diagnostics_summary(res: dict, n_draws: int, n_splits: int, rhat=None, prefix: str = 'dtail') -> dict:
+    """The ``<prefix>_*`` scalars of a ``tail_diagnostics`` result over all its columns (non-finite cells skipped): min and median
+    of ess_bulk and ess_tail, median and max of rhat_folded, the largest mcse_mean / sd (= 1 / sqrt(ess_mean)), the share
+    median(ess_bulk) / n_draws, and, with ``rhat`` (the rank R-hat of ``chain_diagnostics`` on the same columns),
+    ``rhat_rank_max``: the max over the columns of max(rhat, rhat_folded), the convergence figure of Vehtari et al."""
+    import numpy as np
+    a = {k: np.asarray(res[k].detach().cpu(), dtype=np.float64).reshape(-1) for k in TAIL_OUTPUTS}
+    nan = float('nan')
+
+    def stat(fn, v):
+        v = v[np.isfinite(v)]
+        return float(fn(v)) if v.size else nan
+    out = {f'{prefix}_n_splits': int(n_splits)}
+    for k in ('ess_bulk', 'ess_tail'):
+        out[f'{prefix}_{k}_min'], out[f'{prefix}_{k}_median'] = stat(np.min, a[k]), stat(np.median, a[k])
+    out[f'{prefix}_rhat_folded_median'], out[f'{prefix}_rhat_folded_max'] = stat(np.median, a['rhat_folded']), stat(np.max, a['rhat_folded'])
+    if rhat is not None:
+        r = np.asarray(rhat.detach().cpu() if hasattr(rhat, 'detach') else rhat, dtype=np.float64).reshape(-1)
+        out[f'{prefix}_rhat_rank_max'] = stat(np.max, np.fmax(r, a['rhat_folded']))
+    with np.errstate(all='ignore'):
+        out[f'{prefix}_mcse_mean_over_sd_max'] = stat(np.max, 1.0 / np.sqrt(a['ess_mean']))
+    out[f'{prefix}_ess_bulk_share'] = out[f'{prefix}_ess_bulk_median'] / float(n_draws)
+    return out
 
 
 # ---- canonical hidden-unit ordering of FCN draws: one representative of every draw's orbit under the permutations (and, for
