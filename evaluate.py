@@ -3,7 +3,7 @@
 mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
 src/inference/metrics.py:247-312):
 
-    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--function-diagnostics [N_SPLITS]] [--canonical-diagnostics [N_SPLITS]] [--tail-diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo] [--stacking]
+    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--function-diagnostics [N_SPLITS]] [--canonical-diagnostics [N_SPLITS]] [--aligned-diagnostics [N_SPLITS]] [--tail-diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo] [--stacking]
 
 Reloads config.yaml and the samples/<chain>/sample_<n>.npz files, rebuilds the data split with the same
 seed, evaluates all C x S samples on the split in one device pass and writes metrics.json next to them.
@@ -167,6 +167,43 @@ def canonical_diagnostic_metrics(samples, spec, n_splits, key, sign, device, tai
     from mile_amd import metrics as M
     canon = M.canonicalize(spec, torch.from_numpy(ok).to(device), key, sign, return_perm=True)[0]
     return out, arr, tail_keys('cdiag_tail', M.tail_diagnostics(canon, tail_splits), ok.shape[0] * ok.shape[1], tail_splits, res['rhat'])
+
+
+def aligned_refusal(model, activation, sign):
+    """Why --aligned-diagnostics cannot run on an experiment of ``model`` with ``activation``, or None."""
+    if model != 'FCN':
+        return (f'--aligned-diagnostics: the alignment of hidden units to a reference draw is defined for FCN experiments only; '
+                f'this one is {model} (--function-diagnostics compares chains of any model)')
+    if sign and activation != 'tanh':
+        return (f'--align-sign: flipping matched hidden units needs an odd activation (tanh); this net uses {activation}, whose '
+                f'units have no sign symmetry to remove')
+    return None
+
+
+def aligned_diagnostic_metrics(samples, spec, n_splits, reference, rounds, sign, device, tail_splits=None):
+    """--aligned-diagnostics: the statistics of --diagnostics on the finite chains with every draw's hidden units matched to those
+    of one reference draw by assignment (mile_amd.metrics.aligned_diagnostics: mile_align_fcn, then mile_chain_diagnostics, on the
+    device), how often each chain's matching of a layer changes from one draw to the next, and the matched similarity per layer.
+    samples [C, S, d] (host); reference 'first' or a row of d floats.  Returns the adiag_* keys of metrics.json and the arrays of
+    aligned_diagnostics.npz."""
+    from mile_amd import metrics as M
+    fin = np.isfinite(samples).all(axis=(1, 2))
+    ok = np.ascontiguousarray(samples[fin])
+    if ok.shape[0] == 0:
+        raise SystemExit('--aligned-diagnostics: no chain with finite samples')
+    ref = reference if isinstance(reference, str) else torch.from_numpy(np.ascontiguousarray(reference, dtype=np.float32)).to(device)
+    res = M.aligned_diagnostics(spec, torch.from_numpy(ok).to(device), n_splits, reference=ref, rounds=rounds, sign=sign)
+    aligned, dropped = res.pop('theta'), res.pop('dropped')
+    arr = {k: v.detach().cpu().numpy() for k, v in res.items()}
+    out = diagnostic_keys('adiag', arr, spec, n_splits)
+    out['adiag_reference'] = reference if isinstance(reference, str) else 'file'
+    out['adiag_rounds'], out['adiag_sign'], out['adiag_dropped'] = int(rounds), bool(sign), int(dropped)
+    for l in range(arr['switches'].shape[1]):
+        out[f'adiag_switch_rate_layer{l}'] = float(np.mean(arr['switches'][:, l] / max(ok.shape[1] - 1, 1)))
+        out[f'adiag_score_mean_layer{l}'] = float(arr['score_mean'][l])
+    if tail_splits is None:
+        return out, arr
+    return out, arr, tail_keys('adiag_tail', M.tail_diagnostics(aligned, tail_splits), ok.shape[0] * ok.shape[1], tail_splits, res['rhat'])
 
 
 def function_diagnostic_metrics(eng, samples, x, y, task, n_splits, tail_splits=None):
@@ -427,6 +464,27 @@ def build_parser():
     ap.add_argument('--canonical-sign', action='store_true',
                     help='--canonical-diagnostics on a tanh net: flip every hidden unit whose bias is negative first (the sign '
                          'symmetry of an odd activation)')
+    ap.add_argument('--aligned-diagnostics', type=int, nargs='?', const=2, default=None, metavar='N_SPLITS',
+                    help='FCN experiments: the statistics of --diagnostics on the draws of the finite chains ALIGNED to one reference '
+                         'draw (mile_align_fcn, then mile_chain_diagnostics, on the device): per hidden layer, in a forward sweep, the '
+                         'units of every draw are matched to the reference\'s by a linear assignment problem on the similarity of their '
+                         'bias and incoming weights (the last hidden layer also of its outgoing weights), so that a parameter is the same '
+                         'unit in every draw and chain -- an alignment to a mode, where --canonical-diagnostics gives order statistics.  '
+                         'adiag_* keys in metrics.json mirror the diag_* keys, plus adiag_reference, adiag_rounds, adiag_sign, '
+                         'adiag_dropped (draws with a non-finite similarity, copied unchanged), adiag_switch_rate_layer<l> (the share of '
+                         'draws whose matching of hidden layer l differs from the draw before; 0 where each chain stays in one copy of '
+                         'the mode) and adiag_score_mean_layer<l>; wcv, bcv, rhat, ess, crhat, switches (per chain and layer), scores, '
+                         'score_mean and reference in aligned_diagnostics.npz; with --tail-diagnostics also adiag_tail_*.  Hidden widths '
+                         'above 128 run in scipy on the host.  No ReLU rescaling, no sigmoid reflection')
+    ap.add_argument('--align-reference', default='first', metavar='first|PATH.npy',
+                    help='--aligned-diagnostics aligns to the first draw of the first finite chain (default) or to the row of d floats '
+                         'in PATH.npy')
+    ap.add_argument('--align-rounds', type=int, default=2, metavar='R',
+                    help='--aligned-diagnostics: rounds of alignment (default 2); from the second on the reference is the mean of the '
+                         'draws as the round before aligned them')
+    ap.add_argument('--align-sign', action='store_true',
+                    help='--aligned-diagnostics on a tanh net: also flip a matched unit whose similarity to its reference unit is '
+                         'negative (the sign symmetry of an odd activation)')
     ap.add_argument('--moments', action='store_true',
                     help='posterior-predictive moments of all draws on the split, reduced on the device (mile_predict_moments): '
                          'moments_* keys in metrics.json and the per-row arrays in moments.npz (regression: mean, epistemic_var, '
@@ -512,8 +570,20 @@ def main():
     why = canonical_refusal(cfg.model.model, getattr(cfg.model, 'activation', None), args.canonical_sign)
     if args.canonical_diagnostics is not None and why:
         raise SystemExit(why)
+    why = aligned_refusal(cfg.model.model, getattr(cfg.model, 'activation', None), args.align_sign)
+    if args.aligned_diagnostics is not None and why:
+        raise SystemExit(why)
+    if args.aligned_diagnostics is not None and args.align_rounds < 1:
+        raise SystemExit('--align-rounds: at least 1')
+    align_reference = args.align_reference
+    if args.aligned_diagnostics is not None and align_reference != 'first':
+        if not Path(align_reference).is_file():
+            raise SystemExit(f'--align-reference: {align_reference} is neither "first" nor a .npy file')
+        align_reference = np.load(align_reference).reshape(-1)
     tr.build_model(cfg)
     spec = tr.prob_model.spec
+    if args.aligned_diagnostics is not None and not isinstance(align_reference, str) and align_reference.shape[0] != spec.n_params:
+        raise SystemExit(f'--align-reference: the file holds {align_reference.shape[0]} floats, the net has {spec.n_params} parameters')
     samples = load_samples_from_dir(exp / cfg.training.sampler._dir_name, spec)       # [C, S, d]
     if args.crps and crps_refusal(cfg.data.task, samples.shape[0]):
         raise SystemExit(crps_refusal(cfg.data.task, samples.shape[0]))
@@ -622,6 +692,14 @@ def main():
                                                            args.canonical_sign, args.device, args.tail_diagnostics)
         out.update(keys)
         np.savez(exp / 'canonical_diagnostics.npz', **arrays)
+        for tk, ta in tail:
+            out.update(tk)
+            tail_arrays.update(ta)
+    if args.aligned_diagnostics is not None:
+        keys, arrays, *tail = aligned_diagnostic_metrics(samples, spec, args.aligned_diagnostics, align_reference, args.align_rounds,
+                                                         args.align_sign, args.device, args.tail_diagnostics)
+        out.update(keys)
+        np.savez(exp / 'aligned_diagnostics.npz', **arrays)
         for tk, ta in tail:
             out.update(tk)
             tail_arrays.update(ta)

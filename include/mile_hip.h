@@ -726,7 +726,7 @@ int64_t mile_chain_diagnostics_workspace(int32_t C, int32_t S, int64_t d, uint32
  *         other), and a draw gives the same bits whatever M is.  With n_layers == 1, H = 0 and out is a copy.
  *   perm [M][H] int32 (device, or null): perm[m][o_l + j'] = p_l[j'].  sign [M][H] int8 (or null): s_l[p_l[j']].
  * Out of scope: the positive rescaling symmetry of ReLU, sigmoid's reflection (it needs a bias correction downstream),
- * alignment to a reference draw by assignment, and every model other than the FCN.
+ * alignment to a reference draw by assignment (mile_align_fcn below), and every model other than the FCN.
  * MILE_ERR_INVALID, with nothing launched and no device touched: a null spec, theta or out; M < 1 (or > 2^31 - 1); a model
  * other than MILE_MODEL_FCN, use_bias != 1, or a spec mile_create would refuse; unknown bits in `how`; MILE_CANON_SIGN with an
  * activation other than tanh; a hidden width above MILE_CANON_WIDTH_MAX; out overlapping theta.  MILE_ERR_STATE: a workspace
@@ -739,6 +739,57 @@ int32_t mile_canonicalize_fcn(const mile_model_spec *spec, const float *theta, i
                               void *workspace, int64_t workspace_bytes, void *stream);
 int64_t mile_canonicalize_fcn_workspace(const mile_model_spec *spec, int64_t M, uint32_t how);
 int64_t mile_canonical_hidden(const mile_model_spec *spec);
+
+/* `how` of mile_align_fcn: 0, or the sign fix. */
+#define MILE_ALIGN_SIGN      1u
+#define MILE_ALIGN_WIDTH_MAX 128
+
+/* Alignment of FCN draws to a reference draw by hidden-unit assignment (re-basin): every draw's hidden units are matched to
+ * those of ONE reference row by a linear assignment problem per hidden layer, so that "parameter j" is the same unit in every
+ * draw and chain -- an alignment to a mode, where mile_canonicalize_fcn's ordering by a key gives order statistics whose labels
+ * switch wherever two keys cross.  Needs no mile_sampler; launches on the current device.
+ * theta [M][d] fp32 (device) draws and reference [d] fp32 (device) one row, both of the MILE_MODEL_FCN `spec` in the library's
+ * full layout (mile_param_offsets: "layer10" before "layer2").  Hidden layers l = 0 .. n_hidden - 1 (n_hidden = n_layers - 1),
+ * widths W_l, the H axis and its spans [o_l, o_l + W_l) as for mile_canonicalize_fcn.  Inputs and outputs never move.  The
+ * layers are solved in ascending order (a forward sweep); fin is the fan-in of layer l.
+ *   features    reference unit i: (bias^r_l[i], kernel^r_l[0][i], .., kernel^r_l[fin-1][i]).  Draw unit j: (bias_l[j],
+ *               s_{l-1}[t] * kernel_l[p_{l-1}[t]][j] for t = 0 .. fin-1) -- the rows already in the previous layer's aligned
+ *               order and sign (the identity for l = 0).  For the LAST hidden layer both vectors also carry the unit's outgoing
+ *               row kernel_{l+1}[unit][0 .. O-1] (the outputs are never permuted).
+ *   similarity  S[i][j]: the dot product of the two vectors in fp64, starting from the bias product, the terms added one after
+ *               another in the order above.  Products of fp32 values are exact in fp64, so fused and unfused multiply-adds
+ *               round alike: S is reproducible bit for bit.
+ *   gain        G = S; with MILE_ALIGN_SIGN (MILE_ACT_TANH only) G = |S|.
+ *   assignment  the permutation p_l (reference position i <- draw unit p_l[i]) that maximises sum_i G[i][p_l[i]], found on the
+ *               cost c = -G by the shortest-augmenting-path Hungarian method with potentials u (rows), v (columns) in fp64, in
+ *               this operation order: rows are inserted in ascending i; inside an augmentation from the row i0 of the column
+ *               reached last, cur = (c[i0][j] - u[i0]) - v[j] for every unused column j, minv[j] and way[j] are updated on
+ *               cur < minv[j]; the next column is the unused one with the smallest minv, the lowest index among equals, delta
+ *               its minv; then u[p[j]] += delta and v[j] -= delta on the used columns (the row being inserted counts as used),
+ *               minv[j] -= delta on the others; the augmentation ends at a column without a row and the path is flipped.
+ *               Only additions, subtractions and comparisons: the result is the same permutation on every machine.
+ *   sign        with MILE_ALIGN_SIGN s_l[i] = -1 iff S[i][p_l[i]] < 0 (zero and NaN are not flipped), else s_l = +1.
+ *   score [M][n_hidden] fp64 (device, or null): score[m][l] = sum_i G[i][p_l[i]], added in ascending i from 0.
+ *   non-finite  a draw for which any entry of any layer's S is not finite is copied unchanged: perm the identity, sign +1,
+ *               its scores NaN, dropped[m] = 1 (dropped [M] int32, device, or null; 0 for every other draw).  The solver never
+ *               sees a NaN.  A non-finite reference drops every draw.
+ *   out [M][d] (device, required, overlapping neither theta nor reference): exactly mile_canonicalize_fcn's formula with these
+ *               p_l and s_l (s_l[i] the sign of position i): bias_l'[i] = s_l[i] * bias_l[p_l[i]], kernel_l'[t][i] =
+ *               s_{l-1}[t] * s_l[i] * kernel_l[p_{l-1}[t]][p_l[i]].  Every output float is an input float moved, possibly
+ *               negated.  A draw is handled on its own and gives the same bits whatever M is.  With n_layers == 1 out is a copy.
+ *   perm [M][H] int32 (or null): perm[m][o_l + i] = p_l[i].  sign [M][H] int8 (or null): s_l[i].
+ * Out of scope: refinement of inner layers with their outgoing weights, activation matching, ReLU rescaling, sigmoid's
+ * reflection, hidden widths above MILE_ALIGN_WIDTH_MAX, every model other than the FCN.
+ * MILE_ERR_INVALID, with nothing launched and no device touched: a null spec, theta, reference or out; M < 1 (or > 2^31 - 1);
+ * a model other than MILE_MODEL_FCN, use_bias != 1, or a spec mile_create would refuse; unknown bits in `how`; MILE_ALIGN_SIGN
+ * with an activation other than tanh; a hidden width above MILE_ALIGN_WIDTH_MAX; out overlapping theta or reference.
+ * MILE_ERR_STATE: a workspace below mile_align_fcn_workspace's figure, 4 * M * H bytes (the rank words that drive the move);
+ * -1 for a bad shape.  Every refusal leaves its message in mile_last_error.
+ * (Added under ABI 10: two new symbols, no struct or existing entry changed.) */
+int32_t mile_align_fcn(const mile_model_spec *spec, const float *theta, int64_t M, const float *reference, uint32_t how,
+                       float *out, int32_t *perm, int8_t *sign, double *score, int32_t *dropped,
+                       void *workspace, int64_t workspace_bytes, void *stream);
+int64_t mile_align_fcn_workspace(const mile_model_spec *spec, int64_t M, uint32_t how);
 
 /* Function-space chain diagnostics: the statistics of mile_chain_diagnostics of what the draws PREDICT, streamed -- the
  * [C][S][N][O] outputs are never held.  Hidden-unit permutations and other symmetries of the parameters leave these series

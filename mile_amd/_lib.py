@@ -26,6 +26,8 @@ FDIAG_SUMMARY = ('rhat_max', 'rhat_mean', 'rhat_column', 'rhat_gt_1_01', 'rhat_g
 FDIAG_O_MAX = 64
 CANON_BITS = {'bias': 0, 'norm': 1, 'sign': 2}                                                # MILE_CANON_*
 CANON_WIDTH_MAX = 1024
+ALIGN_SIGN = 1                                                                                # MILE_ALIGN_SIGN
+ALIGN_WIDTH_MAX = 128
 MODEL_IDS = {'fcn': 0, 'lenet': 1, 'lenetti': 2, 'attn': 3, 'attn_pretrained': 4, 'attn_wide': 5}
 
 
@@ -224,6 +226,9 @@ SIGNATURES = {
                                           C.c_void_p, C.c_int64, C.c_void_p]),
     'mile_canonicalize_fcn_workspace': (C.c_int64, [C.POINTER(ModelSpecC), C.c_int64, C.c_uint32]),
     'mile_canonical_hidden': (C.c_int64, [C.POINTER(ModelSpecC)]),
+    'mile_align_fcn': (C.c_int32, [C.POINTER(ModelSpecC), C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'mile_align_fcn_workspace': (C.c_int64, [C.POINTER(ModelSpecC), C.c_int64, C.c_uint32]),
     'mile_debug_noise': (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
                                      C.c_void_p, C.c_void_p]),
     'mile_debug_prefill_count': (C.c_int64, [C.c_void_p]),

@@ -73,3 +73,9 @@ static inline bool canon_fits(const CanonPlan &pl) { return canon_draw_lds(pl) <
 static inline size_t canon_rank_lds(const CanonPlan &pl) { return (size_t)pl.H * 8; }
 
 hipError_t mile_launch_canon(const CanonParams &p, hipStream_t st);
+
+// For other makers of rank words (mile_align.hip): the shape check and the layout of the plan, each returning why not or null,
+// and the write phase alone -- k_canon_rows from p.theta and p.ranks [M][H] to p.out (p.how, p.perm and p.sign are not read).
+const char *mile_canon_shape(const mile_model_spec *spec);
+const char *mile_canon_layout(const mile_model_spec *spec, CanonPlan &pl);
+hipError_t mile_launch_canon_rows(const CanonParams &p, hipStream_t st);

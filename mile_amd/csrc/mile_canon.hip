@@ -190,14 +190,19 @@ hipError_t mile_launch_canon(const CanonParams &p, hipStream_t st) {
   const hipError_t e = mile_set_max_lds<k_canon_rank>(CANON_LDS_MAX);
   if (e != hipSuccess) return e;
   k_canon_rank<<<M, CANON_NT, canon_rank_lds(p.pl), st>>>(p);
+  return mile_launch_canon_rows(p, st);
+}
+
+// The write phase alone: out from theta and the rank words p.ranks [M][H], whoever made them (p.how, p.perm, p.sign are not read).
+hipError_t mile_launch_canon_rows(const CanonParams &p, hipStream_t st) {
   const int tiles = (p.pl.max_rows + CANON_TILE_ROWS - 1) / CANON_TILE_ROWS;
-  k_canon_rows<<<dim3(M, (unsigned)std::min(tiles, 65535), (unsigned)p.pl.n_layers), CANON_NT, 0, st>>>(p);
+  k_canon_rows<<<dim3((unsigned)p.M, (unsigned)std::min(tiles, 65535), (unsigned)p.pl.n_layers), CANON_NT, 0, st>>>(p);
   return hipGetLastError();
 }
 
 // ---- the entry points: every check before any launch, none of them touches a device ------------------------------------------------
-// The plan of `spec` under `how`, or why there is none.
-static const char *canon_plan(const mile_model_spec *spec, uint32_t how, CanonPlan &pl) {
+// The shape of `spec` as an FCN whose hidden units can be moved, or why it is none.
+const char *mile_canon_shape(const mile_model_spec *spec) {
   if (!spec) return "null spec";
   if (spec->model != MILE_MODEL_FCN) return "only MILE_MODEL_FCN has a canonical form here";
   if (spec->use_bias != 1) return "use_bias must be 1";
@@ -205,10 +210,21 @@ static const char *canon_plan(const mile_model_spec *spec, uint32_t how, CanonPl
   if (spec->in_features < 1) return "in_features must be >= 1";
   for (int l = 0; l < spec->n_layers; ++l)
     if (spec->widths[l] < 1) return "layer width must be >= 1";
+  return nullptr;
+}
+
+// The plan of `spec` under `how`, or why there is none.
+static const char *canon_plan(const mile_model_spec *spec, uint32_t how, CanonPlan &pl) {
+  if (const char *m = mile_canon_shape(spec)) return m;
   if (how & ~(MILE_CANON_KEY_NORM | MILE_CANON_SIGN)) return "unknown bits in `how`";
   if ((how & MILE_CANON_SIGN) && spec->activation != MILE_ACT_TANH) return "MILE_CANON_SIGN needs an odd activation: tanh only";
   for (int l = 0; l + 1 < spec->n_layers; ++l)
     if (spec->widths[l] > MILE_CANON_WIDTH_MAX) return "unsupported: a hidden width above MILE_CANON_WIDTH_MAX (1024)";
+  return mile_canon_layout(spec, pl);
+}
+
+// The layout of a spec that passed mile_canon_shape: offsets, fans and the hidden spans of the H axis.
+const char *mile_canon_layout(const mile_model_spec *spec, CanonPlan &pl) {
   pl = CanonPlan{};
   const long long d = fcn_param_layout(spec, FcnOffsets{pl.b_off, pl.w_off});
   if (d > 0x7fffffffLL) return "parameter count exceeds int32";

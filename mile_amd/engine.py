@@ -1071,6 +1071,17 @@ class Engine:
         from mile_amd.metrics import canonicalize
         return canonicalize(self.spec, torch.as_tensor(theta).to(self.device, torch.float32), key, sign, return_perm)
 
+    def align(self, theta, reference, sign: bool = False, return_index: bool = False, return_score: bool = False):
+        """theta [C, S, d] or [M, d], reference [d] -> every draw with its hidden units matched to the reference's by assignment
+        on this engine's device (one round of mile_amd.metrics.align with the engine's spec: mile_align_fcn).  With
+        ``return_index`` also ``perm`` and ``sign`` [..., H], with ``return_score`` also ``score`` [..., n_hidden] fp64 and
+        ``dropped`` [...] int32, in this order after the aligned draws."""
+        from mile_amd.metrics import align
+        res = align(self.spec, torch.as_tensor(theta).to(self.device, torch.float32),
+                    torch.as_tensor(reference).to(self.device, torch.float32), 1, sign)
+        out = (res['theta'],) + ((res['perm'], res['sign']) if return_index else ()) + ((res['score'], res['dropped']) if return_score else ())
+        return out[0] if len(out) == 1 else out
+
     @property
     def supports_device_tuner(self) -> bool:
         return self.dim >= 4

@@ -654,6 +654,193 @@ def canonical_diagnostics(spec, samples: torch.Tensor, n_splits: int = 2, key: s
     return res
 
 
+# ---- alignment to a reference draw by hidden-unit assignment: the other half of the above.  Every draw's hidden units are
+# matched to those of ONE reference row by a linear assignment problem per layer, so that "parameter j" is the same unit in
+# every draw and chain.  The rule is stated once, in include/mile_hip.h (mile_align_fcn); the library runs it on device tensors
+# (hidden widths up to 128), the dense form here is the yardstick and the path for everything else.
+
+LAST_ALIGN_PATH = None      # how the last align call ran: 'library' or 'scipy'
+
+
+def _align_check(spec, sign: bool):
+    if not isinstance(spec, ModelSpec):
+        raise ValueError(f'alignment to a reference draw is defined for the FCN only, not for {type(spec).__name__}')
+    if not spec.use_bias:
+        raise ValueError('alignment to a reference draw needs use_bias=True')
+    if sign and spec.activation != 'tanh':
+        raise ValueError(f'sign fixing needs an odd activation: tanh only, not {spec.activation}')
+
+
+def align_dense(spec, theta: torch.Tensor, reference: torch.Tensor, sign: bool = False):
+    """The rule of mile_align_fcn with torch and scipy, on whatever device ``theta`` [M, d] is on: per hidden layer the
+    similarities of all draws as one fp64 matrix product, then ``scipy.optimize.linear_sum_assignment`` per draw on the host, then
+    ``take_along_dim`` of the bias, the columns and the next layer's rows.  Returns ``out`` [M, d] (theta's dtype), ``perm``
+    [M, H] int32, ``sign`` [M, H] int8, ``score`` [M, n_hidden] fp64, ``dropped`` [M] int32.
+
+    The matrix product adds the terms of a similarity in its own order and scipy breaks ties between equally good assignments in
+    its own way, so this form need not give the library's permutation where two assignments tie (or nearly tie); each layer's
+    objective is the same maximum."""
+    import numpy as np
+    from scipy.optimize import linear_sum_assignment
+    _align_check(spec, sign)
+    M, dev = theta.shape[0], theta.device
+    ref = torch.as_tensor(reference).to(dev).reshape(-1)
+    if ref.shape[0] != spec.n_params:
+        raise ValueError(f'reference must hold {spec.n_params} floats, got {tuple(ref.shape)}')
+    leaves = {n.split('.', 1)[1]: (o, sh) for n, o, sh in spec.leaves()}
+    nl = len(spec.hidden_structure)
+    nh = nl - 1
+
+    def layer(li):
+        (ob, (fout,)), (ok, (fin, _)) = leaves[f'layer{li}.bias'], leaves[f'layer{li}.kernel']
+        return ob, ok, fin, fout
+
+    t64, r64 = theta.double(), ref.double()
+    ok_rows = torch.ones(M, dtype=torch.bool, device=dev)
+    perms, signs, scores = [], [], []
+    for li in range(nh):
+        ob, ok, fin, W = layer(li)
+        Kd = t64[:, ok:ok + fin * W].reshape(M, fin, W)
+        if li > 0:
+            Kd = torch.take_along_dim(Kd, perms[-1][:, :, None], dim=1) * signs[-1][:, :, None]
+        Fr = torch.cat([r64[ob:ob + W][None], r64[ok:ok + fin * W].reshape(fin, W)], dim=0)                # [1 + fin, W]
+        Fd = torch.cat([t64[:, None, ob:ob + W], Kd], dim=1)                                              # [M, 1 + fin, W]
+        if li == nh - 1:
+            _, ok2, fin2, O = layer(li + 1)
+            Fr = torch.cat([Fr, r64[ok2:ok2 + fin2 * O].reshape(fin2, O).T], dim=0)
+            Fd = torch.cat([Fd, t64[:, ok2:ok2 + fin2 * O].reshape(M, fin2, O).transpose(1, 2)], dim=1)
+        p = torch.arange(W, device=dev).repeat(M, 1)
+        hit = torch.empty((M, W), dtype=torch.float64, device=dev)
+        step = max(1, (1 << 27) // (W * W))                                                                # 1 GiB of fp64 at a time
+        for m0 in range(0, M, step):
+            S = torch.matmul(Fr.T[None], Fd[m0:m0 + step])                                                 # [m, W, W]
+            fin_rows = torch.isfinite(S).all(dim=2).all(dim=1)
+            ok_rows[m0:m0 + step] &= fin_rows
+            G = (S.abs() if sign else S).cpu().numpy()
+            alive = ok_rows[m0:m0 + step].cpu().numpy()
+            pc = np.tile(np.arange(W), (G.shape[0], 1))
+            for m in range(G.shape[0]):
+                if alive[m]:
+                    pc[m] = linear_sum_assignment(G[m], maximize=True)[1]
+            p[m0:m0 + step] = torch.from_numpy(pc).to(dev)
+            hit[m0:m0 + step] = torch.take_along_dim(S, p[m0:m0 + step, :, None], dim=2)[:, :, 0]
+        s = torch.where(hit < 0, -torch.ones_like(hit), torch.ones_like(hit)) if sign else torch.ones_like(hit)
+        perms.append(p), signs.append(s), scores.append((hit.abs() if sign else hit).sum(dim=1))
+    out = torch.empty_like(theta)
+    for li in range(nl):
+        ob, ok, fin, fout = layer(li)
+        B = theta[:, ob:ob + fout]
+        K = theta[:, ok:ok + fin * fout].reshape(M, fin, fout)
+        if li < nh:
+            sg = signs[li].to(theta.dtype)
+            B = torch.take_along_dim(B, perms[li], dim=1) * sg
+            K = torch.take_along_dim(K, perms[li][:, None, :], dim=2) * sg[:, None, :]
+        if li > 0:
+            K = torch.take_along_dim(K, perms[li - 1][:, :, None], dim=1) * signs[li - 1].to(theta.dtype)[:, :, None]
+        out[:, ob:ob + fout] = B
+        out[:, ok:ok + fin * fout] = K.reshape(M, fin * fout)
+    cat = lambda ts, dt: (torch.cat(ts, dim=1) if ts else torch.empty((M, 0), device=dev)).to(dt)
+    perm, sgn = cat(perms, torch.int32), cat(signs, torch.int8)
+    score = torch.stack(scores, dim=1) if scores else torch.empty((M, 0), dtype=torch.float64, device=dev)
+    # a draw with a non-finite similarity in any layer is copied: identity, +1, NaN scores
+    bad = ~ok_rows
+    if bool(bad.any()):
+        ident = torch.cat([torch.arange(w, device=dev) for w in spec.hidden_structure[:-1]]).to(torch.int32)
+        out[bad], perm[bad], sgn[bad], score[bad] = theta[bad], ident, 1, float('nan')
+    return out, perm, sgn, score, bad.to(torch.int32)
+
+
+def _library_align(spec, theta: torch.Tensor, reference: torch.Tensor, sign: bool, want_index: bool = True, want_score: bool = True):
+    """theta [M, d], reference [d] contiguous CUDA fp32 -> (out, perm, sign, score, dropped) from mile_align_fcn (perm and sign,
+    and score, None unless wanted)."""
+    import ctypes as Ct
+    from mile_amd import _lib
+    lib = _lib.load_library()
+    cs = _lib.fcn_spec_c(spec)
+    M, H, nh = theta.shape[0], canonical_hidden(spec), len(spec.hidden_structure) - 1
+    how = _lib.ALIGN_SIGN if sign else 0
+    ptr = lambda t: Ct.c_void_p(t.data_ptr()) if t is not None else None
+    with torch.cuda.device(theta.device):
+        out = torch.empty((M, theta.shape[1]), dtype=torch.float32, device=theta.device)
+        perm = torch.empty((M, H), dtype=torch.int32, device=theta.device) if want_index else None
+        sgn = torch.empty((M, H), dtype=torch.int8, device=theta.device) if want_index else None
+        score = torch.empty((M, nh), dtype=torch.float64, device=theta.device) if want_score else None
+        dropped = torch.empty(M, dtype=torch.int32, device=theta.device)
+        nws = int(lib.mile_align_fcn_workspace(Ct.byref(cs), M, how))
+        if nws < 0:
+            _lib.check(-1, lib)
+        ws = torch.empty(nws, dtype=torch.uint8, device=theta.device) if nws else None
+        stream = Ct.c_void_p(torch.cuda.current_stream(theta.device).cuda_stream)
+        _lib.check(lib.mile_align_fcn(Ct.byref(cs), ptr(theta), M, ptr(reference), how, ptr(out), ptr(perm), ptr(sgn), ptr(score),
+                                      ptr(dropped), ptr(ws), nws, stream), lib)
+    return out, perm, sgn, score, dropped
+
+
+def align(spec, theta: torch.Tensor, reference='first', rounds: int = 1, sign: bool = False) -> dict:
+    """theta [C, S, d] or [M, d] draws of the FCN ``spec`` -> every draw with its hidden units matched to those of ``reference``
+    ('first': the first draw; or a tensor of d floats) by one linear assignment problem per hidden layer, solved in a forward
+    sweep; with ``sign`` (tanh only) a matched unit that points the other way is flipped.  ``rounds`` >= 2 repeats the alignment
+    of the ORIGINAL draws, round r to the fp64 mean of round r - 1's aligned draws (those not dropped) cast to fp32.  Returns a
+    dict: 'theta' (theta's shape), 'perm' [..., H] int32 (the draw's unit at each reference position), 'sign' [..., H] int8,
+    'score' [..., n_hidden] fp64 (the matched similarity per layer), 'dropped' [...] int32 (draws with a non-finite similarity:
+    copied unchanged, NaN scores) and 'reference' [d], the row the last round aligned to.  CUDA fp32 draws of nets whose hidden
+    widths are at most 128 run in the library (mile_align_fcn); anything else -- wider nets with a UserWarning -- in
+    ``align_dense``, which may break ties differently."""
+    global LAST_ALIGN_PATH
+    import warnings
+    from mile_amd._lib import ALIGN_WIDTH_MAX
+    _align_check(spec, sign)
+    if theta.dim() not in (2, 3) or theta.shape[-1] != spec.n_params:
+        raise ValueError(f'theta must be [C, S, {spec.n_params}] or [M, {spec.n_params}], got {tuple(theta.shape)}')
+    if int(rounds) < 1:
+        raise ValueError(f'rounds must be at least 1, got {rounds}')
+    flat = theta.reshape(-1, theta.shape[-1])
+    if isinstance(reference, str):
+        if reference != 'first':
+            raise ValueError(f"reference {reference!r} (supported: 'first' or a tensor of {spec.n_params} floats)")
+        ref = flat[0].clone()
+    else:
+        ref = torch.as_tensor(reference).to(flat.device, flat.dtype).reshape(-1).clone()
+        if ref.shape[0] != spec.n_params:
+            raise ValueError(f'reference must hold {spec.n_params} floats, got {tuple(ref.shape)}')
+    wide = max(spec.hidden_structure[:-1], default=0) > ALIGN_WIDTH_MAX
+    on_device = theta.is_cuda and theta.dtype == torch.float32
+    if on_device and wide:
+        warnings.warn(f'align: a hidden layer wider than {ALIGN_WIDTH_MAX} is outside the range of the HIP kernel; using scipy on '
+                      'the host', category=UserWarning)
+    for r in range(int(rounds)):
+        if on_device and not wide:
+            res = _library_align(spec, flat.contiguous(), ref.contiguous(), sign)
+            LAST_ALIGN_PATH = 'library'
+        else:
+            res = align_dense(spec, flat, ref, sign)
+            LAST_ALIGN_PATH = 'scipy'
+        used = ref
+        keep = res[4] == 0
+        if r + 1 < int(rounds) and bool(keep.any()):
+            ref = res[0][keep].double().mean(dim=0).to(flat.dtype)
+    lead = tuple(theta.shape[:-1])
+    out, perm, sgn, score, dropped = res
+    return {'theta': out.reshape(theta.shape), 'perm': perm.reshape(*lead, -1), 'sign': sgn.reshape(*lead, -1),
+            'score': score.reshape(*lead, -1), 'dropped': dropped.reshape(lead), 'reference': used}
+
+
+def aligned_diagnostics(spec, samples: torch.Tensor, n_splits: int = 2, reference='first', rounds: int = 2, sign: bool = False) -> dict:
+    """samples [C, S, d] -> ``chain_diagnostics`` of the draws aligned to ``reference`` (``align``), plus 'switches' [C, n_hidden]
+    (``permutation_switches`` of the returned perms: 0 where a chain keeps one matching throughout), 'score_mean' [n_hidden] (the
+    mean matched similarity per layer over the draws kept), 'scores' [C, S, n_hidden], 'dropped' (a count), 'reference' [d] and
+    'theta', the aligned draws."""
+    if samples.dim() != 3:
+        raise ValueError(f'samples must be [C, S, d], got {tuple(samples.shape)}')
+    al = align(spec, samples, reference, rounds, sign)
+    res = chain_diagnostics(al['theta'], n_splits)
+    res['switches'] = permutation_switches(al['perm'], spec)
+    res['score_mean'] = torch.nanmean(al['score'].reshape(-1, al['score'].shape[-1]), dim=0)
+    res['scores'], res['reference'], res['theta'] = al['score'], al['reference'], al['theta']
+    res['dropped'] = int(al['dropped'].sum())
+    return res
+
+
 # ---- chain diagnostics in function space: the statistics above, of what every draw predicts on every row.  The library
 # streams them (Engine.function_diagnostics, mile_function_diagnostics); the dense forms here are the yardstick and the path
 # for CPU tensors.
