@@ -3,7 +3,7 @@
 mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
 src/inference/metrics.py:247-312):
 
-    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--function-diagnostics [N_SPLITS]] [--canonical-diagnostics [N_SPLITS]] [--aligned-diagnostics [N_SPLITS]] [--tail-diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo] [--stacking]
+    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--function-diagnostics [N_SPLITS]] [--canonical-diagnostics [N_SPLITS]] [--aligned-diagnostics [N_SPLITS]] [--tail-diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo] [--loo-predict] [--stacking]
 
 Reloads config.yaml and the samples/<chain>/sample_<n>.npz files, rebuilds the data split with the same
 seed, evaluates all C x S samples on the split in one device pass and writes metrics.json next to them.
@@ -301,6 +301,19 @@ def loo_metrics(rows):
     return out, arrays
 
 
+def loo_predict_metrics(rows, y, task, coverages):
+    """--loo-predict: the metrics.json keys and the loo_predict.npz arrays of the per-row leave-one-out predictions ``rows``
+    (metrics.loo_predict) on the train split.  Keys: ``loopred_`` + every entry of ``metrics.loo_predict_summary``.  Arrays:
+    expect, posterior, ess_w, khat, dropped per row and, for regression, pit (column 3 of expect, whose sum of weights is 1 only up
+    to rounding, clipped to [0, 1])."""
+    from mile_amd.metrics import loo_predict_summary
+    out = {f'loopred_{k}': v for k, v in loo_predict_summary(rows, y, task, coverages).items()}
+    arrays = {k: rows[k].detach().cpu().numpy() for k in ('expect', 'posterior', 'ess_w', 'khat', 'dropped')}
+    if task == 'regr':
+        arrays['pit'] = np.clip(arrays['expect'][:, 3], 0.0, 1.0)
+    return out, arrays
+
+
 def stacking_refusal(n_chains, n_draws):
     """Why --stacking cannot run on ``n_chains`` chains of ``n_draws`` draws, or None."""
     if n_draws < 2:
@@ -505,6 +518,14 @@ def build_parser():
                          'and means nothing on held-out rows.  loo_* keys in metrics.json (elpd_loo, p_loo, elpd_waic, p_waic with '
                          'standard errors, lppd_sum, the counts of rows with khat > 0.7, without a tail fit and with p_waic > 0.4) and '
                          'lppd, p_waic, elpd_loo, khat, dropped per row in loo.npz')
+    ap.add_argument('--loo-predict', action='store_true',
+                    help='leave-one-out predictions of the ensemble from the PSIS weights of --loo, streamed on the device '
+                         '(mile_loo_predict_stream).  Always on the TRAIN split, like --loo; --loo-r-eff and --coverages apply.  '
+                         'loopred_* keys in metrics.json -- regression: rmse, r2, var_epistemic, var_aleatoric, coverage_<c> and '
+                         'cal_error from the LOO-PIT; classification: accuracy, brier, nll (= -mean elpd_loo), ece, mce; each again as '
+                         '*_insample from the posterior that has seen every row; the share of rows with khat > 0.7 and the minimum and '
+                         'median importance-sampling ESS -- and expect, posterior, ess_w, khat, dropped (regression: pit) per row in '
+                         'loo_predict.npz')
     ap.add_argument('--calibration', type=int, nargs='?', const=15, default=None, metavar='N_BINS',
                     help='classification: prediction sets and calibration of every chain and of the ensemble, streamed on the device '
                          '(mile_calibration_stream) -- highest-probability sets at the levels of --coverages, the rank of the label, Brier '
@@ -732,6 +753,14 @@ def main():
         keys, arrays = loo_metrics(rows)
         out.update(keys)
         np.savez(exp / 'loo.npz', **arrays)
+    if args.loo_predict:
+        from mile_amd.metrics import loo_predict
+        train_x = np.ascontiguousarray(tr.loader.train_x).reshape(len(tr.loader.train_x), -1)
+        train_y = np.ascontiguousarray(tr.loader.train_y)
+        rows = loo_predict(eng, torch.from_numpy(samples), torch.from_numpy(train_x), torch.from_numpy(train_y), r_eff=args.loo_r_eff)
+        keys, arrays = loo_predict_metrics(rows, train_y, cfg.data.task, args.coverages)
+        out.update(keys)
+        np.savez(exp / 'loo_predict.npz', **arrays)
     if args.stacking:
         st = torch.from_numpy(samples)
         train_x = np.ascontiguousarray(tr.loader.train_x).reshape(len(tr.loader.train_x), -1)

@@ -521,6 +521,54 @@ int32_t mile_chain_loo_stream(mile_sampler *s, const float *theta, int32_t C, in
                               int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream);
 int64_t mile_chain_loo_stream_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N);   /* bytes; -1 out of range */
 
+/* PSIS-LOO expectations and LOO-PIT of the ensemble: the importance weights that mile_psis_loo forms and discards, kept per draw,
+ * and with them the leave-one-out expectation of any per-draw quantity (E_loo and loo_pit of the loo package and of ArviZ), per
+ * row, on the device.  The reference has no counterpart.  For row n, l_s, the kept draws, M, the cut, the fit and the smoothed and
+ * capped log weights lw_s with their normalisation lw_s -= logsumexp_s lw are exactly those of mile_psis_loo above.  Then
+ *   w_s = exp(lw_s) for a kept draw, 0 for a dropped one (whose values are never read into a sum).
+ *   Tie rule: draws of a row whose fp32 l_s have equal bits share the mean of their weights -- ties inside the tail, where the
+ *   smoothed weight goes by rank, and ties across the tail's boundary, where some copies are smoothed and some are not.  Every
+ *   output is then a function of the multiset {(l_s, h(s))} and does not change under a permutation of the draws (up to the
+ *   rounding of a sum in another order); sum_s w_s = 1 and elpd_loo = log sum_s w_s exp(l_s) are what they were.
+ *   expect[n][q]    = sum_s w_s h_q(s, n)                for Q columns h_q of per-draw values
+ *   posterior[n][q] = (1 / S_n) sum_{kept s} h_q(s, n)   the in-sample counterpart: the difference is the optimism
+ *   ess_w[n]        = 1 / sum_s w_s^2
+ *   khat[n], elpd_loo[n], dropped[n] as mile_psis_loo gives them.
+ *   A non-finite value of a kept draw goes into the sums of its (row, column) by IEEE rules and into no other.  A row with
+ *   S_n < 2 holds NaN in every fp64 output (its row of weights included).
+ * mile_psis_expect needs no handle: loglik [S, N] fp32 and values [S, N, Q] fp32 from anywhere, 1 <= Q <= 64.  expect, posterior
+ * [N, Q], ess_w, khat, elpd_loo [N] (fp64), dropped [N] int32 and weights [N, S] fp64 (row n: the S weights in draw order) are
+ * device pointers; each may be null, but not all; values may be null if neither expect nor posterior is asked for.  The
+ * workspace (a row tile's packed l, its weights where the caller takes none, the partial sums; within 256 MiB) is allocated and
+ * freed in the call, which returns after the kernels finish.
+ * mile_loo_predict_stream forms the columns itself, for draws theta [S, d] full-layout on (X [N, F], y [N]), from ONE forward
+ * per (draw, row): mile_predict's outputs z of the row tile.  l_s = the likelihood head of mile_pointwise_loglik on those z (the
+ * same fp32 operations: khat, elpd_loo and dropped are mile_loo_stream's).  The columns are formed in fp64 from the fp32 z:
+ *   regression (mu, log sigma), Q = 4: mu, mu^2, sigma^2, Phi((y - mu) / sigma) = 0.5 erfc(-(y - mu) / (sigma sqrt 2)), with
+ *   sigma = exp(log sigma) clipped to [1e-6, 1e6] -- so expect gives the LOO predictive mean, E[mu^2] (epistemic variance
+ *   E[mu^2] - E[mu]^2), the aleatoric variance E[sigma^2] and the LOO-PIT of y_n;
+ *   classification with K <= 64 classes, Q = K: softmax(z) -- the LOO class probabilities.
+ * Rows go in tiles of Nt rows: per (draw, row) the forward's block 4 O bytes, the packed l 4 and the weight 8, plus the partial
+ * sums per row, within 256 MiB (Nt a multiple of 32 where it can be; max_rows_per_tile > 0 caps it); inside a tile the forward
+ * runs in passes of at most max_draws_per_pass draws (0: all).  The workspace is the handle's shared one;
+ * mile_loo_predict_stream_workspace gives its bytes for (S, N) with the library's tile, -1 for a null handle, a shape out of
+ * range or a head the call refuses.
+ * The sums over draws run in fp64 over runs of the draw axis whose boundaries depend on S and Q alone, each run in index order,
+ * the runs combined in index order, without floating-point atomics: a row's result depends on its own S draws alone, and the
+ * outputs are bitwise the same for every max_draws_per_pass and max_rows_per_tile.
+ * MILE_ERR_INVALID: the refusals of mile_psis_loo / mile_loo_stream (null pointers, no output asked for, S, N, r_eff, the tail,
+ * the pass and tile sizes), Q < 1 or > 64, expect or posterior without values, a regression head other than (mu, log sigma),
+ * more than 64 classes (the unsupported-spec refusal: form the columns and call mile_psis_expect); MILE_ERR_STATE: frozen tables
+ * not set; MILE_ERR_NOMEM: the workspace.  Nothing is launched on any of them.
+ * (Added under ABI 10: three new symbols, no struct or existing entry changed.) */
+int32_t mile_psis_expect(const float *loglik, const float *values, int64_t S, int64_t N, int32_t Q, double r_eff, double *expect,
+                         double *posterior, double *ess_w, double *khat, double *elpd_loo, int32_t *dropped, double *weights,
+                         void *stream);
+int32_t mile_loo_predict_stream(mile_sampler *s, const float *theta, int64_t S, const void *X, const void *y, int64_t N, double r_eff,
+                                double *expect, double *posterior, double *ess_w, double *khat, double *elpd_loo, int32_t *dropped,
+                                int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream);
+int64_t mile_loo_predict_stream_workspace(const mile_sampler *s, int64_t S, int64_t N);   /* bytes; -1 out of range */
+
 /* Stacking of chains that do not mix (Yao, Vehtari, Simpson & Gelman 2018; Yao, Vehtari & Gelman 2022): one evaluation of the
  * log score of the weighted mixture of the chains' pointwise predictive densities, with its gradient in the weights and the
  * Gram matrix of the responsibilities (the negative Hessian), on the device.  The reference has no counterpart.  No handle.

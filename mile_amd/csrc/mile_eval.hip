@@ -16,6 +16,7 @@
 #include "mile_lppd.h"
 #include "mile_quantiles.h"
 #include "mile_loo.h"
+#include "mile_lxp.h"
 #include "mile_stack.h"
 #include "mile_calib.h"
 #include "mile_crps.h"
@@ -502,6 +503,123 @@ extern "C" int32_t mile_chain_loo_stream(mile_sampler *s, const float *theta, in
                                          int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
   return loo_stream_chains("mile_chain_loo_stream", s, theta, C, S, X, y, N, r_eff, {lppd, p_waic, elpd_loo, khat, dropped}, max_draws_per_pass,
                            max_rows_per_tile, (hipStream_t)stream);
+}
+
+// mile_psis_expect / mile_loo_predict_stream: every check before any launch; rows in tiles whose packed log-likelihoods, weights,
+// partial sums and (streamed) forward block fit the evaluation budget; k_lxp_pack + k_lxp_row, then k_lxp_apply + k_lxp_finish
+// per tile (mile_lxp.h).
+struct LxpOut {   // expect, posterior [N, Q]; ess_w, khat, elpd_loo, dropped [N]; weights [N, S]; any may be null
+  double *expect, *posterior, *ess_w, *khat, *elpd_loo;
+  int32_t *dropped;
+  double *weights;
+  bool any() const { return expect || posterior || ess_w || khat || elpd_loo || dropped || weights; }
+  bool sums() const { return expect || posterior; }
+};
+static const char *lxp_bad_Q(int32_t Q) { return Q < 1 || Q > LXP_MAX_Q ? "Q out of range (1 .. 64)" : nullptr; }
+// what is wrong with the handle's head for the streamed call, or null; Q: the columns it forms
+static const char *lxp_bad_head(const mile_sampler *s, int *Q) {
+  const EvalView v = eval_view(s);
+  if (v.task == MILE_TASK_REGRESSION) { *Q = 4; return not_mu_log_sigma(s); }
+  *Q = v.O;
+  return v.O > LXP_MAX_Q ? "more than 64 classes are not supported on the device (form the columns and call mile_psis_expect, or use the dense form)" : nullptr;
+}
+
+// The plan of one call: rows per tile, draws per pass and the byte offset of every block of its workspace.  O > 0: the streamed
+// call, whose workspace begins with the forward's raw block [S][Nt][O] (tiles of whole transpose tiles).  Per (draw, row): the raw
+// block O * 4, the packed l 4, the weight 8 where the workspace holds it (own_w); per row: the runs' partial sums where a sum is
+// asked for.
+struct LxpTilePlan { int64_t Nt, chunk; int runs; size_t pk, w, part, cnt, total; };
+static LxpTilePlan lxp_tile_plan(int64_t S, int64_t N, int Q, int O, bool own_w, bool sums, int64_t max_rows, int64_t max_draws) {
+  LxpTilePlan t;
+  const int64_t per_row = S * (4 + (int64_t)O * 4 + (own_w ? 8 : 0)) + (sums ? (int64_t)lxp_part_row_bytes(S, Q) : 0);
+  t.Nt = tile_rows(EVAL_PASS_TARGET, per_row, O > 0 ? LOO_TILE : 1, max_rows, N);
+  t.chunk = pass_draws(EVAL_NO_BUDGET, 1, max_draws, S);
+  t.runs = lxp_runs(S, Q);
+  t.pk = O > 0 ? r256((size_t)S * t.Nt * O * 4) : 0;
+  t.w = t.pk + loo_pk_bytes(S, t.Nt);
+  t.part = t.w + (own_w ? lxp_w_bytes(S, t.Nt) : 0);
+  t.cnt = t.part + (sums ? lxp_part_bytes(S, t.Nt, Q) : 0);
+  t.total = t.cnt + (sums ? lxp_cnt_bytes(S, t.Nt, Q) : 0);
+  return t;
+}
+
+// the tiles of one call, each from `source`: the caller's loglik (src LXP_SRC_VALUES, with the caller's values) or the forward's
+// raw outputs, whose head the kernels apply (y: the caller's labels)
+template <class Source>
+static int lxp_run(char *ws, const LxpTilePlan &t, int64_t S, int64_t N, int n_cu, double r_eff, int src, int Q, int O, int task,
+                   const float *values, const void *y, const LxpOut &o, hipStream_t st, Source source) {
+  LxpParams p{};
+  p.S = (int)S; p.O = O; p.task = task; p.pk = (float *)(ws + t.pk); p.r_eff = r_eff; p.M_full = loo_tail_host(S, r_eff);
+  p.src = src; p.Q = Q; p.runs = t.runs;
+  p.part = (double *)(ws + t.part); p.part_cnt = (int32_t *)(ws + t.cnt);
+  for (int64_t r0 = 0; r0 < N; r0 += t.Nt) {
+    p.Nt = (int)std::min<int64_t>(t.Nt, N - r0);
+    p.slices = loo_slices((int)S, p.Nt, n_cu);
+    Tile tile;
+    const int rc = source(r0, p.Nt, tile);
+    if (rc != MILE_OK) return rc;
+    p.ld = tile.ld;
+    if (src == LXP_SRC_VALUES) { p.ll = tile.at; p.values = values ? values + (size_t)r0 * Q : nullptr; }
+    else { p.raw = tile.at; p.y = (const char *)y + (size_t)r0 * 4; }
+    p.w = o.weights ? o.weights + (size_t)r0 * S : o.sums() ? (double *)(ws + t.w) : nullptr;
+    p.ess_w = o.ess_w ? o.ess_w + r0 : nullptr;
+    p.khat = o.khat ? o.khat + r0 : nullptr;
+    p.elpd_loo = o.elpd_loo ? o.elpd_loo + r0 : nullptr;
+    p.dropped = o.dropped ? o.dropped + r0 : nullptr;
+    p.expect = o.expect ? o.expect + (size_t)r0 * Q : nullptr;
+    p.posterior = o.posterior ? o.posterior + (size_t)r0 * Q : nullptr;
+    HIP_TRY(mile_launch_lxp_rows(p, st));
+    if (o.sums()) HIP_TRY(mile_launch_lxp_apply(p, st));
+  }
+  return MILE_OK;
+}
+
+extern "C" int32_t mile_psis_expect(const float *loglik, const float *values, int64_t S, int64_t N, int32_t Q, double r_eff, double *expect,
+                                    double *posterior, double *ess_w, double *khat, double *elpd_loo, int32_t *dropped, double *weights,
+                                    void *stream) {
+  const LxpOut o{expect, posterior, ess_w, khat, elpd_loo, dropped, weights};
+  if (!loglik) return bad("mile_psis_expect", "null loglik");
+  if (const char *m = loo_bad_SN(S, N)) return bad("mile_psis_expect", m);
+  if (const char *m = lxp_bad_Q(Q)) return bad("mile_psis_expect", m);
+  if (const char *m = loo_bad_args(S, r_eff, o.any())) return bad("mile_psis_expect", m);
+  if (!values && o.sums()) return bad("mile_psis_expect", "expect and posterior need values");
+  hipStream_t st = (hipStream_t)stream;
+  int n_cu;
+  const int rc0 = current_cus(&n_cu);
+  if (rc0 != MILE_OK) return rc0;
+  const LxpTilePlan t = lxp_tile_plan(S, N, Q, 0, !weights && o.sums(), o.sums(), 0, 0);
+  return with_call_ws(t.total, "mile_psis_expect: workspace allocation failed", st, [&](char *ws) {
+    return lxp_run(ws, t, S, N, n_cu, r_eff, LXP_SRC_VALUES, Q, 0, 0, values, nullptr, o, st,
+                   [&](int64_t r0, int, Tile &tile) { tile = {loglik + r0, N}; return (int)MILE_OK; });
+  });
+}
+
+extern "C" int64_t mile_loo_predict_stream_workspace(const mile_sampler *s, int64_t S, int64_t N) {
+  int Q = 0;
+  if (!s || loo_bad_SN(S, N) || lxp_bad_head(s, &Q)) return -1;
+  return (int64_t)lxp_tile_plan(S, N, Q, eval_view(s).O, true, true, 0, 0).total;
+}
+
+extern "C" int32_t mile_loo_predict_stream(mile_sampler *s, const float *theta, int64_t S, const void *X, const void *y, int64_t N, double r_eff,
+                                           double *expect, double *posterior, double *ess_w, double *khat, double *elpd_loo, int32_t *dropped,
+                                           int64_t max_draws_per_pass, int64_t max_rows_per_tile, void *stream) {
+  const char *fn = "mile_loo_predict_stream";
+  const LxpOut o{expect, posterior, ess_w, khat, elpd_loo, dropped, nullptr};
+  int Q = 0;
+  const int rc0 = eval_args(fn, s, !theta || !X || !y, loo_bad_SN(S, N), [&]() -> const char * {
+    if (const char *m = loo_bad_args(S, r_eff, o.any())) return m;
+    if (const char *m = bad_caps(max_draws_per_pass, max_rows_per_tile)) return m;
+    return lxp_bad_head(s, &Q);
+  });
+  if (rc0 != MILE_OK) return rc0;
+  hipStream_t st = (hipStream_t)stream;
+  const EvalView v = eval_view(s);
+  const LxpTilePlan t = lxp_tile_plan(S, N, Q, v.O, o.sums(), o.sums(), max_rows_per_tile, max_draws_per_pass);
+  char *ws;
+  const int rc1 = stream_ws(fn, s, t.total, "lower max_rows_per_tile", ws);
+  if (rc1 != MILE_OK) return rc1;
+  const int src = v.task == MILE_TASK_REGRESSION ? LXP_SRC_REGR : LXP_SRC_CLASS;
+  return lxp_run(ws, t, S, N, v.n_cu, r_eff, src, Q, v.O, v.task, nullptr, y, o, st, stream_tiles(s, theta, S, t.chunk, X, ws, st));
 }
 
 // mile_mixture_crps / mile_crps_stream: every check before any launch; rows in tiles that respect the evaluation budget, the

@@ -5,16 +5,7 @@
 
 #include "mile_device.h"
 #include "mile_loo.h"
-
-#define LOO_LOG_DBL_MIN (-708.39641853226410622)   // log(DBL_MIN)
-
-__device__ __forceinline__ bool loo_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }   // false for NaN and +-inf
-// the order-preserving 32-bit image of a finite float, and back
-__device__ __forceinline__ uint32_t loo_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float loo_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+#include "mile_loo_device.h"
 
 __global__ __launch_bounds__(256) void k_loo_pack(const LooParams p) {
   __shared__ float tile[LOO_TILE][LOO_TILE + 1];
@@ -46,75 +37,8 @@ __global__ __launch_bounds__(256) void k_loo_pack(const LooParams p) {
   }
 }
 
-// a thread's, wave's or row's running statistics of the kept l: count, Welford mean and M2, streaming log-sum-exp (m, s), min
-struct LooStat {
-  int n;
-  double mean, M2, m, s, lo;
-};
-__device__ __forceinline__ void loo_stat_add(LooStat &a, double x) {
-  ++a.n;
-  const double d = x - a.mean;
-  a.mean += d / (double)a.n;
-  a.M2 += d * (x - a.mean);
-  if (x > a.m) { a.s = a.s * exp(a.m - x) + 1.0; a.m = x; }
-  else a.s += exp(x - a.m);
-  a.lo = fmin(a.lo, x);
-}
-// Chan's merge of b into a (a before b)
-__device__ __forceinline__ void loo_stat_merge(LooStat &a, const LooStat &b) {
-  if (b.n == 0) return;
-  if (a.n == 0) { a = b; return; }
-  const double na = (double)a.n, nb = (double)b.n, nn = na + nb, d = b.mean - a.mean;
-  a.mean += d * (nb / nn);
-  a.M2 += b.M2 + d * d * (na * nb / nn);
-  const double mm = fmax(a.m, b.m);
-  a.s = a.s * exp(a.m - mm) + b.s * exp(b.m - mm);
-  a.m = mm;
-  a.lo = fmin(a.lo, b.lo);
-  a.n += b.n;
-}
-
-// sum of v over the workgroup, the same bits in every thread: xor butterfly inside the wave, the waves in index order
-__device__ __forceinline__ double loo_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double loo_block_sum(double v, double *red) {
-  v = loo_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < LOO_NW; ++w) t += red[w];
-  __syncthreads();
-  return t;
-}
-__device__ __forceinline__ double loo_block_max(double v, double *red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = red[0];
-#pragma unroll
-  for (int w = 1; w < LOO_NW; ++w) t = fmax(t, red[w]);
-  __syncthreads();
-  return t;
-}
-
-// ascending bitonic network over a[0, n2), n2 a power of two (the network of mile_diag.hip on 32-bit keys)
-__device__ static void loo_bitonic(uint32_t *a, int n2, int tid) {
-  for (int k = 2; k <= n2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < (n2 >> 1); i += LOO_NT) {
-        const int l = ((i & ~(j - 1)) << 1) | (i & (j - 1)), r = l | j;
-        const uint32_t x = a[l], y = a[r];
-        if ((x > y) == ((l & k) == 0)) { a[l] = y; a[r] = x; }
-      }
-      __syncthreads();
-    }
-}
-
+// (LooStat, the workgroup sums and maxima and loo_bitonic: mile_loo_device.h.  k_loo_row keeps its own text of the stages that
+// header also offers as device functions: its machine code, and with it every bit of its outputs, stays what it was.)
 template <bool LDS>
 __global__ __launch_bounds__(LOO_NT) void k_loo_row(const LooParams p) {
   extern __shared__ float loo_row[];                  // <true>: the row's S values

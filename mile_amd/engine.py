@@ -856,6 +856,74 @@ class Engine:
                                                       int(max_draws_per_pass), int(max_rows_per_tile), self._stream()), self.lib)
         return out
 
+    LXP_OUTPUTS = ('expect', 'posterior', 'ess_w', 'khat', 'elpd_loo', 'dropped')
+
+    def _lxp_outputs(self, outputs, names, N, Q, S):
+        outputs = tuple(outputs)
+        if not outputs or any(k not in names for k in outputs):
+            raise ValueError(f'outputs: a non-empty choice of {names}')
+        shapes = {'expect': (N, Q), 'posterior': (N, Q), 'weights': (N, S)}
+        return {k: torch.empty(shapes.get(k, (N,)), dtype=torch.int32 if k == 'dropped' else torch.float64, device=self.device)
+                for k in outputs}
+
+    def psis_expect(self, loglik, values=None, r_eff: float = 1.0, outputs=None) -> dict:
+        """PSIS-LOO expectations per row from pointwise log-likelihoods loglik [S, N] and per-draw columns values [S, N, Q]
+        (fp32, from anywhere; Q <= 64), by the library's kernels (mile_psis_expect): of the ``outputs`` asked for, ``expect`` and
+        ``posterior`` [N, Q] (sum_s w_s h and the in-sample mean), ``ess_w``, ``khat``, ``elpd_loo`` [N] (fp64), ``dropped`` [N]
+        int32 and ``weights`` [N, S] fp64, the smoothed normalised weights in draw order -- ``metrics.psis_expect_dense`` of the
+        same tensors.  ``outputs=None``: all but the weights, without ``expect`` and ``posterior`` where ``values`` is None."""
+        ll = _f32(loglik, self.device, name='loglik')
+        if ll.ndim != 2:
+            raise ValueError('loglik must be [S, N]')
+        ll = ll.contiguous()
+        S_, N = int(ll.shape[0]), int(ll.shape[1])
+        Q = 1
+        if values is not None:
+            values = _f32(values, self.device, name='values')
+            if values.ndim == 2:
+                values = values[:, :, None]
+            if values.ndim != 3 or values.shape[:2] != ll.shape:
+                raise ValueError('values must be [S, N, Q]')
+            values = values.contiguous()
+            Q = int(values.shape[2])
+        if outputs is None:
+            outputs = self.LXP_OUTPUTS if values is not None else self.LXP_OUTPUTS[2:]
+        out = self._lxp_outputs(outputs, self.LXP_OUTPUTS + ('weights',), N, Q, S_)
+        ptr = lambda k: _ptr(out[k]) if k in out else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_psis_expect(_ptr(ll), _ptr(values), S_, N, Q, float(r_eff), ptr('expect'), ptr('posterior'),
+                                                 ptr('ess_w'), ptr('khat'), ptr('elpd_loo'), ptr('dropped'), ptr('weights'),
+                                                 self._stream()), self.lib)
+        return out
+
+    def loo_predict_columns(self) -> int:
+        """Columns of ``loo_predict_stream``'s ``expect``: 4 for regression (mu, mu^2, sigma^2, PIT), K for classification."""
+        return 4 if self.spec.task == 'regr' else int(self.spec.hidden_structure[-1])
+
+    def loo_predict_stream_workspace(self, S: int, N: int) -> int:
+        """Bytes of the workspace ``loo_predict_stream`` keeps in the handle for S draws on N rows with the library's own tile
+        (mile_loo_predict_stream_workspace); -1 where the call would be refused."""
+        return int(self.lib.mile_loo_predict_stream_workspace(self._h, int(S), int(N)))
+
+    def loo_predict_stream(self, theta, X, y, r_eff: float = 1.0, outputs=LXP_OUTPUTS, max_draws_per_pass: int = 0,
+                           max_rows_per_tile: int = 0) -> dict:
+        """Leave-one-out predictions for draws theta [..., d] on (X [N, F], y [N]), the rows the sampler conditioned on, from one
+        forward per (draw, row) and without ever holding a per-draw tensor (mile_loo_predict_stream): ``expect`` [N, Q] =
+        sum_s w_s h_q with the PSIS weights of ``loo_stream``'s l, for regression the columns (mu, mu^2, sigma^2,
+        Phi((y - mu) / sigma)) -- LOO mean, second moment of the mean, aleatoric variance and LOO-PIT -- and for classification
+        (K <= 64) the class probabilities; ``posterior`` [N, Q] their in-sample means; ``ess_w``, ``khat``, ``elpd_loo`` [N]
+        (fp64) and ``dropped`` [N] int32.  The rows go in tiles of at most ``max_rows_per_tile`` (0: the library's choice), the
+        forward in passes of at most ``max_draws_per_pass`` draws (0: all); the result does not depend on either, bit for bit."""
+        _, th, X, y = self._eval_inputs(theta, X, y)
+        N = int(X.shape[0])
+        out = self._lxp_outputs(outputs, self.LXP_OUTPUTS, N, self.loo_predict_columns(), th.shape[0])
+        ptr = lambda k: _ptr(out[k]) if k in out else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_loo_predict_stream(self._h, _ptr(th), th.shape[0], _ptr(X), _ptr(y), N, float(r_eff), ptr('expect'),
+                                                        ptr('posterior'), ptr('ess_w'), ptr('khat'), ptr('elpd_loo'), ptr('dropped'),
+                                                        int(max_draws_per_pass), int(max_rows_per_tile), self._stream()), self.lib)
+        return out
+
     def stack_eval(self, lpd, w, outputs=('score', 'grad', 'hess', 'used'), max_rows_per_tile: int = 0) -> dict:
         """One evaluation of the stacking objective on the device (mile_stack_eval): lpd [C, N] and w [C] (fp64, entries >= 0)
         -> the ``outputs`` asked for among ``score`` [], ``row_score`` [N], ``grad`` [C], ``hess`` [C, C] (fp64) and ``used`` []

@@ -1442,6 +1442,163 @@ def loo_summary(rows: dict) -> dict:
                 'n_p_waic_above_0.4': int((a['p_waic'] > 0.4).sum())}
 
 
+# ---- PSIS-LOO expectations and LOO-PIT: the torch restatement of mile_psis_expect (Engine.psis_expect / loo_predict_stream)
+# over tensors that fit in memory, the predictive columns, and what evaluate.py --loo-predict reports.  All fp64.
+
+def psis_weights_dense(loglik: torch.Tensor, r_eff: float = 1.0) -> dict:
+    """loglik [..., N] -> ``weights`` [N, S] fp64, the smoothed, capped and normalised PSIS weights of ``psis_loo`` in draw
+    order (0 for a dropped draw), with the tie rule: draws of a row with equal l share the mean of their weights, so the
+    weights are a function of the multiset of a row's draws.  Also ``ess_w`` = 1 / sum w^2, ``khat``, ``elpd_loo`` [N] and
+    ``dropped`` [N] int32.  A row with fewer than two kept draws holds NaN (its weights too)."""
+    if not (math.isfinite(r_eff) and r_eff > 0):
+        raise ValueError('r_eff must be finite and positive')
+    N = loglik.shape[-1]
+    l = loglik.reshape(-1, N).t().to(torch.float64)                     # [N, S]
+    S, dev = l.shape[1], l.device
+    ok = torch.isfinite(l)
+    Sn = ok.sum(dim=1)
+    nan = float('nan')
+    out = {k: torch.full((N,), nan, dtype=torch.float64, device=dev) for k in ('ess_w', 'khat', 'elpd_loo')}
+    out['dropped'] = (S - Sn).to(torch.int32)
+    neg = torch.where(ok, -l, torch.full_like(l, -float('inf')))
+    rs, idx = torch.sort(neg, dim=1, stable=True)                       # ascending; the dropped draws come first
+    ls = torch.gather(l, 1, idx)
+    ws = torch.zeros_like(l)                                            # the weights in sorted order
+    for sn in torch.unique(Sn).tolist():
+        rows = torch.nonzero(Sn == sn).reshape(-1)
+        if sn < 2:
+            ws[rows] = nan
+            continue
+        lg = ls[rows, S - sn:]                                          # the kept draws, l descending
+        rg = rs[rows, S - sn:]
+        rg = rg - rg[:, -1:]                                            # r = -l - max(-l), ascending
+        M = int(math.ceil(min(sn / 5.0, 3.0 * math.sqrt(sn / r_eff))))
+        cut = rg[:, sn - M - 1].clamp(min=_LOG_DBL_MIN)
+        ec = torch.exp(cut)
+        tail = rg[:, sn - M:]
+        khat, sigma, ran = _gpdfit(torch.exp(tail) - ec[:, None])
+        p = (torch.arange(1, M + 1, dtype=torch.float64, device=dev) - 0.5) / M
+        lp = torch.log1p(-p)[None]
+        qv = torch.where((khat == 0)[:, None], -sigma[:, None] * lp, sigma[:, None] * torch.expm1(-khat[:, None] * lp) / khat[:, None])
+        lw = torch.cat([rg[:, :sn - M], torch.where(ran[:, None], torch.log(qv + ec[:, None]), tail)], dim=1).clamp(max=0.0)
+        lw = lw - torch.logsumexp(lw, dim=1, keepdim=True)
+        out['elpd_loo'][rows] = torch.logsumexp(lw + lg, dim=1)
+        out['khat'][rows] = khat
+        w = torch.exp(lw)
+        G = rows.numel()                                                # the mean over every run of equal l (adjacent once sorted)
+        first = torch.cat([torch.ones((G, 1), dtype=torch.bool, device=dev), lg[:, 1:] != lg[:, :-1]], dim=1)
+        run = (torch.cumsum(first.reshape(-1).to(torch.int64), 0) - 1)  # rows start a run: ids never cross a row
+        tot = torch.zeros(int(run[-1]) + 1, dtype=torch.float64, device=dev).index_add_(0, run, w.reshape(-1))
+        cnt = torch.zeros_like(tot).index_add_(0, run, torch.ones_like(w).reshape(-1))
+        w = (tot / cnt)[run].reshape(G, sn)
+        out['ess_w'][rows] = 1.0 / (w * w).sum(dim=1)
+        ws[rows, S - sn:] = w
+    out['weights'] = torch.zeros_like(l).scatter_(1, idx, ws)
+    return out
+
+
+def psis_expect_dense(loglik: torch.Tensor, values: torch.Tensor, r_eff: float = 1.0, return_weights: bool = False) -> dict:
+    """The torch form of Engine.psis_expect: loglik [S, N] and values [S, N, Q] (any float dtype, read as fp64) -> ``expect``
+    [N, Q] = sum_s w_s h_q(s, n) with ``psis_weights_dense``'s weights, ``posterior`` [N, Q] the mean over the kept draws,
+    ``ess_w``, ``khat``, ``elpd_loo`` [N], ``dropped`` [N] (and ``weights`` [N, S]).  The values of a dropped draw enter no
+    sum; a non-finite value of a kept draw propagates by IEEE rules; a row with fewer than two kept draws holds NaN."""
+    out = psis_weights_dense(loglik, r_eff)
+    W = out['weights'] if return_weights else out.pop('weights')        # [N, S]
+    N, S = W.shape
+    v = values.reshape(S, N, -1).to(torch.float64).permute(1, 0, 2)     # [N, S, Q]
+    ok = torch.isfinite(loglik.reshape(S, N).t())
+    v = torch.where(ok[..., None], v, torch.zeros_like(v))
+    Sn = ok.sum(dim=1)
+    few = (Sn < 2)[:, None]
+    nan = torch.full((), float('nan'), dtype=torch.float64, device=W.device)
+    out['expect'] = torch.where(few, nan, (torch.where(ok, W, torch.zeros_like(W))[..., None] * v).sum(dim=1))
+    out['posterior'] = torch.where(few, nan, v.sum(dim=1) / Sn.clamp(min=1)[:, None].to(torch.float64))
+    return out
+
+
+def loo_predict_columns(raw: torch.Tensor, y, task: str) -> torch.Tensor:
+    """The predictive columns of mile_loo_predict_stream from raw outputs raw [..., N, O] (Engine.predict), fp64 [..., N, Q]:
+    regression (mu, log sigma) -> (mu, mu^2, sigma^2, Phi((y - mu) / sigma)) with sigma = exp(log sigma) clipped to
+    [1e-6, 1e6]; classification -> softmax(raw)."""
+    z = raw.to(torch.float64)
+    if task == 'regr':
+        mu = z[..., 0]
+        es = torch.exp(z[..., 1])
+        sig = torch.where(torch.isnan(es), es, es.clamp(1e-6, 1e6))
+        yt = torch.as_tensor(y, device=z.device).to(torch.float64)
+        return torch.stack([mu, mu * mu, sig * sig, 0.5 * torch.erfc(-((yt - mu) / sig) * 0.70710678118654752440)], dim=-1)
+    m = z.max(dim=-1, keepdim=True).values
+    return torch.exp(z - (m + torch.log(torch.exp(z - m).sum(dim=-1, keepdim=True))))
+
+
+def loo_predict(eng, samples, x, y, r_eff: float = 1.0, max_draws_per_pass: int = 0, max_rows_per_tile: int = 0, dense: bool = False) -> dict:
+    """Leave-one-out predictions of the ensemble on the rows (x, y) it conditioned on: Engine.loo_predict_stream where the
+    library's limits allow (2 <= S <= 2^20 pooled draws, a tail of at most 4096, (mu, log sigma) or at most 64 classes),
+    otherwise -- or with ``dense`` -- ``psis_expect_dense`` of Engine.pointwise_loglik's tensor and the columns of
+    Engine.predict's.  ``samples`` [..., d]: every leading axis is a draw axis."""
+    th = torch.as_tensor(samples).reshape(-1, eng.d)
+    S = int(th.shape[0])
+    task = eng.spec.task
+    fits = 2 <= S <= (1 << 20) and math.ceil(min(S / 5.0, 3.0 * math.sqrt(S / r_eff))) <= 4096 and eng.loo_predict_stream_workspace(S, len(x)) > 0
+    if fits and not dense:
+        return eng.loo_predict_stream(th, x, y, r_eff=r_eff, max_draws_per_pass=max_draws_per_pass, max_rows_per_tile=max_rows_per_tile)
+    ll = eng.pointwise_loglik(th, x, y)
+    cols = loo_predict_columns(eng.predict(th, x), torch.as_tensor(y).to(ll.device), 'regr' if task == 'regr' else 'class')
+    return psis_expect_dense(ll, cols, r_eff)
+
+
+def loo_predict_summary(rows: dict, y, task: str, coverages=(0.5, 0.75, 0.9, 0.95), n_bins: int = 15) -> dict:
+    """What a per-row LOO prediction (``loo_predict``, Engine.loo_predict_stream or ``psis_expect_dense`` of the predictive
+    columns) says, on the host in fp64; every key once from ``expect`` and once, with ``_insample``, from ``posterior``.
+    Regression (columns mu, mu^2, sigma^2, PIT): ``rmse`` and ``r2`` of the predictive mean, ``var_epistemic`` = mean_n
+    (E[mu^2] - E[mu]^2), ``var_aleatoric`` = mean_n E[sigma^2], ``coverage_<c>`` of the central intervals from the PIT
+    (``coverage_from_pit``) and their ``cal_error``.  Classification (columns: the class probabilities): ``accuracy``,
+    ``brier``, ``nll``, ``ece`` and ``mce`` (``calibration_decide``); the LOO ``nll`` is -mean_n elpd_loo.  Rows with a
+    non-finite prediction are left out and counted in ``n_rows_nan``.  Then the diagnostics of the weights:
+    ``khat_above_0.7_share`` (of the rows with a fitted tail), ``khat_nofit``, ``ess_w_min``, ``ess_w_median``, ``n_rows``,
+    ``dropped``."""
+    f = lambda k: torch.as_tensor(rows[k]).detach().cpu().to(torch.float64)
+    yt = torch.as_tensor(y).detach().cpu().reshape(-1)
+    N = int(yt.shape[0])
+    cov = [float(c) for c in coverages]
+    out = {}
+    for tag, E in (('', f('expect')), ('_insample', f('posterior'))):
+        E = E.reshape(N, -1)
+        good = torch.isfinite(E).all(dim=1)
+        if task == 'regr':
+            yv = yt.to(torch.float64)[good]
+            mean, m2, alea, pit = (E[good, i] for i in range(4))
+            sq = (yv - mean) ** 2
+            out['rmse' + tag] = float(torch.sqrt(sq.mean()))
+            out['r2' + tag] = float(1.0 - sq.sum() / ((yv - yv.mean()) ** 2).sum())
+            out['var_epistemic' + tag] = float((m2 - mean * mean).mean())
+            out['var_aleatoric' + tag] = float(alea.mean())
+            obs = coverage_from_pit(pit, cov)
+            for c, v in zip(cov, obs):
+                out[f'coverage_{c}{tag}'] = float(v)
+            out['cal_error' + tag] = float(calibration_error(cov, obs))
+        else:
+            dec = calibration_decide(E[None], good[None].to(torch.int32), yt, cov, n_bins)
+            s = calibration_summary({'totals': dec['totals'], 'bins': dec['bins'], 'coverages': cov})[0]
+            for k_out, k_in in (('accuracy', 'acc'), ('brier', 'brier'), ('nll', 'nll'), ('ece', 'ece'), ('mce', 'mce')):
+                out[k_out + tag] = s[k_in]
+        if not tag:
+            out['n_rows_nan'] = int((~good).sum())
+    if task != 'regr':
+        el = f('elpd_loo')
+        out['nll'] = float(-el.mean())
+    khat, ess = f('khat'), f('ess_w')
+    fitted = torch.isfinite(khat)
+    out['khat_above_0.7_share'] = float((khat[fitted] > 0.7).to(torch.float64).mean()) if bool(fitted.any()) else float('nan')
+    out['khat_nofit'] = int((~fitted).sum())
+    fin = ess[torch.isfinite(ess)]
+    out['ess_w_min'] = float(fin.min()) if fin.numel() else float('nan')
+    out['ess_w_median'] = float(fin.median()) if fin.numel() else float('nan')
+    out['n_rows'] = N
+    out['dropped'] = int(torch.as_tensor(rows['dropped']).sum())
+    return out
+
+
 # ---- prediction sets and calibration of the classification ensemble: the torch restatement of mile_calibration
 # (Engine.calibration / calibration_stream) over logits that fit in memory.  The fallback for K > 64 and the tools' yardstick.
 
