@@ -3,9 +3,8 @@
 
 #include <math.h>
 
+#include "mile_block.h"
 #include "mile_calib.h"
-
-__device__ __forceinline__ bool cal_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }   // false for NaN and +-inf
 
 __global__ __launch_bounds__(CAL_NT) void k_cal_accum(const CalParams p) {
   const int n = blockIdx.x * CAL_NT + threadIdx.x, c = blockIdx.y;
@@ -23,8 +22,8 @@ __global__ __launch_bounds__(CAL_NT) void k_cal_accum(const CalParams p) {
     const float *x = base;
     for (int s = 0; s < p.J; ++s, x += stride) {
       float m = x[0];
-      bool fin = cal_finite(m);
-      for (int k = 1; k < K; ++k) { const float v = x[k]; fin = fin && cal_finite(v); m = fmaxf(m, v); }
+      bool fin = finite_f32(m);
+      for (int k = 1; k < K; ++k) { const float v = x[k]; fin = fin && finite_f32(v); m = fmaxf(m, v); }
       if (!fin) continue;
       const double md = (double)m;
       // sum of exp(x - m) over k = 0 .. K-1 in that order in every trip, the trip's own classes kept in registers

@@ -4,10 +4,10 @@
 
 #include <math.h>
 
+#include "mile_block.h"
 #include "mile_device.h"
 #include "mile_crps.h"
 
-__device__ __forceinline__ bool crps_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }   // false for NaN and +-inf
 // first chain block of chain c among the C (C + 1) / 2 blocks c <= c', in row-major order of the upper triangle
 __device__ __forceinline__ int crps_block0(int c, int C) { return c * (2 * C - c + 1) / 2; }
 
@@ -26,7 +26,7 @@ __global__ __launch_bounds__(CRPS_NT) void k_crps_pack(const CrpsParams p) {
       float2 v = make_float2(qnan, qnan);
       if (s < S && r0 + tx < Nt) {
         const float2 r = raw[(size_t)s * (size_t)p.ld + r0 + tx];
-        if (crps_finite(r.x) && crps_finite(r.y)) {
+        if (finite_f32(r.x) && finite_f32(r.y)) {
           const float sg = fminf(fmaxf(expf(r.y), 1e-6f), 1e6f);
           v = make_float2(r.x, sg * sg);
         }
@@ -179,19 +179,6 @@ __global__ __launch_bounds__(CRPS_NT) void k_crps_pairs(const CrpsParams p) {
   if (tid == 0) p.part[(size_t)n * units + u] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-// sum of v over the workgroup, the same bits in every thread: xor butterfly inside the wave, the waves in index order
-__device__ __forceinline__ double crps_block_sum(double v, double *red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < CRPS_NT / 64; ++w) t += red[w];
-  __syncthreads();
-  return t;
-}
-
 __global__ __launch_bounds__(CRPS_NT) void k_crps_finish(const CrpsParams p) {
   __shared__ double a_s[CRPS_MAX_C], w_s[CRPS_MAX_C];
   __shared__ int K_s[CRPS_MAX_C];
@@ -209,8 +196,7 @@ __global__ __launch_bounds__(CRPS_NT) void k_crps_finish(const CrpsParams p) {
     const int K = K_s[c];
     double sum = 0.0;
     for (int i = lane; i < K; i += 64) { const float2 v = g[i]; sum += crps_A64(yv - (double)v.x, (double)v.y); }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);
+    sum = wave_sum(sum);
     if (lane == 0) a_s[c] = sum / (double)K;     // NaN for an empty chain
   }
   __syncthreads();
@@ -255,8 +241,8 @@ __global__ __launch_bounds__(CRPS_NT) void k_crps_finish(const CrpsParams p) {
         if (w2 != 0.0) t2 += (c2 == c ? 1.0 : 2.0) * wc * w2 * blk[(size_t)(c2 - c) * upb];
       }
     }
-    t1 = crps_block_sum(t1, red);
-    t2 = crps_block_sum(t2, red);
+    t1 = block_sum<CRPS_NT / 64>(t1, red);
+    t2 = block_sum<CRPS_NT / 64>(t2, red);
     if (tid == 0) {
       const bool none = m == 0 && Ktot == 0;
       if (p.crps_mix) p.crps_mix[(size_t)m * p.N + row] = none ? qnan : t1 - 0.5 * t2;

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(DIAG_POOL_NT) void k_diag_pool_rank(DiagParams p) {
     for (int i = tid; i < n; i += DIAG_POOL_NT) dst[i] = __int_as_float(0x7fc00000);
     return;
   }
-  diag_bitonic(a, n2, tid, DIAG_POOL_NT);
+  bitonic(a, n2, tid, DIAG_POOL_NT);
   for (int i = tid; i < n; i += DIAG_POOL_NT) dst[(uint32_t)a[i]] = (float)diag_rank_score(a, n, i);
 }
 
@@ -60,17 +60,17 @@ __device__ static void diag_split_moments(const float *x, int S, int n_splits, d
                                           double &M, double &ss) {
   double s = 0.0;
   for (int t = tid; t < S; t += DIAG_CHAIN_NT) s += (double)x[t];
-  M = diag_block_sum(s, red, tid) / (double)S;
+  M = block_sum<4>(s, red) / (double)S;
   const int len = S / n_splits, lane = tid & 63, wave = tid >> 6;
   double av = 0.0, as = 0.0;
   for (int k = wave; k < n_splits; k += DIAG_CHAIN_NT / 64) {
     const float *xk = x + k * len;
     double s1 = 0.0;
     for (int t = lane; t < len; t += 64) s1 += (double)xk[t];
-    const double mk = diag_wave_sum(s1) / (double)len;
+    const double mk = wave_sum(s1) / (double)len;
     double s2 = 0.0;
     for (int t = lane; t < len; t += 64) { const double e = (double)xk[t] - mk; s2 += e * e; }
-    av += diag_wave_sum(s2) / (double)(len - 1);
+    av += wave_sum(s2) / (double)(len - 1);
     as += (mk - M) * (mk - M);
   }
   if (lane == 0) { red[wave] = av; red[4 + wave] = as; }
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(DIAG_CHAIN_NT) void k_diag_chain(DiagParams p) {
         for (int i = tid; i < S2; i += DIAG_CHAIN_NT)
           a[i] = i < S ? (((uint64_t)diag_key(xf[i]) << 32) | (uint32_t)i) : ~0ull;
         __syncthreads();
-        diag_bitonic(a, S2, tid, DIAG_CHAIN_NT);
+        bitonic(a, S2, tid, DIAG_CHAIN_NT);
         for (int i = tid; i < S; i += DIAG_CHAIN_NT) xf[(uint32_t)a[i]] = (float)diag_rank_score(a, S, i);
         __syncthreads();
         double sumvar, M, ss;

@@ -1,10 +1,13 @@
-// Device helpers of the chain-diagnostics kernels (mile_diag.hip, mile_dtail.hip): the normal quantile, the order-preserving
-// fp32 key, the bitonic network on (key, index) words, the tie-averaged normal score of a sorted position, and the fixed-order
-// wave and workgroup sums.  One statement of each, so that two kernels that rank the same draws write the same bits.
+// Device helpers of the chain-diagnostics kernels (mile_diag.hip, mile_dtail.hip): the normal quantile, the fp32 key of the
+// (key, index) words that mile_block.h's bitonic network sorts, and the tie-averaged normal score of a sorted position.  One
+// statement of each, so that two kernels that rank the same draws write the same bits.  The fixed-order wave and workgroup sums
+// are mile_block.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include "mile_block.h"
 
 // ---- normal quantile ---------------------------------------------------------------------------------------------------
 // x <= 0 with Phi(x) = q for q in (0, 0.5]: Acklam's rational approximation (relative error 1.2e-9), then two Halley
@@ -42,22 +45,7 @@ __host__ __device__ static inline double diag_score(double rank, int n) {
 // with by the callers before any rank is used.
 __device__ __forceinline__ uint32_t diag_key(float x) {
   if (x == 0.0f) x = 0.0f;
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// Bitonic network over a[0, n2), n2 a power of two, ascending, on (key << 32 | index) words: integer comparisons of
-// distinct words, a fixed number of stages.  The caller has synchronised after filling a[].
-__device__ static void diag_bitonic(uint64_t *a, int n2, int tid, int nt) {
-  for (int k = 2; k <= n2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < (n2 >> 1); i += nt) {
-        const int l = ((i & ~(j - 1)) << 1) | (i & (j - 1)), r = l | j;
-        const uint64_t x = a[l], y = a[r];
-        if ((x > y) == ((l & k) == 0)) { a[l] = y; a[r] = x; }
-      }
-      __syncthreads();
-    }
+  return f32_key(x);
 }
 
 // Normal score of sorted position i of the n real entries: the average of the ranks of its tie group, whose ends come
@@ -76,19 +64,4 @@ __device__ static double diag_rank_score(const uint64_t *a, int n, int i) {
     hi = b;
   }
   return diag_score(0.5 * (double)(lo + hi + 1), n);     // ranks lo+1 .. hi
-}
-
-// ---- fixed-order sums: a wave by xor-shuffles, a workgroup of 256 by its four waves in index order ---------------------------
-__device__ __forceinline__ double diag_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ static double diag_block_sum(double v, double *red, int tid) {
-  v = diag_wave_sum(v);
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  const double t = ((red[0] + red[1]) + red[2]) + red[3];
-  __syncthreads();
-  return t;
 }

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(DIAG_POOL_NT) void k_dtail_derive(DtailParams p) {
     }
     return;
   }
-  diag_bitonic(a, n2, tid, DIAG_POOL_NT);
+  bitonic(a, n2, tid, DIAG_POOL_NT);
   for (int i = tid; i < n; i += DIAG_POOL_NT) z[(uint32_t)a[i]] = (float)diag_rank_score(a, n, i);
   if (tid == 0) {                   // integer indices only: ceil(n/20) - 1, ceil(19n/20) - 1, and the two middle draws
     const float q_lo = src[(uint32_t)a[(n + 19) / 20 - 1]], q_hi = src[(uint32_t)a[(19 * n + 19) / 20 - 1]];
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(DIAG_POOL_NT) void k_dtail_derive(DtailParams p) {
     for (int i = tid; i < n; i += DIAG_POOL_NT) zf[i] = qnan;
     return;
   }
-  diag_bitonic(a, n2, tid, DIAG_POOL_NT);
+  bitonic(a, n2, tid, DIAG_POOL_NT);
   for (int i = tid; i < n; i += DIAG_POOL_NT) zf[(uint32_t)a[i]] = (float)diag_rank_score(a, n, i);
 }
 
@@ -84,7 +84,7 @@ template <class V>
 __device__ __forceinline__ double dtail_piece_mean(V v, int len, int lane) {
   double s = 0.0;
   for (int t = lane; t < len; t += 64) s += v(t);
-  return diag_wave_sum(s) / (double)len;
+  return wave_sum(s) / (double)len;
 }
 
 __global__ __launch_bounds__(DTAIL_ESS_NT) void k_dtail_ess(DtailParams p) {
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(DTAIL_ESS_NT) void k_dtail_ess(DtailParams p) {
   // length), and for the raw series the sd of the pooled draws.
   double s = 0.0;
   for (int i = tid; i < n; i += DTAIL_ESS_NT) s += dtail_value(col, ind, thr, i);
-  const double G = diag_block_sum(s, red, tid) / fn;
+  const double G = block_sum<4>(s, red) / fn;
   double as = 0.0;
   for (int m = wave; m < M; m += DTAIL_ESS_NT / 64) {
     const float *pc = col + (long long)m * len;
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(DTAIL_ESS_NT) void k_dtail_ess(DtailParams p) {
   if (ser == 3) {
     double s2 = 0.0;
     for (int i = tid; i < n; i += DTAIL_ESS_NT) { const double e = (double)col[i] - G; s2 += e * e; }
-    const double sd = sqrt(diag_block_sum(s2, red, tid) / (fn - 1.0));
+    const double sd = sqrt(block_sum<4>(s2, red) / (fn - 1.0));
     if (tid == 0 && p.res) p.res[(long long)q * DTAIL_NRES + 4] = sd;
   }
 

@@ -1,24 +1,49 @@
-// Device helpers of the PSIS kernels, shared by mile_loo.hip (k_loo_row) and mile_lxp.hip (k_lxp_row): the order-preserving key
-// of a float, a row's running statistics and their merge, the workgroup sums and maxima, the LDS bitonic network, and the stages
-// of one row (mile_loo.h numbers them) as device functions of a workgroup of LOO_NT threads, the same operations in the same
-// order as k_loo_row's own text.  Every function that holds a barrier is called by all threads of the workgroup with the same
-// arguments.
+// Device code of the PSIS kernels, shared by mile_loo.hip (k_loo_pack, k_loo_row) and mile_lxp.hip (k_lxp_pack, k_lxp_row): the
+// pack's transpose, a row's running statistics and their merge, and the stages of one row (mile_loo.h numbers them) as device
+// functions of a workgroup of LOO_NT threads.  Both row kernels are built from these stages: this is their one text, so the two
+// write the same bits for the same row.  The workgroup primitives are mile_block.h's.  Every function that holds a barrier is
+// called by all threads of the workgroup with the same arguments.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "mile_block.h"
 #include "mile_loo.h"
 
 #define LOO_LOG_DBL_MIN (-708.39641853226410622)   // log(DBL_MIN)
 
-__device__ __forceinline__ bool loo_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }   // false for NaN and +-inf
-// the order-preserving 32-bit image of a finite float, and back
-__device__ __forceinline__ uint32_t loo_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+// The pack of a tile of Nt rows: workgroup (x, y) of 256 threads transposes slice y of the draws of rows 32 x .. 32 x + 31 into
+// pk [Nt][S], through LDS in 32 x 32 pieces; load(draw, row) is the value, and one that is not finite is packed as NaN.
+template <class Load>
+__device__ __forceinline__ void loo_pack_tile(float *pk, int S, int Nt, int slices, Load load) {
+  __shared__ float tile[LOO_TILE][LOO_TILE + 1];
+  const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
+  const int r0 = blockIdx.x * LOO_TILE, sl = blockIdx.y, row = r0 + tx;
+  const int s_tiles = (S + LOO_TILE - 1) / LOO_TILE;
+  const int t0 = (int)(((long long)sl * s_tiles) / slices), t1 = (int)(((long long)(sl + 1) * s_tiles) / slices);
+  const float qnan = __int_as_float(0x7fc00000);
+  for (int t = t0; t < t1; ++t) {
+    const int sb = t * LOO_TILE;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {     // row tx of draws ty, ty + 8, ...: a half-wave reads 32 consecutive rows of one draw
+      const int j = ty + 8 * k, s = sb + j;
+      float v = qnan;
+      if (s < S && row < Nt) {
+        const float r = load(s, row);
+        if (finite_f32(r)) v = r;
+      }
+      tile[j][tx] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {     // draw sb + tx of rows ty, ty + 8, ...: a half-wave writes 32 consecutive values of one row
+      const int rr = ty + 8 * k, s = sb + tx;
+      if (s < S && r0 + rr < Nt) pk[(size_t)(r0 + rr) * S + s] = tile[tx][rr];
+    }
+    __syncthreads();
+  }
 }
-__device__ __forceinline__ float loo_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 // a thread's, wave's or row's running statistics of the kept l: count, Welford mean and M2, streaming log-sum-exp (m, s), min
 struct LooStat {
@@ -46,47 +71,6 @@ __device__ __forceinline__ void loo_stat_merge(LooStat &a, const LooStat &b) {
   a.m = mm;
   a.lo = fmin(a.lo, b.lo);
   a.n += b.n;
-}
-
-// sum of v over the workgroup, the same bits in every thread: xor butterfly inside the wave, the waves in index order
-__device__ __forceinline__ double loo_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double loo_block_sum(double v, double *red) {
-  v = loo_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < LOO_NW; ++w) t += red[w];
-  __syncthreads();
-  return t;
-}
-__device__ __forceinline__ double loo_block_max(double v, double *red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = red[0];
-#pragma unroll
-  for (int w = 1; w < LOO_NW; ++w) t = fmax(t, red[w]);
-  __syncthreads();
-  return t;
-}
-
-// ascending bitonic network over a[0, n2), n2 a power of two (the network of mile_diag.hip on 32-bit keys)
-__device__ static void loo_bitonic(uint32_t *a, int n2, int tid) {
-  for (int k = 2; k <= n2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < (n2 >> 1); i += LOO_NT) {
-        const int l = ((i & ~(j - 1)) << 1) | (i & (j - 1)), r = l | j;
-        const uint32_t x = a[l], y = a[r];
-        if ((x > y) == ((l & k) == 0)) { a[l] = y; a[r] = x; }
-      }
-      __syncthreads();
-    }
 }
 
 // ---- the stages of one row ------------------------------------------------------------------------------------------------------
@@ -133,7 +117,7 @@ __device__ __forceinline__ LooCut loo_row_select(Val val, int S, int M, uint32_t
     for (int i = tid; i < S; i += LOO_NT) {
       const float v = val(i);
       if (v == v) {
-        const uint32_t k = loo_key(v);
+        const uint32_t k = f32_key(v);
         if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
       }
     }
@@ -162,7 +146,7 @@ __device__ __forceinline__ void loo_row_sort_tail(Val val, int S, int M, const L
   for (int i = tid; i < S; i += LOO_NT) {
     const float v = val(i);
     if (v == v) {
-      const uint32_t k = loo_key(v);
+      const uint32_t k = f32_key(v);
       if (k < c.T) {
         const uint32_t slot = atomicAdd(tail_cnt, 1u);
         if (slot < (uint32_t)LOO_MAX_TAIL) tkey[slot] = k;
@@ -173,7 +157,7 @@ __device__ __forceinline__ void loo_row_sort_tail(Val val, int S, int M, const L
   while (P < M) P <<= 1;
   for (int i = c.n_low + tid; i < P; i += LOO_NT) tkey[i] = i < M ? c.T : 0xffffffffu;
   __syncthreads();
-  loo_bitonic(tkey, P, tid);
+  bitonic(tkey, P, tid, LOO_NT);
 }
 
 // 4. and 5. the exceedances x_i = exp(r_(i)) - ec into tx [0, M), ascending (tx[i] belongs to tkey[M - 1 - i]), and the fit
@@ -182,7 +166,7 @@ __device__ __forceinline__ LooFit loo_row_fit(int M, const uint32_t *tkey, doubl
                                               double *red) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const double qnan = __longlong_as_double(0x7ff8000000000000LL);
-  for (int i = tid; i < M; i += LOO_NT) tx[i] = exp(-(double)loo_unkey(tkey[M - 1 - i]) - mx) - ec;
+  for (int i = tid; i < M; i += LOO_NT) tx[i] = exp(-(double)f32_unkey(tkey[M - 1 - i]) - mx) - ec;
   __syncthreads();
   const double fM = (double)M;
   LooFit f{false, qnan, qnan};
@@ -197,7 +181,7 @@ __device__ __forceinline__ LooFit loo_row_fit(int M, const uint32_t *tkey, doubl
       const double bj = (1.0 - sqrt((double)m / ((double)(j + 1) - 0.5))) / (3.0 * xq) + 1.0 / xM;
       double acc = 0.0;
       for (int i = lane; i < M; i += 64) acc += log1p(-bj * tx[i]);
-      const double kj = loo_wave_sum(acc) / fM;
+      const double kj = wave_sum(acc) / fM;
       if (lane == 0) { cb[j] = bj; cL[j] = fM * (log(-bj / kj) - kj - 1.0); }
     }
     __syncthreads();
@@ -212,7 +196,7 @@ __device__ __forceinline__ LooFit loo_row_fit(int M, const uint32_t *tkey, doubl
     for (int j = 0; j < m; ++j) b += cb[j] * cw[j];
     double acc = 0.0;
     for (int i = tid; i < M; i += LOO_NT) acc += log1p(-b * tx[i]);
-    const double k = loo_block_sum(acc, red) / fM;
+    const double k = block_sum<LOO_NW>(acc, red) / fM;
     f.sigma = -k / b;
     f.khat = (fM * k + 5.0) / (fM + 10.0);
     f.fit = fabs(f.khat) <= 1.7976931348623157e308 && fabs(f.sigma) <= 1.7976931348623157e308;
@@ -229,7 +213,7 @@ __device__ __forceinline__ void loo_row_smooth(int M, const uint32_t *tkey, doub
   const double fM = (double)M;
   __syncthreads();
   for (int i = tid; i < M; i += LOO_NT) {
-    const double l = (double)loo_unkey(tkey[M - 1 - i]);
+    const double l = (double)f32_unkey(tkey[M - 1 - i]);
     double lw;
     if (f.fit) {
       const double lp = log1p(-((double)(i + 1) - 0.5) / fM);
@@ -243,8 +227,8 @@ __device__ __forceinline__ void loo_row_smooth(int M, const uint32_t *tkey, doub
     mlw = fmax(mlw, lw);
     ma = fmax(ma, lw + l);
   }
-  mlw = loo_block_max(mlw, red);
-  ma = loo_block_max(ma, red);
+  mlw = block_max<LOO_NW>(mlw, red);
+  ma = block_max<LOO_NW>(ma, red);
 }
 
 // 6. s1 = sum exp(lw - mlw) and s2 = sum exp(lw + l - ma) over the kept draws: the body from the row, the tail from LDS, the copies
@@ -256,20 +240,20 @@ __device__ __forceinline__ void loo_row_sums(Val val, int S, int M, const LooCut
   s1 = 0.0; s2 = 0.0;
   for (int i = tid; i < S; i += LOO_NT) {
     const float v = val(i);
-    if (v == v && loo_key(v) > c.T) {
+    if (v == v && f32_key(v) > c.T) {
       const double l = (double)v, r = -l - mx;
       s1 += exp(r - mlw);
       s2 += exp((r + l) - ma);
     }
   }
   for (int i = tid; i < M; i += LOO_NT) {
-    const double l = (double)loo_unkey(tkey[M - 1 - i]), lw = tx[i];
+    const double l = (double)f32_unkey(tkey[M - 1 - i]), lw = tx[i];
     s1 += exp(lw - mlw);
     s2 += exp((lw + l) - ma);
   }
-  s1 = loo_block_sum(s1, red);
-  s2 = loo_block_sum(s2, red);
-  const double lT = (double)loo_unkey(c.T), tie_body = (double)(c.neq - c.n_tie);
+  s1 = block_sum<LOO_NW>(s1, red);
+  s2 = block_sum<LOO_NW>(s2, red);
+  const double lT = (double)f32_unkey(c.T), tie_body = (double)(c.neq - c.n_tie);
   s1 += tie_body * exp(r_T - mlw);
   s2 += tie_body * exp((r_T + lT) - ma);
 }

@@ -11,35 +11,10 @@
 // k_loo_pack's transpose; HEAD: the value is row_loglik of the forward's raw outputs of the (draw, row)
 template <bool HEAD>
 __global__ __launch_bounds__(256) void k_lxp_pack(const LxpParams p) {
-  __shared__ float tile[LOO_TILE][LOO_TILE + 1];
-  const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
-  const int r0 = blockIdx.x * LOO_TILE, sl = blockIdx.y, row = r0 + tx;
-  const int S = p.S, Nt = p.Nt;
-  const int s_tiles = (S + LOO_TILE - 1) / LOO_TILE;
-  const int t0 = (int)(((long long)sl * s_tiles) / p.slices), t1 = (int)(((long long)(sl + 1) * s_tiles) / p.slices);
-  const float qnan = __int_as_float(0x7fc00000);
-  for (int t = t0; t < t1; ++t) {
-    const int sb = t * LOO_TILE;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {     // row tx of draws ty, ty + 8, ...: a half-wave reads 32 consecutive rows of one draw
-      const int j = ty + 8 * k, s = sb + j;
-      float v = qnan;
-      if (s < S && row < Nt) {
-        float r;
-        if constexpr (HEAD) r = row_loglik(p.raw + ((size_t)s * (size_t)p.ld + row) * p.O, p.O, p.task, p.y, row);
-        else r = p.ll[(size_t)s * (size_t)p.ld + row];
-        if (loo_finite(r)) v = r;
-      }
-      tile[j][tx] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {     // draw sb + tx of rows ty, ty + 8, ...: a half-wave writes 32 consecutive values of one row
-      const int rr = ty + 8 * k, s = sb + tx;
-      if (s < S && r0 + rr < Nt) p.pk[(size_t)(r0 + rr) * S + s] = tile[tx][rr];
-    }
-    __syncthreads();
-  }
+  loo_pack_tile(p.pk, p.S, p.Nt, p.slices, [&](int s, int row) -> float {
+    if constexpr (HEAD) return row_loglik(p.raw + ((size_t)s * (size_t)p.ld + row) * p.O, p.O, p.task, p.y, row);
+    else return p.ll[(size_t)s * (size_t)p.ld + row];
+  });
 }
 
 template <bool LDS>
@@ -82,7 +57,7 @@ __global__ __launch_bounds__(LOO_NT) void k_lxp_row(const LxpParams p) {
   const double lmin = st.lo, mx = -lmin;     // r = -l - max(-l)
   const LooCut c = loo_row_select(val, S, M, hist, sel);
   loo_row_sort_tail(val, S, M, c, tkey, &tail_cnt);
-  const double r_T = -(double)loo_unkey(c.T) - mx;
+  const double r_T = -(double)f32_unkey(c.T) - mx;
   const double cut = fmax(r_T, LOO_LOG_DBL_MIN), ec = exp(cut);
   const LooFit f = loo_row_fit(M, tkey, tx, mx, ec, cb, cL, cw, red);
   if (tid == 0 && p.khat) p.khat[n] = f.khat;
@@ -109,7 +84,7 @@ __global__ __launch_bounds__(LOO_NT) void k_lxp_row(const LxpParams p) {
   // the draws with key == T: n_tie of them in the tail (slots tx[0, n_tie)), the others in the body at lw = r_T
   double tie = 0.0;
   for (int i = tid; i < c.n_tie; i += LOO_NT) tie += tx[i];
-  tie = loo_block_sum(tie, red);     // (its barriers also publish the heads' slots)
+  tie = block_sum<LOO_NW>(tie, red);     // (its barriers also publish the heads' slots)
   const double w_T = (tie + (double)(c.neq - c.n_tie) * exp(r_T - logZ)) / (double)c.neq;
   // c. every draw's weight, in draw order
   double sq = 0.0;
@@ -117,7 +92,7 @@ __global__ __launch_bounds__(LOO_NT) void k_lxp_row(const LxpParams p) {
     const float v = val(i);
     double w = 0.0;
     if (v == v) {
-      const uint32_t k = loo_key(v);
+      const uint32_t k = f32_key(v);
       if (k > c.T) {
         w = exp((-(double)v - mx) - logZ);
       } else if (k == c.T) {
@@ -134,7 +109,7 @@ __global__ __launch_bounds__(LOO_NT) void k_lxp_row(const LxpParams p) {
     sq += w * w;
     if (wout) wout[i] = w;
   }
-  sq = loo_block_sum(sq, red);
+  sq = block_sum<LOO_NW>(sq, red);
   if (tid == 0 && p.ess_w) p.ess_w[n] = 1.0 / sq;
 }
 

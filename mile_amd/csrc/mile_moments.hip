@@ -4,9 +4,8 @@
 
 #include <math.h>
 
+#include "mile_block.h"
 #include "mile_moments.h"
-
-__device__ __forceinline__ bool mom_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }   // false for NaN and +-inf
 
 // p log p with the product rounded on its own (no contraction into the sum that follows): a draw's entropy and the
 // entropy of a one-draw mean are then the same arithmetic, and their difference is exactly 0
@@ -38,7 +37,7 @@ __global__ __launch_bounds__(MOM_NT) void k_moments_accum(const MomParams p) {
 #pragma unroll 4
     for (int s = s0; s < s1; ++s, r += N) {
       const float2 v = *r;
-      if (mom_finite(v.x) && mom_finite(v.y)) {
+      if (finite_f32(v.x) && finite_f32(v.y)) {
         ++c;
         const double x = (double)v.x, d = x - mean;
         mean += d / (double)c;
@@ -64,8 +63,8 @@ __global__ __launch_bounds__(MOM_NT) void k_moments_accum(const MomParams p) {
       for (int s = s0; s < s1; ++s) {
         const float *x = p.raw + ((size_t)s * N + n) * K;
         float m = x[0];
-        bool fin = mom_finite(m);
-        for (int k = 1; k < K; ++k) { const float v = x[k]; fin = fin && mom_finite(v); m = fmaxf(m, v); }
+        bool fin = finite_f32(m);
+        for (int k = 1; k < K; ++k) { const float v = x[k]; fin = fin && finite_f32(v); m = fmaxf(m, v); }
         if (!fin) continue;
         const double md = (double)m;
         // sum of exp(x - m) over k = 0 .. K-1 in that order in every trip, the trip's own classes kept in registers

@@ -6,10 +6,10 @@
 
 #include <type_traits>
 
+#include "mile_block.h"
 #include "mile_device.h"
 #include "mile_quantiles.h"
 
-__device__ __forceinline__ bool qnt_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }   // false for NaN and +-inf
 __device__ __forceinline__ double qnt_sigma(float log_sigma) { return fmin(fmax(exp((double)log_sigma), 1e-6), 1e6); }
 // 1 / sigma: the clip of the reciprocal is the reciprocal of the clip, and an exp costs about what the division would
 __device__ __forceinline__ double qnt_rsigma(float log_sigma) { return fmin(fmax(exp(-(double)log_sigma), 1e-6), 1e6); }
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void k_qnt_pack(const QntParams p) {
       float2 v = make_float2(qnan, qnan);
       if (s < S && row < Nt) {
         const float2 r = raw[(size_t)s * (size_t)p.ld + row];
-        if (qnt_finite(r.x) && qnt_finite(r.y)) {
+        if (finite_f32(r.x) && finite_f32(r.y)) {
           v = r;
           ++cnt;
           const double mu = (double)r.x, sig = qnt_sigma(r.y);
@@ -80,19 +80,6 @@ __global__ __launch_bounds__(256) void k_qnt_pack(const QntParams p) {
       }
     }
   }
-}
-
-// sum of v over the workgroup, the same bits in every thread: xor butterfly inside the wave, the waves in index order
-__device__ __forceinline__ double qnt_block_sum(double v, double *red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < QNT_NW; ++w) t += red[w];
-  __syncthreads();
-  return t;
 }
 
 // omega of component i's chain, for a walk of increasing i: the division only where the walk enters another chain
@@ -192,8 +179,8 @@ __global__ __launch_bounds__(QNT_NT) void k_qnt_solve(const P p) {
         if (v.x == v.x) { const double sg = qnt_sigma(v.y); sm += (double)v.x; sv += sg * sg; }
       }
     }
-    sm = qnt_block_sum(sm, redb);
-    sv = qnt_block_sum(sv, redb);
+    sm = block_sum<QNT_NW>(sm, redb);
+    sv = block_sum<QNT_NW>(sv, redb);
     const double mean = W ? sm : sm / fk;
     double sd2 = 0.0;
     if constexpr (W) {
@@ -209,7 +196,7 @@ __global__ __launch_bounds__(QNT_NT) void k_qnt_solve(const P p) {
         if (v.x == v.x) { const double d = (double)v.x - mean; sd2 += d * d; }
       }
     }
-    sd2 = qnt_block_sum(sd2, redb);
+    sd2 = block_sum<QNT_NW>(sd2, redb);
     const double sd = W ? sqrt(sd2 + sv) : sqrt((sd2 + sv) / fk);
 
     const int nc = 64 / Q, q = lane % Q, cl = lane / Q;     // components a wave takes at a time; this lane's level and slot
@@ -330,7 +317,7 @@ __global__ __launch_bounds__(QNT_NT) void k_qnt_solve(const P p) {
         if (v.x == v.x) F += qnt_Phi((yv - (double)v.x) * qnt_rsigma(v.y));
       }
     }
-    F = qnt_block_sum(F, redb);
+    F = block_sum<QNT_NW>(F, redb);
     if (tid == 0) p.pit[n] = (float)(W ? F : F / fk);
   }
   if (p.sweeps && tid == 0) p.sweeps[n] = sweeps;
