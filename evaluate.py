@@ -3,7 +3,7 @@
 mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
 src/inference/metrics.py:247-312):
 
-    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--function-diagnostics [N_SPLITS]] [--canonical-diagnostics [N_SPLITS]] [--aligned-diagnostics [N_SPLITS]] [--tail-diagnostics [N_SPLITS]] [--moments] [--running [N_POINTS]] [--intervals] [--loo] [--loo-predict] [--stacking]
+    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--function-diagnostics [N_SPLITS]] [--canonical-diagnostics [N_SPLITS]] [--aligned-diagnostics [N_SPLITS]] [--tail-diagnostics [N_SPLITS]] [--moments] [--sensitivities] [--running [N_POINTS]] [--intervals] [--loo] [--loo-predict] [--stacking]
 
 Reloads config.yaml and the samples/<chain>/sample_<n>.npz files, rebuilds the data split with the same
 seed, evaluates all C x S samples on the split in one device pass and writes metrics.json next to them.
@@ -250,6 +250,43 @@ def moment_metrics(moments, dropped, y, task):
         out = {'moments_probs': col[:K], 'moments_entropy': col[K], 'moments_mutual_information': col[K + 1]}
     arrays['dropped'] = drop
     out['moments_dropped'] = int(drop.sum())
+    return out, arrays
+
+
+def sensitivity_refusal(model: str):
+    """Why --sensitivities cannot run on this experiment, or None."""
+    if model != 'FCN':
+        return (f'--sensitivities: input sensitivities are for FCN (tabular) experiments; this one is {model}, whose inputs are '
+                'token ids or image pixels')
+    return None
+
+
+def feature_labels(features, F: int):
+    """The data config's column names where it gives exactly one per input, else None."""
+    if isinstance(features, (list, tuple)) and len(features) == F:
+        return [str(f) for f in features]
+    return None
+
+
+def sensitivity_metrics(res, feature_names=None):
+    """--sensitivities: the metrics.json keys and the sensitivities.npz arrays of Engine.predict_sensitivities' result ``res``
+    (or metrics.sensitivities_dense's).  Keys, each [P][F] per head output and feature, in the network's units (normalised inputs
+    and targets): ``sens_ape`` the ensemble's average partial effect, ``sens_importance`` the mean |effect|, ``sens_chain_sd``
+    the disagreement of the chains' average effects, ``sens_decided`` the share of rows whose sign is decided, ``sens_ranking``
+    the features by falling importance (``sens_ranked_names`` with names), ``sens_dropped`` the (draw, row) pairs left out.
+    Arrays: the seven outputs, and ``feature_names`` or ``feature_index``."""
+    from mile_amd import metrics as M
+    summ = M.sensitivity_summary(res, feature_names)
+    out = {'sens_ape': summ['ape'], 'sens_importance': summ['importance'], 'sens_chain_sd': summ['chain_sd'],
+           'sens_decided': summ['decided'], 'sens_ranking': summ['ranking'], 'sens_dropped': int(res['dropped'].sum())}
+    if feature_names is not None:
+        out['sens_ranked_names'] = summ['ranked_names']
+    arrays = {k: res[k].detach().cpu().numpy() for k in M.SENS_OUTPUTS}
+    F = arrays['mean'].shape[2]
+    if feature_names is not None:
+        arrays['feature_names'] = np.asarray(feature_names)
+    else:
+        arrays['feature_index'] = np.arange(F, dtype=np.int64)
     return out, arrays
 
 
@@ -558,6 +595,11 @@ def build_parser():
                          'draws enter the pair sums (default 131072; k is recorded as crps_thin_stride)')
     ap.add_argument('--loo-r-eff', '--r-eff', type=float, default=1.0, metavar='R_EFF',
                     help='relative efficiency of the draws behind the PSIS tail length of --loo and --stacking (default 1: independent draws)')
+    ap.add_argument('--sensitivities', action='store_true',
+                    help='FCN experiments: input sensitivities of the ensemble on the split, reduced on the device '
+                         '(mile_predict_sensitivities): per head output and feature the average partial effect, the importance, the '
+                         'chains\' disagreement and the share of rows with a decided sign as sens_* keys in metrics.json, and the '
+                         'per-row and per-chain arrays in sensitivities.npz.  In the network\'s units: normalised inputs and targets')
     ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
     ap.add_argument('--split', default='test', choices=['train', 'valid', 'test'])
     ap.add_argument('--device', default='cuda:0')
@@ -596,6 +638,8 @@ def main():
         raise SystemExit(why)
     if args.aligned_diagnostics is not None and args.align_rounds < 1:
         raise SystemExit('--align-rounds: at least 1')
+    if args.sensitivities and sensitivity_refusal(cfg.model.model):
+        raise SystemExit(sensitivity_refusal(cfg.model.model))
     align_reference = args.align_reference
     if args.aligned_diagnostics is not None and align_reference != 'first':
         if not Path(align_reference).is_file():
@@ -731,6 +775,11 @@ def main():
         keys, arrays = moment_metrics(mom, dropped, np.ascontiguousarray(y), cfg.data.task)
         out.update(keys)
         np.savez(exp / 'moments.npz', **arrays)
+    if args.sensitivities:
+        res = eng.predict_sensitivities(torch.from_numpy(samples), torch.from_numpy(x))
+        keys, arrays = sensitivity_metrics(res, feature_labels(getattr(cfg.data, 'features', None), x.shape[1]))
+        out.update(keys)
+        np.savez(exp / 'sensitivities.npz', **arrays)
     if args.running is not None:
         from mile_amd.metrics import curve_points, streamed_lppd
         res = streamed_lppd(eng, torch.from_numpy(samples), torch.from_numpy(x), torch.from_numpy(np.ascontiguousarray(y)),

@@ -927,6 +927,42 @@ int32_t mile_multichain_ess(const float *series, int32_t C, int32_t S, int64_t m
                             float *ess, void *workspace, int64_t workspace_bytes, void *stream);
 int64_t mile_multichain_ess_workspace(int32_t C, int32_t S, int64_t m, int32_t plane_input);
 
+/* Input sensitivities of the ensemble's predictions: which inputs drive the prediction, in which direction, and whether the
+ * posterior is sure of it.  MILE_MODEL_FCN only.  With a_0 = x, z_l = a_l W_l + b_l, a_{l+1} = phi(z_l) for l < L - 1 and the raw
+ * outputs r = z_{L-1}, the Jacobian of draw s on row n is
+ *   Jraw[o][f] = d r_o / d x_f = [W_0 diag phi'(z_0) W_1 ... diag phi'(z_{L-2}) W_{L-1}]_{f,o},
+ * phi' as the gradient kernels take it (relu' = 1 iff z > 0), formed in fp32 by one forward and P backward sweeps (k_sens_jac,
+ * mile_sens.h).  The reported columns J[p][f], P = the width of the last layer:
+ *   regression, P = 2:   J = Jraw: the sensitivities of mu and of log sigma, unclipped, as mile_predict returns them
+ *   K classes, P = K:    J[k][f] = pi_k (Jraw[k][f] - sum_j pi_j Jraw[j][f]), the sensitivities of the class probabilities
+ *                        pi = softmax(r) (maximum subtracted first, as in the likelihood head); logit Jacobians are not reported
+ * theta [C * S, d] full layout, draw j of chain c at row c * S + j; X [N, F] any device table, as for mile_predict.
+ * A (draw, row) pair is kept iff its raw outputs and all P * F entries of J are finite; otherwise it is left out of that row (per
+ * draw and per row, the rule of mile_predict_moments).  A NaN pre-activation stays NaN in this forward for every activation
+ * (the ReLU of the evaluation kernels answers 0 for it), so a NaN weight or an inf - inf inside the net drops the pair by its raw
+ * outputs.  Outputs (device, any may be null, not all):
+ *   mean, sd, pos [N, P, F] fp32   over the k kept draws of all chains on the row: the mean of J, sd = sqrt(M2 / (k - 1)) (0 for
+ *                                  k = 1: the epistemic spread of the effect) and the share of kept draws with J > 0; a row with
+ *                                  nothing kept holds NaN
+ *   dropped [N] int32              C * S - k
+ *   chain_ape, chain_abs [C, P, F] fp64   over chain c's kept (draw, row) pairs: the mean of J (the average partial effect) and of
+ *                                  |J| (the importance); NaN for a chain with nothing kept
+ *   chain_kept [C] int64           those pairs
+ * Rows go in tiles of at most max_rows_per_tile (0: the library's choice), the draws of a tile in passes of at most
+ * max_draws_per_pass (0: as many as fit 256 MiB of Jacobians) -- never [C * S, N, P, F] at once.  Accumulators are fp64: Welford
+ * per pass with Chan's merge across passes on the draw axis, two-stage sums in a fixed order over rows; no atomics: the outputs
+ * are bitwise reproducible for one (C, S, N, max_draws_per_pass, max_rows_per_tile) and agree across them to fp64 rounding.
+ * The workspace is the handle's shared evaluation workspace (see mile_predict_moments), grown in the call;
+ * mile_predict_sensitivities_workspace gives its bytes with the library's tile and pass, -1 where the call would be refused.
+ * MILE_ERR_INVALID, with nothing launched and the handle usable: a null handle / theta / X; C outside [1, 1024], S < 1,
+ * C * S > 2^31 - 1, N outside [1, 2^30 - 1]; negative caps; no output; an output that overlaps theta or X; a model other than
+ * MILE_MODEL_FCN (token ids and image pixels are out of scope); a network one row of which does not fit 160 KiB of LDS.
+ * MILE_ERR_NOMEM: the workspace.  (Added under ABI 10: two new symbols, no struct or existing entry changed.) */
+int32_t mile_predict_sensitivities(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, int64_t N,
+                                   int64_t max_draws_per_pass, int64_t max_rows_per_tile, float *mean, float *sd, float *pos,
+                                   int32_t *dropped, double *chain_ape, double *chain_abs, int64_t *chain_kept, void *stream);
+int64_t mile_predict_sensitivities_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N);
+
 /* Partition sampling (sampler.partition_sampling of the reference: src/training/partition_sampling.py:304-315 partition_params,
  * src/training/trainer.py:593-659): only the FIRST and the LAST layer of an FCN are sampled; every other layer keeps, per chain,
  * the values of `frozen`.  Target: log_prior(sampled coordinates only) + log_likelihood(full net on sampled U frozen).

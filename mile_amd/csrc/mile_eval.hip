@@ -23,6 +23,7 @@
 #include "mile_diag.h"
 #include "mile_fdiag.h"
 #include "mile_dtail.h"
+#include "mile_sens.h"
 
 // D consecutive draws in passes of `chunk`, each pass at its draw offset of out [D][per sample]: every (draw, row) forward once
 static int forward_draws(mile_sampler *s, const float *theta, int64_t D, int64_t chunk, float *out, hipStream_t st) {
@@ -1249,4 +1250,128 @@ extern "C" int32_t mile_multichain_ess(const float *series, int32_t C, int32_t S
     HIP_TRY(mile_launch_dtail_ess(t, st));
   }
   return MILE_OK;
+}
+
+// mile_predict_sensitivities: every check before any launch; rows in tiles and draws in passes whose block [Sc][Nt][P][F] of
+// Jacobians fits the evaluation budget; k_sens_jac + k_sens_accum + k_sens_chain per pass, k_sens_finish per tile, k_sens_chain_finish
+// after the last (mile_sens.h).
+struct SensOut {
+  float *mean, *sd, *pos;       // [N, P, F]
+  int32_t *dropped;             // [N]
+  double *chain_ape, *chain_abs;   // [C, P, F]
+  int64_t *chain_kept;          // [C]
+  bool any() const { return rows() || chains(); }
+  bool rows() const { return mean || sd || pos || dropped; }
+  bool chains() const { return chain_ape || chain_abs || chain_kept; }
+};
+static const char *sens_bad_shape(int32_t C, int64_t S, int64_t N) {
+  if (C < 1 || C > 1024) return "C out of range (1 .. 1024)";
+  if (S < 1 || S > 0x7fffffff / C) return "C * S out of range (1 .. 2^31 - 1)";
+  return bad_N(N);
+}
+// what keeps the handle's model from k_sens_jac, or null; net: the FCN as the kernel takes it
+static const char *sens_bad_model(const mile_sampler *s, SensNet *net) {
+  const mile_model_spec *spec = eval_spec(s);
+  if (spec->model != MILE_MODEL_FCN) return "needs an FCN (token ids and image pixels have no input sensitivities here)";
+  if (spec->task == MILE_TASK_REGRESSION && spec->widths[spec->n_layers - 1] != 2) return "regression needs (mu, log sigma) outputs";
+  int32_t b_off[MILE_MAX_LAYERS], w_off[MILE_MAX_LAYERS];
+  const long long d = fcn_param_layout(spec, {b_off, w_off});
+  *net = sens_net(spec, b_off, w_off, (int)d);
+  return sens_R(*net) < 1 ? "network too wide: one row's activations and sweeps do not fit 160 KiB of LDS" : nullptr;
+}
+
+// The plan of one call: rows per tile, draws per pass (of the C * S = D draws, chains one after the other), the slices of
+// k_sens_accum and the byte offset of every block of its workspace.  Per (draw, row) P * F floats of jac; per row also the
+// accumulators of at most SENS_MAX_SLICES slices.
+struct SensTilePlan { int64_t Nt, chunk; int slices; size_t acc, chain, total; };
+static SensTilePlan sens_tile_plan(const SensNet &net, int n_cu, int32_t C, int64_t D, int64_t N, int64_t max_rows, int64_t max_draws) {
+  SensTilePlan t;
+  const int64_t PF = (int64_t)net.widths[net.n_layers - 1] * net.in_features;
+  t.Nt = tile_rows(EVAL_PASS_TARGET, PF * 4 + SENS_MAX_SLICES * PF * 24, 1, max_rows, N);
+  t.chunk = pass_draws(EVAL_PASS_TARGET, t.Nt * PF * 4, max_draws, D);
+  // enough workgroups for about eight waves per CU, at most one slice per draw of a pass
+  const int64_t cols = t.Nt * PF;
+  t.slices = (int)std::min<int64_t>(std::min<int64_t>(SENS_MAX_SLICES, t.chunk), std::max<int64_t>(1, ((int64_t)n_cu * 8 * 64 + cols - 1) / cols));
+  t.acc = r256((size_t)t.chunk * t.Nt * PF * 4);
+  t.chain = t.acc + r256(sens_acc_bytes(t.Nt, (int)PF, t.slices));
+  t.total = t.chain + r256(sens_chain_bytes(C, (int)PF));
+  return t;
+}
+
+// the tiles of one call, the passes inside each
+static int sens_run(char *ws, const SensTilePlan &t, const SensNet &net, int n_cu, const float *theta, int32_t C, int64_t S, const float *X,
+                    int64_t N, const SensOut &o, hipStream_t st) {
+  const int F = net.in_features, PF = net.widths[net.n_layers - 1] * F, R = sens_R(net);
+  const int64_t D = (int64_t)C * S;
+  SensJacParams jp{};
+  jp.net = net; jp.jac = (float *)ws; jp.R = R;
+  SensAccParams ap{};
+  ap.jac = (const float *)ws; ap.PF = PF; ap.slices = t.slices; ap.D = D;
+  SensChainParams cp{};
+  cp.jac = (const float *)ws; cp.PF = PF; cp.C = C; cp.S = S;
+  cp.sum = (double *)(ws + t.chain); cp.abs = cp.sum + (size_t)C * PF; cp.kept = (long long *)(cp.abs + (size_t)C * PF);
+  cp.o_ape = o.chain_ape; cp.o_abs = o.chain_abs; cp.o_kept = (long long *)o.chain_kept;
+  if (o.chains()) HIP_TRY(hipMemsetAsync(ws + t.chain, 0, sens_chain_bytes(C, PF), st));
+  for (int64_t r0 = 0; r0 < N; r0 += t.Nt) {
+    const int nt = (int)std::min<int64_t>(t.Nt, N - r0);
+    const size_t cols = (size_t)nt * PF;
+    jp.Nt = ap.Nt = cp.Nt = nt;
+    jp.X = X + (size_t)r0 * F;
+    ap.mean = (double *)(ws + t.acc); ap.M2 = ap.mean + (size_t)t.slices * cols;
+    ap.pos = (int32_t *)(ap.M2 + (size_t)t.slices * cols); ap.cnt = ap.pos + (size_t)t.slices * cols;
+    ap.o_mean = o.mean ? o.mean + (size_t)r0 * PF : nullptr;
+    ap.o_sd = o.sd ? o.sd + (size_t)r0 * PF : nullptr;
+    ap.o_pos = o.pos ? o.pos + (size_t)r0 * PF : nullptr;
+    ap.dropped = o.dropped ? o.dropped + r0 : nullptr;
+    if (o.rows()) HIP_TRY(hipMemsetAsync(ws + t.acc, 0, sens_acc_bytes(nt, PF, t.slices), st));
+    for (int64_t d0 = 0; d0 < D; d0 += t.chunk) {
+      const int Sc = (int)std::min<int64_t>(t.chunk, D - d0);
+      jp.theta = theta + (size_t)d0 * net.d;
+      jp.SB = (int)std::max<int64_t>(1, std::min<int64_t>((2 * (int64_t)n_cu + Sc - 1) / Sc, (nt + R - 1) / R));
+      HIP_TRY(mile_launch_sens_jac(jp, Sc, st));
+      ap.Sc = cp.Sc = Sc; cp.d0 = d0;
+      if (o.rows()) HIP_TRY(mile_launch_sens_accum(ap, st));
+      if (o.chains()) HIP_TRY(mile_launch_sens_chain(cp, st));
+    }
+    if (o.rows()) HIP_TRY(mile_launch_sens_finish(ap, st));
+  }
+  if (o.chains()) HIP_TRY(mile_launch_sens_chain_finish(cp, st));
+  return MILE_OK;
+}
+
+extern "C" int64_t mile_predict_sensitivities_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N) {
+  SensNet net;
+  if (!s || sens_bad_shape(C, S, N) || sens_bad_model(s, &net)) return -1;
+  return (int64_t)sens_tile_plan(net, eval_view(s).n_cu, C, (int64_t)C * S, N, 0, 0).total;
+}
+
+extern "C" int32_t mile_predict_sensitivities(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, int64_t N,
+                                              int64_t max_draws_per_pass, int64_t max_rows_per_tile, float *mean, float *sd, float *pos,
+                                              int32_t *dropped, double *chain_ape, double *chain_abs, int64_t *chain_kept, void *stream) {
+  const char *fn = "mile_predict_sensitivities";
+  const SensOut o{mean, sd, pos, dropped, chain_ape, chain_abs, chain_kept};
+  SensNet net;
+  const int rc0 = eval_args(fn, s, !theta || !X, sens_bad_shape(C, S, N), [&]() -> const char * {
+    if (!o.any()) return "no output asked for";
+    if (const char *m = bad_caps(max_draws_per_pass, max_rows_per_tile)) return m;
+    if (const char *m = sens_bad_model(s, &net)) return m;
+    // no output may lie over theta [C * S, d] or X [N, F]: both are read until the last tile's last pass
+    const size_t PF = (size_t)net.widths[net.n_layers - 1] * net.in_features;
+    const uintptr_t in[2][2] = {{(uintptr_t)theta, (size_t)C * S * net.d * 4}, {(uintptr_t)X, (size_t)N * net.in_features * 4}};
+    const uintptr_t out[7][2] = {{(uintptr_t)mean, (size_t)N * PF * 4}, {(uintptr_t)sd, (size_t)N * PF * 4}, {(uintptr_t)pos, (size_t)N * PF * 4},
+                                 {(uintptr_t)dropped, (size_t)N * 4}, {(uintptr_t)chain_ape, (size_t)C * PF * 8},
+                                 {(uintptr_t)chain_abs, (size_t)C * PF * 8}, {(uintptr_t)chain_kept, (size_t)C * 8}};
+    for (const auto &b : out)
+      for (const auto &a : in)
+        if (b[0] && a[0] < b[0] + b[1] && b[0] < a[0] + a[1]) return "an output overlaps theta or X";
+    return nullptr;
+  });
+  if (rc0 != MILE_OK) return rc0;
+  hipStream_t st = (hipStream_t)stream;
+  const EvalView v = eval_view(s);
+  const SensTilePlan t = sens_tile_plan(net, v.n_cu, C, (int64_t)C * S, N, max_rows_per_tile, max_draws_per_pass);
+  char *ws;
+  const int rc1 = stream_ws(fn, s, t.total, "lower max_draws_per_pass or max_rows_per_tile", ws);
+  if (rc1 != MILE_OK) return rc1;
+  return sens_run(ws, t, net, v.n_cu, theta, C, S, (const float *)X, N, o, st);
 }

@@ -29,6 +29,8 @@ MILE_LOCAL long long fcn_param_layout(const mile_model_spec *spec, FcnOffsets ds
 // what the statistics read of a handle: its device and compute units, the task, the row width F, the head width O, d
 struct EvalView { int device, n_cu, task, in_features, O, d; };
 MILE_LOCAL EvalView eval_view(const mile_sampler *s);
+// the handle's model, for the statistic that runs its own kernel on the FCN's layers (mile_predict_sensitivities)
+MILE_LOCAL const mile_model_spec *eval_spec(const mile_sampler *s);
 
 // every call that evaluates the likelihood refuses a pretrained-attention sampler whose tables are not set
 MILE_LOCAL bool tables_missing(const mile_sampler *s);

@@ -2060,6 +2060,7 @@ static const GradKernel &grad_kernel(int kernel) { return kGrad[kernel - 1]; }
 EvalView eval_view(const mile_sampler *s) {
   return {s->device, s->n_cu, s->spec.task, s->spec.in_features, s->spec.widths[s->spec.n_layers - 1], s->ds.d};
 }
+const mile_model_spec *eval_spec(const mile_sampler *s) { return &s->spec; }
 
 // stage the evaluation rows (and labels) in the handle and describe them in s->ev_set; theta and out are eval_forward's to fill in
 int stage_rows(mile_sampler *s, const float *X, const void *y, int64_t N, hipStream_t st) {

@@ -747,6 +747,39 @@ class Engine:
                for c in range(theta.shape[0])]
         return torch.stack([m for m, _ in res]), torch.stack([int(theta.shape[1]) - d for _, d in res])
 
+    def predict_sensitivities_workspace(self, C: int, S: int, N: int) -> int:
+        """Bytes of the handle's workspace ``predict_sensitivities`` needs for C chains of S draws on N rows with the library's
+        tile and pass, -1 where the call would be refused (mile_predict_sensitivities_workspace)."""
+        return int(self.lib.mile_predict_sensitivities_workspace(self._h, int(C), int(S), int(N)))
+
+    def predict_sensitivities(self, samples, X, *, max_draws_per_pass: int = 0, max_rows_per_tile: int = 0) -> dict:
+        """Input sensitivities of the ensemble's predictions, reduced on the device (mile_predict_sensitivities; FCN only):
+        per draw and row the Jacobian J[p][f] of the head outputs -- mu and log sigma for regression, the class probabilities
+        for classification -- with respect to the row's inputs, by one forward and P backward sweeps in a HIP kernel.
+        ``samples`` [C, S, d] or [S, d] (one chain), ``X`` [N, F].  Returns tensors on the device: ``mean``, ``sd``, ``pos``
+        fp32 [N, P, F] over the kept draws of all chains (sd with ddof 1, the epistemic spread of the effect; pos the share of
+        draws with J > 0), ``dropped`` int32 [N], and per chain over its kept (draw, row) pairs ``chain_ape`` (the average partial
+        effect), ``chain_abs`` (the importance) fp64 [C, P, F] and ``chain_kept`` int64 [C].  A (draw, row) pair with a non-finite
+        raw output or Jacobian entry is left out of that row.  Rows go in tiles of at most ``max_rows_per_tile``, draws in passes
+        of at most ``max_draws_per_pass`` (0: the library's choice); ``metrics.sensitivities_dense`` is the same in torch."""
+        samples = _f32(samples, self.device, name='samples')
+        if samples.ndim == 2:
+            samples = samples[None]
+        if samples.ndim != 3 or samples.shape[2] != self.d:
+            raise ValueError(f'samples must be [C, S, {self.d}] or [S, {self.d}]')
+        (C_, S_), theta, X, _ = self._eval_inputs(samples, X)
+        N, F, P = int(X.shape[0]), int(X.shape[1]), int(self.spec.hidden_structure[-1])
+        new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=self.device)
+        out = {'mean': new(torch.float32, N, P, F), 'sd': new(torch.float32, N, P, F), 'pos': new(torch.float32, N, P, F),
+               'dropped': new(torch.int32, N), 'chain_ape': new(torch.float64, C_, P, F), 'chain_abs': new(torch.float64, C_, P, F),
+               'chain_kept': new(torch.int64, C_)}
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_predict_sensitivities(self._h, _ptr(theta), C_, S_, _ptr(X), N, int(max_draws_per_pass),
+                                                           int(max_rows_per_tile), *[_ptr(out[k]) for k in
+                                                                                     ('mean', 'sd', 'pos', 'dropped', 'chain_ape', 'chain_abs', 'chain_kept')],
+                                                           self._stream()), self.lib)
+        return out
+
     def debug_quantile_sweeps(self):
         """(rows, total sweeps, most sweeps of a row) of the solver in the last ``predict_quantiles`` (test and tool hook)."""
         rows, total, most = C.c_int64(), C.c_int64(), C.c_int32()

@@ -1997,3 +1997,121 @@ def crps_summary(rows: dict, weights=None) -> dict:
             cnt = fin.sum(axis=0)
             res['energy_distance'] = (np.where(fin, D2, 0.0).sum(axis=0) / np.where(cnt > 0, cnt, 1)).tolist()
     return res
+
+
+# ---- input sensitivities of the ensemble's predictions: the torch restatement of mile_predict_sensitivities
+# (Engine.predict_sensitivities) in fp64 from the closed-form chain of matrices.  The tests' yardstick, and the fallback where
+# the library refuses.
+
+SENS_OUTPUTS = ('mean', 'sd', 'pos', 'dropped', 'chain_ape', 'chain_abs', 'chain_kept')
+
+
+def sensitivity_jacobians(spec: ModelSpec, theta: torch.Tensor, X: torch.Tensor):
+    """theta [M, d] draws and X [N, F] -> (raw outputs [M, N, O], J [M, N, P, F]) in theta's dtype.  Jraw[o][f] = d r_o / d x_f =
+    [W_0 diag phi'(z_0) W_1 ... diag phi'(z_{L-2}) W_{L-1}]_{f,o}, phi' expressed through the activation's output (relu' = 1 iff
+    z > 0); regression reports J = Jraw, classification J[k][f] = pi_k (Jraw[k][f] - sum_j pi_j Jraw[j][f]), pi = softmax(r)."""
+    leaves = {n: (o, s) for n, o, s in spec.leaves()}
+    nl = len(spec.hidden_structure)
+    act = {'relu': torch.relu, 'tanh': torch.tanh, 'sigmoid': torch.sigmoid}[spec.activation]
+    dact = {'relu': lambda h: (h > 0).to(h.dtype), 'tanh': lambda h: 1.0 - h * h, 'sigmoid': lambda h: h * (1.0 - h)}[spec.activation]
+    X = X.to(theta.device, theta.dtype)
+    Ws, hs = [], []
+    h = X[None].expand(theta.shape[0], -1, -1)
+    for li in range(nl):
+        ko, ks = leaves[f'{spec.root}.layer{li}.kernel']
+        bo, bs = leaves[f'{spec.root}.layer{li}.bias']
+        W = theta[:, ko:ko + ks[0] * ks[1]].reshape(-1, *ks)
+        h = torch.baddbmm(theta[:, bo:bo + bs[0]][:, None, :], h, W)
+        if li < nl - 1:
+            h = act(h)
+            hs.append(h)
+        Ws.append(W)
+    raw = h
+    g = Ws[-1].transpose(1, 2)[:, None].expand(-1, X.shape[0], -1, -1)          # [M, N, P, width]: d r_p / d a_{L-1}
+    for li in range(nl - 2, -1, -1):
+        g = torch.matmul(g * dact(hs[li])[:, :, None, :], Ws[li].transpose(1, 2)[:, None])
+    if spec.task not in ('regr', 'regression'):
+        pi = torch.softmax(raw, dim=-1)
+        g = pi[..., None] * (g - (pi[..., None] * g).sum(dim=2, keepdim=True))
+    return raw, g
+
+
+def sensitivities_dense(spec: ModelSpec, samples: torch.Tensor, X: torch.Tensor, batch: int = 64) -> dict:
+    """Input sensitivities of ``samples`` [C, S, d] (or [S, d]: one chain) on X [N, F] in torch fp64 on the samples' device, ``batch``
+    draws at a time: the dict of ``Engine.predict_sensitivities``.  Per row and column (p, f) over the kept draws of all chains:
+    ``mean``, ``sd`` (ddof 1; 0 for one kept draw) and ``pos``, the share with J > 0, fp32 [N, P, F]; ``dropped`` int32 [N]; per
+    chain over its kept (draw, row) pairs ``chain_ape`` (mean J), ``chain_abs`` (mean |J|) fp64 [C, P, F] and ``chain_kept`` int64
+    [C].  A (draw, row) pair is kept iff its raw outputs and all its P * F entries are finite; a row or a chain with nothing kept
+    holds NaN."""
+    if not isinstance(spec, ModelSpec):
+        raise ValueError('input sensitivities need an FCN (token ids and image pixels are out of scope)')
+    samples = torch.as_tensor(samples)
+    if samples.ndim == 2:
+        samples = samples[None]
+    C, S, d = samples.shape
+    th = samples.reshape(C * S, d).to(torch.float64)
+    X = torch.as_tensor(X).to(th.device, torch.float64)
+    N, F, P = X.shape[0], X.shape[1], int(spec.hidden_structure[-1])
+    z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=th.device)
+    k, mean, M2, pos = z(N), z(N, P, F), z(N, P, F), z(N, P, F)
+    csum, cabs, ckept = z(C, P, F), z(C, P, F), torch.zeros(C, dtype=torch.int64, device=th.device)
+    for c in range(C):
+        for b0 in range(c * S, (c + 1) * S, batch):
+            raw, J = sensitivity_jacobians(spec, th[b0:min(b0 + batch, (c + 1) * S)], X)
+            ok = torch.isfinite(raw).all(dim=-1) & torch.isfinite(J).all(dim=-1).all(dim=-1)          # [b, N]
+            w = ok.to(torch.float64)[..., None, None]
+            J = torch.where(ok[..., None, None], J, torch.zeros_like(J))
+            kb = ok.sum(dim=0).to(torch.float64)
+            mb = (J * w).sum(dim=0) / kb.clamp(min=1)[:, None, None]
+            db = (J - mb) * w
+            M2b = (db * db).sum(dim=0)
+            kt = k + kb
+            delta = mb - mean
+            mean = mean + delta * (kb / kt.clamp(min=1))[:, None, None]                      # Chan's merge of the batch
+            M2 = M2 + M2b + delta * delta * (k * kb / kt.clamp(min=1))[:, None, None]
+            k = kt
+            pos = pos + ((J > 0).to(torch.float64) * w).sum(dim=0)
+            csum[c] += (J * w).sum(dim=(0, 1))
+            cabs[c] += (J.abs() * w).sum(dim=(0, 1))
+            ckept[c] += ok.sum()
+    nan = torch.full_like(mean, float('nan'))
+    kk = k[:, None, None]
+    some = (kk > 0).expand_as(mean)
+    sd = torch.where(kk > 1, torch.sqrt(M2 / (kk - 1).clamp(min=1)), torch.zeros_like(M2))
+    ck = ckept.to(torch.float64)[:, None, None]
+    cnan = torch.full_like(csum, float('nan'))
+    return {'mean': torch.where(some, mean, nan).to(torch.float32), 'sd': torch.where(some, sd, nan).to(torch.float32),
+            'pos': torch.where(some, pos / kk.clamp(min=1), nan).to(torch.float32), 'dropped': (C * S - k).to(torch.int32),
+            'chain_ape': torch.where(ck > 0, csum / ck.clamp(min=1), cnan), 'chain_abs': torch.where(ck > 0, cabs / ck.clamp(min=1), cnan),
+            'chain_kept': ckept}
+
+
+def sensitivity_summary(result: dict, feature_names=None) -> dict:
+    """What the sensitivities say per head output p, on the host in fp64, from the dict of ``Engine.predict_sensitivities`` /
+    ``sensitivities_dense``: ``ape`` [P][F], the ensemble's average partial effect (the mean of ``chain_ape`` over the chains);
+    ``importance`` [P][F], the mean of ``chain_abs``; ``chain_sd`` [P][F], the sd (ddof 1, 0 for one chain) of ``chain_ape``
+    across the chains -- whether the chains agree on what matters; ``decided`` [P][F], the share of rows whose sign is decided
+    (``pos`` >= 0.95 or <= 0.05; rows with nothing kept do not count); ``ranking`` [P][F], the features by falling importance,
+    as indices, and ``ranked_names`` where ``feature_names`` is given.  Chains with nothing kept are left out of the chain
+    statistics."""
+    import numpy as np
+    a = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in result.items()}
+    ape, imp = a['chain_ape'].astype(np.float64), a['chain_abs'].astype(np.float64)
+    use = np.isfinite(ape).all(axis=(1, 2)) & np.isfinite(imp).all(axis=(1, 2))
+    ape, imp = ape[use], imp[use]
+    P, F = ape.shape[1], ape.shape[2]
+    if feature_names is not None and len(feature_names) != F:
+        raise ValueError(f'feature_names: {F} names expected')
+    pos = a['pos'].astype(np.float32)                                   # compared in its own format: 19 / 20 in fp32 is 0.95 in fp32
+    rows = np.isfinite(pos).all(axis=(1, 2))
+    decided = ((pos[rows] >= np.float32(0.95)) | (pos[rows] <= np.float32(0.05))).mean(axis=0) if rows.any() else np.full((P, F), np.nan)
+    nan = np.full((P, F), np.nan)
+    importance = imp.mean(axis=0) if len(imp) else nan
+    ranking = np.argsort(-np.nan_to_num(importance, nan=-np.inf), axis=1, kind='stable')
+    res = {'ape': (ape.mean(axis=0) if len(ape) else nan).tolist(), 'importance': importance.tolist(),
+           'chain_sd': (ape.std(axis=0, ddof=1) if len(ape) > 1 else np.zeros((P, F)) if len(ape) else nan).tolist(),
+           'decided': decided.tolist(), 'ranking': ranking.tolist(), 'n_chains': int(use.sum()), 'n_rows': int(rows.sum())}
+    if feature_names is not None:
+        res['feature_names'] = [str(n) for n in feature_names]
+        res['ranked_names'] = [[str(feature_names[i]) for i in r] for r in ranking]
+    return res

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Posterior-predictive moments of a finished experiment on NEW inputs (the consumer of mile_predict_moments):
 
-    python predict.py -e results/mile_amd/<experiment> -i <table or .npz> [-o predictions.npz] [--draws-per-pass K] [--intervals C [C ...]] [--sets C [C ...]] [--weights PATH|stacking]
+    python predict.py -e results/mile_amd/<experiment> -i <table or .npz> [-o predictions.npz] [--draws-per-pass K] [--intervals C [C ...]] [--sets C [C ...]] [--weights PATH|stacking] [--sensitivities]
 
 Reloads config.yaml and the samples the way evaluate.py does, applies the training normalisation the loader recorded
 (normalization.npz, written by train.py) to the rows of the table, reduces all C x S draws on the device and writes, per row:
@@ -19,6 +19,11 @@ Reloads config.yaml and the samples the way evaluate.py does, applies the traini
                      ``chain_weights`` [C] is added.  PATH: an .npz with ``weights``, a .npy or a text vector; ``stacking``:
                      <experiment>/stacking.npz, as evaluate.py --stacking wrote it.  One weight per chain LOADED: a vector of
                      another length is refused (evaluate and predict with the same --drop-nonfinite)
+    --sensitivities  FCN experiments: sens_mean, sens_sd, sens_pos [N, P, F] and sens_dropped [N], the input sensitivities of the
+                     equal-weight ensemble on every row (mile_predict_sensitivities): over the draws the mean and the sd of
+                     d output_p / d x_f and the share of draws where it is positive; p = (mu, log sigma) for regression, the
+                     class probabilities for classification.  In the table's units: d mu / d x_f is multiplied by y_std / x_std_f,
+                     d log sigma / d x_f and d pi_k / d x_f are divided by x_std_f (--normalized keeps the network's units)
 
 The table holds one row per input and the model's features as columns (no target column): .npy, .csv (comma), .data / .txt
 (whitespace), or an .npz with an array ``x`` (images [N, C, H, W], token ids [N, T]).  Where the target was z-scored
@@ -113,6 +118,21 @@ def denormalize(arrays: dict, norm: dict) -> dict:
     return out
 
 
+def sensitivity_arrays(res: dict, norm: dict, task: str) -> dict:
+    """sens_mean, sens_sd, sens_pos [N, P, F] and sens_dropped [N] of Engine.predict_sensitivities, in the units of the table where
+    the loader normalised: the network sees x' = (x - x_mean) / x_std and, for a z-scored target, predicts mu' = (mu - y_mean) /
+    y_std, so d mu / d x_f = (y_std / x_std_f) d mu' / d x'_f, while log sigma = log sigma' + log y_std and the class probabilities
+    change with x only: both are divided by x_std_f.  The factors are positive: the sd scales with them and pos stays."""
+    mean, sd = res['mean'].double().cpu().numpy(), res['sd'].double().cpu().numpy()
+    if 'x_std' in norm:
+        scale = np.ones(mean.shape[1:], dtype=np.float64) / np.asarray(norm['x_std'], dtype=np.float64).reshape(1, -1)
+        if task == 'regr' and 'y_std' in norm:
+            scale[0] *= float(norm['y_std'].reshape(-1)[0])
+        mean, sd = mean * scale, sd * scale
+    return {'sens_mean': mean.astype(np.float32), 'sens_sd': sd.astype(np.float32), 'sens_pos': res['pos'].cpu().numpy(),
+            'sens_dropped': res['dropped'].cpu().numpy()}
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description='posterior-predictive moments of an experiment on a table of new inputs')
     ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
@@ -130,6 +150,9 @@ def build_parser():
     ap.add_argument('--weights', default=None, metavar='PATH',
                     help='chain weights (stacking): every output is the weighted mixture\'s.  An .npz with an array weights, a .npy '
                          'or a text vector with one weight per loaded chain; "stacking": <experiment>/stacking.npz')
+    ap.add_argument('--sensitivities', action='store_true',
+                    help='FCN experiments: also the input sensitivities of the ensemble on every row (mile_predict_sensitivities): '
+                         'sens_mean, sens_sd, sens_pos [N, P, F] and sens_dropped [N], in the units of the table unless --normalized')
     ap.add_argument('--normalized', action='store_true',
                     help='the rows already are in the training normalisation; the outputs stay in it')
     ap.add_argument('--drop-nonfinite', action='store_true', help='leave out chains with non-finite samples, as evaluate.py does')
@@ -152,6 +175,10 @@ def main():
         raise SystemExit('--sets: prediction sets are for classification experiments; this one is regression (--intervals is its counterpart)')
     tr.build_model(cfg)
     spec = tr.prob_model.spec
+    if args.sensitivities:
+        from mile_amd.spec import ModelSpec
+        if not isinstance(spec, ModelSpec):
+            raise SystemExit('--sensitivities: input sensitivities are for FCN (tabular) experiments; token ids and image pixels are out of scope')
     samples = load_samples_from_dir(exp / cfg.training.sampler._dir_name, spec)       # [C, S, d]
     bad_chains = ~np.isfinite(samples).all(axis=(1, 2))
     if args.drop_nonfinite and bad_chains.any() and not bad_chains.all():
@@ -203,6 +230,9 @@ def main():
         arrays['set_levels'] = np.asarray(levels, dtype=np.float64)
         arrays['class_order'] = res['order'].cpu().numpy()
         arrays['set_size'] = res['set_size'].cpu().numpy()
+    if args.sensitivities:
+        res = eng.predict_sensitivities(torch.from_numpy(samples), torch.from_numpy(x), max_draws_per_pass=args.draws_per_pass)
+        arrays.update(sensitivity_arrays(res, norm, cfg.data.task))
     out = Path(args.output) if args.output else exp / 'predictions.npz'
     np.savez(out, **arrays)
     print(f'{out}: {len(x)} rows, {samples.shape[0] * samples.shape[1]} draws, {int(arrays["dropped"].sum())} dropped; '
