@@ -3,7 +3,7 @@
 mile_predict; mirrors what the reference's report notebook does with src/inference/evaluation.py:409-544 +
 src/inference/metrics.py:247-312):
 
-    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--function-diagnostics [N_SPLITS]] [--canonical-diagnostics [N_SPLITS]] [--aligned-diagnostics [N_SPLITS]] [--tail-diagnostics [N_SPLITS]] [--moments] [--sensitivities] [--running [N_POINTS]] [--intervals] [--loo] [--loo-predict] [--stacking]
+    python evaluate.py -e results/mile_amd/<experiment> [--split test] [--diagnostics [N_SPLITS]] [--function-diagnostics [N_SPLITS]] [--canonical-diagnostics [N_SPLITS]] [--aligned-diagnostics [N_SPLITS]] [--tail-diagnostics [N_SPLITS]] [--moments] [--sensitivities] [--partial-dependence [G]] [--pd-features I ..] [--running [N_POINTS]] [--intervals] [--loo] [--loo-predict] [--stacking]
 
 Reloads config.yaml and the samples/<chain>/sample_<n>.npz files, rebuilds the data split with the same
 seed, evaluates all C x S samples on the split in one device pass and writes metrics.json next to them.
@@ -259,6 +259,36 @@ def sensitivity_refusal(model: str):
         return (f'--sensitivities: input sensitivities are for FCN (tabular) experiments; this one is {model}, whose inputs are '
                 'token ids or image pixels')
     return None
+
+
+def partial_dependence_refusal(model: str):
+    """Why --partial-dependence cannot run on this experiment, or None."""
+    if model != 'FCN':
+        return (f'--partial-dependence: partial dependence is for FCN (tabular) experiments; this one is {model}, whose inputs are '
+                'token ids or image pixels')
+    return None
+
+
+def partial_dependence_metrics(res, grid, features, feature_names=None):
+    """--partial-dependence: the metrics.json keys and the partial_dependence.npz arrays of Engine.predict_partial_dependence's
+    result ``res`` (or metrics.partial_dependence_dense's) on ``grid`` [Fs, G] of the selected ``features``.  Keys, each [Fs][P]
+    per selected feature and head output, in the network's units (metrics.partial_dependence_summary): ``pd_importance`` the sd
+    of the partial dependence over the grid, ``pd_span``, ``pd_slope``, ``pd_band`` the mean width of the posterior band,
+    ``pd_chain_sd`` and ``pd_chain_ratio`` the chains' disagreement on the curve, alone and against the band,
+    ``pd_ice_heterogeneity`` the spread of the centred ICE curves over the rows; ``pd_features``, ``pd_grid_points``,
+    ``pd_dropped`` the (draw, row, feature) triples left out.  Arrays: the grid, the eight outputs, ``feature_index`` and, with
+    names, ``feature_names`` of the selected features."""
+    from mile_amd import metrics as M
+    summ = M.partial_dependence_summary(res, grid)
+    out = {f'pd_{k}': summ[k] for k in ('importance', 'span', 'slope', 'band', 'chain_sd', 'chain_ratio', 'ice_heterogeneity')}
+    out.update(pd_features=[int(f) for f in features], pd_grid_points=int(grid.shape[1]), pd_dropped=int(res['dropped'].sum()))
+    arrays = {k: res[k].detach().cpu().numpy() for k in M.PD_OUTPUTS}
+    arrays['grid'] = grid.detach().cpu().numpy()
+    arrays['feature_index'] = np.asarray([int(f) for f in features], dtype=np.int64)
+    if feature_names is not None:
+        arrays['feature_names'] = np.asarray([feature_names[int(f)] for f in features])
+        out['pd_feature_names'] = [str(feature_names[int(f)]) for f in features]
+    return out, arrays
 
 
 def feature_labels(features, F: int):
@@ -600,6 +630,14 @@ def build_parser():
                          '(mile_predict_sensitivities): per head output and feature the average partial effect, the importance, the '
                          'chains\' disagreement and the share of rows with a decided sign as sens_* keys in metrics.json, and the '
                          'per-row and per-chain arrays in sensitivities.npz.  In the network\'s units: normalised inputs and targets')
+    ap.add_argument('--partial-dependence', type=int, nargs='?', const=20, default=None, metavar='G',
+                    help='FCN experiments: partial dependence and ICE curves of the ensemble on the split, reduced on the device '
+                         '(mile_predict_partial_dependence), every selected feature over G grid values (default 20) at the 5 %% - 95 %% '
+                         'quantiles of its own column: per feature and head output the importance, span, posterior band, chains\' '
+                         'disagreement and ICE heterogeneity as pd_* keys in metrics.json, and the grid and every output in '
+                         'partial_dependence.npz.  In the network\'s units: normalised inputs and targets')
+    ap.add_argument('--pd-features', type=int, nargs='+', default=None, metavar='I',
+                    help='the features of --partial-dependence, as distinct column indices (default: all); refused without that option')
     ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
     ap.add_argument('--split', default='test', choices=['train', 'valid', 'test'])
     ap.add_argument('--device', default='cuda:0')
@@ -640,6 +678,12 @@ def main():
         raise SystemExit('--align-rounds: at least 1')
     if args.sensitivities and sensitivity_refusal(cfg.model.model):
         raise SystemExit(sensitivity_refusal(cfg.model.model))
+    if args.partial_dependence is not None and partial_dependence_refusal(cfg.model.model):
+        raise SystemExit(partial_dependence_refusal(cfg.model.model))
+    if args.pd_features is not None and args.partial_dependence is None:
+        raise SystemExit('--pd-features selects the features of --partial-dependence: give that option too')
+    if args.partial_dependence is not None and not 1 <= args.partial_dependence <= 256:
+        raise SystemExit('--partial-dependence: G must be in 1 .. 256')
     align_reference = args.align_reference
     if args.aligned_diagnostics is not None and align_reference != 'first':
         if not Path(align_reference).is_file():
@@ -780,6 +824,16 @@ def main():
         keys, arrays = sensitivity_metrics(res, feature_labels(getattr(cfg.data, 'features', None), x.shape[1]))
         out.update(keys)
         np.savez(exp / 'sensitivities.npz', **arrays)
+    if args.partial_dependence is not None:
+        from mile_amd.metrics import pd_grid
+        feats = list(range(x.shape[1])) if args.pd_features is None else args.pd_features
+        if len(set(feats)) != len(feats) or min(feats) < 0 or max(feats) >= x.shape[1]:
+            raise SystemExit(f'--pd-features: distinct indices in 0 .. {x.shape[1] - 1} are needed')
+        grid = pd_grid(x, feats, args.partial_dependence)
+        res = eng.predict_partial_dependence(torch.from_numpy(samples), torch.from_numpy(x), feats, grid)
+        keys, arrays = partial_dependence_metrics(res, grid, feats, feature_labels(getattr(cfg.data, 'features', None), x.shape[1]))
+        out.update(keys)
+        np.savez(exp / 'partial_dependence.npz', **arrays)
     if args.running is not None:
         from mile_amd.metrics import curve_points, streamed_lppd
         res = streamed_lppd(eng, torch.from_numpy(samples), torch.from_numpy(x), torch.from_numpy(np.ascontiguousarray(y)),

@@ -963,6 +963,50 @@ int32_t mile_predict_sensitivities(mile_sampler *s, const float *theta, int32_t 
                                    int32_t *dropped, double *chain_ape, double *chain_abs, int64_t *chain_kept, void *stream);
 int64_t mile_predict_sensitivities_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N);
 
+/* Partial dependence (Friedman 2001) and ICE curves (Goldstein et al. 2015) of the ensemble's predictions: how the prediction
+ * moves when one input runs over a grid, whether the posterior is sure of that curve, and whether the chains agree on it.
+ * MILE_MODEL_FCN only.  The head columns are those of mile_predict_sensitivities: regression P = 2, mu and log sigma, unclipped;
+ * K classes P = K, the softmax probabilities (maximum subtracted first).  For draw s, row n, the selected feature f = features[i]
+ * and the grid value v = grid[i][g],
+ *   h[s, n, i, g, p] = head column p of the FCN on row n with x_{n,f} replaced by v,
+ * computed in fp32 as z_0 = x W_0 + b_0 once per (draw, row), z_0' = z_0 + (v - x_{n,f}) W_0[f, :] (one fmaf per first-layer unit)
+ * per grid value, then the activation, the layers 1 .. L - 1 and the head (k_pdp_fwd, mile_pdp.h).  This arithmetic is the
+ * definition; in exact arithmetic it is the substitution.  A NaN pre-activation stays NaN, as for the sensitivities.
+ * A (draw, row, feature) triple is kept iff all G * P values of the feature are finite -- per feature on purpose: columns of
+ * different features are independent, and a call on a subset of the features returns, for those, the bits of the full call.
+ * A row with a non-finite input is dropped for EVERY feature, the feature of that column included: z_0 already holds the inf,
+ * and z_0 + (v - inf) W_0[f, :] is NaN (true substitution would have kept that one feature).
+ * theta [C * S, d] full layout, draw j of chain c at row c * S + j; X [N, F] device; features [Fs] a HOST array of distinct
+ * indices in [0, F); grid [Fs, G] fp32 device, any values, not necessarily sorted.  Outputs (device, any may be null, not all):
+ *   ice_mean, ice_sd [N, Fs, G, P] fp32   over the k kept draws of all chains on (row, feature): the mean of h and
+ *                                  sd = sqrt(M2 / (k - 1)) (0 for k = 1); NaN where nothing is kept
+ *   dropped [N, Fs] int32          C * S - k
+ *   curves [C * S, Fs, G, P] fp32  the draw's partial dependence: the mean of h over its kept rows, rounded from the fp64 sum;
+ *                                  NaN for a (draw, feature) with no kept row
+ *   pd_mean, pd_sd [Fs, G, P] fp64 mean and sd (ddof 1, 0 for one) over the draws that have a curve, from the fp64 row means and
+ *                                  not from the rounded curves: the posterior band; NaN where no draw has one
+ *   chain_pd [C, Fs, G, P] fp64    the mean of chain c's curves; NaN for a chain without one
+ *   chain_draws [C, Fs] int64      chain c's draws that have a curve
+ * Rows go in tiles of at most max_rows_per_tile (0: the library's choice), the draws of a tile in passes of at most
+ * max_draws_per_pass (0: as many as fit 256 MiB) -- never [C * S, N, Fs, G, P] at once; tiles and passes are sized as if all F
+ * features were selected, so a subset runs the plan of the full call.  Accumulators are fp64: Welford per pass with Chan's merge
+ * across passes on the draw axis, two-stage sums in a fixed order over rows, the draws of a chain and then the chains in index
+ * order; no atomics: the outputs are bitwise reproducible for one (C, S, N, Fs, G, max_draws_per_pass, max_rows_per_tile) and
+ * agree across passes and tiles to fp64 rounding.  The workspace is the handle's shared evaluation workspace, grown in the
+ * call; mile_predict_partial_dependence_workspace gives its bytes with the library's tile and pass, -1 where the call would be
+ * refused.  MILE_ERR_INVALID, with nothing launched and the handle usable: a null handle / theta / X / features / grid; C outside
+ * [1, 1024], S < 1, C * S > 2^31 - 1, N outside [1, 2^30 - 1]; Fs outside [1, F], a feature index out of range or repeated; G
+ * outside [1, 256]; negative caps; no output; an output that overlaps theta, X or grid; a model other than MILE_MODEL_FCN; a
+ * network of which one row's first layer and one pseudo-row do not fit 160 KiB of LDS; per-draw sums C * S * Fs * G * P * 8 bytes
+ * above 1 GiB (call it on fewer features: exact by the drop rule).  MILE_ERR_NOMEM: the workspace.
+ * (Added under ABI 10: two new symbols, no struct or existing entry changed.) */
+int32_t mile_predict_partial_dependence(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, int64_t N,
+                                        const int32_t *features, int32_t Fs, const float *grid, int32_t G,
+                                        int64_t max_draws_per_pass, int64_t max_rows_per_tile,
+                                        float *ice_mean, float *ice_sd, int32_t *dropped, float *curves,
+                                        double *pd_mean, double *pd_sd, double *chain_pd, int64_t *chain_draws, void *stream);
+int64_t mile_predict_partial_dependence_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N, int32_t Fs, int32_t G);
+
 /* Partition sampling (sampler.partition_sampling of the reference: src/training/partition_sampling.py:304-315 partition_params,
  * src/training/trainer.py:593-659): only the FIRST and the LAST layer of an FCN are sampled; every other layer keeps, per chain,
  * the values of `frozen`.  Target: log_prior(sampled coordinates only) + log_likelihood(full net on sampled U frozen).

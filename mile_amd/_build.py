@@ -16,9 +16,9 @@ LIB_PATH = PKG_DIR / 'libmile_hip.so'
 # instead of AGPRs (fewer v_accvgpr moves and spills in the register-bound grad kernels; measured +0.5 % w64, +2 % w128b);
 # mile_w64_fq2.hip is built without it (hipcc 7.2 crashes on k_grad_w64<3,2,true> with it).
 VGPR_FORM = ['-mllvm', '-amdgpu-mfma-vgpr-form']
-SOURCES = {'mile_hip.hip': VGPR_FORM, 'mile_eval.hip': [], 'mile_w64_fq2.hip': [], 'mile_narrow_part.hip': VGPR_FORM, 'mile_lenetti.hip': [], 'mile_attn.hip': [], 'mile_attn_pre.hip': [], 'mile_attn_wide.hip': [], 'mile_diag.hip': [], 'mile_fdiag.hip': [], 'mile_dtail.hip': [], 'mile_moments.hip': [], 'mile_lppd.hip': [], 'mile_quantiles.hip': [], 'mile_loo.hip': [], 'mile_lxp.hip': [], 'mile_calib.hip': [], 'mile_stack.hip': [], 'mile_crps.hip': [], 'mile_canon.hip': [], 'mile_align.hip': [], 'mile_sens.hip': []}
+SOURCES = {'mile_hip.hip': VGPR_FORM, 'mile_eval.hip': [], 'mile_w64_fq2.hip': [], 'mile_narrow_part.hip': VGPR_FORM, 'mile_lenetti.hip': [], 'mile_attn.hip': [], 'mile_attn_pre.hip': [], 'mile_attn_wide.hip': [], 'mile_diag.hip': [], 'mile_fdiag.hip': [], 'mile_dtail.hip': [], 'mile_moments.hip': [], 'mile_lppd.hip': [], 'mile_quantiles.hip': [], 'mile_loo.hip': [], 'mile_lxp.hip': [], 'mile_calib.hip': [], 'mile_stack.hip': [], 'mile_crps.hip': [], 'mile_canon.hip': [], 'mile_align.hip': [], 'mile_sens.hip': [], 'mile_pdp.hip': []}
 HEADERS = ['mile_device.h', 'mile_block.h', 'mile_grad_generic.h', 'mile_grad_narrow.h', 'mile_grad_w64.h', 'mile_grad_w64_block.inc', 'mile_bf16_frag.h',
-           'mile_grad_w128b.h', 'mile_grad_gemm.h', 'mile_mm3.h', 'mile_lenet.h', 'mile_lenet_mfma.h', 'mile_lenetti.h', 'mile_attn.h', 'mile_attn_pre.h', 'mile_attn_wide.h', 'mile_predict.h', 'mile_row_head.h', 'mile_update.h', 'mile_diag.h', 'mile_diag_device.h', 'mile_fdiag.h', 'mile_dtail.h', 'mile_moments.h', 'mile_lppd.h', 'mile_quantiles.h', 'mile_loo.h', 'mile_loo_device.h', 'mile_lxp.h', 'mile_calib.h', 'mile_stack.h', 'mile_crps.h', 'mile_canon.h', 'mile_align.h', 'mile_sens.h', 'mile_eval_plan.h', 'mile_eval_handle.h', 'mile_layer_plan.h']
+           'mile_grad_w128b.h', 'mile_grad_gemm.h', 'mile_mm3.h', 'mile_lenet.h', 'mile_lenet_mfma.h', 'mile_lenetti.h', 'mile_attn.h', 'mile_attn_pre.h', 'mile_attn_wide.h', 'mile_predict.h', 'mile_row_head.h', 'mile_update.h', 'mile_diag.h', 'mile_diag_device.h', 'mile_fdiag.h', 'mile_dtail.h', 'mile_moments.h', 'mile_lppd.h', 'mile_quantiles.h', 'mile_loo.h', 'mile_loo_device.h', 'mile_lxp.h', 'mile_calib.h', 'mile_stack.h', 'mile_crps.h', 'mile_canon.h', 'mile_align.h', 'mile_sens.h', 'mile_chan.h', 'mile_pdp.h', 'mile_eval_plan.h', 'mile_eval_handle.h', 'mile_layer_plan.h']
 OBJ_DIR = PKG_DIR / 'csrc' / '_obj'
 
 

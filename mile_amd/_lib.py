@@ -232,6 +232,11 @@ SIGNATURES = {
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p]),
     'mile_predict_sensitivities_workspace': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64]),
+    'mile_predict_partial_dependence': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64,
+                                                    C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]),
+    'mile_predict_partial_dependence_workspace': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     'mile_canonicalize_fcn': (C.c_int32, [C.POINTER(ModelSpecC), C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int64, C.c_void_p]),
     'mile_canonicalize_fcn_workspace': (C.c_int64, [C.POINTER(ModelSpecC), C.c_int64, C.c_uint32]),

@@ -24,6 +24,7 @@
 #include "mile_fdiag.h"
 #include "mile_dtail.h"
 #include "mile_sens.h"
+#include "mile_pdp.h"
 
 // D consecutive draws in passes of `chunk`, each pass at its draw offset of out [D][per sample]: every (draw, row) forward once
 static int forward_draws(mile_sampler *s, const float *theta, int64_t D, int64_t chunk, float *out, hipStream_t st) {
@@ -1374,4 +1375,147 @@ extern "C" int32_t mile_predict_sensitivities(mile_sampler *s, const float *thet
   const int rc1 = stream_ws(fn, s, t.total, "lower max_draws_per_pass or max_rows_per_tile", ws);
   if (rc1 != MILE_OK) return rc1;
   return sens_run(ws, t, net, v.n_cu, theta, C, S, (const float *)X, N, o, st);
+}
+
+// mile_predict_partial_dependence: every check before any launch; rows in tiles and draws in passes whose block
+// [Sc][Nt][Fs][G][P] of head outputs fits the evaluation budget; k_pdp_fwd + k_pdp_accum + k_pdp_rows per pass, k_pdp_row_finish per
+// tile, k_pdp_finish after the last (mile_pdp.h).
+struct PdpOut {
+  float *ice_mean, *ice_sd;     // [N, Fs, G, P]
+  int32_t *dropped;             // [N, Fs]
+  float *curves;                // [C S, Fs, G, P]
+  double *pd_mean, *pd_sd;      // [Fs, G, P]
+  double *chain_pd;             // [C, Fs, G, P]
+  int64_t *chain_draws;         // [C, Fs]
+  bool any() const { return ice() || pd(); }
+  bool ice() const { return ice_mean || ice_sd || dropped; }
+  bool pd() const { return curves || pd_mean || pd_sd || chain_pd || chain_draws; }
+};
+// what keeps the handle's model or the selection's size from k_pdp_fwd, or null; net: the FCN as the kernel takes it
+static const char *pdp_bad_model(const mile_sampler *s, int32_t C, int64_t S, int32_t Fs, int32_t G, PdpNet *net) {
+  const mile_model_spec *spec = eval_spec(s);
+  if (spec->model != MILE_MODEL_FCN) return "needs an FCN (token ids and image pixels have no partial dependence here)";
+  if (spec->task == MILE_TASK_REGRESSION && spec->widths[spec->n_layers - 1] != 2) return "regression needs (mu, log sigma) outputs";
+  if (Fs < 1 || Fs > spec->in_features) return "Fs out of range (1 .. F)";
+  if (G < 1 || G > PDP_G_MAX) return "G out of range (1 .. 256)";
+  int32_t b_off[MILE_MAX_LAYERS], w_off[MILE_MAX_LAYERS];
+  const long long d = fcn_param_layout(spec, {b_off, w_off});
+  *net = pdp_net(spec, b_off, w_off, (int)d);
+  if (pdp_lds(*net, Fs).R < 1) return "network too wide: one row's first layer and one pseudo-row do not fit 160 KiB of LDS";
+  // C * S <= 2^31 - 1, Fs * G * P small enough for the product to stay inside int64
+  if ((int64_t)Fs * G * spec->widths[spec->n_layers - 1] > PDP_CELL_MAX / 8 / ((int64_t)C * S))
+    return "the per-draw sums [C * S, Fs, G, P] fp64 exceed 1 GiB: call it on fewer features (columns of different features are "
+           "independent, so the results are the same bits)";
+  return nullptr;
+}
+
+// The plan of one call.  Rows per tile, draws per pass and the slices of k_pdp_accum are sized as if all F features were
+// selected, so that a call on a subset of the features runs the tiles, passes and slices of the full call and returns its bits;
+// the blocks of the workspace take what the Fs selected ones need.
+struct PdpTilePlan { int64_t Nt, chunk; int slices; size_t feat, acc, sum, kept, chain, total; };
+static PdpTilePlan pdp_tile_plan(const PdpNet &net, int n_cu, int32_t C, int64_t D, int64_t N, int32_t Fs, int32_t G, int64_t max_rows,
+                                 int64_t max_draws) {
+  PdpTilePlan t;
+  const int64_t GP = (int64_t)G * net.widths[net.n_layers - 1], QF = GP * net.in_features, Q = GP * Fs;
+  t.Nt = tile_rows(EVAL_PASS_TARGET, QF * 4 + PDP_MAX_SLICES * QF * 20, 1, max_rows, N);
+  t.chunk = pass_draws(EVAL_PASS_TARGET, t.Nt * QF * 4, max_draws, D);
+  const int64_t cols = t.Nt * QF;
+  t.slices = (int)std::min<int64_t>(std::min<int64_t>(PDP_MAX_SLICES, t.chunk), std::max<int64_t>(1, ((int64_t)n_cu * 8 * 64 + cols - 1) / cols));
+  t.feat = r256((size_t)t.chunk * t.Nt * Q * 4);
+  t.acc = t.feat + r256((size_t)Fs * 4);
+  t.sum = t.acc + r256(pdp_acc_bytes(t.Nt, Q, t.slices));
+  t.kept = t.sum + r256((size_t)D * Q * 8);
+  t.chain = t.kept + r256((size_t)D * Fs * 4);
+  t.total = t.chain + r256(pdp_chain_bytes(C, Q));
+  return t;
+}
+
+// the tiles of one call, the passes inside each
+static int pdp_run(char *ws, const PdpTilePlan &t, const PdpNet &net, int n_cu, const float *theta, int32_t C, int64_t S, const float *X,
+                   int64_t N, const int32_t *features, int32_t Fs, const float *grid, int32_t G, const PdpOut &o, hipStream_t st) {
+  const int F = net.in_features, GP = G * net.widths[net.n_layers - 1], Q = Fs * GP;
+  const PdpLds lds = pdp_lds(net, Fs);
+  const int64_t D = (int64_t)C * S;
+  // from the caller's pageable array, which may be gone once the call returns: HIP stages a pageable source before
+  // hipMemcpyAsync returns (as for the levels and weights of the quantile calls above)
+  HIP_TRY(hipMemcpyAsync(ws + t.feat, features, (size_t)Fs * 4, hipMemcpyHostToDevice, st));
+  PdpFwdParams fp{};
+  fp.net = net; fp.val = (float *)ws; fp.features = (const int32_t *)(ws + t.feat); fp.grid = grid; fp.Fs = Fs; fp.G = G;
+  fp.R = (int)std::min<int64_t>(lds.R, std::max<int64_t>(1, ((int64_t)1 << 30) / Q));   // R * Q stays inside int
+  fp.PR = lds.PR;
+  PdpAccParams ap{};
+  ap.val = (const float *)ws; ap.Q = Q; ap.GP = GP; ap.slices = t.slices; ap.D = D;
+  PdpRowsParams rp{};
+  rp.val = (const float *)ws; rp.Q = Q; rp.GP = GP; rp.Fs = Fs; rp.C = C; rp.S = S;
+  rp.sum = (double *)(ws + t.sum); rp.kept = (int32_t *)(ws + t.kept);
+  rp.c_mean = (double *)(ws + t.chain); rp.c_M2 = rp.c_mean + (size_t)C * Q; rp.c_n = (int32_t *)(rp.c_M2 + (size_t)C * Q);
+  rp.curves = o.curves; rp.pd_mean = o.pd_mean; rp.pd_sd = o.pd_sd; rp.chain_pd = o.chain_pd; rp.chain_draws = (long long *)o.chain_draws;
+  if (o.pd()) HIP_TRY(hipMemsetAsync(ws + t.sum, 0, t.chain - t.sum, st));
+  for (int64_t r0 = 0; r0 < N; r0 += t.Nt) {
+    const int nt = (int)std::min<int64_t>(t.Nt, N - r0);
+    const size_t cols = (size_t)nt * Q;
+    fp.Nt = ap.Nt = rp.Nt = nt;
+    fp.X = X + (size_t)r0 * F;
+    ap.mean = (double *)(ws + t.acc); ap.M2 = ap.mean + (size_t)t.slices * cols; ap.cnt = (int32_t *)(ap.M2 + (size_t)t.slices * cols);
+    ap.o_mean = o.ice_mean ? o.ice_mean + (size_t)r0 * Q : nullptr;
+    ap.o_sd = o.ice_sd ? o.ice_sd + (size_t)r0 * Q : nullptr;
+    ap.dropped = o.dropped ? o.dropped + (size_t)r0 * Fs : nullptr;
+    if (o.ice()) HIP_TRY(hipMemsetAsync(ws + t.acc, 0, pdp_acc_bytes(nt, Q, t.slices), st));
+    for (int64_t d0 = 0; d0 < D; d0 += t.chunk) {
+      const int Sc = (int)std::min<int64_t>(t.chunk, D - d0);
+      fp.theta = theta + (size_t)d0 * net.d;
+      fp.SB = (int)std::max<int64_t>(1, std::min<int64_t>((2 * (int64_t)n_cu + Sc - 1) / Sc, (nt + fp.R - 1) / fp.R));
+      HIP_TRY(mile_launch_pdp_fwd(fp, Sc, st));
+      ap.Sc = rp.Sc = Sc; rp.d0 = d0;
+      if (o.ice()) HIP_TRY(mile_launch_pdp_accum(ap, st));
+      if (o.pd()) HIP_TRY(mile_launch_pdp_rows(rp, st));
+    }
+    if (o.ice()) HIP_TRY(mile_launch_pdp_row_finish(ap, st));
+  }
+  if (o.pd()) HIP_TRY(mile_launch_pdp_finish(rp, st));
+  return MILE_OK;
+}
+
+extern "C" int64_t mile_predict_partial_dependence_workspace(const mile_sampler *s, int32_t C, int64_t S, int64_t N, int32_t Fs, int32_t G) {
+  PdpNet net;
+  if (!s || sens_bad_shape(C, S, N) || pdp_bad_model(s, C, S, Fs, G, &net)) return -1;
+  return (int64_t)pdp_tile_plan(net, eval_view(s).n_cu, C, (int64_t)C * S, N, Fs, G, 0, 0).total;
+}
+
+extern "C" int32_t mile_predict_partial_dependence(mile_sampler *s, const float *theta, int32_t C, int64_t S, const void *X, int64_t N,
+                                                   const int32_t *features, int32_t Fs, const float *grid, int32_t G,
+                                                   int64_t max_draws_per_pass, int64_t max_rows_per_tile, float *ice_mean, float *ice_sd,
+                                                   int32_t *dropped, float *curves, double *pd_mean, double *pd_sd, double *chain_pd,
+                                                   int64_t *chain_draws, void *stream) {
+  const char *fn = "mile_predict_partial_dependence";
+  const PdpOut o{ice_mean, ice_sd, dropped, curves, pd_mean, pd_sd, chain_pd, chain_draws};
+  PdpNet net;
+  const int rc0 = eval_args(fn, s, !theta || !X || !features || !grid, sens_bad_shape(C, S, N), [&]() -> const char * {
+    if (!o.any()) return "no output asked for";
+    if (const char *m = bad_caps(max_draws_per_pass, max_rows_per_tile)) return m;
+    if (const char *m = pdp_bad_model(s, C, S, Fs, G, &net)) return m;
+    std::vector<char> seen((size_t)net.in_features, 0);
+    for (int i = 0; i < Fs; ++i) {
+      if (features[i] < 0 || features[i] >= net.in_features) return "a feature index is out of range (0 .. F - 1)";
+      if (seen[features[i]]++) return "a feature index is repeated";
+    }
+    // no output may lie over theta [C * S, d], X [N, F] or grid [Fs, G]: all are read until the last tile's last pass
+    const size_t Q = (size_t)Fs * G * net.widths[net.n_layers - 1], D = (size_t)C * S;
+    const uintptr_t in[3][2] = {{(uintptr_t)theta, D * net.d * 4}, {(uintptr_t)X, (size_t)N * net.in_features * 4}, {(uintptr_t)grid, (size_t)Fs * G * 4}};
+    const uintptr_t out[8][2] = {{(uintptr_t)ice_mean, (size_t)N * Q * 4}, {(uintptr_t)ice_sd, (size_t)N * Q * 4}, {(uintptr_t)dropped, (size_t)N * Fs * 4},
+                                 {(uintptr_t)curves, D * Q * 4}, {(uintptr_t)pd_mean, Q * 8}, {(uintptr_t)pd_sd, Q * 8},
+                                 {(uintptr_t)chain_pd, (size_t)C * Q * 8}, {(uintptr_t)chain_draws, (size_t)C * Fs * 8}};
+    for (const auto &b : out)
+      for (const auto &a : in)
+        if (b[0] && a[0] < b[0] + b[1] && b[0] < a[0] + a[1]) return "an output overlaps theta, X or grid";
+    return nullptr;
+  });
+  if (rc0 != MILE_OK) return rc0;
+  hipStream_t st = (hipStream_t)stream;
+  const EvalView v = eval_view(s);
+  const PdpTilePlan t = pdp_tile_plan(net, v.n_cu, C, (int64_t)C * S, N, Fs, G, max_rows_per_tile, max_draws_per_pass);
+  char *ws;
+  const int rc1 = stream_ws(fn, s, t.total, "lower max_draws_per_pass or max_rows_per_tile", ws);
+  if (rc1 != MILE_OK) return rc1;
+  return pdp_run(ws, t, net, v.n_cu, theta, C, S, (const float *)X, N, features, Fs, grid, G, o, st);
 }

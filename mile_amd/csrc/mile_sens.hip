@@ -4,6 +4,7 @@
 #include <math.h>
 
 #include "mile_block.h"
+#include "mile_chan.h"
 #include "mile_device.h"
 #include "mile_sens.h"
 
@@ -110,15 +111,6 @@ __global__ __launch_bounds__(SENS_NT) void k_sens_jac(const SensJacParams p) {
   }
 }
 
-// Chan's merge of (nb, mb, M2b) into (na, ma, M2a); nb > 0
-__device__ __forceinline__ void sens_chan(int &na, double &ma, double &M2a, int nb, double mb, double M2b) {
-  if (na == 0) { na = nb; ma = mb; M2a = M2b; return; }
-  const double nt = (double)na + (double)nb, delta = mb - ma;
-  ma += delta * ((double)nb / nt);
-  M2a += M2b + delta * delta * ((double)na * (double)nb / nt);
-  na += nb;
-}
-
 __global__ __launch_bounds__(SENS_NT) void k_sens_accum(const SensAccParams p) {
   const size_t cols = (size_t)p.Nt * p.PF;
   const size_t j = (size_t)blockIdx.x * SENS_NT + threadIdx.x;
@@ -145,7 +137,7 @@ __global__ __launch_bounds__(SENS_NT) void k_sens_accum(const SensAccParams p) {
   const size_t a = (size_t)sl * cols + j;
   int ca = p.cnt[a];
   double ma = p.mean[a], M2a = p.M2[a];
-  sens_chan(ca, ma, M2a, c, mean, M2);
+  chan_merge(ca, ma, M2a, c, mean, M2);
   p.cnt[a] = ca; p.mean[a] = ma; p.M2[a] = M2a; p.pos[a] += pos;
 }
 
@@ -160,7 +152,7 @@ __global__ __launch_bounds__(SENS_NT) void k_sens_finish(const SensAccParams p) 
     const size_t a = (size_t)sl * cols + j;
     const int cb = p.cnt[a];
     if (cb == 0) continue;
-    sens_chan(c, mean, M2, cb, p.mean[a], p.M2[a]);
+    chan_merge(c, mean, M2, cb, p.mean[a], p.M2[a]);
     pos += p.pos[a];
   }
   const float qnan = __int_as_float(0x7fc00000);

@@ -780,6 +780,53 @@ class Engine:
                                                            self._stream()), self.lib)
         return out
 
+    PD_OUTPUTS = ('ice_mean', 'ice_sd', 'dropped', 'curves', 'pd_mean', 'pd_sd', 'chain_pd', 'chain_draws')
+
+    def predict_partial_dependence_workspace(self, C: int, S: int, N: int, Fs: int, G: int) -> int:
+        """Bytes of the handle's workspace ``predict_partial_dependence`` needs for C chains of S draws on N rows, Fs features
+        and G grid points with the library's tile and pass, -1 where the call would be refused
+        (mile_predict_partial_dependence_workspace)."""
+        return int(self.lib.mile_predict_partial_dependence_workspace(self._h, int(C), int(S), int(N), int(Fs), int(G)))
+
+    def predict_partial_dependence(self, samples, x, features, grid, max_draws_per_pass: int = 0, max_rows_per_tile: int = 0,
+                                   want=PD_OUTPUTS) -> dict:
+        """Partial dependence and ICE curves of the ensemble's predictions, reduced on the device
+        (mile_predict_partial_dependence; FCN only): per draw, row, feature ``features[i]`` and grid value ``grid[i][g]`` the head
+        outputs -- mu and log sigma for regression, the class probabilities for classification -- of the row with that input
+        replaced by the grid value, in a HIP kernel that computes the first layer once per (draw, row).  ``samples`` [C, S, d]
+        or [S, d] (one chain), ``x`` [N, F], ``features`` [Fs] distinct indices, ``grid`` [Fs, G].  Returns the tensors named in
+        ``want``, on the device: ``ice_mean``, ``ice_sd`` fp32 [N, Fs, G, P] over the kept draws of all chains (sd with ddof 1),
+        ``dropped`` int32 [N, Fs]; ``curves`` fp32 [C * S, Fs, G, P], each draw's mean over its kept rows; ``pd_mean``, ``pd_sd``
+        fp64 [Fs, G, P] over the draws that have a curve (the posterior band); ``chain_pd`` fp64 [C, Fs, G, P] and
+        ``chain_draws`` int64 [C, Fs].  A (draw, row, feature) with a non-finite value anywhere on the feature's grid is left
+        out.  Rows go in tiles of at most ``max_rows_per_tile``, draws in passes of at most ``max_draws_per_pass`` (0: the
+        library's choice); ``metrics.partial_dependence_dense`` is the same in torch."""
+        samples = _f32(samples, self.device, name='samples')
+        if samples.ndim == 2:
+            samples = samples[None]
+        if samples.ndim != 3 or samples.shape[2] != self.d:
+            raise ValueError(f'samples must be [C, S, {self.d}] or [S, {self.d}]')
+        (C_, S_), theta, x, _ = self._eval_inputs(samples, x, name_x='x')
+        feats = [int(f) for f in features]
+        grid = _f32(grid, self.device, name='grid')
+        if grid.ndim != 2 or grid.shape[0] != len(feats) or grid.shape[1] < 1:
+            raise ValueError('grid must be [Fs, G] with one row per feature')
+        grid = grid.contiguous()
+        unknown = [k for k in want if k not in self.PD_OUTPUTS]
+        if unknown or not want:
+            raise ValueError(f'want: some of {self.PD_OUTPUTS}')
+        N, Fs, G, P = int(x.shape[0]), len(feats), int(grid.shape[1]), int(self.spec.hidden_structure[-1])
+        new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=self.device)
+        shapes = {'ice_mean': (torch.float32, N, Fs, G, P), 'ice_sd': (torch.float32, N, Fs, G, P), 'dropped': (torch.int32, N, Fs),
+                  'curves': (torch.float32, C_ * S_, Fs, G, P), 'pd_mean': (torch.float64, Fs, G, P), 'pd_sd': (torch.float64, Fs, G, P),
+                  'chain_pd': (torch.float64, C_, Fs, G, P), 'chain_draws': (torch.int64, C_, Fs)}
+        out = {k: new(*shapes[k]) for k in self.PD_OUTPUTS if k in want}
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mile_predict_partial_dependence(self._h, _ptr(theta), C_, S_, _ptr(x), N, (C.c_int32 * Fs)(*feats), Fs,
+                                                                _ptr(grid), G, int(max_draws_per_pass), int(max_rows_per_tile),
+                                                                *[_ptr(out.get(k)) for k in self.PD_OUTPUTS], self._stream()), self.lib)
+        return out
+
     def debug_quantile_sweeps(self):
         """(rows, total sweeps, most sweeps of a row) of the solver in the last ``predict_quantiles`` (test and tool hook)."""
         rows, total, most = C.c_int64(), C.c_int64(), C.c_int32()

@@ -2115,3 +2115,178 @@ def sensitivity_summary(result: dict, feature_names=None) -> dict:
         res['feature_names'] = [str(n) for n in feature_names]
         res['ranked_names'] = [[str(feature_names[i]) for i in r] for r in ranking]
     return res
+
+
+# ---- partial dependence and ICE curves of the ensemble's predictions: the grid, the torch restatement of
+# mile_predict_partial_dependence (Engine.predict_partial_dependence) in fp64 on substituted tables -- the tests' and the timing
+# tool's yardstick, and the fallback on the CPU and where the library refuses -- and what the curves say.
+
+PD_OUTPUTS = ('ice_mean', 'ice_sd', 'dropped', 'curves', 'pd_mean', 'pd_sd', 'chain_pd', 'chain_draws')
+
+
+def pd_grid(x, features, G: int, kind: str = 'quantile', lo: float = 0.05, hi: float = 0.95) -> torch.Tensor:
+    """The grid [Fs, G] fp32 of ``features`` from the columns of the table x [N, F] itself: ``kind='quantile'`` the quantiles
+    (linear interpolation) at G equally spaced levels from ``lo`` to ``hi``, so that every grid value lies where the data do;
+    ``kind='linspace'`` G equally spaced values from the ``lo`` to the ``hi`` quantile.  G = 1: the (lo + hi) / 2 quantile.
+    Non-finite entries of a column are left out.  On x's device for a tensor, on the host otherwise."""
+    import numpy as np
+    if kind not in ('quantile', 'linspace'):
+        raise ValueError("kind: 'quantile' or 'linspace'")
+    if G < 1 or not 0.0 <= lo <= hi <= 1.0:
+        raise ValueError('G >= 1 and 0 <= lo <= hi <= 1 are needed')
+    device = x.device if isinstance(x, torch.Tensor) else 'cpu'
+    a = (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)).astype(np.float64)
+    if a.ndim != 2:
+        raise ValueError('x must be [N, F]')
+    levels = np.linspace(lo, hi, G) if G > 1 else np.array([0.5 * (lo + hi)])
+    rows = []
+    for f in features:
+        if not 0 <= int(f) < a.shape[1]:
+            raise ValueError(f'feature {f} out of range (0 .. {a.shape[1] - 1})')
+        col = a[:, int(f)]
+        col = col[np.isfinite(col)]
+        if not len(col):
+            raise ValueError(f'feature {f} has no finite value')
+        if kind == 'quantile':
+            rows.append(np.quantile(col, levels))
+        else:
+            a0, a1 = np.quantile(col, [lo, hi])
+            rows.append(np.linspace(a0, a1, G) if G > 1 else np.quantile(col, levels))
+    return torch.from_numpy(np.asarray(rows, dtype=np.float64).reshape(len(rows), G).astype(np.float32)).to(device)
+
+
+def _fcn_raw(spec: ModelSpec, theta: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
+    """theta [M, d], X [N, F] -> the raw outputs [M, N, O] of the FCN in theta's dtype."""
+    leaves = {n: (o, s) for n, o, s in spec.leaves()}
+    nl = len(spec.hidden_structure)
+    act = {'relu': torch.relu, 'tanh': torch.tanh, 'sigmoid': torch.sigmoid}[spec.activation]
+    h = X.to(theta.device, theta.dtype)[None].expand(theta.shape[0], -1, -1)
+    for li in range(nl):
+        ko, ks = leaves[f'{spec.root}.layer{li}.kernel']
+        bo, bs = leaves[f'{spec.root}.layer{li}.bias']
+        h = torch.baddbmm(theta[:, bo:bo + bs[0]][:, None, :], h, theta[:, ko:ko + ks[0] * ks[1]].reshape(-1, *ks))
+        if li < nl - 1:
+            h = act(h)
+    return h
+
+
+def partial_dependence_dense(engine_or_forward, samples, x, features, grid, batch: int = 0) -> dict:
+    """Partial dependence and ICE curves of ``samples`` [C, S, d] (or [S, d]: one chain) on x [N, F] as the composition a user
+    writes today: for every feature and grid value a copy of the table with the column replaced, forwarded, and the head
+    outputs [C * S, N, G, P] of a feature reduced in torch fp64 -- the dict of ``Engine.predict_partial_dependence``.  The forward
+    is ``engine_or_forward.predict`` for an Engine (fp32, on the device), the fp64 torch FCN for a ``ModelSpec`` (any device: the
+    fallback), or a callable (theta [M, d], X [N, F]) -> raw [M, N, O] with ``task`` 'regr' assumed unless it has a ``task``
+    attribute.  ``batch`` draws are forwarded at a time (0: 256 for the fp64 torch FCN, all of them otherwise).  The drop rule is per (draw, row, feature): kept iff all G * P values
+    are finite; note that substitution, unlike the library's update z_0 + (v - x_f) W_0[f], takes a non-finite x_f out of the row."""
+    if isinstance(engine_or_forward, ModelSpec):
+        spec = engine_or_forward
+        task, dtype = spec.task, torch.float64
+        forward = lambda th, X: _fcn_raw(spec, th, X)
+    elif hasattr(engine_or_forward, 'predict'):
+        task, dtype = engine_or_forward.spec.task, torch.float32
+        forward = engine_or_forward.predict
+    else:
+        task, dtype = getattr(engine_or_forward, 'task', 'regr'), torch.float32
+        forward = engine_or_forward
+    samples = torch.as_tensor(samples)
+    if samples.ndim == 2:
+        samples = samples[None]
+    if samples.ndim != 3:
+        raise ValueError('samples must be [C, S, d] or [S, d]')
+    C, S, d = samples.shape
+    th = samples.reshape(C * S, d).to(dtype)
+    x = torch.as_tensor(x).to(th.device, dtype)
+    grid = torch.as_tensor(grid).to(th.device, torch.float32)
+    feats = [int(f) for f in features]
+    if x.ndim != 2 or grid.ndim != 2 or grid.shape[0] != len(feats) or len(set(feats)) != len(feats) or not feats:
+        raise ValueError('x must be [N, F], grid [Fs, G] with one row per distinct feature')
+    if min(feats) < 0 or max(feats) >= x.shape[1]:
+        raise ValueError('a feature index is out of range')
+    M, N, G = C * S, x.shape[0], grid.shape[1]
+    batch = int(batch) if batch > 0 else 256 if isinstance(engine_or_forward, ModelSpec) else M
+    regr = task in ('regr', 'regression')
+    res = {k: [] for k in PD_OUTPUTS}
+    nan = float('nan')
+    for i, f in enumerate(feats):
+        cols = []
+        for g in range(G):
+            xs = x.clone()
+            xs[:, f] = grid[i, g].to(dtype)
+            raw = torch.cat([forward(th[b0:b0 + batch], xs) for b0 in range(0, M, batch)]).to(torch.float64)
+            cols.append(raw if regr else torch.softmax(raw, dim=-1))
+        h = torch.stack(cols, dim=2)                                             # [M, N, G, P]
+        ok = torch.isfinite(h).all(dim=-1).all(dim=-1)                           # [M, N]
+        w = ok.to(torch.float64)[..., None, None]
+        h = torch.where(ok[..., None, None], h, torch.zeros_like(h))
+        k = ok.sum(dim=0).to(torch.float64)[:, None, None]                       # kept draws per row
+        mean = h.sum(dim=0) / k.clamp(min=1)
+        dd = (h - mean) * w
+        sd = torch.where(k > 1, torch.sqrt((dd * dd).sum(dim=0) / (k - 1).clamp(min=1)), torch.zeros_like(mean))
+        some = (k > 0).expand_as(mean)
+        res['ice_mean'].append(torch.where(some, mean, torch.full_like(mean, nan)).to(torch.float32))
+        res['ice_sd'].append(torch.where(some, sd, torch.full_like(sd, nan)).to(torch.float32))
+        res['dropped'].append((M - ok.sum(dim=0)).to(torch.int32))
+        kr = ok.sum(dim=1)                                                       # kept rows per draw
+        m = h.sum(dim=1) / kr.to(torch.float64).clamp(min=1)[:, None, None]      # [M, G, P]: the fp64 row means
+        have = kr > 0
+        res['curves'].append(torch.where(have[:, None, None], m, torch.full_like(m, nan)).to(torch.float32))
+
+        def band(mm):
+            n = mm.shape[0]
+            if n == 0:
+                return torch.full_like(m[0], nan), torch.full_like(m[0], nan)
+            return mm.mean(dim=0), (mm.std(dim=0, unbiased=True) if n > 1 else torch.zeros_like(m[0]))
+
+        pm, ps = band(m[have])
+        res['pd_mean'].append(pm)
+        res['pd_sd'].append(ps)
+        res['chain_pd'].append(torch.stack([band(m[c * S:(c + 1) * S][have[c * S:(c + 1) * S]])[0] for c in range(C)]))
+        res['chain_draws'].append(have.reshape(C, S).sum(dim=1).to(torch.int64))
+    stack_at = {'ice_mean': 1, 'ice_sd': 1, 'dropped': 1, 'curves': 1, 'pd_mean': 0, 'pd_sd': 0, 'chain_pd': 1, 'chain_draws': 1}
+    return {k: torch.stack(v, dim=stack_at[k]) for k, v in res.items()}
+
+
+def partial_dependence_summary(res: dict, grid) -> dict:
+    """What the curves say per selected feature i and head column p, on the host in fp64, from the dict of
+    ``Engine.predict_partial_dependence`` / ``partial_dependence_dense`` and the grid [Fs, G]; every entry [Fs][P]:
+    ``importance``, the sd (ddof 1, 0 for G = 1) of ``pd_mean`` over the grid (Greenwell et al. 2018); ``span``, its max - min;
+    ``slope``, its least-squares slope on the grid values (0 for a constant grid); ``band``, the mean over the grid of ``pd_sd``,
+    the posterior's uncertainty about the curve; ``chain_sd``, the sd over the chains (ddof 1, 0 for one chain; chains without a
+    curve left out) of ``chain_pd``, averaged over the grid, and ``chain_ratio`` = chain_sd / band -- chains that hold different
+    functions show a ratio near or above 1; ``ice_heterogeneity``, the sd over the rows (ddof 1) of the ICE curves each centred at
+    its own mean over the grid, averaged over the grid: 0 for an additive effect, > 0 where the effect of the feature depends on
+    the other inputs, which first-order sensitivities cannot show.  Rows with nothing kept are left out."""
+    import numpy as np
+    a = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in res.items()}
+    g = (grid.detach().cpu().numpy() if isinstance(grid, torch.Tensor) else np.asarray(grid)).astype(np.float64)
+    pm, ps = a['pd_mean'].astype(np.float64), a['pd_sd'].astype(np.float64)
+    Fs, G, P = pm.shape
+    if g.shape != (Fs, G):
+        raise ValueError(f'grid must be [{Fs}, {G}]')
+    with np.errstate(all='ignore'):
+        gc = g - g.mean(axis=1, keepdims=True)
+        den = (gc * gc).sum(axis=1)[:, None]
+        slope = np.where(den > 0, (gc[:, :, None] * (pm - pm.mean(axis=1, keepdims=True))).sum(axis=1) / np.where(den > 0, den, 1.0), 0.0)
+        band = ps.mean(axis=1)
+        out = {'importance': pm.std(axis=1, ddof=1) if G > 1 else np.zeros((Fs, P)), 'span': pm.max(axis=1) - pm.min(axis=1),
+               'slope': slope, 'band': band}
+        if 'chain_pd' in a:
+            cp = a['chain_pd'].astype(np.float64)
+            cp = cp[np.isfinite(cp).all(axis=(1, 2, 3))]
+            csd = cp.std(axis=0, ddof=1).mean(axis=1) if len(cp) > 1 else np.zeros((Fs, P)) if len(cp) else np.full((Fs, P), np.nan)
+            out['chain_sd'] = csd
+            out['chain_ratio'] = np.where(band > 0, csd / np.where(band > 0, band, 1.0), np.nan)      # no band: no ratio
+            out['n_chains'] = int(len(cp))
+        if 'ice_mean' in a:
+            ice = a['ice_mean'].astype(np.float64)
+            het = np.full((Fs, P), np.nan)
+            for i in range(Fs):
+                rows = ice[:, i][np.isfinite(ice[:, i]).all(axis=(1, 2))]                     # [n, G, P]
+                if len(rows) > 1:
+                    het[i] = (rows - rows.mean(axis=1, keepdims=True)).std(axis=0, ddof=1).mean(axis=0)
+                elif len(rows) == 1:
+                    het[i] = 0.0
+            out['ice_heterogeneity'] = het
+    # JSON has no NaN or inf: an entry that is not finite (nothing kept, no band) is None
+    clean = lambda v: [clean(e) for e in v] if isinstance(v, list) else (v if math.isfinite(v) else None)
+    return {k: (clean(v.tolist()) if isinstance(v, np.ndarray) else v) for k, v in out.items()}

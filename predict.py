@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Posterior-predictive moments of a finished experiment on NEW inputs (the consumer of mile_predict_moments):
 
-    python predict.py -e results/mile_amd/<experiment> -i <table or .npz> [-o predictions.npz] [--draws-per-pass K] [--intervals C [C ...]] [--sets C [C ...]] [--weights PATH|stacking] [--sensitivities]
+    python predict.py -e results/mile_amd/<experiment> -i <table or .npz> [-o predictions.npz] [--draws-per-pass K] [--intervals C [C ...]] [--sets C [C ...]] [--weights PATH|stacking] [--sensitivities] [--partial-dependence G]
 
 Reloads config.yaml and the samples the way evaluate.py does, applies the training normalisation the loader recorded
 (normalization.npz, written by train.py) to the rows of the table, reduces all C x S draws on the device and writes, per row:
@@ -24,6 +24,12 @@ Reloads config.yaml and the samples the way evaluate.py does, applies the traini
                      d output_p / d x_f and the share of draws where it is positive; p = (mu, log sigma) for regression, the
                      class probabilities for classification.  In the table's units: d mu / d x_f is multiplied by y_std / x_std_f,
                      d log sigma / d x_f and d pi_k / d x_f are divided by x_std_f (--normalized keeps the network's units)
+    --partial-dependence G  FCN experiments: the partial dependence and ICE curves of the equal-weight ensemble on the rows of the
+                     table (mile_predict_partial_dependence), every feature over G values at the 5 % - 95 % quantiles of its own
+                     column: pd_grid [F, G]; pd_ice_mean, pd_ice_sd [N, F, G, P], over the draws the mean and the sd of the
+                     prediction of the row with feature f set to the grid value; pd_dropped [N, F]; pd_mean, pd_sd [F, G, P], the
+                     partial dependence and its posterior band.  In the table's units: the grid in x's, mu in target units,
+                     log sigma shifted by log y_std (--normalized keeps the network's units)
 
 The table holds one row per input and the model's features as columns (no target column): .npy, .csv (comma), .data / .txt
 (whitespace), or an .npz with an array ``x`` (images [N, C, H, W], token ids [N, T]).  Where the target was z-scored
@@ -133,6 +139,23 @@ def sensitivity_arrays(res: dict, norm: dict, task: str) -> dict:
             'sens_dropped': res['dropped'].cpu().numpy()}
 
 
+def partial_dependence_arrays(res: dict, grid, norm: dict, task: str) -> dict:
+    """pd_grid [F, G], pd_ice_mean, pd_ice_sd [N, F, G, P], pd_dropped [N, F] and pd_mean, pd_sd [F, G, P] of
+    Engine.predict_partial_dependence, in the units of the table where the loader normalised: the grid value v' the network sees
+    is (v - x_mean_f) / x_std_f; for a z-scored target mu = mu' y_std + y_mean and log sigma = log sigma' + log y_std, so the mean
+    curves are scaled and shifted and the sd of mu is scaled by y_std; class probabilities stay.  Formed in fp64."""
+    g = grid.double().cpu().numpy()
+    a = {k: res[k].double().cpu().numpy() for k in ('ice_mean', 'ice_sd', 'pd_mean', 'pd_sd')}
+    if 'x_std' in norm:
+        g = g * np.asarray(norm['x_std'], dtype=np.float64).reshape(-1, 1) + np.asarray(norm['x_mean'], dtype=np.float64).reshape(-1, 1)
+    if task == 'regr' and 'y_std' in norm:
+        ys, ym = float(norm['y_std'].reshape(-1)[0]), float(norm['y_mean'].reshape(-1)[0])
+        scale, shift = np.array([ys, 1.0]), np.array([ym, np.log(ys)])
+        a = {k: v * scale + (shift if k.endswith('mean') else 0.0) for k, v in a.items()}
+    return {'pd_grid': g.astype(np.float32), 'pd_ice_mean': a['ice_mean'].astype(np.float32), 'pd_ice_sd': a['ice_sd'].astype(np.float32),
+            'pd_dropped': res['dropped'].cpu().numpy(), 'pd_mean': a['pd_mean'], 'pd_sd': a['pd_sd']}
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description='posterior-predictive moments of an experiment on a table of new inputs')
     ap.add_argument('--exp', '-e', required=True, help='experiment directory (holds config.yaml and samples/)')
@@ -153,6 +176,11 @@ def build_parser():
     ap.add_argument('--sensitivities', action='store_true',
                     help='FCN experiments: also the input sensitivities of the ensemble on every row (mile_predict_sensitivities): '
                          'sens_mean, sens_sd, sens_pos [N, P, F] and sens_dropped [N], in the units of the table unless --normalized')
+    ap.add_argument('--partial-dependence', type=int, default=None, metavar='G',
+                    help='FCN experiments: also the partial dependence and ICE curves of the ensemble on the rows of the table '
+                         '(mile_predict_partial_dependence), every feature over G grid values at the 5 %% - 95 %% quantiles of its own '
+                         'column: pd_grid [F, G], pd_ice_mean, pd_ice_sd [N, F, G, P], pd_dropped [N, F] and pd_mean, pd_sd [F, G, P], '
+                         'in the units of the table (mu in target units, log sigma shifted by log y_std) unless --normalized')
     ap.add_argument('--normalized', action='store_true',
                     help='the rows already are in the training normalisation; the outputs stay in it')
     ap.add_argument('--drop-nonfinite', action='store_true', help='leave out chains with non-finite samples, as evaluate.py does')
@@ -179,6 +207,12 @@ def main():
         from mile_amd.spec import ModelSpec
         if not isinstance(spec, ModelSpec):
             raise SystemExit('--sensitivities: input sensitivities are for FCN (tabular) experiments; token ids and image pixels are out of scope')
+    if args.partial_dependence is not None:
+        from mile_amd.spec import ModelSpec
+        if not isinstance(spec, ModelSpec):
+            raise SystemExit('--partial-dependence: partial dependence is for FCN (tabular) experiments; token ids and image pixels are out of scope')
+        if not 1 <= args.partial_dependence <= 256:
+            raise SystemExit('--partial-dependence: G must be in 1 .. 256')
     samples = load_samples_from_dir(exp / cfg.training.sampler._dir_name, spec)       # [C, S, d]
     bad_chains = ~np.isfinite(samples).all(axis=(1, 2))
     if args.drop_nonfinite and bad_chains.any() and not bad_chains.all():
@@ -233,6 +267,13 @@ def main():
     if args.sensitivities:
         res = eng.predict_sensitivities(torch.from_numpy(samples), torch.from_numpy(x), max_draws_per_pass=args.draws_per_pass)
         arrays.update(sensitivity_arrays(res, norm, cfg.data.task))
+    if args.partial_dependence is not None:
+        from mile_amd.metrics import pd_grid
+        feats = list(range(spec.in_features))
+        grid = pd_grid(x, feats, args.partial_dependence)                  # of the rows as the network sees them
+        res = eng.predict_partial_dependence(torch.from_numpy(samples), torch.from_numpy(x), feats, grid, max_draws_per_pass=args.draws_per_pass,
+                                             want=('ice_mean', 'ice_sd', 'dropped', 'pd_mean', 'pd_sd'))
+        arrays.update(partial_dependence_arrays(res, grid, norm, cfg.data.task))
     out = Path(args.output) if args.output else exp / 'predictions.npz'
     np.savez(out, **arrays)
     print(f'{out}: {len(x)} rows, {samples.shape[0] * samples.shape[1]} draws, {int(arrays["dropped"].sum())} dropped; '
